@@ -38,6 +38,11 @@ Extra objects on the line:
                 against the CPU oracle on a few of the timed clips: max |err| / logit scale against the bar of the parity
                 tests (fp32 / split-bf16: rtol 1e-3 + 1e-5 of the scale, the fp32 oracle; bf16: 1e-2 of the scale and
                 the same arg-max, the bf16-storage oracle).  A failed check makes the run fail, not just the line.
+
+--dump-outputs DIR (rank 0) writes what each timed mode's LAST timed step returned -- the float32 logits a caller of the
+step receives, [B, 12] (with a collective: the all-gathered [world * B, 12]) -- as DIR/logits.npy (headline),
+DIR/alt_precision_logits.npy and DIR/config5_logits.npy, named after the objects of the line.  Weights and clips are
+seeded, so the same arguments give the same inputs on every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -146,6 +151,21 @@ def cpu_baseline(sd_np, t, h, w, budget_s=15.0):
 
 
 PARITY_CLIPS = 3     # clips of the timed batch held against the oracle (first, middle, last)
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: float32 array} -> out_dir/<name>.npy.  Past DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded
+    sample of its rows (in order) so that the dump stays under the limit and stays comparable between runs."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def oracle_logits(sd_np, clips_cpu, t, dtypes):
@@ -271,7 +291,11 @@ def main():
                     help='BASELINE.json configuration of the HEADLINE fields: 2 = the defaults (configs[1], what the metric is '
                          'quoted on; a configs[4] leg follows as the `config5` object); 5 = T=16, 256x256, 64 clips per GPU, '
                          'TSM_DTYPE_BF16 as the headline itself (sets --dtype/--batch/--segments/--size, no alt / config5 / CPU legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the logits of the last timed step of every timed mode to DIR/<name>.npy (float32, rank 0)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.config == 5:
         args.dtype, args.batch, args.segments, args.size = 'bf16', 64, 16, 256
         args.no_alt = args.no_cpu_baseline = args.no_config5 = True
@@ -397,6 +421,8 @@ def main():
         res = {'dtype': dtype, 'geom': geom}
         # the timed steps' own output, kept for the parity check below (a [world * B, 12] gather starts with this rank's rows)
         res['timed_logits'] = out[:B][parity_idx].detach().float().cpu().numpy()
+        if args.dump_outputs:
+            res['last_out'] = out.detach().float().cpu().numpy()     # everything the last timed step returned
         # Per-launch durations of the timed forwards (events were recorded inside the timed region; reading
         # them here keeps the host syncs out of it).
         res['per_launch'] = [eng.layer_times_ms(i) for i in range(n_timed)] if want_launch_times else []
@@ -609,6 +635,13 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(sd, T, H, W)
         print(json.dumps(line), flush=True)
+        if args.dump_outputs:
+            dumped = {'logits': main_res['last_out']}
+            if alt_res is not None:
+                dumped['alt_precision_logits'] = alt_res['last_out']
+            if c5_res is not None:
+                dumped['config5_logits'] = c5_res['last_out']
+            dump_outputs(args.dump_outputs, dumped)
         bad = [d for d, q in parity.items() if not q['ok']]
         if c5_parity is not None and not c5_parity['ok']:
             bad.append('config5/bf16')

@@ -1,5 +1,5 @@
 /*
- * tsm_hip.h -- C ABI of libtsm_hip.so: TSM-ResNet50 clip inference on MI355X (gfx950).
+ * tsm_hip.h -- C ABI of libtsm_hip.so: TSM-ResNet50 (and ResNet-18 / 34) clip inference on MI355X (gfx950).
  *
  * The reference (iucario/WorkoutDetector) has no FFI of its own: the hot path sits behind a
  * Python duck type.  Each entry point below names the reference interface it replaces:
@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -136,8 +136,16 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out);
 void tsm_destroy(tsm_engine *e);
 const char *tsm_last_error(const tsm_engine *e);
 
+/* Backbone of the engine: torchvision's resnet18 / resnet34 (BasicBlock: two 3x3 convs, the temporal shift fused into
+ * the first, fc [num_class, 512]) or resnet50 (Bottleneck, fc [num_class, 2048]) -- create_model(base_model=...),
+ * workoutdetector/models/tsm.py:264-281.  Legal between tsm_create and the first tsm_set_tensor; a later call returns
+ * TSM_ERR_INVALID_ARG, a depth other than 18, 34 or 50 TSM_ERR_UNSUPPORTED.  An engine that never calls it is R50.
+ * State-dict keys of a BasicBlock: "base_model.layerL.B.conv1.net.weight" (or ".conv1.weight"), ".bn1.*",
+ * ".conv2.weight", ".bn2.*", ".downsample.0.weight", ".downsample.1.*". */
+int tsm_set_backbone(tsm_engine *e, int32_t depth);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
- * BN vectors [C], fc [num_class, 2048]).  Names are the reference's TSM.state_dict() keys, e.g.
+ * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;
  * the caller keeps ownership.  Unknown names return TSM_ERR_INVALID_ARG. */
 int tsm_set_tensor(tsm_engine *e, const char *name, const float *host_data, const int64_t *shape,
@@ -165,7 +173,8 @@ int tsm_tune(tsm_engine *e, int32_t n_clips, void *stream);
 /* Same as tsm_forward but stops after `stage` and returns that activation (NHWC fp32) in
  * `out` (capacity in floats); shape [N*T, H, W, C] written to out_shape[4].
  * Stages: "input" (packed NHWC4), "conv1" (stem conv+bn+relu), "stem" (after maxpool),
- * "layer{1..4}.{b}" (block output), "layer{L}.{b}.conv1|conv2" (branch intermediates). */
+ * "layer{1..4}.{b}" (block output), "layer{L}.{b}.conv1|conv2" (branch intermediates; a BasicBlock has
+ * "layer{L}.{b}.conv1" only, its conv2 output is the block output). */
 int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout,
                     int32_t n_clips, const char *stage, float *out, int64_t out_capacity,
                     int64_t out_shape[4], void *stream);
@@ -180,12 +189,13 @@ float tsm_last_forward_ms(tsm_engine *e);
  * inside a timed region below 0.5 %; launches without a pair report -1.  tsm_layer_times
  * synchronises on forward `forward_index` (0-based since the last tsm_set_layer_timing) and writes
  * one duration in ms per launch, in launch order: pack_input, conv1 (stem), maxpool, then per block
- * [downsample,] conv1, conv2, conv3, then head (pool + fc).  *n_out = number of launches. */
+ * [downsample,] conv1, conv2, conv3 (BasicBlock: [downsample,] conv1, conv2), then head (pool + fc).
+ * *n_out = number of launches. */
 int tsm_set_layer_timing(tsm_engine *e, int32_t n_forwards, int32_t only_conv3x3);
 int tsm_layer_times(tsm_engine *e, int32_t forward_index, float *ms_out, int32_t cap, int32_t *n_out);
 
 /* Conv tile code the engine's autotuner chose for each conv launch of an `n_clips` forward, in launch order (stem,
- * then per block [downsample,] conv1, conv2, conv3): 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 32x32 (one wave),
+ * then per block [downsample,] conv1, conv2, conv3 -- BasicBlock: [downsample,] conv1, conv2): 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 32x32 (one wave),
  * 5 = 128x128 on 8 waves, 6 = 256x256 LDS-DMA kernel (bf16), 7 = weight-stationary 3x3 (bf16, 64 -> 64 / 128 -> 128
  * channels), 8 = the 256x256 kernel run persistently over a workgroup's tiles (bf16, K >= 128), 0 = not tuned (heuristic); + 256 = split-K form of a segmented fp32 layer (one workgroup per tile and K
  * segment, combined in segment order); + 1024 (on conv2's code) = the block runs conv2 + conv3 + residual as ONE launch
@@ -209,7 +219,8 @@ int tsm_temporal_shift(const float *x, float *y, int64_t n_frames, int32_t n_seg
 /* y = act( conv(x, w) * bn_scale + bn_bias [+ residual] ), NHWC.
  * x [n,hi,wi,cin]; w OIHW [cout,cin,k,k] (device, raw); gamma/beta/mean/var [cout] (device);
  * k in {1,3,7}; pad = k/2; residual (nullable) and y [n,ho,wo,cout].
- * shift_segments > 0 applies the temporal shift (fold_div) to x on the fly (k == 1, stride 1).
+ * shift_segments > 0 applies the temporal shift (fold_div) to x on the fly: k == 1 at stride 1, or k == 3 at stride 1 or
+ * 2 (the shift is fused into the conv's loader either way; not combined with a residual).
  * dtype: any tsm_dtype (x / residual / y stay fp32 NHWC at this boundary and are converted to and from
  * the storage format of that dtype around the kernel).
  * Packs the weights on every call: a test/debug entry point, not the fast path.  It has no engine, so it is the one

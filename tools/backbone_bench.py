@@ -1,0 +1,102 @@
+"""Clip throughput of the TSM backbones (R18 / R34 / R50) side by side on one GPU: one JSON line per (backbone, dtype).
+
+    python tools/backbone_bench.py [--backbones resnet18,resnet34,resnet50] [--dtypes f32,bf16] [--batch 32]
+                                   [--segments 8] [--size 224] [--steps 20] [--warmup 5]
+
+Each engine gets the seeded synthetic weights of its backbone (weights.make_state_dict(0, 12, base_model)) and one
+device-resident seeded batch [B, T, 3, S, S]; ``warmup()`` tunes the batch's bucket first (never timed), then W untimed
+and K timed forwards run back to back on torch's current stream, one event per step boundary.  Fields:
+
+  ms_per_step      median of the K per-step event durations
+  clips_per_s      batch / ms_per_step
+  gflop_per_step   algorithmic forward work (workoutdetector_amd.flops, 2 FLOPs per MAC; shift / BN / pooling count 0)
+  peak_frac        achieved FLOP/s over the exact-fp32 MFMA peak (f32) or the dense bf16 MFMA peak (bf16, bf16x3): a
+                   whole-forward figure, not a kernel's share of peak
+  logits_err       max |logits - CPU restatement| / max |CPU restatement| on the first two clips of the last timed step:
+                   fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py for R50,
+                   tests/_basicblock_ref.py for R18 / R34)
+
+No CPU fallback: without a GPU it fails.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md, "Peak FP32 (matrix)"
+PEAK_BF16_MFMA_TFLOPS = 2500.0   # MI355X_MICROARCH.md, "Peak BF16/FP16 MFMA", dense
+
+
+def reference_logits(base_model, sd, clips, t, dtype):
+    import torch
+    from oracle import tsm_oracle
+    from tests import _basicblock_ref
+    sd_t = {k: torch.from_numpy(v) for k, v in sd.items()}
+    bf16 = dtype == 'bf16'
+    if base_model == 'resnet50':
+        fwd = tsm_oracle.tsm_forward_bf16 if bf16 else tsm_oracle.tsm_forward
+        return fwd(sd_t, clips, n_segment=t).numpy()
+    return _basicblock_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()
+
+
+def run_one(args, base_model, dtype):
+    import numpy as np
+    import torch
+    from workoutdetector_amd.engine import TsmEngine
+    from workoutdetector_amd.flops import flops_per_clip
+    from workoutdetector_amd.weights import make_state_dict
+    b, t, s = args.batch, args.segments, args.size
+    sd = make_state_dict(0, 12, base_model=base_model)
+    eng = TsmEngine(num_class=12, num_segments=t, height=s, width=s, max_clips=b, state_dict=sd, dtype=dtype,
+                    base_model=base_model)
+    gen = torch.Generator(device='cuda').manual_seed(0)
+    clips = torch.randn(b, t, 3, s, s, device='cuda', generator=gen)
+    logits = torch.empty(b, 12, device='cuda')
+    eng.warmup([b])
+    for _ in range(args.warmup):
+        eng.forward_device(clips, out=logits)
+    torch.cuda.synchronize()
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    marks[0].record()
+    for i in range(args.steps):
+        eng.forward_device(clips, out=logits)
+        marks[i + 1].record()
+    torch.cuda.synchronize()
+    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    ms = step_ms[len(step_ms) // 2]
+    got = logits[:2].cpu().numpy()
+    eng.close()
+    want = reference_logits(base_model, sd, clips[:2].cpu(), t, dtype)
+    gflop = flops_per_clip(t, s, s, 12, base_model=base_model) * b / 1e9
+    peak = PEAK_F32_MFMA_TFLOPS if dtype == 'f32' else PEAK_BF16_MFMA_TFLOPS
+    return {'backbone': base_model, 'dtype': dtype, 'batch': b, 'segments': t, 'size': s,
+            'ms_per_step': round(ms, 3), 'ms_min': round(step_ms[0], 3), 'ms_max': round(step_ms[-1], 3),
+            'clips_per_s': round(b / (ms / 1e3), 1), 'gflop_per_step': round(gflop, 1),
+            'tflops': round(gflop / ms, 2), 'peak_tflops': peak, 'peak_frac': round(gflop / ms / peak, 4),
+            'logits_err': float(np.abs(got - want).max() / np.abs(want).max()), 'steps': args.steps}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--backbones', default='resnet18,resnet34,resnet50')
+    ap.add_argument('--dtypes', default='f32,bf16')
+    ap.add_argument('--batch', type=int, default=32)
+    ap.add_argument('--segments', type=int, default=8)
+    ap.add_argument('--size', type=int, default=224)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit('backbone_bench.py needs a GPU')
+    for dtype in args.dtypes.split(','):
+        for base_model in args.backbones.split(','):
+            print(json.dumps(run_one(args, base_model, dtype)), flush=True)
+
+
+if __name__ == '__main__':
+    main()

@@ -1,12 +1,13 @@
-// Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet50 clip forward on MI355X.
+// Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet clip forward on MI355X (ResNet-50 by default; ResNet-18 / 34
+// through tsm_set_backbone).
 //
 // Owns: packed weights (BatchNorm folded, K-major), an NHWC fp32 activation workspace sized for
 // max_clips, one HIP stream, two timing events.  The forward is a fixed schedule of kernel launches
 // (csrc/tsm_*.hip, one file per kernel family: tsm_device.h lists them); nothing here falls back to a CPU path.
 //
 // Reference behaviour mirrored: workoutdetector/models/tsm.py:409-419 (TSM.forward), :125-137
-// (shift in front of every Bottleneck.conv1), :451-473 (state-dict naming); torchvision-0.13
-// ResNet-50 v1.5 (stride on conv2, BN eps 1e-5).
+// (shift in front of every block's conv1), :451-473 (state-dict naming); torchvision-0.13
+// ResNet-50 v1.5 (stride on conv2, BN eps 1e-5) and ResNet-18 / 34 (BasicBlock: stride on conv1).
 #include <hip/hip_runtime.h>
 
 #include <sys/stat.h>
@@ -37,8 +38,21 @@ using namespace tsm_host;
 // the tree it sits in (mtimes do not survive a copy to another machine).
 const char kBuildTag[] = "tsm-build-id:" TSM_BUILD_ID;
 
-constexpr int kBlocks[4] = {3, 4, 6, 3};
+// Backbones by depth: blocks per stage and the block type.  Planes are 64, 128, 256, 512 for all of them; a Bottleneck widens
+// its output by 4, a BasicBlock by 1 (torchvision resnet18 / resnet34 / resnet50).
+struct Backbone {
+  int depth;
+  int blocks[4];
+  bool basic;
+};
+constexpr Backbone kBackbones[] = {{18, {2, 2, 2, 2}, true}, {34, {3, 4, 6, 3}, true}, {50, {3, 4, 6, 3}, false}};
 constexpr int kPlanes[4] = {64, 128, 256, 512};
+
+const Backbone *find_backbone(int depth) {
+  for (const Backbone &b : kBackbones)
+    if (b.depth == depth) return &b;
+  return nullptr;
+}
 
 // Message of the last failure of an engine-less entry point (tsm_create, the per-op functions): per calling thread, so
 // two threads driving two engines never write the same string (include/tsm_hip.h, "no global state").
@@ -59,8 +73,11 @@ struct ConvLayer {
 };
 
 struct Block {
-  int conv1, conv2, conv3, down;  // indices into convs, down = -1 if none
+  // indices into convs, down = -1 if none.  A Bottleneck has conv1 (1x1, shifted), conv2 (3x3, strided), conv3 (1x1,
+  // + identity); a BasicBlock has conv1 (3x3, shifted, strided) and conv2 (3x3, + identity), conv3 = -1.
+  int conv1, conv2, conv3, down;
   int stride;
+  std::string name;  // "layerL.B"
   // conv3 + downsample as ONE GEMM over K = [conv3 input channels | block input channels]
   float *d_wf = nullptr, *d_bf = nullptr;
   int kpf = 0;
@@ -82,6 +99,10 @@ int ilog2(int v) {
 
 struct tsm_engine {
   tsm_config cfg{};
+  int depth = 50;             // tsm_set_backbone
+  int feat = 2048;            // channels of the last stage = the classifier's input width
+  bool weights_started = false;   // a tsm_set_tensor call has been made: the backbone is fixed
+  size_t tune_sig_base = 0;   // length of tune_sig before the backbone suffix
   std::string err;
   hipStream_t stream = nullptr;
   bool finalized = false;
@@ -160,14 +181,38 @@ void build_topology(tsm_engine *e) {
   // fp32: K = 49 taps x 4 channels; bf16 formats: K = 7 rows x 4 pixel pairs x 8 (fold_and_pack_stem_pairs)
   stem.kp = e->prec == tsm::kPrecF32 ? round_up(7 * 7 * 4, 32) : round_up(7 * 4 * 8, e->prec == tsm::kPrecBf16 ? 64 : 32);
   e->convs.push_back(stem);
+  const Backbone &bb = *find_backbone(e->depth);
+  const int expansion = bb.basic ? 1 : 4;
   int cin = 64;
   for (int li = 0; li < 4; ++li) {
-    for (int b = 0; b < kBlocks[li]; ++b) {
+    for (int b = 0; b < bb.blocks[li]; ++b) {
       const int planes = kPlanes[li];
       const int stride = (b == 0 && li > 0) ? 2 : 1;
       const std::string p = "base_model.layer" + std::to_string(li + 1) + "." + std::to_string(b);
       Block blk;
       blk.stride = stride;
+      blk.name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+      blk.down = -1;
+      if (bb.basic) {
+        // conv1: 3x3 at the block's stride, the temporal shift fused into its loader (no segmented form: kseg = 0);
+        // conv2: 3x3, + identity.  Downsample (1x1 at the stride) where the width or the size changes.
+        ConvLayer c1; c1.wkey = p + ".conv1.net.weight"; c1.bnp = p + ".bn1";
+        c1.cin = cin; c1.cout = planes; c1.k = 3; c1.stride = stride; c1.cp = cin; c1.kp = 9 * cin;
+        ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
+        c2.cin = planes; c2.cout = planes; c2.k = 3; c2.stride = 1; c2.cp = planes; c2.kp = 9 * planes;
+        c1.kseg = e->cfg.is_shift ? 0 : segment_len(c1.kp, e->prec);
+        blk.conv1 = (int)e->convs.size(); e->convs.push_back(c1);
+        blk.conv2 = (int)e->convs.size(); e->convs.push_back(c2);
+        blk.conv3 = -1;
+        if (stride != 1 || cin != planes) {
+          ConvLayer d; d.wkey = p + ".downsample.0.weight"; d.bnp = p + ".downsample.1";
+          d.cin = cin; d.cout = planes; d.k = 1; d.stride = stride; d.cp = cin; d.kp = cin;
+          blk.down = (int)e->convs.size(); e->convs.push_back(d);
+        }
+        e->blocks.push_back(blk);
+        cin = planes;
+        continue;
+      }
       ConvLayer c1; c1.wkey = p + ".conv1.net.weight"; c1.bnp = p + ".bn1";
       c1.cin = cin; c1.cout = planes; c1.k = 1; c1.stride = 1; c1.cp = cin; c1.kp = cin;
       ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
@@ -179,7 +224,6 @@ void build_topology(tsm_engine *e) {
       blk.conv1 = (int)e->convs.size(); e->convs.push_back(c1);
       blk.conv2 = (int)e->convs.size(); e->convs.push_back(c2);
       blk.conv3 = (int)e->convs.size(); e->convs.push_back(c3);
-      blk.down = -1;
       if (b == 0) {
         ConvLayer d; d.wkey = p + ".downsample.0.weight"; d.bnp = p + ".downsample.1";
         d.cin = cin; d.cout = planes * 4; d.k = 1; d.stride = stride; d.cp = cin; d.kp = cin;
@@ -189,6 +233,7 @@ void build_topology(tsm_engine *e) {
       cin = planes * 4;
     }
   }
+  e->feat = kPlanes[3] * expansion;
 }
 
 const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
@@ -495,9 +540,6 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     if (want("stem")) return hit(cur, n, e->hp, e->wp, 64);
   }
   int h = e->hp, w = e->wp;
-  std::vector<std::string> block_names;
-  for (int li = 0; li < 4; ++li)
-    for (int bi = 0; bi < kBlocks[li]; ++bi) block_names.push_back("layer" + std::to_string(li + 1) + "." + std::to_string(bi));
   bool tapped = false;
   // conv3 of block k and shift + conv1 of block k + 1 as ONE launch (bf16: tsm::launch_conv31_fused): `t1_ready` says that
   // the previous block's conv3 launch has already left this block's conv1 output in t1; `prev3` keeps the previous block's
@@ -516,10 +558,35 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     q.fold = shiftT > 0 ? c1n.cp / cfg.shift_div : 0;
     return q;
   };
+  // One BasicBlock on nn frames: x -> y through t1 (and idb for the downsample), three generic launches:
+  //   [downsample (1x1 at the stride, its own launch),] shift + conv1 (3x3 at the stride, shift fused into its loader,
+  //   + ReLU), conv2 (3x3 + identity + ReLU).  None of the Bottleneck fusions applies.
+  auto run_basic = [&](size_t k, int nn, float *x, float *y, int hh, int ww) -> int {
+    const Block &blk = e->blocks[k];
+    const std::string &name = blk.name;
+    const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2];
+    const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+    const float *identity = x;
+    if (blk.down >= 0) {
+      tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, 0, 1, prec);
+      int rcd = conv(blk.down, pd, 1, false);
+      if (rcd) return rcd;
+      identity = idb;
+    }
+    tsm::ConvParams p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, cfg.shift_div, prec);
+    int rc1 = conv(blk.conv1, p1, 3, true);
+    if (rc1) return rc1;
+    if (want(name + ".conv1")) { tapped = true; return hit(t1, nn, ho, wo, c1.cout); }
+    tsm::ConvParams p2 = make_params(c2, t1, identity, y, nn, ho, wo, true, 0, 1, prec);
+    int rc2 = conv(blk.conv2, p2, 3, true);
+    if (rc2) return rc2;
+    if (want(name)) { tapped = true; return hit(y, nn, ho, wo, c2.cout); }
+    return TSM_OK;
+  };
   // One Bottleneck on nn frames: x -> y through the branch temporaries t1, t2 (and idb for an un-fused downsample).
   auto run_block = [&](size_t k, int nn, float *x, float *y, int hh, int ww) -> int {
     const Block &blk = e->blocks[k];
-    const std::string &name = block_names[k];
+    const std::string &name = blk.name;
     const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
     const bool have_t1 = t1_ready;
     t1_ready = false;
@@ -683,7 +750,8 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     // bit 0x1000 of conv3's tile code
     // (set by the tuning pass at the head of the next block), or forced / forbidden through TSM_FUSE_C3C1
     bool did31 = false;
-    if (prec == tsm::kPrecBf16 && !fused && blk.down < 0 && k + 1 < e->blocks.size() && e->fuse31 != 0) {
+    if (prec == tsm::kPrecBf16 && !fused && blk.down < 0 && k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0 &&
+        e->fuse31 != 0) {
       const ConvLayer &c1n = e->convs[e->blocks[k + 1].conv1];
       tsm::Conv31Params q = make_p31(p3, c1n, t1, nn, ho * wo);
       if (tsm::conv31_valid(q)) {
@@ -763,14 +831,14 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     return TSM_OK;
   };
   for (size_t k = 0; k < e->blocks.size(); ++k) {
-    int rc = run_block(k, n, cur, out, h, w);
+    int rc = e->blocks[k].conv3 < 0 ? run_basic(k, n, cur, out, h, w) : run_block(k, n, cur, out, h, w);
     if (rc || tapped) return rc;
     std::swap(cur, out);
     h = (h + 2 - 3) / e->blocks[k].stride + 1;
     w = (w + 2 - 3) / e->blocks[k].stride + 1;
   }
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
-  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T, h * w, 2048,
+  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T, h * w, e->feat,
                                     cfg.num_class, prec, s));
   return TSM_OK;
 }
@@ -922,8 +990,23 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
                   std::to_string(cfg->is_shift ? cfg->shift_div : 0) + " fuse" + std::to_string(e->fuse_down ? 1 : 0) + "/" + std::to_string(e->fuse23) + "/" + std::to_string(e->fuse_block) + "/" + std::to_string(e->fuse31) + "/" + std::to_string(e->fuse_front) +
                   " zz" + std::to_string(e->zigzag ? 1 : 0) + " tk" + std::to_string(e->tail_split ? 1 : 0) + " stem" + std::to_string(e->stem_direct ? 1 : 0) +
                   std::to_string(e->stem_pool ? 1 : 0) + std::to_string(e->stem_planar ? 1 : 0);
+    e->tune_sig_base = e->tune_sig.size();   // (tsm_set_backbone appends " r<depth>" for a backbone other than R50)
   }
   *out = e;
+  return TSM_OK;
+}
+
+int tsm_set_backbone(tsm_engine *e, int32_t depth) {
+  if (!e) return TSM_ERR_INVALID_ARG;
+  if (e->weights_started || e->finalized)
+    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_backbone must come before the first tsm_set_tensor");
+  if (!find_backbone(depth)) return fail(e, TSM_ERR_UNSUPPORTED, "depth must be 18, 34 or 50");
+  e->depth = depth;
+  build_topology(e);
+  if (!e->tune_sig.empty()) {   // tuned codes of one backbone are never read by another
+    e->tune_sig.resize(e->tune_sig_base);
+    if (depth != 50) e->tune_sig += " r" + std::to_string(depth);
+  }
   return TSM_OK;
 }
 
@@ -948,6 +1031,7 @@ int tsm_set_tensor(tsm_engine *e, const char *name, const float *host_data, cons
   if (!name || !host_data || !shape || ndim < 1 || ndim > 4) return fail(e, TSM_ERR_INVALID_ARG, "bad tensor args");
   if (e->finalized) return fail(e, TSM_ERR_INVALID_ARG, "engine already finalized");
   const std::string key(name);
+  e->weights_started = true;
   if (!known_name(e, key)) return fail(e, TSM_ERR_INVALID_ARG, "unknown tensor name: " + key);
   HostTensor t;
   size_t elems = 1;
@@ -1000,7 +1084,7 @@ int tsm_finalize(tsm_engine *e) {
   }
   // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
   for (Block &blk : e->blocks) {
-    if (blk.down < 0 || !e->fuse_down) continue;
+    if (blk.down < 0 || !e->fuse_down || blk.conv3 < 0) continue;   // (Bottlenecks only)
     const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
     blk.kpf = c3.kp + cd.kp;
     blk.ksegf = segment_len(blk.kpf, e->prec);
@@ -1022,6 +1106,7 @@ int tsm_finalize(tsm_engine *e) {
   // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide: conv3's weights once more, in the
   // fragment order of the fused conv2 + conv3 kernel (fp32 and split-bf16 engines).
   for (Block &blk : e->blocks) {
+    if (blk.conv3 < 0) continue;   // (Bottlenecks only)
     const ConvLayer &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
     if (blk.down >= 0 || blk.stride != 1 || (c2.cout != 64 && c2.cout != 128)) continue;
     if (e->prec == tsm::kPrecBf16) {   // weight-stationary form: 64 mid channels only; it reads conv3's packed matrix itself
@@ -1041,8 +1126,8 @@ int tsm_finalize(tsm_engine *e) {
   host_bias.clear();
   const HostTensor *fw = find_tensor(e, "fc.weight"), *fb = find_tensor(e, "fc.bias");
   if (!fw || !fb) return fail(e, TSM_ERR_MISSING_TENSOR, "missing fc.weight / fc.bias");
-  if (fw->shape != std::vector<int64_t>{cfg.num_class, 2048} || fb->shape != std::vector<int64_t>{cfg.num_class})
-    return fail(e, TSM_ERR_SHAPE, "fc shape mismatch (want [num_class, 2048])");
+  if (fw->shape != std::vector<int64_t>{cfg.num_class, e->feat} || fb->shape != std::vector<int64_t>{cfg.num_class})
+    return fail(e, TSM_ERR_SHAPE, "fc shape mismatch (want [num_class, " + std::to_string(e->feat) + "])");
   int rc = dev_alloc(e, &e->d_fcw, fw->data.size());
   if (rc) return rc;
   rc = dev_alloc(e, &e->d_fcb, fb->data.size());
@@ -1050,16 +1135,29 @@ int tsm_finalize(tsm_engine *e) {
   TSM_HIP(e, hipMemcpy(e->d_fcw, fw->data.data(), fw->data.size() * sizeof(float), hipMemcpyHostToDevice));
   TSM_HIP(e, hipMemcpy(e->d_fcb, fb->data.data(), fb->data.size() * sizeof(float), hipMemcpyHostToDevice));
 
-  // Workspace: the largest activation is the stem conv output (== layer1 output), per frame
-  // h1*w1*64 floats; five rotating buffers (block in/out, two branch temporaries, identity).
+  // Workspace: five rotating buffers (block in/out, two branch temporaries, identity), each the largest activation of the
+  // topology per frame: the stem conv output or a conv output of some block (R50: layer1's 256 channels).
   e->h1 = (cfg.height + 6 - 7) / 2 + 1;
   e->w1 = (cfg.width + 6 - 7) / 2 + 1;
   e->hp = (e->h1 + 2 - 3) / 2 + 1;
   e->wp = (e->w1 + 2 - 3) / 2 + 1;
   const size_t frames = (size_t)cfg.max_clips * cfg.num_segments;
   size_t per_frame = (size_t)e->h1 * e->w1 * 64;
-  const size_t l1 = (size_t)e->hp * e->wp * 256;
-  if (l1 > per_frame) per_frame = l1;
+  {
+    int hh = e->hp, ww = e->wp;
+    for (const Block &blk : e->blocks) {
+      const size_t in_px = (size_t)hh * ww;
+      hh = (hh + 2 - 3) / blk.stride + 1;
+      ww = (ww + 2 - 3) / blk.stride + 1;
+      const size_t out_px = (size_t)hh * ww;
+      for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down}) {
+        if (ci < 0) continue;
+        // (a Bottleneck's conv1 runs at the block input's size, every other conv at the block output's)
+        const bool at_input = blk.conv3 >= 0 && ci == blk.conv1;
+        per_frame = std::max(per_frame, (at_input ? in_px : out_px) * (size_t)e->convs[ci].cout);
+      }
+    }
+  }
   e->buf_elems = frames * per_frame;
   for (int i = 0; i < 5; ++i) {
     rc = dev_alloc(e, &e->buf[i], e->buf_elems);
@@ -1069,7 +1167,7 @@ int tsm_finalize(tsm_engine *e) {
   if (rc) return rc;
   rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1));  // 16 bytes per pixel in every format (pairs: odd widths padded)
   if (rc) return rc;
-  rc = dev_alloc(e, &e->d_pooled, frames * 2048);
+  rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat);
   if (rc) return rc;
   rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * cfg.num_class);
   if (rc) return rc;
@@ -1220,13 +1318,13 @@ int tsm_layer_times(tsm_engine *e, int32_t forward_index, float *ms_out, int32_t
 
 int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t cap, int32_t *n_out) {
   if (!e || !tiles_out || !n_out) return TSM_ERR_INVALID_ARG;
-  // launch order: stem, then per block [downsample,] conv1, conv2, conv3
+  // launch order: stem, then per block [downsample,] conv1, conv2, conv3 (Bottleneck) / [downsample,] conv1, conv2 (BasicBlock)
   std::vector<int> order{0};
   for (const Block &b : e->blocks) {
     if (b.down >= 0) order.push_back(b.down);
     order.push_back(b.conv1);
     order.push_back(b.conv2);
-    order.push_back(b.conv3);
+    if (b.conv3 >= 0) order.push_back(b.conv3);
   }
   *n_out = (int32_t)order.size();
   if ((int)order.size() > cap) return fail(e, TSM_ERR_CAPACITY, "tiles_out too small");
@@ -1239,6 +1337,10 @@ int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t c
     size_t i = 1;
     for (const Block &b : e->blocks) {
       if (b.down >= 0) ++i;
+      if (b.conv3 < 0) {   // BasicBlock: no fused forms
+        i += 2;
+        continue;
+      }
       if ((tiles_out[i] & 0x800) || (tiles_out[i + 1] & 0x400)) tiles_out[i + 2] &= ~0x1000;
       i += 3;
     }

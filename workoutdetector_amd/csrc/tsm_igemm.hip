@@ -1,7 +1,7 @@
 // Hand-written CDNA4 (gfx950) kernels for the TSM-ResNet50 clip forward.
 //
 //   conv_igemm       implicit-GEMM convolution (1x1 / 3x3 / 7x7, stride 1|2), NHWC activations, LDS-staged A
-//                    (im2col rows built on the fly, temporal shift fused into the loader) and B (packed
+//                    (im2col rows built on the fly, temporal shift fused into the 1x1 and 3x3 loaders) and B (packed
 //                    weights), epilogue = folded-BN bias + residual + ReLU.  Template axes: tile shape and wave
 //                    layout (128x128 on 4 or 8 waves, 128x64, 64x64, 32x32 on one wave), KS, SHIFT (fused
 //                    temporal shift), RES (residual prefetched under the K loop), PREC (exact-fp32 MFMA /
@@ -65,7 +65,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
   constexpr bool BF = PREC == kPrecBf16;   // plain bf16 storage, one bf16 MFMA per product (config 5)
   constexpr int EB = BF ? 2 : 4;           // bytes per stored element
   constexpr int KC = 128 / EB;             // channels per K-step (an LDS row is always 128 bytes)
-  static_assert(!SHIFT || KS == 1, "the temporal shift is fused into 1x1 convs only");
+  // (a shifted 3x3 holds two more offsets per pass; its segmented form is not built: ConvParams::kseg_len must be 0)
+  static_assert(!SHIFT || KS == 1 || (KS == 3 && !SEG), "the temporal shift is fused into 1x1 and unsegmented 3x3 convs only");
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int TM = WTM / 32, TN = WTN / 32;
   constexpr int APASS = BM / LRP, BPASS = BN / LRP;
@@ -176,7 +177,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
         a_mask[pp] = ok ? mask : 0u;
       }
       if (SHIFT) {
-        const int t = n % p.T;  // channels [0,fold) <- frame t+1, [fold,2fold) <- frame t-1
+        // channels [0,fold) <- frame t+1, [fold,2fold) <- frame t-1 (3x3: the same frame offset for every tap; the
+        // tap's padding mask above still applies, a frame past the clip end reads zeros through kInvalid)
+        const int t = n % p.T;
         a_offp[pp] = (ok && t < p.T - 1) ? (unsigned)(base + frame_bytes) : kInvalid;
         a_offm[pp] = (ok && t > 0) ? (unsigned)(base - frame_bytes) : kInvalid;
       }
@@ -204,24 +207,26 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
     KStep k;
     k.kbytes = (unsigned)kt * (kBK * 4);
     k.dead = (~(unsigned)((kt - nk_) >> 31)) & kInvalid;
+    k.tap = 0;
+    k.tap_off = 0;
+    int c0 = kt * KC;  // first input channel of this K-step
+    if (KS == 3) {  // C >= 32 so a K-step never straddles a tap: tap and its offset are scalars
+      k.tap = (kt * KC) >> (p.logC4 + 2);
+      c0 = kt * KC - k.tap * p.C;
+      const int ky = k.tap / 3, kx = k.tap - ky * 3;
+      k.tap_off = ((ky * p.Wi + kx) * p.C + c0) * EB;
+    }
     k.mp = k.mm = 0u;
     k.m0 = ~0u;
     if (SHIFT) {
       // channels [0,fold) <- frame t+1, [fold,2fold) <- frame t-1, rest <- frame t.  Kept as AND/OR
       // masks: a three-way select over the per-row offset arrays is turned into a scratch-memory
-      // table by the compiler, which serialises the loader behind vmcnt(0).
-      const int c = kt * KC + (X3 ? (chunk >> 1) * 8 : (BF ? chunk * 8 : chunk * 4));
+      // table by the compiler, which serialises the loader behind vmcnt(0).  fold % 4 (fp32) / % 8 (bf16
+      // formats) keeps a 16-B chunk inside one group; a 3x3 K-step is (tap, channels c0 ..), same choice per tap.
+      const int c = c0 + (X3 ? (chunk >> 1) * 8 : (BF ? chunk * 8 : chunk * 4));
       k.mp = 0u - (unsigned)(c < p.fold);
       k.mm = (0u - (unsigned)(c < 2 * p.fold)) & ~k.mp;
       k.m0 = ~(k.mp | k.mm);
-    }
-    k.tap = 0;
-    k.tap_off = 0;
-    if (KS == 3) {  // C >= 32 so a K-step never straddles a tap: tap and its offset are scalars
-      k.tap = (kt * KC) >> (p.logC4 + 2);
-      const int c0 = kt * KC - k.tap * p.C;
-      const int ky = k.tap / 3, kx = k.tap - ky * 3;
-      k.tap_off = ((ky * p.Wi + kx) * p.C + c0) * EB;
     }
     return k;
   };
@@ -240,7 +245,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
           ra[pp] = buf_load4(rsrcA, off | k.dead, k.kbytes);
         }
       } else if (KS == 3) {
-        ra[pp] = buf_load4(rsrcA, (((a_mask[pp] >> k.tap) & 1u) ? a_off[pp] + (unsigned)k.tap_off : kInvalid) | k.dead, 0);
+        if (SHIFT) {
+          // source frame of this chunk, then the tap; a zero frame (clip end) stays kInvalid instead of being offset
+          const unsigned off = (a_offp[pp] & k.mp) | (a_offm[pp] & k.mm) | (a_off[pp] & k.m0);
+          const bool ok = ((a_mask[pp] >> k.tap) & 1u) && off != kInvalid;
+          ra[pp] = buf_load4(rsrcA, (ok ? off + (unsigned)k.tap_off : kInvalid) | k.dead, 0);
+        } else {
+          ra[pp] = buf_load4(rsrcA, (((a_mask[pp] >> k.tap) & 1u) ? a_off[pp] + (unsigned)k.tap_off : kInvalid) | k.dead, 0);
+        }
       } else {
         if constexpr (PAIRS) {
           // bf16-format stem: K = (ky, pair j, pixel-in-pair, c4) = 7 x 4 x 8 = 224; one 8-element group
@@ -727,7 +739,7 @@ static hipError_t launch_conv_seg(ConvParams p, hipStream_t s) {
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT, bool RES>
 static hipError_t launch_conv_t(ConvParams p, hipStream_t s) {
   if (p.kseg_len > 0) {
-    if constexpr (!RES && KS != 7) return launch_conv_seg<BM, BN, WGM, WGN, KS, SHIFT>(p, s);
+    if constexpr (!RES && KS != 7 && !(SHIFT && KS == 3)) return launch_conv_seg<BM, BN, WGM, WGN, KS, SHIFT>(p, s);
     else return hipErrorInvalidValue;
   }
   p.ntm = (p.M + BM - 1) / BM;
@@ -783,11 +795,12 @@ bool conv_tile_valid(const ConvParams &p, int tile) {
     case kTile64x64: return p.Cout % 64 == 0;
     case kTile32x32: return p.Cout % 32 == 0 && p.prec == kPrecF32;  // single-wave tiles: fp32 only
     case kTile128x128w8: return p.Cout % 128 == 0;
-    case kTile256x256:   // (ks is checked at launch: the stem has C == 4 and never qualifies)
-      return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.C % 64 == 0 && !(p.res && p.x2) &&
+    case kTile256x256:   // (ks is checked at launch: the stem has C == 4 and never qualifies; a 3x3 (pad 1) only unshifted, no residual)
+      return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.C % 64 == 0 && !(p.res && p.x2) && (p.pad != 1 || (!p.res && p.T == 0)) &&
              (!p.x2 || (p.K1 % 64 == 0 && p.C2 % 64 == 0));
     case kTile256x256p:   // (ks is checked at launch; at least two K-tiles, the bias of all channels in LDS)
       return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.Cout <= 2048 && p.C % 64 == 0 && p.Kp >= 128 && !(p.res && p.x2) &&
+             (p.pad != 1 || (!p.res && p.T == 0)) &&
              (!p.x2 || (p.K1 % 64 == 0 && p.C2 % 64 == 0));
     case kTileWs: return conv3x3_ws_valid(p) || conv3x3_ws128_valid(p) || conv1x1_ws_valid(p) || conv1x1_wsn_valid(p);   // (pad singles out 3x3 / 1x1)
     default: return false;
@@ -843,7 +856,10 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
   if (p.Cout % 64 != 0 || p.Kp % kc != 0 || p.M <= 0) return hipErrorInvalidValue;
   if ((1 << p.logC4) * 4 != p.C) return hipErrorInvalidValue;
   if (ks != 7 && p.C % kc != 0) return hipErrorInvalidValue;
-  if (p.T > 0 && (ks != 1 || p.stride != 1 || p.N % p.T != 0 || p.fold % 4 != 0)) return hipErrorInvalidValue;
+  // temporal shift: 1x1 at stride 1 (Bottleneck.conv1), 3x3 at stride 1 or 2 (BasicBlock.conv1; unsegmented only)
+  if (p.T > 0 && ((ks != 1 && ks != 3) || (ks == 1 && p.stride != 1) || (ks == 3 && p.kseg_len > 0) || p.N % p.T != 0 ||
+                  p.fold % 4 != 0))
+    return hipErrorInvalidValue;
   if (p.x2 && (ks != 1 || p.T > 0 || p.res || p.K1 % kc != 0 || p.C2 % kc != 0 || p.K1 + p.C2 != p.Kp || p.K1 != p.C))
     return hipErrorInvalidValue;
   if (p.prec != kPrecF32 && p.prec != kPrecBf16x3 && p.prec != kPrecBf16) return hipErrorInvalidValue;
@@ -860,7 +876,9 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
     case 1:
       if (p.res) return p.T > 0 ? hipErrorInvalidValue : launch_conv_ks<1, false, true>(p, s);
       return p.T > 0 ? launch_conv_ks<1, true, false>(p, s) : launch_conv_ks<1, false, false>(p, s);
-    case 3: return p.res ? hipErrorInvalidValue : launch_conv_ks<3, false, false>(p, s);
+    case 3:
+      if (p.res) return p.T > 0 ? hipErrorInvalidValue : launch_conv_ks<3, false, true>(p, s);
+      return p.T > 0 ? launch_conv_ks<3, true, false>(p, s) : launch_conv_ks<3, false, false>(p, s);
     case 7: return p.res ? hipErrorInvalidValue : launch_conv_ks<7, false, false>(p, s);
     default: return hipErrorInvalidValue;
   }

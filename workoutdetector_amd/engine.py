@@ -1,4 +1,4 @@
-"""TsmEngine: Python host side of the MI355X TSM-R50 clip-inference engine.
+"""TsmEngine: Python host side of the MI355X TSM-ResNet clip-inference engine (R50; R18 / R34 via ``base_model``).
 
 Drop-in for the two duck types the reference's hot path is written against:
 
@@ -22,7 +22,8 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys, remap_mmaction_keys
+from .weights import (BACKBONES, DEPTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
+                      remap_mmaction_keys)
 
 
 @dataclass
@@ -43,7 +44,10 @@ class TsmEngine:
 
     def __init__(self, num_class: int = 12, num_segments: int = 8, height: int = 224, width: int = 224,
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
-                 state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32'):
+                 state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
+                 base_model: str = 'resnet50'):
+        if base_model not in DEPTHS:
+            raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.num_class, self.num_segments = int(num_class), int(num_segments)
@@ -52,12 +56,15 @@ class TsmEngine:
         if dtype not in _lib.DTYPES:
             raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
         self.dtype = dtype
+        self.base_model = base_model
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
                               'bf16': _lib.LAYOUT_NTHWC8B}[dtype]
         cfg = _lib.TsmConfig(C.sizeof(_lib.TsmConfig), num_class, num_segments, height, width, shift_div,
                              1 if is_shift else 0, max_clips, device, _lib.DTYPES[dtype])
         _lib.check(self._lib.tsm_create(C.byref(cfg), C.byref(self._h)))
+        if base_model != 'resnet50':
+            _lib.check(self._lib.tsm_set_backbone(self._h, DEPTHS[base_model]), self._h)
         self._finalized = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -219,10 +226,14 @@ class TsmEngine:
     def launch_names(self) -> List[str]:
         """Names of the kernel launches of one forward, in launch order (matches tsm_layer_times)."""
         names = ['pack_input', 'conv1', 'maxpool']
-        for li, nb in enumerate((3, 4, 6, 3), start=1):
+        blocks, kind = BACKBONES[self.base_model]
+        for li, nb in enumerate(blocks, start=1):
             for b in range(nb):
                 p = f'layer{li}.{b}'
-                names += ([p + '.downsample'] if b == 0 else []) + [p + '.conv1', p + '.conv2', p + '.conv3']
+                if kind == 'basic':   # [downsample,] conv1 (shift fused), conv2 (+ identity)
+                    names += ([p + '.downsample'] if b == 0 and li > 1 else []) + [p + '.conv1', p + '.conv2']
+                else:
+                    names += ([p + '.downsample'] if b == 0 else []) + [p + '.conv1', p + '.conv2', p + '.conv3']
         return names + ['head']
 
     TILE_NAMES = {0: 'heuristic', 1: '128x128', 2: '128x64', 3: '64x64', 4: '32x32', 5: '128x128w8', 6: '256x256', 7: 'ws',
@@ -296,9 +307,11 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     ``onnx_import.load_onnx_state_dict``.
     Without a checkpoint the reference starts from torchvision's ImageNet weights, which cannot be
     fetched offline: the engine then gets the seeded synthetic weights of ``weights.make_state_dict``.
+    ``base_model``: 'resnet50' (Bottleneck), 'resnet18' or 'resnet34' (BasicBlock: the shift fused into the 3x3 conv1,
+    fc [num_class, 512]); any other backbone raises NotImplementedError.
     """
-    if base_model != 'resnet50':
-        raise NotImplementedError(f'{base_model}: the engine implements resnet50 only')
+    if base_model not in DEPTHS:
+        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     assert consensus_type in ('avg',), 'the engine implements the avg consensus'
     assert shift_place == 'blockres', 'the engine implements blockres placement'
     if non_local:
@@ -311,18 +324,19 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         dev = int(s.split(':')[1]) if ':' in s else 0
     if checkpoint is not None and str(checkpoint).endswith('.onnx'):
         from .onnx_import import load_onnx_state_dict        # the reference's deployed artefact
-        sd = load_onnx_state_dict(checkpoint, num_class)
+        sd = load_onnx_state_dict(checkpoint, num_class, base_model)
     elif checkpoint is not None:
         import torch
         ckpt = torch.load(checkpoint, map_location='cpu')
         raw = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
         # mmaction2 checkpoints (the reference's --mmlab branch) vs the reference's own TSM / Lightning ones
-        sd = remap_mmaction_keys(raw) if is_mmaction_state_dict(raw) else remap_checkpoint_keys(raw, num_class)
+        sd = (remap_mmaction_keys(raw) if is_mmaction_state_dict(raw)
+              else remap_checkpoint_keys(raw, num_class, base_model))
     else:
-        sd = make_state_dict(seed=seed, num_class=num_class)
+        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width,
                      shift_div=shift_div, is_shift=is_shift, max_clips=max_clips, device=dev, state_dict=sd,
-                     dtype=dtype)
+                     dtype=dtype, base_model=base_model)
 
 
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------

@@ -1,4 +1,4 @@
-"""Weights from an exported ``.onnx`` TSM model -> engine state dict, without the ``onnx`` package.
+"""Weights from an exported ``.onnx`` TSM model (R50, R18 or R34) -> engine state dict, without the ``onnx`` package.
 
 The reference deploys ``checkpoints/*.onnx`` produced by ``torch.onnx.export(model, sample[1,8,3,224,224],
 opset_version=11)`` (workoutdetector/scripts/export_model.py:35-47, trainer.py:325-330) and runs it with
@@ -13,8 +13,12 @@ fields needed) and maps the tensors onto the engine's ``TSM.state_dict()`` keys:
     ``onnx::Conv_###`` weight + bias initialisers): every Conv node is identified by CONNECTIVITY, not by its
     position in the file -- the number of Conv nodes upstream of it in the dataflow graph fixes its place in the
     network (conv1 and downsample of a block see the same upstream set, conv2 one more, conv3 two more; the two
-    1x1 convs that share a count always differ in output channels), the weight shape must agree, and anything
-    ambiguous or missing raises -- and every conv gets an identity BatchNorm carrying its bias.
+    1x1 convs that share a count always differ in output channels; in a BasicBlock conv1 is a 3x3 and the downsample
+    a 1x1), the weight shape must agree, and anything ambiguous or missing raises -- and every conv gets an identity
+    BatchNorm carrying its bias.
+
+The backbone is read from the graph: 53 Conv nodes and a 2048-wide classifier are R50, 20 / 36 Conv nodes, no
+``conv3`` and a 512-wide classifier are R18 / R34.
 
 Tested on files written by torch's own exporter (``torch.onnx.export(..., opset_version=11)`` of an nn.Module with
 the reference's module tree, both export styles; tests/_torch_tsm.py) and on hand-written files
@@ -24,11 +28,11 @@ from __future__ import annotations
 
 import struct
 from collections import OrderedDict
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .weights import conv_specs
+from .weights import DEPTHS, conv_specs, feature_width
 
 BN_EPS = 1e-5
 
@@ -147,7 +151,7 @@ def _resolve_convs(path: str, nodes: List[dict], inits: Dict[str, np.ndarray], s
     """The Conv node of every entry of ``conv_specs()``, found by dataflow position + weight shape."""
     convs = [i for i, n in enumerate(nodes) if n['op_type'] == 'Conv']
     if len(convs) != len(specs):
-        raise ValueError(f'{path}: {len(convs)} Conv nodes, a TSM-ResNet50 has {len(specs)}')
+        raise ValueError(f'{path}: {len(convs)} Conv nodes, the TSM-ResNet has {len(specs)}')
     bit = {ni: 1 << k for k, ni in enumerate(convs)}
     upstream: Dict[str, int] = {}          # tensor name -> bitmask of the Conv nodes it depends on
     depth: Dict[int, int] = {}
@@ -176,7 +180,7 @@ def _resolve_convs(path: str, nodes: List[dict], inits: Dict[str, np.ndarray], s
         cands = by_key.get((want, (cout, cin, k, k)), [])
         if len(cands) != 1:
             raise ValueError(f'{path}: {len(cands)} Conv nodes with {want} upstream convs and weight {(cout, cin, k, k)} '
-                             f'for {wkey}; cannot map the graph onto TSM-ResNet50')
+                             f'for {wkey}; cannot map the graph onto the TSM-ResNet')
         out.append(nodes[cands[0]])
         nxt = specs[idx + 1][0] if idx + 1 < len(specs) else ''
         if idx == 0 or (nxt.endswith('.conv1.net.weight') or nxt == ''):
@@ -184,10 +188,28 @@ def _resolve_convs(path: str, nodes: List[dict], inits: Dict[str, np.ndarray], s
     return out
 
 
-def load_onnx_state_dict(path: str, num_class: int) -> 'OrderedDict[str, np.ndarray]':
-    """Engine state dict (``TsmEngine.load_state_dict``) from a TSM-R50 ``.onnx`` export."""
+def detect_backbone(inits: Dict[str, np.ndarray], nodes: List[dict]) -> str:
+    """'resnet18' | 'resnet34' | 'resnet50' from the graph: the Conv node count (20 / 36 / 53 -- the stem, two or three
+    convs per block, the downsample convs), checked against the state-dict names where the export kept them."""
+    n_conv = sum(n['op_type'] == 'Conv' for n in nodes)
+    by_count = {len(conv_specs(m)): m for m in DEPTHS}
+    if n_conv not in by_count:
+        raise ValueError(f'{n_conv} Conv nodes: not a TSM-ResNet18 / 34 / 50 ({sorted(by_count)})')
+    model = by_count[n_conv]
+    if model != 'resnet50' and any('.conv3.' in k for k in inits):   # (a folded export has anonymous names: counts only)
+        raise ValueError(f'{n_conv} Conv nodes ({model}) but the initialisers hold conv3 weights')
+    return model
+
+
+def load_onnx_state_dict(path: str, num_class: int, base_model: Optional[str] = None) -> 'OrderedDict[str, np.ndarray]':
+    """Engine state dict (``TsmEngine.load_state_dict``) from a TSM-R50 / R18 / R34 ``.onnx`` export.  The backbone is
+    recognised from the graph (``detect_backbone``); a ``base_model`` that disagrees with it raises."""
     inits, nodes = parse_onnx(path)
-    specs = conv_specs()
+    found = detect_backbone(inits, nodes)
+    if base_model is not None and base_model != found:
+        raise ValueError(f'{path}: the graph is a {found}, not a {base_model}')
+    specs = conv_specs(found)
+    feat = feature_width(found)
     named = OrderedDict((_strip_prefix(k), v) for k, v in inits.items())
     if all(w in named or w.replace('.conv1.net.', '.conv1.') in named for w, *_ in specs):
         sd = OrderedDict((k, v) for k, v in named.items()
@@ -207,7 +229,7 @@ def load_onnx_state_dict(path: str, num_class: int) -> 'OrderedDict[str, np.ndar
         if not fc:
             raise ValueError(f'{path}: no Gemm/MatMul node for the classifier')
         w = next(inits[i] for i in fc[-1]['input'] if i in inits and inits[i].ndim == 2)
-        if w.shape == (2048, num_class):
+        if w.shape == (feat, num_class):
             w = w.T
         sd['fc.weight'] = np.ascontiguousarray(w, dtype=np.float32)
         bias = [inits[i] for i in fc[-1]['input'] if i in inits and inits[i].ndim == 1]
@@ -215,6 +237,6 @@ def load_onnx_state_dict(path: str, num_class: int) -> 'OrderedDict[str, np.ndar
             adds = [n for n in nodes if n['op_type'] == 'Add' and fc[-1]['output'][0] in n['input']]
             bias = [inits[i] for n in adds for i in n['input'] if i in inits and inits[i].ndim == 1]
         sd['fc.bias'] = bias[0].astype(np.float32) if bias else np.zeros(num_class, np.float32)
-    if tuple(sd['fc.weight'].shape) != (num_class, 2048):
-        raise ValueError(f'{path}: classifier is {tuple(sd["fc.weight"].shape)}, expected ({num_class}, 2048)')
+    if tuple(sd['fc.weight'].shape) != (num_class, feat):
+        raise ValueError(f'{path}: classifier is {tuple(sd["fc.weight"].shape)}, expected ({num_class}, {feat})')
     return sd

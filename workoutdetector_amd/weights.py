@@ -1,9 +1,9 @@
-"""Weights for the TSM-R50 engine: seeded synthetic state dicts and checkpoint key remapping.
+"""Weights for the TSM-ResNet engine (R50, R18, R34): seeded synthetic state dicts and checkpoint key remapping.
 
 No trained weights exist offline, so benches and parity tests use
 a deterministic, numerically non-trivial state dict keyed exactly like the reference's
-``TSM.state_dict()`` (workoutdetector/models/tsm.py:250-262; conv1 of every Bottleneck is
-wrapped by TemporalShift, hence ``...conv1.net.weight``, tsm.py:134-136).
+``TSM.state_dict()`` (workoutdetector/models/tsm.py:250-262; conv1 of every block -- Bottleneck or
+BasicBlock -- is wrapped by TemporalShift, hence ``...conv1.net.weight``, tsm.py:134-136).
 
 ``remap_checkpoint_keys`` mirrors ``create_model``'s loader (tsm.py:451-473): the last two
 entries of the checkpoint are the classifier, they become ``fc.weight/bias`` iff their row
@@ -19,13 +19,41 @@ import numpy as np
 R50_BLOCKS = (3, 4, 6, 3)
 R50_PLANES = (64, 128, 256, 512)
 EXPANSION = 4
+# torchvision depth -> (blocks per stage, block type); planes are R50_PLANES for all of them
+BACKBONES = {'resnet18': ((2, 2, 2, 2), 'basic'), 'resnet34': ((3, 4, 6, 3), 'basic'),
+             'resnet50': (R50_BLOCKS, 'bottleneck')}
+DEPTHS = {'resnet18': 18, 'resnet34': 34, 'resnet50': 50}
 
 
-def conv_specs() -> List[Tuple[str, str, int, int, int]]:
-    """(conv weight key, bn prefix, cout, cin, k) for the 53 convs of TSM-R50, in forward order."""
+def _backbone(base_model: str):
+    if base_model not in BACKBONES:
+        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(BACKBONES))}')
+    return BACKBONES[base_model]
+
+
+def feature_width(base_model: str = 'resnet50') -> int:
+    """Channels of layer4's output = the classifier's input width: 2048 (Bottleneck), 512 (BasicBlock)."""
+    return R50_PLANES[-1] * (EXPANSION if _backbone(base_model)[1] == 'bottleneck' else 1)
+
+
+def conv_specs(base_model: str = 'resnet50') -> List[Tuple[str, str, int, int, int]]:
+    """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50, 20
+    for R18, 36 for R34).  A BasicBlock is conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the
+    first block of a stage changes the size or the width -- torchvision's module order."""
+    blocks, kind = _backbone(base_model)
     specs = [('base_model.conv1.weight', 'base_model.bn1', 64, 3, 7)]
     cin = 64
-    for li, (nb, planes) in enumerate(zip(R50_BLOCKS, R50_PLANES), start=1):
+    if kind == 'basic':
+        for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
+            for b in range(nb):
+                p = f'base_model.layer{li}.{b}'
+                specs.append((p + '.conv1.net.weight', p + '.bn1', planes, cin, 3))
+                specs.append((p + '.conv2.weight', p + '.bn2', planes, planes, 3))
+                if b == 0 and li > 1:
+                    specs.append((p + '.downsample.0.weight', p + '.downsample.1', planes, cin, 1))
+                cin = planes
+        return specs
+    for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
         for b in range(nb):
             p = f'base_model.layer{li}.{b}'
             specs.append((p + '.conv1.net.weight', p + '.bn1', planes, cin, 1))
@@ -38,40 +66,46 @@ def conv_specs() -> List[Tuple[str, str, int, int, int]]:
     return specs
 
 
-def make_state_dict(seed: int = 0, num_class: int = 12) -> 'OrderedDict[str, np.ndarray]':
-    """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048]).
+def make_state_dict(seed: int = 0, num_class: int = 12,
+                    base_model: str = 'resnet50') -> 'OrderedDict[str, np.ndarray]':
+    """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048] -- [cls, 512] for R18/R34).
 
     He-normal convs; BN statistics are all non-trivial so the fold is exercised; the last BN of
-    each residual branch is damped so activations stay O(1) through 16 blocks; the classifier uses
-    std 0.05 (the reference's init std 0.001, tsm.py:260-262, gives logits too flat to
-    discriminate between clips).
+    each residual branch (bn3 of a Bottleneck, bn2 of a BasicBlock) is damped so activations stay O(1)
+    through 16 blocks; the classifier uses std 0.05 (the reference's init std 0.001, tsm.py:260-262,
+    gives logits too flat to discriminate between clips).  R50 draws the same stream as it always has
+    (tests/golden/tsm_r50_logits.json depends on it).
     """
+    last_bn = '.bn2' if _backbone(base_model)[1] == 'basic' else '.bn3'
     rng = np.random.default_rng(seed)
     sd: 'OrderedDict[str, np.ndarray]' = OrderedDict()
 
     def f32(a):
         return np.ascontiguousarray(a, dtype=np.float32)
 
-    for wkey, bnp, cout, cin, k in conv_specs():
+    for wkey, bnp, cout, cin, k in conv_specs(base_model):
         fan_in = cin * k * k
         sd[wkey] = f32(rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / fan_in))
-        damp = 0.35 if bnp.endswith('.bn3') else 1.0
+        damp = 0.35 if bnp.endswith(last_bn) else 1.0
         sd[bnp + '.weight'] = f32(rng.uniform(0.8, 1.2, cout) * damp)
         sd[bnp + '.bias'] = f32(rng.standard_normal(cout) * 0.1)
         sd[bnp + '.running_mean'] = f32(rng.standard_normal(cout) * 0.1)
         sd[bnp + '.running_var'] = f32(rng.uniform(0.6, 1.4, cout))
-    sd['fc.weight'] = f32(rng.standard_normal((num_class, 512 * EXPANSION)) * 0.05)
+    sd['fc.weight'] = f32(rng.standard_normal((num_class, feature_width(base_model))) * 0.05)
     sd['fc.bias'] = f32(rng.standard_normal(num_class) * 0.1)
     return sd
 
 
-def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int) -> 'OrderedDict[str, object]':
+def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
+                          base_model: str = 'resnet50') -> 'OrderedDict[str, object]':
     """Checkpoint ``state_dict`` (``module.``/``model.``-prefixed) -> engine keys, exactly as create_model does it
     (models/tsm.py:451-473; pinned by tests/golden/ref_ckpt_remap.json, produced by executing those statements):
     the LAST TWO entries are the classifier; they become ``fc.weight`` / ``fc.bias`` iff the weight has ``num_class``
     rows and are dropped otherwise; every key loses its first dotted component.  Like the reference, a classifier
     that is already called ``module.fc`` is dropped by the delete that follows the copy -- the reference then keeps
-    its random-init fc (``strict=False``); the engine reports the missing ``fc.weight`` instead of guessing."""
+    its random-init fc (``strict=False``); the engine reports the missing ``fc.weight`` instead of guessing.
+    The rule does not depend on the backbone; ``base_model`` is checked to be one the engine implements."""
+    _backbone(base_model)
     items = OrderedDict(state_dict)
     keys = list(items.keys())
     fc_w, fc_b = keys[-2], keys[-1]
@@ -122,8 +156,8 @@ def remap_mmaction_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, o
     return out
 
 
-def required_keys(num_class_known: bool = True) -> Iterable[str]:
-    for wkey, bnp, *_ in conv_specs():
+def required_keys(num_class_known: bool = True, base_model: str = 'resnet50') -> Iterable[str]:
+    for wkey, bnp, *_ in conv_specs(base_model):
         yield wkey
         for s in ('.weight', '.bias', '.running_mean', '.running_var'):
             yield bnp + s

@@ -198,11 +198,16 @@ int tsm_layer_times(tsm_engine *e, int32_t forward_index, float *ms_out, int32_t
  * then per block [downsample,] conv1, conv2, conv3 -- BasicBlock: [downsample,] conv1, conv2): 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 32x32 (one wave),
  * 5 = 128x128 on 8 waves, 6 = 256x256 LDS-DMA kernel (bf16), 7 = weight-stationary 3x3 (bf16, 64 -> 64 / 128 -> 128
  * channels), 8 = the 256x256 kernel run persistently over a workgroup's tiles (bf16, K >= 128), 0 = not tuned (heuristic); + 256 = split-K form of a segmented fp32 layer (one workgroup per tile and K
- * segment, combined in segment order); + 1024 (on conv2's code) = the block runs conv2 + conv3 + residual as ONE launch
- * (conv3's slot is then not used); + 2048 (on conv1's code) = the WHOLE block -- shift, conv1, conv2, conv3 (+ the fused
+ * segment, combined in segment order); + 512 = tail split of a segmented 64x64 fp32 layer (only the tiles of the last, partly
+ * filled round of resident workgroups run split-K); + 1024 (on conv2's code) = the block runs conv2 + conv3 + residual as ONE
+ * launch (conv3's slot is then not used); + 2048 (on conv1's code) = the WHOLE block -- shift, conv1, conv2, conv3 (+ the fused
  * downsample branch) + identity -- runs as ONE launch (bf16 layer1; the conv2 / conv3 slots are then not used); + 4096 (on
- * conv3's code) = that launch also runs the temporal shift + conv1 of the NEXT block (bf16 layer2; the next block's conv1
- * slot is then not used).
+ * conv3's code) = that launch also runs the temporal shift + conv1 of the NEXT block (bf16 layer2 / layer3; the next block's
+ * conv1 slot is then not used); + 8192 (on conv1's code) = that launch also runs the block's stride-2 conv2 (bf16 layer2.0;
+ * conv2's slot is then not used).
+ * The report is what an `n_clips` forward RUNS: a fusion bit (1024 / 2048 / 4096 / 8192) is set only where the tuner chose
+ * that form and it runs at this clip count; a form forced through the environment (TSM_FUSE_* = 1) is not a tuner choice
+ * and sets no bit.
  * The first tsm_forward with a new power-of-two bucket of n_clips
  * times every valid code per layer once, SYNCHRONOUSLY (see Conventions: not capture-safe, a few hundred ms; results are
  * bit-identical across codes); TSM_AUTOTUNE=0 in the environment at tsm_create disables it, TSM_TUNE_CACHE=<file> lets a

@@ -36,6 +36,31 @@ def assert_ran_tile(trace, tile, what=''):
     assert ran_tile(trace, tile), f'{what}: TSM_CONV_TILE={tile} did not run its kernel; the trace holds {sorted(set(trace.kernels))}'
 
 
+def assert_fused_slots(eng, x, forced, what=''):
+    """Per-launch timing of one forward of `x`: the conv slots it leaves unrecorded (-1) are exactly those a fused launch took
+    over -- the `forced` names and those of the tuned forms conv_tiles reports ('+block' on conv1: conv2 and conv3; '+conv2' on
+    conv1: conv2; '+conv3' on conv2: conv3; '+conv1' on conv3: the next block's conv1).  (The pack, the max-pool of the
+    pool-fused stem and a Bottleneck's downsample, which runs inside conv3's GEMM, are never launches of their own.)"""
+    eng.set_layer_timing(1)
+    eng.run(None, {'input': x})
+    times = eng.layer_times_ms(0)
+    tiles = eng.conv_tiles(x.shape[0])
+    names = list(tiles)
+    away = set(forced)
+    for i, (k, v) in enumerate(tiles.items()):
+        blk = k.rsplit('.', 1)[0]
+        if '+block' in v:
+            away |= {blk + '.conv2', blk + '.conv3'}
+        if '+conv2' in v:
+            away.add(blk + '.conv2')
+        if '+conv3' in v:
+            away.add(blk + '.conv3')
+        if '+conv1' in v:
+            away.add(next(n for n in names[i + 1:] if n.endswith('.conv1')))
+    unrecorded = {k for k, v in times.items() if v == -1 and k not in ('pack_input', 'maxpool') and not k.endswith('.downsample')}
+    assert unrecorded == away, (what, sorted(unrecorded - away), sorted(away - unrecorded))
+
+
 def assert_close(got, want, rtol, atol_scale=1e-4, what=''):
     """|got - want| <= rtol * |want| + atol_scale * max|want|  (elementwise), fp32 tolerance."""
     got = np.asarray(got, dtype=np.float64)

@@ -33,16 +33,17 @@ static void fuzz_tune_lines(unsigned seed, int rounds) {
     EXPECT(parse_tune_line(line.c_str(), want, kNumTiles, &codes));
     EXPECT(codes[0] == 3 && codes[1] == 259 && codes[2] == 4 && codes[3] == 1 && codes[4] == 5);
   }
-  // the fusion bits survive a round trip: 0x400 (conv2 + conv3 as one launch) and 0x800 (the whole block as one launch;
-  // a parser that dropped such a line would make every rank of a multi-GPU job tune for itself again)
+  // the fusion bits survive a round trip: kCodeConv23 (conv2 + conv3 as one launch) and kCodeBlock (the whole block as one
+  // launch; a parser that dropped such a line would make every rank of a multi-GPU job tune for itself again)
   {
     std::vector<int> codes(5, -1);
-    const std::string line = want + "2054,1030,6,3075,4102\n";       // (4102 = 6 | 0x1000: conv3 also runs the next block's conv1)
+    const std::string line = want + "2054,1030,6,3075,4102\n";       // (4102 = 6 | kCodeConv31: conv3 also runs the next block's conv1)
     EXPECT(parse_tune_line(line.c_str(), want, kNumTiles, &codes));
-    EXPECT(codes[0] == (6 | 0x800) && codes[1] == (6 | 0x400) && codes[2] == 6 && codes[3] == (3 | 0x400 | 0x800) && codes[4] == (6 | 0x1000));
-    const std::string line2 = want + "515,8198,3,3,3\n";             // (515 = 3 | 0x200: tail split; 8198 = 6 | 0x2000: conv1 also runs the stride-2 conv2)
+    EXPECT(codes[0] == (6 | kCodeBlock) && codes[1] == (6 | kCodeConv23) && codes[2] == 6 && codes[3] == (3 | kCodeConv23 | kCodeBlock) &&
+           codes[4] == (6 | kCodeConv31));
+    const std::string line2 = want + "515,8198,3,3,3\n";             // (515 = 3 | kCodeTailK: tail split; 8198 = 6 | kCodeFront: conv1 also runs the stride-2 conv2)
     EXPECT(parse_tune_line(line2.c_str(), want, kNumTiles, &codes));
-    EXPECT(codes[0] == (3 | 0x200) && codes[1] == (6 | 0x2000));
+    EXPECT(codes[0] == (3 | kCodeTailK) && codes[1] == (6 | kCodeFront));
   }
   const char *bad[] = {"", "\n", "|", "abi3", "abi3 gfx950 T8 224x224 dtype0 shift8 fuse1|256|",
                        "abi3 gfx950 T8 224x224 dtype0 shift8 fuse1|256|3,3,3,3",            // too few
@@ -77,7 +78,7 @@ static void fuzz_tune_lines(unsigned seed, int rounds) {
     if (line.size() > 4000) line.resize(4000);
     std::vector<int> codes(5, -7);
     const bool ok = parse_tune_line(line.c_str(), want, kNumTiles, &codes);
-    for (int c : codes) EXPECT(ok ? (c >= 0 && (c & ~0x3F0F) == 0 && (c & 15) < kNumTiles) : c == -7);
+    for (int c : codes) EXPECT(ok ? (c >= 0 && (c & ~kCodeValid) == 0 && (c & kCodeTileMask) < kNumTiles) : c == -7);
   }
 }
 

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import tsm_oracle
-from tests._util import (BF16_TAP_BAR, assert_bf16_op, assert_close, assert_not_ran, assert_ran, assert_ran_tile, bf16_logits_report,
+from tests._util import (BF16_TAP_BAR, assert_bf16_op, assert_close, assert_fused_slots, assert_not_ran, assert_ran, assert_ran_tile, bf16_logits_report,
                          make_input, ran_tile)
 from tests.test_ops_gpu import CONV_CASES, _bn, _nchw, _nhwc
 
@@ -502,13 +502,14 @@ def test_whole_bottleneck_kernel_equals_the_separate_launches_bitwise(hip_lib, m
         with launch_trace() as tr:
             got[flag] = [eng.forward_tap(x, s) for s in ('layer1.0', 'layer1.1', 'layer1.2', 'layer2.0')] + [eng.run(None, {'input': x})[0]]
         tiles = eng.conv_tiles(b)
+        wp = (((w - 1) // 2 + 1) - 1) // 2 + 1          # layer1's row length: stem (stride 2) then max-pool (stride 2)
+        fits = flag == '1' and wp <= 64
+        assert_fused_slots(eng, x, {f'layer1.{k}.conv{c}' for k in range(3) for c in (2, 3)} if fits else set(), flag)
         eng.close()
         assert not any(v.endswith('+block') for v in tiles.values())    # (a forced form is not a tuner choice: no code carries the bit)
         # What RAN.  Forced on, all three layer1 blocks take the whole-block kernel where the line buffer fits (frames of <= 64
         # columns: W <= 256) -- layer1.0 on the 64-channel form, layer1.1 / 1.2 on the 256-channel one (LDS identity at 64
         # columns) -- and a too-wide frame falls back; forced off, it never runs.
-        wp = (((w - 1) // 2 + 1) - 1) // 2 + 1          # layer1's row length: stem (stride 2) then max-pool (stride 2)
-        fits = flag == '1' and wp <= 64
         sh = 'true' if shift else 'false'
         wide = f'bneck_ws_kernel<256, {sh}, true>' if wp == 64 else f'bneck_ws_kernel<256, {sh}>'
         # (taps 'layer1.0' .. 'layer2.0' run 1 + 2 + 3 + 3 blocks, the forward 3, its tuning pass none: the forced form is not timed)
@@ -550,6 +551,10 @@ def test_conv3_conv1_cross_block_kernel_equals_the_separate_launches_bitwise(hip
         eng = TsmEngine(num_segments=t, height=h, width=w, shift_div=div, is_shift=shift, max_clips=b, state_dict=sd, dtype='bf16')
         with launch_trace() as tr:
             got[flag] = [eng.run(None, {'input': x})[0]] + [eng.forward_tap(x, s) for s in stages] + [eng.run(None, {'input': x})[0]]
+        # (the next block's conv1 launches the forced form takes over, per instantiation below)
+        taken = {256: ('layer2.2.conv1', 'layer2.3.conv1'), 128: ('layer3.0.conv1', 'layer3.2.conv1', 'layer3.3.conv1', 'layer3.4.conv1',
+                                                                'layer3.5.conv1')}
+        assert_fused_slots(eng, x, {n for rows, ns in taken.items() if flag == '1' and rows % t == 0 and rows // t >= 8 for n in ns}, flag)
         eng.close()
         # What RAN: forced on, every geometry with a clip-major tile runs its instantiation -- layer2.k -> k+1 (<128, 512, 128, 1>),
         # layer2.3 -> layer3.0 (<128, 512, 256, 2>), layer3.k -> k+1 (<256, 1024, 256, 2>) -- and the geometries without one (odd T,
@@ -626,9 +631,10 @@ def test_front_of_layer2_0_as_one_launch_equals_the_separate_launches_bitwise(hi
         got[flag] = [eng.run(None, {'input': x})[0]]
         with launch_trace() as tr:
             got[flag] += [eng.forward_tap(x, s) for s in stages] + [eng.run(None, {'input': x})[0]]
-        eng.close()
         hp, wp = (((h - 1) // 2 + 1) - 1) // 2 + 1, (((w - 1) // 2 + 1) - 1) // 2 + 1      # layer1's frame = layer2.0's input
         fits = flag == '1' and hp % 2 == 0 and wp <= 64
+        assert_fused_slots(eng, x, {'layer2.0.conv2'} if fits else set(), flag)
+        eng.close()
         kern = 'front_s2_kernel<true>' if shift else 'front_s2_kernel<false>'
         # (the taps 'layer2.0.conv2', 'layer2.0', 'layer2.1' and the forward run layer2.0's front once each)
         assert tr.count(kern) == (4 if fits else 0) and tr.ran('front_s2_kernel') == fits, (flag, sorted(set(tr.kernels)))

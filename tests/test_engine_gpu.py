@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import tsm_oracle
-from tests._util import assert_close, make_input
+from tests._util import assert_close, assert_fused_slots, make_input
 
 pytestmark = pytest.mark.gpu
 
@@ -462,6 +462,35 @@ def test_tune_cache_keeps_the_fusion_bits(hip_lib, sd0, tmp_path, monkeypatch):
     assert np.array_equal(ya, yb)                         # and, as always, not a bit of the result depends on it
 
 
+def test_tune_cache_fusion_bit_of_a_form_that_cannot_run(hip_lib, sd0, tmp_path, monkeypatch):
+    """A cached code may carry the bit of a fused form that cannot run at this geometry (a hand-edited or bucket-shared line):
+    +8192 (shift + conv1 + the stride-2 conv2 of layer2.0 as one launch) on a bf16 90 x 70 engine, whose layer2 input has an
+    odd height.  The forward keeps the two launches, the result does not change, and conv_tiles reports what ran: no '+conv2'."""
+    from workoutdetector_amd.engine import TsmEngine, launch_trace
+    path = tmp_path / 'tiles.txt'
+    monkeypatch.setenv('TSM_TUNE_CACHE', str(path))
+    x = make_input(54, 2, 8, 90, 70)
+    a = TsmEngine(height=90, width=70, max_clips=2, state_dict=sd0, dtype='bf16')
+    ya = a.run(None, {'input': x})[0]
+    a.close()
+    key, codes = path.read_text().splitlines()[0].rsplit('|', 1)
+    codes = [int(c) for c in codes.split(',')]
+    # the line is in the engine's layer order: stem, then per block conv1, conv2, conv3 (, downsample)
+    order = ['conv1'] + [f'layer{li}.{b}.{part}' for li, nb in enumerate((3, 4, 6, 3), 1) for b in range(nb)
+                         for part in ('conv1', 'conv2', 'conv3') + (('downsample',) if b == 0 else ())]
+    codes[order.index('layer2.0.conv1')] |= 0x2000
+    path.write_text(key + '|' + ','.join(str(c) for c in codes) + '\n')
+    b = TsmEngine(height=90, width=70, max_clips=2, state_dict=sd0, dtype='bf16')
+    with launch_trace() as tr:
+        yb = b.run(None, {'input': x})[0]
+    tiles = b.conv_tiles(2)
+    b.close()
+    assert len(path.read_text().splitlines()) == 1, 'the edited line was rejected and the engine tuned again'
+    assert not tr.ran('front_s2_kernel'), sorted(set(tr.kernels))
+    assert '+conv2' not in tiles['layer2.0.conv1'], tiles['layer2.0.conv1']
+    assert np.array_equal(ya, yb)
+
+
 @pytest.mark.parametrize('dtype', ['f32', 'bf16x3', 'bf16'])
 @pytest.mark.parametrize('h,w,b', [(224, 224, 2), (96, 96, 3), (90, 70, 1), (256, 256, 3)])
 def test_fused_conv2_conv3_equals_the_separate_kernels_bitwise(hip_lib, sd0, monkeypatch, h, w, b, dtype):
@@ -480,6 +509,8 @@ def test_fused_conv2_conv3_equals_the_separate_kernels_bitwise(hip_lib, sd0, mon
         eng = TsmEngine(height=h, width=w, max_clips=b, state_dict=sd0, dtype=dtype)
         with launch_trace() as tr:
             got[flag] = [eng.run(None, {'input': x})[0]] + [eng.forward_tap(x, s) for s in ('layer1.1', 'layer1.2', 'layer2.3')]
+        fused_blocks = ('layer1.1', 'layer1.2') + (() if dtype == 'bf16' else ('layer2.1', 'layer2.2', 'layer2.3'))
+        assert_fused_slots(eng, x, {k + '.conv3' for k in fused_blocks} if flag == '1' else set(), flag)
         eng.close()
         # what RAN: bf16 -> conv3x3_ws_kernel<true> (layer1.1-2); fp32 / split-bf16 -> conv23_fused_kernel<64 | 128, X3>
         fused_kernels = ['conv3x3_ws_kernel<true>'] if dtype == 'bf16' else \

@@ -127,23 +127,17 @@ struct tsm_engine {
   // conv tile autotune: per frame count, one ConvTile per conv layer (0 = not tuned yet)
   std::map<int, std::vector<int>> tile_cache;
   bool autotune = true;
-  bool fuse_down = true;  // TSM_FUSE_DOWNSAMPLE=0 runs the downsample branch as its own launch
   bool stem_pool = true;    // TSM_STEM_POOL=0: separate max-pool launch behind the direct stem
   bool stem_direct = true;  // TSM_STEM_DIRECT=0: bf16-format stems on the generic implicit-GEMM kernel (bit-identical, slower)
   bool stem_planar = true;  // TSM_STEM_PLANAR=0: an NTCHW input is packed by its own launch first (bit-identical, one more pass over the input)
   // TSM_TUNE_CACHE=<file>: tuned tile codes are appended to / read from this file, one line per bucket, keyed by
   // `tune_sig` (ABI, device name, geometry, dtype): a later process skips the timing pass.  Codes never change
-  // results and every code is re-validated against its layer at launch (run_forward, code_ok), so a stale, foreign
+  // results and every code is re-validated against its layer at launch (Forward::conv, plan_forward), so a stale, foreign
   // or hand-edited line can only cost speed; malformed lines are ignored.
   std::string tune_path, tune_sig;
   // Tuning hooks, read ONCE in tsm_create (never per launch): TSM_CONV_TILE=<name> forces one tile shape wherever it
-  // is valid, TSM_CONV_CODE=<int> one tile code (tile | 0x100 = split-K form); tests and tools/ sweeps only.
+  // is valid, TSM_CONV_CODE=<int> one tile code (tile | kCodeSplitK = split-K form); tests and tools/ sweeps only.
   int force_tile = 0, force_code = -1;
-  int tail_split = 1;   // TSM_TAIL_SPLIT=0: the tuner does not try the tail-split form (tile code bit 0x200)
-  // Consecutive conv launches walk their output tiles in opposite directions: a kernel starts with the rows its
-  // predecessor wrote last, which are still in the Infinity Cache / L2 (bit-neutral; -1...2 % forward time in the
-  // HBM-bound formats, nothing in fp32).  TSM_ZIGZAG=0 switches it off.
-  bool zigzag = true;
   int fuse23 = -1;   // TSM_FUSE_CONV23: 0 never, 1 wherever a block is eligible, unset: the autotuner times both forms
   int fuse_block = -1;   // TSM_FUSE_BLOCK: the same for the whole-Bottleneck kernel (bf16, layer1.1 / layer1.2)
   int fuse31 = -1;       // TSM_FUSE_C3C1: the same for conv3 of block b + shift + conv1 of block b + 1 as one launch (bf16, layer2)
@@ -327,7 +321,7 @@ void tune_cache_store(tsm_engine *e, int key, const std::vector<int> &codes) {
   fclose(f);
 }
 
-// The tail split of a segmented 64x64 launch (tile code bit 0x200): tsm_host_util.h::tail_split_point on this launch's shape.
+// The tail split of a segmented 64x64 launch (tile code bit kCodeTailK): tsm_host_util.h::tail_split_point on this launch's shape.
 bool tail_split_from(const tsm::ConvParams &p, int n_cu, size_t partial_elems, int *tail_from) {
   if (p.kseg_len <= 0) return false;
   const long from = tsm_host::tail_split_point(p.M, p.Cout, tsm::conv_num_segments(p), n_cu, partial_elems);
@@ -374,146 +368,438 @@ struct LaunchTimer {
   } while (0)
 #define TSM_LAUNCH(e, s, call) TSM_LAUNCH_K(e, s, false, call)
 
+// Keeps `n` launch slots of the per-launch timing (tsm_layer_times) for launches this forward does not make: each is reported
+// as "not recorded", so the slots stay those of TsmEngine.launch_names().
+void skip_slots(tsm_engine *e, int n) {
+  if (e->cur_timing) e->cur_timing->insert(e->cur_timing->end(), 2 * (size_t)n, nullptr);
+}
+
+// Times `launches` (enqueues one or more launches on `s`, returns the first error) the way the tuner makes every choice: four
+// repetitions, each inside one event bracket (so the boundaries between back-to-back kernels and each kernel's cold start on
+// its producer's output are priced, as in a forward), the first discarded (it warms the caches), the best of the other three.
+template <class F>
+int time_best_of(tsm_engine *e, hipStream_t s, F &&launches, float *best_ms) {
+  float ms[4];
+  for (int rep = 0; rep < 4; ++rep) {
+    TSM_HIP(e, hipEventRecord(e->ev0, s));
+    TSM_HIP(e, launches());
+    TSM_HIP(e, hipEventRecord(e->ev1, s));
+    TSM_HIP(e, hipEventSynchronize(e->ev1));
+    TSM_HIP(e, hipEventElapsedTime(&ms[rep], e->ev0, e->ev1));
+  }
+  *best_ms = std::min(ms[1], std::min(ms[2], ms[3]));
+  return TSM_OK;
+}
+
+// Every launch Bottleneck k can make on nn frames of hh x ww pixels, x -> y through the branch temporaries t1, t2, with
+// `reverse` still 0: the three convs (conv3 with the downsample branch K-concatenated behind it where the block has one) and
+// the fused forms.  Built with null tensors too, for the kernels' validity tests, which read shapes only.
+struct BlockLaunches {
+  tsm::ConvParams p1, p2, p3;
+  tsm::BneckParams pb{};     // the whole block (bneck_ws_kernel)
+  tsm::FrontParams pfr{};    // shift + conv1 + the stride-2 conv2 (front_s2_kernel; t1 never exists in memory)
+  tsm::Fused23Params pf{};   // conv2 + conv3 + residual (tsm::launch_conv23_fused)
+  tsm::Conv31Params q{};     // conv3 + residual and the NEXT block's shift + conv1 (conv31_fused_kernel), writing t1
+};
+
+BlockLaunches block_launches(const tsm_engine *e, size_t k, int nn, const float *x, float *y, float *t1, float *t2, int hh, int ww) {
+  const tsm_config &cfg = e->cfg;
+  const Block &blk = e->blocks[k];
+  const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
+  const int T = cfg.num_segments, shiftT = cfg.is_shift ? T : 0, prec = e->prec;
+  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  const bool fused = blk.down >= 0;   // (a Bottleneck's downsample always runs inside conv3's GEMM)
+  BlockLaunches L;
+  L.p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, cfg.shift_div, prec);
+  L.p2 = make_params(c2, t1, nullptr, t2, nn, hh, ww, true, 0, 1, prec);
+  L.p3 = make_params(c3, t2, fused ? nullptr : x, y, nn, ho, wo, true, 0, 1, prec);
+  if (fused) {
+    const ConvLayer &cd = e->convs[blk.down];
+    L.p3.w = blk.d_wf; L.p3.bias = blk.d_bf; L.p3.Kp = blk.kpf; L.p3.K1 = c3.kp; L.p3.kseg_len = blk.ksegf;
+    L.p3.x2 = x; L.p3.C2 = cd.cp; L.p3.Hi2 = hh; L.p3.Wi2 = ww; L.p3.stride2 = blk.stride;
+  }
+  tsm::BneckParams &pb = L.pb;
+  pb.x = x; pb.w1 = c1.d_w; pb.bias1 = c1.d_b; pb.w2 = c2.d_w; pb.bias2 = c2.d_b; pb.y = y;
+  pb.w3 = fused ? blk.d_wf : c3.d_w; pb.bias3 = fused ? blk.d_bf : c3.d_b;
+  pb.cin = c1.cin; pb.N = nn; pb.H = hh; pb.W = ww; pb.T = shiftT; pb.fold = L.p1.fold;
+  tsm::FrontParams &pfr = L.pfr;
+  pfr.x = x; pfr.w1 = c1.d_w; pfr.bias1 = c1.d_b; pfr.w2 = c2.d_w; pfr.bias2 = c2.d_b; pfr.y = t2;
+  pfr.N = nn; pfr.H = hh; pfr.W = ww; pfr.T = shiftT; pfr.fold = L.p1.fold;
+  // (conv3's weights in fragment order for fp32 / split-bf16; the bf16 form reads conv3's packed matrix itself)
+  tsm::Fused23Params &pf = L.pf;
+  pf.x = t1; pf.w2 = c2.d_w; pf.bias2 = c2.d_b; pf.w3f = blk.d_w3f ? blk.d_w3f : c3.d_w; pf.bias3 = c3.d_b; pf.res = x; pf.y = y;
+  pf.N = nn; pf.H = hh; pf.W = ww; pf.M = nn * hh * ww; pf.kseg_len = c2.kseg;
+  if (k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0) {
+    const ConvLayer &c1n = e->convs[e->blocks[k + 1].conv1];
+    tsm::Conv31Params &q = L.q;
+    q.t2 = L.p3.x; q.w3 = L.p3.w; q.bias3 = L.p3.bias; q.res = L.p3.res; q.y = L.p3.y;
+    q.w1 = c1n.d_w; q.bias1 = c1n.d_b; q.t1 = t1;
+    q.n_clips = nn / T; q.T = T; q.HW = ho * wo; q.K3 = L.p3.C; q.C = L.p3.Cout; q.N1 = c1n.cout;
+    q.fold = shiftT > 0 ? c1n.cp / cfg.shift_div : 0;
+  }
+  return L;
+}
+
+// The fused forms Bottleneck k of an nn-frame forward on hh x ww inputs CAN run (BasicBlocks have none): dtype, shape, the
+// kernels' validity tests, TSM_FUSE_* = 0, and the stage being tapped (a tapped tensor must exist in memory).  `front` does
+// not know whether conv1 has already run (BlockPlan::conv1_done).
+struct BlockForms {
+  bool block = false, front = false, conv23 = false, conv31 = false;
+};
+
+BlockForms fused_forms(const tsm_engine *e, size_t k, int nn, int hh, int ww, const char *stage) {
+  BlockForms f;
+  const Block &blk = e->blocks[k];
+  if (blk.conv3 < 0) return f;
+  const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
+  const BlockLaunches L = block_launches(e, k, nn, nullptr, nullptr, nullptr, nullptr, hh, ww);
+  const bool bf16 = e->prec == tsm::kPrecBf16;
+  auto want = [&](const char *part) { return stage && blk.name + part == stage; };
+  f.block = bf16 && blk.stride == 1 && c1.cout == 64 && c2.cin == 64 && c2.cout == 64 && c3.cout == 256 &&
+            (blk.down < 0 ? c1.cin == 256 : c1.cin == 64 && e->convs[blk.down].cp == 64) && e->fuse_block != 0 &&
+            tsm::bneck_ws_valid(L.pb.cin, L.pb.N, L.pb.H, L.pb.W, L.pb.T, L.pb.fold) && !want(".conv1") && !want(".conv2");
+  f.front = bf16 && blk.stride == 2 && c1.cin == 256 && c1.cout == 128 && c2.cin == 128 && c2.cout == 128 && e->fuse_front != 0 &&
+            tsm::front_s2_valid(L.pfr.N, L.pfr.H, L.pfr.W, L.pfr.T, L.pfr.fold) && !want(".conv1");
+  f.conv23 = (blk.d_w3f != nullptr || (bf16 && blk.cmid == 64 && tsm::conv23_ws_valid(nn, hh, ww))) && e->fuse23 != 0 &&
+             !want(".conv2");
+  f.conv31 = bf16 && blk.down < 0 && k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0 && e->fuse31 != 0 &&
+             tsm::conv31_valid(L.q);
+  return f;
+}
+
+// What each block of an nn-frame forward runs: a fused form runs where it can (fused_forms) and was chosen -- forced through
+// TSM_FUSE_* = 1 or its bit in the tuned code.  At most one form per block, in this precedence: the whole block, the front
+// (never when conv1 has already run), conv2 + conv3, conv3 + the next block's conv1; the last sets the next block's
+// conv1_done.  BasicBlocks run no fused form.
+struct BlockPlan {
+  bool block = false, front = false, conv1_done = false, conv23 = false, conv31_next = false;
+};
+
+std::vector<BlockPlan> plan_forward(const tsm_engine *e, const std::vector<int> *codes, int nn, const char *stage) {
+  std::vector<BlockPlan> plan(e->blocks.size());
+  int hh = e->hp, ww = e->wp;
+  for (size_t k = 0; k < e->blocks.size(); ++k) {
+    const Block &blk = e->blocks[k];
+    const BlockForms can = fused_forms(e, k, nn, hh, ww, stage);
+    auto chosen = [&](int force, int conv, int bit) { return force == 1 || (codes && ((*codes)[conv] & bit)); };
+    BlockPlan &p = plan[k];
+    p.conv1_done = k > 0 && plan[k - 1].conv31_next;
+    if (can.block && chosen(e->fuse_block, blk.conv1, kCodeBlock)) p.block = true;
+    else if (can.front && !p.conv1_done && chosen(e->fuse_front, blk.conv1, kCodeFront)) p.front = true;
+    else if (can.conv23 && chosen(e->fuse23, blk.conv2, kCodeConv23)) p.conv23 = true;
+    else if (can.conv31 && chosen(e->fuse31, blk.conv3, kCodeConv31)) p.conv31_next = true;
+    hh = (hh + 2 - 3) / blk.stride + 1;
+    ww = (ww + 2 - 3) / blk.stride + 1;
+  }
+  return plan;
+}
+
+// One forward (run_forward): the state its launches share.
+struct Forward {
+  tsm_engine *e;
+  hipStream_t s;
+  const char *stage;
+  Tap *tap;
+  int T, shiftT, prec;
+  float *t1, *t2, *idb;                // branch temporaries, the BasicBlock's downsample output
+  std::vector<int> *tiles = nullptr;   // tile codes of this bucket (null: heuristic shapes -- TSM_AUTOTUNE=0 or a tap)
+  bool tuning = false;                 // the bucket's tuning pass: time the candidates, write the winners into *tiles
+  bool tapped = false;
+  // Consecutive conv launches walk their output tiles in opposite directions (ConvParams::reverse): a kernel starts with
+  // the rows its predecessor wrote last, which are still in the Infinity Cache / L2 (bit-neutral).
+  int flip = 0;
+  // (tuning) the previous block and its launches, where its conv3 could also run this block's conv1 (timed at this block's head)
+  int prev31 = -1;
+  BlockLaunches prev;
+
+  Forward(tsm_engine *e_, hipStream_t s_, const char *stage_, Tap *tap_)
+      : e(e_), s(s_), stage(stage_), tap(tap_), T(e_->cfg.num_segments), shiftT(e_->cfg.is_shift ? T : 0), prec(e_->prec),
+        t1(e_->buf[2]), t2(e_->buf[3]), idb(e_->buf[4]) {}
+
+  int next_dir() { return flip ^= 1; }
+  bool want(const std::string &name) const { return stage && name == stage; }
+  int hit(const float *p, int64_t a, int64_t b, int64_t c, int64_t d) {
+    tap->ptr = p; tap->shape[0] = a; tap->shape[1] = b; tap->shape[2] = c; tap->shape[3] = d; tap->hit = true;
+    tapped = true;
+    return TSM_OK;
+  }
+  hipError_t launch_code(tsm::ConvParams p, int ks, int code);
+  hipError_t launch_pair(const tsm::ConvParams &a, int ks_a, int code_a, const tsm::ConvParams &b, int ks_b, int code_b) {
+    const hipError_t st = launch_code(a, ks_a, code_a);
+    return st != hipSuccess ? st : launch_code(b, ks_b, code_b);
+  }
+  // (tuning) *wins = the fused launch `one` beat the separate launches `many` it replaces, each timed by time_best_of
+  template <class A, class B>
+  int fused_wins(A &&many, B &&one, bool *wins) {
+    float many_ms = 0.f, one_ms = 0.f;
+    int rc = time_best_of(e, s, many, &many_ms);
+    if (!rc) rc = time_best_of(e, s, one, &one_ms);
+    *wins = one_ms < many_ms;
+    return rc;
+  }
+  int conv(int idx, tsm::ConvParams p, int ks, bool is3x3);
+  int run_basic(size_t k, int nn, float *x, float *y, int hh, int ww);
+  int run_block(size_t k, const BlockPlan &plan, int nn, float *x, float *y, int hh, int ww);
+  int tune_block(size_t k, int nn, float *x, float *y, int hh, int ww);
+};
+
+// A tile code is a ConvTile, plus kCodeSplitK for the split-K form of a segmented layer: one workgroup per (tile, K segment)
+// writes raw segment sums, splitk_reduce adds them in segment order and applies bias / ReLU -- bit-identical to the unsplit
+// launch.  Every output element accumulates its K in the same order whatever the tiling, so codes are bit-neutral.
+hipError_t Forward::launch_code(tsm::ConvParams p, int ks, int code) {
+  p.tile = code & kCodeTileMask;
+  // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
+  // EVERY launch (falling back to the whole-K form, which gives the same bits).
+  if ((code & kCodeSplitK) && p.kseg_len > 0 &&
+      (size_t)tsm::conv_num_segments(p) * (size_t)p.M * (size_t)p.Cout <= e->partial_elems) {
+    float *y = p.y;
+    p.ksplit = 1;
+    p.y = e->d_partial;
+    hipError_t st = tsm::launch_conv(p, ks, s);
+    if (st == hipSuccess)
+      st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M, p.Cout, p.bias, nullptr, y, p.relu, s);
+    return st;
+  }
+  // kCodeTailK: the tail split (ConvParams::ksplit = 2) of a segmented 64x64 layer -- the tiles of the last, partly filled round
+  // of resident workgroups (five per CU) as (tile, segment) pieces.  Re-derived from THIS launch's tile count on every launch;
+  // whenever it does not apply the whole-K form runs (same bits).
+  if ((code & kCodeTailK) && (code & kCodeTileMask) == tsm::kTile64x64 && p.kseg_len > 0) {
+    int tail_from = 0;
+    if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) {
+      float *y = p.y;
+      const int mt0 = tail_from / (p.Cout / 64) * 64;
+      p.ksplit = 2;
+      p.tail_from = tail_from;
+      p.ypart = e->d_partial;
+      hipError_t st = tsm::launch_conv(p, ks, s);
+      if (st == hipSuccess)
+        st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M - mt0, p.Cout, p.bias, nullptr,
+                                       y + (size_t)mt0 * p.Cout, p.relu, s);
+      return st;
+    }
+  }
+  return tsm::launch_conv(p, ks, s);
+}
+
+// One conv launch.  Steady forward: the layer's tuned code, trusted only after it has been checked against THIS layer --
+// anything else falls back to the heuristic shape, so a stale, foreign or hand-edited cache line can only cost speed.
+// Tuning pass: every candidate code timed on the real launch, the fastest kept.
+int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
+  p.reverse = next_dir();
+  if (!tuning) {
+    int code = tiles ? (*tiles)[idx] : 0;
+    if (e->force_tile) code = e->force_tile;
+    if (e->force_code >= 0) code = e->force_code;   // (launch_code ignores the split bit where it does not apply)
+    if (!(code > 0 && (code & ~kCodeValid) == 0 && tsm::conv_tile_valid(p, code & kCodeTileMask))) code = 0;
+    TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, code));
+    return TSM_OK;
+  }
+  std::vector<int> cands;
+  if (p.kseg_len > 0) {
+    // segmented layers: 64x64 / 32x32 tiles, whole-K or split-K (when the segment sums fit the scratch buffer and
+    // whole-K tiles alone would leave CUs idle or nearly so), and the tail split where it applies
+    const size_t need = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
+    const long tiles64 = (long)((p.M + 63) / 64) * (p.Cout / 64);
+    for (int t : {(int)tsm::kTile64x64, (int)tsm::kTile32x32}) {
+      cands.push_back(t);
+      if (need <= e->partial_elems && tiles64 < 4L * e->n_cu) cands.push_back(t | kCodeSplitK);
+    }
+    int tail_from = 0;
+    if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) cands.push_back((int)tsm::kTile64x64 | kCodeTailK);
+  } else {
+    for (int t = 1; t < tsm::kNumTiles; ++t)
+      if (tsm::conv_tile_valid(p, t)) cands.push_back(t);
+  }
+  float best_ms = 0.f;
+  int best = 0;
+  for (int t : cands) {
+    float ms = 0.f;
+    const int rc = time_best_of(e, s, [&] { return launch_code(p, ks, t); }, &ms);
+    if (rc) return rc;
+    if (best == 0 || ms < best_ms) {
+      best = t;
+      best_ms = ms;
+    }
+  }
+  (*tiles)[idx] = best;
+  return TSM_OK;
+}
+
+// One BasicBlock on nn frames: x -> y through t1 (and idb for the downsample), three generic launches:
+//   [downsample (1x1 at the stride, its own launch),] shift + conv1 (3x3 at the stride, shift fused into its loader,
+//   + ReLU), conv2 (3x3 + identity + ReLU).  None of the Bottleneck fusions applies.
+int Forward::run_basic(size_t k, int nn, float *x, float *y, int hh, int ww) {
+  const Block &blk = e->blocks[k];
+  const std::string &name = blk.name;
+  const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2];
+  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  const float *identity = x;
+  if (blk.down >= 0) {
+    tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, 0, 1, prec);
+    int rcd = conv(blk.down, pd, 1, false);
+    if (rcd) return rcd;
+    identity = idb;
+  }
+  tsm::ConvParams p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, e->cfg.shift_div, prec);
+  int rc1 = conv(blk.conv1, p1, 3, true);
+  if (rc1) return rc1;
+  if (want(name + ".conv1")) return hit(t1, nn, ho, wo, c1.cout);
+  tsm::ConvParams p2 = make_params(c2, t1, identity, y, nn, ho, wo, true, 0, 1, prec);
+  int rc2 = conv(blk.conv2, p2, 3, true);
+  if (rc2) return rc2;
+  if (want(name)) return hit(y, nn, ho, wo, c2.cout);
+  return TSM_OK;
+}
+
+// One Bottleneck of a forward on nn frames, x -> y, as `plan` says.  Its timing slots are the downsample's (which always runs
+// inside conv3's GEMM), conv1's, conv2's and conv3's; a fused launch takes the slot of the first launch it replaces and leaves
+// the others not recorded.
+int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float *y, int hh, int ww) {
+  const Block &blk = e->blocks[k];
+  const std::string &name = blk.name;
+  const int c1out = e->convs[blk.conv1].cout, c2out = e->convs[blk.conv2].cout, c3out = e->convs[blk.conv3].cout;
+  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  BlockLaunches L = block_launches(e, k, nn, x, y, t1, t2, hh, ww);
+  if (blk.down >= 0) skip_slots(e, 1);
+  if (plan.block) {
+    L.pb.reverse = next_dir();
+    TSM_LAUNCH(e, s, tsm::launch_bneck_ws(L.pb, s));
+    skip_slots(e, 2);   // conv2, conv3
+    return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+  }
+  if (plan.front) {
+    L.pfr.reverse = next_dir();
+    TSM_LAUNCH(e, s, tsm::launch_front_s2(L.pfr, s));
+    next_dir();         // (it stands for two launches: conv3 keeps the direction it would have had)
+    skip_slots(e, 1);   // conv2
+  } else {
+    if (plan.conv1_done) {
+      skip_slots(e, 1);   // the previous block's conv3 launch has left this conv1's output in t1
+    } else {
+      int rc1 = conv(blk.conv1, L.p1, 1, false);
+      if (rc1) return rc1;
+    }
+    if (want(name + ".conv1")) return hit(t1, nn, hh, ww, c1out);
+    if (plan.conv23) {
+      L.pf.reverse = next_dir();
+      TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(L.pf, blk.cmid, prec, s));
+      skip_slots(e, 1);   // conv3
+      return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+    }
+    int rc2 = conv(blk.conv2, L.p2, 3, true);
+    if (rc2) return rc2;
+  }
+  if (want(name + ".conv2")) return hit(t2, nn, ho, wo, c2out);
+  if (plan.conv31_next) {
+    L.q.reverse = next_dir();
+    TSM_LAUNCH(e, s, tsm::launch_conv31_fused(L.q, s));
+  } else {
+    int rc3 = conv(blk.conv3, L.p3, 1, false);
+    if (rc3) return rc3;
+  }
+  return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+}
+
+// One Bottleneck of the tuning pass: the candidate codes of conv1, conv2 and conv3 (conv()), and each fused form that can run
+// and that TSM_FUSE_* leaves to the tuner, timed against the tuned launches it replaces (same bits).  Every arm walks as in a
+// forward -- separate launches alternate r1, !r1, r1; a fused launch walks like the first launch it replaces -- so both arms
+// see the producer / consumer cache reuse of a real forward.  The conv3 + next conv1 form of the PREVIOUS block is
+// timed here, once this conv1 is tuned.
+int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
+  const Block &blk = e->blocks[k];
+  std::vector<int> &codes = *tiles;
+  const BlockForms can = fused_forms(e, k, nn, hh, ww, nullptr);
+  BlockLaunches L = block_launches(e, k, nn, x, y, t1, t2, hh, ww);
+  const int r1 = flip ^ 1;   // the walk direction conv() is about to give conv1
+  bool wins = false;
+  int rc = conv(blk.conv1, L.p1, 1, false);
+  if (rc) return rc;
+  L.p1.reverse = r1;
+  if (prev31 >= 0 && e->fuse31 < 0) {   // the previous block's conv3 + this conv1 as one launch (both arms write the same bits)
+    const int conv3 = e->blocks[prev31].conv3, code3 = codes[conv3], code1 = codes[blk.conv1];
+    tsm::ConvParams pc = L.p1;
+    pc.reverse = prev.p3.reverse ^ 1;
+    prev.q.reverse = prev.p3.reverse;
+    rc = fused_wins([&] { return launch_pair(prev.p3, 1, code3, pc, 1, code1); },
+                    [&] { return tsm::launch_conv31_fused(prev.q, s); }, &wins);
+    if (rc) return rc;
+    if (wins) codes[conv3] |= kCodeConv31;
+  }
+  rc = conv(blk.conv2, L.p2, 3, true);
+  if (rc) return rc;
+  L.p2.reverse = r1 ^ 1;
+  if (can.front && e->fuse_front < 0) {   // shift + conv1 + conv2 as one launch (both arms write the same bits to t2)
+    const int code1 = codes[blk.conv1], code2 = codes[blk.conv2];
+    L.pfr.reverse = r1;
+    rc = fused_wins([&] { return launch_pair(L.p1, 1, code1, L.p2, 3, code2); },
+                    [&] { return tsm::launch_front_s2(L.pfr, s); }, &wins);
+    if (rc) return rc;
+    if (wins) codes[blk.conv1] |= kCodeFront;
+  }
+  rc = conv(blk.conv3, L.p3, 1, false);
+  if (rc) return rc;
+  L.p3.reverse = r1;   // (what conv() gave it: r1, !r1, r1)
+  prev31 = can.conv31 ? (int)k : -1;
+  prev = L;
+  const int code1 = codes[blk.conv1], code2 = codes[blk.conv2], code3 = codes[blk.conv3];
+  L.pf.reverse = r1 ^ 1;
+  L.pb.reverse = r1;
+  auto pair = [&] { return launch_pair(L.p2, 3, code2, L.p3, 1, code3); };
+  auto fused23 = [&] { return tsm::launch_conv23_fused(L.pf, blk.cmid, prec, s); };
+  bool use_fused = can.conv23 && e->fuse23 == 1;
+  if (can.conv23 && e->fuse23 < 0) {   // conv2 + conv3 as one launch against the pair
+    rc = fused_wins(pair, fused23, &use_fused);
+    if (rc) return rc;
+    if (use_fused) codes[blk.conv2] |= kCodeConv23;
+  }
+  if (can.block && e->fuse_block < 0) {   // the whole block as one launch against conv1 + the better form of the rest
+    rc = fused_wins([&] {
+      const hipError_t st = launch_code(L.p1, 1, code1);
+      return st != hipSuccess ? st : use_fused ? fused23() : pair();
+    }, [&] { return tsm::launch_bneck_ws(L.pb, s); }, &wins);
+    if (rc) return rc;
+    if (wins) codes[blk.conv1] |= kCodeBlock;
+  }
+  return TSM_OK;
+}
+
 // Enqueue the forward on `s`.  If `stage` is non-null, stop right after that stage and report it.
 int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, float *d_logits,
                 hipStream_t s, const char *stage, Tap *tap) {
   const tsm_config &cfg = e->cfg;
   const int T = cfg.num_segments, n = n_clips * T;
-  const int shiftT = cfg.is_shift ? T : 0;
-  auto want = [&](const std::string &name) { return stage && name == stage; };
-  auto hit = [&](const float *p, int64_t a, int64_t b, int64_t c, int64_t d) {
-    tap->ptr = p; tap->shape[0] = a; tap->shape[1] = b; tap->shape[2] = c; tap->shape[3] = d; tap->hit = true;
-    return TSM_OK;
-  };
-
+  Forward f(e, s, stage, tap);
   // Tile shape per conv layer for this frame count: tuned on first use by timing every valid shape on
   // the real launch (all shapes give bit-identical results: the k order per output does not depend on
   // the tile), then cached.  TSM_AUTOTUNE=0 keeps the static heuristic.
-  std::vector<int> *tiles = nullptr;
-  bool tuning = false;
   if (e->autotune && !stage) {
     auto it = e->tile_cache.find(tile_bucket(n_clips) * T);
     if (it == e->tile_cache.end()) {
       it = e->tile_cache.emplace(tile_bucket(n_clips) * T, std::vector<int>(e->convs.size(), 0)).first;
-      tuning = true;
+      f.tuning = true;
     }
-    tiles = &it->second;
+    f.tiles = &it->second;
   }
-  // A tile code is a ConvTile, plus 0x100 for the split-K form of a segmented layer: one workgroup per (tile, K
-  // segment) writes raw segment sums, splitk_reduce adds them in segment order and applies bias / ReLU --
-  // bit-identical to the unsplit launch.  Every output element accumulates its K in the same order whatever the
-  // tiling, so codes are bit-neutral.
-  auto launch_code = [&](tsm::ConvParams p, int ks, int code) -> hipError_t {
-    p.tile = code & 15;
-    // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
-    // EVERY launch (falling back to the whole-K form, which gives the same bits).
-    if ((code & 0x100) && p.kseg_len > 0 &&
-        (size_t)tsm::conv_num_segments(p) * (size_t)p.M * (size_t)p.Cout <= e->partial_elems) {
-      float *y = p.y;
-      p.ksplit = 1;
-      p.y = e->d_partial;
-      hipError_t st = tsm::launch_conv(p, ks, s);
-      if (st == hipSuccess)
-        st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M, p.Cout, p.bias, nullptr, y, p.relu, s);
-      return st;
-    }
-    // 0x200: the tail split (ConvParams::ksplit = 2) of a segmented 64x64 layer -- the tiles of the last, partly filled round of
-    // resident workgroups (five per CU) as (tile, segment) pieces.  Re-derived from THIS launch's tile count on every launch;
-    // whenever it does not apply the whole-K form runs (same bits).
-    if ((code & 0x200) && (code & 15) == tsm::kTile64x64 && p.kseg_len > 0) {
-      int tail_from = 0;
-      if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) {
-        float *y = p.y;
-        const int mt0 = tail_from / (p.Cout / 64) * 64;
-        p.ksplit = 2;
-        p.tail_from = tail_from;
-        p.ypart = e->d_partial;
-        hipError_t st = tsm::launch_conv(p, ks, s);
-        if (st == hipSuccess)
-          st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M - mt0, p.Cout, p.bias, nullptr,
-                                         y + (size_t)mt0 * p.Cout, p.relu, s);
-        return st;
-      }
-    }
-    return tsm::launch_conv(p, ks, s);
-  };
-  // A code read from TSM_TUNE_CACHE (or forced through the environment) is only trusted after it has been checked
-  // against THIS layer: anything else falls back to the heuristic shape, so a stale, foreign or hand-edited cache
-  // line can only cost speed.
-  auto code_ok = [&](const tsm::ConvParams &p, int code) {
-    return code > 0 && (code & ~0x3F0F) == 0 && tsm::conv_tile_valid(p, code & 15);   // (0x400 / 0x800 / 0x1000 / 0x2000: conv2 + conv3 / the whole block / conv3 + the next block's conv1 / conv1 + the stride-2 conv2 run fused, below)
-  };
-  int flip = 0;   // alternates the tile walk direction of consecutive conv launches (ConvParams::reverse)
-  auto conv = [&](int idx, tsm::ConvParams p, int ks, bool is3x3) -> int {
-    p.reverse = e->zigzag ? (flip ^= 1) : 0;
-    if (!tuning) {
-      int code = tiles ? (*tiles)[idx] : 0;
-      if (e->force_tile) code = e->force_tile;
-      if (e->force_code >= 0) code = e->force_code;   // (launch_code ignores the split bit where it does not apply)
-      if (!code_ok(p, code)) code = 0;
-      TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, code));
-      return TSM_OK;
-    }
-    float best_ms = 0.f;
-    int best = 0;
-    std::vector<int> cands;
-    if (p.kseg_len > 0) {
-      // segmented layers: 64x64 / 32x32 tiles, whole-K or split-K (when the segment sums fit the scratch buffer and
-      // whole-K tiles alone would leave CUs idle or nearly so)
-      const size_t need = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
-      const long tiles64 = (long)((p.M + 63) / 64) * (p.Cout / 64);
-      for (int t : {(int)tsm::kTile64x64, (int)tsm::kTile32x32}) {
-        cands.push_back(t);
-        if (need <= e->partial_elems && tiles64 < 4L * e->n_cu) cands.push_back(t | 0x100);
-      }
-      int tail_from = 0;
-      if (e->tail_split && tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) cands.push_back((int)tsm::kTile64x64 | 0x200);
-    } else {
-      for (int t = 1; t < tsm::kNumTiles; ++t)
-        if (tsm::conv_tile_valid(p, t)) cands.push_back(t);
-    }
-    for (int t : cands) {
-      float ms[4];
-      for (int rep = 0; rep < 4; ++rep) {
-        TSM_HIP(e, hipEventRecord(e->ev0, s));
-        TSM_HIP(e, launch_code(p, ks, t));
-        TSM_HIP(e, hipEventRecord(e->ev1, s));
-        TSM_HIP(e, hipEventSynchronize(e->ev1));
-        TSM_HIP(e, hipEventElapsedTime(&ms[rep], e->ev0, e->ev1));
-      }
-      float m = ms[1] < ms[2] ? ms[1] : ms[2];  // rep 0 warms the caches; best of the other three
-      m = ms[3] < m ? ms[3] : m;
-      if (best == 0 || m < best_ms) {
-        best = t;
-        best_ms = m;
-      }
-    }
-    (*tiles)[idx] = best;
-    return TSM_OK;
-  };
 
   const int prec = e->prec;
   const float *in4 = e->d_in4;
   // The pool-fused stem reads the reference layout ([N, T, 3, H, W] fp32) itself and converts while it stages its patch:
   // no pack launch, no packed copy (TSM_STEM_PLANAR=0 and every other stem form keep the pack; all bit-identical).
-  const bool pool_stem = e->stem_direct && e->stem_pool && !want("conv1");
+  const bool pool_stem = e->stem_direct && e->stem_pool && !f.want("conv1");
   // (8-byte loads of pixel pairs: a caller's pointer that is only 4-byte aligned takes the pack launch, which loads floats)
-  const bool planar = layout == TSM_LAYOUT_NTCHW && e->stem_planar && pool_stem && !want("input") &&
+  const bool planar = layout == TSM_LAYOUT_NTCHW && e->stem_planar && pool_stem && !f.want("input") &&
                       (double)cfg.height * cfg.width * 12.0 < 2.0e9 && (reinterpret_cast<uintptr_t>(d_clips) & 15u) == 0;
   if (layout >= TSM_LAYOUT_NTHWC4 || planar) {
-    in4 = d_clips;  // already packed by tsm_preprocess (or read as it is by the stem): consumed in place
-    if (e->cur_timing) {  // keep the pack's launch slot: reported as "not recorded"
-      e->cur_timing->push_back(nullptr);
-      e->cur_timing->push_back(nullptr);
-    }
+    in4 = d_clips;      // already packed by tsm_preprocess (or read as it is by the stem): consumed in place
+    skip_slots(e, 1);   // the pack
   } else {
     TSM_LAUNCH(e, s, tsm::launch_pack_input(d_clips, e->d_in4, n, cfg.height, cfg.width,
                                             layout == TSM_LAYOUT_NTCHW ? 1 : 0, prec, s));
   }
-  if (want("input"))  // fp32: [n,H,W,4]; bf16 formats: pixel pairs [n,H,ceil(W/2),8]
-    return prec == tsm::kPrecF32 ? hit(in4, n, cfg.height, cfg.width, 4) : hit(in4, n, cfg.height, (cfg.width + 1) / 2, 8);
+  if (f.want("input"))  // fp32: [n,H,W,4]; bf16 formats: pixel pairs [n,H,ceil(W/2),8]
+    return prec == tsm::kPrecF32 ? f.hit(in4, n, cfg.height, cfg.width, 4) : f.hit(in4, n, cfg.height, (cfg.width + 1) / 2, 8);
 
-  float *cur = e->buf[0], *out = e->buf[1], *t1 = e->buf[2], *t2 = e->buf[3], *idb = e->buf[4];
+  float *cur = e->buf[0], *out = e->buf[1], *t1 = f.t1;
   {
     tsm::ConvParams p = make_params(e->convs[0], in4, nullptr, t1, n, cfg.height, cfg.width, true, 0, 1, prec);
     // bf16 formats: dedicated direct-conv stem (LDS-resident input patch), with the max-pool fused behind it unless
@@ -522,317 +808,27 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     if (pool_stem) {
       TSM_LAUNCH(e, s, tsm::launch_stem_pool(in4, e->convs[0].d_w, e->convs[0].d_b, cur, n, cfg.height, cfg.width,
                                               e->convs[0].kp, 1, prec, s, planar ? 1 : 0));
-      if (e->cur_timing) {  // keep the max-pool's launch slot: reported as "not recorded"
-        e->cur_timing->push_back(nullptr);
-        e->cur_timing->push_back(nullptr);
-      }
+      skip_slots(e, 1);   // the max-pool
     } else {
       if (direct) {
         TSM_LAUNCH(e, s, tsm::launch_stem_direct(in4, e->convs[0].d_w, e->convs[0].d_b, t1, n, cfg.height, cfg.width,
                                                   e->convs[0].kp, 1, prec, s));
       } else {
-        int rc0 = conv(0, p, 7, false);
+        int rc0 = f.conv(0, p, 7, false);
         if (rc0) return rc0;
       }
-      if (want("conv1")) return hit(t1, n, e->h1, e->w1, 64);
+      if (f.want("conv1")) return f.hit(t1, n, e->h1, e->w1, 64);
       TSM_LAUNCH(e, s, tsm::launch_maxpool3x3s2(t1, cur, n, e->h1, e->w1, 64, prec, s));
     }
-    if (want("stem")) return hit(cur, n, e->hp, e->wp, 64);
+    if (f.want("stem")) return f.hit(cur, n, e->hp, e->wp, 64);
   }
   int h = e->hp, w = e->wp;
-  bool tapped = false;
-  // conv3 of block k and shift + conv1 of block k + 1 as ONE launch (bf16: tsm::launch_conv31_fused): `t1_ready` says that
-  // the previous block's conv3 launch has already left this block's conv1 output in t1; `prev3` keeps the previous block's
-  // conv3 launch for the tuner's A/B at the head of the next block.
-  bool t1_ready = false;
-  struct Prev3 {
-    bool ok = false;
-    tsm::ConvParams p3{};
-    int conv3_idx = -1;
-  } prev3;
-  auto make_p31 = [&](const tsm::ConvParams &p3, const ConvLayer &c1n, float *t1_out, int nn, int hw) {
-    tsm::Conv31Params q{};
-    q.t2 = p3.x; q.w3 = p3.w; q.bias3 = p3.bias; q.res = p3.res; q.y = p3.y;
-    q.w1 = c1n.d_w; q.bias1 = c1n.d_b; q.t1 = t1_out;
-    q.n_clips = nn / T; q.T = T; q.HW = hw; q.K3 = p3.C; q.C = p3.Cout; q.N1 = c1n.cout;
-    q.fold = shiftT > 0 ? c1n.cp / cfg.shift_div : 0;
-    return q;
-  };
-  // One BasicBlock on nn frames: x -> y through t1 (and idb for the downsample), three generic launches:
-  //   [downsample (1x1 at the stride, its own launch),] shift + conv1 (3x3 at the stride, shift fused into its loader,
-  //   + ReLU), conv2 (3x3 + identity + ReLU).  None of the Bottleneck fusions applies.
-  auto run_basic = [&](size_t k, int nn, float *x, float *y, int hh, int ww) -> int {
-    const Block &blk = e->blocks[k];
-    const std::string &name = blk.name;
-    const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2];
-    const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
-    const float *identity = x;
-    if (blk.down >= 0) {
-      tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, 0, 1, prec);
-      int rcd = conv(blk.down, pd, 1, false);
-      if (rcd) return rcd;
-      identity = idb;
-    }
-    tsm::ConvParams p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, cfg.shift_div, prec);
-    int rc1 = conv(blk.conv1, p1, 3, true);
-    if (rc1) return rc1;
-    if (want(name + ".conv1")) { tapped = true; return hit(t1, nn, ho, wo, c1.cout); }
-    tsm::ConvParams p2 = make_params(c2, t1, identity, y, nn, ho, wo, true, 0, 1, prec);
-    int rc2 = conv(blk.conv2, p2, 3, true);
-    if (rc2) return rc2;
-    if (want(name)) { tapped = true; return hit(y, nn, ho, wo, c2.cout); }
-    return TSM_OK;
-  };
-  // One Bottleneck on nn frames: x -> y through the branch temporaries t1, t2 (and idb for an un-fused downsample).
-  auto run_block = [&](size_t k, int nn, float *x, float *y, int hh, int ww) -> int {
-    const Block &blk = e->blocks[k];
-    const std::string &name = blk.name;
-    const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
-    const bool have_t1 = t1_ready;
-    t1_ready = false;
-    const Prev3 prev = prev3;    // (consumed here whatever path this block takes)
-    prev3.ok = false;
-    const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
-    const float *identity = x;
-    const bool fused = blk.down >= 0 && blk.d_wf != nullptr;
-    if (blk.down >= 0 && !fused) {
-      tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, 0, 1, prec);
-      int rcd = conv(blk.down, pd, 1, false);
-      if (rcd) return rcd;
-      identity = idb;
-    } else if (fused && e->cur_timing) {  // keep the launch slot: reported as "not recorded"
-      e->cur_timing->push_back(nullptr);
-      e->cur_timing->push_back(nullptr);
-    }
-    tsm::ConvParams p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, cfg.shift_div, prec);
-    // The WHOLE block as one launch (bf16 layer1: bneck_ws_kernel -- layer1.1 / layer1.2 with the block input as the
-    // residual, layer1.0 with the fused conv3 + downsample weights): bit 0x800 of conv1's tile code (set by the tuning
-    // pass when it beat conv1 + the best conv2 / conv3 form), or forced / forbidden through TSM_FUSE_BLOCK
-    tsm::BneckParams pb{};
-    const bool block_shape = prec == tsm::kPrecBf16 && blk.stride == 1 && c1.cout == 64 && c2.cin == 64 && c2.cout == 64 && c3.cout == 256 &&
-                             ((blk.down < 0 && c1.cin == 256) || (fused && c1.cin == 64 && e->convs[blk.down >= 0 ? blk.down : 0].cp == 64));
-    const bool can_block = block_shape && e->fuse_block != 0 && tsm::bneck_ws_valid(c1.cin, nn, hh, ww, shiftT, p1.fold) &&
-                           !want(name + ".conv1") && !want(name + ".conv2");
-    if (can_block) {
-      pb.x = x; pb.w1 = c1.d_w; pb.bias1 = c1.d_b; pb.w2 = c2.d_w; pb.bias2 = c2.d_b; pb.y = y;
-      pb.w3 = fused ? blk.d_wf : c3.d_w; pb.bias3 = fused ? blk.d_bf : c3.d_b;
-      pb.cin = c1.cin; pb.N = nn; pb.H = hh; pb.W = ww; pb.T = shiftT; pb.fold = p1.fold;
-    }
-    if (can_block && !tuning && (e->fuse_block == 1 || (tiles && ((*tiles)[blk.conv1] & 0x800)))) {
-      pb.reverse = e->zigzag ? (flip ^= 1) : 0;
-      TSM_LAUNCH_K(e, s, false, tsm::launch_bneck_ws(pb, s));
-      if (e->cur_timing)   // keep conv2's and conv3's launch slots: reported as "not recorded"
-        for (int k = 0; k < 4; ++k) e->cur_timing->push_back(nullptr);
-      if (want(name)) { tapped = true; return hit(y, nn, ho, wo, c3.cout); }
-      return TSM_OK;
-    }
-    // shift + conv1 + the stride-2 conv2 of layer2.0 as ONE launch (bf16: front_s2_kernel; t1 never exists in memory): bit 0x2000
-    // of conv1's tile code (set by the tuning pass below when it beat the two tuned launches), or forced / forbidden through
-    // TSM_FUSE_FRONT
-    tsm::FrontParams pfr{};
-    const bool can_front = prec == tsm::kPrecBf16 && blk.stride == 2 && c1.cin == 256 && c1.cout == 128 && c2.cin == 128 && c2.cout == 128 &&
-                           !have_t1 && e->fuse_front != 0 && tsm::front_s2_valid(nn, hh, ww, shiftT, p1.fold) &&
-                           !want(name + ".conv1");
-    if (can_front) {
-      pfr.x = x; pfr.w1 = c1.d_w; pfr.bias1 = c1.d_b; pfr.w2 = c2.d_w; pfr.bias2 = c2.d_b; pfr.y = t2;
-      pfr.N = nn; pfr.H = hh; pfr.W = ww; pfr.T = shiftT; pfr.fold = p1.fold;
-    }
-    bool did_front = false;
-    if (can_front && !tuning && (e->fuse_front == 1 || (tiles && ((*tiles)[blk.conv1] & 0x2000)))) {
-      pfr.reverse = e->zigzag ? (flip ^= 1) : 0;
-      TSM_LAUNCH_K(e, s, false, tsm::launch_front_s2(pfr, s));
-      flip ^= 1;                                    // (it stands for two launches: conv3 keeps the direction it would have had)
-      if (e->cur_timing) {                          // keep conv2's launch slot: reported as "not recorded"
-        e->cur_timing->push_back(nullptr);
-        e->cur_timing->push_back(nullptr);
-      }
-      did_front = true;
-    }
-    const int r1 = e->zigzag ? (flip ^ 1) : 0;   // the walk direction conv() is about to give conv1 (kept for the tuner's A/B below)
-    if (did_front) {
-    } else if (have_t1) {               // the previous block's conv3 launch computed this conv1 as well: keep the launch slot
-      if (e->cur_timing) {
-        e->cur_timing->push_back(nullptr);
-        e->cur_timing->push_back(nullptr);
-      }
-    } else {
-      int rc1 = conv(blk.conv1, p1, 1, false);
-      if (rc1) return rc1;
-    }
-    if (tuning && prev.ok && e->fuse31 < 0) {
-      // conv3 of the previous block + this conv1 as one launch against the two tuned launches, same protocol as the other
-      // fused forms (both arms rewrite the same bits into the previous block's output and into t1, so re-running is harmless)
-      tsm::Conv31Params q = make_p31(prev.p3, c1, t1, nn, hh * ww);
-      if (tsm::conv31_valid(q)) {
-        const int code3 = (*tiles)[prev.conv3_idx], code1 = (*tiles)[blk.conv1];
-        tsm::ConvParams pa = prev.p3, pc = p1;
-        pc.reverse = e->zigzag ? (pa.reverse ^ 1) : 0;
-        q.reverse = pa.reverse;
-        float pair_ms = 0.f, one_ms = 0.f, ms[4];
-        for (int arm = 0; arm < 2; ++arm) {
-          for (int rep = 0; rep < 4; ++rep) {
-            TSM_HIP(e, hipEventRecord(e->ev0, s));
-            if (arm == 0) {
-              TSM_HIP(e, launch_code(pa, 1, code3));
-              TSM_HIP(e, launch_code(pc, 1, code1));
-            } else {
-              TSM_HIP(e, tsm::launch_conv31_fused(q, s));
-            }
-            TSM_HIP(e, hipEventRecord(e->ev1, s));
-            TSM_HIP(e, hipEventSynchronize(e->ev1));
-            TSM_HIP(e, hipEventElapsedTime(&ms[rep], e->ev0, e->ev1));
-          }
-          (arm == 0 ? pair_ms : one_ms) = std::min(ms[1], std::min(ms[2], ms[3]));
-        }
-        if (one_ms < pair_ms) (*tiles)[prev.conv3_idx] |= 0x1000;
-      }
-    }
-    if (!did_front && want(name + ".conv1")) { tapped = true; return hit(t1, nn, hh, ww, c1.cout); }
-    tsm::ConvParams p2 = make_params(c2, t1, nullptr, t2, nn, hh, ww, true, 0, 1, prec);
-    // conv2 + conv3 + residual in one kernel where the block is eligible: bit 0x400 of conv2's tile code (set by the
-    // tuning pass when the fused launch beat the two separate ones), or forced / forbidden through TSM_FUSE_CONV23
-    tsm::Fused23Params pf{};
-    const bool ws23 = prec == tsm::kPrecBf16 && blk.cmid == 64 && tsm::conv23_ws_valid(nn, hh, ww);
-    const bool can_fuse = (blk.d_w3f != nullptr || ws23) && e->fuse23 != 0 && !want(name + ".conv2");
-    if (can_fuse) {
-      pf.x = t1; pf.w2 = c2.d_w; pf.bias2 = c2.d_b; pf.w3f = ws23 ? c3.d_w : blk.d_w3f; pf.bias3 = c3.d_b; pf.res = identity; pf.y = y;
-      pf.N = nn; pf.H = hh; pf.W = ww; pf.M = nn * hh * ww; pf.kseg_len = c2.kseg;
-      pf.reverse = e->zigzag ? (flip ^ 1) : 0;
-    }
-    if (can_fuse && !tuning && (e->fuse23 == 1 || (tiles && ((*tiles)[blk.conv2] & 0x400)))) {
-      TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(pf, blk.cmid, prec, s));
-      flip ^= 1;
-      if (e->cur_timing) {  // keep conv3's launch slot: reported as "not recorded"
-        e->cur_timing->push_back(nullptr);
-        e->cur_timing->push_back(nullptr);
-      }
-      if (want(name)) { tapped = true; return hit(y, nn, ho, wo, c3.cout); }
-      return TSM_OK;
-    }
-    if (!did_front) {
-      int rc2 = conv(blk.conv2, p2, 3, true);
-      if (rc2) return rc2;
-      if (tuning && can_front && e->fuse_front < 0) {
-        // the one launch against the two tuned ones, same protocol as the other fused forms (both arms write the same bits to t2)
-        const int code1 = (*tiles)[blk.conv1], code2 = (*tiles)[blk.conv2];
-        tsm::ConvParams pa = p1, pc = p2;
-        pa.reverse = r1;
-        pc.reverse = e->zigzag ? (r1 ^ 1) : 0;
-        pfr.reverse = r1;
-        float pair_ms = 0.f, one_ms = 0.f, ms[4];
-        for (int arm = 0; arm < 2; ++arm) {
-          for (int rep = 0; rep < 4; ++rep) {
-            TSM_HIP(e, hipEventRecord(e->ev0, s));
-            if (arm == 0) {
-              TSM_HIP(e, launch_code(pa, 1, code1));
-              TSM_HIP(e, launch_code(pc, 3, code2));
-            } else {
-              TSM_HIP(e, tsm::launch_front_s2(pfr, s));
-            }
-            TSM_HIP(e, hipEventRecord(e->ev1, s));
-            TSM_HIP(e, hipEventSynchronize(e->ev1));
-            TSM_HIP(e, hipEventElapsedTime(&ms[rep], e->ev0, e->ev1));
-          }
-          (arm == 0 ? pair_ms : one_ms) = std::min(ms[1], std::min(ms[2], ms[3]));
-        }
-        if (one_ms < pair_ms) (*tiles)[blk.conv1] |= 0x2000;
-      }
-    }
-    if (want(name + ".conv2")) { tapped = true; return hit(t2, nn, ho, wo, c2.cout); }
-    tsm::ConvParams p3 = make_params(c3, t2, fused ? nullptr : identity, y, nn, ho, wo, true, 0, 1, prec);
-    if (fused) {
-      const ConvLayer &cd = e->convs[blk.down];
-      p3.w = blk.d_wf; p3.bias = blk.d_bf; p3.Kp = blk.kpf; p3.K1 = c3.kp; p3.kseg_len = blk.ksegf;
-      p3.x2 = x; p3.C2 = cd.cp; p3.Hi2 = hh; p3.Wi2 = ww; p3.stride2 = blk.stride;
-    }
-    // conv3 + residual of this block and shift + conv1 of the NEXT block as one launch (bf16; this block without a downsample
-    // branch -- the next one may be the first of a stage: its conv1 is a stride-1 1x1 on this block's output either way):
-    // bit 0x1000 of conv3's tile code
-    // (set by the tuning pass at the head of the next block), or forced / forbidden through TSM_FUSE_C3C1
-    bool did31 = false;
-    if (prec == tsm::kPrecBf16 && !fused && blk.down < 0 && k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0 &&
-        e->fuse31 != 0) {
-      const ConvLayer &c1n = e->convs[e->blocks[k + 1].conv1];
-      tsm::Conv31Params q = make_p31(p3, c1n, t1, nn, ho * wo);
-      if (tsm::conv31_valid(q)) {
-        if (tuning) {
-          prev3.ok = true;
-          prev3.conv3_idx = blk.conv3;
-        } else if (e->fuse31 == 1 || (tiles && ((*tiles)[blk.conv3] & 0x1000))) {
-          q.reverse = e->zigzag ? (flip ^= 1) : 0;
-          TSM_LAUNCH_K(e, s, false, tsm::launch_conv31_fused(q, s));
-          did31 = true;
-          t1_ready = true;
-        }
-      }
-    }
-    if (!did31) {
-      const int r3 = e->zigzag ? (flip ^ 1) : 0;
-      int rc3 = conv(blk.conv3, p3, 1, false);
-      if (rc3) return rc3;
-      if (prev3.ok) {
-        prev3.p3 = p3;
-        prev3.p3.reverse = r3;
-      }
-    }
-    if (tuning && ((can_fuse && e->fuse23 < 0) || (can_block && e->fuse_block < 0))) {
-      // Fused forms against the tuned separate launches (same bits), under ONE protocol: four repetitions, the first
-      // discarded, best of the other three, and a sequence of launches timed back to back inside one event bracket (so
-      // the inter-kernel boundaries and each kernel's cold start on its producer's output are priced, as in a forward).
-      const int code1 = (*tiles)[blk.conv1], code2 = (*tiles)[blk.conv2], code3 = (*tiles)[blk.conv3];
-      // ... and with the tile walk directions of a forward (conv() sets `reverse` on its own copy only): separate launches
-      // alternate r1, !r1, r1; the fused conv2 + conv3 walks like conv2, the whole block like conv1 -- both arms of every
-      // comparison then see the producer / consumer cache reuse they would get in a real forward
-      p1.reverse = r1;
-      p2.reverse = e->zigzag ? (r1 ^ 1) : 0;
-      p3.reverse = r1;
-      pf.reverse = p2.reverse;
-      pb.reverse = r1;
-      auto best_of = [&](auto &&launch, float *out_ms) -> int {
-        float ms[4];
-        for (int rep = 0; rep < 4; ++rep) {
-          TSM_HIP(e, hipEventRecord(e->ev0, s));
-          TSM_HIP(e, launch());
-          TSM_HIP(e, hipEventRecord(e->ev1, s));
-          TSM_HIP(e, hipEventSynchronize(e->ev1));
-          TSM_HIP(e, hipEventElapsedTime(&ms[rep], e->ev0, e->ev1));
-        }
-        *out_ms = std::min(ms[1], std::min(ms[2], ms[3]));
-        return TSM_OK;
-      };
-      auto pair = [&]() -> hipError_t {
-        hipError_t st = launch_code(p2, 3, code2);
-        return st != hipSuccess ? st : launch_code(p3, 1, code3);
-      };
-      bool use_fused = can_fuse && e->fuse23 == 1;
-      if (can_fuse && e->fuse23 < 0) {       // conv2 + conv3 as one kernel against the pair
-        float pair_ms = 0.f, fused_ms = 0.f;
-        int rcp = best_of(pair, &pair_ms);
-        if (rcp) return rcp;
-        rcp = best_of([&]() -> hipError_t { return tsm::launch_conv23_fused(pf, blk.cmid, prec, s); }, &fused_ms);
-        if (rcp) return rcp;
-        use_fused = fused_ms < pair_ms;
-        if (use_fused) (*tiles)[blk.conv2] |= 0x400;
-      }
-      if (can_block && e->fuse_block < 0) {   // the whole block as one kernel against conv1 + the better form of the rest
-        float rest_ms = 0.f, block_ms = 0.f;
-        int rcp = best_of([&]() -> hipError_t {
-          hipError_t st = launch_code(p1, 1, code1);
-          if (st != hipSuccess) return st;
-          return use_fused ? tsm::launch_conv23_fused(pf, blk.cmid, prec, s) : pair();
-        }, &rest_ms);
-        if (rcp) return rcp;
-        rcp = best_of([&]() -> hipError_t { return tsm::launch_bneck_ws(pb, s); }, &block_ms);
-        if (rcp) return rcp;
-        if (block_ms < rest_ms) (*tiles)[blk.conv1] |= 0x800;
-      }
-    }
-    if (want(name)) { tapped = true; return hit(y, nn, ho, wo, c3.cout); }
-    return TSM_OK;
-  };
+  const std::vector<BlockPlan> plan = f.tuning ? std::vector<BlockPlan>() : plan_forward(e, f.tiles, n, stage);
   for (size_t k = 0; k < e->blocks.size(); ++k) {
-    int rc = e->blocks[k].conv3 < 0 ? run_basic(k, n, cur, out, h, w) : run_block(k, n, cur, out, h, w);
-    if (rc || tapped) return rc;
+    const int rc = e->blocks[k].conv3 < 0 ? f.run_basic(k, n, cur, out, h, w)
+                   : f.tuning            ? f.tune_block(k, n, cur, out, h, w)
+                                         : f.run_block(k, plan[k], n, cur, out, h, w);
+    if (rc || f.tapped) return rc;
     std::swap(cur, out);
     h = (h + 2 - 3) / e->blocks[k].stride + 1;
     w = (w + 2 - 3) / e->blocks[k].stride + 1;
@@ -944,7 +940,6 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   e->prec = cfg->dtype == TSM_DTYPE_BF16X3 ? tsm::kPrecBf16x3
             : cfg->dtype == TSM_DTYPE_BF16 ? tsm::kPrecBf16 : tsm::kPrecF32;
   if (const char *at = getenv("TSM_AUTOTUNE")) e->autotune = atoi(at) != 0;
-  if (const char *fd = getenv("TSM_FUSE_DOWNSAMPLE")) e->fuse_down = atoi(fd) != 0;
   if (const char *sd = getenv("TSM_STEM_DIRECT")) e->stem_direct = atoi(sd) != 0;
   if (const char *sp = getenv("TSM_STEM_POOL")) e->stem_pool = atoi(sp) != 0;
   if (const char *pl = getenv("TSM_STEM_PLANAR")) e->stem_planar = atoi(pl) != 0;
@@ -954,8 +949,6 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   if (const char *fb = getenv("TSM_FUSE_BLOCK")) e->fuse_block = atoi(fb) != 0;
   if (const char *f31 = getenv("TSM_FUSE_C3C1")) e->fuse31 = atoi(f31) != 0;
   if (const char *ff = getenv("TSM_FUSE_FRONT")) e->fuse_front = atoi(ff) != 0;
-  if (const char *zz = getenv("TSM_ZIGZAG")) e->zigzag = atoi(zz) != 0;
-  if (const char *ts = getenv("TSM_TAIL_SPLIT")) e->tail_split = atoi(ts) != 0;
   // TSM_TUNE_CACHE=<file> names the tune cache; unset: a per-user default ($XDG_CACHE_HOME or $HOME/.cache, then
   // tsm_hip/tune_cache.txt), so that the second process on a machine pays no tuning pass; "", "0" or "off" disables it.
   {
@@ -981,14 +974,14 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
     hipDeviceProp_t prop;
     // (the build id -- csrc/, per-file options AND the build's extra definitions -- : codes of another build of the library
     //  are still SAFE, every code is validated against its layer at launch, but they were timed on other kernels, so they
-    //  are not reused; the same goes for everything else that changes the timings: CU count, walk order, stem forms)
+    //  are not reused; the same goes for everything else that changes the timings: CU count, fused forms, stem forms)
     e->tune_sig = "abi" + std::to_string(TSM_ABI_VERSION) + " build " TSM_BUILD_ID " " +
                   (hipGetDeviceProperties(&prop, cfg->device_id) == hipSuccess ? std::string(prop.gcnArchName) : "?") +
                   " cu" + std::to_string(e->n_cu) +
                   " T" + std::to_string(cfg->num_segments) + " " + std::to_string(cfg->height) + "x" +
                   std::to_string(cfg->width) + " dtype" + std::to_string(cfg->dtype) + " shift" +
-                  std::to_string(cfg->is_shift ? cfg->shift_div : 0) + " fuse" + std::to_string(e->fuse_down ? 1 : 0) + "/" + std::to_string(e->fuse23) + "/" + std::to_string(e->fuse_block) + "/" + std::to_string(e->fuse31) + "/" + std::to_string(e->fuse_front) +
-                  " zz" + std::to_string(e->zigzag ? 1 : 0) + " tk" + std::to_string(e->tail_split ? 1 : 0) + " stem" + std::to_string(e->stem_direct ? 1 : 0) +
+                  std::to_string(cfg->is_shift ? cfg->shift_div : 0) + " fuse" + std::to_string(e->fuse23) + "/" + std::to_string(e->fuse_block) + "/" + std::to_string(e->fuse31) + "/" + std::to_string(e->fuse_front) +
+                  " stem" + std::to_string(e->stem_direct ? 1 : 0) +
                   std::to_string(e->stem_pool ? 1 : 0) + std::to_string(e->stem_planar ? 1 : 0);
     e->tune_sig_base = e->tune_sig.size();   // (tsm_set_backbone appends " r<depth>" for a backbone other than R50)
   }
@@ -1084,7 +1077,7 @@ int tsm_finalize(tsm_engine *e) {
   }
   // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
   for (Block &blk : e->blocks) {
-    if (blk.down < 0 || !e->fuse_down || blk.conv3 < 0) continue;   // (Bottlenecks only)
+    if (blk.down < 0 || blk.conv3 < 0) continue;   // (Bottlenecks only)
     const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
     blk.kpf = c3.kp + cd.kp;
     blk.ksegf = segment_len(blk.kpf, e->prec);
@@ -1318,33 +1311,29 @@ int tsm_layer_times(tsm_engine *e, int32_t forward_index, float *ms_out, int32_t
 
 int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t cap, int32_t *n_out) {
   if (!e || !tiles_out || !n_out) return TSM_ERR_INVALID_ARG;
-  // launch order: stem, then per block [downsample,] conv1, conv2, conv3 (Bottleneck) / [downsample,] conv1, conv2 (BasicBlock)
-  std::vector<int> order{0};
-  for (const Block &b : e->blocks) {
-    if (b.down >= 0) order.push_back(b.down);
-    order.push_back(b.conv1);
-    order.push_back(b.conv2);
-    if (b.conv3 >= 0) order.push_back(b.conv3);
-  }
-  *n_out = (int32_t)order.size();
-  if ((int)order.size() > cap) return fail(e, TSM_ERR_CAPACITY, "tiles_out too small");
+  // Report what RUNS: a fusion bit only where an n_clips forward runs that form (its plan), whatever a hand-edited or
+  // bucket-shared code says; a form forced through TSM_FUSE_* = 1 is not a tuner choice and carries no bit.
+  std::vector<int> codes(e->convs.size(), 0);
   auto it = e->tile_cache.find(tile_bucket(n_clips) * e->cfg.num_segments);
-  for (size_t i = 0; i < order.size(); ++i) tiles_out[i] = it == e->tile_cache.end() ? 0 : it->second[order[i]];
-  // Report what RUNS: a block whose conv2 carries 0x400 (conv2 + conv3 fused) or whose conv1 carries 0x800 (the whole block)
-  // never reaches the conv3 + next-conv1 launch, whatever bit 0x1000 of its conv3 code says (a forced or hand-edited code; the
-  // tuner itself times 0x1000 only on blocks that run conv3 as a launch of its own)  (ADVICE r4).
   if (it != e->tile_cache.end()) {
-    size_t i = 1;
-    for (const Block &b : e->blocks) {
-      if (b.down >= 0) ++i;
-      if (b.conv3 < 0) {   // BasicBlock: no fused forms
-        i += 2;
-        continue;
-      }
-      if ((tiles_out[i] & 0x800) || (tiles_out[i + 1] & 0x400)) tiles_out[i + 2] &= ~0x1000;
-      i += 3;
+    const std::vector<BlockPlan> plan = plan_forward(e, &it->second, n_clips * e->cfg.num_segments, nullptr);
+    for (size_t i = 0; i < codes.size(); ++i) codes[i] = it->second[i] & ~kCodeFused;
+    for (size_t k = 0; k < e->blocks.size(); ++k) {
+      const Block &b = e->blocks[k];
+      const BlockPlan &p = plan[k];
+      codes[b.conv1] |= it->second[b.conv1] & ((p.block ? kCodeBlock : 0) | (p.front ? kCodeFront : 0));
+      if (p.conv23) codes[b.conv2] |= it->second[b.conv2] & kCodeConv23;
+      if (p.conv31_next) codes[b.conv3] |= it->second[b.conv3] & kCodeConv31;
     }
   }
+  // launch order: stem, then per block [downsample,] conv1, conv2, conv3 (Bottleneck) / [downsample,] conv1, conv2 (BasicBlock)
+  std::vector<int> order{0};
+  for (const Block &b : e->blocks)
+    for (int ci : {b.down, b.conv1, b.conv2, b.conv3})
+      if (ci >= 0) order.push_back(ci);
+  *n_out = (int32_t)order.size();
+  if ((int)order.size() > cap) return fail(e, TSM_ERR_CAPACITY, "tiles_out too small");
+  for (size_t i = 0; i < order.size(); ++i) tiles_out[i] = codes[order[i]];
   return TSM_OK;
 }
 

@@ -28,7 +28,7 @@ inline int segment_len(int kp, int prec) {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// The tail split of a segmented 64x64 launch (ConvParams::ksplit = 2, tile code bit 0x200).  The conv_igemm SEG kernel keeps
+// The tail split of a segmented 64x64 launch (ConvParams::ksplit = 2, tile code bit kCodeTailK).  The conv_igemm SEG kernel keeps
 // `wg_per_cu` (five) workgroups per CU resident, so a launch of ntm x ntn tiles runs in rounds of wg_per_cu * n_cu; when the last
 // round is less than ~85 % full its tiles -- rounded DOWN to whole rows of tiles, so that the tail is a contiguous range of output
 // rows -- run as (tile, K segment) pieces.  Returns the first tail tile (a multiple of ntn, in (0, ntm * ntn)), or 0 when the
@@ -166,8 +166,21 @@ inline void pack_w3_fragments_split(const float *w3p, int cmid, std::vector<floa
         }
 }
 
+// A layer's tile code (TSM_TUNE_CACHE lines, tsm_conv_tiles): a ConvTile in the low bits, plus flags.  The fusion bits sit on the
+// code of the first conv they replace and say that the fused form was chosen; it runs only where it can (tsm_engine.hip,
+// plan_forward).
+constexpr int kCodeTileMask = 0xF;     // the ConvTile
+constexpr int kCodeSplitK = 0x100;     // split-K form of a segmented fp32 layer
+constexpr int kCodeTailK = 0x200;      // tail split of a segmented 64x64 layer (ConvParams::ksplit = 2)
+constexpr int kCodeConv23 = 0x400;     // on conv2: conv2 + conv3 + residual as one launch
+constexpr int kCodeBlock = 0x800;      // on conv1: the whole Bottleneck as one launch
+constexpr int kCodeConv31 = 0x1000;    // on conv3: conv3 + the next block's shift + conv1 as one launch
+constexpr int kCodeFront = 0x2000;     // on conv1: shift + conv1 + the block's stride-2 conv2 as one launch
+constexpr int kCodeFused = kCodeConv23 | kCodeBlock | kCodeConv31 | kCodeFront;
+constexpr int kCodeValid = kCodeTileMask | kCodeSplitK | kCodeTailK | kCodeFused;   // every bit a code may carry
+
 // One line of a TSM_TUNE_CACHE file: "<signature>|<bucket>|c0,c1,...".  Succeeds only when the line starts with
-// `want`, holds exactly codes->size() integers and each is a ConvTile below `num_tiles`, optionally | 0x100 (split-K) | 0x400 (block runs conv2 + conv3 fused) | 0x800 (the whole block runs as one launch) | 0x1000 (conv3 also runs the next block's conv1) | 0x2000 (conv1 also runs the block's stride-2 conv2).
+// `want`, holds exactly codes->size() integers and each is a ConvTile below `num_tiles` with no bit outside kCodeValid.
 // Anything else (foreign keys, truncated lines, garbage, overlong numbers) leaves *codes untouched.
 inline bool parse_tune_line(const char *line, const std::string &want, int num_tiles, std::vector<int> *codes) {
   if (strncmp(line, want.c_str(), want.size()) != 0) return false;
@@ -177,7 +190,7 @@ inline bool parse_tune_line(const char *line, const std::string &want, int num_t
     char *end = nullptr;
     const long v = strtol(q, &end, 10);
     if (end == q) return false;
-    if (v < 0 || (v & ~0x3F0FL) != 0 || (int)(v & 15) >= num_tiles) return false;
+    if (v < 0 || (v & ~(long)kCodeValid) != 0 || (int)(v & kCodeTileMask) >= num_tiles) return false;
     got.push_back((int)v);
     if (*end == ',') q = end + 1;
     else if (*end == '\n' || *end == 0) q = end;

@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Throughput bench for the TSM-R50 clip-inference hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what its headline figure needs and nothing more: it builds the library if it is stale, tunes and warms up
+one engine, times the K steps and prints the line (with `step_ms`, `config`, `build_id`, `tune` and the part of `roofline`
+that the timed steps' own launch events give).  --full adds everything else the line can carry: the other precision mode
+(`alt_precision`), the `config5` leg, `cpu_baseline`, the `parity` check of the timed logits, the whole-forward figures of
+`roofline` and, with a collective, the `exchange` object; the --no-* options drop single legs of a --full run.  Given
+--dump-outputs, a plain run also times the other modes, for their outputs alone (see below).
 
 A "step" is one pass of the hot path (HIP engine forward, tsm_forward through the C ABI) over one
 batch of 32 synthetic clips [32, 8, 3, 224, 224] fp32 that is already resident in HBM (BASELINE.json
@@ -12,7 +19,7 @@ clips are independent units so every rank runs its own batch (weak scaling) and 
 RCCL all-gather of per-clip logits, which is inside the timed step.  All ranks share one tile-tuning pass
 (TSM_TUNE_CACHE: rank 0 tunes, the others read).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+Extra objects on the line (those a plain run leaves out are marked --full):
   roofline      the dominant kernel is the kernel the engine's autotuner runs the 3x3 convolutions of
                 layer2..layer4 on (13 launches per forward, one third of the forward's time; `kernel_of` maps the
                 tuner's tile code to the kernel name rocprofv3 prints; if the tuner split them over several
@@ -21,28 +28,33 @@ Extra objects on the line:
                 is a different kernel and is priced with both convs; `achieved` = work / the launches' average duration, measured with HIP-event
                 pairs recorded around each launch on the launch stream during the timed steps
                 (tsm_set_layer_timing / tsm_layer_times), against the exact-fp32 MFMA peak (157.3 TFLOP/s,
-                MI355X_MICROARCH.md).  `forward_achieved` / `forward_frac` price the whole forward
-                (65.395 GFLOP/clip, SURVEY.md section 8d, all 53 conv launches + pool/head kernels).
-  cpu_baseline  the CPU oracle (oracle/tsm_oracle.py, torch-CPU fp32, the same graph; the reference's
+                MI355X_MICROARCH.md).  `forward_achieved` / `forward_frac` (--full) price the whole forward
+                (65.395 GFLOP/clip, SURVEY.md section 8d, all 53 conv launches + pool/head kernels), timed by up to 10
+                more forwards after the timed steps.
+  alt_precision (--full) the same engine, inputs, steps and warm-up in the other precision mode (bf16x3 behind f32).
+  cpu_baseline  (--full) the CPU oracle (oracle/tsm_oracle.py, torch-CPU fp32, the same graph; the reference's
                 own onnxruntime CPU path cannot run here) timed on this box's host cores, batch 1 like
                 the reference (utils/inference_count.py:272), bounded to ~15 s; median (`value`) and best, with the CPU
                 model, the load average and torch's thread count beside them (a shared host: the figure moves with them)
-  config5       BASELINE.json configs[4] behind the headline (default command only): TSM_DTYPE_BF16, T = 16, 256 x 256, 64 clips
-                per GPU through the same call, with its own tuning, timed steps, `roofline` (dominant kernel against the
-                dense bf16 MFMA peak, forward_frac, PMC traffic, forward HBM rate) and `parity` (bf16-storage oracle); the
-                headline fields stay those of configs[1].  --no-config5 skips it (profiling runs).
+  config5       (--full) BASELINE.json configs[4] behind the headline (default shape only): TSM_DTYPE_BF16, T = 16,
+                256 x 256, 64 clips per GPU through the same call, with its own tuning, timed steps, `roofline` (dominant
+                kernel against the dense bf16 MFMA peak, forward_frac, PMC traffic, forward HBM rate) and `parity`
+                (bf16-storage oracle); the headline fields stay those of configs[1].  --no-config5 skips it.
   build_id      tsm_build_id() of the library that ran == the sha of the source tree it was built from (the loader refuses
                 any other); `tune`: where the tile choices came from
-  parity        the logits the TIMED steps produced (the output of the last timed step; what
+  parity        (--full) the logits the TIMED steps produced (the output of the last timed step; what
                 utils/inference_count.py:273-275 would hand to the counter), checked on rank 0 AFTER the timed region
                 against the CPU oracle on a few of the timed clips: max |err| / logit scale against the bar of the parity
                 tests (fp32 / split-bf16: rtol 1e-3 + 1e-5 of the scale, the fp32 oracle; bf16: 1e-2 of the scale and
                 the same arg-max, the bf16-storage oracle).  A failed check makes the run fail, not just the line.
+  exchange      (--full, collective runs) the all-gather's back-to-back latency and every rank's step and forward medians.
 
 --dump-outputs DIR (rank 0) writes what each timed mode's LAST timed step returned -- the float32 logits a caller of the
 step receives, [B, 12] (with a collective: the all-gathered [world * B, 12]) -- as DIR/logits.npy (headline),
-DIR/alt_precision_logits.npy and DIR/config5_logits.npy, named after the objects of the line.  Weights and clips are
-seeded, so the same arguments give the same inputs on every run and two builds can be compared output for output.
+DIR/alt_precision_logits.npy and DIR/config5_logits.npy, named after the objects of a --full line.  A plain run writes the
+same files: it runs the alt_precision and config5 modes for them (without their objects on the line, parity checks or
+extra forwards).  Weights and clips are seeded, so the same arguments give the same inputs on every run and two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -272,7 +284,10 @@ def kernel_of(tile, dtype, cmid, stride=1):
         main.replace('w8', '').replace('x', ', '), waves, prec_id, 'true' if dtype == 'f32' else 'false'), False
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with the legs a run skips already folded into the --no-* flags: a plain run keeps the headline
+    alone (and, given --dump-outputs, the other timed modes whose outputs it writes), --full keeps what the flags and the
+    headline's shape allow."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -293,7 +308,10 @@ def main():
                          'TSM_DTYPE_BF16 as the headline itself (sets --dtype/--batch/--segments/--size, no alt / config5 / CPU legs)')
     ap.add_argument('--dump-outputs', metavar='DIR',
                     help='write the logits of the last timed step of every timed mode to DIR/<name>.npy (float32, rank 0)')
-    args = ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: the other precision mode, the config5 leg, the CPU '
+                         'baseline, the oracle parity check, the whole-forward roofline figures and the exchange latency')
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     if args.config == 5:
@@ -302,7 +320,17 @@ def main():
     headline_defaults = (args.dtype, args.batch, args.segments, args.size) == ('f32', 32, 8, 224)
     if not headline_defaults:
         args.no_config5 = True       # the extra leg rides behind the driver's default command only
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = True
+        if not args.dump_outputs:
+            # --dump-outputs writes the last timed step of every timed mode: with it, the other modes still run for
+            # their outputs (the line stays the headline's)
+            args.no_alt = args.no_config5 = True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # the driver's command form for N > 1 may come without a launcher: start the ranks ourselves, BEFORE torch
         sys.exit(self_launch(args.gpus))
@@ -428,18 +456,22 @@ def main():
         res['per_launch'] = [eng.layer_times_ms(i) for i in range(n_timed)] if want_launch_times else []
         res['step_ms'] = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
         eng.set_layer_timing(0)
-        # Whole-forward kernel time (one HIP-event pair around all launches of a forward), outside the
-        # wall-clock region because reading it synchronises.
-        fwd_ev_ms = []
-        for _ in range(min(args.steps, 10)):
-            eng.forward_device(clips, out=logits)
-            fwd_ev_ms.append(eng.last_forward_ms)
-        torch.cuda.synchronize()
+        res['fwd_ms'] = None
+        if args.full:
+            # Whole-forward kernel time (one HIP-event pair around all launches of a forward), outside the
+            # wall-clock region because reading it synchronises.
+            fwd_ev_ms = []
+            for _ in range(min(args.steps, 10)):
+                eng.forward_device(clips, out=logits)
+                fwd_ev_ms.append(eng.last_forward_ms)
+            torch.cuda.synchronize()
+            res['fwd_ms'] = sorted(fwd_ev_ms)[len(fwd_ev_ms) // 2]
         t_max = torch.tensor([elapsed], device='cuda')
         if collective:
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+        if collective and args.full:
             sm = res['step_ms']
-            mine = torch.tensor([[sm[len(sm) // 2], sorted(fwd_ev_ms)[len(fwd_ev_ms) // 2]]], device='cuda')
+            mine = torch.tensor([[sm[len(sm) // 2], res['fwd_ms']]], device='cuda')
             res['rank_ms'] = all_gather_logits(mine).cpu().tolist()      # [world][step median, forward-kernel median]
             # the exchange step on its own ("all-gather us"), outside the timed region
             torch.cuda.synchronize()
@@ -452,17 +484,14 @@ def main():
         res['tiles'] = eng.conv_tiles(B)
         eng.close()
         res['elapsed'] = float(t_max.item())
-        res['fwd_ms'] = sorted(fwd_ev_ms)[len(fwd_ev_ms) // 2]
         return res
 
     def roofline_of(res):
         """The `roofline` object of one timed mode: the dominant kernel (the instantiation that runs most of the 3x3 time of
-        layer2-4) priced by its algorithmic flops and live launch durations, the whole forward beside it, PMC traffic from
-        the committed stamped passes."""
+        layer2-4) priced by its algorithmic flops and live launch durations, PMC traffic from the committed stamped passes,
+        and in a --full run the whole forward beside it."""
         T, H, W, B = res['geom']
         dtype, tiles, per_launch, fwd_ms = res['dtype'], res['tiles'], res['per_launch'], res['fwd_ms']
-        gflop = flops_per_clip(T, H, W) / 1e9
-        fwd_achieved = gflop * B / fwd_ms  # GFLOP / ms == TFLOP/s
         frames = B * T
         table = {r['name']: r for r in layer_table(H, W)}
         dom = [r for r in table.values() if r['k'] == 3 and r['s'] >= 1 and not r['name'].startswith('layer1.')]
@@ -502,10 +531,13 @@ def main():
                              len(dom_ms) // len(per_launch)),
                 'gflop_per_launch': round(dom_gflop, 3), 'avg_launch_ms': round(dom_avg_ms, 4),
                 'launches_timed': len(dom_ms),
-                'peak_name': peak_name,
-                'forward_achieved': round(fwd_achieved, 2),
-                'forward_frac': round(fwd_achieved / peak, 4),
-                'forward_gflop': round(gflop * B, 3), 'forward_kernel_ms': round(fwd_ms, 4)}
+                'peak_name': peak_name}
+        if fwd_ms is None:
+            return roof
+        gflop = flops_per_clip(T, H, W) / 1e9
+        fwd_achieved = gflop * B / fwd_ms  # GFLOP / ms == TFLOP/s
+        roof.update({'forward_achieved': round(fwd_achieved, 2), 'forward_frac': round(fwd_achieved / peak, 4),
+                     'forward_gflop': round(gflop * B, 3), 'forward_kernel_ms': round(fwd_ms, 4)})
         if traffic_entry and traffic_entry.get('forward_hbm_bytes'):
             # whole-forward HBM rate from the committed PMC passes (bytes) over the live forward time: the second
             # roofline SURVEY 8d asks for beside the MFMA one (matters for the bf16 formats)
@@ -558,7 +590,6 @@ def main():
         elapsed = main_res['elapsed']
         clips_total = B * world * args.steps
         value = clips_total / elapsed
-        gflop = flops_per_clip(T, H, W) / 1e9
         sm = main_res['step_ms']
         if rehearsal:
             parallelism = (f'REHEARSAL: {world} ranks sharing cuda:0, gloo all-gather through host memory -- control flow '
@@ -591,7 +622,7 @@ def main():
             line['parity'] = parity[args.dtype]
         if rehearsal:
             line['rehearsal'] = True
-        if collective:
+        if collective and args.full:
             line['exchange'] = {'collective': 'all_gather_into_tensor of f32[%d, 12] per rank (backend %s%s)'
                                               % (B, backend, ' = RCCL' if backend == 'nccl' else ': NOT RCCL, rehearsal'),
                                 'avg_us': round(main_res['exchange_us'], 1),
@@ -600,8 +631,9 @@ def main():
                                 'tune_cache': 'one TSM_TUNE_CACHE file for all ranks: rank 0 tunes, the others read its '
                                               'tile choices' if world > 1 else 'single rank',
                                 'note': 'back-to-back latency of the only data-path collective, measured outside the timed steps'}
-        if alt_res is not None:
+        if alt_res is not None and args.full:
             a_dtype, a_elapsed, a_fwd = alt_res['dtype'], alt_res['elapsed'], alt_res['fwd_ms']
+            gflop = flops_per_clip(T, H, W) / 1e9
             line['alt_precision'] = {
                 'dtype': a_dtype, 'value': None if rehearsal else round(clips_total / a_elapsed, 2), 'unit': 'clips/s',
                 'ms_per_step': round(1e3 * a_elapsed / args.steps, 4), 'forward_kernel_ms': round(a_fwd, 4),
@@ -613,7 +645,7 @@ def main():
                         if a_dtype == 'bf16x3' else 'exact-fp32 MFMA mode of the same engine'}
             if a_dtype in parity:
                 line['alt_precision']['parity'] = parity[a_dtype]
-        if c5_res is not None:
+        if c5_res is not None and args.full:
             c5_total = 64 * world * args.steps
             c5_sm = c5_res['step_ms']
             line['config5'] = {

@@ -52,7 +52,8 @@ def test_bench_step_through_a_one_rank_rccl_group(hip_lib):
     exchange latency) on a 1-rank nccl group: everything `torchrun --nproc-per-node N bench.py --gpus N` executes
     except a second rank."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
-                          '--batch', '4', '--no-alt', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900,
+                          '--batch', '4', '--no-alt', '--no-cpu-baseline', '--full'],
+                         capture_output=True, text=True, timeout=900,
                          env=_env(TSM_BENCH_FORCE_COLLECTIVE='1', MASTER_PORT=str(_free_port())))
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = _last_json(out.stdout)
@@ -67,7 +68,7 @@ def test_rehearsal_line_is_labelled_and_carries_no_value(hip_lib):
     so and must not offer a throughput value or call the exchange RCCL."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
            '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-           '--warmup', '1', '--batch', '2', '--no-alt', '--no-cpu-baseline']
+           '--warmup', '1', '--batch', '2', '--no-alt', '--no-cpu-baseline', '--full']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=_env(TSM_BENCH_REHEARSAL='1'), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = _last_json(out.stdout)
@@ -81,7 +82,8 @@ def test_bench_starts_its_own_ranks_when_no_launcher_is_given(hip_lib):
     ranks before touching the GPU, they share ONE tune cache (rank 0 tunes, rank 1 reads), rank 0's single JSON line
     comes through the parent's stdout and carries per-rank step medians.  Rehearsal: both ranks on this box's one GPU."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                          '--batch', '2', '--no-alt', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900,
+                          '--batch', '2', '--no-alt', '--no-cpu-baseline', '--full'],
+                         capture_output=True, text=True, timeout=900,
                          env=_env(TSM_BENCH_REHEARSAL='1'), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     json_lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]

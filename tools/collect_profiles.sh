@@ -14,7 +14,7 @@ cp $G/${t}_f32_bench_line.json $P/${t}_f32_b32_bench_line_profiled.json
 cp $G/${t}_bf16c5_bench_line.json $P/${t}_bf16_config5_bench_line_profiled.json
 cp $G/${t}_bf16x3_bench_line.json $P/${t}_bf16x3_b32_bench_line_profiled.json
 [ -f $G/${t}_traffic.json ] && cp $G/${t}_traffic.json $P/traffic.json
-# un-profiled bench lines, if the same call produced them (python bench.py [--config 5 | --dtype bf16 ...] > gpurun_out/<tag>_bench3*.json)
+# un-profiled bench lines, if the same call produced them (python bench.py --full [--config 5 | --dtype bf16 ...] > $G/<tag>_bench3*.json)
 [ -f $G/${t}_bench3.json ] && grep '^{' $G/${t}_bench3.json | tail -1 > $P/${t}_bench_line.json
 [ -f $G/${t}_bench3_c5.json ] && grep '^{' $G/${t}_bench3_c5.json | tail -1 > $P/${t}_bench_line_config5.json
 [ -f $G/${t}_bench3_bf16.json ] && grep '^{' $G/${t}_bench3_bf16.json | tail -1 > $P/${t}_bench_line_bf16_b32.json

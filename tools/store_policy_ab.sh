@@ -11,7 +11,7 @@ for v in "$@"; do
   if [ "$v" = plain ]; then unset TSM_LIB_PATH; else export TSM_LIB_PATH=$R/workoutdetector_amd/libtsm_hip_$v.so; fi
   echo "== $v (${TSM_LIB_PATH:-default library})"
   for i in 1 2; do
-    python3 $R/bench.py --config 5 --no-alt --no-config5 --no-cpu-baseline > $O/sp_${v}_bench$i.json 2> $O/sp_${v}_bench$i.log
+    python3 $R/bench.py --full --config 5 --no-alt --no-config5 --no-cpu-baseline > $O/sp_${v}_bench$i.json 2> $O/sp_${v}_bench$i.log
     python3 -c "import json,sys; d=json.loads(open('$O/sp_${v}_bench$i.json').read().strip().splitlines()[-1]); print('  clips/s', d['value'], 'ms', d['ms_per_step'], 'parity', d.get('parity'))"
   done
   cd /tmp && export TMPDIR=/tmp

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_shift_place, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -143,6 +143,14 @@ const char *tsm_last_error(const tsm_engine *e);
  * State-dict keys of a BasicBlock: "base_model.layerL.B.conv1.net.weight" (or ".conv1.weight"), ".bn1.*",
  * ".conv2.weight", ".bn2.*", ".downsample.0.weight", ".downsample.1.*". */
 int tsm_set_backbone(tsm_engine *e, int32_t depth);
+
+/* Placement of the temporal shift -- create_model(shift_place=...), workoutdetector/models/tsm.py:104-124:
+ * 0 = 'blockres' (default: the shift wraps conv1 of every block, the identity sees the unshifted input), 1 = 'block' (it
+ * wraps every block of layer1-4 whole: conv1, the identity and the downsample all read the shifted input).  is_shift = 0
+ * ignores it, as the reference does.  Same contract as tsm_set_backbone: legal between tsm_create and the first
+ * tsm_set_tensor, later TSM_ERR_INVALID_ARG; any other value TSM_ERR_UNSUPPORTED.  State-dict keys of a block engine:
+ * "base_model.layerL.B.net.<name>" (or the un-wrapped "base_model.layerL.B.<name>"); a blockres "conv1.net" key is unknown. */
+int tsm_set_shift_place(tsm_engine *e, int32_t place);
 
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.

@@ -1,9 +1,10 @@
 """Clip throughput of the TSM backbones (R18 / R34 / R50) side by side on one GPU: one JSON line per (backbone, dtype).
 
     python tools/backbone_bench.py [--backbones resnet18,resnet34,resnet50] [--dtypes f32,bf16] [--batch 32]
-                                   [--segments 8] [--size 224] [--steps 20] [--warmup 5]
+                                   [--segments 8] [--size 224] [--steps 20] [--warmup 5] [--shift-place blockres,block]
 
-Each engine gets the seeded synthetic weights of its backbone (weights.make_state_dict(0, 12, base_model)) and one
+One line per (backbone, dtype, shift placement).  Each engine gets the seeded synthetic weights of its backbone
+(weights.make_state_dict(0, 12, base_model, shift_place); the same numbers under both placements) and one
 device-resident seeded batch [B, T, 3, S, S]; ``warmup()`` tunes the batch's bucket first (never timed), then W untimed
 and K timed forwards run back to back on torch's current stream, one event per step boundary.  Fields:
 
@@ -14,7 +15,7 @@ and K timed forwards run back to back on torch's current stream, one event per s
                    whole-forward figure, not a kernel's share of peak
   logits_err       max |logits - CPU restatement| / max |CPU restatement| on the first two clips of the last timed step:
                    fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py for R50,
-                   tests/_basicblock_ref.py for R18 / R34)
+                   tests/_basicblock_ref.py for R18 / R34, tests/_block_place_ref.py for block placement)
 
 No CPU fallback: without a GPU it fails.
 """
@@ -31,28 +32,31 @@ PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md, "Peak FP32 (matrix)"
 PEAK_BF16_MFMA_TFLOPS = 2500.0   # MI355X_MICROARCH.md, "Peak BF16/FP16 MFMA", dense
 
 
-def reference_logits(base_model, sd, clips, t, dtype):
+def reference_logits(base_model, sd, clips, t, dtype, shift_place='blockres'):
     import torch
     from oracle import tsm_oracle
     from tests import _basicblock_ref
     sd_t = {k: torch.from_numpy(v) for k, v in sd.items()}
     bf16 = dtype == 'bf16'
+    if shift_place == 'block':
+        from tests import _block_place_ref
+        return _block_place_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()
     if base_model == 'resnet50':
         fwd = tsm_oracle.tsm_forward_bf16 if bf16 else tsm_oracle.tsm_forward
         return fwd(sd_t, clips, n_segment=t).numpy()
     return _basicblock_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()
 
 
-def run_one(args, base_model, dtype):
+def run_one(args, base_model, dtype, shift_place='blockres'):
     import numpy as np
     import torch
     from workoutdetector_amd.engine import TsmEngine
     from workoutdetector_amd.flops import flops_per_clip
     from workoutdetector_amd.weights import make_state_dict
     b, t, s = args.batch, args.segments, args.size
-    sd = make_state_dict(0, 12, base_model=base_model)
+    sd = make_state_dict(0, 12, base_model=base_model, shift_place=shift_place)
     eng = TsmEngine(num_class=12, num_segments=t, height=s, width=s, max_clips=b, state_dict=sd, dtype=dtype,
-                    base_model=base_model)
+                    base_model=base_model, shift_place=shift_place)
     gen = torch.Generator(device='cuda').manual_seed(0)
     clips = torch.randn(b, t, 3, s, s, device='cuda', generator=gen)
     logits = torch.empty(b, 12, device='cuda')
@@ -70,10 +74,10 @@ def run_one(args, base_model, dtype):
     ms = step_ms[len(step_ms) // 2]
     got = logits[:2].cpu().numpy()
     eng.close()
-    want = reference_logits(base_model, sd, clips[:2].cpu(), t, dtype)
+    want = reference_logits(base_model, sd, clips[:2].cpu(), t, dtype, shift_place)
     gflop = flops_per_clip(t, s, s, 12, base_model=base_model) * b / 1e9
     peak = PEAK_F32_MFMA_TFLOPS if dtype == 'f32' else PEAK_BF16_MFMA_TFLOPS
-    return {'backbone': base_model, 'dtype': dtype, 'batch': b, 'segments': t, 'size': s,
+    return {'backbone': base_model, 'dtype': dtype, 'shift_place': shift_place, 'batch': b, 'segments': t, 'size': s,
             'ms_per_step': round(ms, 3), 'ms_min': round(step_ms[0], 3), 'ms_max': round(step_ms[-1], 3),
             'clips_per_s': round(b / (ms / 1e3), 1), 'gflop_per_step': round(gflop, 1),
             'tflops': round(gflop / ms, 2), 'peak_tflops': peak, 'peak_frac': round(gflop / ms / peak, 4),
@@ -89,13 +93,15 @@ def main():
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--shift-place', default='blockres', help="comma-separated placements: 'blockres', 'block'")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit('backbone_bench.py needs a GPU')
     for dtype in args.dtypes.split(','):
         for base_model in args.backbones.split(','):
-            print(json.dumps(run_one(args, base_model, dtype)), flush=True)
+            for place in args.shift_place.split(','):
+                print(json.dumps(run_one(args, base_model, dtype, place)), flush=True)
 
 
 if __name__ == '__main__':

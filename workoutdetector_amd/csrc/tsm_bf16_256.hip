@@ -328,11 +328,12 @@ template <int N> __device__ __forceinline__ void wait_vmcnt_lgkm0() { asm volati
 #endif
 constexpr size_t kLds256pBytes = 131072 + 8192 + 8 * 2176;   // two operand buffers | bias [<= 2048] fp32 | residual arm: eight [8][68] fp32 sub-slabs
 
-template <int KS, bool SHIFT, bool DUAL> struct Tile256State {
+template <int KS, bool SHIFT, bool DUAL, bool SHIFT2 = false> struct Tile256State {
   unsigned a_off[2], b_off[2];
   unsigned a_mask[KS == 3 ? 2 : 1];
   unsigned a_offp[SHIFT ? 2 : 1], a_offm[SHIFT ? 2 : 1];
   unsigned a_off2[DUAL ? 2 : 1];
+  unsigned a_off2p[SHIFT2 ? 2 : 1], a_off2m[SHIFT2 ? 2 : 1];   // block placement: x2's frames t+1 / t-1
   int m0, n0;
   // (the operand windows as plain pointers + sizes: the host pass cannot hold __amdgpu_buffer_rsrc_t in a struct; the
   //  descriptors are rebuilt where they are used -- scalar moves)
@@ -343,14 +344,18 @@ template <int KS, bool SHIFT, bool DUAL> struct Tile256State {
 template <int KS, bool SHIFT, bool RES = false, bool DUAL = false>
 __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams p) {
   static_assert(KS == 1 || KS == 3, "1x1 (optionally temporally shifted) and 3x3");
-  static_assert(!(RES || DUAL) || (KS == 1 && !SHIFT), "residual / K-concatenated second source: plain 1x1 convs (conv3)");
+  static_assert(!(RES || DUAL) || KS == 1, "residual / K-concatenated second source: plain 1x1 convs (conv3)");
   static_assert(!(RES && DUAL), "the fused conv3 + downsample GEMM has no residual");
+  // SHIFT with RES / DUAL is block placement (tsm_igemm.hip, BSHIFT): the identity -- the residual, or the second source --
+  // is read through the temporal shift and the first source is not
+  constexpr bool ASHIFT = SHIFT && !RES && !DUAL;   // the A loader's shift (conv1)
+  constexpr bool RSHIFT = SHIFT && RES, XSHIFT = SHIFT && DUAL;
 #if TSM_256P_STAMP
   unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
 #endif
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // 2 buffers x 64 KB | bias [Cout] fp32
   typedef __attribute__((address_space(3))) void lds_void;
-  typedef Tile256State<KS, SHIFT, DUAL> State;
+  typedef Tile256State<KS, ASHIFT, DUAL, XSHIFT> State;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -379,13 +384,14 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
     T.m0 = tm * 256;
     T.n0 = tn * 256;
     const int n_first = T.m0 / HoWo;
-    const int frame0 = SHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
+    const int frame0 = ASHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
     const size_t a_bytes = ((size_t)p.N - frame0) * (size_t)frame_bytes;
     T.pa = reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_bytes;
     T.sza = (int)(a_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a_bytes);
     T.pb = reinterpret_cast<const char *>(p.w) + (size_t)T.n0 * p.Kp * 2;
-    const size_t a2_bytes = DUAL ? ((size_t)p.N - n_first) * (size_t)frame_bytes2 : 0;
-    T.pa2 = reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)n_first * frame_bytes2;
+    const int frame02 = (XSHIFT && n_first > 0) ? n_first - 1 : n_first;
+    const size_t a2_bytes = DUAL ? ((size_t)p.N - frame02) * (size_t)frame_bytes2 : 0;
+    T.pa2 = reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * frame_bytes2;
     T.sza2 = (int)(a2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a2_bytes);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -407,14 +413,19 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
             if ((unsigned)(iy0 + ky) < (unsigned)p.Hi && (unsigned)(ix0 + kx) < (unsigned)p.Wi) mask |= 1u << (ky * 3 + kx);
         T.a_mask[q] = ok ? mask : 0u;
       }
-      if (SHIFT) {
+      if (ASHIFT) {
         const int t = n % p.T;
         T.a_offp[q] = (ok && t < p.T - 1) ? (unsigned)(base + frame_bytes) : kInvalid;
         T.a_offm[q] = (ok && t > 0) ? (unsigned)(base - frame_bytes) : kInvalid;
       }
       if (DUAL)
-        T.a_off2[q] = ok ? (unsigned)((n - n_first) * frame_bytes2 + (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * 2 + chunk * 16)
+        T.a_off2[q] = ok ? (unsigned)((n - frame02) * frame_bytes2 + (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * 2 + chunk * 16)
                          : kInvalid;
+      if (XSHIFT) {
+        const int t = n % p.T;
+        T.a_off2p[q] = (ok && t < p.T - 1) ? T.a_off2[q] + (unsigned)frame_bytes2 : kInvalid;
+        T.a_off2m[q] = (ok && t > 0) ? T.a_off2[q] - (unsigned)frame_bytes2 : kInvalid;
+      }
       T.b_off[q] = (unsigned)(row * p.Kp * 2 + chunk * 16);
     }
   };
@@ -435,8 +446,8 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcB, (lds_void *)(dst + q * 1024), 16, (int)(T.b_off[q] | dead), (int)kbytes, 0, 0);
     } else if (KS == 1) {
       unsigned mp = 0u, mm_ = 0u, m0_ = ~0u;
-      if (SHIFT) {
-        const int c = kt * 64 + kh * 32 + chunk * 8;      // first channel of this lane's chunk
+      if (ASHIFT || XSHIFT) {
+        const int c = kt * 64 + kh * 32 + chunk * 8 - (XSHIFT ? nt1 * 64 : 0);   // first channel of this lane's chunk (of x2)
         mp = 0u - (unsigned)(c < p.fold);
         mm_ = (0u - (unsigned)(c < 2 * p.fold)) & ~mp;
         m0_ = ~(mp | mm_);
@@ -446,9 +457,11 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
       for (int q = 0; q < 2; ++q) {
         if (qsel >= 0 && q != qsel) continue;
         unsigned off = T.a_off[q];
-        if (SHIFT) off = (T.a_offp[q] & mp) | (T.a_offm[q] & mm_) | (T.a_off[q] & m0_);
+        if (ASHIFT) off = (T.a_offp[q] & mp) | (T.a_offm[q] & mm_) | (T.a_off[q] & m0_);
+        unsigned off2 = T.a_off2[q];
+        if (XSHIFT) off2 = (T.a_off2p[q] & mp) | (T.a_off2m[q] & mm_) | (T.a_off2[q] & m0_);
         if (DUAL && second)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA2, (lds_void *)(dst + q * 1024), 16, (int)(T.a_off2[q] | dead),
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA2, (lds_void *)(dst + q * 1024), 16, (int)(off2 | dead),
                                                    (int)(kbytes - (unsigned)nt1 * 128u), 0, 0);
         else
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16, (int)(off | dead), (int)kbytes, 0, 0);
@@ -492,7 +505,22 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
   u32x4 rres[RES ? 8 : 1];
   const int c8 = lane & 7, r8l = lane >> 3;
   auto load_res = [&](const State &T, int t, int slot) {
-    if constexpr (RES) {
+    if constexpr (RSHIFT) {
+      // block placement: row r of the identity reads row r + Ho*Wo (channels [0, fold); zeros at the clip's last frame),
+      // r - Ho*Wo ([fold, 2 fold); zeros at its first frame) or r -- one frame either side of the tile's window
+      const int rbase = T.m0 >= HoWo ? T.m0 - HoWo : 0;
+      const size_t y_bytes = ((size_t)p.M - rbase) * p.Cout * 2;
+      const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * 2), 0,
+          (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+      const int row = wm * 128 + t * 8 + r8l, c = T.n0 + wn * 64 + c8 * 8;
+      const int tt = ((T.m0 + row) / HoWo) % p.T;
+      unsigned o = (unsigned)(((T.m0 - rbase + row) * p.Cout + c) * 2);
+      const unsigned step = (unsigned)(HoWo * p.Cout * 2);
+      if (c < p.fold) o = tt < p.T - 1 ? o + step : kInvalid;
+      else if (c < 2 * p.fold) o = tt > 0 ? o - step : kInvalid;
+      rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)o, 0, 0);
+    } else if constexpr (RES) {
       const size_t y_bytes = ((size_t)p.M - T.m0) * p.Cout * 2;
       const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)T.m0 * p.Cout * 2), 0,
@@ -723,6 +751,11 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
 }
 
 bool conv_bf16_256p_valid(const ConvParams &p, int ks) {
+  if (ks == 1 && p.T > 0 && (p.res || p.x2)) {   // block placement: the shifted identity / second source (8-channel chunks)
+    ConvParams q = p;
+    q.T = 0;
+    return conv_bf16_256p_valid(q, ks) && p.N % p.T == 0 && p.fold % 8 == 0 && 2 * p.fold <= (p.res ? p.Cout : p.C2);
+  }
   return conv_bf16_256_valid(p, ks) && p.Kp >= 128 && p.Cout <= 2048;
 }
 
@@ -754,6 +787,8 @@ hipError_t launch_conv_bf16_256p(ConvParams p, int ks, hipStream_t s) {
   const int slots = di.n_cu & ~7;          // a multiple of 8: a workgroup's tiles then all sit in its own XCD's chunk
   const dim3 grid((unsigned)(ntiles < slots || slots < 8 ? ntiles : slots)), block(512);
   if (ks == 3) TSM_KLAUNCH((conv_bf16_256p_kernel<3, false>), grid, block, kLds256pBytes, s, p);
+  else if (p.T > 0 && p.res) TSM_KLAUNCH((conv_bf16_256p_kernel<1, true, true, false>), grid, block, kLds256pBytes, s, p);
+  else if (p.T > 0 && p.x2) TSM_KLAUNCH((conv_bf16_256p_kernel<1, true, false, true>), grid, block, kLds256pBytes, s, p);
   else if (p.T > 0) TSM_KLAUNCH((conv_bf16_256p_kernel<1, true>), grid, block, kLds256pBytes, s, p);
   else if (p.res) TSM_KLAUNCH((conv_bf16_256p_kernel<1, false, true, false>), grid, block, kLds256pBytes, s, p);
   else if (p.x2) TSM_KLAUNCH((conv_bf16_256p_kernel<1, false, false, true>), grid, block, kLds256pBytes, s, p);
@@ -777,6 +812,8 @@ hipError_t opt_in_bf16_256() {
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<3, false>), kLds256pBytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, false, true, false>), kLds256pBytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, false, false, true>), kLds256pBytes);
+  opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, true, true, false>), kLds256pBytes);
+  opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, true, false, true>), kLds256pBytes);
   return first;
 }
 

@@ -1,5 +1,5 @@
 // Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet clip forward on MI355X (ResNet-50 by default; ResNet-18 / 34
-// through tsm_set_backbone).
+// through tsm_set_backbone; the shift in front of conv1 by default, in front of the whole block through tsm_set_shift_place).
 //
 // Owns: packed weights (BatchNorm folded, K-major), an NHWC fp32 activation workspace sized for
 // max_clips, one HIP stream, two timing events.  The forward is a fixed schedule of kernel launches
@@ -100,9 +100,10 @@ int ilog2(int v) {
 struct tsm_engine {
   tsm_config cfg{};
   int depth = 50;             // tsm_set_backbone
+  int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
   int feat = 2048;            // channels of the last stage = the classifier's input width
   bool weights_started = false;   // a tsm_set_tensor call has been made: the backbone is fixed
-  size_t tune_sig_base = 0;   // length of tune_sig before the backbone suffix
+  size_t tune_sig_base = 0;   // length of tune_sig before the backbone / placement suffix
   std::string err;
   hipStream_t stream = nullptr;
   bool finalized = false;
@@ -182,7 +183,10 @@ void build_topology(tsm_engine *e) {
     for (int b = 0; b < bb.blocks[li]; ++b) {
       const int planes = kPlanes[li];
       const int stride = (b == 0 && li > 0) ? 2 : 1;
-      const std::string p = "base_model.layer" + std::to_string(li + 1) + "." + std::to_string(b);
+      // block placement wraps the whole block in TemporalShift: its tensors are "layerL.B.net.<name>", conv1 unwrapped
+      const bool bp = e->place == 1;
+      const std::string p = "base_model.layer" + std::to_string(li + 1) + "." + std::to_string(b) + (bp ? ".net" : "");
+      const std::string c1key = p + (bp ? ".conv1.weight" : ".conv1.net.weight");
       Block blk;
       blk.stride = stride;
       blk.name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
@@ -190,7 +194,7 @@ void build_topology(tsm_engine *e) {
       if (bb.basic) {
         // conv1: 3x3 at the block's stride, the temporal shift fused into its loader (no segmented form: kseg = 0);
         // conv2: 3x3, + identity.  Downsample (1x1 at the stride) where the width or the size changes.
-        ConvLayer c1; c1.wkey = p + ".conv1.net.weight"; c1.bnp = p + ".bn1";
+        ConvLayer c1; c1.wkey = c1key; c1.bnp = p + ".bn1";
         c1.cin = cin; c1.cout = planes; c1.k = 3; c1.stride = stride; c1.cp = cin; c1.kp = 9 * cin;
         ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
         c2.cin = planes; c2.cout = planes; c2.k = 3; c2.stride = 1; c2.cp = planes; c2.kp = 9 * planes;
@@ -207,7 +211,7 @@ void build_topology(tsm_engine *e) {
         cin = planes;
         continue;
       }
-      ConvLayer c1; c1.wkey = p + ".conv1.net.weight"; c1.bnp = p + ".bn1";
+      ConvLayer c1; c1.wkey = c1key; c1.bnp = p + ".bn1";
       c1.cin = cin; c1.cout = planes; c1.k = 1; c1.stride = 1; c1.cp = cin; c1.kp = cin;
       ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
       c2.cin = planes; c2.cout = planes; c2.k = 3; c2.stride = stride; c2.cp = planes; c2.kp = 9 * planes;
@@ -230,13 +234,24 @@ void build_topology(tsm_engine *e) {
   e->feat = kPlanes[3] * expansion;
 }
 
+// The un-wrapped spelling of an engine key, also accepted: TemporalShift wraps conv1 as ".conv1.net.weight" (blockres) or the
+// whole block as "layerL.B.net.<name>" (block placement); "" when the key has no wrapper.
+std::string unwrapped(const tsm_engine *e, const std::string &key) {
+  if (e->place == 1) {
+    const size_t at = key.find(".net.");
+    return at == std::string::npos ? "" : key.substr(0, at) + key.substr(at + 4);
+  }
+  const std::string net = ".conv1.net.weight";
+  if (key.size() > net.size() && key.compare(key.size() - net.size(), net.size(), net) == 0)
+    return key.substr(0, key.size() - net.size()) + ".conv1.weight";
+  return "";
+}
+
 const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
   auto it = e->tensors.find(key);
   if (it != e->tensors.end()) return &it->second;
-  // TemporalShift wraps conv1 as ".conv1.net.weight"; accept the un-wrapped spelling too.
-  const std::string net = ".conv1.net.weight";
-  if (key.size() > net.size() && key.compare(key.size() - net.size(), net.size(), net) == 0) {
-    std::string alt = key.substr(0, key.size() - net.size()) + ".conv1.weight";
+  const std::string alt = unwrapped(e, key);
+  if (!alt.empty()) {
     it = e->tensors.find(alt);
     if (it != e->tensors.end()) return &it->second;
   }
@@ -246,14 +261,11 @@ const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
 bool known_name(const tsm_engine *e, const std::string &name) {
   if (name == "fc.weight" || name == "fc.bias") return true;
   static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
+  auto is = [&](const std::string &key) { return name == key || name == unwrapped(e, key); };
   for (const ConvLayer &c : e->convs) {
-    if (name == c.wkey) return true;
-    const std::string net = ".conv1.net.weight";
-    if (c.wkey.size() > net.size() && c.wkey.compare(c.wkey.size() - net.size(), net.size(), net) == 0 &&
-        name == c.wkey.substr(0, c.wkey.size() - net.size()) + ".conv1.weight")
-      return true;
+    if (is(c.wkey)) return true;
     for (const char *s : bn_suffix)
-      if (name == c.bnp + s) return true;
+      if (is(c.bnp + s)) return true;
   }
   return false;
 }
@@ -391,6 +403,9 @@ int time_best_of(tsm_engine *e, hipStream_t s, F &&launches, float *best_ms) {
   return TSM_OK;
 }
 
+// Block placement with the shift on: every block reads its input through the shift, the identity path included.
+bool block_shift(const tsm_engine *e) { return e->place == 1 && e->cfg.is_shift; }
+
 // Every launch Bottleneck k can make on nn frames of hh x ww pixels, x -> y through the branch temporaries t1, t2, with
 // `reverse` still 0: the three convs (conv3 with the downsample branch K-concatenated behind it where the block has one) and
 // the fused forms.  Built with null tensors too, for the kernels' validity tests, which read shapes only.
@@ -417,6 +432,10 @@ BlockLaunches block_launches(const tsm_engine *e, size_t k, int nn, const float 
     const ConvLayer &cd = e->convs[blk.down];
     L.p3.w = blk.d_wf; L.p3.bias = blk.d_bf; L.p3.Kp = blk.kpf; L.p3.K1 = c3.kp; L.p3.kseg_len = blk.ksegf;
     L.p3.x2 = x; L.p3.C2 = cd.cp; L.p3.Hi2 = hh; L.p3.Wi2 = ww; L.p3.stride2 = blk.stride;
+  }
+  if (block_shift(e)) {   // block placement: the identity / the downsample operand is the block input through the shift
+    L.p3.T = T;
+    L.p3.fold = (fused ? e->convs[blk.down].cp : c3.cout) / cfg.shift_div;
   }
   tsm::BneckParams &pb = L.pb;
   pb.x = x; pb.w1 = c1.d_w; pb.bias1 = c1.d_b; pb.w2 = c2.d_w; pb.bias2 = c2.d_b; pb.y = y;
@@ -450,7 +469,7 @@ struct BlockForms {
 BlockForms fused_forms(const tsm_engine *e, size_t k, int nn, int hh, int ww, const char *stage) {
   BlockForms f;
   const Block &blk = e->blocks[k];
-  if (blk.conv3 < 0) return f;
+  if (blk.conv3 < 0 || block_shift(e)) return f;   // (none of them reads a shifted identity: block placement runs none)
   const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
   const BlockLaunches L = block_launches(e, k, nn, nullptr, nullptr, nullptr, nullptr, hh, ww);
   const bool bf16 = e->prec == tsm::kPrecBf16;
@@ -635,7 +654,8 @@ int Forward::run_basic(size_t k, int nn, float *x, float *y, int hh, int ww) {
   const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
   const float *identity = x;
   if (blk.down >= 0) {
-    tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, 0, 1, prec);
+    tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, block_shift(e) ? shiftT : 0,
+                                     e->cfg.shift_div, prec);
     int rcd = conv(blk.down, pd, 1, false);
     if (rcd) return rcd;
     identity = idb;
@@ -645,6 +665,10 @@ int Forward::run_basic(size_t k, int nn, float *x, float *y, int hh, int ww) {
   if (rc1) return rc1;
   if (want(name + ".conv1")) return hit(t1, nn, ho, wo, c1.cout);
   tsm::ConvParams p2 = make_params(c2, t1, identity, y, nn, ho, wo, true, 0, 1, prec);
+  if (block_shift(e) && blk.down < 0) {   // block placement: the identity is the block input through the shift
+    p2.T = T;
+    p2.fold = c2.cout / e->cfg.shift_div;
+  }
   int rc2 = conv(blk.conv2, p2, 3, true);
   if (rc2) return rc2;
   if (want(name)) return hit(y, nn, ho, wo, c2.cout);
@@ -869,6 +893,15 @@ hipStream_t pick_stream(tsm_engine *e, int memkind, void *stream) {
   return memkind == TSM_MEM_HOST ? e->stream : nullptr;
 }
 
+// Tuned codes of one backbone or placement are never read by another: " r<depth>" for a backbone other than R50, " block"
+// for block placement (an R50 blockres engine keeps the bare signature, so existing cache lines stay valid).
+void retag_tune_sig(tsm_engine *e) {
+  if (e->tune_sig.empty()) return;
+  e->tune_sig.resize(e->tune_sig_base);
+  if (e->depth != 50) e->tune_sig += " r" + std::to_string(e->depth);
+  if (e->place == 1) e->tune_sig += " block";
+}
+
 int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout, int n_clips) {
   if (!e) return TSM_ERR_INVALID_ARG;
   if (!e->finalized) return fail(e, TSM_ERR_NOT_FINALIZED, "tsm_finalize has not been called");
@@ -983,7 +1016,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
                   std::to_string(cfg->is_shift ? cfg->shift_div : 0) + " fuse" + std::to_string(e->fuse23) + "/" + std::to_string(e->fuse_block) + "/" + std::to_string(e->fuse31) + "/" + std::to_string(e->fuse_front) +
                   " stem" + std::to_string(e->stem_direct ? 1 : 0) +
                   std::to_string(e->stem_pool ? 1 : 0) + std::to_string(e->stem_planar ? 1 : 0);
-    e->tune_sig_base = e->tune_sig.size();   // (tsm_set_backbone appends " r<depth>" for a backbone other than R50)
+    e->tune_sig_base = e->tune_sig.size();   // (retag_tune_sig appends the backbone and the placement)
   }
   *out = e;
   return TSM_OK;
@@ -996,10 +1029,18 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
   if (!find_backbone(depth)) return fail(e, TSM_ERR_UNSUPPORTED, "depth must be 18, 34 or 50");
   e->depth = depth;
   build_topology(e);
-  if (!e->tune_sig.empty()) {   // tuned codes of one backbone are never read by another
-    e->tune_sig.resize(e->tune_sig_base);
-    if (depth != 50) e->tune_sig += " r" + std::to_string(depth);
-  }
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_shift_place(tsm_engine *e, int32_t place) {
+  if (!e) return TSM_ERR_INVALID_ARG;
+  if (e->weights_started || e->finalized)
+    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_shift_place must come before the first tsm_set_tensor");
+  if (place != 0 && place != 1) return fail(e, TSM_ERR_UNSUPPORTED, "place must be 0 (blockres) or 1 (block)");
+  e->place = place;
+  build_topology(e);
+  retag_tune_sig(e);
   return TSM_OK;
 }
 
@@ -1374,6 +1415,10 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
   if (prec == tsm::kPrecBf16 && !stem && cin % 64 != 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "TSM_DTYPE_BF16 needs cin % 64 == 0");
   if (cout % 64 != 0) return fail(nullptr, TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64");
+  // (a launch with both shifts the IDENTITY -- block placement's arm, engine-internal -- not the input this entry point shifts)
+  if (residual && shift_segments > 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted input with a residual: no such launch");
+  if (shift_segments > 0 && k == 1 && stride != 1)   // (the engine's stride-2 shifted 1x1 is block placement's, not offered here)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted 1x1 runs at stride 1 only");
   hipStream_t s = static_cast<hipStream_t>(stream);
   ConvLayer c;
   c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;

@@ -50,19 +50,31 @@ namespace tsm {
 //                32-byte group [hi x8 | lo x8] (same 4 bytes per element, same byte offsets as fp32, so the
 //                loader is shared).  a*b ~= ah*bh + ah*bl + al*bh on v_mfma_f32_32x32x16_bf16 with fp32
 //                accumulation: relative error ~2^-17 per product, three MFMAs at 16x the fp32-MFMA rate.
+//
+// BSHIFT (block placement, shift_place 'block': the block input is shifted as a whole, so its identity path reads the shifted
+// tensor too): the temporal shift moves from the A loader to the identity -- the residual (RES: row r of the identity reads
+// row r +- Ho*Wo per channel chunk, p.fold = Cout / shift_div) or the second source of a DUAL GEMM (the downsample operand
+// gets the A loader's per-chunk frame choice, p.fold = C2 / shift_div; the first source stays unshifted).  p.T > 0 selects
+// it at launch.  Instantiated as PREC | kPrecBlockShift with SHIFT = RES = false (DUAL = false: the shifted residual), so that
+// every other instantiation keeps its name and its code.
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT, bool RES, int PREC, bool DUAL = false, bool SEG = false>
 // (second launch-bounds argument = minimum waves per SIMD: the SEG 64x64 kernel needs 16 registers more than the
 // plain one and would drop from 5 to 4 workgroups per CU; asking for 5 costs 1-2 spills outside the K loop)
-__global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) conv_igemm(const ConvParams p) {
-  static_assert(!SEG || (PREC == kPrecF32 && !RES && WGM * WGN <= 4 && BM == BN && BM <= 64),
+__global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? ((PREC & kPrecBlockShift) ? 4 : 5) : 1)
+conv_igemm(const ConvParams p) {
+  constexpr bool BSHIFT = (PREC & kPrecBlockShift) != 0;
+  constexpr int PMODE = PREC & ~kPrecBlockShift;   // the arithmetic (ConvPrec)
+  static_assert(!BSHIFT || (!SHIFT && !RES), "block placement: a shifted identity (DUAL = false) or a shifted second source");
+  constexpr bool RESID = RES || (BSHIFT && !DUAL);   // a residual is added (block placement: through the shift)
+  static_assert(!SEG || (PMODE == kPrecF32 && !RES && WGM * WGN <= 4 && BM == BN && BM <= 64),
                 "segmented K accumulation: fp32, 64x64 / 32x32 tiles, no residual (ConvParams::kseg_len)");
   static_assert(WGM * WGN == 4 || WGM * WGN == 1 || WGM * WGN == 8,
                 "4 waves per workgroup, 1 (32x32 small-M tiles) or 8 (128x128 with 4 waves per SIMD at 2 workgroups/CU)");
   constexpr int NT = 64 * WGM * WGN;   // threads per workgroup
   constexpr int LRP = NT / 8;          // loader rows per pass (8 threads x 16 bytes per 128-byte row)
   static_assert(!DUAL || (KS == 1 && !SHIFT && !RES), "K-concatenated second source: plain 1x1 convs only");
-  constexpr bool X3 = PREC == kPrecBf16x3;
-  constexpr bool BF = PREC == kPrecBf16;   // plain bf16 storage, one bf16 MFMA per product (config 5)
+  constexpr bool X3 = PMODE == kPrecBf16x3;
+  constexpr bool BF = PMODE == kPrecBf16;   // plain bf16 storage, one bf16 MFMA per product (config 5)
   constexpr int EB = BF ? 2 : 4;           // bytes per stored element
   constexpr int KC = 128 / EB;             // channels per K-step (an LDS row is always 128 bytes)
   // (a shifted 3x3 holds two more offsets per pass; its segmented form is not built: ConvParams::kseg_len must be 0)
@@ -74,7 +86,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
   // tile visible every wave pulls all four k-groups of fragments into registers, a second barrier frees the
   // buffer, and the 16 MFMAs of the step then run from registers while the next tile is written into LDS.
   // Half the LDS per workgroup -> more workgroups per CU, and no LDS wait inside the MFMA sequence.
-  constexpr bool RK = PREC == kPrecF32 && ((BM == 64 && BN == 64) || (BM == 32 && BN == 32));
+  constexpr bool RK = PMODE == kPrecF32 && ((BM == 64 && BN == 64) || (BM == 32 && BN == 32));
   constexpr int NBUF = RK ? 1 : 2;
   constexpr int CLD = BN + 4;  // epilogue staging row stride (floats)
   static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 32x32 MFMA tile");
@@ -117,7 +129,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
   const int frame0 = SHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
   // bf16-format stem: the input is stored as pixel PAIRS (8-element groups = 2 pixels x 4 channels, odd
   // widths padded with a zero pixel), so a frame is Hi x ceil(Wi/2) groups.
-  constexpr bool PAIRS = KS == 7 && PREC != kPrecF32;
+  constexpr bool PAIRS = KS == 7 && PMODE != kPrecF32;
   const int wpairs = (p.Wi + 1) >> 1;
   const size_t frame_elems = PAIRS ? (size_t)p.Hi * wpairs * 8 : (size_t)p.Hi * p.Wi * p.C;
   const size_t a_bytes = ((size_t)p.N - frame0) * frame_elems * EB;
@@ -130,9 +142,10 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
 
   // second A source (DUAL): same output pixels, its own channel count / spatial size / stride
   const size_t frame_elems2 = DUAL ? (size_t)p.Hi2 * p.Wi2 * p.C2 : 0;
-  const size_t a2_bytes = DUAL ? ((size_t)p.N - n_first) * frame_elems2 * EB : 0;
+  const int frame02 = (BSHIFT && DUAL && n_first > 0) ? n_first - 1 : n_first;   // (a shifted x2 also reads frame t-1)
+  const size_t a2_bytes = DUAL ? ((size_t)p.N - frame02) * frame_elems2 * EB : 0;
   const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)n_first * frame_elems2 * EB), 0,
+      const_cast<char *>(reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * frame_elems2 * EB), 0,
       (int)(a2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a2_bytes), 0x00020000);
 
   // ---- per-thread loader state: 8 threads per 32-float row, 32 rows per pass -------------------
@@ -143,6 +156,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
   unsigned a_offp[SHIFT ? APASS : 1], a_offm[SHIFT ? APASS : 1];
   unsigned a_mask[KS == 3 ? APASS : 1];
   unsigned a_off2[DUAL ? APASS : 1];
+  unsigned a_off2p[(BSHIFT && DUAL) ? APASS : 1], a_off2m[(BSHIFT && DUAL) ? APASS : 1];
   int a_iy[KS == 7 ? APASS : 1], a_ix[KS == 7 ? APASS : 1];
 #pragma unroll
   for (int pp = 0; pp < APASS; ++pp) {
@@ -163,9 +177,14 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       const int base = (n - frame0) * frame_bytes + (iy0 * p.Wi + ix0) * p.C * EB + chunk * 16;
       a_off[pp] = (KS == 1 && !ok) ? kInvalid : (unsigned)base;
       if (DUAL)
-        a_off2[pp] = ok ? (unsigned)((n - n_first) * (int)(frame_elems2 * EB) +
+        a_off2[pp] = ok ? (unsigned)((n - frame02) * (int)(frame_elems2 * EB) +
                                      (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * EB + chunk * 16)
                         : kInvalid;
+      if (BSHIFT && DUAL) {   // x2's frames t+1 / t-1 (zeros past the clip's ends), chosen per chunk like the shifted A loader's
+        const int t = n % p.T;
+        a_off2p[pp] = (ok && t < p.T - 1) ? a_off2[pp] + (unsigned)(frame_elems2 * EB) : kInvalid;
+        a_off2m[pp] = (ok && t > 0) ? a_off2[pp] - (unsigned)(frame_elems2 * EB) : kInvalid;
+      }
       if (KS == 3) {
         unsigned mask = 0;
 #pragma unroll
@@ -228,6 +247,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       k.mm = (0u - (unsigned)(c < 2 * p.fold)) & ~k.mp;
       k.m0 = ~(k.mp | k.mm);
     }
+    if (BSHIFT && DUAL) {   // the same masks for a K-step of the second source (channel c0 - K1 of x2; unused on the first)
+      const int c = c0 - nk1 * KC + (X3 ? (chunk >> 1) * 8 : (BF ? chunk * 8 : chunk * 4));
+      k.mp = 0u - (unsigned)(c < p.fold);
+      k.mm = (0u - (unsigned)(c < 2 * p.fold)) & ~k.mp;
+      k.m0 = ~(k.mp | k.mm);
+    }
     return k;
   };
   auto gload_item = [&](const KStep &k, int kt, int item) {
@@ -239,7 +264,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
         if (DUAL) {
           // K-steps [0, nk1) come from the first source, the rest from the second (wave-uniform choice)
           const bool second = kt >= nk1;
-          ra[pp] = buf_load4(second ? rsrcA2 : rsrcA, (second ? a_off2[pp] : off) | k.dead,
+          const unsigned off2 = BSHIFT ? (a_off2p[pp] & k.mp) | (a_off2m[pp] & k.mm) | (a_off2[pp] & k.m0) : a_off2[pp];
+          ra[pp] = buf_load4(second ? rsrcA2 : rsrcA, (second ? off2 : off) | k.dead,
                              second ? k.kbytes - (unsigned)nk1 * 128u : k.kbytes);
         } else {
           ra[pp] = buf_load4(rsrcA, off | k.dead, k.kbytes);
@@ -415,9 +441,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
   constexpr int RPP = NT / TPR;        // rows per pass
   constexpr int EPASS = BM / RPP;
   const int ecol = (tid % TPR) * EW, erow = tid / TPR;
-  f32x4 rres[(RES && !X3 && !BF) ? EPASS : 1];
-  u32x4 rres_h[(RES && (X3 || BF)) ? EPASS : 1], rres_l[(RES && X3) ? EPASS : 1];
-  if (RES && (X3 || BF)) {
+  f32x4 rres[(RESID && !X3 && !BF) ? EPASS : 1];
+  u32x4 rres_h[(RESID && (X3 || BF)) ? EPASS : 1], rres_l[(RESID && X3) ? EPASS : 1];
+  if (RESID && (X3 || BF) && !BSHIFT) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * EB;
     const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)m0 * p.Cout * EB), 0,
@@ -429,7 +455,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       if (X3) rres_l[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)(o + 16), 0, 0);
     }
   }
-  if (RES && !X3 && !BF) {
+  if (RESID && !X3 && !BF && !BSHIFT) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * 4;
     const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(p.res + (size_t)m0 * p.Cout), 0,
@@ -437,6 +463,33 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
 #pragma unroll
     for (int k = 0; k < EPASS; ++k)
       rres[k] = buf_load4(rsrcR, (unsigned)(((erow + k * RPP) * p.Cout + n0 + ecol) * 4), 0);
+  }
+  if constexpr (RESID && BSHIFT) {
+    // Block placement: the identity is the block input through the shift.  A thread's EW channels sit in one group (fold
+    // % 4 / % 8), so its source row is row + Ho*Wo (channels [0, fold); zeros at the clip's last frame), row - Ho*Wo ([fold,
+    // 2 fold); zeros at its first frame) or the row itself.  The descriptor starts one frame before the tile.
+    const int rbase = m0 >= HoWo ? m0 - HoWo : 0;
+    const int c = n0 + ecol;
+    const int sel = c < p.fold ? 1 : c < 2 * p.fold ? -1 : 0;
+    const unsigned step = (unsigned)(HoWo * p.Cout * EB);
+    const size_t r_bytes = ((size_t)p.M - rbase) * p.Cout * EB;
+    const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * EB), 0,
+        (int)(r_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : r_bytes), 0x00020000);
+#pragma unroll
+    for (int k = 0; k < EPASS; ++k) {
+      const int rr = erow + k * RPP;
+      const int t = ((m0 + rr) / HoWo) % p.T;
+      unsigned o = (unsigned)(((m0 - rbase + rr) * p.Cout + c) * EB);
+      if (sel > 0) o = t < p.T - 1 ? o + step : kInvalid;
+      if (sel < 0) o = t > 0 ? o - step : kInvalid;
+      if constexpr (X3 || BF) {
+        rres_h[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)o, 0, 0);
+        if (X3) rres_l[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)(o + 16), 0, 0);
+      } else {
+        rres[k] = buf_load4(rsrcR, o, 0);
+      }
+    }
   }
 
   // ---- main loop -------------------------------------------------------------------------------
@@ -650,7 +703,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       const f32x4 c1 = *reinterpret_cast<const f32x4 *>(Cs + rr * CLD + ecol + 4);
       float v[8] = {c0[0] + bias0[0], c0[1] + bias0[1], c0[2] + bias0[2], c0[3] + bias0[3],
                     c1[0] + bias1[0], c1[1] + bias1[1], c1[2] + bias1[2], c1[3] + bias1[3]};
-      if (RES) {
+      if (RESID) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += split_elem(rres_h[k], e);
       }
@@ -667,7 +720,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       const int rr = erow + k * RPP;
       f32x4 v = *reinterpret_cast<const f32x4 *>(Cs + rr * CLD + ecol);
       v += bias;
-      if (RES) v += rres[k];
+      if (RESID) v += rres[k];
       v[0] = fmaxf(v[0], floor_);
       v[1] = fmaxf(v[1], floor_);
       v[2] = fmaxf(v[2], floor_);
@@ -685,7 +738,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? 5 : 1) con
       const f32x4 c1 = *reinterpret_cast<const f32x4 *>(Cs + rr * CLD + ecol + 4);
       float v[8] = {c0[0] + bias0[0], c0[1] + bias0[1], c0[2] + bias0[2], c0[3] + bias0[3],
                     c1[0] + bias1[0], c1[1] + bias1[1], c1[2] + bias1[2], c1[3] + bias1[3]};
-      if (RES) {
+      if (RESID) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += split_elem(rres_h[k], e) + split_elem(rres_l[k], e);
       }
@@ -726,6 +779,10 @@ static hipError_t launch_conv_seg(ConvParams p, hipStream_t s) {
                                              : ntiles * (p.ksplit ? conv_num_segments(p) : 1)));
     const dim3 block(64 * WGM * WGN);
     if constexpr (KS == 1 && !SHIFT) {
+      if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
+        return hipGetLastError();
+      }
       if (p.x2) {
         TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
         return hipGetLastError();
@@ -746,6 +803,15 @@ static hipError_t launch_conv_t(ConvParams p, hipStream_t s) {
   p.ntn = p.Cout / BN;
   const dim3 grid((unsigned)(p.ntm * p.ntn));
   if constexpr (KS == 1 && !SHIFT && !RES) {
+    if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
+      if (p.prec == kPrecBf16x3)
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      else if (p.prec == kPrecBf16)
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      else
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      return hipGetLastError();
+    }
     if (p.x2) {
       if (p.prec == kPrecBf16x3)
         TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
@@ -753,6 +819,17 @@ static hipError_t launch_conv_t(ConvParams p, hipStream_t s) {
         TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else
         TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      return hipGetLastError();
+    }
+  }
+  if constexpr (RES && !SHIFT && KS != 7) {
+    if (p.T > 0) {   // block placement: the identity through the shift
+      if (p.prec == kPrecBf16x3)
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16x3 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      else if (p.prec == kPrecBf16)
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
+      else
+        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecF32 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
       return hipGetLastError();
     }
   }
@@ -789,6 +866,11 @@ int conv_tile_from_name(const char *name) {
 }
 
 bool conv_tile_valid(const ConvParams &p, int tile) {
+  // Block placement's arms (a shifted identity or second source, a shifted 1x1 at stride 2) exist on conv_igemm's tiles, and for
+  // a 1x1's shifted identity / second source on the persistent 256x256 tile (conv_bf16_256p_kernel<1, true, RES, DUAL>).
+  if (p.T > 0 && (p.res || p.x2 || (p.pad == 0 && p.stride != 1)) &&
+      (tile == kTile256x256 || tile == kTileWs || (tile == kTile256x256p && (p.pad != 0 || !(p.res || p.x2)))))
+    return false;
   switch (tile) {
     case kTile128x128: return p.Cout % 128 == 0;
     case kTile128x64:
@@ -856,12 +938,18 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
   if (p.Cout % 64 != 0 || p.Kp % kc != 0 || p.M <= 0) return hipErrorInvalidValue;
   if ((1 << p.logC4) * 4 != p.C) return hipErrorInvalidValue;
   if (ks != 7 && p.C % kc != 0) return hipErrorInvalidValue;
-  // temporal shift: 1x1 at stride 1 (Bottleneck.conv1), 3x3 at stride 1 or 2 (BasicBlock.conv1; unsegmented only)
-  if (p.T > 0 && ((ks != 1 && ks != 3) || (ks == 1 && p.stride != 1) || (ks == 3 && p.kseg_len > 0) || p.N % p.T != 0 ||
-                  p.fold % 4 != 0))
+  // temporal shift of the A operand: 1x1 (Bottleneck.conv1; stride 2: BasicBlock downsample under block placement), 3x3 at
+  // stride 1 or 2 (BasicBlock.conv1; unsegmented only).  With a residual or a second source (block placement) T shifts the
+  // identity / x2 instead, fold = its channels / shift_div.
+  if (p.T > 0 && ((ks != 1 && ks != 3) || (ks == 3 && p.kseg_len > 0) || p.N % p.T != 0 || p.fold % 4 != 0 ||
+                  (p.res && 2 * p.fold > p.Cout) || (p.x2 && 2 * p.fold > p.C2)))
     return hipErrorInvalidValue;
-  if (p.x2 && (ks != 1 || p.T > 0 || p.res || p.K1 % kc != 0 || p.C2 % kc != 0 || p.K1 + p.C2 != p.Kp || p.K1 != p.C))
+  if (p.x2 && (ks != 1 || p.res || p.K1 % kc != 0 || p.C2 % kc != 0 || p.K1 + p.C2 != p.Kp || p.K1 != p.C))
     return hipErrorInvalidValue;
+  // the second source's window: the frames of a tile (one more before it when shifted), through 32-bit offsets
+  if (p.x2 && (128.0 / ((double)p.Ho * p.Wo) + 4.0) * (double)p.Hi2 * p.Wi2 * p.C2 * 4.0 > 2.0e9) return hipErrorInvalidValue;
+  // a shifted identity reads rows up to one frame either side of the tile through 32-bit offsets
+  if (p.T > 0 && p.res && (128.0 + 2.0 * p.Ho * p.Wo) * p.Cout * 4.0 > 2.0e9) return hipErrorInvalidValue;
   if (p.prec != kPrecF32 && p.prec != kPrecBf16x3 && p.prec != kPrecBf16) return hipErrorInvalidValue;
   if (p.kseg_len < 0 || (p.kseg_len > 0 && (p.prec != kPrecF32 || p.res || ks == 7))) return hipErrorInvalidValue;
   if ((p.ksplit && p.kseg_len <= 0) || p.ksplit < 0 || p.ksplit > 2) return hipErrorInvalidValue;
@@ -873,11 +961,11 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
   const double frames = 128.0 / ((double)p.Ho * p.Wo) + 4.0;
   if (frames * (double)p.Hi * p.Wi * p.C * 4.0 > 2.0e9) return hipErrorInvalidValue;
   switch (ks) {
-    case 1:
-      if (p.res) return p.T > 0 ? hipErrorInvalidValue : launch_conv_ks<1, false, true>(p, s);
-      return p.T > 0 ? launch_conv_ks<1, true, false>(p, s) : launch_conv_ks<1, false, false>(p, s);
+    case 1:   // (with a residual or a second source, T > 0 is block placement's shifted identity: launch_conv_t)
+      if (p.res) return launch_conv_ks<1, false, true>(p, s);
+      return p.T > 0 && !p.x2 ? launch_conv_ks<1, true, false>(p, s) : launch_conv_ks<1, false, false>(p, s);
     case 3:
-      if (p.res) return p.T > 0 ? hipErrorInvalidValue : launch_conv_ks<3, false, true>(p, s);
+      if (p.res) return launch_conv_ks<3, false, true>(p, s);
       return p.T > 0 ? launch_conv_ks<3, true, false>(p, s) : launch_conv_ks<3, false, false>(p, s);
     case 7: return p.res ? hipErrorInvalidValue : launch_conv_ks<7, false, false>(p, s);
     default: return hipErrorInvalidValue;

@@ -51,6 +51,8 @@ struct ConvParams {
 };
 
 enum ConvPrec { kPrecF32 = 0, kPrecBf16x3 = 1, kPrecBf16 = 2 };
+// (conv_igemm's PREC template argument only: the block-placement arms, a ConvPrec | kPrecBlockShift -- tsm_igemm.hip)
+constexpr int kPrecBlockShift = 4;
 
 enum ConvTile {
   kTileAuto = 0, kTile128x128 = 1, kTile128x64 = 2, kTile64x64 = 3, kTile32x32 = 4,

@@ -22,7 +22,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, DEPTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
+from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
                       remap_mmaction_keys)
 
 
@@ -45,9 +45,11 @@ class TsmEngine:
     def __init__(self, num_class: int = 12, num_segments: int = 8, height: int = 224, width: int = 224,
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
-                 base_model: str = 'resnet50'):
+                 base_model: str = 'resnet50', shift_place: str = 'blockres'):
         if base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+        if shift_place not in SHIFT_PLACES:
+            raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.num_class, self.num_segments = int(num_class), int(num_segments)
@@ -57,6 +59,7 @@ class TsmEngine:
             raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
         self.dtype = dtype
         self.base_model = base_model
+        self.shift_place = shift_place
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
                               'bf16': _lib.LAYOUT_NTHWC8B}[dtype]
@@ -65,6 +68,8 @@ class TsmEngine:
         _lib.check(self._lib.tsm_create(C.byref(cfg), C.byref(self._h)))
         if base_model != 'resnet50':
             _lib.check(self._lib.tsm_set_backbone(self._h, DEPTHS[base_model]), self._h)
+        if shift_place != 'blockres':
+            _lib.check(self._lib.tsm_set_shift_place(self._h, SHIFT_PLACES[shift_place]), self._h)
         self._finalized = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -309,11 +314,15 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     fetched offline: the engine then gets the seeded synthetic weights of ``weights.make_state_dict``.
     ``base_model``: 'resnet50' (Bottleneck), 'resnet18' or 'resnet34' (BasicBlock: the shift fused into the 3x3 conv1,
     fc [num_class, 512]); any other backbone raises NotImplementedError.
+    ``shift_place``: 'blockres' (the shift wraps conv1 of every block) or 'block' (it wraps every block whole: the identity
+    and the downsample read the shifted input too; state-dict keys ``base_model.layerL.B.net.*``); anything else raises
+    as the reference's assert does.  ``is_shift=False`` ignores it.
     """
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     assert consensus_type in ('avg',), 'the engine implements the avg consensus'
-    assert shift_place == 'blockres', 'the engine implements blockres placement'
+    if shift_place not in SHIFT_PLACES:
+        raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
     if non_local:
         raise NotImplementedError('non_local')
     dev = 0
@@ -324,7 +333,7 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         dev = int(s.split(':')[1]) if ':' in s else 0
     if checkpoint is not None and str(checkpoint).endswith('.onnx'):
         from .onnx_import import load_onnx_state_dict        # the reference's deployed artefact
-        sd = load_onnx_state_dict(checkpoint, num_class, base_model)
+        sd = load_onnx_state_dict(checkpoint, num_class, base_model, shift_place=shift_place)
     elif checkpoint is not None:
         import torch
         ckpt = torch.load(checkpoint, map_location='cpu')
@@ -333,10 +342,10 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         sd = (remap_mmaction_keys(raw) if is_mmaction_state_dict(raw)
               else remap_checkpoint_keys(raw, num_class, base_model))
     else:
-        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
+        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model, shift_place=shift_place)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width,
                      shift_div=shift_div, is_shift=is_shift, max_clips=max_clips, device=dev, state_dict=sd,
-                     dtype=dtype, base_model=base_model)
+                     dtype=dtype, base_model=base_model, shift_place=shift_place)
 
 
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------

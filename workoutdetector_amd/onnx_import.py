@@ -175,15 +175,15 @@ def _resolve_convs(path: str, nodes: List[dict], inits: Dict[str, np.ndarray], s
         if idx == 0:
             want = 0
         else:
-            role = wkey.rsplit('.', 2)[-2] if '.net.' not in wkey else 'conv1'   # conv2 | conv3 | 0 (downsample) | conv1
-            want = before + {'conv1': 0, '0': 0, 'conv2': 1, 'conv3': 2}[role]
+            role = wkey.rsplit('.', 2)[-2]   # conv2 | conv3 | 0 (downsample) | conv1 | net (blockres: conv1.net)
+            want = before + {'net': 0, 'conv1': 0, '0': 0, 'conv2': 1, 'conv3': 2}[role]
         cands = by_key.get((want, (cout, cin, k, k)), [])
         if len(cands) != 1:
             raise ValueError(f'{path}: {len(cands)} Conv nodes with {want} upstream convs and weight {(cout, cin, k, k)} '
                              f'for {wkey}; cannot map the graph onto the TSM-ResNet')
         out.append(nodes[cands[0]])
         nxt = specs[idx + 1][0] if idx + 1 < len(specs) else ''
-        if idx == 0 or (nxt.endswith('.conv1.net.weight') or nxt == ''):
+        if idx == 0 or (nxt.endswith(('.conv1.net.weight', '.net.conv1.weight')) or nxt == ''):
             before = idx + 1               # a block is complete: everything so far is upstream of the next one
     return out
 
@@ -201,17 +201,20 @@ def detect_backbone(inits: Dict[str, np.ndarray], nodes: List[dict]) -> str:
     return model
 
 
-def load_onnx_state_dict(path: str, num_class: int, base_model: Optional[str] = None) -> 'OrderedDict[str, np.ndarray]':
+def load_onnx_state_dict(path: str, num_class: int, base_model: Optional[str] = None,
+                         shift_place: str = 'blockres') -> 'OrderedDict[str, np.ndarray]':
     """Engine state dict (``TsmEngine.load_state_dict``) from a TSM-R50 / R18 / R34 ``.onnx`` export.  The backbone is
-    recognised from the graph (``detect_backbone``); a ``base_model`` that disagrees with it raises."""
+    recognised from the graph (``detect_backbone``); a ``base_model`` that disagrees with it raises.  The shift placement
+    comes from the caller: it names the keys (``conv_specs``); the graph's convs are the same under both placements."""
     inits, nodes = parse_onnx(path)
     found = detect_backbone(inits, nodes)
     if base_model is not None and base_model != found:
         raise ValueError(f'{path}: the graph is a {found}, not a {base_model}')
-    specs = conv_specs(found)
+    specs = conv_specs(found, shift_place)
     feat = feature_width(found)
     named = OrderedDict((_strip_prefix(k), v) for k, v in inits.items())
-    if all(w in named or w.replace('.conv1.net.', '.conv1.') in named for w, *_ in specs):
+    unwrap = ('.net.', '.') if shift_place == 'block' else ('.conv1.net.', '.conv1.')
+    if all(w in named or w.replace(*unwrap) in named for w, *_ in specs):
         sd = OrderedDict((k, v) for k, v in named.items()
                          if (k.startswith('base_model.') or k.startswith('fc.')) and v.dtype == np.float32)
     else:

@@ -23,6 +23,9 @@ EXPANSION = 4
 BACKBONES = {'resnet18': ((2, 2, 2, 2), 'basic'), 'resnet34': ((3, 4, 6, 3), 'basic'),
              'resnet50': (R50_BLOCKS, 'bottleneck')}
 DEPTHS = {'resnet18': 18, 'resnet34': 34, 'resnet50': 50}
+# create_model(shift_place=...) -> tsm_set_shift_place: 'blockres' wraps conv1 of every block in TemporalShift
+# (``layerL.B.conv1.net.weight``), 'block' wraps every block whole (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1.*``, ...)
+SHIFT_PLACES = {'blockres': 0, 'block': 1}
 
 
 def _backbone(base_model: str):
@@ -36,18 +39,27 @@ def feature_width(base_model: str = 'resnet50') -> int:
     return R50_PLANES[-1] * (EXPANSION if _backbone(base_model)[1] == 'bottleneck' else 1)
 
 
-def conv_specs(base_model: str = 'resnet50') -> List[Tuple[str, str, int, int, int]]:
+def _shift_place(shift_place: str) -> str:
+    if shift_place not in SHIFT_PLACES:
+        raise ValueError(f'shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}')
+    return shift_place
+
+
+def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> List[Tuple[str, str, int, int, int]]:
     """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50, 20
     for R18, 36 for R34).  A BasicBlock is conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the
-    first block of a stage changes the size or the width -- torchvision's module order."""
+    first block of a stage changes the size or the width -- torchvision's module order.  ``shift_place='block'``: the
+    same convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``)."""
     blocks, kind = _backbone(base_model)
+    block = _shift_place(shift_place) == 'block'
+    conv1 = '.conv1.weight' if block else '.conv1.net.weight'
     specs = [('base_model.conv1.weight', 'base_model.bn1', 64, 3, 7)]
     cin = 64
     if kind == 'basic':
         for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
             for b in range(nb):
-                p = f'base_model.layer{li}.{b}'
-                specs.append((p + '.conv1.net.weight', p + '.bn1', planes, cin, 3))
+                p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
+                specs.append((p + conv1, p + '.bn1', planes, cin, 3))
                 specs.append((p + '.conv2.weight', p + '.bn2', planes, planes, 3))
                 if b == 0 and li > 1:
                     specs.append((p + '.downsample.0.weight', p + '.downsample.1', planes, cin, 1))
@@ -55,8 +67,8 @@ def conv_specs(base_model: str = 'resnet50') -> List[Tuple[str, str, int, int, i
         return specs
     for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
         for b in range(nb):
-            p = f'base_model.layer{li}.{b}'
-            specs.append((p + '.conv1.net.weight', p + '.bn1', planes, cin, 1))
+            p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
+            specs.append((p + conv1, p + '.bn1', planes, cin, 1))
             specs.append((p + '.conv2.weight', p + '.bn2', planes, planes, 3))
             specs.append((p + '.conv3.weight', p + '.bn3', planes * EXPANSION, planes, 1))
             if b == 0:
@@ -66,15 +78,16 @@ def conv_specs(base_model: str = 'resnet50') -> List[Tuple[str, str, int, int, i
     return specs
 
 
-def make_state_dict(seed: int = 0, num_class: int = 12,
-                    base_model: str = 'resnet50') -> 'OrderedDict[str, np.ndarray]':
+def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resnet50',
+                    shift_place: str = 'blockres') -> 'OrderedDict[str, np.ndarray]':
     """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048] -- [cls, 512] for R18/R34).
 
     He-normal convs; BN statistics are all non-trivial so the fold is exercised; the last BN of
     each residual branch (bn3 of a Bottleneck, bn2 of a BasicBlock) is damped so activations stay O(1)
     through 16 blocks; the classifier uses std 0.05 (the reference's init std 0.001, tsm.py:260-262,
     gives logits too flat to discriminate between clips).  R50 draws the same stream as it always has
-    (tests/golden/tsm_r50_logits.json depends on it).
+    (tests/golden/tsm_r50_logits.json depends on it).  ``shift_place`` changes the keys only (``conv_specs``): one seed
+    gives the same numbers under both spellings.
     """
     last_bn = '.bn2' if _backbone(base_model)[1] == 'basic' else '.bn3'
     rng = np.random.default_rng(seed)
@@ -83,7 +96,7 @@ def make_state_dict(seed: int = 0, num_class: int = 12,
     def f32(a):
         return np.ascontiguousarray(a, dtype=np.float32)
 
-    for wkey, bnp, cout, cin, k in conv_specs(base_model):
+    for wkey, bnp, cout, cin, k in conv_specs(base_model, shift_place):
         fan_in = cin * k * k
         sd[wkey] = f32(rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / fan_in))
         damp = 0.35 if bnp.endswith(last_bn) else 1.0
@@ -130,7 +143,9 @@ def remap_mmaction_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, o
     ``TemporalShift`` (``.net``): ``backbone.layer1.0.conv1.conv.net.weight`` -> ``base_model.layer1.0.conv1.net.weight``,
     ``backbone.layer1.0.conv1.bn.*`` -> ``base_model.layer1.0.bn1.*``, ``downsample.conv/bn`` -> ``downsample.0/1``,
     stem ``backbone.conv1.conv/bn`` -> ``base_model.conv1`` / ``base_model.bn1``, ``cls_head.fc_cls`` -> ``fc``.
-    Same graph as the reference's own TSM (pytorch-style ResNet-50: stride on the 3x3; blockres shift, shift_div 8)."""
+    Same graph as the reference's own TSM (pytorch-style ResNet-50: stride on the 3x3; blockres shift, shift_div 8).
+    ``ResNetTSM(shift_place='block')`` wraps each block whole, ``.net`` after the block index:
+    ``backbone.layer1.0.net.conv1.conv.weight`` -> ``base_model.layer1.0.net.conv1.weight`` (and so on for every key of the block)."""
     out: 'OrderedDict[str, object]' = OrderedDict()
     for k, v in state_dict.items():
         if k.startswith('cls_head.fc_cls.'):
@@ -143,21 +158,24 @@ def remap_mmaction_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, o
             tail = parts[2:]
             name = ['conv1'] + tail if parts[1] == 'conv' else ['bn1'] + tail
         elif parts[0].startswith('layer'):
+            wrap = ['net'] if parts[2] == 'net' else []          # block placement: the whole block is wrapped
+            if wrap:
+                parts = parts[:2] + parts[3:]
             layer, blk, mod, kind, tail = parts[0], parts[1], parts[2], parts[3], parts[4:]
             if mod == 'downsample':
-                name = [layer, blk, 'downsample', '0' if kind == 'conv' else '1'] + tail
+                name = [layer, blk] + wrap + ['downsample', '0' if kind == 'conv' else '1'] + tail
             elif kind == 'conv':
-                name = [layer, blk, mod] + tail         # keeps a leading 'net' for the shifted conv1
+                name = [layer, blk] + wrap + [mod] + tail         # keeps a leading 'net' for the shifted conv1
             else:
-                name = [layer, blk, 'bn' + mod[-1]] + tail
+                name = [layer, blk] + wrap + ['bn' + mod[-1]] + tail
         else:
             continue
         out['base_model.' + '.'.join(name)] = v
     return out
 
 
-def required_keys(num_class_known: bool = True, base_model: str = 'resnet50') -> Iterable[str]:
-    for wkey, bnp, *_ in conv_specs(base_model):
+def required_keys(num_class_known: bool = True, base_model: str = 'resnet50', shift_place: str = 'blockres') -> Iterable[str]:
+    for wkey, bnp, *_ in conv_specs(base_model, shift_place):
         yield wkey
         for s in ('.weight', '.bias', '.running_mean', '.running_var'):
             yield bnp + s

@@ -18,6 +18,7 @@
  *   tsm_temporal_shift     TemporalShift.shift          workoutdetector/models/tsm.py:35-50
  *   tsm_conv_bn_act        one conv + BatchNorm(eval) [+ residual] [+ ReLU] of the torchvision
  *                          Bottleneck kept by TSM        workoutdetector/models/tsm.py:250-251,264-281
+ *   tsm_conv_op            the same with the engine's other conv forms (shifted identity, conv3 + downsample, tile code)
  *   tsm_maxpool3x3s2       base_model.maxpool
  *   tsm_head               avgpool -> fc -> view(-1,T,cls) -> mean(1)   tsm.py:411-419,165-174
  *   tsm_gather_clips       the loop's clip windows: video[i:i + 16:2] for i in range(0, len(video), 8), zero-padded tail
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_shift_place, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -244,6 +245,41 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
                     int32_t n, int32_t hi, int32_t wi, int32_t cin, int32_t cout, int32_t k,
                     int32_t stride, int32_t relu, int32_t shift_segments, int32_t fold_div,
                     int32_t dtype, void *stream);
+
+/* Everything tsm_conv_bn_act takes, plus the conv forms of the engine it cannot reach: block placement's shifted identity,
+ * the K-concatenated conv3 + downsample GEMM (a second source), a tile code and the tile walk direction.  Zero-initialise
+ * it and set struct_size = sizeof(tsm_conv_args); a zero field keeps tsm_conv_bn_act's meaning. */
+typedef struct tsm_conv_args {
+  int32_t struct_size;     /* = sizeof(tsm_conv_args), ABI guard                                                      */
+  const float *x;          /* [n,hi,wi,cin]                                                                            */
+  const float *w;          /* OIHW [cout,cin,k,k], raw                                                                 */
+  const float *gamma, *beta, *mean, *var;   /* [cout]                                                                  */
+  const float *residual;   /* nullable [n,ho,wo,cout]                                                                  */
+  float *y;                /* [n,ho,wo,cout]                                                                           */
+  int32_t n, hi, wi, cin, cout, k, stride, relu;
+  int32_t shift_segments;  /* T > 0: temporal shift over T segments, fold = channels of the shifted tensor / fold_div   */
+  int32_t fold_div;
+  int32_t dtype;           /* tsm_dtype                                                                                */
+  int32_t shift_target;    /* 0: shift x (as tsm_conv_bn_act).  1: shift the identity -- the residual if given, else the
+                              second source -- or, for a 1x1 at stride 2 with neither, x (BasicBlock downsample)         */
+  /* Second source (1x1 main conv only, no residual): y = act(conv(x, w) + bn + conv1x1(x2 at stride2, w2) + bn2), one GEMM
+   * over K = [cin | cin2] with the summed bias.  x2 [n,hi2,wi2,cin2]; w2 OIHW [cout,cin2,1,1]; the second conv's output
+   * size must equal the first's.  x2 == NULL: single source. */
+  const float *x2;
+  const float *w2;
+  const float *gamma2, *beta2, *mean2, *var2;
+  int32_t cin2, hi2, wi2, stride2;
+  int32_t code;            /* tile code as in tsm_conv_tiles (tile | 0x100 split-K | 0x200 tail split); 0 = heuristic.
+                              A code that does not fit the launch falls back as in the engine: tsm_launch_trace shows what ran */
+  int32_t reverse;         /* walk the output tiles from the last one to the first                                     */
+} tsm_conv_args;
+
+/* One conv launch as the engine makes it (test / debug entry point: packs the weights and allocates on every call; the
+ * split forms' segment scratch too).  Refusals come before any launch: TSM_ERR_INVALID_ARG for a shift_target of 1 with
+ * nothing to shift, a second source with a residual, 2 * fold above the shifted tensor's channels, n % T != 0 or mismatched
+ * sizes; TSM_ERR_UNSUPPORTED for a second source with k != 1 or a fold the dtype's channel groups cannot split (fp32: fold % 4,
+ * bf16 formats: fold % 8).  tsm_conv_bn_act is this call with the tile of TSM_CONV_TILE as its code. */
+int tsm_conv_op(const tsm_conv_args *a, void *stream);
 
 int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi, int32_t c,
                      void *stream);

@@ -32,9 +32,18 @@ class TsmError(RuntimeError):
         self.status = status
 
 
+class TsmConvArgs(C.Structure):
+    """struct tsm_conv_args (include/tsm_hip.h), the argument block of tsm_conv_op."""
+    _fields_ = ([('struct_size', C.c_int32)] + [(n, C.c_void_p) for n in ('x', 'w', 'gamma', 'beta', 'mean', 'var', 'residual', 'y')]
+                + [(n, C.c_int32) for n in ('n', 'hi', 'wi', 'cin', 'cout', 'k', 'stride', 'relu', 'shift_segments', 'fold_div',
+                                            'dtype', 'shift_target')]
+                + [(n, C.c_void_p) for n in ('x2', 'w2', 'gamma2', 'beta2', 'mean2', 'var2')]
+                + [(n, C.c_int32) for n in ('cin2', 'hi2', 'wi2', 'stride2', 'code', 'reverse')])
+
+
 EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_shift_place', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
-           'tsm_maxpool3x3s2', 'tsm_head', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
+           'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
 
 _lib: Optional[C.CDLL] = None
 
@@ -95,6 +104,8 @@ def load() -> C.CDLL:
     lib.tsm_temporal_shift.argtypes = [fp, fp, i64, i32, i64, i32, i32, vp]
     lib.tsm_conv_bn_act.restype = C.c_int
     lib.tsm_conv_bn_act.argtypes = [fp] * 8 + [i32] * 11 + [vp]
+    lib.tsm_conv_op.restype = C.c_int
+    lib.tsm_conv_op.argtypes = [C.POINTER(TsmConvArgs), vp]
     lib.tsm_maxpool3x3s2.restype = C.c_int
     lib.tsm_maxpool3x3s2.argtypes = [fp, fp, i32, i32, i32, i32, vp]
     lib.tsm_preprocess.restype = C.c_int

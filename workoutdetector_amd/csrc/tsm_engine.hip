@@ -341,6 +341,51 @@ bool tail_split_from(const tsm::ConvParams &p, int n_cu, size_t partial_elems, i
   return from > 0;
 }
 
+// A tile code is a ConvTile, plus kCodeSplitK for the split-K form of a segmented layer: one workgroup per (tile, K segment)
+// writes raw segment sums, splitk_reduce adds them in segment order and applies bias / ReLU -- bit-identical to the unsplit
+// launch.  Every output element accumulates its K in the same order whatever the tiling, so codes are bit-neutral.
+// `partial` holds `partial_elems` floats of segment sums (the engine's split-K scratch; the per-op entry point's own).
+hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial, size_t partial_elems, int n_cu, hipStream_t s) {
+  p.tile = code & kCodeTileMask;
+  // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
+  // EVERY launch (falling back to the whole-K form, which gives the same bits).
+  if ((code & kCodeSplitK) && p.kseg_len > 0 &&
+      (size_t)tsm::conv_num_segments(p) * (size_t)p.M * (size_t)p.Cout <= partial_elems) {
+    float *y = p.y;
+    p.ksplit = 1;
+    p.y = partial;
+    hipError_t st = tsm::launch_conv(p, ks, s);
+    if (st == hipSuccess)
+      st = tsm::launch_splitk_reduce(partial, tsm::conv_num_segments(p), p.M, p.Cout, p.bias, nullptr, y, p.relu, s);
+    return st;
+  }
+  // kCodeTailK: the tail split (ConvParams::ksplit = 2) of a segmented 64x64 layer -- the tiles of the last, partly filled round
+  // of resident workgroups (five per CU) as (tile, segment) pieces.  Re-derived from THIS launch's tile count on every launch;
+  // whenever it does not apply the whole-K form runs (same bits).
+  if ((code & kCodeTailK) && (code & kCodeTileMask) == tsm::kTile64x64 && p.kseg_len > 0) {
+    int tail_from = 0;
+    if (tail_split_from(p, n_cu, partial_elems, &tail_from)) {
+      float *y = p.y;
+      const int mt0 = tail_from / (p.Cout / 64) * 64;
+      p.ksplit = 2;
+      p.tail_from = tail_from;
+      p.ypart = partial;
+      hipError_t st = tsm::launch_conv(p, ks, s);
+      if (st == hipSuccess)
+        st = tsm::launch_splitk_reduce(partial, tsm::conv_num_segments(p), p.M - mt0, p.Cout, p.bias, nullptr,
+                                       y + (size_t)mt0 * p.Cout, p.relu, s);
+      return st;
+    }
+  }
+  return tsm::launch_conv(p, ks, s);
+}
+
+// A tile code trusted only after it has been checked against THIS launch: anything else is 0, the heuristic shape (launch_conv_code
+// ignores the split bits where they do not apply).
+int checked_code(const tsm::ConvParams &p, int code) {
+  return code > 0 && (code & ~kCodeValid) == 0 && tsm::conv_tile_valid(p, code & kCodeTileMask) ? code : 0;
+}
+
 struct Tap {
   const float *ptr = nullptr;
   int64_t shape[4] = {0, 0, 0, 0};
@@ -562,42 +607,8 @@ struct Forward {
   int tune_block(size_t k, int nn, float *x, float *y, int hh, int ww);
 };
 
-// A tile code is a ConvTile, plus kCodeSplitK for the split-K form of a segmented layer: one workgroup per (tile, K segment)
-// writes raw segment sums, splitk_reduce adds them in segment order and applies bias / ReLU -- bit-identical to the unsplit
-// launch.  Every output element accumulates its K in the same order whatever the tiling, so codes are bit-neutral.
 hipError_t Forward::launch_code(tsm::ConvParams p, int ks, int code) {
-  p.tile = code & kCodeTileMask;
-  // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
-  // EVERY launch (falling back to the whole-K form, which gives the same bits).
-  if ((code & kCodeSplitK) && p.kseg_len > 0 &&
-      (size_t)tsm::conv_num_segments(p) * (size_t)p.M * (size_t)p.Cout <= e->partial_elems) {
-    float *y = p.y;
-    p.ksplit = 1;
-    p.y = e->d_partial;
-    hipError_t st = tsm::launch_conv(p, ks, s);
-    if (st == hipSuccess)
-      st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M, p.Cout, p.bias, nullptr, y, p.relu, s);
-    return st;
-  }
-  // kCodeTailK: the tail split (ConvParams::ksplit = 2) of a segmented 64x64 layer -- the tiles of the last, partly filled round
-  // of resident workgroups (five per CU) as (tile, segment) pieces.  Re-derived from THIS launch's tile count on every launch;
-  // whenever it does not apply the whole-K form runs (same bits).
-  if ((code & kCodeTailK) && (code & kCodeTileMask) == tsm::kTile64x64 && p.kseg_len > 0) {
-    int tail_from = 0;
-    if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) {
-      float *y = p.y;
-      const int mt0 = tail_from / (p.Cout / 64) * 64;
-      p.ksplit = 2;
-      p.tail_from = tail_from;
-      p.ypart = e->d_partial;
-      hipError_t st = tsm::launch_conv(p, ks, s);
-      if (st == hipSuccess)
-        st = tsm::launch_splitk_reduce(e->d_partial, tsm::conv_num_segments(p), p.M - mt0, p.Cout, p.bias, nullptr,
-                                       y + (size_t)mt0 * p.Cout, p.relu, s);
-      return st;
-    }
-  }
-  return tsm::launch_conv(p, ks, s);
+  return launch_conv_code(p, ks, code, e->d_partial, e->partial_elems, e->n_cu, s);
 }
 
 // One conv launch.  Steady forward: the layer's tuned code, trusted only after it has been checked against THIS layer --
@@ -609,8 +620,7 @@ int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
     int code = tiles ? (*tiles)[idx] : 0;
     if (e->force_tile) code = e->force_tile;
     if (e->force_code >= 0) code = e->force_code;   // (launch_code ignores the split bit where it does not apply)
-    if (!(code > 0 && (code & ~kCodeValid) == 0 && tsm::conv_tile_valid(p, code & kCodeTileMask))) code = 0;
-    TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, code));
+    TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, checked_code(p, code)));
     return TSM_OK;
   }
   std::vector<int> cands;
@@ -1122,12 +1132,9 @@ int tsm_finalize(tsm_engine *e) {
     const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
     blk.kpf = c3.kp + cd.kp;
     blk.ksegf = segment_len(blk.kpf, e->prec);
-    std::vector<float> wf((size_t)c3.cout * blk.kpf), bf(c3.cout);
-    for (int o = 0; o < c3.cout; ++o) {
-      std::memcpy(&wf[(size_t)o * blk.kpf], &host_wp[blk.conv3][(size_t)o * c3.kp], c3.kp * sizeof(float));
-      std::memcpy(&wf[(size_t)o * blk.kpf + c3.kp], &host_wp[blk.down][(size_t)o * cd.kp], cd.kp * sizeof(float));
-      bf[o] = host_bias[blk.conv3][o] + host_bias[blk.down][o];
-    }
+    std::vector<float> wf, bf;
+    concat_k_pair(host_wp[blk.conv3], host_bias[blk.conv3], c3.kp, host_wp[blk.down], host_bias[blk.down], cd.kp, c3.cout,
+                  &wf, &bf);
     if (e->prec == tsm::kPrecBf16x3) to_split(&wf);
     if (e->prec == tsm::kPrecBf16) to_bf16(&wf);
     int rcf = dev_alloc(e, &blk.d_wf, wf.size());
@@ -1398,15 +1405,20 @@ int tsm_temporal_shift(const float *x, float *y, int64_t n_frames, int32_t n_seg
   return TSM_OK;
 }
 
-int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const float *beta, const float *mean,
-                    const float *var, const float *residual, float *y, int32_t n, int32_t hi, int32_t wi,
-                    int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t relu, int32_t shift_segments,
-                    int32_t fold_div, int32_t dtype, void *stream) {
+int tsm_conv_op(const tsm_conv_args *a, void *stream) {
+  if (!a || a->struct_size != (int32_t)sizeof(tsm_conv_args))
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "tsm_conv_args.struct_size must be sizeof(tsm_conv_args)");
+  const int dtype = a->dtype;
   if (dtype != TSM_DTYPE_F32 && dtype != TSM_DTYPE_BF16X3 && dtype != TSM_DTYPE_BF16)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "bad dtype");
   const int prec = dtype == TSM_DTYPE_BF16X3 ? tsm::kPrecBf16x3 : dtype == TSM_DTYPE_BF16 ? tsm::kPrecBf16 : tsm::kPrecF32;
   const bool x3 = prec != tsm::kPrecF32;  // any non-fp32 storage format: convert at the boundary
-  if (!x || !w || !gamma || !beta || !mean || !var || !y) return fail(nullptr, TSM_ERR_INVALID_ARG, "NULL pointer");
+  const int n = a->n, hi = a->hi, wi = a->wi, cin = a->cin, cout = a->cout, k = a->k, stride = a->stride;
+  const int T = a->shift_segments, fold_div = a->fold_div > 0 ? a->fold_div : 1;
+  const float *residual = a->residual;
+  const bool dual = a->x2 != nullptr;
+  if (!a->x || !a->w || !a->gamma || !a->beta || !a->mean || !a->var || !a->y) return fail(nullptr, TSM_ERR_INVALID_ARG, "NULL pointer");
+  if (n <= 0 || hi <= 0 || wi <= 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "n, hi and wi must be positive");
   if (k != 1 && k != 3 && k != 7) return fail(nullptr, TSM_ERR_UNSUPPORTED, "k must be 1, 3 or 7");
   if (stride != 1 && stride != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "stride must be 1 or 2");
   const bool stem = (k == 7);
@@ -1415,61 +1427,106 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
   if (prec == tsm::kPrecBf16 && !stem && cin % 64 != 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "TSM_DTYPE_BF16 needs cin % 64 == 0");
   if (cout % 64 != 0) return fail(nullptr, TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64");
-  // (a launch with both shifts the IDENTITY -- block placement's arm, engine-internal -- not the input this entry point shifts)
-  if (residual && shift_segments > 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted input with a residual: no such launch");
-  if (shift_segments > 0 && k == 1 && stride != 1)   // (the engine's stride-2 shifted 1x1 is block placement's, not offered here)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted 1x1 runs at stride 1 only");
+  if (stem && (residual || dual || T > 0)) return fail(nullptr, TSM_ERR_INVALID_ARG, "the 7x7 stem has no residual, second source or shift");
+  // What the shift moves: the input (0), or the identity (1: block placement) -- the residual, the second source, or for a
+  // 1x1 at stride 2 (a BasicBlock's downsample) the input, which is that block's identity.
+  if (a->shift_target != 0 && a->shift_target != 1) return fail(nullptr, TSM_ERR_INVALID_ARG, "shift_target must be 0 or 1");
+  const bool strided_1x1 = k == 1 && stride != 1;
+  if (a->shift_target == 1 && !residual && !dual && !strided_1x1)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "shift_target 1 needs a residual, a second source or a 1x1 at stride 2");
+  if (T > 0 && a->shift_target == 0) {
+    if (residual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted input with a residual: no such launch (shift_target 1 shifts the residual)");
+    if (dual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted first source with a second source: no such launch");
+    if (strided_1x1) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted 1x1 at stride 2 is the identity's (shift_target 1)");
+  }
+  const int pad_ = k / 2;
+  const int ho = (hi + 2 * pad_ - k) / stride + 1, wo = (wi + 2 * pad_ - k) / stride + 1;
+  const int cin2 = a->cin2;
+  if (dual) {
+    if (k != 1) return fail(nullptr, TSM_ERR_UNSUPPORTED, "a second source needs a 1x1 main conv");
+    if (residual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a second source with a residual: no such launch");
+    if (!a->w2 || !a->gamma2 || !a->beta2 || !a->mean2 || !a->var2) return fail(nullptr, TSM_ERR_INVALID_ARG, "NULL pointer (second source)");
+    if (cin2 % 32 != 0 || (cin2 & (cin2 - 1)) != 0 || (prec == tsm::kPrecBf16 && cin2 % 64 != 0))
+      return fail(nullptr, TSM_ERR_UNSUPPORTED, "cin2 must be a power of two >= 32 (TSM_DTYPE_BF16: >= 64)");
+    if (a->stride2 != 1 && a->stride2 != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "stride2 must be 1 or 2");
+    if (a->hi2 <= 0 || a->wi2 <= 0 || (a->hi2 - 1) / a->stride2 + 1 != ho || (a->wi2 - 1) / a->stride2 + 1 != wo)
+      return fail(nullptr, TSM_ERR_INVALID_ARG, "the second source's output size must equal the main conv's");
+  }
+  int fold = 0;
+  if (T > 0) {
+    const int shifted_c = a->shift_target == 0 ? cin : residual ? cout : dual ? cin2 : cin;
+    fold = shifted_c / fold_div;
+    if (n % T != 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "n must be a whole number of T-frame clips");
+    if (fold % (x3 ? 8 : 4) != 0)
+      return fail(nullptr, TSM_ERR_UNSUPPORTED, x3 ? "the bf16 formats shift whole 8-channel groups: fold % 8 == 0"
+                                                   : "fp32 shifts whole 4-channel groups: fold % 4 == 0");
+    if (2 * fold > shifted_c) return fail(nullptr, TSM_ERR_INVALID_ARG, "2 * fold exceeds the shifted tensor's channels");
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   ConvLayer c;
   c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;
   c.cp = stem ? 4 : cin;
   c.kp = (stem && x3) ? round_up(7 * 4 * 8, prec == tsm::kPrecBf16 ? 64 : 32)
                       : round_up(k * k * c.cp, prec == tsm::kPrecBf16 ? 64 : 32);
-  std::vector<float> hw_((size_t)cout * cin * k * k), hg(cout), hb(cout), hm(cout), hv(cout), wp, bias;
+  const int kp2 = dual ? round_up(cin2, prec == tsm::kPrecBf16 ? 64 : 32) : 0;
 #define TSM_HIP0(call)                                                                              \
   do {                                                                                              \
     hipError_t _st = (call);                                                                        \
     if (_st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
   } while (0)
+  // BatchNorm folded and packed on the host, as tsm_finalize does (a second source: the same K-concatenation as its fused GEMM)
+  auto fetch_packed = [&](const float *w, const float *g, const float *b, const float *m, const float *v, int ci, int kk,
+                          int cp, int kp, std::vector<float> *wp, std::vector<float> *bias) -> int {
+    std::vector<float> hw_((size_t)cout * ci * kk * kk), hg(cout), hb(cout), hm(cout), hv(cout);
+    TSM_HIP0(hipMemcpy(hw_.data(), w, hw_.size() * sizeof(float), hipMemcpyDeviceToHost));
+    TSM_HIP0(hipMemcpy(hg.data(), g, cout * sizeof(float), hipMemcpyDeviceToHost));
+    TSM_HIP0(hipMemcpy(hb.data(), b, cout * sizeof(float), hipMemcpyDeviceToHost));
+    TSM_HIP0(hipMemcpy(hm.data(), m, cout * sizeof(float), hipMemcpyDeviceToHost));
+    TSM_HIP0(hipMemcpy(hv.data(), v, cout * sizeof(float), hipMemcpyDeviceToHost));
+    if (kk == 7 && x3) fold_and_pack_stem_pairs(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, kp, wp, bias);
+    else fold_and_pack(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, ci, kk, cp, kp, wp, bias);
+    return TSM_OK;
+  };
+  if (stem && x3 && stride != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "the bf16 formats implement the 7x7 stem for stride 2 only");
   TSM_HIP0(hipStreamSynchronize(s));
-  TSM_HIP0(hipMemcpy(hw_.data(), w, hw_.size() * sizeof(float), hipMemcpyDeviceToHost));
-  TSM_HIP0(hipMemcpy(hg.data(), gamma, cout * sizeof(float), hipMemcpyDeviceToHost));
-  TSM_HIP0(hipMemcpy(hb.data(), beta, cout * sizeof(float), hipMemcpyDeviceToHost));
-  TSM_HIP0(hipMemcpy(hm.data(), mean, cout * sizeof(float), hipMemcpyDeviceToHost));
-  TSM_HIP0(hipMemcpy(hv.data(), var, cout * sizeof(float), hipMemcpyDeviceToHost));
-  if (stem && x3) {
-    if (stride != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "the bf16 formats implement the 7x7 stem for stride 2 only");
-    fold_and_pack_stem_pairs(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, c.kp, &wp, &bias);
-  } else {
-    fold_and_pack(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, cin, k, c.cp, c.kp, &wp, &bias);
+  std::vector<float> wp, bias;
+  int rc = fetch_packed(a->w, a->gamma, a->beta, a->mean, a->var, cin, k, c.cp, c.kp, &wp, &bias);
+  if (rc) return rc;
+  if (dual) {
+    std::vector<float> wp2, bias2, wf, bf;
+    rc = fetch_packed(a->w2, a->gamma2, a->beta2, a->mean2, a->var2, cin2, 1, cin2, kp2, &wp2, &bias2);
+    if (rc) return rc;
+    concat_k_pair(wp, bias, c.kp, wp2, bias2, kp2, cout, &wf, &bf);
+    wp.swap(wf);
+    bias.swap(bf);
   }
   if (prec == tsm::kPrecBf16x3) to_split(&wp);
   if (prec == tsm::kPrecBf16) to_bf16(&wp);
-  float *d_w = nullptr, *d_b = nullptr, *d_x4 = nullptr, *d_xs = nullptr, *d_rs = nullptr, *d_ys = nullptr;
+  float *d_w = nullptr, *d_b = nullptr, *d_x4 = nullptr, *d_xs = nullptr, *d_rs = nullptr, *d_ys = nullptr, *d_x2s = nullptr,
+        *d_part = nullptr;
   struct Scratch {  // frees the temporaries on every exit path (errors included)
-    float **ptrs[6];
+    float **ptrs[8];
     ~Scratch() {
       for (float **q : ptrs)
         if (*q) (void)hipFree(*q);
     }
-  } scratch{{&d_w, &d_b, &d_x4, &d_xs, &d_rs, &d_ys}};
+  } scratch{{&d_w, &d_b, &d_x4, &d_xs, &d_rs, &d_ys, &d_x2s, &d_part}};
   TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_w), wp.size() * sizeof(float)));
   TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_b), bias.size() * sizeof(float)));
   TSM_HIP0(hipMemcpy(d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
   TSM_HIP0(hipMemcpy(d_b, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
   c.d_w = d_w; c.d_b = d_b;
-  const float *xin = x;
+  const float *xin = a->x, *x2in = a->x2;
   const float *rin = residual;
-  float *yout = y;
-  const int pad_ = k / 2;
-  const size_t out_elems = (size_t)n * ((hi + 2 * pad_ - k) / stride + 1) * ((wi + 2 * pad_ - k) / stride + 1) * cout;
+  float *yout = a->y;
+  const size_t out_elems = (size_t)n * ho * wo * cout;
   if (stem) {  // NHWC3 -> NHWC4 fp32 / NHWC8 split
     TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_x4), (size_t)n * hi * wi * 8 * sizeof(float)));
-    TSM_HIP0(tsm::launch_pack_input(x, d_x4, n, hi, wi, 0, prec, s));
+    TSM_HIP0(tsm::launch_pack_input(a->x, d_x4, n, hi, wi, 0, prec, s));
     xin = d_x4;
   } else if (x3) {
     TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_xs), (size_t)n * hi * wi * cin * sizeof(float)));
-    TSM_HIP0(tsm::launch_from_f32(x, d_xs, (int64_t)n * hi * wi * cin / 8, prec, s));
+    TSM_HIP0(tsm::launch_from_f32(a->x, d_xs, (int64_t)n * hi * wi * cin / 8, prec, s));
     xin = d_xs;
   }
   if (x3) {
@@ -1480,25 +1537,58 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
       TSM_HIP0(tsm::launch_from_f32(residual, d_rs, (int64_t)out_elems / 8, prec, s));
       rin = d_rs;
     }
+    if (dual) {
+      const size_t x2_elems = (size_t)n * a->hi2 * a->wi2 * cin2;
+      TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_x2s), x2_elems * sizeof(float)));
+      TSM_HIP0(tsm::launch_from_f32(a->x2, d_x2s, (int64_t)x2_elems / 8, prec, s));
+      x2in = d_x2s;
+    }
   }
-  tsm::ConvParams p = make_params(c, xin, rin, yout, n, hi, wi, relu != 0, shift_segments,
-                                  fold_div > 0 ? fold_div : 1, prec);
-  // (a test / debug entry point that packs weights and allocates on every call: its tuning hooks are read per call)
+  tsm::ConvParams p = make_params(c, xin, rin, yout, n, hi, wi, a->relu != 0, T > 0 ? T : 0, fold_div, prec);
+  p.fold = fold;
+  p.reverse = a->reverse != 0;
+  if (dual) {   // (as block_launches sets up conv3 + downsample; segmented like the engine's fused GEMM)
+    p.Kp = c.kp + kp2; p.K1 = c.kp; p.kseg_len = segment_len(p.Kp, prec);
+    p.x2 = x2in; p.C2 = cin2; p.Hi2 = a->hi2; p.Wi2 = a->wi2; p.stride2 = a->stride2;
+  }
+  // the code as Forward::conv takes it; the split forms get a segment scratch of their own
+  const int code = checked_code(p, a->code);
+  size_t part_elems = 0;
+  if ((code & (kCodeSplitK | kCodeTailK)) && p.kseg_len > 0) {
+    part_elems = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
+    TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_part), part_elems * sizeof(float)));
+  }
+  int dev = 0, n_cu = 256;
+  TSM_HIP0(hipGetDevice(&dev));
+  TSM_HIP0(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  // (a test / debug entry point that packs weights and allocates on every call: its tuning hook is read per call)
   const char *sd_env = getenv("TSM_STEM_DIRECT");
-  const int forced = tsm::conv_tile_from_name(getenv("TSM_CONV_TILE"));
-  if (forced && tsm::conv_tile_valid(p, forced)) p.tile = forced;
   hipError_t st;
   if (stem && x3 && cout == 64 && !(sd_env && atoi(sd_env) == 0))
-    st = tsm::launch_stem_direct(xin, c.d_w, c.d_b, yout, n, hi, wi, c.kp, relu != 0, prec, s);
+    st = tsm::launch_stem_direct(xin, c.d_w, c.d_b, yout, n, hi, wi, c.kp, a->relu != 0, prec, s);
   else
-    st = tsm::launch_conv(p, k, s);
-  if (st == hipSuccess && x3) st = tsm::launch_to_f32(d_ys, y, (int64_t)out_elems / 8, prec, s);
+    st = launch_conv_code(p, k, code, d_part, part_elems, n_cu, s);
+  if (st == hipSuccess && x3) st = tsm::launch_to_f32(d_ys, a->y, (int64_t)out_elems / 8, prec, s);
   hipError_t st2 = hipStreamSynchronize(s);
   if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
                                     std::string("launch_conv: ") + hipGetErrorString(st));
   if (st2 != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("conv sync: ") + hipGetErrorString(st2));
   return TSM_OK;
 #undef TSM_HIP0
+}
+
+int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const float *beta, const float *mean,
+                    const float *var, const float *residual, float *y, int32_t n, int32_t hi, int32_t wi,
+                    int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t relu, int32_t shift_segments,
+                    int32_t fold_div, int32_t dtype, void *stream) {
+  tsm_conv_args a{};
+  a.struct_size = sizeof(tsm_conv_args);
+  a.x = x; a.w = w; a.gamma = gamma; a.beta = beta; a.mean = mean; a.var = var; a.residual = residual; a.y = y;
+  a.n = n; a.hi = hi; a.wi = wi; a.cin = cin; a.cout = cout; a.k = k; a.stride = stride; a.relu = relu;
+  a.shift_segments = shift_segments; a.fold_div = fold_div; a.dtype = dtype;
+  // (no engine, so the tuning hook is read per call: a tile TSM_CONV_TILE names, where it fits the launch)
+  a.code = tsm::conv_tile_from_name(getenv("TSM_CONV_TILE"));
+  return tsm_conv_op(&a, stream);
 }
 
 int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi, int32_t c, void *stream) {

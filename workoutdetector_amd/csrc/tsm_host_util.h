@@ -116,6 +116,20 @@ inline void fold_and_pack(const float *w, const float *gamma, const float *beta,
   }
 }
 
+// Bottleneck.conv3 + the downsample branch as ONE GEMM over K = [conv3's K | the downsample's K]: row o of the fused matrix is
+// row o of each packed fp32 matrix (fold_and_pack) side by side, and the bias is the two folded biases summed in fp32.
+inline void concat_k_pair(const std::vector<float> &w1, const std::vector<float> &b1, int kp1, const std::vector<float> &w2,
+                          const std::vector<float> &b2, int kp2, int cout, std::vector<float> *wf, std::vector<float> *bf) {
+  const int kpf = kp1 + kp2;
+  wf->assign((size_t)cout * kpf, 0.f);
+  bf->resize(cout);
+  for (int o = 0; o < cout; ++o) {
+    std::memcpy(&(*wf)[(size_t)o * kpf], &w1[(size_t)o * kp1], kp1 * sizeof(float));
+    std::memcpy(&(*wf)[(size_t)o * kpf + kp1], &w2[(size_t)o * kp2], kp2 * sizeof(float));
+    (*bf)[o] = b1[o] + b2[o];
+  }
+}
+
 // Tuned tile shapes are cached per power-of-two bucket of the clip count (ragged last batches of a video
 // would otherwise each pay a tuning pass): the first clip count that lands in a bucket tunes it.
 inline int tile_bucket(int n_clips) {

@@ -413,10 +413,16 @@ def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8):
 
 
 def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool = True, residual=None,
-                     shift_segments: int = 0, fold_div: int = 8, dtype: str = 'f32'):
-    """x NHWC [n,h,w,cin], w OIHW; returns NHWC [n,ho,wo,cout]."""
+                     shift_segments: int = 0, fold_div: int = 8, dtype: str = 'f32', *, shift_identity: bool = False,
+                     x2=None, w2=None, bn2=None, stride2: int = 1, code: Optional[int] = None, reverse: bool = False):
+    """x NHWC [n,h,w,cin], w OIHW; returns NHWC [n,ho,wo,cout].
+
+    The keyword arguments reach the engine's other conv forms through ``tsm_conv_op``: ``shift_identity`` shifts the
+    identity (the residual, else the second source; for a 1x1 at stride 2 the input) instead of the input; ``x2`` [n,h2,w2,cin2]
+    with ``w2`` [cout,cin2,1,1] and ``bn2`` = (gamma, beta, mean, var) adds a 1x1 conv of x2 at ``stride2`` to a 1x1 main conv
+    as one K-concatenated GEMM (conv3 + downsample); ``code`` is a tile code (0 = heuristic), ``reverse`` the tile walk."""
     import torch
-    _need_cuda_f32(x=x, w=w, gamma=gamma, beta=beta, mean=mean, var=var, residual=residual)
+    _need_cuda_f32(x=x, w=w, gamma=gamma, beta=beta, mean=mean, var=var, residual=residual, x2=x2, w2=w2)
     x = x.contiguous()
     n, hi, wi, cin = x.shape
     cout, wcin, k, k2 = w.shape
@@ -429,9 +435,33 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
         raise ValueError(f'residual {tuple(residual.shape)} must have the output shape {tuple(y.shape)}')
     res = None if residual is None else residual.contiguous()
     args = [t.contiguous() for t in (w, gamma, beta, mean, var)]
-    _lib.check(_lib.load().tsm_conv_bn_act(x.data_ptr(), *[a.data_ptr() for a in args], _ptr(res), y.data_ptr(),
-                                           n, hi, wi, cin, cout, k, stride, int(relu), shift_segments, fold_div,
-                                           _lib.DTYPES[dtype], _stream(x)))
+    lib = _lib.load()
+    if not shift_identity and x2 is None and code is None and not reverse:
+        _lib.check(lib.tsm_conv_bn_act(x.data_ptr(), *[a.data_ptr() for a in args], _ptr(res), y.data_ptr(),
+                                       n, hi, wi, cin, cout, k, stride, int(relu), shift_segments, fold_div,
+                                       _lib.DTYPES[dtype], _stream(x)))
+        return y
+    a = _lib.TsmConvArgs()
+    a.struct_size = C.sizeof(_lib.TsmConvArgs)
+    a.x, a.w, a.gamma, a.beta, a.mean, a.var = x.data_ptr(), *[t.data_ptr() for t in args]
+    a.residual, a.y = _ptr(res), y.data_ptr()
+    a.n, a.hi, a.wi, a.cin, a.cout, a.k, a.stride, a.relu = n, hi, wi, cin, cout, k, stride, int(relu)
+    a.shift_segments, a.fold_div, a.dtype, a.shift_target = shift_segments, fold_div, _lib.DTYPES[dtype], int(shift_identity)
+    keep = []   # (the contiguous copies must outlive the call)
+    if x2 is not None:
+        if w2 is None or bn2 is None:
+            raise ValueError('a second source needs w2 and bn2')
+        _need_cuda_f32(**{f'bn2[{i}]': t for i, t in enumerate(bn2)})
+        x2c = x2.contiguous()
+        n2, hi2, wi2, cin2 = x2c.shape
+        if n2 != n or tuple(w2.shape) != (cout, cin2, 1, 1) or any(tuple(t.shape) != (cout,) for t in bn2):
+            raise ValueError(f'x2 {tuple(x2.shape)} / w2 {tuple(w2.shape)} / bn2 do not match x {tuple(x.shape)}, cout {cout}')
+        keep = [x2c] + [t.contiguous() for t in (w2, *bn2)]
+        a.x2, a.w2, a.gamma2, a.beta2, a.mean2, a.var2 = (t.data_ptr() for t in keep)
+        a.cin2, a.hi2, a.wi2, a.stride2 = cin2, hi2, wi2, stride2
+    a.code, a.reverse = int(code or 0), int(reverse)
+    _lib.check(lib.tsm_conv_op(C.byref(a), _stream(x)))
+    del keep
     return y
 
 

@@ -127,7 +127,11 @@ const char *tsm_build_id(void);
  * kernel's name as rocprofv3 would print it up to template-argument spelling, e.g. "bneck_ws_kernel<256, true, true>" or
  * "conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16> [BM = 64, BN = 64, ...]"; tsm_trace_launches(0) stops.
  * tsm_launch_trace copies the newline-separated trace (NUL-terminated) into buf when cap suffices and always returns the
- * bytes needed.  Off by default; per thread, like the engine-less error message: no process-global state.
+ * bytes needed.  A kernel that walks its output tiles / frames in a direction (conv_igemm, conv_bf16_256[p], the weight-
+ * stationary convs, bneck_ws, front_s2, conv31, conv23) ends its line with " [reverse]" when it walks from the far end:
+ * appended after everything else, so the line still ends in ']' and every prefix of it is unchanged.  A forward walk, and
+ * every launch without a walk, leaves the line as above.
+ * Off by default; per thread, like the engine-less error message: no process-global state.
  * (No counterpart in the reference: onnxruntime's session.run is opaque, utils/inference_count.py:273-275.) */
 int tsm_trace_launches(int32_t on);
 int64_t tsm_launch_trace(char *buf, int64_t cap);

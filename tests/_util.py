@@ -24,6 +24,49 @@ def ran_tile(trace, tile):
     return any(trace.ran(p) for p in TILE_KERNELS[tile])
 
 
+# the kernel families that walk their output tiles / frames in a direction; a reverse walk ends its trace line with the
+# marker (tsm_launch_trace: a bracket of its own, so a line still ends in ']' and every prefix of it still matches), every other launch (split-K reduction, stems, pack, head, conversions) never carries it
+WALKING = ('conv_igemm<', 'conv_bf16_256', 'conv3x3_ws', 'conv1x1_ws', 'bneck_ws_kernel<', 'front_s2_kernel<', 'conv31_',
+           'conv23_fused_kernel<')
+REVERSE_MARK = ' [reverse]'
+
+
+def walked(trace):
+    """The trace lines of kernels that walk their tiles / frames in a direction."""
+    assert not any(k.endswith(REVERSE_MARK) for k in trace.kernels if not k.startswith(WALKING)), trace.kernels
+    return [k for k in trace.kernels if k.startswith(WALKING)]
+
+
+def assert_walked(trace, reverse, what=''):
+    """Every tile-walking launch in the trace walked in the direction asked for (and there was one)."""
+    lines = walked(trace)
+    assert lines, f'{what}: no tile-walking launch in {trace.kernels}'
+    wrong = [k for k in lines if k.endswith(REVERSE_MARK) != bool(reverse)]
+    assert not wrong, f'{what}: asked for reverse={bool(reverse)}, these walked the other way: {wrong}'
+
+
+def sweep(codes, run, expect):
+    """Every code in both walk directions: bit-identical to the first run; `expect(code, trace)` checks what ran, and every
+    tile-walking launch carries the direction it was given."""
+    first = None
+    for code in codes:
+        for rev in (False, True):
+            y, tr = run(code, rev)
+            expect(code, tr)
+            assert_walked(tr, rev, f'code {code:#x}')
+            if first is None:
+                first = (code, rev, y)
+            else:
+                assert torch_equal(y, first[2]), (f'code {code:#x} reverse {rev} differs from code {first[0]:#x} '
+                                                  f'reverse {first[1]}')
+    return first[2]
+
+
+def torch_equal(a, b):
+    import torch
+    return torch.equal(a, b)
+
+
 def assert_ran(trace, prefix, what=''):
     assert trace.ran(prefix), f'{what}: no `{prefix}` launch; the trace holds {sorted(set(trace.kernels))}'
 

@@ -16,7 +16,7 @@ import torch
 
 from oracle.tsm_oracle import bf16_round, temporal_shift
 from tests._conv_ref import conv_ref
-from tests._util import IGEMM_TILE_DIMS, assert_bf16_op, assert_close, ran_tile
+from tests._util import IGEMM_TILE_DIMS, assert_bf16_op, assert_close, ran_tile, sweep as _sweep
 
 pytestmark = pytest.mark.gpu
 
@@ -81,21 +81,6 @@ def _run(x, w, bn, dtype, code, reverse, **kw):
 
 def _igemm(tr):
     return [k for k in tr.kernels if k.startswith('conv_igemm<')]
-
-
-def _sweep(codes, run, expect):
-    """Every code in both walk directions: bit-identical to the first run; `expect(code, trace)` checks what ran."""
-    first = None
-    for code in codes:
-        for rev in (False, True):
-            y, tr = run(code, rev)
-            expect(code, tr)
-            if first is None:
-                first = (code, rev, y)
-            else:
-                assert torch.equal(y, first[2]), (f'code {code:#x} reverse {rev} differs from code {first[0]:#x} '
-                                                  f'reverse {first[1]}')
-    return first[2]
 
 
 # ---- a. the shifted identity ------------------------------------------------------------------------------------------

@@ -950,7 +950,7 @@ template <int K3, int C, int N1, int CH>
 static hipError_t launch_c31(const Conv31Params &p, long ntiles, int n_cu, hipStream_t s) {
   constexpr size_t kLdsBytes = C31<K3, C, N1, CH>::kBytes;
   const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(512);
-  TSM_KLAUNCH((conv31_fused_kernel<K3, C, N1, CH>), grid, block, kLdsBytes, s, p);
+  TSM_KLAUNCH_WALK(p.reverse, (conv31_fused_kernel<K3, C, N1, CH>), grid, block, kLdsBytes, s, p);
   return hipGetLastError();
 }
 
@@ -961,7 +961,7 @@ template <int K3, int C, int N1>
 static hipError_t launch_c31p(const Conv31Params &p, long ntiles, int n_cu, hipStream_t s) {
   constexpr size_t kLdsBytes = C31P<K3, C, N1>::kBytes;
   const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(512);
-  TSM_KLAUNCH((conv31_pc_kernel<K3, C, N1>), grid, block, kLdsBytes, s, p);
+  TSM_KLAUNCH_WALK(p.reverse, (conv31_pc_kernel<K3, C, N1>), grid, block, kLdsBytes, s, p);
   return hipGetLastError();
 }
 

@@ -122,6 +122,14 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
     ::tsm::note_launch(#kern, __PRETTY_FUNCTION__);     \
     hipLaunchKernelGGL(kern, __VA_ARGS__);              \
   } while (0)
+// The same for a kernel that walks its output tiles / frames in either direction (`rev`: its params' reverse field): a
+// reverse walk appends " [reverse]" to the trace line, so a test can tell that the direction it asked for reached the kernel
+// (a bracket of its own: the line still ends in ']', and whatever prefix of it a test matches still matches).
+#define TSM_KLAUNCH_WALK(rev, kern, ...)                             \
+  do {                                                               \
+    ::tsm::note_launch(#kern, __PRETTY_FUNCTION__, (rev) ? 1 : 0);   \
+    hipLaunchKernelGGL(kern, __VA_ARGS__);                           \
+  } while (0)
 
 inline unsigned grid_for(int64_t total, int cap) {
   const int64_t blocks = (total + 255) / 256;

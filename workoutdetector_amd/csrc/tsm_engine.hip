@@ -143,6 +143,7 @@ struct tsm_engine {
   int fuse_block = -1;   // TSM_FUSE_BLOCK: the same for the whole-Bottleneck kernel (bf16, layer1.1 / layer1.2)
   int fuse31 = -1;       // TSM_FUSE_C3C1: the same for conv3 of block b + shift + conv1 of block b + 1 as one launch (bf16, layer2)
   int fuse_front = -1;   // TSM_FUSE_FRONT: the same for shift + conv1 + the stride-2 conv2 of layer2.0 as one launch (bf16)
+  int walk = -1;         // TSM_WALK: 0 / 1 every tile-walking launch walks forward / in reverse; unset: alternate (Forward::next_dir)
   int n_cu = 256;
   int timing_left = 0;
   bool timing_only3x3 = false;
@@ -580,7 +581,10 @@ struct Forward {
       : e(e_), s(s_), stage(stage_), tap(tap_), T(e_->cfg.num_segments), shiftT(e_->cfg.is_shift ? T : 0), prec(e_->prec),
         t1(e_->buf[2]), t2(e_->buf[3]), idb(e_->buf[4]) {}
 
-  int next_dir() { return flip ^= 1; }
+  // TSM_WALK pins every direction (tests: each walk of each kernel at the engine's geometries); the alternation still
+  // advances, so unset leaves the schedule exactly as it is
+  int dir(int d) const { return e->walk >= 0 ? e->walk : d; }
+  int next_dir() { return dir(flip ^= 1); }
   bool want(const std::string &name) const { return stage && name == stage; }
   int hit(const float *p, int64_t a, int64_t b, int64_t c, int64_t d) {
     tap->ptr = p; tap->shape[0] = a; tap->shape[1] = b; tap->shape[2] = c; tap->shape[3] = d; tap->hit = true;
@@ -748,11 +752,11 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   bool wins = false;
   int rc = conv(blk.conv1, L.p1, 1, false);
   if (rc) return rc;
-  L.p1.reverse = r1;
+  L.p1.reverse = dir(r1);
   if (prev31 >= 0 && e->fuse31 < 0) {   // the previous block's conv3 + this conv1 as one launch (both arms write the same bits)
     const int conv3 = e->blocks[prev31].conv3, code3 = codes[conv3], code1 = codes[blk.conv1];
     tsm::ConvParams pc = L.p1;
-    pc.reverse = prev.p3.reverse ^ 1;
+    pc.reverse = dir(prev.p3.reverse ^ 1);
     prev.q.reverse = prev.p3.reverse;
     rc = fused_wins([&] { return launch_pair(prev.p3, 1, code3, pc, 1, code1); },
                     [&] { return tsm::launch_conv31_fused(prev.q, s); }, &wins);
@@ -761,10 +765,10 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   }
   rc = conv(blk.conv2, L.p2, 3, true);
   if (rc) return rc;
-  L.p2.reverse = r1 ^ 1;
+  L.p2.reverse = dir(r1 ^ 1);
   if (can.front && e->fuse_front < 0) {   // shift + conv1 + conv2 as one launch (both arms write the same bits to t2)
     const int code1 = codes[blk.conv1], code2 = codes[blk.conv2];
-    L.pfr.reverse = r1;
+    L.pfr.reverse = dir(r1);
     rc = fused_wins([&] { return launch_pair(L.p1, 1, code1, L.p2, 3, code2); },
                     [&] { return tsm::launch_front_s2(L.pfr, s); }, &wins);
     if (rc) return rc;
@@ -772,12 +776,12 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   }
   rc = conv(blk.conv3, L.p3, 1, false);
   if (rc) return rc;
-  L.p3.reverse = r1;   // (what conv() gave it: r1, !r1, r1)
+  L.p3.reverse = dir(r1);   // (what conv() gave it: r1, !r1, r1)
   prev31 = can.conv31 ? (int)k : -1;
   prev = L;
   const int code1 = codes[blk.conv1], code2 = codes[blk.conv2], code3 = codes[blk.conv3];
-  L.pf.reverse = r1 ^ 1;
-  L.pb.reverse = r1;
+  L.pf.reverse = dir(r1 ^ 1);
+  L.pb.reverse = dir(r1);
   auto pair = [&] { return launch_pair(L.p2, 3, code2, L.p3, 1, code3); };
   auto fused23 = [&] { return tsm::launch_conv23_fused(L.pf, blk.cmid, prec, s); };
   bool use_fused = can.conv23 && e->fuse23 == 1;
@@ -992,6 +996,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   if (const char *fb = getenv("TSM_FUSE_BLOCK")) e->fuse_block = atoi(fb) != 0;
   if (const char *f31 = getenv("TSM_FUSE_C3C1")) e->fuse31 = atoi(f31) != 0;
   if (const char *ff = getenv("TSM_FUSE_FRONT")) e->fuse_front = atoi(ff) != 0;
+  if (const char *wk = getenv("TSM_WALK")) e->walk = atoi(wk) != 0;
   // TSM_TUNE_CACHE=<file> names the tune cache; unset: a per-user default ($XDG_CACHE_HOME or $HOME/.cache, then
   // tsm_hip/tune_cache.txt), so that the second process on a machine pays no tuning pass; "", "0" or "off" disables it.
   {

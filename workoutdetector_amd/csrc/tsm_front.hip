@@ -367,8 +367,8 @@ hipError_t launch_front_s2(const FrontParams &p, hipStream_t s) {
   const DeviceInfo &di = device_info();
   if (di.status != hipSuccess) return di.status;
   const dim3 grid((unsigned)(p.N < di.n_cu ? p.N : di.n_cu)), block(256);
-  if (p.T > 0) TSM_KLAUNCH(front_s2_kernel<true>, grid, block, kFrBytes, s, p);
-  else TSM_KLAUNCH(front_s2_kernel<false>, grid, block, kFrBytes, s, p);
+  if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, front_s2_kernel<true>, grid, block, kFrBytes, s, p);
+  else TSM_KLAUNCH_WALK(p.reverse, front_s2_kernel<false>, grid, block, kFrBytes, s, p);
   return hipGetLastError();
 }
 

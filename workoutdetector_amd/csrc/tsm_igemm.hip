@@ -780,15 +780,15 @@ static hipError_t launch_conv_seg(ConvParams p, hipStream_t s) {
     const dim3 block(64 * WGM * WGN);
     if constexpr (KS == 1 && !SHIFT) {
       if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
         return hipGetLastError();
       }
       if (p.x2) {
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
         return hipGetLastError();
       }
     }
-    TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, false, kPrecF32, false, true>), grid, block, 0, s, p);
+    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, false, kPrecF32, false, true>), grid, block, 0, s, p);
     return hipGetLastError();
   }
 }
@@ -805,40 +805,40 @@ static hipError_t launch_conv_t(ConvParams p, hipStream_t s) {
   if constexpr (KS == 1 && !SHIFT && !RES) {
     if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
       if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       return hipGetLastError();
     }
     if (p.x2) {
       if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
       return hipGetLastError();
     }
   }
   if constexpr (RES && !SHIFT && KS != 7) {
     if (p.T > 0) {   // block placement: the identity through the shift
       if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16x3 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16x3 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
       else
-        TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecF32 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecF32 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
       return hipGetLastError();
     }
   }
   if (p.prec == kPrecBf16x3)
-    TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16x3>), grid, dim3(64 * WGM * WGN), 0, s, p);
+    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16x3>), grid, dim3(64 * WGM * WGN), 0, s, p);
   else if (p.prec == kPrecBf16)
-    TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16>), grid, dim3(64 * WGM * WGN), 0, s, p);
+    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16>), grid, dim3(64 * WGM * WGN), 0, s, p);
   else
-    TSM_KLAUNCH((conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecF32>), grid, dim3(64 * WGM * WGN), 0, s, p);
+    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecF32>), grid, dim3(64 * WGM * WGN), 0, s, p);
   return hipGetLastError();
 }
 

@@ -221,7 +221,8 @@ hipError_t launch_scores_to_states(const float *logits, int n, int c, int softma
                                    hipStream_t s);
 
 // Launch trace of the calling thread (tsm_trace_launches / tsm_launch_trace in include/tsm_hip.h; tsm_ops.hip).
-void note_launch(const char *kernel, const char *where);
+// reverse: -1 for a kernel without a tile walk; 0 / 1 the direction of one that has one (1 appends " [reverse]")
+void note_launch(const char *kernel, const char *where, int reverse = -1);
 void trace_launches(bool on);
 const char *launch_trace();   // newline-separated, valid until the thread's next trace call
 

@@ -1260,7 +1260,7 @@ hipError_t launch_conv3x3_ws(ConvParams p, hipStream_t s) {
     const long ntiles = (long)q.N * ((p.Ho + q.tr - 1) / q.tr) * ((p.Wo + q.tc - 1) / q.tc);
     const int n_cu = ws_grid_setup();
     if (device_info().status != hipSuccess) return device_info().status;
-    TSM_KLAUNCH(conv3x3_ws128_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kS2LdsBytes, s, q);
+    TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kS2LdsBytes, s, q);
     return hipGetLastError();
   }
   if (conv3x3_ws128_valid(p)) {
@@ -1271,7 +1271,7 @@ hipError_t launch_conv3x3_ws(ConvParams p, hipStream_t s) {
     const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
     const int n_cu = ws_grid_setup();
     if (device_info().status != hipSuccess) return device_info().status;
-    TSM_KLAUNCH(conv3x3_ws128_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kW8LdsBytes, s, q);
+    TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kW8LdsBytes, s, q);
     return hipGetLastError();
   }
   if (!conv3x3_ws_valid(p)) return hipErrorInvalidValue;
@@ -1282,7 +1282,7 @@ hipError_t launch_conv3x3_ws(ConvParams p, hipStream_t s) {
   const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
   const int n_cu = ws_grid_setup();
   if (device_info().status != hipSuccess) return device_info().status;
-  TSM_KLAUNCH(conv3x3_ws_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes, s, q);
+  TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes, s, q);
   return hipGetLastError();
 }
 
@@ -1295,8 +1295,8 @@ hipError_t launch_conv1x1_ws(const ConvParams &p, hipStream_t s) {
   if (device_info().status != hipSuccess) return device_info().status;
   const int ntiles = (p.M + 127) / 128;
   const unsigned grid = (unsigned)(ntiles < n_cu ? ntiles : n_cu);
-  if (p.C == 256) TSM_KLAUNCH(conv1x1_ws_kernel<256>, dim3(grid), dim3(256), 2 * 16 * 4096 + 256, s, q);
-  else TSM_KLAUNCH(conv1x1_ws_kernel<64>, dim3(grid), dim3(256), 2 * 4 * 4096 + 256, s, q);
+  if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<256>, dim3(grid), dim3(256), 2 * 16 * 4096 + 256, s, q);
+  else TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<64>, dim3(grid), dim3(256), 2 * 4 * 4096 + 256, s, q);
   return hipGetLastError();
 }
 
@@ -1315,11 +1315,11 @@ hipError_t launch_conv1x1_wsn(const ConvParams &p, hipStream_t s) {
   if (p.x2 && p.Kp == 384) {
     const int pairs = n_cu >> 4 << 3;                                     // workgroup pairs: a multiple of 8 (b and b + 8 share an XCD)
     const int np = ntiles < pairs ? (ntiles + 7) / 8 * 8 : pairs;         // (a pair without a tile leaves at once)
-    TSM_KLAUNCH((conv1x1_wsn_kernel<384, 256, true, 2>), dim3((unsigned)(2 * np)), block, 2 * 24 * 2048 + 1024, s, q);
-  } else if (p.x2) TSM_KLAUNCH((conv1x1_wsn_kernel<128, 256, true>), grid, block, kLds, s, q);
-  else if (p.C == 256) TSM_KLAUNCH((conv1x1_wsn_kernel<256, 128, false>), grid, block, kLds, s, q);
-  else if (p.Cout == 128) TSM_KLAUNCH((conv1x1_wsn_kernel<512, 128, false>), grid, block, kLds, s, q);
-  else TSM_KLAUNCH((conv1x1_wsn_kernel<512, 256, false>), grid, block, kLds, s, q);
+    TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<384, 256, true, 2>), dim3((unsigned)(2 * np)), block, 2 * 24 * 2048 + 1024, s, q);
+  } else if (p.x2) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<128, 256, true>), grid, block, kLds, s, q);
+  else if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<256, 128, false>), grid, block, kLds, s, q);
+  else if (p.Cout == 128) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 128, false>), grid, block, kLds, s, q);
+  else TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 256, false>), grid, block, kLds, s, q);
   return hipGetLastError();
 }
 
@@ -1338,7 +1338,7 @@ hipError_t launch_conv23_ws(const Fused23Params &p, hipStream_t s) {
   const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
   const int n_cu = ws_grid_setup();
   if (device_info().status != hipSuccess) return device_info().status;
-  TSM_KLAUNCH(conv3x3_ws_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes3All, s, q);
+  TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes3All, s, q);
   return hipGetLastError();
 }
 

@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width (added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -148,6 +148,13 @@ const char *tsm_last_error(const tsm_engine *e);
  * State-dict keys of a BasicBlock: "base_model.layerL.B.conv1.net.weight" (or ".conv1.weight"), ".bn1.*",
  * ".conv2.weight", ".bn2.*", ".downsample.0.weight", ".downsample.1.*". */
 int tsm_set_backbone(tsm_engine *e, int32_t depth);
+
+/* Bottleneck width of the engine: torchvision's width_per_group.  64 (default: every Bottleneck's mid width is its stage's
+ * planes, 64 / 128 / 256 / 512) or 128 (wide_resnet50_2: mid widths 128 / 256 / 512 / 1024, block outputs still 256 / 512 /
+ * 1024 / 2048, the same state-dict keys as resnet50).  Same contract as tsm_set_backbone: legal between tsm_create and the
+ * first tsm_set_tensor, later TSM_ERR_INVALID_ARG; any other value TSM_ERR_UNSUPPORTED, and so is 128 together with a
+ * BasicBlock depth (18 / 34), whichever of the two calls comes second -- torchvision refuses base_width != 64 there. */
+int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group);
 
 /* Placement of the temporal shift -- create_model(shift_place=...), workoutdetector/models/tsm.py:104-124:
  * 0 = 'blockres' (default: the shift wraps conv1 of every block, the identity sees the unshifted input), 1 = 'block' (it

@@ -1,6 +1,6 @@
-"""Clip throughput of the TSM backbones (R18 / R34 / R50) side by side on one GPU: one JSON line per (backbone, dtype).
+"""Clip throughput of the TSM backbones (R18 / R34 / R50 / WRN-50-2) side by side on one GPU: one JSON line per (backbone, dtype).
 
-    python tools/backbone_bench.py [--backbones resnet18,resnet34,resnet50] [--dtypes f32,bf16] [--batch 32]
+    python tools/backbone_bench.py [--backbones resnet18,resnet34,resnet50,wide_resnet50_2] [--dtypes f32,bf16] [--batch 32]
                                    [--segments 8] [--size 224] [--steps 20] [--warmup 5] [--shift-place blockres,block]
 
 One line per (backbone, dtype, shift placement).  Each engine gets the seeded synthetic weights of its backbone
@@ -14,7 +14,8 @@ and K timed forwards run back to back on torch's current stream, one event per s
   peak_frac        achieved FLOP/s over the exact-fp32 MFMA peak (f32) or the dense bf16 MFMA peak (bf16, bf16x3): a
                    whole-forward figure, not a kernel's share of peak
   logits_err       max |logits - CPU restatement| / max |CPU restatement| on the first two clips of the last timed step:
-                   fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py for R50,
+                   fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py for R50 and
+                   WRN-50-2, whose Bottlenecks take every shape from the state dict,
                    tests/_basicblock_ref.py for R18 / R34, tests/_block_place_ref.py for block placement)
 
 No CPU fallback: without a GPU it fails.
@@ -38,6 +39,8 @@ def reference_logits(base_model, sd, clips, t, dtype, shift_place='blockres'):
     from tests import _basicblock_ref
     sd_t = {k: torch.from_numpy(v) for k, v in sd.items()}
     bf16 = dtype == 'bf16'
+    if base_model == 'wide_resnet50_2':   # R50's schedule: the oracle's Bottleneck reads every width from the state dict
+        base_model = 'resnet50'
     if shift_place == 'block':
         from tests import _block_place_ref
         return _block_place_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()

@@ -41,7 +41,7 @@ class TsmConvArgs(C.Structure):
                 + [(n, C.c_int32) for n in ('cin2', 'hi2', 'wi2', 'stride2', 'code', 'reverse')])
 
 
-EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_shift_place', 'tsm_set_tensor', 'tsm_finalize',
+EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
            'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
 
@@ -82,6 +82,8 @@ def load() -> C.CDLL:
     lib.tsm_last_error.argtypes = [vp]
     lib.tsm_set_backbone.restype = C.c_int
     lib.tsm_set_backbone.argtypes = [vp, i32]
+    lib.tsm_set_bottleneck_width.restype = C.c_int
+    lib.tsm_set_bottleneck_width.argtypes = [vp, i32]
     lib.tsm_set_shift_place.restype = C.c_int
     lib.tsm_set_shift_place.argtypes = [vp, i32]
     lib.tsm_set_tensor.restype = C.c_int

@@ -39,7 +39,8 @@ using namespace tsm_host;
 const char kBuildTag[] = "tsm-build-id:" TSM_BUILD_ID;
 
 // Backbones by depth: blocks per stage and the block type.  Planes are 64, 128, 256, 512 for all of them; a Bottleneck widens
-// its output by 4, a BasicBlock by 1 (torchvision resnet18 / resnet34 / resnet50).
+// its output by 4, a BasicBlock by 1 (torchvision resnet18 / resnet34 / resnet50).  A Bottleneck's mid width is planes *
+// width_per_group / 64 (tsm_set_bottleneck_width: 64, or 128 for wide_resnet50_2).
 struct Backbone {
   int depth;
   int blocks[4];
@@ -83,10 +84,12 @@ struct Block {
   int kpf = 0;
   int ksegf = 0;  // segment length of the fused GEMM
   // conv2 + conv3 (+ residual) as ONE kernel (tsm::launch_conv23_fused): fp32 / split-bf16 blocks without a downsample branch whose
-  // mid tensor has 64 / 128 channels (layer1.1-2, layer2.1-3); d_w3f = conv3's folded weights in fragment order
+  // mid tensor has 64 / 128 channels and conv3 4x as many (layer1.1-2, layer2.1-3), or 128 channels and conv3 2x as many
+  // (wide_resnet50_2's layer1.1-2); d_w3f = conv3's folded weights in fragment order
   // (fp32 / split-bf16; the bf16 form, 64 channels only, reads conv3's own packed matrix: d_w3f stays null, cmid = 64)
   float *d_w3f = nullptr;
   int cmid = 0;
+  int cout3 = 0;   // conv3's output channels where cmid is set: 4 * cmid, or 2 * cmid (conv23_fused2_kernel)
 };
 
 int ilog2(int v) {
@@ -100,6 +103,7 @@ int ilog2(int v) {
 struct tsm_engine {
   tsm_config cfg{};
   int depth = 50;             // tsm_set_backbone
+  int width = 64;             // tsm_set_bottleneck_width: torchvision's width_per_group
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
   int feat = 2048;            // channels of the last stage = the classifier's input width
   bool weights_started = false;   // a tsm_set_tensor call has been made: the backbone is fixed
@@ -183,6 +187,7 @@ void build_topology(tsm_engine *e) {
   for (int li = 0; li < 4; ++li) {
     for (int b = 0; b < bb.blocks[li]; ++b) {
       const int planes = kPlanes[li];
+      const int mid = planes * e->width / 64;   // (Bottleneck only: a BasicBlock engine is always width 64)
       const int stride = (b == 0 && li > 0) ? 2 : 1;
       // block placement wraps the whole block in TemporalShift: its tensors are "layerL.B.net.<name>", conv1 unwrapped
       const bool bp = e->place == 1;
@@ -213,11 +218,11 @@ void build_topology(tsm_engine *e) {
         continue;
       }
       ConvLayer c1; c1.wkey = c1key; c1.bnp = p + ".bn1";
-      c1.cin = cin; c1.cout = planes; c1.k = 1; c1.stride = 1; c1.cp = cin; c1.kp = cin;
+      c1.cin = cin; c1.cout = mid; c1.k = 1; c1.stride = 1; c1.cp = cin; c1.kp = cin;
       ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
-      c2.cin = planes; c2.cout = planes; c2.k = 3; c2.stride = stride; c2.cp = planes; c2.kp = 9 * planes;
+      c2.cin = mid; c2.cout = mid; c2.k = 3; c2.stride = stride; c2.cp = mid; c2.kp = 9 * mid;
       ConvLayer c3; c3.wkey = p + ".conv3.weight"; c3.bnp = p + ".bn3";
-      c3.cin = planes; c3.cout = planes * 4; c3.k = 1; c3.stride = 1; c3.cp = planes; c3.kp = planes;
+      c3.cin = mid; c3.cout = planes * 4; c3.k = 1; c3.stride = 1; c3.cp = mid; c3.kp = mid;
       c1.kseg = segment_len(c1.kp, e->prec);
       c2.kseg = segment_len(c2.kp, e->prec);
       blk.conv1 = (int)e->convs.size(); e->convs.push_back(c1);
@@ -720,7 +725,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
     if (want(name + ".conv1")) return hit(t1, nn, hh, ww, c1out);
     if (plan.conv23) {
       L.pf.reverse = next_dir();
-      TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(L.pf, blk.cmid, prec, s));
+      TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(L.pf, blk.cmid, blk.cout3, prec, s));
       skip_slots(e, 1);   // conv3
       return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
     }
@@ -783,7 +788,7 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   L.pf.reverse = dir(r1 ^ 1);
   L.pb.reverse = dir(r1);
   auto pair = [&] { return launch_pair(L.p2, 3, code2, L.p3, 1, code3); };
-  auto fused23 = [&] { return tsm::launch_conv23_fused(L.pf, blk.cmid, prec, s); };
+  auto fused23 = [&] { return tsm::launch_conv23_fused(L.pf, blk.cmid, blk.cout3, prec, s); };
   bool use_fused = can.conv23 && e->fuse23 == 1;
   if (can.conv23 && e->fuse23 < 0) {   // conv2 + conv3 as one launch against the pair
     rc = fused_wins(pair, fused23, &use_fused);
@@ -907,12 +912,14 @@ hipStream_t pick_stream(tsm_engine *e, int memkind, void *stream) {
   return memkind == TSM_MEM_HOST ? e->stream : nullptr;
 }
 
-// Tuned codes of one backbone or placement are never read by another: " r<depth>" for a backbone other than R50, " block"
-// for block placement (an R50 blockres engine keeps the bare signature, so existing cache lines stay valid).
+// Tuned codes of one backbone or placement are never read by another: " r<depth>" for a backbone other than R50, " w<width>"
+// for a wide one, " block" for block placement (an R50 blockres engine keeps the bare signature, so existing cache lines stay
+// valid).
 void retag_tune_sig(tsm_engine *e) {
   if (e->tune_sig.empty()) return;
   e->tune_sig.resize(e->tune_sig_base);
   if (e->depth != 50) e->tune_sig += " r" + std::to_string(e->depth);
+  if (e->width != 64) e->tune_sig += " w" + std::to_string(e->width);
   if (e->place == 1) e->tune_sig += " block";
 }
 
@@ -1042,7 +1049,25 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
   if (e->weights_started || e->finalized)
     return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_backbone must come before the first tsm_set_tensor");
   if (!find_backbone(depth)) return fail(e, TSM_ERR_UNSUPPORTED, "depth must be 18, 34 or 50");
+  if (find_backbone(depth)->basic && e->width != 64)
+    return fail(e, TSM_ERR_UNSUPPORTED, "a BasicBlock backbone (depth 18 / 34) has no bottleneck width: the engine's is " +
+                                            std::to_string(e->width));
   e->depth = depth;
+  build_topology(e);
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
+  if (!e) return TSM_ERR_INVALID_ARG;
+  if (e->weights_started || e->finalized)
+    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_bottleneck_width must come before the first tsm_set_tensor");
+  if (width_per_group != 64 && width_per_group != 128)
+    return fail(e, TSM_ERR_UNSUPPORTED, "width_per_group must be 64 or 128 (wide_resnet50_2)");
+  if (width_per_group != 64 && find_backbone(e->depth)->basic)
+    return fail(e, TSM_ERR_UNSUPPORTED, "width_per_group 128 needs a Bottleneck backbone (depth 50): torchvision's BasicBlock "
+                                        "supports 64 only");
+  e->width = width_per_group;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1149,24 +1174,28 @@ int tsm_finalize(tsm_engine *e) {
     TSM_HIP(e, hipMemcpy(blk.d_wf, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
     TSM_HIP(e, hipMemcpy(blk.d_bf, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide: conv3's weights once more, in the
-  // fragment order of the fused conv2 + conv3 kernel (fp32 and split-bf16 engines).
+  // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide and whose conv3 has 4x as many outputs
+  // (conv23_fused_kernel: four phase-C chunks), or 128 wide with 2x as many (conv23_fused2_kernel, wide_resnet50_2's
+  // layer1.1-2: two chunks): conv3's weights once more, in the fragment order of the fused conv2 + conv3 kernel (fp32 and
+  // split-bf16 engines).  Any other mid / output pair keeps the two separate launches.
   for (Block &blk : e->blocks) {
     if (blk.conv3 < 0) continue;   // (Bottlenecks only)
     const ConvLayer &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
     if (blk.down >= 0 || blk.stride != 1 || (c2.cout != 64 && c2.cout != 128)) continue;
     if (e->prec == tsm::kPrecBf16) {   // weight-stationary form: 64 mid channels only; it reads conv3's packed matrix itself
-      if (c2.cout == 64 && c2.cin == 64 && c3.cout == 256) blk.cmid = 64;
+      if (c2.cout == 64 && c2.cin == 64 && c3.cout == 256) { blk.cmid = 64; blk.cout3 = 256; }
       continue;
     }
+    const int nchunk = c3.cout == 4 * c2.cout ? 4 : (c3.cout == 2 * c2.cout && c2.cout == 128) ? 2 : 0;
+    if (nchunk == 0) continue;
     std::vector<float> w3f;
-    if (e->prec == tsm::kPrecBf16x3) pack_w3_fragments_split(host_wp[blk.conv3].data(), c2.cout, &w3f);
-    else pack_w3_fragments(host_wp[blk.conv3].data(), c2.cout, &w3f);
+    if (e->prec == tsm::kPrecBf16x3) pack_w3_fragments_split(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
+    else pack_w3_fragments(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
     int rcw = dev_alloc(e, &blk.d_w3f, w3f.size());
     if (rcw) return rcw;
     TSM_HIP(e, hipMemcpy(blk.d_w3f, w3f.data(), w3f.size() * sizeof(float), hipMemcpyHostToDevice));
     blk.cmid = c2.cout;
-    (void)c3;
+    blk.cout3 = c3.cout;
   }
   host_wp.clear();
   host_bias.clear();

@@ -139,15 +139,16 @@ inline int tile_bucket(int n_clips) {
 }
 
 
-// conv3 weights of a fused conv2+conv3 block (conv23_fused_kernel) in MFMA-fragment order.  w3p is the packed,
-// BN-folded matrix [4 * cmid][cmid]; the kernel's wave `wn` (of cmid / 32) loads, for output chunk j (of 4, cmid
-// channels each) and k-group kk (of cmid / 8), ONE 16-byte element per lane:
+// conv3 weights of a fused conv2+conv3 block (conv23_fused_kernel / conv23_fused2_kernel) in MFMA-fragment order.  w3p is
+// the packed, BN-folded matrix [nchunk * cmid][cmid] (nchunk = 4, or 2 for the Cout = 2 * cmid form); the kernel's wave
+// `wn` (of cmid / 32) loads, for output chunk j (of nchunk, cmid channels each) and k-group kk (of cmid / 8), ONE 16-byte
+// element per lane:
 //   out[(((j * wgn + wn) * nkk + kk) * 64 + lane) * 4 + s] = W3[n = j * cmid + wn * 32 + (lane & 31)][k = 8 kk + 4 (lane >> 5) + s]
 // i.e. exactly the B operand of v_mfma_f32_32x32x2_f32 step s of that k-group, so the load is lane-linear (coalesced).
-inline void pack_w3_fragments(const float *w3p, int cmid, std::vector<float> *out) {
+inline void pack_w3_fragments(const float *w3p, int cmid, std::vector<float> *out, int nchunk = 4) {
   const int wgn = cmid / 32, nkk = cmid / 8;
-  out->assign((size_t)4 * cmid * cmid, 0.f);
-  for (int j = 0; j < 4; ++j)
+  out->assign((size_t)nchunk * cmid * cmid, 0.f);
+  for (int j = 0; j < nchunk; ++j)
     for (int wn = 0; wn < wgn; ++wn)
       for (int kk = 0; kk < nkk; ++kk)
         for (int lane = 0; lane < 64; ++lane)
@@ -161,11 +162,11 @@ inline void pack_w3_fragments(const float *w3p, int cmid, std::vector<float> *ou
 // per lane, the hi and the lo halves of the 8 channels k = 16 kq + 8 (lane >> 5) + 0..7 of row n:
 //   element (((j * wgn + wn) * (2 * nkq) + 2 * kq + part) * 64 + lane), part 0 = hi x8, 1 = lo x8  (bf16 pairs per float slot)
 // with hi = bf16(w), lo = bf16(w - hi) exactly as to_split() stores the conv3 weights of the un-fused path.
-inline void pack_w3_fragments_split(const float *w3p, int cmid, std::vector<float> *out) {
+inline void pack_w3_fragments_split(const float *w3p, int cmid, std::vector<float> *out, int nchunk = 4) {
   const int wgn = cmid / 32, nkq = cmid / 16;
-  out->assign((size_t)4 * cmid * cmid, 0.f);
+  out->assign((size_t)nchunk * cmid * cmid, 0.f);
   uint16_t *o = reinterpret_cast<uint16_t *>(out->data());
-  for (int j = 0; j < 4; ++j)
+  for (int j = 0; j < nchunk; ++j)
     for (int wn = 0; wn < wgn; ++wn)
       for (int kq = 0; kq < nkq; ++kq)
         for (int lane = 0; lane < 64; ++lane) {

@@ -76,7 +76,8 @@ bool conv1x1_ws_valid(const ConvParams &p);   // 1x1, 64 / 256 -> 64 channels, o
 // ks in {1, 3, 7}.  Returns hipSuccess or the launch error.
 hipError_t launch_conv(const ConvParams &p, int ks, hipStream_t s);
 // Bottleneck.conv2 (3x3, stride 1, pad 1) + bn2 + ReLU + conv3 (1x1) + bn3 + residual + ReLU as ONE launch (fp32 or split-bf16),
-// for CMID = 64 / 128 (layer1 / layer2 blocks without a downsample branch).  Bit-identical to launch_conv(conv2)
+// for CMID = 64 / 128 (layer1 / layer2 blocks without a downsample branch; Cout3 = 4 * CMID), and for CMID = 128 with
+// Cout3 = 2 * CMID (wide_resnet50_2's layer1.1-2; conv23_fused2_kernel).  Bit-identical to launch_conv(conv2)
 // followed by launch_conv(conv3 with residual).  prec == kPrecBf16: CMID = 64 only, on the weight-stationary kernel
 // (conv3x3_ws_kernel<true>); w3f is then conv3's packed weight matrix [256][64] bf16 itself (no fragment packing).
 struct Fused23Params {
@@ -84,15 +85,16 @@ struct Fused23Params {
   const float *w2;     // [CMID][9 * CMID]  conv2 weights, K = (ky, kx, c), bn2 scale folded in
   const float *bias2;  // [CMID]
   const float *w3f;    // conv3 weights (bn3 scale folded in) in MFMA-fragment order, tsm_host::pack_w3_fragments[_split]
-  const float *bias3;  // [4 * CMID]
-  const float *res;    // [M, 4 * CMID]  the block input (identity branch)
-  float *y;            // [M, 4 * CMID]
+  const float *bias3;  // [Cout3]  (Cout3 = 4 * CMID, or 2 * CMID: launch_conv23_fused's cout3)
+  const float *res;    // [M, Cout3]  the block input (identity branch)
+  float *y;            // [M, Cout3]
   int N, H, W;
   int M;               // N * H * W
   int kseg_len;        // conv2's K-segment length (ConvParams::kseg_len of that layer; 0 = unsegmented)
   int reverse;         // walk the tiles from the last one to the first (ConvParams::reverse)
 };
-hipError_t launch_conv23_fused(const Fused23Params &p, int cmid, int prec, hipStream_t s);
+// cout3 = conv3's output channels: 4 * cmid (conv23_fused_kernel), or 2 * cmid with cmid = 128 (conv23_fused2_kernel)
+hipError_t launch_conv23_fused(const Fused23Params &p, int cmid, int cout3, int prec, hipStream_t s);
 // Does the bf16 form apply to n frames of h x w pixels?
 bool conv23_ws_valid(int n, int h, int w);
 

@@ -1,4 +1,4 @@
-"""TsmEngine: Python host side of the MI355X TSM-ResNet clip-inference engine (R50; R18 / R34 via ``base_model``).
+"""TsmEngine: Python host side of the MI355X TSM-ResNet clip-inference engine (R50; R18 / R34 / WRN-50-2 via ``base_model``).
 
 Drop-in for the two duck types the reference's hot path is written against:
 
@@ -22,7 +22,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
+from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
                       remap_mmaction_keys)
 
 
@@ -66,8 +66,10 @@ class TsmEngine:
         cfg = _lib.TsmConfig(C.sizeof(_lib.TsmConfig), num_class, num_segments, height, width, shift_div,
                              1 if is_shift else 0, max_clips, device, _lib.DTYPES[dtype])
         _lib.check(self._lib.tsm_create(C.byref(cfg), C.byref(self._h)))
-        if base_model != 'resnet50':
+        if DEPTHS[base_model] != 50:
             _lib.check(self._lib.tsm_set_backbone(self._h, DEPTHS[base_model]), self._h)
+        if base_model in WIDTHS:
+            _lib.check(self._lib.tsm_set_bottleneck_width(self._h, WIDTHS[base_model]), self._h)
         if shift_place != 'blockres':
             _lib.check(self._lib.tsm_set_shift_place(self._h, SHIFT_PLACES[shift_place]), self._h)
         self._finalized = False
@@ -312,7 +314,8 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     ``onnx_import.load_onnx_state_dict``.
     Without a checkpoint the reference starts from torchvision's ImageNet weights, which cannot be
     fetched offline: the engine then gets the seeded synthetic weights of ``weights.make_state_dict``.
-    ``base_model``: 'resnet50' (Bottleneck), 'resnet18' or 'resnet34' (BasicBlock: the shift fused into the 3x3 conv1,
+    ``base_model``: 'resnet50' (Bottleneck), 'wide_resnet50_2' (Bottleneck, mid widths doubled: torchvision's
+    width_per_group = 128; the keys are R50's), 'resnet18' or 'resnet34' (BasicBlock: the shift fused into the 3x3 conv1,
     fc [num_class, 512]); any other backbone raises NotImplementedError.
     ``shift_place``: 'blockres' (the shift wraps conv1 of every block) or 'block' (it wraps every block whole: the identity
     and the downsample read the shifted input too; state-dict keys ``base_model.layerL.B.net.*``); anything else raises

@@ -1,7 +1,7 @@
 """Algorithmic work of the TSM-ResNet forward: per-layer GEMM shapes and MACs.
 
 Used by ``bench.py`` (roofline accounting) and ``tools/``; derived from ``weights.conv_specs()`` and the spatial
-schedule of ResNet-50 v1.5 (7x7 s2 stem, 3x3 s2 max-pool, stride on the 3x3 of each stage's first block) or of
+schedule of ResNet-50 v1.5 / Wide-ResNet-50-2 (7x7 s2 stem, 3x3 s2 max-pool, stride on the 3x3 of each stage's first block) or of
 ResNet-18 / 34 (BasicBlock: stride on conv1).
 Shift, BN fold, ReLU, pooling and the segment mean count zero FLOPs.
 """

@@ -1,4 +1,4 @@
-"""Weights from an exported ``.onnx`` TSM model (R50, R18 or R34) -> engine state dict, without the ``onnx`` package.
+"""Weights from an exported ``.onnx`` TSM model (R50, WRN-50-2, R18 or R34) -> engine state dict, without the ``onnx`` package.
 
 The reference deploys ``checkpoints/*.onnx`` produced by ``torch.onnx.export(model, sample[1,8,3,224,224],
 opset_version=11)`` (workoutdetector/scripts/export_model.py:35-47, trainer.py:325-330) and runs it with
@@ -17,8 +17,8 @@ fields needed) and maps the tensors onto the engine's ``TSM.state_dict()`` keys:
     a 1x1), the weight shape must agree, and anything ambiguous or missing raises -- and every conv gets an identity
     BatchNorm carrying its bias.
 
-The backbone is read from the graph: 53 Conv nodes and a 2048-wide classifier are R50, 20 / 36 Conv nodes, no
-``conv3`` and a 512-wide classifier are R18 / R34.
+The backbone is read from the graph: 53 Conv nodes and a 2048-wide classifier are R50, or WRN-50-2 where layer1.0.conv1
+is 128 channels wide instead of 64; 20 / 36 Conv nodes, no ``conv3`` and a 512-wide classifier are R18 / R34.
 
 Tested on files written by torch's own exporter (``torch.onnx.export(..., opset_version=11)`` of an nn.Module with
 the reference's module tree, both export styles; tests/_torch_tsm.py) and on hand-written files
@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .weights import DEPTHS, conv_specs, feature_width
+from .weights import BACKBONES, DEPTHS, conv_specs, feature_width
 
 BN_EPS = 1e-5
 
@@ -188,22 +188,45 @@ def _resolve_convs(path: str, nodes: List[dict], inits: Dict[str, np.ndarray], s
     return out
 
 
+def _layer1_mid_width(inits: Dict[str, np.ndarray], nodes: List[dict]) -> int:
+    """Output width of layer1.0.conv1 = input width of the first 3x3 Conv after the 7x7 stem (layer1.0.conv2), whatever
+    order the export wrote conv1 and the downsample in."""
+    for n in nodes:
+        if n['op_type'] != 'Conv' or len(n['input']) < 2:
+            continue
+        w = inits.get(n['input'][1])
+        if w is not None and w.ndim == 4 and w.shape[2:] == (3, 3):
+            return int(w.shape[1])
+    raise ValueError('no 3x3 Conv node with an initialiser weight: cannot tell the bottleneck width')
+
+
 def detect_backbone(inits: Dict[str, np.ndarray], nodes: List[dict]) -> str:
-    """'resnet18' | 'resnet34' | 'resnet50' from the graph: the Conv node count (20 / 36 / 53 -- the stem, two or three
-    convs per block, the downsample convs), checked against the state-dict names where the export kept them."""
+    """'resnet18' | 'resnet34' | 'resnet50' | 'wide_resnet50_2' from the graph: the Conv node count (20 / 36 / 53 / 53 --
+    the stem, two or three convs per block, the downsample convs), then, where the count is shared (R50 and WRN-50-2),
+    the output width of layer1.0.conv1 (64 / 128); checked against the state-dict names where the export kept them."""
     n_conv = sum(n['op_type'] == 'Conv' for n in nodes)
-    by_count = {len(conv_specs(m)): m for m in DEPTHS}
+    by_count: Dict[int, List[str]] = {}
+    for m in DEPTHS:
+        by_count.setdefault(len(conv_specs(m)), []).append(m)
     if n_conv not in by_count:
-        raise ValueError(f'{n_conv} Conv nodes: not a TSM-ResNet18 / 34 / 50 ({sorted(by_count)})')
-    model = by_count[n_conv]
-    if model != 'resnet50' and any('.conv3.' in k for k in inits):   # (a folded export has anonymous names: counts only)
+        raise ValueError(f'{n_conv} Conv nodes: not a TSM-ResNet18 / 34 / 50 or WRN-50-2 ({sorted(by_count)})')
+    cands = by_count[n_conv]
+    if len(cands) > 1:
+        width = _layer1_mid_width(inits, nodes)
+        by_width = {conv_specs(m)[1][2]: m for m in cands}   # (conv_specs()[1] = layer1.0.conv1)
+        if width not in by_width:
+            raise ValueError(f'{n_conv} Conv nodes, layer1.0.conv1 {width} channels wide: not one of '
+                             f'{", ".join(f"{m} ({w})" for w, m in sorted(by_width.items()))}')
+        cands = [by_width[width]]
+    model = cands[0]
+    if BACKBONES[model][1] != 'bottleneck' and any('.conv3.' in k for k in inits):   # (a folded export has anonymous names: counts only)
         raise ValueError(f'{n_conv} Conv nodes ({model}) but the initialisers hold conv3 weights')
     return model
 
 
 def load_onnx_state_dict(path: str, num_class: int, base_model: Optional[str] = None,
                          shift_place: str = 'blockres') -> 'OrderedDict[str, np.ndarray]':
-    """Engine state dict (``TsmEngine.load_state_dict``) from a TSM-R50 / R18 / R34 ``.onnx`` export.  The backbone is
+    """Engine state dict (``TsmEngine.load_state_dict``) from a TSM-R50 / R18 / R34 / WRN-50-2 ``.onnx`` export.  The backbone is
     recognised from the graph (``detect_backbone``); a ``base_model`` that disagrees with it raises.  The shift placement
     comes from the caller: it names the keys (``conv_specs``); the graph's convs are the same under both placements."""
     inits, nodes = parse_onnx(path)

@@ -1,4 +1,4 @@
-"""Weights for the TSM-ResNet engine (R50, R18, R34): seeded synthetic state dicts and checkpoint key remapping.
+"""Weights for the TSM-ResNet engine (R50, R18, R34, WRN-50-2): seeded synthetic state dicts and checkpoint key remapping.
 
 No trained weights exist offline, so benches and parity tests use
 a deterministic, numerically non-trivial state dict keyed exactly like the reference's
@@ -19,10 +19,14 @@ import numpy as np
 R50_BLOCKS = (3, 4, 6, 3)
 R50_PLANES = (64, 128, 256, 512)
 EXPANSION = 4
-# torchvision depth -> (blocks per stage, block type); planes are R50_PLANES for all of them
+# torchvision model -> (blocks per stage, block type); planes are R50_PLANES for all of them
 BACKBONES = {'resnet18': ((2, 2, 2, 2), 'basic'), 'resnet34': ((3, 4, 6, 3), 'basic'),
-             'resnet50': (R50_BLOCKS, 'bottleneck')}
-DEPTHS = {'resnet18': 18, 'resnet34': 34, 'resnet50': 50}
+             'resnet50': (R50_BLOCKS, 'bottleneck'), 'wide_resnet50_2': (R50_BLOCKS, 'bottleneck')}
+# -> tsm_set_backbone: the depth alone (WRN-50-2 is a depth-50 schedule) ...
+DEPTHS = {'resnet18': 18, 'resnet34': 34, 'resnet50': 50, 'wide_resnet50_2': 50}
+# ... and -> tsm_set_bottleneck_width: torchvision's width_per_group, 64 unless listed.  A Bottleneck's mid width is
+# planes * width / 64 (WRN-50-2: 128 / 256 / 512 / 1024); its output stays planes * 4.
+WIDTHS = {'wide_resnet50_2': 128}
 # create_model(shift_place=...) -> tsm_set_shift_place: 'blockres' wraps conv1 of every block in TemporalShift
 # (``layerL.B.conv1.net.weight``), 'block' wraps every block whole (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1.*``, ...)
 SHIFT_PLACES = {'blockres': 0, 'block': 1}
@@ -32,6 +36,12 @@ def _backbone(base_model: str):
     if base_model not in BACKBONES:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(BACKBONES))}')
     return BACKBONES[base_model]
+
+
+def bottleneck_width(base_model: str = 'resnet50') -> int:
+    """torchvision's ``width_per_group`` of ``base_model``: 128 for WRN-50-2, 64 for every other backbone."""
+    _backbone(base_model)
+    return WIDTHS.get(base_model, 64)
 
 
 def feature_width(base_model: str = 'resnet50') -> int:
@@ -46,8 +56,9 @@ def _shift_place(shift_place: str) -> str:
 
 
 def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> List[Tuple[str, str, int, int, int]]:
-    """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50, 20
-    for R18, 36 for R34).  A BasicBlock is conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the
+    """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50 and
+    WRN-50-2, 20 for R18, 36 for R34).  A Bottleneck of stage planes p is conv1 [m, cin], conv2 [m, m, 3, 3], conv3
+    [4p, m] and, in the first block of a stage, downsample [4p, cin], with mid width m = p * width / 64 (``WIDTHS``).  A BasicBlock is conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the
     first block of a stage changes the size or the width -- torchvision's module order.  ``shift_place='block'``: the
     same convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``)."""
     blocks, kind = _backbone(base_model)
@@ -65,12 +76,14 @@ def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> L
                     specs.append((p + '.downsample.0.weight', p + '.downsample.1', planes, cin, 1))
                 cin = planes
         return specs
+    width = bottleneck_width(base_model)
     for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
+        mid = planes * width // 64
         for b in range(nb):
             p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
-            specs.append((p + conv1, p + '.bn1', planes, cin, 1))
-            specs.append((p + '.conv2.weight', p + '.bn2', planes, planes, 3))
-            specs.append((p + '.conv3.weight', p + '.bn3', planes * EXPANSION, planes, 1))
+            specs.append((p + conv1, p + '.bn1', mid, cin, 1))
+            specs.append((p + '.conv2.weight', p + '.bn2', mid, mid, 3))
+            specs.append((p + '.conv3.weight', p + '.bn3', planes * EXPANSION, mid, 1))
             if b == 0:
                 specs.append((p + '.downsample.0.weight', p + '.downsample.1',
                               planes * EXPANSION, cin, 1))
@@ -86,7 +99,7 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
     each residual branch (bn3 of a Bottleneck, bn2 of a BasicBlock) is damped so activations stay O(1)
     through 16 blocks; the classifier uses std 0.05 (the reference's init std 0.001, tsm.py:260-262,
     gives logits too flat to discriminate between clips).  R50 draws the same stream as it always has
-    (tests/golden/tsm_r50_logits.json depends on it).  ``shift_place`` changes the keys only (``conv_specs``): one seed
+    (tests/golden/tsm_r50_logits.json depends on it); every other backbone draws its own shapes from the same procedure.  ``shift_place`` changes the keys only (``conv_specs``): one seed
     gives the same numbers under both spellings.
     """
     last_bn = '.bn2' if _backbone(base_model)[1] == 'basic' else '.bn3'

@@ -64,7 +64,10 @@ typedef enum tsm_status {
   TSM_ERR_MISSING_TENSOR = -4,
   TSM_ERR_SHAPE = -5,
   TSM_ERR_CAPACITY = -6,
-  TSM_ERR_UNSUPPORTED = -7
+  TSM_ERR_UNSUPPORTED = -7,
+  TSM_ERR_GUARD = -8 /* hostile-memory check (tsm_conv_op always; an engine under TSM_POISON=1): a launch stored into the poisoned
+                        band before or after a device buffer; the message names buffer, side and element offset.  Additive:
+                        no existing entry point changed, TSM_ABI_VERSION stays 7 */
 } tsm_status;
 
 typedef enum tsm_memkind { TSM_MEM_HOST = 0, TSM_MEM_DEVICE = 1 } tsm_memkind;

@@ -192,8 +192,51 @@ static void check_tail_split() {
   EXPECT(tail_split_point(50176, 96, 4, 256, big) == 0 && tail_split_point(0, 256, 4, 256, big) == 0 && tail_split_point(50176, 256, 4, 0, big) == 0);
 }
 
+// guard_layout / guard_first_bad / guard_message: the band arithmetic of the hostile-memory buffers (tsm_conv_op, TSM_POISON=1).
+static void check_guard_bands() {
+  EXPECT(kPoisonWord == 0x7FC07FC0u);
+  EXPECT(std::isnan(bf2f((uint16_t)(kPoisonWord >> 16))) && std::isnan(bf2f((uint16_t)(kPoisonWord & 0xffffu))));
+  float as_f32;
+  std::memcpy(&as_f32, &kPoisonWord, 4);
+  EXPECT(std::isnan(as_f32));
+  EXPECT(guard_band_bytes(0) == 4096 && guard_band_bytes(64) == 4096 && guard_band_bytes(4096) == 4096);
+  EXPECT(guard_band_bytes(4097) == 4608 && guard_band_bytes(4752) == 5120 && guard_band_bytes(32 * 32 * 64 * 4) == 32 * 32 * 64 * 4);
+  std::mt19937 rng(11);
+  for (int r = 0; r < 20000; ++r) {
+    const size_t payload = (size_t)(rng() % 300000), frame = (size_t)(rng() % 70000);
+    const GuardLayout g = guard_layout(payload, frame);
+    EXPECT(g.lead >= 4096 && g.lead >= frame && g.lead % 512 == 0 && g.lead < frame + 512 + 4096);
+    EXPECT(g.payload >= payload && g.payload < payload + 4 && g.payload % 4 == 0);
+    EXPECT(g.tail >= g.lead && g.tail < g.lead + 512 && (g.lead + g.payload + g.tail) % 512 == 0 && g.total() == g.lead + g.payload + g.tail);
+    // a buffer laid out so, filled, written inside the payload only: both bands clean; one stray word on either side: found
+    if (r % 200 == 0) {
+      std::vector<uint32_t> buf(g.total() / 4, kPoisonWord);
+      for (size_t i = 0; i < g.payload / 4; ++i) buf[g.lead / 4 + i] = (uint32_t)i;
+      const uint32_t *before = buf.data(), *after = buf.data() + (g.lead + g.payload) / 4;
+      EXPECT(guard_first_bad(before, g.lead / 4) == -1 && guard_first_bad(after, g.tail / 4) == -1);
+      const size_t hit = rng() % (g.tail / 4);
+      buf[(g.lead + g.payload) / 4 + hit] = 0x3f800000u;
+      EXPECT(guard_first_bad(after, g.tail / 4) == (long)hit);
+      buf[g.lead / 4 - 1] = 0;
+      EXPECT(guard_first_bad(before, g.lead / 4) == (long)(g.lead / 4 - 1));
+    }
+  }
+  EXPECT(guard_first_bad(nullptr, 0) == -1);
+  const GuardLayout g = guard_layout(1000 * 4, 100 * 4);
+  const std::string past = guard_message("d_ys", g, true, 0, 4, 0x3f800000u);
+  EXPECT(past.find("d_ys") == 0 && past.find("after the buffer, element offset 1000 (0 bytes past its end)") != std::string::npos &&
+         past.find("0x3f800000") != std::string::npos);
+  const std::string pre = guard_message("d_xs", g, false, g.lead / 4 - 1, 4, 0u);
+  EXPECT(pre.find("before the buffer, element offset -1 (4 bytes before its start)") != std::string::npos);
+  const std::string bf = guard_message("d_rs", g, true, 3, 2, 1u);       // bf16 elements: 12 bytes = 6 elements past the end
+  EXPECT(bf.find("element offset 2006 (12 bytes past its end)") != std::string::npos);
+  const std::string far = guard_message("buf[0]", g, false, 0, 4, 1u);   // the far end of the band before
+  EXPECT(far.find("element offset -1024 (4096 bytes before its start)") != std::string::npos);
+}
+
 int main(int argc, char **argv) {
   check_tail_split();
+  check_guard_bands();
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;
   fuzz_tune_lines(1234, rounds);
   check_packing(99);

@@ -49,6 +49,11 @@ def test_no_kernel_stub_is_missing_from_the_library():
 def test_abi_version_and_config_layout(lib):
     from workoutdetector_amd import _lib
     assert lib.tsm_abi_version() == _lib.ABI_VERSION == 7
+    # the statuses of the header and of the binding are the same table (TSM_ERR_GUARD = -8 joined within ABI 7)
+    text = open(os.path.join(ROOT, 'include', 'tsm_hip.h')).read()
+    enum = re.search(r'typedef enum tsm_status \{(.*?)\} tsm_status;', re.sub(r'/\*.*?\*/', '', text, flags=re.S), flags=re.S).group(1)
+    declared = {int(v): k for k, v in re.findall(r'(TSM_[A-Z_]+)\s*=\s*(-?\d+)', enum)}
+    assert declared == _lib.STATUS_NAMES and declared[-8] == 'TSM_ERR_GUARD'
     assert ctypes.sizeof(_lib.TsmConfig) == 40          # 10 x int32, matches struct tsm_config
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import tsm_oracle
+from tests._guard import guarded_conv
 from tests._util import (BF16_TAP_BAR, assert_bf16_op, assert_close, assert_fused_slots, assert_not_ran, assert_ran, assert_ran_tile, bf16_logits_report,
                          make_input, ran_tile)
 from tests.test_ops_gpu import CONV_CASES, _bn, _nchw, _nhwc
@@ -22,7 +23,6 @@ BF16_CASES = [c for c in CONV_CASES if c[3] % 64 == 0 or c[5] == 7]
 
 @pytest.mark.parametrize('n,hi,wi,cin,cout,k,stride,relu,use_res,shiftT', BF16_CASES)
 def test_conv_bn_act_bf16(hip_lib, n, hi, wi, cin, cout, k, stride, relu, use_res, shiftT):
-    from workoutdetector_amd.engine import conv_bn_act_nhwc
     g = torch.Generator().manual_seed(1000 + cin + cout + k + hi)
     x = torch.randn(n, cin, hi, wi, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
@@ -32,9 +32,9 @@ def test_conv_bn_act_bf16(hip_lib, n, hi, wi, cin, cout, k, stride, relu, use_re
     res = torch.randn(n, cout, ho, wo, generator=g) if use_res else None
     xin = tsm_oracle.temporal_shift(x, shiftT, 8) if shiftT else x
     want = tsm_oracle.conv_bn_act_bf16(xin, w, bn, stride, pad, relu, res)
-    got = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
-                           residual=None if res is None else _nhwc(res).cuda(), shift_segments=shiftT, fold_div=8,
-                           dtype='bf16')
+    got = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
+                       residual=None if res is None else _nhwc(res).cuda(), shift_segments=shiftT, fold_div=8,
+                       dtype='bf16')
     assert_bf16_op(_nchw(got.cpu()).numpy(), want.numpy(), what='conv bf16')
 
 
@@ -128,7 +128,7 @@ def test_direct_stem_equals_the_generic_kernel_bitwise(hip_lib, monkeypatch, dty
     """The dedicated stem of the bf16 formats (direct conv from an LDS-resident pixel-pair patch, persistent workgroups)
     against the generic implicit-GEMM kernel on the same packed weights: same K order per output -> same bits,
     including ragged tiles (sizes that are not multiples of the 8x16 tile), odd widths and more tiles than workgroups."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(500 + hi + wi)
     x = _nhwc(torch.randn(n, 3, hi, wi, generator=g)).cuda()
     w = (torch.randn(64, 3, 7, 7, generator=g) * (2.0 / 147) ** 0.5).cuda()
@@ -138,7 +138,7 @@ def test_direct_stem_equals_the_generic_kernel_bitwise(hip_lib, monkeypatch, dty
         monkeypatch.setenv('TSM_STEM_DIRECT', flag)
         for relu in (True, False):
             with launch_trace() as tr:
-                outs[flag, relu] = conv_bn_act_nhwc(x, w, *bn, stride=2, relu=relu, dtype=dtype).cpu()
+                outs[flag, relu] = guarded_conv(x, w, *bn, stride=2, relu=relu, dtype=dtype).cpu()
             assert tr.ran('stem_direct_kernel<') == (flag == '1') and tr.ran('conv_igemm<') == (flag == '0'), tr.kernels
     for relu in (True, False):
         assert torch.equal(outs['1', relu], outs['0', relu]), relu
@@ -234,7 +234,7 @@ def test_lds_dma_256_tile_equals_the_128_tiles_bitwise(hip_lib, monkeypatch, n, 
     conv_bf16_256p_kernel (flat K pipeline across a workgroup's tiles, transposed product, register epilogue) against
     conv_igemm's bf16 tiles through the per-op entry point: same k order per output -> same bits; and against the
     bf16-storage oracle at the bf16 mode's per-op bar."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(7000 + cin + cout + k + hi)
     x = torch.randn(n, cin, hi, wi, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
@@ -247,9 +247,9 @@ def test_lds_dma_256_tile_equals_the_128_tiles_bitwise(hip_lib, monkeypatch, n, 
     for tile in ('256x256', '128x128', '64x64') + (('256x256p',) if persistent else ()):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
-                                          residual=None if res is None else _nhwc(res).cuda(),
-                                          shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
+                                      residual=None if res is None else _nhwc(res).cuda(),
+                                      shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
         assert_ran_tile(tr, tile, f'per-op conv forced onto {tile}')
     assert torch.equal(outs['256x256'], outs['128x128']) and torch.equal(outs['256x256'], outs['64x64'])
     if persistent:      # the same pipeline run persistently over a workgroup's tiles, register epilogue
@@ -281,7 +281,7 @@ def test_weight_stationary_3x3_equals_the_igemm_tiles_bitwise(hip_lib, monkeypat
     32-output-channel slice per wave for 128 --, input patch by LDS-DMA, transposed MFMA, register epilogue through
     v_permlane32_swap) against conv_igemm's bf16 tiles through the per-op entry point: same k order per output -> same
     bits; and against the fp32 oracle at the bf16 mode's tolerance."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(9100 + ch + n + hi + wi)
     x = torch.randn(n, ch, hi, wi, generator=g)
     w = torch.randn(ch, ch, 3, 3, generator=g) * (2.0 / (9 * ch)) ** 0.5
@@ -290,7 +290,7 @@ def test_weight_stationary_3x3_equals_the_igemm_tiles_bitwise(hip_lib, monkeypat
     for tile in ('ws', '128x64', '64x64'):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu, dtype='bf16').cpu()
         if tile == 'ws':
             assert_ran(tr, 'conv3x3_ws_kernel<false>' if ch == 64 else 'conv3x3_ws128_kernel<false>', 'weight-stationary 3x3')
         else:
@@ -319,7 +319,7 @@ def test_weight_stationary_3x3_stride2_equals_the_igemm_tiles_bitwise(hip_lib, m
     """conv3x3_ws128_kernel<true> (layer2.0's conv2: stride 2, 128 -> 128 channels; the patch stored with de-interleaved
     columns, one M-tile pair per tile, the accumulator sets alternating between tiles) against conv_igemm's bf16 tiles
     through the per-op entry point: same bits; and against the oracle at the bf16 mode's tolerance."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(9300 + n + hi + wi)
     x = torch.randn(n, 128, hi, wi, generator=g)
     w = torch.randn(128, 128, 3, 3, generator=g) * (2.0 / (9 * 128)) ** 0.5
@@ -328,7 +328,7 @@ def test_weight_stationary_3x3_stride2_equals_the_igemm_tiles_bitwise(hip_lib, m
     for tile in ('ws', '128x128', '64x64'):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=2, relu=relu, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=2, relu=relu, dtype='bf16').cpu()
         if tile == 'ws':
             assert_ran(tr, 'conv3x3_ws128_kernel<true>', 'stride-2 weight-stationary 3x3')
         else:
@@ -354,7 +354,7 @@ def test_weight_stationary_1x1_equals_the_igemm_tiles_bitwise(hip_lib, monkeypat
     """conv1x1_ws_kernel (layer1's conv1: W1 resident in registers, a whole 128-pixel tile by LDS-DMA one tile ahead, the
     temporal shift as an address choice per 16-byte chunk, zeros at the clip's ends) against conv_igemm's bf16 tiles
     through the per-op entry point -- same bits -- and against the fp32 oracle at the bf16 mode's tolerance."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(9300 + cin + n + hi)
     x = torch.randn(n, cin, hi, wi, generator=g)
     w = torch.randn(64, cin, 1, 1, generator=g) * (2.0 / cin) ** 0.5
@@ -363,8 +363,8 @@ def test_weight_stationary_1x1_equals_the_igemm_tiles_bitwise(hip_lib, monkeypat
     for tile in ('ws', '128x64', '64x64'):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu,
-                                          shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu,
+                                      shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
         if tile == 'ws':
             assert_ran(tr, 'conv1x1_ws_kernel<%d>' % cin, 'weight-stationary 1x1')
         else:
@@ -388,7 +388,7 @@ def test_weight_stationary_1x1_equals_the_igemm_tiles_bitwise(hip_lib, monkeypat
 def test_weight_stationary_1x1_wide_equals_the_igemm_tiles_bitwise(hip_lib, monkeypatch, cin, cout, n, hi, wi, shiftT, relu):
     """conv1x1_wsn_kernel (output channels split over the waves, whole pixel tiles by LDS-DMA one tile ahead, fused temporal
     shift) against conv_igemm's bf16 tiles through the per-op entry point -- same bits -- and against the fp32 oracle."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     g = torch.Generator().manual_seed(9500 + cin + cout + n + hi)
     x = torch.randn(n, cin, hi, wi, generator=g)
     w = torch.randn(cout, cin, 1, 1, generator=g) * (2.0 / cin) ** 0.5
@@ -397,8 +397,8 @@ def test_weight_stationary_1x1_wide_equals_the_igemm_tiles_bitwise(hip_lib, monk
     for tile in ('ws', '128x128', '64x64'):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu,
-                                          shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=relu,
+                                      shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
         if tile == 'ws':
             assert_ran(tr, 'conv1x1_wsn_kernel<%d, %d, false>' % (cin, cout), 'wide weight-stationary 1x1')
         else:
@@ -454,7 +454,7 @@ def _random_ws_cases():
 def test_weight_stationary_kernels_on_random_shapes_bitwise(hip_lib, monkeypatch, kind, cin, cout, n, hi, wi, shiftT):
     """Seeded random frame counts / sizes / segment counts (ragged tiles, tiles straddling frames and clips, frames
     smaller than a tile) through every weight-stationary kernel family, bit-compared with the 64x64 igemm tile."""
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     k = 3 if kind == '3x3' else 1
     g = torch.Generator().manual_seed(n * 1000 + hi * 10 + wi + cin)
     x = torch.randn(n, cin, hi, wi, generator=g)
@@ -464,8 +464,8 @@ def test_weight_stationary_kernels_on_random_shapes_bitwise(hip_lib, monkeypatch
     for tile in ('ws', '64x64'):
         monkeypatch.setenv('TSM_CONV_TILE', tile)
         with launch_trace() as tr:
-            outs[tile] = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=True,
-                                          shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
+            outs[tile] = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=1, relu=True,
+                                      shift_segments=shiftT, fold_div=8, dtype='bf16').cpu()
         assert_ran_tile(tr, tile, f'{kind} {cin}->{cout} n={n} {hi}x{wi} T={shiftT}')
     assert torch.equal(outs['ws'], outs['64x64'])
 

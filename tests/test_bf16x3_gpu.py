@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import transform_oracle, tsm_oracle
+from tests._guard import guarded_conv
 from tests._util import assert_close, make_input
 from tests.test_ops_gpu import CONV_CASES, _bn, _nchw, _nhwc
 
@@ -16,7 +17,6 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize('n,hi,wi,cin,cout,k,stride,relu,use_res,shiftT', CONV_CASES)
 def test_conv_bn_act_x3(hip_lib, n, hi, wi, cin, cout, k, stride, relu, use_res, shiftT):
-    from workoutdetector_amd.engine import conv_bn_act_nhwc
     g = torch.Generator().manual_seed(1000 + cin + cout + k + hi)
     x = torch.randn(n, cin, hi, wi, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) * (2.0 / (cin * k * k)) ** 0.5
@@ -26,9 +26,9 @@ def test_conv_bn_act_x3(hip_lib, n, hi, wi, cin, cout, k, stride, relu, use_res,
     res = torch.randn(n, cout, ho, wo, generator=g) if use_res else None
     xin = tsm_oracle.temporal_shift(x, shiftT, 8) if shiftT else x
     want = tsm_oracle.conv_bn_act(xin, w, bn, stride, pad, relu, res)
-    got = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
-                           residual=None if res is None else _nhwc(res).cuda(), shift_segments=shiftT, fold_div=8,
-                           dtype='bf16x3')
+    got = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], stride=stride, relu=relu,
+                       residual=None if res is None else _nhwc(res).cuda(), shift_segments=shiftT, fold_div=8,
+                       dtype='bf16x3')
     assert_close(_nchw(got.cpu()).numpy(), want.numpy(), rtol=3e-4, atol_scale=3e-4, what='conv x3')
 
 

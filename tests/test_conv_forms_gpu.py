@@ -16,6 +16,7 @@ import torch
 
 from oracle.tsm_oracle import bf16_round, temporal_shift
 from tests._conv_ref import conv_ref
+from tests._guard import guarded_conv
 from tests._util import IGEMM_TILE_DIMS, assert_bf16_op, assert_close, ran_tile, sweep as _sweep
 
 pytestmark = pytest.mark.gpu
@@ -69,12 +70,11 @@ def _check(got, want, dtype, what):
 
 
 def _run(x, w, bn, dtype, code, reverse, **kw):
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     bn2 = kw.pop('bn2', None)
     with launch_trace() as tr:
-        y = conv_bn_act_nhwc(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], dtype=dtype, code=code, reverse=reverse,
-                             bn2=None if bn2 is None else [b.cuda() for b in bn2], **kw)
-        torch.cuda.synchronize()
+        y = guarded_conv(_nhwc(x).cuda(), w.cuda(), *[b.cuda() for b in bn], dtype=dtype, code=code, reverse=reverse,
+                         bn2=None if bn2 is None else [b.cuda() for b in bn2], **kw)     # (hostile memory: tests/_guard.py)
     assert not tr.ran('temporal_shift_kernel'), ('the shifted tensor must never be materialised', tr.kernels)
     return _nchw(y.cpu()), tr
 

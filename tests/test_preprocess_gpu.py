@@ -4,9 +4,25 @@ import pytest
 import torch
 
 from oracle import transform_oracle
+from tests._guard import check, guarded, guarded_out
 from tests._stub import synthetic_video
 
 pytestmark = pytest.mark.gpu
+
+
+def _preprocess(frames, crop=224, layout=None, packed=True, **kw):
+    """engine.preprocess_frames in hostile memory (tests/_guard.py): the frames between poisoned bands, the output poisoned
+    before the launch; bands and payload checked after it."""
+    from workoutdetector_amd import _lib
+    from workoutdetector_amd.engine import preprocess_frames
+    lay = layout if layout is not None else (_lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW)
+    n, pairs = frames.shape[0], (crop + 1) // 2
+    shape = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
+             _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4), _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}[lay]
+    src, out = guarded(frames, name='frames'), guarded_out(shape, name='out')
+    assert preprocess_frames(src, crop=crop, layout=layout, packed=packed, out=out, **kw) is out
+    check(src, out)
+    return out
 
 
 def _check(got, want, what):
@@ -19,15 +35,14 @@ def _check(got, want, what):
 @pytest.mark.parametrize('h,w', [(360, 206), (272, 480), (256, 256), (224, 224), (720, 1280), (225, 640), (90, 52)])
 @pytest.mark.parametrize('scale_255', [False, True])
 def test_preprocess_matches_oracle(hip_lib, h, w, scale_255):
-    from workoutdetector_amd.engine import preprocess_frames
     vid = torch.from_numpy(synthetic_video(h + w, 3, h, w))
     rng = np.random.default_rng(h * w)
     vid = torch.from_numpy(rng.integers(0, 256, size=(3, h, w, 3), dtype=np.uint8))
     want = transform_oracle.test_transform(vid.permute(0, 3, 1, 2).float(), scale_255=scale_255)
-    packed = preprocess_frames(vid.cuda(), scale_255=scale_255).cpu()
+    packed = _preprocess(vid.cuda(), scale_255=scale_255).cpu()
     assert tuple(packed.shape) == (3, 224, 224, 4) and float(packed[..., 3].abs().max()) == 0.0
     _check(packed[..., :3].permute(0, 3, 1, 2), want, 'u8 packed')
-    nchw = preprocess_frames(vid.float().cuda(), scale_255=scale_255, packed=False).cpu()
+    nchw = _preprocess(vid.float().cuda(), scale_255=scale_255, packed=False).cpu()
     _check(nchw, want, 'f32 nchw')
     _check(nchw, packed[..., :3].permute(0, 3, 1, 2), 'u8 vs f32 source')  # separate instantiations: fma contraction may differ
 
@@ -55,17 +70,16 @@ def test_pixel_pair_layouts_of_the_bf16_formats(hip_lib, crop, resize):
     rows of ceil(crop/2) pairs, an odd crop ending in a zero pixel.  Decoded and compared with the fp32 NCHW
     output of the same kernel: bf16 = fp32 rounded to 8 significand bits (RNE); split = hi + lo within 2^-16."""
     from workoutdetector_amd import _lib
-    from workoutdetector_amd.engine import preprocess_frames
     rng = np.random.default_rng(crop)
     vid = torch.from_numpy(rng.integers(0, 256, size=(2, 90, 52, 3), dtype=np.uint8)).cuda()
-    want = preprocess_frames(vid, resize=resize, crop=crop, packed=False).cpu().permute(0, 2, 3, 1)   # [n,crop,crop,3]
+    want = _preprocess(vid, resize=resize, crop=crop, packed=False).cpu().permute(0, 2, 3, 1)   # [n,crop,crop,3]
     pairs = (crop + 1) // 2
-    b = preprocess_frames(vid, resize=resize, crop=crop, layout=_lib.LAYOUT_NTHWC8B).cpu()
+    b = _preprocess(vid, resize=resize, crop=crop, layout=_lib.LAYOUT_NTHWC8B).cpu()
     assert tuple(b.shape) == (2, crop, pairs, 4)
     px = b.view(torch.bfloat16).reshape(2, crop, pairs * 2, 4).float()
     assert torch.equal(px[:, :, :crop, :3], want.to(torch.bfloat16).float())
     assert float(px[..., 3].abs().max()) == 0.0 and float(px[:, :, crop:].abs().max() if crop % 2 else 0.0) == 0.0
-    s = preprocess_frames(vid, resize=resize, crop=crop, layout=_lib.LAYOUT_NTHWC8S).cpu()
+    s = _preprocess(vid, resize=resize, crop=crop, layout=_lib.LAYOUT_NTHWC8S).cpu()
     assert tuple(s.shape) == (2, crop, pairs, 8)
     g = s.view(torch.bfloat16).reshape(2, crop, pairs, 2, 8).float()       # [hi x8 | lo x8] per pair
     val = (g[:, :, :, 0] + g[:, :, :, 1]).reshape(2, crop, pairs * 2, 4)
@@ -93,11 +107,13 @@ def test_gather_clips_equals_the_reference_windows(hip_lib, layout_name):
         f_lo = starts[lo] // 2
         f_hi = min((starts[hi - 1] + 16) // 2, (total + 1) // 2)
         even = torch.cat([video[0::2][f_lo:f_hi], torch.zeros((1, 36, 52, 3), dtype=torch.uint8)]).cuda()
-        frames = engine.preprocess_frames(even, resize=32, crop=24, layout=layout)
+        frames = guarded(_preprocess(even, resize=32, crop=24, layout=layout), name='frames')
         src = 8 * torch.arange(lo, hi)[:, None] + 2 * torch.arange(8)[None, :]
         idx = torch.where(src < total, src // 2 - f_lo, torch.full_like(src, frames.shape[0] - 1))
         want = frames[idx.cuda()]
-        got = engine.gather_clips(frames, f_lo, total, lo, hi - lo)
+        got = guarded_out(want.shape, name='clips')
+        assert engine.gather_clips(frames, f_lo, total, lo, hi - lo, out=got) is got
+        check(frames, got)
         assert got.shape == want.shape and torch.equal(got, want), (total, lo, hi)
         # into a slice of a larger buffer, as the batcher does
         buf = torch.full((3 + (hi - lo) + 2, 8) + tuple(frames.shape[1:]), -7.0, device='cuda')
@@ -106,9 +122,11 @@ def test_gather_clips_equals_the_reference_windows(hip_lib, layout_name):
     # a padded tail on 16-byte frames, and more rows than one launch cuts (65535: the binding splits the range) -- the
     # windows stay those of index_select
     for n_buf, n_clips in ((4200, 1050), (70000, 17000)):       # 8 400 rows with a padded last clip; 136 000 rows = three launches
-        buf = torch.arange(n_buf * 4, dtype=torch.float32, device='cuda').reshape(n_buf, 4)
+        buf = guarded(torch.arange(n_buf * 4, dtype=torch.float32, device='cuda').reshape(n_buf, 4), name='frames')
         total = 2 * (n_buf - 1)
-        got = engine.gather_clips(buf, 0, total, 0, n_clips)
+        got = guarded_out((n_clips, 8, 4), name='clips')     # (a stray row of the padded tail or of a launch cut lands in a band)
+        assert engine.gather_clips(buf, 0, total, 0, n_clips, out=got) is got
+        check(buf, got)
         src = 8 * torch.arange(n_clips)[:, None] + 2 * torch.arange(8)[None, :]
         idx = torch.where(src < total, src // 2, torch.full_like(src, n_buf - 1))
         assert torch.equal(got, buf[idx.cuda()]), (n_buf, n_clips)

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from tests._conv_ref import conv_ref
+from tests._guard import guarded_conv
 from tests._util import (IGEMM_TILE_DIMS, REVERSE_MARK, assert_bf16_op, assert_close, assert_walked, make_input, ran_tile,
                          sweep)
 from tests._walk_cases import cases, count_tiles, tail_split_applies
@@ -68,7 +69,7 @@ CASES = cases(_n_cu())
 
 @pytest.mark.parametrize('case', CASES, ids=[c['id'] for c in CASES])
 def test_walk_per_op(hip_lib, monkeypatch, case):
-    from workoutdetector_amd.engine import conv_bn_act_nhwc, launch_trace
+    from workoutdetector_amd.engine import launch_trace
     monkeypatch.setenv('TSM_STEM_DIRECT', '0')   # (the bf16 stems through conv_igemm; tsm_conv_op reads it per call)
     c = case
     assert count_tiles(c) == c['tiles'], c['id']
@@ -96,8 +97,10 @@ def test_walk_per_op(hip_lib, monkeypatch, case):
 
     def run(code, rev):
         with launch_trace() as tr:
-            y = conv_bn_act_nhwc(xd, wd, *bnd, stride=c['stride'], dtype=dtype, code=code, reverse=rev, **kw)
-            torch.cuda.synchronize()
+            # (hostile memory: fp32 kernels run on these guarded tensors themselves, so a tile no direction writes stays POISON
+            #  in y; the bf16 formats run on tsm_conv_op's own staging buffers, which are poisoned and banded the same way --
+            #  an unwritten tile of d_ys reaches y as poison through the conversion, a stray store fails the call)
+            y = guarded_conv(xd, wd, *bnd, stride=c['stride'], dtype=dtype, code=code, reverse=rev, **kw)
         return _nchw(y.cpu()), tr
 
     def expect(code, tr):

@@ -18,7 +18,7 @@ DTYPES = {'f32': DTYPE_F32, 'bf16x3': DTYPE_BF16X3, 'bf16': DTYPE_BF16}
 
 STATUS_NAMES = {0: 'TSM_OK', -1: 'TSM_ERR_INVALID_ARG', -2: 'TSM_ERR_HIP', -3: 'TSM_ERR_NOT_FINALIZED',
                 -4: 'TSM_ERR_MISSING_TENSOR', -5: 'TSM_ERR_SHAPE', -6: 'TSM_ERR_CAPACITY',
-                -7: 'TSM_ERR_UNSUPPORTED'}
+                -7: 'TSM_ERR_UNSUPPORTED', -8: 'TSM_ERR_GUARD'}
 
 
 class TsmConfig(C.Structure):

@@ -98,6 +98,47 @@ int ilog2(int v) {
   return l;
 }
 
+// A device buffer between two poisoned bands (tsm_host_util.h: guard_layout).  tsm_conv_op's temporaries always are; the
+// engine's buffers are under TSM_POISON=1.
+struct GuardBuf {
+  std::string name;
+  char *base = nullptr;     // the allocation (what hipFree takes)
+  GuardLayout lay;
+  size_t elem_bytes = 4;    // for the message: offsets are reported in elements of the buffer
+  float *ptr() const { return reinterpret_cast<float *>(base + lay.lead); }
+};
+
+// Allocate `payload_bytes` between bands sized for `frame_bytes`, the WHOLE allocation filled with the poison word (so the
+// payload too: whatever is not written afterwards stays poison).  Synchronous.
+hipError_t guard_alloc(GuardBuf *g, const char *name, size_t payload_bytes, size_t frame_bytes, size_t elem_bytes = 4) {
+  g->name = name;
+  g->lay = guard_layout(payload_bytes, frame_bytes);
+  g->elem_bytes = elem_bytes;
+  void *q = nullptr;
+  hipError_t st = hipMalloc(&q, g->lay.total());
+  if (st != hipSuccess) return st;
+  g->base = static_cast<char *>(q);
+  st = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(q), (int)kPoisonWord, g->lay.total() / 4);
+  return st != hipSuccess ? st : hipDeviceSynchronize();
+}
+
+// Both bands copied to the host (the bands only) and compared with the poison word.  Returns hipSuccess with *msg empty when
+// they are intact, with *msg naming buffer, side and element offset when not.
+hipError_t guard_verify(const GuardBuf &g, std::string *msg) {
+  std::vector<uint32_t> host(std::max(g.lay.lead, g.lay.tail) / 4);
+  for (int after = 0; after < 2; ++after) {
+    const size_t bytes = after ? g.lay.tail : g.lay.lead;
+    const hipError_t st = hipMemcpy(host.data(), g.base + (after ? g.lay.lead + g.lay.payload : 0), bytes, hipMemcpyDeviceToHost);
+    if (st != hipSuccess) return st;
+    const long bad = guard_first_bad(host.data(), bytes / 4);
+    if (bad >= 0) {
+      *msg = guard_message(g.name, g.lay, after != 0, (size_t)bad, g.elem_bytes, host[bad]);
+      return hipSuccess;
+    }
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 struct tsm_engine {
@@ -128,6 +169,11 @@ struct tsm_engine {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool have_time = false;
   std::vector<void *> allocs;
+  // TSM_POISON=1 (read once in tsm_create; tests only): every device buffer sits between poisoned bands, every forward first
+  // fills the activation / scratch buffers with the poison word, and after its last launch synchronises and verifies all
+  // bands (TSM_ERR_GUARD).  No result bit changes; forwards become synchronous and are not capture-safe.
+  bool poison = false;
+  std::vector<GuardBuf> guards;
   // per-launch timing (tsm_set_layer_timing): timing[f] = events of forward f, 2 per launch
   // conv tile autotune: per frame count, one ConvTile per conv layer (0 = not tuned yet)
   std::map<int, std::vector<int>> tile_cache;
@@ -276,11 +322,43 @@ bool known_name(const tsm_engine *e, const std::string &name) {
   return false;
 }
 
-int dev_alloc(tsm_engine *e, float **p, size_t elems) {
+int dev_alloc(tsm_engine *e, float **p, size_t elems, const char *name = "weights", size_t frame_elems = 0) {
+  if (e->poison) {   // between poisoned bands of one frame of this buffer, poison all over until something is written
+    GuardBuf g;
+    TSM_HIP(e, guard_alloc(&g, name, elems * sizeof(float), frame_elems * sizeof(float)));
+    e->allocs.push_back(g.base);
+    e->guards.push_back(g);
+    *p = g.ptr();
+    return TSM_OK;
+  }
   void *q = nullptr;
   TSM_HIP(e, hipMalloc(&q, elems * sizeof(float)));
   e->allocs.push_back(q);
   *p = static_cast<float *>(q);
+  return TSM_OK;
+}
+
+// TSM_POISON=1, immediately before the first launch of a forward proper: every activation / scratch buffer filled with the
+// poison word, so whatever a kernel relies on in them must be written by THIS forward, not inherited.  Weights are not touched.
+int poison_workspace(tsm_engine *e, hipStream_t s) {
+  if (!e->poison) return TSM_OK;
+  const float *targets[] = {e->buf[0], e->buf[1], e->buf[2], e->buf[3], e->buf[4], e->d_in4, e->d_pooled, e->d_logits, e->d_partial, e->d_tap};
+  for (const GuardBuf &g : e->guards)
+    for (const float *t : targets)
+      if (t && t == g.ptr())
+        TSM_HIP(e, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.ptr()), (int)kPoisonWord, g.lay.payload / 4, s));
+  return TSM_OK;
+}
+
+// TSM_POISON=1, after a forward's last launch: synchronise and verify the bands of every buffer.
+int verify_guards(tsm_engine *e, hipStream_t s) {
+  if (!e->poison) return TSM_OK;
+  TSM_HIP(e, hipStreamSynchronize(s));
+  for (const GuardBuf &g : e->guards) {
+    std::string msg;
+    TSM_HIP(e, guard_verify(g, &msg));
+    if (!msg.empty()) return fail(e, TSM_ERR_GUARD, msg);
+  }
   return TSM_OK;
 }
 
@@ -1004,6 +1082,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   if (const char *f31 = getenv("TSM_FUSE_C3C1")) e->fuse31 = atoi(f31) != 0;
   if (const char *ff = getenv("TSM_FUSE_FRONT")) e->fuse_front = atoi(ff) != 0;
   if (const char *wk = getenv("TSM_WALK")) e->walk = atoi(wk) != 0;
+  if (const char *po = getenv("TSM_POISON")) e->poison = atoi(po) != 0;
   // TSM_TUNE_CACHE=<file> names the tune cache; unset: a per-user default ($XDG_CACHE_HOME or $HOME/.cache, then
   // tsm_hip/tune_cache.txt), so that the second process on a machine pays no tuning pass; "", "0" or "off" disables it.
   {
@@ -1235,20 +1314,21 @@ int tsm_finalize(tsm_engine *e) {
   }
   e->buf_elems = frames * per_frame;
   for (int i = 0; i < 5; ++i) {
-    rc = dev_alloc(e, &e->buf[i], e->buf_elems);
+    static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
+    rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame);
     if (rc) return rc;
   }
-  rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width);
+  rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width);
   if (rc) return rc;
-  rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1));  // 16 bytes per pixel in every format (pairs: odd widths padded)
+  rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1));  // 16 bytes per pixel in every format (pairs: odd widths padded)
   if (rc) return rc;
-  rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat);
+  rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat);
   if (rc) return rc;
-  rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * cfg.num_class);
+  rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * cfg.num_class, "d_logits", (size_t)cfg.num_class);
   if (rc) return rc;
   if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
     e->partial_elems = (size_t)16 << 20;
-    rc = dev_alloc(e, &e->d_partial, e->partial_elems);
+    rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame);
     if (rc) return rc;
   }
   e->tensors.clear();  // host copies are no longer needed
@@ -1281,6 +1361,8 @@ int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layou
   // timing events and synchronises); the real pass below then runs from the cache.
   rc = ensure_tuned(e, d_clips, layout, n_clips, d_out, s);
   if (rc) return rc;
+  rc = poison_workspace(e, s);   // (TSM_POISON=1 only; after the tuning pass, before the forward proper)
+  if (rc) return rc;
   TSM_HIP(e, hipEventRecord(e->ev0, s));
   rc = run_forward(e, d_clips, layout, n_clips, d_out, s, nullptr, nullptr);
   e->cur_timing = nullptr;
@@ -1292,7 +1374,7 @@ int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layou
                               hipMemcpyDeviceToHost, s));
     TSM_HIP(e, hipStreamSynchronize(s));
   }
-  return TSM_OK;
+  return e->poison ? verify_guards(e, s) : TSM_OK;
 }
 
 int tsm_tune(tsm_engine *e, int32_t n_clips, void *stream) {
@@ -1338,6 +1420,8 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
     TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, s));
     d_clips = e->d_in;
   }
+  rc = poison_workspace(e, s);
+  if (rc) return rc;
   Tap tap;
   rc = run_forward(e, d_clips, layout, n_clips, e->d_logits, s, stage, &tap);
   if (rc) return rc;
@@ -1349,7 +1433,7 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
       const size_t cap = e->buf_elems > (size_t)e->cfg.max_clips * e->cfg.num_segments * 8 * e->cfg.height * e->cfg.width
                              ? e->buf_elems
                              : (size_t)e->cfg.max_clips * e->cfg.num_segments * 8 * e->cfg.height * e->cfg.width;
-      rc = dev_alloc(e, &e->d_tap, cap);
+      rc = dev_alloc(e, &e->d_tap, cap, "d_tap", cap / ((size_t)e->cfg.max_clips * e->cfg.num_segments));
       if (rc) return rc;
     }
     TSM_HIP(e, tsm::launch_to_f32(tap.ptr, e->d_tap, elems / 8, e->prec, s));
@@ -1358,7 +1442,7 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
   TSM_HIP(e, hipMemcpyAsync(out, tap.ptr, (size_t)elems * sizeof(float),
                             memkind == TSM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
   TSM_HIP(e, hipStreamSynchronize(s));
-  return TSM_OK;
+  return e->poison ? verify_guards(e, s) : TSM_OK;
 }
 
 int tsm_set_layer_timing(tsm_engine *e, int32_t n_forwards, int32_t only_conv3x3) {
@@ -1538,15 +1622,27 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   if (prec == tsm::kPrecBf16) to_bf16(&wp);
   float *d_w = nullptr, *d_b = nullptr, *d_x4 = nullptr, *d_xs = nullptr, *d_rs = nullptr, *d_ys = nullptr, *d_x2s = nullptr,
         *d_part = nullptr;
+  // Hostile memory, always on (a debug entry point that allocates per call): every temporary sits between poisoned bands of one
+  // frame of that buffer and starts out poison all over -- so the elements of d_ys / d_part that the launch does not write reach
+  // y as poison (through to_f32 / the reduction), a read before frame 0 or behind the last tile returns poison instead of the
+  // allocator's leftovers, and a stray store is found in the bands after the final synchronise (TSM_ERR_GUARD).
   struct Scratch {  // frees the temporaries on every exit path (errors included)
-    float **ptrs[8];
+    GuardBuf g[8];
+    int n = 0;
     ~Scratch() {
-      for (float **q : ptrs)
-        if (*q) (void)hipFree(*q);
+      for (int i = 0; i < n; ++i)
+        if (g[i].base) (void)hipFree(g[i].base);
     }
-  } scratch{{&d_w, &d_b, &d_x4, &d_xs, &d_rs, &d_ys, &d_x2s, &d_part}};
-  TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_w), wp.size() * sizeof(float)));
-  TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_b), bias.size() * sizeof(float)));
+  } scratch;
+  auto galloc = [&scratch](float **p, const char *name, size_t bytes, size_t frame_bytes, size_t elem_bytes) -> hipError_t {
+    GuardBuf &g = scratch.g[scratch.n++];
+    const hipError_t st_ = guard_alloc(&g, name, bytes, frame_bytes, elem_bytes);
+    if (st_ == hipSuccess) *p = g.ptr();
+    return st_;
+  };
+  const size_t act_bytes = prec == tsm::kPrecBf16 ? 2 : 4;   // bytes per stored activation element (split-bf16: hi + lo = 4)
+  TSM_HIP0(galloc(&d_w, "d_w", wp.size() * sizeof(float), (size_t)(wp.size() / cout) * sizeof(float), 4));
+  TSM_HIP0(galloc(&d_b, "d_b", bias.size() * sizeof(float), 0, 4));
   TSM_HIP0(hipMemcpy(d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
   TSM_HIP0(hipMemcpy(d_b, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
   c.d_w = d_w; c.d_b = d_b;
@@ -1555,25 +1651,25 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   float *yout = a->y;
   const size_t out_elems = (size_t)n * ho * wo * cout;
   if (stem) {  // NHWC3 -> NHWC4 fp32 / NHWC8 split
-    TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_x4), (size_t)n * hi * wi * 8 * sizeof(float)));
+    TSM_HIP0(galloc(&d_x4, "d_x4", (size_t)n * hi * wi * 8 * sizeof(float), (size_t)hi * wi * 8 * sizeof(float), 4));
     TSM_HIP0(tsm::launch_pack_input(a->x, d_x4, n, hi, wi, 0, prec, s));
     xin = d_x4;
   } else if (x3) {
-    TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_xs), (size_t)n * hi * wi * cin * sizeof(float)));
+    TSM_HIP0(galloc(&d_xs, "d_xs", (size_t)n * hi * wi * cin * act_bytes, (size_t)hi * wi * cin * act_bytes, act_bytes));
     TSM_HIP0(tsm::launch_from_f32(a->x, d_xs, (int64_t)n * hi * wi * cin / 8, prec, s));
     xin = d_xs;
   }
   if (x3) {
-    TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_ys), out_elems * sizeof(float)));
+    TSM_HIP0(galloc(&d_ys, "d_ys", out_elems * act_bytes, (size_t)ho * wo * cout * act_bytes, act_bytes));
     yout = d_ys;
     if (residual) {
-      TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_rs), out_elems * sizeof(float)));
+      TSM_HIP0(galloc(&d_rs, "d_rs", out_elems * act_bytes, (size_t)ho * wo * cout * act_bytes, act_bytes));
       TSM_HIP0(tsm::launch_from_f32(residual, d_rs, (int64_t)out_elems / 8, prec, s));
       rin = d_rs;
     }
     if (dual) {
       const size_t x2_elems = (size_t)n * a->hi2 * a->wi2 * cin2;
-      TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_x2s), x2_elems * sizeof(float)));
+      TSM_HIP0(galloc(&d_x2s, "d_x2s", x2_elems * act_bytes, (size_t)a->hi2 * a->wi2 * cin2 * act_bytes, act_bytes));
       TSM_HIP0(tsm::launch_from_f32(a->x2, d_x2s, (int64_t)x2_elems / 8, prec, s));
       x2in = d_x2s;
     }
@@ -1590,7 +1686,7 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   size_t part_elems = 0;
   if ((code & (kCodeSplitK | kCodeTailK)) && p.kseg_len > 0) {
     part_elems = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
-    TSM_HIP0(hipMalloc(reinterpret_cast<void **>(&d_part), part_elems * sizeof(float)));
+    TSM_HIP0(galloc(&d_part, "d_part", part_elems * sizeof(float), (size_t)ho * wo * cout * sizeof(float), 4));
   }
   int dev = 0, n_cu = 256;
   TSM_HIP0(hipGetDevice(&dev));
@@ -1607,6 +1703,11 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
                                     std::string("launch_conv: ") + hipGetErrorString(st));
   if (st2 != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("conv sync: ") + hipGetErrorString(st2));
+  for (int i = 0; i < scratch.n; ++i) {
+    std::string msg;
+    TSM_HIP0(guard_verify(scratch.g[i], &msg));
+    if (!msg.empty()) return fail(nullptr, TSM_ERR_GUARD, "tsm_conv_op: " + msg);
+  }
   return TSM_OK;
 #undef TSM_HIP0
 }

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -128,6 +129,55 @@ inline void concat_k_pair(const std::vector<float> &w1, const std::vector<float>
     std::memcpy(&(*wf)[(size_t)o * kpf + kp1], &w2[(size_t)o * kp2], kp2 * sizeof(float));
     (*bf)[o] = b1[o] + b2[o];
   }
+}
+
+// ---- hostile memory (tsm_conv_op's staging buffers; the engine under TSM_POISON=1) -----------------------------------------
+// A guarded device buffer is [band | payload | slack + band]: the bands hold kPoisonWord (as fp32 a quiet NaN with a payload
+// arithmetic never produces, as two bf16 two quiet NaNs, as an int32 no class id) and must still hold it after the launches --
+// a stray store lands in owned memory and is reported, a stray read returns poison instead of a plausible leftover.  Band = one
+// frame of the buffer (the reach of a wrong temporal-shift or halo index) rounded up to 512 bytes, at least 4 KiB; the payload
+// keeps the 512-byte alignment of the allocation.
+constexpr uint32_t kPoisonWord = 0x7FC07FC0u;
+constexpr size_t kGuardAlign = 512, kGuardMinBand = 4096;
+
+inline size_t guard_band_bytes(size_t frame_bytes) {
+  const size_t r = (frame_bytes + kGuardAlign - 1) / kGuardAlign * kGuardAlign;
+  return r < kGuardMinBand ? kGuardMinBand : r;
+}
+
+struct GuardLayout {
+  size_t lead = 0;     // bytes of the band before the payload (= the payload's offset in the allocation)
+  size_t payload = 0;  // bytes of the payload (a multiple of 4)
+  size_t tail = 0;     // bytes behind the payload: the slack up to 512 bytes + the band after
+  size_t total() const { return lead + payload + tail; }
+};
+
+inline GuardLayout guard_layout(size_t payload_bytes, size_t frame_bytes) {
+  GuardLayout g;
+  g.payload = (payload_bytes + 3) / 4 * 4;
+  g.lead = guard_band_bytes(frame_bytes);
+  g.tail = (g.payload + kGuardAlign - 1) / kGuardAlign * kGuardAlign - g.payload + g.lead;
+  return g;
+}
+
+// Index of the first word of a band that no longer holds `fill`, or -1.
+inline long guard_first_bad(const uint32_t *words, size_t n, uint32_t fill = kPoisonWord) {
+  for (size_t i = 0; i < n; ++i)
+    if (words[i] != fill) return (long)i;
+  return -1;
+}
+
+// The message for word `idx` of the band before (`after` = false) or after the payload: the buffer, the side and the offset in
+// elements of `elem_bytes` relative to the payload's first element (negative before it, >= its element count after it).
+inline std::string guard_message(const std::string &name, const GuardLayout &g, bool after, size_t idx, size_t elem_bytes, uint32_t got) {
+  const long long rel = after ? (long long)(g.payload + 4 * idx) : (long long)(4 * idx) - (long long)g.lead;   // bytes from the payload's start
+  const long long eb = elem_bytes ? (long long)elem_bytes : 4;
+  const long long elem = rel >= 0 ? rel / eb : -((-rel + eb - 1) / eb);
+  char hex[16];
+  std::snprintf(hex, sizeof hex, "0x%08x", got);
+  return name + ": stray store into the band " + (after ? "after" : "before") + " the buffer, element offset " + std::to_string(elem) +
+         (after ? " (" + std::to_string(rel - (long long)g.payload) + " bytes past its end)" : " (" + std::to_string(-rel) + " bytes before its start)") +
+         ", the word there is " + hex;
 }
 
 // Tuned tile shapes are cached per power-of-two bucket of the clip count (ragged last batches of a video

@@ -401,7 +401,21 @@ def _need_cuda_f32(**tensors) -> None:
             raise ValueError(f'{name} must be a float32 CUDA tensor')
 
 
-def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8):
+def _out(out, shape, dtype, like, name: str = 'out'):
+    """The op wrappers' optional ``out=``: checked here, before anything is launched (the C ABI takes a bare pointer) -- a
+    contiguous tensor of exactly this shape and dtype on `like`'s device; allocated when None."""
+    import torch
+    shape = tuple(int(d) for d in shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if not (hasattr(out, 'is_cuda') and out.is_cuda and out.device == like.device and out.dtype == dtype
+            and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {shape} on {like.device}, got '
+                         f'{getattr(out, "dtype", type(out))} {tuple(getattr(out, "shape", ()))} on {getattr(out, "device", None)}')
+    return out
+
+
+def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8, out=None):
     """x: CUDA float32 [N*T, H, W, C] (NHWC) -> shifted copy (tsm.py:35-50)."""
     import torch
     _need_cuda_f32(x=x)
@@ -409,7 +423,7 @@ def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8):
     n, h, w, c = x.shape
     if n_segment <= 0 or n % n_segment:
         raise ValueError(f'{n} frames are not a whole number of {n_segment}-frame clips')
-    y = torch.empty_like(x)
+    y = _out(out, x.shape, torch.float32, x)
     _lib.check(_lib.load().tsm_temporal_shift(x.data_ptr(), y.data_ptr(), n, n_segment, h * w, c, fold_div,
                                               _stream(x)))
     return y
@@ -417,13 +431,14 @@ def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8):
 
 def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool = True, residual=None,
                      shift_segments: int = 0, fold_div: int = 8, dtype: str = 'f32', *, shift_identity: bool = False,
-                     x2=None, w2=None, bn2=None, stride2: int = 1, code: Optional[int] = None, reverse: bool = False):
+                     x2=None, w2=None, bn2=None, stride2: int = 1, code: Optional[int] = None, reverse: bool = False, out=None):
     """x NHWC [n,h,w,cin], w OIHW; returns NHWC [n,ho,wo,cout].
 
     The keyword arguments reach the engine's other conv forms through ``tsm_conv_op``: ``shift_identity`` shifts the
     identity (the residual, else the second source; for a 1x1 at stride 2 the input) instead of the input; ``x2`` [n,h2,w2,cin2]
     with ``w2`` [cout,cin2,1,1] and ``bn2`` = (gamma, beta, mean, var) adds a 1x1 conv of x2 at ``stride2`` to a 1x1 main conv
-    as one K-concatenated GEMM (conv3 + downsample); ``code`` is a tile code (0 = heuristic), ``reverse`` the tile walk."""
+    as one K-concatenated GEMM (conv3 + downsample); ``code`` is a tile code (0 = heuristic), ``reverse`` the tile walk.
+    ``out``: write into this tensor (contiguous float32 [n,ho,wo,cout] on x's device) instead of allocating one."""
     import torch
     _need_cuda_f32(x=x, w=w, gamma=gamma, beta=beta, mean=mean, var=var, residual=residual, x2=x2, w2=w2)
     x = x.contiguous()
@@ -433,7 +448,7 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
         raise ValueError(f'w {tuple(w.shape)} / BatchNorm vectors do not match x {tuple(x.shape)}')
     pad = k // 2
     ho, wo = (hi + 2 * pad - k) // stride + 1, (wi + 2 * pad - k) // stride + 1
-    y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
+    y = _out(out, (n, ho, wo, cout), torch.float32, x)
     if residual is not None and tuple(residual.shape) != tuple(y.shape):
         raise ValueError(f'residual {tuple(residual.shape)} must have the output shape {tuple(y.shape)}')
     res = None if residual is None else residual.contiguous()
@@ -469,7 +484,7 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
 
 
 def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: bool = False, packed: bool = True,
-                      layout: Optional[int] = None):
+                      layout: Optional[int] = None, out=None):
     """HIP test transform.  frames: CUDA uint8 or float32 [n,H,W,3] (decoder layout, values 0..255).
     Returns float32 [n,crop,crop,4] (``packed``: feed ``forward_device(..., layout=LAYOUT_NTHWC4)``),
     [n,3,crop,crop] (``packed=False``), or with ``layout=engine.packed_layout`` the packed format of that
@@ -492,7 +507,7 @@ def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: boo
     shape = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
              _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4),     # 8 bf16 = 16 bytes = 4 float slots per pair
              _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}[layout]
-    out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    out = _out(out, shape, torch.float32, frames)
     _lib.check(_lib.load().tsm_preprocess(frames.data_ptr(), pixel, n, h, w, out.data_ptr(), layout, resize, crop,
                                           int(scale_255), _stream(frames)))
     return out
@@ -524,7 +539,7 @@ def gather_clips(frames, first_frame: int, total_frames: int, first_clip: int, n
     return out
 
 
-def scores_to_states(logits, threshold: float = 0.5, softmax: bool = True, return_top: bool = False):
+def scores_to_states(logits, threshold: float = 0.5, softmax: bool = True, return_top: bool = False, out=None, out_top=None):
     """K9 on the GPU: CUDA float32 logits [n, num_class] -> int32 states [n] (utils/eval.py:153-164: softmax, first
     arg-max, class id if its score >= threshold else -1) and optionally the winning score.  Enqueues on torch's
     current stream; no host sync."""
@@ -534,24 +549,26 @@ def scores_to_states(logits, threshold: float = 0.5, softmax: bool = True, retur
         raise ValueError(f'logits must be [n >= 1, num_class], got {tuple(logits.shape)}')
     logits = logits.contiguous()
     n, c = logits.shape
-    states = torch.empty(n, dtype=torch.int32, device=logits.device)
-    top = torch.empty(n, dtype=torch.float32, device=logits.device) if return_top else None
+    if out_top is not None and not return_top:
+        raise ValueError('out_top needs return_top=True')
+    states = _out(out, (n,), torch.int32, logits)
+    top = _out(out_top, (n,), torch.float32, logits, 'out_top') if return_top else None
     _lib.check(_lib.load().tsm_scores_to_states(logits.data_ptr(), n, c, int(softmax), float(threshold),
                                                 states.data_ptr(), _ptr(top), _stream(logits)))
     return (states, top) if return_top else states
 
 
-def maxpool3x3s2_nhwc(x):
+def maxpool3x3s2_nhwc(x, out=None):
     import torch
     _need_cuda_f32(x=x)
     x = x.contiguous()
     n, hi, wi, c = x.shape
-    y = torch.empty((n, (hi - 1) // 2 + 1, (wi - 1) // 2 + 1, c), dtype=torch.float32, device=x.device)
+    y = _out(out, (n, (hi - 1) // 2 + 1, (wi - 1) // 2 + 1, c), torch.float32, x)
     _lib.check(_lib.load().tsm_maxpool3x3s2(x.data_ptr(), y.data_ptr(), n, hi, wi, c, _stream(x)))
     return y
 
 
-def head_nhwc(feat, fc_w, fc_b, n_segment: int):
+def head_nhwc(feat, fc_w, fc_b, n_segment: int, out=None):
     import torch
     _need_cuda_f32(feat=feat, fc_w=fc_w, fc_b=fc_b)
     feat = feat.contiguous()
@@ -559,7 +576,7 @@ def head_nhwc(feat, fc_w, fc_b, n_segment: int):
     if n_segment <= 0 or n % n_segment or tuple(fc_w.shape)[1:] != (c,) or tuple(fc_b.shape) != (fc_w.shape[0],):
         raise ValueError(f'feat {tuple(feat.shape)}, fc_w {tuple(fc_w.shape)}, fc_b {tuple(fc_b.shape)}, T={n_segment} do not fit')
     b = n // n_segment
-    out = torch.empty((b, fc_w.shape[0]), dtype=torch.float32, device=feat.device)
+    out = _out(out, (b, fc_w.shape[0]), torch.float32, feat)
     _lib.check(_lib.load().tsm_head(feat.data_ptr(), fc_w.contiguous().data_ptr(), fc_b.contiguous().data_ptr(),
                                     out.data_ptr(), b, n_segment, h * w, c, fc_w.shape[0], _stream(feat)))
     return out

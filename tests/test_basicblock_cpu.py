@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests._basicblock_ref import TorchBasicTSM
+from oracle import tsm_oracle
+from tests._torch_tsm import TorchTSM
 from workoutdetector_amd import flops, weights
 
 BASIC = ['resnet18', 'resnet34']
@@ -13,7 +14,7 @@ BASIC = ['resnet18', 'resnet34']
 @pytest.mark.parametrize('base_model', BASIC)
 def test_basic_keys_and_shapes_match_a_torch_module(base_model):
     """conv_specs / make_state_dict / required_keys spell the module tree of TSM-R18/34 (conv1 wrapped as `.net`)."""
-    want = TorchBasicTSM(base_model).engine_state_dict()
+    want = TorchTSM(base_model).engine_state_dict()
     sd = weights.make_state_dict(3, 12, base_model=base_model)
     assert list(sd) == list(want)                                   # same keys, torchvision's module order
     for k, v in want.items():
@@ -27,7 +28,7 @@ def test_basic_keys_and_shapes_match_a_torch_module(base_model):
     # bn2 closes the residual branch of a BasicBlock: it is the damped one
     assert sd['base_model.layer1.0.bn2.weight'].max() < 0.5 < sd['base_model.layer1.0.bn1.weight'].min()
     # and the engine-facing model loads it strictly
-    TorchBasicTSM(base_model).load_engine_state_dict(sd)
+    TorchTSM(base_model).load_engine_state_dict(sd)
 
 
 def test_r50_weights_stream_is_unchanged():
@@ -86,7 +87,7 @@ def test_r50_flops_unchanged():
 
 def test_basic_checkpoint_remap():
     """A Lightning checkpoint of TSM-R18 (``model.`` prefix, ``new_fc`` last) maps onto the engine keys."""
-    net = TorchBasicTSM('resnet18')
+    net = TorchTSM('resnet18')
     raw = {'model.' + k: v for k, v in net.state_dict().items()}
     got = weights.remap_checkpoint_keys(raw, 12, base_model='resnet18')
     want = net.engine_state_dict()
@@ -99,11 +100,10 @@ def test_basic_checkpoint_remap():
 def test_basic_onnx_export_is_imported(tmp_path, style):
     """``torch.onnx.export`` of the R18 module: recognised as R18 from the graph; the names-kept export gives the state
     dict back exactly, the Conv+BN-fused one drives the CPU reference to the same logits."""
-    from tests import _basicblock_ref as ref
     from tests._torch_tsm import LitWrapper, export_onnx
     from workoutdetector_amd.onnx_import import load_onnx_state_dict, parse_onnx
     sd = weights.make_state_dict(5, 12, base_model='resnet18')
-    net = TorchBasicTSM('resnet18').load_engine_state_dict(sd)
+    net = TorchTSM('resnet18').load_engine_state_dict(sd)
     path = str(tmp_path / f'r18_{style}.onnx')
     export_onnx(LitWrapper(net), path, sample_shape=(1, 8, 3, 64, 64), training=(style == 'training'))
     inits, nodes = parse_onnx(path)
@@ -116,8 +116,8 @@ def test_basic_onnx_export_is_imported(tmp_path, style):
     if style == 'training':
         assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
     x = torch.randn(1, 8, 3, 64, 64, generator=torch.Generator().manual_seed(2))
-    want = ref.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x, 'resnet18')
-    have = ref.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x, 'resnet18')
+    want = tsm_oracle.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x, 'resnet18')
+    have = tsm_oracle.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x, 'resnet18')
     assert float((have - want).abs().max()) <= 1e-5 * float(want.abs().max())
     with torch.no_grad():
         assert float((net.eval()(x) - want).abs().max()) <= 1e-4 * float(want.abs().max())

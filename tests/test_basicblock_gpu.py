@@ -1,5 +1,5 @@
 """TSM-ResNet18 / 34 on the MI355X: the shifted 3x3 loader and the 3x3 + residual epilogue per op, the BasicBlock
-forward end to end against the CPU reference (tests/_basicblock_ref.py), and what runs (launch trace).
+forward end to end against the CPU reference (oracle/tsm_oracle.py), and what runs (launch trace).
 
 Bars: fp32 and split-bf16 as for the R50 engine (rtol 1e-3 on logits and taps); bf16 against the bf16-storage
 restatement (BF16_E2E_BAR on logits, BF16_TAP_BAR on taps); per op as in test_ops_gpu / test_bf16x3_gpu / test_bf16_gpu."""
@@ -11,7 +11,6 @@ import pytest
 import torch
 
 from oracle import tsm_oracle
-from tests import _basicblock_ref as ref
 from tests._util import BF16_TAP_BAR, assert_bf16_op, assert_close, bf16_logits_report, make_input
 
 pytestmark = pytest.mark.gpu
@@ -145,11 +144,11 @@ def test_basic_engine_against_cpu_reference(hip_lib, capsys, base_model, h, w, d
     eng = create_model(num_class=12, base_model=base_model, height=h, width=w, max_clips=2, dtype=dtype)
     x = make_input(31, 2, 8, h, w)
     taps, taps16 = {}, {}
-    want = ref.forward(_torch_sd(sd), torch.from_numpy(x), base_model, taps=taps).numpy()
+    want = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), base_model, taps=taps).numpy()
     got = eng.run(None, {'input': x})[0]
     what = f'{base_model} {dtype} {h}x{w}'
     if dtype == 'bf16':
-        want16 = ref.forward(_torch_sd(sd), torch.from_numpy(x), base_model, taps=taps16, bf16=True).numpy()
+        want16 = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), base_model, bf16=True, taps=taps16).numpy()
         bf16_logits_report(got, want16, want, what, capsys)
     else:
         assert_close(got, want, rtol=1e-3, atol_scale=1e-5, what=what + ' logits')
@@ -201,9 +200,9 @@ def test_basic_engine_without_shift(hip_lib):
     with launch_trace() as tr:
         got = eng.run(None, {'input': x})[0]
     assert not any('SHIFT = true' in k for k in tr.kernels)
-    want = ref.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18', is_shift=False).numpy()
+    want = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18', is_shift=False).numpy()
     assert_close(got, want, rtol=1e-3, atol_scale=1e-5, what='resnet18 no shift')
-    shifted = ref.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18').numpy()
+    shifted = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18').numpy()
     assert np.abs(shifted - want).max() > 1e-3 * np.abs(want).max()      # the shift matters at this size
 
 
@@ -244,15 +243,15 @@ def test_basic_engine_batch_split_is_identical(hip_lib, dtype):
 
 
 def test_basic_onnx_export_runs_on_the_engine(hip_lib, tmp_path):
-    from tests._torch_tsm import LitWrapper, export_onnx
+    from tests._torch_tsm import LitWrapper, TorchTSM, export_onnx
     from workoutdetector_amd.engine import create_model
     sd = _sd('resnet18', 6)
-    net = ref.TorchBasicTSM('resnet18').load_engine_state_dict(sd)
+    net = TorchTSM('resnet18').load_engine_state_dict(sd)
     path = str(tmp_path / 'tsm_r18.onnx')
     export_onnx(LitWrapper(net), path, sample_shape=(1, 8, 3, 64, 64))
     eng = create_model(num_class=12, checkpoint=path, base_model='resnet18', height=112, width=112, max_clips=2)
     x = make_input(3, 2, 8, 112, 112)
-    want = ref.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18').numpy()
+    want = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), 'resnet18').numpy()
     assert_close(eng.run(None, {'input': x})[0], want, rtol=1e-3, atol_scale=1e-5, what='onnx r18')
     eng.close()
 

@@ -1,5 +1,5 @@
 """Block placement of the temporal shift (``shift_place='block'``) on the CPU: argument checking, state-dict keys, the
-checkpoint / mmaction2 / ONNX key mappings, the CPU reference (tests/_block_place_ref.py) and the new kernel instantiations
+checkpoint / mmaction2 / ONNX key mappings, the CPU reference (oracle/tsm_oracle.py) and the new kernel instantiations
 in the built code object."""
 from collections import OrderedDict
 
@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import _block_place_ref as bref
+from oracle import tsm_oracle
+from tests._torch_tsm import TorchTSM
 from workoutdetector_amd.weights import (SHIFT_PLACES, conv_specs, make_state_dict, remap_checkpoint_keys,
                                          remap_mmaction_keys)
 
@@ -47,14 +48,14 @@ def test_block_keys(base_model):
         assert bb == f'base_model.{layer}.{b}.net.' + br.split('.', 3)[3]
     sd_r = make_state_dict(5, 12, base_model)
     sd_b = make_state_dict(5, 12, base_model, shift_place='block')
-    assert list(sd_b) == list(bref.as_block_keys(sd_r))
+    assert list(sd_b) == list(tsm_oracle.as_block_keys(sd_r))
     assert all(np.array_equal(a, b) for a, b in zip(sd_r.values(), sd_b.values()))     # one RNG stream, two spellings
     assert {k for k in sd_b if not k.startswith('base_model.layer')} == {k for k in sd_r if not k.startswith('base_model.layer')}
 
 
 @pytest.mark.parametrize('base_model', MODELS)
 def test_module_spelling_has_the_block_keys(base_model):
-    net = bref.torch_block_tsm(base_model)
+    net = TorchTSM(base_model, shift_place='block')
     keys = [k.replace('new_fc.', 'fc.') for k in net.state_dict() if not k.endswith('num_batches_tracked')]
     assert sorted(keys) == sorted(make_state_dict(0, 12, base_model, shift_place='block'))
 
@@ -89,14 +90,12 @@ def test_reference_matches_the_module_and_differs_from_blockres(base_model):
     sd = make_state_dict(2, 12, base_model, shift_place='block')
     tsd = {k: torch.from_numpy(v) for k, v in sd.items()}
     x = torch.randn(2, 8, 3, 64, 64, generator=torch.Generator().manual_seed(0))
-    want = bref.forward(tsd, x, base_model)
+    want = tsm_oracle.forward(tsd, x, base_model, 'block')
     with torch.no_grad():
-        got = bref.torch_block_tsm(base_model).load_engine_state_dict(sd).eval()(x)
+        got = TorchTSM(base_model, shift_place='block').load_engine_state_dict(sd).eval()(x)
     assert float((got - want).abs().max()) <= 1e-5 * float(want.abs().max())
     res_sd = {k: torch.from_numpy(v) for k, v in make_state_dict(2, 12, base_model).items()}
-    from tests import _basicblock_ref as basic
-    from oracle import tsm_oracle
-    blockres = (tsm_oracle.tsm_forward(res_sd, x) if base_model == 'resnet50' else basic.forward(res_sd, x, base_model))
+    blockres = tsm_oracle.forward(res_sd, x, base_model)
     assert float((blockres - want).abs().max()) > 1e-3 * float(want.abs().max())
 
 
@@ -109,7 +108,7 @@ def test_torch_export_of_block_placement_is_imported(tmp_path, base_model, style
     from workoutdetector_amd.onnx_import import load_onnx_state_dict, parse_onnx
     sd = make_state_dict(4, 12, base_model, shift_place='block')
     path = str(tmp_path / f'block_{style}.onnx')
-    export_onnx(LitWrapper(bref.torch_block_tsm(base_model).load_engine_state_dict(sd)), path,
+    export_onnx(LitWrapper(TorchTSM(base_model, shift_place='block').load_engine_state_dict(sd)), path,
                 sample_shape=(1, 8, 3, 64, 64), training=(style == 'training'))
     inits, _ = parse_onnx(path)
     assert any(k.startswith('onnx::Conv_') for k in inits) == (style == 'eval')
@@ -119,8 +118,8 @@ def test_torch_export_of_block_placement_is_imported(tmp_path, base_model, style
     else:
         assert set(got) == set(sd)
     x = torch.randn(1, 8, 3, 64, 64, generator=torch.Generator().manual_seed(1))
-    want = bref.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x, base_model)
-    have = bref.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x, base_model)
+    want = tsm_oracle.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x, base_model, 'block')
+    have = tsm_oracle.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x, base_model, 'block')
     assert float((have - want).abs().max()) <= 1e-5 * float(want.abs().max())
 
 

@@ -1,5 +1,5 @@
 """Block placement of the temporal shift (``shift_place='block'``) on the MI355X: logits and stage taps against the CPU
-reference (tests/_block_place_ref.py) for R50 / R18 / R34 in every precision, the shifted-identity / shifted-second-source
+reference (oracle/tsm_oracle.py) for R50 / R18 / R34 in every precision, the shifted-identity / shifted-second-source
 arms of conv_igemm on every generic tile (bit-identical, asserted from the launch trace), the fused forms a block engine
 refuses, the C ABI contract of tsm_set_shift_place, ONNX checkpoints and the counting pipeline.
 
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import _block_place_ref as bref
+from oracle import tsm_oracle
 from tests._util import BF16_TAP_BAR, IGEMM_TILE_DIMS, assert_close, bf16_logits_report, make_input
 
 pytestmark = pytest.mark.gpu
@@ -61,14 +61,15 @@ def test_block_engine_against_reference(hip_lib, capsys, base_model, dtype, b, t
                        width=w, max_clips=b, dtype=dtype)
     x = make_input(41, b, t, h, w)
     taps, taps16 = {}, {}
-    want = bref.forward(_t(sd), torch.from_numpy(x), base_model, t, div, taps=taps).numpy()
+    want = tsm_oracle.forward(_t(sd), torch.from_numpy(x), base_model, 'block', n_segment=t, shift_div=div, taps=taps).numpy()
     with launch_trace() as tr:
         got = eng.run(None, {'input': x})[0]
     assert _arms(tr), tr.kernels
     assert not tr.ran('temporal_shift_kernel'), 'the shifted block input must never be materialised'
     what = f'{base_model} {dtype} B{b} T{t} {h}x{w} div{div}'
     if dtype == 'bf16':
-        want16 = bref.forward(_t(sd), torch.from_numpy(x), base_model, t, div, taps=taps16, bf16=True).numpy()
+        want16 = tsm_oracle.forward(_t(sd), torch.from_numpy(x), base_model, 'block', bf16=True, n_segment=t, shift_div=div,
+                                    taps=taps16).numpy()
         bf16_logits_report(got, want16, want, what, capsys)
     else:
         assert_close(got, want, rtol=1e-3, atol_scale=1e-5, what=what + ' logits')
@@ -222,15 +223,15 @@ def test_set_shift_place_contract(hip_lib, tmp_path, monkeypatch):
 
 @pytest.mark.parametrize('style', ['eval', 'training'])
 def test_onnx_checkpoint_of_block_placement(hip_lib, tmp_path, style):
-    from tests._torch_tsm import LitWrapper, export_onnx
+    from tests._torch_tsm import LitWrapper, TorchTSM, export_onnx
     from workoutdetector_amd.engine import create_model
     sd = _sd('resnet50', 7)
     path = str(tmp_path / f'block_{style}.onnx')
-    export_onnx(LitWrapper(bref.torch_block_tsm('resnet50').load_engine_state_dict(sd)), path,
+    export_onnx(LitWrapper(TorchTSM(shift_place='block').load_engine_state_dict(sd)), path,
                 sample_shape=(1, 8, 3, 64, 64), training=(style == 'training'))
     eng = create_model(num_class=12, checkpoint=path, shift_place='block', height=96, width=112, max_clips=2)
     x = make_input(8, 2, 8, 96, 112)
-    want = bref.forward(_t(sd), torch.from_numpy(x)).numpy()
+    want = tsm_oracle.forward(_t(sd), torch.from_numpy(x), shift_place='block').numpy()
     assert_close(eng.run(None, {'input': x})[0], want, rtol=1e-3, atol_scale=1e-5, what=f'onnx block {style}')
     eng.close()
 
@@ -253,7 +254,8 @@ def test_counting_pipeline_with_a_block_engine(hip_lib):
     eng = TsmEngine(num_class=12, num_segments=8, max_clips=32, shift_place='block', state_dict=sd)
     vid = torch.from_numpy(synthetic_video(23, 140, 90, 52, period=24))
     got = ic.video_clip_logits(eng, vid, build_test_transform(False), batch_clips=32)
-    want = torch.cat([bref.forward(_t(sd), transform_oracle.clip_to_input(transform_oracle.make_clip(vid, s)))
+    want = torch.cat([tsm_oracle.forward(_t(sd), transform_oracle.clip_to_input(transform_oracle.make_clip(vid, s)),
+                                         shift_place='block')
                       for s in range(0, 140, 8)])
     assert_close(got.numpy(), want.numpy(), rtol=1e-3, atol_scale=1e-5, what='block stream logits')
     states = scores_to_preds(got.tolist())

@@ -432,6 +432,7 @@ def test_tune_cache_keeps_the_fusion_bits(hip_lib, sd0, tmp_path, monkeypatch):
     tuner picks the whole-block kernel writes its line; the line is then edited (every layer1 / layer2 fusion bit the
     layer supports is set or cleared by hand) and a second engine must report exactly the edited codes."""
     from workoutdetector_amd.engine import TsmEngine
+    from workoutdetector_amd.weights import BACKBONES
     path = tmp_path / 'tiles.txt'
     monkeypatch.setenv('TSM_TUNE_CACHE', str(path))
     x = make_input(52, 32, 8, 224, 224)[:32]
@@ -444,7 +445,7 @@ def test_tune_cache_keeps_the_fusion_bits(hip_lib, sd0, tmp_path, monkeypatch):
     codes = [int(c) for c in codes.split(',')]
     assert any(c & 0x800 for c in codes) or any(c & 0x400 for c in codes), tiles_a     # the tuner uses a fused form at this size
     # the line is in the engine's layer order: stem, then per block conv1, conv2, conv3 (, downsample)
-    order = ['conv1'] + [f'layer{li}.{b}.{part}' for li, nb in enumerate((3, 4, 6, 3), 1) for b in range(nb)
+    order = ['conv1'] + [f'layer{li}.{b}.{part}' for li, nb in enumerate(BACKBONES['resnet50'][0], 1) for b in range(nb)
                          for part in ('conv1', 'conv2', 'conv3') + (('downsample',) if b == 0 else ())]
     assert len(order) == len(codes) == 53
     flipped = list(codes)
@@ -467,6 +468,7 @@ def test_tune_cache_fusion_bit_of_a_form_that_cannot_run(hip_lib, sd0, tmp_path,
     +8192 (shift + conv1 + the stride-2 conv2 of layer2.0 as one launch) on a bf16 90 x 70 engine, whose layer2 input has an
     odd height.  The forward keeps the two launches, the result does not change, and conv_tiles reports what ran: no '+conv2'."""
     from workoutdetector_amd.engine import TsmEngine, launch_trace
+    from workoutdetector_amd.weights import BACKBONES
     path = tmp_path / 'tiles.txt'
     monkeypatch.setenv('TSM_TUNE_CACHE', str(path))
     x = make_input(54, 2, 8, 90, 70)
@@ -476,7 +478,7 @@ def test_tune_cache_fusion_bit_of_a_form_that_cannot_run(hip_lib, sd0, tmp_path,
     key, codes = path.read_text().splitlines()[0].rsplit('|', 1)
     codes = [int(c) for c in codes.split(',')]
     # the line is in the engine's layer order: stem, then per block conv1, conv2, conv3 (, downsample)
-    order = ['conv1'] + [f'layer{li}.{b}.{part}' for li, nb in enumerate((3, 4, 6, 3), 1) for b in range(nb)
+    order = ['conv1'] + [f'layer{li}.{b}.{part}' for li, nb in enumerate(BACKBONES['resnet50'][0], 1) for b in range(nb)
                          for part in ('conv1', 'conv2', 'conv3') + (('downsample',) if b == 0 else ())]
     codes[order.index('layer2.0.conv1')] |= 0x2000
     path.write_text(key + '|' + ','.join(str(c) for c in codes) + '\n')

@@ -17,7 +17,6 @@ import pytest
 import torch
 
 from oracle import tsm_oracle
-from tests import _basicblock_ref, _block_place_ref, _wide_ref
 from tests._guard import POISON
 from tests._util import assert_close, assert_ran, assert_walked, bf16_logits_report, make_input
 from tests.test_walk_gpu import ENGINE_PARAMS, FORMS, FUSE_KNOBS, GEOMETRIES, _fused_kernel
@@ -255,10 +254,5 @@ def test_other_backbones_under_poison(hip_lib, monkeypatch, capsys, base_model, 
                              base_model=base_model, shift_place=place)
     stages = R18_STAGES if base_model == 'resnet18' else R50_STAGES
     out, _ = _pair(monkeypatch, {'TSM_TUNE_CACHE': 'off'}, make, lambda e: _outputs(e, x, stages))
-    if base_model == 'resnet18':
-        ref = lambda bf16: _basicblock_ref.forward(sdt, xt, base_model, t, bf16=bf16).numpy()      # noqa: E731
-    elif place == 'block':
-        ref = lambda bf16: _block_place_ref.forward(sdt, xt, base_model, t, bf16=bf16).numpy()     # noqa: E731
-    else:
-        ref = lambda bf16: _wide_ref.forward(sdt, xt, t, shift_place=place, bf16=bf16).numpy()     # noqa: E731
+    ref = lambda bf16: tsm_oracle.forward(sdt, xt, base_model, place, bf16, n_segment=t).numpy()      # noqa: E731
     _oracle_bar(out['logits'], sdt, x, t, dtype, f'{base_model} {place} {dtype} poisoned', capsys, ref=ref)

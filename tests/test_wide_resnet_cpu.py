@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests._wide_ref import TorchWideTSM
+from oracle import tsm_oracle
+from tests._torch_tsm import TorchTSM
 from workoutdetector_amd import flops, weights
 
 WRN = 'wide_resnet50_2'
@@ -48,8 +49,8 @@ def test_wide_state_dict_matches_a_torch_module(place):
             assert sd[bn + s].shape == (co,)
     assert sd['fc.weight'].shape == (12, 2048)
     if place == 'blockres':
-        TorchWideTSM(128).load_engine_state_dict(sd)                 # the module tree spells the same keys
-        assert set(TorchWideTSM(128).engine_state_dict()) == set(sd)
+        TorchTSM(WRN, 128).load_engine_state_dict(sd)                 # the module tree spells the same keys
+        assert set(TorchTSM(WRN, 128).engine_state_dict()) == set(sd)
 
 
 def test_wide_weights_stream_is_deterministic_and_r50_is_unchanged():
@@ -98,7 +99,7 @@ def test_create_model_accepts_wrn_and_refuses_the_deep_backbones():
 
 
 def test_wide_checkpoint_remap_keeps_the_r50_keys():
-    net = TorchWideTSM(128)
+    net = TorchTSM(WRN, 128)
     raw = {'model.' + k: v for k, v in net.state_dict().items()}
     got = weights.remap_checkpoint_keys(raw, 12, base_model=WRN)
     want = net.engine_state_dict()
@@ -110,13 +111,12 @@ def test_wide_checkpoint_remap_keeps_the_r50_keys():
 @pytest.mark.parametrize('style', ['training', 'eval'])
 def test_wide_and_r50_onnx_exports_are_told_apart(tmp_path, style):
     """53 Conv nodes each: a WRN export imports as WRN, an R50 export of the same module class still as R50."""
-    from tests import _wide_ref
     from tests._torch_tsm import LitWrapper, export_onnx
     from workoutdetector_amd.onnx_import import detect_backbone, load_onnx_state_dict, parse_onnx
     x = torch.randn(1, 8, 3, 64, 64, generator=torch.Generator().manual_seed(2))
     for base_model, width in ((WRN, 128), ('resnet50', 64)):
         sd = weights.make_state_dict(5, 12, base_model=base_model)
-        net = TorchWideTSM(width).load_engine_state_dict(sd)
+        net = TorchTSM(base_model, width).load_engine_state_dict(sd)
         path = str(tmp_path / f'{base_model}_{style}.onnx')
         export_onnx(LitWrapper(net), path, sample_shape=(1, 8, 3, 64, 64), training=(style == 'training'))
         inits, nodes = parse_onnx(path)
@@ -129,8 +129,8 @@ def test_wide_and_r50_onnx_exports_are_told_apart(tmp_path, style):
             load_onnx_state_dict(path, 12, base_model=other)
         if style == 'training':
             assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
-        want = _wide_ref.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x)
-        have = _wide_ref.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x)
+        want = tsm_oracle.forward({k: torch.from_numpy(v) for k, v in sd.items()}, x, base_model)
+        have = tsm_oracle.forward({k: torch.from_numpy(np.asarray(v)) for k, v in got.items()}, x, base_model)
         assert float((have - want).abs().max()) <= 1e-5 * float(want.abs().max())
         with torch.no_grad():
             assert float((net.eval()(x) - want).abs().max()) <= 1e-4 * float(want.abs().max())

@@ -1,5 +1,5 @@
 """TSM-Wide-ResNet-50-2 on the MI355X: logits and stage taps against the CPU oracle (which reads every width from the state
-dict: tests/_wide_ref.py) under both shift placements, the two-chunk fused conv2 + conv3 kernel of layer1.1-2 (bitwise
+dict: oracle/tsm_oracle.py) under both shift placements, the two-chunk fused conv2 + conv3 kernel of layer1.1-2 (bitwise
 against the separate launches), every other fused / specialised form either bit-identical or refused, tuned vs untuned,
 the tsm_set_bottleneck_width contract and the tune cache.
 
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import _wide_ref
+from oracle import tsm_oracle
 from tests._util import BF16_TAP_BAR, assert_close, assert_fused_slots, bf16_logits_report, make_input
 
 pytestmark = pytest.mark.gpu
@@ -52,11 +52,11 @@ def test_wide_engine_against_oracle(hip_lib, capsys, dtype, place, T, is_shift, 
     x = make_input(41 + T, 2, T, h, w)
     got = eng.run(None, {'input': x})[0]
     t32, t16 = {}, {}
-    want = _wide_ref.forward(_torch_sd(sd), torch.from_numpy(x), T, is_shift=is_shift, shift_place=place, taps=t32).numpy()
+    want = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), WRN, place, n_segment=T, is_shift=is_shift, taps=t32).numpy()
     what = f'WRN-50-2 {dtype} {place} T{T} shift {is_shift} {h}x{w}'
     if dtype == 'bf16':
-        want16 = _wide_ref.forward(_torch_sd(sd), torch.from_numpy(x), T, is_shift=is_shift, shift_place=place, taps=t16,
-                                   bf16=True).numpy()
+        want16 = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), WRN, place, True, n_segment=T, is_shift=is_shift,
+                                    taps=t16).numpy()
         bf16_logits_report(got, want16, want, what, capsys)
     else:
         assert_close(got, want, rtol=1e-3, atol_scale=1e-5, what=what + ' logits')
@@ -236,14 +236,14 @@ def test_tune_cache_keeps_wrn_and_r50_apart(hip_lib, monkeypatch, tmp_path):
 
 
 def test_wrn_onnx_export_runs_on_the_engine(hip_lib, tmp_path):
-    from tests._torch_tsm import LitWrapper, export_onnx
+    from tests._torch_tsm import LitWrapper, TorchTSM, export_onnx
     from workoutdetector_amd.engine import create_model
     sd = _sd(6)
-    net = _wide_ref.TorchWideTSM(128).load_engine_state_dict(sd)
+    net = TorchTSM(WRN, 128).load_engine_state_dict(sd)
     path = str(tmp_path / 'tsm_wrn.onnx')
     export_onnx(LitWrapper(net), path, sample_shape=(1, 8, 3, 64, 64))
     eng = create_model(num_class=12, checkpoint=path, base_model=WRN, height=112, width=112, max_clips=2)
     x = make_input(3, 2, 8, 112, 112)
-    want = _wide_ref.forward(_torch_sd(sd), torch.from_numpy(x)).numpy()
+    want = tsm_oracle.forward(_torch_sd(sd), torch.from_numpy(x), WRN).numpy()
     assert_close(eng.run(None, {'input': x})[0], want, rtol=1e-3, atol_scale=1e-5, what='onnx wrn')
     eng.close()

@@ -14,9 +14,8 @@ and K timed forwards run back to back on torch's current stream, one event per s
   peak_frac        achieved FLOP/s over the exact-fp32 MFMA peak (f32) or the dense bf16 MFMA peak (bf16, bf16x3): a
                    whole-forward figure, not a kernel's share of peak
   logits_err       max |logits - CPU restatement| / max |CPU restatement| on the first two clips of the last timed step:
-                   fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py for R50 and
-                   WRN-50-2, whose Bottlenecks take every shape from the state dict,
-                   tests/_basicblock_ref.py for R18 / R34, tests/_block_place_ref.py for block placement)
+                   fp32 reference for f32 / bf16x3, the bf16-storage restatement for bf16 (oracle/tsm_oracle.py: one
+                   ``forward`` for every backbone and placement)
 
 No CPU fallback: without a GPU it fails.
 """
@@ -36,18 +35,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0   # MI355X_MICROARCH.md, "Peak BF16/FP16 MFMA", d
 def reference_logits(base_model, sd, clips, t, dtype, shift_place='blockres'):
     import torch
     from oracle import tsm_oracle
-    from tests import _basicblock_ref
     sd_t = {k: torch.from_numpy(v) for k, v in sd.items()}
-    bf16 = dtype == 'bf16'
-    if base_model == 'wide_resnet50_2':   # R50's schedule: the oracle's Bottleneck reads every width from the state dict
-        base_model = 'resnet50'
-    if shift_place == 'block':
-        from tests import _block_place_ref
-        return _block_place_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()
-    if base_model == 'resnet50':
-        fwd = tsm_oracle.tsm_forward_bf16 if bf16 else tsm_oracle.tsm_forward
-        return fwd(sd_t, clips, n_segment=t).numpy()
-    return _basicblock_ref.forward(sd_t, clips, base_model, n_segment=t, bf16=bf16).numpy()
+    return tsm_oracle.forward(sd_t, clips, base_model, shift_place, bf16=(dtype == 'bf16'), n_segment=t).numpy()
 
 
 def run_one(args, base_model, dtype, shift_place='blockres'):

@@ -8,6 +8,7 @@ import os
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from workoutdetector_amd.flops import layer_table  # noqa: E402
+from workoutdetector_amd.weights import BACKBONES  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from hbm_traffic import forward_starts  # noqa: E402
 
@@ -46,7 +47,7 @@ def match_schedule(convs):
         return r
 
     take(['conv1'])
-    blocks = [f'layer{li}.{b}' for li, nb in enumerate((3, 4, 6, 3), 1) for b in range(nb)]
+    blocks = [f'layer{li}.{b}' for li, nb in enumerate(BACKBONES['resnet50'][0], 1) for b in range(nb)]
     have_t1 = False       # the previous block's conv3 launch (conv31_fused_kernel) ran this block's shift + conv1 as well
     for k, p in enumerate(blocks):
         if True:

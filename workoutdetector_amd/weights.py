@@ -55,39 +55,50 @@ def _shift_place(shift_place: str) -> str:
     return shift_place
 
 
+STEM = ('base_model.conv1.weight', 'base_model.bn1', 64, 3, 7)
+
+
+def block_specs(base_model: str = 'resnet50'):
+    """The structure of TSM-``base_model``, one ``(stage, block, stride, convs)`` per block in forward order; ``convs``
+    lists the block's convs in torchvision's module order as ``(role, cout, cin, k, stride, at_input)``: role is
+    ``conv1|conv2|conv3|downsample``, ``at_input`` says whether the conv reads at the block's input size (else at its
+    output size).  A Bottleneck of stage planes p is conv1 [m, cin], conv2 [m, m, 3, 3] (strided), conv3 [4p, m] and, in
+    the first block of a stage, downsample [4p, cin], with mid width m = p * width / 64 (``WIDTHS``).  A BasicBlock is
+    conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the first block of a stage changes the size or
+    the width."""
+    blocks, kind = _backbone(base_model)
+    width = bottleneck_width(base_model)
+    cin = 64
+    for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
+        mid, cout = (planes, planes) if kind == 'basic' else (planes * width // 64, planes * EXPANSION)
+        for b in range(nb):
+            s = 2 if (b == 0 and li > 1) else 1
+            if kind == 'basic':
+                convs = [('conv1', mid, cin, 3, s, True), ('conv2', cout, mid, 3, 1, False)]
+                down = b == 0 and li > 1
+            else:
+                convs = [('conv1', mid, cin, 1, 1, True), ('conv2', mid, mid, 3, s, True), ('conv3', cout, mid, 1, 1, False)]
+                down = b == 0
+            if down:
+                convs.append(('downsample', cout, cin, 1, s, True))
+            yield li, b, s, convs
+            cin = cout
+
+
 def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> List[Tuple[str, str, int, int, int]]:
     """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50 and
-    WRN-50-2, 20 for R18, 36 for R34).  A Bottleneck of stage planes p is conv1 [m, cin], conv2 [m, m, 3, 3], conv3
-    [4p, m] and, in the first block of a stage, downsample [4p, cin], with mid width m = p * width / 64 (``WIDTHS``).  A BasicBlock is conv1 (3x3, shifted, strided), conv2 (3x3), then its downsample where the
-    first block of a stage changes the size or the width -- torchvision's module order.  ``shift_place='block'``: the
-    same convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``)."""
-    blocks, kind = _backbone(base_model)
+    WRN-50-2, 20 for R18, 36 for R34): the stem, then ``block_specs`` flattened.  ``shift_place='block'``: the same
+    convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``)."""
     block = _shift_place(shift_place) == 'block'
-    conv1 = '.conv1.weight' if block else '.conv1.net.weight'
-    specs = [('base_model.conv1.weight', 'base_model.bn1', 64, 3, 7)]
-    cin = 64
-    if kind == 'basic':
-        for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
-            for b in range(nb):
-                p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
-                specs.append((p + conv1, p + '.bn1', planes, cin, 3))
-                specs.append((p + '.conv2.weight', p + '.bn2', planes, planes, 3))
-                if b == 0 and li > 1:
-                    specs.append((p + '.downsample.0.weight', p + '.downsample.1', planes, cin, 1))
-                cin = planes
-        return specs
-    width = bottleneck_width(base_model)
-    for li, (nb, planes) in enumerate(zip(blocks, R50_PLANES), start=1):
-        mid = planes * width // 64
-        for b in range(nb):
-            p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
-            specs.append((p + conv1, p + '.bn1', mid, cin, 1))
-            specs.append((p + '.conv2.weight', p + '.bn2', mid, mid, 3))
-            specs.append((p + '.conv3.weight', p + '.bn3', planes * EXPANSION, mid, 1))
-            if b == 0:
-                specs.append((p + '.downsample.0.weight', p + '.downsample.1',
-                              planes * EXPANSION, cin, 1))
-            cin = planes * EXPANSION
+    specs = [STEM]
+    for li, b, _stride, convs in block_specs(base_model):
+        p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
+        for role, cout, cin, k, _s, _at_input in convs:
+            if role == 'downsample':
+                specs.append((p + '.downsample.0.weight', p + '.downsample.1', cout, cin, k))
+            else:
+                wkey = '.conv1.net.weight' if (role == 'conv1' and not block) else f'.{role}.weight'
+                specs.append((p + wkey, p + '.bn' + role[-1], cout, cin, k))
     return specs
 
 

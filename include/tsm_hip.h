@@ -12,6 +12,7 @@
  *       model.run(None, {input_name: float32[1,8,3,224,224]}) -> [float32[1,num_class]]
  *       workoutdetector/utils/inference_count.py:273-275, scripts/eval_classification.py:43-44
  *       == TSM.forward(x[B*T,3,H,W]) -> [B,num_class]   workoutdetector/models/tsm.py:409-419
+ *       ([B,T,num_class] with consensus_type='identity', tsm_set_consensus)
  *   tsm_tune               (no counterpart: onnxruntime optimises its graph inside InferenceSession(), :620; this is the
  *                          engine's per-batch-size kernel selection, made callable ahead of the first request)
  *   tsm_forward_tap        (parity tests) activation after a named stage of TSM.forward
@@ -21,6 +22,8 @@
  *   tsm_conv_op            the same with the engine's other conv forms (shifted identity, conv3 + downsample, tile code)
  *   tsm_maxpool3x3s2       base_model.maxpool
  *   tsm_head               avgpool -> fc -> view(-1,T,cls) -> mean(1)   tsm.py:411-419,165-174
+ *   tsm_set_consensus      create_model(consensus_type='avg' | 'identity')   workoutdetector/models/tsm.py:438,165-174
+ *   tsm_head_segments      avgpool -> fc -> view(-1,T,cls), SegmentConsensus('identity'): no mean   tsm.py:411-419,165-174
  *   tsm_gather_clips       the loop's clip windows: video[i:i + 16:2] for i in range(0, len(video), 8), zero-padded tail
  *   tsm_scores_to_states   per clip: to_softmax, first arg-max, score >= 0.5 ? class : -1
  *                          workoutdetector/utils/eval.py:153-164, utils/visualize.py:140-150
@@ -54,7 +57,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width (added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments (added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -167,6 +170,14 @@ int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group);
  * "base_model.layerL.B.net.<name>" (or the un-wrapped "base_model.layerL.B.<name>"); a blockres "conv1.net" key is unknown. */
 int tsm_set_shift_place(tsm_engine *e, int32_t place);
 
+/* Segment consensus of the head -- create_model(consensus_type=...), workoutdetector/models/tsm.py:438,165-174:
+ * 0 = 'avg' (default: the mean of the segments' fc outputs, logits [n_clips, num_class]), 1 = 'identity' (the fc output of
+ * every segment, logits [n_clips, num_segments, num_class]; one launch, head_seg_kernel).  Same contract as
+ * tsm_set_shift_place: legal between tsm_create and the first tsm_set_tensor, later TSM_ERR_INVALID_ARG; any other value
+ * TSM_ERR_UNSUPPORTED.  It changes neither a weight nor a conv launch, and the tune cache does not carry it: a cache line
+ * written by an avg engine serves an identity engine of the same geometry. */
+int tsm_set_consensus(tsm_engine *e, int32_t consensus);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;
@@ -178,7 +189,9 @@ int tsm_finalize(tsm_engine *e);
 
 /* Hot path ---------------------------------------------------------------------------------
  * clips:  n_clips x T x 3 x H x W float32 in `layout`, in `memkind` memory.
- * logits: float32 [n_clips, num_class] in the same memkind.  Raw scores (before softmax). */
+ * logits: float32 [n_clips, num_class] in the same memkind.  Raw scores (before softmax).
+ *         An identity engine (tsm_set_consensus(e, 1)) writes n_clips * num_segments * num_class floats, ordered
+ *         [clip][segment][class]: the caller's buffer must hold that many. */
 int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips,
                 float *logits, void *stream);
 
@@ -330,6 +343,12 @@ int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, 
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits,
              int32_t n_clips, int32_t n_segment, int32_t hw, int32_t c, int32_t num_class,
              void *stream);
+
+/* The per-segment head: feat [n_frames, hw, c] NHWC fp32 -> logits [n_frames, num_class] = fc(mean_hw feat[f]) + fc_b, one
+ * launch, no scratch (the consensus_type='identity' head; a frame's pooled value is tsm_head's to the bit).
+ * c % 8 == 0 and c <= 2048, else TSM_ERR_UNSUPPORTED.  Enqueues on `stream`; no synchronisation. */
+int tsm_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int32_t n_frames,
+                      int32_t hw, int32_t c, int32_t num_class, void *stream);
 
 /* Scores -> states on the GPU (device pointers), the post-step of the hot path:
  *   logits [n_clips, num_class] fp32 -> states [n_clips] int32: (softmax != 0: fp32 softmax over the classes,) the FIRST

@@ -41,9 +41,9 @@ class TsmConvArgs(C.Structure):
                 + [(n, C.c_int32) for n in ('cin2', 'hi2', 'wi2', 'stride2', 'code', 'reverse')])
 
 
-EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_tensor', 'tsm_finalize',
+EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_consensus', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
-           'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
+           'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_head_segments', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
 
 _lib: Optional[C.CDLL] = None
 
@@ -86,6 +86,8 @@ def load() -> C.CDLL:
     lib.tsm_set_bottleneck_width.argtypes = [vp, i32]
     lib.tsm_set_shift_place.restype = C.c_int
     lib.tsm_set_shift_place.argtypes = [vp, i32]
+    lib.tsm_set_consensus.restype = C.c_int
+    lib.tsm_set_consensus.argtypes = [vp, i32]
     lib.tsm_set_tensor.restype = C.c_int
     lib.tsm_set_tensor.argtypes = [vp, C.c_char_p, fp, C.POINTER(i64), i32]
     lib.tsm_finalize.restype = C.c_int
@@ -118,6 +120,8 @@ def load() -> C.CDLL:
     lib.tsm_gather_clips.argtypes = [vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp]
     lib.tsm_head.restype = C.c_int
     lib.tsm_head.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
+    lib.tsm_head_segments.restype = C.c_int
+    lib.tsm_head_segments.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.tsm_scores_to_states.restype = C.c_int
     lib.tsm_scores_to_states.argtypes = [fp, i32, i32, i32, C.c_float, vp, fp, vp]
     if lib.tsm_abi_version() != ABI_VERSION:

@@ -146,6 +146,7 @@ struct tsm_engine {
   int depth = 50;             // tsm_set_backbone
   int width = 64;             // tsm_set_bottleneck_width: torchvision's width_per_group
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
+  int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
   bool weights_started = false;   // a tsm_set_tensor call has been made: the backbone is fixed
   size_t tune_sig_base = 0;   // length of tune_sig before the backbone / placement suffix
@@ -955,6 +956,10 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     w = (w + 2 - 3) / e->blocks[k].stride + 1;
   }
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
+  if (e->consensus == 1) {   // per-segment logits: one launch, d_pooled is not written (the head's one timing slot either way)
+    TSM_LAUNCH(e, s, tsm::launch_head_segments(cur, e->d_fcw, e->d_fcb, d_logits, n, h * w, e->feat, cfg.num_class, prec, s));
+    return TSM_OK;
+  }
   TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T, h * w, e->feat,
                                     cfg.num_class, prec, s));
   return TSM_OK;
@@ -1163,6 +1168,15 @@ int tsm_set_shift_place(tsm_engine *e, int32_t place) {
   return TSM_OK;
 }
 
+int tsm_set_consensus(tsm_engine *e, int32_t consensus) {
+  if (!e) return TSM_ERR_INVALID_ARG;
+  if (e->weights_started || e->finalized)
+    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_consensus must come before the first tsm_set_tensor");
+  if (consensus != 0 && consensus != 1) return fail(e, TSM_ERR_UNSUPPORTED, "consensus must be 0 (avg) or 1 (identity)");
+  e->consensus = consensus;   // (the head is not tuned: the tune signature does not carry it)
+  return TSM_OK;
+}
+
 void tsm_destroy(tsm_engine *e) {
   if (!e) return;
   (void)hipSetDevice(e->cfg.device_id);
@@ -1324,7 +1338,9 @@ int tsm_finalize(tsm_engine *e) {
   if (rc) return rc;
   rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat);
   if (rc) return rc;
-  rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * cfg.num_class, "d_logits", (size_t)cfg.num_class);
+  // avg: one row per clip; identity: one per (clip, segment)
+  rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
+                 (size_t)cfg.num_class);
   if (rc) return rc;
   if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
     e->partial_elems = (size_t)16 << 20;
@@ -1370,8 +1386,8 @@ int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layou
   TSM_HIP(e, hipEventRecord(e->ev1, s));
   e->have_time = true;
   if (memkind == TSM_MEM_HOST) {
-    TSM_HIP(e, hipMemcpyAsync(logits, e->d_logits, (size_t)n_clips * e->cfg.num_class * sizeof(float),
-                              hipMemcpyDeviceToHost, s));
+    const size_t rows = (size_t)n_clips * (e->consensus == 1 ? e->cfg.num_segments : 1);
+    TSM_HIP(e, hipMemcpyAsync(logits, e->d_logits, rows * e->cfg.num_class * sizeof(float), hipMemcpyDeviceToHost, s));
     TSM_HIP(e, hipStreamSynchronize(s));
   }
   return e->poison ? verify_guards(e, s) : TSM_OK;
@@ -1793,6 +1809,17 @@ int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *log
   (void)hipFree(pooled);
   if (st != hipSuccess || st2 != hipSuccess)
     return fail(nullptr, TSM_ERR_HIP, std::string("head: ") + hipGetErrorString(st != hipSuccess ? st : st2));
+  return TSM_OK;
+}
+
+int tsm_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int32_t n_frames, int32_t hw,
+                      int32_t c, int32_t num_class, void *stream) {
+  if (!feat || !fc_w || !fc_b || !logits || n_frames <= 0 || hw <= 0 || c <= 0 || num_class <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "head_segments: NULL pointer or non-positive size");
+  if (c % 8 != 0 || c > 2048) return fail(nullptr, TSM_ERR_UNSUPPORTED, "head_segments: c must be a multiple of 8, at most 2048");
+  hipError_t st = tsm::launch_head_segments(feat, fc_w, fc_b, logits, n_frames, hw, c, num_class, tsm::kPrecF32,
+                                            static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("head_segments: ") + hipGetErrorString(st));
   return TSM_OK;
 }
 

@@ -217,6 +217,9 @@ hipError_t launch_temporal_shift(const float *x, float *y, int64_t n_frames, int
 hipError_t launch_head(const float *feat, const float *fc_w, const float *fc_b, float *pooled,
                        float *logits, int n_clips, int n_segment, int hw, int c, int num_class, int prec,
                        hipStream_t s);
+// per-segment head: logits [n_frames, num_class], one launch, no scratch (c % 8 == 0, c <= 2048)
+hipError_t launch_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int n_frames,
+                                int hw, int c, int num_class, int prec, hipStream_t s);
 
 // K9: per clip, (softmax,) first arg-max, class id if its score >= threshold else -1; top (nullable) = that score.
 hipError_t launch_scores_to_states(const float *logits, int n, int c, int softmax, float threshold, int *states, float *top,

@@ -449,6 +449,61 @@ hipError_t launch_head(const float *feat, const float *fc_w, const float *fc_b, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-segment head (consensus_type='identity', tsm.py:165-174): logits[f] = fc( mean_hw feat[f,hw,:] ) + bias for every
+// FRAME, no mean over the segments -- so nothing crosses a frame and the whole head is ONE launch, one 256-thread workgroup
+// per frame, and `pooled` never goes to memory:
+//   phase 1: head_pool_kernel's loop (same row order, same division: the pooled value of a frame is the avg head's to the
+//            bit), one channel group per thread and pass, into LDS as fp32 (c <= 2048: 8 KB);
+//   phase 2: the four waves take the classes round robin; the lanes stride the channels with 16-byte LDS reads and fc_w
+//            loads (head_fc_kernel's k order and pairing), a wave reduction, lane 0 stores.
+// ---------------------------------------------------------------------------------------------
+constexpr int kHeadSegMaxC = 2048;
+
+template <int FMT>
+__global__ void __launch_bounds__(256) head_seg_kernel(const float *__restrict__ feat, const float *__restrict__ fc_w,
+                                                       const float *__restrict__ fc_b, float *__restrict__ logits,
+                                                       int rows, int c, int num_class) {
+  constexpr int GF = Fmt<FMT>::gf, GC = Fmt<FMT>::ch;
+  __shared__ __attribute__((aligned(16))) float pooled[kHeadSegMaxC];
+  const int b = blockIdx.x;
+  const int cg = c / GC;
+  for (int t = threadIdx.x; t < cg; t += 256) {
+    const float *src = feat + ((size_t)b * rows * cg + t) * GF;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 7
+    for (int r = 0; r < rows; ++r) {
+      float v[8];
+      load_group<FMT>(src + (size_t)r * cg * GF, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < GC; ++e) pooled[t * GC + e] = acc[e] / (float)rows;
+  }
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int cls = wave; cls < num_class; cls += 4) {
+    const float *wv = fc_w + (size_t)cls * c;
+    float s = 0.f;
+    for (int k = lane * 4; k < c; k += 256) {
+      const f32x4 f = *reinterpret_cast<const f32x4 *>(pooled + k);
+      const f32x4 w = *reinterpret_cast<const f32x4 *>(wv + k);
+      s += (f[0] * w[0] + f[1] * w[1]) + (f[2] * w[2] + f[3] * w[3]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if (lane == 0) logits[(size_t)b * num_class + cls] = s + fc_b[cls];
+  }
+}
+
+hipError_t launch_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int n_frames,
+                                int hw, int c, int num_class, int prec, hipStream_t s) {
+  if (n_frames <= 0 || hw <= 0 || num_class <= 0 || c <= 0 || c % 8 != 0 || c > kHeadSegMaxC) return hipErrorInvalidValue;
+  TSM_DISPATCH_FMT(prec, head_seg_kernel, n_frames, s, feat, fc_w, fc_b, logits, hw, c, num_class);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // K9: logits -> per-clip state on the GPU (utils/eval.py:153-164 + to_softmax, utils/visualize.py:140-150):
 // optional fp32 softmax over the classes, FIRST maximum, class id if its score >= threshold else -1.  One thread per
 // clip (n_clips x num_class is tiny; the point is that a streaming step copies 8 bytes per window to the host instead

@@ -72,6 +72,9 @@ def gather_clip_logits(local: torch.Tensor, n_total: int, group=None) -> torch.T
     """Ragged form: rank r holds the logits of its ``shard_range`` block (possibly fewer than
     ``per_rank`` rows, possibly none).  Pads to ``per_rank`` rows, all-gathers once, trims to
     ``n_total`` rows in global clip order."""
+    if local.dim() == 3:     # [clips, T, num_class]: what an engine built with consensus_type='identity' returns
+        raise ValueError(f'gather_clip_logits takes one row per clip, [clips, num_class], got {tuple(local.shape)}: per-segment '
+                         "logits of a consensus_type='identity' engine are not sharded by clip rows")
     rank, world = world_info()
     if not collective_enabled():
         return local[:n_total]

@@ -25,6 +25,8 @@ from . import _lib
 from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
                       remap_mmaction_keys)
 
+CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
+
 
 @dataclass
 class NodeArg:
@@ -45,11 +47,13 @@ class TsmEngine:
     def __init__(self, num_class: int = 12, num_segments: int = 8, height: int = 224, width: int = 224,
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
-                 base_model: str = 'resnet50', shift_place: str = 'blockres'):
+                 base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg'):
         if base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
         if shift_place not in SHIFT_PLACES:
             raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
+        if consensus_type not in CONSENSUS_TYPES:
+            raise ValueError(f"consensus_type must be one of {list(CONSENSUS_TYPES)}, got {consensus_type!r}")
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.num_class, self.num_segments = int(num_class), int(num_segments)
@@ -60,6 +64,7 @@ class TsmEngine:
         self.dtype = dtype
         self.base_model = base_model
         self.shift_place = shift_place
+        self.consensus_type = consensus_type
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
                               'bf16': _lib.LAYOUT_NTHWC8B}[dtype]
@@ -72,6 +77,8 @@ class TsmEngine:
             _lib.check(self._lib.tsm_set_bottleneck_width(self._h, WIDTHS[base_model]), self._h)
         if shift_place != 'blockres':
             _lib.check(self._lib.tsm_set_shift_place(self._h, SHIFT_PLACES[shift_place]), self._h)
+        if consensus_type != 'avg':
+            _lib.check(self._lib.tsm_set_consensus(self._h, CONSENSUS_TYPES[consensus_type]), self._h)
         self._finalized = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -99,7 +106,12 @@ class TsmEngine:
         return [NodeArg(self.INPUT_NAME, [None, self.num_segments, 3, self.height, self.width])]
 
     def get_outputs(self) -> List[NodeArg]:
-        return [NodeArg(self.OUTPUT_NAME, [None, self.num_class])]
+        return [NodeArg(self.OUTPUT_NAME, [None] + list(self._out_shape(0)[1:]))]
+
+    def _out_shape(self, b: int) -> tuple:
+        """Logits of ``b`` clips: [b, num_class] ('avg'), [b, T, num_class] ('identity': the fc output of every segment,
+        tsm.py:165-174).  Dimension 0 is the clip axis either way, so a ``max_clips`` chunk is a contiguous slice."""
+        return (b, self.num_segments, self.num_class) if self.consensus_type == 'identity' else (b, self.num_class)
 
     def run(self, output_names: Optional[Sequence[str]], input_feed: Dict[str, np.ndarray]) -> List[np.ndarray]:
         if output_names is not None and list(output_names) != [self.OUTPUT_NAME]:
@@ -115,7 +127,7 @@ class TsmEngine:
     # ---- nn.Module duck type ----------------------------------------------------------------------
     def __call__(self, x):
         """x: [B*T,3,H,W] (or [B,T,3,H,W]) torch tensor (cpu or on this engine's GPU) or ndarray;
-        returns logits [B,num_class] of the same kind."""
+        returns logits [B,num_class] ([B,T,num_class] with consensus_type='identity') of the same kind."""
         is_torch = hasattr(x, 'is_cuda')
         shape = tuple(x.shape)
         if len(shape) == 4:
@@ -162,7 +174,7 @@ class TsmEngine:
         clips = _as_f32(clips)
         b = clips.shape[0]
         self._check_clips(clips.size, b, layout)
-        out = np.empty((b, self.num_class), dtype=np.float32)
+        out = np.empty(self._out_shape(b), dtype=np.float32)
         for s in range(0, b, self.max_clips):
             chunk = np.ascontiguousarray(clips[s:s + self.max_clips])
             o = out[s:s + chunk.shape[0]]
@@ -172,7 +184,10 @@ class TsmEngine:
 
     def forward_device(self, clips, out=None, layout: int = _lib.LAYOUT_NTCHW):
         """clips: contiguous float32 CUDA tensor [B,T,3,H,W] on this engine's device.  Enqueues on
-        torch's current stream and returns a CUDA tensor [B,num_class] (no host sync)."""
+        torch's current stream and returns a CUDA tensor [B,num_class] ([B,T,num_class] with consensus_type='identity';
+        no host sync).  An engine takes ONE in-flight call: a host forward (``run`` / ``forward_host`` / ``forward_tap``) runs on the
+        engine's own non-blocking stream over the same workspace, so synchronise (``torch.cuda.synchronize()`` or the stream) after
+        a device forward before the next host call on this engine."""
         import torch
         self._need_finalized()
         if not (clips.is_cuda and clips.dtype == torch.float32):
@@ -183,10 +198,10 @@ class TsmEngine:
         b = clips.shape[0]
         self._check_clips(clips.numel(), b, layout)
         if out is None:
-            out = torch.empty((b, self.num_class), dtype=torch.float32, device=clips.device)
+            out = torch.empty(self._out_shape(b), dtype=torch.float32, device=clips.device)
         elif not (out.is_cuda and out.device == clips.device and out.dtype == torch.float32 and out.is_contiguous()
-                  and tuple(out.shape) == (b, self.num_class)):
-            raise ValueError(f'out must be a contiguous float32 [{b},{self.num_class}] tensor on {clips.device}')
+                  and tuple(out.shape) == self._out_shape(b)):
+            raise ValueError(f'out must be a contiguous float32 {list(self._out_shape(b))} tensor on {clips.device}')
         stream = torch.cuda.current_stream(clips.device).cuda_stream
         for s in range(0, b, self.max_clips):
             n = min(self.max_clips, b - s)
@@ -320,10 +335,14 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     ``shift_place``: 'blockres' (the shift wraps conv1 of every block) or 'block' (it wraps every block whole: the identity
     and the downsample read the shifted input too; state-dict keys ``base_model.layerL.B.net.*``); anything else raises
     as the reference's assert does.  ``is_shift=False`` ignores it.
+    ``consensus_type``: 'avg' (logits [B, num_class], the mean of the segments' fc outputs) or 'identity' (the fc output of
+    every segment, [B, T, num_class]: one launch, head_seg_kernel); anything else fails the reference's assert
+    (tsm.py:438).  It is the caller's argument for every kind of checkpoint: an ``.onnx`` file is read for its weights only,
+    the consensus is not detected from its graph.
     """
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
-    assert consensus_type in ('avg',), 'the engine implements the avg consensus'
+    assert consensus_type in ['avg', 'identity']
     if shift_place not in SHIFT_PLACES:
         raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
     if non_local:
@@ -348,7 +367,7 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model, shift_place=shift_place)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width,
                      shift_div=shift_div, is_shift=is_shift, max_clips=max_clips, device=dev, state_dict=sd,
-                     dtype=dtype, base_model=base_model, shift_place=shift_place)
+                     dtype=dtype, base_model=base_model, shift_place=shift_place, consensus_type=consensus_type)
 
 
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------
@@ -579,4 +598,19 @@ def head_nhwc(feat, fc_w, fc_b, n_segment: int, out=None):
     out = _out(out, (b, fc_w.shape[0]), torch.float32, feat)
     _lib.check(_lib.load().tsm_head(feat.data_ptr(), fc_w.contiguous().data_ptr(), fc_b.contiguous().data_ptr(),
                                     out.data_ptr(), b, n_segment, h * w, c, fc_w.shape[0], _stream(feat)))
+    return out
+
+
+def head_segments_nhwc(feat, fc_w, fc_b, out=None):
+    """The per-segment head (``tsm_head_segments``): feat CUDA float32 [n_frames, H, W, C] (NHWC) -> logits
+    [n_frames, num_class], fc of every frame's average-pooled features (consensus_type='identity': no mean over the segments)."""
+    import torch
+    _need_cuda_f32(feat=feat, fc_w=fc_w, fc_b=fc_b)
+    feat = feat.contiguous()
+    n, h, w, c = feat.shape
+    if n <= 0 or h * w <= 0 or tuple(fc_w.shape)[1:] != (c,) or tuple(fc_b.shape) != (fc_w.shape[0],):
+        raise ValueError(f'feat {tuple(feat.shape)}, fc_w {tuple(fc_w.shape)}, fc_b {tuple(fc_b.shape)} do not fit')
+    out = _out(out, (n, fc_w.shape[0]), torch.float32, feat)
+    _lib.check(_lib.load().tsm_head_segments(feat.data_ptr(), fc_w.contiguous().data_ptr(), fc_b.contiguous().data_ptr(),
+                                             out.data_ptr(), n, h * w, c, fc_w.shape[0], _stream(feat)))
     return out

@@ -94,6 +94,16 @@ def make_clip(video_thwc_u8: torch.Tensor, start: int) -> torch.Tensor:
     return clip
 
 
+def need_clip_rows(model, where: str) -> None:
+    """The pipelines here take ONE row of scores per clip: refuse a model that returns one per segment up front (an engine
+    built with consensus_type='identity', logits [B, T, num_class]) instead of failing later on a shape.  Sessions and
+    stubs without the attribute are 'avg'."""
+    consensus = getattr(model, 'consensus_type', 'avg')
+    if consensus != 'avg':
+        raise ValueError(f"{where} needs one row of scores per clip: the model was built with consensus_type={consensus!r} "
+                         "(per-segment logits [B, T, num_class]); build it with consensus_type='avg'")
+
+
 # ---- single clip, reference signature ------------------------------------------------------------------
 def inference_video(model, inputs: Union[torch.Tensor, np.ndarray], threshold: float = 0.5,
                     transform: Optional[Callable] = None) -> List[Tuple[int, float]]:
@@ -101,6 +111,7 @@ def inference_video(model, inputs: Union[torch.Tensor, np.ndarray], threshold: f
 
     inputs: Tensor [8,H,W,3] (decoder layout; permuted to [8,3,H,W] here) or ndarray already [8,3,H,W].
     ``threshold`` is accepted and unused, as in the reference (:248,:258)."""
+    need_clip_rows(model, 'inference_video')
     if not isinstance(inputs, torch.Tensor):
         x = torch.from_numpy(np.asarray(inputs)).float()
     else:
@@ -806,6 +817,7 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     clips of every video over the ranks (one all-gather per video: lowest latency for ONE stream, but every rank reads
     every video); ``shard='videos'`` is the round-2 form, whole videos round-robin with an exchange per round of W
     videos (each round lasts as long as its longest video).  All three write identical files."""
+    need_clip_rows(model, 'inference_dataset')
     rank, _world = tdist.world_info()
     if shard is None:
         shard = 'global'
@@ -853,6 +865,7 @@ def count_by_video_model(model, frames: Iterable[Union[np.ndarray, torch.Tensor]
     """Online counting over a frame source (HWC uint8, RGB): every 8 queued frames form one window
     (non-overlapping, stride 8), the window's state is pushed into an incremental counter.
     ``on_window(window_index, state, count)`` is called after each window."""
+    need_clip_rows(model, 'count_by_video_model')
     transform = transform or build_test_transform(False)
     queue: Deque[torch.Tensor] = deque(maxlen=NUM_SEGMENTS)
     counter = RepCounter(step)

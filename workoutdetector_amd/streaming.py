@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .counting import RepCounter, scores_to_preds
-from .inference_count import NUM_SEGMENTS, _engine_device
+from .inference_count import NUM_SEGMENTS, _engine_device, need_clip_rows
 from .transform import TestTransform, build_test_transform
 
 
@@ -48,6 +48,7 @@ class StreamBatcher:
                  transform: Optional[TestTransform] = None,
                  on_window: Optional[Callable[[Hashable, int, int, int], None]] = None,
                  max_pinned_bytes: int = 1 << 30, max_free_per_shape: int = 64):
+        need_clip_rows(model, 'StreamBatcher')
         self.model = model
         self.threshold, self.softmax, self.step_frames = threshold, softmax, step
         self.max_batch = max_batch

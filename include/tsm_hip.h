@@ -25,6 +25,8 @@
  *   tsm_set_consensus      create_model(consensus_type='avg' | 'identity')   workoutdetector/models/tsm.py:438,165-174
  *   tsm_head_segments      avgpool -> fc -> view(-1,T,cls), SegmentConsensus('identity'): no mean   tsm.py:411-419,165-174
  *   tsm_gather_clips       the loop's clip windows: video[i:i + 16:2] for i in range(0, len(video), 8), zero-padded tail
+ *   tsm_preprocess_clips   build_test_transform(person_crop=True) from the detector's box on: PersonCrop -> Resize((224, 224))
+ *                          -> Normalize, fused with the clip windows   datasets/build.py:123-129, datasets/transform.py:247-259
  *   tsm_scores_to_states   per clip: to_softmax, first arg-max, score >= 0.5 ? class : -1
  *                          workoutdetector/utils/eval.py:153-164, utils/visualize.py:140-150
  *
@@ -57,7 +59,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments (added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips (both added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -338,6 +340,33 @@ int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int3
 int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, int64_t first_frame, int64_t total_frames,
                      int64_t pad_frame, int64_t first_clip, int32_t n_clips, int32_t n_segment, int32_t clip_step,
                      int32_t clip_stride, void *out, void *stream);
+
+/* The person-crop test transform fused with the clip iterator (device pointers), straight from staged RAW frames to the
+ * input of tsm_forward in ONE launch; the transformed frames are never written:
+ *   build_test_transform(person_crop=True) = ConvertImageDtype -> PersonCrop -> Resize((224, 224)) -> Normalize(ImageNet)
+ *   datasets/build.py:123-129, datasets/transform.py:226-259 -- from the detector's box on; the Faster-RCNN detector is not
+ *   part of this library, the boxes are the caller's.
+ * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255), tsm_gather_clips' convention: buffer frame j =
+ *         source frame clip_stride * (first_frame + j).
+ * boxes:  DEVICE int32 [n_clips, 4] = (top, left, bh, bw) in source-frame pixels, row c for clip first_clip + c.
+ * out:    [n_clips, n_segment, ...one frame] in out_layout, as tsm_preprocess with `size` in place of `crop`.
+ *   out[c][k] = source frame s = clip_step * (first_clip + c) + clip_stride * k, cropped to box c, resized to size x size
+ *   (bilinear, align_corners=False, no antialias, aspect ratio not kept), then (v [/ 255] - mean) / std.  Three rules:
+ *   - zero fill: where the box leaves the frame the crop reads 0 (torchvision's tensor crop pads BEFORE Normalize), so a
+ *     pixel wholly outside is (0 - mean) / std;
+ *   - no person: bh <= 0 or bw <= 0 stands for the whole frame (0, 0, h, w) (transform.py:254, `if w * h == 0: return images`);
+ *   - padded tail: s >= total_frames is the reference's zero frame, every channel (0 - mean) / std; nothing is read for
+ *     it and the buffer holds no pad frame.
+ * Validated on the host before the launch (TSM_ERR_INVALID_ARG, nothing launched), by tsm_gather_clips' rules: non-NULL
+ * pointers, positive sizes, pixel type and layout, clip_step % clip_stride == 0, each clip starts inside the video, every
+ * source frame < total_frames the range reads lies in [first_frame, first_frame + n_frames).  The BOXES cannot be validated
+ * (device memory): the kernel is total in them -- for any int32 contents it reads only inside `frames` (coordinate sums in
+ * 64 bits, a tap is read only where it lies in the frame) and writes exactly `out`.  n_clips is not limited by the launch
+ * geometry.  Enqueues on `stream`; no synchronisation. */
+int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, int64_t first_frame,
+                         int64_t total_frames, int64_t first_clip, int32_t n_clips, int32_t n_segment, int32_t clip_step,
+                         int32_t clip_stride, const int32_t *boxes, float *out, int32_t out_layout, int32_t size,
+                         int32_t scale_255, void *stream);
 
 /* feat [n_clips*T, hw, c] NHWC -> logits [n_clips, num_class]; fc_w [num_class, c], fc_b. */
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits,

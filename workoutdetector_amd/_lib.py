@@ -43,7 +43,7 @@ class TsmConvArgs(C.Structure):
 
 EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_consensus', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
-           'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_head_segments', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_scores_to_states')
+           'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_head_segments', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_preprocess_clips', 'tsm_scores_to_states')
 
 _lib: Optional[C.CDLL] = None
 
@@ -118,6 +118,8 @@ def load() -> C.CDLL:
     lib.tsm_tune.argtypes = [vp, i32, vp]
     lib.tsm_gather_clips.restype = C.c_int
     lib.tsm_gather_clips.argtypes = [vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp]
+    lib.tsm_preprocess_clips.restype = C.c_int
+    lib.tsm_preprocess_clips.argtypes = [vp, i32, i64, i32, i32, i64, i64, i64, i32, i32, i32, i32, vp, fp, i32, i32, i32, vp]
     lib.tsm_head.restype = C.c_int
     lib.tsm_head.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     lib.tsm_head_segments.restype = C.c_int

@@ -1796,6 +1796,35 @@ int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, 
   return TSM_OK;
 }
 
+int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, int64_t first_frame,
+                         int64_t total_frames, int64_t first_clip, int32_t n_clips, int32_t n_segment, int32_t clip_step,
+                         int32_t clip_stride, const int32_t *boxes, float *out, int32_t out_layout, int32_t size,
+                         int32_t scale_255, void *stream) {
+  if (!frames || !boxes || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: null pointer");
+  if (n_frames <= 0 || h <= 0 || w <= 0 || size <= 0 || n_clips <= 0 || n_segment <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: non-positive size");
+  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
+      out_layout != TSM_LAYOUT_NTHWC8B)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  tsm::ClipPreprocParams p{};
+  p.src = frames; p.dst = out; p.boxes = boxes; p.n_frames = n_frames; p.first_frame = first_frame;
+  p.total_frames = total_frames; p.first_clip = first_clip; p.n_clips = n_clips; p.n_segment = n_segment;
+  p.clip_step = clip_step; p.clip_stride = clip_stride; p.h = h; p.w = w; p.size = size;
+  p.src_is_u8 = pixel == TSM_PIXEL_U8;
+  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
+               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
+  p.pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  hipError_t st = tsm::launch_preprocess_clips(p, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess)
+    return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
+                st == hipErrorInvalidValue ? std::string("preprocess_clips: clip_step is not a multiple of clip_stride, a clip "
+                                                         "starts past the end of the video, or a clip of the range reads "
+                                                         "outside the frame buffer")
+                                           : std::string("preprocess_clips: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits, int32_t n_clips,
              int32_t n_segment, int32_t hw, int32_t c, int32_t num_class, void *stream) {
   if (!feat || !fc_w || !fc_b || !logits || n_clips <= 0 || n_segment <= 0 || hw <= 0 || c <= 0 || num_class <= 0)

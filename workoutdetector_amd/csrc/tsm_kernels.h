@@ -209,6 +209,23 @@ struct GatherParams {
 };
 hipError_t launch_gather_clips(const GatherParams &p, hipStream_t s);
 
+// Person-crop test transform fused with the clip iterator (see preprocess_clips_kernel): staged raw frames [n_frames,h,w,3]
+// u8|f32 (buffer frame j = source frame clip_stride * (first_frame + j), as GatherParams) + one box per clip -> out
+// [n_clips, n_segment, ...one frame of `size`] in any out_mode of PreprocParams.  The launcher validates every FRAME index on
+// the host (hipErrorInvalidValue, nothing launched); the kernel is total in the BOX contents, which live in device memory.
+struct ClipPreprocParams {
+  const void *src;
+  float *dst;
+  const int *boxes;   // device, [n_clips, 4] = (top, left, bh, bw) in source-frame pixels; bh <= 0 or bw <= 0: the whole frame
+  int64_t n_frames, first_frame, total_frames, first_clip;
+  int n_clips, n_segment, clip_step, clip_stride;
+  int h, w, size;
+  int src_is_u8;
+  int out_mode;       // as PreprocParams
+  float pre_scale;
+};
+hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s);
+
 hipError_t launch_maxpool3x3s2(const float *x, float *y, int n, int hi, int wi, int c, int prec,
                                hipStream_t s);
 hipError_t launch_temporal_shift(const float *x, float *y, int64_t n_frames, int n_segment,

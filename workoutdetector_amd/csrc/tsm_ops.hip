@@ -297,6 +297,129 @@ hipError_t launch_gather_clips(const GatherParams &p_in, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// preprocess_clips: the person-crop test transform (datasets/build.py:123-129 of the reference: PersonCrop ->
+// Resize((size, size)) -> Normalize, from the detector's box on) fused with the clip iterator above, one launch from the
+// staged RAW frames to the engine's packed input: out[c][k] = source frame clip_step * (first_clip + c) + clip_stride * k,
+// cropped to clip c's box (top, left, bh, bw), resized to size x size, normalised.  The transform sits BEHIND the gather
+// because the box is per clip: an even frame shared by two overlapping windows is cropped twice, with two boxes.
+//   * zero fill: a tap of the box outside the frame has the value 0 and is not read (torchvision's tensor crop pads with
+//     zeros BEFORE Normalize: a pixel wholly outside becomes (0 - mean) / std);
+//   * no person: bh <= 0 or bw <= 0 stands for the whole frame (0, 0, h, w) (transform.py:254 `if w * h == 0: return images`);
+//   * padded tail: a source index >= total_frames is the reference's zero frame: every channel (0 - mean) / std, nothing is
+//     read and the buffer needs no pad frame.
+// Bilinear sampling is preprocess_pixel's (ATen UpSampleBilinear2d, no antialias) in box coordinates.
+// TOTAL in the boxes: they live in device memory, so no host check can see them; for ANY int32 contents the kernel reads only
+// inside the frames it was given -- the box index is clamped to the box, the sum with top / left is formed in 64 bits and a
+// tap is read only where 0 <= y < h and 0 <= x < w.  (The frame index is the host's to validate: launch_preprocess_clips.)
+// One thread per output group as in preprocess_kernel; neighbouring threads are neighbouring ox: contiguous 16-byte stores.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ void clip_pixel(const ClipPreprocParams &p, const T *frame, int64_t top, int64_t left, int bh, int bw,
+                                           int oy, int ox, float *v) {
+  const float sh = (float)bh / (float)p.size, sw = (float)bw / (float)p.size;
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  float fy = sh * ((float)oy + 0.5f) - 0.5f;
+  float fx = sw * ((float)ox + 0.5f) - 0.5f;
+  fy = fy < 0.f ? 0.f : fy;
+  fx = fx < 0.f ? 0.f : fx;
+  // (int) of a float at or above 2^31 is undefined: sides near INT32_MAX are held below it, and the index inside the box
+  const float big = 2147483520.f;
+  int y0 = (int)(fy < big ? fy : big), x0 = (int)(fx < big ? fx : big);
+  y0 = y0 < bh - 1 ? y0 : bh - 1;
+  x0 = x0 < bw - 1 ? x0 : bw - 1;
+  const int y1 = y0 + (y0 < bh - 1 ? 1 : 0), x1 = x0 + (x0 < bw - 1 ? 1 : 0);
+  const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
+  // image coordinates of the four taps, in 64 bits (top + y0 leaves int32 for a hostile box); a tap outside the frame is 0
+  const int64_t iy0 = top + y0, iy1 = top + y1, ix0 = left + x0, ix1 = left + x1;
+  const bool vy0 = iy0 >= 0 && iy0 < p.h, vy1 = iy1 >= 0 && iy1 < p.h;
+  const bool vx0 = ix0 >= 0 && ix0 < p.w, vx1 = ix1 >= 0 && ix1 < p.w;
+  // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
+  const T *r0 = frame + (vy0 ? iy0 : 0) * p.w * 3, *r1 = frame + (vy1 ? iy1 : 0) * p.w * 3;
+  const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
+  const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float p00 = vy0 && vx0 ? (float)a00[c] : 0.f, p01 = vy0 && vx1 ? (float)a01[c] : 0.f;
+    const float p10 = vy1 && vx0 ? (float)a10[c] : 0.f, p11 = vy1 && vx1 ? (float)a11[c] : 0.f;
+    const float t = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11);
+    v[c] = (t * p.pre_scale - mean[c]) / stdv[c];
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) preprocess_clips_kernel(const ClipPreprocParams p) {
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int wg = (p.size + px - 1) / px;
+  const int64_t per_frame = (int64_t)wg * p.size;
+  const int64_t total = (int64_t)p.n_clips * p.n_segment * per_frame;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const T *src = static_cast<const T *>(p.src);
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int gx = (int)(i % wg);
+    const int oy = (int)((i / wg) % p.size);
+    const int64_t f = i / per_frame;             // (clip, segment) row of the output
+    const int64_t c = f / p.n_segment;
+    const int k = (int)(f - c * p.n_segment);
+    const int64_t s = (int64_t)p.clip_step * (p.first_clip + c) + (int64_t)p.clip_stride * k;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (s < p.total_frames) {
+      // the clip's box: four dwords, the same for every thread of (nearly every) wave
+      const int *b = p.boxes + c * 4;
+      int64_t top = b[0], left = b[1];
+      int bh = b[2], bw = b[3];
+      if (bh <= 0 || bw <= 0) {
+        top = 0; left = 0; bh = p.h; bw = p.w;
+      }
+      const T *frame = src + (s / p.clip_stride - p.first_frame) * (int64_t)p.h * p.w * 3;
+      clip_pixel<T>(p, frame, top, left, bh, bw, oy, gx * px, v);
+      if (px == 2 && gx * 2 + 1 < p.size) clip_pixel<T>(p, frame, top, left, bh, bw, oy, gx * 2 + 1, v + 4);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        v[ch] = (0.f - mean[ch]) / stdv[ch];
+        if (px == 2 && gx * 2 + 1 < p.size) v[4 + ch] = v[ch];
+      }
+    }
+    if (p.out_mode == 1) {
+      float *o = p.dst + f * 3 * (int64_t)p.size * p.size + (int64_t)oy * p.size + gx;
+      o[0] = v[0];
+      o[(int64_t)p.size * p.size] = v[1];
+      o[2 * (int64_t)p.size * p.size] = v[2];
+    } else if (p.out_mode == 2) {
+      store_group<kPrecBf16x3>(p.dst + i * 8, v);
+    } else if (p.out_mode == 3) {
+      store_group<kPrecBf16>(p.dst + i * 4, v);
+    } else {
+      store_group<kPrecF32>(p.dst + i * 4, v);
+    }
+  }
+}
+
+hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
+  if (!p.src || !p.dst || !p.boxes || p.n_frames <= 0 || p.h <= 0 || p.w <= 0 || p.size <= 0 || p.n_clips <= 0 ||
+      p.n_segment <= 0 || p.clip_step <= 0 || p.clip_stride <= 0 || p.clip_step % p.clip_stride != 0 || p.first_clip < 0 ||
+      p.first_frame < 0 || p.total_frames <= 0 || p.first_clip >= p.total_frames || p.out_mode < 0 || p.out_mode > 3)
+    return hipErrorInvalidValue;
+  // every frame index the kernel will form, checked here (launch_gather_clips' rules; there is no pad frame to check)
+  const int64_t lo = (int64_t)p.clip_step * p.first_clip;
+  const int64_t hi = (int64_t)p.clip_step * (p.first_clip + p.n_clips - 1) + (int64_t)p.clip_stride * (p.n_segment - 1);
+  if (lo >= p.total_frames) return hipErrorInvalidValue;                       // a clip starts inside its video
+  const int64_t last = (hi < p.total_frames ? hi : p.total_frames - 1) / p.clip_stride - p.first_frame;
+  const int64_t first = lo / p.clip_stride - p.first_frame;
+  if (first < 0 || last >= p.n_frames) return hipErrorInvalidValue;
+  // one grid-stride launch covers a range of any length (64-bit group index): nothing of the launch geometry limits n_clips
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int64_t total = (int64_t)p.n_clips * p.n_segment * p.size * ((p.size + px - 1) / px);
+  const unsigned grid = grid_for(total, 8192);
+  if (p.src_is_u8)
+    TSM_KLAUNCH(preprocess_clips_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, p);
+  else
+    TSM_KLAUNCH(preprocess_clips_kernel<float>, dim3(grid), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // maxpool 3x3 stride 2 pad 1, NHWC; one thread per (output pixel, channel group).
 // ---------------------------------------------------------------------------------------------
 template <int FMT>

@@ -558,6 +558,44 @@ def gather_clips(frames, first_frame: int, total_frames: int, first_clip: int, n
     return out
 
 
+def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_clip: int, n_clips: int, size: int = 224,
+                     scale_255: bool = False, layout: Optional[int] = None, packed: bool = True, n_segment: int = 8,
+                     clip_step: int = 8, clip_stride: int = 2, out=None):
+    """The person-crop test transform fused with the clip windows (``tsm_preprocess_clips``: PersonCrop -> Resize((size,
+    size)) -> Normalize of the reference's ``build_test_transform(person_crop=True)``, from the detector's box on), one
+    launch from staged raw frames to the engine's input.
+
+    frames: CUDA uint8 or float32 [n,H,W,3] (values 0..255) holding every ``clip_stride``-th frame of the video from source
+    frame ``clip_stride * first_frame`` on (``gather_clips``' convention; no pad frame is needed).  boxes: CUDA int32
+    [n_clips, 4] = (top, left, h, w) in source-frame pixels, row c for clip ``first_clip + c``; a box may leave the frame
+    (zero fill) and a non-positive h or w stands for the whole frame.  Returns float32 [n_clips, n_segment, ...one frame]
+    in the layouts of ``preprocess_frames`` with ``size`` in place of ``crop``; the zero-padded tail segments of the last
+    clips are (0 - mean) / std."""
+    import torch
+    if frames.dtype == torch.uint8:
+        pixel = _lib.PIXEL_U8
+    elif frames.dtype == torch.float32:
+        pixel = _lib.PIXEL_F32
+    else:
+        raise ValueError(f'frames must be uint8 or float32, got {frames.dtype}')
+    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError('frames must be a contiguous CUDA tensor [n,H,W,3]')
+    n, h, w, _ = frames.shape
+    if not (hasattr(boxes, 'is_cuda') and boxes.is_cuda and boxes.device == frames.device and boxes.dtype == torch.int32
+            and tuple(boxes.shape) == (n_clips, 4) and boxes.is_contiguous()):
+        raise ValueError(f'boxes must be a contiguous int32 tensor [{n_clips}, 4] = (top, left, h, w) on {frames.device}')
+    if layout is None:
+        layout = _lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW
+    pairs = (size + 1) // 2
+    frame = {_lib.LAYOUT_NTHWC4: (size, size, 4), _lib.LAYOUT_NTHWC8S: (size, pairs, 8), _lib.LAYOUT_NTHWC8B: (size, pairs, 4),
+             _lib.LAYOUT_NTCHW: (3, size, size)}[layout]
+    out = _out(out, (n_clips, n_segment) + frame, torch.float32, frames)
+    _lib.check(_lib.load().tsm_preprocess_clips(frames.data_ptr(), pixel, n, h, w, int(first_frame), int(total_frames),
+                                                int(first_clip), n_clips, n_segment, clip_step, clip_stride, boxes.data_ptr(),
+                                                out.data_ptr(), layout, size, int(scale_255), _stream(frames)))
+    return out
+
+
 def scores_to_states(logits, threshold: float = 0.5, softmax: bool = True, return_top: bool = False, out=None, out_top=None):
     """K9 on the GPU: CUDA float32 logits [n, num_class] -> int32 states [n] (utils/eval.py:153-164: softmax, first
     arg-max, class id if its score >= threshold else -1) and optionally the winning score.  Enqueues on torch's

@@ -15,6 +15,9 @@ What differs from the reference, on purpose:
     once per *frame* (each even frame belongs to two half-overlapping windows; the transform is
     per-frame, so this equals transforming per clip) and the windows are pushed through the engine in
     batches instead of one synchronous ``run`` per clip.
+  * ``person_crop=True`` takes the boxes from the caller (``boxes=``; the Faster-RCNN detector is out of scope): the box is
+    per clip, so the transform moves behind the clip windows -- one ``tsm_preprocess_clips`` launch per batch cuts,
+    crops, resizes, normalises and packs straight from the staged uint8 frames (``shard='clips'`` / ``'videos'``).
   * videos come from a pluggable ``video_reader`` (the image has no H.264 decoder): ``.npy`` files of
     uint8 [F,H,W,3] frames are read natively, anything else goes to ``torchvision.io.read_video`` when
     that is importable.
@@ -51,7 +54,7 @@ import torch
 from . import distributed as tdist
 from .counting import RepCounter, pred_to_count, scores_to_preds  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
-from .transform import TestTransform, build_test_transform
+from .transform import PersonCropTransform, TestTransform, build_test_transform
 
 NUM_SEGMENTS = 8
 CLIP_SPAN = 16
@@ -230,15 +233,20 @@ def stage_video(model, video_thwc_u8: torch.Tensor, clip_range: Optional[Tuple[i
     return StagedVideo(total, lo, hi, f_lo, hw, frames, True, ready, pinned)
 
 
-def staged_clip_logits(model, st: StagedVideo, transform: TestTransform, batch_clips: int = 32) -> torch.Tensor:
+def staged_clip_logits(model, st: StagedVideo, transform: Union[TestTransform, PersonCropTransform], batch_clips: int = 32,
+                       video_name: Optional[str] = None) -> torch.Tensor:
     """Raw logits [hi - lo, num_class] (CPU float32) of a staged clip range.  Frames are transformed once
-    each; clips are gathered from the transformed frames."""
+    each; clips are gathered from the transformed frames.  A ``PersonCropTransform`` (one box per clip, looked up under
+    ``video_name``) transforms per clip instead, behind the windows: ``_person_crop_logits``."""
     if st.hi <= st.lo:
         return torch.empty((0, getattr(model, 'num_class', 0)), dtype=torch.float32)
+    person = isinstance(transform, PersonCropTransform)
+    if person and video_name is None:
+        raise ValueError('a PersonCropTransform looks its boxes up by video: pass video_name')
     starts = clip_starts(st.total)
     dev = _engine_device(model)
-    if (not st.on_device and dev is not None and hasattr(model, 'packed_layout') and isinstance(transform, TestTransform)
-            and int(st.frames.numel()) > MAX_STAGE_BYTES):
+    if (not st.on_device and dev is not None and hasattr(model, 'packed_layout')
+            and isinstance(transform, (TestTransform, PersonCropTransform)) and int(st.frames.numel()) > MAX_STAGE_BYTES):
         # oversized video: pieces of consecutive clips whose even frames fit the staging bound, each staged on its own
         per_frame = max(1, int(st.frames[0].numel()))
         clips_per_piece = max(1, (MAX_STAGE_BYTES // per_frame - CLIP_SPAN // CLIP_STRIDE) // (CLIP_STEP // CLIP_STRIDE))
@@ -261,12 +269,51 @@ def staged_clip_logits(model, st: StagedVideo, transform: TestTransform, batch_c
             finally:
                 _pinned_pool.release(slot, ready)
             parts.append(staged_clip_logits(model, StagedVideo(st.total, a, b, f_a, st.hw, frames, True, ready, pinned),
-                                            transform, batch_clips))
+                                            transform, batch_clips, video_name))
         return torch.cat(parts, dim=0)
+    if person:
+        return _person_crop_logits(model, st, transform, batch_clips, video_name)
     frames, idx, hip_transform = _staged_clips(model, st, transform)
     n = int(idx.shape[0])
     out = [_forward_clips(model, _gather(frames, idx, st, b, min(b + batch_clips, n)), hip_transform)
            for b in range(0, n, batch_clips)]
+    return torch.cat(out, dim=0).to(torch.float32).cpu()
+
+
+def _person_crop_logits(model, st: StagedVideo, transform: PersonCropTransform, batch_clips: int, video_name: str) -> torch.Tensor:
+    """``staged_clip_logits`` for a per-clip box.  Device-staged frames of a TsmEngine: the range's boxes go up once (a few
+    hundred bytes from a pinned int32 tensor), then every batch is ONE ``tsm_preprocess_clips`` launch from the uint8 frames
+    straight into the engine's packed input, and the forward -- no transformed intermediate, no gather, no torch kernel.
+    Anything else (a session, a stub, no GPU): the torch ``PersonCropTransform`` clip by clip."""
+    n = st.hi - st.lo
+    dev = _engine_device(model)
+    if st.on_device and hasattr(model, 'packed_layout'):
+        from .engine import preprocess_clips
+        cur = torch.cuda.current_stream(dev)
+        cur.wait_event(st.ready)
+        st.frames.record_stream(cur)
+        boxes = transform.box_rows(video_name, st.lo, st.hi).pin_memory().to(dev, non_blocking=True)
+        frames = st.frames[:-1]           # (the staged zero frame of the centre-crop path: this kernel needs no pad frame)
+        out = []
+        for a in range(0, n, batch_clips):
+            b = min(a + batch_clips, n)
+            clips = preprocess_clips(frames, boxes[a:b], st.f_lo, st.total, st.lo + a, b - a, size=transform.size,
+                                     scale_255=transform.scale_255, layout=model.packed_layout, n_segment=NUM_SEGMENTS,
+                                     clip_step=CLIP_STEP, clip_stride=CLIP_STRIDE)
+            out.append(model.forward_device(clips, layout=model.packed_layout))
+        return torch.cat(out, dim=0).to(torch.float32).cpu()
+    even = st.frames[:-1] if st.on_device else st.frames
+    if dev is not None and not even.is_cuda:
+        even = even.to(dev, non_blocking=True)
+    clips = []
+    for c in range(st.lo, st.hi):
+        j = [(CLIP_STEP * c + CLIP_STRIDE * k) // CLIP_STRIDE - st.f_lo for k in range(NUM_SEGMENTS)
+             if CLIP_STEP * c + CLIP_STRIDE * k < st.total]
+        clip = even[j[0]:j[-1] + 1].to(torch.float32)
+        if len(j) < NUM_SEGMENTS:        # the zero-padded tail, padded BEFORE the transform as the reference does
+            clip = torch.cat([clip, clip.new_zeros((NUM_SEGMENTS - len(j),) + tuple(clip.shape[1:]))])
+        clips.append(transform(clip.permute(0, 3, 1, 2), transform.box(video_name, c)))
+    out = [_forward_clips(model, torch.stack(clips[a:a + batch_clips]), False) for a in range(0, n, batch_clips)]
     return torch.cat(out, dim=0).to(torch.float32).cpu()
 
 
@@ -332,11 +379,12 @@ def _forward_clips(model, clips: torch.Tensor, hip_transform: bool) -> torch.Ten
     return torch.from_numpy(np.asarray(model.run(None, {name: clips.cpu().numpy()})[0]))
 
 
-def video_clip_logits(model, video_thwc_u8: torch.Tensor, transform: TestTransform,
-                      clip_range: Optional[Tuple[int, int]] = None, batch_clips: int = 32) -> torch.Tensor:
+def video_clip_logits(model, video_thwc_u8: torch.Tensor, transform: Union[TestTransform, PersonCropTransform],
+                      clip_range: Optional[Tuple[int, int]] = None, batch_clips: int = 32,
+                      video_name: Optional[str] = None) -> torch.Tensor:
     """Raw logits [n_clips_in_range, num_class] (CPU float32) for the clips ``clip_range`` (default all)
-    of one video."""
-    return staged_clip_logits(model, stage_video(model, video_thwc_u8, clip_range), transform, batch_clips)
+    of one video (``video_name``: the key a ``PersonCropTransform`` looks its boxes up under)."""
+    return staged_clip_logits(model, stage_video(model, video_thwc_u8, clip_range), transform, batch_clips, video_name)
 
 
 def prefetch_staged(model, videos: Iterable[Tuple[object, torch.Tensor]],
@@ -492,7 +540,7 @@ def _inference_dataset_by_videos(model, items: list, out_dir: str, checkpoint: s
         except StopIteration:            # cannot happen: `mine` has one entry per round this rank takes part in
             item, st = None, None
         if st is not None:
-            local = staged_clip_logits(model, st, transform, batch_clips)
+            local = staged_clip_logits(model, st, transform, batch_clips, item.video_name)
             meta = torch.tensor([st.total, local.shape[0], local.shape[1]], dtype=torch.int64)
         else:
             local = torch.empty((0, num_class or 0), dtype=torch.float32)
@@ -804,7 +852,7 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
                       data_root: Optional[str] = None, anno_path: Optional[str] = None,
                       video_reader: Optional[Callable[[str], torch.Tensor]] = None, action: Sequence[str] = ('all',),
                       batch_clips: int = 32, scale_255: bool = False, shard: Optional[str] = None,
-                      frame_counter: Optional[Callable[[str], int]] = None) -> Optional[Dict[str, torch.Tensor]]:
+                      frame_counter: Optional[Callable[[str], int]] = None, boxes=None) -> Optional[Dict[str, torch.Tensor]]:
     """Inference the RepCount dataset; one ``{video_name}.score.json`` per video with the reference's
     schema: video_name, model, input_shape, checkpoint, total_frames, ground_truth, action, scores.
 
@@ -816,18 +864,26 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     ``shard='clips'`` is the reference's loop shape, one video at a time, and under ``torch.distributed`` splits the
     clips of every video over the ranks (one all-gather per video: lowest latency for ONE stream, but every rank reads
     every video); ``shard='videos'`` is the round-2 form, whole videos round-robin with an exchange per round of W
-    videos (each round lasts as long as its longest video).  All three write identical files."""
+    videos (each round lasts as long as its longest video).  All three write identical files.
+
+    ``person_crop=True`` is the reference's PersonCrop -> Resize((224, 224)) -> Normalize with the boxes given by the caller:
+    ``boxes`` is a callable ``(video_name, clip_index) -> (top, left, h, w) or None`` or a mapping ``video_name -> boxes``
+    (``transform.PersonCropTransform``; the detector is out of scope).  It runs under ``shard='clips'`` (the default then)
+    or ``'videos'``; ``'global'`` is refused: its batcher shares transformed frames between overlapping clips."""
     need_clip_rows(model, 'inference_dataset')
     rank, _world = tdist.world_info()
     if shard is None:
-        shard = 'global'
+        shard = 'clips' if person_crop else 'global'
     if shard not in ('clips', 'videos', 'global'):
         raise ValueError("shard must be 'clips', 'videos' or 'global'")
+    if person_crop and shard == 'global':
+        raise ValueError("person_crop=True runs with shard='clips' or 'videos': the global batcher transforms every frame once "
+                         "and shares it between overlapping clips, and a person box is per clip")
+    transform = build_test_transform(person_crop=person_crop, scale_255=scale_255, boxes=boxes)
     os.makedirs(out_dir, exist_ok=True)       # (every rank: with shard='global' each writes the files of its own videos)
     data_root = osp.expanduser(data_root or '~/data/RepCount/')
     helper = RepcountHelper(data_root, anno_path or osp.join(data_root, 'annotation.csv'))
     data = helper.get_rep_data(splits, action=list(action))
-    transform = build_test_transform(person_crop=person_crop, scale_255=scale_255)
     reader = video_reader or read_video
     if rank == 0:
         print('==> transform:', transform)
@@ -841,7 +897,8 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     videos = ((item, (lambda p=item.video_path: reader(p))) for item in data.values())
     for item, staged in prefetch_staged(model, videos, lambda v: _rank_clip_range(int(v.shape[0]))):
         n_frames = staged.total
-        logits = _gather_video_logits(model, staged_clip_logits(model, staged, transform, batch_clips), n_frames)
+        logits = _gather_video_logits(model, staged_clip_logits(model, staged, transform, batch_clips, item.video_name),
+                                      n_frames)
         if rank == 0:
             _write_score_json(out_dir, item, checkpoint, logits, n_frames)
 

@@ -556,12 +556,12 @@ def test_conv3_conv1_cross_block_kernel_equals_the_separate_launches_bitwise(hip
                                                                 'layer3.5.conv1')}
         assert_fused_slots(eng, x, {n for rows, ns in taken.items() if flag == '1' and rows % t == 0 and rows // t >= 8 for n in ns}, flag)
         eng.close()
-        # What RAN: forced on, every geometry with a clip-major tile runs its instantiation -- layer2.k -> k+1 (<128, 512, 128, 1>),
-        # layer2.3 -> layer3.0 (<128, 512, 256, 2>), layer3.k -> k+1 (<256, 1024, 256, 2>) -- and the geometries without one (odd T,
+        # What RAN: forced on, every geometry with a clip-major tile runs its instantiation -- layer2.k -> k+1 (<128, 512, 128>),
+        # layer2.3 -> layer3.0 (<128, 512, 256>), layer3.k -> k+1 (<256, 1024, 256>) -- and the geometries without one (odd T,
         # T = 64; T = 32 on the 128-row forms) fall back; forced off, none runs.
-        # (a tile is `rows` = T frames x rows / T >= 8 pixels: 256 rows on the 8-wave form, 128 on the wave-pair forms)
-        for rows, inst in ((256, 'conv31_fused_kernel<K3, C, N1, CH> [K3 = 128, C = 512, N1 = 128, CH = 1]'),
-                           (128, 'conv31_pc_kernel<K3, C, N1> [K3 = 128, C = 512, N1 = 256]'),       # (round 5: producer / consumer waves)
+        # (a tile is `rows` = T frames x rows / T >= 8 pixels: 256 rows on conv31_fused_kernel, 128 on conv31_pc_kernel)
+        for rows, inst in ((256, 'conv31_fused_kernel<K3, C, N1> [K3 = 128, C = 512, N1 = 128]'),
+                           (128, 'conv31_pc_kernel<K3, C, N1> [K3 = 128, C = 512, N1 = 256]'),       # (producer / consumer waves)
                            (128, 'conv31_pc_kernel<K3, C, N1> [K3 = 256, C = 1024, N1 = 256]')):
             has_tile = flag == '1' and rows % t == 0 and rows // t >= 8
             assert tr.ran(inst) == has_tile, (flag, inst, sorted(set(tr.kernels)))

@@ -309,10 +309,10 @@ def test_profiling_tools_find_the_forwards_with_and_without_a_pack_launch():
     # one bf16 forward as the engine launches it at config 5: whole-block layer1, cross-block launches in layer2-3
     names = ['stem_pool_kernel<false, true>'] + ['bneck_ws_kernel<64, true, false>'] + ['bneck_ws_kernel<256, true, true>'] * 2
     names += ['conv1x1_wsn_kernel<256, 128, false>', 'conv3x3_ws128_kernel<true>', 'conv_bf16_256p_kernel<1, false, false, true>']      # layer2.0
-    names += ['conv1x1_wsn_kernel<512, 128, false>', 'conv3x3_ws128_kernel<false>', 'conv31_fused_kernel<128, 512, 128, 1>']           # layer2.1 (+ 2.2.conv1)
-    names += ['conv3x3_ws128_kernel<false>', 'conv31_fused_kernel<128, 512, 128, 1>', 'conv3x3_ws128_kernel<false>', 'conv31_fused_kernel<128, 512, 256, 2>']
+    names += ['conv1x1_wsn_kernel<512, 128, false>', 'conv3x3_ws128_kernel<false>', 'conv31_fused_kernel<128, 512, 128>']              # layer2.1 (+ 2.2.conv1)
+    names += ['conv3x3_ws128_kernel<false>', 'conv31_fused_kernel<128, 512, 128>', 'conv3x3_ws128_kernel<false>', 'conv31_pc_kernel<128, 512, 256>']
     names += ['conv_bf16_256p_kernel<3, false, false, false>', 'conv_bf16_256p_kernel<1, false, false, true>']                          # layer3.0 (conv1 came fused)
-    names += ['conv_bf16_256p_kernel<1, true, false, false>'] + ['conv_bf16_256p_kernel<3, false, false, false>', 'conv31_fused_kernel<256, 1024, 256, 2>'] * 4
+    names += ['conv_bf16_256p_kernel<1, true, false, false>'] + ['conv_bf16_256p_kernel<3, false, false, false>', 'conv31_pc_kernel<256, 1024, 256>'] * 4
     names += ['conv_bf16_256p_kernel<3, false, false, false>', 'conv_bf16_256p_kernel<1, false, true, false>']                           # layer3.5
     names += ['conv_bf16_256p_kernel<1, true, false, false>', 'conv_bf16_256p_kernel<3, false, false, false>', 'conv_bf16_256p_kernel<1, false, false, true>']
     names += ['conv_bf16_256p_kernel<1, true, false, false>', 'conv_bf16_256p_kernel<3, false, false, false>', 'conv_bf16_256p_kernel<1, false, true, false>'] * 2
@@ -322,12 +322,9 @@ def test_profiling_tools_find_the_forwards_with_and_without_a_pack_launch():
     assert labels[0] == 'conv1' and labels[1] == 'layer1.0 (block)' and labels[4] == 'layer2.0.conv1'
     assert 'layer2.1.conv3+layer2.2.conv1' in labels and 'layer2.3.conv3+layer3.0.conv1' in labels and 'layer3.4.conv3+layer3.5.conv1' in labels
     assert labels[-1] == 'layer4.2.conv3' and 'layer3.0.conv1' not in labels and 'layer3.1.conv1' in labels
-    # round 5's schedule: layer2.0's conv1 + stride-2 conv2 as one launch, its conv3 + downsample on workgroup pairs, the
-    # producer / consumer form of conv3 + next conv1
+    # round 5's schedule: layer2.0's conv1 + stride-2 conv2 as one launch, its conv3 + downsample on workgroup pairs
     names5 = list(names)
     names5[4:7] = ['front_s2_kernel<true>', 'conv1x1_wsn_kernel<384, 256, true, 2>']
-    names5 = [n.replace('conv31_fused_kernel<128, 512, 256, 2>', 'conv31_pc_kernel<128, 512, 256>')
-               .replace('conv31_fused_kernel<256, 1024, 256, 2>', 'conv31_pc_kernel<256, 1024, 256>') for n in names5]
     rows5, ok5 = match_schedule([dict(Kernel_Name='void tsm::' + n + '(tsm::ConvParams)') for n in names5])
     assert ok5 and len(rows5) == len(names5) == len(names) - 1
     labels5 = [r[0] for r in rows5]

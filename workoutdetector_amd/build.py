@@ -18,7 +18,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), 'include')
 # (TSM_LIB_PATH / TSM_BUILD_DEFS: tooling hooks for A/B builds of one kernel variant against another, e.g.
-#  TSM_LIB_PATH=.../libtsm_hip_v1.so TSM_BUILD_DEFS='-DTSM_256_SCHED=1' python -m workoutdetector_amd.build --force)
+#  TSM_LIB_PATH=.../libtsm_hip_v1.so TSM_BUILD_DEFS='-DTSM_OUT_AUX=16' python -m workoutdetector_amd.build --force)
 LIB_PATH = os.environ.get('TSM_LIB_PATH') or os.path.join(PKG_DIR, 'libtsm_hip.so')
 # One translation unit per kernel family (csrc/tsm_device.h lists them): objects are rebuilt only when their own source or
 # a header changed, in parallel, then linked.

@@ -72,12 +72,6 @@ template <int CIN> struct BnLds {
 // 2s - 1 (M-tiles 0, 1) was the second row of the PREVIOUS step's input: holding it for a step takes 32 registers the file
 // does not have (built: 512 registers and 20 spills), so it still comes from memory.  With the temporal shift the first 64
 // channels of a slot come from frames t +- 1, so the wave that owns output channels 0-63 keeps loading all of its identity.
-#ifndef TSM_BNECK_PXR64
-#define TSM_BNECK_PXR64 4   // conv2's fragment ring of the 64-channel form (8 = reads seven steps ahead instead of three: measured, no change)
-#endif
-#ifndef TSM_BNECK_X
-#define TSM_BNECK_X 0       // timing probes (garbage results): 1 the output stores fully coalesced (1 KB contiguous per instruction),
-#endif                      // 2 the identity loads of the 64-channel form likewise
 #ifndef TSM_BNECK_STAMP
 #define TSM_BNECK_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0's four waves (s_memtime), printed at the kernel's end
 #endif
@@ -282,17 +276,10 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
         // ("+v") in front of their first consumer; the ISA is audited for moves of them (tests/test_code_objects.py).
         asm volatile("s_nop 4" ::: "memory");            // (the descriptor may be fresh from scalar moves: nothing inside asm is padded)
         if constexpr (DUAL) {
-#if TSM_BNECK_X & 2
-          const unsigned o = (unsigned)((s * 16 + mt * 4) * 1024 + lane * 16);
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(res[mt][g]) : "v"(o), "s"(rsrcR), "n"(g * 1024) : "memory");
-#else
           const unsigned o = ok ? (unsigned)((r * W + c) * XROW + half * 16) : kInvalid;
 #pragma unroll
           for (int g = 0; g < 4; ++g)
             asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(res[mt][g]) : "v"(o), "s"(rsrcR), "n"(g * 32) : "memory");
-#endif
         } else {
           const unsigned o = ok ? (unsigned)((r * W + c) * 512 + (2 * wave) * 64 + 2 * half * 16) : kInvalid;
 #pragma unroll
@@ -394,8 +381,8 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-        // fragment reads run PXR - 1 steps ahead of their MFMA (3; the 64-channel form has registers for a ring of eight: no change)
-        constexpr int PXR = TSM_BNECK_PXR64 > 4 && CIN == 64 ? TSM_BNECK_PXR64 : 4;
+        // fragment reads run PXR - 1 steps ahead of their MFMA
+        constexpr int PXR = 4;
         u32x4 px[PXR][2];
         unsigned tb[2] = {0u, 0u};
         auto rd = [&](int st) {
@@ -475,11 +462,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
           for (int itl = 0; itl < 2; ++itl)
             c3[itl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w3r[itl][g]), __builtin_bit_cast(bf16x8, bf[g]), c3[itl], 0, 0, 0);
         const int dr = ml >= W ? 1 : 0, c = ml - dr * W, r = r0 + dr;
-#if TSM_BNECK_X & 1
-        const unsigned yo = (unsigned)(((s * 4 + wave) * 16 + mt * 4) * 1024 + lane * 16 - (l31 * 0));   // (+ itl * 64 + qq * 16 below: patched to * 1024 there)
-#else
         const unsigned yo = (ml < W2 && (unsigned)r < (unsigned)H) ? (unsigned)((r * W + c) * 512 + (2 * wave) * 64 + 2 * half * 16) : kInvalid;
-#endif
         // this M-tile's identity operand; younger operations: M-tiles 0, 1 -- the other early loads (4 / 0), the next input
         // (NDMA), the late loads (8), the stores so far (0 / 4) = NDMA + 12; M-tiles 2, 3 -- the other late loads and the
         // stores so far = 12
@@ -543,11 +526,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq) {
             const u32x4 o = {pk[qq][0], pk[qq][1], pk[qq + 2][0], pk[qq + 2][1]};
-#if TSM_BNECK_X & 1
-            __builtin_amdgcn_raw_buffer_store_b128(o, rsrcY, (int)yo, (itl * 2 + qq) * 1024, TSM_AUX_BNECK);
-#else
             __builtin_amdgcn_raw_buffer_store_b128(o, rsrcY, (int)yo, itl * 64 + qq * 16, TSM_AUX_BNECK);
-#endif
           }
         }
       });

@@ -99,17 +99,29 @@ __device__ __forceinline__ void static_for(F &&f) {
   static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
-// `s_waitcnt vmcnt(n)` for a compile-time-foldable n (the instruction takes an immediate).
+// Counted vector-memory waits (the instruction takes an immediate).  wait_vmcnt<N>(): `s_waitcnt vmcnt(N)` for a constant
+// expression; wait_vmcnt_lgkm0<N>(): with lgkmcnt(0) in the same instruction; wait_vmcnt(n): for an n that is a constant only
+// after inlining and unrolling (the switch folds to its one case).
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vmcnt_lgkm0() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
 __device__ __forceinline__ void wait_vmcnt(int n) {
-#define TSM_VMCNT_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+#define TSM_VMCNT_CASE(k) case k: wait_vmcnt<k>(); break;
   switch (n) {
-    TSM_VMCNT_CASE(0) TSM_VMCNT_CASE(4) TSM_VMCNT_CASE(8) TSM_VMCNT_CASE(12) TSM_VMCNT_CASE(16) TSM_VMCNT_CASE(20)
-    TSM_VMCNT_CASE(24) TSM_VMCNT_CASE(28) TSM_VMCNT_CASE(32) TSM_VMCNT_CASE(36) TSM_VMCNT_CASE(40) TSM_VMCNT_CASE(44)
-    TSM_VMCNT_CASE(48) TSM_VMCNT_CASE(52) TSM_VMCNT_CASE(56) TSM_VMCNT_CASE(60)
-    TSM_VMCNT_CASE(3) TSM_VMCNT_CASE(7) TSM_VMCNT_CASE(11) TSM_VMCNT_CASE(15) TSM_VMCNT_CASE(19) TSM_VMCNT_CASE(23)
-    TSM_VMCNT_CASE(27) TSM_VMCNT_CASE(31) TSM_VMCNT_CASE(35) TSM_VMCNT_CASE(39) TSM_VMCNT_CASE(43) TSM_VMCNT_CASE(47)
-    TSM_VMCNT_CASE(51) TSM_VMCNT_CASE(55) TSM_VMCNT_CASE(59) TSM_VMCNT_CASE(63)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    TSM_VMCNT_CASE(0) TSM_VMCNT_CASE(1) TSM_VMCNT_CASE(2) TSM_VMCNT_CASE(3) TSM_VMCNT_CASE(4) TSM_VMCNT_CASE(5) TSM_VMCNT_CASE(6) TSM_VMCNT_CASE(7)
+    TSM_VMCNT_CASE(8) TSM_VMCNT_CASE(9) TSM_VMCNT_CASE(10) TSM_VMCNT_CASE(11) TSM_VMCNT_CASE(12) TSM_VMCNT_CASE(13) TSM_VMCNT_CASE(14) TSM_VMCNT_CASE(15)
+    TSM_VMCNT_CASE(16) TSM_VMCNT_CASE(17) TSM_VMCNT_CASE(18) TSM_VMCNT_CASE(19) TSM_VMCNT_CASE(20) TSM_VMCNT_CASE(21) TSM_VMCNT_CASE(22) TSM_VMCNT_CASE(23)
+    TSM_VMCNT_CASE(24) TSM_VMCNT_CASE(25) TSM_VMCNT_CASE(26) TSM_VMCNT_CASE(27) TSM_VMCNT_CASE(28) TSM_VMCNT_CASE(29) TSM_VMCNT_CASE(30) TSM_VMCNT_CASE(31)
+    TSM_VMCNT_CASE(32) TSM_VMCNT_CASE(33) TSM_VMCNT_CASE(34) TSM_VMCNT_CASE(35) TSM_VMCNT_CASE(36) TSM_VMCNT_CASE(37) TSM_VMCNT_CASE(38) TSM_VMCNT_CASE(39)
+    TSM_VMCNT_CASE(40) TSM_VMCNT_CASE(41) TSM_VMCNT_CASE(42) TSM_VMCNT_CASE(43) TSM_VMCNT_CASE(44) TSM_VMCNT_CASE(45) TSM_VMCNT_CASE(46) TSM_VMCNT_CASE(47)
+    TSM_VMCNT_CASE(48) TSM_VMCNT_CASE(49) TSM_VMCNT_CASE(50) TSM_VMCNT_CASE(51) TSM_VMCNT_CASE(52) TSM_VMCNT_CASE(53) TSM_VMCNT_CASE(54) TSM_VMCNT_CASE(55)
+    TSM_VMCNT_CASE(56) TSM_VMCNT_CASE(57) TSM_VMCNT_CASE(58) TSM_VMCNT_CASE(59) TSM_VMCNT_CASE(60) TSM_VMCNT_CASE(61) TSM_VMCNT_CASE(62) TSM_VMCNT_CASE(63)
+    default: wait_vmcnt<0>(); break;
   }
 #undef TSM_VMCNT_CASE
 }

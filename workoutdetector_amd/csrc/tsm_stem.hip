@@ -178,9 +178,6 @@ constexpr int kPoolPR = 2 * kPoolCR + 5, kPoolPC = kPoolCC + 3;      // input pa
 // pack_input_kernel would have written: a patch chunk is then six floats (two pixels x three colour planes) that are held
 // raw while the previous tile computes and rounded / split exactly as pack_input does (store_group's arithmetic) when the
 // patch is written to LDS -- same bits, and the forward loses the pack launch with its write and re-read of the packed tensor.
-#ifndef TSM_STEM_WREG
-#define TSM_STEM_WREG 4
-#endif
 #ifndef TSM_STEM_STAMP
 #define TSM_STEM_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0 (s_memtime), printed at the kernel's end
 #endif
@@ -318,8 +315,8 @@ __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float 
   if ((int)blockIdx.x < n_tiles) fetch_patch((int)xcd_chunked(blockIdx.x, n_tiles));
   // bf16: the weight fragments of this lane's second channel tile (14 x 16 bytes) live in registers for the life of the workgroup
   // -- the kernel used 56 of the 128 registers two workgroups per CU leave it, and every wave read the same 28 fragments from
-  // LDS for every tile: one LDS read in three of the MFMA phase is gone (TSM_STEM_WREG)
-  constexpr int NWREG = X3 ? 0 : TSM_STEM_WREG;     // fragments held (the first NWREG k16 steps)
+  // LDS for every tile: one LDS read in three of the MFMA phase is gone
+  constexpr int NWREG = X3 ? 0 : 4;                 // fragments held (the first NWREG k16 steps)
   constexpr bool kWreg = NWREG > 0;
   u32x4 wreg[kWreg ? NWREG : 1];
   if constexpr (kWreg) {

@@ -579,9 +579,6 @@ static int ws128_read_cycles(bool s2, int TR, int TC, int mode) {
   return cycles;
 }
 static int ws128_best_swap(bool s2, int TR, int TC) {
-#ifdef TSM_WS128_SWZ_FORCE      // A/B builds only (TSM_BUILD_DEFS): 0 = rounds 2-4's bit-3 swap
-  return TSM_WS128_SWZ_FORCE;
-#endif
   int best = 0, best_c = ws128_read_cycles(s2, TR, TC, 0);
   for (int mode = 1; mode < 4; ++mode) {
     const int c = ws128_read_cycles(s2, TR, TC, mode);
@@ -1219,7 +1216,9 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
         }
       }
     }
-    wait_vmcnt(NTW * 2);        // the next tile's last piece is older than the last M-tile's stores (and younger than every other store)
+    // the next tile's last piece is older than the last M-tile's NTW * 2 stores (and younger than every other store).  COUT = 128
+    // waits for its two stores as well: it always has (wait_vmcnt once had no case for 2); the counted wait is unmeasured there
+    wait_vmcnt(NTW == 1 ? 0 : NTW * 2);
   }
 }
 

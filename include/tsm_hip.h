@@ -29,6 +29,10 @@
  *                          -> Normalize, fused with the clip windows   datasets/build.py:123-129, datasets/transform.py:247-259
  *   tsm_scores_to_states   per clip: to_softmax, first arg-max, score >= 0.5 ? class : -1
  *                          workoutdetector/utils/eval.py:153-164, utils/visualize.py:140-150
+ *   tsm_preprocess_image   data_transform of the image model: ToPILImage -> Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize
+ *                          (Pillow's antialiased resample, to the bit)   workoutdetector/utils/inference_count.py:27-34,168-189
+ *   tsm_frame_votes        count_by_image_model's vote: arg-max per frame, deque of 7, sum(que) >= 4
+ *                          workoutdetector/utils/inference_count.py:221-231
  *
  * Conventions
  *   - Plain pointers and sizes only; no torch / HIP types in signatures.  hip streams travel as
@@ -59,7 +63,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips (both added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips, tsm_preprocess_image, tsm_frame_votes (all four added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -386,6 +390,45 @@ int tsm_head_segments(const float *feat, const float *fc_w, const float *fc_b, f
  * the host instead of the logits and feeds pred_to_count directly. */
 int tsm_scores_to_states(const float *logits, int32_t n_clips, int32_t num_class, int32_t softmax, float threshold,
                          int32_t *states, float *top_score, void *stream);
+
+/* The per-frame transform of the reference's IMAGE model on the GPU (device pointers), one launch from staged uint8 frames to
+ * the packed input of a num_segments = 1 engine:
+ *   data_transform = ToPILImage -> Resize(resize) -> CenterCrop(crop) -> ToTensor -> Normalize(ImageNet)
+ *   workoutdetector/utils/inference_count.py:27-34 -- Pillow's ImagingResample for 8-bit channels with the bilinear (triangle)
+ *   filter: antialiased (support = max(in / out, 1)), a horizontal pass rounded to uint8, then a vertical pass over those
+ *   uint8 values, each u8 = clamp((2^21 + sum(pixel * k)) >> 22, 0, 255) in int32.  NOT tsm_preprocess (ATen's bilinear on
+ *   floats without antialias): for a 720 x 1280 frame the two differ by several grey levels per pixel.
+ * frames: uint8 [n, h, w, 3].  The channel order is kept as given (the reference hands cv2's BGR frames to ToPILImage as they
+ *         are: which order the model was trained on is the caller's business).
+ * Sizes:  torchvision's Resize(int): shorter side -> resize, longer -> int(resize * long / short); an axis that keeps its size
+ *         is not resampled (Pillow skips that pass).  Crop window: top = int(round((nh - crop) / 2.0)) (round half to even),
+ *         left likewise.  Only the window's pixels are computed and only their taps are read.
+ * tables: DEVICE int32 [table_words], the coefficient tables the HOST computes in double (Pillow's precompute_coeffs +
+ *         normalize_coeffs_8bpc; workoutdetector_amd/transform.py::image_tables builds and caches the block), for the crop
+ *         window's output indices only.  When the width changes: hb [crop][2] = (first source column, taps) of output columns
+ *         left .. left + crop - 1, then hk [crop][ksx] = their weights, int(w * 2^22 +- 0.5), zero-padded to ksx =
+ *         ceil(max(w / nw, 1)) * 2 + 1; when the height changes: vb [crop][2], vk [crop][ksy] likewise for rows top .. top +
+ *         crop - 1.  table_words must be exactly crop * (2 + ksx) [+ crop * (2 + ksy)] (0 and tables == NULL when neither axis
+ *         changes), else TSM_ERR_INVALID_ARG.  The table CONTENTS cannot be validated (device memory): the kernel is total in
+ *         them -- every bound is clamped into the frame before use, so it reads only inside `frames` and writes exactly `out`.
+ * out:    as tsm_preprocess: TSM_LAYOUT_NTHWC4 / NTHWC8S / NTHWC8B / NTCHW, values ((u8 / 255) - mean) / std in fp32.
+ * One workgroup per (frame, band of <= 8 output rows) keeps the horizontally resampled rows under the band's vertical support
+ * in LDS; TSM_ERR_UNSUPPORTED (nothing launched) when one output row's support does not fit 64 KB (crop 224: beyond a 47x
+ * vertical downscale; a 2160-line frame to 256 is 8.4x).  Enqueues on `stream`; no synchronisation. */
+int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, const int32_t *tables, int64_t table_words,
+                         float *out, int32_t out_layout, int32_t resize, int32_t crop, void *stream);
+
+/* The image model's vote on the GPU (device pointers)   workoutdetector/utils/inference_count.py:221-231:
+ *   logits [n_frames, num_class] fp32 -> pred [n_frames] int32, the FIRST arg-max of every row (numpy.argmax's tie rule), and
+ *   state [n_frames] int32 0 / 1 = (sum of the last up-to-7 preds ending at that frame) >= 4: the reference's deque(maxlen=7)
+ *   and `sum(que) >= 4`.  The sum is over CLASS IDS, exactly as the reference's is: with two classes "at least 4 of the last 7
+ *   frames are class 1"; with more classes it is whatever that sum gives -- reproduced, not repaired.
+ * A video spans many calls: history [n_hist], n_hist in 0..6, holds the preds of the frames before this batch, oldest first;
+ * history_out [6] (nullable; must not alias history) receives the last min(6, n_hist + n_frames) preds of (history ++ this
+ * batch), oldest first, and -1 in the slots behind them -- the next call's history, with that count.  Inputs are finite (NaN handling is the reference's:
+ * unspecified).  One launch, no host synchronisation, on `stream`. */
+int tsm_frame_votes(const float *logits, int32_t n_frames, int32_t num_class, const int32_t *history, int32_t n_hist,
+                    int32_t *pred, int32_t *state, int32_t *history_out, void *stream);
 
 #ifdef __cplusplus
 }

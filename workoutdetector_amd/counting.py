@@ -4,6 +4,7 @@ Counterparts of (reference file:line):
   pred_to_count     workoutdetector/utils/inference_count.py:114-165
   to_softmax        workoutdetector/utils/visualize.py:140-150
   scores_to_preds   workoutdetector/utils/eval.py:153-164 (arg-max, ``score >= threshold`` else -1)
+  vote_states       workoutdetector/utils/inference_count.py:221-231 (the image model's deque of 7, ``sum(que) >= 4``)
   obo_mae           workoutdetector/utils/eval.py:11-24
   eval_count        workoutdetector/datasets/repcount_dataset.py:212-251 (metric part)
 
@@ -79,6 +80,21 @@ def scores_to_preds(scores: Iterable[Sequence[float]], threshold: float = 0.5, s
     best = p.argmax(axis=1)           # first maximum, like Python's max() over dict items
     top = p[np.arange(len(p)), best]
     return [int(b) if t >= threshold else -1 for b, t in zip(best, top)]
+
+
+VOTE_WINDOW = 7         # count_by_image_model's deque(maxlen=7) ...
+VOTE_SUM = 4            # ... and its `sum(que) >= 4`
+
+
+def vote_states(preds: Sequence[int], history: Sequence[int] = ()) -> Tuple[List[int], List[int]]:
+    """The image model's vote on the host (utils/inference_count.py:221-231): per frame ``state = sum(last <= 7 preds) >= 4``
+    as 0 / 1.  The sum is over CLASS IDS, exactly as the reference's ``sum(que)`` is (two classes: at least 4 of the last 7
+    frames are class 1; more classes: whatever that sum gives -- reproduced, not repaired).  ``history``: the preds of the
+    up to 6 frames before these (a video spans many batches).  Returns (states, the history for the next batch)."""
+    seq = [int(p) for p in history][-(VOTE_WINDOW - 1):] + [int(p) for p in preds]
+    off = len(seq) - len(preds)
+    states = [int(sum(seq[max(0, off + i - VOTE_WINDOW + 1): off + i + 1]) >= VOTE_SUM) for i in range(len(preds))]
+    return states, seq[-(VOTE_WINDOW - 1):]
 
 
 def obo_mae(preds: Sequence[int], targets: Sequence[int], ratio: bool = True):

@@ -1825,6 +1825,64 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
   return TSM_OK;
 }
 
+// taps per row of Pillow's coefficient table for one axis (Resample.c precompute_coeffs: ksize = ceil(support) * 2 + 1)
+static int pil_ksize(int in, int out) {
+  const double scale = (double)in / out, support = scale < 1.0 ? 1.0 : scale;
+  return (int)std::ceil(support) * 2 + 1;
+}
+
+int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, const int32_t *tables, int64_t table_words,
+                         float *out, int32_t out_layout, int32_t resize, int32_t crop, void *stream) {
+  if (!frames || !out || n <= 0 || h <= 0 || w <= 0 || resize <= 0 || crop <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: NULL pointer or non-positive size");
+  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
+      out_layout != TSM_LAYOUT_NTHWC8B)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  tsm::ImagePreprocParams p{};
+  p.src = static_cast<const unsigned char *>(frames); p.dst = out; p.n = n; p.h = h; p.w = w;
+  // torchvision Resize(int) on a PIL image: short side -> resize, long side -> int(resize * long / short)
+  if (h <= w) { p.nh = resize; p.nw = (int)((double)resize * w / h); }
+  else { p.nh = (int)((double)resize * h / w); p.nw = resize; }
+  if (crop > p.nh || crop > p.nw) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: crop larger than the resized frame");
+  // center_crop: int(round((dim - crop) / 2.0)) with Python's round-half-to-even
+  p.top = (int)std::nearbyint((p.nh - crop) / 2.0);
+  p.left = (int)std::nearbyint((p.nw - crop) / 2.0);
+  p.crop = crop;
+  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
+               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
+  // the table block: [hb 2 * crop][hk crop * ksx] when the width changes, then [vb 2 * crop][vk crop * ksy] when the height does
+  const bool horiz = p.nw != w, vert = p.nh != h;
+  p.ksx = horiz ? pil_ksize(w, p.nw) : 0;
+  p.ksy = vert ? pil_ksize(h, p.nh) : 0;
+  const int64_t hwords = horiz ? (int64_t)crop * (2 + p.ksx) : 0, vwords = vert ? (int64_t)crop * (2 + p.ksy) : 0;
+  if (table_words != hwords + vwords || (table_words > 0 && !tables))
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: the table block must hold " + std::to_string(hwords + vwords) +
+                " int32 words for this geometry (crop * (2 + taps) per resampled axis), got " + std::to_string(table_words));
+  if (horiz) { p.hb = tables; p.hk = tables + 2 * (int64_t)crop; }
+  if (vert) { p.vb = tables + hwords; p.vk = tables + hwords + 2 * (int64_t)crop; }
+  hipError_t st = tsm::launch_preprocess_image(p, static_cast<hipStream_t>(stream));
+  if (st == hipErrorNotSupported)
+    return fail(nullptr, TSM_ERR_UNSUPPORTED, "preprocess_image: the rows under one output row's vertical support do not fit 64 KB "
+                "of LDS (downscale " + std::to_string(h) + " -> " + std::to_string(p.nh) + " lines at crop " + std::to_string(crop) + ")");
+  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
+                                    std::string("preprocess_image: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
+int tsm_frame_votes(const float *logits, int32_t n_frames, int32_t num_class, const int32_t *history, int32_t n_hist,
+                    int32_t *pred, int32_t *state, int32_t *history_out, void *stream) {
+  if (!logits || !pred || !state || n_frames <= 0 || num_class <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "frame_votes: NULL pointer or non-positive size");
+  if (n_hist < 0 || n_hist > 6 || (n_hist > 0 && !history))
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "frame_votes: n_hist must be 0..6, with a history of that many entries");
+  if (history_out && history_out == history)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "frame_votes: history_out must not alias history");
+  hipError_t st = tsm::launch_frame_votes(logits, n_frames, num_class, history, n_hist, pred, state, history_out,
+                                          static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("frame_votes: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits, int32_t n_clips,
              int32_t n_segment, int32_t hw, int32_t c, int32_t num_class, void *stream) {
   if (!feat || !fc_w || !fc_b || !logits || n_clips <= 0 || n_segment <= 0 || hw <= 0 || c <= 0 || num_class <= 0)

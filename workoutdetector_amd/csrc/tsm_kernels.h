@@ -226,6 +226,32 @@ struct ClipPreprocParams {
 };
 hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s);
 
+// The image model's per-frame transform (see preprocess_image_kernel): staged uint8 frames [n,h,w,3] -> Pillow's antialiased
+// bilinear resize to nh x nw (integer arithmetic from host-built tables), the crop window (top, left, crop) of it, normalised
+// and packed in any out_mode of PreprocParams.  Tables (device int32, rows for the crop window's output indices only):
+// hb / vb [crop][2] = (first source index, taps), hk / vk [crop][ksx | ksy] = weights scaled by 2^22; hk == nullptr or
+// vk == nullptr skips that pass (legal only where the axis keeps its size).  The launcher picks band / rows_cap / stride and
+// returns hipErrorNotSupported when one output row's vertical support does not fit kImageMaxLds.
+constexpr int kImageMaxLds = 65536;
+struct ImagePreprocParams {
+  const unsigned char *src;
+  float *dst;
+  const int *hb, *hk, *vb, *vk;
+  int n, h, w;        // source frames
+  int nh, nw;         // resized size
+  int top, left, crop;
+  int ksx, ksy;       // taps per table row
+  int out_mode;       // as PreprocParams
+  int band, rows_cap, stride;   // set by the launcher: output rows per workgroup, LDS rows, bytes per LDS row
+};
+hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s);
+
+// The image model's vote (see frame_votes_kernel): pred [n] = first arg-max, state [n] = (sum of the last <= 7 preds) >= 4,
+// hist_in [n_hist <= 6] the preds before this batch (oldest first), hist_out [6] (nullable, must not alias hist_in) the last
+// min(6, n_hist + n) afterwards.
+hipError_t launch_frame_votes(const float *logits, int n, int c, const int *hist_in, int n_hist, int *pred, int *state,
+                              int *hist_out, hipStream_t s);
+
 hipError_t launch_maxpool3x3s2(const float *x, float *y, int n, int hi, int wi, int c, int prec,
                                hipStream_t s);
 hipError_t launch_temporal_shift(const float *x, float *y, int64_t n_frames, int n_segment,

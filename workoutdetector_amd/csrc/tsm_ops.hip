@@ -686,6 +686,220 @@ hipError_t launch_scores_to_states(const float *logits, int n, int c, int softma
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// preprocess_image: the per-frame transform of the reference's IMAGE model (utils/inference_count.py:27-34: ToPILImage ->
+// Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize), i.e. Pillow's ImagingResample for 8-bit channels with the
+// bilinear (triangle) filter: an antialiased horizontal pass rounded to uint8, then a vertical pass over those uint8 values,
+// each u8 = clamp((2^21 + sum(pixel * k)) >> 22, 0, 255) with int32 weights the HOST computed in double (bounds + weights per
+// output index of the crop window: transform.py::pil_resample_tables).  The kernel is integer arithmetic up to the final
+// normalisation, which is what makes it Pillow's result to the bit.
+// One workgroup per (frame, band of `band` output rows):
+//   phase 1  the horizontally resampled uint8 rows the band's vertical support needs -> LDS (only the crop window's columns,
+//            only their taps are read); a thread per (row, column), three channels each;
+//   phase 2  the vertical pass from LDS, (u8 / 255 - mean) / std in fp32 (true divisions: the value is NumPy's to the bit),
+//            packed as preprocess_kernel packs; a thread per output group.
+// LDS rows are plain byte rows [rows][crop * 3, padded to 4 bytes]: in both phases the lanes of a wave walk consecutive columns
+// of ONE row, i.e. consecutive bytes -- at most 192 contiguous bytes = 48 of the 64 banks per wave access, lanes that share a
+// dword share its bank AND its address (a broadcast, not a conflict).  The rounding to uint8 between the passes is why a row
+// costs one byte per channel here and why there are two real passes.
+// A pass whose axis keeps its size is skipped (hk / vk == nullptr), as Pillow skips it: phase 1 then copies, phase 2 reads its
+// own row.  TOTAL in the tables (device memory, no host check sees them): every bound is clamped into the frame / the rows in
+// LDS before it is used, so for ANY table contents the kernel reads only inside `src` and its own LDS rows.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ unsigned clip8(unsigned acc) {
+  const int v = (int)acc >> 22;          // (arithmetic shift: Pillow's clip8 floors a negative sum, then clamps it to 0)
+  return (unsigned)clampi(v, 0, 255);
+}
+
+__global__ void __launch_bounds__(256) preprocess_image_kernel(const ImagePreprocParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char img_rows[];
+  const int nb = (p.crop + p.band - 1) / p.band;
+  const int64_t f = blockIdx.x / nb;
+  const int r0 = (int)(blockIdx.x - f * nb) * p.band;
+  const int r1 = r0 + p.band < p.crop ? r0 + p.band : p.crop;
+  // source rows [y0, y0 + nrows) under the band's vertical support
+  int y0, nrows;
+  if (p.vk) {
+    y0 = clampi(p.vb[2 * r0], 0, p.h - 1);
+    const int yend = clampi(p.vb[2 * (r1 - 1)] + p.vb[2 * (r1 - 1) + 1], y0 + 1, p.h);
+    nrows = yend - y0 < p.rows_cap ? yend - y0 : p.rows_cap;
+  } else {
+    y0 = p.top + r0;
+    nrows = r1 - r0;
+  }
+  const unsigned char *frame = p.src + f * (int64_t)p.h * p.w * 3;
+  for (int i = threadIdx.x; i < nrows * p.crop; i += 256) {
+    const int r = i / p.crop, cx = i - r * p.crop;
+    const unsigned char *row = frame + (int64_t)(y0 + r) * p.w * 3;
+    unsigned char *o = img_rows + r * p.stride + cx * 3;
+    if (p.hk) {
+      const int xmin = clampi(p.hb[2 * cx], 0, p.w - 1);
+      const int room = p.w - xmin < p.ksx ? p.w - xmin : p.ksx;
+      const int cnt = clampi(p.hb[2 * cx + 1], 0, room);
+      const int *k = p.hk + (int64_t)cx * p.ksx;
+      const unsigned char *q = row + xmin * 3;
+      unsigned s0 = 1u << 21, s1 = 1u << 21, s2 = 1u << 21;
+      for (int t = 0; t < cnt; ++t) {
+        const unsigned kv = (unsigned)k[t];
+        s0 += q[3 * t] * kv;
+        s1 += q[3 * t + 1] * kv;
+        s2 += q[3 * t + 2] * kv;
+      }
+      o[0] = (unsigned char)clip8(s0);
+      o[1] = (unsigned char)clip8(s1);
+      o[2] = (unsigned char)clip8(s2);
+    } else {
+      const unsigned char *q = row + (p.left + cx) * 3;
+      o[0] = q[0];
+      o[1] = q[1];
+      o[2] = q[2];
+    }
+  }
+  __syncthreads();
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int wg = (p.crop + px - 1) / px;
+  for (int i = threadIdx.x; i < (r1 - r0) * wg; i += 256) {
+    const int ry = i / wg, gx = i - ry * wg;
+    const int cy = r0 + ry;
+    int ymin = ry, cnt = 1;
+    const int *k = nullptr;
+    if (p.vk) {
+      ymin = clampi(p.vb[2 * cy] - y0, 0, nrows - 1);
+      const int room = nrows - ymin < p.ksy ? nrows - ymin : p.ksy;
+      cnt = clampi(p.vb[2 * cy + 1], 0, room);
+      k = p.vk + (int64_t)cy * p.ksy;
+    }
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int x = gx * px + q;
+      if (q >= px || x >= p.crop) continue;
+      const unsigned char *col = img_rows + ymin * p.stride + x * 3;
+      unsigned u[3];
+      if (k) {
+        unsigned s0 = 1u << 21, s1 = 1u << 21, s2 = 1u << 21;
+        for (int t = 0; t < cnt; ++t) {
+          const unsigned kv = (unsigned)k[t];
+          const unsigned char *e = col + t * p.stride;
+          s0 += e[0] * kv;
+          s1 += e[1] * kv;
+          s2 += e[2] * kv;
+        }
+        u[0] = clip8(s0);
+        u[1] = clip8(s1);
+        u[2] = clip8(s2);
+      } else {
+        u[0] = col[0];
+        u[1] = col[1];
+        u[2] = col[2];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[4 * q + c] = ((float)u[c] / 255.0f - mean[c]) / stdv[c];
+    }
+    const int64_t g = (f * p.crop + cy) * wg + gx;       // output group, as preprocess_kernel numbers them
+    if (p.out_mode == 1) {
+      float *o = p.dst + f * 3 * (int64_t)p.crop * p.crop + (int64_t)cy * p.crop + gx;
+      o[0] = v[0];
+      o[(int64_t)p.crop * p.crop] = v[1];
+      o[2 * (int64_t)p.crop * p.crop] = v[2];
+    } else if (p.out_mode == 2) {
+      store_group<kPrecBf16x3>(p.dst + g * 8, v);
+    } else if (p.out_mode == 3) {
+      store_group<kPrecBf16>(p.dst + g * 4, v);
+    } else {
+      store_group<kPrecF32>(p.dst + g * 4, v);
+    }
+  }
+}
+
+// LDS rows a band of `band` output rows can need: ymin(first) >= c0 - support - 0.5 and yend(last) <= c1 + support + 0.5 with
+// c1 - c0 = (band - 1) * scale, so the span is at most (band - 1) * scale + 2 * support + 1 rows.
+static int image_rows_cap(int band, int in, int out) {
+  const double scale = (double)in / out, support = scale < 1.0 ? 1.0 : scale;
+  return (int)((band - 1) * scale + 2.0 * support) + 2;
+}
+
+hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s) {
+  if (!p.src || !p.dst || p.n <= 0 || p.h <= 0 || p.w <= 0 || p.nh <= 0 || p.nw <= 0 || p.crop <= 0 || p.top < 0 || p.left < 0 ||
+      p.top + p.crop > p.nh || p.left + p.crop > p.nw || p.out_mode < 0 || p.out_mode > 3)
+    return hipErrorInvalidValue;
+  // a pass without tables copies: legal only where that axis keeps its size (the crop window then lies inside the frame)
+  if ((!p.hk && p.nw != p.w) || (!p.vk && p.nh != p.h) || (p.hk && (!p.hb || p.ksx <= 0)) || (p.vk && (!p.vb || p.ksy <= 0)))
+    return hipErrorInvalidValue;
+  p.stride = (p.crop * 3 + 3) & ~3;
+  // the band height: 8 output rows unless the rows under their support do not fit 64 KB of LDS (a > 9x downscale at crop 224)
+  for (p.band = 8;; p.band /= 2) {
+    p.rows_cap = p.vk ? image_rows_cap(p.band, p.h, p.nh) : p.band;
+    if ((int64_t)p.rows_cap * p.stride <= kImageMaxLds) break;
+    if (p.band == 1) return hipErrorNotSupported;
+  }
+  const int64_t blocks = (int64_t)p.n * ((p.crop + p.band - 1) / p.band);
+  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+  TSM_KLAUNCH(preprocess_image_kernel, dim3((unsigned)blocks), dim3(256), (size_t)p.rows_cap * p.stride, s, p);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// frame_votes: the image model's vote (utils/inference_count.py:221-231): per frame the FIRST arg-max of its logits (as
+// numpy.argmax breaks ties), pushed into a queue of 7; state = sum(queue) >= 4.  The sum is over CLASS IDS, exactly as the
+// reference's sum(que) is -- for two classes "at least 4 of the last 7 frames are class 1", for more classes whatever that
+// sum gives.  A video spans many batches: hist_in holds the arg-max of the n_hist (0..6) frames before this batch, oldest
+// first, hist_out [6] receives the last min(6, n_hist + n) of (history ++ this batch), -1 behind them.  One thread per frame: it takes the arg-max
+// of its own row and of the up to six rows before it again (num_class is tiny) instead of waiting for other threads, so the
+// whole vote is one launch with no ordering between workgroups; the thread of the last frame writes hist_out.  hist_in and
+// hist_out must not alias (threads of other workgroups still read the old history).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int first_argmax(const float *s, int c) {
+  float best = s[0];
+  int arg = 0;
+  for (int j = 1; j < c; ++j)
+    if (s[j] > best) {
+      best = s[j];
+      arg = j;
+    }
+  return arg;
+}
+
+__global__ void __launch_bounds__(64) frame_votes_kernel(const float *__restrict__ logits, int n, int c,
+                                                         const int *__restrict__ hist_in, int n_hist, int *__restrict__ pred,
+                                                         int *__restrict__ state, int *__restrict__ hist_out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  int last[7];       // arg-max of sequence positions i - 6 .. i (position < 0: the history; before it: nothing, -1)
+  int sum = 0;
+#pragma unroll
+  for (int d = 0; d < 7; ++d) {
+    const int j = i - 6 + d;
+    int a = -1;
+    if (j >= 0)
+      a = first_argmax(logits + (size_t)j * c, c);
+    else if (n_hist + j >= 0)
+      a = hist_in[n_hist + j];
+    last[d] = a;
+    sum += a < 0 ? 0 : a;
+  }
+  pred[i] = last[6];
+  state[i] = sum >= 4 ? 1 : 0;
+  if (i == n - 1 && hist_out) {
+    const int m = n_hist + n < 6 ? n_hist + n : 6;
+#pragma unroll
+    for (int d = 1; d < 7; ++d)          // (static register index, run-time slot: position n - 7 + d is slot d - (7 - m))
+      if (d >= 7 - m) hist_out[d - (7 - m)] = last[d];
+    for (int e = m; e < 6; ++e) hist_out[e] = -1;     // the slots behind the count: defined, and no class id
+  }
+}
+
+hipError_t launch_frame_votes(const float *logits, int n, int c, const int *hist_in, int n_hist, int *pred, int *state,
+                              int *hist_out, hipStream_t s) {
+  if (!logits || !pred || !state || n <= 0 || c <= 0 || n_hist < 0 || n_hist > 6 || (n_hist > 0 && !hist_in) ||
+      (hist_out && hist_out == hist_in))
+    return hipErrorInvalidValue;
+  TSM_KLAUNCH(frame_votes_kernel, dim3((n + 63) / 64), dim3(64), 0, s, logits, n, c, hist_in, n_hist, pred, state, hist_out);
+  return hipGetLastError();
+}
+
 
 // ---- launch trace (tests): which kernels did this thread launch? ---------------------------------------------------
 namespace {

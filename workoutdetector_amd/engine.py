@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
-                      remap_mmaction_keys)
+                      remap_mmaction_keys, remap_torchvision_keys)
 
 CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
 
@@ -370,6 +370,39 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
                      dtype=dtype, base_model=base_model, shift_place=shift_place, consensus_type=consensus_type)
 
 
+def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpoint: Optional[str] = None, max_frames: int = 32,
+                       dtype: str = 'f32', resize: int = 256, crop: int = 224, seed: int = 0,
+                       device: Optional[object] = None) -> TsmEngine:
+    """The reference's per-frame image classifier (image_classification.py:214: a torchvision ``resnet18`` with a replaced
+    ``fc``; ``inference_image`` / ``count_by_image_model``, utils/inference_count.py:168-243) as a ``TsmEngine`` with
+    ``num_segments=1``, ``is_shift=False``, ``consensus_type='avg'`` and ``height = width = crop``: one frame is one clip, so
+    ``max_frames`` is the engine's ``max_clips``.  ``resize`` / ``crop`` are the ``data_transform`` the engine's frames go
+    through (``engine.image_resize`` / ``engine.image_crop``; ``inference_count.inference_images`` reads them).
+    ``checkpoint``: a ``torch.save``d ``state_dict`` (or a dict with a ``state_dict`` entry) with plain torchvision keys --
+    ``conv1.weight``, ``layer1.0.*``, ``fc.*`` -- or a Lightning one whose keys carry one leading component
+    (``weights.remap_torchvision_keys``).  Without one the engine gets the seeded synthetic weights, as ``create_model`` does."""
+    if base_model not in DEPTHS:
+        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+    if crop > resize:
+        raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
+    dev = 0
+    if device is not None:
+        s = str(device)
+        if s == 'cpu':
+            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
+        dev = int(s.split(':')[1]) if ':' in s else 0
+    if checkpoint is not None:
+        import torch
+        ckpt = torch.load(checkpoint, map_location='cpu')
+        sd = remap_torchvision_keys(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+    else:
+        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
+    eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
+                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg')
+    eng.image_resize, eng.image_crop = int(resize), int(crop)
+    return eng
+
+
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------
 class launch_trace:
     """``with launch_trace() as tr: ...`` records one line per kernel launch the library makes from THIS thread inside the
@@ -530,6 +563,82 @@ def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: boo
     _lib.check(_lib.load().tsm_preprocess(frames.data_ptr(), pixel, n, h, w, out.data_ptr(), layout, resize, crop,
                                           int(scale_255), _stream(frames)))
     return out
+
+
+_image_tables_dev: Dict[tuple, object] = {}       # (h, w, resize, crop, device) -> int32 CUDA tensor
+
+
+def image_tables_device(h: int, w: int, resize: int, crop: int, device):
+    """``transform.image_tables`` on ``device``: built on the host in double once per geometry, uploaded once per device."""
+    import torch
+    from .transform import image_tables
+    key = (int(h), int(w), int(resize), int(crop), str(device))
+    t = _image_tables_dev.get(key)
+    if t is None:
+        if len(_image_tables_dev) >= 64:
+            _image_tables_dev.clear()
+        t = _image_tables_dev[key] = torch.from_numpy(image_tables(*key[:4]).copy()).to(device)
+    return t
+
+
+def preprocess_image(frames, resize: int = 256, crop: int = 224, out_layout: Optional[int] = None, out=None, tables=None):
+    """The image model's per-frame transform on the GPU (``tsm_preprocess_image``: ``ToPILImage -> Resize(resize) ->
+    CenterCrop(crop) -> ToTensor -> Normalize`` of utils/inference_count.py:27-34, Pillow's antialiased 8-bit resample to the
+    bit), one launch.  frames: CUDA uint8 [n,H,W,3]; the channel order is kept as given (the reference feeds cv2's BGR frames
+    to ToPILImage as they are: the caller's business).  Returns float32 in ``out_layout`` (default LAYOUT_NTHWC4), shaped as
+    ``preprocess_frames`` shapes it.  ``tables``: the int32 CUDA table block of this geometry (``transform.image_tables``);
+    built, cached and uploaded here when None."""
+    import torch
+    if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4
+            and frames.shape[3] == 3 and frames.is_contiguous()):
+        raise ValueError('frames must be a contiguous uint8 CUDA tensor [n,H,W,3]')
+    n, h, w, _ = frames.shape
+    layout = _lib.LAYOUT_NTHWC4 if out_layout is None else out_layout
+    pairs = (crop + 1) // 2
+    shapes = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
+              _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4), _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}
+    if layout not in shapes:
+        raise ValueError(f'out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW, got {layout}')
+    if tables is None:
+        tables = image_tables_device(h, w, resize, crop, frames.device)
+    elif not (hasattr(tables, 'is_cuda') and tables.is_cuda and tables.device == frames.device and tables.dtype == torch.int32
+              and tables.dim() == 1 and tables.is_contiguous()):
+        raise ValueError(f'tables must be a contiguous 1-d int32 tensor on {frames.device}')
+    out = _out(out, shapes[layout], torch.float32, frames)
+    _lib.check(_lib.load().tsm_preprocess_image(frames.data_ptr(), n, h, w, tables.data_ptr() if tables.numel() else None,
+                                                tables.numel(), out.data_ptr(), layout, resize, crop, _stream(frames)))
+    return out
+
+
+def frame_votes(logits, history=None, out=None):
+    """The image model's vote on the GPU (``tsm_frame_votes``; utils/inference_count.py:221-231): CUDA float32 logits
+    [n, num_class] -> ``(pred, state, history)``: int32 [n] first arg-max per frame (numpy.argmax's tie rule), int32 [n]
+    0 / 1 = ``sum(last <= 7 preds) >= 4``, and the int32 preds of the last min(6, ...) frames for the next batch.  The sum is
+    over CLASS IDS, exactly as the reference's ``sum(que) >= 4`` -- not repaired for more than two classes.
+    ``history``: int32 CUDA tensor of 0..6 preds of the frames before this batch (what the previous call returned), or None.
+    ``out``: ``(pred [n], state [n], history [6])`` to write into; the history buffer must not be the one passed in.
+    One launch on torch's current stream; no host sync."""
+    import torch
+    _need_cuda_f32(logits=logits)
+    if logits.dim() != 2 or logits.shape[0] == 0 or logits.shape[1] == 0:
+        raise ValueError(f'logits must be [n >= 1, num_class >= 1], got {tuple(logits.shape)}')
+    logits = logits.contiguous()
+    n, c = logits.shape
+    n_hist = 0
+    if history is not None:
+        if not (hasattr(history, 'is_cuda') and history.is_cuda and history.device == logits.device and history.dtype == torch.int32
+                and history.dim() == 1 and history.shape[0] <= 6 and history.is_contiguous()):
+            raise ValueError(f'history must be a contiguous int32 tensor of at most 6 preds on {logits.device}')
+        n_hist = int(history.shape[0])
+    o_pred, o_state, o_hist = out if out is not None else (None, None, None)
+    pred = _out(o_pred, (n,), torch.int32, logits, 'out[0]')
+    state = _out(o_state, (n,), torch.int32, logits, 'out[1]')
+    hist = _out(o_hist, (6,), torch.int32, logits, 'out[2]')
+    if n_hist and hist.data_ptr() == history.data_ptr():
+        raise ValueError('out[2] must not be the history passed in')
+    _lib.check(_lib.load().tsm_frame_votes(logits.data_ptr(), n, c, history.data_ptr() if n_hist else None, n_hist,
+                                           pred.data_ptr(), state.data_ptr(), hist.data_ptr(), _stream(logits)))
+    return pred, state, hist[:min(6, n_hist + n)]
 
 
 def gather_clips(frames, first_frame: int, total_frames: int, first_clip: int, n_clips: int, out=None,

@@ -6,6 +6,8 @@ Counterpart of workoutdetector/utils/inference_count.py for the video-model path
   inference_dataset      :342-421   every video of the selected splits -> {out_dir}/{video}.score.json
   count_by_video_model   :285-339   streaming 8-frame windows -> (count, reps)   [intent, see below]
   pred_to_count          :114-165   (re-exported from .counting)
+  inference_image        :168-189   one frame through the IMAGE model -> scores [num_class]
+  count_by_image_model   :192-243   per-frame scores, vote over the last 7 arg-maxes, pred_to_count(states, step=7)
   save_scores_to_json    :47-67
 
 What differs from the reference, on purpose:
@@ -52,9 +54,9 @@ import numpy as np
 import torch
 
 from . import distributed as tdist
-from .counting import RepCounter, pred_to_count, scores_to_preds  # noqa: F401  (re-export)
+from .counting import RepCounter, pred_to_count, scores_to_preds, vote_states  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
-from .transform import PersonCropTransform, TestTransform, build_test_transform
+from .transform import ImageTransform, PersonCropTransform, TestTransform, build_test_transform
 
 NUM_SEGMENTS = 8
 CLIP_SPAN = 16
@@ -942,3 +944,156 @@ def count_by_video_model(model, frames: Iterable[Union[np.ndarray, torch.Tensor]
         gt = len(ground_truth) // 2
         print(f'count={counter.count}, gt_count={gt}, correct={abs(gt - counter.count) <= 1}')
     return counter.count, list(counter.reps)
+
+
+# ---- the image-model path ------------------------------------------------------------------------------
+def _image_geometry(model) -> Tuple[int, int]:
+    """(resize, crop) of the model's ``data_transform``: what ``create_image_model`` recorded, else the reference's 256 / 224."""
+    return int(getattr(model, 'image_resize', 256)), int(getattr(model, 'image_crop', 224))
+
+
+def _is_image_engine(model) -> bool:
+    return _engine_device(model) is not None and hasattr(model, 'packed_layout')
+
+
+def _frames_u8(frames) -> torch.Tensor:
+    t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
+        raise ValueError(f'frames must be uint8 [n >= 1, H, W, 3], got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def _image_logits_device(model, frames_u8: torch.Tensor) -> torch.Tensor:
+    """Engine path of one batch: pinned staging, ONE ``tsm_preprocess_image`` launch into the engine's packed layout, the
+    forward; returns the CUDA logits [n, num_class] (nothing synchronised)."""
+    from .engine import preprocess_image
+    if getattr(model, 'num_segments', 1) != 1:
+        raise ValueError('the image path needs an engine with num_segments=1 (engine.create_image_model)')
+    need_clip_rows(model, 'inference_images')
+    dev = _engine_device(model)
+    resize, crop = _image_geometry(model)
+    if (model.height, model.width) != (crop, crop):
+        raise ValueError(f'the engine takes {model.height} x {model.width} frames, the transform crops to {crop}')
+    if frames_u8.is_cuda:
+        staged = frames_u8.contiguous()
+    else:
+        flat, slot = _pinned_pool.take(int(frames_u8.numel()))
+        ready = None
+        try:
+            pinned = flat.view(frames_u8.shape)
+            pinned.copy_(frames_u8)
+            staged = pinned.to(dev, non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record()
+        finally:
+            _pinned_pool.release(slot, ready)
+    x = preprocess_image(staged, resize, crop, out_layout=model.packed_layout)
+    n = x.shape[0]
+    return model.forward_device(x.view((n, 1) + tuple(x.shape[1:])), layout=model.packed_layout)
+
+
+def _image_scores_host(model, frames_u8: torch.Tensor, transform: ImageTransform) -> np.ndarray:
+    """Non-engine models: the CPU ``ImageTransform``, then a torch module (``model(x[n,3,H,W])``) or an onnxruntime-style
+    session (one ``run`` per frame on [1,3,H,W], as the reference feeds it)."""
+    x = transform(frames_u8)
+    if hasattr(model, 'run') and hasattr(model, 'get_inputs'):
+        name = model.get_inputs()[0].name
+        return np.stack([np.asarray(model.run(None, {name: x[i:i + 1].numpy()})[0][0], dtype=np.float32)
+                         for i in range(x.shape[0])])
+    with torch.no_grad():
+        p = next(iter(model.parameters()), None) if hasattr(model, 'parameters') else None
+        y = model(x.to(p.device) if p is not None else x)
+    return np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y, dtype=np.float32)
+
+
+def inference_images(model, frames_u8) -> np.ndarray:
+    """The batched form of ``inference_image``: uint8 frames [n,H,W,3] (ndarray or tensor) -> float32 scores [n, num_class].
+    A ``TsmEngine`` (``engine.create_image_model``) stages the frames, does ONE ``tsm_preprocess_image`` launch and the
+    forward (``max_frames`` frames per engine call); any other model takes the CPU ``ImageTransform``.  The channel order is
+    kept as given: the reference hands cv2's BGR frames to its transform as they are -- the caller's business."""
+    frames = _frames_u8(frames_u8)
+    if _is_image_engine(model):
+        return _image_logits_device(model, frames).cpu().numpy()
+    resize, crop = _image_geometry(model)
+    return _image_scores_host(model, frames, ImageTransform(resize, crop))
+
+
+def inference_image(model, frame: np.ndarray) -> np.ndarray:
+    """One frame (H, W, 3) uint8 through the image model -> scores [num_class] float32 (utils/inference_count.py:168-189)."""
+    f = frame if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    return inference_images(model, f[None])[0].astype(np.float32)
+
+
+def _frame_batches(frames, batch: int) -> Iterator[torch.Tensor]:
+    """uint8 [<= batch, H, W, 3] pieces of a [N,H,W,3] array / tensor or of an iterable of HWC frames."""
+    if (isinstance(frames, torch.Tensor) or isinstance(frames, np.ndarray)) and frames.ndim == 4:
+        for a in range(0, int(frames.shape[0]), batch):
+            yield _frames_u8(frames[a:a + batch])
+        return
+    held: List[torch.Tensor] = []
+    for f in frames:
+        held.append(torch.as_tensor(np.asarray(f) if not isinstance(f, torch.Tensor) else f))
+        if len(held) == batch:
+            yield _frames_u8(torch.stack(held))
+            held = []
+    if held:
+        yield _frames_u8(torch.stack(held))
+
+
+def image_states(model, frames, batch_frames: Optional[int] = None,
+                 return_scores: bool = False) -> Tuple[List[int], Optional[np.ndarray]]:
+    """The voted per-frame states (0 / 1) of a video under the image model, and its scores [N, num_class] when asked for:
+    the loop of ``count_by_image_model`` without the count.  A ``TsmEngine`` works in batches of ``batch_frames`` (default:
+    its ``max_clips``): pinned staging, one ``tsm_preprocess_image`` launch, the forward, one ``tsm_frame_votes`` launch with
+    the history of the last 6 arg-maxes carried on the device; states -- and scores -- cross PCIe once, at the end.  Any other
+    model takes the CPU ``ImageTransform`` and the host vote (``counting.vote_states``)."""
+    engine = _is_image_engine(model)
+    batch = int(batch_frames or (getattr(model, 'max_clips', 32) if engine else 32))
+    if batch <= 0:
+        raise ValueError(f'batch_frames must be positive, got {batch_frames}')
+    scores: List = []
+    if engine:
+        from .engine import frame_votes
+        states_dev: List[torch.Tensor] = []
+        history = None
+        for piece in _frame_batches(frames, batch):
+            logits = _image_logits_device(model, piece)
+            _pred, state, history = frame_votes(logits, history)
+            states_dev.append(state)
+            if return_scores:
+                scores.append(logits)
+        states = torch.cat(states_dev).cpu().tolist() if states_dev else []
+        rows = torch.cat(scores).cpu().numpy() if scores else None
+    else:
+        transform = ImageTransform(*_image_geometry(model))
+        states, hist = [], []
+        for piece in _frame_batches(frames, batch):
+            s = _image_scores_host(model, piece, transform)
+            st, hist = vote_states(s.argmax(axis=1).tolist(), hist)
+            states += st
+            scores.append(s)
+        rows = np.concatenate(scores) if scores and return_scores else None
+    return states, rows
+
+
+def count_by_image_model(model, frames: Iterable[Union[np.ndarray, torch.Tensor]], ground_truth: Optional[list] = None,
+                         pred_out_path: Optional[str] = None, threshold: float = 0.1,
+                         batch_frames: Optional[int] = None) -> Tuple[int, List[int]]:
+    """Repetition count of a video with the per-frame image model (utils/inference_count.py:192-243): every frame's scores,
+    a vote over the arg-max of the last 7 frames (``sum(que) >= 4``: over class ids, as the reference sums them), then
+    ``pred_to_count(states, step=7)``.  Returns ``(count, reps)``.
+
+    frames: an iterable of HWC uint8 frames or a [N,H,W,3] array / tensor, as ``count_by_video_model`` takes them (no cv2
+    here; the channel order is kept as given -- the reference reads BGR with cv2 and never converts).
+    The per-batch work is ``image_states``': on a ``TsmEngine`` everything up to the states stays on the GPU and crosses PCIe
+    once, at the end -- and so do the scores, when ``pred_out_path`` is given (``save_scores_to_json(scores, path, '',
+    step=1)``).  ``threshold`` is accepted and unused, as in the reference (:197,:208).  ``video_out_path`` /
+    ``write_to_video`` is out of scope."""
+    states, rows = image_states(model, frames, batch_frames, return_scores=bool(pred_out_path))
+    count, reps = pred_to_count(states, step=7)
+    if ground_truth is not None:
+        gt = len(ground_truth) // 2
+        print(f'count={count} gt_count={gt} correct={abs(count - gt) <= 1}')
+    if pred_out_path:
+        save_scores_to_json([] if rows is None else rows.tolist(), pred_out_path, '', step=1)
+    return count, reps

@@ -16,11 +16,19 @@ Runs as torch ops on whatever device the frames live on (the engine's GPU in the
 ``ConvertImageDtype -> PersonCrop -> Resize((224, 224)) -> Normalize`` (datasets/build.py:123-129,
 datasets/transform.py:226-259), from the detector's boxes on: ``PersonCropTransform``.  The Faster-RCNN detector itself is
 out of scope; the boxes are the caller's (their own detector, a tracker, annotations).
+
+The IMAGE model's transform is a third one (``data_transform``, utils/inference_count.py:27-34): ``ToPILImage -> Resize(256)
+-> CenterCrop(224) -> ToTensor -> Normalize`` -- Pillow's antialiased two-pass resample on uint8, NOT the tensor bilinear
+above.  ``pil_resample_tables`` / ``pil_resize_u8`` / ``ImageTransform`` reproduce it to the bit without Pillow;
+``image_tables`` packs the tables ``tsm_preprocess_image`` takes.
 """
 from __future__ import annotations
 
+import functools
+import math
 from typing import Callable, Mapping, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -147,3 +155,123 @@ def build_test_transform(person_crop: bool = False, scale_255: bool = False, box
                                       'video_name -> boxes (transform.person_box turns detections into such a box)')
         return PersonCropTransform(boxes, scale_255=scale_255)
     return TestTransform(scale_255=scale_255)
+
+
+# ---- the image model's transform: Pillow's 8-bit bilinear resample, to the bit ------------------------------------------
+PRECISION_BITS = 32 - 8 - 2         # Pillow's fixed point: weights are scaled by 2^22
+
+
+def pil_ksize(in_size: int, out_size: int) -> int:
+    """Taps per row of the coefficient table: ``int(ceil(support)) * 2 + 1`` with support = max(in / out, 1)."""
+    return int(math.ceil(max(in_size / out_size, 1.0))) * 2 + 1
+
+
+@functools.lru_cache(maxsize=64)
+def pil_resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's coefficient tables of one axis for the bilinear (triangle) filter on 8-bit channels (Resample.c:
+    ``precompute_coeffs`` + ``normalize_coeffs_8bpc``), computed in double: ``bounds`` int32 [out, 2] = (first source index,
+    taps) and ``kk`` int32 [out, ksize] = the weights, normalised to sum 1, times 2^22, rounded half away from zero, zero
+    behind a row's taps.  The returned arrays are cached and read-only."""
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError(f'sizes must be positive, got {in_size} -> {out_size}')
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    kk = np.zeros((out_size, ksize), dtype=np.int32)
+    ss = 1.0 / filterscale
+    for i in range(out_size):
+        center = (i + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        xmax = min(in_size, int(center + support + 0.5)) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:                             # (Pillow adds the weights in order, in double; sum() may compensate)
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[i] = (xmin, xmax)
+        kk[i, :xmax] = [int(v * (1 << PRECISION_BITS) + (-0.5 if v < 0 else 0.5)) for v in w]
+    bounds.setflags(write=False)
+    kk.setflags(write=False)
+    return bounds, kk
+
+
+def _pil_pass(img: np.ndarray, in_size: int, out_size: int) -> np.ndarray:
+    """One pass along axis 0 of uint8 [in, ...]: u8 = clamp((2^21 + sum(pixel * k)) >> 22, 0, 255)."""
+    bounds, kk = pil_resample_tables(in_size, out_size)
+    out = np.empty((out_size,) + img.shape[1:], dtype=np.uint8)
+    src = img.astype(np.int64)
+    for i in range(out_size):
+        xmin, n = int(bounds[i, 0]), int(bounds[i, 1])
+        acc = np.tensordot(kk[i, :n].astype(np.int64), src[xmin:xmin + n], axes=1) + (1 << (PRECISION_BITS - 1))
+        out[i] = np.clip(acc >> PRECISION_BITS, 0, 255)
+    return out
+
+
+def pil_resize_u8(frame_hwc_u8: np.ndarray, resize: int = 256) -> np.ndarray:
+    """``Resize(resize)`` of torchvision on a PIL image = ``Image.resize((nw, nh), BILINEAR)`` of Pillow, in NumPy: uint8
+    [H, W, C] -> uint8 [nh, nw, C] with the shorter side ``resize`` and the longer ``int(resize * long / short)``; the
+    horizontal pass first, rounded to uint8, then the vertical one; a pass whose axis keeps its size is skipped."""
+    img = np.asarray(frame_hwc_u8)
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise ValueError(f'frame must be uint8 [H, W, C], got {img.dtype} {img.shape}')
+    h, w = img.shape[:2]
+    nh, nw = resized_hw(h, w, resize)
+    if nw != w:
+        img = _pil_pass(img.transpose(1, 0, 2), w, nw).transpose(1, 0, 2)
+    if nh != h:
+        img = _pil_pass(img, h, nh)
+    return np.ascontiguousarray(img)
+
+
+@functools.lru_cache(maxsize=64)
+def image_tables(h: int, w: int, resize: int = 256, crop: int = INPUT_SIZE) -> np.ndarray:
+    """The table block ``tsm_preprocess_image`` takes for h x w frames (include/tsm_hip.h): int32, rows of the crop window's
+    output indices only -- [hb crop x 2][hk crop x ksx] when the width changes, then [vb crop x 2][vk crop x ksy] when the
+    height does; empty when neither does.  A few KB per geometry, cached; the engine uploads it once per device."""
+    nh, nw = resized_hw(h, w, resize)
+    if crop > nh or crop > nw:
+        raise ValueError(f'crop {crop} larger than the resized frame {nh} x {nw}')
+    top, left = crop_offsets(nh, nw, crop)
+    parts = []
+    for size, new, first in ((w, nw, left), (h, nh, top)):
+        if new != size:
+            bounds, kk = pil_resample_tables(size, new)
+            parts += [bounds[first:first + crop].reshape(-1), kk[first:first + crop].reshape(-1)]
+    block = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    block.setflags(write=False)
+    return block
+
+
+class ImageTransform:
+    """``data_transform`` of the image model (utils/inference_count.py:27-34) on the CPU, for models that are not engines:
+    uint8 frames [n, H, W, 3] (or one [H, W, 3]; ndarray or tensor) -> float32 tensor [n, 3, crop, crop] = ``ToPILImage ->
+    Resize(resize) -> CenterCrop(crop) -> ToTensor -> Normalize(ImageNet)``, built on ``pil_resize_u8``: no Pillow at run
+    time.  The channel order is kept as given: the reference feeds cv2's BGR frames straight into ToPILImage, so whatever
+    order the model was trained on is the caller's business.  A ``TsmEngine`` runs the same in one launch per batch
+    (``engine.preprocess_image``)."""
+
+    def __init__(self, resize: int = 256, crop: int = INPUT_SIZE):
+        self.resize, self.crop = int(resize), int(crop)
+
+    def crop_u8(self, frame_hwc_u8: np.ndarray) -> np.ndarray:
+        """uint8 [crop, crop, C]: the resized frame's centre window."""
+        img = pil_resize_u8(frame_hwc_u8, self.resize)
+        if self.crop > img.shape[0] or self.crop > img.shape[1]:
+            raise ValueError(f'crop {self.crop} larger than the resized frame {img.shape[0]} x {img.shape[1]}')
+        top, left = crop_offsets(img.shape[0], img.shape[1], self.crop)
+        return img[top:top + self.crop, left:left + self.crop]
+
+    def __call__(self, frames_u8) -> torch.Tensor:
+        a = frames_u8.cpu().numpy() if isinstance(frames_u8, torch.Tensor) else np.asarray(frames_u8)
+        if a.ndim == 3:
+            a = a[None]
+        u8 = np.stack([self.crop_u8(f) for f in a])
+        x = u8.astype(np.float32) / np.float32(255.0)
+        x = (x - np.float32(MEAN)) / np.float32(STD)
+        return torch.from_numpy(np.ascontiguousarray(x.transpose(0, 3, 1, 2)))
+
+    def __repr__(self):
+        return f'ImageTransform(ToPILImage, Resize({self.resize}), CenterCrop({self.crop}), ToTensor, Normalize(ImageNet))'

@@ -154,6 +154,34 @@ def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
     return OrderedDict(('.'.join(k.split('.')[1:]), v) for k, v in items.items())
 
 
+def remap_torchvision_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, object]':
+    """A plain torchvision ResNet ``state_dict`` (``conv1.weight``, ``bn1.*``, ``layer1.0.conv1.weight``, ..., ``fc.*``: the
+    image model, image_classification.py:214 -- ``resnet18`` with a replaced ``fc``) -> engine keys: the backbone under
+    ``base_model.``, ``fc.*`` as it is.  A Lightning ``state_dict`` carries one leading component on every key
+    (``model.conv1.weight``): it is stripped when every key has the same one and ``conv1.weight`` is not already there.
+    ``num_batches_tracked`` buffers pass through (the engine ignores them); anything else that is not a ResNet key raises."""
+    keys = list(state_dict.keys())
+    if not keys:
+        raise ValueError('empty state dict')
+    strip = 0
+    if 'conv1.weight' not in state_dict:
+        heads = {k.split('.', 1)[0] for k in keys}
+        if len(heads) != 1 or f'{next(iter(heads))}.conv1.weight' not in state_dict:
+            raise ValueError('not a torchvision ResNet state dict: no conv1.weight, with or without one leading component')
+        strip = len(next(iter(heads))) + 1
+    out: 'OrderedDict[str, object]' = OrderedDict()
+    for k, v in state_dict.items():
+        name = k[strip:]
+        head = name.split('.', 1)[0]
+        if head == 'fc':
+            out[name] = v
+        elif head in ('conv1', 'bn1') or (head.startswith('layer') and head[5:].isdigit()):
+            out['base_model.' + name] = v
+        else:
+            raise ValueError(f'{k}: not a key of a torchvision ResNet')
+    return out
+
+
 def is_mmaction_state_dict(state_dict: Mapping[str, object]) -> bool:
     """mmaction2 ``Recognizer2D`` checkpoints (the reference's ``--mmlab`` branch, utils/inference_count.py:516-519,
     configs/tsm_MultiActionRepCount_sthv2.py:5-22) name their parts ``backbone.*`` / ``cls_head.*``."""

@@ -27,12 +27,17 @@
  *   tsm_gather_clips       the loop's clip windows: video[i:i + 16:2] for i in range(0, len(video), 8), zero-padded tail
  *   tsm_preprocess_clips   build_test_transform(person_crop=True) from the detector's box on: PersonCrop -> Resize((224, 224))
  *                          -> Normalize, fused with the clip windows   datasets/build.py:123-129, datasets/transform.py:247-259
+ *   tsm_preprocess_indexed build_test_transform(person_crop=False) over FrameDataset's sampled frames: one launch from staged raw
+ *                          frames through a device index table (sample_frames(total, 8, start, random=False) per labelled
+ *                          segment)   datasets/common.py:99-117, datasets/transform.py:16-65, datasets/build.py:131-136
  *   tsm_scores_to_states   per clip: to_softmax, first arg-max, score >= 0.5 ? class : -1
  *                          workoutdetector/utils/eval.py:153-164, utils/visualize.py:140-150
  *   tsm_preprocess_image   data_transform of the image model: ToPILImage -> Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize
  *                          (Pillow's antialiased resample, to the bit)   workoutdetector/utils/inference_count.py:27-34,168-189
  *   tsm_frame_votes        count_by_image_model's vote: arg-max per frame, deque of 7, sum(que) >= 4
  *                          workoutdetector/utils/inference_count.py:221-231
+ *   tsm_top1_tally         the comparison of the accuracy loop: arg-max == label, counted per class (the loop's intent: the
+ *                          snapshot compares a logits row and never counts the totals)   scripts/eval_classification.py:42-49
  *
  * Conventions
  *   - Plain pointers and sizes only; no torch / HIP types in signatures.  hip streams travel as
@@ -63,7 +68,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips, tsm_preprocess_image, tsm_frame_votes (all four added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips, tsm_preprocess_image, tsm_frame_votes, tsm_preprocess_indexed, tsm_top1_tally (all six added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -372,6 +377,27 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
                          int32_t clip_stride, const int32_t *boxes, float *out, int32_t out_layout, int32_t size,
                          int32_t scale_255, void *stream);
 
+/* The centre-crop test transform through a DEVICE index table (device pointers), straight from staged RAW frames to the
+ * input of tsm_forward in ONE launch -- the access pattern of the reference's FrameDataset (datasets/common.py:99-117), which
+ * samples 8 frames per labelled segment with sample_frames(total, 8, start, random=False) (datasets/transform.py:16-65):
+ * irregular lists (a segment shorter than 8 frames repeats frames, two segments of one video share no window, unsampled
+ * frames are never needed) that the regular windows of tsm_gather_clips / tsm_preprocess_clips cannot express.
+ * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255): whatever frames the caller staged.
+ * index:  DEVICE int32 [n_clips * n_segment], buffer-frame numbers.
+ * out:    [n_clips, n_segment, ...one frame] in out_layout; out_layout, resize, crop, scale_255 as tsm_preprocess.
+ *   out[c][k] = tsm_preprocess' result for buffer frame index[c * n_segment + k] (build_test_transform(person_crop=False):
+ *   ATen bilinear, no antialias, centre crop, normalise) -- the same per-pixel code, so the row equals that frame's row from
+ *   tsm_preprocess bit for bit.
+ * Validated on the host before the launch (TSM_ERR_INVALID_ARG, nothing launched): non-NULL pointers, positive sizes, pixel
+ * type and layout, crop no larger than the resized frame -- exactly tsm_preprocess' checks.  The TABLE cannot be validated
+ * (device memory): the kernel is total in it.  An entry outside [0, n_frames) -- INT32_MIN and INT32_MAX included -- reads
+ * nothing and yields the normalised zero frame, every channel (0 - mean) / std, as tsm_preprocess_clips' padded tail does;
+ * a frame address is formed in 64 bits, and only after the range test.  One grid-stride launch: n_clips is not limited by the
+ * launch geometry.  Enqueues on `stream`; no synchronisation. */
+int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, const int32_t *index,
+                           int32_t n_clips, int32_t n_segment, float *out, int32_t out_layout, int32_t resize, int32_t crop,
+                           int32_t scale_255, void *stream);
+
 /* feat [n_clips*T, hw, c] NHWC -> logits [n_clips, num_class]; fc_w [num_class, c], fc_b. */
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits,
              int32_t n_clips, int32_t n_segment, int32_t hw, int32_t c, int32_t num_class,
@@ -429,6 +455,19 @@ int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, co
  * unspecified).  One launch, no host synchronisation, on `stream`. */
 int tsm_frame_votes(const float *logits, int32_t n_frames, int32_t num_class, const int32_t *history, int32_t n_hist,
                     int32_t *pred, int32_t *state, int32_t *history_out, void *stream);
+
+/* The accuracy tally on the GPU (device pointers)   scripts/eval_classification.py:42-49, its intent (the snapshot compares a
+ * logits row with the label and never increments class_total):
+ *   logits [n, num_class] fp32, labels [n] DEVICE int32 -> pred [n] int32 (nullable), the FIRST arg-max of every row
+ *   (tsm_frame_votes' tie rule), and per class the counters correct [num_class] / total [num_class] (int32), which
+ *   ACCUMULATE: for a label in [0, num_class) total[label] += 1 and correct[label] += (pred == label); any other label is
+ *   counted nowhere (the kernel is total in the labels).  The caller zeroes the counters once and reads them once per
+ *   dataset; correct and total must not alias (TSM_ERR_INVALID_ARG).
+ * One launch of one workgroup: per-launch counts in LDS, then one thread per class adds them to the global counters with an
+ * ordinary load, add and store -- launches on one stream are ordered, so calls that share counters must share a stream.
+ * num_class <= 1024, else TSM_ERR_UNSUPPORTED.  Inputs are finite.  No host synchronisation, on `stream`. */
+int tsm_top1_tally(const float *logits, const int32_t *labels, int32_t n, int32_t num_class, int32_t *pred, int32_t *correct,
+                   int32_t *total, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@
 //   tsm_front.hip      front_s2_kernel: shift + conv1 + stride-2 conv2 of layer2.0 per launch (bf16)
 //   tsm_fused23.hip    conv23_fused_kernel: conv2 + conv3 + residual per launch (fp32 / split-bf16)
 //   tsm_stem.hip       stem_direct / stem_pool[_f32]: the 7x7 stem with the max-pool fused behind it
-//   tsm_ops.hip        pack / convert / preprocess / gather_clips / preprocess_clips / maxpool / shift / head / scores_to_states, device_info()
+//   tsm_ops.hip        pack / convert / preprocess / gather_clips / preprocess_clips / preprocess_indexed / maxpool / shift / head / scores_to_states / top1_tally, device_info()
 #pragma once
 #include "tsm_kernels.h"
 

@@ -1825,6 +1825,49 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
   return TSM_OK;
 }
 
+int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, const int32_t *index,
+                           int32_t n_clips, int32_t n_segment, float *out, int32_t out_layout, int32_t resize, int32_t crop,
+                           int32_t scale_255, void *stream) {
+  if (!frames || !index || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: null pointer");
+  if (n_frames <= 0 || h <= 0 || w <= 0 || n_clips <= 0 || n_segment <= 0 || resize <= 0 || crop <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: non-positive size");
+  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
+      out_layout != TSM_LAYOUT_NTHWC8B)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  tsm::IndexedPreprocParams q{};
+  tsm::PreprocParams &p = q.pp;
+  q.index = index; q.n_frames = n_frames; q.n_rows = (int64_t)n_clips * n_segment;
+  p.src = frames; p.dst = out; p.h = h; p.w = w;
+  // the geometry of tsm_preprocess: Resize(int), then CenterCrop with Python's round-half-to-even
+  if (h <= w) { p.nh = resize; p.nw = (int)((double)resize * w / h); }
+  else { p.nh = (int)((double)resize * h / w); p.nw = resize; }
+  if (crop > p.nh || crop > p.nw) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: crop larger than the resized frame");
+  p.top = (int)std::nearbyint((p.nh - crop) / 2.0);
+  p.left = (int)std::nearbyint((p.nw - crop) / 2.0);
+  p.crop = crop;
+  p.src_is_u8 = pixel == TSM_PIXEL_U8;
+  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
+               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
+  p.pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  hipError_t st = tsm::launch_preprocess_indexed(q, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
+                                    std::string("preprocess_indexed: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
+int tsm_top1_tally(const float *logits, const int32_t *labels, int32_t n, int32_t num_class, int32_t *pred, int32_t *correct,
+                   int32_t *total, void *stream) {
+  if (!logits || !labels || !correct || !total || n <= 0 || num_class <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "top1_tally: NULL pointer or non-positive size");
+  if (correct == total) return fail(nullptr, TSM_ERR_INVALID_ARG, "top1_tally: correct and total must not alias");
+  if (num_class > tsm::kTallyMaxClass)
+    return fail(nullptr, TSM_ERR_UNSUPPORTED, "top1_tally: num_class must be at most " + std::to_string(tsm::kTallyMaxClass));
+  hipError_t st = tsm::launch_top1_tally(logits, labels, n, num_class, pred, correct, total, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("top1_tally: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
 // taps per row of Pillow's coefficient table for one axis (Resample.c precompute_coeffs: ksize = ceil(support) * 2 + 1)
 static int pil_ksize(int in, int out) {
   const double scale = (double)in / out, support = scale < 1.0 ? 1.0 : scale;

@@ -226,6 +226,17 @@ struct ClipPreprocParams {
 };
 hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s);
 
+// The centre-crop test transform through a device index table (see preprocess_indexed_kernel): staged raw frames
+// [n_frames,h,w,3] u8|f32 -> out row r = launch_preprocess' result for buffer frame index[r], r < n_rows = n_clips * n_segment,
+// in any out_mode.  `pp` is launch_preprocess' geometry (pp.n is not used); the kernel is total in the TABLE contents, which
+// live in device memory: an entry outside [0, n_frames) reads nothing and yields the normalised zero frame.
+struct IndexedPreprocParams {
+  PreprocParams pp;
+  const int *index;   // device, [n_rows] buffer-frame numbers
+  int64_t n_frames, n_rows;
+};
+hipError_t launch_preprocess_indexed(const IndexedPreprocParams &p, hipStream_t s);
+
 // The image model's per-frame transform (see preprocess_image_kernel): staged uint8 frames [n,h,w,3] -> Pillow's antialiased
 // bilinear resize to nh x nw (integer arithmetic from host-built tables), the crop window (top, left, crop) of it, normalised
 // and packed in any out_mode of PreprocParams.  Tables (device int32, rows for the crop window's output indices only):
@@ -251,6 +262,13 @@ hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s);
 // min(6, n_hist + n) afterwards.
 hipError_t launch_frame_votes(const float *logits, int n, int c, const int *hist_in, int n_hist, int *pred, int *state,
                               int *hist_out, hipStream_t s);
+
+// Accuracy tally (see top1_tally_kernel): pred [n] (nullable) = first arg-max of logits [n, c]; for a label in [0, c):
+// total[label] += 1, correct[label] += (pred == label); any other label is counted nowhere.  correct / total [c] ACCUMULATE.
+// c <= kTallyMaxClass, else hipErrorNotSupported.
+constexpr int kTallyMaxClass = 1024;
+hipError_t launch_top1_tally(const float *logits, const int *labels, int n, int c, int *pred, int *correct, int *total,
+                             hipStream_t s);
 
 hipError_t launch_maxpool3x3s2(const float *x, float *y, int n, int hi, int wi, int c, int prec,
                                hipStream_t s);

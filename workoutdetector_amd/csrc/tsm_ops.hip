@@ -168,12 +168,19 @@ hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStre
 // out = h0*(w0*p00 + w1*p01) + h1*(w0*p10 + w1*p11); then (v*pre_scale - mean)/std.
 // datasets/build.py:131-136 of the reference (torchvision tensor transforms).
 // ---------------------------------------------------------------------------------------------
+// The arithmetic of a pixel is spelled out -- contraction off, the three fused steps written as fmaf -- so that EVERY inlined
+// copy of this function computes the same bits: left to the compiler, the second pixel of a pixel pair rounded the other
+// product of each bilinear sum (fma(w0, p00, w1 * p01) where the first pixel had fma(w1, p01, w0 * p00)), so a pair layout's
+// odd pixels were one fp32 ulp of the interpolated value away from the fp32 layouts' -- after the mean is subtracted, up to
+// 1e-4 relative on a value near zero.  Now NTHWC8S / NTHWC8B hold the split / the rounding of exactly the numbers NTHWC4 and
+// NTCHW hold, in preprocess_kernel and in preprocess_indexed_kernel alike.
 template <typename T>
 __device__ __forceinline__ void preprocess_pixel(const PreprocParams &p, const T *frame, int cy, int cx, float *v) {
+#pragma clang fp contract(off)
   const float sh = (float)p.h / (float)p.nh, sw = (float)p.w / (float)p.nw;
   const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-  float fy = sh * ((float)(cy + p.top) + 0.5f) - 0.5f;
-  float fx = sw * ((float)(cx + p.left) + 0.5f) - 0.5f;
+  float fy = __builtin_fmaf(sh, (float)(cy + p.top) + 0.5f, -0.5f);      // (fused, as every copy had it before)
+  float fx = __builtin_fmaf(sw, (float)(cx + p.left) + 0.5f, -0.5f);
   fy = fy < 0.f ? 0.f : fy;
   fx = fx < 0.f ? 0.f : fx;
   const int y0 = (int)fy, x0 = (int)fx;
@@ -184,8 +191,10 @@ __device__ __forceinline__ void preprocess_pixel(const PreprocParams &p, const T
   for (int c = 0; c < 3; ++c) {
     const float p00 = (float)r0[x0 * 3 + c], p01 = (float)r0[x1 * 3 + c];
     const float p10 = (float)r1[x0 * 3 + c], p11 = (float)r1[x1 * 3 + c];
-    const float t = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11);
-    v[c] = (t * p.pre_scale - mean[c]) / stdv[c];
+    // h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), then (t * pre_scale - mean) / std
+    const float row0 = __builtin_fmaf(w1, p01, w0 * p00), row1 = __builtin_fmaf(w1, p11, w0 * p10);
+    const float t = __builtin_fmaf(h1, row1, h0 * row0);
+    v[c] = __builtin_fmaf(t, p.pre_scale, -mean[c]) / stdv[c];
   }
 }
 
@@ -416,6 +425,81 @@ hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
     TSM_KLAUNCH(preprocess_clips_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, p);
   else
     TSM_KLAUNCH(preprocess_clips_kernel<float>, dim3(grid), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// preprocess_indexed: the centre-crop test transform (preprocess_kernel: build_test_transform(person_crop=False)) through a
+// DEVICE index table, one launch from the staged RAW frames to the engine's packed input: out row r = the transform of
+// buffer frame index[r].  This is the access pattern of the reference's FrameDataset (datasets/common.py:99-117:
+// sample_frames(total, 8, start, random=False) per labelled segment): irregular lists -- a segment shorter than 8 frames
+// repeats frames, two segments of one video share no window, unsampled frames are never needed -- that the regular windows
+// of gather_clips / preprocess_clips (step * c + stride * k) cannot express.  A frame two rows share is transformed twice:
+// the rows are independent, and the alternative (transform each staged frame once, then gather) is a second pass and a
+// transformed intermediate in memory.
+// The pixel is preprocess_pixel's, so a row equals preprocess_kernel's row for the same frame bit for bit.
+// TOTAL in the table: it lives in device memory, so no host check can see it; for ANY int32 contents the kernel reads only
+// inside the frames it was given -- the entry is range-tested first, and only then widened to 64 bits and multiplied into a
+// frame address.  An entry outside [0, n_frames) reads nothing and yields the normalised zero frame (0 - mean) / std, as
+// preprocess_clips' padded tail does.
+// One thread per output group as in preprocess_kernel; the table entry is one dword, the same for (nearly) every thread of a wave.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) preprocess_indexed_kernel(const IndexedPreprocParams q) {
+  const PreprocParams &p = q.pp;
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int wg = (p.crop + px - 1) / px;
+  const int64_t per_frame = (int64_t)wg * p.crop;
+  const int64_t total = q.n_rows * per_frame;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const T *src = static_cast<const T *>(p.src);
+  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int gx = (int)(i % wg);
+    const int cy = (int)((i / wg) % p.crop);
+    const int64_t f = i / per_frame;             // (clip, segment) row of the output
+    const int j = q.index[f];
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (j >= 0 && (int64_t)j < q.n_frames) {
+      const T *frame = src + (int64_t)j * p.h * p.w * 3;
+      preprocess_pixel<T>(p, frame, cy, gx * px, v);
+      if (px == 2 && gx * 2 + 1 < p.crop) preprocess_pixel<T>(p, frame, cy, gx * 2 + 1, v + 4);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        v[ch] = (0.f - mean[ch]) / stdv[ch];
+        if (px == 2 && gx * 2 + 1 < p.crop) v[4 + ch] = v[ch];
+      }
+    }
+    if (p.out_mode == 1) {
+      float *o = p.dst + f * 3 * (int64_t)p.crop * p.crop + (int64_t)cy * p.crop + gx;
+      o[0] = v[0];
+      o[(int64_t)p.crop * p.crop] = v[1];
+      o[2 * (int64_t)p.crop * p.crop] = v[2];
+    } else if (p.out_mode == 2) {
+      store_group<kPrecBf16x3>(p.dst + i * 8, v);
+    } else if (p.out_mode == 3) {
+      store_group<kPrecBf16>(p.dst + i * 4, v);
+    } else {
+      store_group<kPrecF32>(p.dst + i * 4, v);
+    }
+  }
+}
+
+hipError_t launch_preprocess_indexed(const IndexedPreprocParams &q, hipStream_t s) {
+  const PreprocParams &p = q.pp;
+  // launch_preprocess' checks on the geometry, and the table's own
+  if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || p.h <= 0 || p.w <= 0 || p.crop <= 0 || p.top < 0 ||
+      p.left < 0 || p.top + p.crop > p.nh || p.left + p.crop > p.nw || p.out_mode < 0 || p.out_mode > 3)
+    return hipErrorInvalidValue;
+  // one grid-stride launch covers a table of any length (64-bit group index): nothing of the launch geometry limits n_clips
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int64_t total = q.n_rows * p.crop * ((p.crop + px - 1) / px);
+  const unsigned grid = grid_for(total, 8192);
+  if (p.src_is_u8)
+    TSM_KLAUNCH(preprocess_indexed_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, q);
+  else
+    TSM_KLAUNCH(preprocess_indexed_kernel<float>, dim3(grid), dim3(256), 0, s, q);
   return hipGetLastError();
 }
 
@@ -897,6 +981,50 @@ hipError_t launch_frame_votes(const float *logits, int n, int c, const int *hist
       (hist_out && hist_out == hist_in))
     return hipErrorInvalidValue;
   TSM_KLAUNCH(frame_votes_kernel, dim3((n + 63) / 64), dim3(64), 0, s, logits, n, c, hist_in, n_hist, pred, state, hist_out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// top1_tally: the comparison of scripts/eval_classification.py on the device -- per row the FIRST arg-max of its logits
+// (frame_votes' tie rule), compared with the row's label, counted per class: total[label] += 1, correct[label] += (pred ==
+// label).  The reference's loop (:42-46) compares a logits row with the label and never increments class_total; this is its
+// intent.  The counters ACCUMULATE over the batches of a dataset: the caller zeroes them once and reads them once, so a
+// batch leaves 4 bytes per sample (pred) and nothing else to fetch.
+// ONE workgroup of 1024 threads: the rows go round the threads (n x c is tiny: a batch of clips), the launch's own counts
+// are LDS atomics, then thread c adds class c's two sums to the global counters with an ordinary load, add and (vector) store.
+// Launches on one stream are ordered and a launch has one workgroup, so no two threads ever touch one global counter: no
+// global atomic is needed.  TOTAL in the labels (device memory): a label outside [0, c) indexes nothing and is counted nowhere.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kTallyMaxClass) top1_tally_kernel(const float *__restrict__ logits,
+                                                                    const int *__restrict__ labels, int n, int c,
+                                                                    int *__restrict__ pred, int *__restrict__ correct,
+                                                                    int *__restrict__ total) {
+  __shared__ int n_correct[kTallyMaxClass], n_total[kTallyMaxClass];
+  const int t = threadIdx.x;
+  n_correct[t] = 0;
+  n_total[t] = 0;
+  __syncthreads();
+  for (int i = t; i < n; i += kTallyMaxClass) {
+    const int a = first_argmax(logits + (size_t)i * c, c);
+    if (pred) pred[i] = a;
+    const int l = labels[i];
+    if (l >= 0 && l < c) {
+      atomicAdd(&n_total[l], 1);
+      if (a == l) atomicAdd(&n_correct[l], 1);
+    }
+  }
+  __syncthreads();
+  if (t < c) {
+    correct[t] += n_correct[t];
+    total[t] += n_total[t];
+  }
+}
+
+hipError_t launch_top1_tally(const float *logits, const int *labels, int n, int c, int *pred, int *correct, int *total,
+                             hipStream_t s) {
+  if (!logits || !labels || !correct || !total || n <= 0 || c <= 0) return hipErrorInvalidValue;
+  if (c > kTallyMaxClass) return hipErrorNotSupported;
+  TSM_KLAUNCH(top1_tally_kernel, dim3(1), dim3(kTallyMaxClass), 0, s, logits, labels, n, c, pred, correct, total);
   return hipGetLastError();
 }
 

@@ -705,6 +705,65 @@ def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_c
     return out
 
 
+def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_255: bool = True, layout: Optional[int] = None,
+                       out=None):
+    """The centre-crop test transform through a device index table (``tsm_preprocess_indexed``), one launch from staged raw
+    frames to the engine's input: the access pattern of the reference's ``FrameDataset`` (``sample_frames`` per labelled
+    segment: irregular lists, repeated frames, no shared windows).
+
+    frames: contiguous CUDA uint8 or float32 [n,H,W,3] (values 0..255), whatever frames the caller staged.  index: contiguous
+    CUDA int32 [n_clips, n_segment] of buffer-frame numbers.  Returns float32 [n_clips, n_segment, ...one frame] in the
+    layouts of ``preprocess_frames`` (default LAYOUT_NTHWC4); row (c, k) equals ``preprocess_frames``' row for frame
+    ``index[c, k]`` bit for bit.  An entry outside [0, n) reads nothing and yields the normalised zero frame (0 - mean) / std
+    -- the kernel is total in the table; validate the table on the host where a wrong entry should be an error."""
+    import torch
+    if not hasattr(frames, 'is_cuda') or frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f'frames must be a uint8 or float32 tensor, got {getattr(frames, "dtype", type(frames))}')
+    pixel = _lib.PIXEL_U8 if frames.dtype == torch.uint8 else _lib.PIXEL_F32
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0 or not frames.is_cuda or not frames.is_contiguous():
+        raise ValueError('frames must be a contiguous CUDA tensor [n >= 1,H,W,3]')
+    n, h, w, _ = frames.shape
+    if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
+            and index.dim() == 2 and index.shape[0] > 0 and index.shape[1] > 0 and index.is_contiguous()):
+        raise ValueError(f'index must be a contiguous int32 tensor [n_clips >= 1, n_segment >= 1] on {frames.device}')
+    n_clips, n_segment = (int(d) for d in index.shape)
+    if layout is None:
+        layout = _lib.LAYOUT_NTHWC4
+    pairs = (crop + 1) // 2
+    shapes = {_lib.LAYOUT_NTHWC4: (crop, crop, 4), _lib.LAYOUT_NTHWC8S: (crop, pairs, 8), _lib.LAYOUT_NTHWC8B: (crop, pairs, 4),
+              _lib.LAYOUT_NTCHW: (3, crop, crop)}
+    if layout not in shapes:
+        raise ValueError(f'layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW, got {layout}')
+    out = _out(out, (n_clips, n_segment) + shapes[layout], torch.float32, frames)
+    _lib.check(_lib.load().tsm_preprocess_indexed(frames.data_ptr(), pixel, n, h, w, index.data_ptr(), n_clips, n_segment,
+                                                  out.data_ptr(), layout, int(resize), int(crop), int(scale_255),
+                                                  _stream(frames)))
+    return out
+
+
+def top1_tally(logits, labels, correct, total, out=None):
+    """The accuracy tally on the GPU (``tsm_top1_tally``; the intent of scripts/eval_classification.py:42-49): CUDA float32
+    logits [n, num_class] and int32 labels [n] -> int32 ``pred`` [n], the first arg-max per row (numpy.argmax's tie rule),
+    while the int32 counters ``correct`` / ``total`` [num_class] ACCUMULATE ``pred == label`` / 1 under every label in
+    [0, num_class); any other label is counted nowhere.  Zero the counters once, call this once per batch (on one stream),
+    read them once.  ``out``: the pred tensor to write into.  One launch on torch's current stream; no host sync."""
+    import torch
+    _need_cuda_f32(logits=logits)
+    if logits.dim() != 2 or logits.shape[0] == 0 or logits.shape[1] == 0 or not logits.is_contiguous():
+        raise ValueError(f'logits must be contiguous [n >= 1, num_class >= 1], got {tuple(logits.shape)}')
+    n, c = (int(d) for d in logits.shape)
+    for name, t, shape in (('labels', labels, (n,)), ('correct', correct, (c,)), ('total', total, (c,))):
+        if not (hasattr(t, 'is_cuda') and t.is_cuda and t.device == logits.device and t.dtype == torch.int32
+                and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError(f'{name} must be a contiguous int32 tensor of shape {shape} on {logits.device}')
+    if correct.data_ptr() == total.data_ptr():
+        raise ValueError('correct and total must be two tensors')
+    pred = _out(out, (n,), torch.int32, logits)
+    _lib.check(_lib.load().tsm_top1_tally(logits.data_ptr(), labels.data_ptr(), n, c, pred.data_ptr(), correct.data_ptr(),
+                                          total.data_ptr(), _stream(logits)))
+    return pred
+
+
 def scores_to_states(logits, threshold: float = 0.5, softmax: bool = True, return_top: bool = False, out=None, out_top=None):
     """K9 on the GPU: CUDA float32 logits [n, num_class] -> int32 states [n] (utils/eval.py:153-164: softmax, first
     arg-max, class id if its score >= threshold else -1) and optionally the winning score.  Enqueues on torch's

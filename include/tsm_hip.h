@@ -38,6 +38,11 @@
  *                          workoutdetector/utils/inference_count.py:221-231
  *   tsm_top1_tally         the comparison of the accuracy loop: arg-max == label, counted per class (the loop's intent: the
  *                          snapshot compares a logits row and never counts the totals)   scripts/eval_classification.py:42-49
+ *   tsm_forward_features   cnn_feature / video_feature: timm.create_model(name, num_classes=0)(frames) -> the pooled vector of
+ *                          every frame   workoutdetector/utils/common.py:79-116
+ *   tsm_pool_features      the global average pool such a model ends in, and sklearn's normalize() of its rows
+ *   tsm_cosine_distances   plot_sim: pairwise_distances(feats, metric='cosine'), the temporal self-similarity matrix
+ *                          workoutdetector/utils/common.py:118-143
  *
  * Conventions
  *   - Plain pointers and sizes only; no torch / HIP types in signatures.  hip streams travel as
@@ -68,7 +73,7 @@
 extern "C" {
 #endif
 
-#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips, tsm_preprocess_image, tsm_frame_votes, tsm_preprocess_indexed, tsm_top1_tally (all six added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
+#define TSM_ABI_VERSION 7 /* 7: tsm_build_id, tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_consensus, tsm_head_segments, tsm_preprocess_clips, tsm_preprocess_image, tsm_frame_votes, tsm_preprocess_indexed, tsm_top1_tally, tsm_forward_features, tsm_pool_features, tsm_cosine_distances (all nine added later within 7: no existing entry point changed), tsm_set_shift_place, tsm_conv_op, tsm_trace_launches / tsm_launch_trace; 6: tsm_tune, per-user default tune cache; 5: tsm_gather_clips; 4: tsm_scores_to_states; tile codes lost the tail field; TSM_* variables read in tsm_create only */
 
 typedef enum tsm_status {
   TSM_OK = 0,
@@ -205,6 +210,20 @@ int tsm_finalize(tsm_engine *e);
  *         [clip][segment][class]: the caller's buffer must hold that many. */
 int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips,
                 float *logits, void *stream);
+
+/* Frame embeddings: tsm_forward with the head replaced by ONE pool_feat_kernel launch -- the reference's classifier-free
+ * route, utils/common.py:79-116 (a ResNet with num_classes=0 over every frame, the pooled vector per frame).
+ * features: float32 [n_clips * num_segments, feat_dim] in the same memkind (feat_dim = 2048; 512 for resnet18 / resnet34):
+ *           row f = mean over the pixels of frame f's last block output when normalize == 0, that row divided by its
+ *           Euclidean norm (a norm of 0 counts as 1: an all-zero row stays all-zero, sklearn.preprocessing.normalize)
+ *           otherwise.  A frame's pooled value is the avg head's d_pooled to the bit.
+ * Everything else is tsm_forward's contract word for word: the first call of a bucket tunes (the tune cache and the tile
+ * choices are shared with tsm_forward; no conv launch differs), later calls only enqueue and are capture-safe, n_clips <=
+ * max_clips, TSM_MEM_HOST copies and synchronises.  Legal on any finalized engine whatever its consensus, backbone, shift
+ * placement or dtype (a shifted engine yields shift-aware per-frame embeddings); the pool launch takes the head's timing
+ * slot. */
+int tsm_forward_features(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips,
+                         float *features, int32_t normalize, void *stream);
 
 /* Tune the kernels of the bucket `n_clips` falls into NOW (synchronous: a few hundred ms of timed launches on the
  * engine's own zeroed input buffer; no caller memory is touched), or read the choices from the tune cache file: what
@@ -408,6 +427,28 @@ int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *log
  * c % 8 == 0 and c <= 2048, else TSM_ERR_UNSUPPORTED.  Enqueues on `stream`; no synchronisation. */
 int tsm_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int32_t n_frames,
                       int32_t hw, int32_t c, int32_t num_class, void *stream);
+
+/* The pool of tsm_forward_features on its own (device pointers): feat [n_frames, hw, c] NHWC fp32 -> pooled [n_frames, c] =
+ * mean_hw feat[f] (tsm_head's pooled value to the bit) and unit [n_frames, c] = pooled[f] / ||pooled[f]||2 (a norm of 0
+ * counts as 1).  Either output may be NULL, both NULL is TSM_ERR_INVALID_ARG; pointers are 16-byte aligned.  One launch,
+ * one workgroup per frame, no scratch; the sum of squares runs in an order that depends on c alone, so a frame's rows do
+ * not depend on n_frames or on the frames it shares a launch with.  c % 8 == 0 and c <= 2048, else TSM_ERR_UNSUPPORTED.
+ * Inputs are finite.  Enqueues on `stream`; no synchronisation. */
+int tsm_pool_features(const float *feat, float *pooled, float *unit, int32_t n_frames, int32_t hw, int32_t c, void *stream);
+
+/* The temporal self-similarity matrix (device pointers)   workoutdetector/utils/common.py:118-143 (plot_sim):
+ *   unit [n_total, c] fp32, rows [0, row1) valid and of unit length (tsm_pool_features' / tsm_forward_features' unit rows)
+ *   dist [n_total, n_total] fp32: the call writes D[i][j] = clamp(1 - <unit_i, unit_j>, 0, 2) for i in [row0, row1) and
+ *   j in [0, row1), D[i][i] = 0 exactly, and the mirror D[j][i] from the same computed value -- scikit-learn's
+ *   cosine_distances with X is Y.  Nothing else of dist is touched.  row0 = 0, row1 = n_total is the whole matrix; a video
+ *   that spans many batches calls once per batch with that batch's band (as tsm_frame_votes carries its history).
+ * Exact-fp32 MFMA, ONE chain over k = 0 .. c - 1 in ascending order per element: a value does not depend on which band, tile
+ * or launch computed it, and D == D^T bit for bit.  Rows are not re-normalised: garbage in unit gives garbage distances,
+ * but the kernel is total -- for any float contents it reads only unit rows [0, row1) and writes exactly the region above.
+ * TSM_ERR_INVALID_ARG (nothing launched): NULL or not 16-byte aligned pointers, row0 < 0, row0 >= row1, row1 > n_total,
+ * c <= 0; TSM_ERR_UNSUPPORTED: c % 8 != 0.  No upper limit on c; n_total is not limited by the launch geometry.
+ * Enqueues on `stream`; no synchronisation. */
+int tsm_cosine_distances(const float *unit, int32_t n_total, int32_t c, int32_t row0, int32_t row1, float *dist, void *stream);
 
 /* Scores -> states on the GPU (device pointers), the post-step of the hot path:
  *   logits [n_clips, num_class] fp32 -> states [n_clips] int32: (softmax != 0: fp32 softmax over the classes,) the FIRST

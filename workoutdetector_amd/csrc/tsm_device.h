@@ -9,7 +9,8 @@
 //   tsm_front.hip      front_s2_kernel: shift + conv1 + stride-2 conv2 of layer2.0 per launch (bf16)
 //   tsm_fused23.hip    conv23_fused_kernel: conv2 + conv3 + residual per launch (fp32 / split-bf16)
 //   tsm_stem.hip       stem_direct / stem_pool[_f32]: the 7x7 stem with the max-pool fused behind it
-//   tsm_ops.hip        pack / convert / preprocess / gather_clips / preprocess_clips / preprocess_indexed / maxpool / shift / head / scores_to_states / top1_tally, device_info()
+//   tsm_ops.hip        pack / convert / preprocess / gather_clips / preprocess_clips / preprocess_indexed / maxpool / shift / head / pool_feat / scores_to_states / top1_tally, device_info()
+//   tsm_similarity.hip cosine_dist_kernel: the cosine-distance matrix of unit rows on the exact-fp32 MFMA
 #pragma once
 #include "tsm_kernels.h"
 

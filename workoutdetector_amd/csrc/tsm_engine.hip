@@ -148,6 +148,7 @@ struct tsm_engine {
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
   int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
+  int features = 0;           // for the duration of a tsm_forward_features call: 1 = the forward ends in the pooled rows, 2 = in the unit rows
   bool weights_started = false;   // a tsm_set_tensor call has been made: the backbone is fixed
   size_t tune_sig_base = 0;   // length of tune_sig before the backbone / placement suffix
   std::string err;
@@ -956,6 +957,11 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     w = (w + 2 - 3) / e->blocks[k].stride + 1;
   }
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
+  if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
+    TSM_LAUNCH(e, s, tsm::launch_pool_features(cur, e->features == 1 ? d_logits : nullptr, e->features == 2 ? d_logits : nullptr, n,
+                                               h * w, e->feat, prec, s));
+    return TSM_OK;
+  }
   if (e->consensus == 1) {   // per-segment logits: one launch, d_pooled is not written (the head's one timing slot either way)
     TSM_LAUNCH(e, s, tsm::launch_head_segments(cur, e->d_fcw, e->d_fcb, d_logits, n, h * w, e->feat, cfg.num_class, prec, s));
     return TSM_OK;
@@ -1352,21 +1358,28 @@ int tsm_finalize(tsm_engine *e) {
   return TSM_OK;
 }
 
-int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips,
-                float *logits, void *stream) {
+// tsm_forward (features = 0: `out` = the logits) and tsm_forward_features (1 / 2: `out` = the pooled / unit rows): one contract,
+// one body.  The host-memory staging buffer of the output is d_logits or d_pooled, each sized for max_clips.
+static int forward_to(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips, float *out,
+                      int features, void *stream) {
   int rc = check_forward_args(e, clips, memkind, layout, n_clips);
   if (rc) return rc;
-  if (!logits) return fail(e, TSM_ERR_INVALID_ARG, "logits is NULL");
+  if (!out) return fail(e, TSM_ERR_INVALID_ARG, features ? "features is NULL" : "logits is NULL");
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
   hipStream_t s = pick_stream(e, memkind, stream);
   const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * 3 * e->cfg.height * e->cfg.width;
   const float *d_clips = static_cast<const float *>(clips);
-  float *d_out = logits;
+  float *d_out = out, *d_stage = features ? e->d_pooled : e->d_logits;
   if (memkind == TSM_MEM_HOST) {
     TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, s));
     d_clips = e->d_in;
-    d_out = e->d_logits;
+    d_out = d_stage;
   }
+  struct Mode {   // run_forward's last launch, for this call only (every return path)
+    tsm_engine *e;
+    ~Mode() { e->features = 0; }
+  } mode{e};
+  e->features = features;
   e->cur_timing = nullptr;
   if (e->timing_left > 0) {
     --e->timing_left;
@@ -1386,11 +1399,22 @@ int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layou
   TSM_HIP(e, hipEventRecord(e->ev1, s));
   e->have_time = true;
   if (memkind == TSM_MEM_HOST) {
-    const size_t rows = (size_t)n_clips * (e->consensus == 1 ? e->cfg.num_segments : 1);
-    TSM_HIP(e, hipMemcpyAsync(logits, e->d_logits, rows * e->cfg.num_class * sizeof(float), hipMemcpyDeviceToHost, s));
+    const size_t elems = features ? (size_t)n_clips * e->cfg.num_segments * e->feat
+                                  : (size_t)n_clips * (e->consensus == 1 ? e->cfg.num_segments : 1) * e->cfg.num_class;
+    TSM_HIP(e, hipMemcpyAsync(out, d_stage, elems * sizeof(float), hipMemcpyDeviceToHost, s));
     TSM_HIP(e, hipStreamSynchronize(s));
   }
   return e->poison ? verify_guards(e, s) : TSM_OK;
+}
+
+int tsm_forward(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips,
+                float *logits, void *stream) {
+  return forward_to(e, clips, memkind, layout, n_clips, logits, 0, stream);
+}
+
+int tsm_forward_features(tsm_engine *e, const void *clips, int32_t memkind, int32_t layout, int32_t n_clips, float *features,
+                         int32_t normalize, void *stream) {
+  return forward_to(e, clips, memkind, layout, n_clips, features, normalize ? 2 : 1, stream);
 }
 
 int tsm_tune(tsm_engine *e, int32_t n_clips, void *stream) {
@@ -1950,6 +1974,29 @@ int tsm_head_segments(const float *feat, const float *fc_w, const float *fc_b, f
   hipError_t st = tsm::launch_head_segments(feat, fc_w, fc_b, logits, n_frames, hw, c, num_class, tsm::kPrecF32,
                                             static_cast<hipStream_t>(stream));
   if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("head_segments: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
+int tsm_pool_features(const float *feat, float *pooled, float *unit, int32_t n_frames, int32_t hw, int32_t c, void *stream) {
+  if (!feat || (!pooled && !unit) || n_frames <= 0 || hw <= 0 || c <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "pool_features: NULL pointer (feat, or both outputs) or non-positive size");
+  if ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(pooled) | reinterpret_cast<uintptr_t>(unit)) & 15u)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "pool_features: pointers must be 16-byte aligned");
+  if (c % 8 != 0 || c > 2048) return fail(nullptr, TSM_ERR_UNSUPPORTED, "pool_features: c must be a multiple of 8, at most 2048");
+  hipError_t st = tsm::launch_pool_features(feat, pooled, unit, n_frames, hw, c, tsm::kPrecF32, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("pool_features: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
+int tsm_cosine_distances(const float *unit, int32_t n_total, int32_t c, int32_t row0, int32_t row1, float *dist, void *stream) {
+  if (!unit || !dist) return fail(nullptr, TSM_ERR_INVALID_ARG, "cosine_distances: NULL pointer");
+  if ((reinterpret_cast<uintptr_t>(unit) | reinterpret_cast<uintptr_t>(dist)) & 15u)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "cosine_distances: pointers must be 16-byte aligned");
+  if (row0 < 0 || row0 >= row1 || row1 > n_total || c <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "cosine_distances: need 0 <= row0 < row1 <= n_total and c > 0");
+  if (c % 8 != 0) return fail(nullptr, TSM_ERR_UNSUPPORTED, "cosine_distances: c must be a multiple of 8");
+  hipError_t st = tsm::launch_cosine_distances(unit, n_total, c, row0, row1, dist, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("cosine_distances: ") + hipGetErrorString(st));
   return TSM_OK;
 }
 

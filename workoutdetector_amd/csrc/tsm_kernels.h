@@ -281,6 +281,12 @@ hipError_t launch_head(const float *feat, const float *fc_w, const float *fc_b, 
 // per-segment head: logits [n_frames, num_class], one launch, no scratch (c % 8 == 0, c <= 2048)
 hipError_t launch_head_segments(const float *feat, const float *fc_w, const float *fc_b, float *logits, int n_frames,
                                 int hw, int c, int num_class, int prec, hipStream_t s);
+// frame embeddings (see pool_feat_kernel): pooled / unit [n_frames, c], either nullable; one launch (c % 8 == 0, c <= 2048)
+hipError_t launch_pool_features(const float *feat, float *pooled, float *unit, int n_frames, int hw, int c, int prec,
+                                hipStream_t s);
+// cosine-distance band (see cosine_dist_kernel, tsm_similarity.hip): rows [row0, row1) x columns [0, row1) of dist
+// [n_total, n_total] and their mirror, from unit rows [n_total, c] (c % 8 == 0)
+hipError_t launch_cosine_distances(const float *unit, int n_total, int c, int row0, int row1, float *dist, hipStream_t s);
 
 // K9: per clip, (softmax,) first arg-max, class id if its score >= threshold else -1; top (nullable) = that score.
 hipError_t launch_scores_to_states(const float *logits, int n, int c, int softmax, float threshold, int *states, float *top,

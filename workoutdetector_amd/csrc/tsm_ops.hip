@@ -711,6 +711,67 @@ hipError_t launch_head_segments(const float *feat, const float *fc_w, const floa
 }
 
 // ---------------------------------------------------------------------------------------------
+// Frame embeddings (utils/common.py:79-116, cnn_feature / video_feature: a ResNet with num_classes=0 yields the pooled
+// vector of every frame): pooled[f] = mean_hw feat[f,hw,:] and unit[f] = pooled[f] / ||pooled[f]||2, the row scikit-learn's
+// pairwise_distances(metric='cosine') normalises to (utils/common.py:133).  ONE launch, one 256-thread workgroup per frame,
+// no scratch buffer; either output may be null:
+//   phase 1: head_seg_kernel's phase 1 (same row order, same division: a frame's pooled value is head_pool_kernel's to the
+//            bit) into LDS;
+//   phase 2: sum of squares in an order that depends on c alone -- thread t adds channels 4t .. 4t + 3, then 1024 + 4t ..,
+//            ascending; a shuffle tree per wave; ((w0 + w1) + (w2 + w3)) over the four waves -- so a frame's unit row does
+//            not depend on n_frames or on which frames share the launch;
+//   phase 3: norm = sqrtf(ss), 0 replaced by 1 (sklearn.preprocessing.normalize: an all-zero row stays all-zero), unit = pooled / norm.
+// ---------------------------------------------------------------------------------------------
+template <int FMT>
+__global__ void __launch_bounds__(256) pool_feat_kernel(const float *__restrict__ feat, float *__restrict__ pooled_out,
+                                                        float *__restrict__ unit_out, int rows, int c) {
+  constexpr int GF = Fmt<FMT>::gf, GC = Fmt<FMT>::ch;
+  __shared__ __attribute__((aligned(16))) float pooled[kHeadSegMaxC];
+  __shared__ float wave_ss[4];
+  const int b = blockIdx.x;
+  const int cg = c / GC;
+  for (int t = threadIdx.x; t < cg; t += 256) {
+    const float *src = feat + ((size_t)b * rows * cg + t) * GF;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 7
+    for (int r = 0; r < rows; ++r) {
+      float v[8];
+      load_group<FMT>(src + (size_t)r * cg * GF, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < GC; ++e) pooled[t * GC + e] = acc[e] / (float)rows;
+  }
+  __syncthreads();
+  float ss = 0.f;
+  for (int k = threadIdx.x * 4; k < c; k += 1024) {
+    const f32x4 f = *reinterpret_cast<const f32x4 *>(pooled + k);
+    if (pooled_out) *reinterpret_cast<f32x4 *>(pooled_out + (size_t)b * c + k) = f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ss += f[e] * f[e];
+  }
+  if (!unit_out) return;   // (uniform over the workgroup)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_ss[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  float norm = sqrtf((wave_ss[0] + wave_ss[1]) + (wave_ss[2] + wave_ss[3]));
+  if (norm == 0.f) norm = 1.f;
+  for (int k = threadIdx.x * 4; k < c; k += 1024) {
+    const f32x4 f = *reinterpret_cast<const f32x4 *>(pooled + k);
+    *reinterpret_cast<f32x4 *>(unit_out + (size_t)b * c + k) = f32x4{f[0] / norm, f[1] / norm, f[2] / norm, f[3] / norm};
+  }
+}
+
+hipError_t launch_pool_features(const float *feat, float *pooled, float *unit, int n_frames, int hw, int c, int prec,
+                                hipStream_t s) {
+  if (n_frames <= 0 || hw <= 0 || c <= 0 || c % 8 != 0 || c > kHeadSegMaxC || (!pooled && !unit)) return hipErrorInvalidValue;
+  TSM_DISPATCH_FMT(prec, pool_feat_kernel, n_frames, s, feat, pooled, unit, hw, c);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
 // K9: logits -> per-clip state on the GPU (utils/eval.py:153-164 + to_softmax, utils/visualize.py:140-150):
 // optional fp32 softmax over the classes, FIRST maximum, class id if its score >= threshold else -1.  One thread per
 // clip (n_clips x num_class is tiny; the point is that a streaming step copies 8 bytes per window to the host instead

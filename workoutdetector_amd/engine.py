@@ -22,8 +22,8 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys,
-                      remap_mmaction_keys, remap_torchvision_keys)
+from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, feature_width, is_mmaction_state_dict, make_state_dict,
+                      remap_checkpoint_keys, remap_mmaction_keys, remap_torchvision_keys)
 
 CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
 
@@ -65,6 +65,7 @@ class TsmEngine:
         self.base_model = base_model
         self.shift_place = shift_place
         self.consensus_type = consensus_type
+        self.feature_dim = feature_width(base_model)      # row width of forward_features
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
                               'bf16': _lib.LAYOUT_NTHWC8B}[dtype]
@@ -208,6 +209,44 @@ class TsmEngine:
             _lib.check(self._lib.tsm_forward(self._h, clips[s:s + n].data_ptr(), _lib.MEM_DEVICE, layout, n,
                                              out[s:s + n].data_ptr(), stream), self._h)
         return out
+
+    def forward_features(self, clips, normalize: bool = False, out=None, layout: int = _lib.LAYOUT_NTCHW):
+        """Frame embeddings (``tsm_forward_features``; the reference's ``cnn_feature``, utils/common.py:79-106): the forward with
+        ONE ``pool_feat_kernel`` launch in place of the head.  clips: what ``forward_device`` (a float32 CUDA tensor) or
+        ``forward_host`` (an ndarray) takes.  Returns float32 [B*T, feature_dim] of the same kind: the mean over the pixels of
+        every frame's last block output, or with ``normalize`` that row over its Euclidean norm (an all-zero row stays zero).
+        ``out`` (CUDA input only): a contiguous float32 [B*T, feature_dim] tensor to write into, e.g. a band of a video's
+        feature buffer.  Any engine: consensus, backbone, placement and dtype change nothing about the call."""
+        self._need_finalized()
+        t, d = self.num_segments, self.feature_dim
+        if hasattr(clips, 'is_cuda'):
+            import torch
+            if not (clips.is_cuda and clips.dtype == torch.float32):
+                raise ValueError('forward_features needs a float32 CUDA tensor or an ndarray')
+            if clips.device.index != self.device:
+                raise ValueError(f'tensor on cuda:{clips.device.index}, engine on cuda:{self.device}')
+            clips = clips.contiguous()
+            b = clips.shape[0]
+            self._check_clips(clips.numel(), b, layout)
+            out = _out(out, (b * t, d), torch.float32, clips)
+            stream = torch.cuda.current_stream(clips.device).cuda_stream
+            for s in range(0, b, self.max_clips):
+                n = min(self.max_clips, b - s)
+                _lib.check(self._lib.tsm_forward_features(self._h, clips[s:s + n].data_ptr(), _lib.MEM_DEVICE, layout, n,
+                                                          out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
+            return out
+        if out is not None:
+            raise ValueError('out= goes with a CUDA tensor')
+        clips = _as_f32(clips)
+        b = clips.shape[0]
+        self._check_clips(clips.size, b, layout)
+        res = np.empty((b * t, d), dtype=np.float32)
+        for s in range(0, b, self.max_clips):
+            chunk = np.ascontiguousarray(clips[s:s + self.max_clips])
+            o = res[s * t:(s + chunk.shape[0]) * t]
+            _lib.check(self._lib.tsm_forward_features(self._h, chunk.ctypes.data, _lib.MEM_HOST, layout, chunk.shape[0],
+                                                      o.ctypes.data, int(bool(normalize)), None), self._h)
+        return res
 
     def warmup(self, batch_sizes: Optional[Sequence[int]] = None) -> 'TsmEngine':
         """Tune every power-of-two bucket of the clip count that will occur (default: 1, 2, 4, ... max_clips) now
@@ -395,6 +434,44 @@ def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpo
         import torch
         ckpt = torch.load(checkpoint, map_location='cpu')
         sd = remap_torchvision_keys(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+    else:
+        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
+    eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
+                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg')
+    eng.image_resize, eng.image_crop = int(resize), int(crop)
+    return eng
+
+
+def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str] = None, max_frames: int = 32, dtype: str = 'f32',
+                         resize: int = 224, crop: int = 224, seed: int = 0, device: Optional[object] = None) -> TsmEngine:
+    """The reference's feature extractor (utils/common.py:129: ``timm.create_model(name, pretrained=True, num_classes=0)``) as
+    a ``TsmEngine`` built like ``create_image_model``'s -- ``num_segments=1``, ``is_shift=False``, ``height = width = crop`` --
+    whose product is ``forward_features`` ([n, feature_dim]: 512 for resnet18 / resnet34, 2048 for resnet50 /
+    wide_resnet50_2); ``similarity.video_features`` / ``self_similarity`` drive it.  ``checkpoint``: a ``torch.save``d
+    torchvision-keyed ``state_dict`` as ``create_image_model`` reads it; a ``num_classes=0`` model has no ``fc.*``, so a zero
+    ``fc`` [1, feature_dim] stands in (the engine's finalize wants a classifier; its logits are never asked for).  Without a
+    checkpoint: the seeded synthetic weights.  ``resize`` / ``crop``: ``Resize(resize)`` + ``CenterCrop(crop)`` through
+    ``tsm_preprocess`` (the reference resizes to 224 without a crop; an engine has one geometry -- DESIGN 4.17)."""
+    if base_model not in DEPTHS:
+        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+    if crop > resize:
+        raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
+    dev = 0
+    if device is not None:
+        s = str(device)
+        if s == 'cpu':
+            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
+        dev = int(s.split(':')[1]) if ':' in s else 0
+    num_class = 1
+    if checkpoint is not None:
+        import torch
+        ckpt = torch.load(checkpoint, map_location='cpu')
+        sd = remap_torchvision_keys(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+        if 'fc.weight' in sd:
+            num_class = int(sd['fc.weight'].shape[0])
+        else:
+            sd['fc.weight'] = np.zeros((1, feature_width(base_model)), dtype=np.float32)
+            sd['fc.bias'] = np.zeros((1,), dtype=np.float32)
     else:
         sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
     eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
@@ -819,4 +896,41 @@ def head_segments_nhwc(feat, fc_w, fc_b, out=None):
     out = _out(out, (n, fc_w.shape[0]), torch.float32, feat)
     _lib.check(_lib.load().tsm_head_segments(feat.data_ptr(), fc_w.contiguous().data_ptr(), fc_b.contiguous().data_ptr(),
                                              out.data_ptr(), n, h * w, c, fc_w.shape[0], _stream(feat)))
+    return out
+
+
+def pool_features_nhwc(feat, out=None, out_unit=None):
+    """The pool of ``forward_features`` on its own (``tsm_pool_features``): feat CUDA float32 [n_frames, H, W, C] (NHWC) ->
+    ``(pooled, unit)``, each [n_frames, C]: the mean over the pixels (``head_nhwc``'s pooled value to the bit) and that row
+    over its Euclidean norm (a zero row stays zero).  ``out`` / ``out_unit``: tensors to write into; pass ``False`` for one
+    of them to skip that output (it is then returned as None).  One launch on torch's current stream; no host sync."""
+    import torch
+    _need_cuda_f32(feat=feat)
+    feat = feat.contiguous()
+    n, h, w, c = feat.shape
+    if n <= 0 or h * w <= 0:
+        raise ValueError(f'feat {tuple(feat.shape)} is empty')
+    if out is False and out_unit is False:
+        raise ValueError('at least one of out / out_unit must be produced')
+    pooled = None if out is False else _out(out, (n, c), torch.float32, feat)
+    unit = None if out_unit is False else _out(out_unit, (n, c), torch.float32, feat, 'out_unit')
+    _lib.check(_lib.load().tsm_pool_features(feat.data_ptr(), _ptr(pooled), _ptr(unit), n, h * w, c, _stream(feat)))
+    return pooled, unit
+
+
+def cosine_distances(unit, out=None, rows=None):
+    """The cosine-distance matrix of unit rows (``tsm_cosine_distances``; scikit-learn's ``cosine_distances(X)``, which the
+    reference's ``plot_sim`` calls through ``pairwise_distances(metric='cosine')``): unit CUDA float32 [n, C], rows of unit
+    length -> ``out`` [n, n] with D[i][j] = clip(1 - <u_i, u_j>, 0, 2), a zero diagonal and D == D.T bit for bit.
+    ``rows=(row0, row1)`` writes the band i in [row0, row1), j in [0, row1) and its mirror only (rows of ``unit`` from row1
+    on are not read, the rest of ``out`` is not touched): call once per batch of a long video; the bands add up to the
+    one-shot matrix bit for bit.  ``out`` is allocated (uninitialised outside the band) when None.  One launch; no host sync."""
+    import torch
+    _need_cuda_f32(unit=unit)
+    if unit.dim() != 2 or unit.shape[0] == 0 or not unit.is_contiguous():
+        raise ValueError(f'unit must be contiguous [n >= 1, C], got {tuple(unit.shape)}')
+    n, c = (int(d) for d in unit.shape)
+    row0, row1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    out = _out(out, (n, n), torch.float32, unit)
+    _lib.check(_lib.load().tsm_cosine_distances(unit.data_ptr(), n, c, row0, row1, out.data_ptr(), _stream(unit)))
     return out

@@ -6,6 +6,8 @@
 //      a user-supplied file): truncated lines, huge numbers, stray bytes, missing separators, wrong code counts.
 //   2. fold_and_pack / fold_and_pack_stem_pairs / to_split / to_bf16 on ragged sizes, with the packed-buffer
 //      invariants checked (every weight lands inside [cout][kp], padding stays zero, split hi+lo == value to 2^-16).
+//   3. clip_window_range against an enumeration and at the ends of int32 / int64, center_crop_geometry against a table.
+#include <climits>
 #include <cstdio>
 #include <random>
 
@@ -234,7 +236,74 @@ static void check_guard_bands() {
   EXPECT(far.find("element offset -1024 (4096 bytes before its start)") != std::string::npos);
 }
 
+// clip_window_range / center_crop_geometry: the integer parts of the frame transforms' argument checks.
+static void check_frame_transform_args() {
+  // the window range against an enumeration of every (clip, segment) position
+  for (int total = 1; total <= 20; ++total)
+    for (int first_clip = 0; first_clip <= 4; ++first_clip)
+      for (int n_clips = 1; n_clips <= 3; ++n_clips)
+        for (int n_segment = 1; n_segment <= 3; ++n_segment)
+          for (int stride = 1; stride <= 3; ++stride)
+            for (int step = stride; step <= 3 * stride; step += stride)
+              for (int first_frame = 0; first_frame <= 2; ++first_frame) {
+                int64_t lo = INT64_MAX, hi = INT64_MIN;
+                bool tail = false;
+                const int n_frames = 4 + total % 5;
+                for (int c = first_clip; c < first_clip + n_clips; ++c)
+                  for (int k = 0; k < n_segment; ++k) {
+                    const int64_t s = (int64_t)step * c + (int64_t)stride * k;
+                    if (s >= total) { tail = true; continue; }
+                    const int64_t j = s / stride - first_frame;
+                    lo = j < lo ? j : lo;
+                    hi = j > hi ? j : hi;
+                  }
+                WindowRange r{};
+                const bool ok = clip_window_range(total, first_clip, n_clips, n_segment, step, stride, first_frame, n_frames, &r);
+                if ((int64_t)step * first_clip >= total) {          // the first clip starts past the video
+                  EXPECT(!ok);
+                  continue;
+                }
+                EXPECT(ok == (r.first >= 0 && r.last < n_frames));    // (the range is filled in either way)
+                // `last` is the video's last frame once the range reaches the tail: the touched maximum where the windows leave
+                // no gap between them, a bound on it otherwise
+                EXPECT(r.first == lo && r.tail == tail && r.last >= hi && r.last <= (total - 1) / stride - first_frame);
+                if (!tail || stride * n_segment >= step) EXPECT(r.last == hi);
+              }
+  // near the ends of the types: every product is of two int32, every sum stays below 2^63 (UBSAN watches)
+  const int i32 = INT32_MAX;
+  const int64_t i64 = INT64_MAX;
+  WindowRange r{};
+  EXPECT(!clip_window_range(i64, i64, i32, i32, i32, 1, 0, i64, &r));                   // first_clip * step would leave int64
+  EXPECT(!clip_window_range(i64, i64 / i32 + 1, 1, 1, i32, i32, 0, i64, &r));           // the first product just past the video
+  EXPECT(clip_window_range(i64, i64 / i32, i32, i32, i32, i32, 0, i64, &r) && r.tail && r.last == (i64 - 1) / i32);
+  EXPECT(!clip_window_range(i64, 0, i32, i32, i32, i32, i64, i64, &r) && !r.tail && r.first == -i64 &&      // before the buffer
+         r.last == ((int64_t)i32 * (i32 - 1) * 2) / i32 - i64);
+  EXPECT(clip_window_range(i64, 1, i32, i32, i32, 1, 0, i64, &r) && !r.tail && r.first == i32 &&
+         r.last == (int64_t)i32 * i32 + (i32 - 1));
+  EXPECT(clip_window_range(1, 0, i32, i32, i32, 1, 0, 1, &r) && r.tail && r.first == 0 && r.last == 0);
+  // refused arguments, each alone: a non-positive size, a step that is no multiple of the stride, negative origins
+  EXPECT(!clip_window_range(0, 0, 1, 1, 1, 1, 0, 9, &r) && !clip_window_range(9, -1, 1, 1, 1, 1, 0, 9, &r) &&
+         !clip_window_range(9, 0, 0, 1, 1, 1, 0, 9, &r) && !clip_window_range(9, 0, 1, 0, 1, 1, 0, 9, &r) &&
+         !clip_window_range(9, 0, 1, 1, 0, 1, 0, 9, &r) && !clip_window_range(9, 0, 1, 1, 1, 0, 0, 9, &r) &&
+         !clip_window_range(9, 0, 1, 1, 3, 2, 0, 9, &r) && !clip_window_range(9, 0, 1, 1, 1, 1, -1, 9, &r) &&
+         !clip_window_range(9, 0, 1, 1, 1, 1, 0, 0, &r) && clip_window_range(9, 0, 1, 1, 1, 1, 0, 9, &r));
+  // Resize(int) + CenterCrop: (h, w, resize, crop) -> (nh, nw, top, left); (nh - crop) / 2 = 0.5, 1.5, 2.5 round to even
+  const int geo[][8] = {{240, 320, 256, 224, 256, 341, 16, 58}, {320, 240, 256, 224, 341, 256, 58, 16}, {224, 224, 224, 224, 224, 224, 0, 0},
+                        {40, 56, 36, 32, 36, 50, 2, 9},         {57, 33, 36, 33, 62, 36, 14, 2},        {24, 24, 17, 17, 17, 17, 0, 0},
+                        {10, 10, 33, 32, 33, 33, 0, 0},         {10, 10, 35, 32, 35, 35, 2, 2},         {10, 10, 37, 32, 37, 37, 2, 2},
+                        {1080, 1920, 256, 224, 256, 455, 16, 116}, {3, 2000, 256, 224, 256, 170666, 16, 85221}};
+  for (const auto &q : geo) {
+    CropGeometry g{};
+    EXPECT(center_crop_geometry(q[0], q[1], q[2], q[3], &g));
+    EXPECT(g.nh == q[4] && g.nw == q[5] && g.top == q[6] && g.left == q[7]);
+  }
+  CropGeometry g{};
+  EXPECT(!center_crop_geometry(240, 320, 200, 224, &g) && !center_crop_geometry(320, 240, 224, 225, &g));
+  EXPECT(center_crop_geometry(1, i32, 1, 1, &g) && g.nh == 1 && g.nw == i32 && g.left == (i32 - 1) / 2);
+}
+
 int main(int argc, char **argv) {
+  check_frame_transform_args();
   check_tail_split();
   check_guard_bands();
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;

@@ -37,10 +37,8 @@ def _rows(boxes):
 
 
 def _shape(layout, n, size):
-    from workoutdetector_amd import _lib
-    pairs = (size + 1) // 2
-    return (n, 8) + {_lib.LAYOUT_NTHWC4: (size, size, 4), _lib.LAYOUT_NTHWC8S: (size, pairs, 8),
-                     _lib.LAYOUT_NTHWC8B: (size, pairs, 4), _lib.LAYOUT_NTCHW: (3, size, size)}[layout]
+    from workoutdetector_amd.engine import _frame_shape
+    return (n, 8) + _frame_shape(layout, size)
 
 
 def _launch(even, boxes, size, layout, first_frame=0, first_clip=0, total=TOTAL, **kw):
@@ -121,6 +119,39 @@ def test_padded_tail_is_exactly_the_normalised_zero_and_reads_nothing(hip_lib):
         assert not torch.equal(got[2, 5], zero[0]) and not torch.equal(got[3, 1], zero[0])
         packed = _launch(even, boxes, size, _lib.LAYOUT_NTHWC4, scale_255=scale_255)
         assert torch.equal(packed[..., :3].permute(0, 1, 4, 2, 3), got)
+
+
+@pytest.mark.parametrize('size', [16, 17])
+def test_whole_frame_boxes_equal_the_gathered_centre_crop_bit_for_bit(hip_lib, size):
+    """The two samplers share one core.  On square frames Resize((size, size)) of the whole frame and Resize(size) +
+    CenterCrop(size) are the same map, so preprocess_clips with every box "no person" equals gather_clips(preprocess_frames(
+    resize=size, crop=size)) bit for bit: all four layouts, uint8 and float32 sources, scale_255 on and off.  24 x 24 frames,
+    14 staged even frames, 4 clips of which the last two end in the padded tail: preprocess_clips writes the normalised zero
+    frame there, the other route transforms a staged raw zero frame and gathers it as the pad frame.  Size 17 ends every row in a
+    half-filled pixel pair.  (An NTCHW frame of 17 x 17 is 3468 bytes, no multiple of gather_clips' 16: those clips are picked
+    with torch from the same transformed frames.)"""
+    from workoutdetector_amd import _lib
+    from workoutdetector_amd.engine import _frame_shape, gather_clips, preprocess_frames
+    even = pc.video(size, TOTAL, 24, 24)[0::2].contiguous()
+    staged = torch.cat([even, torch.zeros_like(even[:1])])                    # ... + the pad frame, raw zeros
+    pick = torch.tensor([[min(4 * c + k, 14) for k in range(8)] for c in range(N_CLIPS)])    # even frame of (clip, segment)
+    for layout in (_lib.LAYOUT_NTHWC4, _lib.LAYOUT_NTCHW, _lib.LAYOUT_NTHWC8S, _lib.LAYOUT_NTHWC8B):
+        for f32_src, scale_255 in [(False, False), (True, True), (False, True), (True, False)]:
+            what = f'24x24 -> {size} layout {layout} {"f32" if f32_src else "u8"} scale_255={scale_255}'
+            fused = _launch(even.float() if f32_src else even, (None,) * N_CLIPS, size, layout, scale_255=scale_255)
+            src = guarded((staged.float() if f32_src else staged).cuda(), name='frames')
+            frames = guarded_out((15,) + _frame_shape(layout, size), name='transformed')
+            preprocess_frames(src, resize=size, crop=size, scale_255=scale_255, layout=layout, out=frames)
+            if frames[0].numel() * 4 % 16 == 0:
+                clips = guarded_out(_shape(layout, N_CLIPS, size), name='clips')
+                gather_clips(frames, 0, TOTAL, 0, N_CLIPS, out=clips)
+            else:
+                clips = None
+            torch.cuda.synchronize()
+            check(src, frames, clips)
+            want = clips.cpu() if clips is not None else frames.cpu()[pick]
+            assert torch.equal(fused.view(torch.int32), want.view(torch.int32)), what
+            assert not torch.equal(want[2, 5], want[2, 6]) and torch.equal(want[2, 6], want[3, 7]), what     # real / tail rows
 
 
 @pytest.mark.parametrize('layout_name', ['nthwc4', 'nthwc8s'])

@@ -14,11 +14,9 @@ def _preprocess(frames, crop=224, layout=None, packed=True, **kw):
     """engine.preprocess_frames in hostile memory (tests/_guard.py): the frames between poisoned bands, the output poisoned
     before the launch; bands and payload checked after it."""
     from workoutdetector_amd import _lib
-    from workoutdetector_amd.engine import preprocess_frames
+    from workoutdetector_amd.engine import _frame_shape, preprocess_frames
     lay = layout if layout is not None else (_lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW)
-    n, pairs = frames.shape[0], (crop + 1) // 2
-    shape = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
-             _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4), _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}[lay]
+    shape = (frames.shape[0],) + _frame_shape(lay, crop)
     src, out = guarded(frames, name='frames'), guarded_out(shape, name='out')
     assert preprocess_frames(src, crop=crop, layout=layout, packed=packed, out=out, **kw) is out
     check(src, out)

@@ -44,10 +44,8 @@ def _layouts():
 
 
 def _shape(layout, n, t, crop):
-    from workoutdetector_amd import _lib
-    pairs = (crop + 1) // 2
-    return (n, t) + {_lib.LAYOUT_NTHWC4: (crop, crop, 4), _lib.LAYOUT_NTHWC8S: (crop, pairs, 8),
-                     _lib.LAYOUT_NTHWC8B: (crop, pairs, 4), _lib.LAYOUT_NTCHW: (3, crop, crop)}[layout]
+    from workoutdetector_amd.engine import _frame_shape
+    return (n, t) + _frame_shape(layout, crop)
 
 
 def _launch(frames, table, resize, crop, layout, **kw):

@@ -1033,6 +1033,31 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
 
 }  // namespace
 
+// ---- the frame transforms (tsm_preprocess, _clips, _indexed, _image): their shared argument checks ----------------------------
+static int check_pixel(int32_t pixel) {
+  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  return TSM_OK;
+}
+static int check_out_layout(int32_t out_layout) {
+  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
+      out_layout != TSM_LAYOUT_NTHWC8B)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  return TSM_OK;
+}
+static int out_mode_of(int32_t out_layout) {          // PreprocParams::out_mode
+  return out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2 : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
+}
+static float pre_scale_of(int32_t scale_255) { return scale_255 ? 1.0f / 255.0f : 1.0f; }
+// Resize(resize) + CenterCrop(crop) of an h x w frame into a PreprocParams / ImagePreprocParams (tsm_host::center_crop_geometry);
+// false when the crop is larger than the resized frame.
+template <typename P>
+static bool set_crop_geometry(P *p, int h, int w, int resize, int crop) {
+  tsm_host::CropGeometry g;
+  if (!tsm_host::center_crop_geometry(h, w, resize, crop, &g)) return false;
+  p->h = h; p->w = w; p->nh = g.nh; p->nw = g.nw; p->top = g.top; p->left = g.left; p->crop = crop;
+  return true;
+}
+
 extern "C" {
 
 int tsm_abi_version(void) { return TSM_ABI_VERSION; }
@@ -1778,24 +1803,14 @@ int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int3
                    int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream) {
   if (!frames || !out || n <= 0 || h <= 0 || w <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "bad preprocess arguments");
-  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
-  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
-      out_layout != TSM_LAYOUT_NTHWC8B)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  if (int rc = check_pixel(pixel)) return rc;
+  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::PreprocParams p{};
-  p.src = frames; p.dst = out; p.n = n; p.h = h; p.w = w;
-  // torchvision 0.13 Resize(int): short side -> resize, long side -> int(resize * long / short)
-  if (h <= w) { p.nh = resize; p.nw = (int)((double)resize * w / h); }
-  else { p.nh = (int)((double)resize * h / w); p.nw = resize; }
-  if (crop > p.nh || crop > p.nw) return fail(nullptr, TSM_ERR_INVALID_ARG, "crop larger than the resized frame");
-  // CenterCrop: int(round((dim - crop) / 2)) with Python's round-half-to-even
-  p.top = (int)std::nearbyint((p.nh - crop) / 2.0);
-  p.left = (int)std::nearbyint((p.nw - crop) / 2.0);
-  p.crop = crop;
+  p.src = frames; p.dst = out; p.n = n;
+  if (!set_crop_geometry(&p, h, w, resize, crop)) return fail(nullptr, TSM_ERR_INVALID_ARG, "crop larger than the resized frame");
   p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
-               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
-  p.pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  p.out_mode = out_mode_of(out_layout);
+  p.pre_scale = pre_scale_of(scale_255);
   hipError_t st = tsm::launch_preprocess(p, static_cast<hipStream_t>(stream));
   if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
                                     std::string("preprocess: ") + hipGetErrorString(st));
@@ -1827,18 +1842,15 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
   if (!frames || !boxes || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: null pointer");
   if (n_frames <= 0 || h <= 0 || w <= 0 || size <= 0 || n_clips <= 0 || n_segment <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: non-positive size");
-  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
-  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
-      out_layout != TSM_LAYOUT_NTHWC8B)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  if (int rc = check_pixel(pixel)) return rc;
+  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::ClipPreprocParams p{};
   p.src = frames; p.dst = out; p.boxes = boxes; p.n_frames = n_frames; p.first_frame = first_frame;
   p.total_frames = total_frames; p.first_clip = first_clip; p.n_clips = n_clips; p.n_segment = n_segment;
   p.clip_step = clip_step; p.clip_stride = clip_stride; p.h = h; p.w = w; p.size = size;
   p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
-               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
-  p.pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  p.out_mode = out_mode_of(out_layout);
+  p.pre_scale = pre_scale_of(scale_255);
   hipError_t st = tsm::launch_preprocess_clips(p, static_cast<hipStream_t>(stream));
   if (st != hipSuccess)
     return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
@@ -1855,25 +1867,17 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
   if (!frames || !index || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: null pointer");
   if (n_frames <= 0 || h <= 0 || w <= 0 || n_clips <= 0 || n_segment <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: non-positive size");
-  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
-  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
-      out_layout != TSM_LAYOUT_NTHWC8B)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  if (int rc = check_pixel(pixel)) return rc;
+  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::IndexedPreprocParams q{};
   tsm::PreprocParams &p = q.pp;
   q.index = index; q.n_frames = n_frames; q.n_rows = (int64_t)n_clips * n_segment;
-  p.src = frames; p.dst = out; p.h = h; p.w = w;
-  // the geometry of tsm_preprocess: Resize(int), then CenterCrop with Python's round-half-to-even
-  if (h <= w) { p.nh = resize; p.nw = (int)((double)resize * w / h); }
-  else { p.nh = (int)((double)resize * h / w); p.nw = resize; }
-  if (crop > p.nh || crop > p.nw) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: crop larger than the resized frame");
-  p.top = (int)std::nearbyint((p.nh - crop) / 2.0);
-  p.left = (int)std::nearbyint((p.nw - crop) / 2.0);
-  p.crop = crop;
+  p.src = frames; p.dst = out;
+  if (!set_crop_geometry(&p, h, w, resize, crop))
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: crop larger than the resized frame");
   p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
-               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
-  p.pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  p.out_mode = out_mode_of(out_layout);
+  p.pre_scale = pre_scale_of(scale_255);
   hipError_t st = tsm::launch_preprocess_indexed(q, static_cast<hipStream_t>(stream));
   if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
                                     std::string("preprocess_indexed: ") + hipGetErrorString(st));
@@ -1902,21 +1906,12 @@ int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, co
                          float *out, int32_t out_layout, int32_t resize, int32_t crop, void *stream) {
   if (!frames || !out || n <= 0 || h <= 0 || w <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: NULL pointer or non-positive size");
-  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
-      out_layout != TSM_LAYOUT_NTHWC8B)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::ImagePreprocParams p{};
-  p.src = static_cast<const unsigned char *>(frames); p.dst = out; p.n = n; p.h = h; p.w = w;
-  // torchvision Resize(int) on a PIL image: short side -> resize, long side -> int(resize * long / short)
-  if (h <= w) { p.nh = resize; p.nw = (int)((double)resize * w / h); }
-  else { p.nh = (int)((double)resize * h / w); p.nw = resize; }
-  if (crop > p.nh || crop > p.nw) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: crop larger than the resized frame");
-  // center_crop: int(round((dim - crop) / 2.0)) with Python's round-half-to-even
-  p.top = (int)std::nearbyint((p.nh - crop) / 2.0);
-  p.left = (int)std::nearbyint((p.nw - crop) / 2.0);
-  p.crop = crop;
-  p.out_mode = out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2
-               : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
+  p.src = static_cast<const unsigned char *>(frames); p.dst = out; p.n = n;
+  if (!set_crop_geometry(&p, h, w, resize, crop))          // (torchvision's Resize(int) + center_crop on a PIL image: the same rule)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: crop larger than the resized frame");
+  p.out_mode = out_mode_of(out_layout);
   // the table block: [hb 2 * crop][hk crop * ksx] when the width changes, then [vb 2 * crop][vk crop * ksy] when the height does
   const bool horiz = p.nw != w, vert = p.nh != h;
   p.ksx = horiz ? pil_ksize(w, p.nw) : 0;

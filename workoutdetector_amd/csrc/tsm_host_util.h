@@ -1,7 +1,7 @@
 // Pure-host pieces of the engine: BatchNorm folding / weight packing, the bf16 storage-format converters, the
-// segment-length rule and the TSM_TUNE_CACHE line parser.  No HIP types, so this header also compiles with plain g++:
-// tests/host_sanitize.cpp builds it with -fsanitize=address,undefined and fuzzes the parser (CPU only; GPU ASAN is
-// not available on this pool).
+// segment-length rule, the frame transforms' window and crop arithmetic and the TSM_TUNE_CACHE line parser.  No HIP types,
+// so this header also compiles with plain g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined and
+// fuzzes the parser (CPU only; GPU ASAN is not available on this pool).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -178,6 +178,47 @@ inline std::string guard_message(const std::string &name, const GuardLayout &g, 
   return name + ": stray store into the band " + (after ? "after" : "before") + " the buffer, element offset " + std::to_string(elem) +
          (after ? " (" + std::to_string(rel - (long long)g.payload) + " bytes past its end)" : " (" + std::to_string(-rel) + " bytes before its start)") +
          ", the word there is " + hex;
+}
+
+// ---- frame transforms (tsm_preprocess*, tsm_gather_clips): the pure-integer parts of their argument checks -----------------
+// torchvision's Resize(int) + CenterCrop(crop) of an h x w frame: the short side -> resize, the long side ->
+// int(resize * long / short); the crop window starts at int(round((dim - crop) / 2)) with Python's round-half-to-even.
+// False when the crop is larger than the resized frame.  h, w, resize, crop > 0.
+struct CropGeometry {
+  int nh, nw, top, left;
+};
+inline bool center_crop_geometry(int h, int w, int resize, int crop, CropGeometry *g) {
+  if (h <= w) { g->nh = resize; g->nw = (int)((double)resize * w / h); }
+  else { g->nh = (int)((double)resize * h / w); g->nw = resize; }
+  if (crop > g->nh || crop > g->nw) return false;
+  g->top = (int)std::nearbyint((g->nh - crop) / 2.0);
+  g->left = (int)std::nearbyint((g->nw - crop) / 2.0);
+  return true;
+}
+
+// The buffer frames a range of clip windows touches.  Clip c, segment k is source frame step * c + stride * k; a position at or
+// past total_frames is the padded tail and reads no video frame; buffer frame j holds source frame stride * (first_frame + j).
+// For clips first_clip .. first_clip + n_clips - 1: `tail` = whether any position is padded, `first` = the buffer frame of the
+// first position, `last` = that of the last position, or of the video's last frame when the range reaches the tail.
+// False -- for ANY arguments, and no intermediate leaves int64 (products of two int32 and their sum only) -- unless the sizes
+// are positive, step is a multiple of stride, the first clip starts inside the video and first .. last lie in a buffer of
+// n_frames frames.
+struct WindowRange {
+  int64_t first, last;
+  bool tail;
+};
+inline bool clip_window_range(int64_t total_frames, int64_t first_clip, int n_clips, int n_segment, int step, int stride,
+                              int64_t first_frame, int64_t n_frames, WindowRange *r) {
+  if (total_frames <= 0 || first_clip < 0 || n_clips <= 0 || n_segment <= 0 || step <= 0 || stride <= 0 || step % stride != 0 ||
+      first_frame < 0 || n_frames <= 0)
+    return false;
+  if (first_clip > (total_frames - 1) / step) return false;       // step * first_clip >= total_frames, without the product
+  const int64_t lo = (int64_t)step * first_clip;
+  const int64_t span = (int64_t)step * (n_clips - 1) + (int64_t)stride * (n_segment - 1);     // the last position is lo + span
+  r->tail = span >= total_frames - lo;
+  r->first = lo / stride - first_frame;
+  r->last = (r->tail ? total_frames - 1 : lo + span) / stride - first_frame;
+  return r->first >= 0 && r->last < n_frames;
 }
 
 // Tuned tile shapes are cached per power-of-two bucket of the clip count (ragged last batches of a video

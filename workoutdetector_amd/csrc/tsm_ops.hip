@@ -1,5 +1,6 @@
 // Small streaming kernels around the conv stack, and device_info().
 #include "tsm_device.h"
+#include "tsm_host_util.h"
 
 #include <string>
 
@@ -163,84 +164,146 @@ hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStre
 }
 
 // ---------------------------------------------------------------------------------------------
-// preprocess (K8): one thread per output pixel.  Bilinear sampling follows ATen's CPU kernel
-// (UpSampleBilinear2d): src = scale*(dst+0.5)-0.5 clamped at 0, scale = in/out,
-// out = h0*(w0*p00 + w1*p01) + h1*(w0*p10 + w1*p11); then (v*pre_scale - mean)/std.
-// datasets/build.py:131-136 of the reference (torchvision tensor transforms).
+// Frame transforms: staged raw frames [n,h,w,3] u8|f32 -> resized, normalised frames in the engine's input formats.
+// One thread per output group: a pixel (out_mode 0 NHWC4 fp32, 1 NCHW fp32) or a pixel pair (2 split-bf16, 3 bf16: the
+// stem's packed-pair input, see pack_input_kernel); neighbouring threads are neighbouring ox: contiguous 16-byte stores.
+// preprocess_kernel, preprocess_indexed_kernel and preprocess_clips_kernel are ONE row loop (preprocess_rows) over three
+// row sources -- which frame, and which window of it, output row f shows -- and two samplers over one bilinear-and-
+// normalise core; preprocess_image_kernel (Pillow's antialiased resample, further down) shares the constants and the
+// group writer.  Bilinear sampling follows ATen's CPU kernel (UpSampleBilinear2d, no antialias): src = scale * (dst + 0.5)
+// - 0.5 clamped at 0, scale = in / out, out = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11); then
+// (v * pre_scale - mean) / std.  datasets/build.py:123-136 of the reference (torchvision tensor transforms).
 // ---------------------------------------------------------------------------------------------
-// The arithmetic of a pixel is spelled out -- contraction off, the three fused steps written as fmaf -- so that EVERY inlined
-// copy of this function computes the same bits: left to the compiler, the second pixel of a pixel pair rounded the other
-// product of each bilinear sum (fma(w0, p00, w1 * p01) where the first pixel had fma(w1, p01, w0 * p00)), so a pair layout's
-// odd pixels were one fp32 ulp of the interpolated value away from the fp32 layouts' -- after the mean is subtracted, up to
-// 1e-4 relative on a value near zero.  Now NTHWC8S / NTHWC8B hold the split / the rounding of exactly the numbers NTHWC4 and
-// NTCHW hold, in preprocess_kernel and in preprocess_indexed_kernel alike.
+__device__ constexpr float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};   // Normalize, ImageNet
+
+// The arithmetic of a pixel is spelled out -- contraction off, the fused steps written as fmaf -- so that EVERY inlined copy
+// of it computes the same bits: left to the compiler, the second pixel of a pixel pair rounded the other product of each
+// bilinear sum (fma(w0, p00, w1 * p01) where the first pixel had fma(w1, p01, w0 * p00)), so a pair layout's odd pixels
+// were one fp32 ulp of the interpolated value away from the fp32 layouts' -- after the mean is subtracted, up to 1e-4
+// relative on a value near zero.  With one spelling NTHWC8S / NTHWC8B hold the split / the rounding of exactly the numbers
+// NTHWC4 and NTCHW hold, in all three kernels, and a whole-frame box equals the centre crop of the same map bit for bit.
+__device__ __forceinline__ float sample_coord(float scale, float o) {
+#pragma clang fp contract(off)
+  const float f = __builtin_fmaf(scale, o + 0.5f, -0.5f);
+  return f < 0.f ? 0.f : f;
+}
+// channel c of one output pixel from its four taps: h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), normalised
+__device__ __forceinline__ float bilinear_normalised(float p00, float p01, float p10, float p11, float w0, float w1, float h0,
+                                                     float h1, float pre_scale, int c) {
+#pragma clang fp contract(off)
+  // (the two rows as the lanes of one packed multiply and one packed fma: the same two roundings per lane)
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  const f32x2 row = __builtin_elementwise_fma(f32x2{w1, w1}, f32x2{p01, p11}, f32x2{w0, w0} * f32x2{p00, p10});
+  const float t = __builtin_fmaf(h1, row[1], h0 * row[0]);
+  return __builtin_fmaf(t, pre_scale, -kMean[c]) / kStd[c];
+}
+// The reference's zero frame after Normalize: the padded tail of a clip, a table entry outside the buffer.
+__device__ __forceinline__ void zero_frame_pixel(float *v) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (0.f - kMean[c]) / kStd[c];
+}
+
+// One output group (pixel gx, or pixels 2 gx and 2 gx + 1, of row oy of frame f; `g` its running number) to dst.
+__device__ __forceinline__ void store_pixel_group(float *dst, int out_mode, int size, int64_t f, int oy, int gx, int64_t g,
+                                                  const float v[8]) {
+  if (out_mode == 1) {
+    float *o = dst + f * 3 * (int64_t)size * size + (int64_t)oy * size + gx;
+    o[0] = v[0];
+    o[(int64_t)size * size] = v[1];
+    o[2 * (int64_t)size * size] = v[2];
+  } else if (out_mode == 2) {
+    store_group<kPrecBf16x3>(dst + g * 8, v);
+  } else if (out_mode == 3) {
+    store_group<kPrecBf16>(dst + g * 4, v);
+  } else {
+    store_group<kPrecF32>(dst + g * 4, v);
+  }
+}
+
+// The row loop.  A row source has a `Row` (where a row's pixels come from), locate(f, &row) -- false: the row has no frame
+// and is the zero frame -- and pixel(row, oy, ox, v), its sampler.  Sources are passed by value and inlined.
+template <typename Source>
+__device__ __forceinline__ void preprocess_rows(float *dst, int out_mode, int size, int64_t n_rows, const Source src) {
+  const int px = out_mode >= 2 ? 2 : 1;
+  const int wg = (size + px - 1) / px;
+  const int64_t per_frame = (int64_t)wg * size;
+  const int64_t total = n_rows * per_frame;
+  // (256 = the block size of every launch, TSM_LAUNCH_ROWS: read as blockDim.x in here it costs a vector load and a wait at
+  //  the head of the kernel, which the scalar load of a kernel's own blockDim.x does not)
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    const int gx = (int)(i % wg);
+    const int oy = (int)((i / wg) % size);
+    const int64_t f = i / per_frame;
+    const bool pair = px == 2 && gx * 2 + 1 < size;      // (an odd size ends in a half-filled pair: the second pixel stays 0)
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    typename Source::Row row;
+    if (src.locate(f, &row)) {
+      src.pixel(row, oy, gx * px, v);
+      if (pair) src.pixel(row, oy, gx * 2 + 1, v + 4);
+    } else {
+      zero_frame_pixel(v);
+      if (pair) zero_frame_pixel(v + 4);
+    }
+    store_pixel_group(dst, out_mode, size, f, oy, gx, i, v);
+  }
+}
+
+// preprocess (K8): Resize(int) + CenterCrop.  The sampler of the centre-crop sources: every tap lies in the frame (the
+// launcher checks the crop window against the resized size), so nothing is masked.
 template <typename T>
 __device__ __forceinline__ void preprocess_pixel(const PreprocParams &p, const T *frame, int cy, int cx, float *v) {
 #pragma clang fp contract(off)
-  const float sh = (float)p.h / (float)p.nh, sw = (float)p.w / (float)p.nw;
-  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-  float fy = __builtin_fmaf(sh, (float)(cy + p.top) + 0.5f, -0.5f);      // (fused, as every copy had it before)
-  float fx = __builtin_fmaf(sw, (float)(cx + p.left) + 0.5f, -0.5f);
-  fy = fy < 0.f ? 0.f : fy;
-  fx = fx < 0.f ? 0.f : fx;
+  const float fy = sample_coord((float)p.h / (float)p.nh, (float)(cy + p.top));
+  const float fx = sample_coord((float)p.w / (float)p.nw, (float)(cx + p.left));
   const int y0 = (int)fy, x0 = (int)fx;
   const int y1 = y0 + (y0 < p.h - 1 ? 1 : 0), x1 = x0 + (x0 < p.w - 1 ? 1 : 0);
   const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
   const T *r0 = frame + (int64_t)y0 * p.w * 3, *r1 = frame + (int64_t)y1 * p.w * 3;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float p00 = (float)r0[x0 * 3 + c], p01 = (float)r0[x1 * 3 + c];
-    const float p10 = (float)r1[x0 * 3 + c], p11 = (float)r1[x1 * 3 + c];
-    // h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11), then (t * pre_scale - mean) / std
-    const float row0 = __builtin_fmaf(w1, p01, w0 * p00), row1 = __builtin_fmaf(w1, p11, w0 * p10);
-    const float t = __builtin_fmaf(h1, row1, h0 * row0);
-    v[c] = __builtin_fmaf(t, p.pre_scale, -mean[c]) / stdv[c];
-  }
+  for (int c = 0; c < 3; ++c)
+    v[c] = bilinear_normalised((float)r0[x0 * 3 + c], (float)r0[x1 * 3 + c], (float)r1[x0 * 3 + c], (float)r1[x1 * 3 + c], w0, w1,
+                               h0, h1, p.pre_scale, c);
 }
 
-// One thread per output group: a pixel (out_mode 0 NHWC4 fp32, 1 NCHW fp32) or a pixel pair (2 split-bf16,
-// 3 bf16: the stem's packed-pair input, see pack_input_kernel).
+// row f is frame f
+template <typename T>
+struct FrameRows {
+  const PreprocParams &p;
+  using Row = const T *;
+  __device__ __forceinline__ bool locate(int64_t f, Row *frame) const {
+    *frame = static_cast<const T *>(p.src) + f * (int64_t)p.h * p.w * 3;
+    return true;
+  }
+  __device__ __forceinline__ void pixel(Row frame, int oy, int ox, float *v) const { preprocess_pixel<T>(p, frame, oy, ox, v); }
+};
+
 template <typename T>
 __global__ void __launch_bounds__(256) preprocess_kernel(const PreprocParams p) {
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int wg = (p.crop + px - 1) / px;
-  const int64_t total = (int64_t)p.n * p.crop * wg;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const T *src = static_cast<const T *>(p.src);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int gx = (int)(i % wg);
-    const int cy = (int)((i / wg) % p.crop);
-    const int64_t f = i / ((int64_t)wg * p.crop);
-    const T *frame = src + f * (int64_t)p.h * p.w * 3;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    preprocess_pixel<T>(p, frame, cy, gx * px, v);
-    if (px == 2 && gx * 2 + 1 < p.crop) preprocess_pixel<T>(p, frame, cy, gx * 2 + 1, v + 4);
-    if (p.out_mode == 1) {
-      float *o = p.dst + f * 3 * (int64_t)p.crop * p.crop + (int64_t)cy * p.crop + gx;
-      o[0] = v[0];
-      o[(int64_t)p.crop * p.crop] = v[1];
-      o[2 * (int64_t)p.crop * p.crop] = v[2];
-    } else if (p.out_mode == 2) {
-      store_group<kPrecBf16x3>(p.dst + i * 8, v);
-    } else if (p.out_mode == 3) {
-      store_group<kPrecBf16>(p.dst + i * 4, v);
-    } else {
-      store_group<kPrecF32>(p.dst + i * 4, v);
-    }
-  }
+  preprocess_rows(p.dst, p.out_mode, p.crop, p.n, FrameRows<T>{p});
 }
 
+// The crop window of a centre-crop launch lies in the resized frame (PreprocParams, ImagePreprocParams).
+template <typename P>
+static bool crop_window_ok(const P &p) {
+  return p.h > 0 && p.w > 0 && p.crop > 0 && p.top >= 0 && p.left >= 0 && p.top + p.crop <= p.nh && p.left + p.crop <= p.nw;
+}
+
+// One grid-stride launch of a row-loop kernel covers any number of rows (64-bit group index): nothing of the launch geometry
+// limits a range of clips or a table.
+#define TSM_LAUNCH_ROWS(KERNEL, is_u8, n_rows, size, out_mode, stream, params)                             \
+  do {                                                                                                      \
+    const int px_ = (out_mode) >= 2 ? 2 : 1;                                                                \
+    const unsigned grid_ = grid_for((int64_t)(n_rows) * (size) * (((size) + px_ - 1) / px_), 8192);         \
+    if (is_u8)                                                                                              \
+      TSM_KLAUNCH(KERNEL<unsigned char>, dim3(grid_), dim3(256), 0, stream, params);                        \
+    else                                                                                                    \
+      TSM_KLAUNCH(KERNEL<float>, dim3(grid_), dim3(256), 0, stream, params);                                \
+  } while (0)
+
 hipError_t launch_preprocess(const PreprocParams &p, hipStream_t s) {
-  if (p.n <= 0 || p.h <= 0 || p.w <= 0 || p.crop <= 0 || p.top < 0 || p.left < 0 || p.top + p.crop > p.nh ||
-      p.left + p.crop > p.nw)
-    return hipErrorInvalidValue;
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int64_t total = (int64_t)p.n * p.crop * ((p.crop + px - 1) / px);
-  const unsigned grid = grid_for(total, 8192);
-  if (p.src_is_u8)
-    TSM_KLAUNCH(preprocess_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, p);
-  else
-    TSM_KLAUNCH(preprocess_kernel<float>, dim3(grid), dim3(256), 0, s, p);
+  if (p.n <= 0 || !crop_window_ok(p)) return hipErrorInvalidValue;
+  TSM_LAUNCH_ROWS(preprocess_kernel, p.src_is_u8, p.n, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -275,20 +338,16 @@ __global__ void __launch_bounds__(256) gather_clips_kernel(const GatherParams p)
 
 hipError_t launch_gather_clips(const GatherParams &p_in, hipStream_t s) {
   GatherParams p = p_in;
-  if (!p.frames || !p.out || p.n_frames <= 0 || p.frame_bytes <= 0 || p.frame_bytes % 16 != 0 || p.n_clips <= 0 ||
-      p.n_segment <= 0 || p.clip_step <= 0 || p.clip_stride <= 0 || p.clip_step % p.clip_stride != 0 ||
-      p.first_clip < 0 || p.first_frame < 0 || p.total_frames <= 0)
+  // every index the kernel will form, checked here: a clip starts inside its video, the first and the last in-video position of
+  // the range lie in the buffer, and the pad frame
+  tsm_host::WindowRange r;
+  if (!p.frames || !p.out || p.frame_bytes <= 0 || p.frame_bytes % 16 != 0 ||
+      !tsm_host::clip_window_range(p.total_frames, p.first_clip, p.n_clips, p.n_segment, p.clip_step, p.clip_stride, p.first_frame,
+                                   p.n_frames, &r))
     return hipErrorInvalidValue;
-  // every index the kernel will form, checked here: the first and the last in-video position of the range, and the pad frame
-  const int64_t lo = (int64_t)p.clip_step * p.first_clip;
-  const int64_t hi = (int64_t)p.clip_step * (p.first_clip + p.n_clips - 1) + (int64_t)p.clip_stride * (p.n_segment - 1);
-  if (lo >= p.total_frames) return hipErrorInvalidValue;                       // a clip starts inside its video
-  const int64_t last = (hi < p.total_frames ? hi : p.total_frames - 1) / p.clip_stride - p.first_frame;
-  const int64_t first = lo / p.clip_stride - p.first_frame;
-  if (first < 0 || last >= p.n_frames) return hipErrorInvalidValue;
   // a padded tail reads the pad frame: it must lie in the buffer and must not be one of the range's own video frames (a
   // mis-sized buffer or a wrong first_frame / total_frames pair would otherwise pass a real frame off as the zero frame)
-  if (hi >= p.total_frames && (p.pad_frame < 0 || p.pad_frame >= p.n_frames || (p.pad_frame >= first && p.pad_frame <= last)))
+  if (r.tail && (p.pad_frame < 0 || p.pad_frame >= p.n_frames || (p.pad_frame >= r.first && p.pad_frame <= r.last)))
     return hipErrorInvalidValue;
   const int64_t n16 = p.frame_bytes / 16;
   const unsigned gx = (unsigned)((n16 + 1023) / 1024 < 64 ? (n16 + 1023) / 1024 : 64);
@@ -316,115 +375,76 @@ hipError_t launch_gather_clips(const GatherParams &p_in, hipStream_t s) {
 //   * no person: bh <= 0 or bw <= 0 stands for the whole frame (0, 0, h, w) (transform.py:254 `if w * h == 0: return images`);
 //   * padded tail: a source index >= total_frames is the reference's zero frame: every channel (0 - mean) / std, nothing is
 //     read and the buffer needs no pad frame.
-// Bilinear sampling is preprocess_pixel's (ATen UpSampleBilinear2d, no antialias) in box coordinates.
+// The sampler is preprocess_pixel's arithmetic in box coordinates.
 // TOTAL in the boxes: they live in device memory, so no host check can see them; for ANY int32 contents the kernel reads only
 // inside the frames it was given -- the box index is clamped to the box, the sum with top / left is formed in 64 bits and a
 // tap is read only where 0 <= y < h and 0 <= x < w.  (The frame index is the host's to validate: launch_preprocess_clips.)
-// One thread per output group as in preprocess_kernel; neighbouring threads are neighbouring ox: contiguous 16-byte stores.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-__device__ __forceinline__ void clip_pixel(const ClipPreprocParams &p, const T *frame, int64_t top, int64_t left, int bh, int bw,
-                                           int oy, int ox, float *v) {
-  const float sh = (float)bh / (float)p.size, sw = (float)bw / (float)p.size;
-  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-  float fy = sh * ((float)oy + 0.5f) - 0.5f;
-  float fx = sw * ((float)ox + 0.5f) - 0.5f;
-  fy = fy < 0.f ? 0.f : fy;
-  fx = fx < 0.f ? 0.f : fx;
-  // (int) of a float at or above 2^31 is undefined: sides near INT32_MAX are held below it, and the index inside the box
-  const float big = 2147483520.f;
-  int y0 = (int)(fy < big ? fy : big), x0 = (int)(fx < big ? fx : big);
-  y0 = y0 < bh - 1 ? y0 : bh - 1;
-  x0 = x0 < bw - 1 ? x0 : bw - 1;
-  const int y1 = y0 + (y0 < bh - 1 ? 1 : 0), x1 = x0 + (x0 < bw - 1 ? 1 : 0);
-  const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
-  // image coordinates of the four taps, in 64 bits (top + y0 leaves int32 for a hostile box); a tap outside the frame is 0
-  const int64_t iy0 = top + y0, iy1 = top + y1, ix0 = left + x0, ix1 = left + x1;
-  const bool vy0 = iy0 >= 0 && iy0 < p.h, vy1 = iy1 >= 0 && iy1 < p.h;
-  const bool vx0 = ix0 >= 0 && ix0 < p.w, vx1 = ix1 >= 0 && ix1 < p.w;
-  // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
-  const T *r0 = frame + (vy0 ? iy0 : 0) * p.w * 3, *r1 = frame + (vy1 ? iy1 : 0) * p.w * 3;
-  const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
-  const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float p00 = vy0 && vx0 ? (float)a00[c] : 0.f, p01 = vy0 && vx1 ? (float)a01[c] : 0.f;
-    const float p10 = vy1 && vx0 ? (float)a10[c] : 0.f, p11 = vy1 && vx1 ? (float)a11[c] : 0.f;
-    const float t = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11);
-    v[c] = (t * p.pre_scale - mean[c]) / stdv[c];
+struct ClipRows {
+  const ClipPreprocParams &p;
+  struct Row {
+    const T *frame;
+    int64_t top, left;
+    int bh, bw;
+  };
+  __device__ __forceinline__ bool locate(int64_t f, Row *r) const {
+    const int64_t c = f / p.n_segment;             // f = the (clip, segment) row of the output
+    const int k = (int)(f - c * p.n_segment);
+    const int64_t s = (int64_t)p.clip_step * (p.first_clip + c) + (int64_t)p.clip_stride * k;
+    if (s >= p.total_frames) return false;
+    // the clip's box: four dwords, the same for every thread of (nearly every) wave -- ONE 16-byte load (two dependent 8-byte
+    // loads are one more memory latency per group), which asks no alignment of the caller
+    typedef int box_t __attribute__((ext_vector_type(4), aligned(4)));
+    const box_t b = *reinterpret_cast<const box_t *>(p.boxes + c * 4);
+    const bool person = b[2] > 0 && b[3] > 0;
+    r->top = person ? b[0] : 0;
+    r->left = person ? b[1] : 0;
+    r->bh = person ? b[2] : p.h;
+    r->bw = person ? b[3] : p.w;
+    r->frame = static_cast<const T *>(p.src) + (s / p.clip_stride - p.first_frame) * (int64_t)p.h * p.w * 3;
+    return true;
   }
-}
+  // the sampler: preprocess_pixel in box coordinates, total in the box
+  __device__ __forceinline__ void pixel(const Row &r, int oy, int ox, float *v) const {
+#pragma clang fp contract(off)
+    const float fy = sample_coord((float)r.bh / (float)p.size, (float)oy);
+    const float fx = sample_coord((float)r.bw / (float)p.size, (float)ox);
+    // (int) of a float at or above 2^31 is undefined: sides near INT32_MAX are held below it, and the index inside the box
+    const float big = 2147483520.f;
+    int y0 = (int)(fy < big ? fy : big), x0 = (int)(fx < big ? fx : big);
+    y0 = y0 < r.bh - 1 ? y0 : r.bh - 1;
+    x0 = x0 < r.bw - 1 ? x0 : r.bw - 1;
+    const int y1 = y0 + (y0 < r.bh - 1 ? 1 : 0), x1 = x0 + (x0 < r.bw - 1 ? 1 : 0);
+    const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
+    // image coordinates of the four taps, in 64 bits (top + y0 leaves int32 for a hostile box); a tap outside the frame is 0
+    const int64_t iy0 = r.top + y0, iy1 = r.top + y1, ix0 = r.left + x0, ix1 = r.left + x1;
+    const bool vy0 = iy0 >= 0 && iy0 < p.h, vy1 = iy1 >= 0 && iy1 < p.h;
+    const bool vx0 = ix0 >= 0 && ix0 < p.w, vx1 = ix1 >= 0 && ix1 < p.w;
+    // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
+    const T *r0 = r.frame + (vy0 ? iy0 : 0) * p.w * 3, *r1 = r.frame + (vy1 ? iy1 : 0) * p.w * 3;
+    const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
+    const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      v[c] = bilinear_normalised(vy0 && vx0 ? (float)a00[c] : 0.f, vy0 && vx1 ? (float)a01[c] : 0.f,
+                                 vy1 && vx0 ? (float)a10[c] : 0.f, vy1 && vx1 ? (float)a11[c] : 0.f, w0, w1, h0, h1, p.pre_scale, c);
+  }
+};
 
 template <typename T>
 __global__ void __launch_bounds__(256) preprocess_clips_kernel(const ClipPreprocParams p) {
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int wg = (p.size + px - 1) / px;
-  const int64_t per_frame = (int64_t)wg * p.size;
-  const int64_t total = (int64_t)p.n_clips * p.n_segment * per_frame;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const T *src = static_cast<const T *>(p.src);
-  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int gx = (int)(i % wg);
-    const int oy = (int)((i / wg) % p.size);
-    const int64_t f = i / per_frame;             // (clip, segment) row of the output
-    const int64_t c = f / p.n_segment;
-    const int k = (int)(f - c * p.n_segment);
-    const int64_t s = (int64_t)p.clip_step * (p.first_clip + c) + (int64_t)p.clip_stride * k;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (s < p.total_frames) {
-      // the clip's box: four dwords, the same for every thread of (nearly every) wave
-      const int *b = p.boxes + c * 4;
-      int64_t top = b[0], left = b[1];
-      int bh = b[2], bw = b[3];
-      if (bh <= 0 || bw <= 0) {
-        top = 0; left = 0; bh = p.h; bw = p.w;
-      }
-      const T *frame = src + (s / p.clip_stride - p.first_frame) * (int64_t)p.h * p.w * 3;
-      clip_pixel<T>(p, frame, top, left, bh, bw, oy, gx * px, v);
-      if (px == 2 && gx * 2 + 1 < p.size) clip_pixel<T>(p, frame, top, left, bh, bw, oy, gx * 2 + 1, v + 4);
-    } else {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        v[ch] = (0.f - mean[ch]) / stdv[ch];
-        if (px == 2 && gx * 2 + 1 < p.size) v[4 + ch] = v[ch];
-      }
-    }
-    if (p.out_mode == 1) {
-      float *o = p.dst + f * 3 * (int64_t)p.size * p.size + (int64_t)oy * p.size + gx;
-      o[0] = v[0];
-      o[(int64_t)p.size * p.size] = v[1];
-      o[2 * (int64_t)p.size * p.size] = v[2];
-    } else if (p.out_mode == 2) {
-      store_group<kPrecBf16x3>(p.dst + i * 8, v);
-    } else if (p.out_mode == 3) {
-      store_group<kPrecBf16>(p.dst + i * 4, v);
-    } else {
-      store_group<kPrecF32>(p.dst + i * 4, v);
-    }
-  }
+  preprocess_rows(p.dst, p.out_mode, p.size, (int64_t)p.n_clips * p.n_segment, ClipRows<T>{p});
 }
 
 hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
-  if (!p.src || !p.dst || !p.boxes || p.n_frames <= 0 || p.h <= 0 || p.w <= 0 || p.size <= 0 || p.n_clips <= 0 ||
-      p.n_segment <= 0 || p.clip_step <= 0 || p.clip_stride <= 0 || p.clip_step % p.clip_stride != 0 || p.first_clip < 0 ||
-      p.first_frame < 0 || p.total_frames <= 0 || p.first_clip >= p.total_frames || p.out_mode < 0 || p.out_mode > 3)
-    return hipErrorInvalidValue;
   // every frame index the kernel will form, checked here (launch_gather_clips' rules; there is no pad frame to check)
-  const int64_t lo = (int64_t)p.clip_step * p.first_clip;
-  const int64_t hi = (int64_t)p.clip_step * (p.first_clip + p.n_clips - 1) + (int64_t)p.clip_stride * (p.n_segment - 1);
-  if (lo >= p.total_frames) return hipErrorInvalidValue;                       // a clip starts inside its video
-  const int64_t last = (hi < p.total_frames ? hi : p.total_frames - 1) / p.clip_stride - p.first_frame;
-  const int64_t first = lo / p.clip_stride - p.first_frame;
-  if (first < 0 || last >= p.n_frames) return hipErrorInvalidValue;
-  // one grid-stride launch covers a range of any length (64-bit group index): nothing of the launch geometry limits n_clips
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int64_t total = (int64_t)p.n_clips * p.n_segment * p.size * ((p.size + px - 1) / px);
-  const unsigned grid = grid_for(total, 8192);
-  if (p.src_is_u8)
-    TSM_KLAUNCH(preprocess_clips_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, p);
-  else
-    TSM_KLAUNCH(preprocess_clips_kernel<float>, dim3(grid), dim3(256), 0, s, p);
+  tsm_host::WindowRange r;
+  if (!p.src || !p.dst || !p.boxes || p.h <= 0 || p.w <= 0 || p.size <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
+      !tsm_host::clip_window_range(p.total_frames, p.first_clip, p.n_clips, p.n_segment, p.clip_step, p.clip_stride, p.first_frame,
+                                   p.n_frames, &r))
+    return hipErrorInvalidValue;
+  TSM_LAUNCH_ROWS(preprocess_clips_kernel, p.src_is_u8, (int64_t)p.n_clips * p.n_segment, p.size, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -441,65 +461,31 @@ hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
 // TOTAL in the table: it lives in device memory, so no host check can see it; for ANY int32 contents the kernel reads only
 // inside the frames it was given -- the entry is range-tested first, and only then widened to 64 bits and multiplied into a
 // frame address.  An entry outside [0, n_frames) reads nothing and yields the normalised zero frame (0 - mean) / std, as
-// preprocess_clips' padded tail does.
-// One thread per output group as in preprocess_kernel; the table entry is one dword, the same for (nearly) every thread of a wave.
+// preprocess_clips' padded tail does.  The table entry is one dword, the same for (nearly) every thread of a wave.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
-__global__ void __launch_bounds__(256) preprocess_indexed_kernel(const IndexedPreprocParams q) {
-  const PreprocParams &p = q.pp;
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int wg = (p.crop + px - 1) / px;
-  const int64_t per_frame = (int64_t)wg * p.crop;
-  const int64_t total = q.n_rows * per_frame;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const T *src = static_cast<const T *>(p.src);
-  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int gx = (int)(i % wg);
-    const int cy = (int)((i / wg) % p.crop);
-    const int64_t f = i / per_frame;             // (clip, segment) row of the output
+struct IndexedRows {
+  const IndexedPreprocParams &q;
+  using Row = const T *;
+  __device__ __forceinline__ bool locate(int64_t f, Row *frame) const {
     const int j = q.index[f];
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (j >= 0 && (int64_t)j < q.n_frames) {
-      const T *frame = src + (int64_t)j * p.h * p.w * 3;
-      preprocess_pixel<T>(p, frame, cy, gx * px, v);
-      if (px == 2 && gx * 2 + 1 < p.crop) preprocess_pixel<T>(p, frame, cy, gx * 2 + 1, v + 4);
-    } else {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        v[ch] = (0.f - mean[ch]) / stdv[ch];
-        if (px == 2 && gx * 2 + 1 < p.crop) v[4 + ch] = v[ch];
-      }
-    }
-    if (p.out_mode == 1) {
-      float *o = p.dst + f * 3 * (int64_t)p.crop * p.crop + (int64_t)cy * p.crop + gx;
-      o[0] = v[0];
-      o[(int64_t)p.crop * p.crop] = v[1];
-      o[2 * (int64_t)p.crop * p.crop] = v[2];
-    } else if (p.out_mode == 2) {
-      store_group<kPrecBf16x3>(p.dst + i * 8, v);
-    } else if (p.out_mode == 3) {
-      store_group<kPrecBf16>(p.dst + i * 4, v);
-    } else {
-      store_group<kPrecF32>(p.dst + i * 4, v);
-    }
+    if (j < 0 || (int64_t)j >= q.n_frames) return false;
+    *frame = static_cast<const T *>(q.pp.src) + (int64_t)j * q.pp.h * q.pp.w * 3;
+    return true;
   }
+  __device__ __forceinline__ void pixel(Row frame, int oy, int ox, float *v) const { preprocess_pixel<T>(q.pp, frame, oy, ox, v); }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) preprocess_indexed_kernel(const IndexedPreprocParams q) {
+  preprocess_rows(q.pp.dst, q.pp.out_mode, q.pp.crop, q.n_rows, IndexedRows<T>{q});
 }
 
 hipError_t launch_preprocess_indexed(const IndexedPreprocParams &q, hipStream_t s) {
   const PreprocParams &p = q.pp;
-  // launch_preprocess' checks on the geometry, and the table's own
-  if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || p.h <= 0 || p.w <= 0 || p.crop <= 0 || p.top < 0 ||
-      p.left < 0 || p.top + p.crop > p.nh || p.left + p.crop > p.nw || p.out_mode < 0 || p.out_mode > 3)
+  if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3)
     return hipErrorInvalidValue;
-  // one grid-stride launch covers a table of any length (64-bit group index): nothing of the launch geometry limits n_clips
-  const int px = p.out_mode >= 2 ? 2 : 1;
-  const int64_t total = q.n_rows * p.crop * ((p.crop + px - 1) / px);
-  const unsigned grid = grid_for(total, 8192);
-  if (p.src_is_u8)
-    TSM_KLAUNCH(preprocess_indexed_kernel<unsigned char>, dim3(grid), dim3(256), 0, s, q);
-  else
-    TSM_KLAUNCH(preprocess_indexed_kernel<float>, dim3(grid), dim3(256), 0, s, q);
+  TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, q.n_rows, p.crop, p.out_mode, s, q);
   return hipGetLastError();
 }
 
@@ -902,7 +888,6 @@ __global__ void __launch_bounds__(256) preprocess_image_kernel(const ImagePrepro
     }
   }
   __syncthreads();
-  const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
   const int px = p.out_mode >= 2 ? 2 : 1;
   const int wg = (p.crop + px - 1) / px;
   for (int i = threadIdx.x; i < (r1 - r0) * wg; i += 256) {
@@ -941,21 +926,10 @@ __global__ void __launch_bounds__(256) preprocess_image_kernel(const ImagePrepro
         u[2] = col[2];
       }
 #pragma unroll
-      for (int c = 0; c < 3; ++c) v[4 * q + c] = ((float)u[c] / 255.0f - mean[c]) / stdv[c];
+      for (int c = 0; c < 3; ++c) v[4 * q + c] = ((float)u[c] / 255.0f - kMean[c]) / kStd[c];
     }
-    const int64_t g = (f * p.crop + cy) * wg + gx;       // output group, as preprocess_kernel numbers them
-    if (p.out_mode == 1) {
-      float *o = p.dst + f * 3 * (int64_t)p.crop * p.crop + (int64_t)cy * p.crop + gx;
-      o[0] = v[0];
-      o[(int64_t)p.crop * p.crop] = v[1];
-      o[2 * (int64_t)p.crop * p.crop] = v[2];
-    } else if (p.out_mode == 2) {
-      store_group<kPrecBf16x3>(p.dst + g * 8, v);
-    } else if (p.out_mode == 3) {
-      store_group<kPrecBf16>(p.dst + g * 4, v);
-    } else {
-      store_group<kPrecF32>(p.dst + g * 4, v);
-    }
+    const int64_t g = (f * p.crop + cy) * wg + gx;       // output group, as preprocess_rows numbers them
+    store_pixel_group(p.dst, p.out_mode, p.crop, f, cy, gx, g, v);
   }
 }
 
@@ -967,8 +941,7 @@ static int image_rows_cap(int band, int in, int out) {
 }
 
 hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s) {
-  if (!p.src || !p.dst || p.n <= 0 || p.h <= 0 || p.w <= 0 || p.nh <= 0 || p.nw <= 0 || p.crop <= 0 || p.top < 0 || p.left < 0 ||
-      p.top + p.crop > p.nh || p.left + p.crop > p.nw || p.out_mode < 0 || p.out_mode > 3)
+  if (!p.src || !p.dst || p.n <= 0 || p.nh <= 0 || p.nw <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3)
     return hipErrorInvalidValue;
   // a pass without tables copies: legal only where that axis keeps its size (the crop window then lies inside the frame)
   if ((!p.hk && p.nw != p.w) || (!p.vk && p.nh != p.h) || (p.hk && (!p.hb || p.ksx <= 0)) || (p.vk && (!p.vb || p.ksy <= 0)))

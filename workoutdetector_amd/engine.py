@@ -612,6 +612,29 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
     return y
 
 
+def _frame_shape(layout: int, size: int, what: str = 'layout') -> tuple:
+    """Shape of ONE size x size frame as the frame transforms write it (float32 slots).  The bf16 formats store pixel PAIRS:
+    one 8-element group = 2 pixels x 4 channels, split-bf16 in 8 float slots, bf16 in 4 (8 bf16 = 16 bytes)."""
+    pairs = (size + 1) // 2
+    shapes = {_lib.LAYOUT_NTHWC4: (size, size, 4), _lib.LAYOUT_NTHWC8S: (size, pairs, 8), _lib.LAYOUT_NTHWC8B: (size, pairs, 4),
+              _lib.LAYOUT_NTCHW: (3, size, size)}
+    if layout not in shapes:
+        raise ValueError(f'{what} must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW, got {layout}')
+    return shapes[layout]
+
+
+def _pixel_of(frames, want: str, u8_only: bool = False, min_frames: int = 0) -> int:
+    """The C ABI's pixel code of staged raw frames -- a contiguous CUDA uint8 or float32 tensor [n >= min_frames,H,W,3] -- or
+    ValueError (``want``: how the caller words that requirement)."""
+    import torch
+    if not u8_only and getattr(frames, 'dtype', None) not in (torch.uint8, torch.float32):
+        raise ValueError(f'frames must be uint8 or float32, got {getattr(frames, "dtype", type(frames))}')
+    if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
+            and frames.shape[0] >= min_frames and (frames.dtype == torch.uint8 or not u8_only)):
+        raise ValueError(f'frames must be {want}')
+    return _lib.PIXEL_U8 if frames.dtype == torch.uint8 else _lib.PIXEL_F32
+
+
 def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: bool = False, packed: bool = True,
                       layout: Optional[int] = None, out=None):
     """HIP test transform.  frames: CUDA uint8 or float32 [n,H,W,3] (decoder layout, values 0..255).
@@ -621,22 +644,11 @@ def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: boo
     split-bf16 group per pixel pair; LAYOUT_NTHWC8B: [n,crop,ceil(crop/2),4] float slots = 8 bf16 per pair)."""
     import torch
     frames = frames.contiguous()
-    if frames.dtype == torch.uint8:
-        pixel = _lib.PIXEL_U8
-    elif frames.dtype == torch.float32:
-        pixel = _lib.PIXEL_F32
-    else:
-        raise ValueError(f'frames must be uint8 or float32, got {frames.dtype}')
-    n, h, w, c = frames.shape
-    if c != 3 or not frames.is_cuda:
-        raise ValueError('frames must be a CUDA tensor [n,H,W,3]')
+    pixel = _pixel_of(frames, 'a CUDA tensor [n,H,W,3]')
+    n, h, w, _ = frames.shape
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW
-    pairs = (crop + 1) // 2     # the bf16 formats store pixel PAIRS: one 8-element group = 2 pixels x 4 channels
-    shape = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
-             _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4),     # 8 bf16 = 16 bytes = 4 float slots per pair
-             _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}[layout]
-    out = _out(out, shape, torch.float32, frames)
+    out = _out(out, (n,) + _frame_shape(layout, crop), torch.float32, frames)
     _lib.check(_lib.load().tsm_preprocess(frames.data_ptr(), pixel, n, h, w, out.data_ptr(), layout, resize, crop,
                                           int(scale_255), _stream(frames)))
     return out
@@ -666,22 +678,16 @@ def preprocess_image(frames, resize: int = 256, crop: int = 224, out_layout: Opt
     ``preprocess_frames`` shapes it.  ``tables``: the int32 CUDA table block of this geometry (``transform.image_tables``);
     built, cached and uploaded here when None."""
     import torch
-    if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4
-            and frames.shape[3] == 3 and frames.is_contiguous()):
-        raise ValueError('frames must be a contiguous uint8 CUDA tensor [n,H,W,3]')
+    _pixel_of(frames, 'a contiguous uint8 CUDA tensor [n,H,W,3]', u8_only=True)
     n, h, w, _ = frames.shape
     layout = _lib.LAYOUT_NTHWC4 if out_layout is None else out_layout
-    pairs = (crop + 1) // 2
-    shapes = {_lib.LAYOUT_NTHWC4: (n, crop, crop, 4), _lib.LAYOUT_NTHWC8S: (n, crop, pairs, 8),
-              _lib.LAYOUT_NTHWC8B: (n, crop, pairs, 4), _lib.LAYOUT_NTCHW: (n, 3, crop, crop)}
-    if layout not in shapes:
-        raise ValueError(f'out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW, got {layout}')
+    shape = (n,) + _frame_shape(layout, crop, 'out_layout')
     if tables is None:
         tables = image_tables_device(h, w, resize, crop, frames.device)
     elif not (hasattr(tables, 'is_cuda') and tables.is_cuda and tables.device == frames.device and tables.dtype == torch.int32
               and tables.dim() == 1 and tables.is_contiguous()):
         raise ValueError(f'tables must be a contiguous 1-d int32 tensor on {frames.device}')
-    out = _out(out, shapes[layout], torch.float32, frames)
+    out = _out(out, shape, torch.float32, frames)
     _lib.check(_lib.load().tsm_preprocess_image(frames.data_ptr(), n, h, w, tables.data_ptr() if tables.numel() else None,
                                                 tables.numel(), out.data_ptr(), layout, resize, crop, _stream(frames)))
     return out
@@ -758,24 +764,14 @@ def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_c
     in the layouts of ``preprocess_frames`` with ``size`` in place of ``crop``; the zero-padded tail segments of the last
     clips are (0 - mean) / std."""
     import torch
-    if frames.dtype == torch.uint8:
-        pixel = _lib.PIXEL_U8
-    elif frames.dtype == torch.float32:
-        pixel = _lib.PIXEL_F32
-    else:
-        raise ValueError(f'frames must be uint8 or float32, got {frames.dtype}')
-    if frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_cuda or not frames.is_contiguous():
-        raise ValueError('frames must be a contiguous CUDA tensor [n,H,W,3]')
+    pixel = _pixel_of(frames, 'a contiguous CUDA tensor [n,H,W,3]')
     n, h, w, _ = frames.shape
     if not (hasattr(boxes, 'is_cuda') and boxes.is_cuda and boxes.device == frames.device and boxes.dtype == torch.int32
             and tuple(boxes.shape) == (n_clips, 4) and boxes.is_contiguous()):
         raise ValueError(f'boxes must be a contiguous int32 tensor [{n_clips}, 4] = (top, left, h, w) on {frames.device}')
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW
-    pairs = (size + 1) // 2
-    frame = {_lib.LAYOUT_NTHWC4: (size, size, 4), _lib.LAYOUT_NTHWC8S: (size, pairs, 8), _lib.LAYOUT_NTHWC8B: (size, pairs, 4),
-             _lib.LAYOUT_NTCHW: (3, size, size)}[layout]
-    out = _out(out, (n_clips, n_segment) + frame, torch.float32, frames)
+    out = _out(out, (n_clips, n_segment) + _frame_shape(layout, size), torch.float32, frames)
     _lib.check(_lib.load().tsm_preprocess_clips(frames.data_ptr(), pixel, n, h, w, int(first_frame), int(total_frames),
                                                 int(first_clip), n_clips, n_segment, clip_step, clip_stride, boxes.data_ptr(),
                                                 out.data_ptr(), layout, size, int(scale_255), _stream(frames)))
@@ -796,9 +792,7 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
     import torch
     if not hasattr(frames, 'is_cuda') or frames.dtype not in (torch.uint8, torch.float32):
         raise ValueError(f'frames must be a uint8 or float32 tensor, got {getattr(frames, "dtype", type(frames))}')
-    pixel = _lib.PIXEL_U8 if frames.dtype == torch.uint8 else _lib.PIXEL_F32
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0 or not frames.is_cuda or not frames.is_contiguous():
-        raise ValueError('frames must be a contiguous CUDA tensor [n >= 1,H,W,3]')
+    pixel = _pixel_of(frames, 'a contiguous CUDA tensor [n >= 1,H,W,3]', min_frames=1)
     n, h, w, _ = frames.shape
     if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
             and index.dim() == 2 and index.shape[0] > 0 and index.shape[1] > 0 and index.is_contiguous()):
@@ -806,12 +800,7 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
     n_clips, n_segment = (int(d) for d in index.shape)
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4
-    pairs = (crop + 1) // 2
-    shapes = {_lib.LAYOUT_NTHWC4: (crop, crop, 4), _lib.LAYOUT_NTHWC8S: (crop, pairs, 8), _lib.LAYOUT_NTHWC8B: (crop, pairs, 4),
-              _lib.LAYOUT_NTCHW: (3, crop, crop)}
-    if layout not in shapes:
-        raise ValueError(f'layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW, got {layout}')
-    out = _out(out, (n_clips, n_segment) + shapes[layout], torch.float32, frames)
+    out = _out(out, (n_clips, n_segment) + _frame_shape(layout, crop), torch.float32, frames)
     _lib.check(_lib.load().tsm_preprocess_indexed(frames.data_ptr(), pixel, n, h, w, index.data_ptr(), n_clips, n_segment,
                                                   out.data_ptr(), layout, int(resize), int(crop), int(scale_255),
                                                   _stream(frames)))

@@ -56,7 +56,8 @@ import torch
 from . import distributed as tdist
 from .counting import RepCounter, pred_to_count, scores_to_preds, vote_states  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
-from .transform import ImageTransform, PersonCropTransform, TestTransform, build_test_transform
+from .transform import (ImageTransform, PersonCropTransform, TestTransform, as_frames_u8, build_test_transform,
+                        need_frame_engine)
 
 NUM_SEGMENTS = 8
 CLIP_SPAN = 16
@@ -956,24 +957,14 @@ def _is_image_engine(model) -> bool:
     return _engine_device(model) is not None and hasattr(model, 'packed_layout')
 
 
-def _frames_u8(frames) -> torch.Tensor:
-    t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
-        raise ValueError(f'frames must be uint8 [n >= 1, H, W, 3], got {t.dtype} {tuple(t.shape)}')
-    return t
-
-
 def _image_logits_device(model, frames_u8: torch.Tensor) -> torch.Tensor:
     """Engine path of one batch: pinned staging, ONE ``tsm_preprocess_image`` launch into the engine's packed layout, the
     forward; returns the CUDA logits [n, num_class] (nothing synchronised)."""
     from .engine import preprocess_image
-    if getattr(model, 'num_segments', 1) != 1:
-        raise ValueError('the image path needs an engine with num_segments=1 (engine.create_image_model)')
     need_clip_rows(model, 'inference_images')
     dev = _engine_device(model)
     resize, crop = _image_geometry(model)
-    if (model.height, model.width) != (crop, crop):
-        raise ValueError(f'the engine takes {model.height} x {model.width} frames, the transform crops to {crop}')
+    need_frame_engine(model, crop, 'image', 'create_image_model')
     if frames_u8.is_cuda:
         staged = frames_u8.contiguous()
     else:
@@ -1011,7 +1002,7 @@ def inference_images(model, frames_u8) -> np.ndarray:
     A ``TsmEngine`` (``engine.create_image_model``) stages the frames, does ONE ``tsm_preprocess_image`` launch and the
     forward (``max_frames`` frames per engine call); any other model takes the CPU ``ImageTransform``.  The channel order is
     kept as given: the reference hands cv2's BGR frames to its transform as they are -- the caller's business."""
-    frames = _frames_u8(frames_u8)
+    frames = as_frames_u8(frames_u8)
     if _is_image_engine(model):
         return _image_logits_device(model, frames).cpu().numpy()
     resize, crop = _image_geometry(model)
@@ -1028,16 +1019,16 @@ def _frame_batches(frames, batch: int) -> Iterator[torch.Tensor]:
     """uint8 [<= batch, H, W, 3] pieces of a [N,H,W,3] array / tensor or of an iterable of HWC frames."""
     if (isinstance(frames, torch.Tensor) or isinstance(frames, np.ndarray)) and frames.ndim == 4:
         for a in range(0, int(frames.shape[0]), batch):
-            yield _frames_u8(frames[a:a + batch])
+            yield as_frames_u8(frames[a:a + batch])
         return
     held: List[torch.Tensor] = []
     for f in frames:
         held.append(torch.as_tensor(np.asarray(f) if not isinstance(f, torch.Tensor) else f))
         if len(held) == batch:
-            yield _frames_u8(torch.stack(held))
+            yield as_frames_u8(torch.stack(held))
             held = []
     if held:
-        yield _frames_u8(torch.stack(held))
+        yield as_frames_u8(torch.stack(held))
 
 
 def image_states(model, frames, batch_frames: Optional[int] = None,

@@ -23,7 +23,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .transform import TestTransform
+from .transform import TestTransform, as_frames_u8, need_frame_engine
 
 
 def cosine_distances_host(feats) -> np.ndarray:
@@ -46,13 +46,6 @@ def _is_engine(model) -> bool:
     return hasattr(model, 'forward_features') and hasattr(model, 'packed_layout')
 
 
-def _frames_u8(frames) -> torch.Tensor:
-    t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
-        raise ValueError(f'frames must be uint8 [n >= 1, H, W, 3], got {t.dtype} {tuple(t.shape)}')
-    return t
-
-
 def _geometry(model):
     return int(getattr(model, 'image_resize', 224)), int(getattr(model, 'image_crop', 224))
 
@@ -60,11 +53,8 @@ def _geometry(model):
 def _engine_rows(model, frames: torch.Tensor, normalize: bool, batch_frames: Optional[int], dist: bool):
     """The engine path of both functions: (features [N, feature_dim], distances [N, N] or None), CUDA tensors."""
     from .engine import cosine_distances, preprocess_frames
-    if model.num_segments != 1:
-        raise ValueError('the similarity path needs an engine with num_segments=1 (engine.create_feature_model)')
     resize, crop = _geometry(model)
-    if (model.height, model.width) != (crop, crop):
-        raise ValueError(f'the engine takes {model.height} x {model.width} frames, the transform crops to {crop}')
+    need_frame_engine(model, crop, 'similarity', 'create_feature_model')
     dev = torch.device('cuda', model.device)
     n = int(frames.shape[0])
     step = int(batch_frames) if batch_frames else model.max_clips
@@ -102,7 +92,7 @@ def video_features(model, frames_u8, normalize: bool = False, batch_frames: Opti
     float32 [N, feature_dim], one pooled vector per frame (``normalize``: each over its Euclidean norm).  A ``TsmEngine``
     returns a CUDA tensor (``batch_frames`` frames per forward, default the engine's ``max_clips``); any other model an
     ndarray."""
-    frames = _frames_u8(frames_u8)
+    frames = as_frames_u8(frames_u8)
     if _is_engine(model):
         return _engine_rows(model, frames, normalize, batch_frames, dist=False)[0]
     feats = _host_features(model, frames, batch_frames)
@@ -118,7 +108,7 @@ def self_similarity(model, frames_u8, batch_frames: Optional[int] = None):
     [N, N] cosine distances of the frames' embeddings, symmetric, zero diagonal, values in [0, 2].  A ``TsmEngine`` returns a
     float32 CUDA tensor, built band by band as the batches come off the engine; any other model a float64 ndarray
     (``cosine_distances_host``)."""
-    frames = _frames_u8(frames_u8)
+    frames = as_frames_u8(frames_u8)
     if _is_engine(model):
         return _engine_rows(model, frames, True, batch_frames, dist=True)[1]
     return cosine_distances_host(_host_features(model, frames, batch_frames))

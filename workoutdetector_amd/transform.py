@@ -275,3 +275,21 @@ class ImageTransform:
 
     def __repr__(self):
         return f'ImageTransform(ToPILImage, Resize({self.resize}), CenterCrop({self.crop}), ToTensor, Normalize(ImageNet))'
+
+
+# ---- the per-frame engine paths (image model, frame embeddings): what both ask of their input and of their engine -----------
+def as_frames_u8(frames) -> torch.Tensor:
+    """Decoded frames (ndarray or tensor) as a uint8 tensor [n >= 1, H, W, 3], or ValueError."""
+    t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
+        raise ValueError(f'frames must be uint8 [n >= 1, H, W, 3], got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def need_frame_engine(model, crop: int, path: str, factory: str) -> None:
+    """A per-frame path feeds every frame as a clip of one segment, cropped to the engine's own size: refuse any other
+    engine up front (``path`` / ``factory``: how the caller's message names itself and the constructor to use)."""
+    if getattr(model, 'num_segments', 1) != 1:
+        raise ValueError(f'the {path} path needs an engine with num_segments=1 (engine.{factory})')
+    if (model.height, model.width) != (crop, crop):
+        raise ValueError(f'the engine takes {model.height} x {model.width} frames, the transform crops to {crop}')

@@ -30,6 +30,8 @@
  *   tsm_preprocess_indexed build_test_transform(person_crop=False) over FrameDataset's sampled frames: one launch from staged raw
  *                          frames through a device index table (sample_frames(total, 8, start, random=False) per labelled
  *                          segment)   datasets/common.py:99-117, datasets/transform.py:16-65, datasets/build.py:131-136
+ *   tsm_preprocess_windows either test transform over the windows of one step of a stream server: frame sizes differ per
+ *                          window, optional person box per window   utils/inference_count.py:285-339, app/inference.py:87-111
  *   tsm_scores_to_states   per clip: to_softmax, first arg-max, score >= 0.5 ? class : -1
  *                          workoutdetector/utils/eval.py:153-164, utils/visualize.py:140-150
  *   tsm_preprocess_image   data_transform of the image model: ToPILImage -> Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize
@@ -416,6 +418,34 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
 int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, const int32_t *index,
                            int32_t n_clips, int32_t n_segment, float *out, int32_t out_layout, int32_t resize, int32_t crop,
                            int32_t scale_255, void *stream);
+
+/* Either test transform over windows of DIFFERENT frame sizes (device pointers), straight from RAW frames to the input of
+ * tsm_forward in ONE launch, in batch order -- a step of a stream server (StreamBatcher), whose streams differ in resolution
+ * and complete their windows together; with person_crop = 1 the reference's accuracy option on streams.
+ * arena:  one device allocation of arena_bytes, 16-byte aligned, holding every window's frames; pixel: TSM_PIXEL_U8 or
+ *         TSM_PIXEL_F32 (values 0..255) for the whole launch.
+ * desc:   DEVICE int32 [n_windows, 8], 16-byte aligned; row c = {off_lo, off_hi, h, w, top, left, bh, bw}:
+ *           off = off_hi * 2^32 + (unsigned) off_lo, the byte offset in `arena` of window c's first frame; its n_segment
+ *                 frames are contiguous [n_segment, h, w, 3] of `pixel`;
+ *           (top, left, bh, bw): the window's person box in source-frame pixels; read with person_crop = 1 only.
+ * out:    [n_windows, n_segment, ...one frame] in out_layout; out_layout, scale_255 as tsm_preprocess.
+ *   person_crop = 0: out[c][k] = tsm_preprocess' result (resize, crop) for frame k of window c, the Resize / CenterCrop
+ *     geometry computed on the device from the window's own h, w in integers -- the same per-pixel code, so the row equals
+ *     that frame's row from tsm_preprocess bit for bit.
+ *   person_crop = 1: out[c][k] = tsm_preprocess_clips' result (size = crop; `resize` is not used) for that frame under the
+ *     window's box, by its rules -- zero fill where the box leaves the frame, bh <= 0 or bw <= 0 = the whole frame -- and the
+ *     same per-pixel code: bit for bit that row.
+ * Validated on the host before the launch (TSM_ERR_INVALID_ARG, nothing launched): non-NULL pointers, `arena` and `desc`
+ * 16-byte aligned, positive sizes, pixel type and layout, person_crop 0 or 1, crop <= resize with person_crop = 0.  The
+ * TABLE cannot be validated (device memory): the kernel is total in it.  A descriptor is valid only if off >= 0,
+ * off % 16 == 0, 1 <= h, w <= 65535 and off + n_segment * h * w * 3 * (bytes per channel) <= arena_bytes -- and, with
+ * person_crop = 0, the crop fits the resized frame; the test is formed in 64 bits without overflow for ANY int32 words
+ * (INT32_MIN and INT32_MAX included) before an address exists.  Every row of an invalid window is the normalised zero frame,
+ * every channel (0 - mean) / std, and nothing is read for it; the box is total as in tsm_preprocess_clips.  One grid-stride
+ * launch: n_windows is not limited by the launch geometry.  Enqueues on `stream`; no synchronisation. */
+int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel, const int32_t *desc,
+                           int32_t n_windows, int32_t n_segment, int32_t person_crop, float *out,
+                           int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream);
 
 /* feat [n_clips*T, hw, c] NHWC -> logits [n_clips, num_class]; fc_w [num_class, c], fc_b. */
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits,

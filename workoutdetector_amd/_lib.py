@@ -44,7 +44,7 @@ class TsmConvArgs(C.Structure):
 EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_consensus', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
            'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_head_segments', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_preprocess_clips', 'tsm_scores_to_states', 'tsm_preprocess_image', 'tsm_frame_votes',
-           'tsm_preprocess_indexed', 'tsm_top1_tally', 'tsm_forward_features', 'tsm_pool_features', 'tsm_cosine_distances')
+           'tsm_preprocess_indexed', 'tsm_preprocess_windows', 'tsm_top1_tally', 'tsm_forward_features', 'tsm_pool_features', 'tsm_cosine_distances')
 
 _lib: Optional[C.CDLL] = None
 
@@ -133,6 +133,8 @@ def load() -> C.CDLL:
     lib.tsm_frame_votes.argtypes = [fp, i32, i32, vp, i32, vp, vp, vp, vp]
     lib.tsm_preprocess_indexed.restype = C.c_int
     lib.tsm_preprocess_indexed.argtypes = [vp, i32, i64, i32, i32, vp, i32, i32, fp, i32, i32, i32, i32, vp]
+    lib.tsm_preprocess_windows.restype = C.c_int
+    lib.tsm_preprocess_windows.argtypes = [vp, i64, i32, vp, i32, i32, i32, fp, i32, i32, i32, i32, vp]
     lib.tsm_top1_tally.restype = C.c_int
     lib.tsm_top1_tally.argtypes = [fp, vp, i32, i32, vp, vp, vp, vp]
     lib.tsm_forward_features.restype = C.c_int

@@ -1033,7 +1033,7 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
 
 }  // namespace
 
-// ---- the frame transforms (tsm_preprocess, _clips, _indexed, _image): their shared argument checks ----------------------------
+// ---- the frame transforms (tsm_preprocess, _clips, _indexed, _windows, _image): their shared argument checks ----------------------------
 static int check_pixel(int32_t pixel) {
   if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
   return TSM_OK;
@@ -1881,6 +1881,31 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
   hipError_t st = tsm::launch_preprocess_indexed(q, static_cast<hipStream_t>(stream));
   if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
                                     std::string("preprocess_indexed: ") + hipGetErrorString(st));
+  return TSM_OK;
+}
+
+int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel, const int32_t *desc,
+                           int32_t n_windows, int32_t n_segment, int32_t person_crop, float *out,
+                           int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream) {
+  if (!arena || !desc || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: null pointer");
+  if ((reinterpret_cast<uintptr_t>(arena) & 15) != 0 || (reinterpret_cast<uintptr_t>(desc) & 15) != 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: arena and desc must be 16-byte aligned");
+  if (arena_bytes <= 0 || n_windows <= 0 || n_segment <= 0 || resize <= 0 || crop <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: non-positive size");
+  if (int rc = check_pixel(pixel)) return rc;
+  if (int rc = check_out_layout(out_layout)) return rc;
+  if (person_crop != 0 && person_crop != 1) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: person_crop must be 0 or 1");
+  if (!person_crop && crop > resize)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: crop larger than the resized frame");
+  tsm::WindowPreprocParams p{};
+  p.arena = arena; p.dst = out; p.desc = desc; p.arena_bytes = arena_bytes; p.n_windows = n_windows; p.n_segment = n_segment;
+  p.person_crop = person_crop; p.resize = resize; p.crop = crop;
+  p.src_is_u8 = pixel == TSM_PIXEL_U8;
+  p.out_mode = out_mode_of(out_layout);
+  p.pre_scale = pre_scale_of(scale_255);
+  hipError_t st = tsm::launch_preprocess_windows(p, static_cast<hipStream_t>(stream));
+  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
+                                    std::string("preprocess_windows: ") + hipGetErrorString(st));
   return TSM_OK;
 }
 

@@ -196,6 +196,49 @@ inline bool center_crop_geometry(int h, int w, int resize, int crop, CropGeometr
   return true;
 }
 
+// ---- tsm_preprocess_windows: the per-window arithmetic its kernel runs, as pure-integer functions that compile for the host
+// too, so that the kernel's bounds logic is tested on a CPU (tests/windows_host.cpp, under ASAN + UBSAN) before it runs on a GPU.
+#if defined(__HIPCC__)
+#define TSM_HOST_DEVICE __host__ __device__
+#else
+#define TSM_HOST_DEVICE
+#endif
+
+// center_crop_geometry in integers: the long side is resize * long / short in int64 (the double quotient above truncates to
+// the same integer: a non-integral quotient lies at least 1 / 65535 from one, far outside a double's rounding of a product
+// below 2^47), the crop starts at round-half-to-even of (dim - crop) / 2.  Equal to center_crop_geometry for h, w in
+// 1 .. 65535.  False when the crop is larger than the resized frame or the long side does not fit an int32.
+TSM_HOST_DEVICE inline bool center_crop_geometry_int(int h, int w, int resize, int crop, CropGeometry *g) {
+  const int64_t lng = h <= w ? ((int64_t)resize * w) / h : ((int64_t)resize * h) / w;
+  if (lng > INT32_MAX) return false;
+  g->nh = h <= w ? resize : (int)lng;
+  g->nw = h <= w ? (int)lng : resize;
+  if (crop > g->nh || crop > g->nw) return false;
+  const int dh = g->nh - crop, dw = g->nw - crop;       // a half rounds to the even neighbour: up only from an odd floor
+  g->top = (dh >> 1) + (dh & (dh >> 1) & 1);
+  g->left = (dw >> 1) + (dw & (dw >> 1) & 1);
+  return true;
+}
+
+// One window of a tsm_preprocess_windows launch as its descriptor words say it: n_segment contiguous frames [h, w, 3] of
+// elem_bytes (1 or 4) per channel, the first at byte `off` of an arena of arena_bytes (> 0); n_segment, resize, crop > 0.
+// d = {off_lo, off_hi, h, w, top, left, bh, bw}.  True -- for ANY eight int32 words, and no intermediate leaves int64 -- only
+// if off >= 0, off % 16 == 0, 1 <= h, w <= 65535 and off + n_segment * h * w * 3 * elem_bytes <= arena_bytes; with `center`
+// the centre crop must also fit the resized frame, and *g is its geometry.  *off is set whenever the result is true.
+constexpr int kWindowDescWords = 8, kWindowMaxSide = 65535;
+TSM_HOST_DEVICE inline bool window_descriptor_ok(const int32_t d[kWindowDescWords], int n_segment, int elem_bytes, int64_t arena_bytes,
+                                                 bool center, int resize, int crop, int64_t *off, CropGeometry *g) {
+  const int64_t o = (int64_t)(((uint64_t)(uint32_t)d[1] << 32) | (uint32_t)d[0]);
+  const int h = d[2], w = d[3];
+  if (o < 0 || (o & 15) != 0 || h < 1 || h > kWindowMaxSide || w < 1 || w > kWindowMaxSide || o > arena_bytes) return false;
+  const int64_t frame_bytes = (int64_t)h * w * 3 * elem_bytes;       // < 2^36
+  int64_t bytes;
+  if (__builtin_mul_overflow((int64_t)n_segment, frame_bytes, &bytes) || bytes > arena_bytes - o) return false;
+  if (center && !center_crop_geometry_int(h, w, resize, crop, g)) return false;
+  *off = o;
+  return true;
+}
+
 // The buffer frames a range of clip windows touches.  Clip c, segment k is source frame step * c + stride * k; a position at or
 // past total_frames is the padded tail and reads no video frame; buffer frame j holds source frame stride * (first_frame + j).
 // For clips first_clip .. first_clip + n_clips - 1: `tail` = whether any position is padded, `first` = the buffer frame of the

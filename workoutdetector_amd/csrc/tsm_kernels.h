@@ -237,6 +237,26 @@ struct IndexedPreprocParams {
 };
 hipError_t launch_preprocess_indexed(const IndexedPreprocParams &p, hipStream_t s);
 
+// Either test transform over windows of DIFFERENT frame sizes (see preprocess_windows_kernel): window c is n_segment
+// contiguous raw frames [h, w, 3] u8|f32 somewhere in one device arena, described by 8 int32 words of a device table
+// (tsm_host::window_descriptor_ok) -> out [n_windows, n_segment, ...one frame of `crop`] in any out_mode.  person_crop 0:
+// launch_preprocess' transform with the geometry of each window's own size; 1: launch_preprocess_clips' with the window's box.
+// The kernel is total in the TABLE contents, which live in device memory: an invalid descriptor reads nothing and yields
+// the normalised zero frame for every row of its window.
+struct WindowPreprocParams {
+  const void *arena;
+  float *dst;
+  const int *desc;    // device, 16-byte aligned, [n_windows, 8] = {off_lo, off_hi, h, w, top, left, bh, bw}
+  int64_t arena_bytes;
+  int n_windows, n_segment;
+  int person_crop;
+  int resize, crop;   // crop: the output size in both modes
+  int src_is_u8;
+  int out_mode;       // as PreprocParams
+  float pre_scale;
+};
+hipError_t launch_preprocess_windows(const WindowPreprocParams &p, hipStream_t s);
+
 // The image model's per-frame transform (see preprocess_image_kernel): staged uint8 frames [n,h,w,3] -> Pillow's antialiased
 // bilinear resize to nh x nw (integer arithmetic from host-built tables), the crop window (top, left, crop) of it, normalised
 // and packed in any out_mode of PreprocParams.  Tables (device int32, rows for the crop window's output indices only):

@@ -167,8 +167,8 @@ hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStre
 // Frame transforms: staged raw frames [n,h,w,3] u8|f32 -> resized, normalised frames in the engine's input formats.
 // One thread per output group: a pixel (out_mode 0 NHWC4 fp32, 1 NCHW fp32) or a pixel pair (2 split-bf16, 3 bf16: the
 // stem's packed-pair input, see pack_input_kernel); neighbouring threads are neighbouring ox: contiguous 16-byte stores.
-// preprocess_kernel, preprocess_indexed_kernel and preprocess_clips_kernel are ONE row loop (preprocess_rows) over three
-// row sources -- which frame, and which window of it, output row f shows -- and two samplers over one bilinear-and-
+// preprocess_kernel, preprocess_indexed_kernel, preprocess_clips_kernel and preprocess_windows_kernel are ONE row loop
+// (preprocess_rows) over four row sources -- which frame, and which window of it, output row f shows -- and two samplers over one bilinear-and-
 // normalise core; preprocess_image_kernel (Pillow's antialiased resample, further down) shares the constants and the
 // group writer.  Bilinear sampling follows ATen's CPU kernel (UpSampleBilinear2d, no antialias): src = scale * (dst + 0.5)
 // - 0.5 clamped at 0, scale = in / out, out = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11); then
@@ -375,11 +375,40 @@ hipError_t launch_gather_clips(const GatherParams &p_in, hipStream_t s) {
 //   * no person: bh <= 0 or bw <= 0 stands for the whole frame (0, 0, h, w) (transform.py:254 `if w * h == 0: return images`);
 //   * padded tail: a source index >= total_frames is the reference's zero frame: every channel (0 - mean) / std, nothing is
 //     read and the buffer needs no pad frame.
-// The sampler is preprocess_pixel's arithmetic in box coordinates.
+// The sampler (box_pixel) is preprocess_pixel's arithmetic in box coordinates.
 // TOTAL in the boxes: they live in device memory, so no host check can see them; for ANY int32 contents the kernel reads only
 // inside the frames it was given -- the box index is clamped to the box, the sum with top / left is formed in 64 bits and a
 // tap is read only where 0 <= y < h and 0 <= x < w.  (The frame index is the host's to validate: launch_preprocess_clips.)
 // ---------------------------------------------------------------------------------------------
+// The sampler of the box sources (ClipRows, WindowRows in person-crop mode): preprocess_pixel in the coordinates of a box
+// (top, left, bh, bw; bh, bw > 0) of an h x w frame resized to size x size, total in the box.
+template <typename T>
+__device__ __forceinline__ void box_pixel(const T *frame, int h, int w, int64_t top, int64_t left, int bh, int bw, int size,
+                                          float pre_scale, int oy, int ox, float *v) {
+#pragma clang fp contract(off)
+  const float fy = sample_coord((float)bh / (float)size, (float)oy);
+  const float fx = sample_coord((float)bw / (float)size, (float)ox);
+  // (int) of a float at or above 2^31 is undefined: sides near INT32_MAX are held below it, and the index inside the box
+  const float big = 2147483520.f;
+  int y0 = (int)(fy < big ? fy : big), x0 = (int)(fx < big ? fx : big);
+  y0 = y0 < bh - 1 ? y0 : bh - 1;
+  x0 = x0 < bw - 1 ? x0 : bw - 1;
+  const int y1 = y0 + (y0 < bh - 1 ? 1 : 0), x1 = x0 + (x0 < bw - 1 ? 1 : 0);
+  const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
+  // image coordinates of the four taps, in 64 bits (top + y0 leaves int32 for a hostile box); a tap outside the frame is 0
+  const int64_t iy0 = top + y0, iy1 = top + y1, ix0 = left + x0, ix1 = left + x1;
+  const bool vy0 = iy0 >= 0 && iy0 < h, vy1 = iy1 >= 0 && iy1 < h;
+  const bool vx0 = ix0 >= 0 && ix0 < w, vx1 = ix1 >= 0 && ix1 < w;
+  // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
+  const T *r0 = frame + (vy0 ? iy0 : 0) * w * 3, *r1 = frame + (vy1 ? iy1 : 0) * w * 3;
+  const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
+  const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    v[c] = bilinear_normalised(vy0 && vx0 ? (float)a00[c] : 0.f, vy0 && vx1 ? (float)a01[c] : 0.f,
+                               vy1 && vx0 ? (float)a10[c] : 0.f, vy1 && vx1 ? (float)a11[c] : 0.f, w0, w1, h0, h1, pre_scale, c);
+}
+
 template <typename T>
 struct ClipRows {
   const ClipPreprocParams &p;
@@ -405,30 +434,8 @@ struct ClipRows {
     r->frame = static_cast<const T *>(p.src) + (s / p.clip_stride - p.first_frame) * (int64_t)p.h * p.w * 3;
     return true;
   }
-  // the sampler: preprocess_pixel in box coordinates, total in the box
   __device__ __forceinline__ void pixel(const Row &r, int oy, int ox, float *v) const {
-#pragma clang fp contract(off)
-    const float fy = sample_coord((float)r.bh / (float)p.size, (float)oy);
-    const float fx = sample_coord((float)r.bw / (float)p.size, (float)ox);
-    // (int) of a float at or above 2^31 is undefined: sides near INT32_MAX are held below it, and the index inside the box
-    const float big = 2147483520.f;
-    int y0 = (int)(fy < big ? fy : big), x0 = (int)(fx < big ? fx : big);
-    y0 = y0 < r.bh - 1 ? y0 : r.bh - 1;
-    x0 = x0 < r.bw - 1 ? x0 : r.bw - 1;
-    const int y1 = y0 + (y0 < r.bh - 1 ? 1 : 0), x1 = x0 + (x0 < r.bw - 1 ? 1 : 0);
-    const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
-    // image coordinates of the four taps, in 64 bits (top + y0 leaves int32 for a hostile box); a tap outside the frame is 0
-    const int64_t iy0 = r.top + y0, iy1 = r.top + y1, ix0 = r.left + x0, ix1 = r.left + x1;
-    const bool vy0 = iy0 >= 0 && iy0 < p.h, vy1 = iy1 >= 0 && iy1 < p.h;
-    const bool vx0 = ix0 >= 0 && ix0 < p.w, vx1 = ix1 >= 0 && ix1 < p.w;
-    // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
-    const T *r0 = r.frame + (vy0 ? iy0 : 0) * p.w * 3, *r1 = r.frame + (vy1 ? iy1 : 0) * p.w * 3;
-    const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
-    const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      v[c] = bilinear_normalised(vy0 && vx0 ? (float)a00[c] : 0.f, vy0 && vx1 ? (float)a01[c] : 0.f,
-                                 vy1 && vx0 ? (float)a10[c] : 0.f, vy1 && vx1 ? (float)a11[c] : 0.f, w0, w1, h0, h1, p.pre_scale, c);
+    box_pixel<T>(r.frame, p.h, p.w, r.top, r.left, r.bh, r.bw, p.size, p.pre_scale, oy, ox, v);
   }
 };
 
@@ -486,6 +493,83 @@ hipError_t launch_preprocess_indexed(const IndexedPreprocParams &q, hipStream_t 
   if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3)
     return hipErrorInvalidValue;
   TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, q.n_rows, p.crop, p.out_mode, s, q);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// preprocess_windows: either test transform over windows of DIFFERENT frame sizes, one launch from raw frames to the engine's
+// packed input in batch order -- a step of StreamBatcher, whose streams (phones, webcams, uploaded clips) differ in
+// resolution.  Output row f is frame f % n_segment of window f / n_segment; the window's 8-dword descriptor {off_lo, off_hi,
+// h, w, top, left, bh, bw} says where its n_segment contiguous frames [h, w, 3] start in the arena (a byte offset) and, in
+// person-crop mode, its box.  The descriptor is the same for (nearly) every thread of a wave: two 16-byte loads.
+//   * person_crop 0: Resize(resize) + CenterCrop(crop) with the geometry of THIS window's size, computed here in integers
+//     (tsm_host::center_crop_geometry_int = the host's center_crop_geometry), the pixel preprocess_pixel's: a row equals
+//     preprocess_kernel's row for the same frame bit for bit.  The box words are ignored.
+//   * person_crop 1: the box -> Resize((crop, crop)) by box_pixel, preprocess_clips' rules (zero fill, bh <= 0 or bw <= 0 =
+//     the whole frame): a row equals preprocess_clips_kernel's row for the same frame and box bit for bit.
+// TOTAL in the table: it lives in device memory, so no host check can see it.  tsm_host::window_descriptor_ok decides, in
+// int64 without overflow for ANY int32 words, whether the window lies in the arena (and, mode 0, whether the crop fits the
+// resized frame) BEFORE an address is formed; every row of a window that fails is the normalised zero frame and reads nothing.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+struct WindowRows {
+  const WindowPreprocParams &p;
+  struct Row {
+    const T *frame;
+    int h, w;
+    int top, left;      // mode 0: the crop window's corner in the resized frame; mode 1: the box's corner in the source frame
+    int sh, sw;         // mode 0: the resized size (nh, nw); mode 1: the box's size (bh, bw)
+  };
+  __device__ __forceinline__ bool locate(int64_t f, Row *r) const {
+    const int64_t c = f / p.n_segment;
+    const int k = (int)(f - c * p.n_segment);
+    typedef int desc_t __attribute__((ext_vector_type(4)));         // (16-byte aligned: the launcher checks the table's base)
+    const desc_t *dp = reinterpret_cast<const desc_t *>(p.desc) + c * 2;
+    const desc_t lo = dp[0], hi = dp[1];
+    const int32_t d[tsm_host::kWindowDescWords] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    int64_t off;
+    tsm_host::CropGeometry g;
+    if (!tsm_host::window_descriptor_ok(d, p.n_segment, (int)sizeof(T), p.arena_bytes, !p.person_crop, p.resize, p.crop, &off, &g))
+      return false;
+    r->h = d[2];
+    r->w = d[3];
+    r->frame = reinterpret_cast<const T *>(static_cast<const char *>(p.arena) + off) + (int64_t)k * r->h * r->w * 3;
+    if (p.person_crop) {
+      const bool person = d[6] > 0 && d[7] > 0;
+      r->top = person ? d[4] : 0;
+      r->left = person ? d[5] : 0;
+      r->sh = person ? d[6] : r->h;
+      r->sw = person ? d[7] : r->w;
+    } else {
+      r->top = g.top;
+      r->left = g.left;
+      r->sh = g.nh;
+      r->sw = g.nw;
+    }
+    return true;
+  }
+  __device__ __forceinline__ void pixel(const Row &r, int oy, int ox, float *v) const {
+    if (p.person_crop) {
+      box_pixel<T>(r.frame, r.h, r.w, r.top, r.left, r.sh, r.sw, p.crop, p.pre_scale, oy, ox, v);
+    } else {
+      PreprocParams q;            // (preprocess_pixel reads only these)
+      q.h = r.h; q.w = r.w; q.nh = r.sh; q.nw = r.sw; q.top = r.top; q.left = r.left; q.pre_scale = p.pre_scale;
+      preprocess_pixel<T>(q, r.frame, oy, ox, v);
+    }
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) preprocess_windows_kernel(const WindowPreprocParams p) {
+  preprocess_rows(p.dst, p.out_mode, p.crop, (int64_t)p.n_windows * p.n_segment, WindowRows<T>{p});
+}
+
+hipError_t launch_preprocess_windows(const WindowPreprocParams &p, hipStream_t s) {
+  if (!p.arena || !p.dst || !p.desc || (reinterpret_cast<uintptr_t>(p.arena) & 15) != 0 || (reinterpret_cast<uintptr_t>(p.desc) & 15) != 0 ||
+      p.arena_bytes <= 0 || p.n_windows <= 0 || p.n_segment <= 0 || p.resize <= 0 || p.crop <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
+      (p.person_crop != 0 && p.person_crop != 1) || (!p.person_crop && p.crop > p.resize))
+    return hipErrorInvalidValue;
+  TSM_LAUNCH_ROWS(preprocess_windows_kernel, p.src_is_u8, (int64_t)p.n_windows * p.n_segment, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 

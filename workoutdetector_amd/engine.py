@@ -807,6 +807,39 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
     return out
 
 
+def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_crop: bool = False, resize: int = 256,
+                       crop: int = 224, scale_255: bool = False, layout: Optional[int] = None, out=None):
+    """Either test transform over windows of different frame sizes (``tsm_preprocess_windows``), one launch from raw frames
+    to the engine's input, in batch order: what one step of ``StreamBatcher`` needs.
+
+    arena: contiguous CUDA uint8 or float32 tensor (values 0..255; any shape) holding every window's frames; desc: contiguous
+    CUDA int32 [n_windows, 8], row c = (off_lo, off_hi, h, w, top, left, bh, bw) -- window c is ``n_segment`` contiguous
+    frames [h, w, 3] from byte ``off`` of the arena on (``transform.window_descriptors`` builds and validates the table).
+    ``person_crop=False``: Resize(resize) + CenterCrop(crop) + Normalize, every row bit for bit ``preprocess_frames``' row for
+    that frame; ``True``: the window's box -> Resize((crop, crop)) -> Normalize, bit for bit ``preprocess_clips``' row.  Returns
+    float32 [n_windows, n_segment, ...one frame] in the layouts of ``preprocess_frames`` (default LAYOUT_NTHWC4).  The kernel
+    is total in the table: a window whose descriptor does not lie in the arena (or whose centre crop does not fit) reads
+    nothing and yields normalised zero frames."""
+    import torch
+    if not (hasattr(arena, 'is_cuda') and arena.is_cuda and arena.dtype in (torch.uint8, torch.float32) and arena.is_contiguous()
+            and arena.numel() > 0 and arena.data_ptr() % 16 == 0):
+        raise ValueError('arena must be a contiguous, 16-byte aligned, non-empty uint8 or float32 CUDA tensor')
+    n_windows, n_segment = int(n_windows), int(n_segment)
+    if n_windows <= 0 or n_segment <= 0:
+        raise ValueError(f'n_windows and n_segment must be positive, got {n_windows}, {n_segment}')
+    if not (hasattr(desc, 'is_cuda') and desc.is_cuda and desc.device == arena.device and desc.dtype == torch.int32
+            and tuple(desc.shape) == (n_windows, 8) and desc.is_contiguous() and desc.data_ptr() % 16 == 0):
+        raise ValueError(f'desc must be a contiguous, 16-byte aligned int32 tensor [{n_windows}, 8] on {arena.device}')
+    if layout is None:
+        layout = _lib.LAYOUT_NTHWC4
+    out = _out(out, (n_windows, n_segment) + _frame_shape(layout, crop), torch.float32, arena)
+    pixel = _lib.PIXEL_U8 if arena.dtype == torch.uint8 else _lib.PIXEL_F32
+    _lib.check(_lib.load().tsm_preprocess_windows(arena.data_ptr(), arena.numel() * arena.element_size(), pixel, desc.data_ptr(),
+                                                  n_windows, n_segment, int(bool(person_crop)), out.data_ptr(), layout,
+                                                  int(resize), int(crop), int(scale_255), _stream(arena)))
+    return out
+
+
 def top1_tally(logits, labels, correct, total, out=None):
     """The accuracy tally on the GPU (``tsm_top1_tally``; the intent of scripts/eval_classification.py:42-49): CUDA float32
     logits [n, num_class] and int32 labels [n] -> int32 ``pred`` [n], the first arg-max per row (numpy.argmax's tie rule),

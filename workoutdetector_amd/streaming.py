@@ -8,6 +8,10 @@ frames, ``input_queue.clear()``) and the WebSocket loop of ``app/inference.py:87
 engine as ONE batch (fused HIP transform + ``tsm_forward``), then feeds each stream's incremental counter.
 The reference runs one blocking batch-1 ``session.run`` per client window.
 
+``person_crop=True`` is the reference's accuracy option (``build_test_transform(person_crop=True)``, datasets/build.py:123-129)
+on streams: ``push(..., box=)`` carries the detector's first box of a frame, a window is cropped to the union of its frames'
+boxes (``transform.person_box``).  The detector and any tracker stay the caller's.
+
 No transport here (the WebSocket/HTTP front is outside the hot path): a server
 calls ``push`` from its receive loop and ``step`` on a timer or whenever ``ready()`` is large enough.
 """
@@ -22,7 +26,7 @@ import torch
 
 from .counting import RepCounter, scores_to_preds
 from .inference_count import NUM_SEGMENTS, _engine_device, need_clip_rows
-from .transform import TestTransform, build_test_transform
+from .transform import Box, PersonCropTransform, TestTransform, build_test_transform, person_box, window_descriptors
 
 
 @dataclass
@@ -30,6 +34,8 @@ class StreamState:
     counter: RepCounter
     frames: List[np.ndarray] = field(default_factory=list)        # frames of the window being filled (host path)
     windows: Deque[object] = field(default_factory=deque)         # complete [8,H,W,3] uint8 windows not yet run
+    crops: Deque[Optional[Box]] = field(default_factory=deque)    # one per entry of `windows`: its person box, None = whole frame
+    boxes: List[Tuple[float, ...]] = field(default_factory=list)  # detector boxes pushed with the frames of the window being filled
     states: List[int] = field(default_factory=list)               # one state per processed window
     frames_seen: int = 0
     cur: Optional[torch.Tensor] = None                            # HIP path: page-locked window being filled
@@ -41,19 +47,26 @@ class StreamBatcher:
     stream in batches of at most ``max_batch`` and returns ``{stream_id: [(window_index, state, count), ...]}``.
 
     Windows are non-overlapping with stride 8 like the reference's streaming loop; ``softmax``/``threshold``
-    follow utils/eval.py:153-164; frame sizes may differ between streams (windows are transformed per source
-    resolution, then batched at 224x224)."""
+    follow utils/eval.py:153-164; frame sizes may differ between streams (a batch of mixed sizes is still ONE transform
+    launch, ``tsm_preprocess_windows``, in batch order at 224x224).
+
+    ``person_crop=True``: ``push(stream_id, frame, box=(x1, y1, x2, y2))`` takes the detector's first box of that frame; a
+    complete window is cropped to ``transform.person_box`` of the boxes pushed with its frames and resized to the crop size
+    without keeping the aspect ratio; a window none of whose frames came with a box is "no person": the whole frame."""
 
     def __init__(self, model, threshold: float = 0.5, softmax: bool = True, step: int = 8, max_batch: int = 32,
                  transform: Optional[TestTransform] = None,
                  on_window: Optional[Callable[[Hashable, int, int, int], None]] = None,
-                 max_pinned_bytes: int = 1 << 30, max_free_per_shape: int = 64):
+                 max_pinned_bytes: int = 1 << 30, max_free_per_shape: int = 64, person_crop: bool = False):
         need_clip_rows(model, 'StreamBatcher')
         self.model = model
         self.threshold, self.softmax, self.step_frames = threshold, softmax, step
         self.max_batch = max_batch
         self.transform = transform or build_test_transform(False)
         self.on_window = on_window
+        self.person_crop = bool(person_crop)
+        # (host path: the torch person-crop transform at this transform's output size; its box comes with each call)
+        self._crop_transform = PersonCropTransform({}, size=self.transform.crop, scale_255=self.transform.scale_255)
         self.streams: Dict[Hashable, StreamState] = {}
         # HIP path: every frame is copied into a page-locked [8,H,W,3] window buffer when it ARRIVES (push), so that a
         # complete window is one DMA away from the GPU when step() runs -- the 1.8-MB host gather of a 360x206 window
@@ -73,7 +86,13 @@ class StreamBatcher:
             self.streams[stream_id] = StreamState(RepCounter(self.step_frames))
         return self.streams[stream_id]
 
-    def push(self, stream_id: Hashable, frame) -> None:
+    def push(self, stream_id: Hashable, frame, box=None) -> None:
+        if box is not None:
+            if not self.person_crop:
+                raise ValueError('a box needs StreamBatcher(person_crop=True)')
+            box = tuple(float(v) for v in np.asarray(box, dtype=np.float64).reshape(-1))
+            if len(box) != 4 or not all(np.isfinite(box)):
+                raise ValueError(f'box must be four finite numbers (x1, y1, x2, y2), got {box}')
         st = self.open(stream_id)
         arr = np.asarray(frame)
         if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
@@ -84,18 +103,37 @@ class StreamBatcher:
                 st.cur, st.n_cur = self._take_window(tuple(arr.shape)), 0
             elif tuple(st.cur.shape[1:]) != tuple(arr.shape):
                 raise ValueError('frame size changed inside a window')
+            if box is not None:
+                st.boxes.append(box)
             st.cur[st.n_cur].copy_(torch.from_numpy(np.ascontiguousarray(arr)))
             st.n_cur += 1
             if st.n_cur == NUM_SEGMENTS:
-                st.windows.append(st.cur)
-                st.cur = None                   # input_queue.clear() of the reference
+                buf, st.cur = st.cur, None      # input_queue.clear() of the reference
+                self._complete(st, buf)
             return
         if st.frames and st.frames[0].shape != arr.shape:
             raise ValueError('frame size changed inside a window')
+        if box is not None:
+            st.boxes.append(box)
         st.frames.append(arr)
         if len(st.frames) == NUM_SEGMENTS:
-            st.windows.append(np.stack(st.frames))
-            st.frames = []                      # input_queue.clear() of the reference
+            frames, st.frames = st.frames, []   # input_queue.clear() of the reference
+            self._complete(st, np.stack(frames))
+
+    def _complete(self, st: StreamState, window) -> None:
+        """Queue a complete window with its crop box: ``person_box`` over the boxes that came with its frames (the union,
+        enlarged by 10 %; datasets/transform.py:247-259), None -- the whole frame -- when none came or the union is empty.
+        A union that the enlargement leaves with a side of 0 pixels raises ValueError as ``person_box`` does (the reference
+        fails inside Resize there); that window is dropped."""
+        boxes, st.boxes = st.boxes, []
+        try:
+            crop = person_box(boxes) if boxes else None
+        except ValueError:
+            if isinstance(window, torch.Tensor):
+                self._give_back(window)
+            raise
+        st.windows.append(window)
+        st.crops.append(crop)
 
     def _recycle(self, wait: bool = False) -> None:
         """Window buffers whose upload has finished go back to the free lists (capped per shape; the surplus and every
@@ -159,39 +197,40 @@ class StreamBatcher:
         return st.counter.count, list(st.counter.reps)
 
     # ---- compute ------------------------------------------------------------------------------------------
-    def _logits(self, windows: List[object]):
-        """[n,8,H,W,3] uint8 windows (possibly of different sizes) -> raw logits [n, num_class]: a CUDA tensor that is
-        still being computed on the HIP path (the caller syncs once per step), an ndarray on the duck-typed CPU path."""
+    def _logits(self, windows: List[object], crops: List[Optional[Box]]):
+        """[n,8,H,W,3] uint8 windows (possibly of different sizes) and their person boxes -> raw logits [n, num_class]: a CUDA
+        tensor that is still being computed on the HIP path (the caller syncs once per step), an ndarray on the duck-typed
+        CPU path."""
         dev = self._dev
+        tf = self.transform
         if dev is not None:
-            from .engine import preprocess_frames
-            layout = self.model.packed_layout
-            by_shape: Dict[Tuple[int, ...], List[int]] = {}
-            for i, w in enumerate(windows):     # one transform launch per source resolution
-                by_shape.setdefault(tuple(w.shape), []).append(i)
-            clips = None
-            for shape, idx in by_shape.items():
-                # the windows are already page-locked (filled at push time): one DMA each, straight into place
-                if len(idx) == 1:
-                    fr = windows[idx[0]].to(dev, non_blocking=True)
-                else:
-                    fr = torch.empty((len(idx) * shape[0],) + tuple(shape[1:]), dtype=torch.uint8, device=dev)
-                    for j, i in enumerate(idx):
-                        fr[j * shape[0]:(j + 1) * shape[0]].copy_(windows[i], non_blocking=True)
-                done = torch.cuda.Event()
-                done.record()
-                self._inflight += [(done, windows[i]) for i in idx]
-                pk = preprocess_frames(fr, resize=self.transform.size, crop=self.transform.crop,
-                                       scale_255=self.transform.scale_255, layout=layout)
-                pk = pk.view((len(idx), NUM_SEGMENTS) + tuple(pk.shape[1:]))
-                if len(by_shape) == 1:
-                    clips = pk
-                else:
-                    if clips is None:
-                        clips = torch.empty((len(windows),) + tuple(pk.shape[1:]), dtype=pk.dtype, device=dev)
-                    clips[torch.tensor(idx, device=dev)] = pk
-            return self.model.forward_device(clips.contiguous(), layout=layout)
-        xs = [self.transform(torch.from_numpy(w).permute(0, 3, 1, 2).float()) for w in windows]
+            from .engine import preprocess_windows
+            # every window into ONE device arena (they are already page-locked, filled at push time: one DMA each, each start
+            # 16-byte aligned), one small descriptor table, ONE transform launch in batch order for any mix of frame sizes
+            offsets, total = [], 0
+            for w in windows:
+                offsets.append(total)
+                total += (w.numel() + 15) // 16 * 16
+            arena = torch.empty((total,), dtype=torch.uint8, device=dev)
+            for w, off in zip(windows, offsets):
+                arena[off:off + w.numel()].copy_(w.view(-1), non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            self._inflight += [(done, w) for w in windows]
+            table = window_descriptors([tuple(w.shape[1:]) for w in windows], offsets, crops if self.person_crop else None,
+                                       resize=tf.size, crop=tf.crop)
+            # (page-locked staging from torch's caching host allocator: an upload from pageable memory would wait for the
+            #  batches already queued on the stream)
+            staged = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
+            staged.copy_(torch.from_numpy(table))
+            clips = preprocess_windows(arena, staged.to(dev, non_blocking=True), len(windows), NUM_SEGMENTS,
+                                       person_crop=self.person_crop, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255,
+                                       layout=self.model.packed_layout)
+            return self.model.forward_device(clips, layout=self.model.packed_layout)
+        if self.person_crop:
+            xs = [self._crop_transform(torch.from_numpy(w).permute(0, 3, 1, 2).float(), box) for w, box in zip(windows, crops)]
+        else:
+            xs = [tf(torch.from_numpy(w).permute(0, 3, 1, 2).float()) for w in windows]
         name = self.model.get_inputs()[0].name
         return np.asarray(self.model.run(None, {name: torch.stack(xs).numpy()})[0])
 
@@ -201,17 +240,17 @@ class StreamBatcher:
         order: List[Hashable] = []
         pending = []
         while self.ready():
-            batch: List[Tuple[Hashable, np.ndarray]] = []
+            batch: List[Tuple[Hashable, object, Optional[Box]]] = []
             progressed = True
             while len(batch) < self.max_batch and progressed:   # round-robin keeps per-stream order and fairness
                 progressed = False
                 for sid, st in self.streams.items():
                     if st.windows and len(batch) < self.max_batch:
-                        batch.append((sid, st.windows.popleft()))
+                        batch.append((sid, st.windows.popleft(), st.crops.popleft()))
                         progressed = True
             # enqueue only: the host gathers / pins batch i+1 while the GPU still computes batch i
-            pending.append(self._logits([w for _, w in batch]))
-            order += [sid for sid, _ in batch]
+            pending.append(self._logits([w for _, w, _ in batch], [c for _, _, c in batch]))
+            order += [sid for sid, _, _ in batch]
         if pending:
             if isinstance(pending[0], torch.Tensor):
                 # HIP path: softmax / arg-max / threshold on the GPU too (tsm_scores_to_states): one int32 per window

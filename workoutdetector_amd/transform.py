@@ -157,6 +157,43 @@ def build_test_transform(person_crop: bool = False, scale_255: bool = False, box
     return TestTransform(scale_255=scale_255)
 
 
+def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int = INPUT_SIZE) -> np.ndarray:
+    """The descriptor table ``tsm_preprocess_windows`` takes (include/tsm_hip.h), built and VALIDATED on the host: int32
+    [n, 8], row c = ``(off_lo, off_hi, h, w, top, left, bh, bw)``.  ``shapes``: one frame size ``(h, w)`` (or ``(h, w, 3)``)
+    per window; ``offsets``: the byte offset of each window's first frame in the arena.  ``boxes=None`` builds a centre-crop
+    table (the box words are 0; ``resize`` / ``crop`` are those of the launch); otherwise one box ``(top, left, h, w)`` or
+    None ("no person": the all-zero box the kernel reads as the whole frame) per window.
+
+    The kernel is total in this table and turns an invalid row into zero frames; a caller who builds the table here gets an
+    error instead: ValueError for a side outside 1 .. 65535, an offset that is negative or no multiple of 16, a centre crop
+    larger than the resized frame, a box that is not four integers of the int32 range."""
+    shapes, offsets = list(shapes), list(offsets)
+    if len(shapes) != len(offsets) or (boxes is not None and len(boxes) != len(shapes)):
+        raise ValueError('shapes, offsets and boxes must have one entry per window')
+    desc = np.zeros((len(shapes), 8), dtype=np.int32)
+    for c, (shape, off) in enumerate(zip(shapes, offsets)):
+        shape = tuple(shape)
+        if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3) or not all(isinstance(d, (int, np.integer)) for d in shape):
+            raise ValueError(f'window {c}: shape must be (h, w) or (h, w, 3), got {shape}')
+        h, w = int(shape[0]), int(shape[1])
+        if not (1 <= h <= 65535 and 1 <= w <= 65535):
+            raise ValueError(f'window {c}: frame sides must lie in 1 .. 65535, got {h} x {w}')
+        if not isinstance(off, (int, np.integer)) or off < 0 or off % 16 != 0 or off >= 1 << 63:
+            raise ValueError(f'window {c}: offset must be a non-negative multiple of 16 bytes, got {off!r}')
+        off = int(off)
+        desc[c, :4] = ((off & 0xFFFFFFFF) - ((off & 0x80000000) << 1), off >> 32, h, w)
+        if boxes is None:
+            nh, nw = resized_hw(h, w, resize)
+            if crop > nh or crop > nw:
+                raise ValueError(f'window {c}: crop {crop} larger than the resized frame {nh} x {nw}')
+        elif boxes[c] is not None:
+            box = tuple(boxes[c])
+            if len(box) != 4 or not all(isinstance(v, (int, np.integer)) and -2 ** 31 <= v < 2 ** 31 for v in box):
+                raise ValueError(f'window {c}: box must be four int32 (top, left, h, w) or None, got {boxes[c]!r}')
+            desc[c, 4:] = [int(v) for v in box]
+    return desc
+
+
 # ---- the image model's transform: Pillow's 8-bit bilinear resample, to the bit ------------------------------------------
 PRECISION_BITS = 32 - 8 - 2         # Pillow's fixed point: weights are scaled by 2^22
 

@@ -337,7 +337,9 @@ typedef struct tsm_conv_args {
  * split forms' segment scratch too).  Refusals come before any launch: TSM_ERR_INVALID_ARG for a shift_target of 1 with
  * nothing to shift, a second source with a residual, 2 * fold above the shifted tensor's channels, n % T != 0 or mismatched
  * sizes; TSM_ERR_UNSUPPORTED for a second source with k != 1 or a fold the dtype's channel groups cannot split (fp32: fold % 4,
- * bf16 formats: fold % 8).  tsm_conv_bn_act is this call with the tile of TSM_CONV_TILE as its code. */
+ * bf16 formats: fold % 8); TSM_ERR_CAPACITY, as tsm_create, for sizes beyond the kernels' 32-bit indices: n * ho * wo output
+ * rows, or the elements of the input, the output, the second source or the packed weights, at or above 2^31, or a padded K
+ * that does not fit an int.  tsm_conv_bn_act is this call with the tile of TSM_CONV_TILE as its code. */
 int tsm_conv_op(const tsm_conv_args *a, void *stream);
 
 int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi, int32_t c,

@@ -7,6 +7,10 @@
 //   2. fold_and_pack / fold_and_pack_stem_pairs / to_split / to_bf16 on ragged sizes, with the packed-buffer
 //      invariants checked (every weight lands inside [cout][kp], padding stays zero, split hi+lo == value to 2^-16).
 //   3. clip_window_range against an enumeration and at the ends of int32 / int64, center_crop_geometry against a table.
+//   4. conv_op_check, the rules of tsm_conv_op: one row per refusal (status and message verbatim), the accepted forms the GPU
+//      tests use with their derived plans, and a loop over random and extreme int32 arguments on which it must be total and
+//      every accepted element count below 2^31.
+//   5. layer_geometry / conv_out_size against the per-layer values of ResNet-50, ResNet-18 / 34 and wide-ResNet-50-2.
 #include <climits>
 #include <cstdio>
 #include <random>
@@ -302,12 +306,237 @@ static void check_frame_transform_args() {
   EXPECT(center_crop_geometry(1, i32, 1, 1, &g) && g.nh == 1 && g.nw == i32 && g.left == (i32 - 1) / 2);
 }
 
+// ---- conv_op_check: tsm_conv_op's rules ------------------------------------------------------------------------------------
+static float dummy;   // the check compares pointers with NULL and never reads through them
+static tsm_conv_args conv_args(int dtype, int n, int hw, int cin, int cout, int k, int stride) {
+  tsm_conv_args a{};
+  a.struct_size = sizeof a;
+  a.x = a.w = a.gamma = a.beta = a.mean = a.var = &dummy;
+  a.y = &dummy;
+  a.n = n; a.hi = a.wi = hw; a.cin = cin; a.cout = cout; a.k = k; a.stride = stride; a.dtype = dtype;
+  return a;
+}
+static void second_source(tsm_conv_args &a, int cin2, int hw2, int stride2) {
+  a.x2 = a.w2 = a.gamma2 = a.beta2 = a.mean2 = a.var2 = &dummy;
+  a.cin2 = cin2; a.hi2 = a.wi2 = hw2; a.stride2 = stride2;
+}
+static void shift(tsm_conv_args &a, int T, int fold_div, int target) { a.shift_segments = T; a.fold_div = fold_div; a.shift_target = target; }
+
+static void check_conv_op_refusals() {
+  const char *abi = "tsm_conv_args.struct_size must be sizeof(tsm_conv_args)";
+  {
+    const ConvOpPlan v = conv_op_check(nullptr);
+    EXPECT(v.status == TSM_ERR_INVALID_ARG && std::string(v.message) == abi);
+  }
+  // every row edits an accepted 1x1 (fp32, 16 frames of 4 x 4 x 64 -> 64 channels); messages as tsm_conv_op has always worded them
+  struct Row { void (*edit)(tsm_conv_args &); int status; const char *message; };
+  const Row rows[] = {
+      {[](tsm_conv_args &a) { a.struct_size -= 4; }, TSM_ERR_INVALID_ARG, abi},
+      {[](tsm_conv_args &a) { a.dtype = 3; }, TSM_ERR_UNSUPPORTED, "bad dtype"},
+      {[](tsm_conv_args &a) { a.dtype = -1; }, TSM_ERR_UNSUPPORTED, "bad dtype"},
+      {[](tsm_conv_args &a) { a.x = nullptr; }, TSM_ERR_INVALID_ARG, "NULL pointer"},
+      {[](tsm_conv_args &a) { a.var = nullptr; }, TSM_ERR_INVALID_ARG, "NULL pointer"},
+      {[](tsm_conv_args &a) { a.y = nullptr; }, TSM_ERR_INVALID_ARG, "NULL pointer"},
+      {[](tsm_conv_args &a) { a.n = 0; }, TSM_ERR_INVALID_ARG, "n, hi and wi must be positive"},
+      {[](tsm_conv_args &a) { a.wi = -4; }, TSM_ERR_INVALID_ARG, "n, hi and wi must be positive"},
+      {[](tsm_conv_args &a) { a.k = 5; }, TSM_ERR_UNSUPPORTED, "k must be 1, 3 or 7"},
+      {[](tsm_conv_args &a) { a.stride = 3; }, TSM_ERR_UNSUPPORTED, "stride must be 1 or 2"},
+      {[](tsm_conv_args &a) { a.cin = 48; }, TSM_ERR_UNSUPPORTED, "cin must be 3 (k=7) or a power of two >= 32"},
+      {[](tsm_conv_args &a) { a.cin = 0; }, TSM_ERR_UNSUPPORTED, "cin must be 3 (k=7) or a power of two >= 32"},
+      {[](tsm_conv_args &a) { a.k = 7; a.cin = 4; }, TSM_ERR_UNSUPPORTED, "cin must be 3 (k=7) or a power of two >= 32"},
+      {[](tsm_conv_args &a) { a.dtype = TSM_DTYPE_BF16; a.cin = 32; }, TSM_ERR_UNSUPPORTED, "TSM_DTYPE_BF16 needs cin % 64 == 0"},
+      {[](tsm_conv_args &a) { a.cout = 96; }, TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64"},
+      {[](tsm_conv_args &a) { a.cout = 0; }, TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64"},
+      {[](tsm_conv_args &a) { a.k = 7; a.cin = 3; a.residual = &dummy; }, TSM_ERR_INVALID_ARG, "the 7x7 stem has no residual, second source or shift"},
+      {[](tsm_conv_args &a) { a.k = 7; a.cin = 3; shift(a, 8, 8, 0); }, TSM_ERR_INVALID_ARG, "the 7x7 stem has no residual, second source or shift"},
+      {[](tsm_conv_args &a) { a.shift_target = 2; }, TSM_ERR_INVALID_ARG, "shift_target must be 0 or 1"},
+      {[](tsm_conv_args &a) { a.k = 3; shift(a, 8, 8, 1); }, TSM_ERR_INVALID_ARG, "shift_target 1 needs a residual, a second source or a 1x1 at stride 2"},
+      {[](tsm_conv_args &a) { a.residual = &dummy; shift(a, 8, 8, 0); }, TSM_ERR_INVALID_ARG,
+       "a shifted input with a residual: no such launch (shift_target 1 shifts the residual)"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 4, 1); shift(a, 8, 8, 0); }, TSM_ERR_INVALID_ARG,
+       "a shifted first source with a second source: no such launch"},
+      {[](tsm_conv_args &a) { a.stride = 2; shift(a, 8, 8, 0); }, TSM_ERR_INVALID_ARG, "a shifted 1x1 at stride 2 is the identity's (shift_target 1)"},
+      {[](tsm_conv_args &a) { a.k = 3; second_source(a, 64, 4, 1); }, TSM_ERR_UNSUPPORTED, "a second source needs a 1x1 main conv"},
+      {[](tsm_conv_args &a) { a.residual = &dummy; second_source(a, 64, 4, 1); }, TSM_ERR_INVALID_ARG, "a second source with a residual: no such launch"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 4, 1); a.beta2 = nullptr; }, TSM_ERR_INVALID_ARG, "NULL pointer (second source)"},
+      {[](tsm_conv_args &a) { second_source(a, 96, 4, 1); }, TSM_ERR_UNSUPPORTED, "cin2 must be a power of two >= 32 (TSM_DTYPE_BF16: >= 64)"},
+      {[](tsm_conv_args &a) { a.dtype = TSM_DTYPE_BF16; second_source(a, 32, 4, 1); }, TSM_ERR_UNSUPPORTED,
+       "cin2 must be a power of two >= 32 (TSM_DTYPE_BF16: >= 64)"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 4, 0); }, TSM_ERR_UNSUPPORTED, "stride2 must be 1 or 2"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 9, 2); }, TSM_ERR_INVALID_ARG, "the second source's output size must equal the main conv's"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 0, 1); }, TSM_ERR_INVALID_ARG, "the second source's output size must equal the main conv's"},
+      {[](tsm_conv_args &a) { a.residual = &dummy; shift(a, 3, 8, 1); }, TSM_ERR_INVALID_ARG, "n must be a whole number of T-frame clips"},
+      {[](tsm_conv_args &a) { shift(a, 8, 32, 0); }, TSM_ERR_UNSUPPORTED, "fp32 shifts whole 4-channel groups: fold % 4 == 0"},
+      {[](tsm_conv_args &a) { a.dtype = TSM_DTYPE_BF16X3; a.residual = &dummy; shift(a, 8, 16, 1); }, TSM_ERR_UNSUPPORTED,
+       "the bf16 formats shift whole 8-channel groups: fold % 8 == 0"},
+      {[](tsm_conv_args &a) { a.residual = &dummy; shift(a, 8, 1, 1); }, TSM_ERR_INVALID_ARG, "2 * fold exceeds the shifted tensor's channels"},
+      {[](tsm_conv_args &a) { second_source(a, 64, 4, 1); shift(a, 8, 1, 1); }, TSM_ERR_INVALID_ARG, "2 * fold exceeds the shifted tensor's channels"},
+      {[](tsm_conv_args &a) { a.dtype = TSM_DTYPE_BF16; a.k = 7; a.cin = 3; a.stride = 1; }, TSM_ERR_UNSUPPORTED,
+       "the bf16 formats implement the 7x7 stem for stride 2 only"},
+      // the one new kind: sizes that 32-bit arithmetic cannot hold (they were undefined behaviour)
+      {[](tsm_conv_args &a) { a.k = 3; a.cin = 1 << 30; }, TSM_ERR_CAPACITY, "the padded K (k * k * cin, plus cin2) must fit a 32-bit int"},
+      {[](tsm_conv_args &a) { a.cin = 1 << 30; second_source(a, 1 << 30, 4, 1); }, TSM_ERR_CAPACITY,
+       "the padded K (k * k * cin, plus cin2) must fit a 32-bit int"},
+      {[](tsm_conv_args &a) { a.n = 1 << 20; a.hi = a.wi = 64; }, TSM_ERR_CAPACITY, "n * ho * wo (output rows) must stay below 2^31"},
+      {[](tsm_conv_args &a) { a.n = INT_MAX; a.hi = a.wi = INT_MAX; }, TSM_ERR_CAPACITY, "n * ho * wo (output rows) must stay below 2^31"},
+      {[](tsm_conv_args &a) { a.n = 1 << 15; a.hi = a.wi = 64; }, TSM_ERR_CAPACITY,
+       "the input, the output, the second source and the packed weights must each stay below 2^31 elements"},
+      {[](tsm_conv_args &a) { a.cin = 1 << 16; a.cout = 1 << 16; }, TSM_ERR_CAPACITY,
+       "the input, the output, the second source and the packed weights must each stay below 2^31 elements"},
+  };
+  for (const Row &r : rows) {
+    tsm_conv_args a = conv_args(TSM_DTYPE_F32, 16, 4, 64, 64, 1, 1);
+    EXPECT(conv_op_check(&a).status == TSM_OK);
+    r.edit(a);
+    const ConvOpPlan v = conv_op_check(&a);
+    if (v.status != r.status || std::string(v.message) != r.message) {
+      std::fprintf(stderr, "FAIL refusal row %d: got %d \"%s\", want %d \"%s\"\n", (int)(&r - rows), v.status, v.message, r.status, r.message);
+      ++failures;
+    }
+  }
+}
+
+// The accepted forms of the per-op GPU tests, each plan against values worked out by hand.
+static void check_conv_op_plans() {
+  struct Want { int prec, stem, dual, T, fold, ho, cp, kp, pairs, kp2; long rows, x, y, x2, w; };
+  auto same = [](const tsm_conv_args &a, const Want &w, int line) {
+    const ConvOpPlan v = conv_op_check(&a), &p = v;
+    const bool ok = v.status == TSM_OK && std::string(v.message).empty() && p.prec == w.prec && p.stem == (w.stem != 0) &&
+                    p.dual == (w.dual != 0) && p.T == w.T && p.fold == w.fold && p.ho == w.ho && p.wo == w.ho && p.geo.cp == w.cp &&
+                    p.geo.kp == w.kp && p.geo.stem_pairs == (w.pairs != 0) && p.kp2 == w.kp2 && p.rows == w.rows && p.x_elems == w.x &&
+                    p.y_elems == w.y && p.x2_elems == w.x2 && p.w_elems == w.w;
+    if (!ok) {
+      std::fprintf(stderr, "FAIL plan at line %d: status %d \"%s\"\n", line, v.status, v.message);
+      ++failures;
+    }
+  };
+  tsm_conv_args a = conv_args(TSM_DTYPE_F32, 8, 32, 3, 64, 7, 2);      // the stem: 49 taps x 4 channels = 196 -> 224
+  same(a, {0, 1, 0, 0, 0, 16, 4, 224, 0, 0, 2048, 65536, 131072, 0, 14336}, __LINE__);
+  a.dtype = TSM_DTYPE_BF16X3;                                          // pixel pairs: 7 x 4 x 8 = 224
+  same(a, {1, 1, 0, 0, 0, 16, 4, 224, 1, 0, 2048, 65536, 131072, 0, 14336}, __LINE__);
+  a.dtype = TSM_DTYPE_BF16;                                            // ... rounded up to the bf16 K-step of 64
+  same(a, {2, 1, 0, 0, 0, 16, 4, 256, 1, 0, 2048, 65536, 131072, 0, 16384}, __LINE__);
+  a = conv_args(TSM_DTYPE_F32, 16, 4, 64, 64, 1, 1);                   // 1x1
+  same(a, {0, 0, 0, 0, 0, 4, 64, 64, 0, 0, 256, 16384, 16384, 0, 4096}, __LINE__);
+  shift(a, 8, 8, 0);                                                   // ... its input shifted
+  same(a, {0, 0, 0, 8, 8, 4, 64, 64, 0, 0, 256, 16384, 16384, 0, 4096}, __LINE__);
+  a = conv_args(TSM_DTYPE_BF16, 16, 4, 64, 128, 1, 1);                 // shifted residual: the fold is of cout
+  a.residual = &dummy;
+  shift(a, 8, 8, 1);
+  same(a, {2, 0, 0, 8, 16, 4, 64, 64, 0, 0, 256, 16384, 32768, 0, 8192}, __LINE__);
+  a = conv_args(TSM_DTYPE_F32, 8, 8, 64, 128, 3, 1);                   // 3x3 at stride 1
+  same(a, {0, 0, 0, 0, 0, 8, 64, 576, 0, 0, 512, 32768, 65536, 0, 73728}, __LINE__);
+  a = conv_args(TSM_DTYPE_BF16X3, 8, 9, 64, 128, 3, 2);                // 3x3 at stride 2 of 9 x 9: 5 x 5
+  shift(a, 8, 8, 0);
+  same(a, {1, 0, 0, 8, 8, 5, 64, 576, 0, 0, 200, 41472, 25600, 0, 73728}, __LINE__);
+  a = conv_args(TSM_DTYPE_F32, 16, 4, 64, 64, 1, 1);                   // conv3 + downsample at stride 1, the second source shifted
+  second_source(a, 256, 4, 1);
+  shift(a, 8, 8, 1);
+  same(a, {0, 0, 1, 8, 32, 4, 64, 64, 0, 256, 256, 16384, 16384, 65536, 20480}, __LINE__);
+  second_source(a, 256, 7, 2);                                         // ... at stride 2: 7 x 7 -> 4 x 4
+  a.shift_segments = 0;
+  same(a, {0, 0, 1, 0, 0, 4, 64, 64, 0, 256, 256, 16384, 16384, 200704, 20480}, __LINE__);
+  a = conv_args(TSM_DTYPE_F32, 16, 8, 64, 128, 1, 2);                  // the strided 1x1 of a BasicBlock's identity, shifted
+  shift(a, 8, 8, 1);
+  same(a, {0, 0, 0, 8, 8, 4, 64, 64, 0, 0, 256, 65536, 32768, 0, 8192}, __LINE__);
+}
+
+// Random and extreme int32 arguments: the check is total (UBSAN watches), and whatever it accepts has counts that 32-bit
+// arithmetic holds and that are what the arguments say, recomputed in 128 bits.
+static void fuzz_conv_op_check(unsigned seed, int rounds) {
+  std::mt19937 rng(seed);
+  unsigned wild = 0;   // of 16: how often a field is not one of its likely values (per round: none, a few, most)
+  auto pick = [&rng, &wild](std::initializer_list<int> likely) {
+    const unsigned r = rng() % 16;
+    if (r >= wild) return likely.begin()[rng() % likely.size()];
+    if (r % 3 == 0) return (int)(1u << (rng() % 31));                                   // powers of two up to 2^30
+    if (r % 3 == 1) return (int)rng();
+    const int ends[] = {0, -1, INT_MAX, INT_MIN, -(1 << 30), INT_MAX - 1};
+    return ends[rng() % 6];
+  };
+  int accepted = 0;
+  for (int r = 0; r < rounds; ++r) {
+    wild = r % 3 == 0 ? 0 : r % 3 == 1 ? 2 : 9;
+    tsm_conv_args a = conv_args(pick({0, 1, 2}), pick({1, 8, 16, 64}), 1, pick({3, 32, 64, 256}), pick({64, 128, 512}), pick({1, 3, 7}), pick({1, 2}));
+    a.hi = pick({1, 4, 7, 56});
+    a.wi = pick({1, 4, 7, 56});
+    if (rng() % 4 == 0) a.residual = &dummy;
+    if (rng() % 4 == 0) second_source(a, pick({32, 64, 256}), 1, pick({1, 2}));
+    const int h2 = (int)(2u * (unsigned)a.hi), w2 = (int)(2u * (unsigned)a.wi);   // (wrapping: the sizes may be extreme)
+    a.hi2 = pick({a.hi, h2, (int)((unsigned)h2 - 1u)});
+    a.wi2 = pick({a.wi, w2, (int)((unsigned)w2 - 1u)});
+    shift(a, pick({0, 0, 8}), pick({0, 8, 4}), pick({0, 1}));
+    if (rng() % 64 == 0) a.y = nullptr;
+    const ConvOpPlan v = conv_op_check(&a);
+    EXPECT(v.message != nullptr && (v.status == TSM_OK) == (v.message[0] == 0));
+    if (v.status != TSM_OK) continue;
+    ++accepted;
+    const ConvOpPlan &p = v;
+    typedef __int128 i128;
+    const i128 lim = (i128)1 << 31;
+    EXPECT(p.ho > 0 && p.wo > 0 && p.geo.kp > 0 && p.geo.kp % 32 == 0 && p.kp2 % 32 == 0 && (i128)p.geo.kp + p.kp2 < lim);
+    EXPECT(p.geo.kp >= (p.geo.stem_pairs ? 224 : a.k * a.k * p.geo.cp) && p.kp2 >= (p.dual ? a.cin2 : 0));
+    EXPECT(p.rows == (i128)a.n * p.ho * p.wo && p.rows > 0 && p.rows < lim);
+    EXPECT(p.x_elems == (i128)a.n * a.hi * a.wi * (p.stem ? 8 : a.cin) && p.x_elems > 0 && p.x_elems < lim);
+    EXPECT(p.y_elems == (i128)p.rows * a.cout && p.y_elems > 0 && p.y_elems < lim);
+    EXPECT(p.x2_elems == (p.dual ? (i128)a.n * a.hi2 * a.wi2 * a.cin2 : 0) && p.x2_elems < lim);
+    EXPECT(p.w_elems == (i128)a.cout * (p.geo.kp + p.kp2) && p.w_elems < lim);
+    EXPECT(p.fold >= 0 && (p.T > 0 || p.fold == 0));
+  }
+  EXPECT(accepted > rounds / 50);     // (the loop is not vacuous)
+  std::printf("conv_op_check: %d of %d random argument sets accepted\n", accepted, rounds);
+}
+
+// layer_geometry and conv_out_size against the values the engine's topology has always had: a layer's K is k * k * cin as it
+// stands (every width is a multiple of 64), but the stem's.
+static void check_layer_geometry() {
+  for (int prec : {kPrecF32, kPrecBf16x3, kPrecBf16}) {
+    const LayerGeom stem = layer_geometry(3, 7, 2, prec);
+    EXPECT(stem.cp == 4 && stem.kp == (prec == kPrecBf16 ? 256 : 224) && stem.kseg == 0 && stem.stem_pairs == (prec != kPrecF32));
+    // {cin, k, stride} of conv1 / conv2 / conv3 / downsample, stage by stage
+    const int r50[][3] = {{64, 1, 1},   {64, 3, 1},  {64, 1, 1},  {64, 1, 1},   {256, 1, 1},  {128, 3, 2}, {128, 1, 1}, {256, 1, 2},
+                          {512, 1, 1},  {256, 3, 2}, {256, 1, 1}, {512, 1, 2},  {1024, 1, 1}, {512, 3, 2}, {512, 1, 1}, {1024, 1, 2},
+                          {2048, 1, 1}, {512, 3, 1}};
+    const int wide[][3] = {{64, 1, 1},   {128, 3, 1}, {128, 1, 1}, {256, 1, 1},   {256, 3, 2},  {256, 1, 1},  {512, 1, 1},
+                           {512, 3, 2},  {512, 1, 1}, {1024, 1, 1}, {1024, 3, 2}, {1024, 1, 1}, {2048, 1, 1}, {1024, 3, 1}};
+    const int r18[][3] = {{64, 3, 1}, {64, 3, 2}, {128, 3, 1}, {64, 1, 2}, {128, 3, 2}, {256, 3, 1}, {128, 1, 2}, {256, 3, 2}, {512, 3, 1}, {256, 1, 2}};
+    auto table = [prec](const int (*rows)[3], size_t n) {
+      for (size_t i = 0; i < n; ++i) {
+        const LayerGeom g = layer_geometry(rows[i][0], rows[i][1], rows[i][2], prec);
+        EXPECT(g.cp == rows[i][0] && g.kp == rows[i][1] * rows[i][1] * rows[i][0] && !g.stem_pairs && g.kseg == segment_len(g.kp, prec));
+      }
+    };
+    table(r50, sizeof r50 / sizeof r50[0]);
+    table(wide, sizeof wide / sizeof wide[0]);
+    table(r18, sizeof r18 / sizeof r18[0]);
+  }
+  // the segmented fp32 layers by number: K-steps of 32, segments of about 16
+  EXPECT(layer_geometry(512, 3, 1, kPrecF32).kp == 4608 && layer_geometry(512, 3, 1, kPrecF32).kseg == 16);
+  EXPECT(layer_geometry(128, 3, 2, kPrecF32).kseg == 18 && layer_geometry(1024, 1, 1, kPrecF32).kseg == 16 && layer_geometry(512, 1, 1, kPrecF32).kseg == 0);
+  EXPECT(layer_geometry(3, 7, 1, kPrecBf16).kp == 256 && !layer_geometry(3, 7, 1, kPrecBf16).stem_pairs);   // (only the stride-2 stem reads pairs)
+  EXPECT(conv_out_size(224, 7, 2) == 112 && conv_out_size(112, 3, 2) == 56 && conv_out_size(56, 3, 1) == 56 && conv_out_size(56, 3, 2) == 28 &&
+         conv_out_size(7, 1, 2) == 4 && conv_out_size(33, 7, 2) == 17 && conv_out_size(1, 3, 2) == 1 && conv_out_size(INT_MAX, 7, 1) == INT_MAX &&
+         conv_out_size(INT_MAX, 1, 1) == INT_MAX);
+  EXPECT(prec_of_dtype(TSM_DTYPE_F32) == kPrecF32 && prec_of_dtype(TSM_DTYPE_BF16X3) == kPrecBf16x3 && prec_of_dtype(TSM_DTYPE_BF16) == kPrecBf16 &&
+         prec_of_dtype(3) == -1 && prec_of_dtype(-1) == -1 && prec_of_dtype(INT_MIN) == -1);
+  EXPECT(packed_layout_of(kPrecF32) == TSM_LAYOUT_NTHWC4 && packed_layout_of(kPrecBf16x3) == TSM_LAYOUT_NTHWC8S && packed_layout_of(kPrecBf16) == TSM_LAYOUT_NTHWC8B);
+  std::vector<float> v(64, 1.5f), s3 = v, h = v;
+  to_storage(&v, kPrecF32);
+  to_storage(&s3, kPrecBf16x3);
+  to_storage(&h, kPrecBf16);
+  EXPECT(v.size() == 64 && v[63] == 1.5f && s3.size() == 64 && h.size() == 32);
+}
+
 int main(int argc, char **argv) {
+  check_conv_op_refusals();
+  check_conv_op_plans();
+  check_layer_geometry();
   check_frame_transform_args();
   check_tail_split();
   check_guard_bands();
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;
   fuzz_tune_lines(1234, rounds);
+  fuzz_conv_op_check(4321, 10 * rounds);
   check_packing(99);
   if (failures) {
     std::fprintf(stderr, "%d failures\n", failures);

@@ -140,6 +140,19 @@ def test_create_rejects_bad_config_before_touching_the_gpu(lib):
     assert lib.tsm_forward(None, None, 0, 0, 1, None, None) == -1
 
 
+def test_conv_op_refuses_a_null_or_foreign_argument_block_before_touching_the_gpu(lib):
+    """The first rule of tsm_conv_op (csrc/tsm_host_util.h, conv_op_check) as the library applies it: no GPU needed.  Only NULL
+    and a wrong struct_size are tried here -- the block never holds a made-up pointer, which a lost refusal would
+    dereference on a GPU machine; every other rule is held to its status and text by tests/host_sanitize.cpp."""
+    from workoutdetector_amd import _lib
+    message = b'tsm_conv_args.struct_size must be sizeof(tsm_conv_args)'
+    assert lib.tsm_conv_op(None, None) == -1 and lib.tsm_last_error(None) == message
+    for size in (0, ctypes.sizeof(_lib.TsmConvArgs) - 4, ctypes.sizeof(_lib.TsmConvArgs) + 8):
+        args = _lib.TsmConvArgs(struct_size=size)                        # every pointer NULL
+        assert lib.tsm_create(None, None) == -1 and lib.tsm_last_error(None) != message      # (another text in between)
+        assert lib.tsm_conv_op(ctypes.byref(args), None) == -1 and lib.tsm_last_error(None) == message
+
+
 def test_engine_fails_loudly_without_gpu():
     """No CPU fallback: on a box without a GPU construction raises (on a GPU box this test is moot)."""
     import torch

@@ -1,8 +1,11 @@
 """ASAN + UBSAN build of the engine's pure-host translation-unit pieces (host-side sanitizer build).
 
 csrc/tsm_host_util.h holds everything of tsm_engine.hip that needs no HIP type -- BatchNorm folding and weight
-packing, the bf16 / split-bf16 converters, the segment rule and the TSM_TUNE_CACHE line parser; tests/host_sanitize.cpp
-fuzzes the parser with malformed lines and checks the packers' invariants.  CPU only."""
+packing, the bf16 / split-bf16 converters, the segment rule, a conv layer's packed geometry (layer_geometry,
+conv_out_size), tsm_conv_op's argument rules (conv_op_check) and the TSM_TUNE_CACHE line parser; tests/host_sanitize.cpp
+fuzzes the parser with malformed lines, checks the packers' invariants, holds conv_op_check to one row per refusal (status
+and message), to the plans of the accepted forms the GPU tests use and to a loop over random and extreme int32 arguments,
+and layer_geometry to the per-layer values of every backbone.  CPU only."""
 import os
 import shutil
 import subprocess

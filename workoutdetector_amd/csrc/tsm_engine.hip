@@ -33,6 +33,7 @@
 namespace {
 
 using namespace tsm_host;
+static_assert(kPrecF32 == tsm::kPrecF32 && kPrecBf16x3 == tsm::kPrecBf16x3 && kPrecBf16 == tsm::kPrecBf16, "one precision enumeration");
 
 // The tag is also what workoutdetector_amd/build.py looks for in the FILE to decide whether a prebuilt library belongs to
 // the tree it sits in (mtimes do not survive a copy to another machine).
@@ -64,12 +65,9 @@ struct HostTensor {
   std::vector<int64_t> shape;
 };
 
-struct ConvLayer {
+struct ConvLayer : LayerGeom {   // cp, kp, kseg: tsm_host_util.h, layer_geometry
   std::string wkey, bnp;
   int cin = 0, cout = 0, k = 1, stride = 1;
-  int cp = 0;   // channel count the kernel sees (stem: 3 -> 4)
-  int kp = 0;   // padded K
-  int kseg = 0; // K-steps per accumulation segment (fp32 layers with long K, ConvParams::kseg_len); 0 = unsegmented
   float *d_w = nullptr, *d_b = nullptr;
 };
 
@@ -81,8 +79,6 @@ struct Block {
   std::string name;  // "layerL.B"
   // conv3 + downsample as ONE GEMM over K = [conv3 input channels | block input channels]
   float *d_wf = nullptr, *d_bf = nullptr;
-  int kpf = 0;
-  int ksegf = 0;  // segment length of the fused GEMM
   // conv2 + conv3 (+ residual) as ONE kernel (tsm::launch_conv23_fused): fp32 / split-bf16 blocks without a downsample branch whose
   // mid tensor has 64 / 128 channels and conv3 4x as many (layer1.1-2, layer2.1-3), or 128 channels and conv3 2x as many
   // (wide_resnet50_2's layer1.1-2); d_w3f = conv3's folded weights in fragment order
@@ -218,23 +214,26 @@ int fail(tsm_engine *e, int code, const std::string &msg) {
       return fail((e), TSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st));        \
   } while (0)
 
+// Appends a conv layer in its packed geometry; returns its index.  `segmented` = false keeps a long-K fp32 layer whole-K.
+int add_conv(tsm_engine *e, const std::string &wkey, const std::string &bnp, int cin, int cout, int k, int stride, bool segmented) {
+  ConvLayer c;
+  static_cast<LayerGeom &>(c) = layer_geometry(cin, k, stride, e->prec);
+  if (!segmented) c.kseg = 0;
+  c.wkey = wkey; c.bnp = bnp; c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;
+  e->convs.push_back(c);
+  return (int)e->convs.size() - 1;
+}
+
 void build_topology(tsm_engine *e) {
   e->convs.clear();
   e->blocks.clear();
-  ConvLayer stem;
-  stem.wkey = "base_model.conv1.weight";
-  stem.bnp = "base_model.bn1";
-  stem.cin = 3; stem.cout = 64; stem.k = 7; stem.stride = 2;
-  stem.cp = 4;
-  // fp32: K = 49 taps x 4 channels; bf16 formats: K = 7 rows x 4 pixel pairs x 8 (fold_and_pack_stem_pairs)
-  stem.kp = e->prec == tsm::kPrecF32 ? round_up(7 * 7 * 4, 32) : round_up(7 * 4 * 8, e->prec == tsm::kPrecBf16 ? 64 : 32);
-  e->convs.push_back(stem);
+  add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false);
   const Backbone &bb = *find_backbone(e->depth);
   const int expansion = bb.basic ? 1 : 4;
   int cin = 64;
   for (int li = 0; li < 4; ++li) {
     for (int b = 0; b < bb.blocks[li]; ++b) {
-      const int planes = kPlanes[li];
+      const int planes = kPlanes[li], cout = planes * expansion;
       const int mid = planes * e->width / 64;   // (Bottleneck only: a BasicBlock engine is always width 64)
       const int stride = (b == 0 && li > 0) ? 2 : 1;
       // block placement wraps the whole block in TemporalShift: its tensors are "layerL.B.net.<name>", conv1 unwrapped
@@ -244,45 +243,21 @@ void build_topology(tsm_engine *e) {
       Block blk;
       blk.stride = stride;
       blk.name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
-      blk.down = -1;
       if (bb.basic) {
-        // conv1: 3x3 at the block's stride, the temporal shift fused into its loader (no segmented form: kseg = 0);
+        // conv1: 3x3 at the block's stride, the temporal shift fused into its loader (which has no segmented form);
         // conv2: 3x3, + identity.  Downsample (1x1 at the stride) where the width or the size changes.
-        ConvLayer c1; c1.wkey = c1key; c1.bnp = p + ".bn1";
-        c1.cin = cin; c1.cout = planes; c1.k = 3; c1.stride = stride; c1.cp = cin; c1.kp = 9 * cin;
-        ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
-        c2.cin = planes; c2.cout = planes; c2.k = 3; c2.stride = 1; c2.cp = planes; c2.kp = 9 * planes;
-        c1.kseg = e->cfg.is_shift ? 0 : segment_len(c1.kp, e->prec);
-        blk.conv1 = (int)e->convs.size(); e->convs.push_back(c1);
-        blk.conv2 = (int)e->convs.size(); e->convs.push_back(c2);
+        blk.conv1 = add_conv(e, c1key, p + ".bn1", cin, planes, 3, stride, !e->cfg.is_shift);
+        blk.conv2 = add_conv(e, p + ".conv2.weight", p + ".bn2", planes, planes, 3, 1, false);
         blk.conv3 = -1;
-        if (stride != 1 || cin != planes) {
-          ConvLayer d; d.wkey = p + ".downsample.0.weight"; d.bnp = p + ".downsample.1";
-          d.cin = cin; d.cout = planes; d.k = 1; d.stride = stride; d.cp = cin; d.kp = cin;
-          blk.down = (int)e->convs.size(); e->convs.push_back(d);
-        }
-        e->blocks.push_back(blk);
-        cin = planes;
-        continue;
+      } else {   // conv1 1x1 (shifted), conv2 3x3 at the stride, conv3 1x1 + identity; downsample in every stage's first block
+        blk.conv1 = add_conv(e, c1key, p + ".bn1", cin, mid, 1, 1, true);
+        blk.conv2 = add_conv(e, p + ".conv2.weight", p + ".bn2", mid, mid, 3, stride, true);
+        blk.conv3 = add_conv(e, p + ".conv3.weight", p + ".bn3", mid, cout, 1, 1, false);
       }
-      ConvLayer c1; c1.wkey = c1key; c1.bnp = p + ".bn1";
-      c1.cin = cin; c1.cout = mid; c1.k = 1; c1.stride = 1; c1.cp = cin; c1.kp = cin;
-      ConvLayer c2; c2.wkey = p + ".conv2.weight"; c2.bnp = p + ".bn2";
-      c2.cin = mid; c2.cout = mid; c2.k = 3; c2.stride = stride; c2.cp = mid; c2.kp = 9 * mid;
-      ConvLayer c3; c3.wkey = p + ".conv3.weight"; c3.bnp = p + ".bn3";
-      c3.cin = mid; c3.cout = planes * 4; c3.k = 1; c3.stride = 1; c3.cp = mid; c3.kp = mid;
-      c1.kseg = segment_len(c1.kp, e->prec);
-      c2.kseg = segment_len(c2.kp, e->prec);
-      blk.conv1 = (int)e->convs.size(); e->convs.push_back(c1);
-      blk.conv2 = (int)e->convs.size(); e->convs.push_back(c2);
-      blk.conv3 = (int)e->convs.size(); e->convs.push_back(c3);
-      if (b == 0) {
-        ConvLayer d; d.wkey = p + ".downsample.0.weight"; d.bnp = p + ".downsample.1";
-        d.cin = cin; d.cout = planes * 4; d.k = 1; d.stride = stride; d.cp = cin; d.kp = cin;
-        blk.down = (int)e->convs.size(); e->convs.push_back(d);
-      }
+      const bool down = bb.basic ? (stride != 1 || cin != planes) : b == 0;
+      blk.down = down ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false) : -1;
       e->blocks.push_back(blk);
-      cin = planes * 4;
+      cin = cout;
     }
   }
   e->feat = kPlanes[3] * expansion;
@@ -340,6 +315,32 @@ int dev_alloc(tsm_engine *e, float **p, size_t elems, const char *name = "weight
   return TSM_OK;
 }
 
+// One weight preparation, for tsm_finalize and tsm_conv_op alike.  Raw OIHW weights + the four BatchNorm vectors of layer c -> the folded fp32 matrix [cout][kp] in c's geometry, and the bias.
+void prepare_weights(const ConvLayer &c, const float *w, const float *gamma, const float *beta, const float *mean, const float *var,
+                     std::vector<float> *wp, std::vector<float> *bias) {
+  if (c.stem_pairs) fold_and_pack_stem_pairs(w, gamma, beta, mean, var, c.cout, c.kp, wp, bias);
+  else fold_and_pack(w, gamma, beta, mean, var, c.cout, c.cin, c.k, c.cp, c.kp, wp, bias);
+}
+
+// Allocate, then copy.  `alloc(&ptr, name, elems, frame_elems)` returns a status: the engine's dev_alloc, or tsm_conv_op's
+// guarded temporaries (e = NULL).
+template <class Alloc>
+int upload(tsm_engine *e, Alloc &alloc, float **p, const char *name, const std::vector<float> &v, size_t frame_elems = 0) {
+  const int rc = alloc(p, name, v.size(), frame_elems);
+  if (rc) return rc;
+  TSM_HIP(e, hipMemcpy(*p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+  return TSM_OK;
+}
+
+// A folded fp32 matrix [cout][K] (converted in place to the storage format of `prec`) and its bias, to the device.
+template <class Alloc>
+int upload_conv(tsm_engine *e, Alloc &alloc, int prec, int cout, std::vector<float> *wp, const std::vector<float> &bias, float **d_w,
+                float **d_b) {
+  to_storage(wp, prec);
+  const int rc = upload(e, alloc, d_w, "d_w", *wp, wp->size() / cout);
+  return rc ? rc : upload(e, alloc, d_b, "d_b", bias);
+}
+
 // TSM_POISON=1, immediately before the first launch of a forward proper: every activation / scratch buffer filled with the
 // poison word, so whatever a kernel relies on in them must be written by THIS forward, not inherited.  Weights are not touched.
 int poison_workspace(tsm_engine *e, hipStream_t s) {
@@ -371,12 +372,21 @@ tsm::ConvParams make_params(const ConvLayer &c, const float *x, const float *res
   p.x = x; p.w = c.d_w; p.bias = c.d_b; p.res = res; p.y = y;
   p.N = n; p.Hi = hi; p.Wi = wi; p.C = c.cp; p.logC4 = ilog2(c.cp / 4);
   p.pad = c.k / 2; p.stride = c.stride;
-  p.Ho = (hi + 2 * p.pad - c.k) / c.stride + 1;
-  p.Wo = (wi + 2 * p.pad - c.k) / c.stride + 1;
+  p.Ho = conv_out_size(hi, c.k, c.stride);
+  p.Wo = conv_out_size(wi, c.k, c.stride);
   p.Cout = c.cout; p.Kp = c.kp; p.M = n * p.Ho * p.Wo; p.relu = relu ? 1 : 0;
   p.T = T; p.fold = T > 0 ? c.cp / shift_div : 0;
   p.kseg_len = res ? 0 : c.kseg;   // (no layer with a residual has a long K; the per-op entry point passes kseg = 0)
   return p;
+}
+
+// A second source behind p's own K: one GEMM over K = [p's K | kp2] (Bottleneck.conv3 + the downsample branch, concat_k_pair's
+// matrix; the caller sets p->w and p->bias), segmented by the whole K.  x2 is [N, hi2, wi2, c2], read at stride2.
+void set_second_source(tsm::ConvParams *p, int kp2, const float *x2, int c2, int hi2, int wi2, int stride2) {
+  p->K1 = p->Kp;
+  p->Kp += kp2;
+  p->kseg_len = segment_len(p->Kp, p->prec);
+  p->x2 = x2; p->C2 = c2; p->Hi2 = hi2; p->Wi2 = wi2; p->stride2 = stride2;
 }
 
 // $XDG_CACHE_HOME/tsm_hip/tune_cache.txt, else $HOME/.cache/tsm_hip/tune_cache.txt ("" when neither is set or the
@@ -553,7 +563,7 @@ BlockLaunches block_launches(const tsm_engine *e, size_t k, int nn, const float 
   const Block &blk = e->blocks[k];
   const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
   const int T = cfg.num_segments, shiftT = cfg.is_shift ? T : 0, prec = e->prec;
-  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   const bool fused = blk.down >= 0;   // (a Bottleneck's downsample always runs inside conv3's GEMM)
   BlockLaunches L;
   L.p1 = make_params(c1, x, nullptr, t1, nn, hh, ww, true, shiftT, cfg.shift_div, prec);
@@ -561,8 +571,8 @@ BlockLaunches block_launches(const tsm_engine *e, size_t k, int nn, const float 
   L.p3 = make_params(c3, t2, fused ? nullptr : x, y, nn, ho, wo, true, 0, 1, prec);
   if (fused) {
     const ConvLayer &cd = e->convs[blk.down];
-    L.p3.w = blk.d_wf; L.p3.bias = blk.d_bf; L.p3.Kp = blk.kpf; L.p3.K1 = c3.kp; L.p3.kseg_len = blk.ksegf;
-    L.p3.x2 = x; L.p3.C2 = cd.cp; L.p3.Hi2 = hh; L.p3.Wi2 = ww; L.p3.stride2 = blk.stride;
+    L.p3.w = blk.d_wf; L.p3.bias = blk.d_bf;
+    set_second_source(&L.p3, cd.kp, x, cd.cp, hh, ww, blk.stride);
   }
   if (block_shift(e)) {   // block placement: the identity / the downsample operand is the block input through the shift
     L.p3.T = T;
@@ -638,8 +648,8 @@ std::vector<BlockPlan> plan_forward(const tsm_engine *e, const std::vector<int> 
     else if (can.front && !p.conv1_done && chosen(e->fuse_front, blk.conv1, kCodeFront)) p.front = true;
     else if (can.conv23 && chosen(e->fuse23, blk.conv2, kCodeConv23)) p.conv23 = true;
     else if (can.conv31 && chosen(e->fuse31, blk.conv3, kCodeConv31)) p.conv31_next = true;
-    hh = (hh + 2 - 3) / blk.stride + 1;
-    ww = (ww + 2 - 3) / blk.stride + 1;
+    hh = conv_out_size(hh, 3, blk.stride);
+    ww = conv_out_size(ww, 3, blk.stride);
   }
   return plan;
 }
@@ -750,7 +760,7 @@ int Forward::run_basic(size_t k, int nn, float *x, float *y, int hh, int ww) {
   const Block &blk = e->blocks[k];
   const std::string &name = blk.name;
   const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2];
-  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   const float *identity = x;
   if (blk.down >= 0) {
     tsm::ConvParams pd = make_params(e->convs[blk.down], x, nullptr, idb, nn, hh, ww, false, block_shift(e) ? shiftT : 0,
@@ -781,7 +791,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
   const Block &blk = e->blocks[k];
   const std::string &name = blk.name;
   const int c1out = e->convs[blk.conv1].cout, c2out = e->convs[blk.conv2].cout, c3out = e->convs[blk.conv3].cout;
-  const int ho = (hh + 2 - 3) / blk.stride + 1, wo = (ww + 2 - 3) / blk.stride + 1;
+  const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   BlockLaunches L = block_launches(e, k, nn, x, y, t1, t2, hh, ww);
   if (blk.down >= 0) skip_slots(e, 1);
   if (plan.block) {
@@ -953,8 +963,8 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
                                          : f.run_block(k, plan[k], n, cur, out, h, w);
     if (rc || f.tapped) return rc;
     std::swap(cur, out);
-    h = (h + 2 - 3) / e->blocks[k].stride + 1;
-    w = (w + 2 - 3) / e->blocks[k].stride + 1;
+    h = conv_out_size(h, 3, e->blocks[k].stride);
+    w = conv_out_size(w, 3, e->blocks[k].stride);
   }
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
   if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
@@ -1020,9 +1030,7 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
   if (layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
   if (layout >= TSM_LAYOUT_NTHWC4 && memkind != TSM_MEM_DEVICE)
     return fail(e, TSM_ERR_INVALID_ARG, "packed layouts (NTHWC4 / NTHWC8S / NTHWC8B) are device-memory layouts");
-  if ((layout == TSM_LAYOUT_NTHWC4 && e->prec != tsm::kPrecF32) ||
-      (layout == TSM_LAYOUT_NTHWC8S && e->prec != tsm::kPrecBf16x3) ||
-      (layout == TSM_LAYOUT_NTHWC8B && e->prec != tsm::kPrecBf16))
+  if (layout >= TSM_LAYOUT_NTHWC4 && layout != packed_layout_of(e->prec))
     return fail(e, TSM_ERR_INVALID_ARG, "packed layout does not match the engine dtype");
   if (n_clips <= 0) return fail(e, TSM_ERR_INVALID_ARG, "n_clips must be positive");
   if (n_clips > e->cfg.max_clips)
@@ -1031,23 +1039,90 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
   return TSM_OK;
 }
 
+// Behind check_forward_args: the engine's device, the call's stream, and clips in host memory staged into d_in.
+int stage_input(tsm_engine *e, const void *clips, int memkind, int n_clips, void *stream, hipStream_t *s, const float **d_clips) {
+  TSM_HIP(e, hipSetDevice(e->cfg.device_id));
+  *s = pick_stream(e, memkind, stream);
+  *d_clips = static_cast<const float *>(clips);
+  if (memkind == TSM_MEM_HOST) {
+    const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * 3 * e->cfg.height * e->cfg.width;
+    TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, *s));
+    *d_clips = e->d_in;
+  }
+  return TSM_OK;
+}
+
+// The backbone, the placement and the consensus are fixed once weights arrive.
+int check_before_weights(tsm_engine *e, const char *setter) {
+  if (!e) return TSM_ERR_INVALID_ARG;
+  if (e->weights_started || e->finalized) return fail(e, TSM_ERR_INVALID_ARG, std::string(setter) + " must come before the first tsm_set_tensor");
+  return TSM_OK;
+}
+
+// A TSM_* variable of tsm_create: *v keeps its default when the variable is unset.
+template <class T, class F>
+void env_read(const char *name, T *v, F parse) { if (const char *s = getenv(name)) *v = parse(s); }
+
+// tsm_conv_op's temporaries.  Hostile memory, always on (a debug entry point that allocates per call): every temporary sits
+// between poisoned bands of one frame of that buffer and starts out poison all over -- so the elements of d_ys / d_part that the
+// launch does not write reach y as poison (through to_f32 / the reduction), a read before frame 0 or behind the last tile returns
+// poison instead of the allocator's leftovers, and a stray store is found in the bands after the final synchronise
+// (TSM_ERR_GUARD).  Freed on every exit path (errors included).
+struct GuardedScratch {
+  GuardBuf g[8];
+  int n = 0;
+  ~GuardedScratch() {
+    for (int i = 0; i < n; ++i)
+      if (g[i].base) (void)hipFree(g[i].base);
+  }
+  int alloc(float **p, const char *name, size_t elems, size_t frame_elems, size_t elem_bytes = 4) {
+    GuardBuf &b = g[n++];
+    TSM_HIP(nullptr, guard_alloc(&b, name, elems * elem_bytes, frame_elems * elem_bytes, elem_bytes));
+    *p = b.ptr();
+    return TSM_OK;
+  }
+};
+
+// tsm_conv_op: layer c's raw OIHW weights and BatchNorm vectors copied from device memory, then prepare_weights.
+int fetch_prepared(const ConvLayer &c, const float *w, const float *gamma, const float *beta, const float *mean, const float *var,
+                   std::vector<float> *wp, std::vector<float> *bias) {
+  const size_t nw = (size_t)c.cout * c.cin * c.k * c.k, nc = (size_t)c.cout;
+  std::vector<float> host(nw + 4 * nc);
+  const float *src[5] = {w, gamma, beta, mean, var};
+  float *dst = host.data();
+  for (int i = 0; i < 5; ++i) {   // [raw weights | gamma | beta | mean | var]
+    TSM_HIP(nullptr, hipMemcpy(dst, src[i], (i ? nc : nw) * sizeof(float), hipMemcpyDeviceToHost));
+    dst += i ? nc : nw;
+  }
+  const float *bn = host.data() + nw;
+  prepare_weights(c, host.data(), bn, bn + nc, bn + 2 * nc, bn + 3 * nc, wp, bias);
+  return TSM_OK;
+}
+
+// The status of an engine-less entry point's launch: `op`: and HIP's text, or for hipErrorInvalidValue -- the launchers'
+// "these arguments fit no launch" -- `invalid_text` where the entry point has a better one.
+int op_status(const char *op, hipError_t st, const char *invalid_text = nullptr) {
+  if (st == hipSuccess) return TSM_OK;
+  const int code = st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP;
+  return fail(nullptr, code, std::string(op) + ": " + (invalid_text && code == TSM_ERR_INVALID_ARG ? invalid_text : hipGetErrorString(st)));
+}
+
 }  // namespace
 
 // ---- the frame transforms (tsm_preprocess, _clips, _indexed, _windows, _image): their shared argument checks ----------------------------
-static int check_pixel(int32_t pixel) {
+static int out_mode_of(int32_t out_layout, int *mode) {          // PreprocParams::out_mode of an output layout; any other is refused
+  *mode = out_layout == TSM_LAYOUT_NTHWC4 ? 0 : out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2 : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : -1;
+  return *mode >= 0 ? TSM_OK : fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
+}
+// The pixel type, output layout and scale of a frame transform, checked and written into its parameter block.
+template <typename P>
+static int set_pixel_format(P *p, int32_t pixel, int32_t out_layout, int32_t scale_255) {
   if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  if (int rc = out_mode_of(out_layout, &p->out_mode)) return rc;
+  p->src_is_u8 = pixel == TSM_PIXEL_U8;
+  p->pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
   return TSM_OK;
 }
-static int check_out_layout(int32_t out_layout) {
-  if (out_layout != TSM_LAYOUT_NTHWC4 && out_layout != TSM_LAYOUT_NTCHW && out_layout != TSM_LAYOUT_NTHWC8S &&
-      out_layout != TSM_LAYOUT_NTHWC8B)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "out_layout must be NTHWC4, NTHWC8S, NTHWC8B or NTCHW");
-  return TSM_OK;
-}
-static int out_mode_of(int32_t out_layout) {          // PreprocParams::out_mode
-  return out_layout == TSM_LAYOUT_NTCHW ? 1 : out_layout == TSM_LAYOUT_NTHWC8S ? 2 : out_layout == TSM_LAYOUT_NTHWC8B ? 3 : 0;
-}
-static float pre_scale_of(int32_t scale_255) { return scale_255 ? 1.0f / 255.0f : 1.0f; }
 // Resize(resize) + CenterCrop(crop) of an h x w frame into a PreprocParams / ImagePreprocParams (tsm_host::center_crop_geometry);
 // false when the crop is larger than the resized frame.
 template <typename P>
@@ -1094,7 +1169,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   }
   if (cfg->shift_div <= 0 || (64 % cfg->shift_div) != 0 || (64 / cfg->shift_div) % 4 != 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "shift_div must divide 64 with fold % 4 == 0 (8 or 16... )");
-  if (cfg->dtype != TSM_DTYPE_F32 && cfg->dtype != TSM_DTYPE_BF16X3 && cfg->dtype != TSM_DTYPE_BF16)
+  if (prec_of_dtype(cfg->dtype) < 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "dtype must be TSM_DTYPE_F32, TSM_DTYPE_BF16X3 or TSM_DTYPE_BF16");
   if (cfg->dtype != TSM_DTYPE_F32 && (64 / cfg->shift_div) % 8 != 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "the bf16 formats need fold % 8 == 0 (shift_div <= 8)");
@@ -1105,30 +1180,25 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad device_id");
   tsm_engine *e = new tsm_engine();
   e->cfg = *cfg;
-  e->prec = cfg->dtype == TSM_DTYPE_BF16X3 ? tsm::kPrecBf16x3
-            : cfg->dtype == TSM_DTYPE_BF16 ? tsm::kPrecBf16 : tsm::kPrecF32;
-  if (const char *at = getenv("TSM_AUTOTUNE")) e->autotune = atoi(at) != 0;
-  if (const char *sd = getenv("TSM_STEM_DIRECT")) e->stem_direct = atoi(sd) != 0;
-  if (const char *sp = getenv("TSM_STEM_POOL")) e->stem_pool = atoi(sp) != 0;
-  if (const char *pl = getenv("TSM_STEM_PLANAR")) e->stem_planar = atoi(pl) != 0;
-  if (const char *ft = getenv("TSM_CONV_TILE")) e->force_tile = tsm::conv_tile_from_name(ft);
-  if (const char *fc = getenv("TSM_CONV_CODE")) e->force_code = atoi(fc);
-  if (const char *f23 = getenv("TSM_FUSE_CONV23")) e->fuse23 = atoi(f23) != 0;
-  if (const char *fb = getenv("TSM_FUSE_BLOCK")) e->fuse_block = atoi(fb) != 0;
-  if (const char *f31 = getenv("TSM_FUSE_C3C1")) e->fuse31 = atoi(f31) != 0;
-  if (const char *ff = getenv("TSM_FUSE_FRONT")) e->fuse_front = atoi(ff) != 0;
-  if (const char *wk = getenv("TSM_WALK")) e->walk = atoi(wk) != 0;
-  if (const char *po = getenv("TSM_POISON")) e->poison = atoi(po) != 0;
+  e->prec = prec_of_dtype(cfg->dtype);
+  const auto on = [](const char *s) { return atoi(s) != 0; };
+  env_read("TSM_AUTOTUNE", &e->autotune, on);
+  env_read("TSM_STEM_DIRECT", &e->stem_direct, on);
+  env_read("TSM_STEM_POOL", &e->stem_pool, on);
+  env_read("TSM_STEM_PLANAR", &e->stem_planar, on);
+  env_read("TSM_CONV_TILE", &e->force_tile, tsm::conv_tile_from_name);
+  env_read("TSM_CONV_CODE", &e->force_code, atoi);
+  env_read("TSM_FUSE_CONV23", &e->fuse23, on);
+  env_read("TSM_FUSE_BLOCK", &e->fuse_block, on);
+  env_read("TSM_FUSE_C3C1", &e->fuse31, on);
+  env_read("TSM_FUSE_FRONT", &e->fuse_front, on);
+  env_read("TSM_WALK", &e->walk, on);
+  env_read("TSM_POISON", &e->poison, on);
   // TSM_TUNE_CACHE=<file> names the tune cache; unset: a per-user default ($XDG_CACHE_HOME or $HOME/.cache, then
   // tsm_hip/tune_cache.txt), so that the second process on a machine pays no tuning pass; "", "0" or "off" disables it.
-  {
-    const char *tc = getenv("TSM_TUNE_CACHE");
-    if (tc) {
-      if (*tc && strcmp(tc, "0") != 0 && strcmp(tc, "off") != 0) e->tune_path = tc;
-    } else {
-      e->tune_path = default_tune_cache_path();
-    }
-  }
+  const char *tc = getenv("TSM_TUNE_CACHE");
+  if (!tc) e->tune_path = default_tune_cache_path();
+  else if (*tc && strcmp(tc, "0") != 0 && strcmp(tc, "off") != 0) e->tune_path = tc;
   build_topology(e);
   st = hipSetDevice(cfg->device_id);
   if (st == hipSuccess) st = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
@@ -1160,9 +1230,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
 }
 
 int tsm_set_backbone(tsm_engine *e, int32_t depth) {
-  if (!e) return TSM_ERR_INVALID_ARG;
-  if (e->weights_started || e->finalized)
-    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_backbone must come before the first tsm_set_tensor");
+  if (int rc = check_before_weights(e, "tsm_set_backbone")) return rc;
   if (!find_backbone(depth)) return fail(e, TSM_ERR_UNSUPPORTED, "depth must be 18, 34 or 50");
   if (find_backbone(depth)->basic && e->width != 64)
     return fail(e, TSM_ERR_UNSUPPORTED, "a BasicBlock backbone (depth 18 / 34) has no bottleneck width: the engine's is " +
@@ -1174,9 +1242,7 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
 }
 
 int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
-  if (!e) return TSM_ERR_INVALID_ARG;
-  if (e->weights_started || e->finalized)
-    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_bottleneck_width must come before the first tsm_set_tensor");
+  if (int rc = check_before_weights(e, "tsm_set_bottleneck_width")) return rc;
   if (width_per_group != 64 && width_per_group != 128)
     return fail(e, TSM_ERR_UNSUPPORTED, "width_per_group must be 64 or 128 (wide_resnet50_2)");
   if (width_per_group != 64 && find_backbone(e->depth)->basic)
@@ -1189,9 +1255,7 @@ int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
 }
 
 int tsm_set_shift_place(tsm_engine *e, int32_t place) {
-  if (!e) return TSM_ERR_INVALID_ARG;
-  if (e->weights_started || e->finalized)
-    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_shift_place must come before the first tsm_set_tensor");
+  if (int rc = check_before_weights(e, "tsm_set_shift_place")) return rc;
   if (place != 0 && place != 1) return fail(e, TSM_ERR_UNSUPPORTED, "place must be 0 (blockres) or 1 (block)");
   e->place = place;
   build_topology(e);
@@ -1200,9 +1264,7 @@ int tsm_set_shift_place(tsm_engine *e, int32_t place) {
 }
 
 int tsm_set_consensus(tsm_engine *e, int32_t consensus) {
-  if (!e) return TSM_ERR_INVALID_ARG;
-  if (e->weights_started || e->finalized)
-    return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_consensus must come before the first tsm_set_tensor");
+  if (int rc = check_before_weights(e, "tsm_set_consensus")) return rc;
   if (consensus != 0 && consensus != 1) return fail(e, TSM_ERR_UNSUPPORTED, "consensus must be 0 (avg) or 1 (identity)");
   e->consensus = consensus;   // (the head is not tuned: the tune signature does not carry it)
   return TSM_OK;
@@ -1248,6 +1310,7 @@ int tsm_finalize(tsm_engine *e) {
   if (e->finalized) return TSM_OK;
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
   const tsm_config &cfg = e->cfg;
+  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };   // ("weights", no frame)
   std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
   for (size_t ci = 0; ci < e->convs.size(); ++ci) {
     ConvLayer &c = e->convs[ci];
@@ -1261,42 +1324,21 @@ int tsm_finalize(tsm_engine *e) {
     for (const HostTensor *t : {g, b, m, v})
       if (t->shape.size() != 1 || t->shape[0] != c.cout) return fail(e, TSM_ERR_SHAPE, "BN shape mismatch for " + c.bnp);
     std::vector<float> wp, bias;
-    if (c.k == 7 && e->prec != tsm::kPrecF32)
-      fold_and_pack_stem_pairs(w->data.data(), g->data.data(), b->data.data(), m->data.data(), v->data.data(), c.cout,
-                               c.kp, &wp, &bias);
-    else
-      fold_and_pack(w->data.data(), g->data.data(), b->data.data(), m->data.data(), v->data.data(), c.cout,
-                    c.cin, c.k, c.cp, c.kp, &wp, &bias);
+    prepare_weights(c, w->data.data(), g->data.data(), b->data.data(), m->data.data(), v->data.data(), &wp, &bias);
     if (c.k == 1) {  // fp32 packed copies of the 1x1 layers, for the conv3 + downsample fusion below
       host_wp[ci] = wp;
       host_bias[ci] = bias;
     }
-    if (e->prec == tsm::kPrecBf16x3) to_split(&wp);
-    if (e->prec == tsm::kPrecBf16) to_bf16(&wp);
-    int rc = dev_alloc(e, &c.d_w, wp.size());
-    if (rc) return rc;
-    rc = dev_alloc(e, &c.d_b, bias.size());
-    if (rc) return rc;
-    TSM_HIP(e, hipMemcpy(c.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    TSM_HIP(e, hipMemcpy(c.d_b, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
   }
   // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
   for (Block &blk : e->blocks) {
     if (blk.down < 0 || blk.conv3 < 0) continue;   // (Bottlenecks only)
     const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
-    blk.kpf = c3.kp + cd.kp;
-    blk.ksegf = segment_len(blk.kpf, e->prec);
     std::vector<float> wf, bf;
     concat_k_pair(host_wp[blk.conv3], host_bias[blk.conv3], c3.kp, host_wp[blk.down], host_bias[blk.down], cd.kp, c3.cout,
                   &wf, &bf);
-    if (e->prec == tsm::kPrecBf16x3) to_split(&wf);
-    if (e->prec == tsm::kPrecBf16) to_bf16(&wf);
-    int rcf = dev_alloc(e, &blk.d_wf, wf.size());
-    if (rcf) return rcf;
-    rcf = dev_alloc(e, &blk.d_bf, bf.size());
-    if (rcf) return rcf;
-    TSM_HIP(e, hipMemcpy(blk.d_wf, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-    TSM_HIP(e, hipMemcpy(blk.d_bf, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = upload_conv(e, alloc, e->prec, c3.cout, &wf, bf, &blk.d_wf, &blk.d_bf)) return rc;
   }
   // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide and whose conv3 has 4x as many outputs
   // (conv23_fused_kernel: four phase-C chunks), or 128 wide with 2x as many (conv23_fused2_kernel, wide_resnet50_2's
@@ -1315,9 +1357,7 @@ int tsm_finalize(tsm_engine *e) {
     std::vector<float> w3f;
     if (e->prec == tsm::kPrecBf16x3) pack_w3_fragments_split(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
     else pack_w3_fragments(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
-    int rcw = dev_alloc(e, &blk.d_w3f, w3f.size());
-    if (rcw) return rcw;
-    TSM_HIP(e, hipMemcpy(blk.d_w3f, w3f.data(), w3f.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = upload(e, alloc, &blk.d_w3f, "d_w3f", w3f)) return rc;
     blk.cmid = c2.cout;
     blk.cout3 = c3.cout;
   }
@@ -1327,27 +1367,23 @@ int tsm_finalize(tsm_engine *e) {
   if (!fw || !fb) return fail(e, TSM_ERR_MISSING_TENSOR, "missing fc.weight / fc.bias");
   if (fw->shape != std::vector<int64_t>{cfg.num_class, e->feat} || fb->shape != std::vector<int64_t>{cfg.num_class})
     return fail(e, TSM_ERR_SHAPE, "fc shape mismatch (want [num_class, " + std::to_string(e->feat) + "])");
-  int rc = dev_alloc(e, &e->d_fcw, fw->data.size());
-  if (rc) return rc;
-  rc = dev_alloc(e, &e->d_fcb, fb->data.size());
-  if (rc) return rc;
-  TSM_HIP(e, hipMemcpy(e->d_fcw, fw->data.data(), fw->data.size() * sizeof(float), hipMemcpyHostToDevice));
-  TSM_HIP(e, hipMemcpy(e->d_fcb, fb->data.data(), fb->data.size() * sizeof(float), hipMemcpyHostToDevice));
+  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
+  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
 
   // Workspace: five rotating buffers (block in/out, two branch temporaries, identity), each the largest activation of the
   // topology per frame: the stem conv output or a conv output of some block (R50: layer1's 256 channels).
-  e->h1 = (cfg.height + 6 - 7) / 2 + 1;
-  e->w1 = (cfg.width + 6 - 7) / 2 + 1;
-  e->hp = (e->h1 + 2 - 3) / 2 + 1;
-  e->wp = (e->w1 + 2 - 3) / 2 + 1;
+  e->h1 = conv_out_size(cfg.height, 7, 2);
+  e->w1 = conv_out_size(cfg.width, 7, 2);
+  e->hp = conv_out_size(e->h1, 3, 2);   // (the max-pool)
+  e->wp = conv_out_size(e->w1, 3, 2);
   const size_t frames = (size_t)cfg.max_clips * cfg.num_segments;
   size_t per_frame = (size_t)e->h1 * e->w1 * 64;
   {
     int hh = e->hp, ww = e->wp;
     for (const Block &blk : e->blocks) {
       const size_t in_px = (size_t)hh * ww;
-      hh = (hh + 2 - 3) / blk.stride + 1;
-      ww = (ww + 2 - 3) / blk.stride + 1;
+      hh = conv_out_size(hh, 3, blk.stride);
+      ww = conv_out_size(ww, 3, blk.stride);
       const size_t out_px = (size_t)hh * ww;
       for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down}) {
         if (ci < 0) continue;
@@ -1360,23 +1396,17 @@ int tsm_finalize(tsm_engine *e) {
   e->buf_elems = frames * per_frame;
   for (int i = 0; i < 5; ++i) {
     static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
-    rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame);
-    if (rc) return rc;
+    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame))) return rc;
   }
-  rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width);
-  if (rc) return rc;
-  rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1));  // 16 bytes per pixel in every format (pairs: odd widths padded)
-  if (rc) return rc;
-  rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat);
-  if (rc) return rc;
+  if ((rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width))) return rc;
+  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1)))) return rc;  // 16 bytes per pixel in every format (pairs: odd widths padded)
+  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
   // avg: one row per clip; identity: one per (clip, segment)
-  rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
-                 (size_t)cfg.num_class);
-  if (rc) return rc;
+  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
+                 (size_t)cfg.num_class))) return rc;
   if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
     e->partial_elems = (size_t)16 << 20;
-    rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame);
-    if (rc) return rc;
+    if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame))) return rc;
   }
   e->tensors.clear();  // host copies are no longer needed
   e->finalized = true;
@@ -1390,16 +1420,10 @@ static int forward_to(tsm_engine *e, const void *clips, int32_t memkind, int32_t
   int rc = check_forward_args(e, clips, memkind, layout, n_clips);
   if (rc) return rc;
   if (!out) return fail(e, TSM_ERR_INVALID_ARG, features ? "features is NULL" : "logits is NULL");
-  TSM_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipStream_t s = pick_stream(e, memkind, stream);
-  const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * 3 * e->cfg.height * e->cfg.width;
-  const float *d_clips = static_cast<const float *>(clips);
-  float *d_out = out, *d_stage = features ? e->d_pooled : e->d_logits;
-  if (memkind == TSM_MEM_HOST) {
-    TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, s));
-    d_clips = e->d_in;
-    d_out = d_stage;
-  }
+  hipStream_t s;
+  const float *d_clips;
+  if ((rc = stage_input(e, clips, memkind, n_clips, stream, &s, &d_clips))) return rc;
+  float *d_stage = features ? e->d_pooled : e->d_logits, *d_out = memkind == TSM_MEM_HOST ? d_stage : out;
   struct Mode {   // run_forward's last launch, for this call only (every return path)
     tsm_engine *e;
     ~Mode() { e->features = 0; }
@@ -1456,7 +1480,7 @@ int tsm_tune(tsm_engine *e, int32_t n_clips, void *stream) {
   // anybody else's (a cold process pays first-use code-object loads for those)
   const size_t frames = (size_t)n_clips * e->cfg.num_segments;
   TSM_HIP(e, hipMemsetAsync(e->d_in4, 0, frames * 4 * e->cfg.height * (e->cfg.width + 1) * sizeof(float), s));
-  const int layout = e->prec == tsm::kPrecF32 ? TSM_LAYOUT_NTHWC4 : e->prec == tsm::kPrecBf16x3 ? TSM_LAYOUT_NTHWC8S : TSM_LAYOUT_NTHWC8B;
+  const int layout = packed_layout_of(e->prec);
   bool from_file = false;
   int rc = ensure_tuned(e, e->d_in4, layout, n_clips, e->d_logits, s, &from_file);
   if (rc || !from_file) return rc;
@@ -1477,14 +1501,9 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
   int rc = check_forward_args(e, clips, memkind, layout, n_clips);
   if (rc) return rc;
   if (!stage || !out || !out_shape) return fail(e, TSM_ERR_INVALID_ARG, "stage/out/out_shape is NULL");
-  TSM_HIP(e, hipSetDevice(e->cfg.device_id));
-  hipStream_t s = pick_stream(e, memkind, stream);
-  const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * 3 * e->cfg.height * e->cfg.width;
-  const float *d_clips = static_cast<const float *>(clips);
-  if (memkind == TSM_MEM_HOST) {
-    TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, s));
-    d_clips = e->d_in;
-  }
+  hipStream_t s;
+  const float *d_clips;
+  if ((rc = stage_input(e, clips, memkind, n_clips, stream, &s, &d_clips))) return rc;
   rc = poison_workspace(e, s);
   if (rc) return rc;
   Tap tap;
@@ -1495,9 +1514,7 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
   if (elems > out_capacity) return fail(e, TSM_ERR_CAPACITY, "tap output buffer too small");
   if (e->prec != tsm::kPrecF32) {  // taps are reported as fp32 whatever the storage format
     if (!e->d_tap) {
-      const size_t cap = e->buf_elems > (size_t)e->cfg.max_clips * e->cfg.num_segments * 8 * e->cfg.height * e->cfg.width
-                             ? e->buf_elems
-                             : (size_t)e->cfg.max_clips * e->cfg.num_segments * 8 * e->cfg.height * e->cfg.width;
+      const size_t cap = std::max(e->buf_elems, (size_t)e->cfg.max_clips * e->cfg.num_segments * 8 * e->cfg.height * e->cfg.width);
       rc = dev_alloc(e, &e->d_tap, cap, "d_tap", cap / ((size_t)e->cfg.max_clips * e->cfg.num_segments));
       if (rc) return rc;
     }
@@ -1582,199 +1599,91 @@ int tsm_temporal_shift(const float *x, float *y, int64_t n_frames, int32_t n_seg
                        int32_t fold_div, void *stream) {
   if (!x || !y || n_frames <= 0 || hw <= 0 || c <= 0 || fold_div <= 0) return TSM_ERR_INVALID_ARG;
   const int fold = c / fold_div;
-  hipError_t st = tsm::launch_temporal_shift(x, y, n_frames, n_segment, hw, c, fold, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("temporal_shift: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("temporal_shift", tsm::launch_temporal_shift(x, y, n_frames, n_segment, hw, c, fold, static_cast<hipStream_t>(stream)));
 }
 
 int tsm_conv_op(const tsm_conv_args *a, void *stream) {
-  if (!a || a->struct_size != (int32_t)sizeof(tsm_conv_args))
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "tsm_conv_args.struct_size must be sizeof(tsm_conv_args)");
-  const int dtype = a->dtype;
-  if (dtype != TSM_DTYPE_F32 && dtype != TSM_DTYPE_BF16X3 && dtype != TSM_DTYPE_BF16)
-    return fail(nullptr, TSM_ERR_UNSUPPORTED, "bad dtype");
-  const int prec = dtype == TSM_DTYPE_BF16X3 ? tsm::kPrecBf16x3 : dtype == TSM_DTYPE_BF16 ? tsm::kPrecBf16 : tsm::kPrecF32;
+  const ConvOpPlan pl = conv_op_check(a);   // every refusal, before the first HIP call
+  if (pl.status != TSM_OK) return fail(nullptr, pl.status, pl.message);
+  const int prec = pl.prec, n = a->n, hi = a->hi, wi = a->wi, cout = a->cout;
   const bool x3 = prec != tsm::kPrecF32;  // any non-fp32 storage format: convert at the boundary
-  const int n = a->n, hi = a->hi, wi = a->wi, cin = a->cin, cout = a->cout, k = a->k, stride = a->stride;
-  const int T = a->shift_segments, fold_div = a->fold_div > 0 ? a->fold_div : 1;
-  const float *residual = a->residual;
-  const bool dual = a->x2 != nullptr;
-  if (!a->x || !a->w || !a->gamma || !a->beta || !a->mean || !a->var || !a->y) return fail(nullptr, TSM_ERR_INVALID_ARG, "NULL pointer");
-  if (n <= 0 || hi <= 0 || wi <= 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "n, hi and wi must be positive");
-  if (k != 1 && k != 3 && k != 7) return fail(nullptr, TSM_ERR_UNSUPPORTED, "k must be 1, 3 or 7");
-  if (stride != 1 && stride != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "stride must be 1 or 2");
-  const bool stem = (k == 7);
-  if (stem ? (cin != 3) : (cin % 32 != 0 || (cin & (cin - 1)) != 0))
-    return fail(nullptr, TSM_ERR_UNSUPPORTED, "cin must be 3 (k=7) or a power of two >= 32");
-  if (prec == tsm::kPrecBf16 && !stem && cin % 64 != 0)
-    return fail(nullptr, TSM_ERR_UNSUPPORTED, "TSM_DTYPE_BF16 needs cin % 64 == 0");
-  if (cout % 64 != 0) return fail(nullptr, TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64");
-  if (stem && (residual || dual || T > 0)) return fail(nullptr, TSM_ERR_INVALID_ARG, "the 7x7 stem has no residual, second source or shift");
-  // What the shift moves: the input (0), or the identity (1: block placement) -- the residual, the second source, or for a
-  // 1x1 at stride 2 (a BasicBlock's downsample) the input, which is that block's identity.
-  if (a->shift_target != 0 && a->shift_target != 1) return fail(nullptr, TSM_ERR_INVALID_ARG, "shift_target must be 0 or 1");
-  const bool strided_1x1 = k == 1 && stride != 1;
-  if (a->shift_target == 1 && !residual && !dual && !strided_1x1)
-    return fail(nullptr, TSM_ERR_INVALID_ARG, "shift_target 1 needs a residual, a second source or a 1x1 at stride 2");
-  if (T > 0 && a->shift_target == 0) {
-    if (residual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted input with a residual: no such launch (shift_target 1 shifts the residual)");
-    if (dual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted first source with a second source: no such launch");
-    if (strided_1x1) return fail(nullptr, TSM_ERR_INVALID_ARG, "a shifted 1x1 at stride 2 is the identity's (shift_target 1)");
-  }
-  const int pad_ = k / 2;
-  const int ho = (hi + 2 * pad_ - k) / stride + 1, wo = (wi + 2 * pad_ - k) / stride + 1;
-  const int cin2 = a->cin2;
-  if (dual) {
-    if (k != 1) return fail(nullptr, TSM_ERR_UNSUPPORTED, "a second source needs a 1x1 main conv");
-    if (residual) return fail(nullptr, TSM_ERR_INVALID_ARG, "a second source with a residual: no such launch");
-    if (!a->w2 || !a->gamma2 || !a->beta2 || !a->mean2 || !a->var2) return fail(nullptr, TSM_ERR_INVALID_ARG, "NULL pointer (second source)");
-    if (cin2 % 32 != 0 || (cin2 & (cin2 - 1)) != 0 || (prec == tsm::kPrecBf16 && cin2 % 64 != 0))
-      return fail(nullptr, TSM_ERR_UNSUPPORTED, "cin2 must be a power of two >= 32 (TSM_DTYPE_BF16: >= 64)");
-    if (a->stride2 != 1 && a->stride2 != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "stride2 must be 1 or 2");
-    if (a->hi2 <= 0 || a->wi2 <= 0 || (a->hi2 - 1) / a->stride2 + 1 != ho || (a->wi2 - 1) / a->stride2 + 1 != wo)
-      return fail(nullptr, TSM_ERR_INVALID_ARG, "the second source's output size must equal the main conv's");
-  }
-  int fold = 0;
-  if (T > 0) {
-    const int shifted_c = a->shift_target == 0 ? cin : residual ? cout : dual ? cin2 : cin;
-    fold = shifted_c / fold_div;
-    if (n % T != 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "n must be a whole number of T-frame clips");
-    if (fold % (x3 ? 8 : 4) != 0)
-      return fail(nullptr, TSM_ERR_UNSUPPORTED, x3 ? "the bf16 formats shift whole 8-channel groups: fold % 8 == 0"
-                                                   : "fp32 shifts whole 4-channel groups: fold % 4 == 0");
-    if (2 * fold > shifted_c) return fail(nullptr, TSM_ERR_INVALID_ARG, "2 * fold exceeds the shifted tensor's channels");
-  }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  ConvLayer c;
-  c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;
-  c.cp = stem ? 4 : cin;
-  c.kp = (stem && x3) ? round_up(7 * 4 * 8, prec == tsm::kPrecBf16 ? 64 : 32)
-                      : round_up(k * k * c.cp, prec == tsm::kPrecBf16 ? 64 : 32);
-  const int kp2 = dual ? round_up(cin2, prec == tsm::kPrecBf16 ? 64 : 32) : 0;
-#define TSM_HIP0(call)                                                                              \
-  do {                                                                                              \
-    hipError_t _st = (call);                                                                        \
-    if (_st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
-  } while (0)
-  // BatchNorm folded and packed on the host, as tsm_finalize does (a second source: the same K-concatenation as its fused GEMM)
-  auto fetch_packed = [&](const float *w, const float *g, const float *b, const float *m, const float *v, int ci, int kk,
-                          int cp, int kp, std::vector<float> *wp, std::vector<float> *bias) -> int {
-    std::vector<float> hw_((size_t)cout * ci * kk * kk), hg(cout), hb(cout), hm(cout), hv(cout);
-    TSM_HIP0(hipMemcpy(hw_.data(), w, hw_.size() * sizeof(float), hipMemcpyDeviceToHost));
-    TSM_HIP0(hipMemcpy(hg.data(), g, cout * sizeof(float), hipMemcpyDeviceToHost));
-    TSM_HIP0(hipMemcpy(hb.data(), b, cout * sizeof(float), hipMemcpyDeviceToHost));
-    TSM_HIP0(hipMemcpy(hm.data(), m, cout * sizeof(float), hipMemcpyDeviceToHost));
-    TSM_HIP0(hipMemcpy(hv.data(), v, cout * sizeof(float), hipMemcpyDeviceToHost));
-    if (kk == 7 && x3) fold_and_pack_stem_pairs(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, kp, wp, bias);
-    else fold_and_pack(hw_.data(), hg.data(), hb.data(), hm.data(), hv.data(), cout, ci, kk, cp, kp, wp, bias);
-    return TSM_OK;
-  };
-  if (stem && x3 && stride != 2) return fail(nullptr, TSM_ERR_UNSUPPORTED, "the bf16 formats implement the 7x7 stem for stride 2 only");
-  TSM_HIP0(hipStreamSynchronize(s));
+  TSM_HIP(nullptr, hipStreamSynchronize(s));
+  // The weights, prepared as tsm_finalize prepares a layer's (a second source: as its conv3 + downsample GEMM's).
+  ConvLayer c, c2;
+  static_cast<LayerGeom &>(c) = pl.geo;
+  c.kseg = 0;   // (a single source runs whole-K here)
+  c.cin = a->cin; c.cout = cout; c.k = a->k; c.stride = a->stride;
   std::vector<float> wp, bias;
-  int rc = fetch_packed(a->w, a->gamma, a->beta, a->mean, a->var, cin, k, c.cp, c.kp, &wp, &bias);
-  if (rc) return rc;
-  if (dual) {
+  if (int rc = fetch_prepared(c, a->w, a->gamma, a->beta, a->mean, a->var, &wp, &bias)) return rc;
+  if (pl.dual) {
     std::vector<float> wp2, bias2, wf, bf;
-    rc = fetch_packed(a->w2, a->gamma2, a->beta2, a->mean2, a->var2, cin2, 1, cin2, kp2, &wp2, &bias2);
-    if (rc) return rc;
-    concat_k_pair(wp, bias, c.kp, wp2, bias2, kp2, cout, &wf, &bf);
+    c2.cin = c2.cp = a->cin2; c2.cout = cout; c2.kp = pl.kp2;
+    if (int rc = fetch_prepared(c2, a->w2, a->gamma2, a->beta2, a->mean2, a->var2, &wp2, &bias2)) return rc;
+    concat_k_pair(wp, bias, c.kp, wp2, bias2, c2.kp, cout, &wf, &bf);
     wp.swap(wf);
     bias.swap(bf);
   }
-  if (prec == tsm::kPrecBf16x3) to_split(&wp);
-  if (prec == tsm::kPrecBf16) to_bf16(&wp);
-  float *d_w = nullptr, *d_b = nullptr, *d_x4 = nullptr, *d_xs = nullptr, *d_rs = nullptr, *d_ys = nullptr, *d_x2s = nullptr,
-        *d_part = nullptr;
-  // Hostile memory, always on (a debug entry point that allocates per call): every temporary sits between poisoned bands of one
-  // frame of that buffer and starts out poison all over -- so the elements of d_ys / d_part that the launch does not write reach
-  // y as poison (through to_f32 / the reduction), a read before frame 0 or behind the last tile returns poison instead of the
-  // allocator's leftovers, and a stray store is found in the bands after the final synchronise (TSM_ERR_GUARD).
-  struct Scratch {  // frees the temporaries on every exit path (errors included)
-    GuardBuf g[8];
-    int n = 0;
-    ~Scratch() {
-      for (int i = 0; i < n; ++i)
-        if (g[i].base) (void)hipFree(g[i].base);
-    }
-  } scratch;
-  auto galloc = [&scratch](float **p, const char *name, size_t bytes, size_t frame_bytes, size_t elem_bytes) -> hipError_t {
-    GuardBuf &g = scratch.g[scratch.n++];
-    const hipError_t st_ = guard_alloc(&g, name, bytes, frame_bytes, elem_bytes);
-    if (st_ == hipSuccess) *p = g.ptr();
-    return st_;
-  };
+  GuardedScratch scratch;
+  auto alloc = [&scratch](float **q, const char *name, size_t elems, size_t frame_elems) { return scratch.alloc(q, name, elems, frame_elems); };
+  int rc = upload_conv(nullptr, alloc, prec, cout, &wp, bias, &c.d_w, &c.d_b);
+  if (rc) return rc;
+  // The operands in the storage format (fp32: the caller's own, but for the stem's NHWC3 -> NHWC4 / pixel pairs).
   const size_t act_bytes = prec == tsm::kPrecBf16 ? 2 : 4;   // bytes per stored activation element (split-bf16: hi + lo = 4)
-  TSM_HIP0(galloc(&d_w, "d_w", wp.size() * sizeof(float), (size_t)(wp.size() / cout) * sizeof(float), 4));
-  TSM_HIP0(galloc(&d_b, "d_b", bias.size() * sizeof(float), 0, 4));
-  TSM_HIP0(hipMemcpy(d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-  TSM_HIP0(hipMemcpy(d_b, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
-  c.d_w = d_w; c.d_b = d_b;
-  const float *xin = a->x, *x2in = a->x2;
-  const float *rin = residual;
-  float *yout = a->y;
-  const size_t out_elems = (size_t)n * ho * wo * cout;
-  if (stem) {  // NHWC3 -> NHWC4 fp32 / NHWC8 split
-    TSM_HIP0(galloc(&d_x4, "d_x4", (size_t)n * hi * wi * 8 * sizeof(float), (size_t)hi * wi * 8 * sizeof(float), 4));
-    TSM_HIP0(tsm::launch_pack_input(a->x, d_x4, n, hi, wi, 0, prec, s));
+  const size_t in_px = (size_t)hi * wi, out_frame = (size_t)pl.ho * pl.wo * cout, out_elems = (size_t)pl.y_elems;
+  auto staged = [&](const float *src, const char *name, size_t elems, size_t frame_elems, const float **dst) -> int {
+    float *d = nullptr;
+    if (int r = scratch.alloc(&d, name, elems, frame_elems, act_bytes)) return r;
+    TSM_HIP(nullptr, tsm::launch_from_f32(src, d, (int64_t)elems / 8, prec, s));
+    *dst = d;
+    return TSM_OK;
+  };
+  const float *xin = a->x, *x2in = a->x2, *rin = a->residual;
+  float *yout = a->y, *d_x4 = nullptr, *d_ys = nullptr, *d_part = nullptr;
+  if (pl.stem) {
+    if ((rc = scratch.alloc(&d_x4, "d_x4", n * in_px * 8, in_px * 8))) return rc;
+    TSM_HIP(nullptr, tsm::launch_pack_input(a->x, d_x4, n, hi, wi, 0, prec, s));
     xin = d_x4;
-  } else if (x3) {
-    TSM_HIP0(galloc(&d_xs, "d_xs", (size_t)n * hi * wi * cin * act_bytes, (size_t)hi * wi * cin * act_bytes, act_bytes));
-    TSM_HIP0(tsm::launch_from_f32(a->x, d_xs, (int64_t)n * hi * wi * cin / 8, prec, s));
-    xin = d_xs;
+  } else if (x3 && (rc = staged(a->x, "d_xs", (size_t)pl.x_elems, in_px * a->cin, &xin))) {
+    return rc;
   }
   if (x3) {
-    TSM_HIP0(galloc(&d_ys, "d_ys", out_elems * act_bytes, (size_t)ho * wo * cout * act_bytes, act_bytes));
+    if ((rc = scratch.alloc(&d_ys, "d_ys", out_elems, out_frame, act_bytes))) return rc;
     yout = d_ys;
-    if (residual) {
-      TSM_HIP0(galloc(&d_rs, "d_rs", out_elems * act_bytes, (size_t)ho * wo * cout * act_bytes, act_bytes));
-      TSM_HIP0(tsm::launch_from_f32(residual, d_rs, (int64_t)out_elems / 8, prec, s));
-      rin = d_rs;
-    }
-    if (dual) {
-      const size_t x2_elems = (size_t)n * a->hi2 * a->wi2 * cin2;
-      TSM_HIP0(galloc(&d_x2s, "d_x2s", x2_elems * act_bytes, (size_t)a->hi2 * a->wi2 * cin2 * act_bytes, act_bytes));
-      TSM_HIP0(tsm::launch_from_f32(a->x2, d_x2s, (int64_t)x2_elems / 8, prec, s));
-      x2in = d_x2s;
-    }
+    if (rin && (rc = staged(rin, "d_rs", out_elems, out_frame, &rin))) return rc;
+    if (pl.dual && (rc = staged(x2in, "d_x2s", (size_t)pl.x2_elems, (size_t)a->hi2 * a->wi2 * a->cin2, &x2in))) return rc;
   }
-  tsm::ConvParams p = make_params(c, xin, rin, yout, n, hi, wi, a->relu != 0, T > 0 ? T : 0, fold_div, prec);
-  p.fold = fold;
+  tsm::ConvParams p = make_params(c, xin, rin, yout, n, hi, wi, a->relu != 0, pl.T, 1, prec);
+  p.fold = pl.fold;
   p.reverse = a->reverse != 0;
-  if (dual) {   // (as block_launches sets up conv3 + downsample; segmented like the engine's fused GEMM)
-    p.Kp = c.kp + kp2; p.K1 = c.kp; p.kseg_len = segment_len(p.Kp, prec);
-    p.x2 = x2in; p.C2 = cin2; p.Hi2 = a->hi2; p.Wi2 = a->wi2; p.stride2 = a->stride2;
-  }
+  if (pl.dual) set_second_source(&p, c2.kp, x2in, a->cin2, a->hi2, a->wi2, a->stride2);
   // the code as Forward::conv takes it; the split forms get a segment scratch of their own
   const int code = checked_code(p, a->code);
   size_t part_elems = 0;
   if ((code & (kCodeSplitK | kCodeTailK)) && p.kseg_len > 0) {
     part_elems = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
-    TSM_HIP0(galloc(&d_part, "d_part", part_elems * sizeof(float), (size_t)ho * wo * cout * sizeof(float), 4));
+    if ((rc = scratch.alloc(&d_part, "d_part", part_elems, out_frame))) return rc;
   }
   int dev = 0, n_cu = 256;
-  TSM_HIP0(hipGetDevice(&dev));
-  TSM_HIP0(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  TSM_HIP(nullptr, hipGetDevice(&dev));
+  TSM_HIP(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   // (a test / debug entry point that packs weights and allocates on every call: its tuning hook is read per call)
   const char *sd_env = getenv("TSM_STEM_DIRECT");
   hipError_t st;
-  if (stem && x3 && cout == 64 && !(sd_env && atoi(sd_env) == 0))
+  if (pl.stem && x3 && cout == 64 && !(sd_env && atoi(sd_env) == 0))
     st = tsm::launch_stem_direct(xin, c.d_w, c.d_b, yout, n, hi, wi, c.kp, a->relu != 0, prec, s);
   else
-    st = launch_conv_code(p, k, code, d_part, part_elems, n_cu, s);
+    st = launch_conv_code(p, a->k, code, d_part, part_elems, n_cu, s);
   if (st == hipSuccess && x3) st = tsm::launch_to_f32(d_ys, a->y, (int64_t)out_elems / 8, prec, s);
-  hipError_t st2 = hipStreamSynchronize(s);
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("launch_conv: ") + hipGetErrorString(st));
+  const hipError_t st2 = hipStreamSynchronize(s);
+  if (st != hipSuccess) return op_status("launch_conv", st);
   if (st2 != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("conv sync: ") + hipGetErrorString(st2));
   for (int i = 0; i < scratch.n; ++i) {
     std::string msg;
-    TSM_HIP0(guard_verify(scratch.g[i], &msg));
+    TSM_HIP(nullptr, guard_verify(scratch.g[i], &msg));
     if (!msg.empty()) return fail(nullptr, TSM_ERR_GUARD, "tsm_conv_op: " + msg);
   }
   return TSM_OK;
-#undef TSM_HIP0
 }
 
 int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const float *beta, const float *mean,
@@ -1793,28 +1702,18 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
 
 int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi, int32_t c, void *stream) {
   if (!x || !y || n <= 0 || hi <= 0 || wi <= 0) return TSM_ERR_INVALID_ARG;
-  hipError_t st = tsm::launch_maxpool3x3s2(x, y, n, hi, wi, c, tsm::kPrecF32, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("maxpool: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("maxpool", tsm::launch_maxpool3x3s2(x, y, n, hi, wi, c, tsm::kPrecF32, static_cast<hipStream_t>(stream)));
 }
 
 int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int32_t w, float *out,
                    int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream) {
   if (!frames || !out || n <= 0 || h <= 0 || w <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "bad preprocess arguments");
-  if (int rc = check_pixel(pixel)) return rc;
-  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::PreprocParams p{};
+  if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
   p.src = frames; p.dst = out; p.n = n;
   if (!set_crop_geometry(&p, h, w, resize, crop)) return fail(nullptr, TSM_ERR_INVALID_ARG, "crop larger than the resized frame");
-  p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_mode_of(out_layout);
-  p.pre_scale = pre_scale_of(scale_255);
-  hipError_t st = tsm::launch_preprocess(p, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("preprocess: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("preprocess", tsm::launch_preprocess(p, static_cast<hipStream_t>(stream)));
 }
 
 int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, int64_t first_frame, int64_t total_frames,
@@ -1825,14 +1724,8 @@ int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, 
   p.frames = frames; p.out = out; p.n_frames = n_frames; p.frame_bytes = frame_bytes; p.first_frame = first_frame;
   p.total_frames = total_frames; p.first_clip = first_clip; p.pad_frame = pad_frame; p.n_clips = n_clips;
   p.n_segment = n_segment; p.clip_step = clip_step; p.clip_stride = clip_stride;
-  hipError_t st = tsm::launch_gather_clips(p, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess)
-    return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                st == hipErrorInvalidValue ? std::string("gather_clips: a clip of the range reads outside the frame buffer, "
-                                                         "the pad frame is one of the range's video frames, or frame_bytes "
-                                                         "is not a multiple of 16")
-                                           : std::string("gather_clips: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("gather_clips", tsm::launch_gather_clips(p, static_cast<hipStream_t>(stream)),
+                   "a clip of the range reads outside the frame buffer, the pad frame is one of the range's video frames, or frame_bytes is not a multiple of 16");
 }
 
 int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, int64_t first_frame,
@@ -1842,23 +1735,13 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
   if (!frames || !boxes || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: null pointer");
   if (n_frames <= 0 || h <= 0 || w <= 0 || size <= 0 || n_clips <= 0 || n_segment <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: non-positive size");
-  if (int rc = check_pixel(pixel)) return rc;
-  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::ClipPreprocParams p{};
+  if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
   p.src = frames; p.dst = out; p.boxes = boxes; p.n_frames = n_frames; p.first_frame = first_frame;
   p.total_frames = total_frames; p.first_clip = first_clip; p.n_clips = n_clips; p.n_segment = n_segment;
   p.clip_step = clip_step; p.clip_stride = clip_stride; p.h = h; p.w = w; p.size = size;
-  p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_mode_of(out_layout);
-  p.pre_scale = pre_scale_of(scale_255);
-  hipError_t st = tsm::launch_preprocess_clips(p, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess)
-    return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                st == hipErrorInvalidValue ? std::string("preprocess_clips: clip_step is not a multiple of clip_stride, a clip "
-                                                         "starts past the end of the video, or a clip of the range reads "
-                                                         "outside the frame buffer")
-                                           : std::string("preprocess_clips: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("preprocess_clips", tsm::launch_preprocess_clips(p, static_cast<hipStream_t>(stream)),
+                   "clip_step is not a multiple of clip_stride, a clip starts past the end of the video, or a clip of the range reads outside the frame buffer");
 }
 
 int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, int32_t h, int32_t w, const int32_t *index,
@@ -1867,21 +1750,14 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
   if (!frames || !index || !out) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: null pointer");
   if (n_frames <= 0 || h <= 0 || w <= 0 || n_clips <= 0 || n_segment <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: non-positive size");
-  if (int rc = check_pixel(pixel)) return rc;
-  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::IndexedPreprocParams q{};
   tsm::PreprocParams &p = q.pp;
+  if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
   q.index = index; q.n_frames = n_frames; q.n_rows = (int64_t)n_clips * n_segment;
   p.src = frames; p.dst = out;
   if (!set_crop_geometry(&p, h, w, resize, crop))
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_indexed: crop larger than the resized frame");
-  p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_mode_of(out_layout);
-  p.pre_scale = pre_scale_of(scale_255);
-  hipError_t st = tsm::launch_preprocess_indexed(q, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("preprocess_indexed: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("preprocess_indexed", tsm::launch_preprocess_indexed(q, static_cast<hipStream_t>(stream)));
 }
 
 int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel, const int32_t *desc,
@@ -1892,21 +1768,14 @@ int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: arena and desc must be 16-byte aligned");
   if (arena_bytes <= 0 || n_windows <= 0 || n_segment <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: non-positive size");
-  if (int rc = check_pixel(pixel)) return rc;
-  if (int rc = check_out_layout(out_layout)) return rc;
+  tsm::WindowPreprocParams p{};
+  if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
   if (person_crop != 0 && person_crop != 1) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: person_crop must be 0 or 1");
   if (!person_crop && crop > resize)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: crop larger than the resized frame");
-  tsm::WindowPreprocParams p{};
   p.arena = arena; p.dst = out; p.desc = desc; p.arena_bytes = arena_bytes; p.n_windows = n_windows; p.n_segment = n_segment;
   p.person_crop = person_crop; p.resize = resize; p.crop = crop;
-  p.src_is_u8 = pixel == TSM_PIXEL_U8;
-  p.out_mode = out_mode_of(out_layout);
-  p.pre_scale = pre_scale_of(scale_255);
-  hipError_t st = tsm::launch_preprocess_windows(p, static_cast<hipStream_t>(stream));
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("preprocess_windows: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("preprocess_windows", tsm::launch_preprocess_windows(p, static_cast<hipStream_t>(stream)));
 }
 
 int tsm_top1_tally(const float *logits, const int32_t *labels, int32_t n, int32_t num_class, int32_t *pred, int32_t *correct,
@@ -1931,12 +1800,11 @@ int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, co
                          float *out, int32_t out_layout, int32_t resize, int32_t crop, void *stream) {
   if (!frames || !out || n <= 0 || h <= 0 || w <= 0 || resize <= 0 || crop <= 0)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: NULL pointer or non-positive size");
-  if (int rc = check_out_layout(out_layout)) return rc;
   tsm::ImagePreprocParams p{};
+  if (int rc = out_mode_of(out_layout, &p.out_mode)) return rc;
   p.src = static_cast<const unsigned char *>(frames); p.dst = out; p.n = n;
   if (!set_crop_geometry(&p, h, w, resize, crop))          // (torchvision's Resize(int) + center_crop on a PIL image: the same rule)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_image: crop larger than the resized frame");
-  p.out_mode = out_mode_of(out_layout);
   // the table block: [hb 2 * crop][hk crop * ksx] when the width changes, then [vb 2 * crop][vk crop * ksy] when the height does
   const bool horiz = p.nw != w, vert = p.nh != h;
   p.ksx = horiz ? pil_ksize(w, p.nw) : 0;
@@ -1951,9 +1819,7 @@ int tsm_preprocess_image(const void *frames, int32_t n, int32_t h, int32_t w, co
   if (st == hipErrorNotSupported)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "preprocess_image: the rows under one output row's vertical support do not fit 64 KB "
                 "of LDS (downscale " + std::to_string(h) + " -> " + std::to_string(p.nh) + " lines at crop " + std::to_string(crop) + ")");
-  if (st != hipSuccess) return fail(nullptr, st == hipErrorInvalidValue ? TSM_ERR_INVALID_ARG : TSM_ERR_HIP,
-                                    std::string("preprocess_image: ") + hipGetErrorString(st));
-  return TSM_OK;
+  return op_status("preprocess_image", st);
 }
 
 int tsm_frame_votes(const float *logits, int32_t n_frames, int32_t num_class, const int32_t *history, int32_t n_hist,

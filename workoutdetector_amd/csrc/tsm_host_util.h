@@ -1,7 +1,8 @@
 // Pure-host pieces of the engine: BatchNorm folding / weight packing, the bf16 storage-format converters, the
-// segment-length rule, the frame transforms' window and crop arithmetic and the TSM_TUNE_CACHE line parser.  No HIP types,
-// so this header also compiles with plain g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined and
-// fuzzes the parser (CPU only; GPU ASAN is not available on this pool).
+// segment-length rule, a conv layer's packed geometry, tsm_conv_op's argument rules (conv_op_check), the frame transforms'
+// window and crop arithmetic and the TSM_TUNE_CACHE line parser.  No HIP types, so this header also compiles with plain
+// g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined, fuzzes the parser and drives conv_op_check over
+// its refusals, its accepted forms and the ends of int32 (CPU only; GPU ASAN is not available on this pool).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -12,15 +13,18 @@
 #include <string>
 #include <vector>
 
+#include "../../include/tsm_hip.h"
+
 namespace tsm_host {
 
 constexpr float kBnEps = 1e-5f;
+constexpr int kPrecF32 = 0, kPrecBf16x3 = 1, kPrecBf16 = 2;   // = tsm::ConvPrec (tsm_kernels.h)
 
 // Long-K fp32 layers accumulate K in segments of ~16 K-steps (512 channels-taps) so that they can also run
 // split-K (one workgroup per tile and segment) with bit-identical results when the batch is too small to
 // fill the chip with whole-K tiles.  The choice depends on the layer only, never on the batch size.
 inline int segment_len(int kp, int prec) {
-  if (prec != 0 /* kPrecF32 */) return 0;
+  if (prec != kPrecF32) return 0;
   const int nk = kp / 32;
   if (nk < 32) return 0;
   const int nseg = nk / 16;   // (segments of 8 K-steps were measured in round 2: no gain at batch 1-4)
@@ -129,6 +133,129 @@ inline void concat_k_pair(const std::vector<float> &w1, const std::vector<float>
     std::memcpy(&(*wf)[(size_t)o * kpf + kp1], &w2[(size_t)o * kp2], kp2 * sizeof(float));
     (*bf)[o] = b1[o] + b2[o];
   }
+}
+
+// In the engine's storage format: fp32 as it is, split-bf16 in place, bf16 at half the length.
+inline void to_storage(std::vector<float> *v, int prec) {
+  if (prec == kPrecBf16x3) to_split(v);
+  if (prec == kPrecBf16) to_bf16(v);
+}
+
+// ---- one conv layer: geometry and tsm_conv_op's rules, shared by the engine (build_topology) and the per-op conv ------------
+inline int prec_of_dtype(int dtype) {   // tsm_dtype -> precision, -1 for anything else
+  return dtype == TSM_DTYPE_F32 ? kPrecF32 : dtype == TSM_DTYPE_BF16X3 ? kPrecBf16x3 : dtype == TSM_DTYPE_BF16 ? kPrecBf16 : -1;
+}
+inline int packed_layout_of(int prec) {   // the packed device-memory clip layout an engine of that precision consumes in place
+  return prec == kPrecF32 ? TSM_LAYOUT_NTHWC4 : prec == kPrecBf16x3 ? TSM_LAYOUT_NTHWC8S : TSM_LAYOUT_NTHWC8B;
+}
+
+// Output size of a k x k conv with padding k / 2 (k odd; also the 3x3 max-pool) at `stride` > 0.  64-bit inside: total for h >= 1.
+inline int conv_out_size(int h, int k, int stride) { return (int)(((int64_t)h + 2 * (k / 2) - k) / stride + 1); }
+
+struct LayerGeom {
+  int cp = 0;    // channel count the kernel sees (stem: 3 -> 4)
+  int kp = 0;    // padded K
+  int kseg = 0;  // K-steps per accumulation segment (fp32 layers with long K, ConvParams::kseg_len); 0 = unsegmented
+  bool stem_pairs = false;   // K in fold_and_pack_stem_pairs' order
+};
+// The packed geometry of a k x k conv over cin channels (k * k * cin + 63 fits an int).  K = (ky, kx, c) rounded up to the
+// K-step of the format, 32 (bf16: 64); the 7x7 stem sees 4 channels, and in the bf16 formats, whose stride-2 stem reads
+// pixel pairs, K = 7 rows x 4 pairs x 8.  Output channels and, beyond the stem's layout, the stride change nothing.
+inline LayerGeom layer_geometry(int cin, int k, int stride, int prec) {
+  LayerGeom g;
+  g.stem_pairs = k == 7 && stride == 2 && prec != kPrecF32;
+  g.cp = k == 7 ? 4 : cin;
+  g.kp = round_up(g.stem_pairs ? 7 * 4 * 8 : k * k * g.cp, prec == kPrecBf16 ? 64 : 32);
+  g.kseg = segment_len(g.kp, prec);
+  return g;
+}
+
+// conv_op_check's verdict on a tsm_conv_args: TSM_OK and what tsm_conv_op derives from the arguments, or the refusal.
+struct ConvOpPlan {
+  int status = TSM_OK;         // the refusal's tsm_status
+  const char *message = "";    // and its text
+  int prec = 0;
+  bool stem = false, dual = false;
+  int T = 0, fold = 0;         // segments of the shift (0: none) and the channels it moves each way
+  int ho = 0, wo = 0;
+  LayerGeom geo;               // the main conv's cp, kp
+  int kp2 = 0;                 // the second source's padded K (0: none)
+  // element counts, each below 2^31: output rows, the staged input (stem: 8 per pixel), the output, the second source, [cout][kp + kp2]
+  int64_t rows = 0, x_elems = 0, y_elems = 0, x2_elems = 0, w_elems = 0;
+};
+
+constexpr int64_t kInt31 = (int64_t)1 << 31;
+// x * y of two counts in [0, 2^31], saturating at 2^31.
+inline int64_t mul_sat31(int64_t x, int64_t y) { return x >= kInt31 || y >= kInt31 || x * y >= kInt31 ? kInt31 : x * y; }
+
+// Every rule of tsm_conv_op, before its first HIP call: total for ANY argument values (pointers are compared with NULL, never
+// read).  Sizes that the kernels' and the staging's 32-bit arithmetic cannot hold are TSM_ERR_CAPACITY, as in tsm_create.
+inline ConvOpPlan conv_op_check(const tsm_conv_args *a) {
+  ConvOpPlan p;
+  auto refuse = [&p](int status, const char *message) { p.status = status; p.message = message; return p; };
+  if (!a || a->struct_size != (int32_t)sizeof(tsm_conv_args)) return refuse(TSM_ERR_INVALID_ARG, "tsm_conv_args.struct_size must be sizeof(tsm_conv_args)");
+  p.prec = prec_of_dtype(a->dtype);
+  if (p.prec < 0) return refuse(TSM_ERR_UNSUPPORTED, "bad dtype");
+  const bool x3 = p.prec != kPrecF32, bf16 = p.prec == kPrecBf16;   // x3: any non-fp32 storage format
+  const int n = a->n, hi = a->hi, wi = a->wi, cin = a->cin, cout = a->cout, k = a->k, stride = a->stride, cin2 = a->cin2;
+  const int fold_div = a->fold_div > 0 ? a->fold_div : 1;
+  const bool residual = a->residual != nullptr;
+  p.T = a->shift_segments > 0 ? a->shift_segments : 0;
+  p.dual = a->x2 != nullptr;
+  if (!a->x || !a->w || !a->gamma || !a->beta || !a->mean || !a->var || !a->y) return refuse(TSM_ERR_INVALID_ARG, "NULL pointer");
+  if (n <= 0 || hi <= 0 || wi <= 0) return refuse(TSM_ERR_INVALID_ARG, "n, hi and wi must be positive");
+  if (k != 1 && k != 3 && k != 7) return refuse(TSM_ERR_UNSUPPORTED, "k must be 1, 3 or 7");
+  if (stride != 1 && stride != 2) return refuse(TSM_ERR_UNSUPPORTED, "stride must be 1 or 2");
+  p.stem = k == 7;
+  if (p.stem ? (cin != 3) : (cin < 32 || (cin & (cin - 1)) != 0)) return refuse(TSM_ERR_UNSUPPORTED, "cin must be 3 (k=7) or a power of two >= 32");
+  if (bf16 && !p.stem && cin % 64 != 0) return refuse(TSM_ERR_UNSUPPORTED, "TSM_DTYPE_BF16 needs cin % 64 == 0");
+  if (cout <= 0 || cout % 64 != 0) return refuse(TSM_ERR_UNSUPPORTED, "cout must be a multiple of 64");
+  if (p.stem && (residual || p.dual || p.T > 0)) return refuse(TSM_ERR_INVALID_ARG, "the 7x7 stem has no residual, second source or shift");
+  // What the shift moves: the input (0), or the identity (1: block placement) -- the residual, the second source, or for a
+  // 1x1 at stride 2 (a BasicBlock's downsample) the input, which is that block's identity.
+  if (a->shift_target != 0 && a->shift_target != 1) return refuse(TSM_ERR_INVALID_ARG, "shift_target must be 0 or 1");
+  const bool strided_1x1 = k == 1 && stride != 1;
+  if (a->shift_target == 1 && !residual && !p.dual && !strided_1x1)
+    return refuse(TSM_ERR_INVALID_ARG, "shift_target 1 needs a residual, a second source or a 1x1 at stride 2");
+  if (p.T > 0 && a->shift_target == 0) {
+    if (residual) return refuse(TSM_ERR_INVALID_ARG, "a shifted input with a residual: no such launch (shift_target 1 shifts the residual)");
+    if (p.dual) return refuse(TSM_ERR_INVALID_ARG, "a shifted first source with a second source: no such launch");
+    if (strided_1x1) return refuse(TSM_ERR_INVALID_ARG, "a shifted 1x1 at stride 2 is the identity's (shift_target 1)");
+  }
+  p.ho = conv_out_size(hi, k, stride);
+  p.wo = conv_out_size(wi, k, stride);
+  if (p.dual) {
+    if (k != 1) return refuse(TSM_ERR_UNSUPPORTED, "a second source needs a 1x1 main conv");
+    if (residual) return refuse(TSM_ERR_INVALID_ARG, "a second source with a residual: no such launch");
+    if (!a->w2 || !a->gamma2 || !a->beta2 || !a->mean2 || !a->var2) return refuse(TSM_ERR_INVALID_ARG, "NULL pointer (second source)");
+    if (cin2 < 32 || (cin2 & (cin2 - 1)) != 0 || (bf16 && cin2 % 64 != 0))
+      return refuse(TSM_ERR_UNSUPPORTED, "cin2 must be a power of two >= 32 (TSM_DTYPE_BF16: >= 64)");
+    if (a->stride2 != 1 && a->stride2 != 2) return refuse(TSM_ERR_UNSUPPORTED, "stride2 must be 1 or 2");
+    if (a->hi2 <= 0 || a->wi2 <= 0 || conv_out_size(a->hi2, 1, a->stride2) != p.ho || conv_out_size(a->wi2, 1, a->stride2) != p.wo)
+      return refuse(TSM_ERR_INVALID_ARG, "the second source's output size must equal the main conv's");
+  }
+  if (p.T > 0) {
+    const int shifted_c = a->shift_target == 0 ? cin : residual ? cout : p.dual ? cin2 : cin;
+    p.fold = shifted_c / fold_div;
+    if (n % p.T != 0) return refuse(TSM_ERR_INVALID_ARG, "n must be a whole number of T-frame clips");
+    if (p.fold % (x3 ? 8 : 4) != 0)
+      return refuse(TSM_ERR_UNSUPPORTED, x3 ? "the bf16 formats shift whole 8-channel groups: fold % 8 == 0" : "fp32 shifts whole 4-channel groups: fold % 4 == 0");
+    if (2 * (int64_t)p.fold > shifted_c) return refuse(TSM_ERR_INVALID_ARG, "2 * fold exceeds the shifted tensor's channels");
+  }
+  if (p.stem && x3 && stride != 2) return refuse(TSM_ERR_UNSUPPORTED, "the bf16 formats implement the 7x7 stem for stride 2 only");
+  if ((int64_t)k * k * cin + 63 + (p.dual ? (int64_t)cin2 + 63 : 0) > INT32_MAX)
+    return refuse(TSM_ERR_CAPACITY, "the padded K (k * k * cin, plus cin2) must fit a 32-bit int");
+  p.geo = layer_geometry(cin, k, stride, p.prec);
+  p.kp2 = p.dual ? layer_geometry(cin2, 1, a->stride2, p.prec).kp : 0;
+  p.rows = mul_sat31(mul_sat31(n, p.ho), p.wo);
+  if (p.rows >= kInt31) return refuse(TSM_ERR_CAPACITY, "n * ho * wo (output rows) must stay below 2^31");
+  p.x_elems = mul_sat31(mul_sat31(mul_sat31(n, hi), wi), p.stem ? 8 : cin);
+  p.y_elems = mul_sat31(p.rows, cout);
+  p.x2_elems = p.dual ? mul_sat31(mul_sat31(mul_sat31(n, a->hi2), a->wi2), cin2) : 0;
+  p.w_elems = mul_sat31(cout, p.geo.kp + p.kp2);
+  if (p.x_elems >= kInt31 || p.y_elems >= kInt31 || p.x2_elems >= kInt31 || p.w_elems >= kInt31)
+    return refuse(TSM_ERR_CAPACITY, "the input, the output, the second source and the packed weights must each stay below 2^31 elements");
+  return p;
 }
 
 // ---- hostile memory (tsm_conv_op's staging buffers; the engine under TSM_POISON=1) -----------------------------------------

@@ -329,9 +329,16 @@ typedef struct tsm_conv_args {
   const float *gamma2, *beta2, *mean2, *var2;
   int32_t cin2, hi2, wi2, stride2;
   int32_t code;            /* tile code as in tsm_conv_tiles (tile | 0x100 split-K | 0x200 tail split); 0 = heuristic.
-                              A code that does not fit the launch falls back as in the engine: tsm_launch_trace shows what ran */
+                              A code that does not fit the launch falls back as in the engine: tsm_launch_trace shows what ran.
+                              | 0x4000 (TSM_CONV_CODE_SEGMENTED, this entry point only; no tsm_conv_tiles code carries it): a
+                              single fp32 source accumulates K in the engine's segments of ~16 K-steps, as its long-K layers do
+                              (a 1x1 at cin >= 1024, an unshifted 3x3 at cin >= 128), so that 0x100 / 0x200 apply
+                              to it.  Refused (TSM_ERR_INVALID_ARG), never ignored, where no segmented kernel exists: a
+                              residual, a shifted 3x3, the stem, a non-fp32 dtype, a second source (segmented by its whole K
+                              already) or fewer than 32 K-steps */
   int32_t reverse;         /* walk the output tiles from the last one to the first                                     */
 } tsm_conv_args;
+#define TSM_CONV_CODE_SEGMENTED 0x4000
 
 /* One conv launch as the engine makes it (test / debug entry point: packs the weights and allocates on every call; the
  * split forms' segment scratch too).  Refusals come before any launch: TSM_ERR_INVALID_ARG for a shift_target of 1 with

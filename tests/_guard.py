@@ -153,7 +153,7 @@ def check(*tensors):
             _check_one(t)
 
 
-def guarded_conv(x, w, gamma, beta, mean, var, *, residual=None, x2=None, w2=None, bn2=None, stride=1, **kw):
+def guarded_conv(x, w, gamma, beta, mean, var, *, residual=None, x2=None, w2=None, bn2=None, stride=1, segmented=False, **kw):
     """engine.conv_bn_act_nhwc between guards: every operand (the second source, the weights and the BatchNorm vectors
     included) goes in as guarded(), the output as guarded_out(), and check() runs after the call.  Same arguments (CUDA
     tensors), same result."""
@@ -166,7 +166,7 @@ def guarded_conv(x, w, gamma, beta, mean, var, *, residual=None, x2=None, w2=Non
     gbn2 = None if bn2 is None else [guarded(t, name=f'bn2[{i}]') for i, t in enumerate(bn2)]
     y = guarded_out((n, ho, wo, w.shape[0]), torch.float32, x.device, name='y')
     got = conv_bn_act_nhwc(ops['x'], ops['w'], ops['gamma'], ops['beta'], ops['mean'], ops['var'], stride=stride,
-                           residual=ops['residual'], x2=ops['x2'], w2=ops['w2'], bn2=gbn2, out=y, **kw)
+                           residual=ops['residual'], x2=ops['x2'], w2=ops['w2'], bn2=gbn2, out=y, segmented=segmented, **kw)
     assert got is y
     torch.cuda.synchronize()
     check(y, *ops.values(), *(gbn2 or ()))

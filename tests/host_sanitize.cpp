@@ -9,7 +9,7 @@
 //   3. clip_window_range against an enumeration and at the ends of int32 / int64, center_crop_geometry against a table.
 //   4. conv_op_check, the rules of tsm_conv_op: one row per refusal (status and message verbatim), the accepted forms the GPU
 //      tests use with their derived plans, and a loop over random and extreme int32 arguments on which it must be total and
-//      every accepted element count below 2^31.
+//      every accepted element count below 2^31; the segmented single-source form (TSM_CONV_CODE_SEGMENTED): its refusals and plans.
 //   5. layer_geometry / conv_out_size against the per-layer values of ResNet-50, ResNet-18 / 34 and wide-ResNet-50-2.
 #include <climits>
 #include <cstdio>
@@ -383,6 +383,20 @@ static void check_conv_op_refusals() {
        "the input, the output, the second source and the packed weights must each stay below 2^31 elements"},
       {[](tsm_conv_args &a) { a.cin = 1 << 16; a.cout = 1 << 16; }, TSM_ERR_CAPACITY,
        "the input, the output, the second source and the packed weights must each stay below 2^31 elements"},
+      // the segmented single-source form (TSM_CONV_CODE_SEGMENTED): refused, never ignored, where no segmented kernel exists
+      {[](tsm_conv_args &a) { a.cin = 1024; a.dtype = TSM_DTYPE_BF16X3; a.code = 3 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a segmented conv is fp32 only"},
+      {[](tsm_conv_args &a) { a.cin = 1024; a.dtype = TSM_DTYPE_BF16; a.code = TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a segmented conv is fp32 only"},
+      {[](tsm_conv_args &a) { a.k = 7; a.cin = 3; a.stride = 2; a.code = 3 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "the 7x7 stem has no segmented form"},
+      {[](tsm_conv_args &a) { a.cin = 1024; a.residual = &dummy; a.code = 3 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a conv with a residual has no segmented form"},
+      {[](tsm_conv_args &a) { a.k = 3; a.cin = 128; a.residual = &dummy; shift(a, 8, 8, 1); a.code = 4 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG,
+       "a conv with a residual has no segmented form"},
+      {[](tsm_conv_args &a) { a.cin = 1024; second_source(a, 1024, 4, 1); a.code = 3 | 0x100 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG,
+       "a second source is segmented by its whole K already: the segmented bit is a single source's"},
+      {[](tsm_conv_args &a) { a.k = 3; a.cin = 128; shift(a, 8, 8, 0); a.code = 3 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a shifted 3x3 has no segmented form"},
+      {[](tsm_conv_args &a) { a.code = 3 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a segmented conv needs at least 32 K-steps (k * k * cin >= 1024)"},
+      {[](tsm_conv_args &a) { a.cin = 512; a.code = TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG, "a segmented conv needs at least 32 K-steps (k * k * cin >= 1024)"},
+      {[](tsm_conv_args &a) { a.k = 3; a.cin = 64; a.code = 3 | 0x200 | TSM_CONV_CODE_SEGMENTED; }, TSM_ERR_INVALID_ARG,
+       "a segmented conv needs at least 32 K-steps (k * k * cin >= 1024)"},
   };
   for (const Row &r : rows) {
     tsm_conv_args a = conv_args(TSM_DTYPE_F32, 16, 4, 64, 64, 1, 1);
@@ -441,6 +455,37 @@ static void check_conv_op_plans() {
   same(a, {0, 0, 0, 8, 8, 4, 64, 64, 0, 0, 256, 65536, 32768, 0, 8192}, __LINE__);
 }
 
+// The segmented single-source form: the plan carries layer_geometry's segment length exactly when the code asks for it, for the
+// forms the engine segments (build_topology: Bottleneck conv1 = a shifted 1x1 at cin 1024 / 2048, conv2 = a 3x3 at stride 1 or 2
+// at cin 128 .. 512; a no-shift BasicBlock's conv1), and 0 otherwise -- the default launch is untouched.
+static void check_conv_op_segmented() {
+  struct Row { int cin, k, stride, T, kseg, nseg; };
+  const Row rows[] = {{1024, 1, 1, 8, 16, 2}, {2048, 1, 1, 8, 16, 4}, {1024, 1, 1, 0, 16, 2}, {128, 3, 1, 0, 18, 2}, {128, 3, 2, 0, 18, 2},
+                      {256, 3, 1, 0, 18, 4}, {256, 3, 2, 0, 18, 4}, {512, 3, 1, 0, 16, 9}, {512, 3, 2, 0, 16, 9}, {4096, 1, 1, 0, 16, 8},
+                      {8192, 1, 1, 3, 16, 16}};
+  for (const Row &r : rows) {
+    tsm_conv_args a = conv_args(TSM_DTYPE_F32, 24, 5, r.cin, 64, r.k, r.stride);
+    if (r.T) shift(a, r.T, 8, 0);
+    for (int code : {0, 3, 4, 3 | 0x100, 3 | 0x200, -1, INT_MIN, INT_MIN | TSM_CONV_CODE_SEGMENTED, -TSM_CONV_CODE_SEGMENTED}) {   // (a negative code is no code)
+      a.code = code;
+      const ConvOpPlan v = conv_op_check(&a);
+      EXPECT(v.status == TSM_OK && v.kseg == 0 && v.geo.kseg == r.kseg);
+    }
+    for (int code : {0, 3, 4, 3 | 0x100, 4 | 0x100, 3 | 0x200, 0x7fff0000}) {
+      a.code = code | TSM_CONV_CODE_SEGMENTED;
+      const ConvOpPlan v = conv_op_check(&a);
+      const int nk = v.geo.kp / 32;
+      EXPECT(v.status == TSM_OK && v.kseg == r.kseg && v.geo.kp == r.k * r.k * r.cin && (nk + v.kseg - 1) / v.kseg == r.nseg);
+    }
+  }
+  // the other formats keep their whole-K geometry: nothing to ask for
+  for (int dtype : {TSM_DTYPE_BF16X3, TSM_DTYPE_BF16}) {
+    tsm_conv_args a = conv_args(dtype, 24, 5, 1024, 64, 1, 1);
+    const ConvOpPlan v = conv_op_check(&a);
+    EXPECT(v.status == TSM_OK && v.kseg == 0 && v.geo.kseg == 0);
+  }
+}
+
 // Random and extreme int32 arguments: the check is total (UBSAN watches), and whatever it accepts has counts that 32-bit
 // arithmetic holds and that are what the arguments say, recomputed in 128 bits.
 static void fuzz_conv_op_check(unsigned seed, int rounds) {
@@ -466,6 +511,7 @@ static void fuzz_conv_op_check(unsigned seed, int rounds) {
     a.hi2 = pick({a.hi, h2, (int)((unsigned)h2 - 1u)});
     a.wi2 = pick({a.wi, w2, (int)((unsigned)w2 - 1u)});
     shift(a, pick({0, 0, 8}), pick({0, 8, 4}), pick({0, 1}));
+    a.code = pick({0, 0, 3, 3 | TSM_CONV_CODE_SEGMENTED, 0x100 | TSM_CONV_CODE_SEGMENTED});
     if (rng() % 64 == 0) a.y = nullptr;
     const ConvOpPlan v = conv_op_check(&a);
     EXPECT(v.message != nullptr && (v.status == TSM_OK) == (v.message[0] == 0));
@@ -482,6 +528,8 @@ static void fuzz_conv_op_check(unsigned seed, int rounds) {
     EXPECT(p.x2_elems == (p.dual ? (i128)a.n * a.hi2 * a.wi2 * a.cin2 : 0) && p.x2_elems < lim);
     EXPECT(p.w_elems == (i128)a.cout * (p.geo.kp + p.kp2) && p.w_elems < lim);
     EXPECT(p.fold >= 0 && (p.T > 0 || p.fold == 0));
+    const bool asked = a.code > 0 && (a.code & TSM_CONV_CODE_SEGMENTED);
+    EXPECT(p.kseg == (asked ? p.geo.kseg : 0) && (!asked || (p.kseg >= 16 && p.prec == kPrecF32 && !p.stem && !p.dual && !a.residual)));
   }
   EXPECT(accepted > rounds / 50);     // (the loop is not vacuous)
   std::printf("conv_op_check: %d of %d random argument sets accepted\n", accepted, rounds);
@@ -530,6 +578,7 @@ static void check_layer_geometry() {
 int main(int argc, char **argv) {
   check_conv_op_refusals();
   check_conv_op_plans();
+  check_conv_op_segmented();
   check_layer_geometry();
   check_frame_transform_args();
   check_tail_split();

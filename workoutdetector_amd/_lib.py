@@ -14,6 +14,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 LAYOUT_NTCHW, LAYOUT_NTHWC, LAYOUT_NTHWC4, LAYOUT_NTHWC8S, LAYOUT_NTHWC8B = 0, 1, 2, 3, 4
 PIXEL_U8, PIXEL_F32 = 0, 1
 DTYPE_F32, DTYPE_BF16X3, DTYPE_BF16 = 0, 1, 2
+CONV_CODE_SEGMENTED = 0x4000   # TSM_CONV_CODE_SEGMENTED: tsm_conv_args.code only
 DTYPES = {'f32': DTYPE_F32, 'bf16x3': DTYPE_BF16X3, 'bf16': DTYPE_BF16}
 
 STATUS_NAMES = {0: 'TSM_OK', -1: 'TSM_ERR_INVALID_ARG', -2: 'TSM_ERR_HIP', -3: 'TSM_ERR_NOT_FINALIZED',

@@ -376,7 +376,7 @@ tsm::ConvParams make_params(const ConvLayer &c, const float *x, const float *res
   p.Wo = conv_out_size(wi, c.k, c.stride);
   p.Cout = c.cout; p.Kp = c.kp; p.M = n * p.Ho * p.Wo; p.relu = relu ? 1 : 0;
   p.T = T; p.fold = T > 0 ? c.cp / shift_div : 0;
-  p.kseg_len = res ? 0 : c.kseg;   // (no layer with a residual has a long K; the per-op entry point passes kseg = 0)
+  p.kseg_len = res ? 0 : c.kseg;   // (no layer with a residual has a long K; the per-op entry point refuses the pair)
   return p;
 }
 
@@ -1612,7 +1612,7 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   // The weights, prepared as tsm_finalize prepares a layer's (a second source: as its conv3 + downsample GEMM's).
   ConvLayer c, c2;
   static_cast<LayerGeom &>(c) = pl.geo;
-  c.kseg = 0;   // (a single source runs whole-K here)
+  c.kseg = pl.kseg;   // (a single source runs whole-K here unless the code asks for the engine's segments: kCodeOpSegmented)
   c.cin = a->cin; c.cout = cout; c.k = a->k; c.stride = a->stride;
   std::vector<float> wp, bias;
   if (int rc = fetch_prepared(c, a->w, a->gamma, a->beta, a->mean, a->var, &wp, &bias)) return rc;
@@ -1658,7 +1658,7 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   p.reverse = a->reverse != 0;
   if (pl.dual) set_second_source(&p, c2.kp, x2in, a->cin2, a->hi2, a->wi2, a->stride2);
   // the code as Forward::conv takes it; the split forms get a segment scratch of their own
-  const int code = checked_code(p, a->code);
+  const int code = checked_code(p, a->code > 0 ? a->code & ~kCodeOpSegmented : a->code);
   size_t part_elems = 0;
   if ((code & (kCodeSplitK | kCodeTailK)) && p.kseg_len > 0) {
     part_elems = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;

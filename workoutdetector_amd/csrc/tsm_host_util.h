@@ -180,9 +180,15 @@ struct ConvOpPlan {
   int ho = 0, wo = 0;
   LayerGeom geo;               // the main conv's cp, kp
   int kp2 = 0;                 // the second source's padded K (0: none)
+  int kseg = 0;                // a single source's K-steps per segment where the code asks for it (kCodeOpSegmented); else 0
   // element counts, each below 2^31: output rows, the staged input (stem: 8 per pixel), the output, the second source, [cout][kp + kp2]
   int64_t rows = 0, x_elems = 0, y_elems = 0, x2_elems = 0, w_elems = 0;
 };
+
+// tsm_conv_args.code only (TSM_CONV_CODE_SEGMENTED): a single fp32 source accumulates K in layer_geometry's segments, as the
+// engine's add_conv(..., segmented = true) layers do.  Outside kCodeValid (below): tsm_conv_op takes it off before the code
+// is checked, and no engine code, tsm_conv_tiles report or TSM_TUNE_CACHE line ever carries it.
+constexpr int kCodeOpSegmented = 0x4000;
 
 constexpr int64_t kInt31 = (int64_t)1 << 31;
 // x * y of two counts in [0, 2^31], saturating at 2^31.
@@ -247,6 +253,15 @@ inline ConvOpPlan conv_op_check(const tsm_conv_args *a) {
     return refuse(TSM_ERR_CAPACITY, "the padded K (k * k * cin, plus cin2) must fit a 32-bit int");
   p.geo = layer_geometry(cin, k, stride, p.prec);
   p.kp2 = p.dual ? layer_geometry(cin2, 1, a->stride2, p.prec).kp : 0;
+  if (a->code > 0 && (a->code & kCodeOpSegmented)) {   // the engine's segmented single-source form, where a kernel for it exists
+    if (p.prec != kPrecF32) return refuse(TSM_ERR_INVALID_ARG, "a segmented conv is fp32 only");
+    if (p.stem) return refuse(TSM_ERR_INVALID_ARG, "the 7x7 stem has no segmented form");
+    if (residual) return refuse(TSM_ERR_INVALID_ARG, "a conv with a residual has no segmented form");
+    if (p.dual) return refuse(TSM_ERR_INVALID_ARG, "a second source is segmented by its whole K already: the segmented bit is a single source's");
+    if (k == 3 && p.T > 0) return refuse(TSM_ERR_INVALID_ARG, "a shifted 3x3 has no segmented form");
+    if (p.geo.kseg == 0) return refuse(TSM_ERR_INVALID_ARG, "a segmented conv needs at least 32 K-steps (k * k * cin >= 1024)");
+    p.kseg = p.geo.kseg;
+  }
   p.rows = mul_sat31(mul_sat31(n, p.ho), p.wo);
   if (p.rows >= kInt31) return refuse(TSM_ERR_CAPACITY, "n * ho * wo (output rows) must stay below 2^31");
   p.x_elems = mul_sat31(mul_sat31(mul_sat31(n, hi), wi), p.stem ? 8 : cin);
@@ -454,6 +469,7 @@ constexpr int kCodeConv31 = 0x1000;    // on conv3: conv3 + the next block's shi
 constexpr int kCodeFront = 0x2000;     // on conv1: shift + conv1 + the block's stride-2 conv2 as one launch
 constexpr int kCodeFused = kCodeConv23 | kCodeBlock | kCodeConv31 | kCodeFront;
 constexpr int kCodeValid = kCodeTileMask | kCodeSplitK | kCodeTailK | kCodeFused;   // every bit a code may carry
+static_assert((kCodeOpSegmented & kCodeValid) == 0, "the per-op segmented bit must stay clear of the engine's code bits");
 
 // One line of a TSM_TUNE_CACHE file: "<signature>|<bucket>|c0,c1,...".  Succeeds only when the line starts with
 // `want`, holds exactly codes->size() integers and each is a ConvTile below `num_tiles` with no bit outside kCodeValid.

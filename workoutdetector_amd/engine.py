@@ -560,14 +560,17 @@ def temporal_shift_nhwc(x, n_segment: int, fold_div: int = 8, out=None):
 
 def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool = True, residual=None,
                      shift_segments: int = 0, fold_div: int = 8, dtype: str = 'f32', *, shift_identity: bool = False,
-                     x2=None, w2=None, bn2=None, stride2: int = 1, code: Optional[int] = None, reverse: bool = False, out=None):
+                     x2=None, w2=None, bn2=None, stride2: int = 1, code: Optional[int] = None, reverse: bool = False, out=None,
+                     segmented: bool = False):
     """x NHWC [n,h,w,cin], w OIHW; returns NHWC [n,ho,wo,cout].
 
     The keyword arguments reach the engine's other conv forms through ``tsm_conv_op``: ``shift_identity`` shifts the
     identity (the residual, else the second source; for a 1x1 at stride 2 the input) instead of the input; ``x2`` [n,h2,w2,cin2]
     with ``w2`` [cout,cin2,1,1] and ``bn2`` = (gamma, beta, mean, var) adds a 1x1 conv of x2 at ``stride2`` to a 1x1 main conv
     as one K-concatenated GEMM (conv3 + downsample); ``code`` is a tile code (0 = heuristic), ``reverse`` the tile walk.
-    ``out``: write into this tensor (contiguous float32 [n,ho,wo,cout] on x's device) instead of allocating one."""
+    ``out``: write into this tensor (contiguous float32 [n,ho,wo,cout] on x's device) instead of allocating one.
+    ``segmented``: a single fp32 source accumulates K in the engine's segments (TSM_CONV_CODE_SEGMENTED), the form the engine
+    launches for its long-K layers, so that the split-K / tail-split codes apply; refused where no such kernel exists."""
     import torch
     _need_cuda_f32(x=x, w=w, gamma=gamma, beta=beta, mean=mean, var=var, residual=residual, x2=x2, w2=w2)
     x = x.contiguous()
@@ -583,7 +586,7 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
     res = None if residual is None else residual.contiguous()
     args = [t.contiguous() for t in (w, gamma, beta, mean, var)]
     lib = _lib.load()
-    if not shift_identity and x2 is None and code is None and not reverse:
+    if not shift_identity and x2 is None and code is None and not reverse and not segmented:
         _lib.check(lib.tsm_conv_bn_act(x.data_ptr(), *[a.data_ptr() for a in args], _ptr(res), y.data_ptr(),
                                        n, hi, wi, cin, cout, k, stride, int(relu), shift_segments, fold_div,
                                        _lib.DTYPES[dtype], _stream(x)))
@@ -606,7 +609,7 @@ def conv_bn_act_nhwc(x, w, gamma, beta, mean, var, stride: int = 1, relu: bool =
         keep = [x2c] + [t.contiguous() for t in (w2, *bn2)]
         a.x2, a.w2, a.gamma2, a.beta2, a.mean2, a.var2 = (t.data_ptr() for t in keep)
         a.cin2, a.hi2, a.wi2, a.stride2 = cin2, hi2, wi2, stride2
-    a.code, a.reverse = int(code or 0), int(reverse)
+    a.code, a.reverse = int(code or 0) | (_lib.CONV_CODE_SEGMENTED if segmented else 0), int(reverse)
     _lib.check(lib.tsm_conv_op(C.byref(a), _stream(x)))
     del keep
     return y

@@ -11,6 +11,11 @@
 //      tests use with their derived plans, and a loop over random and extreme int32 arguments on which it must be total and
 //      every accepted element count below 2^31; the segmented single-source form (TSM_CONV_CODE_SEGMENTED): its refusals and plans.
 //   5. layer_geometry / conv_out_size against the per-layer values of ResNet-50, ResNet-18 / 34 and wide-ResNet-50-2.
+//   6. the conv launch rules (workoutdetector_amd/csrc/tsm_conv_rules.h): the weight-stationary tile geometries and the tail split
+//      against the values tests/_walk_cases.py restates, conv_route by one hand-written row per kernel family and template arm, one
+//      row per refusal of launch_conv's argument rules, and a loop over random and extreme tsm_conv_args that conv_op_check accepts,
+//      turned into a launch the way tsm_conv_op does, on which every accepted route keeps its invariants (tiles cover M and Cout,
+//      a persistent grid never exceeds its tiles, the tile code asked for is one conv_tile_valid offers).
 #include <climits>
 #include <cstdio>
 #include <random>
@@ -575,6 +580,390 @@ static void check_layer_geometry() {
   EXPECT(v.size() == 64 && v[63] == 1.5f && s3.size() == 64 && h.size() == 32);
 }
 
+// ---- 6. the conv launch rules (csrc/tsm_conv_rules.h) ------------------------------------------------------------------------------
+// A launch's parameter block the way the engine's make_params builds it (pointers: only the null-ness of res / x2 is ever read).
+static tsm::ConvParams layer_params(int prec, int n, int hw, int cin, int cout, int k, int stride, int T = 0, bool residual = false, bool segmented = false) {
+  LayerGeom g = layer_geometry(cin, k, stride, prec);
+  if (!segmented) g.kseg = 0;
+  tsm::ConvParams p = conv_shape_params(g, k, stride, cout, n, hw, hw, true, T, 8, prec, residual);
+  if (residual) p.res = &dummy;
+  return p;
+}
+static void add_second_source(tsm::ConvParams *p, int cin2, int hw2, int stride2) {
+  second_source_shape(p, layer_geometry(cin2, 1, stride2, p->prec).kp, cin2, hw2, hw2, stride2);
+  p->x2 = &dummy;
+}
+// ... and the way tsm_conv_op builds it from arguments conv_op_check accepted
+static tsm::ConvParams conv_op_params(const tsm_conv_args &a, const ConvOpPlan &pl) {
+  LayerGeom g = pl.geo;
+  g.kseg = pl.kseg;
+  tsm::ConvParams p = conv_shape_params(g, a.k, a.stride, a.cout, a.n, a.hi, a.wi, a.relu != 0, pl.T, 1, pl.prec, a.residual != nullptr);
+  p.res = a.residual;
+  p.fold = pl.fold;
+  p.reverse = a.reverse != 0;
+  if (pl.dual) {
+    second_source_shape(&p, pl.kp2, a.cin2, a.hi2, a.wi2, a.stride2);
+    p.x2 = a.x2;
+  }
+  return p;
+}
+
+static void check_conv_geometry() {
+  using namespace tsm;
+  int tr = 0, tc = 0, swz = -1;
+  // conv3x3_ws: (tr, tc) per frame size, as tests/_walk_cases.py restates the rule
+  const int ws[][4] = {{56, 56, 8, 29}, {28, 28, 28, 7}, {14, 14, 14, 14}, {112, 112, 16, 16}, {57, 33, 15, 17}, {3, 5, 3, 5}};
+  for (const auto &r : ws) EXPECT(ws_tile_geometry(r[0], r[1], &tr, &tc) && tr == r[2] && tc == r[3]);
+  EXPECT(!ws_tile_geometry(0, 56, &tr, &tc) && !ws_tile_geometry(56, 0, &tr, &tc) && !ws_tile_geometry(-3, -3, &tr, &tc));
+  EXPECT(ws_tile_geometry(INT_MAX, INT_MAX, &tr, &tc) && tr * tc <= 256 && (tr + 2) * (tc + 2) <= kWsPatchMax);
+  // conv3x3_ws128: tiles per frame at stride 1 (the input frame) and at stride 2 (the OUTPUT frame)
+  const int w8[][3] = {{56, 56, 28}, {28, 28, 7}, {14, 14, 2}, {7, 7, 1}, {57, 33, 18}};
+  for (const auto &r : w8) {
+    EXPECT(ws128_tile_geometry(r[0], r[1], &tr, &tc, &swz) && ws_frame_tiles(1, r[0], r[1], tr, tc) == r[2]);
+    EXPECT(tr * tc <= 128 && (tr + 2) * (tc + 2) <= kW8PatchMax && swz >= 0 && swz < 4);
+    int tr2 = 0, tc2 = 0, swz2 = -1;     // the calling thread's memo answers the same
+    EXPECT(ws128_tile_geometry(r[0], r[1], &tr2, &tc2, &swz2) && tr2 == tr && tc2 == tc && swz2 == swz);
+  }
+  EXPECT(!ws128_tile_geometry(0, 5, &tr, &tc, nullptr));
+  const int s2[][3] = {{56, 56, 49}, {28, 28, 14}, {14, 14, 4}, {7, 7, 1}};
+  for (const auto &r : s2) {
+    EXPECT(ws_s2_tile_geometry(r[0], r[1], &tr, &tc) && ws_frame_tiles(1, r[0], r[1], tr, tc) == r[2]);
+    EXPECT(tc <= ws_s2_lanes_per_row(tc) && tr * ws_s2_lanes_per_row(tc) <= 64 && (2 * tr + 1) * (2 * tc + 1) <= kS2PatchMax);
+    const int m = ws128s2_swap(tr, tc);
+    EXPECT(m >= 0 && m < 4 && m == ws128_best_swap(true, tr, tc) && ws128_read_cycles(true, tr, tc, m) <= ws128_read_cycles(true, tr, tc, 0));
+  }
+  // every lane of a tile lands inside the patch plane the kernel stages (both forms, every geometry above)
+  for (int q = 0; q < 128; ++q) {
+    int prow, pcol, pp0;
+    ws128_lane_pixel(false, 8, 16, 18, q, &prow, &pcol, &pp0);
+    EXPECT(pp0 >= 0 && pp0 + 2 * 18 + 2 < kW8PatchMax && (prow == 0x4000 || (prow < 8 && pcol < 16)));
+    if (q < 64) {
+      ws128_lane_pixel(true, 8, 8, 17, q, &prow, &pcol, &pp0);
+      EXPECT(pp0 >= 0 && pp0 + 2 * 17 + 9 < kS2PatchMax && (prow == 0x4000 || (prow < 8 && pcol < 8)));
+    }
+  }
+  // the tail split (tsm_host_util.h) at the shapes the walk cases quote
+  EXPECT(tail_split_point(25088, 256, 4, 256, (size_t)1 << 30) > 0);
+  EXPECT(tail_split_point(6272, 256, 8, 256, (size_t)1 << 30) == 0);
+  // tile names, dimensions, segments
+  EXPECT(conv_tile_from_name("128x128w8") == kTile128x128w8 && conv_tile_from_name("ws") == kTileWs && conv_tile_from_name("256x256p") == kTile256x256p &&
+         conv_tile_from_name("") == kTileAuto && conv_tile_from_name(nullptr) == kTileAuto && conv_tile_from_name("64x64 ") == kTileAuto);
+  int bm, bn;
+  conv_tile_dims(kTile128x64, &bm, &bn);
+  EXPECT(bm == 128 && bn == 64);
+  conv_tile_dims(kTileWs, &bm, &bn);
+  EXPECT(bm == 256 && bn == 64);
+  ConvParams p = layer_params(kPrecF32, 8, 7, 2048, 512, 1, 1, 8, false, true);
+  EXPECT(p.kseg_len == 16 && conv_num_segments(p) == 4);
+  p.kseg_len = 0;
+  EXPECT(conv_num_segments(p) == 1);
+}
+
+// One row per kernel family and template arm: what runs, on how many tiles, with which grid.
+static void check_conv_routes() {
+  using namespace tsm;
+  struct Want { int family, bm, bn, wgm, wgn; bool shift, res, dual, block_shift; int ntm, ntn; long tiles; unsigned grid; };
+  auto same = [](const ConvParams &p, int ks, int n_cu, const Want &w, int line) {
+    const ConvRoute r = conv_route(p, ks, n_cu);
+    const bool ok = r.family == w.family && r.ks == ks && r.bm == w.bm && r.bn == w.bn && r.wgm == w.wgm && r.wgn == w.wgn && r.shift == w.shift && r.res == w.res &&
+                    r.dual == w.dual && r.block_shift == w.block_shift && r.ntm == w.ntm && r.ntn == w.ntn && r.tiles == w.tiles && r.grid == w.grid;
+    if (!ok) {
+      std::fprintf(stderr, "FAIL route at line %d: family %d tile %dx%d waves %dx%d arm %d%d%d%d ntm %d ntn %d tiles %ld grid %u\n", line, r.family, r.bm, r.bn, r.wgm,
+                   r.wgn, r.shift, r.res, r.dual, r.block_shift, r.ntm, r.ntn, r.tiles, r.grid);
+      ++failures;
+    }
+  };
+  // conv_igemm: 8 frames of 56 x 56 = 25 088 rows
+  ConvParams p = layer_params(kPrecF32, 8, 56, 64, 64, 3, 1);                  // heuristic: 196 tiles of 128 rows < 256 -> 64x64
+  same(p, 3, 256, {kFamIgemm, 64, 64, 2, 2, false, false, false, false, 392, 1, 392, 392}, __LINE__);
+  p = layer_params(kPrecBf16x3, 8, 56, 64, 128, 1, 1, 8);                      // the shifted 1x1 on 128x128
+  p.tile = kTile128x128;
+  same(p, 1, 256, {kFamIgemm, 128, 128, 2, 2, true, false, false, false, 196, 1, 196, 196}, __LINE__);
+  p.tile = kTile128x128w8;                                                     // ... on eight waves
+  same(p, 1, 256, {kFamIgemm, 128, 128, 4, 2, true, false, false, false, 196, 1, 196, 196}, __LINE__);
+  p.tile = kTile128x64;
+  same(p, 1, 256, {kFamIgemm, 128, 64, 2, 2, true, false, false, false, 196, 2, 392, 392}, __LINE__);
+  p = layer_params(kPrecF32, 8, 56, 128, 64, 1, 1, 0, true);                   // 1x1 + residual, one wave per tile
+  p.tile = kTile32x32;
+  same(p, 1, 256, {kFamIgemm, 32, 32, 1, 1, false, true, false, false, 784, 2, 1568, 1568}, __LINE__);
+  p.T = 8; p.fold = 8;                                                         // block placement: the residual through the shift
+  same(p, 1, 256, {kFamIgemm, 32, 32, 1, 1, false, true, false, true, 784, 2, 1568, 1568}, __LINE__);
+  p = layer_params(kPrecBf16, 8, 56, 64, 64, 3, 1, 8);                         // the shifted 3x3 (BasicBlock.conv1)
+  same(p, 3, 256, {kFamIgemm, 64, 64, 2, 2, true, false, false, false, 392, 1, 392, 392}, __LINE__);
+  p = layer_params(kPrecF32, 8, 56, 64, 64, 3, 1, 0, true);                    // 3x3 + residual, and its shifted identity
+  same(p, 3, 256, {kFamIgemm, 64, 64, 2, 2, false, true, false, false, 392, 1, 392, 392}, __LINE__);
+  p.T = 8; p.fold = 8;
+  same(p, 3, 256, {kFamIgemm, 64, 64, 2, 2, false, true, false, true, 392, 1, 392, 392}, __LINE__);
+  p = layer_params(kPrecBf16x3, 8, 28, 64, 128, 1, 1);                         // conv3 + downsample: a second source at stride 2
+  add_second_source(&p, 64, 56, 2);
+  same(p, 1, 256, {kFamIgemm, 64, 64, 2, 2, false, false, true, false, 98, 2, 196, 196}, __LINE__);
+  p.T = 8; p.fold = 8;                                                         // ... through the shift
+  same(p, 1, 256, {kFamIgemm, 64, 64, 2, 2, false, false, true, true, 98, 2, 196, 196}, __LINE__);
+  p = layer_params(kPrecF32, 8, 56, 64, 64, 1, 2, 8);                          // the shifted 1x1 at stride 2 (BasicBlock downsample)
+  same(p, 1, 256, {kFamIgemm, 64, 64, 2, 2, true, false, false, false, 98, 1, 98, 98}, __LINE__);
+  p = layer_params(kPrecBf16, 8, 64, 3, 64, 7, 2);                             // the stem on the generic kernel
+  same(p, 7, 256, {kFamIgemm, 64, 64, 2, 2, false, false, false, false, 128, 1, 128, 128}, __LINE__);
+  // segmented K (fp32): 2048 channels = 64 K-steps in 4 segments of 16; 8 frames of 7 x 7 = 392 rows
+  p = layer_params(kPrecF32, 8, 7, 2048, 512, 1, 1, 8, false, true);
+  same(p, 1, 256, {kFamIgemmSeg, 64, 64, 2, 2, true, false, false, false, 7, 8, 56, 56}, __LINE__);
+  p.tile = kTile128x128w8;                                                     // no segmented form on the large tiles: 64x64 runs
+  same(p, 1, 256, {kFamIgemmSeg, 64, 64, 2, 2, true, false, false, false, 7, 8, 56, 56}, __LINE__);
+  p.tile = kTile32x32;
+  p.ksplit = 1;                                                                // split-K: a workgroup per (tile, segment)
+  same(p, 1, 256, {kFamIgemmSeg, 32, 32, 1, 1, true, false, false, false, 13, 16, 208, 832}, __LINE__);
+  p.tile = kTile64x64;
+  p.ksplit = 2; p.tail_from = 40;                                              // the tail split: 40 whole-K tiles + 16 x 4 pieces
+  same(p, 1, 256, {kFamIgemmSeg, 64, 64, 2, 2, true, false, false, false, 7, 8, 56, 104}, __LINE__);
+  for (int bad : {0, -8, 56, 64, 41}) {                                        // (not inside the tiles, not whole rows of tiles)
+    p.tail_from = bad;
+    EXPECT(conv_route(p, 1, 256).family == kFamInvalid);
+  }
+  p = layer_params(kPrecF32, 8, 14, 512, 2048, 1, 1);                          // the segmented conv3 + downsample GEMM, shifted
+  add_second_source(&p, 1024, 14, 1);
+  EXPECT(p.kseg_len == 16);
+  p.T = 8; p.fold = 128;
+  same(p, 1, 256, {kFamIgemmSeg, 64, 64, 2, 2, false, false, true, true, 25, 32, 800, 800}, __LINE__);
+  // the 256 x 256 LDS-DMA tile (bf16), one-shot and persistent
+  p = layer_params(kPrecBf16, 64, 14, 1024, 256, 1, 1, 8);
+  p.tile = kTile256x256;
+  same(p, 1, 256, {kFamBf16_256, 256, 256, 2, 4, true, false, false, false, 49, 1, 49, 49}, __LINE__);
+  p = layer_params(kPrecBf16, 64, 28, 128, 512, 1, 1, 0, true);
+  p.tile = kTile256x256;
+  same(p, 1, 256, {kFamBf16_256, 256, 256, 2, 4, false, true, false, false, 196, 2, 392, 392}, __LINE__);
+  p.tile = kTile256x256p;                                                      // persistent: a multiple of 8 workgroups, at most the tiles
+  same(p, 1, 256, {kFamBf16_256p, 256, 256, 2, 4, false, true, false, false, 196, 2, 392, 256}, __LINE__);
+  same(p, 1, 304, {kFamBf16_256p, 256, 256, 2, 4, false, true, false, false, 196, 2, 392, 304}, __LINE__);
+  same(p, 1, 15, {kFamBf16_256p, 256, 256, 2, 4, false, true, false, false, 196, 2, 392, 8}, __LINE__);
+  same(p, 1, 7, {kFamBf16_256p, 256, 256, 2, 4, false, true, false, false, 196, 2, 392, 392}, __LINE__);
+  p.T = 8; p.fold = 64;                                                        // block placement exists on the persistent tile only
+  same(p, 1, 256, {kFamBf16_256p, 256, 256, 2, 4, true, true, false, false, 196, 2, 392, 256}, __LINE__);
+  p.tile = kTile256x256;
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid && !conv_tile_valid(p, kTile256x256, 256));
+  p = layer_params(kPrecBf16, 8, 14, 256, 256, 3, 1);
+  p.tile = kTile256x256p;
+  same(p, 3, 256, {kFamBf16_256p, 256, 256, 2, 4, false, false, false, false, 7, 1, 7, 7}, __LINE__);
+  p = layer_params(kPrecBf16, 8, 28, 128, 512, 1, 1);
+  add_second_source(&p, 256, 56, 2);
+  p.tile = kTile256x256p;
+  same(p, 1, 256, {kFamBf16_256p, 256, 256, 2, 4, false, false, true, false, 25, 2, 50, 50}, __LINE__);
+  p.T = 8; p.fold = 32;
+  same(p, 1, 256, {kFamBf16_256p, 256, 256, 2, 4, true, false, true, false, 25, 2, 50, 50}, __LINE__);
+  p = layer_params(kPrecBf16, 8, 56, 64, 256, 1, 1);                           // K = 64: one K-tile, the persistent form needs two
+  p.tile = kTile256x256p;
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid && !conv_tile_valid(p, kTile256x256p, 256));
+  // the weight-stationary kernels (tile code "ws")
+  p = layer_params(kPrecBf16, 8, 56, 64, 64, 3, 1);
+  p.tile = kTileWs;
+  ConvRoute r = conv_route(p, 3, 256);
+  EXPECT(r.family == kFamWs3x3 && r.tr == 8 && r.tc == 29 && r.swz == 0 && r.tiles == 8 * 14 && r.grid == 112);
+  EXPECT(conv_route(p, 3, 64).grid == 64);
+  p = layer_params(kPrecBf16, 8, 28, 128, 128, 3, 1);
+  p.tile = kTileWs;
+  r = conv_route(p, 3, 256);
+  EXPECT(r.family == kFamWs128 && r.tiles == 8 * 7 && r.grid == 56 && r.tr * r.tc <= 128 && r.swz >= 0 && r.swz < 4);
+  p = layer_params(kPrecBf16, 8, 56, 128, 128, 3, 2);
+  p.tile = kTileWs;
+  r = conv_route(p, 3, 256);
+  EXPECT(r.family == kFamWs128s2 && r.tiles == 8 * 14 && r.grid == 112 && r.tr == 4 && r.tc == 14 && r.swz == ws128_best_swap(true, 4, 14));
+  p = layer_params(kPrecBf16, 8, 56, 256, 64, 1, 1, 8);
+  p.tile = kTileWs;
+  r = conv_route(p, 1, 256);
+  EXPECT(r.family == kFamWs1x1 && r.tiles == 196 && r.grid == 196 && conv_route(p, 1, 64).grid == 64);
+  p = layer_params(kPrecBf16, 8, 56, 256, 128, 1, 1, 8);
+  p.tile = kTileWs;
+  r = conv_route(p, 1, 256);
+  EXPECT(r.family == kFamWsn && r.tiles == 196 && r.grid == 196);
+  p = layer_params(kPrecBf16, 8, 28, 512, 128, 1, 1, 8);                       // 512 input channels: tiles of 64 pixels
+  p.tile = kTileWs;
+  r = conv_route(p, 1, 256);
+  EXPECT(r.family == kFamWsn && r.tiles == 98 && r.grid == 98);
+  p = layer_params(kPrecBf16, 8, 28, 128, 512, 1, 1);                          // layer2.0's conv3 + downsample: two halves per pixel tile
+  add_second_source(&p, 256, 56, 2);
+  p.tile = kTileWs;
+  r = conv_route(p, 1, 256);
+  EXPECT(r.family == kFamWsn && r.tiles == 98 && r.grid == 2 * 104);           // (98 tiles < 128 pairs: rounded up to 8)
+  EXPECT(conv_route(p, 1, 64).grid == 2 * 32 && conv_route(p, 1, 16).grid == 16);
+  EXPECT(conv_route(p, 1, 15).family == kFamInvalid && !conv_tile_valid(p, kTileWs, 15) && conv_tile_valid(p, kTileWs, 16));   // pairs of workgroups in eights
+  p = layer_params(kPrecBf16x3, 8, 56, 64, 64, 3, 1);                          // not bf16: no such kernel
+  p.tile = kTileWs;
+  EXPECT(conv_route(p, 3, 256).family == kFamInvalid);
+  p = layer_params(kPrecBf16, 8, 56, 64, 64, 1, 1, 0, true);                   // a residual: none of the 1x1 forms
+  p.tile = kTileWs;
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid);
+  // a tile code that does not fit falls to a refusal here (the engine's checked_code asks conv_tile_valid first)
+  p = layer_params(kPrecF32, 8, 56, 64, 320, 1, 1);
+  p.tile = kTile128x128;
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid && !conv_tile_valid(p, kTile128x128, 256) && conv_tile_valid(p, kTile64x64, 256));
+  p.tile = 9;
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid);
+  p = layer_params(kPrecBf16, 8, 56, 64, 64, 1, 1);
+  p.tile = kTile32x32;                                                         // single-wave tiles: fp32 only
+  EXPECT(conv_route(p, 1, 256).family == kFamInvalid);
+}
+
+// The argument rules that moved out of launch_conv: every row edits an accepted launch into one refusal.  A row shows that the
+// edited launch is refused on every tile, not WHICH rule refused it: each edit leaves the other rules' fields as the accepted base
+// had them, so that the rule its comment names is the first that can object.
+static void check_conv_arg_refusals() {
+  using namespace tsm;
+  struct Row { int base; void (*edit)(ConvParams &, int &ks); };
+  // bases: 0 fp32 1x1 64 -> 64; 1 ... shifted; 2 ... with a residual; 3 ... with a second source; 4 fp32 segmented 1x1; 5 the bf16 stem
+  auto base = [](int which, int *ks) {
+    *ks = which == 5 ? 7 : 1;
+    switch (which) {
+      case 1: return layer_params(kPrecF32, 16, 8, 64, 64, 1, 1, 8);
+      case 2: return layer_params(kPrecF32, 16, 8, 64, 64, 1, 1, 0, true);
+      case 3: { ConvParams p = layer_params(kPrecF32, 16, 8, 64, 64, 1, 1); add_second_source(&p, 64, 8, 1); return p; }
+      case 4: return layer_params(kPrecF32, 16, 8, 1024, 64, 1, 1, 0, false, true);
+      case 5: return layer_params(kPrecBf16, 16, 32, 3, 64, 7, 2);
+      default: return layer_params(kPrecF32, 16, 8, 64, 64, 1, 1);
+    }
+  };
+  const Row rows[] = {
+      {0, [](ConvParams &p, int &) { p.Cout = 96; }},                               // Cout % 64
+      {0, [](ConvParams &p, int &) { p.Kp = 80; }},                                 // Kp % 32
+      {0, [](ConvParams &p, int &) { p.prec = kPrecBf16; p.Kp = 96; }},             // ... bf16: % 64
+      {0, [](ConvParams &p, int &) { p.M = 0; }},
+      {0, [](ConvParams &p, int &) { p.M = -64; }},
+      {0, [](ConvParams &p, int &) { p.logC4 = 3; }},                               // (1 << logC4) * 4 != C
+      {0, [](ConvParams &p, int &) { p.logC4 = -1; }},
+      {0, [](ConvParams &p, int &) { p.logC4 = 31; }},
+      {0, [](ConvParams &p, int &) { p.C = 16; p.logC4 = 2; }},                     // C % 32 (not the stem)
+      {5, [](ConvParams &p, int &) { p.T = 8; p.fold = 0; }},                       // a shifted stem
+      {4, [](ConvParams &p, int &ks) { ks = 3; p.T = 8; p.fold = 128; }},           // a shifted 3x3, segmented
+      {1, [](ConvParams &p, int &) { p.N = 12; }},                                  // N % T
+      {1, [](ConvParams &p, int &) { p.fold = 6; }},                                // fold % 4
+      {2, [](ConvParams &p, int &) { p.T = 8; p.fold = 36; }},                      // 2 fold > Cout (a shifted residual)
+      {3, [](ConvParams &p, int &) { p.T = 8; p.fold = 36; }},                      // 2 fold > C2 (a shifted second source)
+      {3, [](ConvParams &p, int &) { p.T = 8; p.fold = INT_MAX - 3; }},             // ... at the end of int32
+      {3, [](ConvParams &, int &ks) { ks = 3; }},                                   // a second source behind a 3x3
+      {3, [](ConvParams &p, int &) { p.res = &dummy; }},                            // ... with a residual
+      // (K1 % 32 has no row of its own: K1 == C and C % 32 refuse first whatever K1 is)
+      {3, [](ConvParams &p, int &) { p.C2 = 48; p.Kp = 112; }},                     // C2 % 32
+      {3, [](ConvParams &p, int &) { p.Kp = 160; }},                                // K1 + C2 != Kp
+      {3, [](ConvParams &p, int &) { p.K1 = INT_MAX - 31; p.C2 = INT_MAX - 31; }},  // ... whose sum leaves int32
+      {3, [](ConvParams &p, int &) { p.K1 = 32; p.Kp = 96; }},                      // K1 != C
+      {3, [](ConvParams &p, int &) { p.Hi2 = p.Wi2 = 2048; }},                      // the second source's window past 32-bit offsets
+      {2, [](ConvParams &p, int &) { p.T = 8; p.fold = 8; p.Ho = p.Wo = 2048; }},   // the shifted identity's window
+      {0, [](ConvParams &p, int &) { p.prec = 3; }},
+      {0, [](ConvParams &p, int &) { p.prec = -1; }},
+      {0, [](ConvParams &p, int &) { p.kseg_len = -1; }},
+      {4, [](ConvParams &p, int &) { p.prec = kPrecBf16x3; }},                      // segmented, not fp32
+      {4, [](ConvParams &p, int &) { p.res = &dummy; }},                            // segmented with a residual
+      {5, [](ConvParams &p, int &) { p.prec = kPrecF32; p.Kp = 224; p.kseg_len = 4; }},   // a segmented stem
+      {0, [](ConvParams &p, int &) { p.ksplit = 1; }},                              // split-K of an unsegmented launch
+      {4, [](ConvParams &p, int &) { p.ksplit = -1; }},
+      {4, [](ConvParams &p, int &) { p.ksplit = 3; }},
+      {1, [](ConvParams &p, int &) { p.prec = kPrecBf16x3; p.fold = 4; }},          // the bf16 formats shift 8-channel groups
+      {5, [](ConvParams &p, int &) { p.C = 64; p.logC4 = 4; }},                     // the stem sees 4 channels
+      {5, [](ConvParams &p, int &) { p.stride = 1; }},                              // pixel pairs: stride 2
+      {5, [](ConvParams &p, int &) { p.pad = 2; }},                                 // ... pad 3
+      {0, [](ConvParams &p, int &) { p.Hi = p.Wi = 4096; }},                        // the input window past 32-bit offsets
+      {0, [](ConvParams &, int &ks) { ks = 5; }},
+      {0, [](ConvParams &, int &ks) { ks = 0; }},
+      {5, [](ConvParams &p, int &) { p.res = &dummy; }},                            // a stem with a residual
+  };
+  for (int b = 0; b <= 5; ++b) {
+    int ks;
+    const ConvParams p = base(b, &ks);
+    EXPECT(!conv_args_refused(p, ks) && conv_route(p, ks, 256).family != kFamInvalid);
+  }
+  for (const Row &row : rows) {
+    int ks;
+    ConvParams p = base(row.base, &ks);
+    row.edit(p, ks);
+    bool refused = conv_args_refused(p, ks);
+    for (int tile = 0; tile < kNumTiles; ++tile) {
+      p.tile = tile;
+      refused = refused && conv_route(p, ks, 256).family == kFamInvalid;
+    }
+    if (!refused) {
+      std::fprintf(stderr, "FAIL launch refusal row %d: accepted\n", (int)(&row - rows));
+      ++failures;
+    }
+  }
+}
+
+// What every accepted route promises, whatever the arguments.
+static void check_route_invariants(const tsm::ConvParams &p, int ks, int n_cu, const tsm::ConvRoute &r) {
+  using namespace tsm;
+  const bool igemm = r.family == kFamIgemm || r.family == kFamIgemmSeg, t256 = r.family == kFamBf16_256 || r.family == kFamBf16_256p;
+  EXPECT(r.tiles > 0 && r.grid > 0 && r.ks == ks);
+  if (igemm || t256) EXPECT((long)r.bm * r.ntm >= p.M && (long)r.bm * (r.ntm - 1) < p.M && r.bn * r.ntn == p.Cout && r.tiles == (long)r.ntm * r.ntn);
+  if (r.family == kFamIgemm || r.family == kFamBf16_256) EXPECT((long)r.grid == r.tiles);
+  if (r.family == kFamIgemmSeg) EXPECT((r.bm == 64 || r.bm == 32) && r.bn == r.bm && !r.res && (long)r.grid >= r.tiles && (long)r.grid <= r.tiles * conv_num_segments(p));
+  if (r.family >= kFamBf16_256p && r.family != kFamWsn) EXPECT((long)r.grid <= r.tiles);            // the persistent families
+  if (r.family >= kFamWs3x3) EXPECT((long)r.grid <= (n_cu > 16 ? n_cu : 16));
+  if (r.family == kFamWsn)   // (the two-halves form: a PAIR of workgroups per tile, pairs in eights -- idle ones leave at once)
+    EXPECT((long)r.grid <= r.tiles || (p.x2 && p.Kp == 384 && r.grid % 16 == 0 && (long)r.grid / 2 < r.tiles + 8));
+  if (r.family == kFamBf16_256p) EXPECT(r.grid % 8 == 0 || (long)r.grid == r.tiles);
+  if (r.family == kFamWs3x3 || r.family == kFamWs128 || r.family == kFamWs128s2)
+    EXPECT(r.tr > 0 && r.tc > 0 && r.tiles == ws_frame_tiles(p.N, p.Ho, p.Wo, r.tr, r.tc) && r.swz >= 0 && r.swz < 4);
+  if (igemm) EXPECT(r.wgm * r.wgn * 64 <= 512 && !(r.shift && r.res) && !(r.block_shift && r.shift));
+  if (p.tile != kTileAuto) EXPECT(conv_tile_valid(p, p.tile, n_cu));   // (by construction: the route asks it first; kept as the contract's statement)
+}
+
+// Random and extreme int32 tsm_conv_args that conv_op_check accepts, as tsm_conv_op turns them into a launch, with every tile code
+// and split form: conv_route is total on them (UBSAN watches) and every accepted route keeps the invariants.
+static void fuzz_conv_routes(unsigned seed, int rounds) {
+  using namespace tsm;
+  std::mt19937 rng(seed);
+  unsigned wild = 0;
+  auto pick = [&rng, &wild](std::initializer_list<int> likely) {
+    const unsigned r = rng() % 16;
+    if (r >= wild) return likely.begin()[rng() % likely.size()];
+    if (r % 3 == 0) return (int)(1u << (rng() % 31));
+    if (r % 3 == 1) return (int)rng();
+    const int ends[] = {0, -1, INT_MAX, INT_MIN, -(1 << 30), INT_MAX - 1};
+    return ends[rng() % 6];
+  };
+  long args_ok = 0, routed = 0, accepted = 0;
+  int families[kFamWsn + 1] = {};
+  for (int i = 0; i < rounds; ++i) {
+    wild = i % 4 == 0 ? 2 : i % 4 == 1 ? 5 : 0;
+    tsm_conv_args a = conv_args(pick({0, 1, 2, 2}), pick({1, 8, 16, 64, 256}), 1, pick({3, 64, 128, 256, 512, 1024}), pick({64, 128, 256, 512}), pick({1, 1, 3, 7}), pick({1, 1, 2}));
+    a.hi = pick({7, 14, 28, 56, 57});
+    a.wi = rng() % 4 ? a.hi : pick({7, 14, 28, 33});
+    if (a.k == 7) a.cin = pick({3, 3, 3, 64});
+    a.relu = (int)(rng() & 1);
+    a.reverse = (int)(rng() & 1);
+    if (rng() % 4 == 0) a.residual = &dummy;
+    if (rng() % 4 == 0) {
+      second_source(a, pick({64, 128, 256, 1024}), 1, pick({1, 2}));
+      a.hi2 = pick({a.hi, (int)(2u * (unsigned)a.hi)});
+      a.wi2 = pick({a.wi, (int)(2u * (unsigned)a.wi)});
+    }
+    shift(a, pick({0, 0, 8}), pick({8, 8, 4}), pick({0, 1}));
+    a.code = pick({0, 0, TSM_CONV_CODE_SEGMENTED});
+    const ConvOpPlan pl = conv_op_check(&a);
+    if (pl.status != TSM_OK) continue;
+    ++args_ok;
+    ConvParams p = conv_op_params(a, pl);
+    EXPECT(p.M > 0 && p.M == pl.rows && p.Kp == pl.geo.kp + pl.kp2);
+    p.tile = (int)(rng() % (kNumTiles + 1));
+    if (p.kseg_len > 0) {
+      p.ksplit = (int)(rng() % 3);
+      if (p.ksplit == 2) {
+        const long from = tail_split_point(p.M, p.Cout, conv_num_segments(p), 1 + (int)(rng() % 304), (size_t)1 << 40);
+        p.tail_from = from > 0 && rng() % 8 ? (int)from : pick({0, 64, -1});
+        p.ypart = &dummy;
+      }
+    }
+    for (int n_cu : {1, 8, 256}) {
+      const ConvRoute r = conv_route(p, a.k, n_cu);
+      ++routed;
+      EXPECT(p.tile != kTileAuto || p.ksplit == 2 || (r.family == kFamInvalid) == conv_args_refused(p, a.k));   // the heuristic shape always runs
+      if (r.family == kFamInvalid) continue;
+      ++accepted;
+      ++families[r.family];
+      check_route_invariants(p, a.k, n_cu, r);
+    }
+  }
+  EXPECT(args_ok > rounds / 10 && accepted > routed / 10);     // (the loop is not vacuous)
+  for (int f = kFamIgemm; f <= kFamWsn; ++f) EXPECT(rounds < 100000 || families[f] > 0);   // ... and reaches every family
+  std::printf("conv_route: %ld of %d random argument sets passed conv_op_check, %ld of their %ld routes accepted\n", args_ok, rounds, accepted, routed);
+}
+
 int main(int argc, char **argv) {
   check_conv_op_refusals();
   check_conv_op_plans();
@@ -583,9 +972,13 @@ int main(int argc, char **argv) {
   check_frame_transform_args();
   check_tail_split();
   check_guard_bands();
+  check_conv_geometry();
+  check_conv_routes();
+  check_conv_arg_refusals();
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;
   fuzz_tune_lines(1234, rounds);
   fuzz_conv_op_check(4321, 10 * rounds);
+  fuzz_conv_routes(8765, 10 * rounds);
   check_packing(99);
   if (failures) {
     std::fprintf(stderr, "%d failures\n", failures);

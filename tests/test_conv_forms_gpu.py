@@ -17,7 +17,9 @@ import torch
 from oracle.tsm_oracle import bf16_round, temporal_shift
 from tests._conv_ref import conv_ref
 from tests._guard import guarded_conv
+from tests._k_cases import conv_num_segments, segment_len
 from tests._util import IGEMM_TILE_DIMS, assert_bf16_op, assert_close, ran_tile, sweep as _sweep
+from tests._walk_cases import tail_split_applies
 
 pytestmark = pytest.mark.gpu
 
@@ -46,19 +48,6 @@ def _w(cout, cin, k, g):
 
 def _igemm_codes(dtype, cout):
     return [c for c in (1, 2, 3, 4, 5) if (cout % 128 == 0 or c in (2, 3, 4)) and (c != 4 or dtype == 'f32')]
-
-
-def _num_segments(kp):
-    """K segments of an fp32 launch over kp channels (tsm_host::segment_len, conv_num_segments); 1 = unsegmented."""
-    nk = kp // 32
-    if nk < 32:
-        return 1
-    kseg = -(-nk // (nk // 16))
-    return -(-nk // kseg)
-
-
-def _segmented(dtype, kp):
-    return dtype == 'f32' and _num_segments(kp) > 1
 
 
 def _check(got, want, dtype, what):
@@ -140,16 +129,6 @@ TAIL_CASE = DUAL_CASES[-1]
 DUAL_PARAMS = [(d,) + c for c in DUAL_CASES for d in DTYPES if c != TAIL_CASE or d == 'f32']   # (segmented in fp32 only)
 
 
-def _tail_applies(m, cout, nseg, n_cu):
-    ntn, ntm = cout // 64, (m + 63) // 64
-    tiles, slots = ntm * ntn, 5 * n_cu
-    rounds, rem = tiles // slots, tiles % slots
-    if nseg < 2 or rounds < 1 or rem == 0 or rem * 100 > slots * 85:
-        return False
-    frm = rounds * slots // ntn * ntn
-    return 0 < frm < tiles
-
-
 @pytest.mark.parametrize('shift', [False, True])
 @pytest.mark.parametrize('dtype,k1,c2,cout,ho,wo,s2,hi2,wi2,clips,T,div', DUAL_PARAMS)
 def test_conv3_downsample_gemm(hip_lib, dtype, shift, k1, c2, cout, ho, wo, s2, hi2, wi2, clips, T, div):
@@ -157,7 +136,7 @@ def test_conv3_downsample_gemm(hip_lib, dtype, shift, k1, c2, cout, ho, wo, s2, 
     n = clips * T
     x, w, bn = torch.randn(n, k1, ho, wo, generator=g), _w(cout, k1, 1, g), _bn(cout, g)
     x2, w2, bn2 = torch.randn(n, c2, hi2, wi2, generator=g), _w(cout, c2, 1, g), _bn(cout, g)
-    seg = _segmented(dtype, k1 + c2)
+    seg = segment_len(k1 + c2, dtype) > 0
     if seg:   # segmented: whole-K 64x64 / 32x32, split-K and the tail split, all the same bits
         codes = [3, 4, 3 | SPLITK, 4 | SPLITK, 3 | TAILK]
     else:
@@ -167,7 +146,7 @@ def test_conv3_downsample_gemm(hip_lib, dtype, shift, k1, c2, cout, ho, wo, s2, 
         if dtype == 'bf16' and not shift and (k1, c2, cout) in ((64, 64, 256), (128, 256, 512)):
             codes.append(7)   # (conv1x1_wsn_valid: the layer1.0 / layer2.0 shapes, unshifted)
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
-    tail = seg and _tail_applies(n * ho * wo, cout, _num_segments(k1 + c2), n_cu)
+    tail = seg and tail_split_applies(n * ho * wo, cout, conv_num_segments(k1 + c2, segment_len(k1 + c2, dtype)), n_cu)
     if (k1, c2, cout, ho, wo, s2, hi2, wi2, clips, T, div) == TAIL_CASE and n_cu == 256:
         assert tail, 'the tail-split shape must split on a 256-CU part'
 
@@ -269,7 +248,7 @@ def test_shifted_second_source_moves_exactly(hip_lib, dtype, k1, c2, ho, wo, s2,
     scale = np.float32(1.0) / np.sqrt(np.float32(1.0) + np.float32(1e-5))
     if dtype == 'bf16':
         scale = float(bf16_round(torch.tensor([scale])).item())
-    codes = ([3, 4, 3 | SPLITK] if _segmented(dtype, k1 + c2) else _igemm_codes(dtype, cout) +
+    codes = ([3, 4, 3 | SPLITK] if segment_len(k1 + c2, dtype) > 0 else _igemm_codes(dtype, cout) +
              ([8] if dtype == 'bf16' and cout % 256 == 0 else []))
     got = _sweep(codes, lambda code, rev: _run(x, w, bn, dtype, code, rev, relu=False, x2=_nhwc(x2).cuda(), w2=w2.cuda(), bn2=bn2,
                                                stride2=s2, shift_segments=T, fold_div=div, shift_identity=True),

@@ -5,7 +5,16 @@ packing, the bf16 / split-bf16 converters, the segment rule, a conv layer's pack
 conv_out_size), tsm_conv_op's argument rules (conv_op_check) and the TSM_TUNE_CACHE line parser; tests/host_sanitize.cpp
 fuzzes the parser with malformed lines, checks the packers' invariants, holds conv_op_check to one row per refusal (status
 and message), to the plans of the accepted forms the GPU tests use and to a loop over random and extreme int32 arguments,
-and layer_geometry to the per-layer values of every backbone.  CPU only."""
+and layer_geometry to the per-layer values of every backbone.
+
+csrc/tsm_conv_rules.h holds the conv launch rules, HIP-free: the parameter blocks, the weight-stationary kernels' LDS budgets
+and tile geometries (ws_tile_geometry, ws_s2_tile_geometry, ws128_tile_geometry with its bank-conflict model), every kernel
+family's validity and grid rule, conv_tile_valid, the fused forms' rules and conv_route.  host_sanitize.cpp holds the
+geometries and the tail split to the values tests/_walk_cases.py restates, conv_route to one hand-written row per kernel
+family and template arm and one row per refusal of launch_conv's argument rules, and runs 200 000 random and extreme
+tsm_conv_args that conv_op_check accepts, turned into a launch the way tsm_conv_op does, through conv_route for 1, 8 and 256
+CUs: every accepted route covers M and Cout with its tiles, keeps a persistent grid within its tiles and ran a tile that
+conv_tile_valid offers.  CPU only."""
 import os
 import shutil
 import subprocess

@@ -264,15 +264,6 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256_kernel(const ConvParams 
   }
 }
 
-bool conv_bf16_256_valid(const ConvParams &p, int ks) {
-  if (p.prec != kPrecBf16 || (ks != 1 && ks != 3) || p.Cout % 256 != 0 || p.C % 64 != 0 || p.Kp % 64 != 0 || p.kseg_len != 0)
-    return false;
-  if (ks == 3) return !p.res && !p.x2 && p.T == 0;
-  if (p.T > 0) return !p.res && !p.x2;                    // shifted conv1
-  if (p.x2) return !p.res && p.K1 % 64 == 0 && p.C2 % 64 == 0;
-  return true;
-}
-
 // ---------------------------------------------------------------------------------------------
 // conv_bf16_256p: conv_bf16_256's K pipeline run PERSISTENTLY over the tiles of a workgroup, without ever draining.
 //
@@ -710,58 +701,29 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the dead tail stages (zeros) land before the workgroup leaves its LDS
 }
 
-bool conv_bf16_256p_valid(const ConvParams &p, int ks) {
-  if (ks == 1 && p.T > 0 && (p.res || p.x2)) {   // block placement: the shifted identity / second source (8-channel chunks)
-    ConvParams q = p;
-    q.T = 0;
-    return conv_bf16_256p_valid(q, ks) && p.N % p.T == 0 && p.fold % 8 == 0 && 2 * p.fold <= (p.res ? p.Cout : p.C2);
-  }
-  return conv_bf16_256_valid(p, ks) && p.Kp >= 128 && p.Cout <= 2048;
-}
-
 constexpr size_t kLds256Bytes = 131072;
 
-hipError_t launch_conv_bf16_256(ConvParams p, int ks, hipStream_t s) {
-  if (!conv_bf16_256_valid(p, ks)) return hipErrorInvalidValue;
-  p.ntm = (p.M + 255) / 256;
-  p.ntn = p.Cout / 256;
-  const dim3 grid((unsigned)(p.ntm * p.ntn)), block(512);
-  constexpr size_t kLdsBytes = kLds256Bytes;
-  const DeviceInfo &di = device_info();   // the > 64 KB dynamic-LDS opt-in, once per device
-  if (di.status != hipSuccess) return di.status;
-  if (ks == 3) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<3, false>), grid, block, kLdsBytes, s, p);
-  else if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, true>), grid, block, kLdsBytes, s, p);
-  else if (p.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false, true, false>), grid, block, kLdsBytes, s, p);
-  else if (p.x2) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false, false, true>), grid, block, kLdsBytes, s, p);
-  else TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false>), grid, block, kLdsBytes, s, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_conv_bf16_256p(ConvParams p, int ks, hipStream_t s) {
-  if (!conv_bf16_256p_valid(p, ks)) return hipErrorInvalidValue;
-  p.ntm = (p.M + 255) / 256;
-  p.ntn = p.Cout / 256;
-  const DeviceInfo &di = device_info();   // CU count of this device + the > 64 KB dynamic-LDS opt-in
-  if (di.status != hipSuccess) return di.status;
-  const int ntiles = p.ntm * p.ntn;
-  const int slots = di.n_cu & ~7;          // a multiple of 8: a workgroup's tiles then all sit in its own XCD's chunk
-  const dim3 grid((unsigned)(ntiles < slots || slots < 8 ? ntiles : slots)), block(512);
-  if (ks == 3) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<3, false>), grid, block, kLds256pBytes, s, p);
-  else if (p.T > 0 && p.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true, true, false>), grid, block, kLds256pBytes, s, p);
-  else if (p.T > 0 && p.x2) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true, false, true>), grid, block, kLds256pBytes, s, p);
-  else if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true>), grid, block, kLds256pBytes, s, p);
-  else if (p.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, false, true, false>), grid, block, kLds256pBytes, s, p);
-  else if (p.x2) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, false, false, true>), grid, block, kLds256pBytes, s, p);
+// Both kernels.  The route (conv_bf16_256[p]_valid, tile counts, grid: tsm_conv_rules.h) names the family and the arm <KS, SHIFT, RES, DUAL>.
+hipError_t launch_conv_bf16_256(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
+  const dim3 grid(r.grid), block(512);
+  if (r.family == kFamBf16_256) {
+    if (r.ks == 3) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<3, false>), grid, block, kLds256Bytes, s, p);
+    else if (r.shift) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, true>), grid, block, kLds256Bytes, s, p);
+    else if (r.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false, true, false>), grid, block, kLds256Bytes, s, p);
+    else if (r.dual) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false, false, true>), grid, block, kLds256Bytes, s, p);
+    else TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256_kernel<1, false>), grid, block, kLds256Bytes, s, p);
+  } else if (r.ks == 3) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<3, false>), grid, block, kLds256pBytes, s, p);
+  else if (r.shift && r.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true, true, false>), grid, block, kLds256pBytes, s, p);
+  else if (r.shift && r.dual) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true, false, true>), grid, block, kLds256pBytes, s, p);
+  else if (r.shift) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, true>), grid, block, kLds256pBytes, s, p);
+  else if (r.res) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, false, true, false>), grid, block, kLds256pBytes, s, p);
+  else if (r.dual) TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, false, false, true>), grid, block, kLds256pBytes, s, p);
   else TSM_KLAUNCH_WALK(p.reverse, (conv_bf16_256p_kernel<1, false>), grid, block, kLds256pBytes, s, p);
   return hipGetLastError();
 }
 
 hipError_t opt_in_bf16_256() {
-  hipError_t first = hipSuccess;
-  auto opt_in = [&](const void *fn, size_t bytes) {
-    const hipError_t st = lds_opt_in(fn, bytes);
-    if (st != hipSuccess && first == hipSuccess) first = st;
-  };
+  OptIn opt_in;
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256_kernel<1, false>), kLds256Bytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256_kernel<1, true>), kLds256Bytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256_kernel<3, false>), kLds256Bytes);
@@ -774,7 +736,7 @@ hipError_t opt_in_bf16_256() {
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, false, false, true>), kLds256pBytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, true, true, false>), kLds256pBytes);
   opt_in(reinterpret_cast<const void *>(&conv_bf16_256p_kernel<1, true, false, true>), kLds256pBytes);
-  return first;
+  return opt_in.first;
 }
 
 }  // namespace tsm

@@ -540,43 +540,31 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
 #endif
 }
 
-bool bneck_ws_valid(int cin, int n, int h, int w, int T, int fold) {
-  return (cin == 256 || cin == 64) && n > 0 && h > 0 && w >= 1 && w <= 64 && (double)h * w * 512.0 * 3.0 < 2.0e9 &&
-         (T == 0 || (T > 0 && n % T == 0 && fold == cin / 8));
-}
-
 hipError_t launch_bneck_ws(const BneckParams &p, hipStream_t s) {
   if (!p.x || !p.w1 || !p.bias1 || !p.w2 || !p.bias2 || !p.w3 || !p.bias3 || !p.y) return hipErrorInvalidValue;
   if (!bneck_ws_valid(p.cin, p.N, p.H, p.W, p.T, p.fold)) return hipErrorInvalidValue;
   const DeviceInfo &di = device_info();
   if (di.status != hipSuccess) return di.status;
-  const dim3 grid((unsigned)(p.N < di.n_cu ? p.N : di.n_cu)), block(256);
-  if (p.cin == 256 && p.W == 64) {   // the identity from the input slots in LDS
-    if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, true, true>), grid, block, BnLds<256>::kBytesIdl, s, p);
-    else TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, false, true>), grid, block, BnLds<256>::kBytesIdl, s, p);
-  } else if (p.cin == 256) {
-    if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, true>), grid, block, BnLds<256>::kBytes, s, p);
-    else TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, false>), grid, block, BnLds<256>::kBytes, s, p);
-  } else {
-    if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<64, true>), grid, block, BnLds<64>::kBytes, s, p);
-    else TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<64, false>), grid, block, BnLds<64>::kBytes, s, p);
-  }
+  const dim3 grid(persistent_grid(p.N, di.n_cu)), block(256);   // a frame per step
+  const bool idl = p.cin == 256 && p.W == 64, shift = p.T > 0;   // idl: the identity from the input slots in LDS
+  if (idl && shift) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, true, true>), grid, block, BnLds<256>::kBytesIdl, s, p);
+  else if (idl) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, false, true>), grid, block, BnLds<256>::kBytesIdl, s, p);
+  else if (p.cin == 256 && shift) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, true>), grid, block, BnLds<256>::kBytes, s, p);
+  else if (p.cin == 256) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<256, false>), grid, block, BnLds<256>::kBytes, s, p);
+  else if (shift) TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<64, true>), grid, block, BnLds<64>::kBytes, s, p);
+  else TSM_KLAUNCH_WALK(p.reverse, (bneck_ws_kernel<64, false>), grid, block, BnLds<64>::kBytes, s, p);
   return hipGetLastError();
 }
 
 hipError_t opt_in_bneck() {
-  hipError_t first = hipSuccess;
-  auto opt_in = [&](const void *fn, size_t bytes) {
-    const hipError_t st = lds_opt_in(fn, bytes);
-    if (st != hipSuccess && first == hipSuccess) first = st;
-  };
+  OptIn opt_in;
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<256, true>), BnLds<256>::kBytes);
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<256, false>), BnLds<256>::kBytes);
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<256, true, true>), BnLds<256>::kBytesIdl);
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<256, false, true>), BnLds<256>::kBytesIdl);
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<64, true>), BnLds<64>::kBytes);
   opt_in(reinterpret_cast<const void *>(&bneck_ws_kernel<64, false>), BnLds<64>::kBytes);
-  return first;
+  return opt_in.first;
 }
 
 }  // namespace tsm

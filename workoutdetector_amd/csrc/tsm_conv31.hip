@@ -821,26 +821,11 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
   }
 }
 
-// Instantiations: (K3, C, N1) = (128, 512, 128) layer2.k -> layer2.k+1 on conv31_fused_kernel (tiles of 256 rows); (128, 512, 256)
-// layer2.3 -> layer3.0 and (256, 1024, 256) layer3.k -> layer3.k+1 on conv31_pc_kernel (tiles of 128 rows).
-static int conv31_rows(const Conv31Params &p) {
-  if (p.K3 == 128 && p.C == 512 && p.N1 == 128) return 256;
-  if ((p.K3 == 128 && p.C == 512 && p.N1 == 256) || (p.K3 == 256 && p.C == 1024 && p.N1 == 256)) return 128;
-  return 0;
-}
-
-bool conv31_valid(const Conv31Params &p) {
-  const int m = conv31_rows(p);
-  if (m == 0) return false;
-  if (p.n_clips <= 0 || p.HW <= 0 || p.T <= 0 || m % p.T != 0 || m / p.T < 8) return false;
-  if (p.fold != 0 && (p.fold % 64 != 0 || 2 * p.fold > p.C)) return false;  // a 64-channel chunk is shifted as a whole
-  return (double)p.T * p.HW * p.C * 2.0 < 2.0e9;                             // 32-bit offsets inside a clip's block
-}
-
+// (which shapes there are, and their tile rows: conv31_rows / conv31_valid, tsm_conv_rules.h)
 template <int K3, int C, int N1>
 static hipError_t launch_c31(const Conv31Params &p, long ntiles, int n_cu, hipStream_t s) {
   constexpr size_t kLdsBytes = C31<K3, C, N1>::kBytes;
-  const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(512);
+  const dim3 grid(persistent_grid(ntiles, n_cu)), block(512);
   TSM_KLAUNCH_WALK(p.reverse, (conv31_fused_kernel<K3, C, N1>), grid, block, kLdsBytes, s, p);
   return hipGetLastError();
 }
@@ -848,7 +833,7 @@ static hipError_t launch_c31(const Conv31Params &p, long ntiles, int n_cu, hipSt
 template <int K3, int C, int N1>
 static hipError_t launch_c31p(const Conv31Params &p, long ntiles, int n_cu, hipStream_t s) {
   constexpr size_t kLdsBytes = C31P<K3, C, N1>::kBytes;
-  const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(512);
+  const dim3 grid(persistent_grid(ntiles, n_cu)), block(512);
   TSM_KLAUNCH_WALK(p.reverse, (conv31_pc_kernel<K3, C, N1>), grid, block, kLdsBytes, s, p);
   return hipGetLastError();
 }
@@ -868,15 +853,11 @@ hipError_t launch_conv31_fused(const Conv31Params &p_in, hipStream_t s) {
 }
 
 hipError_t opt_in_conv31() {
-  hipError_t first = hipSuccess;
-  auto opt_in = [&](const void *fn, size_t bytes) {
-    const hipError_t st = lds_opt_in(fn, bytes);
-    if (st != hipSuccess && first == hipSuccess) first = st;
-  };
+  OptIn opt_in;
   opt_in(reinterpret_cast<const void *>(&conv31_fused_kernel<128, 512, 128>), C31<128, 512, 128>::kBytes);
   opt_in(reinterpret_cast<const void *>(&conv31_pc_kernel<128, 512, 256>), C31P<128, 512, 256>::kBytes);
   opt_in(reinterpret_cast<const void *>(&conv31_pc_kernel<256, 1024, 256>), C31P<256, 1024, 256>::kBytes);
-  return first;
+  return opt_in.first;
 }
 
 }  // namespace tsm

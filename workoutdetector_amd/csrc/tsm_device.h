@@ -1,7 +1,8 @@
 // Device-side helpers shared by the kernel families of libtsm_hip.so (one translation unit per family: an edit to one
 // family recompiles one object) and the internal launch functions they call across files.  gfx950 only.
 //
-//   tsm_igemm.hip      conv_igemm (every precision, every tile), launch_conv's dispatch, the split-K reduction
+//   tsm_conv_rules.h   (HIP-free) parameter blocks, tile geometries, every family's validity / grid rule, conv_route
+//   tsm_igemm.hip      conv_igemm (every precision, every tile), launch_conv (conv_route -> one launch), the split-K reduction
 //   tsm_bf16_256.hip   conv_bf16_256[p]_kernel: the 256 x 256 LDS-DMA tile, one-shot and persistent
 //   tsm_ws.hip         weight-stationary bf16 kernels: conv3x3_ws[128], conv1x1_ws[n]
 //   tsm_bneck.hip      bneck_ws_kernel: a whole layer1 Bottleneck per launch (bf16)
@@ -32,7 +33,6 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // rows of a group land on 16 distinct 4-bank slots (row*36 mod 64 is a permutation of multiples
 // of 4), so fragment reads are conflict-free; ds_write_b128 of 8 consecutive lanes covers one row.
 constexpr int kLds = 36;
-constexpr int kBK = 32;
 
 constexpr unsigned kInvalid = 0x80000000u;  // >= num_records of every descriptor below
 
@@ -159,6 +159,13 @@ struct DeviceInfo {
 };
 const DeviceInfo &device_info();
 hipError_t lds_opt_in(const void *kernel, size_t bytes);   // hipFuncSetAttribute(MaxDynamicSharedMemorySize)
+struct OptIn {   // a family's opt-ins: the first error of its lds_opt_in calls
+  hipError_t first = hipSuccess;
+  void operator()(const void *fn, size_t bytes) {
+    const hipError_t st = lds_opt_in(fn, bytes);
+    if (st != hipSuccess && first == hipSuccess) first = st;
+  }
+};
 hipError_t opt_in_bf16_256();
 hipError_t opt_in_ws();
 hipError_t opt_in_bneck();
@@ -166,11 +173,9 @@ hipError_t opt_in_conv31();
 hipError_t opt_in_front();
 
 // launch functions one family's dispatch calls in another family's file
-hipError_t launch_conv_bf16_256(ConvParams p, int ks, hipStream_t s);
-hipError_t launch_conv_bf16_256p(ConvParams p, int ks, hipStream_t s);
-hipError_t launch_conv3x3_ws(ConvParams p, hipStream_t s);
-hipError_t launch_conv1x1_ws(const ConvParams &p, hipStream_t s);
-hipError_t launch_conv1x1_wsn(const ConvParams &p, hipStream_t s);
+// (of a route conv_route accepted for one of the file's families, after launch_conv's device_info() status check; p.ntm / p.ntn set)
+hipError_t launch_conv_bf16_256(const ConvParams &p, const ConvRoute &r, hipStream_t s);
+hipError_t launch_conv_ws(const ConvParams &p, const ConvRoute &r, hipStream_t s);
 hipError_t launch_conv23_ws(const Fused23Params &p, hipStream_t s);
 
 }  // namespace tsm

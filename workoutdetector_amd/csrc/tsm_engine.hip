@@ -33,7 +33,6 @@
 namespace {
 
 using namespace tsm_host;
-static_assert(kPrecF32 == tsm::kPrecF32 && kPrecBf16x3 == tsm::kPrecBf16x3 && kPrecBf16 == tsm::kPrecBf16, "one precision enumeration");
 
 // The tag is also what workoutdetector_amd/build.py looks for in the FILE to decide whether a prebuilt library belongs to
 // the tree it sits in (mtimes do not survive a copy to another machine).
@@ -87,12 +86,6 @@ struct Block {
   int cmid = 0;
   int cout3 = 0;   // conv3's output channels where cmid is set: 4 * cmid, or 2 * cmid (conv23_fused2_kernel)
 };
-
-int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
 
 // A device buffer between two poisoned bands (tsm_host_util.h: guard_layout).  tsm_conv_op's temporaries always are; the
 // engine's buffers are under TSM_POISON=1.
@@ -365,28 +358,19 @@ int verify_guards(tsm_engine *e, hipStream_t s) {
   return TSM_OK;
 }
 
+// (the shapes: tsm_host_util.h, conv_shape_params / second_source_shape)
 tsm::ConvParams make_params(const ConvLayer &c, const float *x, const float *res, float *y, int n, int hi,
                             int wi, bool relu, int T, int shift_div, int prec = tsm::kPrecF32) {
-  tsm::ConvParams p{};
-  p.prec = prec;
+  tsm::ConvParams p = conv_shape_params(c, c.k, c.stride, c.cout, n, hi, wi, relu, T, shift_div, prec, res != nullptr);
   p.x = x; p.w = c.d_w; p.bias = c.d_b; p.res = res; p.y = y;
-  p.N = n; p.Hi = hi; p.Wi = wi; p.C = c.cp; p.logC4 = ilog2(c.cp / 4);
-  p.pad = c.k / 2; p.stride = c.stride;
-  p.Ho = conv_out_size(hi, c.k, c.stride);
-  p.Wo = conv_out_size(wi, c.k, c.stride);
-  p.Cout = c.cout; p.Kp = c.kp; p.M = n * p.Ho * p.Wo; p.relu = relu ? 1 : 0;
-  p.T = T; p.fold = T > 0 ? c.cp / shift_div : 0;
-  p.kseg_len = res ? 0 : c.kseg;   // (no layer with a residual has a long K; the per-op entry point refuses the pair)
   return p;
 }
 
 // A second source behind p's own K: one GEMM over K = [p's K | kp2] (Bottleneck.conv3 + the downsample branch, concat_k_pair's
-// matrix; the caller sets p->w and p->bias), segmented by the whole K.  x2 is [N, hi2, wi2, c2], read at stride2.
+// matrix; the caller sets p->w and p->bias).  x2 is [N, hi2, wi2, c2], read at stride2.
 void set_second_source(tsm::ConvParams *p, int kp2, const float *x2, int c2, int hi2, int wi2, int stride2) {
-  p->K1 = p->Kp;
-  p->Kp += kp2;
-  p->kseg_len = segment_len(p->Kp, p->prec);
-  p->x2 = x2; p->C2 = c2; p->Hi2 = hi2; p->Wi2 = wi2; p->stride2 = stride2;
+  second_source_shape(p, kp2, c2, hi2, wi2, stride2);
+  p->x2 = x2;
 }
 
 // $XDG_CACHE_HOME/tsm_hip/tune_cache.txt, else $HOME/.cache/tsm_hip/tune_cache.txt ("" when neither is set or the
@@ -478,8 +462,8 @@ hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial,
 
 // A tile code trusted only after it has been checked against THIS launch: anything else is 0, the heuristic shape (launch_conv_code
 // ignores the split bits where they do not apply).
-int checked_code(const tsm::ConvParams &p, int code) {
-  return code > 0 && (code & ~kCodeValid) == 0 && tsm::conv_tile_valid(p, code & kCodeTileMask) ? code : 0;
+int checked_code(const tsm::ConvParams &p, int code, int n_cu) {
+  return code > 0 && (code & ~kCodeValid) == 0 && tsm::conv_tile_valid(p, code & kCodeTileMask, n_cu) ? code : 0;
 }
 
 struct Tap {
@@ -719,7 +703,7 @@ int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
     int code = tiles ? (*tiles)[idx] : 0;
     if (e->force_tile) code = e->force_tile;
     if (e->force_code >= 0) code = e->force_code;   // (launch_code ignores the split bit where it does not apply)
-    TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, checked_code(p, code)));
+    TSM_LAUNCH_K(e, s, is3x3, launch_code(p, ks, checked_code(p, code, e->n_cu)));
     return TSM_OK;
   }
   std::vector<int> cands;
@@ -736,7 +720,7 @@ int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
     if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) cands.push_back((int)tsm::kTile64x64 | kCodeTailK);
   } else {
     for (int t = 1; t < tsm::kNumTiles; ++t)
-      if (tsm::conv_tile_valid(p, t)) cands.push_back(t);
+      if (tsm::conv_tile_valid(p, t, e->n_cu)) cands.push_back(t);
   }
   float best_ms = 0.f;
   int best = 0;
@@ -1657,16 +1641,16 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
   p.fold = pl.fold;
   p.reverse = a->reverse != 0;
   if (pl.dual) set_second_source(&p, c2.kp, x2in, a->cin2, a->hi2, a->wi2, a->stride2);
+  int dev = 0, n_cu = 256;
+  TSM_HIP(nullptr, hipGetDevice(&dev));
+  TSM_HIP(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   // the code as Forward::conv takes it; the split forms get a segment scratch of their own
-  const int code = checked_code(p, a->code > 0 ? a->code & ~kCodeOpSegmented : a->code);
+  const int code = checked_code(p, a->code > 0 ? a->code & ~kCodeOpSegmented : a->code, n_cu);
   size_t part_elems = 0;
   if ((code & (kCodeSplitK | kCodeTailK)) && p.kseg_len > 0) {
     part_elems = (size_t)tsm::conv_num_segments(p) * p.M * p.Cout;
     if ((rc = scratch.alloc(&d_part, "d_part", part_elems, out_frame))) return rc;
   }
-  int dev = 0, n_cu = 256;
-  TSM_HIP(nullptr, hipGetDevice(&dev));
-  TSM_HIP(nullptr, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   // (a test / debug entry point that packs weights and allocates on every call: its tuning hook is read per call)
   const char *sd_env = getenv("TSM_STEM_DIRECT");
   hipError_t st;

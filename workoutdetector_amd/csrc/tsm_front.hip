@@ -356,17 +356,12 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
 #endif
 }
 
-bool front_s2_valid(int n, int h, int w, int T, int fold) {
-  return n > 0 && h >= 2 && (h & 1) == 0 && w >= 2 && w <= 64 && (double)h * w * 512.0 * 3.0 < 2.0e9 &&
-         (T == 0 || (T > 0 && n % T == 0 && fold == 32));
-}
-
 hipError_t launch_front_s2(const FrontParams &p, hipStream_t s) {
   if (!p.x || !p.w1 || !p.bias1 || !p.w2 || !p.bias2 || !p.y) return hipErrorInvalidValue;
   if (!front_s2_valid(p.N, p.H, p.W, p.T, p.fold)) return hipErrorInvalidValue;
   const DeviceInfo &di = device_info();
   if (di.status != hipSuccess) return di.status;
-  const dim3 grid((unsigned)(p.N < di.n_cu ? p.N : di.n_cu)), block(256);
+  const dim3 grid(persistent_grid(p.N, di.n_cu)), block(256);   // a frame per step
   if (p.T > 0) TSM_KLAUNCH_WALK(p.reverse, front_s2_kernel<true>, grid, block, kFrBytes, s, p);
   else TSM_KLAUNCH_WALK(p.reverse, front_s2_kernel<false>, grid, block, kFrBytes, s, p);
   return hipGetLastError();

@@ -1,6 +1,7 @@
 // Pure-host pieces of the engine: BatchNorm folding / weight packing, the bf16 storage-format converters, the
-// segment-length rule, a conv layer's packed geometry, tsm_conv_op's argument rules (conv_op_check), the frame transforms'
-// window and crop arithmetic and the TSM_TUNE_CACHE line parser.  No HIP types, so this header also compiles with plain
+// segment-length rule, a conv layer's packed geometry and the shapes of its launch's parameter block (conv_shape_params),
+// tsm_conv_op's argument rules (conv_op_check), the frame transforms' window and crop arithmetic and the TSM_TUNE_CACHE line
+// parser.  (The launch rules themselves: tsm_conv_rules.h.)  No HIP types, so this header also compiles with plain
 // g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined, fuzzes the parser and drives conv_op_check over
 // its refusals, its accepted forms and the ends of int32 (CPU only; GPU ASAN is not available on this pool).
 #pragma once
@@ -14,11 +15,14 @@
 #include <vector>
 
 #include "../../include/tsm_hip.h"
+#include "tsm_conv_rules.h"
 
 namespace tsm_host {
 
 constexpr float kBnEps = 1e-5f;
-constexpr int kPrecF32 = 0, kPrecBf16x3 = 1, kPrecBf16 = 2;   // = tsm::ConvPrec (tsm_kernels.h)
+using tsm::kPrecF32;   // the precision enumeration: tsm::ConvPrec (tsm_conv_rules.h)
+using tsm::kPrecBf16x3;
+using tsm::kPrecBf16;
 
 // Long-K fp32 layers accumulate K in segments of ~16 K-steps (512 channels-taps) so that they can also run
 // split-K (one workgroup per tile and segment) with bit-identical results when the batch is too small to
@@ -168,6 +172,35 @@ inline LayerGeom layer_geometry(int cin, int k, int stride, int prec) {
   g.kp = round_up(g.stem_pairs ? 7 * 4 * 8 : k * k * g.cp, prec == kPrecBf16 ? 64 : 32);
   g.kseg = segment_len(g.kp, prec);
   return g;
+}
+
+inline int ilog2(int v) {
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return l;
+}
+
+// The shapes of a conv launch's parameter block from its layer's packed geometry, on n frames of hi x wi pixels (the pointers,
+// which the engine's make_params and set_second_source add, stay NULL).  `residual`: the launch adds one.
+inline tsm::ConvParams conv_shape_params(const LayerGeom &g, int k, int stride, int cout, int n, int hi, int wi, bool relu, int T,
+                                         int shift_div, int prec, bool residual) {
+  tsm::ConvParams p{};
+  p.prec = prec;
+  p.N = n; p.Hi = hi; p.Wi = wi; p.C = g.cp; p.logC4 = ilog2(g.cp / 4);
+  p.pad = k / 2; p.stride = stride;
+  p.Ho = conv_out_size(hi, k, stride);
+  p.Wo = conv_out_size(wi, k, stride);
+  p.Cout = cout; p.Kp = g.kp; p.M = n * p.Ho * p.Wo; p.relu = relu ? 1 : 0;
+  p.T = T; p.fold = T > 0 ? g.cp / shift_div : 0;
+  p.kseg_len = residual ? 0 : g.kseg;   // (no layer with a residual has a long K; the per-op entry point refuses the pair)
+  return p;
+}
+// A second source behind p's own K: one GEMM over K = [p's K | kp2], segmented by the whole K.  [N, hi2, wi2, c2], read at stride2.
+inline void second_source_shape(tsm::ConvParams *p, int kp2, int c2, int hi2, int wi2, int stride2) {
+  p->K1 = p->Kp;
+  p->Kp += kp2;
+  p->kseg_len = segment_len(p->Kp, p->prec);
+  p->C2 = c2; p->Hi2 = hi2; p->Wi2 = wi2; p->stride2 = stride2;
 }
 
 // conv_op_check's verdict on a tsm_conv_args: TSM_OK and what tsm_conv_op derives from the arguments, or the refusal.
@@ -340,12 +373,6 @@ inline bool center_crop_geometry(int h, int w, int resize, int crop, CropGeometr
 
 // ---- tsm_preprocess_windows: the per-window arithmetic its kernel runs, as pure-integer functions that compile for the host
 // too, so that the kernel's bounds logic is tested on a CPU (tests/windows_host.cpp, under ASAN + UBSAN) before it runs on a GPU.
-#if defined(__HIPCC__)
-#define TSM_HOST_DEVICE __host__ __device__
-#else
-#define TSM_HOST_DEVICE
-#endif
-
 // center_crop_geometry in integers: the long side is resize * long / short in int64 (the double quotient above truncates to
 // the same integer: a non-integral quotient lies at least 1 / 65535 from one, far outside a double's rounding of a product
 // below 2^47), the crop starts at round-half-to-even of (dim - crop) / 2.  Equal to center_crop_geometry for h, w in

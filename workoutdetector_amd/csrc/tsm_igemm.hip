@@ -758,33 +758,36 @@ conv_igemm(const ConvParams p) {
   }
 }
 
-int conv_num_segments(const ConvParams &p) {
-  if (p.kseg_len <= 0) return 1;
-  const int nk = p.Kp / kBK;
-  return (nk + p.kseg_len - 1) / p.kseg_len;
-}
+// Launch: conv_route (tsm_conv_rules.h) has decided everything; this maps a route to its instantiation.  The launch trace records a kernel as
+// its launch line spells it, with the enclosing function's template arguments, and tests pin both: so every instantiation keeps a launch line,
+// and the per-precision triple is a macro over the arm's spelling, not a template (whose line would read the same for every arm).
+#define TSM_KLAUNCH_WALK_X(rev, kern, ...) TSM_KLAUNCH_WALK(rev, kern, __VA_ARGS__)   // (expands `kern` before it is spelled)
+// ARM(PREC): an arm's instantiation for one precision (TSM_ARM_*: they spell BM .. RES of the enclosing template); launched for p.prec out
+// of a function with p, grid, block, s, which then RETURNS the launch status.
+#define TSM_LAUNCH_IGEMM_AND_RETURN(ARM)                                                                \
+  do {                                                                                                  \
+    if (p.prec == kPrecBf16x3) TSM_KLAUNCH_WALK_X(p.reverse, ARM(kPrecBf16x3), grid, block, 0, s, p);   \
+    else if (p.prec == kPrecBf16) TSM_KLAUNCH_WALK_X(p.reverse, ARM(kPrecBf16), grid, block, 0, s, p);  \
+    else TSM_KLAUNCH_WALK_X(p.reverse, ARM(kPrecF32), grid, block, 0, s, p);                            \
+    return hipGetLastError();                                                                           \
+  } while (0)
+#define TSM_ARM_DUAL_SHIFT(PREC) (conv_igemm<BM, BN, WGM, WGN, 1, false, false, PREC | kPrecBlockShift, true>)
+#define TSM_ARM_DUAL(PREC) (conv_igemm<BM, BN, WGM, WGN, 1, false, false, PREC, true>)
+#define TSM_ARM_RES_SHIFT(PREC) (conv_igemm<BM, BN, WGM, WGN, KS, false, false, PREC | kPrecBlockShift>)
+#define TSM_ARM_PLAIN(PREC) (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, PREC>)
 
 // Segmented-K instantiations (fp32, 64x64 / 32x32 tiles, no residual): one workgroup per tile, or per
 // (tile, segment) when p.ksplit is set.
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT>
-static hipError_t launch_conv_seg(ConvParams p, hipStream_t s) {
+static hipError_t launch_conv_seg(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
   if constexpr (!((BM == 64 && BN == 64) || (BM == 32 && BN == 32))) {
     return hipErrorInvalidValue;
   } else {
-    p.ntm = (p.M + BM - 1) / BM;
-    p.ntn = p.Cout / BN;
-    const int ntiles = p.ntm * p.ntn;
-    if (p.ksplit == 2 && (!p.ypart || p.tail_from <= 0 || p.tail_from >= ntiles || p.tail_from % p.ntn != 0)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)(p.ksplit == 2 ? p.tail_from + (ntiles - p.tail_from) * conv_num_segments(p)
-                                             : ntiles * (p.ksplit ? conv_num_segments(p) : 1)));
-    const dim3 block(64 * WGM * WGN);
+    const dim3 grid(r.grid), block(64 * WGM * WGN);
     if constexpr (KS == 1 && !SHIFT) {
-      if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
-        return hipGetLastError();
-      }
-      if (p.x2) {
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
+      if (r.dual) {   // (block_shift: block placement, the downsample operand through the shift)
+        if (r.block_shift) TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
+        else TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
         return hipGetLastError();
       }
     }
@@ -794,184 +797,48 @@ static hipError_t launch_conv_seg(ConvParams p, hipStream_t s) {
 }
 
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT, bool RES>
-static hipError_t launch_conv_t(ConvParams p, hipStream_t s) {
-  if (p.kseg_len > 0) {
-    if constexpr (!RES && KS != 7 && !(SHIFT && KS == 3)) return launch_conv_seg<BM, BN, WGM, WGN, KS, SHIFT>(p, s);
+static hipError_t launch_conv_t(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
+  if (r.family == kFamIgemmSeg) {
+    if constexpr (!RES && KS != 7 && !(SHIFT && KS == 3)) return launch_conv_seg<BM, BN, WGM, WGN, KS, SHIFT>(p, r, s);
     else return hipErrorInvalidValue;
   }
-  p.ntm = (p.M + BM - 1) / BM;
-  p.ntn = p.Cout / BN;
-  const dim3 grid((unsigned)(p.ntm * p.ntn));
+  const dim3 grid(r.grid), block(64 * WGM * WGN);
   if constexpr (KS == 1 && !SHIFT && !RES) {
-    if (p.x2 && p.T > 0) {   // block placement: the downsample operand through the shift
-      if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      return hipGetLastError();
-    }
-    if (p.x2) {
-      if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16x3, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecBf16, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      return hipGetLastError();
-    }
+    if (r.dual && r.block_shift) TSM_LAUNCH_IGEMM_AND_RETURN(TSM_ARM_DUAL_SHIFT);   // block placement: the downsample operand through the shift
+    if (r.dual) TSM_LAUNCH_IGEMM_AND_RETURN(TSM_ARM_DUAL);
   }
   if constexpr (RES && !SHIFT && KS != 7) {
-    if (p.T > 0) {   // block placement: the identity through the shift
-      if (p.prec == kPrecBf16x3)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16x3 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else if (p.prec == kPrecBf16)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecBf16 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      else
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, false, false, kPrecF32 | kPrecBlockShift>), grid, dim3(64 * WGM * WGN), 0, s, p);
-      return hipGetLastError();
-    }
+    if (r.block_shift) TSM_LAUNCH_IGEMM_AND_RETURN(TSM_ARM_RES_SHIFT);              // block placement: the identity through the shift
   }
-  if (p.prec == kPrecBf16x3)
-    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16x3>), grid, dim3(64 * WGM * WGN), 0, s, p);
-  else if (p.prec == kPrecBf16)
-    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecBf16>), grid, dim3(64 * WGM * WGN), 0, s, p);
-  else
-    TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, KS, SHIFT, RES, kPrecF32>), grid, dim3(64 * WGM * WGN), 0, s, p);
-  return hipGetLastError();
+  TSM_LAUNCH_IGEMM_AND_RETURN(TSM_ARM_PLAIN);
 }
-
-void conv_tile_shape(const ConvParams &p, int *bm, int *bn) {
-  // Cout is a multiple of 64 everywhere in ResNet-50.  Prefer 128x128; fall back to smaller tiles
-  // when the grid would leave most of the 256 CUs idle (small M at batch 1).
-  int BN = (p.Cout % 128 == 0) ? 128 : 64;
-  int BM = 128;
-  const long tiles128 = (long)((p.M + 127) / 128) * (p.Cout / BN);
-  if (tiles128 < 256) {
-    BM = 64;
-    BN = 64;
-  }
-  *bm = BM;
-  *bn = BN;
-}
-
-int conv_tile_from_name(const char *name) {
-  if (!name) return kTileAuto;
-  static const struct { const char *n; int t; } names[] = {{"128x128", kTile128x128}, {"128x64", kTile128x64},
-      {"64x64", kTile64x64}, {"32x32", kTile32x32}, {"128x128w8", kTile128x128w8}, {"256x256", kTile256x256}, {"ws", kTileWs}, {"256x256p", kTile256x256p}};
-  for (const auto &e : names)
-    if (strcmp(name, e.n) == 0) return e.t;
-  return kTileAuto;
-}
-
-bool conv_tile_valid(const ConvParams &p, int tile) {
-  // Block placement's arms (a shifted identity or second source, a shifted 1x1 at stride 2) exist on conv_igemm's tiles, and for
-  // a 1x1's shifted identity / second source on the persistent 256x256 tile (conv_bf16_256p_kernel<1, true, RES, DUAL>).
-  if (p.T > 0 && (p.res || p.x2 || (p.pad == 0 && p.stride != 1)) &&
-      (tile == kTile256x256 || tile == kTileWs || (tile == kTile256x256p && (p.pad != 0 || !(p.res || p.x2)))))
-    return false;
-  switch (tile) {
-    case kTile128x128: return p.Cout % 128 == 0;
-    case kTile128x64:
-    case kTile64x64: return p.Cout % 64 == 0;
-    case kTile32x32: return p.Cout % 32 == 0 && p.prec == kPrecF32;  // single-wave tiles: fp32 only
-    case kTile128x128w8: return p.Cout % 128 == 0;
-    case kTile256x256:   // (ks is checked at launch: the stem has C == 4 and never qualifies; a 3x3 (pad 1) only unshifted, no residual)
-      return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.C % 64 == 0 && !(p.res && p.x2) && (p.pad != 1 || (!p.res && p.T == 0)) &&
-             (!p.x2 || (p.K1 % 64 == 0 && p.C2 % 64 == 0));
-    case kTile256x256p:   // (ks is checked at launch; at least two K-tiles, the bias of all channels in LDS)
-      return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.Cout <= 2048 && p.C % 64 == 0 && p.Kp >= 128 && !(p.res && p.x2) &&
-             (p.pad != 1 || (!p.res && p.T == 0)) &&
-             (!p.x2 || (p.K1 % 64 == 0 && p.C2 % 64 == 0));
-    case kTileWs: return conv3x3_ws_valid(p) || conv3x3_ws128_valid(p) || conv1x1_ws_valid(p) || conv1x1_wsn_valid(p);   // (pad singles out 3x3 / 1x1)
-    default: return false;
-  }
-}
-
-void conv_tile_dims(int tile, int *bm, int *bn) {
-  *bm = (tile == kTile256x256 || tile == kTile256x256p || tile == kTileWs) ? 256 : tile == kTile32x32 ? 32 : (tile == kTile64x64 ? 64 : 128);
-  *bn = (tile == kTile256x256 || tile == kTile256x256p) ? 256 : tile == kTile32x32 ? 32 : ((tile == kTile128x128 || tile == kTile128x128w8) ? 128 : 64);
-}
-
 
 template <int KS, bool SHIFT, bool RES>
-static hipError_t launch_conv_ks(const ConvParams &p_in, hipStream_t s) {
-  ConvParams p = p_in;
-  int bm, bn;
-  conv_tile_shape(p, &bm, &bn);
-  if (p.tile != kTileAuto) {
-    if (!conv_tile_valid(p, p.tile)) return hipErrorInvalidValue;
-    conv_tile_dims(p.tile, &bm, &bn);
-  }
-  if (p.tile == kTile256x256) {
-    if constexpr (KS != 7) return launch_conv_bf16_256(p, KS, s);
-    else return hipErrorInvalidValue;
-  }
-  if (p.tile == kTile256x256p) {
-    if constexpr (KS != 7) return launch_conv_bf16_256p(p, KS, s);
-    else return hipErrorInvalidValue;
-  }
-  if (p.tile == kTileWs) {
-    if constexpr (KS == 3) return launch_conv3x3_ws(p, s);
-    else if constexpr (KS == 1 && !RES) return conv1x1_ws_valid(p) ? launch_conv1x1_ws(p, s) : launch_conv1x1_wsn(p, s);
-    else return hipErrorInvalidValue;
-  }
-  if (p.kseg_len > 0 && !(bm == 32 && bn == 32)) {  // segmented accumulation exists on 64x64 / 32x32 tiles only
-    bm = 64;
-    bn = 64;
-    if (p.tile == kTile128x128w8) p.tile = kTile64x64;
-  }
-  if (bm == 32 && bn == 32) {
-    if (p.prec != kPrecF32) return hipErrorInvalidValue;
-    return launch_conv_t<32, 32, 1, 1, KS, SHIFT, RES>(p, s);
-  }
-  if (bm == 128 && bn == 128 && p.tile == kTile128x128w8) return launch_conv_t<128, 128, 4, 2, KS, SHIFT, RES>(p, s);
-  if (bm == 128 && bn == 128) return launch_conv_t<128, 128, 2, 2, KS, SHIFT, RES>(p, s);
-  if (bm == 128 && bn == 64) return launch_conv_t<128, 64, 2, 2, KS, SHIFT, RES>(p, s);
-  return launch_conv_t<64, 64, 2, 2, KS, SHIFT, RES>(p, s);
+static hipError_t launch_conv_ks(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
+  if (r.bm == 32) return launch_conv_t<32, 32, 1, 1, KS, SHIFT, RES>(p, r, s);
+  if (r.bm == 128 && r.bn == 128 && r.wgm == 4) return launch_conv_t<128, 128, 4, 2, KS, SHIFT, RES>(p, r, s);
+  if (r.bm == 128 && r.bn == 128) return launch_conv_t<128, 128, 2, 2, KS, SHIFT, RES>(p, r, s);
+  if (r.bm == 128) return launch_conv_t<128, 64, 2, 2, KS, SHIFT, RES>(p, r, s);
+  return launch_conv_t<64, 64, 2, 2, KS, SHIFT, RES>(p, r, s);
 }
 
 hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
+  // These tile codes' families size a persistent grid by the device's CU count and need its > 64 KB LDS opt-in: asked BEFORE the
+  // route, which takes the CU count (so a launch that its arguments refuse has run device_info() too).
+  const bool device = p_in.tile == kTile256x256 || p_in.tile == kTile256x256p || p_in.tile == kTileWs;
+  const DeviceInfo *di = device ? &device_info() : nullptr;
+  const ConvRoute r = conv_route(p_in, ks, di ? di->n_cu : 0);
+  if (r.family == kFamInvalid) return hipErrorInvalidValue;
+  if (di && di->status != hipSuccess) return di->status;
   ConvParams p = p_in;
-  const int kc = p.prec == kPrecBf16 ? 64 : kBK;  // channels per K-step
-  if (p.Cout % 64 != 0 || p.Kp % kc != 0 || p.M <= 0) return hipErrorInvalidValue;
-  if ((1 << p.logC4) * 4 != p.C) return hipErrorInvalidValue;
-  if (ks != 7 && p.C % kc != 0) return hipErrorInvalidValue;
-  // temporal shift of the A operand: 1x1 (Bottleneck.conv1; stride 2: BasicBlock downsample under block placement), 3x3 at
-  // stride 1 or 2 (BasicBlock.conv1; unsegmented only).  With a residual or a second source (block placement) T shifts the
-  // identity / x2 instead, fold = its channels / shift_div.
-  if (p.T > 0 && ((ks != 1 && ks != 3) || (ks == 3 && p.kseg_len > 0) || p.N % p.T != 0 || p.fold % 4 != 0 ||
-                  (p.res && 2 * p.fold > p.Cout) || (p.x2 && 2 * p.fold > p.C2)))
-    return hipErrorInvalidValue;
-  if (p.x2 && (ks != 1 || p.res || p.K1 % kc != 0 || p.C2 % kc != 0 || p.K1 + p.C2 != p.Kp || p.K1 != p.C))
-    return hipErrorInvalidValue;
-  // the second source's window: the frames of a tile (one more before it when shifted), through 32-bit offsets
-  if (p.x2 && (128.0 / ((double)p.Ho * p.Wo) + 4.0) * (double)p.Hi2 * p.Wi2 * p.C2 * 4.0 > 2.0e9) return hipErrorInvalidValue;
-  // a shifted identity reads rows up to one frame either side of the tile through 32-bit offsets
-  if (p.T > 0 && p.res && (128.0 + 2.0 * p.Ho * p.Wo) * p.Cout * 4.0 > 2.0e9) return hipErrorInvalidValue;
-  if (p.prec != kPrecF32 && p.prec != kPrecBf16x3 && p.prec != kPrecBf16) return hipErrorInvalidValue;
-  if (p.kseg_len < 0 || (p.kseg_len > 0 && (p.prec != kPrecF32 || p.res || ks == 7))) return hipErrorInvalidValue;
-  if ((p.ksplit && p.kseg_len <= 0) || p.ksplit < 0 || p.ksplit > 2) return hipErrorInvalidValue;
-  if (p.prec != kPrecF32 && p.T > 0 && p.fold % 8 != 0) return hipErrorInvalidValue;
-  // stem: 4 channels per pixel (3 + a zero); the bf16 formats read pixel pairs, which needs stride 2 / pad 3
-  if (ks == 7 && (p.C != 4 || (p.prec != kPrecF32 && (p.stride != 2 || p.pad != 3)))) return hipErrorInvalidValue;
-  // 32-bit byte offsets inside a workgroup's rebased window: a tile touches at most
-  // BM/(Ho*Wo) + 4 input frames.
-  const double frames = 128.0 / ((double)p.Ho * p.Wo) + 4.0;
-  if (frames * (double)p.Hi * p.Wi * p.C * 4.0 > 2.0e9) return hipErrorInvalidValue;
-  switch (ks) {
-    case 1:   // (with a residual or a second source, T > 0 is block placement's shifted identity: launch_conv_t)
-      if (p.res) return launch_conv_ks<1, false, true>(p, s);
-      return p.T > 0 && !p.x2 ? launch_conv_ks<1, true, false>(p, s) : launch_conv_ks<1, false, false>(p, s);
-    case 3:
-      if (p.res) return launch_conv_ks<3, false, true>(p, s);
-      return p.T > 0 ? launch_conv_ks<3, true, false>(p, s) : launch_conv_ks<3, false, false>(p, s);
-    case 7: return p.res ? hipErrorInvalidValue : launch_conv_ks<7, false, false>(p, s);
-    default: return hipErrorInvalidValue;
-  }
+  p.ntm = r.ntm; p.ntn = r.ntn;
+  if (r.family == kFamBf16_256 || r.family == kFamBf16_256p) return launch_conv_bf16_256(p, r, s);
+  if (r.family >= kFamWs3x3) return launch_conv_ws(p, r, s);
+  if (p.ksplit == 2 && !p.ypart) return hipErrorInvalidValue;   // (the tail split's segment sums)
+  if (ks == 1) return r.res ? launch_conv_ks<1, false, true>(p, r, s) : r.shift ? launch_conv_ks<1, true, false>(p, r, s) : launch_conv_ks<1, false, false>(p, r, s);
+  if (ks == 3) return r.res ? launch_conv_ks<3, false, true>(p, r, s) : r.shift ? launch_conv_ks<3, true, false>(p, r, s) : launch_conv_ks<3, false, false>(p, r, s);
+  return launch_conv_ks<7, false, false>(p, r, s);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Split-K reduction (fp32): the segment sums of a ksplit launch are added in segment order -- the order the

@@ -27,8 +27,7 @@ namespace tsm {
 // Per output the products enter the fp32 accumulator in conv_igemm's order (taps ascending, k16 groups ascending, the
 // same eight k per lane half; a*b commutes), so results are bit-identical to the other bf16 tiles.
 // ---------------------------------------------------------------------------------------------
-constexpr int kWsRounds = 11;                    // DMA rounds of 32 patch pixels (4 waves x 8 pixels)
-constexpr int kWsPatchMax = kWsRounds * 32;      // 352 patch pixels per buffer (18 x 18 for a 16 x 16 tile, 6 x 58 for 4 x 56)
+// (kWsRounds, kWsPatchMax and the tile geometry ws_tile_geometry: tsm_conv_rules.h)
 constexpr int kWsPlane = kWsPatchMax * 32;      // one k16 group of every patch pixel
 constexpr int kWsBufBytes = 4 * kWsPlane;        // 45 056 B
 constexpr int kWsLdsBytes = 2 * kWsBufBytes + 256;
@@ -39,27 +38,6 @@ constexpr int kWsLaneOff = kWsRingOff + 4 * kWsSlots * 4096;       // ... six pe
 constexpr int kWsLdsBytes3All = kWsLaneOff + 6 * 1024;             // 162 048 B
 static_assert(kWsLdsBytes3All <= 160 * 1024, "LDS budget of the fused weight-stationary kernel");
 constexpr int kWsAgprFrags1 = 20;                // fragments of the second output-channel tile kept in accumulation registers
-
-// Tile geometry for an H x W frame: TR x TC <= 256 output pixels, (TR + 2) x (TC + 2) <= kWsPatchMax patch pixels,
-// fewest tiles per frame (ties: the smaller patch).  Returns false when nothing fits.
-static bool ws_tile_geometry(int H, int W, int *tr_out, int *tc_out, int max_px = 256, int max_patch = kWsPatchMax) {
-  long best_tiles = -1;
-  int best_tr = 0, best_tc = 0, best_patch = 0;
-  for (int tc = 4; tc <= 128; ++tc) {
-    int tr = max_px / tc;
-    if (tr > H) tr = H;
-    if (tr < 1) continue;
-    const int patch = (tr + 2) * (tc + 2);
-    if (patch > max_patch) continue;
-    const long tiles = (long)((H + tr - 1) / tr) * ((W + tc - 1) / tc);
-    if (best_tiles < 0 || tiles < best_tiles || (tiles == best_tiles && patch < best_patch)) {
-      best_tiles = tiles; best_tr = tr; best_tc = tc; best_patch = patch;
-    }
-  }
-  *tr_out = best_tr;
-  *tc_out = best_tc;
-  return best_tiles > 0;
-}
 
 // Vector-memory operations of the fused kernel's conv3 phase that are younger than the ring fill R_it when tile `it`
 // waits for it.  Issue order with D = kWsSlots:  R_0 .. R_{D-1} | P (kWsRounds) | [it = 0: wait, R_D, S_0] [1: wait,
@@ -480,150 +458,15 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
 // M-tile's lanes are laid out LPR = 8 / 16 / 32 lanes per tile row with, for LPR = 8, rows r and r + 4 in the same 16-lane
 // group (rows 2 (2 TC + 1) x 4 positions apart: an odd multiple of 8, i.e. the other 16-byte half of the same banks).
 // ---------------------------------------------------------------------------------------------
-constexpr int kW8Rounds = 6;                      // DMA rounds of 32 patch pixels per plane
-constexpr int kW8PatchMax = kW8Rounds * 32;       // 192 patch pixels (10 x 18 for an 8 x 16 tile, 6 x 30 for 4 x 28)
+// (kW8Rounds, kW8PatchMax, kS2PatchMax, the tile geometries, ws128_lane_pixel / ws128_swap and the bank-conflict model: tsm_conv_rules.h)
 constexpr int kW8Plane = kW8PatchMax * 32;
 constexpr int kW8BufBytes = 8 * kW8Plane;         // 49 152 B
 constexpr int kW8LdsBytes = 2 * kW8BufBytes + 512;
 constexpr int kW8AgprFrags = 56;                  // fragments kept in accumulation registers
-constexpr int kS2PatchMax = 289;                  // 17 x 17 for an 8 x 8 tile (config 5: 32 x 32 outputs), 9 x 29 for 4 x 14 (28 x 28)
 constexpr int kS2Rounds = 10;                     // the tenth: one pixel
 constexpr int kS2Plane = kS2PatchMax * 32;        // 9 248 B
 constexpr int kS2BufBytes = 8 * kS2Plane;         // 73 984 B
 constexpr int kS2LdsBytes = 2 * kS2BufBytes + 512;
-
-// Stride 2: lanes per tile row of an M-tile pair (64 lanes), and the tile geometry for Ho x Wo outputs: TC <= LPR columns,
-// TR <= 64 / LPR rows, (2 TR + 1) x (2 TC + 1) <= kS2PatchMax patch pixels, fewest tiles per frame (ties: the smaller patch).
-static int ws_s2_lanes_per_row(int tc) { return tc <= 8 ? 8 : tc <= 16 ? 16 : tc <= 32 ? 32 : 64; }
-static bool ws_s2_tile_geometry(int Ho, int Wo, int *tr_out, int *tc_out) {
-  long best_tiles = -1;
-  int best_tr = 0, best_tc = 0, best_patch = 0;
-  for (int tc = 1; tc <= 64; ++tc) {
-    int tr = 64 / ws_s2_lanes_per_row(tc);
-    if (tr > Ho) tr = Ho;
-    if (tr < 1) continue;
-    const int patch = (2 * tr + 1) * (2 * tc + 1);
-    if (patch > kS2PatchMax) continue;
-    if (2 * tr * (2 * tc + 1) + ws_s2_lanes_per_row(tc) + tc >= kS2PatchMax) continue;   // idle lanes of a row read behind it: the largest position they form stays <= kS2PatchMax - 1, inside the plane
-    const long tiles = (long)((Ho + tr - 1) / tr) * ((Wo + tc - 1) / tc);
-    if (best_tiles < 0 || tiles < best_tiles || (tiles == best_tiles && patch < best_patch)) {
-      best_tiles = tiles; best_tr = tr; best_tc = tc; best_patch = patch;
-    }
-  }
-  *tr_out = best_tr;
-  *tc_out = best_tc;
-  return best_tiles > 0;
-}
-
-// The pixel of lane l31 of M-tile mt (q = 32 mt + l31): its row / column in the tile (row 0x4000: an idle lane) and the patch
-// position of its top-left tap.  One definition for the kernel and for the host's bank-conflict model below.
-__host__ __device__ inline void ws128_lane_pixel(bool s2, int TR, int TC, int PW, int q, int *prow, int *pcol, int *pp0) {
-  if (s2) {
-    const int lpr = TC <= 8 ? 8 : TC <= 16 ? 16 : TC <= 32 ? 32 : 64;
-    const int j = q / lpr, c = q - j * lpr;
-    const int r = lpr == 8 ? (j >> 1) + 4 * (j & 1) : j;         // LPR = 8: rows r, r + 4 share a 16-lane group
-    const bool ok = r < TR && c < TC;
-    *prow = ok ? r : 0x4000;
-    *pcol = c;
-    *pp0 = (r < TR ? 2 * r * PW : 0) + c;                          // (idle lanes read inside the plane, next to their row's pixels)
-  } else {
-    const bool ok = q < TR * TC;
-    const int r = q / TC, c = q - r * TC;
-    *prow = ok ? r : 0x4000;
-    *pcol = c;
-    *pp0 = ok ? r * PW + c : 0;
-  }
-}
-// Which 16-byte half of its 32-byte plane entry holds k 0-7 of patch position pp (row r = pp / PW, place q = pp % PW in the row):
-// half (k >> 3) ^ swap.  A ds_read_b128 is served in four groups of 16 lanes -- lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and
-// the same + 32 (MI355X_MICROARCH.md, LDS) -- one LDS cycle per group when its 16 lanes hit 16 different 16-byte slots of the
-// 256-byte bank row; slot = 2 (pp mod 8) + half ^ swap, so two positions of a group that agree mod 8 must differ in `swap`.
-// Round 2-4 swapped on bit 3 of pp, which is conflict-free for 16 CONSECUTIVE positions per group -- not what the hardware's
-// groups read: every fragment read of the config-5 tiles was 2-way conflicted (SQ_LDS_BANK_CONFLICT 65 % / 49 % of the LDS
-// cycles, profiles/r04_bf16c5_pmc_sq1.txt; the model below says 50 %), at one read per MFMA exactly the matrix pipe's time.
-// mode 0: bit 3 of pp; 1: bit 1 of q; 2: bit 0 of r; 3: bit 1 of r.  The host picks the mode with the fewest conflict cycles.
-__host__ __device__ inline int ws128_swap(int mode, int pp, int PW) {
-  const int r = pp / PW, q = pp - r * PW;
-  return (mode == 1 ? (q >> 1) : mode == 2 ? r : mode == 3 ? (r >> 1) : (pp >> 3)) & 1;
-}
-// LDS cycles of the fragment reads of one tile (all M-tiles x 9 taps, one k16 plane) under swap mode `mode`; 4 per read = conflict-free.
-static int ws128_read_cycles(bool s2, int TR, int TC, int mode) {
-  static const int kGroup[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                    {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
-  const int PW = s2 ? 2 * TC + 1 : TC + 2, kMT = s2 ? 2 : 4;
-  int cycles = 0;
-  for (int mt = 0; mt < kMT; ++mt)
-    for (int tap = 0; tap < 9; ++tap) {
-      const int ky = tap / 3, kx = tap - ky * 3;
-      for (int half = 0; half < 2; ++half)
-        for (int g = 0; g < 2; ++g) {
-          int addr[16], worst = 1;
-          for (int i = 0; i < 16; ++i) {
-            int prow, pcol, pp0;
-            ws128_lane_pixel(s2, TR, TC, PW, mt * 32 + kGroup[g][i], &prow, &pcol, &pp0);
-            const int pp = pp0 + ky * PW + (s2 ? (kx == 1 ? TC + 1 : kx >> 1) : kx);
-            addr[i] = pp * 2 + (half ^ ws128_swap(mode, pp, PW));      // in 16-byte units
-          }
-          for (int i = 0; i < 16; ++i) {     // distinct addresses on the same slot (equal addresses broadcast)
-            int ways = 0;
-            for (int k = 0; k < 16; ++k) {
-              bool first = (addr[k] & 15) == (addr[i] & 15);
-              for (int m = 0; first && m < k; ++m) first = addr[m] != addr[k];
-              ways += first ? 1 : 0;
-            }
-            worst = ways > worst ? ways : worst;
-          }
-          cycles += worst;
-        }
-    }
-  return cycles;
-}
-static int ws128_best_swap(bool s2, int TR, int TC) {
-  int best = 0, best_c = ws128_read_cycles(s2, TR, TC, 0);
-  for (int mode = 1; mode < 4; ++mode) {
-    const int c = ws128_read_cycles(s2, TR, TC, mode);
-    if (c < best_c) { best = mode; best_c = c; }
-  }
-  return best;
-}
-
-// The stride-1 tile of a frame: fewest tiles first (ws_tile_geometry's rule), and among the shapes with that many tiles the one whose
-// fragment reads cost the fewest LDS cycles under its best swap -- the shapes differ by a factor of two there: on 32 x 32 frames
-// 16 x 8 and 8 x 16 both give 8 tiles, but an M-tile of four 8-pixel rows puts FOUR lanes of a 16-lane read group on one pair of
-// 16-byte slots (two entries per slot pair: 2-way conflicts whatever the swap, 50 % of the LDS cycles), while two 16-pixel rows
-// with the halves swapped on the row's parity read conflict-free.
-static bool ws128_tile_geometry(int H, int W, int *tr_out, int *tc_out, int *swz_out) {
-  // (a pure function of the frame size, but ~10^7 operations of modelling: every launch of an engine asks for the same one or
-  //  two sizes, so the calling thread remembers its last four answers)
-  struct Memo { int H, W, tr, tc, swz; bool ok; };
-  static thread_local Memo memo[4] = {};
-  static thread_local int memo_next = 0;
-  for (const Memo &m : memo)
-    if (m.H == H && m.W == W && m.H > 0) {
-      *tr_out = m.tr; *tc_out = m.tc;
-      if (swz_out) *swz_out = m.swz;
-      return m.ok;
-    }
-  long best_tiles = -1;
-  int best_tr = 0, best_tc = 0, best_cycles = 0, best_swz = 0;
-  for (int tc = 4; tc <= 128; ++tc) {
-    int tr = 128 / tc;
-    if (tr > H) tr = H;
-    if (tr < 1 || (tr + 2) * (tc + 2) > kW8PatchMax) continue;
-    const long tiles = (long)((H + tr - 1) / tr) * ((W + tc - 1) / tc);
-    if (best_tiles >= 0 && tiles > best_tiles) continue;
-    const int swz = ws128_best_swap(false, tr, tc), cycles = ws128_read_cycles(false, tr, tc, swz);
-    if (best_tiles < 0 || tiles < best_tiles || cycles < best_cycles) {
-      best_tiles = tiles; best_tr = tr; best_tc = tc; best_cycles = cycles; best_swz = swz;
-    }
-  }
-  *tr_out = best_tr;
-  *tc_out = best_tc;
-  if (swz_out) *swz_out = best_swz;
-  memo[memo_next] = Memo{H, W, best_tr, best_tc, best_swz, best_tiles > 0};
-  memo_next = (memo_next + 1) & 3;
-  return best_tiles > 0;
-}
 
 template <bool S2>
 __global__ void __launch_bounds__(256, 1) conv3x3_ws128_kernel(const WsParams p) {
@@ -872,24 +715,6 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws128_kernel(const WsParams p)
   }
 }
 
-static bool conv3x3_ws128_common(const ConvParams &p) {
-  return p.prec == kPrecBf16 && p.C == 128 && p.Cout == 128 && p.Kp == 1152 && p.pad == 1 && !p.res && !p.x2 && p.T == 0 &&
-         p.kseg_len == 0 && (double)p.M * 256.0 < 2.0e9 && (double)p.Hi * p.Wi * 256.0 < 2.0e9;
-}
-
-// stride 2 (layer2.0's conv2)
-static bool conv3x3_ws128s2_valid(const ConvParams &p) {
-  int tr, tc;
-  return conv3x3_ws128_common(p) && p.stride == 2 && p.Ho == (p.Hi - 1) / 2 + 1 && p.Wo == (p.Wi - 1) / 2 + 1 && p.Wi <= 2048 &&
-         ws_s2_tile_geometry(p.Ho, p.Wo, &tr, &tc);
-}
-
-bool conv3x3_ws128_valid(const ConvParams &p) {
-  int tr, tc;
-  if (conv3x3_ws128s2_valid(p)) return true;
-  return conv3x3_ws128_common(p) && p.stride == 1 && p.Hi == p.Ho && p.Wi == p.Wo && ws128_tile_geometry(p.Hi, p.Wi, &tr, &tc, nullptr);
-}
-
 // ---------------------------------------------------------------------------------------------
 // conv1x1_ws: Bottleneck.conv1 of layer1 in bf16 (1x1, CIN = 64 or 256 -> 64 channels, the temporal shift fused into
 // the loader).  These launches are pure HBM streams (2.7 GB in 0.58 ms with conv_igemm's register-staged K loop, which
@@ -1023,13 +848,6 @@ __global__ void __launch_bounds__(256, 1) conv1x1_ws_kernel(const Ws1Params p) {
     }
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // the next tile is older than this tile's four stores
   }
-}
-
-bool conv1x1_ws_valid(const ConvParams &p) {
-  return p.prec == kPrecBf16 && (p.C == 64 || p.C == 256) && p.Cout == 64 && p.Kp == p.C && p.stride == 1 && p.pad == 0 &&
-         p.Hi == p.Ho && p.Wi == p.Wo && !p.res && !p.x2 && p.kseg_len == 0 && (double)p.M * 128.0 < 2.0e9 &&
-         (p.T == 0 || (p.N % p.T == 0 && p.fold % 8 == 0 && 2 * p.fold <= p.C)) &&
-         (double)(128 + 2.0 * p.Hi * p.Wi) * p.C * 2.0 < 2.0e9;
 }
 
 // conv1x1_wsn: the same streaming form for 128 / 256 output channels (conv1 of layer2 and of layer3.0, conv3 + downsample of
@@ -1222,131 +1040,60 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
   }
 }
 
-bool conv1x1_wsn_valid(const ConvParams &p) {
-  if (p.prec != kPrecBf16 || p.stride != 1 || p.pad != 0 || p.Hi != p.Ho || p.Wi != p.Wo || p.res || p.kseg_len != 0) return false;
-  if ((double)(128 + 2.0 * p.Hi * p.Wi) * p.C * 2.0 >= 2.0e9) return false;
-  if (p.x2) {   // conv3 + downsample of layer1.0: 64 + 64 -> 256; of layer2.0: 128 + 256 -> 512 (two halves of 256)
-    const bool l1 = p.C == 64 && p.C2 == 64 && p.K1 == 64 && p.Kp == 128 && p.Cout == 256;
-    const bool l2 = p.C == 128 && p.C2 == 256 && p.K1 == 128 && p.Kp == 384 && p.Cout == 512 && device_info().n_cu >= 16;
-    return p.T == 0 && (l1 || l2) && (double)(128.0 / (p.Hi * p.Wi) + 2.0) * p.Hi2 * p.Wi2 * p.C2 * 2.0 < 2.0e9;
-  }
-  if (p.Kp != p.C) return false;
-  if (p.T > 0 && (p.N % p.T != 0 || p.fold % 8 != 0 || 2 * p.fold > p.C)) return false;
-  return (p.C == 256 && p.Cout == 128) || (p.C == 512 && p.Cout == 128) || (p.C == 512 && p.Cout == 256);
-}
-
-bool conv3x3_ws_valid(const ConvParams &p) {
-  int tr, tc;
-  return p.prec == kPrecBf16 && p.C == 64 && p.Cout == 64 && p.Kp == 576 && p.stride == 1 && p.pad == 1 && p.Hi == p.Ho &&
-         p.Wi == p.Wo && !p.res && !p.x2 && p.T == 0 && p.kseg_len == 0 && (double)p.M * 128.0 < 2.0e9 &&
-         ws_tile_geometry(p.Hi, p.Wi, &tr, &tc);
-}
-
-
-static int ws_grid_setup() { return device_info().n_cu; }
-
-hipError_t launch_conv3x3_ws(ConvParams p, hipStream_t s) {
-  if (conv3x3_ws128s2_valid(p)) {
-    WsParams q{};
-    q.x = p.x; q.w2 = p.w; q.bias2 = p.bias; q.y = p.y;
-    q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.M = p.M; q.relu = p.relu; q.reverse = p.reverse;
-    ws_s2_tile_geometry(p.Ho, p.Wo, &q.tr, &q.tc);
-    {
-      static thread_local int m_tr = 0, m_tc = 0, m_swz = 0;       // (the same modelling cost: remembered per thread)
-      if (m_tr != q.tr || m_tc != q.tc) { m_swz = ws128_best_swap(true, q.tr, q.tc); m_tr = q.tr; m_tc = q.tc; }
-      q.swz = m_swz;
-    }
-    const long ntiles = (long)q.N * ((p.Ho + q.tr - 1) / q.tr) * ((p.Wo + q.tc - 1) / q.tc);
-    const int n_cu = ws_grid_setup();
-    if (device_info().status != hipSuccess) return device_info().status;
-    TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kS2LdsBytes, s, q);
-    return hipGetLastError();
-  }
-  if (conv3x3_ws128_valid(p)) {
-    WsParams q{};
-    q.x = p.x; q.w2 = p.w; q.bias2 = p.bias; q.y = p.y;
-    q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.M = p.M; q.relu = p.relu; q.reverse = p.reverse;
-    ws128_tile_geometry(q.H, q.W, &q.tr, &q.tc, &q.swz);
-    const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
-    const int n_cu = ws_grid_setup();
-    if (device_info().status != hipSuccess) return device_info().status;
-    TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kW8LdsBytes, s, q);
-    return hipGetLastError();
-  }
-  if (!conv3x3_ws_valid(p)) return hipErrorInvalidValue;
+// Launch.  Which kernel applies, its tile geometry and its grid are the route's (tsm_conv_rules.h); launch_conv has checked
+// device_info().status.
+static WsParams ws_params(const void *x, const void *w2, const float *bias2, void *y, int n, int h, int w, int m, int relu, int reverse,
+                          int tr, int tc, int swz) {
   WsParams q{};
-  q.x = p.x; q.w2 = p.w; q.bias2 = p.bias; q.y = p.y;
-  q.N = p.N; q.H = p.Hi; q.W = p.Wi; q.M = p.M; q.relu = p.relu; q.reverse = p.reverse;
-  ws_tile_geometry(q.H, q.W, &q.tr, &q.tc);
-  const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
-  const int n_cu = ws_grid_setup();
-  if (device_info().status != hipSuccess) return device_info().status;
-  TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<false>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes, s, q);
-  return hipGetLastError();
+  q.x = x; q.w2 = w2; q.bias2 = bias2; q.y = y;
+  q.N = n; q.H = h; q.W = w; q.M = m; q.relu = relu; q.reverse = reverse;
+  q.tr = tr; q.tc = tc; q.swz = swz;
+  return q;
 }
 
-hipError_t launch_conv1x1_ws(const ConvParams &p, hipStream_t s) {
-  if (!conv1x1_ws_valid(p)) return hipErrorInvalidValue;
-  Ws1Params q{};
-  q.x = p.x; q.w = p.w; q.bias = p.bias; q.y = p.y;
-  q.M = p.M; q.HW = p.Hi * p.Wi; q.T = p.T; q.fold = p.fold; q.relu = p.relu; q.reverse = p.reverse;
-  const int n_cu = ws_grid_setup();
-  if (device_info().status != hipSuccess) return device_info().status;
-  const int ntiles = (p.M + 127) / 128;
-  const unsigned grid = (unsigned)(ntiles < n_cu ? ntiles : n_cu);
-  if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<256>, dim3(grid), dim3(256), 2 * 16 * 4096 + 256, s, q);
-  else TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<64>, dim3(grid), dim3(256), 2 * 4 * 4096 + 256, s, q);
-  return hipGetLastError();
-}
-
-hipError_t launch_conv1x1_wsn(const ConvParams &p, hipStream_t s) {
-  if (!conv1x1_wsn_valid(p)) return hipErrorInvalidValue;
-  WsnParams q{};
-  q.x = p.x; q.x2 = p.x2; q.w = p.w; q.bias = p.bias; q.y = p.y;
-  q.M = p.M; q.HW = p.Hi * p.Wi; q.Wo = p.Wo; q.T = p.T; q.fold = p.fold; q.relu = p.relu; q.reverse = p.reverse;
-  q.K1 = p.x2 ? p.K1 : p.C; q.Hi2 = p.Hi2; q.Wi2 = p.Wi2; q.stride2 = p.stride2;
-  const int n_cu = ws_grid_setup();
-  if (device_info().status != hipSuccess) return device_info().status;
-  const int px = p.Kp <= 256 ? 128 : 64;
-  const int ntiles = (p.M + px - 1) / px;
-  const dim3 grid((unsigned)(ntiles < n_cu ? ntiles : n_cu)), block(256);
-  constexpr size_t kLds = 2 * 65536 + 1024;
-  if (p.x2 && p.Kp == 384) {
-    const int pairs = n_cu >> 4 << 3;                                     // workgroup pairs: a multiple of 8 (b and b + 8 share an XCD)
-    const int np = ntiles < pairs ? (ntiles + 7) / 8 * 8 : pairs;         // (a pair without a tile leaves at once)
-    TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<384, 256, true, 2>), dim3((unsigned)(2 * np)), block, 2 * 24 * 2048 + 1024, s, q);
-  } else if (p.x2) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<128, 256, true>), grid, block, kLds, s, q);
-  else if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<256, 128, false>), grid, block, kLds, s, q);
-  else if (p.Cout == 128) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 128, false>), grid, block, kLds, s, q);
-  else TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 256, false>), grid, block, kLds, s, q);
+hipError_t launch_conv_ws(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
+  const dim3 grid(r.grid), block(256);
+  if (r.family <= kFamWs128s2) {   // the 3x3 kernels
+    const WsParams q = ws_params(p.x, p.w, p.bias, p.y, p.N, p.Hi, p.Wi, p.M, p.relu, p.reverse, r.tr, r.tc, r.swz);
+    if (r.family == kFamWs128s2) TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<true>, grid, block, kS2LdsBytes, s, q);
+    else if (r.family == kFamWs128) TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws128_kernel<false>, grid, block, kW8LdsBytes, s, q);
+    else TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<false>, grid, block, kWsLdsBytes, s, q);
+  } else if (r.family == kFamWs1x1) {
+    Ws1Params q{};
+    q.x = p.x; q.w = p.w; q.bias = p.bias; q.y = p.y;
+    q.M = p.M; q.HW = p.Hi * p.Wi; q.T = p.T; q.fold = p.fold; q.relu = p.relu; q.reverse = p.reverse;
+    if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<256>, grid, block, 2 * 16 * 4096 + 256, s, q);
+    else TSM_KLAUNCH_WALK(q.reverse, conv1x1_ws_kernel<64>, grid, block, 2 * 4 * 4096 + 256, s, q);
+  } else {
+    WsnParams q{};
+    q.x = p.x; q.x2 = p.x2; q.w = p.w; q.bias = p.bias; q.y = p.y;
+    q.M = p.M; q.HW = p.Hi * p.Wi; q.Wo = p.Wo; q.T = p.T; q.fold = p.fold; q.relu = p.relu; q.reverse = p.reverse;
+    q.K1 = p.x2 ? p.K1 : p.C; q.Hi2 = p.Hi2; q.Wi2 = p.Wi2; q.stride2 = p.stride2;
+    constexpr size_t kLds = 2 * 65536 + 1024;
+    if (p.x2 && p.Kp == 384) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<384, 256, true, 2>), grid, block, 2 * 24 * 2048 + 1024, s, q);
+    else if (p.x2) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<128, 256, true>), grid, block, kLds, s, q);
+    else if (p.C == 256) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<256, 128, false>), grid, block, kLds, s, q);
+    else if (p.Cout == 128) TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 128, false>), grid, block, kLds, s, q);
+    else TSM_KLAUNCH_WALK(q.reverse, (conv1x1_wsn_kernel<512, 256, false>), grid, block, kLds, s, q);
+  }
   return hipGetLastError();
 }
 
 // Fused23Params with bf16 operands: w3f = conv3's packed weights [256][64] bf16 (row-major, as launch_conv takes them).
-bool conv23_ws_valid(int n, int h, int w) {
-  int tr, tc;
-  return n > 0 && h > 0 && w > 0 && (double)h * w * 512.0 < 2.0e9 && (double)n * h * w < 2.0e9 && ws_tile_geometry(h, w, &tr, &tc);
-}
-
 hipError_t launch_conv23_ws(const Fused23Params &p, hipStream_t s) {
-  if (!conv23_ws_valid(p.N, p.H, p.W) || p.kseg_len != 0) return hipErrorInvalidValue;
-  WsParams q{};
-  q.x = p.x; q.w2 = p.w2; q.bias2 = p.bias2; q.w3 = p.w3f; q.bias3 = p.bias3; q.res = p.res; q.y = p.y;
-  q.N = p.N; q.H = p.H; q.W = p.W; q.M = p.M; q.relu = 1; q.reverse = p.reverse;
-  ws_tile_geometry(q.H, q.W, &q.tr, &q.tc);
-  const long ntiles = (long)q.N * ((q.H + q.tr - 1) / q.tr) * ((q.W + q.tc - 1) / q.tc);
-  const int n_cu = ws_grid_setup();
-  if (device_info().status != hipSuccess) return device_info().status;
-  TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<true>, dim3((unsigned)(ntiles < n_cu ? ntiles : n_cu)), dim3(256), kWsLdsBytes3All, s, q);
+  int tr, tc;
+  if (!conv23_ws_valid(p.N, p.H, p.W, &tr, &tc) || p.kseg_len != 0) return hipErrorInvalidValue;
+  WsParams q = ws_params(p.x, p.w2, p.bias2, p.y, p.N, p.H, p.W, p.M, 1, p.reverse, tr, tc, 0);
+  q.w3 = p.w3f; q.bias3 = p.bias3; q.res = p.res;
+  const DeviceInfo &di = device_info();
+  if (di.status != hipSuccess) return di.status;
+  const dim3 grid(persistent_grid(ws_frame_tiles(q.N, q.H, q.W, tr, tc), di.n_cu)), block(256);
+  TSM_KLAUNCH_WALK(q.reverse, conv3x3_ws_kernel<true>, grid, block, kWsLdsBytes3All, s, q);
   return hipGetLastError();
 }
 
 hipError_t opt_in_ws() {
-  hipError_t first = hipSuccess;
-  auto opt_in = [&](const void *fn, size_t bytes) {
-    const hipError_t st = lds_opt_in(fn, bytes);
-    if (st != hipSuccess && first == hipSuccess) first = st;
-  };
+  OptIn opt_in;
   opt_in(reinterpret_cast<const void *>(&conv3x3_ws_kernel<false>), kWsLdsBytes);
   opt_in(reinterpret_cast<const void *>(&conv3x3_ws_kernel<true>), kWsLdsBytes3All);
   opt_in(reinterpret_cast<const void *>(&conv3x3_ws128_kernel<false>), kW8LdsBytes);
@@ -1357,7 +1104,7 @@ hipError_t opt_in_ws() {
   opt_in(reinterpret_cast<const void *>(&conv1x1_wsn_kernel<256, 128, false>), 2 * 65536 + 1024);
   opt_in(reinterpret_cast<const void *>(&conv1x1_wsn_kernel<512, 128, false>), 2 * 65536 + 1024);
   opt_in(reinterpret_cast<const void *>(&conv1x1_wsn_kernel<512, 256, false>), 2 * 65536 + 1024);
-  return first;
+  return opt_in.first;
 }
 
 }  // namespace tsm

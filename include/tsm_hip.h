@@ -196,10 +196,23 @@ int tsm_set_shift_place(tsm_engine *e, int32_t place);
  * written by an avg engine serves an identity engine of the same geometry. */
 int tsm_set_consensus(tsm_engine *e, int32_t consensus);
 
+/* Non-local blocks -- create_model(non_local=True), the TSM code base's make_non_local: on = 1 wraps blocks 0 and 2 of layer2
+ * and blocks 0, 2 and 4 of layer3 in an embedded-Gaussian non-local block.  With x [B*T, C, H, W] the wrapped block's (post-ReLU)
+ * output and d = C / 2: theta = conv1x1x1(x), phi = g = conv1x1x1(x) followed by MaxPool3d((1, 2, 2)) (floor mode), the
+ * T*H*W x T*(H/2)*(W/2) scores f = theta^T phi without a scale factor, y = softmax_j(f) g, z = BN(conv1x1x1(y)) + x without a
+ * ReLU; z is the wrapped block's output.  The scores are never materialised (nonlocal_attn_kernel: online softmax).
+ * State-dict keys of a wrapped block: its own tensors under "base_model.layerL.B.block.<name>" (the spelling without ".block"
+ * is accepted too), and "base_model.layerL.B.nl.{theta, phi.0, g.0}.{weight [d, C, 1, 1, 1], bias}", "...nl.W.0.{weight
+ * [C, d, 1, 1, 1], bias}", "...nl.W.1.{weight, bias, running_mean, running_var}".  Taps: "layerL.B" is z, "layerL.B.block" the
+ * block's own output, "layerL.B.nl.y" is y.
+ * Same contract as tsm_set_shift_place: legal between tsm_create and the first tsm_set_tensor, later TSM_ERR_INVALID_ARG.
+ * TSM_ERR_UNSUPPORTED, whichever call comes second: a dtype other than TSM_DTYPE_F32, a BasicBlock backbone (depth 18 / 34). */
+int tsm_set_non_local(tsm_engine *e, int32_t on);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;
- * the caller keeps ownership.  Unknown names return TSM_ERR_INVALID_ARG. */
+ * the caller keeps ownership.  Unknown names return TSM_ERR_INVALID_ARG.  ndim <= 5 (the non-local block's conv3d weights). */
 int tsm_set_tensor(tsm_engine *e, const char *name, const float *host_data, const int64_t *shape,
                    int32_t ndim);
 /* Fold BatchNorm into the convs, pack to K-major NHWC tiles, upload, allocate the workspace. */
@@ -488,6 +501,23 @@ int tsm_pool_features(const float *feat, float *pooled, float *unit, int32_t n_f
  * c <= 0; TSM_ERR_UNSUPPORTED: c % 8 != 0.  No upper limit on c; n_total is not limited by the launch geometry.
  * Enqueues on `stream`; no synchronisation. */
 int tsm_cosine_distances(const float *unit, int32_t n_total, int32_t c, int32_t row0, int32_t row1, float *dist, void *stream);
+
+/* The non-local block's two kernels (device pointers, fp32, NHWC; enqueue on `stream`, no synchronisation).
+ * tsm_maxpool2x2: MaxPool3d((1, 2, 2)) = a 2x2 max-pool at stride 2, floor mode, no padding, of channels [c0, c0 + c) of
+ *   x [n, hi, wi, ld] (ld = the row stride in floats) into the DENSE y [n, hi / 2, wi / 2, c]; a last odd row / column is
+ *   dropped.  TSM_ERR_INVALID_ARG: NULL pointers, hi < 2 or wi < 2, c0 / c / ld not multiples of 4, c0 + c > ld, pointers not
+ *   16-byte aligned.
+ * tsm_nonlocal_attention: y[b, i, :] = sum_j softmax_j(q[b, i, :] . k[b, j, :]) v[b, j, :] for b < n_clips, i < nq, j < nk over
+ *   d channels, no scale factor.  Row (b, i) of q starts at q + (b * nq + i) * ldq, row (b, j) of k / v at
+ *   (b * nk + j) * ldkv, row (b, i) of y at (b * nq + i) * ldy: the operands may be channel slices of wider tensors.  Online
+ *   softmax: no buffer proportional to nq * nk exists.  Every output element is summed in ONE fixed order that depends on
+ *   (i, nk) only -- not on the clip, the number of clips or the grid -- without atomics: a clip's rows equal its own
+ *   single-clip launch bit for bit.  Rows >= nq and keys >= nk are neither read nor written.
+ *   TSM_ERR_UNSUPPORTED (nothing launched): d other than 256 or 512.  TSM_ERR_INVALID_ARG: NULL pointers, non-positive sizes,
+ *   a row stride below d, ldq or ldkv not a multiple of 4, q / k / v not 16-byte aligned, n_clips > 65535, nk > 2^31 - 65. */
+int tsm_maxpool2x2(const float *x, int64_t ld, int32_t c0, int32_t c, float *y, int32_t n, int32_t hi, int32_t wi, void *stream);
+int tsm_nonlocal_attention(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *y, int64_t ldy,
+                           int32_t n_clips, int32_t nq, int32_t nk, int32_t d, void *stream);
 
 /* Scores -> states on the GPU (device pointers), the post-step of the hot path:
  *   logits [n_clips, num_class] fp32 -> states [n_clips] int32: (softmax != 0: fp32 softmax over the classes,) the FIRST

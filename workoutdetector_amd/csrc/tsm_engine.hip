@@ -67,6 +67,10 @@ struct HostTensor {
 struct ConvLayer : LayerGeom {   // cp, kp, kseg: tsm_host_util.h, layer_geometry
   std::string wkey, bnp;
   int cin = 0, cout = 0, k = 1, stride = 1;
+  // non-local block convs, both with a conv bias: 1 = theta | phi | g as one 1x1 conv (wkey = "<nlp>.theta.weight", no BatchNorm),
+  // 2 = W ("<nlp>.W.0.weight", BatchNorm "<nlp>.W.1"); nlp = "base_model.layerL.B.nl"
+  int nl = 0;
+  std::string nlp;
   float *d_w = nullptr, *d_b = nullptr;
 };
 
@@ -85,6 +89,10 @@ struct Block {
   float *d_w3f = nullptr;
   int cmid = 0;
   int cout3 = 0;   // conv3's output channels where cmid is set: 4 * cmid, or 2 * cmid (conv23_fused2_kernel)
+  // a non-local engine's wrapped blocks: the theta | phi | g conv and the W conv behind the block (-1: not wrapped), and the
+  // tap name of the block's OWN output ("layerL.B.block" when wrapped: "layerL.B" is then the wrapper's)
+  int nl_qkv = -1, nl_w = -1;
+  std::string out_name;
 };
 
 // A device buffer between two poisoned bands (tsm_host_util.h: guard_layout).  tsm_conv_op's temporaries always are; the
@@ -135,6 +143,7 @@ struct tsm_engine {
   int depth = 50;             // tsm_set_backbone
   int width = 64;             // tsm_set_bottleneck_width: torchvision's width_per_group
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
+  int non_local = 0;          // tsm_set_non_local: non-local blocks around layer2.{0,2} and layer3.{0,2,4} (fp32 Bottleneck engines)
   int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
   int features = 0;           // for the duration of a tsm_forward_features call: 1 = the forward ends in the pooled rows, 2 = in the unit rows
@@ -231,7 +240,10 @@ void build_topology(tsm_engine *e) {
       const int stride = (b == 0 && li > 0) ? 2 : 1;
       // block placement wraps the whole block in TemporalShift: its tensors are "layerL.B.net.<name>", conv1 unwrapped
       const bool bp = e->place == 1;
-      const std::string p = "base_model.layer" + std::to_string(li + 1) + "." + std::to_string(b) + (bp ? ".net" : "");
+      // a non-local engine wraps some blocks once more: their own tensors move under "layerL.B.block", the new ones are "layerL.B.nl.*"
+      const bool nl = e->non_local && !bb.basic && nonlocal_wrapped(li + 1, b);
+      const std::string lb = "base_model.layer" + std::to_string(li + 1) + "." + std::to_string(b);
+      const std::string p = lb + (nl ? ".block" : "") + (bp ? ".net" : "");
       const std::string c1key = p + (bp ? ".conv1.weight" : ".conv1.net.weight");
       Block blk;
       blk.stride = stride;
@@ -249,6 +261,14 @@ void build_topology(tsm_engine *e) {
       }
       const bool down = bb.basic ? (stride != 1 || cin != planes) : b == 0;
       blk.down = down ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false) : -1;
+      blk.out_name = blk.name + (nl ? ".block" : "");
+      if (nl) {   // theta | phi | g: cout -> 3 * cout / 2 (bias, no BN, no ReLU); W: cout / 2 -> cout (bias + BN, + x, no ReLU)
+        blk.nl_qkv = add_conv(e, lb + ".nl.theta.weight", "", cout, 3 * (cout / 2), 1, 1, false);
+        blk.nl_w = add_conv(e, lb + ".nl.W.0.weight", lb + ".nl.W.1", cout / 2, cout, 1, 1, false);
+        e->convs[blk.nl_qkv].nl = 1;
+        e->convs[blk.nl_w].nl = 2;
+        e->convs[blk.nl_qkv].nlp = e->convs[blk.nl_w].nlp = lb + ".nl";
+      }
       e->blocks.push_back(blk);
       cin = cout;
     }
@@ -258,6 +278,12 @@ void build_topology(tsm_engine *e) {
 
 // The un-wrapped spelling of an engine key, also accepted: TemporalShift wraps conv1 as ".conv1.net.weight" (blockres) or the
 // whole block as "layerL.B.net.<name>" (block placement); "" when the key has no wrapper.
+// The spelling of an engine key without the non-local wrapper's ".block" ("" when it has none).
+std::string without_block(const std::string &key) {
+  const size_t at = key.find(".block.");
+  return at == std::string::npos ? "" : key.substr(0, at) + key.substr(at + 6);
+}
+
 std::string unwrapped(const tsm_engine *e, const std::string &key) {
   if (e->place == 1) {
     const size_t at = key.find(".net.");
@@ -272,8 +298,10 @@ std::string unwrapped(const tsm_engine *e, const std::string &key) {
 const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
   auto it = e->tensors.find(key);
   if (it != e->tensors.end()) return &it->second;
-  const std::string alt = unwrapped(e, key);
-  if (!alt.empty()) {
+  // (every spelling: without the shift wrapper, without the non-local wrapper, without both)
+  const std::string nb = without_block(key);
+  for (const std::string &alt : {unwrapped(e, key), nb, nb.empty() ? nb : unwrapped(e, nb)}) {
+    if (alt.empty()) continue;
     it = e->tensors.find(alt);
     if (it != e->tensors.end()) return &it->second;
   }
@@ -283,8 +311,17 @@ const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
 bool known_name(const tsm_engine *e, const std::string &name) {
   if (name == "fc.weight" || name == "fc.bias") return true;
   static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
-  auto is = [&](const std::string &key) { return name == key || name == unwrapped(e, key); };
+  auto is = [&](const std::string &key) {
+    const std::string nb = without_block(key);
+    return name == key || name == unwrapped(e, key) || (!nb.empty() && (name == nb || name == unwrapped(e, nb)));
+  };
   for (const ConvLayer &c : e->convs) {
+    if (c.nl == 1) {
+      for (const char *s : {".theta.weight", ".theta.bias", ".phi.0.weight", ".phi.0.bias", ".g.0.weight", ".g.0.bias"})
+        if (name == c.nlp + s) return true;
+      continue;
+    }
+    if (c.nl == 2 && name == c.nlp + ".W.0.bias") return true;
     if (is(c.wkey)) return true;
     for (const char *s : bn_suffix)
       if (is(c.bnp + s)) return true;
@@ -687,6 +724,7 @@ struct Forward {
   int conv(int idx, tsm::ConvParams p, int ks, bool is3x3);
   int run_basic(size_t k, int nn, float *x, float *y, int hh, int ww);
   int run_block(size_t k, const BlockPlan &plan, int nn, float *x, float *y, int hh, int ww);
+  int run_nonlocal(size_t k, int nn, float *x, float *z, int hh, int ww);
   int tune_block(size_t k, int nn, float *x, float *y, int hh, int ww);
 };
 
@@ -782,7 +820,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
     L.pb.reverse = next_dir();
     TSM_LAUNCH(e, s, tsm::launch_bneck_ws(L.pb, s));
     skip_slots(e, 2);   // conv2, conv3
-    return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+    return want(blk.out_name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
   }
   if (plan.front) {
     L.pfr.reverse = next_dir();
@@ -801,7 +839,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
       L.pf.reverse = next_dir();
       TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(L.pf, blk.cmid, blk.cout3, prec, s));
       skip_slots(e, 1);   // conv3
-      return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+      return want(blk.out_name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
     }
     int rc2 = conv(blk.conv2, L.p2, 3, true);
     if (rc2) return rc2;
@@ -814,7 +852,31 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
     int rc3 = conv(blk.conv3, L.p3, 1, false);
     if (rc3) return rc3;
   }
-  return want(name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+  return want(blk.out_name) ? hit(y, nn, ho, wo, c3out) : TSM_OK;
+}
+
+// The non-local block behind wrapped Bottleneck k (steady forward and tuning pass alike: its two convs go through conv(), the
+// pool and the attention have one form each): x = the block's output [nn, hh, ww, C], z = BN(W y + b) + x.  Four launches, four
+// timing slots:
+//   theta | phi | g as ONE 1x1 conv C -> 3 d into t1 (d = C / 2);
+//   the 2x2 max-pool of the phi | g channels [d, 3 d) of t1 into t2, dense [nn, hh / 2, ww / 2, 2 d];
+//   the attention per clip, theta read in place (ldq = 3 d), phi = t2's channels [0, d), g = [d, 2 d), y [nn * hh * ww, d] into idb;
+//   W as a 1x1 conv d -> C with the residual x.
+// t1, t2 and idb are free here: the branch temporaries are dead behind the block, and only BasicBlocks use idb.
+int Forward::run_nonlocal(size_t k, int nn, float *x, float *z, int hh, int ww) {
+  const Block &blk = e->blocks[k];
+  const ConvLayer &cq = e->convs[blk.nl_qkv], &cw = e->convs[blk.nl_w];
+  const int d = cw.cin;
+  const int64_t nq = nonlocal_positions(T, hh, ww), nkeys = nonlocal_keys(T, hh, ww);
+  if (nq <= 0 || nkeys <= 0) return fail(e, TSM_ERR_UNSUPPORTED, blk.name + ": a non-local block needs at least 2 x 2 pixels");
+  int rc = conv(blk.nl_qkv, make_params(cq, x, nullptr, t1, nn, hh, ww, false, 0, 1, prec), 1, false);
+  if (rc) return rc;
+  TSM_LAUNCH(e, s, tsm::launch_maxpool2x2(t1, 3 * d, d, 2 * d, t2, nn, hh, ww, s));
+  TSM_LAUNCH(e, s, tsm::launch_nonlocal_attention(t1, 3 * d, t2, t2 + d, 2 * d, idb, d, nn / T, (int)nq, (int)nkeys, d, s));
+  if (want(blk.name + ".nl.y")) return hit(idb, nn, hh, ww, d);
+  rc = conv(blk.nl_w, make_params(cw, idb, x, z, nn, hh, ww, false, 0, 1, prec), 1, false);
+  if (rc) return rc;
+  return want(blk.name) ? hit(z, nn, hh, ww, cw.cout) : TSM_OK;
 }
 
 // One Bottleneck of the tuning pass: the candidate codes of conv1, conv2 and conv3 (conv()), and each fused form that can run
@@ -949,6 +1011,11 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     std::swap(cur, out);
     h = conv_out_size(h, 3, e->blocks[k].stride);
     w = conv_out_size(w, 3, e->blocks[k].stride);
+    if (e->blocks[k].nl_qkv >= 0) {   // the wrapper: the block's output (now cur) -> z in the block's dead input buffer
+      const int rcn = f.run_nonlocal(k, n, cur, out, h, w);
+      if (rcn || f.tapped) return rcn;
+      std::swap(cur, out);
+    }
   }
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
   if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
@@ -1004,6 +1071,7 @@ void retag_tune_sig(tsm_engine *e) {
   if (e->depth != 50) e->tune_sig += " r" + std::to_string(e->depth);
   if (e->width != 64) e->tune_sig += " w" + std::to_string(e->width);
   if (e->place == 1) e->tune_sig += " block";
+  if (e->non_local) e->tune_sig += " nl";
 }
 
 int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout, int n_clips) {
@@ -1219,6 +1287,8 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
   if (find_backbone(depth)->basic && e->width != 64)
     return fail(e, TSM_ERR_UNSUPPORTED, "a BasicBlock backbone (depth 18 / 34) has no bottleneck width: the engine's is " +
                                             std::to_string(e->width));
+  if (find_backbone(depth)->basic && e->non_local)
+    return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks need a Bottleneck backbone (depth 50)");
   e->depth = depth;
   build_topology(e);
   retag_tune_sig(e);
@@ -1242,6 +1312,19 @@ int tsm_set_shift_place(tsm_engine *e, int32_t place) {
   if (int rc = check_before_weights(e, "tsm_set_shift_place")) return rc;
   if (place != 0 && place != 1) return fail(e, TSM_ERR_UNSUPPORTED, "place must be 0 (blockres) or 1 (block)");
   e->place = place;
+  build_topology(e);
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_non_local(tsm_engine *e, int32_t on) {
+  if (int rc = check_before_weights(e, "tsm_set_non_local")) return rc;
+  if (on != 0 && on != 1) return fail(e, TSM_ERR_UNSUPPORTED, "non_local must be 0 or 1");
+  if (on && e->prec != tsm::kPrecF32)
+    return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks run in TSM_DTYPE_F32 only (the bf16 formats' fused forms do not know the block)");
+  if (on && find_backbone(e->depth)->basic)
+    return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks need a Bottleneck backbone (depth 50)");
+  e->non_local = on;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1272,7 +1355,7 @@ void tsm_destroy(tsm_engine *e) {
 int tsm_set_tensor(tsm_engine *e, const char *name, const float *host_data, const int64_t *shape,
                    int32_t ndim) {
   if (!e) return TSM_ERR_INVALID_ARG;
-  if (!name || !host_data || !shape || ndim < 1 || ndim > 4) return fail(e, TSM_ERR_INVALID_ARG, "bad tensor args");
+  if (!name || !host_data || !shape || ndim < 1 || ndim > 5) return fail(e, TSM_ERR_INVALID_ARG, "bad tensor args");   // (5: the non-local block's conv3d weights)
   if (e->finalized) return fail(e, TSM_ERR_INVALID_ARG, "engine already finalized");
   const std::string key(name);
   e->weights_started = true;
@@ -1298,6 +1381,32 @@ int tsm_finalize(tsm_engine *e) {
   std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
   for (size_t ci = 0; ci < e->convs.size(); ++ci) {
     ConvLayer &c = e->convs[ci];
+    if (c.nl) {   // the non-local block's convs: [cout, cin, 1, 1, 1] weights with a bias; theta | phi | g concatenated along cout
+      const int parts = c.nl == 1 ? 3 : 1, pc = c.cout / parts;
+      static const char *const kQkv[3] = {".theta", ".phi.0", ".g.0"};
+      std::vector<float> wp((size_t)c.cout * c.kp, 0.f), bias(c.cout);
+      const HostTensor *bn[4] = {nullptr, nullptr, nullptr, nullptr};
+      if (c.nl == 2) {
+        static const char *const kBn[4] = {".weight", ".bias", ".running_mean", ".running_var"};
+        for (int i = 0; i < 4; ++i) {
+          bn[i] = find_tensor(e, c.bnp + kBn[i]);
+          if (!bn[i]) return fail(e, TSM_ERR_MISSING_TENSOR, "missing BatchNorm tensors of " + c.bnp);
+          if (bn[i]->shape != std::vector<int64_t>{c.cout}) return fail(e, TSM_ERR_SHAPE, "BN shape mismatch for " + c.bnp);
+        }
+      }
+      for (int part = 0; part < parts; ++part) {
+        const std::string base = c.nlp + (c.nl == 1 ? kQkv[part] : ".W.0");
+        const HostTensor *w = find_tensor(e, base + ".weight"), *b = find_tensor(e, base + ".bias");
+        if (!w || !b) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + base + (w ? ".bias" : ".weight"));
+        if (w->shape != std::vector<int64_t>{pc, c.cin, 1, 1, 1}) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + base + ".weight");
+        if (b->shape != std::vector<int64_t>{pc}) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + base + ".bias");
+        fold_and_pack_bias(w->data.data(), b->data.data(), bn[0] ? bn[0]->data.data() : nullptr, bn[0] ? bn[1]->data.data() : nullptr,
+                           bn[0] ? bn[2]->data.data() : nullptr, bn[0] ? bn[3]->data.data() : nullptr, pc, c.cin, c.kp, part * pc,
+                           &wp, &bias);
+      }
+      if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
+      continue;
+    }
     const HostTensor *w = find_tensor(e, c.wkey);
     const HostTensor *g = find_tensor(e, c.bnp + ".weight"), *b = find_tensor(e, c.bnp + ".bias");
     const HostTensor *m = find_tensor(e, c.bnp + ".running_mean"), *v = find_tensor(e, c.bnp + ".running_var");
@@ -1375,6 +1484,8 @@ int tsm_finalize(tsm_engine *e) {
         const bool at_input = blk.conv3 >= 0 && ci == blk.conv1;
         per_frame = std::max(per_frame, (at_input ? in_px : out_px) * (size_t)e->convs[ci].cout);
       }
+      // (a non-local engine only: theta | phi | g of a wrapped block, 3 d channels at the block's output size)
+      if (blk.nl_qkv >= 0) per_frame = std::max(per_frame, out_px * (size_t)e->convs[blk.nl_qkv].cout);
     }
   }
   e->buf_elems = frames * per_frame;
@@ -1559,9 +1670,10 @@ int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t c
     }
   }
   // launch order: stem, then per block [downsample,] conv1, conv2, conv3 (Bottleneck) / [downsample,] conv1, conv2 (BasicBlock)
+  // [, the wrapper's theta | phi | g and W convs]
   std::vector<int> order{0};
   for (const Block &b : e->blocks)
-    for (int ci : {b.down, b.conv1, b.conv2, b.conv3})
+    for (int ci : {b.down, b.conv1, b.conv2, b.conv3, b.nl_qkv, b.nl_w})
       if (ci >= 0) order.push_back(ci);
   *n_out = (int32_t)order.size();
   if ((int)order.size() > cap) return fail(e, TSM_ERR_CAPACITY, "tiles_out too small");
@@ -1687,6 +1799,23 @@ int tsm_conv_bn_act(const float *x, const float *w, const float *gamma, const fl
 int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi, int32_t c, void *stream) {
   if (!x || !y || n <= 0 || hi <= 0 || wi <= 0) return TSM_ERR_INVALID_ARG;
   return op_status("maxpool", tsm::launch_maxpool3x3s2(x, y, n, hi, wi, c, tsm::kPrecF32, static_cast<hipStream_t>(stream)));
+}
+
+int tsm_maxpool2x2(const float *x, int64_t ld, int32_t c0, int32_t c, float *y, int32_t n, int32_t hi, int32_t wi, void *stream) {
+  if (!x || !y || n <= 0 || c <= 0 || c0 < 0) return fail(nullptr, TSM_ERR_INVALID_ARG, "maxpool2x2: NULL pointer or non-positive size");
+  if (hi < 2 || wi < 2) return fail(nullptr, TSM_ERR_INVALID_ARG, "maxpool2x2: needs at least 2 x 2 pixels");
+  return op_status("maxpool2x2", tsm::launch_maxpool2x2(x, ld, c0, c, y, n, hi, wi, static_cast<hipStream_t>(stream)),
+                   "c0, c and ld must be multiples of 4 with c0 + c <= ld, and the pointers 16-byte aligned");
+}
+
+int tsm_nonlocal_attention(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *y, int64_t ldy,
+                           int32_t n_clips, int32_t nq, int32_t nk, int32_t d, void *stream) {
+  if (d != 256 && d != 512) return fail(nullptr, TSM_ERR_UNSUPPORTED, "nonlocal_attention: d must be 256 or 512, got " + std::to_string(d));
+  if (!q || !k || !v || !y || n_clips <= 0 || nq <= 0 || nk <= 0)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "nonlocal_attention: NULL pointer or non-positive size");
+  return op_status("nonlocal_attention",
+                   tsm::launch_nonlocal_attention(q, ldq, k, v, ldkv, y, ldy, n_clips, nq, nk, d, static_cast<hipStream_t>(stream)),
+                   "row strides must be >= d (ldq, ldkv multiples of 4), q / k / v 16-byte aligned, n_clips <= 65535");
 }
 
 int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int32_t w, float *out,

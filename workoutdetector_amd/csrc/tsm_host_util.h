@@ -139,6 +139,42 @@ inline void concat_k_pair(const std::vector<float> &w1, const std::vector<float>
   }
 }
 
+// A 1x1 conv WITH a bias [cout][cin] -> rows [row0, row0 + cout) of the packed matrix [rows][kp] and of the bias vector (both
+// sized by the caller).  gamma == nullptr: no BatchNorm behind it -- the scale is exactly 1, weights and bias are copied
+// bit for bit (the non-local block's theta / phi / g).  Otherwise BN(conv(x) + b) = conv(x) * s + (beta + (b - mean) * s) with
+// s = gamma / sqrt(var + eps) (its W).
+inline void fold_and_pack_bias(const float *w, const float *cbias, const float *gamma, const float *beta, const float *mean,
+                               const float *var, int cout, int cin, int kp, int row0, std::vector<float> *wp,
+                               std::vector<float> *bias) {
+  for (int o = 0; o < cout; ++o) {
+    float *dst = wp->data() + (size_t)(row0 + o) * kp;
+    if (!gamma) {
+      std::memcpy(dst, w + (size_t)o * cin, (size_t)cin * sizeof(float));
+      (*bias)[row0 + o] = cbias[o];
+      continue;
+    }
+    const float scale = gamma[o] / std::sqrt(var[o] + kBnEps);
+    for (int c = 0; c < cin; ++c) dst[c] = w[(size_t)o * cin + c] * scale;
+    (*bias)[row0 + o] = beta[o] + (cbias[o] - mean[o]) * scale;
+  }
+}
+
+// ---- non-local blocks (TSM's make_non_local: NL3DWrapper around every other block of layer2 and layer3) ---------------------
+// layer and block as in the state-dict key "layer<layer>.<block>": layer2.{0, 2} and layer3.{0, 2, 4} of a [3, 4, 6, 3] backbone.
+inline bool nonlocal_wrapped(int layer, int block) { return (layer == 2 || layer == 3) && block % 2 == 0; }
+// MaxPool3d((1, 2, 2)): floor mode, no padding -- a last odd row / column is dropped; 0 when nothing is left.
+inline int pool2_size(int h) { return h > 0 ? h / 2 : 0; }
+// Positions of one clip: queries T * h * w, keys T * (h / 2) * (w / 2); -1 when the product leaves int32 (the attention
+// kernel's nq / nk are ints) or a size is not positive.
+inline int64_t nonlocal_positions(int T, int h, int w) {
+  if (T <= 0 || h <= 0 || w <= 0) return -1;
+  const int64_t lim = (int64_t)1 << 31, th = (int64_t)T * h;   // (each factor < 2^31: no product here leaves int64)
+  return th >= lim || th * w >= lim ? -1 : th * w;
+}
+inline int64_t nonlocal_keys(int T, int h, int w) { return nonlocal_positions(T, pool2_size(h), pool2_size(w)); }
+// Tiles of `tile` rows that cover n rows (the attention kernel's query tiles per clip and key tiles per query tile).
+inline int64_t tiles_over(int64_t n, int tile) { return n <= 0 || tile <= 0 ? 0 : (n + tile - 1) / tile; }
+
 // In the engine's storage format: fp32 as it is, split-bf16 in place, bf16 at half the length.
 inline void to_storage(std::vector<float> *v, int prec) {
   if (prec == kPrecBf16x3) to_split(v);

@@ -162,6 +162,14 @@ hipError_t launch_pool_features(const float *feat, float *pooled, float *unit, i
 // [n_total, n_total] and their mirror, from unit rows [n_total, c] (c % 8 == 0)
 hipError_t launch_cosine_distances(const float *unit, int n_total, int c, int row0, int row1, float *dist, hipStream_t s);
 
+// non-local block (tsm_nonlocal.hip).  maxpool2x2: 2x2 / stride 2 / floor-mode max-pool of channels [c0, c0 + c) of NHWC rows
+// `ld` floats apart into the dense [n, hi / 2, wi / 2, c] tensor y (c0, c, ld multiples of 4; hi, wi >= 2).
+hipError_t launch_maxpool2x2(const float *x, int64_t ld, int c0, int c, float *y, int n, int hi, int wi, hipStream_t s);
+// y[b, i, :] = sum_j softmax_j(q[b, i, :] . k[b, j, :]) v[b, j, :] (see nonlocal_attn_kernel): rows of q / k, v / y are ldq / ldkv /
+// ldy floats apart (ldq, ldkv multiples of 4; q, k, v 16-byte aligned).  d in {256, 512}, else hipErrorNotSupported (nothing launched).
+hipError_t launch_nonlocal_attention(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *y,
+                                     int64_t ldy, int n_clips, int nq, int nk, int d, hipStream_t s);
+
 // K9: per clip, (softmax,) first arg-max, class id if its score >= threshold else -1; top (nullable) = that score.
 hipError_t launch_scores_to_states(const float *logits, int n, int c, int softmax, float threshold, int *states, float *top,
                                    hipStream_t s);

@@ -22,7 +22,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, DEPTHS, SHIFT_PLACES, WIDTHS, feature_width, is_mmaction_state_dict, make_state_dict,
+from .weights import (BACKBONES, DEPTHS, NL_BLOCKS, SHIFT_PLACES, WIDTHS, feature_width, is_mmaction_state_dict, make_state_dict,
                       remap_checkpoint_keys, remap_mmaction_keys, remap_torchvision_keys)
 
 CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
@@ -47,9 +47,11 @@ class TsmEngine:
     def __init__(self, num_class: int = 12, num_segments: int = 8, height: int = 224, width: int = 224,
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
-                 base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg'):
+                 base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg',
+                 non_local: bool = False):
         if base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+        _check_non_local(non_local, base_model, dtype)
         if shift_place not in SHIFT_PLACES:
             raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
         if consensus_type not in CONSENSUS_TYPES:
@@ -65,6 +67,7 @@ class TsmEngine:
         self.base_model = base_model
         self.shift_place = shift_place
         self.consensus_type = consensus_type
+        self.non_local = bool(non_local)
         self.feature_dim = feature_width(base_model)      # row width of forward_features
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
@@ -80,6 +83,8 @@ class TsmEngine:
             _lib.check(self._lib.tsm_set_shift_place(self._h, SHIFT_PLACES[shift_place]), self._h)
         if consensus_type != 'avg':
             _lib.check(self._lib.tsm_set_consensus(self._h, CONSENSUS_TYPES[consensus_type]), self._h)
+        if non_local:
+            _lib.check(self._lib.tsm_set_non_local(self._h, 1), self._h)
         self._finalized = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -285,7 +290,8 @@ class TsmEngine:
 
     # ---- per-launch timing (bench.py roofline) -------------------------------------------------------
     def launch_names(self) -> List[str]:
-        """Names of the kernel launches of one forward, in launch order (matches tsm_layer_times)."""
+        """Names of the kernel launches of one forward, in launch order (matches tsm_layer_times).  A non-local engine's
+        wrapped blocks add four: the theta | phi | g conv, the pool, the attention and the W conv."""
         names = ['pack_input', 'conv1', 'maxpool']
         blocks, kind = BACKBONES[self.base_model]
         for li, nb in enumerate(blocks, start=1):
@@ -295,6 +301,8 @@ class TsmEngine:
                     names += ([p + '.downsample'] if b == 0 and li > 1 else []) + [p + '.conv1', p + '.conv2']
                 else:
                     names += ([p + '.downsample'] if b == 0 else []) + [p + '.conv1', p + '.conv2', p + '.conv3']
+                    if self.non_local and (li, b) in NL_BLOCKS:
+                        names += [p + '.nl.qkv', p + '.nl.pool', p + '.nl.attn', p + '.nl.W']
         return names + ['head']
 
     TILE_NAMES = {0: 'heuristic', 1: '128x128', 2: '128x64', 3: '64x64', 4: '32x32', 5: '128x128w8', 6: '256x256', 7: 'ws',
@@ -318,7 +326,7 @@ class TsmEngine:
         buf = (C.c_int32 * 64)()
         n = C.c_int32()
         _lib.check(self._lib.tsm_conv_tiles(self._h, n_clips, buf, 64, C.byref(n)), self._h)
-        names = [k for k in self.launch_names() if k not in ('pack_input', 'maxpool', 'head')]
+        names = [k for k in self.launch_names() if k not in ('pack_input', 'maxpool', 'head') and not k.endswith(('.nl.pool', '.nl.attn'))]
         assert n.value == len(names)
         return {k: self.tile_name(buf[i]) for i, k in enumerate(names)}
 
@@ -353,6 +361,17 @@ class TsmEngine:
             pass
 
 
+def _check_non_local(non_local: bool, base_model: str, dtype: str) -> None:
+    """``non_local=True`` is refused up front, never ignored, where the engine has no non-local block: BasicBlock backbones
+    and the bf16 formats (whose cross-block fused forms and storage formats do not know the block)."""
+    if not non_local:
+        return
+    if BACKBONES[base_model][1] != 'bottleneck':
+        raise NotImplementedError(f'non_local=True needs a Bottleneck backbone (resnet50, wide_resnet50_2), not {base_model}')
+    if dtype != 'f32':
+        raise NotImplementedError(f"non_local=True runs in dtype='f32' only, not {dtype!r}")
+
+
 def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'resnet50',
                  checkpoint: Optional[str] = None, device: Optional[object] = None, fc_lr5: bool = True,
                  is_shift: bool = True, shift_div: int = 8, shift_place: str = 'blockres',
@@ -378,14 +397,19 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     every segment, [B, T, num_class]: one launch, head_seg_kernel); anything else fails the reference's assert
     (tsm.py:438).  It is the caller's argument for every kind of checkpoint: an ``.onnx`` file is read for its weights only,
     the consensus is not detected from its graph.
+    ``non_local=True``: blocks 0 and 2 of layer2 and 0, 2 and 4 of layer3 are wrapped in an embedded-Gaussian non-local block
+    (self-attention over all T*H*W positions of a clip; state-dict keys ``layerL.B.block.*`` / ``layerL.B.nl.*``,
+    include/tsm_hip.h: tsm_set_non_local).  ``dtype='f32'`` and Bottleneck backbones only; the bf16 formats, resnet18 / 34 and
+    an ``.onnx`` checkpoint raise NotImplementedError, and mmaction2's non-local key spelling is not mapped.
     """
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     assert consensus_type in ['avg', 'identity']
     if shift_place not in SHIFT_PLACES:
         raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
-    if non_local:
-        raise NotImplementedError('non_local')
+    _check_non_local(non_local, base_model, dtype)
+    if non_local and checkpoint is not None and str(checkpoint).endswith('.onnx'):
+        raise NotImplementedError('non_local=True with an .onnx checkpoint: the importer does not read non-local blocks')
     dev = 0
     if device is not None:
         s = str(device)
@@ -400,13 +424,16 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         ckpt = torch.load(checkpoint, map_location='cpu')
         raw = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
         # mmaction2 checkpoints (the reference's --mmlab branch) vs the reference's own TSM / Lightning ones
+        if non_local and is_mmaction_state_dict(raw):
+            raise NotImplementedError('non_local=True with an mmaction2 checkpoint: its non-local key spelling is not mapped')
         sd = (remap_mmaction_keys(raw) if is_mmaction_state_dict(raw)
-              else remap_checkpoint_keys(raw, num_class, base_model))
+              else remap_checkpoint_keys(raw, num_class, base_model, non_local=non_local))
     else:
-        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model, shift_place=shift_place)
+        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model, shift_place=shift_place, non_local=non_local)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width,
                      shift_div=shift_div, is_shift=is_shift, max_clips=max_clips, device=dev, state_dict=sd,
-                     dtype=dtype, base_model=base_model, shift_place=shift_place, consensus_type=consensus_type)
+                     dtype=dtype, base_model=base_model, shift_place=shift_place, consensus_type=consensus_type,
+                     non_local=non_local)
 
 
 def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpoint: Optional[str] = None, max_frames: int = 32,
@@ -892,6 +919,57 @@ def maxpool3x3s2_nhwc(x, out=None):
     n, hi, wi, c = x.shape
     y = _out(out, (n, (hi - 1) // 2 + 1, (wi - 1) // 2 + 1, c), torch.float32, x)
     _lib.check(_lib.load().tsm_maxpool3x3s2(x.data_ptr(), y.data_ptr(), n, hi, wi, c, _stream(x)))
+    return y
+
+
+def _rows_view(t, name: str):
+    """(pointer, row stride in floats, shape) of a tensor whose LAST dimension is contiguous and whose leading dimensions
+    are laid out like a contiguous tensor of rows ``ld`` floats apart: a contiguous tensor or a channel slice of one."""
+    shape = tuple(int(d) for d in t.shape)
+    strides = tuple(int(v) for v in t.stride())
+    ld, acc, ok = None, 1, strides[-1] == 1 or shape[-1] == 1
+    for dim, st in zip(reversed(shape[:-1]), reversed(strides[:-1])):      # (the stride of a dimension of size 1 means nothing)
+        if dim != 1:
+            if ld is None:
+                ok, ld = ok and st % acc == 0, st // acc
+            else:
+                ok = ok and st == ld * acc
+        acc *= dim
+    ld = shape[-1] if ld is None else ld
+    if not ok or ld < shape[-1] or 0 in shape:
+        raise ValueError(f'{name} must be a non-empty contiguous tensor or a channel slice of one, got shape {shape} strides {strides}')
+    return t.data_ptr(), ld, shape
+
+
+def maxpool2x2_nhwc(x, c0: int = 0, c: Optional[int] = None, out=None):
+    """``tsm_maxpool2x2``: MaxPool3d((1, 2, 2)) of channels [c0, c0 + c) of x, CUDA float32 [N, H, W, C] (NHWC; a channel
+    slice of a wider tensor keeps its row stride) -> dense [N, H // 2, W // 2, c].  Floor mode: a last odd row / column is
+    dropped.  One launch on torch's current stream."""
+    import torch
+    _need_cuda_f32(x=x)
+    ptr, ld, (n, hi, wi, cx) = _rows_view(x, 'x')
+    c = cx - c0 if c is None else int(c)
+    if c0 < 0 or c <= 0 or c0 + c > cx:
+        raise ValueError(f'channels [{c0}, {c0 + c}) are not inside the {cx} of x')
+    y = _out(out, (n, hi // 2, wi // 2, c), torch.float32, x)
+    _lib.check(_lib.load().tsm_maxpool2x2(ptr, ld, c0, c, y.data_ptr(), n, hi, wi, _stream(x)))
+    return y
+
+
+def nonlocal_attention(q, k, v, out=None):
+    """``tsm_nonlocal_attention``: q CUDA float32 [B, Nq, d], k and v [B, Nk, d] (each a contiguous tensor or a channel slice
+    of one; k and v with the same row stride) -> y [B, Nq, d] = softmax_j(q . k^T) v without a scale factor, by the fused
+    online-softmax kernel (d = 256 or 512; nothing of size Nq * Nk is allocated).  ``out``: a contiguous [B, Nq, d] tensor.
+    One launch on torch's current stream."""
+    import torch
+    _need_cuda_f32(q=q, k=k, v=v)
+    qp, ldq, (b, nq, d) = _rows_view(q, 'q')
+    kp, ldk, kshape = _rows_view(k, 'k')
+    vp, ldv, vshape = _rows_view(v, 'v')
+    if kshape != vshape or kshape[0] != b or kshape[2] != d or ldk != ldv:
+        raise ValueError(f'q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit (k and v share shape and row stride)')
+    y = _out(out, (b, nq, d), torch.float32, q)
+    _lib.check(_lib.load().tsm_nonlocal_attention(qp, ldq, kp, vp, ldk, y.data_ptr(), d, b, nq, kshape[1], d, _stream(q)))
     return y
 
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Dict, List
 
-from .weights import STEM, block_specs, feature_width
+from .weights import NL_BLOCKS, STEM, block_specs, feature_width, nonlocal_specs
 
 
 def _out(size: int, k: int, stride: int) -> int:
@@ -36,6 +36,27 @@ def macs_per_frame(height: int = 224, width: int = 224, num_class: int = 12, bas
     return sum(r['macs'] for r in layer_table(height, width, base_model)) + feature_width(base_model) * num_class
 
 
+def _stage_size(size: int, layer: int) -> int:
+    """Side of layer<layer>'s output: the stem, the max-pool, then one strided 3x3 per stage from layer2 on."""
+    s = _out(_out(size, 7, 2), 3, 2)
+    for _ in range(layer - 1):
+        s = _out(s, 3, 2)
+    return s
+
+
+def nonlocal_table(num_segments: int = 8, height: int = 224, width: int = 224, base_model: str = 'resnet50') -> List[Dict[str, int]]:
+    """One row per non-local block (``create_model(non_local=True)``): name, c, d = c // 2, nq = T * H * W, nk = T * (H // 2) *
+    (W // 2) and the MACs PER CLIP of its 1x1 convs (theta | phi | g: nq * c * 3 d, W: nq * d * c) and of the attention (the
+    scores nq * nk * d, P V the same again).  The pool and the softmax count zero FLOPs."""
+    rows = []
+    for (li, b), (_prefix, c, d) in zip(NL_BLOCKS, nonlocal_specs(base_model)):      # (raises for a BasicBlock backbone)
+        h, w = _stage_size(height, li), _stage_size(width, li)
+        nq, nk = num_segments * h * w, num_segments * (h // 2) * (w // 2)
+        rows.append(dict(name=f'layer{li}.{b}.nl', c=c, d=d, nq=nq, nk=nk, conv_macs=nq * (c * 3 * d + d * c), attn_macs=2 * nq * nk * d))
+    return rows
+
+
 def flops_per_clip(num_segments: int = 8, height: int = 224, width: int = 224, num_class: int = 12,
-                   base_model: str = 'resnet50') -> float:
-    return 2.0 * macs_per_frame(height, width, num_class, base_model) * num_segments
+                   base_model: str = 'resnet50', non_local: bool = False) -> float:
+    nl = sum(r['conv_macs'] + r['attn_macs'] for r in nonlocal_table(num_segments, height, width, base_model)) if non_local else 0
+    return 2.0 * (macs_per_frame(height, width, num_class, base_model) * num_segments + nl)

@@ -30,6 +30,14 @@ WIDTHS = {'wide_resnet50_2': 128}
 # create_model(shift_place=...) -> tsm_set_shift_place: 'blockres' wraps conv1 of every block in TemporalShift
 # (``layerL.B.conv1.net.weight``), 'block' wraps every block whole (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1.*``, ...)
 SHIFT_PLACES = {'blockres': 0, 'block': 1}
+# create_model(non_local=True) -> tsm_set_non_local: the TSM code base's make_non_local wraps these (stage, block) pairs of a
+# Bottleneck backbone in NL3DWrapper: the block's own tensors move under ``layerL.B.block``, the new ones are ``layerL.B.nl.*``
+NL_BLOCKS = ((2, 0), (2, 2), (3, 0), (3, 2), (3, 4))
+# make_state_dict(non_local=True): theta and phi are drawn with std gain / sqrt(C).  The scores' spread grows with gain^2, with
+# sqrt(d) and with the mean square of the block's output, which rises from wrapped block to wrapped block; one gain for all five
+# leaves the later ones one-hot.  These keep the largest probability of >= 98 % of the seeded R50's softmax rows inside
+# (2 / N_k, 0.9) at 64 x 64 and 48 x 48 (N_k = 128 / 72 in layer2, 32 / 8 in layer3; tests/test_nonlocal_cpu.py asserts 90 %).
+NL_GAINS = {(2, 0): 0.2, (2, 2): 0.16, (3, 0): 0.14, (3, 2): 0.11, (3, 4): 0.08}
 
 
 def _backbone(base_model: str):
@@ -53,6 +61,28 @@ def _shift_place(shift_place: str) -> str:
     if shift_place not in SHIFT_PLACES:
         raise ValueError(f'shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}')
     return shift_place
+
+
+def _non_local(non_local: bool, base_model: str) -> bool:
+    if non_local and _backbone(base_model)[1] != 'bottleneck':
+        raise NotImplementedError(f'non_local=True needs a Bottleneck backbone (resnet50, wide_resnet50_2), not {base_model}')
+    return bool(non_local)
+
+
+def nonlocal_specs(base_model: str = 'resnet50') -> List[Tuple[str, int, int]]:
+    """(key prefix ``base_model.layerL.B.nl``, C, d = C // 2) of every non-local block, in forward order."""
+    _non_local(True, base_model)
+    return [(f'base_model.layer{li}.{b}.nl', R50_PLANES[li - 1] * EXPANSION, R50_PLANES[li - 1] * EXPANSION // 2) for li, b in NL_BLOCKS]
+
+
+def nonlocal_keys(base_model: str = 'resnet50') -> List[str]:
+    """The state-dict keys the non-local blocks add (NONLocalBlock3D: theta, phi = Sequential(conv, pool), g likewise,
+    W = Sequential(conv, BatchNorm3d))."""
+    keys = []
+    for p, _c, _d in nonlocal_specs(base_model):
+        keys += [p + t + s for t in ('.theta', '.phi.0', '.g.0', '.W.0') for s in ('.weight', '.bias')]
+        keys += [p + '.W.1' + s for s in ('.weight', '.bias', '.running_mean', '.running_var')]
+    return keys
 
 
 STEM = ('base_model.conv1.weight', 'base_model.bn1', 64, 3, 7)
@@ -85,14 +115,18 @@ def block_specs(base_model: str = 'resnet50'):
             cin = cout
 
 
-def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> List[Tuple[str, str, int, int, int]]:
+def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres',
+               non_local: bool = False) -> List[Tuple[str, str, int, int, int]]:
     """(conv weight key, bn prefix, cout, cin, k) for every conv of TSM-``base_model``, in forward order (53 for R50 and
     WRN-50-2, 20 for R18, 36 for R34): the stem, then ``block_specs`` flattened.  ``shift_place='block'``: the same
-    convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``)."""
+    convs, every block's keys under its TemporalShift wrapper (``layerL.B.net.conv1.weight``, ``layerL.B.net.bn1``).
+    ``non_local=True``: the same convs again, the keys of the ``NL_BLOCKS`` under ``layerL.B.block`` (the non-local blocks' own
+    tensors are not convs with a BatchNorm of this form: ``nonlocal_specs`` / ``nonlocal_keys``)."""
     block = _shift_place(shift_place) == 'block'
+    non_local = _non_local(non_local, base_model)
     specs = [STEM]
     for li, b, _stride, convs in block_specs(base_model):
-        p = f'base_model.layer{li}.{b}' + ('.net' if block else '')
+        p = f'base_model.layer{li}.{b}' + ('.block' if non_local and (li, b) in NL_BLOCKS else '') + ('.net' if block else '')
         for role, cout, cin, k, _s, _at_input in convs:
             if role == 'downsample':
                 specs.append((p + '.downsample.0.weight', p + '.downsample.1', cout, cin, k))
@@ -103,7 +137,7 @@ def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres') -> L
 
 
 def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resnet50',
-                    shift_place: str = 'blockres') -> 'OrderedDict[str, np.ndarray]':
+                    shift_place: str = 'blockres', non_local: bool = False) -> 'OrderedDict[str, np.ndarray]':
     """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048] -- [cls, 512] for R18/R34).
 
     He-normal convs; BN statistics are all non-trivial so the fold is exercised; the last BN of
@@ -112,6 +146,10 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
     gives logits too flat to discriminate between clips).  R50 draws the same stream as it always has
     (tests/golden/tsm_r50_logits.json depends on it); every other backbone draws its own shapes from the same procedure.  ``shift_place`` changes the keys only (``conv_specs``): one seed
     gives the same numbers under both spellings.
+    ``non_local=True`` adds the ``nl.*`` tensors from a SECOND generator seeded from ``(seed, "nl")``, after everything else:
+    every other key keeps its numbers.  theta / phi std ``NL_GAINS`` / sqrt(C) (soft but not uniform attention at the test
+    sizes), g std 1 / sqrt(C), W.0 std 1 / sqrt(d), biases std 0.1; W.1 like every other BatchNorm with gamma damped by 0.35 -- NOT the zero
+    of the original init, under which the block is the identity.
     """
     last_bn = '.bn2' if _backbone(base_model)[1] == 'basic' else '.bn3'
     rng = np.random.default_rng(seed)
@@ -120,7 +158,7 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
     def f32(a):
         return np.ascontiguousarray(a, dtype=np.float32)
 
-    for wkey, bnp, cout, cin, k in conv_specs(base_model, shift_place):
+    for wkey, bnp, cout, cin, k in conv_specs(base_model, shift_place, non_local):
         fan_in = cin * k * k
         sd[wkey] = f32(rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / fan_in))
         damp = 0.35 if bnp.endswith(last_bn) else 1.0
@@ -130,19 +168,35 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
         sd[bnp + '.running_var'] = f32(rng.uniform(0.6, 1.4, cout))
     sd['fc.weight'] = f32(rng.standard_normal((num_class, feature_width(base_model))) * 0.05)
     sd['fc.bias'] = f32(rng.standard_normal(num_class) * 0.1)
+    if non_local:
+        nl = np.random.default_rng([seed, int.from_bytes(b'nl', 'big')])
+        for (p, c, d), lb in zip(nonlocal_specs(base_model), NL_BLOCKS):
+            for name, cout, cin, std in (('.theta', d, c, NL_GAINS[lb] / np.sqrt(c)), ('.phi.0', d, c, NL_GAINS[lb] / np.sqrt(c)),
+                                         ('.g.0', d, c, 1.0 / np.sqrt(c)), ('.W.0', c, d, 1.0 / np.sqrt(d))):
+                sd[p + name + '.weight'] = f32(nl.standard_normal((cout, cin, 1, 1, 1)) * std)
+                sd[p + name + '.bias'] = f32(nl.standard_normal(cout) * 0.1)
+            sd[p + '.W.1.weight'] = f32(nl.uniform(0.8, 1.2, c) * 0.35)
+            sd[p + '.W.1.bias'] = f32(nl.standard_normal(c) * 0.1)
+            sd[p + '.W.1.running_mean'] = f32(nl.standard_normal(c) * 0.1)
+            sd[p + '.W.1.running_var'] = f32(nl.uniform(0.6, 1.4, c))
     return sd
 
 
 def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
-                          base_model: str = 'resnet50') -> 'OrderedDict[str, object]':
+                          base_model: str = 'resnet50', non_local: bool = False) -> 'OrderedDict[str, object]':
     """Checkpoint ``state_dict`` (``module.``/``model.``-prefixed) -> engine keys, exactly as create_model does it
     (models/tsm.py:451-473; pinned by tests/golden/ref_ckpt_remap.json, produced by executing those statements):
     the LAST TWO entries are the classifier; they become ``fc.weight`` / ``fc.bias`` iff the weight has ``num_class``
     rows and are dropped otherwise; every key loses its first dotted component.  Like the reference, a classifier
     that is already called ``module.fc`` is dropped by the delete that follows the copy -- the reference then keeps
     its random-init fc (``strict=False``); the engine reports the missing ``fc.weight`` instead of guessing.
-    The rule does not depend on the backbone; ``base_model`` is checked to be one the engine implements."""
+    The rule does not depend on the backbone; ``base_model`` is checked to be one the engine implements.
+    ``non_local=True``: a TSM-NL checkpoint's ``layerL.B.block.*`` / ``layerL.B.nl.*`` keys pass through the same rule (they are
+    the engine's spelling already); a checkpoint without any ``.nl.`` key is refused here, by name, rather than at the
+    engine's first missing tensor.  mmaction2's NL spelling is not mapped."""
     _backbone(base_model)
+    if _non_local(non_local, base_model) and not any('.nl.' in k for k in state_dict):
+        raise KeyError('non_local=True, but the checkpoint has no non-local block tensors (no ".nl." key)')
     items = OrderedDict(state_dict)
     keys = list(items.keys())
     fc_w, fc_b = keys[-2], keys[-1]
@@ -226,11 +280,14 @@ def remap_mmaction_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, o
     return out
 
 
-def required_keys(num_class_known: bool = True, base_model: str = 'resnet50', shift_place: str = 'blockres') -> Iterable[str]:
-    for wkey, bnp, *_ in conv_specs(base_model, shift_place):
+def required_keys(num_class_known: bool = True, base_model: str = 'resnet50', shift_place: str = 'blockres',
+                  non_local: bool = False) -> Iterable[str]:
+    for wkey, bnp, *_ in conv_specs(base_model, shift_place, non_local):
         yield wkey
         for s in ('.weight', '.bias', '.running_mean', '.running_var'):
             yield bnp + s
+    if non_local:
+        yield from nonlocal_keys(base_model)
     yield 'fc.weight'
     yield 'fc.bias'
 

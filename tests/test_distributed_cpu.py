@@ -232,7 +232,7 @@ def _dataset_global_warmup_failing_worker(rank, world, root, out_dir):
     """Rank 0's model fails in warmup() (a tsm_tune HIP error / OOM in the real engine) -- after the plan exchange, before the
     loop: it must ride the status row of the final exchange like a failure inside the loop."""
     from tests._stub import StubModel
-    from workoutdetector_amd import inference_count as ic
+    from workoutdetector_amd import inference_count as ic, staging
 
     class ColdFail(StubModel):
         def warmup(self, sizes):
@@ -240,9 +240,9 @@ def _dataset_global_warmup_failing_worker(rank, world, root, out_dir):
                 raise MemoryError('tune scratch')
             return self
 
-    # (the warm-up only runs for a model on a device: give the stub one the way _engine_device reads it)
-    orig = ic._engine_device
-    ic._engine_device = lambda m: None
+    # (the warm-up only runs for a model on a device: give the stub one the way staging.engine_device reads it)
+    orig = staging.engine_device
+    staging.engine_device = lambda m: None
     try:
         model = ColdFail()
         run_global = ic._run_global
@@ -258,7 +258,7 @@ def _dataset_global_warmup_failing_worker(rank, world, root, out_dir):
         assert rank != 0 and 'rank(s) [0] failed' in str(exc), str(exc)
         open(os.path.join(out_dir, f'raised{rank}'), 'w').write('peer')
     finally:
-        ic._engine_device = orig
+        staging.engine_device = orig
 
 
 def test_global_sharding_failure_on_one_rank_reaches_every_rank(tmp_path, golden_dir):

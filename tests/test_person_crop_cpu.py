@@ -110,8 +110,8 @@ def test_dataset_driver_runs_the_torch_transform_for_a_model_that_is_not_an_engi
     """A session / stub has no device path: every clip goes through PersonCropTransform.__call__ with ITS box, the tail
     padded before the transform; shard None resolves to 'clips' and 'videos' writes the same files."""
     import pandas as pd
-    from workoutdetector_amd import inference_count as ic
-    monkeypatch.setattr(ic, '_engine_device', lambda model: None)       # (the stub has no device path on a GPU box either)
+    from workoutdetector_amd import inference_count as ic, staging
+    monkeypatch.setattr(staging, 'engine_device', lambda model: None)       # (the stub has no device path on a GPU box either)
     anno = pd.read_csv(f'{golden_dir}/repcount_annotation.csv', index_col=0)
     rows = anno[anno['name'].isin(['stu1_40.mp4', 'stu5_32.mp4'])].copy()
     rows['name'] = [n.replace('.mp4', '.npy') for n in rows['name']]

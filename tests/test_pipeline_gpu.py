@@ -277,3 +277,30 @@ def test_dataset_loop_pieces_shrink_to_the_staging_bound(probe_engine, tmp_path,
     for f in files:
         assert open(os.path.join(whole, f)).read() == open(os.path.join(pieces, f)).read(), f
     assert sorted(int(v.shape[0]) for v in got.values()) == [2, 10, 17]
+
+
+def test_uploads_reuse_pool_slots_under_real_events():
+    """Five ``staging.upload`` calls through a 2-slot pool on a side stream: slots 0, 1, 0, 1, 0, so the third upload on
+    waits for a real event before it overwrites a buffer, the 9-frame shapes grow what the 5- and 2-frame ones leave, and
+    every device tensor equals its source once ``wait_upload`` has made the current stream wait.  A sixth upload whose
+    ``fill`` raises gives its slot back: the pool stays usable."""
+    from workoutdetector_amd import staging
+    dev = torch.device('cuda', 0)
+    pool, side = staging.PinnedPool(slots=2), torch.cuda.Stream(dev)
+    gen = torch.Generator().manual_seed(5)
+    for n in (5, 9, 2, 9, 1):
+        src = torch.randint(0, 256, (n, 6, 8, 3), dtype=torch.uint8, generator=gen)
+        got, ready = staging.upload(src.shape, lambda pinned: pinned.copy_(src), dev, side, pool)
+        staging.wait_upload(got, ready)
+        assert got.device == dev and got.dtype == torch.uint8 and torch.equal(got.cpu(), src)
+
+    def failing(pinned):
+        raise OSError('no frames')
+    with pytest.raises(OSError, match='no frames'):
+        staging.upload((3, 6, 8, 3), failing, dev, side, pool)
+    assert pool.taken == [False, False] and pool.busy[1] is None
+    src = torch.randint(0, 256, (4, 6, 8, 3), dtype=torch.uint8, generator=gen)
+    for _ in range(2):                                                      # both slots, the failed one included
+        got, ready = staging.upload(src.shape, lambda pinned: pinned.copy_(src), dev, side, pool)
+        staging.wait_upload(got, ready)
+        assert torch.equal(got.cpu(), src)

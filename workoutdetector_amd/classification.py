@@ -42,6 +42,7 @@ import numpy as np
 import torch
 
 from . import inference_count as ic
+from . import staging
 from .transform import INPUT_SIZE, TestTransform
 
 FILENAME_TMPL = 'img_{:05}.jpg'
@@ -155,11 +156,10 @@ def _pieces(rows: Sequence[Sequence[int]], per_frame_bytes: int, budget: int) ->
 def _eval_engine(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
     """The device path: see the module docstring.  Returns (correct, total, preds, logits | None) in PROCESSING order."""
     from .engine import preprocess_indexed, top1_tally
-    dev = ic._engine_device(model)
+    dev = staging.engine_device(model)
     n, c = len(samples), int(model.num_class)
-    cur = torch.cuda.current_stream(dev)
     # (host zeros copied up, empty device buffers written by the library's own launches: no torch kernel anywhere)
-    counters = torch.zeros((2, c), dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+    counters = staging.upload_table(torch.zeros((2, c), dtype=torch.int32), dev)
     preds = torch.empty((n,), dtype=torch.int32, device=dev)
     logits = torch.empty((n, c), dtype=torch.float32, device=dev) if want_logits else None
     done = 0
@@ -172,11 +172,8 @@ def _eval_engine(model, samples, groups, reader, batch: int, transform: TestTran
             table = torch.from_numpy(_table(union, rows[a:b]))
             labels = torch.tensor([int(samples[i]['label']) for i in ids[a:b]], dtype=torch.int32)
             rest = [f for f in union if f != union_all[0]]
-            shape = (len(union),) + tuple(probe.shape[1:])
-            flat, slot = ic._pinned_pool.take(int(np.prod(shape)))
-            ready = None
-            try:
-                pinned = flat.view(shape)
+
+            def fill(pinned: torch.Tensor) -> None:
                 if len(rest) < len(union):                               # (the probed frame is the smallest: row 0)
                     pinned[0].copy_(probe[0])
                 if rest:
@@ -184,13 +181,8 @@ def _eval_engine(model, samples, groups, reader, batch: int, transform: TestTran
                     if tuple(got.shape[1:]) != tuple(probe.shape[1:]):
                         raise ValueError(f'{frame_dir}: frames of {tuple(got.shape[1:3])} and {tuple(probe.shape[1:3])} pixels')
                     pinned[len(union) - len(rest):].copy_(got)
-                frames = pinned.to(dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record(cur)
-            finally:
-                ic._pinned_pool.release(slot, ready)
-            table = table.pin_memory().to(dev, non_blocking=True)
-            labels = labels.pin_memory().to(dev, non_blocking=True)
+            frames, _ready = staging.upload((len(union),) + tuple(probe.shape[1:]), fill, dev)
+            table, labels = staging.upload_table(table, dev), staging.upload_table(labels, dev)
             for lo in range(0, b - a, batch):
                 hi = min(lo + batch, b - a)
                 clips = preprocess_indexed(frames, table[lo:hi], resize=transform.size, crop=transform.crop,
@@ -262,7 +254,7 @@ def eval_classification(model, samples: Sequence[Mapping], frame_reader: Optiona
         transform = TestTransform(RESIZE, int(getattr(model, 'height', INPUT_SIZE)), scale_255=True)
     samples = list(samples)
     groups = _by_directory(samples, t)
-    engine = ic._engine_device(model) is not None and hasattr(model, 'packed_layout')
+    engine = staging.device_path(model)
     limit = int(model.max_clips) if engine else None
     batch = int(batch_clips or limit or 32)
     if batch <= 0:

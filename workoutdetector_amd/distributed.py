@@ -11,7 +11,7 @@ Backend: ``nccl`` (= RCCL over xGMI on ROCm) for CUDA tensors, ``gloo`` for the 
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -68,6 +68,14 @@ def all_gather_logits(local: torch.Tensor, group=None) -> torch.Tensor:
     return out
 
 
+def _pad_rows(local: torch.Tensor, per: int) -> torch.Tensor:
+    """``local`` with zero rows behind it, up to ``per`` rows: every rank brings the same shape to an all-gather."""
+    if local.shape[0] >= per:
+        return local
+    pad = torch.zeros((per - local.shape[0],) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+    return torch.cat([local, pad], dim=0)
+
+
 def gather_clip_logits(local: torch.Tensor, n_total: int, group=None) -> torch.Tensor:
     """Ragged form: rank r holds the logits of its ``shard_range`` block (possibly fewer than
     ``per_rank`` rows, possibly none).  Pads to ``per_rank`` rows, all-gathers once, trims to
@@ -81,10 +89,22 @@ def gather_clip_logits(local: torch.Tensor, n_total: int, group=None) -> torch.T
     per = per_rank(n_total, world)
     lo, hi = shard_range(n_total, world, rank)
     assert local.shape[0] == hi - lo, f'rank {rank}: got {local.shape[0]} rows for block [{lo},{hi})'
-    if local.shape[0] < per:
-        pad = torch.zeros((per - local.shape[0],) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
-        local = torch.cat([local, pad], dim=0)
-    return all_gather_logits(local, group)[:n_total]
+    return all_gather_logits(_pad_rows(local, per), group)[:n_total]
+
+
+def all_gather_host(local: torch.Tensor, dev: Optional[torch.device] = None, n_total: Optional[int] = None) -> torch.Tensor:
+    """The exchange of a HOST tensor, result on the host: through ``dev`` (the rank's GPU, None without one) when the group
+    moves CUDA tensors (RCCL), on the host otherwise.  ``all_gather_logits``, or with ``n_total`` the ragged
+    ``gather_clip_logits``."""
+    if dev is not None and on_rccl():
+        local = local.to(dev)
+    return (all_gather_logits(local) if n_total is None else gather_clip_logits(local, n_total)).cpu()
+
+
+def gather_padded_host(local: torch.Tensor, per: int, dev: Optional[torch.device] = None) -> torch.Tensor:
+    """Host rows [n <= per, C], n its own on every rank -> [W, per, C] on the host, each rank's block zero-padded to ``per``
+    rows (the caller exchanged the row counts before)."""
+    return all_gather_host(_pad_rows(local, per), dev).reshape((world_info()[1], per) + tuple(local.shape[1:]))
 
 
 def shard_list(items: List, world: int, rank: int) -> List:

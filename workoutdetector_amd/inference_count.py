@@ -39,7 +39,6 @@ Reference quirks reproduced by default (flags to change): frames are NOT divided
 """
 from __future__ import annotations
 
-import contextlib
 import json
 import os
 import os.path as osp
@@ -54,6 +53,7 @@ import numpy as np
 import torch
 
 from . import distributed as tdist
+from . import staging
 from .counting import RepCounter, pred_to_count, scores_to_preds, vote_states  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
 from .transform import (ImageTransform, PersonCropTransform, TestTransform, as_frames_u8, build_test_transform,
@@ -131,12 +131,6 @@ def inference_video(model, inputs: Union[torch.Tensor, np.ndarray], threshold: f
 
 
 # ---- batched device path -------------------------------------------------------------------------------
-def _engine_device(model) -> Optional[torch.device]:
-    if hasattr(model, 'forward_device') and torch.cuda.is_available():
-        return torch.device('cuda', getattr(model, 'device', 0))
-    return None
-
-
 @dataclass
 class StagedVideo:
     """The frames a clip range needs, on their way to (or already on) the engine's device."""
@@ -148,54 +142,28 @@ class StagedVideo:
     frames: torch.Tensor            # uint8 [n_even (+1 zero frame on the HIP path), H, W, 3]
     on_device: bool
     ready: Optional[object] = None  # torch.cuda.Event recorded after the H2D copy
-    _pinned: Optional[torch.Tensor] = None
 
 
-class _PinnedPool:
-    """Reusable page-locked staging buffers.  Pinning fresh memory for every video costs a hipHostMalloc /
-    hipHostFree pair that serialises with the GPU queue; here a few flat byte buffers are grown geometrically
-    and handed out round-robin.  Ownership is explicit: ``take`` hands a slot to exactly one user (the prefetch
-    worker thread and the main thread's oversized-video loop share the pool) and the slot stays taken -- while it
-    is being filled on the host AND while the H2D copy out of it is in flight -- until that user calls ``release``
-    with the event recorded behind its copy; the next taker of the slot waits for the release, then for the event."""
-
-    def __init__(self, slots: int = 3):
-        self.bufs: List[Optional[torch.Tensor]] = [None] * slots
-        self.busy: List[Optional[object]] = [None] * slots      # event of the last copy out of the slot
-        self.taken: List[bool] = [False] * slots                # handed out and not yet released
-        self.next = 0
-        self.cv = threading.Condition()
-
-    def take(self, nbytes: int) -> Tuple[torch.Tensor, int]:
-        with self.cv:
-            i = self.next
-            self.next = (i + 1) % len(self.bufs)
-            while self.taken[i]:
-                self.cv.wait()
-            self.taken[i] = True
-            ev, self.busy[i] = self.busy[i], None
-        try:
-            if ev is not None:
-                ev.synchronize()
-            if self.bufs[i] is None or self.bufs[i].numel() < nbytes:
-                self.bufs[i] = None                              # free before growing
-                self.bufs[i] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-        except BaseException:
-            # (a failed event wait or pinned allocation: the callers' try/finally only starts once take() has returned,
-            #  so the slot is handed back here -- the next taker must get an error or a buffer, never an endless wait)
-            self.release(i, None)
-            raise
-        return self.bufs[i][:nbytes], i
-
-    def release(self, slot: int, event: Optional[object]) -> None:
-        """The user's host fill is done and its H2D copy is enqueued; ``event`` completes when the copy has."""
-        with self.cv:
-            self.busy[slot] = event
-            self.taken[slot] = False
-            self.cv.notify_all()
+def clips_per_piece(per_frame_bytes: int) -> int:
+    """The most consecutive clips whose staged frames fit ``MAX_STAGE_BYTES`` (read now, at the call): n clips sample 4 n + 4
+    even frames and stage a zero frame behind them.  At least 1, whatever the frame size."""
+    return max(1, (MAX_STAGE_BYTES // max(1, per_frame_bytes) - CLIP_SPAN // CLIP_STRIDE) // (CLIP_STEP // CLIP_STRIDE))
 
 
-_pinned_pool = _PinnedPool()
+def even_frame_range(total: int, lo: int, hi: int) -> Tuple[int, int]:
+    """[f_lo, f_hi) in even-frame units (source frame // 2) of what clips [lo, hi), lo < hi, sample in a video of ``total``
+    frames: only even source frames are ever sampled (starts are multiples of 8, stride 2)."""
+    return CLIP_STEP * lo // CLIP_STRIDE, min((CLIP_STEP * (hi - 1) + CLIP_SPAN) // CLIP_STRIDE, (total + 1) // CLIP_STRIDE)
+
+
+def _stage(dev, total: int, lo: int, hi: int, f_lo: int, hw: Tuple[int, int], even: torch.Tensor,
+           stream: Optional[object] = None) -> StagedVideo:
+    """``even`` -- the frames ``even_frame_range`` names for clips [lo, hi) -- and a zero frame behind them, to ``dev``."""
+    def fill(pinned: torch.Tensor) -> None:
+        pinned[:-1].copy_(even)
+        pinned[-1].zero_()              # the zero frame the padded tail clip reads
+    frames, ready = staging.upload((even.shape[0] + 1,) + tuple(even.shape[1:]), fill, dev, stream)
+    return StagedVideo(total, lo, hi, f_lo, hw, frames, True, ready)
 
 
 def stage_video(model, video_thwc_u8: torch.Tensor, clip_range: Optional[Tuple[int, int]] = None,
@@ -203,37 +171,17 @@ def stage_video(model, video_thwc_u8: torch.Tensor, clip_range: Optional[Tuple[i
     """Slice the even frames a clip range samples and, for a TsmEngine, copy them to its GPU through a
     pinned buffer on ``stream`` (so the copy of video i+1 can run under the compute of video i)."""
     total = int(video_thwc_u8.shape[0])
-    starts = clip_starts(total)
-    lo, hi = clip_range if clip_range is not None else (0, len(starts))
+    lo, hi = clip_range if clip_range is not None else (0, len(clip_starts(total)))
     hw = (int(video_thwc_u8.shape[1]), int(video_thwc_u8.shape[2]))
     if hi <= lo:
         return StagedVideo(total, lo, lo, 0, hw, video_thwc_u8[:0], False)
-    # only even source frames are ever sampled (starts are multiples of 8, stride 2)
-    f_lo = starts[lo] // CLIP_STRIDE
-    f_hi = min((starts[hi - 1] + CLIP_SPAN) // CLIP_STRIDE, (total + 1) // CLIP_STRIDE)
+    f_lo, f_hi = even_frame_range(total, lo, hi)
     even = video_thwc_u8[0::CLIP_STRIDE][f_lo:f_hi]
-    dev = _engine_device(model)
-    if dev is None or not hasattr(model, 'packed_layout'):
+    if not staging.device_path(model) or int(even.numel()) > MAX_STAGE_BYTES:
+        # (no device path; or too large to pin / upload in one piece: hand the (strided, un-copied) host view on;
+        #  staged_clip_logits walks the clip range in pieces that fit)
         return StagedVideo(total, lo, hi, f_lo, hw, even, False)
-    if int(even.numel()) > MAX_STAGE_BYTES:
-        # too large to pin / upload in one piece: hand the (strided, un-copied) host view on; staged_clip_logits
-        # walks the clip range in pieces that fit
-        return StagedVideo(total, lo, hi, f_lo, hw, even, False)
-    shape = (even.shape[0] + 1,) + tuple(even.shape[1:])
-    flat, slot = _pinned_pool.take(int(np.prod(shape)))
-    ready = None
-    try:
-        pinned = flat.view(shape)
-        pinned[:-1].copy_(even)
-        pinned[-1].zero_()              # the zero frame the padded tail clip reads
-        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-        with ctx:
-            frames = pinned.to(dev, non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record()
-    finally:
-        _pinned_pool.release(slot, ready)
-    return StagedVideo(total, lo, hi, f_lo, hw, frames, True, ready, pinned)
+    return _stage(staging.engine_device(model), total, lo, hi, f_lo, hw, even, stream)
 
 
 def staged_clip_logits(model, st: StagedVideo, transform: Union[TestTransform, PersonCropTransform], batch_clips: int = 32,
@@ -246,33 +194,16 @@ def staged_clip_logits(model, st: StagedVideo, transform: Union[TestTransform, P
     person = isinstance(transform, PersonCropTransform)
     if person and video_name is None:
         raise ValueError('a PersonCropTransform looks its boxes up by video: pass video_name')
-    starts = clip_starts(st.total)
-    dev = _engine_device(model)
-    if (not st.on_device and dev is not None and hasattr(model, 'packed_layout')
+    if (not st.on_device and staging.device_path(model)
             and isinstance(transform, (TestTransform, PersonCropTransform)) and int(st.frames.numel()) > MAX_STAGE_BYTES):
         # oversized video: pieces of consecutive clips whose even frames fit the staging bound, each staged on its own
-        per_frame = max(1, int(st.frames[0].numel()))
-        clips_per_piece = max(1, (MAX_STAGE_BYTES // per_frame - CLIP_SPAN // CLIP_STRIDE) // (CLIP_STEP // CLIP_STRIDE))
+        step = clips_per_piece(int(st.frames[0].numel()))
         parts = []
-        for a in range(st.lo, st.hi, clips_per_piece):
-            b = min(a + clips_per_piece, st.hi)
-            f_a = starts[a] // CLIP_STRIDE
-            f_b = min((starts[b - 1] + CLIP_SPAN) // CLIP_STRIDE, (st.total + 1) // CLIP_STRIDE)
-            piece = st.frames[f_a - st.f_lo:f_b - st.f_lo]
-            shape = (piece.shape[0] + 1,) + tuple(piece.shape[1:])
-            flat, slot = _pinned_pool.take(int(np.prod(shape)))
-            ready = None
-            try:
-                pinned = flat.view(shape)
-                pinned[:-1].copy_(piece)
-                pinned[-1].zero_()
-                frames = pinned.to(dev, non_blocking=True)
-                ready = torch.cuda.Event()
-                ready.record()
-            finally:
-                _pinned_pool.release(slot, ready)
-            parts.append(staged_clip_logits(model, StagedVideo(st.total, a, b, f_a, st.hw, frames, True, ready, pinned),
-                                            transform, batch_clips, video_name))
+        for a in range(st.lo, st.hi, step):
+            b = min(a + step, st.hi)
+            f_a, f_b = even_frame_range(st.total, a, b)
+            piece = _stage(staging.engine_device(model), st.total, a, b, f_a, st.hw, st.frames[f_a - st.f_lo:f_b - st.f_lo])
+            parts.append(staged_clip_logits(model, piece, transform, batch_clips, video_name))
         return torch.cat(parts, dim=0)
     if person:
         return _person_crop_logits(model, st, transform, batch_clips, video_name)
@@ -289,13 +220,11 @@ def _person_crop_logits(model, st: StagedVideo, transform: PersonCropTransform, 
     straight into the engine's packed input, and the forward -- no transformed intermediate, no gather, no torch kernel.
     Anything else (a session, a stub, no GPU): the torch ``PersonCropTransform`` clip by clip."""
     n = st.hi - st.lo
-    dev = _engine_device(model)
+    dev = staging.engine_device(model)
     if st.on_device and hasattr(model, 'packed_layout'):
         from .engine import preprocess_clips
-        cur = torch.cuda.current_stream(dev)
-        cur.wait_event(st.ready)
-        st.frames.record_stream(cur)
-        boxes = transform.box_rows(video_name, st.lo, st.hi).pin_memory().to(dev, non_blocking=True)
+        staging.wait_upload(st.frames, st.ready)
+        boxes = staging.upload_table(transform.box_rows(video_name, st.lo, st.hi), dev)
         frames = st.frames[:-1]           # (the staged zero frame of the centre-crop path: this kernel needs no pad frame)
         out = []
         for a in range(0, n, batch_clips):
@@ -324,15 +253,13 @@ def _staged_clips(model, st: StagedVideo, transform: TestTransform) -> Tuple[tor
     """Transformed frames of a staged clip range (each frame once), the [n_clips, 8] frame indices of its clips as a
     HOST tensor (the zero-padded tail points at one shared zero frame, the last of the buffer), and whether the frames
     are in the engine's packed device format (HIP transform) rather than float32 [n,3,224,224]."""
-    dev = _engine_device(model)
+    dev = staging.engine_device(model)
     hip_transform = st.on_device and isinstance(transform, TestTransform)
     if hip_transform:
         # HIP path: uint8 frames (+ one zero frame for the padded tail) -> fused resize/crop/normalise
         # kernel -> the engine's packed input format, consumed in place.
         from .engine import preprocess_frames
-        cur = torch.cuda.current_stream(dev)
-        cur.wait_event(st.ready)
-        st.frames.record_stream(cur)
+        staging.wait_upload(st.frames, st.ready)
         frames = preprocess_frames(st.frames, resize=transform.size, crop=transform.crop,
                                    scale_255=transform.scale_255, layout=model.packed_layout)
     else:
@@ -366,7 +293,7 @@ def _gather(frames: torch.Tensor, idx: torch.Tensor, st: Optional[StagedVideo], 
         return got.view((n, NUM_SEGMENTS) + tuple(frames.shape[1:]))
     sel = idx[a:b].reshape(-1)
     if frames.is_cuda:
-        sel = sel.pin_memory().to(frames.device, non_blocking=True)
+        sel = staging.upload_table(sel, frames.device)
     got = torch.index_select(frames, 0, sel) if out is None else torch.index_select(frames, 0, sel, out=out)
     return got.view((n, NUM_SEGMENTS) + tuple(frames.shape[1:]))
 
@@ -376,7 +303,7 @@ def _forward_clips(model, clips: torch.Tensor, hip_transform: bool) -> torch.Ten
     [b, num_class] (a device tensor on the engine paths: no host sync here)."""
     if hip_transform:
         return model.forward_device(clips.contiguous(), layout=model.packed_layout)
-    if _engine_device(model) is not None and hasattr(model, 'forward_device'):
+    if staging.engine_device(model) is not None and hasattr(model, 'forward_device'):
         return model.forward_device(clips.contiguous())
     name = model.get_inputs()[0].name
     return torch.from_numpy(np.asarray(model.run(None, {name: clips.cpu().numpy()})[0]))
@@ -395,8 +322,7 @@ def prefetch_staged(model, videos: Iterable[Tuple[object, torch.Tensor]],
                     ) -> Iterator[Tuple[object, StagedVideo]]:
     """Double buffering over a stream of ``(key, uint8 video)``: while the caller computes on video i, a
     worker thread reads / slices / pins video i+1 and copies it to the GPU on a side stream."""
-    dev = _engine_device(model)
-    side = torch.cuda.Stream(dev) if dev is not None and hasattr(model, 'packed_layout') else None
+    side = torch.cuda.Stream(staging.engine_device(model)) if staging.device_path(model) else None
 
     def work(item):
         key, vid = item
@@ -431,9 +357,8 @@ class prefetch_pieces:
 
     def __init__(self, model, videos: Iterable[Tuple[object, torch.Tensor]], piece_clips: int = PIECE_CLIPS,
                  depth: int = 3):
-        dev = _engine_device(model)
         self._model, self._videos, self._piece = model, videos, int(piece_clips)
-        self._side = torch.cuda.Stream(dev) if dev is not None and hasattr(model, 'packed_layout') else None
+        self._side = torch.cuda.Stream(staging.engine_device(model)) if staging.device_path(model) else None
         self._out: 'queue.Queue' = queue.Queue(maxsize=max(1, int(depth)))
         self._stop = threading.Event()
         self._worker = threading.Thread(target=self._produce, name='tsm-stage', daemon=True)
@@ -453,9 +378,7 @@ class prefetch_pieces:
             for key, vid in self._videos:
                 vid = vid() if callable(vid) else vid
                 n = len(clip_starts(int(vid.shape[0])))
-                per_frame = max(1, int(vid[0].numel())) if int(vid.shape[0]) else 1
-                fit = (MAX_STAGE_BYTES // per_frame - CLIP_SPAN // CLIP_STRIDE) // (CLIP_STEP // CLIP_STRIDE)
-                step = max(1, min(self._piece, fit))
+                step = max(1, min(self._piece, clips_per_piece(int(vid[0].numel()) if n else 1)))
                 if n == 0 and not self._put((key, stage_video(self._model, vid, (0, 0), self._side), True)):
                     return
                 for a in range(0, n, step):
@@ -502,10 +425,7 @@ def _gather_video_logits(model, local: torch.Tensor, total_frames: int) -> torch
     lo, hi = tdist.shard_range(n, world, rank)
     num_class = getattr(model, 'num_class', local.shape[1] if local.numel() else 0)
     local = local.reshape(hi - lo, num_class)
-    dev = _engine_device(model)
-    if dev is not None and tdist.on_rccl():
-        local = local.to(dev)
-    return tdist.gather_clip_logits(local, n).cpu()
+    return tdist.all_gather_host(local, staging.engine_device(model), n_total=n)
 
 
 def scores_dict(logits: torch.Tensor, total_frames: int) -> Dict[int, Dict[int, float]]:
@@ -532,8 +452,7 @@ def _inference_dataset_by_videos(model, items: list, out_dir: str, checkpoint: s
     per round of W videos the ranks exchange [frame count, clip count] and then the padded logits (two small
     all-gathers), and rank 0 writes the round's JSON files."""
     rank, world = tdist.world_info()
-    dev = _engine_device(model)
-    on_gpu = dev is not None and tdist.collective_enabled() and tdist.on_rccl()
+    dev = staging.engine_device(model)
     num_class = getattr(model, 'num_class', None)
     mine = items[rank::world]
     staged = prefetch_staged(model, ((it, (lambda p=it.video_path: reader(p))) for it in mine))
@@ -551,11 +470,9 @@ def _inference_dataset_by_videos(model, items: list, out_dir: str, checkpoint: s
         if not tdist.collective_enabled():
             _write_score_json(out_dir, item, checkpoint, local, st.total)
             continue
-        metas = tdist.all_gather_logits((meta.to(dev) if on_gpu else meta).reshape(1, 3)).cpu()
+        metas = tdist.all_gather_host(meta.reshape(1, 3), dev)
         per, ncls = int(metas[:, 1].max()), int(metas[:, 2].max())
-        pad = torch.zeros((per, ncls), dtype=torch.float32)
-        pad[:local.shape[0]] = local.reshape(local.shape[0], ncls) if local.numel() else pad[:0]
-        every = tdist.all_gather_logits(pad.to(dev) if on_gpu else pad).cpu().reshape(world, per, ncls)
+        every = tdist.gather_padded_host(local.reshape(local.shape[0], ncls), per, dev)
         if rank == 0:
             for r in range(min(world, len(items) - r0)):
                 _write_score_json(out_dir, items[r0 + r], checkpoint, every[r, :int(metas[r, 1])], int(metas[r, 0]))
@@ -717,7 +634,7 @@ def _inference_dataset_global(model, items: list, out_dir: str, checkpoint: str,
     rank, instead of after the last video); and a rank whose loop raises still enters the final exchange, with an error
     marker in the video table, so that the others raise too instead of blocking in an all-gather that never completes."""
     rank, world = tdist.world_info()
-    dev = _engine_device(model)
+    dev = staging.engine_device(model)
     plan_failure: Optional[BaseException] = None
     counts: List[int] = []
     owner: List[int] = []
@@ -734,7 +651,7 @@ def _inference_dataset_global(model, items: list, out_dir: str, checkpoint: str,
         # no rank is left blocked in it
         sig = torch.tensor([[zlib.crc32(repr((owner, counts)).encode()), len(items), 0 if plan_failure is None else 1]],
                            dtype=torch.int64)
-        sigs = tdist.all_gather_logits(sig.to(dev) if dev is not None and tdist.on_rccl() else sig).cpu()
+        sigs = tdist.all_gather_host(sig, dev)
         failed = [r for r in range(world) if int(sigs[r, 2]) != 0]
         if failed:
             if plan_failure is not None:
@@ -823,10 +740,9 @@ def _run_global(model, items: list, mine: List[int], counts: List[int], make_pie
             out[items[v].video_name] = local[pos:pos + n]
             pos += n
         return out
-    on_gpu = dev is not None and tdist.on_rccl()
     meta[:len(mine), 3] = num_class      # (a rank without videos does not know the class count: it rides in the table)
     meta[-1] = torch.tensor([0 if failure is None else 1, 0, 0, 0])
-    metas = tdist.all_gather_logits(meta.to(dev) if on_gpu else meta).cpu().reshape(world, len(items) + 1, 4)
+    metas = tdist.all_gather_host(meta, dev).reshape(world, len(items) + 1, 4)
     failed = [r for r in range(world) if int(metas[r, -1, 0]) != 0]
     if failed:       # every rank sees the same table: all of them stop here, none is left waiting in the logits all-gather
         if failure is not None:
@@ -835,9 +751,7 @@ def _run_global(model, items: list, mine: List[int], counts: List[int], make_pie
     metas = metas[:, :-1]
     per = max(1, int(metas[:, :, 2].clamp(min=0).sum(dim=1).max()))
     ncls = max(num_class, int(metas[:, :, 3].max()))
-    pad = torch.zeros((per, ncls), dtype=torch.float32)
-    pad[:local.shape[0]] = local.reshape(local.shape[0], ncls)
-    every = tdist.all_gather_logits(pad.to(dev) if on_gpu else pad).cpu().reshape(world, per, ncls)
+    every = tdist.gather_padded_host(local.reshape(local.shape[0], ncls), per, dev)
     # the exchange leaves every rank with the whole job's per-clip logits in dataset order (what the serial rep counter of
     # utils/eval.py needs); the score files are already on disk
     where = {}
@@ -953,31 +867,16 @@ def _image_geometry(model) -> Tuple[int, int]:
     return int(getattr(model, 'image_resize', 256)), int(getattr(model, 'image_crop', 224))
 
 
-def _is_image_engine(model) -> bool:
-    return _engine_device(model) is not None and hasattr(model, 'packed_layout')
-
-
 def _image_logits_device(model, frames_u8: torch.Tensor) -> torch.Tensor:
     """Engine path of one batch: pinned staging, ONE ``tsm_preprocess_image`` launch into the engine's packed layout, the
     forward; returns the CUDA logits [n, num_class] (nothing synchronised)."""
     from .engine import preprocess_image
     need_clip_rows(model, 'inference_images')
-    dev = _engine_device(model)
+    dev = staging.engine_device(model)
     resize, crop = _image_geometry(model)
     need_frame_engine(model, crop, 'image', 'create_image_model')
-    if frames_u8.is_cuda:
-        staged = frames_u8.contiguous()
-    else:
-        flat, slot = _pinned_pool.take(int(frames_u8.numel()))
-        ready = None
-        try:
-            pinned = flat.view(frames_u8.shape)
-            pinned.copy_(frames_u8)
-            staged = pinned.to(dev, non_blocking=True)
-            ready = torch.cuda.Event()
-            ready.record()
-        finally:
-            _pinned_pool.release(slot, ready)
+    staged = (frames_u8.contiguous() if frames_u8.is_cuda
+              else staging.upload(frames_u8.shape, lambda pinned: pinned.copy_(frames_u8), dev)[0])
     x = preprocess_image(staged, resize, crop, out_layout=model.packed_layout)
     n = x.shape[0]
     return model.forward_device(x.view((n, 1) + tuple(x.shape[1:])), layout=model.packed_layout)
@@ -991,10 +890,7 @@ def _image_scores_host(model, frames_u8: torch.Tensor, transform: ImageTransform
         name = model.get_inputs()[0].name
         return np.stack([np.asarray(model.run(None, {name: x[i:i + 1].numpy()})[0][0], dtype=np.float32)
                          for i in range(x.shape[0])])
-    with torch.no_grad():
-        p = next(iter(model.parameters()), None) if hasattr(model, 'parameters') else None
-        y = model(x.to(p.device) if p is not None else x)
-    return np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y, dtype=np.float32)
+    return staging.call_host_module(model, x)
 
 
 def inference_images(model, frames_u8) -> np.ndarray:
@@ -1003,7 +899,7 @@ def inference_images(model, frames_u8) -> np.ndarray:
     forward (``max_frames`` frames per engine call); any other model takes the CPU ``ImageTransform``.  The channel order is
     kept as given: the reference hands cv2's BGR frames to its transform as they are -- the caller's business."""
     frames = as_frames_u8(frames_u8)
-    if _is_image_engine(model):
+    if staging.device_path(model):
         return _image_logits_device(model, frames).cpu().numpy()
     resize, crop = _image_geometry(model)
     return _image_scores_host(model, frames, ImageTransform(resize, crop))
@@ -1038,7 +934,7 @@ def image_states(model, frames, batch_frames: Optional[int] = None,
     its ``max_clips``): pinned staging, one ``tsm_preprocess_image`` launch, the forward, one ``tsm_frame_votes`` launch with
     the history of the last 6 arg-maxes carried on the device; states -- and scores -- cross PCIe once, at the end.  Any other
     model takes the CPU ``ImageTransform`` and the host vote (``counting.vote_states``)."""
-    engine = _is_image_engine(model)
+    engine = staging.device_path(model)
     batch = int(batch_frames or (getattr(model, 'max_clips', 32) if engine else 32))
     if batch <= 0:
         raise ValueError(f'batch_frames must be positive, got {batch_frames}')

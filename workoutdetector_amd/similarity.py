@@ -23,6 +23,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import staging
 from .transform import TestTransform, as_frames_u8, need_frame_engine
 
 
@@ -42,10 +43,6 @@ def cosine_distances_host(feats) -> np.ndarray:
     return d
 
 
-def _is_engine(model) -> bool:
-    return hasattr(model, 'forward_features') and hasattr(model, 'packed_layout')
-
-
 def _geometry(model):
     return int(getattr(model, 'image_resize', 224)), int(getattr(model, 'image_crop', 224))
 
@@ -55,12 +52,12 @@ def _engine_rows(model, frames: torch.Tensor, normalize: bool, batch_frames: Opt
     from .engine import cosine_distances, preprocess_frames
     resize, crop = _geometry(model)
     need_frame_engine(model, crop, 'similarity', 'create_feature_model')
-    dev = torch.device('cuda', model.device)
+    dev = staging.engine_device(model)
     n = int(frames.shape[0])
     step = int(batch_frames) if batch_frames else model.max_clips
     if step <= 0:
         raise ValueError(f'batch_frames must be positive, got {batch_frames}')
-    staged = frames.contiguous() if frames.is_cuda else frames.contiguous().pin_memory().to(dev, non_blocking=True)   # once
+    staged = frames.contiguous() if frames.is_cuda else staging.upload_table(frames, dev)   # once
     feats = torch.empty((n, model.feature_dim), dtype=torch.float32, device=dev)
     mat = torch.empty((n, n), dtype=torch.float32, device=dev) if dist else None
     for lo in range(0, n, step):
@@ -78,12 +75,8 @@ def _host_features(model, frames: torch.Tensor, batch_frames: Optional[int]) -> 
     tf = TestTransform(resize, crop, scale_255=True)
     step = int(batch_frames) if batch_frames else 10          # (the reference's batch_size, utils/common.py:91)
     rows = []
-    with torch.no_grad():
-        for lo in range(0, frames.shape[0], step):
-            x = tf(frames[lo:lo + step].cpu().permute(0, 3, 1, 2))
-            p = next(iter(model.parameters()), None) if hasattr(model, 'parameters') else None
-            y = model(x.to(p.device) if p is not None else x)
-            rows.append(np.asarray(y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else y, dtype=np.float32))
+    for lo in range(0, frames.shape[0], step):
+        rows.append(staging.call_host_module(model, tf(frames[lo:lo + step].cpu().permute(0, 3, 1, 2))))
     return np.concatenate(rows).reshape(frames.shape[0], -1)
 
 
@@ -93,7 +86,7 @@ def video_features(model, frames_u8, normalize: bool = False, batch_frames: Opti
     returns a CUDA tensor (``batch_frames`` frames per forward, default the engine's ``max_clips``); any other model an
     ndarray."""
     frames = as_frames_u8(frames_u8)
-    if _is_engine(model):
+    if staging.device_path(model):
         return _engine_rows(model, frames, normalize, batch_frames, dist=False)[0]
     feats = _host_features(model, frames, batch_frames)
     if normalize:
@@ -109,6 +102,6 @@ def self_similarity(model, frames_u8, batch_frames: Optional[int] = None):
     float32 CUDA tensor, built band by band as the batches come off the engine; any other model a float64 ndarray
     (``cosine_distances_host``)."""
     frames = as_frames_u8(frames_u8)
-    if _is_engine(model):
+    if staging.device_path(model):
         return _engine_rows(model, frames, True, batch_frames, dist=True)[1]
     return cosine_distances_host(_host_features(model, frames, batch_frames))

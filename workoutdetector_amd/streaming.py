@@ -24,8 +24,9 @@ from typing import Callable, Deque, Dict, Hashable, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import staging
 from .counting import RepCounter, scores_to_preds
-from .inference_count import NUM_SEGMENTS, _engine_device, need_clip_rows
+from .inference_count import NUM_SEGMENTS, need_clip_rows
 from .transform import Box, PersonCropTransform, TestTransform, build_test_transform, person_box, window_descriptors
 
 
@@ -71,7 +72,7 @@ class StreamBatcher:
         # HIP path: every frame is copied into a page-locked [8,H,W,3] window buffer when it ARRIVES (push), so that a
         # complete window is one DMA away from the GPU when step() runs -- the 1.8-MB host gather of a 360x206 window
         # (~0.15 ms) leaves the window's critical path.  Buffers are recycled once their H2D copy has completed.
-        self._dev = _engine_device(model) if hasattr(model, 'packed_layout') else None
+        self._dev = staging.engine_device(model) if staging.device_path(model) else None
         # Page-locked memory is bounded: at most ``max_pinned_bytes`` in window buffers (a producer that runs ahead of
         # step(), or many resolutions, falls back to pageable windows beyond it -- slower upload, no hipHostMalloc on
         # the frame-arrival path, no unbounded pinning), at most ``max_free_per_shape`` idle buffers per frame size.
@@ -219,11 +220,7 @@ class StreamBatcher:
             self._inflight += [(done, w) for w in windows]
             table = window_descriptors([tuple(w.shape[1:]) for w in windows], offsets, crops if self.person_crop else None,
                                        resize=tf.size, crop=tf.crop)
-            # (page-locked staging from torch's caching host allocator: an upload from pageable memory would wait for the
-            #  batches already queued on the stream)
-            staged = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
-            staged.copy_(torch.from_numpy(table))
-            clips = preprocess_windows(arena, staged.to(dev, non_blocking=True), len(windows), NUM_SEGMENTS,
+            clips = preprocess_windows(arena, staging.upload_table(torch.from_numpy(table), dev), len(windows), NUM_SEGMENTS,
                                        person_crop=self.person_crop, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255,
                                        layout=self.model.packed_layout)
             return self.model.forward_device(clips, layout=self.model.packed_layout)

@@ -341,7 +341,7 @@ typedef struct tsm_conv_args {
   const float *w2;
   const float *gamma2, *beta2, *mean2, *var2;
   int32_t cin2, hi2, wi2, stride2;
-  int32_t code;            /* tile code as in tsm_conv_tiles (tile | 0x100 split-K | 0x200 tail split); 0 = heuristic.
+  int32_t code;            /* tile code as in tsm_conv_tiles (tile | 0x80 position-major 3x3 | 0x100 split-K | 0x200 tail split); 0 = heuristic.
                               A code that does not fit the launch falls back as in the engine: tsm_launch_trace shows what ran.
                               | 0x4000 (TSM_CONV_CODE_SEGMENTED, this entry point only; no tsm_conv_tiles code carries it): a
                               single fp32 source accumulates K in the engine's segments of ~16 K-steps, as its long-K layers do

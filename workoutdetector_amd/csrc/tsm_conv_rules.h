@@ -58,11 +58,20 @@ struct ConvParams {
   // Walk the output tiles from the last one to the first.  The engine alternates this between consecutive launches:
   // a kernel that starts with the rows its predecessor wrote LAST finds them in the 256-MB Infinity Cache / L2.
   int reverse;
+  // Position-major rows (segmented fp32 3x3 on 64x64 tiles, pos_major_valid below): GEMM row m' is output position m' / N of
+  // frame m' % N, so with N % 64 == 0 a 64-row tile holds ONE output position of 64 frames.  A tap that is padding for that
+  // position is padding for the whole tile and its K-steps are not issued at all: they would add +-0 to accumulators that
+  // start at +0 and are therefore never -0 (the folded weights are finite), so every bit stays what it is.  A request only:
+  // where pos_major_valid does not hold the launch runs in natural order (n, oy, ox).  y and the tail's reduction keep the
+  // natural layout [N, Ho, Wo, Cout]; the tail's segment sums (ypart) are in m' order.
+  int pos_major;
 };
 
 enum ConvPrec { kPrecF32 = 0, kPrecBf16x3 = 1, kPrecBf16 = 2 };
 // (conv_igemm's PREC template argument only: the block-placement arms, a ConvPrec | kPrecBlockShift -- tsm_igemm.hip)
 constexpr int kPrecBlockShift = 4;
+// (the same: the position-major arm of the segmented fp32 3x3, kPrecF32 | kPrecPosMajor)
+constexpr int kPrecPosMajor = 8;
 
 enum ConvTile {
   kTileAuto = 0, kTile128x128 = 1, kTile128x64 = 2, kTile64x64 = 3, kTile32x32 = 4,
@@ -460,6 +469,7 @@ struct ConvRoute {
   // shift, conv_igemm<.., false, false, PREC | kPrecBlockShift(, true)>, which adds the residual itself.  256 / 256p: their
   // <KS, SHIFT, RES, DUAL>.
   bool shift = false, res = false, dual = false, block_shift = false;
+  bool pos_major = false;   // kFamIgemmSeg only: the position-major arm, conv_igemm<64, 64, 2, 2, 3, .., kPrecF32 | kPrecPosMajor, false, true>
   int ntm = 0, ntn = 0;   // what the launcher puts into ConvParams (igemm families, 256 / 256p)
   long tiles = 0;         // output tiles (the segmented forms launch up to conv_num_segments workgroups for each)
   unsigned grid = 0;      // workgroups
@@ -493,6 +503,46 @@ inline bool conv_args_refused(const ConvParams &p, int ks) {
   // 32-bit byte offsets inside a workgroup's rebased window: a tile touches at most BM/(Ho*Wo) + 4 input frames.
   if ((128.0 / ((double)p.Ho * p.Wo) + 4.0) * (double)p.Hi * p.Wi * p.C * 4.0 > 2.0e9) return true;
   return (ks != 1 && ks != 3 && ks != 7) || (ks == 7 && p.res);
+}
+
+// ---- position-major rows (ConvParams::pos_major): what the kernel and the split reduction compute, callable on the CPU --------
+// GEMM row m of a position-major launch over n_frames frames: its frame and its output position.  m -> frame * HoWo + pos (the
+// row of y it is stored to) is a bijection of [0, n_frames * HoWo).
+TSM_HOST_DEVICE inline void pos_major_row(int m, int n_frames, int *frame, int *pos) {
+  *pos = m / n_frames;
+  *frame = m - *pos * n_frames;
+}
+// Bit ky * 3 + kx is set when tap (ky, kx) of output position `pos` reads inside the Hi x Wi frame; a clear bit is a tap of the
+// zero padding, for every frame alike.
+TSM_HOST_DEVICE inline unsigned pos_major_tap_mask(int pos, int Wo, int Hi, int Wi, int stride, int pad) {
+  const int oy = pos / Wo, ox = pos - oy * Wo;
+  const int iy0 = oy * stride - pad, ix0 = ox * stride - pad;
+  unsigned mask = 0;
+  for (int ky = 0; ky < 3; ++ky)
+    for (int kx = 0; kx < 3; ++kx)
+      if ((unsigned)(iy0 + ky) < (unsigned)Hi && (unsigned)(ix0 + kx) < (unsigned)Wi) mask |= 1u << (ky * 3 + kx);
+  return mask;
+}
+// The first K-step in [kt, nk) whose tap is set in `mask`, or nk when there is none.  K is ordered (ky, kx, c): tap t owns the
+// K-steps [t, t + 1) * steps_per_tap, steps_per_tap = C / 32, a power of two (ConvParams::logC4).
+TSM_HOST_DEVICE inline int next_live_kstep(int kt, unsigned mask, int steps_per_tap, int nk) {
+  if (kt < 0 || kt >= nk) return nk;
+  const int log_spt = __builtin_ctz((unsigned)steps_per_tap);
+  const int tap = kt >> log_spt;
+  const unsigned rest = tap < 9 ? (mask & 0x1ffu) >> tap : 0u;
+  if (rest & 1u) return kt;
+  if (rest == 0u) return nk;
+  const int next = (tap + __builtin_ctz(rest)) << log_spt;
+  return next < nk ? next : nk;
+}
+// May this launch run position-major?  Everything the arm assumes: one output position per 64-row tile and no row past M
+// (N % 64 == 0), whole taps per K-step, y and all N input frames inside one buffer descriptor (2 GB).
+inline bool pos_major_valid(const ConvParams &p, int ks) {
+  return p.prec == kPrecF32 && ks == 3 && p.pad == 1 && (p.stride == 1 || p.stride == 2) && p.kseg_len > 0 && p.T == 0 &&
+         !p.res && !p.x2 && (p.tile == kTile64x64 || p.tile == kTileAuto) && (p.ksplit == 0 || p.ksplit == 2) &&
+         p.N > 0 && p.N % 64 == 0 && p.Ho > 0 && p.Wo > 0 && (int64_t)p.N * p.Ho * p.Wo == p.M &&
+         p.C >= kBK && (p.C & (p.C - 1)) == 0 && p.Kp == (int64_t)9 * p.C &&
+         (double)p.N * p.Hi * p.Wi * p.C * 4.0 < 2.0e9 && (double)p.M * p.Cout * 4.0 < 2.0e9;
 }
 
 // ks in {1, 3, 7}; n_cu sizes the persistent grids (read by the 256p and weight-stationary families only).  A grid past 2^31 - 1
@@ -548,6 +598,7 @@ inline ConvRoute conv_route(const ConvParams &p, int ks, int n_cu) {
     if (r.res || ks == 7 || (r.shift && ks == 3)) return refused;
     if (p.ksplit == 2 && (p.tail_from <= 0 || p.tail_from >= r.tiles || p.tail_from % r.ntn != 0)) return refused;
     r.family = kFamIgemmSeg;
+    r.pos_major = p.pos_major != 0 && r.bm == 64 && pos_major_valid(p, ks);   // (anything else: natural order, the same bits)
     grid = p.ksplit == 2 ? p.tail_from + (r.tiles - p.tail_from) * conv_num_segments(p) : r.tiles * (p.ksplit ? conv_num_segments(p) : 1);
   } else {
     r.family = kFamIgemm;

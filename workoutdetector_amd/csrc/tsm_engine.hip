@@ -193,6 +193,7 @@ struct tsm_engine {
   int fuse_block = -1;   // TSM_FUSE_BLOCK: the same for the whole-Bottleneck kernel (bf16, layer1.1 / layer1.2)
   int fuse31 = -1;       // TSM_FUSE_C3C1: the same for conv3 of block b + shift + conv1 of block b + 1 as one launch (bf16, layer2)
   int fuse_front = -1;   // TSM_FUSE_FRONT: the same for shift + conv1 + the stride-2 conv2 of layer2.0 as one launch (bf16)
+  bool pos_major = true; // TSM_POS_MAJOR=0: the tuner does not offer the position-major 3x3 codes (kCodePosMajor); for the A/B
   int walk = -1;         // TSM_WALK: 0 / 1 every tile-walking launch walks forward / in reverse; unset: alternate (Forward::next_dir)
   int n_cu = 256;
   int timing_left = 0;
@@ -464,6 +465,11 @@ bool tail_split_from(const tsm::ConvParams &p, int n_cu, size_t partial_elems, i
 // `partial` holds `partial_elems` floats of segment sums (the engine's split-K scratch; the per-op entry point's own).
 hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial, size_t partial_elems, int n_cu, hipStream_t s) {
   p.tile = code & kCodeTileMask;
+  // kCodePosMajor: position-major rows, honoured only where pos_major_valid holds for THIS launch (whole-K or with the tail
+  // split; never with kCodeSplitK); anywhere else the bit is ignored and the natural order runs (same bits).
+  const bool pos_major = (code & kCodePosMajor) && !(code & kCodeSplitK) && (code & kCodeTileMask) == tsm::kTile64x64 &&
+                         tsm::pos_major_valid(p, ks);
+  p.pos_major = pos_major ? 1 : 0;
   // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
   // EVERY launch (falling back to the whole-K form, which gives the same bits).
   if ((code & kCodeSplitK) && p.kseg_len > 0 &&
@@ -488,7 +494,10 @@ hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial,
       p.tail_from = tail_from;
       p.ypart = partial;
       hipError_t st = tsm::launch_conv(p, ks, s);
-      if (st == hipSuccess)
+      if (st == hipSuccess && pos_major)   // (the tail's rows are GEMM rows mt0 .. M - 1: the last positions of every frame)
+        st = tsm::launch_splitk_reduce_pos(partial, tsm::conv_num_segments(p), mt0, p.M - mt0, p.N, p.Ho * p.Wo, p.Cout, p.bias, y,
+                                           p.relu, s);
+      else if (st == hipSuccess)
         st = tsm::launch_splitk_reduce(partial, tsm::conv_num_segments(p), p.M - mt0, p.Cout, p.bias, nullptr,
                                        y + (size_t)mt0 * p.Cout, p.relu, s);
       return st;
@@ -755,7 +764,15 @@ int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
       if (need <= e->partial_elems && tiles64 < 4L * e->n_cu) cands.push_back(t | kCodeSplitK);
     }
     int tail_from = 0;
-    if (tail_split_from(p, e->n_cu, e->partial_elems, &tail_from)) cands.push_back((int)tsm::kTile64x64 | kCodeTailK);
+    const bool tail = tail_split_from(p, e->n_cu, e->partial_elems, &tail_from);
+    if (tail) cands.push_back((int)tsm::kTile64x64 | kCodeTailK);
+    // position-major rows (3x3 layers of whole 64-frame batches): the padding taps' MFMAs are not issued
+    tsm::ConvParams q = p;
+    q.tile = tsm::kTile64x64;
+    if (e->pos_major && tsm::pos_major_valid(q, ks)) {
+      cands.push_back((int)tsm::kTile64x64 | kCodePosMajor);
+      if (tail) cands.push_back((int)tsm::kTile64x64 | kCodePosMajor | kCodeTailK);
+    }
   } else {
     for (int t = 1; t < tsm::kNumTiles; ++t)
       if (tsm::conv_tile_valid(p, t, e->n_cu)) cands.push_back(t);
@@ -1240,6 +1257,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   env_read("TSM_STEM_PLANAR", &e->stem_planar, on);
   env_read("TSM_CONV_TILE", &e->force_tile, tsm::conv_tile_from_name);
   env_read("TSM_CONV_CODE", &e->force_code, atoi);
+  env_read("TSM_POS_MAJOR", &e->pos_major, on);
   env_read("TSM_FUSE_CONV23", &e->fuse23, on);
   env_read("TSM_FUSE_BLOCK", &e->fuse_block, on);
   env_read("TSM_FUSE_C3C1", &e->fuse31, on);

@@ -524,6 +524,7 @@ inline void pack_w3_fragments_split(const float *w3p, int cmid, std::vector<floa
 // code of the first conv they replace and say that the fused form was chosen; it runs only where it can (tsm_engine.hip,
 // plan_forward).
 constexpr int kCodeTileMask = 0xF;     // the ConvTile
+constexpr int kCodePosMajor = 0x80;    // position-major rows of a segmented fp32 3x3 on 64x64 tiles (ConvParams::pos_major), alone or with kCodeTailK
 constexpr int kCodeSplitK = 0x100;     // split-K form of a segmented fp32 layer
 constexpr int kCodeTailK = 0x200;      // tail split of a segmented 64x64 layer (ConvParams::ksplit = 2)
 constexpr int kCodeConv23 = 0x400;     // on conv2: conv2 + conv3 + residual as one launch
@@ -531,7 +532,7 @@ constexpr int kCodeBlock = 0x800;      // on conv1: the whole Bottleneck as one 
 constexpr int kCodeConv31 = 0x1000;    // on conv3: conv3 + the next block's shift + conv1 as one launch
 constexpr int kCodeFront = 0x2000;     // on conv1: shift + conv1 + the block's stride-2 conv2 as one launch
 constexpr int kCodeFused = kCodeConv23 | kCodeBlock | kCodeConv31 | kCodeFront;
-constexpr int kCodeValid = kCodeTileMask | kCodeSplitK | kCodeTailK | kCodeFused;   // every bit a code may carry
+constexpr int kCodeValid = kCodeTileMask | kCodePosMajor | kCodeSplitK | kCodeTailK | kCodeFused;   // every bit a code may carry
 static_assert((kCodeOpSegmented & kCodeValid) == 0, "the per-op segmented bit must stay clear of the engine's code bits");
 
 // One line of a TSM_TUNE_CACHE file: "<signature>|<bucket>|c0,c1,...".  Succeeds only when the line starts with

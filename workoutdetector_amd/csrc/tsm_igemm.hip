@@ -57,13 +57,22 @@ namespace tsm {
 // gets the A loader's per-chunk frame choice, p.fold = C2 / shift_div; the first source stays unshifted).  p.T > 0 selects
 // it at launch.  Instantiated as PREC | kPrecBlockShift with SHIFT = RES = false (DUAL = false: the shifted residual), so that
 // every other instantiation keeps its name and its code.
+//
+// POSM (position-major rows, ConvParams::pos_major): the segmented fp32 3x3 on 64x64 tiles with GEMM row m' = output position
+// m' / N of frame m' % N.  N % 64 == 0 (pos_major_valid), so a tile is ONE output position of 64 frames: the padding mask is a
+// wave-uniform scalar, the per-row mask registers and the per-load select go, and the K loop walks the live taps' K-steps only
+// (next_live_kstep) -- a padding tap's MFMAs would add +-0 to accumulators that are never -0.  Instantiated as PREC |
+// kPrecPosMajor on <64, 64, 2, 2, 3, false, false, .., false, true> alone, like BSHIFT, for the same reason.
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT, bool RES, int PREC, bool DUAL = false, bool SEG = false>
 // (second launch-bounds argument = minimum waves per SIMD: the SEG 64x64 kernel needs 16 registers more than the
 // plain one and would drop from 5 to 4 workgroups per CU; asking for 5 costs 1-2 spills outside the K loop)
 __global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? ((PREC & kPrecBlockShift) ? 4 : 5) : 1)
 conv_igemm(const ConvParams p) {
   constexpr bool BSHIFT = (PREC & kPrecBlockShift) != 0;
-  constexpr int PMODE = PREC & ~kPrecBlockShift;   // the arithmetic (ConvPrec)
+  constexpr bool POSM = (PREC & kPrecPosMajor) != 0;
+  constexpr int PMODE = PREC & ~(kPrecBlockShift | kPrecPosMajor);   // the arithmetic (ConvPrec)
+  static_assert(!POSM || (SEG && KS == 3 && BM == 64 && BN == 64 && !SHIFT && !RES && !DUAL && !BSHIFT && PMODE == kPrecF32),
+                "position-major rows: the segmented fp32 3x3 on 64x64 tiles only (pos_major_valid)");
   static_assert(!BSHIFT || (!SHIFT && !RES), "block placement: a shifted identity (DUAL = false) or a shifted second source");
   constexpr bool RESID = RES || (BSHIFT && !DUAL);   // a residual is added (block placement: through the shift)
   static_assert(!SEG || (PMODE == kPrecF32 && !RES && WGM * WGN <= 4 && BM == BN && BM <= 64),
@@ -125,7 +134,7 @@ conv_igemm(const ConvParams p) {
 
   // ---- descriptors, rebased to this workgroup's first input frame / first weight row ------------
   const int HoWo = p.Ho * p.Wo;
-  const int n_first = m0 / HoWo;
+  const int n_first = POSM ? 0 : m0 / HoWo;   // (position-major: a tile's rows are 64 frames anywhere in the batch)
   const int frame0 = SHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
   // bf16-format stem: the input is stored as pixel PAIRS (8-element groups = 2 pixels x 4 channels, odd
   // widths padded with a zero pixel), so a frame is Hi x ceil(Wi/2) groups.
@@ -154,17 +163,24 @@ conv_igemm(const ConvParams p) {
   const int frame_bytes = (int)(frame_elems * EB);
   unsigned a_off[APASS];                       // byte offset of (row, tap 0, this thread's chunk)
   unsigned a_offp[SHIFT ? APASS : 1], a_offm[SHIFT ? APASS : 1];
-  unsigned a_mask[KS == 3 ? APASS : 1];
+  unsigned a_mask[(KS == 3 && !POSM) ? APASS : 1];
+  // POSM: the tile's output position, its first frame and its live taps, all wave-uniform
+  int pm_pos = 0, pm_n0 = 0;
+  unsigned pm_live = 0x1ffu;
+  if constexpr (POSM) {
+    pos_major_row(m0, p.N, &pm_n0, &pm_pos);
+    pm_live = pos_major_tap_mask(pm_pos, p.Wo, p.Hi, p.Wi, p.stride, p.pad);
+  }
   unsigned a_off2[DUAL ? APASS : 1];
   unsigned a_off2p[(BSHIFT && DUAL) ? APASS : 1], a_off2m[(BSHIFT && DUAL) ? APASS : 1];
   int a_iy[KS == 7 ? APASS : 1], a_ix[KS == 7 ? APASS : 1];
 #pragma unroll
   for (int pp = 0; pp < APASS; ++pp) {
     const int m = m0 + lrow + LRP * pp;
-    const bool ok = m < p.M;
+    const bool ok = POSM || m < p.M;   // (position-major: M % 64 == 0)
     const int mm = ok ? m : m0;
-    const int n = mm / HoWo;
-    const int rem = mm - n * HoWo;
+    const int n = POSM ? pm_n0 + lrow + LRP * pp : mm / HoWo;
+    const int rem = POSM ? pm_pos : mm - n * HoWo;
     const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
     const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
     if (KS == 7) {
@@ -185,7 +201,7 @@ conv_igemm(const ConvParams p) {
         a_off2p[pp] = (ok && t < p.T - 1) ? a_off2[pp] + (unsigned)(frame_elems2 * EB) : kInvalid;
         a_off2m[pp] = (ok && t > 0) ? a_off2[pp] - (unsigned)(frame_elems2 * EB) : kInvalid;
       }
-      if (KS == 3) {
+      if (KS == 3 && !POSM) {
         unsigned mask = 0;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
@@ -276,6 +292,8 @@ conv_igemm(const ConvParams p) {
           const unsigned off = (a_offp[pp] & k.mp) | (a_offm[pp] & k.mm) | (a_off[pp] & k.m0);
           const bool ok = ((a_mask[pp] >> k.tap) & 1u) && off != kInvalid;
           ra[pp] = buf_load4(rsrcA, (ok ? off + (unsigned)k.tap_off : kInvalid) | k.dead, 0);
+        } else if (POSM) {   // only live taps are walked
+          ra[pp] = buf_load4(rsrcA, (a_off[pp] + (unsigned)k.tap_off) | k.dead, 0);
         } else {
           ra[pp] = buf_load4(rsrcA, (((a_mask[pp] >> k.tap) & 1u) ? a_off[pp] + (unsigned)k.tap_off : kInvalid) | k.dead, 0);
         }
@@ -537,15 +555,19 @@ conv_igemm(const ConvParams p) {
   // out of the inner loop on purpose: inside it the compiler if-converts the flush and drains the MFMA chain on
   // every K-step).  Without SEG there is a single pass over [kt0, nk).
   const int seg_len = (SEG && p.kseg_len > 0) ? p.kseg_len : 0x3fffffff;
+  // POSM: the K-steps walked are the live taps' (pm_first, then next_live_kstep from one to the next; nk = none left, a dead step)
+  const int pm_spt = POSM ? p.C / KC : 1;
+  const int pm_first = POSM ? next_live_kstep(kt0, pm_live, pm_spt, nk) : kt0;
+  const int pm_second = POSM ? next_live_kstep(pm_first + 1, pm_live, pm_spt, nk) : kt0 + 1;
   {
-    const KStep k0 = kstep(kt0, nk);
+    const KStep k0 = kstep(pm_first, nk);
 #pragma unroll
-    for (int it = 0; it < NITEMS; ++it) gload_item(k0, kt0, it);
+    for (int it = 0; it < NITEMS; ++it) gload_item(k0, pm_first, it);
 #pragma unroll
     for (int it = 0; it < NITEMS; ++it) lstore_item(0, it);
-    const KStep k1 = kstep(kt0 + 1, nk);
+    const KStep k1 = kstep(pm_second, nk);
 #pragma unroll
-    for (int it = 0; it < NITEMS; ++it) gload_item(k1, kt0 + 1, it);
+    for (int it = 0; it < NITEMS; ++it) gload_item(k1, pm_second, it);
   }
   __syncthreads();
   if constexpr (BF) {
@@ -580,6 +602,51 @@ conv_igemm(const ConvParams p) {
     // 4 k only: it runs as a 4-MFMA tail instead of 16 (the 12 skipped MFMAs multiply zeros; same bits).
     const bool trim = KS == 7 && p.Kp == 224 && nk == 7;
     const int nk_full = trim ? nk - 1 : nk;
+    if constexpr (POSM) {
+      // The loop below over the live steps only: kt is the step in LDS, kt1 the one in the loader registers, kt2 the one whose
+      // loads are injected.  A segment ends at its boundary in absolute K-steps, so the segment sums and their order are the
+      // natural arm's; a segment without a live step is never entered (its flush would add +0).  The step's body is the
+      // natural loop's, word for word (a lambda shared by both moved other instantiations' registers).
+      int kt = pm_first, kt1 = pm_second;
+      while (kt < nk) {
+        const int bound = (kt / seg_len + 1) * seg_len, kend = bound < nk ? bound : nk;
+        while (kt < kend) {
+          const int kt2 = next_live_kstep(kt1 + 1, pm_live, pm_spt, nk);
+          const KStep k2 = kstep(kt2, nk);
+          {
+            const float *As = smem + (wm * WTM + l31) * kLds + half * 4;
+            const float *Bs = smem + BM * kLds + (wn * WTN + l31) * kLds + half * 4;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+              ra_[kk] = *reinterpret_cast<const f32x4 *>(As + kk * 8);
+              rb_[kk] = *reinterpret_cast<const f32x4 *>(Bs + kk * 8);
+            }
+          }
+          __syncthreads();  // every wave holds its fragments: the buffer may be overwritten
+          int cnt = 0;
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+              acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ra_[kk][s4], rb_[kk][s4], acc[0][0], 0, 0, 0);
+              ++cnt;
+              // 2*NITEMS loader items over the first 12 MFMAs: the ds_writes of tile kt+1, then the loads of kt+2
+              const int done = cnt < 12 ? (cnt * 2 * NITEMS) / 12 : 2 * NITEMS;
+              const int before = cnt - 1 < 12 ? ((cnt - 1) * 2 * NITEMS) / 12 : 2 * NITEMS;
+#pragma unroll
+              for (int it = before; it < done; ++it) {
+                if (it < NITEMS) lstore_item(0, it);
+                else gload_item(k2, kt2, it - NITEMS);
+                __builtin_amdgcn_sched_barrier(0);
+              }
+            }
+          __syncthreads();  // tile kt+1 is complete in LDS
+          kt = kt1;
+          kt1 = kt2;
+        }
+        seg_flush();
+      }
+    } else {
     for (int kt = kt0; kt < nk_full;) {
     const int kend = (SEG && kt + seg_len < nk_full) ? kt + seg_len : nk_full;
     for (; kt < kend; ++kt) {
@@ -614,6 +681,7 @@ conv_igemm(const ConvParams p) {
       __syncthreads();  // tile kt+1 is complete in LDS
     }
     seg_flush();
+    }
     }
     if (KS == 7 && trim) {
       const f32x4 a0 = *reinterpret_cast<const f32x4 *>(smem + (wm * WTM + l31) * kLds + half * 4);
@@ -686,9 +754,12 @@ conv_igemm(const ConvParams p) {
   // Stores go through a descriptor that ends at row M: rows past the end are dropped by the range
   // check, which keeps the epilogue branch-free (no per-pass wait on earlier stores).
   const bool partial = split_wg;  // raw segment sums to y = partial[seg][M][Cout] (tail split: ypart = partial[seg][tail rows][Cout]): no bias, no ReLU
-  const size_t y_bytes = ((size_t)p.M - m0) * p.Cout * EB;
+  // POSM: a whole tile's row rr is frame pm_n0 + rr at position pm_pos, row (pm_n0 + rr) * HoWo + pm_pos of y (the descriptor
+  // starts at p.y and spans it); a tail piece writes ypart in m' order like any other (the reduction maps its rows)
+  const bool y_scatter = POSM && !in_tail;
+  const size_t y_bytes = ((size_t)p.M - (y_scatter ? 0 : m0)) * p.Cout * EB;
   const int mt0 = in_tail ? (p.tail_from / p.ntn) * BM : 0;   // first row of the tail
-  char *ybase = in_tail ? reinterpret_cast<char *>(p.ypart) + ((size_t)seg * (p.M - mt0) + (m0 - mt0)) * p.Cout * EB
+  char *ybase = y_scatter ? reinterpret_cast<char *>(p.y) : in_tail ? reinterpret_cast<char *>(p.ypart) + ((size_t)seg * (p.M - mt0) + (m0 - mt0)) * p.Cout * EB
                         : reinterpret_cast<char *>(p.y) + ((size_t)(partial ? seg : 0) * p.M + m0) * p.Cout * EB;
   const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
       ybase, 0, (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
@@ -725,8 +796,9 @@ conv_igemm(const ConvParams p) {
       v[1] = fmaxf(v[1], floor_);
       v[2] = fmaxf(v[2], floor_);
       v[3] = fmaxf(v[3], floor_);
+      const int yr = y_scatter ? (pm_n0 + rr) * HoWo + pm_pos : rr;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcY,
-                                             (int)((rr * p.Cout + n0 + ecol) * 4), 0, 0);
+                                             (int)((yr * p.Cout + n0 + ecol) * 4), 0, 0);
     }
   } else {
     const f32x4 bias0 = *reinterpret_cast<const f32x4 *>(p.bias + n0 + ecol);
@@ -788,6 +860,12 @@ static hipError_t launch_conv_seg(const ConvParams &p, const ConvRoute &r, hipSt
       if (r.dual) {   // (block_shift: block placement, the downsample operand through the shift)
         if (r.block_shift) TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32 | kPrecBlockShift, true, true>), grid, block, 0, s, p);
         else TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<BM, BN, WGM, WGN, 1, false, false, kPrecF32, true, true>), grid, block, 0, s, p);
+        return hipGetLastError();
+      }
+    }
+    if constexpr (BM == 64 && WGM == 2 && KS == 3 && !SHIFT) {
+      if (r.pos_major) {   // position-major rows (ConvParams::pos_major where pos_major_valid holds)
+        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 64, 2, 2, 3, false, false, kPrecF32 | kPrecPosMajor, false, true>), grid, block, 0, s, p);
         return hipGetLastError();
       }
     }
@@ -864,6 +942,41 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float *__restr
   }
 }
 
+
+// The same for the tail of a position-major launch (ConvParams::pos_major): row i of the segment sums is GEMM row m_first + i,
+// frame m' % n_frames at position m' / n_frames, and goes to row frame * howo + position of y (y: the whole output).
+__global__ void __launch_bounds__(256) splitk_reduce_pos_kernel(const float *__restrict__ partial, int n_seg, int64_t n4,
+                                                                int64_t seg_stride4, int cout4, int m_first, int n_frames,
+                                                                int howo, const float *__restrict__ bias,
+                                                                float *__restrict__ y, int relu) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const float floor_ = relu ? 0.f : -INFINITY;
+  const f32x4 *p4 = reinterpret_cast<const f32x4 *>(partial);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 t = p4[i];
+    for (int sgm = 1; sgm < n_seg; ++sgm) t += p4[i + sgm * seg_stride4];
+    const int row = (int)(i / cout4), c4 = (int)(i - (int64_t)row * cout4);
+    int frame, pos;
+    pos_major_row(m_first + row, n_frames, &frame, &pos);
+    f32x4 v = t + reinterpret_cast<const f32x4 *>(bias)[c4];
+    v[0] = fmaxf(v[0], floor_);
+    v[1] = fmaxf(v[1], floor_);
+    v[2] = fmaxf(v[2], floor_);
+    v[3] = fmaxf(v[3], floor_);
+    reinterpret_cast<f32x4 *>(y)[((int64_t)frame * howo + pos) * cout4 + c4] = v;
+  }
+}
+
+hipError_t launch_splitk_reduce_pos(const float *partial, int n_seg, int64_t m_first, int64_t m, int n_frames, int howo, int cout,
+                                    const float *bias, float *y, int relu, hipStream_t s) {
+  if (!partial || !bias || !y || n_seg < 1 || m_first < 0 || m <= 0 || n_frames <= 0 || howo <= 0 || cout <= 0 || cout % 4 != 0 ||
+      m_first + m != (int64_t)n_frames * howo || (m_first + m) * cout >= ((int64_t)1 << 31))
+    return hipErrorInvalidValue;
+  const int64_t n4 = m * cout / 4;
+  TSM_KLAUNCH(splitk_reduce_pos_kernel, dim3(grid_for(n4, 2048)), dim3(256), 0, s, partial, n_seg, n4, n4, cout / 4, (int)m_first,
+                     n_frames, howo, bias, y, relu);
+  return hipGetLastError();
+}
 
 hipError_t launch_splitk_reduce(const float *partial, int n_seg, int64_t m, int cout, const float *bias,
                                 const float *res, float *y, int relu, hipStream_t s) {

@@ -31,6 +31,10 @@ hipError_t launch_stem_pool(const float *x, const float *w, const float *bias, f
 // y = act(((p[0] + p[1]) + ...) + bias (+ res)) over fp32 partial tiles [n_seg][M*Cout] written by a ksplit launch.
 hipError_t launch_splitk_reduce(const float *partial, int n_seg, int64_t m, int cout, const float *bias,
                                 const float *res, float *y, int relu, hipStream_t s);
+// The tail of a position-major launch (ConvParams::pos_major): partial is [n_seg][m rows][cout] for the GEMM rows m_first ..
+// m_first + m - 1 = n_frames * howo - 1; row m' goes to row (m' % n_frames) * howo + m' / n_frames of y, the WHOLE output.
+hipError_t launch_splitk_reduce_pos(const float *partial, int n_seg, int64_t m_first, int64_t m, int n_frames, int howo, int cout,
+                                    const float *bias, float *y, int relu, hipStream_t s);
 
 // prec == kPrecF32: dst is NHWC4 fp32; bf16 formats: one 8-element group per pixel PAIR (rows of ceil(w/2) groups).
 hipError_t launch_pack_input(const float *src, float *dst, int64_t n_frames, int h, int w,

@@ -4,6 +4,140 @@
 namespace tsm {
 
 // ---------------------------------------------------------------------------------------------
+// The operand loader of both kernels: the state of one 256 x 256 tile and the LDS-DMA that stages its K-tiles.
+//
+// A K-tile (64 channels of 256 A rows and 256 B rows) is staged as four 16-KB half-operands, {A, B} x {channels 0-31,
+// 32-63}: 256 rows x 64 B each.  A wave-instruction of `buffer_load ... lds` writes 1 KiB = 16 rows x 64 B, and a wave
+// stages two such pieces per half-operand: lane l fills LDS slot (row, l & 3) of rows piece * 16 + (l >> 2), piece =
+// 2 * wave + q.  The 16-byte chunk a slot holds is XOR-swizzled on the SOURCE side, chunk = (l & 3) ^ f(row) with
+// f(row) = (row >> 2) & 3 = (l >> 4) & 3, and the kernels' fragment reads apply the same involution.  What a lane needs
+// per tile is therefore two byte offsets per operand (+ the frames t +- 1 of a shifted source, + the valid-tap mask of a
+// 3x3), relative to windows that start at the tile's first frame / weight row: 32-bit offsets whatever the batch.
+// ---------------------------------------------------------------------------------------------
+template <int KS, bool SHIFT, bool DUAL, bool SHIFT2 = false> struct Tile256State {
+  unsigned a_off[2], b_off[2];
+  unsigned a_mask[KS == 3 ? 2 : 1];
+  unsigned a_offp[SHIFT ? 2 : 1], a_offm[SHIFT ? 2 : 1];
+  unsigned a_off2[DUAL ? 2 : 1];
+  unsigned a_off2p[SHIFT2 ? 2 : 1], a_off2m[SHIFT2 ? 2 : 1];   // block placement: x2's frames t+1 / t-1
+  int m0, n0;
+  // (the operand windows as plain pointers + sizes: the host pass cannot hold __amdgpu_buffer_rsrc_t in a struct; the
+  //  descriptors are rebuilt where they are used -- scalar moves)
+  const char *pa, *pb, *pa2;
+  int sza, sza2;
+};
+
+// What a kernel computes once and the loader reads per tile / per stage
+struct Tile256Launch {
+  int HoWo, frame_bytes, frame_bytes2;   // output pixels per frame; bytes per frame of x and (DUAL) of x2
+  int nt1;                               // DUAL: K-tiles of the first source
+  int wave, lane, chunk;                 // chunk: the global 16-B chunk held by this lane's LDS slot
+};
+
+// The loader state of output tile `tile` (row-major over ntm x ntn).  SHIFT: the A loader's temporal shift (conv1); DUAL:
+// the K-concatenated second source x2 (conv3 + downsample as one GEMM, K = [conv3 input channels | block input channels]);
+// SHIFT2: x2 read through the shift (block placement).
+template <int KS, bool SHIFT, bool DUAL, bool SHIFT2>
+__device__ __forceinline__ void tile256_setup(Tile256State<KS, SHIFT, DUAL, SHIFT2> &T, const ConvParams &p, const Tile256Launch &L, int tile) {
+  const int tm = tile / p.ntn, tn = tile - tm * p.ntn;
+  T.m0 = tm * 256;
+  T.n0 = tn * 256;
+  const int n_first = T.m0 / L.HoWo;
+  const int frame0 = SHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
+  const size_t a_bytes = ((size_t)p.N - frame0) * (size_t)L.frame_bytes;
+  T.pa = reinterpret_cast<const char *>(p.x) + (size_t)frame0 * L.frame_bytes;
+  T.sza = window_bytes(a_bytes);
+  T.pb = reinterpret_cast<const char *>(p.w) + (size_t)T.n0 * p.Kp * 2;
+  const int frame02 = (SHIFT2 && n_first > 0) ? n_first - 1 : n_first;
+  const size_t a2_bytes = DUAL ? ((size_t)p.N - frame02) * (size_t)L.frame_bytes2 : 0;
+  T.pa2 = reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * L.frame_bytes2;
+  T.sza2 = window_bytes(a2_bytes);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int row = (2 * L.wave + q) * 16 + (L.lane >> 2);
+    const int m = T.m0 + row;
+    const bool ok = m < p.M;
+    const int mm = ok ? m : T.m0;
+    const int n = mm / L.HoWo, rem = mm - n * L.HoWo;
+    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+    const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
+    const int base = (n - frame0) * L.frame_bytes + (iy0 * p.Wi + ix0) * p.C * 2 + L.chunk * 16;
+    T.a_off[q] = (KS == 1 && !ok) ? kInvalid : (unsigned)base;
+    if (KS == 3) {
+      unsigned mask = 0;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+          if ((unsigned)(iy0 + ky) < (unsigned)p.Hi && (unsigned)(ix0 + kx) < (unsigned)p.Wi) mask |= 1u << (ky * 3 + kx);
+      T.a_mask[q] = ok ? mask : 0u;
+    }
+    if (SHIFT) {
+      const int t = n % p.T;
+      T.a_offp[q] = (ok && t < p.T - 1) ? (unsigned)(base + L.frame_bytes) : kInvalid;
+      T.a_offm[q] = (ok && t > 0) ? (unsigned)(base - L.frame_bytes) : kInvalid;
+    }
+    if (DUAL)
+      T.a_off2[q] = ok ? (unsigned)((n - frame02) * L.frame_bytes2 + (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * 2 + L.chunk * 16)
+                       : kInvalid;
+    if (SHIFT2) {
+      const int t = n % p.T;
+      T.a_off2p[q] = (ok && t < p.T - 1) ? T.a_off2[q] + (unsigned)L.frame_bytes2 : kInvalid;
+      T.a_off2m[q] = (ok && t > 0) ? T.a_off2[q] - (unsigned)L.frame_bytes2 : kInvalid;
+    }
+    T.b_off[q] = (unsigned)(row * p.Kp * 2 + L.chunk * 16);
+  }
+}
+
+// Stage one half-operand of K-tile kt of the tile with state T into operand buffer `par` (0 / 1) of `lds`: which = 0 A k0-31,
+// 1 B k0-31, 2 A k32-63, 3 B k32-63 (two 1-KiB pieces per wave); dead = kInvalid: zeros, no memory traffic
+template <int KS, bool SHIFT, bool DUAL, bool SHIFT2>
+__device__ __forceinline__ void tile256_stage(unsigned char *lds, const Tile256State<KS, SHIFT, DUAL, SHIFT2> &T, const ConvParams &p,
+                                              const Tile256Launch &L, int kt, unsigned par, int which, unsigned dead) {
+  typedef __attribute__((address_space(3))) void lds_void;
+  const int kh = which >> 1;
+  const unsigned kbytes = (unsigned)kt * 128u + (unsigned)kh * 64u;
+  unsigned char *dst = lds + par * 65536u + ((which & 1) * 2 + kh) * 16384 + L.wave * 2048;
+  const __amdgpu_buffer_rsrc_t rsrcA = buffer_fixed(T.pa, T.sza);
+  const __amdgpu_buffer_rsrc_t rsrcB = buffer_fixed(T.pb, 256 * p.Kp * 2);
+  const __amdgpu_buffer_rsrc_t rsrcA2 = buffer_fixed(T.pa2, T.sza2);
+  if (which & 1) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcB, (lds_void *)(dst + q * 1024), 16, (int)(T.b_off[q] | dead), (int)kbytes, 0, 0);
+  } else if (KS == 1) {
+    unsigned mp = 0u, mm_ = 0u, m0_ = ~0u;
+    if (SHIFT || SHIFT2) {
+      const int c = kt * 64 + kh * 32 + L.chunk * 8 - (SHIFT2 ? L.nt1 * 64 : 0);   // first channel of this lane's chunk (of x2)
+      mp = 0u - (unsigned)(c < p.fold);
+      mm_ = (0u - (unsigned)(c < 2 * p.fold)) & ~mp;
+      m0_ = ~(mp | mm_);
+    }
+    const bool second = DUAL && kt >= L.nt1;              // wave-uniform: which source this K-tile comes from
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      unsigned off = T.a_off[q];
+      if (SHIFT) off = (T.a_offp[q] & mp) | (T.a_offm[q] & mm_) | (T.a_off[q] & m0_);
+      unsigned off2 = T.a_off2[q];
+      if (SHIFT2) off2 = (T.a_off2p[q] & mp) | (T.a_off2m[q] & mm_) | (T.a_off2[q] & m0_);
+      if (DUAL && second)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA2, (lds_void *)(dst + q * 1024), 16, (int)(off2 | dead),
+                                                 (int)(kbytes - (unsigned)L.nt1 * 128u), 0, 0);
+      else
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16, (int)(off | dead), (int)kbytes, 0, 0);
+    }
+  } else {
+    const int tap = (kt * 64) >> (p.logC4 + 2);           // C >= 64: a K-tile never straddles a tap
+    const int ky = tap / 3, kx = tap - ky * 3;
+    const unsigned tap_off = (unsigned)(((ky * p.Wi + kx) * p.C + (kt * 64 - tap * p.C) + kh * 32) * 2);
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16,
+                                               (int)((((T.a_mask[q] >> tap) & 1u) ? T.a_off[q] + tap_off : kInvalid) | dead), 0, 0, 0);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // conv_bf16_256: the bf16 implicit GEMM on a 256 x 256 tile, ONE 8-wave workgroup per CU, operands staged by LDS-DMA.
 //
 // Why: the 128 x 128 bf16 tiles of conv_igemm are LDS-bound -- per MFMA they need as many LDS-array cycles
@@ -43,104 +177,19 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256_kernel(const ConvParams 
   const int half = lane >> 5, l31 = lane & 31;
 
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  int tile = xcd_chunked32(bid, nwg);
   if (p.reverse) tile = nwg - 1 - tile;
-  const int tm = tile / p.ntn, tn = tile - tm * p.ntn;
-  const int m0 = tm * 256, n0 = tn * 256;
 
-  const int HoWo = p.Ho * p.Wo;
-  const int n_first = m0 / HoWo;
-  const int frame0 = SHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
-  const int frame_bytes = p.Hi * p.Wi * p.C * 2;
-  const size_t a_bytes = ((size_t)p.N - frame0) * (size_t)frame_bytes;
-  const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_bytes), 0,
-      (int)(a_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(p.w) + (size_t)n0 * p.Kp * 2), 0, 256 * p.Kp * 2, 0x00020000);
-
-  // second A source (DUAL: conv3 + downsample as one GEMM, K = [conv3 input channels | block input channels])
-  const int frame_bytes2 = DUAL ? p.Hi2 * p.Wi2 * p.C2 * 2 : 0;
-  const size_t a2_bytes = DUAL ? ((size_t)p.N - n_first) * (size_t)frame_bytes2 : 0;
-  const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)n_first * frame_bytes2), 0,
-      (int)(a2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a2_bytes), 0x00020000);
-  const int nt1 = DUAL ? p.K1 / 64 : 0;                   // K-tiles of the first source
-
-  // ---- loader state: this lane fills LDS slot (row, lane & 3) of rows piece * 16 + (lane >> 2), piece = 2 * wave + q
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);      // global 16-B chunk held by that slot (swizzle on the source)
-  unsigned a_off[2], a_offp[SHIFT ? 2 : 1], a_offm[SHIFT ? 2 : 1], a_mask[KS == 3 ? 2 : 1], b_off[2], a_off2[DUAL ? 2 : 1];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int row = (2 * wave + q) * 16 + (lane >> 2);
-    const int m = m0 + row;
-    const bool ok = m < p.M;
-    const int mm = ok ? m : m0;
-    const int n = mm / HoWo, rem = mm - n * HoWo;
-    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-    const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-    const int base = (n - frame0) * frame_bytes + (iy0 * p.Wi + ix0) * p.C * 2 + chunk * 16;
-    a_off[q] = (KS == 1 && !ok) ? kInvalid : (unsigned)base;
-    if (KS == 3) {
-      unsigned mask = 0;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-          if ((unsigned)(iy0 + ky) < (unsigned)p.Hi && (unsigned)(ix0 + kx) < (unsigned)p.Wi) mask |= 1u << (ky * 3 + kx);
-      a_mask[q] = ok ? mask : 0u;
-    }
-    if (SHIFT) {
-      const int t = n % p.T;
-      a_offp[q] = (ok && t < p.T - 1) ? (unsigned)(base + frame_bytes) : kInvalid;
-      a_offm[q] = (ok && t > 0) ? (unsigned)(base - frame_bytes) : kInvalid;
-    }
-    if (DUAL)
-      a_off2[q] = ok ? (unsigned)((n - n_first) * frame_bytes2 + (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * 2 + chunk * 16)
-                     : kInvalid;
-    b_off[q] = (unsigned)(row * p.Kp * 2 + chunk * 16);
-  }
+  const Tile256Launch L = {p.Ho * p.Wo, p.Hi * p.Wi * p.C * 2, DUAL ? p.Hi2 * p.Wi2 * p.C2 * 2 : 0, DUAL ? p.K1 / 64 : 0,
+                           wave, lane, (lane & 3) ^ ((lane >> 4) & 3)};
+  Tile256State<KS, SHIFT, DUAL> T;
+  tile256_setup(T, p, L, tile);
+  const int m0 = T.m0, n0 = T.n0;
   const int nt = p.Kp / 64;                               // K-tiles
-  typedef __attribute__((address_space(3))) void lds_void;
-  // Stage one half-operand of K-tile kt: which = 0 A k0-31, 1 B k0-31, 2 A k32-63, 3 B k32-63 (two 1-KiB pieces per wave)
+  // Stage one half-operand of K-tile kt (tile256_stage) into the buffer of its parity; K-tiles past the end: zeros
   auto stage = [&](int kt, int which) {
     const unsigned dead = (~(unsigned)((kt - nt) >> 31)) & kInvalid;
-    const int kh = which >> 1;
-    const unsigned kbytes = (unsigned)kt * 128u + (unsigned)kh * 64u;
-    unsigned char *dst = lds + (kt & 1) * 65536 + ((which & 1) * 2 + kh) * 16384 + wave * 2048;
-    if (which & 1) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcB, (lds_void *)(dst + q * 1024), 16, (int)(b_off[q] | dead), (int)kbytes, 0, 0);
-    } else if (KS == 1) {
-      unsigned mp = 0u, mm_ = 0u, m0_ = ~0u;
-      if (SHIFT) {
-        const int c = kt * 64 + kh * 32 + chunk * 8;      // first channel of this lane's chunk
-        mp = 0u - (unsigned)(c < p.fold);
-        mm_ = (0u - (unsigned)(c < 2 * p.fold)) & ~mp;
-        m0_ = ~(mp | mm_);
-      }
-      const bool second = DUAL && kt >= nt1;               // wave-uniform: which source this K-tile comes from
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        unsigned off = a_off[q];
-        if (SHIFT) off = (a_offp[q] & mp) | (a_offm[q] & mm_) | (a_off[q] & m0_);
-        if (DUAL && second)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA2, (lds_void *)(dst + q * 1024), 16, (int)(a_off2[q] | dead),
-                                                   (int)(kbytes - (unsigned)nt1 * 128u), 0, 0);
-        else
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16, (int)(off | dead), (int)kbytes, 0, 0);
-      }
-    } else {
-      const int tap = (kt * 64) >> (p.logC4 + 2);         // C >= 64: a K-tile never straddles a tap
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const unsigned tap_off = (unsigned)(((ky * p.Wi + kx) * p.C + (kt * 64 - tap * p.C) + kh * 32) * 2);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16,
-                                                 (int)((((a_mask[q] >> tap) & 1u) ? a_off[q] + tap_off : kInvalid) | dead), 0, 0, 0);
-    }
+    tile256_stage(lds, T, p, L, kt, (unsigned)(kt & 1), which, dead);
   };
 
   f32x16 acc[4][2];
@@ -215,16 +264,13 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256_kernel(const ConvParams 
   // ---- epilogue: per wave, four 32 x 64 slabs through a private LDS region ---------------------------------
   float *Cs = reinterpret_cast<float *>(lds + wave * 8704);  // [32][68] fp32
   const size_t y_bytes = ((size_t)p.M - m0) * p.Cout * 2;
-  const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<char *>(p.y) + (size_t)m0 * p.Cout * 2, 0, (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcY = buffer_window(reinterpret_cast<char *>(p.y) + (size_t)m0 * p.Cout * 2, y_bytes);
   const float floor_ = p.relu ? 0.f : -INFINITY;
   const int c8 = lane & 7, r8l = lane >> 3;
   const f32x4 bias0 = *reinterpret_cast<const f32x4 *>(p.bias + n0 + wn * 64 + c8 * 8);
   const f32x4 bias1 = *reinterpret_cast<const f32x4 *>(p.bias + n0 + wn * 64 + c8 * 8 + 4);
   // residual (RES): the 8 channels of this lane's row segment, fetched one slab ahead of their use
-  const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(RES ? p.res : p.y) + (size_t)m0 * p.Cout * 2), 0,
-      (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(reinterpret_cast<const char *>(RES ? p.res : p.y) + (size_t)m0 * p.Cout * 2, y_bytes);
   u32x4 rres[2][RES ? 4 : 1];
   auto load_res = [&](int i, int set) {
     if constexpr (RES) {
@@ -295,30 +341,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256_kernel(const ConvParams 
 #ifndef TSM_256P_STAMP
 #define TSM_256P_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0 (s_memtime), printed at the kernel's end (1: conv3 + downsample, 2: 3x3)
 #endif
-#if TSM_256P_STAMP
-#define P256_STAMP(i)                                       \
-  do {                                                      \
-    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-    stamp_acc[i] += _t - stamp_last;                        \
-    stamp_last = _t;                                        \
-  } while (0)
-#else
-#define P256_STAMP(i) do {} while (0)
-#endif
 constexpr size_t kLds256pBytes = 131072 + 8192 + 8 * 2176;   // two operand buffers | bias [<= 2048] fp32 | residual arm: eight [8][68] fp32 sub-slabs
-
-template <int KS, bool SHIFT, bool DUAL, bool SHIFT2 = false> struct Tile256State {
-  unsigned a_off[2], b_off[2];
-  unsigned a_mask[KS == 3 ? 2 : 1];
-  unsigned a_offp[SHIFT ? 2 : 1], a_offm[SHIFT ? 2 : 1];
-  unsigned a_off2[DUAL ? 2 : 1];
-  unsigned a_off2p[SHIFT2 ? 2 : 1], a_off2m[SHIFT2 ? 2 : 1];   // block placement: x2's frames t+1 / t-1
-  int m0, n0;
-  // (the operand windows as plain pointers + sizes: the host pass cannot hold __amdgpu_buffer_rsrc_t in a struct; the
-  //  descriptors are rebuilt where they are used -- scalar moves)
-  const char *pa, *pb, *pa2;
-  int sza, sza2;
-};
 
 template <int KS, bool SHIFT, bool RES = false, bool DUAL = false>
 __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams p) {
@@ -329,11 +352,8 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
   // is read through the temporal shift and the first source is not
   constexpr bool ASHIFT = SHIFT && !RES && !DUAL;   // the A loader's shift (conv1)
   constexpr bool RSHIFT = SHIFT && RES, XSHIFT = SHIFT && DUAL;
-#if TSM_256P_STAMP
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+  TSM_STAMP_DECL(TSM_256P_STAMP, 6);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];   // 2 buffers x 64 KB | bias [Cout] fp32
-  typedef __attribute__((address_space(3))) void lds_void;
   typedef Tile256State<KS, ASHIFT, DUAL, XSHIFT> State;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -342,116 +362,19 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
 
   const int ntiles = p.ntm * p.ntn, nwg = (int)gridDim.x, bid = (int)blockIdx.x;
   const int my = (ntiles - bid + nwg - 1) / nwg;          // tiles of this workgroup (>= 1: the grid never exceeds the tiles)
-  const int q8 = ntiles >> 3, r8 = ntiles & 7;
   const int HoWo = p.Ho * p.Wo;
-  const int frame_bytes = p.Hi * p.Wi * p.C * 2;
-  const int frame_bytes2 = DUAL ? p.Hi2 * p.Wi2 * p.C2 * 2 : 0;
-  const int nt1 = DUAL ? p.K1 / 64 : 0;                   // K-tiles of the first source
+  const Tile256Launch L = {HoWo, p.Hi * p.Wi * p.C * 2, DUAL ? p.Hi2 * p.Wi2 * p.C2 * 2 : 0, DUAL ? p.K1 / 64 : 0,
+                           wave, lane, (lane & 3) ^ ((lane >> 4) & 3)};
   const int nt = p.Kp / 64;                               // K-tiles per tile (>= 2)
-  const int chunk = (lane & 3) ^ ((lane >> 4) & 3);       // global 16-B chunk held by this lane's LDS slot (source-side swizzle)
 
   float *bias_lds = reinterpret_cast<float *>(lds + 131072);
   for (int i = tid; i < p.Cout; i += 512) bias_lds[i] = p.bias[i];
 
-  // the loader state of the s-th tile of this workgroup (virtual block bid + s * nwg in conv_bf16_256's XCD-chunked order)
-  auto setup = [&](State &T, int s) {
-    const int v = bid + s * nwg, xcd = v & 7;
-    int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
+  // the s-th tile of this workgroup (virtual block bid + s * nwg in conv_bf16_256's XCD-chunked order)
+  auto tile_of = [&](int s) {
+    int tile = xcd_chunked32(bid + s * nwg, ntiles);
     if (tile >= ntiles) tile = ntiles - 1;                // (s == my: never staged live, kept in range for the arithmetic)
-    if (p.reverse) tile = ntiles - 1 - tile;
-    const int tm = tile / p.ntn, tn = tile - tm * p.ntn;
-    T.m0 = tm * 256;
-    T.n0 = tn * 256;
-    const int n_first = T.m0 / HoWo;
-    const int frame0 = ASHIFT ? (n_first > 0 ? n_first - 1 : 0) : n_first;
-    const size_t a_bytes = ((size_t)p.N - frame0) * (size_t)frame_bytes;
-    T.pa = reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_bytes;
-    T.sza = (int)(a_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a_bytes);
-    T.pb = reinterpret_cast<const char *>(p.w) + (size_t)T.n0 * p.Kp * 2;
-    const int frame02 = (XSHIFT && n_first > 0) ? n_first - 1 : n_first;
-    const size_t a2_bytes = DUAL ? ((size_t)p.N - frame02) * (size_t)frame_bytes2 : 0;
-    T.pa2 = reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * frame_bytes2;
-    T.sza2 = (int)(a2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a2_bytes);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int row = (2 * wave + q) * 16 + (lane >> 2);
-      const int m = T.m0 + row;
-      const bool ok = m < p.M;
-      const int mm = ok ? m : T.m0;
-      const int n = mm / HoWo, rem = mm - n * HoWo;
-      const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-      const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-      const int base = (n - frame0) * frame_bytes + (iy0 * p.Wi + ix0) * p.C * 2 + chunk * 16;
-      T.a_off[q] = (KS == 1 && !ok) ? kInvalid : (unsigned)base;
-      if (KS == 3) {
-        unsigned mask = 0;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-          for (int kx = 0; kx < 3; ++kx)
-            if ((unsigned)(iy0 + ky) < (unsigned)p.Hi && (unsigned)(ix0 + kx) < (unsigned)p.Wi) mask |= 1u << (ky * 3 + kx);
-        T.a_mask[q] = ok ? mask : 0u;
-      }
-      if (ASHIFT) {
-        const int t = n % p.T;
-        T.a_offp[q] = (ok && t < p.T - 1) ? (unsigned)(base + frame_bytes) : kInvalid;
-        T.a_offm[q] = (ok && t > 0) ? (unsigned)(base - frame_bytes) : kInvalid;
-      }
-      if (DUAL)
-        T.a_off2[q] = ok ? (unsigned)((n - frame02) * frame_bytes2 + (oy * p.stride2 * p.Wi2 + ox * p.stride2) * p.C2 * 2 + chunk * 16)
-                         : kInvalid;
-      if (XSHIFT) {
-        const int t = n % p.T;
-        T.a_off2p[q] = (ok && t < p.T - 1) ? T.a_off2[q] + (unsigned)frame_bytes2 : kInvalid;
-        T.a_off2m[q] = (ok && t > 0) ? T.a_off2[q] - (unsigned)frame_bytes2 : kInvalid;
-      }
-      T.b_off[q] = (unsigned)(row * p.Kp * 2 + chunk * 16);
-    }
-  };
-
-  // Stage one half-operand of K-tile kt of the tile with state T into buffer `par`: which = 0 A k0-31, 1 B k0-31,
-  // 2 A k32-63, 3 B k32-63 (two 1-KiB pieces per wave); dead = kInvalid: zeros, no memory traffic
-  auto stage_of = [&](const State &T, int kt, unsigned par, int which, unsigned dead) {
-    const int kh = which >> 1;
-    const unsigned kbytes = (unsigned)kt * 128u + (unsigned)kh * 64u;
-    unsigned char *dst = lds + par * 65536u + ((which & 1) * 2 + kh) * 16384 + wave * 2048;
-    const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(T.pa), 0, T.sza, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(T.pb), 0, 256 * p.Kp * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(T.pa2), 0, T.sza2, 0x00020000);
-    if (which & 1) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcB, (lds_void *)(dst + q * 1024), 16, (int)(T.b_off[q] | dead), (int)kbytes, 0, 0);
-    } else if (KS == 1) {
-      unsigned mp = 0u, mm_ = 0u, m0_ = ~0u;
-      if (ASHIFT || XSHIFT) {
-        const int c = kt * 64 + kh * 32 + chunk * 8 - (XSHIFT ? nt1 * 64 : 0);   // first channel of this lane's chunk (of x2)
-        mp = 0u - (unsigned)(c < p.fold);
-        mm_ = (0u - (unsigned)(c < 2 * p.fold)) & ~mp;
-        m0_ = ~(mp | mm_);
-      }
-      const bool second = DUAL && kt >= nt1;               // wave-uniform: which source this K-tile comes from
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        unsigned off = T.a_off[q];
-        if (ASHIFT) off = (T.a_offp[q] & mp) | (T.a_offm[q] & mm_) | (T.a_off[q] & m0_);
-        unsigned off2 = T.a_off2[q];
-        if (XSHIFT) off2 = (T.a_off2p[q] & mp) | (T.a_off2m[q] & mm_) | (T.a_off2[q] & m0_);
-        if (DUAL && second)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA2, (lds_void *)(dst + q * 1024), 16, (int)(off2 | dead),
-                                                   (int)(kbytes - (unsigned)nt1 * 128u), 0, 0);
-        else
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16, (int)(off | dead), (int)kbytes, 0, 0);
-      }
-    } else {
-      const int tap = (kt * 64) >> (p.logC4 + 2);         // C >= 64: a K-tile never straddles a tap
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const unsigned tap_off = (unsigned)(((ky * p.Wi + kx) * p.C + (kt * 64 - tap * p.C) + kh * 32) * 2);
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_void *)(dst + q * 1024), 16,
-                                                 (int)((((T.a_mask[q] >> tap) & 1u) ? T.a_off[q] + tap_off : kInvalid) | dead), 0, 0, 0);
-    }
+    return p.reverse ? ntiles - 1 - tile : tile;
   };
 
   f32x16 acc[4][2];      // acc[i][j]: rows = channels n0 + 64 wn + 32 j + .., columns = pixels m0 + 128 wm + 32 i + l31
@@ -486,9 +409,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
       // r - Ho*Wo ([fold, 2 fold); zeros at its first frame) or r -- one frame either side of the tile's window
       const int rbase = T.m0 >= HoWo ? T.m0 - HoWo : 0;
       const size_t y_bytes = ((size_t)p.M - rbase) * p.Cout * 2;
-      const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * 2), 0,
-          (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * 2, y_bytes);
       const int row = wm * 128 + t * 8 + r8l, c = T.n0 + wn * 64 + c8 * 8;
       const int tt = ((T.m0 + row) / HoWo) % p.T;
       unsigned o = (unsigned)(((T.m0 - rbase + row) * p.Cout + c) * 2);
@@ -498,19 +419,18 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
       rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)o, 0, 0);
     } else if constexpr (RES) {
       const size_t y_bytes = ((size_t)p.M - T.m0) * p.Cout * 2;
-      const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)T.m0 * p.Cout * 2), 0,
-          (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(reinterpret_cast<const char *>(p.res) + (size_t)T.m0 * p.Cout * 2, y_bytes);
       rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(
           rsrcR, ((wm * 128 + t * 8 + r8l) * p.Cout + T.n0 + wn * 64 + c8 * 8) * 2, 0, 0);
     }
   };
 
   State cur, nxt;
-  setup(cur, 0);
+  tile256_setup(cur, p, L, tile_of(0));
   // prologue: the six half-operands the schedule has in flight before the first K-tile starts (nt >= 2: all of tile 0)
-  stage_of(cur, 0, 0u, 0, 0u); stage_of(cur, 0, 0u, 1, 0u); stage_of(cur, 0, 0u, 2, 0u); stage_of(cur, 0, 0u, 3, 0u);
-  stage_of(cur, 1, 1u, 0, 0u); stage_of(cur, 1, 1u, 1, 0u);
+  tile256_stage(lds, cur, p, L, 0, 0u, 0, 0u); tile256_stage(lds, cur, p, L, 0, 0u, 1, 0u);
+  tile256_stage(lds, cur, p, L, 0, 0u, 2, 0u); tile256_stage(lds, cur, p, L, 0, 0u, 3, 0u);
+  tile256_stage(lds, cur, p, L, 1, 1u, 0, 0u); tile256_stage(lds, cur, p, L, 1, 1u, 1, 0u);
   asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");   // K-tile 0, k 0-31 of A and B have landed (this wave's share); the bias is written
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();              // the stagger of conv_bf16_256: waves 4-7 one barrier behind
@@ -518,16 +438,16 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
   int g = 0;                                              // K-tiles done so far: the LDS buffer of a K-tile is its parity
   for (int s = 0; s < my; ++s) {
     const unsigned next_dead = s + 1 < my ? 0u : kInvalid;
-    P256_STAMP(5);
-    setup(nxt, s + 1);
-    P256_STAMP(0);
+    TSM_STAMP(TSM_256P_STAMP, 5);
+    tile256_setup(nxt, p, L, tile_of(s + 1));
+    TSM_STAMP(TSM_256P_STAMP, 0);
     for (int kt = 0; kt < nt; ++kt, ++g) {
       const unsigned buf = (unsigned)(g & 1) * 65536u;
       // K-tile kt + d of the flat sequence: this tile's, or the first ones of the next tile
       auto stage = [&](int d, int which) {
         const unsigned par = (unsigned)((g + d) & 1);
-        if (kt + d < nt) stage_of(cur, kt + d, par, which, 0u);
-        else stage_of(nxt, kt + d - nt, par, which, next_dead);
+        if (kt + d < nt) tile256_stage(lds, cur, p, L, kt + d, par, which, 0u);
+        else tile256_stage(lds, nxt, p, L, kt + d - nt, par, which, next_dead);
       };
       auto stage_ph = [&](int ph) {
         if (ph == 0) stage(1, 2);
@@ -613,14 +533,13 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
         __builtin_amdgcn_s_barrier();
       }
       }
-      P256_STAMP((kt == 0 ? 1 : kt == 1 ? 2 : 3));
+      TSM_STAMP(TSM_256P_STAMP, (kt == 0 ? 1 : kt == 1 ? 2 : 3));
     }
     // ---- epilogue of tile s: the next tile's first operands are in flight ----
     if constexpr (!RES) {   // from registers (no LDS, no barrier)
       const size_t y_bytes = ((size_t)p.M - cur.m0) * p.Cout * 2;
-      const int ysz = (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes);
-      const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<char *>(p.y) + (size_t)cur.m0 * p.Cout * 2, 0, ysz, 0x00020000);
+      const int ysz = window_bytes(y_bytes);
+      const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)cur.m0 * p.Cout * 2, ysz);
       const int cbase = (cur.n0 + wn * 64) * 2 + half * 32;               // this lane's first byte within a pixel's row
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -657,8 +576,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
     } else {                // residual arm: 16 sub-slabs of 8 rows through this wave's [8][68] fp32 slab
       float *Cs = reinterpret_cast<float *>(lds + 131072 + 8192 + wave * 2176);
       const size_t y_bytes = ((size_t)p.M - cur.m0) * p.Cout * 2;
-      const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<char *>(p.y) + (size_t)cur.m0 * p.Cout * 2, 0, (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcY = buffer_window(reinterpret_cast<char *>(p.y) + (size_t)cur.m0 * p.Cout * 2, y_bytes);
       const f32x4 bias0 = *reinterpret_cast<const f32x4 *>(bias_lds + cur.n0 + wn * 64 + c8 * 8);
       const f32x4 bias1 = *reinterpret_cast<const f32x4 *>(bias_lds + cur.n0 + wn * 64 + c8 * 8 + 4);
 #pragma unroll
@@ -689,7 +607,7 @@ __global__ void __launch_bounds__(512, 1) conv_bf16_256p_kernel(const ConvParams
 #pragma unroll
           for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
     }
-    P256_STAMP(4);
+    TSM_STAMP(TSM_256P_STAMP, 4);
     cur = nxt;
   }
 #if TSM_256P_STAMP

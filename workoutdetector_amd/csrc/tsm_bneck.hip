@@ -75,16 +75,6 @@ template <int CIN> struct BnLds {
 #ifndef TSM_BNECK_STAMP
 #define TSM_BNECK_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0's four waves (s_memtime), printed at the kernel's end
 #endif
-#if TSM_BNECK_STAMP
-#define BN_STAMP(i)                                         \
-  do {                                                      \
-    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-    stamp_acc[i] += _t - stamp_last;                        \
-    stamp_last = _t;                                        \
-  } while (0)
-#else
-#define BN_STAMP(i) do {} while (0)
-#endif
 template <int CIN, bool SHIFT, bool IDL = false>
 __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
   constexpr bool DUAL = CIN == 64;
@@ -105,9 +95,9 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
   const int nsteps = H / 2 + 1;
 
   // ---- the stationary operands
-  const __amdgpu_buffer_rsrc_t rsrcW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w1), 0, 64 * CIN * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w2), 0, 64 * 576 * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w3), 0, 256 * 16 * NG3 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW1 = buffer_fixed(p.w1, 64 * CIN * 2);
+  const __amdgpu_buffer_rsrc_t rsrcW2 = buffer_fixed(p.w2, 64 * 576 * 2);
+  const __amdgpu_buffer_rsrc_t rsrcW3 = buffer_fixed(p.w3, 256 * 16 * NG3 * 2);
   u32x4 w1r[2][NG1], w2r[36];
 #pragma unroll
   for (int s = 0; s < 36; ++s)
@@ -193,7 +183,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
   };
   auto x_piece = [&](const XDma &d, auto gc) __attribute__((always_inline)) {
     constexpr int g = decltype(gc)::value;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(d.base), 0, 3 * xframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(d.base, 3 * xframe);
     // fold = CIN / 8 channels: CIN 256 -- k16 groups 0, 1 from t + 1 and 2, 3 from t - 1; CIN 64 -- ONE 16-byte chunk each:
     // the two halves of k16 group 0 (the loader lane's hsel picks the chunk)
     const unsigned v0 = !SHIFT ? d.vC : (DUAL ? (hsel ? d.vB : d.vA) : d.vA);
@@ -211,8 +201,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
   // a contiguous eighth of the frames per XCD its neighbours' workgroups fetch the same lines at about the same time), then
   // the engine's alternating direction
   auto frame_of = [&](int v) {
-    const int n = p.N, q8 = n >> 3, r8 = n & 7, x = v & 7;          // xcd_chunked() in 32 bits (scalar registers are short here)
-    const int c = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (v >> 3);
+    const int c = xcd_chunked32(v, p.N);                            // (in 32 bits: scalar registers are short here)
     return p.reverse ? p.N - 1 - c : c;
   };
   int fi = blockIdx.x;
@@ -220,16 +209,12 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                                         // biases and the zeroed line buffer are in place
 
-#if TSM_BNECK_STAMP
-  unsigned long long stamp_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+  TSM_STAMP_DECL(TSM_BNECK_STAMP, 10);
   for (; fi < p.N; fi += gridDim.x) {
     const int f = frame_of(fi);
     const int fnext = fi + (int)gridDim.x < p.N ? frame_of(fi + (int)gridDim.x) : -1;
-    const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)f * xframe), 0, xframe, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(p.y) + (size_t)f * yframe, 0, yframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcR = buffer_fixed(reinterpret_cast<const char *>(p.x) + (size_t)f * xframe, xframe);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)f * yframe, yframe);
     // rows -2 and -1 of the new frame (slots 0, 1) are zeros; every wave is past the last conv2 of the previous frame
     for (int i = tid; i < 2 * kBnRP * 2 * 4; i += 256) {                // 2 slots x RP pixels x 2 halves, 4 planes
       const int pl = i / (2 * kBnRP * 2), r = i - pl * (2 * kBnRP * 2);
@@ -238,10 +223,10 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
     for (int s = 0; s < nsteps; ++s) {
       const int r0 = 2 * s - 1;                                         // output rows r0, r0 + 1; conv1 rows 2s, 2s + 1
       // ================= conv1: rows 2s, 2s + 1 -> line buffer =================
-      BN_STAMP(6);
+      TSM_STAMP(TSM_BNECK_STAMP, 6);
       asm volatile("s_waitcnt vmcnt(16)" ::: "memory");                 // this step's input has landed (the 16 youngest operations are the previous step's stores)
       if constexpr (IDL) __builtin_amdgcn_s_barrier();                  // ... every wave's: the identity below is read from all four slots
-      BN_STAMP(0);
+      TSM_STAMP(TSM_BNECK_STAMP, 0);
       // The identity operand of this step's four M-tiles, 4 x 16 bytes per lane and M-tile:
       //   CIN 256  res[mt][2 itl + qq] = bytes [64 it + 16 (2 half + qq), + 16) of the pixel's 512 (the store layout);
       //   CIN 64   res[mt][g] = channels 16 g + 8 half .. + 8 of the pixel: the B fragment of k16 group g.
@@ -357,9 +342,9 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      BN_STAMP(1);
+      TSM_STAMP(TSM_BNECK_STAMP, 1);
       __builtin_amdgcn_s_barrier();    // rows 2s - 2 .. 2s + 1 are complete; nobody still reads the mid tile of the previous step
-      BN_STAMP(2);
+      TSM_STAMP(TSM_BNECK_STAMP, 2);
       // IDL: ... nor anybody's input slot: re-arm it (a step minus the conv1 phase ahead), piece by piece behind conv2's MFMAs
       // (round 5; behind the late identity loads in the wave's issue order)
       XDma xd{};
@@ -396,7 +381,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
             px[st & (PXR - 1)][m] = *reinterpret_cast<const u32x4 *>(lds + tb[m] + g * kBnT1Plane);
           }
         };
-        BN_STAMP(7);      // (conv2's prologue: the late identity loads, lane geometry, accumulators)
+        TSM_STAMP(TSM_BNECK_STAMP, 7);      // (conv2's prologue: the late identity loads, lane geometry, accumulators)
 #pragma unroll
         for (int st = 0; st < PXR - 1; ++st) rd(st);
         static_for<36>([&](auto sc) __attribute__((always_inline)) {
@@ -412,7 +397,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
           }
           __builtin_amdgcn_sched_barrier(0);
         });
-        BN_STAMP(8);      // (conv2's 36 steps)
+        TSM_STAMP(TSM_BNECK_STAMP, 8);      // (conv2's 36 steps)
         // bias2, ReLU, bf16 -> the mid tile, in conv3's B-fragment order (plane g' = 2 nt2 + qq)
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
@@ -434,9 +419,9 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      BN_STAMP(3);
+      TSM_STAMP(TSM_BNECK_STAMP, 3);
       __builtin_amdgcn_s_barrier();    // the mid tile is complete; the line buffer may be overwritten by the next step
-      BN_STAMP(4);
+      TSM_STAMP(TSM_BNECK_STAMP, 4);
       // ================= conv3 + identity: all four M-tiles, output channels 64 wave .. + 64 =================
       u32x4 w3r[2][NG3];
 #pragma unroll
@@ -530,7 +515,7 @@ __global__ void __launch_bounds__(256, 1) bneck_ws_kernel(const BneckParams p) {
           }
         }
       });
-      BN_STAMP(5);
+      TSM_STAMP(TSM_BNECK_STAMP, 5);
     }
   }
 #if TSM_BNECK_STAMP

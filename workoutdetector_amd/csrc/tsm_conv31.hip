@@ -146,8 +146,8 @@ __global__ void __launch_bounds__(512, 2) conv31_fused_kernel(const Conv31Params
     const int row = (wave * L::NW1 + i) * 8 + (lane >> 3), slot = lane & 7;
     w1off[i] = (unsigned)(row * (C * 2) + ((slot ^ ((row >> 1) & 7)) << 4));
   }
-  const __amdgpu_buffer_rsrc_t rsrcW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w3), 0, C * K3 * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w1), 0, N1 * C * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW3 = buffer_fixed(p.w3, C * K3 * 2);
+  const __amdgpu_buffer_rsrc_t rsrcW1 = buffer_fixed(p.w1, N1 * C * 2);
   const size_t clip_rows = (size_t)T * HW;
   // (plain ints, not L:: constants, inside the scalar-offset arguments of the buffer builtins below: with a template-dependent
   //  constant expression there the HOST pass of hipcc silently drops the kernel's stub from the object -- no diagnostic)
@@ -172,8 +172,7 @@ __global__ void __launch_bounds__(512, 2) conv31_fused_kernel(const Conv31Params
   };
   // pieces i0 .. i0 + n - 1 of the t2 tile (clip, p0) into the staging buffer
   auto issue_t2 = [&](int clip, int p0, int i0, int n, unsigned dead) {
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.t2) + (size_t)clip * clip_rows * L::RB3), 0, (int)(clip_rows * L::RB3), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = buffer_fixed(reinterpret_cast<const char *>(p.t2) + (size_t)clip * clip_rows * L::RB3, (int)(clip_rows * L::RB3));
     for (int i = i0; i < i0 + n; ++i) {
       const int row = 32 * wave + i * L::RPP3 + lane / L::LPR3, slot = lane % L::LPR3;
       const int t = row >> lpx, px = row & (PX - 1);
@@ -187,8 +186,7 @@ __global__ void __launch_bounds__(512, 2) conv31_fused_kernel(const Conv31Params
   // the residual of a chunk's epilogue steps, requested RD chunks ahead (register set = chunk index mod RD)
   u32x4 rres[L::RD * L::NQ];
   auto load_res = [&](int slot, int q, int clip, int p0, int nc, unsigned dead) {
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)clip * clip_rows * (C * 2)), 0, (int)(clip_rows * (C * 2)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = buffer_fixed(reinterpret_cast<const char *>(p.res) + (size_t)clip * clip_rows * (C * 2), (int)(clip_rows * (C * 2)));
     const unsigned inv = (unsigned)p0 + epx[q] < (unsigned)HW ? 0u : kInvalid;
     rres[slot] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(evoff[q] | inv | dead), p0 * cb + nc * 128, 0);
   };
@@ -219,8 +217,7 @@ __global__ void __launch_bounds__(512, 2) conv31_fused_kernel(const Conv31Params
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc2[j][e] = 0.f;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the staging buffer is refilled from chunk 0's epilogue on: behind barrier A)
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(p.y) + (size_t)clip * clip_rows * (C * 2), 0, (int)(clip_rows * (C * 2)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)clip * clip_rows * (C * 2), (int)(clip_rows * (C * 2)));
     unsigned einv[L::NQ];
 #pragma unroll
     for (int q = 0; q < L::NQ; ++q) einv[q] = (unsigned)p0 + epx[q] < (unsigned)HW ? 0u : kInvalid;
@@ -346,8 +343,7 @@ __global__ void __launch_bounds__(512, 2) conv31_fused_kernel(const Conv31Params
      }
     }
     // ---- t1 of the tile: relu(acc2 + bias1) -> bf16, whole 128-byte row segments ----
-    const __amdgpu_buffer_rsrc_t rsrcT1 = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(p.t1) + (size_t)clip * clip_rows * (N1 * 2), 0, (int)(clip_rows * (N1 * 2)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcT1 = buffer_fixed(reinterpret_cast<char *>(p.t1) + (size_t)clip * clip_rows * (N1 * 2), (int)(clip_rows * (N1 * 2)));
 #pragma unroll
     for (int jh = 0; jh < L::NTL2 / 2; ++jh) {
       const int col0 = jh * 64;
@@ -444,22 +440,10 @@ template <int K3, int C, int N1> struct C31P {
 #ifndef TSM_C31P_STAMP
 #define TSM_C31P_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0 (s_memtime), printed at the kernel's end
 #endif
-#if TSM_C31P_STAMP
-#define C31P_STAMP(i)                                       \
-  do {                                                      \
-    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-    stamp_acc[i] += _t - stamp_last;                        \
-    stamp_last = _t;                                        \
-  } while (0)
-#else
-#define C31P_STAMP(i) do {} while (0)
-#endif
 template <int K3, int C, int N1>
 __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p) {
   typedef C31P<K3, C, N1> L;
-#if TSM_C31P_STAMP
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+  TSM_STAMP_DECL(TSM_C31P_STAMP, 6);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   typedef __attribute__((address_space(3))) void lds_void;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -512,8 +496,7 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
     // (inline asm like the residual loads below, for the same reason: with the builtin, hipcc cannot tell that the loads of a
     //  tile's LAST chunk are consumed by the next tile only, and puts a wait ladder for them in front of every other chunk's GEMM1)
     auto load_afr = [&](int clip, int p0, unsigned dead) {
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.t2) + (size_t)clip * clip_rows * L::RB3), 0, (int)(clip_rows * L::RB3), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrc = buffer_fixed(reinterpret_cast<const char *>(p.t2) + (size_t)clip * clip_rows * L::RB3, (int)(clip_rows * L::RB3));
       const unsigned inv = (unsigned)p0 + afpx < (unsigned)HW ? 0u : kInvalid;
       const unsigned voff = afoff | inv | dead;
       const int soff = __builtin_amdgcn_readfirstlane(p0 * rb3);
@@ -531,8 +514,7 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
     // visible to the compiler: what it does not count can only make ITS waits tighter than needed, never looser.
     u32x4 rres[L::RD * L::NQ];                            // residual register sets: chunk index mod RD
     auto load_res = [&](int slot, int q, int clip, int p0, int nc, unsigned dead) {
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)clip * clip_rows * (C * 2)), 0, (int)(clip_rows * (C * 2)), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrc = buffer_fixed(reinterpret_cast<const char *>(p.res) + (size_t)clip * clip_rows * (C * 2), (int)(clip_rows * (C * 2)));
       const unsigned inv = (unsigned)p0 + epx[q] < (unsigned)HW ? 0u : kInvalid;
       const unsigned voff = evoff[q] | inv | dead;
       const int soff = __builtin_amdgcn_readfirstlane(p0 * cb + nc * 128);
@@ -568,8 +550,7 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
         asm volatile("s_waitcnt vmcnt(%8)"
                      : "+v"(afr[0]), "+v"(afr[1]), "+v"(afr[2]), "+v"(afr[3]), "+v"(afr[4]), "+v"(afr[5]), "+v"(afr[6]), "+v"(afr[7])
                      : "n"(2 * L::NQ) : "memory");
-      const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<char *>(p.y) + (size_t)clip * clip_rows * (C * 2), 0, (int)(clip_rows * (C * 2)), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)clip * clip_rows * (C * 2), (int)(clip_rows * (C * 2)));
       unsigned einv[L::NQ];
 #pragma unroll
       for (int q = 0; q < L::NQ; ++q) einv[q] = (unsigned)p0 + epx[q] < (unsigned)HW ? 0u : kInvalid;
@@ -579,9 +560,9 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
         for (int rset = 0; rset < L::RD; ++rset) {
           const int nc = nc0 + rset;
           const bool last = nc + 1 == L::NC;
-          C31P_STAMP(4);                                                   // (the tail of the previous slot)
+          TSM_STAMP(TSM_C31P_STAMP, 4);                                                   // (the tail of the previous slot)
           __builtin_amdgcn_s_barrier();                                    // A: W3's chunk nc is in LDS; LDS tile buffer `ybuf` is free
-          C31P_STAMP(0);
+          TSM_STAMP(TSM_C31P_STAMP, 0);
           // ---- GEMM1: y[this wave's 32 rows][the chunk's 64 channels] ----
           f32x16 acc1[2];
 #pragma unroll
@@ -608,9 +589,9 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
             }
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          C31P_STAMP(1);
+          TSM_STAMP(TSM_C31P_STAMP, 1);
           __builtin_amdgcn_s_barrier();                                    // B: every producer has read W3's chunk
-          C31P_STAMP(2);
+          TSM_STAMP(TSM_C31P_STAMP, 2);
           if (last) load_afr(nclip, np0, next_dead);                       // GEMM1 of this tile is over: the next tile's A fragments
           // ---- epilogue of the chunk: + bias3, + residual, ReLU, bf16 -> y (global) and the LDS tile ----
           const f32x4 bias0 = *reinterpret_cast<const f32x4 *>(bias3_l + nc * 64 + c8 * 8);
@@ -640,10 +621,10 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
             const f32x4 c0 = cpair[q & 1][0], c1 = cpair[q & 1][1];
             // this step's residual (requested RD chunks ago)
             static_assert(L::wait_res(L::NC - 1) == L::wait_res(0) && L::wait_res(L::RD - 1) == L::wait_res(L::NC - 2), "the two cases below");
-            C31P_STAMP(3);
+            TSM_STAMP(TSM_C31P_STAMP, 3);
             if (wrap) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(rres[rset * L::NQ + q]) : "n"(L::wait_res(0)) : "memory");
             else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(rres[rset * L::NQ + q]) : "n"(L::wait_res(L::RD - 1)) : "memory");
-            C31P_STAMP(5);
+            TSM_STAMP(TSM_C31P_STAMP, 5);
             float v[8] = {c0[0] + bias0[0], c0[1] + bias0[1], c0[2] + bias0[2], c0[3] + bias0[3],
                           c1[0] + bias1[0], c1[1] + bias1[1], c1[2] + bias1[2], c1[3] + bias1[3]};
 #pragma unroll
@@ -657,7 +638,7 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
             else load_res(rset * L::NQ + q, q, nclip, np0, nc + L::RD - L::NC, next_dead);
           }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's rows of the LDS tile are written (before the next A)
-          C31P_STAMP(3);
+          TSM_STAMP(TSM_C31P_STAMP, 3);
           ybuf ^= (unsigned)(L::M * 128);
         }
       }
@@ -697,8 +678,8 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
       const int row = (rg * L::NW1 + i) * 8 + (lane >> 3), slot = lane & 7;
       w1off[i] = (unsigned)(row * (C * 2) + ((slot ^ ((row >> 1) & 7)) << 4));
     }
-    const __amdgpu_buffer_rsrc_t rsrcW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w3), 0, C * K3 * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w1), 0, N1 * C * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcW3 = buffer_fixed(p.w3, C * K3 * 2);
+    const __amdgpu_buffer_rsrc_t rsrcW1 = buffer_fixed(p.w1, N1 * C * 2);
     auto w1_piece = [&](int nc, unsigned buf, unsigned dead, int i) {    // buf: byte offset of the W1 buffer
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcW1, (lds_void *)(lds + L::kW1 + buf + (rg * L::NW1 + i) * 1024), 16,
                                                (int)(w1off[i] | dead), nc * 128, 0, 0);
@@ -725,9 +706,9 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
       const bool live_p = g < nslots;
       const int kc = kp == 0 ? L::NC - 1 : kp - 1;                         // the chunk this slot multiplies (g >= 1)
       const bool have = g >= 1;
-      C31P_STAMP(4);
+      TSM_STAMP(TSM_C31P_STAMP, 4);
       __builtin_amdgcn_s_barrier();                                        // A: LDS tile (g - 1) & 1 is written, W3 / W1 pieces of the last slot have landed
-      C31P_STAMP(0);
+      TSM_STAMP(TSM_C31P_STAMP, 0);
       const unsigned w1buf = par * (unsigned)(N1 * 128), w1dead = live_p ? 0u : kInvalid;   // W1's chunk kp -> buffer g & 1 (free: read two slots ago)
       // ---- GEMM2 of chunk kc: t1 += shift(y chunk) * W1[:, chunk]^T, from LDS tile / W1 buffer (g - 1) & 1 ----
       const unsigned prev = (par ^ 1u);
@@ -750,9 +731,9 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
       }
 #pragma unroll
       for (int i = 0; i < L::NW1; ++i) w1_piece(kp, w1buf, w1dead, i);
-      C31P_STAMP(1);
+      TSM_STAMP(TSM_C31P_STAMP, 1);
       __builtin_amdgcn_s_barrier();                                        // B: the producers have read W3's chunk kp
-      C31P_STAMP(2);
+      TSM_STAMP(TSM_C31P_STAMP, 2);
       const int kn = kp + 1 == L::NC ? 0 : kp + 1;                         // W3's chunk of the NEXT slot
       const unsigned w3dead = g + 1 < nslots ? 0u : kInvalid;
       issue_w3(kn, w3dead);
@@ -768,13 +749,12 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   // the fragment reads of this slot are over (before the next A)
-      C31P_STAMP(3);
+      TSM_STAMP(TSM_C31P_STAMP, 3);
       if (have && kc == L::NC - 1) {
         // ---- t1 of the tile the producers finished a slot ago: relu(acc2 + bias1) -> bf16, whole 128-byte row segments ----
         int tclip, tp0;
         tile_of(kp == 0 ? sp - 1 : sp, &tclip, &tp0);
-        const __amdgpu_buffer_rsrc_t rsrcT1 = __builtin_amdgcn_make_buffer_rsrc(
-            reinterpret_cast<char *>(p.t1) + (size_t)tclip * clip_rows * (N1 * 2), 0, (int)(clip_rows * (N1 * 2)), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrcT1 = buffer_fixed(reinterpret_cast<char *>(p.t1) + (size_t)tclip * clip_rows * (N1 * 2), (int)(clip_rows * (N1 * 2)));
 #pragma unroll
         for (int jh = 0; jh < L::NTL2 / 2; ++jh) {
           const int col0 = jh * 64;
@@ -808,7 +788,7 @@ __global__ void __launch_bounds__(512, 2) conv31_pc_kernel(const Conv31Params p)
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // this slot's DMA pieces have landed
       }
-      C31P_STAMP(5);
+      TSM_STAMP(TSM_C31P_STAMP, 5);
       par ^= 1u;
       if (++kp == L::NC) { kp = 0; ++sp; }
     }

@@ -45,6 +45,23 @@ __device__ __forceinline__ long xcd_chunked(long v, long n) {
   const long q8 = n >> 3, r8 = n & 7, x = v & 7;
   return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (v >> 3);
 }
+__device__ __forceinline__ int xcd_chunked32(int v, int n) {   // the same in 32 bits (tile counts fit; half the scalar work)
+  const int q8 = n >> 3, r8 = n & 7, x = v & 7;
+  return (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (v >> 3);
+}
+
+// Buffer descriptors: a raw (untyped, unswizzled) window of `bytes` bytes at `base`; offsets at or past num_records load
+// zeros and store nothing.  buffer_window: a window that may exceed what 32-bit offsets reach (a tensor's tail from a
+// tile's first row on) -- clamped, the kernel addresses only its tile's neighbourhood; buffer_fixed: a size that is an int.
+// (Kernels that keep a window in a struct store base + window_bytes() and build the descriptor where it is used: hipcc's
+//  host pass cannot hold __amdgpu_buffer_rsrc_t in a struct.)
+__device__ __forceinline__ int window_bytes(size_t bytes) { return (int)(bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : bytes); }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_fixed(const void *base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_window(const void *base, size_t bytes) {
+  return buffer_fixed(base, window_bytes(bytes));
+}
 
 // Cache policy of the activation stores of the bf16 kernel families (the aux operand of raw_buffer_store: 0 = plain,
 // 2 = nt, 16 = sc1 = write-through that drops the line from the XCD's L2, MI355X_MICROARCH.md "stores of each flavour").
@@ -127,6 +144,21 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
   }
 #undef TSM_VMCNT_CASE
 }
+// Phase stamps of a diagnostic build (-DTSM_<FAMILY>_STAMP=1, the switch each family file declares; tools/probes/*_stamp.py):
+// TSM_STAMP_DECL(on, n) declares n cycle sums `stamp_acc` and the clock reading they are measured from, TSM_STAMP(on, i) adds
+// the s_memtime cycles since the previous stamp to sum i; the kernel prints the sums at its end.  `on` is the family's switch:
+// with 0, the product, both are constant-folded away and leave the code object as it is without them.
+#define TSM_STAMP_DECL(on, n) \
+  [[maybe_unused]] unsigned long long stamp_acc[(on) ? (n) : 1] = {}, stamp_last = (on) ? __builtin_amdgcn_s_memtime() : 0
+#define TSM_STAMP(on, i)                                          \
+  do {                                                            \
+    if (on) {                                                     \
+      const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
+      stamp_acc[(on) ? (i) : 0] += _t - stamp_last;               \
+      stamp_last = _t;                                            \
+    }                                                             \
+  } while (0)
+
 // Every kernel launch of the library goes through this macro: the launch itself, plus one line in the calling thread's
 // launch trace when a test has switched it on (tsm_trace_launches; note_launch is a thread-local pointer test otherwise).
 // The trace names the kernel as the launch site spells it and, for a launch inside a template, the enclosing

@@ -49,21 +49,9 @@ constexpr int kFrC1Pieces = TSM_FRONT_C1_PIECES;   // pieces of the even row's r
 #ifndef TSM_FRONT_STAMP
 #define TSM_FRONT_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0, wave 0 (s_memtime), printed at the kernel's end
 #endif
-#if TSM_FRONT_STAMP
-#define FRONT_STAMP(i)                                      \
-  do {                                                      \
-    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-    stamp_acc[i] += _t - stamp_last;                        \
-    stamp_last = _t;                                        \
-  } while (0)
-#else
-#define FRONT_STAMP(i) do {} while (0)
-#endif
 template <bool SHIFT>
 __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
-#if TSM_FRONT_STAMP
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+  TSM_STAMP_DECL(TSM_FRONT_STAMP, 6);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   typedef __attribute__((address_space(3))) void lds_void;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -73,8 +61,8 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
   const int xframe = H * W * 512, yframe = Ho * Wo * 256;
 
   // ---- the stationary operands: this wave's 32 mid channels of W1, its 32 output channels of W2
-  const __amdgpu_buffer_rsrc_t rsrcW1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w1), 0, 128 * 256 * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcW2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w2), 0, 128 * 1152 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW1 = buffer_fixed(p.w1, 128 * 256 * 2);
+  const __amdgpu_buffer_rsrc_t rsrcW2 = buffer_fixed(p.w2, 128 * 1152 * 2);
   u32x4 w1r[16], w2r[72];
 #pragma unroll
   for (int s = 0; s < 72; ++s)
@@ -117,8 +105,7 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
 
   // virtual frame index -> frame: XCD-chunked (the shifted channels come from frames f - 1 and f + 1), then the engine's direction
   auto frame_of = [&](int v) {
-    const int n = p.N, q8 = n >> 3, r8 = n & 7, x = v & 7;
-    const int c = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + (v >> 3);
+    const int c = xcd_chunked32(v, p.N);
     return p.reverse ? p.N - 1 - c : c;
   };
   // LDS-DMA of a row into a row slot, as eight pieces that can be issued one at a time (between MFMAs: a piece costs ~100 cycles of
@@ -150,7 +137,7 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
   };
   auto piece = [&](const RowDma &d, int k) {
     const int j = k >> 2, pl = k & 3;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(d.base), 0, 3 * xframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(d.base, 3 * xframe);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcX, (lds_void *)(d.dst + pl * 2048 + j * 1024), 16, (int)(pl < 2 ? d.v01[j] : d.v23[j]), pl * 32, 0, 0);
   };
 
@@ -179,8 +166,7 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
   int xslot = 0;                         // input ring slot of the row being multiplied (runs on across frames)
   for (; fi < p.N; fi += gridDim.x) {
     const int f = frame_of(fi);
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(p.y) + (size_t)f * yframe, 0, yframe, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)f * yframe, yframe);
     int lslot = 1;                       // line-buffer slot of row r: (r + 1) % 3 (row -1 lives in slot 0)
     // conv1 of the row in input slot `xs_slot` -> line-buffer slot `ls`; the eight pieces of `d` (if any) ride between its MFMAs.
     // Four batches of eight k16 groups -- (M-tile 0, groups 0-7), (0, 8-15), (1, 0-7), (1, 8-15) -- software-pipelined: the fragment
@@ -249,11 +235,11 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
       // ================= even row r: conv1 -> line-buffer slot lslot (its input slot is re-armed from inside the next row) =================
       // this wave's pieces of row r have landed (they were the SECOND group of row r - 3): younger are that row's two stores and
       // all of row r - 1's operations (8 + 8 + 2)
-      FRONT_STAMP(5);
+      TSM_STAMP(TSM_FRONT_STAMP, 5);
       asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-      FRONT_STAMP(0);
+      TSM_STAMP(TSM_FRONT_STAMP, 0);
       __builtin_amdgcn_s_barrier();      // ... every wave's; nobody still reads the line buffer (conv2 of the previous row pair is over)
-      FRONT_STAMP(1);
+      TSM_STAMP(TSM_FRONT_STAMP, 1);
       if (r == 0) {                      // row -1 of the new frame: zeros in slot 0 (the previous frame's row H - 2 lived there)
         for (int i = tid; i < 8 * kFrRP * 2; i += 256) {
           const int pl = i / (kFrRP * 2), q = i - pl * (kFrRP * 2);
@@ -266,27 +252,27 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
         conv1_row(xs_even, ls_even, false, none);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      FRONT_STAMP(2);
+      TSM_STAMP(TSM_FRONT_STAMP, 2);
       __builtin_amdgcn_s_barrier();      // the line-buffer row is complete; every wave has read input slot xs_even
-      FRONT_STAMP(1);
+      TSM_STAMP(TSM_FRONT_STAMP, 1);
       xslot = xslot == 2 ? 0 : xslot + 1;
       lslot = lslot == 2 ? 0 : lslot + 1;
       // ================= odd row r + 1: conv1 (+ the refill of slot xs_even), conv2 (+ the refill of its own slot) =================
       // its pieces were the FIRST group of row r - 1: younger are that row's second group and its two stores
-      FRONT_STAMP(5);
+      TSM_STAMP(TSM_FRONT_STAMP, 5);
       asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-      FRONT_STAMP(0);
+      TSM_STAMP(TSM_FRONT_STAMP, 0);
       __builtin_amdgcn_s_barrier();
-      FRONT_STAMP(1);
+      TSM_STAMP(TSM_FRONT_STAMP, 1);
       const RowDma dA = prep_next(xs_even);
       conv1_row(xslot, lslot, true, dA);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      FRONT_STAMP(2);
+      TSM_STAMP(TSM_FRONT_STAMP, 2);
       __builtin_amdgcn_s_barrier();      // rows r - 1, r, r + 1 of the line buffer are complete; every wave has read input slot xslot
-      FRONT_STAMP(1);
+      TSM_STAMP(TSM_FRONT_STAMP, 1);
       {
         const RowDma dB = prep_next(xslot);
-        FRONT_STAMP(3);
+        TSM_STAMP(TSM_FRONT_STAMP, 3);
         // ---- conv2: output row s = r / 2 from line-buffer rows r - 1, r, r + 1 ----
         const int s = r >> 1;
         // (slot of row r - 1 + ky: lslot is row r + 1's, i.e. ky = 2; ky = 1 -> lslot - 1, ky = 0 -> lslot - 2, mod 3)
@@ -319,7 +305,7 @@ __global__ void __launch_bounds__(256, 1) front_s2_kernel(const FrontParams p) {
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w2r[st]), __builtin_bit_cast(bf16x8, px[st & 7]), acc, 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         });
-        FRONT_STAMP(4);
+        TSM_STAMP(TSM_FRONT_STAMP, 4);
         // bias2, ReLU, bf16; lanes 0-31 take groups 0, 1 and lanes 32-63 groups 2, 3 of the pixel: two 16-byte stores into this
         // wave's 64-byte slice of the pixel
         unsigned pk[4][2];

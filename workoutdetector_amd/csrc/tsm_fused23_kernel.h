@@ -62,11 +62,9 @@ __global__ void __launch_bounds__(128 * (CMID / 32), 4) TSM_F23_KERNEL(const Fus
   const int frame0 = m0 / HW;
   const int frame_bytes = HW * CMID * 4;
   const size_t a_bytes = ((size_t)p.N - frame0) * frame_bytes;
-  const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_bytes), 0,
-      (int)(a_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcA = buffer_window(reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_bytes, a_bytes);
   const __amdgpu_buffer_rsrc_t rsrcB =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w2), 0, CMID * 9 * CMID * 4, 0x00020000);
+      buffer_fixed(p.w2, CMID * 9 * CMID * 4);
 
   const int lrow = tid >> 3, chunk = tid & 7;
   unsigned a_off[APASS], a_mask[APASS], b_off[BPASS];
@@ -112,10 +110,9 @@ __global__ void __launch_bounds__(128 * (CMID / 32), 4) TSM_F23_KERNEL(const Fus
   // residual / output window of this workgroup: rows m0 .., all 4 * CMID channels (rows past M are dropped / zero)
   const int cout = NCHUNK * BNC;
   const size_t y_bytes = ((size_t)p.M - m0) * cout * 4;
-  const int y_rec = (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes);
-  const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(p.res + (size_t)m0 * cout), 0, y_rec, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(p.y + (size_t)m0 * cout, 0, y_rec, 0x00020000);
+  const int y_rec = window_bytes(y_bytes);
+  const __amdgpu_buffer_rsrc_t rsrcR = buffer_fixed(p.res + (size_t)m0 * cout, y_rec);
+  const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(p.y + (size_t)m0 * cout, y_rec);
 
   // ---- phase A: 3x3 conv, K = 9 * CMID, register-resident K-step pipeline -------------------------------
   f32x16 acc, tot;

@@ -142,20 +142,14 @@ conv_igemm(const ConvParams p) {
   const int wpairs = (p.Wi + 1) >> 1;
   const size_t frame_elems = PAIRS ? (size_t)p.Hi * wpairs * 8 : (size_t)p.Hi * p.Wi * p.C;
   const size_t a_bytes = ((size_t)p.N - frame0) * frame_elems * EB;
-  const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_elems * EB), 0,
-      (int)(a_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(p.w) + (size_t)n0 * p.Kp * EB), 0, BN * p.Kp * EB,
-      0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcA = buffer_window(reinterpret_cast<const char *>(p.x) + (size_t)frame0 * frame_elems * EB, a_bytes);
+  const __amdgpu_buffer_rsrc_t rsrcB = buffer_fixed(reinterpret_cast<const char *>(p.w) + (size_t)n0 * p.Kp * EB, BN * p.Kp * EB);
 
   // second A source (DUAL): same output pixels, its own channel count / spatial size / stride
   const size_t frame_elems2 = DUAL ? (size_t)p.Hi2 * p.Wi2 * p.C2 : 0;
   const int frame02 = (BSHIFT && DUAL && n_first > 0) ? n_first - 1 : n_first;   // (a shifted x2 also reads frame t-1)
   const size_t a2_bytes = DUAL ? ((size_t)p.N - frame02) * frame_elems2 * EB : 0;
-  const __amdgpu_buffer_rsrc_t rsrcA2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char *>(reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * frame_elems2 * EB), 0,
-      (int)(a2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : a2_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcA2 = buffer_window(reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)frame02 * frame_elems2 * EB, a2_bytes);
 
   // ---- per-thread loader state: 8 threads per 32-float row, 32 rows per pass -------------------
   const int lrow = tid >> 3;
@@ -463,9 +457,7 @@ conv_igemm(const ConvParams p) {
   u32x4 rres_h[(RESID && (X3 || BF)) ? EPASS : 1], rres_l[(RESID && X3) ? EPASS : 1];
   if (RESID && (X3 || BF) && !BSHIFT) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * EB;
-    const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)m0 * p.Cout * EB), 0,
-        (int)(r_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : r_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(reinterpret_cast<const char *>(p.res) + (size_t)m0 * p.Cout * EB, r_bytes);
 #pragma unroll
     for (int k = 0; k < EPASS; ++k) {
       const unsigned o = (unsigned)(((erow + k * RPP) * p.Cout + n0 + ecol) * EB);
@@ -475,9 +467,7 @@ conv_igemm(const ConvParams p) {
   }
   if (RESID && !X3 && !BF && !BSHIFT) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * 4;
-    const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(p.res + (size_t)m0 * p.Cout), 0,
-        (int)(r_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : r_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(p.res + (size_t)m0 * p.Cout, r_bytes);
 #pragma unroll
     for (int k = 0; k < EPASS; ++k)
       rres[k] = buf_load4(rsrcR, (unsigned)(((erow + k * RPP) * p.Cout + n0 + ecol) * 4), 0);
@@ -491,9 +481,7 @@ conv_igemm(const ConvParams p) {
     const int sel = c < p.fold ? 1 : c < 2 * p.fold ? -1 : 0;
     const unsigned step = (unsigned)(HoWo * p.Cout * EB);
     const size_t r_bytes = ((size_t)p.M - rbase) * p.Cout * EB;
-    const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * EB), 0,
-        (int)(r_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : r_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(reinterpret_cast<const char *>(p.res) + (size_t)rbase * p.Cout * EB, r_bytes);
 #pragma unroll
     for (int k = 0; k < EPASS; ++k) {
       const int rr = erow + k * RPP;
@@ -761,8 +749,7 @@ conv_igemm(const ConvParams p) {
   const int mt0 = in_tail ? (p.tail_from / p.ntn) * BM : 0;   // first row of the tail
   char *ybase = y_scatter ? reinterpret_cast<char *>(p.y) : in_tail ? reinterpret_cast<char *>(p.ypart) + ((size_t)seg * (p.M - mt0) + (m0 - mt0)) * p.Cout * EB
                         : reinterpret_cast<char *>(p.y) + ((size_t)(partial ? seg : 0) * p.M + m0) * p.Cout * EB;
-  const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-      ybase, 0, (int)(y_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : y_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcY = buffer_window(ybase, y_bytes);
   const float floor_ = (p.relu && !partial) ? 0.f : -INFINITY;  // ReLU as a branch-free clamp
   if constexpr (BF) {
     const f32x4 bias0 = *reinterpret_cast<const f32x4 *>(p.bias + n0 + ecol);

@@ -64,8 +64,7 @@ __global__ void __launch_bounds__(64 * WAVES) stem_direct_kernel(const float *__
     const int tx = (int)(t % tiles_x), ty = (int)((t / tiles_x) % tiles_y), f = (int)(t / ((long)tiles_x * tiles_y));
     const int iy0 = 2 * ty * kStemTH - 3, pc0 = tx * kStemTW - 2;
     // descriptor rebased to the tile's frame: 32-bit offsets suffice whatever the batch
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(x) + (size_t)f * x_frame), 0, (int)x_frame, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(reinterpret_cast<const char *>(x) + (size_t)f * x_frame, x_frame);
 #pragma unroll
     for (int q = 0; q < PPASS; ++q) {
       const int ci = tid + q * NT;               // chunk index inside the patch
@@ -81,8 +80,7 @@ __global__ void __launch_bounds__(64 * WAVES) stem_direct_kernel(const float *__
   for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     const int tx = (int)(t % tiles_x), ty = (int)((t / tiles_x) % tiles_y), f = (int)(t / ((long)tiles_x * tiles_y));
     const int oy0 = ty * kStemTH, ox0 = tx * kStemTW;
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(y) + (size_t)f * y_frame, 0, (int)y_frame, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(y) + (size_t)f * y_frame, y_frame);
     __syncthreads();  // previous tile's patch and staging are free (and the weights are in place)
 #pragma unroll
     for (int q = 0; q < PPASS; ++q)
@@ -181,16 +179,6 @@ constexpr int kPoolPR = 2 * kPoolCR + 5, kPoolPC = kPoolCC + 3;      // input pa
 #ifndef TSM_STEM_STAMP
 #define TSM_STEM_STAMP 0   // diagnostic builds only: per-phase cycle sums of workgroup 0 (s_memtime), printed at the kernel's end
 #endif
-#if TSM_STEM_STAMP
-#define ST_STAMP(i)                                         \
-  do {                                                      \
-    const unsigned long long _t = __builtin_amdgcn_s_memtime(); \
-    stamp_acc[i] += _t - stamp_last;                        \
-    stamp_last = _t;                                        \
-  } while (0)
-#else
-#define ST_STAMP(i) do {} while (0)
-#endif
 template <bool X3, bool PLANAR>
 // (bf16: 77 760 B of LDS and <= 128 registers, so that TWO workgroups share a CU and overlap each other's phases)
 __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float *__restrict__ x, const float *__restrict__ w,
@@ -255,9 +243,8 @@ __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float 
     const int f = t / tiles_f, rem = t - f * tiles_f, ty = rem / tiles_x, tx = rem - ty * tiles_x;
     // conv tile origin (2*py0 - 1, 2*px0 - 1)  ->  input rows from 2*(2*py0 - 1) - 3, pairs from (2*px0 - 1) - 2
     const int iy0 = 4 * ty * kPoolPH - 5, pc0 = 2 * tx * kPoolPW - 3;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(x) + (size_t)f * (PLANAR ? 3 * (size_t)plane_bytes : (size_t)x_frame)), 0,
-        (int)(PLANAR ? 3 * plane_bytes : x_frame), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(
+        reinterpret_cast<const char *>(x) + (size_t)f * (PLANAR ? 3 * (size_t)plane_bytes : (size_t)x_frame), PLANAR ? 3 * plane_bytes : x_frame);
 #pragma unroll
     for (int q = 0; q < PPASS; ++q) {
       const int ci = tid + q * NT;
@@ -309,9 +296,7 @@ __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float 
     }
   };
   // (tiles in XCD-chunked order: horizontally and vertically neighbouring tiles share up to half of their patch lines)
-#if TSM_STEM_STAMP
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+  TSM_STAMP_DECL(TSM_STEM_STAMP, 6);
   if ((int)blockIdx.x < n_tiles) fetch_patch((int)xcd_chunked(blockIdx.x, n_tiles));
   // bf16: the weight fragments of this lane's second channel tile (14 x 16 bytes) live in registers for the life of the workgroup
   // -- the kernel used 56 of the 128 registers two workgroups per CU leave it, and every wave read the same 28 fragments from
@@ -329,18 +314,17 @@ __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float 
     const int f = t / tiles_f, rem = t - f * tiles_f, ty = rem / tiles_x, tx = rem - ty * tiles_x;
     const int py0 = ty * kPoolPH, px0 = tx * kPoolPW;
     const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1;   // conv pixel of tile position (0, 0)
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(y) + (size_t)f * y_frame, 0, (int)y_frame, 0x00020000);
-    ST_STAMP(5);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(y) + (size_t)f * y_frame, y_frame);
+    TSM_STAMP(TSM_STEM_STAMP, 5);
     __syncthreads();
-    ST_STAMP(0);
+    TSM_STAMP(TSM_STEM_STAMP, 0);
 #pragma unroll
     for (int q = 0; q < PPASS; ++q)
       if (tid + q * NT < PCH) *reinterpret_cast<u32x4 *>(Ps + patch_slot(tid + q * NT)) = packed_chunk(q);
     if (v + (int)gridDim.x < n_tiles) fetch_patch((int)xcd_chunked(v + gridDim.x, n_tiles));
-    ST_STAMP(1);
+    TSM_STAMP(TSM_STEM_STAMP, 1);
     __syncthreads();
-    ST_STAMP(2);
+    TSM_STAMP(TSM_STEM_STAMP, 2);
     f32x16 acc[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -407,9 +391,9 @@ __global__ void __launch_bounds__(512, X3 ? 1 : 4) stem_pool_kernel(const float 
           *reinterpret_cast<u32x2 *>(Cs16 + mi * 72 + j * 32 + 8 * q + 4 * half) = inside ? o : ninf;
         }
     }
-    ST_STAMP(3);
+    TSM_STAMP(TSM_STEM_STAMP, 3);
     __syncthreads();
-    ST_STAMP(4);
+    TSM_STAMP(TSM_STEM_STAMP, 4);
     if (tid < kPoolPH * kPoolPW * 8) {  // one 8-channel group of one pooled pixel per thread
       const int pp = tid >> 3, cg = tid & 7;
       const int pyl = pp / kPoolPW, pxl = pp - pyl * kPoolPW;
@@ -526,9 +510,8 @@ __global__ void __launch_bounds__(512) stem_pool_f32_kernel(const float *__restr
   auto fetch_patch = [&](long t) {
     const int tx = (int)(t % tiles_x), ty = (int)((t / tiles_x) % tiles_y), f = (int)(t / ((long)tiles_x * tiles_y));
     const int iy0 = 4 * ty * kPoolPH - 5, ix0 = 4 * tx * kPoolPW - 5;   // 2 * (2 * p0 - 1) - 3
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(x) + (size_t)f * (PLANAR ? 3 * (size_t)plane_bytes : (size_t)x_frame)), 0,
-        (int)(PLANAR ? 3 * plane_bytes : x_frame), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(
+        reinterpret_cast<const char *>(x) + (size_t)f * (PLANAR ? 3 * (size_t)plane_bytes : (size_t)x_frame), PLANAR ? 3 * plane_bytes : x_frame);
 #pragma unroll
     for (int q = 0; q < PPASS; ++q) {
       const int ci = tid + q * NT;
@@ -551,8 +534,7 @@ __global__ void __launch_bounds__(512) stem_pool_f32_kernel(const float *__restr
     const int tx = (int)(t % tiles_x), ty = (int)((t / tiles_x) % tiles_y), f = (int)(t / ((long)tiles_x * tiles_y));
     const int py0 = ty * kPoolPH, px0 = tx * kPoolPW;
     const int oy0 = 2 * py0 - 1, ox0 = 2 * px0 - 1;
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(y) + (size_t)f * y_frame, 0, (int)y_frame, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(y) + (size_t)f * y_frame, y_frame);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < PPASS; ++q)

@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
 
   // ---- the stationary operand: fragment s = tap * 4 + g of output-channel tile nt, k = 16 s + 8 half .. + 8.
   // 56 of the 72 fragments are pinned to the accumulation-register half of the file (MFMA reads them there directly).
-  const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w2), 0, 64 * 576 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW = buffer_fixed(p.w2, 64 * 576 * 2);
   u32x4 wr[2][36];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
   if (tid < 64) bias_lds[tid] = p.bias2[tid];
   if constexpr (FUSE3) {
     bias3_lds[tid] = p.bias3[tid];
-    const __amdgpu_buffer_rsrc_t rsrcW3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w3), 0, 256 * 64 * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcW3 = buffer_fixed(p.w3, 256 * 64 * 2);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int f = wave * 8 + k, it = f >> 2, g = f & 3;
@@ -136,8 +136,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
     const int f = t / tiles_f, rem = t - f * tiles_f;
     const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
     const int x0 = tx * TC;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)f * frame_bytes), 0, frame_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(reinterpret_cast<const char *>(p.x) + (size_t)f * frame_bytes, frame_bytes);
     const int tbase = ((ty * TR - 1) * W + (x0 - 1)) * 128;             // rows above / below the frame fall outside the descriptor: zeros
     unsigned char *dst = lds + b * kWsBufBytes + wave * kWsPlane;
 #pragma unroll
@@ -158,8 +157,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
     const int f = tq / tiles_f, rem = tq - f * tiles_f;
     const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
     const int x0 = tx * TC;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.x) + (size_t)f * frame_bytes), 0, frame_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(reinterpret_cast<const char *>(p.x) + (size_t)f * frame_bytes, frame_bytes);
     const int tbase = ((ty * TR - 1) * W + (x0 - 1)) * 128;
     unsigned char *dst = lds + wave * kWsPlane;
 #pragma unroll
@@ -184,7 +182,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
     pp0[mt] = ok ? r * PW + c : 0;
   }
   // !FUSE3: one descriptor over the whole output (stores of a tile are issued while the next one is computed)
-  const __amdgpu_buffer_rsrc_t rsrcYall = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((size_t)p.M * 128), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcYall = buffer_fixed(p.y, (int)((size_t)p.M * 128));
 
   // The accumulators of one 32-pixel M-tile -> bf16, in ten pieces (they ride on the MFMA steps of the NEXT M-tile):
   // lane = pixel, a[nt][4 q + j] = channel nt * 32 + 8 q + 4 half + j.  Pieces 0-3 / 5-8: bias, ReLU, bf16 of group q of
@@ -315,10 +313,8 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws_kernel(const WsParams p) {
       const int tt = p.reverse ? ntiles - 1 - t : t;
       const int f = tt / tiles_f, rem = tt - f * tiles_f;
       const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
-      const __amdgpu_buffer_rsrc_t rsrcR = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char *>(reinterpret_cast<const char *>(p.res) + (size_t)f * frame_out), 0, frame_out, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<char *>(p.y) + (size_t)f * frame_out, 0, frame_out, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcR = buffer_fixed(reinterpret_cast<const char *>(p.res) + (size_t)f * frame_out, frame_out);
+      const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(reinterpret_cast<char *>(p.y) + (size_t)f * frame_out, frame_out);
       unsigned yo[2], ro[4];       // byte offset of the 256 channels of: this lane's pixel of M-tile mt / its loader pixel j (+ its chunk)
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
@@ -486,7 +482,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws128_kernel(const WsParams p)
   const int frame_bytes = H * W * 256;
 
   // ---- the stationary operand: fragment s = tap * 8 + g of this wave's 32 output channels, k = 16 s + 8 half .. + 8
-  const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w2), 0, 128 * 1152 * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW = buffer_fixed(p.w2, 128 * 1152 * 2);
   u32x4 wr[72];
 #pragma unroll
   for (int s = 0; s < 72; ++s)
@@ -534,7 +530,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws128_kernel(const WsParams p)
   auto patch_piece = [&](const PatchDma &d, int k) {
     const int i = k >> 1, pl = k & 1;
     if (d.live && i < nr && (!S2 || i < kS2Rounds - 1 || lane < 2)) {   // (S2's tenth round: position 288 alone)
-      const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(d.base), 0, frame_bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(d.base, frame_bytes);
       const int xg = d.x0 + (int)(dslot[i] >> 24);
       const unsigned off = (unsigned)d.tbase + ((dslot[i] & 0xFFFFFFu) << 4) + (pl ? 32u : 0u);
       const unsigned o = (unsigned)xg < (unsigned)W ? off : kInvalid;
@@ -570,7 +566,7 @@ __global__ void __launch_bounds__(256, 1) conv3x3_ws128_kernel(const WsParams p)
       hsw3 |= (unsigned)(half ^ ws128_swap(p.swz, pp0[3] + ky * PW + kx, PW)) << tap;
     }
   }
-  const __amdgpu_buffer_rsrc_t rsrcYall = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((size_t)p.M * 256), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcYall = buffer_fixed(p.y, (int)((size_t)p.M * 256));
 
   // epilogue of a PAIR of M-tiles in ten pieces: per M-tile four (bias, ReLU, bf16 of group q) and one (lanes 0-31 take
   // groups 0, 1, lanes 32-63 groups 2, 3: swap, two 16-byte stores into this wave's 64-byte slice of the pixel)
@@ -748,7 +744,7 @@ __global__ void __launch_bounds__(256, 1) conv1x1_ws_kernel(const Ws1Params p) {
   const int half = lane >> 5, l31 = lane & 31;
   const int ntiles = (p.M + 127) >> 7;
 
-  const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, 64 * CIN * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW = buffer_fixed(p.w, 64 * CIN * 2);
   u32x4 wr[2][NG];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
@@ -766,9 +762,7 @@ __global__ void __launch_bounds__(256, 1) conv1x1_ws_kernel(const Ws1Params p) {
     const int m0 = t * 128;
     // descriptor rebased one frame before the tile: every offset below is small and non-negative
     const long base_row = (long)m0 - p.HW;
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char *>(reinterpret_cast<const char *>(p.x) + base_row * (long)(CIN * 2)), 0,
-        (int)((size_t)(128 + 2 * p.HW) * CIN * 2 > 0x7FFFFFF0u ? 0x7FFFFFF0u : (size_t)(128 + 2 * p.HW) * CIN * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_window(reinterpret_cast<const char *>(p.x) + base_row * (long)(CIN * 2), (size_t)(128 + 2 * p.HW) * CIN * 2);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int pl = 32 * i + (lane >> 1);
@@ -792,7 +786,7 @@ __global__ void __launch_bounds__(256, 1) conv1x1_ws_kernel(const Ws1Params p) {
     }
   };
 
-  const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((size_t)p.M * 128), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(p.y, (int)((size_t)p.M * 128));
   const int pp = wave * 32 + l31;                                        // this lane's pixel of the tile
   const unsigned rd = (unsigned)(pp * 32 + ((half ^ ((pp >> 3) & 1)) << 4));
 
@@ -889,7 +883,7 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
   const int nh = NSPLIT == 2 ? ((int)blockIdx.x >> 3) & 1 : 0;          // this workgroup's half of the output channels
   const int tfirst = NSPLIT == 2 ? ((int)blockIdx.x & 7) + 8 * ((int)blockIdx.x >> 4) : (int)blockIdx.x;
   const int tstep = NSPLIT == 2 ? (int)gridDim.x >> 1 : (int)gridDim.x;   // (NSPLIT = 2: the grid is a multiple of 16)
-  const __amdgpu_buffer_rsrc_t rsrcW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.w), 0, CTOT * CIN * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcW = buffer_fixed(p.w, CTOT * CIN * 2);
   u32x4 wr[NTW][NG];
 #pragma unroll
   for (int nt = 0; nt < NTW; ++nt)
@@ -924,10 +918,10 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
     const long base_row = (long)m0 - p.HW;
     const size_t span = (size_t)(PX + 2 * p.HW) * C1 * 2;
     d.px = reinterpret_cast<const char *>(p.x) + base_row * (long)(C1 * 2);
-    d.szx = (int)(span > 0x7FFFFFF0u ? 0x7FFFFFF0u : span);
+    d.szx = window_bytes(span);
     const int n0 = m0 / p.HW;                                           // first frame of the tile
     d.px2 = reinterpret_cast<const char *>(DUAL ? p.x2 : p.x) + (size_t)n0 * frame2_bytes;
-    d.szx2 = DUAL ? (int)((size_t)(PX / p.HW + 2) * frame2_bytes > 0x7FFFFFF0u ? 0x7FFFFFF0u : (size_t)(PX / p.HW + 2) * frame2_bytes) : 0;
+    d.szx2 = DUAL ? window_bytes((size_t)(PX / p.HW + 2) * frame2_bytes) : 0;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int pl = 32 * i + (lane >> 1);
@@ -947,8 +941,8 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
     return d;
   };
   auto piece = [&](const TileDma &d, int b, int i, int k) {
-    const __amdgpu_buffer_rsrc_t rsrcX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(d.px), 0, d.szx, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrcX2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(d.px2), 0, d.szx2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcX = buffer_fixed(d.px, d.szx);
+    const __amdgpu_buffer_rsrc_t rsrcX2 = buffer_fixed(d.px2, d.szx2);
     const int g = PPW * wave + k;
     const int c0 = (2 * g + hsel) * 8;
     lds_void *dst = (lds_void *)(lds + b * kBuf + g * kPlane + i * 1024);
@@ -985,8 +979,8 @@ __global__ void __launch_bounds__(256, 1) conv1x1_wsn_kernel(const WsnParams p) 
     const unsigned char *buf = lds + nb * kBuf;
     // output window of the tile (rebased: 32-bit offsets whatever M * COUT is)
     const size_t y0 = (size_t)tt * PX * CTOT * 2;
-    const __amdgpu_buffer_rsrc_t rsrcY = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char *>(p.y) + y0, 0, (int)(ybytes - y0 > (size_t)PX * CTOT * 2 ? (size_t)PX * CTOT * 2 : ybytes - y0), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_fixed(
+        reinterpret_cast<char *>(p.y) + y0, (int)(ybytes - y0 > (size_t)PX * CTOT * 2 ? (size_t)PX * CTOT * 2 : ybytes - y0));
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const int pp = mt * 32 + l31;

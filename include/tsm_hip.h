@@ -469,7 +469,9 @@ int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel
                            int32_t n_windows, int32_t n_segment, int32_t person_crop, float *out,
                            int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream);
 
-/* feat [n_clips*T, hw, c] NHWC -> logits [n_clips, num_class]; fc_w [num_class, c], fc_b. */
+/* feat [n_clips*T, hw, c] NHWC -> logits [n_clips, num_class]; fc_w [num_class, c], fc_b.  Enqueues on `stream`; no
+ * synchronisation: the pooled rows between its two launches are a stream-ordered allocation (hipMallocAsync / hipFreeAsync on
+ * `stream`), inside a stream capture the graph's own allocation and free nodes. */
 int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *logits,
              int32_t n_clips, int32_t n_segment, int32_t hw, int32_t c, int32_t num_class,
              void *stream);

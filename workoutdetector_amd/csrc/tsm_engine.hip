@@ -1972,12 +1972,13 @@ int tsm_head(const float *feat, const float *fc_w, const float *fc_b, float *log
   if (!feat || !fc_w || !fc_b || !logits || n_clips <= 0 || n_segment <= 0 || hw <= 0 || c <= 0 || num_class <= 0)
     return TSM_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  // The pooled rows between the two launches live in a stream-ordered allocation: allocated and freed ON `s`, so the call only
+  // enqueues, and inside a stream capture the pair becomes the graph's own allocation and free nodes.
   float *pooled = nullptr;
-  hipError_t st = hipMalloc(reinterpret_cast<void **>(&pooled), (size_t)n_clips * n_segment * c * sizeof(float));
+  hipError_t st = hipMallocAsync(reinterpret_cast<void **>(&pooled), (size_t)n_clips * n_segment * c * sizeof(float), s);
   if (st != hipSuccess) return fail(nullptr, TSM_ERR_HIP, std::string("head scratch: ") + hipGetErrorString(st));
   st = tsm::launch_head(feat, fc_w, fc_b, pooled, logits, n_clips, n_segment, hw, c, num_class, tsm::kPrecF32, s);
-  hipError_t st2 = hipStreamSynchronize(s);
-  (void)hipFree(pooled);
+  const hipError_t st2 = hipFreeAsync(pooled, s);
   if (st != hipSuccess || st2 != hipSuccess)
     return fail(nullptr, TSM_ERR_HIP, std::string("head: ") + hipGetErrorString(st != hipSuccess ? st : st2));
   return TSM_OK;

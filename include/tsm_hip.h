@@ -209,6 +209,23 @@ int tsm_set_consensus(tsm_engine *e, int32_t consensus);
  * TSM_ERR_UNSUPPORTED, whichever call comes second: a dtype other than TSM_DTYPE_F32, a BasicBlock backbone (depth 18 / 34). */
 int tsm_set_non_local(tsm_engine *e, int32_t on);
 
+/* Temporal pool -- create_model(temporal_pool=True), the TSM code base's make_temporal_pool: on = 1 wraps layer2 in
+ * TemporalPool.  With x [B*T, C, H, W] layer1's output viewed [B, T, C, H, W], the pool is max_pool3d with kernel (3, 1, 1),
+ * stride (2, 1, 1), padding (1, 0, 0): output frame t' in [0, T/2) of a clip is the elementwise max over its source frames
+ * {2t'-1, 2t', 2t'+1} cut to [0, T); a frame of another clip is never read.  One launch of its own (temporal_maxpool_kernel),
+ * bit-exact in the storage format.  Layers 2-4 then run on B*T/2 frames and shift over T/2 segments (layer1 keeps T, in both
+ * placements; with T = 2 the later stages have one segment and the shifted channels are zero); the head's consensus runs
+ * over T/2 frames: tsm_forward writes [n_clips, num_class] (avg) or [n_clips, T/2, num_class] (identity),
+ * tsm_forward_features [n_clips * T/2, feat_dim], and every tap from layer2 on has n_clips * T/2 frames.  The tap
+ * "layer2.tpool" is the pooled tensor; the launch has a timing slot of that name behind layer1's last block.
+ * No new tensors.  State-dict keys of layer2 under the wrapper: "base_model.layer2.net.<b>.<rest>" (the wrapper holds the
+ * stage as `net`), accepted beside the plain "base_model.layer2.<b>.<rest>".
+ * Same contract as tsm_set_shift_place: legal between tsm_create and the first tsm_set_tensor, later TSM_ERR_INVALID_ARG; a
+ * value other than 0 or 1 TSM_ERR_UNSUPPORTED.  on = 1 is TSM_ERR_UNSUPPORTED on a TSM_DTYPE_BF16 engine (its cross-block
+ * and whole-block kernels tile over all T frames of a clip), with is_shift = 0, with an odd num_segments, and together with
+ * tsm_set_non_local(e, 1), whichever of the two calls comes second (the non-local wrapper assumes one segment count). */
+int tsm_set_temporal_pool(tsm_engine *e, int32_t on);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;

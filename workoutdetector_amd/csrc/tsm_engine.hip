@@ -93,6 +93,10 @@ struct Block {
   // tap name of the block's OWN output ("layerL.B.block" when wrapped: "layerL.B" is then the wrapper's)
   int nl_qkv = -1, nl_w = -1;
   std::string out_name;
+  // the segment count of the block's stage: cfg.num_segments, or half of it from layer2 on in a temporal-pool engine; and
+  // whether the temporal pool runs behind this block (the last one of layer1)
+  int T = 0;
+  bool tpool_after = false;
 };
 
 // A device buffer between two poisoned bands (tsm_host_util.h: guard_layout).  tsm_conv_op's temporaries always are; the
@@ -143,6 +147,7 @@ struct tsm_engine {
   int depth = 50;             // tsm_set_backbone
   int width = 64;             // tsm_set_bottleneck_width: torchvision's width_per_group
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
+  int temporal_pool = 0;      // tsm_set_temporal_pool: max-pool over time in front of layer2; layers 2-4 and the head see T / 2 frames per clip
   int non_local = 0;          // tsm_set_non_local: non-local blocks around layer2.{0,2} and layer3.{0,2,4} (fp32 Bottleneck engines)
   int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
@@ -248,6 +253,8 @@ void build_topology(tsm_engine *e) {
       const std::string c1key = p + (bp ? ".conv1.weight" : ".conv1.net.weight");
       Block blk;
       blk.stride = stride;
+      blk.T = e->temporal_pool && li > 0 ? temporal_pool_segments(e->cfg.num_segments) : e->cfg.num_segments;
+      blk.tpool_after = e->temporal_pool && li == 0 && b == bb.blocks[0] - 1;
       blk.name = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
       if (bb.basic) {
         // conv1: 3x3 at the block's stride, the temporal shift fused into its loader (which has no segmented form);
@@ -296,12 +303,19 @@ std::string unwrapped(const tsm_engine *e, const std::string &key) {
   return "";
 }
 
+// A temporal-pool engine: the spelling of a layer2 key under the TemporalPool wrapper, which holds the stage as `net`
+// ("base_model.layer2.net.<b>.<rest>"); "" for any other key or engine.
+std::string pool_wrapped(const tsm_engine *e, const std::string &key) {
+  const std::string stage = "base_model.layer2.";
+  return e->temporal_pool && key.compare(0, stage.size(), stage) == 0 ? stage + "net." + key.substr(stage.size()) : "";
+}
+
 const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
   auto it = e->tensors.find(key);
   if (it != e->tensors.end()) return &it->second;
-  // (every spelling: without the shift wrapper, without the non-local wrapper, without both)
-  const std::string nb = without_block(key);
-  for (const std::string &alt : {unwrapped(e, key), nb, nb.empty() ? nb : unwrapped(e, nb)}) {
+  // (every spelling: without the shift wrapper, without the non-local wrapper, without both; each under the temporal pool's wrapper)
+  const std::string nb = without_block(key), uw = unwrapped(e, key);
+  for (const std::string &alt : {uw, nb, nb.empty() ? nb : unwrapped(e, nb), pool_wrapped(e, key), pool_wrapped(e, uw)}) {
     if (alt.empty()) continue;
     it = e->tensors.find(alt);
     if (it != e->tensors.end()) return &it->second;
@@ -314,7 +328,8 @@ bool known_name(const tsm_engine *e, const std::string &name) {
   static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
   auto is = [&](const std::string &key) {
     const std::string nb = without_block(key);
-    return name == key || name == unwrapped(e, key) || (!nb.empty() && (name == nb || name == unwrapped(e, nb)));
+    if (name == key || name == unwrapped(e, key) || (!nb.empty() && (name == nb || name == unwrapped(e, nb)))) return true;
+    return e->temporal_pool && (name == pool_wrapped(e, key) || name == pool_wrapped(e, unwrapped(e, key)));
   };
   for (const ConvLayer &c : e->convs) {
     if (c.nl == 1) {
@@ -574,6 +589,9 @@ int time_best_of(tsm_engine *e, hipStream_t s, F &&launches, float *best_ms) {
   return TSM_OK;
 }
 
+// Segments per clip behind the backbone (the head's, the feature rows', the per-segment logits'): T, or T / 2 behind the temporal pool.
+int out_segments(const tsm_engine *e) { return e->temporal_pool ? temporal_pool_segments(e->cfg.num_segments) : e->cfg.num_segments; }
+
 // Block placement with the shift on: every block reads its input through the shift, the identity path included.
 bool block_shift(const tsm_engine *e) { return e->place == 1 && e->cfg.is_shift; }
 
@@ -592,7 +610,7 @@ BlockLaunches block_launches(const tsm_engine *e, size_t k, int nn, const float 
   const tsm_config &cfg = e->cfg;
   const Block &blk = e->blocks[k];
   const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
-  const int T = cfg.num_segments, shiftT = cfg.is_shift ? T : 0, prec = e->prec;
+  const int T = blk.T, shiftT = cfg.is_shift ? T : 0, prec = e->prec;
   const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   const bool fused = blk.down >= 0;   // (a Bottleneck's downsample always runs inside conv3's GEMM)
   BlockLaunches L;
@@ -652,7 +670,7 @@ BlockForms fused_forms(const tsm_engine *e, size_t k, int nn, int hh, int ww, co
             tsm::front_s2_valid(L.pfr.N, L.pfr.H, L.pfr.W, L.pfr.T, L.pfr.fold) && !want(".conv1");
   f.conv23 = (blk.d_w3f != nullptr || (bf16 && blk.cmid == 64 && tsm::conv23_ws_valid(nn, hh, ww))) && e->fuse23 != 0 &&
              !want(".conv2");
-  f.conv31 = bf16 && blk.down < 0 && k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0 && e->fuse31 != 0 &&
+  f.conv31 = bf16 && blk.down < 0 && !blk.tpool_after && k + 1 < e->blocks.size() && e->blocks[k + 1].conv3 >= 0 && e->fuse31 != 0 &&
              tsm::conv31_valid(L.q);
   return f;
 }
@@ -680,6 +698,7 @@ std::vector<BlockPlan> plan_forward(const tsm_engine *e, const std::vector<int> 
     else if (can.conv31 && chosen(e->fuse31, blk.conv3, kCodeConv31)) p.conv31_next = true;
     hh = conv_out_size(hh, 3, blk.stride);
     ww = conv_out_size(ww, 3, blk.stride);
+    if (blk.tpool_after) nn /= 2;   // the temporal pool: layers 2-4 run on half the frames
   }
   return plan;
 }
@@ -690,7 +709,7 @@ struct Forward {
   hipStream_t s;
   const char *stage;
   Tap *tap;
-  int T, shiftT, prec;
+  int prec;
   float *t1, *t2, *idb;                // branch temporaries, the BasicBlock's downsample output
   std::vector<int> *tiles = nullptr;   // tile codes of this bucket (null: heuristic shapes -- TSM_AUTOTUNE=0 or a tap)
   bool tuning = false;                 // the bucket's tuning pass: time the candidates, write the winners into *tiles
@@ -703,7 +722,7 @@ struct Forward {
   BlockLaunches prev;
 
   Forward(tsm_engine *e_, hipStream_t s_, const char *stage_, Tap *tap_)
-      : e(e_), s(s_), stage(stage_), tap(tap_), T(e_->cfg.num_segments), shiftT(e_->cfg.is_shift ? T : 0), prec(e_->prec),
+      : e(e_), s(s_), stage(stage_), tap(tap_), prec(e_->prec),
         t1(e_->buf[2]), t2(e_->buf[3]), idb(e_->buf[4]) {}
 
   // TSM_WALK pins every direction (tests: each walk of each kernel at the engine's geometries); the alternation still
@@ -799,6 +818,7 @@ int Forward::run_basic(size_t k, int nn, float *x, float *y, int hh, int ww) {
   const Block &blk = e->blocks[k];
   const std::string &name = blk.name;
   const ConvLayer &c1 = e->convs[blk.conv1], &c2 = e->convs[blk.conv2];
+  const int T = blk.T, shiftT = e->cfg.is_shift ? T : 0;   // (the stage's segment count)
   const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   const float *identity = x;
   if (blk.down >= 0) {
@@ -883,7 +903,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
 int Forward::run_nonlocal(size_t k, int nn, float *x, float *z, int hh, int ww) {
   const Block &blk = e->blocks[k];
   const ConvLayer &cq = e->convs[blk.nl_qkv], &cw = e->convs[blk.nl_w];
-  const int d = cw.cin;
+  const int d = cw.cin, T = blk.T;
   const int64_t nq = nonlocal_positions(T, hh, ww), nkeys = nonlocal_keys(T, hh, ww);
   if (nq <= 0 || nkeys <= 0) return fail(e, TSM_ERR_UNSUPPORTED, blk.name + ": a non-local block needs at least 2 x 2 pixels");
   int rc = conv(blk.nl_qkv, make_params(cq, x, nullptr, t1, nn, hh, ww, false, 0, 1, prec), 1, false);
@@ -963,7 +983,8 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
 int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, float *d_logits,
                 hipStream_t s, const char *stage, Tap *tap) {
   const tsm_config &cfg = e->cfg;
-  const int T = cfg.num_segments, n = n_clips * T;
+  const int T = cfg.num_segments;
+  int n = n_clips * T;   // (a temporal-pool engine halves it behind layer1)
   Forward f(e, s, stage, tap);
   // Tile shape per conv layer for this frame count: tuned on first use by timing every valid shape on
   // the real launch (all shapes give bit-identical results: the k order per output does not depend on
@@ -1033,7 +1054,16 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
       if (rcn || f.tapped) return rcn;
       std::swap(cur, out);
     }
+    if (e->blocks[k].tpool_after) {   // the temporal pool: layer1's output (cur) -> T / 2 frames per clip in the dead buffer
+      const Block &blk = e->blocks[k];
+      const int c = e->convs[blk.conv3 >= 0 ? blk.conv3 : blk.conv2].cout;
+      TSM_LAUNCH(e, s, tsm::launch_temporal_maxpool(cur, out, n_clips, T, (int64_t)h * w, c, prec, s));
+      std::swap(cur, out);
+      n /= 2;
+      if (f.want("layer2.tpool")) return f.hit(cur, n, h, w, c);
+    }
   }
+  const int T_out = out_segments(e);
   if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
   if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
     TSM_LAUNCH(e, s, tsm::launch_pool_features(cur, e->features == 1 ? d_logits : nullptr, e->features == 2 ? d_logits : nullptr, n,
@@ -1044,7 +1074,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     TSM_LAUNCH(e, s, tsm::launch_head_segments(cur, e->d_fcw, e->d_fcb, d_logits, n, h * w, e->feat, cfg.num_class, prec, s));
     return TSM_OK;
   }
-  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T, h * w, e->feat,
+  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T_out, h * w, e->feat,
                                     cfg.num_class, prec, s));
   return TSM_OK;
 }
@@ -1089,6 +1119,7 @@ void retag_tune_sig(tsm_engine *e) {
   if (e->width != 64) e->tune_sig += " w" + std::to_string(e->width);
   if (e->place == 1) e->tune_sig += " block";
   if (e->non_local) e->tune_sig += " nl";
+  if (e->temporal_pool) e->tune_sig += " tp";
 }
 
 int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout, int n_clips) {
@@ -1342,7 +1373,19 @@ int tsm_set_non_local(tsm_engine *e, int32_t on) {
     return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks run in TSM_DTYPE_F32 only (the bf16 formats' fused forms do not know the block)");
   if (on && find_backbone(e->depth)->basic)
     return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks need a Bottleneck backbone (depth 50)");
+  if (on && e->temporal_pool) return fail(e, TSM_ERR_UNSUPPORTED, temporal_pool_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, 1));
   e->non_local = on;
+  build_topology(e);
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_temporal_pool(tsm_engine *e, int32_t on) {
+  if (int rc = check_before_weights(e, "tsm_set_temporal_pool")) return rc;
+  if (on != 0 && on != 1) return fail(e, TSM_ERR_UNSUPPORTED, "temporal_pool must be 0 or 1");
+  if (on)
+    if (const char *why = temporal_pool_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, e->non_local)) return fail(e, TSM_ERR_UNSUPPORTED, why);
+  e->temporal_pool = on;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1515,7 +1558,7 @@ int tsm_finalize(tsm_engine *e) {
   if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1)))) return rc;  // 16 bytes per pixel in every format (pairs: odd widths padded)
   if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
   // avg: one row per clip; identity: one per (clip, segment)
-  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
+  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? out_segments(e) : 1) * cfg.num_class, "d_logits",
                  (size_t)cfg.num_class))) return rc;
   if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
     e->partial_elems = (size_t)16 << 20;
@@ -1561,8 +1604,8 @@ static int forward_to(tsm_engine *e, const void *clips, int32_t memkind, int32_t
   TSM_HIP(e, hipEventRecord(e->ev1, s));
   e->have_time = true;
   if (memkind == TSM_MEM_HOST) {
-    const size_t elems = features ? (size_t)n_clips * e->cfg.num_segments * e->feat
-                                  : (size_t)n_clips * (e->consensus == 1 ? e->cfg.num_segments : 1) * e->cfg.num_class;
+    const size_t elems = features ? (size_t)n_clips * out_segments(e) * e->feat
+                                  : (size_t)n_clips * (e->consensus == 1 ? out_segments(e) : 1) * e->cfg.num_class;
     TSM_HIP(e, hipMemcpyAsync(out, d_stage, elems * sizeof(float), hipMemcpyDeviceToHost, s));
     TSM_HIP(e, hipStreamSynchronize(s));
   }

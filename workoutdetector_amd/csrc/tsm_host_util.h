@@ -175,6 +175,30 @@ inline int64_t nonlocal_keys(int T, int h, int w) { return nonlocal_positions(T,
 // Tiles of `tile` rows that cover n rows (the attention kernel's query tiles per clip and key tiles per query tile).
 inline int64_t tiles_over(int64_t n, int tile) { return n <= 0 || tile <= 0 ? 0 : (n + tile - 1) / tile; }
 
+// ---- temporal pool (TSM's make_temporal_pool: TemporalPool around layer2) -----------------------------------------------------
+// max_pool3d over time, kernel 3, stride 2, padding 1, per clip: T frames -> T / 2.  -1 for a T the engine does not pool
+// (not positive, or odd: the original's n_segment_list = [T, T // 2, ...] and its view(-1, T // 2, ...) assume an even T).
+inline int temporal_pool_segments(int T) { return T > 0 && T % 2 == 0 ? T / 2 : -1; }
+// The source frames of output frame t_out of a T-frame clip: {2 t_out - 1, 2 t_out, 2 t_out + 1} cut to [0, T), inclusive ends;
+// first > last when t_out is no output frame of such a clip.
+struct PoolWindow {
+  int first, last;
+};
+inline PoolWindow temporal_pool_window(int T, int t_out) {
+  if (temporal_pool_segments(T) < 0 || t_out < 0 || t_out >= T / 2) return {0, -1};
+  const int64_t lo = 2 * (int64_t)t_out - 1, hi = 2 * (int64_t)t_out + 1;
+  return {(int)(lo < 0 ? 0 : lo), (int)(hi > T - 1 ? T - 1 : hi)};
+}
+// Why an engine of this precision, shift flag, segment count and non-local flag cannot pool; nullptr when it can.
+inline const char *temporal_pool_refusal(int prec, int is_shift, int T, int non_local) {
+  if (prec == kPrecBf16)
+    return "the temporal pool runs in TSM_DTYPE_F32 and TSM_DTYPE_BF16X3 only (the bf16 cross-block and whole-block kernels tile over all T frames of a clip)";
+  if (!is_shift) return "the temporal pool needs is_shift = 1 (make_temporal_pool is a branch of make_temporal_shift)";
+  if (temporal_pool_segments(T) < 0) return "the temporal pool needs an even num_segments";
+  if (non_local) return "the temporal pool and the non-local blocks exclude each other (the non-local wrapper assumes one segment count)";
+  return nullptr;
+}
+
 // In the engine's storage format: fp32 as it is, split-bf16 in place, bf16 at half the length.
 inline void to_storage(std::vector<float> *v, int prec) {
   if (prec == kPrecBf16x3) to_split(v);

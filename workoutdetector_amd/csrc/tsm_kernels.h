@@ -152,6 +152,10 @@ hipError_t launch_maxpool3x3s2(const float *x, float *y, int n, int hi, int wi, 
                                hipStream_t s);
 hipError_t launch_temporal_shift(const float *x, float *y, int64_t n_frames, int n_segment,
                                  int64_t hw, int c, int fold, hipStream_t s);
+// temporal max-pool (see temporal_maxpool_kernel): x [n_clips * T, hw, c] -> y [n_clips * T / 2, hw, c] in `prec`'s storage
+// format (kPrecF32 or kPrecBf16x3), kernel 3 / stride 2 / padding 1 over the frames of each clip; T even, c a multiple of the
+// format's channel group; anything else hipErrorInvalidValue, nothing launched
+hipError_t launch_temporal_maxpool(const float *x, float *y, int64_t n_clips, int T, int64_t hw, int c, int prec, hipStream_t s);
 // pooled: scratch [n_clips * n_segment, c]
 hipError_t launch_head(const float *feat, const float *fc_w, const float *fc_b, float *pooled,
                        float *logits, int n_clips, int n_segment, int hw, int c, int num_class, int prec,

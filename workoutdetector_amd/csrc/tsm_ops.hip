@@ -622,7 +622,98 @@ hipError_t launch_maxpool3x3s2(const float *x, float *y, int n, int hi, int wi, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stand-alone temporal shift (NHWC fp32).  One thread per 16-B channel quad; fold % 4 == 0 so a quad
+// Temporal max-pool (TemporalPool in front of layer2: max_pool3d, kernel (3,1,1), stride (2,1,1), padding (1,0,0)) on NHWC
+// tensors in the storage format: output frame t' of a clip = max over its frames {2t'-1, 2t', 2t'+1} cut to [0, T), T even.
+// One thread owns a (clip, pixel, channel group) column and walks its T frames in order, keeping the last odd frame in
+// registers: every input group is loaded once, every output group stored once.  No LDS, no atomics; nothing depends on the
+// grid or on the other clips.  A group's words stay as they are: fp32 values by fmaxf; split-bf16 pairs (hi, lo) compared by
+// hi, then by lo -- |lo| <= ulp(hi) / 2, so that is the order of hi + lo -- and the winner's pair copied.  fp32 and split-bf16
+// only (the launcher refuses bf16: no bf16 engine pools).
+// ---------------------------------------------------------------------------------------------
+template <int FMT>
+struct PoolGroup {
+  u32x4 h, l;   // fp32: h = the four floats' bits; split-bf16: h | l, 8 elements each
+};
+
+template <int FMT>
+__device__ __forceinline__ PoolGroup<FMT> pool_load(const float *p) {
+  PoolGroup<FMT> g;
+  g.h = *reinterpret_cast<const u32x4 *>(p);
+  g.l = FMT == kPrecBf16x3 ? *reinterpret_cast<const u32x4 *>(p + 4) : u32x4{0u, 0u, 0u, 0u};
+  return g;
+}
+
+template <int FMT>
+__device__ __forceinline__ void pool_store(float *p, const PoolGroup<FMT> &g) {
+  *reinterpret_cast<u32x4 *>(p) = g.h;
+  if (FMT == kPrecBf16x3) *reinterpret_cast<u32x4 *>(p + 4) = g.l;
+}
+
+template <int FMT>
+__device__ __forceinline__ PoolGroup<FMT> pool_max(const PoolGroup<FMT> &a, const PoolGroup<FMT> &b) {
+  PoolGroup<FMT> m;
+  m.l = u32x4{0u, 0u, 0u, 0u};
+  if (FMT == kPrecF32) {   // (whole vectors through the cast: element by element on the words)
+    const f32x4 fa = __builtin_bit_cast(f32x4, a.h), fb = __builtin_bit_cast(f32x4, b.h);
+    m.h = __builtin_bit_cast(u32x4, f32x4{fmaxf(fa[0], fb[0]), fmaxf(fa[1], fb[1]), fmaxf(fa[2], fb[2]), fmaxf(fa[3], fb[3])});
+    return m;
+  }
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    {
+      unsigned keep_a = 0u;   // the 16-bit halves of word w that a wins
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int e = 2 * w + half;
+        const float ah = split_elem(a.h, e), bh = split_elem(b.h, e);
+        bool a_wins = ah > bh;
+        if (FMT == kPrecBf16x3) a_wins = a_wins || (ah == bh && split_elem(a.l, e) > split_elem(b.l, e));
+        if (a_wins) keep_a |= half ? 0xFFFF0000u : 0x0000FFFFu;
+      }
+      m.h[w] = (a.h[w] & keep_a) | (b.h[w] & ~keep_a);
+      if (FMT == kPrecBf16x3) m.l[w] = (a.l[w] & keep_a) | (b.l[w] & ~keep_a);
+    }
+  }
+  return m;
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(256) temporal_maxpool_kernel(const float *__restrict__ x, float *__restrict__ y,
+                                                               int64_t n_clips, int T, int64_t frame_groups) {
+  constexpr int GF = Fmt<FMT>::gf;
+  const int64_t total = n_clips * frame_groups;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t frame = frame_groups * GF;   // floats per frame
+  const int t_out = T / 2;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t clip = i / frame_groups, col = i - clip * frame_groups;
+    const float *src = x + clip * T * frame + col * GF;
+    float *dst = y + clip * t_out * frame + col * GF;
+    PoolGroup<FMT> odd = pool_load<FMT>(src);   // (frame 0 stands in for frame -1: max(x0, x0, x1) = max(x0, x1))
+    for (int t = 0; t < t_out; ++t) {
+      const PoolGroup<FMT> even = t == 0 ? odd : pool_load<FMT>(src + (int64_t)(2 * t) * frame);
+      const PoolGroup<FMT> next = pool_load<FMT>(src + (int64_t)(2 * t + 1) * frame);
+      pool_store<FMT>(dst + (int64_t)t * frame, pool_max<FMT>(pool_max<FMT>(odd, even), next));
+      odd = next;
+    }
+  }
+}
+
+hipError_t launch_temporal_maxpool(const float *x, float *y, int64_t n_clips, int T, int64_t hw, int c, int prec, hipStream_t s) {
+  const int gch = prec == kPrecF32 ? 4 : 8;
+  if (n_clips <= 0 || hw <= 0 || c <= 0 || c % gch != 0 || tsm_host::temporal_pool_segments(T) < 0) return hipErrorInvalidValue;
+  if (prec != kPrecF32 && prec != kPrecBf16x3) return hipErrorInvalidValue;   // (no bf16 engine pools: tsm_set_temporal_pool)
+  const int64_t frame_groups = hw * (c / gch);
+  const unsigned grid = grid_for(n_clips * frame_groups, 8192);
+  if (prec == kPrecF32)
+    TSM_KLAUNCH(temporal_maxpool_kernel<kPrecF32>, dim3(grid), dim3(256), 0, s, x, y, n_clips, T, frame_groups);
+  else
+    TSM_KLAUNCH(temporal_maxpool_kernel<kPrecBf16x3>, dim3(grid), dim3(256), 0, s, x, y, n_clips, T, frame_groups);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stand-alone temporal shift (NHWC fp32). One thread per 16-B channel quad; fold % 4 == 0 so a quad
 // never straddles a fold boundary.  tsm.py:35-50.  (The forward uses the conv kernel's fused loader.)
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) temporal_shift_kernel(const float *__restrict__ x,

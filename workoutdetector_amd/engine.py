@@ -48,10 +48,11 @@ class TsmEngine:
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
                  base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg',
-                 non_local: bool = False):
+                 non_local: bool = False, temporal_pool: bool = False):
         if base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
         _check_non_local(non_local, base_model, dtype)
+        _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
         if shift_place not in SHIFT_PLACES:
             raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
         if consensus_type not in CONSENSUS_TYPES:
@@ -68,6 +69,7 @@ class TsmEngine:
         self.shift_place = shift_place
         self.consensus_type = consensus_type
         self.non_local = bool(non_local)
+        self.temporal_pool = bool(temporal_pool)
         self.feature_dim = feature_width(base_model)      # row width of forward_features
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
@@ -85,6 +87,8 @@ class TsmEngine:
             _lib.check(self._lib.tsm_set_consensus(self._h, CONSENSUS_TYPES[consensus_type]), self._h)
         if non_local:
             _lib.check(self._lib.tsm_set_non_local(self._h, 1), self._h)
+        if temporal_pool:
+            _lib.check(self._lib.tsm_set_temporal_pool(self._h, 1), self._h)
         self._finalized = False
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -114,10 +118,17 @@ class TsmEngine:
     def get_outputs(self) -> List[NodeArg]:
         return [NodeArg(self.OUTPUT_NAME, [None] + list(self._out_shape(0)[1:]))]
 
+    @property
+    def out_segments(self) -> int:
+        """Segments per clip behind the backbone -- the rows of ``forward_features`` and of the 'identity' logits: T, or T / 2
+        behind the temporal pool."""
+        return self.num_segments // 2 if getattr(self, 'temporal_pool', False) else self.num_segments
+
     def _out_shape(self, b: int) -> tuple:
         """Logits of ``b`` clips: [b, num_class] ('avg'), [b, T, num_class] ('identity': the fc output of every segment,
-        tsm.py:165-174).  Dimension 0 is the clip axis either way, so a ``max_clips`` chunk is a contiguous slice."""
-        return (b, self.num_segments, self.num_class) if self.consensus_type == 'identity' else (b, self.num_class)
+        tsm.py:165-174; T / 2 segments behind the temporal pool).  Dimension 0 is the clip axis either way, so a ``max_clips``
+        chunk is a contiguous slice."""
+        return (b, self.out_segments, self.num_class) if self.consensus_type == 'identity' else (b, self.num_class)
 
     def run(self, output_names: Optional[Sequence[str]], input_feed: Dict[str, np.ndarray]) -> List[np.ndarray]:
         if output_names is not None and list(output_names) != [self.OUTPUT_NAME]:
@@ -223,7 +234,7 @@ class TsmEngine:
         ``out`` (CUDA input only): a contiguous float32 [B*T, feature_dim] tensor to write into, e.g. a band of a video's
         feature buffer.  Any engine: consensus, backbone, placement and dtype change nothing about the call."""
         self._need_finalized()
-        t, d = self.num_segments, self.feature_dim
+        t, d = self.out_segments, self.feature_dim
         if hasattr(clips, 'is_cuda'):
             import torch
             if not (clips.is_cuda and clips.dtype == torch.float32):
@@ -303,6 +314,8 @@ class TsmEngine:
                     names += ([p + '.downsample'] if b == 0 else []) + [p + '.conv1', p + '.conv2', p + '.conv3']
                     if self.non_local and (li, b) in NL_BLOCKS:
                         names += [p + '.nl.qkv', p + '.nl.pool', p + '.nl.attn', p + '.nl.W']
+            if self.temporal_pool and li == 1:      # the pool's own launch, behind layer1's last block
+                names.append('layer2.tpool')
         return names + ['head']
 
     TILE_NAMES = {0: 'heuristic', 1: '128x128', 2: '128x64', 3: '64x64', 4: '32x32', 5: '128x128w8', 6: '256x256', 7: 'ws',
@@ -327,7 +340,7 @@ class TsmEngine:
         buf = (C.c_int32 * 64)()
         n = C.c_int32()
         _lib.check(self._lib.tsm_conv_tiles(self._h, n_clips, buf, 64, C.byref(n)), self._h)
-        names = [k for k in self.launch_names() if k not in ('pack_input', 'maxpool', 'head') and not k.endswith(('.nl.pool', '.nl.attn'))]
+        names = [k for k in self.launch_names() if k not in ('pack_input', 'maxpool', 'head', 'layer2.tpool') and not k.endswith(('.nl.pool', '.nl.attn'))]
         assert n.value == len(names)
         return {k: self.tile_name(buf[i]) for i, k in enumerate(names)}
 
@@ -373,12 +386,28 @@ def _check_non_local(non_local: bool, base_model: str, dtype: str) -> None:
         raise NotImplementedError(f"non_local=True runs in dtype='f32' only, not {dtype!r}")
 
 
+def _check_temporal_pool(temporal_pool: bool, num_segments: int, is_shift: bool, dtype: str, non_local: bool) -> None:
+    """``temporal_pool=True`` is refused up front, never ignored, where the engine cannot pool: ``dtype='bf16'`` (its cross-block
+    and whole-block kernels tile over all T frames of a clip), ``is_shift=False`` (make_temporal_pool is a branch of
+    make_temporal_shift), an odd ``num_segments``, and together with ``non_local=True`` (whose wrapper assumes one segment count)."""
+    if not temporal_pool:
+        return
+    if dtype == 'bf16':
+        raise NotImplementedError("temporal_pool=True runs in dtype='f32' and 'bf16x3' only, not 'bf16'")
+    if non_local:
+        raise NotImplementedError('temporal_pool=True and non_local=True exclude each other')
+    if not is_shift:
+        raise ValueError('temporal_pool=True needs is_shift=True')
+    if num_segments <= 0 or num_segments % 2:
+        raise ValueError(f'temporal_pool=True needs an even num_segments, got {num_segments}')
+
+
 def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'resnet50',
                  checkpoint: Optional[str] = None, device: Optional[object] = None, fc_lr5: bool = True,
                  is_shift: bool = True, shift_div: int = 8, shift_place: str = 'blockres',
                  consensus_type: str = 'avg', img_feature_dim: int = 256, non_local: bool = False,
                  height: int = 224, width: int = 224, max_clips: int = 32, seed: int = 0, dtype: str = 'f32',
-                 **kwargs) -> TsmEngine:
+                 temporal_pool: bool = False, **kwargs) -> TsmEngine:
     """Counterpart of the reference factory (tsm.py:422-476) returning a ready TsmEngine.
 
     ``checkpoint`` is a ``torch.save``d dict with a ``state_dict`` entry (mmaction2 ``backbone.*``/``cls_head.*``
@@ -402,6 +431,11 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     (self-attention over all T*H*W positions of a clip; state-dict keys ``layerL.B.block.*`` / ``layerL.B.nl.*``,
     include/tsm_hip.h: tsm_set_non_local).  ``dtype='f32'`` and Bottleneck backbones only; the bf16 formats, resnet18 / 34 and
     an ``.onnx`` checkpoint raise NotImplementedError, and mmaction2's non-local key spelling is not mapped.
+    ``temporal_pool=True``: layer2 is wrapped in TemporalPool (a max-pool over time, kernel 3, stride 2, padding 1, per clip:
+    include/tsm_hip.h: tsm_set_temporal_pool), so layers 2-4 and the head see ``num_segments // 2`` frames per clip
+    (``engine.out_segments``): 'avg' logits stay [B, num_class], 'identity' logits are [B, T/2, num_class].  A checkpoint's
+    ``layer2.net.<b>.*`` keys are mapped (``weights.remap_checkpoint_keys``).  ``dtype='bf16'``, ``non_local=True`` and an
+    ``.onnx`` checkpoint raise NotImplementedError; ``is_shift=False`` and an odd ``num_segments`` raise ValueError.
     """
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
@@ -409,8 +443,11 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     if shift_place not in SHIFT_PLACES:
         raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
     _check_non_local(non_local, base_model, dtype)
+    _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
     if non_local and checkpoint is not None and str(checkpoint).endswith('.onnx'):
         raise NotImplementedError('non_local=True with an .onnx checkpoint: the importer does not read non-local blocks')
+    if temporal_pool and checkpoint is not None and str(checkpoint).endswith('.onnx'):
+        raise NotImplementedError('temporal_pool=True with an .onnx checkpoint: the importer does not read the pooled graph')
     dev = 0
     if device is not None:
         s = str(device)
@@ -428,13 +465,13 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
         if non_local and is_mmaction_state_dict(raw):
             raise NotImplementedError('non_local=True with an mmaction2 checkpoint: its non-local key spelling is not mapped')
         sd = (remap_mmaction_keys(raw) if is_mmaction_state_dict(raw)
-              else remap_checkpoint_keys(raw, num_class, base_model, non_local=non_local))
+              else remap_checkpoint_keys(raw, num_class, base_model, non_local=non_local, temporal_pool=temporal_pool))
     else:
         sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model, shift_place=shift_place, non_local=non_local)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width,
                      shift_div=shift_div, is_shift=is_shift, max_clips=max_clips, device=dev, state_dict=sd,
                      dtype=dtype, base_model=base_model, shift_place=shift_place, consensus_type=consensus_type,
-                     non_local=non_local)
+                     non_local=non_local, temporal_pool=temporal_pool)
 
 
 def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpoint: Optional[str] = None, max_frames: int = 32,

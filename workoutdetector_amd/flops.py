@@ -57,6 +57,15 @@ def nonlocal_table(num_segments: int = 8, height: int = 224, width: int = 224, b
 
 
 def flops_per_clip(num_segments: int = 8, height: int = 224, width: int = 224, num_class: int = 12,
-                   base_model: str = 'resnet50', non_local: bool = False) -> float:
+                   base_model: str = 'resnet50', non_local: bool = False, temporal_pool: bool = False) -> float:
+    """``temporal_pool=True`` (``create_model(temporal_pool=True)``): the stem and layer1 run on all ``num_segments`` frames of a
+    clip, layers 2-4 and the classifier on the ``num_segments // 2`` frames the pool leaves; the pool itself counts zero FLOPs."""
     nl = sum(r['conv_macs'] + r['attn_macs'] for r in nonlocal_table(num_segments, height, width, base_model)) if non_local else 0
-    return 2.0 * (macs_per_frame(height, width, num_class, base_model) * num_segments + nl)
+    if not temporal_pool:
+        return 2.0 * (macs_per_frame(height, width, num_class, base_model) * num_segments + nl)
+    if non_local or num_segments <= 0 or num_segments % 2:
+        raise ValueError('temporal_pool=True needs an even num_segments and excludes non_local=True')
+    rows = layer_table(height, width, base_model)
+    pooled = sum(r['macs'] for r in rows if r['name'].startswith(('layer2.', 'layer3.', 'layer4.'))) + feature_width(base_model) * num_class
+    full = sum(r['macs'] for r in rows if not r['name'].startswith(('layer2.', 'layer3.', 'layer4.')))
+    return 2.0 * (full * num_segments + pooled * (num_segments // 2))

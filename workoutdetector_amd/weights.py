@@ -183,7 +183,8 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
 
 
 def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
-                          base_model: str = 'resnet50', non_local: bool = False) -> 'OrderedDict[str, object]':
+                          base_model: str = 'resnet50', non_local: bool = False,
+                          temporal_pool: bool = False) -> 'OrderedDict[str, object]':
     """Checkpoint ``state_dict`` (``module.``/``model.``-prefixed) -> engine keys, exactly as create_model does it
     (models/tsm.py:451-473; pinned by tests/golden/ref_ckpt_remap.json, produced by executing those statements):
     the LAST TWO entries are the classifier; they become ``fc.weight`` / ``fc.bias`` iff the weight has ``num_class``
@@ -193,7 +194,10 @@ def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
     The rule does not depend on the backbone; ``base_model`` is checked to be one the engine implements.
     ``non_local=True``: a TSM-NL checkpoint's ``layerL.B.block.*`` / ``layerL.B.nl.*`` keys pass through the same rule (they are
     the engine's spelling already); a checkpoint without any ``.nl.`` key is refused here, by name, rather than at the
-    engine's first missing tensor.  mmaction2's NL spelling is not mapped."""
+    engine's first missing tensor.  mmaction2's NL spelling is not mapped.
+    ``temporal_pool=True``: TemporalPool holds layer2 as ``net``, so a temporal-pool checkpoint spells the stage's keys
+    ``base_model.layer2.net.<b>.<rest>`` (``layer2.net.<b>.net.<rest>`` under block placement); the wrapper's ``net.`` is dropped,
+    which gives the engine's keys.  A checkpoint with plain ``layer2.<b>.`` keys passes unchanged."""
     _backbone(base_model)
     if _non_local(non_local, base_model) and not any('.nl.' in k for k in state_dict):
         raise KeyError('non_local=True, but the checkpoint has no non-local block tensors (no ".nl." key)')
@@ -205,7 +209,11 @@ def remap_checkpoint_keys(state_dict: Mapping[str, object], num_class: int,
         items['module.fc.bias'] = items[fc_b]
     del items[fc_w]
     del items[fc_b]
-    return OrderedDict(('.'.join(k.split('.')[1:]), v) for k, v in items.items())
+    out = OrderedDict(('.'.join(k.split('.')[1:]), v) for k, v in items.items())
+    if temporal_pool:
+        wrapped = 'base_model.layer2.net.'
+        out = OrderedDict((('base_model.layer2.' + k[len(wrapped):]) if k.startswith(wrapped) else k, v) for k, v in out.items())
+    return out
 
 
 def remap_torchvision_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, object]':

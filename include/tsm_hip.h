@@ -108,7 +108,31 @@ typedef enum tsm_layout {
                              TSM_DTYPE_BF16 engine */
 } tsm_layout;
 
-typedef enum tsm_pixel { TSM_PIXEL_U8 = 0, TSM_PIXEL_F32 = 1 } tsm_pixel;
+/* The staged frames of a frame transform (tsm_preprocess, _clips, _indexed, _windows).
+ *   TSM_PIXEL_U8 / TSM_PIXEL_F32   [h, w, 3] RGB, values 0..255.
+ *   TSM_PIXEL_NV12_*               what a hardware decoder leaves: h * w luma bytes, then h / 2 rows of w bytes of interleaved
+ *     (U, V) pairs -- dense (no pitch; the chroma plane follows the luma plane directly), h and w even, 3 h w / 2 bytes per
+ *     frame, frames of a buffer at that distance.  Converted inside the transform's taps, never written as RGB: luma pixel
+ *     (y, x) takes the pair at chroma row y >> 1, bytes 2 (x >> 1) and 2 (x >> 1) + 1 (nearest-neighbour chroma, as
+ *     cv2.COLOR_YUV2RGB_NV12), and with C = Y - y_off, D = U - 128, E = V - 128, in int32 with an arithmetic shift:
+ *       R = clamp((cy C + crv E + 8192) >> 14, 0, 255)
+ *       G = clamp((cy C + cgu D + cgv E + 8192) >> 14, 0, 255)
+ *       B = clamp((cy C + cbu D + 8192) >> 14, 0, 255)
+ *                       y_off     cy    crv    cgu     cgv    cbu
+ *       BT601 (limited)    16  19077  26149  -6419  -13320  33050
+ *       BT709 (limited)    16  19077  29372  -3494   -8731  34610
+ *       BT601_FULL          0  16384  22970  -5638  -11700  29032
+ *       BT709_FULL          0  16384  25802  -3069   -7670  30402
+ *     Everything behind the conversion (bilinear taps, zero fill, normalisation) is the RGB transform's, bit for bit that of
+ *     the converted frame.  Codes 2..15 and 20 on are invalid. */
+typedef enum tsm_pixel {
+  TSM_PIXEL_U8 = 0,
+  TSM_PIXEL_F32 = 1,
+  TSM_PIXEL_NV12_BT601 = 16,
+  TSM_PIXEL_NV12_BT709 = 17,
+  TSM_PIXEL_NV12_BT601_FULL = 18,
+  TSM_PIXEL_NV12_BT709_FULL = 19
+} tsm_pixel;
 
 /* Arithmetic of the conv stack.
  *   TSM_DTYPE_F32     fp32 storage, exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): bit-for-bit an fp32 fma chain.
@@ -386,6 +410,8 @@ int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi
  *   build_test_transform(person_crop=False) = ConvertImageDtype -> Resize(resize) -> CenterCrop(crop)
  *   -> Normalize(ImageNet)            workoutdetector/datasets/build.py:131-136
  * frames: [n, h, w, 3] decoder layout, TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255).
+ *         or [n, 3h/2, w] bytes with a TSM_PIXEL_NV12_* code (tsm_pixel): h, w the luma size, both even (an odd side is
+ *         TSM_ERR_INVALID_ARG, nothing launched), `frames` 2-byte aligned.
  * out:    out_layout TSM_LAYOUT_NTHWC4 -> [n, crop, crop, 4] fp32, TSM_LAYOUT_NTHWC8S -> split-bf16 /
  *         TSM_LAYOUT_NTHWC8B -> bf16 pixel pairs [n, crop, ceil(crop/2), 8] (feed tsm_forward of an engine
  *         of the matching dtype directly) or TSM_LAYOUT_NTCHW -> [n, 3, crop, crop] fp32.
@@ -416,7 +442,8 @@ int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, 
  *   datasets/build.py:123-129, datasets/transform.py:226-259 -- from the detector's box on; the Faster-RCNN detector is not
  *   part of this library, the boxes are the caller's.
  * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255), tsm_gather_clips' convention: buffer frame j =
- *         source frame clip_stride * (first_frame + j).
+ *         source frame clip_stride * (first_frame + j).  Or NV12 frames of 3 h w / 2 bytes (a TSM_PIXEL_NV12_* code, h and w
+ *         even, `frames` 2-byte aligned); the box is in luma pixels and a tap outside the frame is RGB 0, not a YUV value.
  * boxes:  DEVICE int32 [n_clips, 4] = (top, left, bh, bw) in source-frame pixels, row c for clip first_clip + c.
  * out:    [n_clips, n_segment, ...one frame] in out_layout, as tsm_preprocess with `size` in place of `crop`.
  *   out[c][k] = source frame s = clip_step * (first_clip + c) + clip_stride * k, cropped to box c, resized to size x size
@@ -443,6 +470,7 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
  * irregular lists (a segment shorter than 8 frames repeats frames, two segments of one video share no window, unsampled
  * frames are never needed) that the regular windows of tsm_gather_clips / tsm_preprocess_clips cannot express.
  * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255): whatever frames the caller staged.
+ *         Or NV12 frames of 3 h w / 2 bytes (a TSM_PIXEL_NV12_* code, h and w even, `frames` 2-byte aligned).
  * index:  DEVICE int32 [n_clips * n_segment], buffer-frame numbers.
  * out:    [n_clips, n_segment, ...one frame] in out_layout; out_layout, resize, crop, scale_255 as tsm_preprocess.
  *   out[c][k] = tsm_preprocess' result for buffer frame index[c * n_segment + k] (build_test_transform(person_crop=False):
@@ -462,7 +490,8 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
  * tsm_forward in ONE launch, in batch order -- a step of a stream server (StreamBatcher), whose streams differ in resolution
  * and complete their windows together; with person_crop = 1 the reference's accuracy option on streams.
  * arena:  one device allocation of arena_bytes, 16-byte aligned, holding every window's frames; pixel: TSM_PIXEL_U8 or
- *         TSM_PIXEL_F32 (values 0..255) for the whole launch.
+ *         TSM_PIXEL_F32 (values 0..255) for the whole launch, or a TSM_PIXEL_NV12_* code: then a window is n_segment
+ *         contiguous NV12 frames of 3 h w / 2 bytes, and a descriptor with an odd h or w is invalid (zero frames).
  * desc:   DEVICE int32 [n_windows, 8], 16-byte aligned; row c = {off_lo, off_hi, h, w, top, left, bh, bw}:
  *           off = off_hi * 2^32 + (unsigned) off_lo, the byte offset in `arena` of window c's first frame; its n_segment
  *                 frames are contiguous [n_segment, h, w, 3] of `pixel`;

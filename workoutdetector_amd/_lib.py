@@ -13,6 +13,19 @@ ABI_VERSION = 7
 MEM_HOST, MEM_DEVICE = 0, 1
 LAYOUT_NTCHW, LAYOUT_NTHWC, LAYOUT_NTHWC4, LAYOUT_NTHWC8S, LAYOUT_NTHWC8B = 0, 1, 2, 3, 4
 PIXEL_U8, PIXEL_F32 = 0, 1
+PIXEL_NV12_BT601, PIXEL_NV12_BT709, PIXEL_NV12_BT601_FULL, PIXEL_NV12_BT709_FULL = 16, 17, 18, 19
+_NV12_PIXELS = {'bt601': PIXEL_NV12_BT601, 'bt709': PIXEL_NV12_BT709, 'bt601-full': PIXEL_NV12_BT601_FULL,
+                'bt709-full': PIXEL_NV12_BT709_FULL}
+
+
+def nv12_pixel(colorimetry: str = 'bt601') -> int:
+    """The tsm_pixel code of NV12 frames of a colorimetry (transform.COLORIMETRIES), or ValueError."""
+    try:
+        return _NV12_PIXELS[colorimetry]
+    except (KeyError, TypeError):
+        raise ValueError(f'colorimetry must be one of {tuple(_NV12_PIXELS)}, got {colorimetry!r}') from None
+
+
 DTYPE_F32, DTYPE_BF16X3, DTYPE_BF16 = 0, 1, 2
 CONV_CODE_SEGMENTED = 0x4000   # TSM_CONV_CODE_SEGMENTED: tsm_conv_args.code only
 DTYPES = {'f32': DTYPE_F32, 'bf16x3': DTYPE_BF16X3, 'bf16': DTYPE_BF16}

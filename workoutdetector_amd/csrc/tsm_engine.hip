@@ -1217,10 +1217,22 @@ static int out_mode_of(int32_t out_layout, int *mode) {          // PreprocParam
 // The pixel type, output layout and scale of a frame transform, checked and written into its parameter block.
 template <typename P>
 static int set_pixel_format(P *p, int32_t pixel, int32_t out_layout, int32_t scale_255) {
-  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  tsm_host::Nv12Coef k{};
+  p->src_is_nv12 = tsm_host::nv12_coefficients(pixel, &k);
+  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32 && !p->src_is_nv12) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
   if (int rc = out_mode_of(out_layout, &p->out_mode)) return rc;
   p->src_is_u8 = pixel == TSM_PIXEL_U8;
+  const int32_t words[tsm_host::kNv12CoefWords] = {k.y_off, k.cy, k.crv, k.cgu, k.cgv, k.cbu};
+  memcpy(p->nv12, words, sizeof words);
   p->pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
+  return TSM_OK;
+}
+// NV12 frames of a launch whose frame size is an argument: both sides even, the buffer 2-byte aligned.
+static int check_nv12_frames(const char *op, int32_t pixel, const void *frames, int h, int w) {
+  if (!tsm_host::pixel_is_nv12(pixel)) return TSM_OK;
+  if ((h | w) & 1)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, std::string(op) + ": NV12 frames need an even h and an even w, got " + std::to_string(h) + " x " + std::to_string(w));
+  if (reinterpret_cast<uintptr_t>(frames) & 1) return fail(nullptr, TSM_ERR_INVALID_ARG, std::string(op) + ": NV12 frames must be 2-byte aligned");
   return TSM_OK;
 }
 // Resize(resize) + CenterCrop(crop) of an h x w frame into a PreprocParams / ImagePreprocParams (tsm_host::center_crop_geometry);
@@ -1885,6 +1897,7 @@ int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int3
     return fail(nullptr, TSM_ERR_INVALID_ARG, "bad preprocess arguments");
   tsm::PreprocParams p{};
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
+  if (int rc = check_nv12_frames("preprocess", pixel, frames, h, w)) return rc;
   p.src = frames; p.dst = out; p.n = n;
   if (!set_crop_geometry(&p, h, w, resize, crop)) return fail(nullptr, TSM_ERR_INVALID_ARG, "crop larger than the resized frame");
   return op_status("preprocess", tsm::launch_preprocess(p, static_cast<hipStream_t>(stream)));
@@ -1911,6 +1924,7 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: non-positive size");
   tsm::ClipPreprocParams p{};
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
+  if (int rc = check_nv12_frames("preprocess_clips", pixel, frames, h, w)) return rc;
   p.src = frames; p.dst = out; p.boxes = boxes; p.n_frames = n_frames; p.first_frame = first_frame;
   p.total_frames = total_frames; p.first_clip = first_clip; p.n_clips = n_clips; p.n_segment = n_segment;
   p.clip_step = clip_step; p.clip_stride = clip_stride; p.h = h; p.w = w; p.size = size;
@@ -1927,6 +1941,7 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
   tsm::IndexedPreprocParams q{};
   tsm::PreprocParams &p = q.pp;
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
+  if (int rc = check_nv12_frames("preprocess_indexed", pixel, frames, h, w)) return rc;
   q.index = index; q.n_frames = n_frames; q.n_rows = (int64_t)n_clips * n_segment;
   p.src = frames; p.dst = out;
   if (!set_crop_geometry(&p, h, w, resize, crop))

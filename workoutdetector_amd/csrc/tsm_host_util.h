@@ -1,7 +1,7 @@
 // Pure-host pieces of the engine: BatchNorm folding / weight packing, the bf16 storage-format converters, the
 // segment-length rule, a conv layer's packed geometry and the shapes of its launch's parameter block (conv_shape_params),
-// tsm_conv_op's argument rules (conv_op_check), the frame transforms' window and crop arithmetic and the TSM_TUNE_CACHE line
-// parser.  (The launch rules themselves: tsm_conv_rules.h.)  No HIP types, so this header also compiles with plain
+// tsm_conv_op's argument rules (conv_op_check), the frame transforms' window and crop arithmetic, the NV12 conversion and the
+// TSM_TUNE_CACHE line parser.  (The launch rules themselves: tsm_conv_rules.h.)  No HIP types, so this header also compiles with plain
 // g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined, fuzzes the parser and drives conv_op_check over
 // its refusals, its accepted forms and the ends of int32 (CPU only; GPU ASAN is not available on this pool).
 #pragma once
@@ -461,6 +461,66 @@ TSM_HOST_DEVICE inline bool window_descriptor_ok(const int32_t d[kWindowDescWord
   const int h = d[2], w = d[3];
   if (o < 0 || (o & 15) != 0 || h < 1 || h > kWindowMaxSide || w < 1 || w > kWindowMaxSide || o > arena_bytes) return false;
   const int64_t frame_bytes = (int64_t)h * w * 3 * elem_bytes;       // < 2^36
+  int64_t bytes;
+  if (__builtin_mul_overflow((int64_t)n_segment, frame_bytes, &bytes) || bytes > arena_bytes - o) return false;
+  if (center && !center_crop_geometry_int(h, w, resize, crop, g)) return false;
+  *off = o;
+  return true;
+}
+
+// ---- NV12 frames (TSM_PIXEL_NV12_*): the integer arithmetic the frame-transform kernels run, as functions that compile for
+// the host too (tests/nv12_host.cpp, under ASAN + UBSAN).  One frame is h * w luma bytes, then h / 2 rows of w bytes of
+// interleaved (U, V) pairs, dense; h and w are even.  A 2x2 block of luma pixels shares one pair (nearest-neighbour chroma).
+//   C = Y - y_off, D = U - 128, E = V - 128
+//   R = clamp((cy C + crv E + 8192) >> 14),  G = clamp((cy C + cgu D + cgv E + 8192) >> 14),  B = clamp((cy C + cbu D + 8192) >> 14)
+// in int32 (the largest magnitude is below 2^24), the coefficients round(x * 2^14) of the BT.601 / BT.709 matrices.
+struct Nv12Coef {
+  int32_t y_off, cy, crv, cgu, cgv, cbu;
+};
+constexpr int kNv12CoefWords = 6;   // a launch's parameter block carries the row as six plain words, in the struct's order
+TSM_HOST_DEVICE inline Nv12Coef nv12_coef_of(const int32_t k[kNv12CoefWords]) { return {k[0], k[1], k[2], k[3], k[4], k[5]}; }
+TSM_HOST_DEVICE inline bool pixel_is_nv12(int pixel) { return pixel >= TSM_PIXEL_NV12_BT601 && pixel <= TSM_PIXEL_NV12_BT709_FULL; }
+// The coefficient row of an NV12 pixel code; false (and *k untouched) for any other code.
+TSM_HOST_DEVICE inline bool nv12_coefficients(int pixel, Nv12Coef *k) {
+  switch (pixel) {
+    case TSM_PIXEL_NV12_BT601: *k = {16, 19077, 26149, -6419, -13320, 33050}; return true;
+    case TSM_PIXEL_NV12_BT709: *k = {16, 19077, 29372, -3494, -8731, 34610}; return true;
+    case TSM_PIXEL_NV12_BT601_FULL: *k = {0, 16384, 22970, -5638, -11700, 29032}; return true;
+    case TSM_PIXEL_NV12_BT709_FULL: *k = {0, 16384, 25802, -3069, -7670, 30402}; return true;
+    default: return false;
+  }
+}
+// Bytes of one h x w frame of a pixel code (h, w in 1 .. 65535: below 2^36); -1 for an unknown code, or an NV12 code with an
+// odd side.
+TSM_HOST_DEVICE inline int64_t frame_bytes_of(int pixel, int h, int w) {
+  if (h < 1 || w < 1) return -1;
+  const int64_t hw = (int64_t)h * w;
+  if (pixel == TSM_PIXEL_U8) return hw * 3;
+  if (pixel == TSM_PIXEL_F32) return hw * 12;
+  if (pixel_is_nv12(pixel)) return ((h | w) & 1) ? -1 : hw / 2 * 3;
+  return -1;
+}
+TSM_HOST_DEVICE inline int nv12_clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// One pixel: bytes (Y, U, V) -> rgb[3] in 0 .. 255.
+TSM_HOST_DEVICE inline void nv12_pixel_rgb(const Nv12Coef &k, int Y, int U, int V, int rgb[3]) {
+  const int c = k.cy * (Y - k.y_off) + 8192, d = U - 128, e = V - 128;
+  rgb[0] = nv12_clamp255((c + k.crv * e) >> 14);
+  rgb[1] = nv12_clamp255((c + k.cgu * d + k.cgv * e) >> 14);
+  rgb[2] = nv12_clamp255((c + k.cbu * d) >> 14);
+}
+// Byte offsets in an h x w frame of luma pixel (y, x) and of the U byte of its chroma pair (V follows; the offset is even).
+TSM_HOST_DEVICE inline int64_t nv12_luma_offset(int w, int64_t y, int64_t x) { return y * w + x; }
+TSM_HOST_DEVICE inline int64_t nv12_chroma_offset(int h, int w, int64_t y, int64_t x) {
+  return (int64_t)h * w + (y >> 1) * w + ((x >> 1) << 1);
+}
+// window_descriptor_ok for a window of NV12 frames: n_segment contiguous frames of 3 h w / 2 bytes, h and w even.
+TSM_HOST_DEVICE inline bool nv12_window_descriptor_ok(const int32_t d[kWindowDescWords], int n_segment, int64_t arena_bytes, bool center,
+                                                      int resize, int crop, int64_t *off, CropGeometry *g) {
+  const int64_t o = (int64_t)(((uint64_t)(uint32_t)d[1] << 32) | (uint32_t)d[0]);
+  const int h = d[2], w = d[3];
+  if (o < 0 || (o & 15) != 0 || h < 2 || h > kWindowMaxSide || w < 2 || w > kWindowMaxSide || ((h | w) & 1) != 0 || o > arena_bytes)
+    return false;
+  const int64_t frame_bytes = (int64_t)h * w / 2 * 3;       // < 2^33
   int64_t bytes;
   if (__builtin_mul_overflow((int64_t)n_segment, frame_bytes, &bytes) || bytes > arena_bytes - o) return false;
   if (center && !center_crop_geometry_int(h, w, resize, crop, g)) return false;

@@ -42,7 +42,7 @@ hipError_t launch_pack_input(const float *src, float *dst, int64_t n_frames, int
 // fp32 [n8 * 8 channels] <-> the storage format of `prec` (kPrecBf16x3 or kPrecBf16)
 hipError_t launch_from_f32(const float *x, float *y, int64_t n8, int prec, hipStream_t s);
 hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStream_t s);
-// Fused test transform: [n,h,w,3] u8|f32 frames -> resize (short side -> `resize`, bilinear, no
+// Fused test transform: [n,h,w,3] u8|f32 (or [n,3h/2,w] NV12) frames -> resize (short side -> `resize`, bilinear, no
 // antialias, align_corners=False) -> centre crop -> ImageNet normalise -> NHWC4 (out_nchw=0) or NCHW.
 struct PreprocParams {
   const void *src;
@@ -51,6 +51,8 @@ struct PreprocParams {
   int nh, nw;         // resized size
   int top, left, crop;
   int src_is_u8;
+  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // 0 = NHWC4 fp32, 1 = NCHW fp32, 2 = NHWC8 split-bf16, 3 = NHWC8 bf16
   float pre_scale;    // 1/255 when frames are to be scaled to [0,1] first, else 1
 };
@@ -79,6 +81,8 @@ struct ClipPreprocParams {
   int n_clips, n_segment, clip_step, clip_stride;
   int h, w, size;
   int src_is_u8;
+  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // as PreprocParams
   float pre_scale;
 };
@@ -110,6 +114,8 @@ struct WindowPreprocParams {
   int person_crop;
   int resize, crop;   // crop: the output size in both modes
   int src_is_u8;
+  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // as PreprocParams
   float pre_scale;
 };

@@ -164,13 +164,15 @@ hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStre
 }
 
 // ---------------------------------------------------------------------------------------------
-// Frame transforms: staged raw frames [n,h,w,3] u8|f32 -> resized, normalised frames in the engine's input formats.
+// Frame transforms: staged raw frames [n,h,w,3] u8|f32, or NV12 [n,3h/2,w] bytes, -> resized, normalised frames in the
+// engine's input formats.
 // One thread per output group: a pixel (out_mode 0 NHWC4 fp32, 1 NCHW fp32) or a pixel pair (2 split-bf16, 3 bf16: the
 // stem's packed-pair input, see pack_input_kernel); neighbouring threads are neighbouring ox: contiguous 16-byte stores.
 // preprocess_kernel, preprocess_indexed_kernel, preprocess_clips_kernel and preprocess_windows_kernel are ONE row loop
-// (preprocess_rows) over four row sources -- which frame, and which window of it, output row f shows -- and two samplers over one bilinear-and-
-// normalise core; preprocess_image_kernel (Pillow's antialiased resample, further down) shares the constants and the
-// group writer.  Bilinear sampling follows ATen's CPU kernel (UpSampleBilinear2d, no antialias): src = scale * (dst + 0.5)
+// (preprocess_rows) over four row sources -- which frame, and which window of it, output row f shows -- and two samplers over
+// one bilinear-and-normalise core, which read their taps from one of three tap sources (Taps<T>); preprocess_image_kernel
+// (Pillow's antialiased resample, further down) shares the constants and the group writer.
+// Bilinear sampling follows ATen's CPU kernel (UpSampleBilinear2d, no antialias): src = scale * (dst + 0.5)
 // - 0.5 clamped at 0, scale = in / out, out = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11); then
 // (v * pre_scale - mean) / std.  datasets/build.py:123-136 of the reference (torchvision tensor transforms).
 // ---------------------------------------------------------------------------------------------
@@ -220,6 +222,79 @@ __device__ __forceinline__ void store_pixel_group(float *dst, int out_mode, int 
   }
 }
 
+// Tap sources: the frame a sampler reads.  Taps<T> is one staged frame of a launch; quad() gives the three channel values, as
+// floats, of the four taps (y0 | y1, x0 | x1) of a bilinear sample.  Coordinates lie in the frame; a tap whose mask is false
+// is RGB 0 (the person crop's zero fill) whatever the frame holds there.
+//   * Taps<unsigned char>, Taps<float>: [h, w, 3] of T, three loads per tap.
+//   * Taps<Nv12>: h * w luma bytes, then h / 2 rows of w bytes of (U, V) pairs (tsm_host_util.h: the layout, the integer
+//     conversion and both offsets are the host's text).  A tap is one luma byte and one aligned 2-byte chroma load (U the low
+//     byte); taps of one 2x2 block share a pair, so the second column and the second row load only where they leave the block
+//     of the first.  The conversion's three integers in 0 .. 255 become floats exactly as a staged uint8 RGB frame's bytes do.
+struct Nv12 {};
+template <typename T>
+struct Taps {
+  const T *frame;
+  int w;
+  static __device__ __forceinline__ Taps of(const void *base, int64_t j, int h, int w, const int32_t *) {
+    return {static_cast<const T *>(base) + j * (int64_t)h * w * 3, w};
+  }
+  static __device__ __forceinline__ bool descriptor_ok(const int32_t *d, int n_segment, int64_t arena_bytes, bool center, int resize,
+                                                       int crop, int64_t *off, tsm_host::CropGeometry *g) {
+    return tsm_host::window_descriptor_ok(d, n_segment, (int)sizeof(T), arena_bytes, center, resize, crop, off, g);
+  }
+  __device__ __forceinline__ void quad(int64_t y0, int64_t y1, int64_t x0, int64_t x1, bool m00, bool m01, bool m10, bool m11,
+                                       float t[4][3]) const {
+    const T *r0 = frame + y0 * w * 3, *r1 = frame + y1 * w * 3;
+    const T *a00 = r0 + x0 * 3, *a01 = r0 + x1 * 3, *a10 = r1 + x0 * 3, *a11 = r1 + x1 * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      t[0][c] = m00 ? (float)a00[c] : 0.f;
+      t[1][c] = m01 ? (float)a01[c] : 0.f;
+      t[2][c] = m10 ? (float)a10[c] : 0.f;
+      t[3][c] = m11 ? (float)a11[c] : 0.f;
+    }
+  }
+};
+template <>
+struct Taps<Nv12> {
+  const unsigned char *frame;
+  int h, w;
+  tsm_host::Nv12Coef k;
+  static __device__ __forceinline__ Taps of(const void *base, int64_t j, int h, int w, const int32_t *coef) {
+    return {static_cast<const unsigned char *>(base) + j * ((int64_t)h * w / 2 * 3), h, w, tsm_host::nv12_coef_of(coef)};
+  }
+  static __device__ __forceinline__ bool descriptor_ok(const int32_t *d, int n_segment, int64_t arena_bytes, bool center, int resize,
+                                                       int crop, int64_t *off, tsm_host::CropGeometry *g) {
+    return tsm_host::nv12_window_descriptor_ok(d, n_segment, arena_bytes, center, resize, crop, off, g);
+  }
+  __device__ __forceinline__ unsigned pair(int64_t y, int64_t x) const {
+    return *reinterpret_cast<const unsigned short *>(frame + tsm_host::nv12_chroma_offset(h, w, y, x));
+  }
+  __device__ __forceinline__ void tap(int64_t y, int64_t x, unsigned uv, bool m, float *t) const {
+    int rgb[3];
+    tsm_host::nv12_pixel_rgb(k, frame[tsm_host::nv12_luma_offset(w, y, x)], (int)(uv & 255u), (int)(uv >> 8), rgb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = m ? (float)rgb[c] : 0.f;
+  }
+  __device__ __forceinline__ void quad(int64_t y0, int64_t y1, int64_t x0, int64_t x1, bool m00, bool m01, bool m10, bool m11,
+                                       float t[4][3]) const {
+    const bool new_col = (x1 >> 1) != (x0 >> 1), new_row = (y1 >> 1) != (y0 >> 1);
+    const unsigned uv00 = pair(y0, x0);
+    unsigned uv01 = uv00;
+    if (new_col) uv01 = pair(y0, x1);
+    unsigned uv10 = uv00, uv11 = uv01;
+    if (new_row) {
+      uv10 = pair(y1, x0);
+      uv11 = uv10;
+      if (new_col) uv11 = pair(y1, x1);
+    }
+    tap(y0, x0, uv00, m00, t[0]);
+    tap(y0, x1, uv01, m01, t[1]);
+    tap(y1, x0, uv10, m10, t[2]);
+    tap(y1, x1, uv11, m11, t[3]);
+  }
+};
+
 // The row loop.  A row source has a `Row` (where a row's pixels come from), locate(f, &row) -- false: the row has no frame
 // and is the zero frame -- and pixel(row, oy, ox, v), its sampler.  Sources are passed by value and inlined.
 template <typename Source>
@@ -252,30 +327,29 @@ __device__ __forceinline__ void preprocess_rows(float *dst, int out_mode, int si
 // preprocess (K8): Resize(int) + CenterCrop.  The sampler of the centre-crop sources: every tap lies in the frame (the
 // launcher checks the crop window against the resized size), so nothing is masked.
 template <typename T>
-__device__ __forceinline__ void preprocess_pixel(const PreprocParams &p, const T *frame, int cy, int cx, float *v) {
+__device__ __forceinline__ void preprocess_pixel(const PreprocParams &p, const Taps<T> &frame, int cy, int cx, float *v) {
 #pragma clang fp contract(off)
   const float fy = sample_coord((float)p.h / (float)p.nh, (float)(cy + p.top));
   const float fx = sample_coord((float)p.w / (float)p.nw, (float)(cx + p.left));
   const int y0 = (int)fy, x0 = (int)fx;
   const int y1 = y0 + (y0 < p.h - 1 ? 1 : 0), x1 = x0 + (x0 < p.w - 1 ? 1 : 0);
   const float h1 = fy - (float)y0, h0 = 1.f - h1, w1 = fx - (float)x0, w0 = 1.f - w1;
-  const T *r0 = frame + (int64_t)y0 * p.w * 3, *r1 = frame + (int64_t)y1 * p.w * 3;
+  float t[4][3];
+  frame.quad(y0, y1, x0, x1, true, true, true, true, t);
 #pragma unroll
-  for (int c = 0; c < 3; ++c)
-    v[c] = bilinear_normalised((float)r0[x0 * 3 + c], (float)r0[x1 * 3 + c], (float)r1[x0 * 3 + c], (float)r1[x1 * 3 + c], w0, w1,
-                               h0, h1, p.pre_scale, c);
+  for (int c = 0; c < 3; ++c) v[c] = bilinear_normalised(t[0][c], t[1][c], t[2][c], t[3][c], w0, w1, h0, h1, p.pre_scale, c);
 }
 
 // row f is frame f
 template <typename T>
 struct FrameRows {
   const PreprocParams &p;
-  using Row = const T *;
+  using Row = Taps<T>;
   __device__ __forceinline__ bool locate(int64_t f, Row *frame) const {
-    *frame = static_cast<const T *>(p.src) + f * (int64_t)p.h * p.w * 3;
+    *frame = Taps<T>::of(p.src, f, p.h, p.w, p.nv12);
     return true;
   }
-  __device__ __forceinline__ void pixel(Row frame, int oy, int ox, float *v) const { preprocess_pixel<T>(p, frame, oy, ox, v); }
+  __device__ __forceinline__ void pixel(const Row &frame, int oy, int ox, float *v) const { preprocess_pixel<T>(p, frame, oy, ox, v); }
 };
 
 template <typename T>
@@ -289,21 +363,28 @@ static bool crop_window_ok(const P &p) {
   return p.h > 0 && p.w > 0 && p.crop > 0 && p.top >= 0 && p.left >= 0 && p.top + p.crop <= p.nh && p.left + p.crop <= p.nw;
 }
 
+// NV12 frames of a launch whose size the host knows: both sides even, the buffer 2-byte aligned (the chroma pair is one load).
+static bool nv12_frames_ok(int is_nv12, const void *src, int h, int w) {
+  return !is_nv12 || (((h | w) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 1) == 0);
+}
+
 // One grid-stride launch of a row-loop kernel covers any number of rows (64-bit group index): nothing of the launch geometry
 // limits a range of clips or a table.
-#define TSM_LAUNCH_ROWS(KERNEL, is_u8, n_rows, size, out_mode, stream, params)                             \
+#define TSM_LAUNCH_ROWS(KERNEL, is_u8, is_nv12, n_rows, size, out_mode, stream, params)                    \
   do {                                                                                                      \
     const int px_ = (out_mode) >= 2 ? 2 : 1;                                                                \
     const unsigned grid_ = grid_for((int64_t)(n_rows) * (size) * (((size) + px_ - 1) / px_), 8192);         \
-    if (is_u8)                                                                                              \
+    if (is_nv12)                                                                                            \
+      TSM_KLAUNCH(KERNEL<Nv12>, dim3(grid_), dim3(256), 0, stream, params);                                 \
+    else if (is_u8)                                                                                         \
       TSM_KLAUNCH(KERNEL<unsigned char>, dim3(grid_), dim3(256), 0, stream, params);                        \
     else                                                                                                    \
       TSM_KLAUNCH(KERNEL<float>, dim3(grid_), dim3(256), 0, stream, params);                                \
   } while (0)
 
 hipError_t launch_preprocess(const PreprocParams &p, hipStream_t s) {
-  if (p.n <= 0 || !crop_window_ok(p)) return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_kernel, p.src_is_u8, p.n, p.crop, p.out_mode, s, p);
+  if (p.n <= 0 || !crop_window_ok(p) || !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w)) return hipErrorInvalidValue;
+  TSM_LAUNCH_ROWS(preprocess_kernel, p.src_is_u8, p.src_is_nv12, p.n, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -383,7 +464,7 @@ hipError_t launch_gather_clips(const GatherParams &p_in, hipStream_t s) {
 // The sampler of the box sources (ClipRows, WindowRows in person-crop mode): preprocess_pixel in the coordinates of a box
 // (top, left, bh, bw; bh, bw > 0) of an h x w frame resized to size x size, total in the box.
 template <typename T>
-__device__ __forceinline__ void box_pixel(const T *frame, int h, int w, int64_t top, int64_t left, int bh, int bw, int size,
+__device__ __forceinline__ void box_pixel(const Taps<T> &frame, int h, int w, int64_t top, int64_t left, int bh, int bw, int size,
                                           float pre_scale, int oy, int ox, float *v) {
 #pragma clang fp contract(off)
   const float fy = sample_coord((float)bh / (float)size, (float)oy);
@@ -400,20 +481,17 @@ __device__ __forceinline__ void box_pixel(const T *frame, int h, int w, int64_t 
   const bool vy0 = iy0 >= 0 && iy0 < h, vy1 = iy1 >= 0 && iy1 < h;
   const bool vx0 = ix0 >= 0 && ix0 < w, vx1 = ix1 >= 0 && ix1 < w;
   // (addresses are formed from coordinates held inside the frame: no product of a hostile sum, no pointer outside the buffer)
-  const T *r0 = frame + (vy0 ? iy0 : 0) * w * 3, *r1 = frame + (vy1 ? iy1 : 0) * w * 3;
-  const int64_t c0 = (vx0 ? ix0 : 0) * 3, c1 = (vx1 ? ix1 : 0) * 3;
-  const T *a00 = r0 + c0, *a01 = r0 + c1, *a10 = r1 + c0, *a11 = r1 + c1;
+  float t[4][3];
+  frame.quad(vy0 ? iy0 : 0, vy1 ? iy1 : 0, vx0 ? ix0 : 0, vx1 ? ix1 : 0, vy0 && vx0, vy0 && vx1, vy1 && vx0, vy1 && vx1, t);
 #pragma unroll
-  for (int c = 0; c < 3; ++c)
-    v[c] = bilinear_normalised(vy0 && vx0 ? (float)a00[c] : 0.f, vy0 && vx1 ? (float)a01[c] : 0.f,
-                               vy1 && vx0 ? (float)a10[c] : 0.f, vy1 && vx1 ? (float)a11[c] : 0.f, w0, w1, h0, h1, pre_scale, c);
+  for (int c = 0; c < 3; ++c) v[c] = bilinear_normalised(t[0][c], t[1][c], t[2][c], t[3][c], w0, w1, h0, h1, pre_scale, c);
 }
 
 template <typename T>
 struct ClipRows {
   const ClipPreprocParams &p;
   struct Row {
-    const T *frame;
+    Taps<T> frame;
     int64_t top, left;
     int bh, bw;
   };
@@ -431,7 +509,7 @@ struct ClipRows {
     r->left = person ? b[1] : 0;
     r->bh = person ? b[2] : p.h;
     r->bw = person ? b[3] : p.w;
-    r->frame = static_cast<const T *>(p.src) + (s / p.clip_stride - p.first_frame) * (int64_t)p.h * p.w * 3;
+    r->frame = Taps<T>::of(p.src, s / p.clip_stride - p.first_frame, p.h, p.w, p.nv12);
     return true;
   }
   __device__ __forceinline__ void pixel(const Row &r, int oy, int ox, float *v) const {
@@ -448,10 +526,11 @@ hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
   // every frame index the kernel will form, checked here (launch_gather_clips' rules; there is no pad frame to check)
   tsm_host::WindowRange r;
   if (!p.src || !p.dst || !p.boxes || p.h <= 0 || p.w <= 0 || p.size <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
+      !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w) ||
       !tsm_host::clip_window_range(p.total_frames, p.first_clip, p.n_clips, p.n_segment, p.clip_step, p.clip_stride, p.first_frame,
                                    p.n_frames, &r))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_clips_kernel, p.src_is_u8, (int64_t)p.n_clips * p.n_segment, p.size, p.out_mode, s, p);
+  TSM_LAUNCH_ROWS(preprocess_clips_kernel, p.src_is_u8, p.src_is_nv12, (int64_t)p.n_clips * p.n_segment, p.size, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -473,14 +552,14 @@ hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
 template <typename T>
 struct IndexedRows {
   const IndexedPreprocParams &q;
-  using Row = const T *;
+  using Row = Taps<T>;
   __device__ __forceinline__ bool locate(int64_t f, Row *frame) const {
     const int j = q.index[f];
     if (j < 0 || (int64_t)j >= q.n_frames) return false;
-    *frame = static_cast<const T *>(q.pp.src) + (int64_t)j * q.pp.h * q.pp.w * 3;
+    *frame = Taps<T>::of(q.pp.src, j, q.pp.h, q.pp.w, q.pp.nv12);
     return true;
   }
-  __device__ __forceinline__ void pixel(Row frame, int oy, int ox, float *v) const { preprocess_pixel<T>(q.pp, frame, oy, ox, v); }
+  __device__ __forceinline__ void pixel(const Row &frame, int oy, int ox, float *v) const { preprocess_pixel<T>(q.pp, frame, oy, ox, v); }
 };
 
 template <typename T>
@@ -490,9 +569,10 @@ __global__ void __launch_bounds__(256) preprocess_indexed_kernel(const IndexedPr
 
 hipError_t launch_preprocess_indexed(const IndexedPreprocParams &q, hipStream_t s) {
   const PreprocParams &p = q.pp;
-  if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3)
+  if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3 ||
+      !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, q.n_rows, p.crop, p.out_mode, s, q);
+  TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, p.src_is_nv12, q.n_rows, p.crop, p.out_mode, s, q);
   return hipGetLastError();
 }
 
@@ -515,7 +595,7 @@ template <typename T>
 struct WindowRows {
   const WindowPreprocParams &p;
   struct Row {
-    const T *frame;
+    Taps<T> frame;
     int h, w;
     int top, left;      // mode 0: the crop window's corner in the resized frame; mode 1: the box's corner in the source frame
     int sh, sw;         // mode 0: the resized size (nh, nw); mode 1: the box's size (bh, bw)
@@ -529,11 +609,10 @@ struct WindowRows {
     const int32_t d[tsm_host::kWindowDescWords] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     int64_t off;
     tsm_host::CropGeometry g;
-    if (!tsm_host::window_descriptor_ok(d, p.n_segment, (int)sizeof(T), p.arena_bytes, !p.person_crop, p.resize, p.crop, &off, &g))
-      return false;
+    if (!Taps<T>::descriptor_ok(d, p.n_segment, p.arena_bytes, !p.person_crop, p.resize, p.crop, &off, &g)) return false;
     r->h = d[2];
     r->w = d[3];
-    r->frame = reinterpret_cast<const T *>(static_cast<const char *>(p.arena) + off) + (int64_t)k * r->h * r->w * 3;
+    r->frame = Taps<T>::of(static_cast<const char *>(p.arena) + off, k, r->h, r->w, p.nv12);
     if (p.person_crop) {
       const bool person = d[6] > 0 && d[7] > 0;
       r->top = person ? d[4] : 0;
@@ -569,7 +648,7 @@ hipError_t launch_preprocess_windows(const WindowPreprocParams &p, hipStream_t s
       p.arena_bytes <= 0 || p.n_windows <= 0 || p.n_segment <= 0 || p.resize <= 0 || p.crop <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
       (p.person_crop != 0 && p.person_crop != 1) || (!p.person_crop && p.crop > p.resize))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_windows_kernel, p.src_is_u8, (int64_t)p.n_windows * p.n_segment, p.crop, p.out_mode, s, p);
+  TSM_LAUNCH_ROWS(preprocess_windows_kernel, p.src_is_u8, p.src_is_nv12, (int64_t)p.n_windows * p.n_segment, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 

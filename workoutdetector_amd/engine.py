@@ -703,17 +703,38 @@ def _pixel_of(frames, want: str, u8_only: bool = False, min_frames: int = 0) -> 
     return _lib.PIXEL_U8 if frames.dtype == torch.uint8 else _lib.PIXEL_F32
 
 
+def _staged_frames(frames, frame_format: str, colorimetry: Optional[str], want: str, min_frames: int = 0) -> tuple:
+    """``(pixel, n, h, w)`` of staged raw frames: ``_pixel_of``'s for ``frame_format='rgb'``; for ``'nv12'`` a contiguous CUDA
+    uint8 tensor [n, 3h/2, w] with h and w even (h, w: the luma size) and the pixel code of the colorimetry.  Every refusal is
+    a ValueError raised before the library is touched."""
+    import torch
+    from .transform import check_frame_format, nv12_luma_hw
+    colorimetry = check_frame_format(frame_format, colorimetry)
+    if frame_format == 'rgb':
+        pixel = _pixel_of(frames, want, min_frames=min_frames)
+        return (pixel,) + tuple(int(d) for d in frames.shape[:3])
+    if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
+            and frames.is_contiguous() and frames.shape[0] >= min_frames):
+        raise ValueError(f'NV12 frames must be a contiguous uint8 CUDA tensor [n >= {min_frames}, 3h/2, w], got '
+                         f'{getattr(frames, "dtype", type(frames))} {tuple(getattr(frames, "shape", ()))}')
+    h, w = nv12_luma_hw(frames.shape)
+    return _lib.nv12_pixel(colorimetry), int(frames.shape[0]), h, w
+
+
 def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: bool = False, packed: bool = True,
-                      layout: Optional[int] = None, out=None):
+                      layout: Optional[int] = None, out=None, frame_format: str = 'rgb', colorimetry: Optional[str] = None):
     """HIP test transform.  frames: CUDA uint8 or float32 [n,H,W,3] (decoder layout, values 0..255).
     Returns float32 [n,crop,crop,4] (``packed``: feed ``forward_device(..., layout=LAYOUT_NTHWC4)``),
     [n,3,crop,crop] (``packed=False``), or with ``layout=engine.packed_layout`` the packed format of that
     engine (LAYOUT_NTHWC8S for a bf16x3 engine: a float32-typed buffer [n,crop,ceil(crop/2),8] holding one
-    split-bf16 group per pixel pair; LAYOUT_NTHWC8B: [n,crop,ceil(crop/2),4] float slots = 8 bf16 per pair)."""
+    split-bf16 group per pixel pair; LAYOUT_NTHWC8B: [n,crop,ceil(crop/2),4] float slots = 8 bf16 per pair).
+    ``frame_format='nv12'``: frames are CUDA uint8 [n,3H/2,W] decoder surfaces (H, W even), converted to RGB inside the
+    launch's taps by ``colorimetry`` (``transform.COLORIMETRIES``, default ``'bt601'``): bit for bit the result for
+    ``transform.nv12_to_rgb(frames)``, and no RGB frame is written."""
     import torch
-    frames = frames.contiguous()
-    pixel = _pixel_of(frames, 'a CUDA tensor [n,H,W,3]')
-    n, h, w, _ = frames.shape
+    if hasattr(frames, 'contiguous'):
+        frames = frames.contiguous()
+    pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a CUDA tensor [n,H,W,3]')
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW
     out = _out(out, (n,) + _frame_shape(layout, crop), torch.float32, frames)
@@ -820,7 +841,8 @@ def gather_clips(frames, first_frame: int, total_frames: int, first_clip: int, n
 
 def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_clip: int, n_clips: int, size: int = 224,
                      scale_255: bool = False, layout: Optional[int] = None, packed: bool = True, n_segment: int = 8,
-                     clip_step: int = 8, clip_stride: int = 2, out=None):
+                     clip_step: int = 8, clip_stride: int = 2, out=None, frame_format: str = 'rgb',
+                     colorimetry: Optional[str] = None):
     """The person-crop test transform fused with the clip windows (``tsm_preprocess_clips``: PersonCrop -> Resize((size,
     size)) -> Normalize of the reference's ``build_test_transform(person_crop=True)``, from the detector's box on), one
     launch from staged raw frames to the engine's input.
@@ -830,10 +852,10 @@ def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_c
     [n_clips, 4] = (top, left, h, w) in source-frame pixels, row c for clip ``first_clip + c``; a box may leave the frame
     (zero fill) and a non-positive h or w stands for the whole frame.  Returns float32 [n_clips, n_segment, ...one frame]
     in the layouts of ``preprocess_frames`` with ``size`` in place of ``crop``; the zero-padded tail segments of the last
-    clips are (0 - mean) / std."""
+    clips are (0 - mean) / std.  ``frame_format='nv12'`` / ``colorimetry``: as ``preprocess_frames``; the boxes are in luma
+    pixels and the zero fill is RGB 0."""
     import torch
-    pixel = _pixel_of(frames, 'a contiguous CUDA tensor [n,H,W,3]')
-    n, h, w, _ = frames.shape
+    pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a contiguous CUDA tensor [n,H,W,3]')
     if not (hasattr(boxes, 'is_cuda') and boxes.is_cuda and boxes.device == frames.device and boxes.dtype == torch.int32
             and tuple(boxes.shape) == (n_clips, 4) and boxes.is_contiguous()):
         raise ValueError(f'boxes must be a contiguous int32 tensor [{n_clips}, 4] = (top, left, h, w) on {frames.device}')
@@ -847,7 +869,7 @@ def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_c
 
 
 def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_255: bool = True, layout: Optional[int] = None,
-                       out=None):
+                       out=None, frame_format: str = 'rgb', colorimetry: Optional[str] = None):
     """The centre-crop test transform through a device index table (``tsm_preprocess_indexed``), one launch from staged raw
     frames to the engine's input: the access pattern of the reference's ``FrameDataset`` (``sample_frames`` per labelled
     segment: irregular lists, repeated frames, no shared windows).
@@ -856,12 +878,12 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
     CUDA int32 [n_clips, n_segment] of buffer-frame numbers.  Returns float32 [n_clips, n_segment, ...one frame] in the
     layouts of ``preprocess_frames`` (default LAYOUT_NTHWC4); row (c, k) equals ``preprocess_frames``' row for frame
     ``index[c, k]`` bit for bit.  An entry outside [0, n) reads nothing and yields the normalised zero frame (0 - mean) / std
-    -- the kernel is total in the table; validate the table on the host where a wrong entry should be an error."""
+    -- the kernel is total in the table; validate the table on the host where a wrong entry should be an error.
+    ``frame_format='nv12'`` / ``colorimetry``: as ``preprocess_frames``."""
     import torch
-    if not hasattr(frames, 'is_cuda') or frames.dtype not in (torch.uint8, torch.float32):
+    if frame_format == 'rgb' and (not hasattr(frames, 'is_cuda') or frames.dtype not in (torch.uint8, torch.float32)):
         raise ValueError(f'frames must be a uint8 or float32 tensor, got {getattr(frames, "dtype", type(frames))}')
-    pixel = _pixel_of(frames, 'a contiguous CUDA tensor [n >= 1,H,W,3]', min_frames=1)
-    n, h, w, _ = frames.shape
+    pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a contiguous CUDA tensor [n >= 1,H,W,3]', min_frames=1)
     if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
             and index.dim() == 2 and index.shape[0] > 0 and index.shape[1] > 0 and index.is_contiguous()):
         raise ValueError(f'index must be a contiguous int32 tensor [n_clips >= 1, n_segment >= 1] on {frames.device}')
@@ -876,7 +898,8 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
 
 
 def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_crop: bool = False, resize: int = 256,
-                       crop: int = 224, scale_255: bool = False, layout: Optional[int] = None, out=None):
+                       crop: int = 224, scale_255: bool = False, layout: Optional[int] = None, out=None,
+                       frame_format: str = 'rgb', colorimetry: Optional[str] = None):
     """Either test transform over windows of different frame sizes (``tsm_preprocess_windows``), one launch from raw frames
     to the engine's input, in batch order: what one step of ``StreamBatcher`` needs.
 
@@ -887,8 +910,14 @@ def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_c
     that frame; ``True``: the window's box -> Resize((crop, crop)) -> Normalize, bit for bit ``preprocess_clips``' row.  Returns
     float32 [n_windows, n_segment, ...one frame] in the layouts of ``preprocess_frames`` (default LAYOUT_NTHWC4).  The kernel
     is total in the table: a window whose descriptor does not lie in the arena (or whose centre crop does not fit) reads
-    nothing and yields normalised zero frames."""
+    nothing and yields normalised zero frames.  ``frame_format='nv12'``: the same uint8 arena with windows of ``n_segment``
+    contiguous NV12 frames [3h/2, w] (``window_descriptors(..., frame_format='nv12')``; h, w of a row the luma size), converted
+    in the taps by ``colorimetry``; a row with an odd side is invalid."""
     import torch
+    from .transform import check_frame_format
+    colorimetry = check_frame_format(frame_format, colorimetry)
+    if colorimetry is not None and getattr(arena, 'dtype', None) != torch.uint8:
+        raise ValueError('an arena of NV12 windows must be a uint8 tensor')
     if not (hasattr(arena, 'is_cuda') and arena.is_cuda and arena.dtype in (torch.uint8, torch.float32) and arena.is_contiguous()
             and arena.numel() > 0 and arena.data_ptr() % 16 == 0):
         raise ValueError('arena must be a contiguous, 16-byte aligned, non-empty uint8 or float32 CUDA tensor')
@@ -901,7 +930,7 @@ def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_c
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4
     out = _out(out, (n_windows, n_segment) + _frame_shape(layout, crop), torch.float32, arena)
-    pixel = _lib.PIXEL_U8 if arena.dtype == torch.uint8 else _lib.PIXEL_F32
+    pixel = _lib.nv12_pixel(colorimetry) if colorimetry is not None else _lib.PIXEL_U8 if arena.dtype == torch.uint8 else _lib.PIXEL_F32
     _lib.check(_lib.load().tsm_preprocess_windows(arena.data_ptr(), arena.numel() * arena.element_size(), pixel, desc.data_ptr(),
                                                   n_windows, n_segment, int(bool(person_crop)), out.data_ptr(), layout,
                                                   int(resize), int(crop), int(scale_255), _stream(arena)))

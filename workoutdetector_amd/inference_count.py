@@ -57,7 +57,7 @@ from . import staging
 from .counting import RepCounter, pred_to_count, scores_to_preds, vote_states  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
 from .transform import (ImageTransform, PersonCropTransform, TestTransform, as_frames_u8, build_test_transform,
-                        need_frame_engine)
+                        check_frame_format, frame_hw, need_frame_engine, nv12_black, nv12_to_rgb)
 
 NUM_SEGMENTS = 8
 CLIP_SPAN = 16
@@ -139,9 +139,11 @@ class StagedVideo:
     hi: int                         # clip range [lo, hi)
     f_lo: int                       # index (in even-frame units) of the first staged frame
     hw: Tuple[int, int]
-    frames: torch.Tensor            # uint8 [n_even (+1 zero frame on the HIP path), H, W, 3]
+    frames: torch.Tensor            # uint8 [n_even (+1 zero frame on the HIP path), H, W, 3]; 'nv12': [..., 3H/2, W]
     on_device: bool
     ready: Optional[object] = None  # torch.cuda.Event recorded after the H2D copy
+    frame_format: str = 'rgb'       # 'nv12': decoder surfaces, converted inside the HIP transforms' taps (hw is the luma size)
+    colorimetry: Optional[str] = None   # of 'nv12' frames (transform.COLORIMETRIES)
 
 
 def clips_per_piece(per_frame_bytes: int) -> int:
@@ -157,31 +159,56 @@ def even_frame_range(total: int, lo: int, hi: int) -> Tuple[int, int]:
 
 
 def _stage(dev, total: int, lo: int, hi: int, f_lo: int, hw: Tuple[int, int], even: torch.Tensor,
-           stream: Optional[object] = None) -> StagedVideo:
-    """``even`` -- the frames ``even_frame_range`` names for clips [lo, hi) -- and a zero frame behind them, to ``dev``."""
+           stream: Optional[object] = None, frame_format: str = 'rgb', colorimetry: Optional[str] = None) -> StagedVideo:
+    """``even`` -- the frames ``even_frame_range`` names for clips [lo, hi) -- and a zero frame behind them, to ``dev``.
+    Behind NV12 frames the pad is ``nv12_black``, not zero bytes: the reference pads a clip with RGB-zero frames, and only
+    black converts to that (zero bytes are a saturated green)."""
     def fill(pinned: torch.Tensor) -> None:
         pinned[:-1].copy_(even)
-        pinned[-1].zero_()              # the zero frame the padded tail clip reads
+        if frame_format == 'nv12':
+            pinned[-1].copy_(torch.from_numpy(nv12_black(hw[0], hw[1], colorimetry)))
+        else:
+            pinned[-1].zero_()          # the zero frame the padded tail clip reads
     frames, ready = staging.upload((even.shape[0] + 1,) + tuple(even.shape[1:]), fill, dev, stream)
-    return StagedVideo(total, lo, hi, f_lo, hw, frames, True, ready)
+    return StagedVideo(total, lo, hi, f_lo, hw, frames, True, ready, frame_format, colorimetry)
+
+
+def _rgb_staged(st: StagedVideo) -> StagedVideo:
+    """A staged NV12 range as host RGB frames (``nv12_to_rgb``): what every path that is not a HIP transform takes."""
+    if st.frame_format != 'nv12':
+        return st
+    if st.on_device:
+        staging.wait_upload(st.frames, st.ready)
+    even = (st.frames[:-1] if st.on_device else st.frames).cpu()
+    rgb = torch.from_numpy(nv12_to_rgb(even.numpy(), st.colorimetry)) if even.shape[0] else even.new_zeros((0,) + st.hw + (3,))
+    return StagedVideo(st.total, st.lo, st.hi, st.f_lo, st.hw, rgb, False)
 
 
 def stage_video(model, video_thwc_u8: torch.Tensor, clip_range: Optional[Tuple[int, int]] = None,
-                stream: Optional[object] = None) -> StagedVideo:
+                stream: Optional[object] = None, frame_format: str = 'rgb', colorimetry: Optional[str] = None) -> StagedVideo:
     """Slice the even frames a clip range samples and, for a TsmEngine, copy them to its GPU through a
-    pinned buffer on ``stream`` (so the copy of video i+1 can run under the compute of video i)."""
+    pinned buffer on ``stream`` (so the copy of video i+1 can run under the compute of video i).
+    ``frame_format='nv12'``: the video is uint8 [T, 3H/2, W] decoder surfaces (``colorimetry``: default ``'bt601'``), staged
+    as they are -- half the bytes of RGB -- with ``nv12_black`` as the pad frame; ``hw`` is the luma size.  A model without a
+    device path gets ``nv12_to_rgb`` of the sampled frames on the host, and from there exactly the RGB path."""
+    colorimetry = check_frame_format(frame_format, colorimetry)
+    nv12 = frame_format == 'nv12'
+    if nv12 and (video_thwc_u8.dtype != torch.uint8 or video_thwc_u8.dim() != 3):
+        raise ValueError(f'an NV12 video must be uint8 [T, 3H/2, W], got {video_thwc_u8.dtype} {tuple(video_thwc_u8.shape)}')
     total = int(video_thwc_u8.shape[0])
     lo, hi = clip_range if clip_range is not None else (0, len(clip_starts(total)))
-    hw = (int(video_thwc_u8.shape[1]), int(video_thwc_u8.shape[2]))
+    hw = frame_hw(video_thwc_u8.shape, frame_format) if nv12 else (int(video_thwc_u8.shape[1]), int(video_thwc_u8.shape[2]))
     if hi <= lo:
-        return StagedVideo(total, lo, lo, 0, hw, video_thwc_u8[:0], False)
+        return StagedVideo(total, lo, lo, 0, hw, video_thwc_u8[:0], False, None, frame_format, colorimetry)
     f_lo, f_hi = even_frame_range(total, lo, hi)
     even = video_thwc_u8[0::CLIP_STRIDE][f_lo:f_hi]
-    if not staging.device_path(model) or int(even.numel()) > MAX_STAGE_BYTES:
-        # (no device path; or too large to pin / upload in one piece: hand the (strided, un-copied) host view on;
+    if not staging.device_path(model):
+        return _rgb_staged(StagedVideo(total, lo, hi, f_lo, hw, even, False, None, frame_format, colorimetry))
+    if int(even.numel()) > MAX_STAGE_BYTES:
+        # (too large to pin / upload in one piece: hand the (strided, un-copied) host view on;
         #  staged_clip_logits walks the clip range in pieces that fit)
-        return StagedVideo(total, lo, hi, f_lo, hw, even, False)
-    return _stage(staging.engine_device(model), total, lo, hi, f_lo, hw, even, stream)
+        return StagedVideo(total, lo, hi, f_lo, hw, even, False, None, frame_format, colorimetry)
+    return _stage(staging.engine_device(model), total, lo, hi, f_lo, hw, even, stream, frame_format, colorimetry)
 
 
 def staged_clip_logits(model, st: StagedVideo, transform: Union[TestTransform, PersonCropTransform], batch_clips: int = 32,
@@ -202,9 +229,12 @@ def staged_clip_logits(model, st: StagedVideo, transform: Union[TestTransform, P
         for a in range(st.lo, st.hi, step):
             b = min(a + step, st.hi)
             f_a, f_b = even_frame_range(st.total, a, b)
-            piece = _stage(staging.engine_device(model), st.total, a, b, f_a, st.hw, st.frames[f_a - st.f_lo:f_b - st.f_lo])
+            piece = _stage(staging.engine_device(model), st.total, a, b, f_a, st.hw, st.frames[f_a - st.f_lo:f_b - st.f_lo],
+                           None, st.frame_format, st.colorimetry)
             parts.append(staged_clip_logits(model, piece, transform, batch_clips, video_name))
         return torch.cat(parts, dim=0)
+    if not (st.on_device and hasattr(model, 'packed_layout') and isinstance(transform, (TestTransform, PersonCropTransform))):
+        st = _rgb_staged(st)             # (no HIP transform will read these frames: NV12 becomes RGB on the host)
     if person:
         return _person_crop_logits(model, st, transform, batch_clips, video_name)
     frames, idx, hip_transform = _staged_clips(model, st, transform)
@@ -231,7 +261,8 @@ def _person_crop_logits(model, st: StagedVideo, transform: PersonCropTransform, 
             b = min(a + batch_clips, n)
             clips = preprocess_clips(frames, boxes[a:b], st.f_lo, st.total, st.lo + a, b - a, size=transform.size,
                                      scale_255=transform.scale_255, layout=model.packed_layout, n_segment=NUM_SEGMENTS,
-                                     clip_step=CLIP_STEP, clip_stride=CLIP_STRIDE)
+                                     clip_step=CLIP_STEP, clip_stride=CLIP_STRIDE, frame_format=st.frame_format,
+                                     colorimetry=st.colorimetry)
             out.append(model.forward_device(clips, layout=model.packed_layout))
         return torch.cat(out, dim=0).to(torch.float32).cpu()
     even = st.frames[:-1] if st.on_device else st.frames
@@ -255,13 +286,16 @@ def _staged_clips(model, st: StagedVideo, transform: TestTransform) -> Tuple[tor
     are in the engine's packed device format (HIP transform) rather than float32 [n,3,224,224]."""
     dev = staging.engine_device(model)
     hip_transform = st.on_device and isinstance(transform, TestTransform)
+    if not hip_transform:
+        st = _rgb_staged(st)
     if hip_transform:
         # HIP path: uint8 frames (+ one zero frame for the padded tail) -> fused resize/crop/normalise
         # kernel -> the engine's packed input format, consumed in place.
         from .engine import preprocess_frames
         staging.wait_upload(st.frames, st.ready)
         frames = preprocess_frames(st.frames, resize=transform.size, crop=transform.crop,
-                                   scale_255=transform.scale_255, layout=model.packed_layout)
+                                   scale_255=transform.scale_255, layout=model.packed_layout, frame_format=st.frame_format,
+                                   colorimetry=st.colorimetry)
     else:
         even = st.frames[:-1] if st.on_device else st.frames
         if dev is not None and not even.is_cuda:
@@ -311,15 +345,18 @@ def _forward_clips(model, clips: torch.Tensor, hip_transform: bool) -> torch.Ten
 
 def video_clip_logits(model, video_thwc_u8: torch.Tensor, transform: Union[TestTransform, PersonCropTransform],
                       clip_range: Optional[Tuple[int, int]] = None, batch_clips: int = 32,
-                      video_name: Optional[str] = None) -> torch.Tensor:
+                      video_name: Optional[str] = None, frame_format: str = 'rgb',
+                      colorimetry: Optional[str] = None) -> torch.Tensor:
     """Raw logits [n_clips_in_range, num_class] (CPU float32) for the clips ``clip_range`` (default all)
-    of one video (``video_name``: the key a ``PersonCropTransform`` looks its boxes up under)."""
-    return staged_clip_logits(model, stage_video(model, video_thwc_u8, clip_range), transform, batch_clips, video_name)
+    of one video (``video_name``: the key a ``PersonCropTransform`` looks its boxes up under).  ``frame_format='nv12'``: the
+    video is uint8 [T, 3H/2, W] (``stage_video``); the logits equal those of ``nv12_to_rgb(video)`` bit for bit."""
+    st = stage_video(model, video_thwc_u8, clip_range, None, frame_format, colorimetry)
+    return staged_clip_logits(model, st, transform, batch_clips, video_name)
 
 
 def prefetch_staged(model, videos: Iterable[Tuple[object, torch.Tensor]],
-                    clip_range_of: Optional[Callable[[torch.Tensor], Optional[Tuple[int, int]]]] = None
-                    ) -> Iterator[Tuple[object, StagedVideo]]:
+                    clip_range_of: Optional[Callable[[torch.Tensor], Optional[Tuple[int, int]]]] = None,
+                    frame_format: str = 'rgb', colorimetry: Optional[str] = None) -> Iterator[Tuple[object, StagedVideo]]:
     """Double buffering over a stream of ``(key, uint8 video)``: while the caller computes on video i, a
     worker thread reads / slices / pins video i+1 and copies it to the GPU on a side stream."""
     side = torch.cuda.Stream(staging.engine_device(model)) if staging.device_path(model) else None
@@ -328,7 +365,7 @@ def prefetch_staged(model, videos: Iterable[Tuple[object, torch.Tensor]],
         key, vid = item
         vid = vid() if callable(vid) else vid          # lazy readers run on the worker thread too
         rng = clip_range_of(vid) if clip_range_of is not None else None
-        return key, stage_video(model, vid, rng, side)
+        return key, stage_video(model, vid, rng, side, frame_format, colorimetry)
 
     it = iter(videos)
     with ThreadPoolExecutor(max_workers=1) as pool:
@@ -447,7 +484,7 @@ def _write_score_json(out_dir: str, item, checkpoint: str, logits: torch.Tensor,
 
 
 def _inference_dataset_by_videos(model, items: list, out_dir: str, checkpoint: str, transform, reader,
-                                 batch_clips: int) -> None:
+                                 batch_clips: int, frame_format: str = 'rgb', colorimetry: Optional[str] = None) -> None:
     """``shard='videos'``: rank r decodes and runs videos r, r+W, r+2W, ... whole (no video is decoded twice);
     per round of W videos the ranks exchange [frame count, clip count] and then the padded logits (two small
     all-gathers), and rank 0 writes the round's JSON files."""
@@ -455,7 +492,7 @@ def _inference_dataset_by_videos(model, items: list, out_dir: str, checkpoint: s
     dev = staging.engine_device(model)
     num_class = getattr(model, 'num_class', None)
     mine = items[rank::world]
-    staged = prefetch_staged(model, ((it, (lambda p=it.video_path: reader(p))) for it in mine))
+    staged = prefetch_staged(model, ((it, (lambda p=it.video_path: reader(p))) for it in mine), None, frame_format, colorimetry)
     for r0 in range(0, len(items), world):
         try:
             item, st = next(staged) if r0 + rank < len(items) else (None, None)
@@ -769,7 +806,8 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
                       data_root: Optional[str] = None, anno_path: Optional[str] = None,
                       video_reader: Optional[Callable[[str], torch.Tensor]] = None, action: Sequence[str] = ('all',),
                       batch_clips: int = 32, scale_255: bool = False, shard: Optional[str] = None,
-                      frame_counter: Optional[Callable[[str], int]] = None, boxes=None) -> Optional[Dict[str, torch.Tensor]]:
+                      frame_counter: Optional[Callable[[str], int]] = None, boxes=None, frame_format: str = 'rgb',
+                      colorimetry: Optional[str] = None) -> Optional[Dict[str, torch.Tensor]]:
     """Inference the RepCount dataset; one ``{video_name}.score.json`` per video with the reference's
     schema: video_name, model, input_shape, checkpoint, total_frames, ground_truth, action, scores.
 
@@ -786,11 +824,18 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     ``person_crop=True`` is the reference's PersonCrop -> Resize((224, 224)) -> Normalize with the boxes given by the caller:
     ``boxes`` is a callable ``(video_name, clip_index) -> (top, left, h, w) or None`` or a mapping ``video_name -> boxes``
     (``transform.PersonCropTransform``; the detector is out of scope).  It runs under ``shard='clips'`` (the default then)
-    or ``'videos'``; ``'global'`` is refused: its batcher shares transformed frames between overlapping clips."""
+    or ``'videos'``; ``'global'`` is refused: its batcher shares transformed frames between overlapping clips.
+
+    ``frame_format='nv12'`` (``colorimetry``: default ``'bt601'``): ``video_reader`` returns uint8 [T, 3H/2, W] decoder
+    surfaces, staged as they are and converted inside the HIP transforms (``stage_video``).  It runs under ``shard='clips'``
+    (the default then) or ``'videos'``; ``'global'`` is not implemented: its stager sizes and cuts pieces as RGB frames."""
     need_clip_rows(model, 'inference_dataset')
+    colorimetry = check_frame_format(frame_format, colorimetry)
     rank, _world = tdist.world_info()
     if shard is None:
-        shard = 'clips' if person_crop else 'global'
+        shard = 'clips' if person_crop or frame_format == 'nv12' else 'global'
+    if frame_format == 'nv12' and shard == 'global':
+        raise NotImplementedError("frame_format='nv12' runs with shard='clips' or 'videos'; shard='global' takes RGB frames only")
     if shard not in ('clips', 'videos', 'global'):
         raise ValueError("shard must be 'clips', 'videos' or 'global'")
     if person_crop and shard == 'global':
@@ -805,14 +850,15 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     if rank == 0:
         print('==> transform:', transform)
     if shard == 'videos':
-        _inference_dataset_by_videos(model, list(data.values()), out_dir, checkpoint, transform, reader, batch_clips)
+        _inference_dataset_by_videos(model, list(data.values()), out_dir, checkpoint, transform, reader, batch_clips,
+                                     frame_format, colorimetry)
         return
     if shard == 'global':     # (returns {video_name: logits [clips, classes]} on every rank; the reference returns None)
         return _inference_dataset_global(model, list(data.values()), out_dir, checkpoint, transform, reader, batch_clips,
                                          frame_counter)
     # Video i+1 is read, sliced, pinned and copied to the GPU by a worker thread while video i computes.
     videos = ((item, (lambda p=item.video_path: reader(p))) for item in data.values())
-    for item, staged in prefetch_staged(model, videos, lambda v: _rank_clip_range(int(v.shape[0]))):
+    for item, staged in prefetch_staged(model, videos, lambda v: _rank_clip_range(int(v.shape[0])), frame_format, colorimetry):
         n_frames = staged.total
         logits = _gather_video_logits(model, staged_clip_logits(model, staged, transform, batch_clips, item.video_name),
                                       n_frames)

@@ -27,7 +27,8 @@ import torch
 from . import staging
 from .counting import RepCounter, scores_to_preds
 from .inference_count import NUM_SEGMENTS, need_clip_rows
-from .transform import Box, PersonCropTransform, TestTransform, build_test_transform, person_box, window_descriptors
+from .transform import (Box, PersonCropTransform, TestTransform, build_test_transform, check_frame_format, nv12_luma_hw,
+                        nv12_to_rgb, person_box, window_descriptors)
 
 
 @dataclass
@@ -53,12 +54,21 @@ class StreamBatcher:
 
     ``person_crop=True``: ``push(stream_id, frame, box=(x1, y1, x2, y2))`` takes the detector's first box of that frame; a
     complete window is cropped to ``transform.person_box`` of the boxes pushed with its frames and resized to the crop size
-    without keeping the aspect ratio; a window none of whose frames came with a box is "no person": the whole frame."""
+    without keeping the aspect ratio; a window none of whose frames came with a box is "no person": the whole frame.
+
+    ``frame_format='nv12'`` (``colorimetry``: ``transform.COLORIMETRIES``, default ``'bt601'``): ``push`` takes decoder
+    surfaces, uint8 [3H/2, W] of any mix of even sizes; boxes are in luma pixels.  A batch is still ONE launch, and one launch
+    has one pixel code, so the format belongs to the batcher, not to the frame.  The windows are staged as they are (half the
+    bytes of RGB, in the pinned budget too) and converted inside the transform's taps: states and counts equal those of an RGB
+    batcher fed ``nv12_to_rgb`` of the frames.  On the host path the frames are converted when they arrive."""
 
     def __init__(self, model, threshold: float = 0.5, softmax: bool = True, step: int = 8, max_batch: int = 32,
                  transform: Optional[TestTransform] = None,
                  on_window: Optional[Callable[[Hashable, int, int, int], None]] = None,
-                 max_pinned_bytes: int = 1 << 30, max_free_per_shape: int = 64, person_crop: bool = False):
+                 max_pinned_bytes: int = 1 << 30, max_free_per_shape: int = 64, person_crop: bool = False,
+                 frame_format: str = 'rgb', colorimetry: Optional[str] = None):
+        self.colorimetry = check_frame_format(frame_format, colorimetry)
+        self.frame_format = frame_format
         need_clip_rows(model, 'StreamBatcher')
         self.model = model
         self.threshold, self.softmax, self.step_frames = threshold, softmax, step
@@ -96,7 +106,13 @@ class StreamBatcher:
                 raise ValueError(f'box must be four finite numbers (x1, y1, x2, y2), got {box}')
         st = self.open(stream_id)
         arr = np.asarray(frame)
-        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+        if self.frame_format == 'nv12':
+            if arr.dtype != np.uint8 or arr.ndim != 2:
+                raise ValueError(f'an NV12 frame must be uint8 [3H/2,W], got {arr.dtype} {arr.shape}')
+            nv12_luma_hw(arr.shape)
+            if self._dev is None:
+                arr = nv12_to_rgb(arr, self.colorimetry)[0]
+        elif arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
             raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
         st.frames_seen += 1
         if self._dev is not None:
@@ -218,11 +234,12 @@ class StreamBatcher:
             done = torch.cuda.Event()
             done.record()
             self._inflight += [(done, w) for w in windows]
-            table = window_descriptors([tuple(w.shape[1:]) for w in windows], offsets, crops if self.person_crop else None,
-                                       resize=tf.size, crop=tf.crop)
+            nv12 = self.frame_format == 'nv12'
+            table = window_descriptors([nv12_luma_hw(w.shape) if nv12 else tuple(w.shape[1:]) for w in windows], offsets,
+                                       crops if self.person_crop else None, resize=tf.size, crop=tf.crop, frame_format=self.frame_format)
             clips = preprocess_windows(arena, staging.upload_table(torch.from_numpy(table), dev), len(windows), NUM_SEGMENTS,
                                        person_crop=self.person_crop, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255,
-                                       layout=self.model.packed_layout)
+                                       layout=self.model.packed_layout, frame_format=self.frame_format, colorimetry=self.colorimetry)
             return self.model.forward_device(clips, layout=self.model.packed_layout)
         if self.person_crop:
             xs = [self._crop_transform(torch.from_numpy(w).permute(0, 3, 1, 2).float(), box) for w, box in zip(windows, crops)]

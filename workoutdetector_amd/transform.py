@@ -157,7 +157,124 @@ def build_test_transform(person_crop: bool = False, scale_255: bool = False, box
     return TestTransform(scale_255=scale_255)
 
 
-def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int = INPUT_SIZE) -> np.ndarray:
+# ---- NV12 frames: what a hardware decoder leaves, and the exact integer conversion the kernels run in their taps -------------
+# One frame [3h/2, w] uint8: h rows of luma, then h/2 rows of interleaved (U, V) pairs; h and w even.  Luma pixel (y, x) takes
+# the pair at chroma row y >> 1, columns 2 (x >> 1) and 2 (x >> 1) + 1 (nearest-neighbour chroma, as cv2.COLOR_YUV2RGB_NV12;
+# ffmpeg's default swscale path interpolates chroma and is NOT reproduced bit for bit).  With C = Y - y_off, D = U - 128,
+# E = V - 128, in int32 with an arithmetic shift:
+#   R = clamp((cy C + crv E + 8192) >> 14),  G = clamp((cy C + cgu D + cgv E + 8192) >> 14),  B = clamp((cy C + cbu D + 8192) >> 14)
+# name -> (y_off, cy, crv, cgu, cgv, cbu): round(x * 2^14) of the BT.601 / BT.709 matrices, limited range (255/219 for luma,
+# 255/224 for chroma) or full range.  The order is that of the pixel codes 16 .. 19 (include/tsm_hip.h).
+_NV12_COEFFICIENTS = {
+    'bt601': (16, 19077, 26149, -6419, -13320, 33050),
+    'bt709': (16, 19077, 29372, -3494, -8731, 34610),
+    'bt601-full': (0, 16384, 22970, -5638, -11700, 29032),
+    'bt709-full': (0, 16384, 25802, -3069, -7670, 30402),
+}
+COLORIMETRIES = tuple(_NV12_COEFFICIENTS)
+FRAME_FORMATS = ('rgb', 'nv12')
+# (Kr, Kb, limited) of each colorimetry: the float64 matrices the integer rows are rounded from
+_NV12_MATRIX = {'bt601': (0.299, 0.114, True), 'bt709': (0.2126, 0.0722, True),
+                'bt601-full': (0.299, 0.114, False), 'bt709-full': (0.2126, 0.0722, False)}
+
+
+def nv12_coefficients(colorimetry: str = 'bt601') -> Tuple[int, int, int, int, int, int]:
+    """``(y_off, cy, crv, cgu, cgv, cbu)`` of a colorimetry, or ValueError."""
+    try:
+        return _NV12_COEFFICIENTS[colorimetry]
+    except (KeyError, TypeError):
+        raise ValueError(f'colorimetry must be one of {COLORIMETRIES}, got {colorimetry!r}') from None
+
+
+def check_frame_format(frame_format: str, colorimetry: Optional[str]) -> Optional[str]:
+    """The colorimetry a call runs with: None for ``'rgb'`` frames (which take none: giving one is a ValueError), for
+    ``'nv12'`` the given one (default ``'bt601'``), checked.  Touches nothing but its arguments."""
+    if frame_format not in FRAME_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS}, got {frame_format!r}')
+    if frame_format == 'rgb':
+        if colorimetry is not None:
+            raise ValueError(f"colorimetry={colorimetry!r} was given with frame_format='rgb': RGB frames have none")
+        return None
+    colorimetry = 'bt601' if colorimetry is None else colorimetry
+    nv12_coefficients(colorimetry)
+    return colorimetry
+
+
+def nv12_luma_hw(shape) -> Tuple[int, int]:
+    """The luma size ``(h, w)`` of NV12 frames whose last two dimensions are ``[3h/2, w]``; ValueError unless the rows are a
+    multiple of 3 and h and w are even and positive."""
+    rows, w = int(shape[-2]), int(shape[-1])
+    if rows <= 0 or w <= 0 or rows % 3 != 0 or w % 2 != 0:       # (h = 2 rows / 3 is then even)
+        raise ValueError(f'NV12 frames are [3h/2, w] with h and w even, got {rows} x {w}')
+    return rows // 3 * 2, w
+
+
+def frame_hw(shape, frame_format: str = 'rgb') -> Tuple[int, int]:
+    """``(h, w)`` of one frame of a video or frame whose shape is ``[..., h, w, 3]`` (``'rgb'``) or ``[..., 3h/2, w]``."""
+    return nv12_luma_hw(shape) if frame_format == 'nv12' else (int(shape[-3]), int(shape[-2]))
+
+
+def frame_bytes(h: int, w: int, frame_format: str = 'rgb') -> int:
+    """Bytes of one staged uint8 frame of luma size h x w."""
+    return 3 * h * w // 2 if frame_format == 'nv12' else 3 * h * w
+
+
+def nv12_to_rgb(frames, colorimetry: str = 'bt601') -> np.ndarray:
+    """uint8 ``[n, 3h/2, w]`` (or one ``[3h/2, w]``) -> uint8 ``[n, h, w, 3]``: the conversion above, in int32 -- to the bit
+    what the NV12 kernels feed their bilinear taps."""
+    y_off, cy, crv, cgu, cgv, cbu = nv12_coefficients(colorimetry)
+    a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError(f'NV12 frames must be uint8 [n, 3h/2, w] or [3h/2, w], got {a.dtype} {a.shape}')
+    h, w = nv12_luma_hw(a.shape)
+    a = a.reshape(-1, 3 * h // 2, w)
+    c = cy * (a[:, :h].astype(np.int32) - y_off) + 8192
+    uv = a[:, h:].reshape(-1, h // 2, w // 2, 2).astype(np.int32) - 128
+    uv = uv.repeat(2, axis=1).repeat(2, axis=2)              # a 2x2 block shares one pair
+    d, e = uv[..., 0], uv[..., 1]
+    rgb = np.stack([(c + crv * e) >> 14, (c + cgu * d + cgv * e) >> 14, (c + cbu * d) >> 14], axis=-1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+def rgb_to_nv12(frames, colorimetry: str = 'bt601') -> np.ndarray:
+    """uint8 ``[n, h, w, 3]`` (or one ``[h, w, 3]``; h, w even) -> uint8 ``[n, 3h/2, w]``: the float64 forward matrix, chroma
+    the mean of each 2x2 block, rounded half up and clipped.  A convenience for tests, tools and callers without a decoder;
+    it is no codec's exact output."""
+    nv12_coefficients(colorimetry)
+    kr, kb, limited = _NV12_MATRIX[colorimetry]
+    a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f'RGB frames must be uint8 [n, h, w, 3] or [h, w, 3], got {a.dtype} {a.shape}')
+    a = a.reshape((-1,) + a.shape[-3:])
+    n, h, w = a.shape[:3]
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f'NV12 needs an even h and an even w, got {h} x {w}')
+    r, g, b = (a[..., i].astype(np.float64) for i in range(3))
+    y = kr * r + (1.0 - kr - kb) * g + kb * b
+    cb, cr = (b - y) / (2.0 * (1.0 - kb)), (r - y) / (2.0 * (1.0 - kr))
+    ys, yo, cs = (219.0 / 255.0, 16.0, 224.0 / 255.0) if limited else (1.0, 0.0, 1.0)
+    block = lambda p: p.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4))
+    out = np.empty((n, 3 * h // 2, w), dtype=np.uint8)
+    quant = lambda v: np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint8)
+    out[:, :h] = quant(y * ys + yo)
+    out[:, h:, 0::2] = quant(block(cb) * cs + 128.0)
+    out[:, h:, 1::2] = quant(block(cr) * cs + 128.0)
+    return out
+
+
+def nv12_black(h: int, w: int, colorimetry: str = 'bt601') -> np.ndarray:
+    """One NV12 frame ``[3h/2, w]`` that converts to RGB (0, 0, 0) everywhere: luma ``y_off``, chroma 128.  (A frame of zero
+    bytes does NOT: under ``'bt601'`` it is (0, 136, 0).)"""
+    y_off = nv12_coefficients(colorimetry)[0]
+    if h <= 0 or w <= 0 or h % 2 or w % 2:
+        raise ValueError(f'NV12 needs an even h and an even w, got {h} x {w}')
+    out = np.full((3 * h // 2, w), 128, dtype=np.uint8)
+    out[:h] = y_off
+    return out
+
+
+def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int = INPUT_SIZE,
+                       frame_format: str = 'rgb') -> np.ndarray:
     """The descriptor table ``tsm_preprocess_windows`` takes (include/tsm_hip.h), built and VALIDATED on the host: int32
     [n, 8], row c = ``(off_lo, off_hi, h, w, top, left, bh, bw)``.  ``shapes``: one frame size ``(h, w)`` (or ``(h, w, 3)``)
     per window; ``offsets``: the byte offset of each window's first frame in the arena.  ``boxes=None`` builds a centre-crop
@@ -166,7 +283,10 @@ def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int
 
     The kernel is total in this table and turns an invalid row into zero frames; a caller who builds the table here gets an
     error instead: ValueError for a side outside 1 .. 65535, an offset that is negative or no multiple of 16, a centre crop
-    larger than the resized frame, a box that is not four integers of the int32 range."""
+    larger than the resized frame, a box that is not four integers of the int32 range.  ``frame_format='nv12'``: the
+    windows hold NV12 frames, ``shapes`` are their luma sizes ``(h, w)``, and an odd side is a ValueError too."""
+    if frame_format not in FRAME_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS}, got {frame_format!r}')
     shapes, offsets = list(shapes), list(offsets)
     if len(shapes) != len(offsets) or (boxes is not None and len(boxes) != len(shapes)):
         raise ValueError('shapes, offsets and boxes must have one entry per window')
@@ -178,6 +298,8 @@ def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int
         h, w = int(shape[0]), int(shape[1])
         if not (1 <= h <= 65535 and 1 <= w <= 65535):
             raise ValueError(f'window {c}: frame sides must lie in 1 .. 65535, got {h} x {w}')
+        if frame_format == 'nv12' and (len(shape) != 2 or h % 2 or w % 2):
+            raise ValueError(f'window {c}: an NV12 window is (h, w) with both sides even, got {shape}')
         if not isinstance(off, (int, np.integer)) or off < 0 or off % 16 != 0 or off >= 1 << 63:
             raise ValueError(f'window {c}: offset must be a non-negative multiple of 16 bytes, got {off!r}')
         off = int(off)

@@ -124,14 +124,47 @@ typedef enum tsm_layout {
  *       BT601_FULL          0  16384  22970  -5638  -11700  29032
  *       BT709_FULL          0  16384  25802  -3069   -7670  30402
  *     Everything behind the conversion (bilinear taps, zero fill, normalisation) is the RGB transform's, bit for bit that of
- *     the converted frame.  Codes 2..15 and 20 on are invalid. */
+ *     the converted frame.
+ *   TSM_PIXEL_I420_* .. TSM_PIXEL_UYVY_*   code 32 + 4 f + c: f the format (I420 0, YV12 1, P010 2, YUYV 3, UYVY 4), c the
+ *     coefficient row in the order above.  What other sources leave; all dense, converted in the taps by the same formula,
+ *     bit for bit the RGB transform of the converted frame.
+ *       I420 (a software decoder's yuv420p): h * w Y bytes, then h/2 * w/2 U bytes, then h/2 * w/2 V bytes; 3 h w / 2 bytes,
+ *         h and w even; pixel (y, x) takes U and V at (y >> 1, x >> 1) of their planes.  YV12: the V plane before the U plane.
+ *       P010 (a 10-bit decode): NV12's arrangement with 16-bit little-endian samples, the 10 significant bits in the most
+ *         significant bits; 3 h w bytes, h and w even, `frames` 4-byte aligned.  A sample enters the formula as its HIGH byte
+ *         (word >> 8) and the low byte is ignored whatever it holds: everything downstream is the 8-bit RGB pipeline, so a
+ *         P010 frame equals, bit for bit, the NV12 frame made of its high bytes.
+ *       YUYV (a capture device's packed 4:2:2): h rows of w / 2 groups of the bytes (Y0, U, Y1, V); 2 h w bytes, w even,
+ *         any h >= 1, `frames` 4-byte aligned; the two pixels of a group share its U and V, rows share nothing.  UYVY: the
+ *         bytes of a group are (U, Y0, V, Y1).
+ *     Codes 2..15, 20..31 and 52 on are invalid. */
 typedef enum tsm_pixel {
   TSM_PIXEL_U8 = 0,
   TSM_PIXEL_F32 = 1,
   TSM_PIXEL_NV12_BT601 = 16,
   TSM_PIXEL_NV12_BT709 = 17,
   TSM_PIXEL_NV12_BT601_FULL = 18,
-  TSM_PIXEL_NV12_BT709_FULL = 19
+  TSM_PIXEL_NV12_BT709_FULL = 19,
+  TSM_PIXEL_I420_BT601 = 32,
+  TSM_PIXEL_I420_BT709 = 33,
+  TSM_PIXEL_I420_BT601_FULL = 34,
+  TSM_PIXEL_I420_BT709_FULL = 35,
+  TSM_PIXEL_YV12_BT601 = 36,
+  TSM_PIXEL_YV12_BT709 = 37,
+  TSM_PIXEL_YV12_BT601_FULL = 38,
+  TSM_PIXEL_YV12_BT709_FULL = 39,
+  TSM_PIXEL_P010_BT601 = 40,
+  TSM_PIXEL_P010_BT709 = 41,
+  TSM_PIXEL_P010_BT601_FULL = 42,
+  TSM_PIXEL_P010_BT709_FULL = 43,
+  TSM_PIXEL_YUYV_BT601 = 44,
+  TSM_PIXEL_YUYV_BT709 = 45,
+  TSM_PIXEL_YUYV_BT601_FULL = 46,
+  TSM_PIXEL_YUYV_BT709_FULL = 47,
+  TSM_PIXEL_UYVY_BT601 = 48,
+  TSM_PIXEL_UYVY_BT709 = 49,
+  TSM_PIXEL_UYVY_BT601_FULL = 50,
+  TSM_PIXEL_UYVY_BT709_FULL = 51
 } tsm_pixel;
 
 /* Arithmetic of the conv stack.
@@ -411,7 +444,8 @@ int tsm_maxpool3x3s2(const float *x, float *y, int32_t n, int32_t hi, int32_t wi
  *   -> Normalize(ImageNet)            workoutdetector/datasets/build.py:131-136
  * frames: [n, h, w, 3] decoder layout, TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255).
  *         or [n, 3h/2, w] bytes with a TSM_PIXEL_NV12_* code (tsm_pixel): h, w the luma size, both even (an odd side is
- *         TSM_ERR_INVALID_ARG, nothing launched), `frames` 2-byte aligned.
+ *         TSM_ERR_INVALID_ARG, nothing launched), `frames` 2-byte aligned.  Or frames of another YUV code (tsm_pixel: the
+ *         frame size, parity and alignment of each format; a frame that does not fit is TSM_ERR_INVALID_ARG, nothing launched).
  * out:    out_layout TSM_LAYOUT_NTHWC4 -> [n, crop, crop, 4] fp32, TSM_LAYOUT_NTHWC8S -> split-bf16 /
  *         TSM_LAYOUT_NTHWC8B -> bf16 pixel pairs [n, crop, ceil(crop/2), 8] (feed tsm_forward of an engine
  *         of the matching dtype directly) or TSM_LAYOUT_NTCHW -> [n, 3, crop, crop] fp32.
@@ -443,7 +477,8 @@ int tsm_gather_clips(const void *frames, int64_t n_frames, int64_t frame_bytes, 
  *   part of this library, the boxes are the caller's.
  * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255), tsm_gather_clips' convention: buffer frame j =
  *         source frame clip_stride * (first_frame + j).  Or NV12 frames of 3 h w / 2 bytes (a TSM_PIXEL_NV12_* code, h and w
- *         even, `frames` 2-byte aligned); the box is in luma pixels and a tap outside the frame is RGB 0, not a YUV value.
+ *         even, `frames` 2-byte aligned) or of another YUV code (tsm_pixel); the box is in luma pixels and a tap outside the
+ *         frame is RGB 0, not a YUV value.
  * boxes:  DEVICE int32 [n_clips, 4] = (top, left, bh, bw) in source-frame pixels, row c for clip first_clip + c.
  * out:    [n_clips, n_segment, ...one frame] in out_layout, as tsm_preprocess with `size` in place of `crop`.
  *   out[c][k] = source frame s = clip_step * (first_clip + c) + clip_stride * k, cropped to box c, resized to size x size
@@ -470,7 +505,8 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
  * irregular lists (a segment shorter than 8 frames repeats frames, two segments of one video share no window, unsampled
  * frames are never needed) that the regular windows of tsm_gather_clips / tsm_preprocess_clips cannot express.
  * frames: [n_frames, h, w, 3] TSM_PIXEL_U8 or TSM_PIXEL_F32 (values 0..255): whatever frames the caller staged.
- *         Or NV12 frames of 3 h w / 2 bytes (a TSM_PIXEL_NV12_* code, h and w even, `frames` 2-byte aligned).
+ *         Or NV12 frames of 3 h w / 2 bytes (a TSM_PIXEL_NV12_* code, h and w even, `frames` 2-byte aligned), or frames of
+ *         another YUV code (tsm_pixel).
  * index:  DEVICE int32 [n_clips * n_segment], buffer-frame numbers.
  * out:    [n_clips, n_segment, ...one frame] in out_layout; out_layout, resize, crop, scale_255 as tsm_preprocess.
  *   out[c][k] = tsm_preprocess' result for buffer frame index[c * n_segment + k] (build_test_transform(person_crop=False):
@@ -491,7 +527,9 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
  * and complete their windows together; with person_crop = 1 the reference's accuracy option on streams.
  * arena:  one device allocation of arena_bytes, 16-byte aligned, holding every window's frames; pixel: TSM_PIXEL_U8 or
  *         TSM_PIXEL_F32 (values 0..255) for the whole launch, or a TSM_PIXEL_NV12_* code: then a window is n_segment
- *         contiguous NV12 frames of 3 h w / 2 bytes, and a descriptor with an odd h or w is invalid (zero frames).
+ *         contiguous NV12 frames of 3 h w / 2 bytes, and a descriptor with an odd h or w is invalid (zero frames); or another
+ *         YUV code (tsm_pixel): a window is n_segment contiguous frames of that format, and a descriptor whose h or w has
+ *         the wrong parity for it is invalid.
  * desc:   DEVICE int32 [n_windows, 8], 16-byte aligned; row c = {off_lo, off_hi, h, w, top, left, bh, bw}:
  *           off = off_hi * 2^32 + (unsigned) off_lo, the byte offset in `arena` of window c's first frame; its n_segment
  *                 frames are contiguous [n_segment, h, w, 3] of `pixel`;

@@ -26,6 +26,30 @@ def nv12_pixel(colorimetry: str = 'bt601') -> int:
         raise ValueError(f'colorimetry must be one of {tuple(_NV12_PIXELS)}, got {colorimetry!r}') from None
 
 
+# The other YUV formats: code 32 + 4 f + c, f in the order of YUV_FORMATS, c in the order of the NV12 codes (include/tsm_hip.h).
+YUV_FORMATS = ('i420', 'yv12', 'p010', 'yuyv', 'uyvy')
+PIXEL_YUV_BASE = 32
+for _f, _name in enumerate(YUV_FORMATS):
+    for _c, _col in enumerate(_NV12_PIXELS):
+        globals()[f'PIXEL_{_name.upper()}_{_col.upper().replace("-", "_")}'] = PIXEL_YUV_BASE + 4 * _f + _c
+del _f, _name, _c, _col
+
+
+def pixel_code(frame_format: str, colorimetry=None) -> int:
+    """The tsm_pixel code of uint8 frames of a frame format (``'rgb'``, ``'nv12'`` or one of YUV_FORMATS) and, for the YUV
+    formats, a colorimetry (transform.COLORIMETRIES; None: ``'bt601'``); ValueError for an unknown name, or a colorimetry given with ``'rgb'``."""
+    if frame_format == 'rgb':
+        if colorimetry is not None:
+            raise ValueError(f"colorimetry={colorimetry!r} was given with frame_format='rgb': RGB frames have none")
+        return PIXEL_U8
+    c = nv12_pixel('bt601' if colorimetry is None else colorimetry) - PIXEL_NV12_BT601
+    if frame_format == 'nv12':
+        return PIXEL_NV12_BT601 + c
+    if not isinstance(frame_format, str) or frame_format not in YUV_FORMATS:
+        raise ValueError(f"frame_format must be one of {('rgb', 'nv12') + YUV_FORMATS}, got {frame_format!r}")
+    return PIXEL_YUV_BASE + 4 * YUV_FORMATS.index(frame_format) + c
+
+
 DTYPE_F32, DTYPE_BF16X3, DTYPE_BF16 = 0, 1, 2
 CONV_CODE_SEGMENTED = 0x4000   # TSM_CONV_CODE_SEGMENTED: tsm_conv_args.code only
 DTYPES = {'f32': DTYPE_F32, 'bf16x3': DTYPE_BF16X3, 'bf16': DTYPE_BF16}

@@ -1218,8 +1218,8 @@ static int out_mode_of(int32_t out_layout, int *mode) {          // PreprocParam
 template <typename P>
 static int set_pixel_format(P *p, int32_t pixel, int32_t out_layout, int32_t scale_255) {
   tsm_host::Nv12Coef k{};
-  p->src_is_nv12 = tsm_host::nv12_coefficients(pixel, &k);
-  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32 && !p->src_is_nv12) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
+  p->src_yuv = tsm_host::nv12_coefficients(pixel, &k) ? 1 : tsm_host::yuv_coefficients(pixel, &k) ? 2 + tsm_host::yuv_layout_of(pixel) : 0;
+  if (pixel != TSM_PIXEL_U8 && pixel != TSM_PIXEL_F32 && !p->src_yuv) return fail(nullptr, TSM_ERR_INVALID_ARG, "bad pixel type");
   if (int rc = out_mode_of(out_layout, &p->out_mode)) return rc;
   p->src_is_u8 = pixel == TSM_PIXEL_U8;
   const int32_t words[tsm_host::kNv12CoefWords] = {k.y_off, k.cy, k.crv, k.cgu, k.cgv, k.cbu};
@@ -1227,8 +1227,21 @@ static int set_pixel_format(P *p, int32_t pixel, int32_t out_layout, int32_t sca
   p->pre_scale = scale_255 ? 1.0f / 255.0f : 1.0f;
   return TSM_OK;
 }
-// NV12 frames of a launch whose frame size is an argument: both sides even, the buffer 2-byte aligned.
-static int check_nv12_frames(const char *op, int32_t pixel, const void *frames, int h, int w) {
+// YUV frames of a launch whose frame size is an argument.  NV12: both sides even, the buffer 2-byte aligned.  The other
+// formats: the parity and the alignment of their layout (tsm_host::yuv_sides_ok, yuv_alignment).
+static int check_yuv_frames(const char *op, int32_t pixel, const void *frames, int h, int w) {
+  const int layout = tsm_host::yuv_layout_of(pixel);
+  if (layout >= 0) {
+    static const char *const names[tsm_host::kYuvLayouts] = {"I420", "YV12", "P010", "YUYV", "UYVY"};
+    const std::string what = std::string(op) + ": " + names[layout] + " frames ";
+    if (!tsm_host::yuv_sides_ok(layout, h, w))
+      return fail(nullptr, TSM_ERR_INVALID_ARG, what + (tsm_host::yuv_is_420(layout) ? "need an even h and an even w, got " : "need an even w, got ") +
+                                                    std::to_string(h) + " x " + std::to_string(w));
+    const int align = tsm_host::yuv_alignment(layout);
+    if (reinterpret_cast<uintptr_t>(frames) & (uintptr_t)(align - 1))
+      return fail(nullptr, TSM_ERR_INVALID_ARG, what + "must be " + std::to_string(align) + "-byte aligned");
+    return TSM_OK;
+  }
   if (!tsm_host::pixel_is_nv12(pixel)) return TSM_OK;
   if ((h | w) & 1)
     return fail(nullptr, TSM_ERR_INVALID_ARG, std::string(op) + ": NV12 frames need an even h and an even w, got " + std::to_string(h) + " x " + std::to_string(w));
@@ -1897,7 +1910,7 @@ int tsm_preprocess(const void *frames, int32_t pixel, int32_t n, int32_t h, int3
     return fail(nullptr, TSM_ERR_INVALID_ARG, "bad preprocess arguments");
   tsm::PreprocParams p{};
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
-  if (int rc = check_nv12_frames("preprocess", pixel, frames, h, w)) return rc;
+  if (int rc = check_yuv_frames("preprocess", pixel, frames, h, w)) return rc;
   p.src = frames; p.dst = out; p.n = n;
   if (!set_crop_geometry(&p, h, w, resize, crop)) return fail(nullptr, TSM_ERR_INVALID_ARG, "crop larger than the resized frame");
   return op_status("preprocess", tsm::launch_preprocess(p, static_cast<hipStream_t>(stream)));
@@ -1924,7 +1937,7 @@ int tsm_preprocess_clips(const void *frames, int32_t pixel, int64_t n_frames, in
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_clips: non-positive size");
   tsm::ClipPreprocParams p{};
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
-  if (int rc = check_nv12_frames("preprocess_clips", pixel, frames, h, w)) return rc;
+  if (int rc = check_yuv_frames("preprocess_clips", pixel, frames, h, w)) return rc;
   p.src = frames; p.dst = out; p.boxes = boxes; p.n_frames = n_frames; p.first_frame = first_frame;
   p.total_frames = total_frames; p.first_clip = first_clip; p.n_clips = n_clips; p.n_segment = n_segment;
   p.clip_step = clip_step; p.clip_stride = clip_stride; p.h = h; p.w = w; p.size = size;
@@ -1941,7 +1954,7 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
   tsm::IndexedPreprocParams q{};
   tsm::PreprocParams &p = q.pp;
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
-  if (int rc = check_nv12_frames("preprocess_indexed", pixel, frames, h, w)) return rc;
+  if (int rc = check_yuv_frames("preprocess_indexed", pixel, frames, h, w)) return rc;
   q.index = index; q.n_frames = n_frames; q.n_rows = (int64_t)n_clips * n_segment;
   p.src = frames; p.dst = out;
   if (!set_crop_geometry(&p, h, w, resize, crop))

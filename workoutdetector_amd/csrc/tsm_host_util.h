@@ -490,14 +490,46 @@ TSM_HOST_DEVICE inline bool nv12_coefficients(int pixel, Nv12Coef *k) {
     default: return false;
   }
 }
-// Bytes of one h x w frame of a pixel code (h, w in 1 .. 65535: below 2^36); -1 for an unknown code, or an NV12 code with an
-// odd side.
+// ---- The other YUV frame formats (TSM_PIXEL_I420_* .. TSM_PIXEL_UYVY_*): pixel code 32 + 4 f + c, f the layout below, c the
+// coefficient row in the order of the NV12 codes.  All dense; the conversion is nv12_pixel_rgb on 8-bit samples.
+//   I420  h * w Y bytes, then h/2 * w/2 U bytes, then h/2 * w/2 V bytes; a 2x2 block shares one U and one V byte.
+//   YV12  I420 with the V plane before the U plane.
+//   P010  NV12's arrangement in 16-bit little-endian samples, the 10 significant bits on top; a sample enters the formula as
+//         its HIGH byte (word >> 8), the low byte is ignored: a P010 frame is the NV12 frame made of its high bytes.
+//   YUYV  h rows of w/2 groups of the bytes (Y0, U, Y1, V): the two pixels of a group share U and V; rows share nothing.
+//   UYVY  the same with the bytes (U, Y0, V, Y1).
+// w is even everywhere, h too in the three 4:2:0 layouts.  P010, YUYV and UYVY frames are read in aligned 4-byte groups: the
+// base is 4-byte aligned (every frame size of theirs is a multiple of 4).
+enum YuvLayout { kYuvI420 = 0, kYuvYv12 = 1, kYuvP010 = 2, kYuvYuyv = 3, kYuvUyvy = 4, kYuvLayouts = 5 };
+// The layout of a pixel code, -1 for every code outside TSM_PIXEL_I420_BT601 .. TSM_PIXEL_UYVY_BT709_FULL (NV12's included).
+TSM_HOST_DEVICE inline int yuv_layout_of(int pixel) {
+  return pixel >= TSM_PIXEL_I420_BT601 && pixel <= TSM_PIXEL_UYVY_BT709_FULL ? (pixel - TSM_PIXEL_I420_BT601) >> 2 : -1;
+}
+// The coefficient row of such a code (that of the NV12 code with the same c); false (and *k untouched) for any other code.
+TSM_HOST_DEVICE inline bool yuv_coefficients(int pixel, Nv12Coef *k) {
+  return yuv_layout_of(pixel) >= 0 && nv12_coefficients(TSM_PIXEL_NV12_BT601 + ((pixel - TSM_PIXEL_I420_BT601) & 3), k);
+}
+TSM_HOST_DEVICE inline bool yuv_is_420(int layout) { return layout <= kYuvP010; }
+TSM_HOST_DEVICE inline bool yuv_sides_ok(int layout, int h, int w) {
+  return h >= 1 && w >= 2 && (w & 1) == 0 && (!yuv_is_420(layout) || (h & 1) == 0);
+}
+// Bytes of one frame (sides as yuv_sides_ok has them, at most 65535: below 2^34) and the alignment its base needs.
+TSM_HOST_DEVICE inline int64_t yuv_frame_bytes(int layout, int h, int w) {
+  const int64_t hw = (int64_t)h * w;
+  return layout == kYuvP010 ? hw * 3 : yuv_is_420(layout) ? hw / 2 * 3 : hw * 2;
+}
+TSM_HOST_DEVICE inline int yuv_alignment(int layout) { return layout >= kYuvP010 ? 4 : 1; }
+
+// Bytes of one h x w frame of a pixel code (h, w in 1 .. 65535: below 2^36); -1 for an unknown code, or a YUV code with a
+// side of the wrong parity.
 TSM_HOST_DEVICE inline int64_t frame_bytes_of(int pixel, int h, int w) {
   if (h < 1 || w < 1) return -1;
   const int64_t hw = (int64_t)h * w;
   if (pixel == TSM_PIXEL_U8) return hw * 3;
   if (pixel == TSM_PIXEL_F32) return hw * 12;
   if (pixel_is_nv12(pixel)) return ((h | w) & 1) ? -1 : hw / 2 * 3;
+  const int layout = yuv_layout_of(pixel);
+  if (layout >= 0) return yuv_sides_ok(layout, h, w) ? yuv_frame_bytes(layout, h, w) : -1;
   return -1;
 }
 TSM_HOST_DEVICE inline int nv12_clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
@@ -523,6 +555,53 @@ TSM_HOST_DEVICE inline bool nv12_window_descriptor_ok(const int32_t d[kWindowDes
   const int64_t frame_bytes = (int64_t)h * w / 2 * 3;       // < 2^33
   int64_t bytes;
   if (__builtin_mul_overflow((int64_t)n_segment, frame_bytes, &bytes) || bytes > arena_bytes - o) return false;
+  if (center && !center_crop_geometry_int(h, w, resize, crop, g)) return false;
+  *off = o;
+  return true;
+}
+
+// Byte offsets in an h x w frame of a YuvLayout of the 8-bit samples pixel (y, x) converts from: its Y, U and V (P010: the
+// high bytes).  yuv_group_offset: the aligned 4 bytes that hold both chroma samples of the pixel -- and, in the packed
+// layouts, both luma samples of its pair -- which the kernels load once (P010, YUYV, UYVY; the planar layouts have none).
+TSM_HOST_DEVICE inline int64_t yuv_group_offset(int layout, int h, int w, int64_t y, int64_t x) {
+  return layout == kYuvP010 ? (int64_t)h * w * 2 + (y >> 1) * w * 2 + ((x >> 1) << 2) : y * w * 2 + ((x >> 1) << 2);
+}
+TSM_HOST_DEVICE inline int64_t yuv_y_offset(int layout, int h, int w, int64_t y, int64_t x) {
+  switch (layout) {
+    case kYuvP010: return (y * w + x) * 2 + 1;
+    case kYuvYuyv: return yuv_group_offset(layout, h, w, y, x) + ((x & 1) << 1);
+    case kYuvUyvy: return yuv_group_offset(layout, h, w, y, x) + ((x & 1) << 1) + 1;
+    default: return y * w + x;
+  }
+}
+TSM_HOST_DEVICE inline int64_t yuv_u_offset(int layout, int h, int w, int64_t y, int64_t x) {
+  const int64_t plane = (int64_t)(h >> 1) * (w >> 1);
+  switch (layout) {
+    case kYuvI420: return (int64_t)h * w + (y >> 1) * (w >> 1) + (x >> 1);
+    case kYuvYv12: return (int64_t)h * w + plane + (y >> 1) * (w >> 1) + (x >> 1);
+    case kYuvUyvy: return yuv_group_offset(layout, h, w, y, x);
+    default: return yuv_group_offset(layout, h, w, y, x) + 1;       // P010 (the high byte of the first word), YUYV
+  }
+}
+TSM_HOST_DEVICE inline int64_t yuv_v_offset(int layout, int h, int w, int64_t y, int64_t x) {
+  const int64_t plane = (int64_t)(h >> 1) * (w >> 1);
+  switch (layout) {
+    case kYuvI420: return (int64_t)h * w + plane + (y >> 1) * (w >> 1) + (x >> 1);
+    case kYuvYv12: return (int64_t)h * w + (y >> 1) * (w >> 1) + (x >> 1);
+    case kYuvUyvy: return yuv_group_offset(layout, h, w, y, x) + 2;
+    default: return yuv_group_offset(layout, h, w, y, x) + 3;       // P010 (the high byte of the second word), YUYV
+  }
+}
+// window_descriptor_ok for a window of frames of a YuvLayout: n_segment contiguous frames of yuv_frame_bytes, the sides as
+// yuv_sides_ok has them.  (An offset is a multiple of 16 and a frame a multiple of the layout's alignment: every frame of a
+// valid window is aligned.)
+TSM_HOST_DEVICE inline bool yuv_window_descriptor_ok(int layout, const int32_t d[kWindowDescWords], int n_segment, int64_t arena_bytes,
+                                                     bool center, int resize, int crop, int64_t *off, CropGeometry *g) {
+  const int64_t o = (int64_t)(((uint64_t)(uint32_t)d[1] << 32) | (uint32_t)d[0]);
+  const int h = d[2], w = d[3];
+  if (o < 0 || (o & 15) != 0 || h > kWindowMaxSide || w > kWindowMaxSide || !yuv_sides_ok(layout, h, w) || o > arena_bytes) return false;
+  int64_t bytes;
+  if (__builtin_mul_overflow((int64_t)n_segment, yuv_frame_bytes(layout, h, w), &bytes) || bytes > arena_bytes - o) return false;
   if (center && !center_crop_geometry_int(h, w, resize, crop, g)) return false;
   *off = o;
   return true;

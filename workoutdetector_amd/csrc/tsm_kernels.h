@@ -51,7 +51,7 @@ struct PreprocParams {
   int nh, nw;         // resized size
   int top, left, crop;
   int src_is_u8;
-  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int src_yuv;        // 0: RGB frames; 1: NV12; 2 + tsm_host::YuvLayout: I420 .. UYVY.  Converted in the taps; src_is_u8 is 0
   int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // 0 = NHWC4 fp32, 1 = NCHW fp32, 2 = NHWC8 split-bf16, 3 = NHWC8 bf16
   float pre_scale;    // 1/255 when frames are to be scaled to [0,1] first, else 1
@@ -81,7 +81,7 @@ struct ClipPreprocParams {
   int n_clips, n_segment, clip_step, clip_stride;
   int h, w, size;
   int src_is_u8;
-  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int src_yuv;        // 0: RGB frames; 1: NV12; 2 + tsm_host::YuvLayout: I420 .. UYVY.  Converted in the taps; src_is_u8 is 0
   int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // as PreprocParams
   float pre_scale;
@@ -114,7 +114,7 @@ struct WindowPreprocParams {
   int person_crop;
   int resize, crop;   // crop: the output size in both modes
   int src_is_u8;
-  int src_is_nv12;    // the frames are NV12 (3 h w / 2 bytes each, h and w even), converted in the taps; src_is_u8 is 0
+  int src_yuv;        // 0: RGB frames; 1: NV12; 2 + tsm_host::YuvLayout: I420 .. UYVY.  Converted in the taps; src_is_u8 is 0
   int32_t nv12[6];    // tsm_host::Nv12Coef's words {y_off, cy, crv, cgu, cgv, cbu} (tsm_host_util.h)
   int out_mode;       // as PreprocParams
   float pre_scale;

@@ -170,7 +170,7 @@ hipError_t launch_to_f32(const float *x, float *y, int64_t n8, int prec, hipStre
 // stem's packed-pair input, see pack_input_kernel); neighbouring threads are neighbouring ox: contiguous 16-byte stores.
 // preprocess_kernel, preprocess_indexed_kernel, preprocess_clips_kernel and preprocess_windows_kernel are ONE row loop
 // (preprocess_rows) over four row sources -- which frame, and which window of it, output row f shows -- and two samplers over
-// one bilinear-and-normalise core, which read their taps from one of three tap sources (Taps<T>); preprocess_image_kernel
+// one bilinear-and-normalise core, which read their taps from a tap source (Taps<T>: RGB u8 | f32, NV12 and five more YUV formats); preprocess_image_kernel
 // (Pillow's antialiased resample, further down) shares the constants and the group writer.
 // Bilinear sampling follows ATen's CPU kernel (UpSampleBilinear2d, no antialias): src = scale * (dst + 0.5)
 // - 0.5 clamped at 0, scale = in / out, out = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11); then
@@ -295,6 +295,88 @@ struct Taps<Nv12> {
   }
 };
 
+// The other YUV sources (tsm_host_util.h: YuvLayout, the offsets and the descriptor rule are the host's text), one
+// specialisation per format over one body, YuvTaps<Tag>: the layout is a compile-time constant, so every offset folds to the
+// address arithmetic of that format alone and a launch pays for no format but its own.  Taps that share their chroma load
+// it once, as Taps<Nv12>'s do; `group` is what they share:
+//   * I420, Yv12: one U byte and one V byte per 2x2 block (two byte loads), luma one byte per tap.
+//   * P010: one aligned 4-byte load per 2x2 block holds the U and the V word; luma is the high byte of its word, one byte per tap.
+//   * Yuyv, Uyvy: one aligned 4-byte load per pixel pair holds both luma bytes, U and V: a tap needs no load of its own.
+//     Rows share nothing (4:2:2), so the second row loads again unless it is the first (a tap clamped at the border).
+struct I420 { static constexpr int kLayout = tsm_host::kYuvI420; };
+struct Yv12 { static constexpr int kLayout = tsm_host::kYuvYv12; };
+struct P010 { static constexpr int kLayout = tsm_host::kYuvP010; };
+struct Yuyv { static constexpr int kLayout = tsm_host::kYuvYuyv; };
+struct Uyvy { static constexpr int kLayout = tsm_host::kYuvUyvy; };
+template <typename Tag>
+struct YuvTaps {
+  static constexpr int L = Tag::kLayout;
+  static constexpr bool kPlanar = L == tsm_host::kYuvI420 || L == tsm_host::kYuvYv12;
+  static constexpr bool kPacked = L == tsm_host::kYuvYuyv || L == tsm_host::kYuvUyvy;
+  const unsigned char *frame;
+  int h, w;
+  tsm_host::Nv12Coef k;
+  static __device__ __forceinline__ YuvTaps of(const void *base, int64_t j, int h, int w, const int32_t *coef) {
+    return {static_cast<const unsigned char *>(base) + j * tsm_host::yuv_frame_bytes(L, h, w), h, w, tsm_host::nv12_coef_of(coef)};
+  }
+  static __device__ __forceinline__ bool descriptor_ok(const int32_t *d, int n_segment, int64_t arena_bytes, bool center, int resize,
+                                                       int crop, int64_t *off, tsm_host::CropGeometry *g) {
+    return tsm_host::yuv_window_descriptor_ok(L, d, n_segment, arena_bytes, center, resize, crop, off, g);
+  }
+  // what the taps of one chroma group share: (U | V << 8) of the planar layouts, the aligned 4 bytes of the others
+  __device__ __forceinline__ unsigned group(int64_t y, int64_t x) const {
+    if constexpr (kPlanar)
+      return (unsigned)frame[tsm_host::yuv_u_offset(L, h, w, y, x)] | ((unsigned)frame[tsm_host::yuv_v_offset(L, h, w, y, x)] << 8);
+    else
+      return *reinterpret_cast<const unsigned *>(frame + tsm_host::yuv_group_offset(L, h, w, y, x));
+  }
+  __device__ __forceinline__ void tap(int64_t y, int64_t x, unsigned g, bool m, float *t) const {
+    int Y, U, V;
+    if constexpr (kPlanar) {
+      Y = frame[tsm_host::yuv_y_offset(L, h, w, y, x)]; U = (int)(g & 255u); V = (int)(g >> 8);
+    } else if constexpr (L == tsm_host::kYuvP010) {
+      Y = frame[tsm_host::yuv_y_offset(L, h, w, y, x)]; U = (int)((g >> 8) & 255u); V = (int)(g >> 24);
+    } else if constexpr (L == tsm_host::kYuvYuyv) {
+      Y = (int)((g >> (((unsigned)x & 1u) << 4)) & 255u); U = (int)((g >> 8) & 255u); V = (int)(g >> 24);
+    } else {
+      Y = (int)((g >> ((((unsigned)x & 1u) << 4) + 8)) & 255u); U = (int)(g & 255u); V = (int)((g >> 16) & 255u);
+    }
+    int rgb[3];
+    tsm_host::nv12_pixel_rgb(k, Y, U, V, rgb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = m ? (float)rgb[c] : 0.f;
+  }
+  __device__ __forceinline__ void quad(int64_t y0, int64_t y1, int64_t x0, int64_t x1, bool m00, bool m01, bool m10, bool m11,
+                                       float t[4][3]) const {
+    const bool new_col = (x1 >> 1) != (x0 >> 1), new_row = kPacked ? y1 != y0 : (y1 >> 1) != (y0 >> 1);
+    const unsigned g00 = group(y0, x0);
+    unsigned g01 = g00;
+    if (new_col) g01 = group(y0, x1);
+    unsigned g10 = g00, g11 = g01;
+    if (new_row) {
+      g10 = group(y1, x0);
+      g11 = g10;
+      if (new_col) g11 = group(y1, x1);
+    }
+    tap(y0, x0, g00, m00, t[0]);
+    tap(y0, x1, g01, m01, t[1]);
+    tap(y1, x0, g10, m10, t[2]);
+    tap(y1, x1, g11, m11, t[3]);
+  }
+};
+#define TSM_YUV_TAPS(Tag)                                                          \
+  template <>                                                                      \
+  struct Taps<Tag> : YuvTaps<Tag> {                                                \
+    Taps() = default;                                                              \
+    __device__ __forceinline__ Taps(const YuvTaps<Tag> &b) : YuvTaps<Tag>(b) {}    \
+  }
+TSM_YUV_TAPS(I420);
+TSM_YUV_TAPS(Yv12);
+TSM_YUV_TAPS(P010);
+TSM_YUV_TAPS(Yuyv);
+TSM_YUV_TAPS(Uyvy);
+#undef TSM_YUV_TAPS
+
 // The row loop.  A row source has a `Row` (where a row's pixels come from), locate(f, &row) -- false: the row has no frame
 // and is the zero frame -- and pixel(row, oy, ox, v), its sampler.  Sources are passed by value and inlined.
 template <typename Source>
@@ -363,28 +445,38 @@ static bool crop_window_ok(const P &p) {
   return p.h > 0 && p.w > 0 && p.crop > 0 && p.top >= 0 && p.left >= 0 && p.top + p.crop <= p.nh && p.left + p.crop <= p.nw;
 }
 
-// NV12 frames of a launch whose size the host knows: both sides even, the buffer 2-byte aligned (the chroma pair is one load).
-static bool nv12_frames_ok(int is_nv12, const void *src, int h, int w) {
-  return !is_nv12 || (((h | w) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 1) == 0);
+// YUV frames of a launch whose size the host knows (src_yuv of the parameter blocks).  NV12: both sides even, the buffer
+// 2-byte aligned (the chroma pair is one load); the other formats: their layout's parity and alignment.
+static bool yuv_frames_ok(int src_yuv, const void *src, int h, int w) {
+  if (src_yuv >= 2)
+    return tsm_host::yuv_sides_ok(src_yuv - 2, h, w) && (reinterpret_cast<uintptr_t>(src) & (uintptr_t)(tsm_host::yuv_alignment(src_yuv - 2) - 1)) == 0;
+  return !src_yuv || (((h | w) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 1) == 0);
 }
 
 // One grid-stride launch of a row-loop kernel covers any number of rows (64-bit group index): nothing of the launch geometry
 // limits a range of clips or a table.
-#define TSM_LAUNCH_ROWS(KERNEL, is_u8, is_nv12, n_rows, size, out_mode, stream, params)                    \
+#define TSM_LAUNCH_ROWS(KERNEL, is_u8, src_yuv, n_rows, size, out_mode, stream, params)                    \
   do {                                                                                                      \
     const int px_ = (out_mode) >= 2 ? 2 : 1;                                                                \
     const unsigned grid_ = grid_for((int64_t)(n_rows) * (size) * (((size) + px_ - 1) / px_), 8192);         \
-    if (is_nv12)                                                                                            \
-      TSM_KLAUNCH(KERNEL<Nv12>, dim3(grid_), dim3(256), 0, stream, params);                                 \
-    else if (is_u8)                                                                                         \
-      TSM_KLAUNCH(KERNEL<unsigned char>, dim3(grid_), dim3(256), 0, stream, params);                        \
-    else                                                                                                    \
-      TSM_KLAUNCH(KERNEL<float>, dim3(grid_), dim3(256), 0, stream, params);                                \
+    switch (src_yuv) {                                                                                      \
+      case 1: TSM_KLAUNCH(KERNEL<Nv12>, dim3(grid_), dim3(256), 0, stream, params); break;                  \
+      case 2 + tsm_host::kYuvI420: TSM_KLAUNCH(KERNEL<I420>, dim3(grid_), dim3(256), 0, stream, params); break; \
+      case 2 + tsm_host::kYuvYv12: TSM_KLAUNCH(KERNEL<Yv12>, dim3(grid_), dim3(256), 0, stream, params); break; \
+      case 2 + tsm_host::kYuvP010: TSM_KLAUNCH(KERNEL<P010>, dim3(grid_), dim3(256), 0, stream, params); break; \
+      case 2 + tsm_host::kYuvYuyv: TSM_KLAUNCH(KERNEL<Yuyv>, dim3(grid_), dim3(256), 0, stream, params); break; \
+      case 2 + tsm_host::kYuvUyvy: TSM_KLAUNCH(KERNEL<Uyvy>, dim3(grid_), dim3(256), 0, stream, params); break; \
+      default:                                                                                              \
+        if (is_u8)                                                                                          \
+          TSM_KLAUNCH(KERNEL<unsigned char>, dim3(grid_), dim3(256), 0, stream, params);                    \
+        else                                                                                                \
+          TSM_KLAUNCH(KERNEL<float>, dim3(grid_), dim3(256), 0, stream, params);                            \
+    }                                                                                                       \
   } while (0)
 
 hipError_t launch_preprocess(const PreprocParams &p, hipStream_t s) {
-  if (p.n <= 0 || !crop_window_ok(p) || !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w)) return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_kernel, p.src_is_u8, p.src_is_nv12, p.n, p.crop, p.out_mode, s, p);
+  if (p.n <= 0 || !crop_window_ok(p) || !yuv_frames_ok(p.src_yuv, p.src, p.h, p.w)) return hipErrorInvalidValue;
+  TSM_LAUNCH_ROWS(preprocess_kernel, p.src_is_u8, p.src_yuv, p.n, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -526,11 +618,11 @@ hipError_t launch_preprocess_clips(const ClipPreprocParams &p, hipStream_t s) {
   // every frame index the kernel will form, checked here (launch_gather_clips' rules; there is no pad frame to check)
   tsm_host::WindowRange r;
   if (!p.src || !p.dst || !p.boxes || p.h <= 0 || p.w <= 0 || p.size <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
-      !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w) ||
+      !yuv_frames_ok(p.src_yuv, p.src, p.h, p.w) ||
       !tsm_host::clip_window_range(p.total_frames, p.first_clip, p.n_clips, p.n_segment, p.clip_step, p.clip_stride, p.first_frame,
                                    p.n_frames, &r))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_clips_kernel, p.src_is_u8, p.src_is_nv12, (int64_t)p.n_clips * p.n_segment, p.size, p.out_mode, s, p);
+  TSM_LAUNCH_ROWS(preprocess_clips_kernel, p.src_is_u8, p.src_yuv, (int64_t)p.n_clips * p.n_segment, p.size, p.out_mode, s, p);
   return hipGetLastError();
 }
 
@@ -570,9 +662,9 @@ __global__ void __launch_bounds__(256) preprocess_indexed_kernel(const IndexedPr
 hipError_t launch_preprocess_indexed(const IndexedPreprocParams &q, hipStream_t s) {
   const PreprocParams &p = q.pp;
   if (!p.src || !p.dst || !q.index || q.n_frames <= 0 || q.n_rows <= 0 || !crop_window_ok(p) || p.out_mode < 0 || p.out_mode > 3 ||
-      !nv12_frames_ok(p.src_is_nv12, p.src, p.h, p.w))
+      !yuv_frames_ok(p.src_yuv, p.src, p.h, p.w))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, p.src_is_nv12, q.n_rows, p.crop, p.out_mode, s, q);
+  TSM_LAUNCH_ROWS(preprocess_indexed_kernel, p.src_is_u8, p.src_yuv, q.n_rows, p.crop, p.out_mode, s, q);
   return hipGetLastError();
 }
 
@@ -648,7 +740,7 @@ hipError_t launch_preprocess_windows(const WindowPreprocParams &p, hipStream_t s
       p.arena_bytes <= 0 || p.n_windows <= 0 || p.n_segment <= 0 || p.resize <= 0 || p.crop <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
       (p.person_crop != 0 && p.person_crop != 1) || (!p.person_crop && p.crop > p.resize))
     return hipErrorInvalidValue;
-  TSM_LAUNCH_ROWS(preprocess_windows_kernel, p.src_is_u8, p.src_is_nv12, (int64_t)p.n_windows * p.n_segment, p.crop, p.out_mode, s, p);
+  TSM_LAUNCH_ROWS(preprocess_windows_kernel, p.src_is_u8, p.src_yuv, (int64_t)p.n_windows * p.n_segment, p.crop, p.out_mode, s, p);
   return hipGetLastError();
 }
 

@@ -705,20 +705,27 @@ def _pixel_of(frames, want: str, u8_only: bool = False, min_frames: int = 0) -> 
 
 def _staged_frames(frames, frame_format: str, colorimetry: Optional[str], want: str, min_frames: int = 0) -> tuple:
     """``(pixel, n, h, w)`` of staged raw frames: ``_pixel_of``'s for ``frame_format='rgb'``; for ``'nv12'`` a contiguous CUDA
-    uint8 tensor [n, 3h/2, w] with h and w even (h, w: the luma size) and the pixel code of the colorimetry.  Every refusal is
-    a ValueError raised before the library is touched."""
+    uint8 tensor [n, 3h/2, w] with h and w even (h, w: the luma size) and the pixel code of the colorimetry; for the other
+    YUV formats (``transform.YUV_FORMATS``) the same with that format's container and parity.  Every refusal is a
+    ValueError raised before the library is touched."""
     import torch
-    from .transform import check_frame_format, nv12_luma_hw
+    from .transform import check_frame_format, yuv_luma_hw
     colorimetry = check_frame_format(frame_format, colorimetry)
     if frame_format == 'rgb':
         pixel = _pixel_of(frames, want, min_frames=min_frames)
         return (pixel,) + tuple(int(d) for d in frames.shape[:3])
     if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 3
             and frames.is_contiguous() and frames.shape[0] >= min_frames):
-        raise ValueError(f'NV12 frames must be a contiguous uint8 CUDA tensor [n >= {min_frames}, 3h/2, w], got '
+        raise ValueError(f'{frame_format.upper()} frames must be a contiguous uint8 CUDA tensor [n >= {min_frames}, rows, bytes], got '
                          f'{getattr(frames, "dtype", type(frames))} {tuple(getattr(frames, "shape", ()))}')
-    h, w = nv12_luma_hw(frames.shape)
-    return _lib.nv12_pixel(colorimetry), int(frames.shape[0]), h, w
+    h, w = yuv_luma_hw(frames.shape, frame_format)
+    return _lib.pixel_code(frame_format, colorimetry), int(frames.shape[0]), h, w
+
+
+def _yuv_bytes(frames, frame_format: str):
+    """Staged frames as the uint8 container of their format: a 16-bit ``'p010'`` tensor [n, 3h/2, w] is viewed as bytes."""
+    from .transform import yuv_frame_bytes_view
+    return yuv_frame_bytes_view(frames, frame_format) if hasattr(frames, 'is_cuda') else frames
 
 
 def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: bool = False, packed: bool = True,
@@ -730,10 +737,13 @@ def preprocess_frames(frames, resize: int = 256, crop: int = 224, scale_255: boo
     split-bf16 group per pixel pair; LAYOUT_NTHWC8B: [n,crop,ceil(crop/2),4] float slots = 8 bf16 per pair).
     ``frame_format='nv12'``: frames are CUDA uint8 [n,3H/2,W] decoder surfaces (H, W even), converted to RGB inside the
     launch's taps by ``colorimetry`` (``transform.COLORIMETRIES``, default ``'bt601'``): bit for bit the result for
-    ``transform.nv12_to_rgb(frames)``, and no RGB frame is written."""
+    ``transform.nv12_to_rgb(frames)``, and no RGB frame is written.  ``frame_format`` in ``transform.YUV_FORMATS``
+    (``'i420'``, ``'yv12'``, ``'p010'``, ``'yuyv'``, ``'uyvy'``): the uint8 container of that format (a 16-bit ``'p010'``
+    tensor is taken as its bytes), bit for bit the result for ``transform.yuv_to_rgb(frames, frame_format, colorimetry)``."""
     import torch
     if hasattr(frames, 'contiguous'):
         frames = frames.contiguous()
+    frames = _yuv_bytes(frames, frame_format)
     pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a CUDA tensor [n,H,W,3]')
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4 if packed else _lib.LAYOUT_NTCHW
@@ -855,6 +865,7 @@ def preprocess_clips(frames, boxes, first_frame: int, total_frames: int, first_c
     clips are (0 - mean) / std.  ``frame_format='nv12'`` / ``colorimetry``: as ``preprocess_frames``; the boxes are in luma
     pixels and the zero fill is RGB 0."""
     import torch
+    frames = _yuv_bytes(frames, frame_format)
     pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a contiguous CUDA tensor [n,H,W,3]')
     if not (hasattr(boxes, 'is_cuda') and boxes.is_cuda and boxes.device == frames.device and boxes.dtype == torch.int32
             and tuple(boxes.shape) == (n_clips, 4) and boxes.is_contiguous()):
@@ -883,6 +894,7 @@ def preprocess_indexed(frames, index, resize: int = 256, crop: int = 224, scale_
     import torch
     if frame_format == 'rgb' and (not hasattr(frames, 'is_cuda') or frames.dtype not in (torch.uint8, torch.float32)):
         raise ValueError(f'frames must be a uint8 or float32 tensor, got {getattr(frames, "dtype", type(frames))}')
+    frames = _yuv_bytes(frames, frame_format)
     pixel, n, h, w = _staged_frames(frames, frame_format, colorimetry, 'a contiguous CUDA tensor [n >= 1,H,W,3]', min_frames=1)
     if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
             and index.dim() == 2 and index.shape[0] > 0 and index.shape[1] > 0 and index.is_contiguous()):
@@ -912,12 +924,13 @@ def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_c
     is total in the table: a window whose descriptor does not lie in the arena (or whose centre crop does not fit) reads
     nothing and yields normalised zero frames.  ``frame_format='nv12'``: the same uint8 arena with windows of ``n_segment``
     contiguous NV12 frames [3h/2, w] (``window_descriptors(..., frame_format='nv12')``; h, w of a row the luma size), converted
-    in the taps by ``colorimetry``; a row with an odd side is invalid."""
+    in the taps by ``colorimetry``; a row with an odd side is invalid.  A ``transform.YUV_FORMATS`` name: windows of that
+    format's frames, and a row whose side has the wrong parity for it is invalid."""
     import torch
     from .transform import check_frame_format
     colorimetry = check_frame_format(frame_format, colorimetry)
     if colorimetry is not None and getattr(arena, 'dtype', None) != torch.uint8:
-        raise ValueError('an arena of NV12 windows must be a uint8 tensor')
+        raise ValueError(f'an arena of {frame_format.upper()} windows must be a uint8 tensor')
     if not (hasattr(arena, 'is_cuda') and arena.is_cuda and arena.dtype in (torch.uint8, torch.float32) and arena.is_contiguous()
             and arena.numel() > 0 and arena.data_ptr() % 16 == 0):
         raise ValueError('arena must be a contiguous, 16-byte aligned, non-empty uint8 or float32 CUDA tensor')
@@ -930,7 +943,7 @@ def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_c
     if layout is None:
         layout = _lib.LAYOUT_NTHWC4
     out = _out(out, (n_windows, n_segment) + _frame_shape(layout, crop), torch.float32, arena)
-    pixel = _lib.nv12_pixel(colorimetry) if colorimetry is not None else _lib.PIXEL_U8 if arena.dtype == torch.uint8 else _lib.PIXEL_F32
+    pixel = _lib.pixel_code(frame_format, colorimetry) if colorimetry is not None else _lib.PIXEL_U8 if arena.dtype == torch.uint8 else _lib.PIXEL_F32
     _lib.check(_lib.load().tsm_preprocess_windows(arena.data_ptr(), arena.numel() * arena.element_size(), pixel, desc.data_ptr(),
                                                   n_windows, n_segment, int(bool(person_crop)), out.data_ptr(), layout,
                                                   int(resize), int(crop), int(scale_255), _stream(arena)))

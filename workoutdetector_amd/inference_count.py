@@ -57,7 +57,8 @@ from . import staging
 from .counting import RepCounter, pred_to_count, scores_to_preds, vote_states  # noqa: F401  (re-export)
 from .repcount import RepcountHelper
 from .transform import (ImageTransform, PersonCropTransform, TestTransform, as_frames_u8, build_test_transform,
-                        check_frame_format, frame_hw, need_frame_engine, nv12_black, nv12_to_rgb)
+                        black_frame, check_frame_format, frame_hw, need_frame_engine, nv12_black, nv12_to_rgb,
+                        yuv_frame_bytes_view, yuv_to_rgb)
 
 NUM_SEGMENTS = 8
 CLIP_SPAN = 16
@@ -161,12 +162,14 @@ def even_frame_range(total: int, lo: int, hi: int) -> Tuple[int, int]:
 def _stage(dev, total: int, lo: int, hi: int, f_lo: int, hw: Tuple[int, int], even: torch.Tensor,
            stream: Optional[object] = None, frame_format: str = 'rgb', colorimetry: Optional[str] = None) -> StagedVideo:
     """``even`` -- the frames ``even_frame_range`` names for clips [lo, hi) -- and a zero frame behind them, to ``dev``.
-    Behind NV12 frames the pad is ``nv12_black``, not zero bytes: the reference pads a clip with RGB-zero frames, and only
-    black converts to that (zero bytes are a saturated green)."""
+    Behind NV12 frames the pad is ``nv12_black`` (behind the other YUV formats ``black_frame``), not zero bytes: the reference
+    pads a clip with RGB-zero frames, and only black converts to that (zero bytes are a saturated green)."""
     def fill(pinned: torch.Tensor) -> None:
         pinned[:-1].copy_(even)
         if frame_format == 'nv12':
             pinned[-1].copy_(torch.from_numpy(nv12_black(hw[0], hw[1], colorimetry)))
+        elif frame_format != 'rgb':
+            pinned[-1].copy_(torch.from_numpy(black_frame(hw[0], hw[1], frame_format, colorimetry)))
         else:
             pinned[-1].zero_()          # the zero frame the padded tail clip reads
     frames, ready = staging.upload((even.shape[0] + 1,) + tuple(even.shape[1:]), fill, dev, stream)
@@ -174,13 +177,15 @@ def _stage(dev, total: int, lo: int, hi: int, f_lo: int, hw: Tuple[int, int], ev
 
 
 def _rgb_staged(st: StagedVideo) -> StagedVideo:
-    """A staged NV12 range as host RGB frames (``nv12_to_rgb``): what every path that is not a HIP transform takes."""
-    if st.frame_format != 'nv12':
+    """A staged YUV range as host RGB frames (``nv12_to_rgb`` / ``yuv_to_rgb``): what every path that is not a HIP transform
+    takes."""
+    if st.frame_format == 'rgb':
         return st
     if st.on_device:
         staging.wait_upload(st.frames, st.ready)
     even = (st.frames[:-1] if st.on_device else st.frames).cpu()
-    rgb = torch.from_numpy(nv12_to_rgb(even.numpy(), st.colorimetry)) if even.shape[0] else even.new_zeros((0,) + st.hw + (3,))
+    to_rgb = nv12_to_rgb if st.frame_format == 'nv12' else (lambda a, c: yuv_to_rgb(a, st.frame_format, c))
+    rgb = torch.from_numpy(to_rgb(even.numpy(), st.colorimetry)) if even.shape[0] else even.new_zeros((0,) + st.hw + (3,))
     return StagedVideo(st.total, st.lo, st.hi, st.f_lo, st.hw, rgb, False)
 
 
@@ -190,14 +195,18 @@ def stage_video(model, video_thwc_u8: torch.Tensor, clip_range: Optional[Tuple[i
     pinned buffer on ``stream`` (so the copy of video i+1 can run under the compute of video i).
     ``frame_format='nv12'``: the video is uint8 [T, 3H/2, W] decoder surfaces (``colorimetry``: default ``'bt601'``), staged
     as they are -- half the bytes of RGB -- with ``nv12_black`` as the pad frame; ``hw`` is the luma size.  A model without a
-    device path gets ``nv12_to_rgb`` of the sampled frames on the host, and from there exactly the RGB path."""
+    device path gets ``nv12_to_rgb`` of the sampled frames on the host, and from there exactly the RGB path.  A
+    ``transform.YUV_FORMATS`` name: the same with that format's container per frame, ``black_frame`` and ``yuv_to_rgb``."""
     colorimetry = check_frame_format(frame_format, colorimetry)
-    nv12 = frame_format == 'nv12'
-    if nv12 and (video_thwc_u8.dtype != torch.uint8 or video_thwc_u8.dim() != 3):
-        raise ValueError(f'an NV12 video must be uint8 [T, 3H/2, W], got {video_thwc_u8.dtype} {tuple(video_thwc_u8.shape)}')
+    yuv = frame_format != 'rgb'                   # (any YUV format: one 2-d uint8 container per frame)
+    if yuv and frame_format != 'nv12':
+        video_thwc_u8 = yuv_frame_bytes_view(video_thwc_u8, frame_format)
+    if yuv and (video_thwc_u8.dtype != torch.uint8 or video_thwc_u8.dim() != 3):
+        what = 'an NV12 video must be uint8 [T, 3H/2, W]' if frame_format == 'nv12' else f'a {frame_format} video must be uint8 [T, rows, bytes]'
+        raise ValueError(f'{what}, got {video_thwc_u8.dtype} {tuple(video_thwc_u8.shape)}')
     total = int(video_thwc_u8.shape[0])
     lo, hi = clip_range if clip_range is not None else (0, len(clip_starts(total)))
-    hw = frame_hw(video_thwc_u8.shape, frame_format) if nv12 else (int(video_thwc_u8.shape[1]), int(video_thwc_u8.shape[2]))
+    hw = frame_hw(video_thwc_u8.shape, frame_format) if yuv else (int(video_thwc_u8.shape[1]), int(video_thwc_u8.shape[2]))
     if hi <= lo:
         return StagedVideo(total, lo, lo, 0, hw, video_thwc_u8[:0], False, None, frame_format, colorimetry)
     f_lo, f_hi = even_frame_range(total, lo, hi)
@@ -833,9 +842,9 @@ def inference_dataset(model, splits: List[str], out_dir: str, checkpoint: str, p
     colorimetry = check_frame_format(frame_format, colorimetry)
     rank, _world = tdist.world_info()
     if shard is None:
-        shard = 'clips' if person_crop or frame_format == 'nv12' else 'global'
-    if frame_format == 'nv12' and shard == 'global':
-        raise NotImplementedError("frame_format='nv12' runs with shard='clips' or 'videos'; shard='global' takes RGB frames only")
+        shard = 'clips' if person_crop or frame_format != 'rgb' else 'global'
+    if frame_format != 'rgb' and shard == 'global':
+        raise NotImplementedError(f"frame_format={frame_format!r} runs with shard='clips' or 'videos'; shard='global' takes RGB frames only")
     if shard not in ('clips', 'videos', 'global'):
         raise ValueError("shard must be 'clips', 'videos' or 'global'")
     if person_crop and shard == 'global':

@@ -28,7 +28,7 @@ from . import staging
 from .counting import RepCounter, scores_to_preds
 from .inference_count import NUM_SEGMENTS, need_clip_rows
 from .transform import (Box, PersonCropTransform, TestTransform, build_test_transform, check_frame_format, nv12_luma_hw,
-                        nv12_to_rgb, person_box, window_descriptors)
+                        nv12_to_rgb, person_box, window_descriptors, yuv_frame_bytes_view, yuv_luma_hw, yuv_to_rgb)
 
 
 @dataclass
@@ -60,7 +60,9 @@ class StreamBatcher:
     surfaces, uint8 [3H/2, W] of any mix of even sizes; boxes are in luma pixels.  A batch is still ONE launch, and one launch
     has one pixel code, so the format belongs to the batcher, not to the frame.  The windows are staged as they are (half the
     bytes of RGB, in the pinned budget too) and converted inside the transform's taps: states and counts equal those of an RGB
-    batcher fed ``nv12_to_rgb`` of the frames.  On the host path the frames are converted when they arrive."""
+    batcher fed ``nv12_to_rgb`` of the frames.  On the host path the frames are converted when they arrive.  A
+    ``transform.YUV_FORMATS`` name (``'i420'``, ``'yv12'``, ``'p010'``, ``'yuyv'``, ``'uyvy'``): the same with that format's
+    uint8 container per frame (a 16-bit ``'p010'`` frame is taken as its bytes) and ``yuv_to_rgb`` as the conversion."""
 
     def __init__(self, model, threshold: float = 0.5, softmax: bool = True, step: int = 8, max_batch: int = 32,
                  transform: Optional[TestTransform] = None,
@@ -112,6 +114,13 @@ class StreamBatcher:
             nv12_luma_hw(arr.shape)
             if self._dev is None:
                 arr = nv12_to_rgb(arr, self.colorimetry)[0]
+        elif self.frame_format != 'rgb':
+            arr = yuv_frame_bytes_view(arr, self.frame_format)
+            if arr.dtype != np.uint8 or arr.ndim != 2:
+                raise ValueError(f'a {self.frame_format} frame must be its uint8 container [rows, bytes], got {arr.dtype} {arr.shape}')
+            yuv_luma_hw(arr.shape, self.frame_format)
+            if self._dev is None:
+                arr = yuv_to_rgb(arr, self.frame_format, self.colorimetry)[0]
         elif arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
             raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
         st.frames_seen += 1
@@ -234,8 +243,8 @@ class StreamBatcher:
             done = torch.cuda.Event()
             done.record()
             self._inflight += [(done, w) for w in windows]
-            nv12 = self.frame_format == 'nv12'
-            table = window_descriptors([nv12_luma_hw(w.shape) if nv12 else tuple(w.shape[1:]) for w in windows], offsets,
+            yuv = self.frame_format != 'rgb'
+            table = window_descriptors([yuv_luma_hw(w.shape, self.frame_format) if yuv else tuple(w.shape[1:]) for w in windows], offsets,
                                        crops if self.person_crop else None, resize=tf.size, crop=tf.crop, frame_format=self.frame_format)
             clips = preprocess_windows(arena, staging.upload_table(torch.from_numpy(table), dev), len(windows), NUM_SEGMENTS,
                                        person_crop=self.person_crop, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255,

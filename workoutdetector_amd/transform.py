@@ -172,7 +172,8 @@ _NV12_COEFFICIENTS = {
     'bt709-full': (0, 16384, 25802, -3069, -7670, 30402),
 }
 COLORIMETRIES = tuple(_NV12_COEFFICIENTS)
-FRAME_FORMATS = ('rgb', 'nv12')
+YUV_FORMATS = ('i420', 'yv12', 'p010', 'yuyv', 'uyvy')     # the order of the pixel codes 32 + 4 f + c (include/tsm_hip.h)
+FRAME_FORMATS = ('rgb', 'nv12') + YUV_FORMATS
 # (Kr, Kb, limited) of each colorimetry: the float64 matrices the integer rows are rounded from
 _NV12_MATRIX = {'bt601': (0.299, 0.114, True), 'bt709': (0.2126, 0.0722, True),
                 'bt601-full': (0.299, 0.114, False), 'bt709-full': (0.2126, 0.0722, False)}
@@ -188,7 +189,7 @@ def nv12_coefficients(colorimetry: str = 'bt601') -> Tuple[int, int, int, int, i
 
 def check_frame_format(frame_format: str, colorimetry: Optional[str]) -> Optional[str]:
     """The colorimetry a call runs with: None for ``'rgb'`` frames (which take none: giving one is a ValueError), for
-    ``'nv12'`` the given one (default ``'bt601'``), checked.  Touches nothing but its arguments."""
+    ``'nv12'`` and the YUV_FORMATS the given one (default ``'bt601'``), checked.  Touches nothing but its arguments."""
     if frame_format not in FRAME_FORMATS:
         raise ValueError(f'frame_format must be one of {FRAME_FORMATS}, got {frame_format!r}')
     if frame_format == 'rgb':
@@ -209,14 +210,177 @@ def nv12_luma_hw(shape) -> Tuple[int, int]:
     return rows // 3 * 2, w
 
 
+# ---- The other YUV formats (YUV_FORMATS), all dense; (h, w) is the luma size and w is even:
+#   'i420'  [3h/2, w] bytes: h rows of Y, then the h/2 x w/2 U plane, then the V plane (FFmpeg's yuv420p); h even.
+#   'yv12'  'i420' with the V plane before the U plane.
+#   'p010'  [3h/2, 2w] bytes: NV12's arrangement in 16-bit little-endian samples, 10 significant bits on top (a 16-bit
+#           array [3h/2, w] is taken as its bytes); h even.  A sample converts as its HIGH byte, the low byte is ignored:
+#           a P010 frame is the NV12 frame of its high bytes.
+#   'yuyv'  [h, 2w] bytes: per pixel pair (Y0, U, Y1, V); the pair shares U and V, rows share nothing; any h >= 1.
+#   'uyvy'  [h, 2w] bytes: per pixel pair (U, Y0, V, Y1).
+def _is_420(frame_format: str) -> bool:
+    return frame_format in ('nv12', 'i420', 'yv12', 'p010')
+
+
+def yuv_luma_hw(shape, frame_format: str) -> Tuple[int, int]:
+    """The luma size ``(h, w)`` of frames of ``'nv12'`` or a YUV_FORMATS name whose last two dimensions are those of the
+    format's uint8 container; ValueError when they cannot be: rows no multiple of 3 (4:2:0), an odd w, a side of 0."""
+    if frame_format in ('nv12', 'i420', 'yv12'):
+        try:
+            return nv12_luma_hw(shape)
+        except ValueError:
+            raise ValueError(f'{frame_format} frames are [3h/2, w] with h and w even, got {int(shape[-2])} x {int(shape[-1])}') from None
+    if frame_format not in YUV_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS[1:]}, got {frame_format!r}')
+    rows, cols = int(shape[-2]), int(shape[-1])
+    if frame_format == 'p010':
+        if rows <= 0 or cols <= 0 or rows % 3 != 0 or cols % 4 != 0:
+            raise ValueError(f'p010 frames are [3h/2, 2w] bytes with h and w even, got {rows} x {cols}')
+        return rows // 3 * 2, cols // 2
+    if rows <= 0 or cols <= 0 or cols % 4 != 0:
+        raise ValueError(f'{frame_format} frames are [h, 2w] bytes with w even, got {rows} x {cols}')
+    return rows, cols // 2
+
+
+def frame_container(h: int, w: int, frame_format: str) -> Tuple[int, ...]:
+    """The shape of one uint8 frame of luma size h x w as it is staged: ``(h, w, 3)`` for ``'rgb'``, else the two dimensions
+    listed above; ValueError for a side of the wrong parity."""
+    if frame_format not in FRAME_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS}, got {frame_format!r}')
+    if frame_format == 'rgb':
+        return (h, w, 3)
+    if h <= 0 or w <= 0 or w % 2 or (_is_420(frame_format) and h % 2):
+        raise ValueError(f'{frame_format} needs an even w' + (' and an even h' if _is_420(frame_format) else '') + f', got {h} x {w}')
+    return {'p010': (3 * h // 2, 2 * w), 'yuyv': (h, 2 * w), 'uyvy': (h, 2 * w)}.get(frame_format, (3 * h // 2, w))
+
+
 def frame_hw(shape, frame_format: str = 'rgb') -> Tuple[int, int]:
-    """``(h, w)`` of one frame of a video or frame whose shape is ``[..., h, w, 3]`` (``'rgb'``) or ``[..., 3h/2, w]``."""
-    return nv12_luma_hw(shape) if frame_format == 'nv12' else (int(shape[-3]), int(shape[-2]))
+    """``(h, w)`` of one frame of a video or frame whose shape is ``[..., h, w, 3]`` (``'rgb'``) or ends in the container
+    of a YUV format (``[..., 3h/2, w]`` for ``'nv12'``)."""
+    return (int(shape[-3]), int(shape[-2])) if frame_format == 'rgb' else yuv_luma_hw(shape, frame_format)
 
 
 def frame_bytes(h: int, w: int, frame_format: str = 'rgb') -> int:
     """Bytes of one staged uint8 frame of luma size h x w."""
-    return 3 * h * w // 2 if frame_format == 'nv12' else 3 * h * w
+    return {'rgb': 3 * h * w, 'p010': 3 * h * w, 'yuyv': 2 * h * w, 'uyvy': 2 * h * w}.get(frame_format, 3 * h * w // 2)
+
+
+def yuv_frame_bytes_view(frames, frame_format: str):
+    """``frames`` (NumPy array or tensor) as the uint8 container of its format: a 16-bit ``'p010'`` array [..., 3h/2, w] is
+    viewed as bytes [..., 3h/2, 2w] (little-endian, as the format is); anything else is returned as it is."""
+    if frame_format != 'p010':
+        return frames
+    if isinstance(frames, torch.Tensor):
+        if frames.dtype in (torch.int16, getattr(torch, 'uint16', torch.int16)):
+            return frames.contiguous().view(torch.uint8)
+    elif isinstance(frames, np.ndarray) and frames.dtype in (np.uint16, np.int16):
+        return np.ascontiguousarray(frames).astype('<u2', copy=False).view(np.uint8)
+    return frames
+
+
+def yuv_planes(frames, frame_format: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """uint8 frames ``[n, ...container]`` -> the 8-bit samples every pixel converts from: ``(Y, U, V)``, each uint8
+    ``[n, h, w]`` (chroma repeated over the pixels that share it).  ``'nv12'`` and the YUV_FORMATS."""
+    h, w = yuv_luma_hw(frames.shape, frame_format)
+    a = frames.reshape((-1,) + tuple(frames.shape[-2:]))
+    n = a.shape[0]
+    up = lambda p: p.repeat(2, axis=1).repeat(2, axis=2)
+    if frame_format == 'nv12':
+        uv = a[:, h:].reshape(n, h // 2, w // 2, 2)
+        return a[:, :h], up(uv[..., 0]), up(uv[..., 1])
+    if frame_format in ('i420', 'yv12'):
+        planes = a[:, h:].reshape(n, 2, h // 2, w // 2)
+        first, second = up(planes[:, 0]), up(planes[:, 1])
+        return (a[:, :h], first, second) if frame_format == 'i420' else (a[:, :h], second, first)
+    if frame_format == 'p010':
+        hi = a[:, :, 1::2]                                    # the high byte of every little-endian sample
+        uv = hi[:, h:].reshape(n, h // 2, w // 2, 2)
+        return hi[:, :h], up(uv[..., 0]), up(uv[..., 1])
+    g = a.reshape(n, h, w // 2, 4)
+    y0, u, y1, v = (0, 1, 2, 3) if frame_format == 'yuyv' else (1, 0, 3, 2)
+    return g[..., [y0, y1]].reshape(n, h, w), g[..., u].repeat(2, axis=2), g[..., v].repeat(2, axis=2)
+
+
+def yuv_to_rgb(frames, frame_format: str, colorimetry: str = 'bt601') -> np.ndarray:
+    """uint8 frames ``[n, ...container]`` (or one frame) of ``'nv12'`` or a YUV_FORMATS name -> uint8 ``[n, h, w, 3]``: the
+    NumPy text of the device arithmetic (the int32 formula of ``nv12_to_rgb`` on the samples of ``yuv_planes``) -- to the bit
+    what the kernels of that format feed their bilinear taps."""
+    y_off, cy, crv, cgu, cgv, cbu = nv12_coefficients(colorimetry)
+    if frame_format != 'nv12' and frame_format not in YUV_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS[1:]}, got {frame_format!r}')
+    a = yuv_frame_bytes_view(frames, frame_format)
+    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError(f'{frame_format} frames must be uint8 [n, rows, bytes] or [rows, bytes], got {a.dtype} {a.shape}')
+    y, u, v = yuv_planes(a, frame_format)
+    c = cy * (y.astype(np.int32) - y_off) + 8192
+    d, e = u.astype(np.int32) - 128, v.astype(np.int32) - 128
+    rgb = np.stack([(c + crv * e) >> 14, (c + cgu * d + cgv * e) >> 14, (c + cbu * d) >> 14], axis=-1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+def rgb_to_yuv(frames, frame_format: str, colorimetry: str = 'bt601') -> np.ndarray:
+    """uint8 ``[n, h, w, 3]`` (or one ``[h, w, 3]``) -> uint8 frames ``[n, ...container]`` of ``'nv12'`` or a YUV_FORMATS
+    name: the float64 forward matrix of ``rgb_to_nv12``, chroma the mean of the pixels that share it (a 2x2 block, or a pair
+    of one row for the 4:2:2 formats), rounded half up and clipped; ``'p010'`` holds the 8-bit value in the high byte and 0
+    in the low one.  For building inputs; it is no codec's exact output."""
+    nv12_coefficients(colorimetry)
+    if frame_format != 'nv12' and frame_format not in YUV_FORMATS:
+        raise ValueError(f'frame_format must be one of {FRAME_FORMATS[1:]}, got {frame_format!r}')
+    a = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError(f'RGB frames must be uint8 [n, h, w, 3] or [h, w, 3], got {a.dtype} {a.shape}')
+    a = a.reshape((-1,) + a.shape[-3:])
+    n, h, w = a.shape[:3]
+    shape = frame_container(h, w, frame_format)
+    if _is_420(frame_format):
+        nv = rgb_to_nv12(a, colorimetry)
+        if frame_format == 'nv12':
+            return nv
+        uv = nv[:, h:].reshape(n, h // 2, w // 2, 2)
+        out = np.zeros((n,) + shape, dtype=np.uint8)
+        if frame_format == 'p010':
+            out[:, :, 1::2] = nv
+            return out
+        out[:, :h] = nv[:, :h]
+        u, v = (0, 1) if frame_format == 'i420' else (1, 0)
+        out[:, h:].reshape(n, 2, h // 2, w // 2)[:, u] = uv[..., 0]
+        out[:, h:].reshape(n, 2, h // 2, w // 2)[:, v] = uv[..., 1]
+        return out
+    kr, kb, limited = _NV12_MATRIX[colorimetry]
+    r, g, b = (a[..., i].astype(np.float64) for i in range(3))
+    y = kr * r + (1.0 - kr - kb) * g + kb * b
+    cb, cr = (b - y) / (2.0 * (1.0 - kb)), (r - y) / (2.0 * (1.0 - kr))
+    ys, yo, cs = (219.0 / 255.0, 16.0, 224.0 / 255.0) if limited else (1.0, 0.0, 1.0)
+    quant = lambda p: np.clip(np.floor(p + 0.5), 0, 255).astype(np.uint8)
+    pair = lambda p: p.reshape(n, h, w // 2, 2).mean(axis=3)
+    out = np.empty((n, h, w // 2, 4), dtype=np.uint8)
+    y0, u, y1, v = (0, 1, 2, 3) if frame_format == 'yuyv' else (1, 0, 3, 2)
+    yq = quant(y * ys + yo).reshape(n, h, w // 2, 2)
+    out[..., y0], out[..., y1] = yq[..., 0], yq[..., 1]
+    out[..., u], out[..., v] = quant(pair(cb) * cs + 128.0), quant(pair(cr) * cs + 128.0)
+    return out.reshape((n,) + shape)
+
+
+def black_frame(h: int, w: int, frame_format: str, colorimetry: str = 'bt601') -> np.ndarray:
+    """One uint8 frame of a format that converts to RGB (0, 0, 0) everywhere: Y = the colorimetry's offset, chroma 128
+    (``'p010'``: those values in the high byte, 0 in the low one); zero bytes for ``'rgb'``.  The staged pad frame: a YUV
+    frame of zero bytes is green (``nv12_black``)."""
+    shape = frame_container(h, w, frame_format)
+    if frame_format == 'rgb':
+        return np.zeros(shape, dtype=np.uint8)
+    y_off = nv12_coefficients(colorimetry)[0]
+    if frame_format == 'nv12':
+        return nv12_black(h, w, colorimetry)
+    out = np.full(shape, 128, dtype=np.uint8)
+    if frame_format in ('i420', 'yv12'):
+        out[:h] = y_off
+    elif frame_format == 'p010':
+        out[:, 0::2] = 0
+        out[:h, 1::2] = y_off
+    else:
+        out[:, (0 if frame_format == 'yuyv' else 1)::2] = y_off
+    return out
 
 
 def nv12_to_rgb(frames, colorimetry: str = 'bt601') -> np.ndarray:
@@ -283,8 +447,9 @@ def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int
 
     The kernel is total in this table and turns an invalid row into zero frames; a caller who builds the table here gets an
     error instead: ValueError for a side outside 1 .. 65535, an offset that is negative or no multiple of 16, a centre crop
-    larger than the resized frame, a box that is not four integers of the int32 range.  ``frame_format='nv12'``: the
-    windows hold NV12 frames, ``shapes`` are their luma sizes ``(h, w)``, and an odd side is a ValueError too."""
+    larger than the resized frame, a box that is not four integers of the int32 range.  ``frame_format='nv12'`` or a
+    YUV_FORMATS name: the windows hold frames of that format, ``shapes`` are their luma sizes ``(h, w)``, and a side of the
+    wrong parity (an odd w; an odd h except for ``'yuyv'`` / ``'uyvy'``) is a ValueError too."""
     if frame_format not in FRAME_FORMATS:
         raise ValueError(f'frame_format must be one of {FRAME_FORMATS}, got {frame_format!r}')
     shapes, offsets = list(shapes), list(offsets)
@@ -300,6 +465,9 @@ def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int
             raise ValueError(f'window {c}: frame sides must lie in 1 .. 65535, got {h} x {w}')
         if frame_format == 'nv12' and (len(shape) != 2 or h % 2 or w % 2):
             raise ValueError(f'window {c}: an NV12 window is (h, w) with both sides even, got {shape}')
+        if frame_format in YUV_FORMATS and (len(shape) != 2 or w % 2 or (_is_420(frame_format) and h % 2)):
+            raise ValueError(f'window {c}: a {frame_format} window is (h, w) with an even w' +
+                             (' and an even h' if _is_420(frame_format) else '') + f', got {shape}')
         if not isinstance(off, (int, np.integer)) or off < 0 or off % 16 != 0 or off >= 1 << 63:
             raise ValueError(f'window {c}: offset must be a non-negative multiple of 16 bytes, got {off!r}')
         off = int(off)

@@ -283,6 +283,27 @@ int tsm_set_non_local(tsm_engine *e, int32_t on);
  * tsm_set_non_local(e, 1), whichever of the two calls comes second (the non-local wrapper assumes one segment count). */
 int tsm_set_temporal_pool(tsm_engine *e, int32_t on);
 
+/* ConvNeXt image model -- create_image_model(base_model='convnext_base'): the engine builds a ConvNeXt topology (timm 0.5.4
+ * convnext_base: widths 128 / 256 / 512 / 1024, depths[s] blocks in stage s, (3, 3, 27, 3) for the model itself) in place
+ * of the ResNet one.  Input [n, 3, H, W], one frame per clip.  Stem: Conv2d(3, 128, k 4, s 4) + LayerNorm; stages 1 .. 3 start
+ * with LayerNorm + Conv2d(C / 2, C, k 2, s 2) (floor mode: a last odd row / column is dropped); a block is
+ * x + gamma * fc2(GELU(fc1(LN(dwconv7x7(x))))) with an exact (erf) GELU and no activation behind the add; the head is the mean
+ * over the pixels, LayerNorm, fc.  Every LayerNorm is over the channels of one pixel, biased variance, eps 1e-6, affine.
+ * Launches: the depthwise 7x7 and its LayerNorm are one kernel (dwconv7_ln_kernel); the stem, the downsamples, fc1 and fc2 run
+ * on conv_igemm as 1x1 convs (the layer scale gamma folded into fc2, the residual in its epilogue); GELU is an in-place pass.
+ * State-dict keys, timm's: "stem.0.{weight [128, 3, 4, 4], bias}", "stem.1.{weight, bias}", "stages.S.downsample.0.{weight,
+ * bias}" (LayerNorm) and "stages.S.downsample.1.{weight [C, C / 2, 2, 2], bias}" for S = 1 .. 3, "stages.S.blocks.B.conv_dw.{weight
+ * [C, 1, 7, 7], bias}", "....norm.{weight, bias}", "....mlp.fc1.{weight [4 C, C], bias}", "....mlp.fc2.{weight [C, 4 C], bias}",
+ * "....gamma [C]", "head.norm.{weight, bias}", "head.fc.{weight [num_class, 1024], bias}".
+ * tsm_forward writes [n_clips, num_class]; tsm_forward_features [n_clips, 1024], the head LayerNorm's output (normalize: each
+ * row over its Euclidean norm).  Taps: "stem", "stages.S.downsample", "stages.S.blocks.B" (the block's output), "....dwln" (the
+ * normalised depthwise output), "....fc1" (behind the GELU), "head.pool", "head.norm".
+ * Legal between tsm_create and the first tsm_set_tensor, later TSM_ERR_INVALID_ARG (as is depths == NULL).
+ * TSM_ERR_UNSUPPORTED: num_segments != 1, is_shift != 0, a dtype other than TSM_DTYPE_F32, a depth outside 1 .. 64, and after
+ * tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_shift_place, tsm_set_non_local(e, 1) or tsm_set_temporal_pool(e, 1);
+ * those five are TSM_ERR_UNSUPPORTED in turn on an engine that is already a ConvNeXt one. */
+int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;

@@ -13,6 +13,7 @@
 //   tsm_ops.hip        pack / convert / preprocess / gather_clips / preprocess_clips / preprocess_indexed / maxpool / shift / head / pool_feat / scores_to_states / top1_tally, device_info()
 //   tsm_similarity.hip cosine_dist_kernel: the cosine-distance matrix of unit rows on the exact-fp32 MFMA
 //   tsm_nonlocal.hip   maxpool2x2_kernel, nonlocal_attn_kernel: the non-local block's pool and its fused online-softmax attention (fp32)
+//   tsm_convnext.hip   dwconv7_ln_kernel, ln_kernel, stem_pack4_kernel, gelu_kernel: the non-GEMM part of a ConvNeXt-Base image model (fp32)
 #pragma once
 #include "tsm_kernels.h"
 

@@ -1,5 +1,6 @@
 // Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet clip forward on MI355X (ResNet-50 by default; ResNet-18 / 34
-// through tsm_set_backbone; the shift in front of conv1 by default, in front of the whole block through tsm_set_shift_place).
+// through tsm_set_backbone; the shift in front of conv1 by default, in front of the whole block through tsm_set_shift_place),
+// and for the ConvNeXt-Base image model through tsm_set_convnext (build_convnext_topology, run_convnext, finalize_convnext).
 //
 // Owns: packed weights (BatchNorm folded, K-major), an NHWC fp32 activation workspace sized for
 // max_clips, one HIP stream, two timing events.  The forward is a fixed schedule of kernel launches
@@ -71,6 +72,10 @@ struct ConvLayer : LayerGeom {   // cp, kp, kseg: tsm_host_util.h, layer_geometr
   // 2 = W ("<nlp>.W.0.weight", BatchNorm "<nlp>.W.1"); nlp = "base_model.layerL.B.nl"
   int nl = 0;
   std::string nlp;
+  // a ConvNeXt engine's GEMMs, all with a conv bias and no BatchNorm (wkey = "<name>.weight", bias "<name>.bias"): 1 = the stem
+  // [cout, 3, 4, 4], 2 = a downsample [cout, cout / 2, 2, 2], 3 = fc1 [cout, cin], 4 = fc2 [cout, cin] with the block's gamma folded in
+  int cnx = 0;
+  std::string gkey;   // (4) the block's "gamma"
   float *d_w = nullptr, *d_b = nullptr;
 };
 
@@ -97,6 +102,25 @@ struct Block {
   // whether the temporal pool runs behind this block (the last one of layer1)
   int T = 0;
   bool tpool_after = false;
+};
+
+// A ConvNeXt engine (tsm_set_convnext): one LayerNorm's affine pair, one block, one stage.  Every GEMM is a ConvLayer of
+// e->convs (added through add_conv, in launch order: the stem, then per stage [its downsample,] fc1 and fc2 of every block).
+struct CnxNorm {
+  std::string key;   // "<key>.weight" / "<key>.bias", [c]
+  int c = 0;
+  float *d_w = nullptr, *d_b = nullptr;
+};
+struct CnxBlock {
+  int c = 0, fc1 = -1, fc2 = -1;   // width; indices into convs
+  std::string name;                // "stages.S.blocks.B"
+  CnxNorm norm;
+  float *d_dw = nullptr, *d_dwb = nullptr;   // conv_dw [49][c] (cnx_pack_dw) and its bias
+};
+struct CnxStage {
+  int down = -1;   // the 2x2 stride-2 conv as a 1x1 over the space-to-depth rows (-1: stage 0)
+  CnxNorm norm;    // the LayerNorm in front of it
+  int first = 0, count = 0;   // its blocks in e->cnx_blocks
 };
 
 // A device buffer between two poisoned bands (tsm_host_util.h: guard_layout).  tsm_conv_op's temporaries always are; the
@@ -149,6 +173,12 @@ struct tsm_engine {
   int place = 0;              // tsm_set_shift_place: 0 blockres, 1 block
   int temporal_pool = 0;      // tsm_set_temporal_pool: max-pool over time in front of layer2; layers 2-4 and the head see T / 2 frames per clip
   int non_local = 0;          // tsm_set_non_local: non-local blocks around layer2.{0,2} and layer3.{0,2,4} (fp32 Bottleneck engines)
+  int convnext = 0;           // tsm_set_convnext: a ConvNeXt-Base topology (cnx_*) in place of the ResNet one
+  int backbone_set = 0;       // tsm_set_backbone / tsm_set_bottleneck_width / tsm_set_shift_place has been called
+  int cnx_depths[4] = {0, 0, 0, 0};
+  std::vector<CnxBlock> cnx_blocks;
+  CnxStage cnx_stages[4];
+  CnxNorm cnx_stem_norm, cnx_head_norm;
   int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
   int features = 0;           // for the duration of a tsm_forward_features call: 1 = the forward ends in the pooled rows, 2 = in the unit rows
@@ -232,7 +262,47 @@ int add_conv(tsm_engine *e, const std::string &wkey, const std::string &bnp, int
   return (int)e->convs.size() - 1;
 }
 
+// The ConvNeXt topology (timm 0.5.4 key spelling).  Every GEMM goes through add_conv as a 1x1 conv: the stem over its packed 4x4
+// patches (K = 64), a downsample over the space-to-depth rows (K = 4 * C / 2), fc1 (C -> 4 C) and fc2 (4 C -> C, + the block
+// input).  Layers without a residual are segmented where their K is long enough, as every such layer of the ResNets is.
+void build_convnext_topology(tsm_engine *e) {
+  e->convs.clear();
+  e->blocks.clear();
+  e->cnx_blocks.clear();
+  auto norm = [](const std::string &key, int c) { CnxNorm n; n.key = key; n.c = c; return n; };
+  e->convs[add_conv(e, "stem.0.weight", "", kCnxStemK, kCnxWidths[0], 1, 1, true)].cnx = 1;
+  e->cnx_stem_norm = norm("stem.1", kCnxWidths[0]);
+  for (int s = 0; s < kCnxStages; ++s) {
+    const int c = kCnxWidths[s];
+    const std::string sp = "stages." + std::to_string(s);
+    CnxStage &st = e->cnx_stages[s];
+    st = CnxStage();
+    if (s > 0) {
+      st.norm = norm(sp + ".downsample.0", c / 2);
+      st.down = add_conv(e, sp + ".downsample.1.weight", "", 4 * (c / 2), c, 1, 1, true);
+      e->convs[st.down].cnx = 2;
+    }
+    st.first = (int)e->cnx_blocks.size();
+    st.count = e->cnx_depths[s];
+    for (int b = 0; b < st.count; ++b) {
+      CnxBlock blk;
+      blk.c = c;
+      blk.name = sp + ".blocks." + std::to_string(b);
+      blk.norm = norm(blk.name + ".norm", c);
+      blk.fc1 = add_conv(e, blk.name + ".mlp.fc1.weight", "", c, 4 * c, 1, 1, true);
+      blk.fc2 = add_conv(e, blk.name + ".mlp.fc2.weight", "", 4 * c, c, 1, 1, false);
+      e->convs[blk.fc1].cnx = 3;
+      e->convs[blk.fc2].cnx = 4;
+      e->convs[blk.fc2].gkey = blk.name + ".gamma";
+      e->cnx_blocks.push_back(blk);
+    }
+  }
+  e->cnx_head_norm = norm("head.norm", kCnxWidths[kCnxStages - 1]);
+  e->feat = kCnxWidths[kCnxStages - 1];
+}
+
 void build_topology(tsm_engine *e) {
+  if (e->convnext) return build_convnext_topology(e);
   e->convs.clear();
   e->blocks.clear();
   add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false);
@@ -323,7 +393,22 @@ const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
   return nullptr;
 }
 
+// A ConvNeXt engine's tensors: timm's keys as they are ("head.fc.*" is the classifier).
+bool known_convnext_name(const tsm_engine *e, const std::string &name) {
+  if (name == "head.fc.weight" || name == "head.fc.bias") return true;
+  auto is_norm = [&](const CnxNorm &n) { return !n.key.empty() && (name == n.key + ".weight" || name == n.key + ".bias"); };
+  if (is_norm(e->cnx_stem_norm) || is_norm(e->cnx_head_norm)) return true;
+  for (const CnxStage &st : e->cnx_stages)
+    if (is_norm(st.norm)) return true;
+  for (const CnxBlock &b : e->cnx_blocks)
+    if (is_norm(b.norm) || name == b.name + ".conv_dw.weight" || name == b.name + ".conv_dw.bias") return true;
+  for (const ConvLayer &c : e->convs)
+    if (name == c.wkey || name == c.wkey.substr(0, c.wkey.size() - 6) + "bias" || (!c.gkey.empty() && name == c.gkey)) return true;
+  return false;
+}
+
 bool known_name(const tsm_engine *e, const std::string &name) {
+  if (e->convnext) return known_convnext_name(e, name);
   if (name == "fc.weight" || name == "fc.bias") return true;
   static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
   auto is = [&](const std::string &key) {
@@ -979,6 +1064,73 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   return TSM_OK;
 }
 
+// The forward of a ConvNeXt engine (tsm_set_convnext) on n frames, the block schedule beside the ResNet one.  Launches and
+// timing slots, in order:
+//   pack_input (skipped for a packed input), stem.pack, stem.conv, stem.norm;
+//   per stage s > 0: stages.s.downsample.norm (LayerNorm + space-to-depth), stages.s.downsample (the 1x1 GEMM over it);
+//   per block: .dwln (depthwise 7x7 + LayerNorm), .fc1, .gelu, .fc2 (+ the block input, gamma folded in);
+//   head.pool, head.norm, head (tsm_forward_features: the pool kernel once more over the normalised rows, which copies them or
+//   divides them by their norm).
+// Buffers: the block input in cur, its output in out; t1 holds the normalised tensor a GEMM reads (and the stem's patches),
+// t2 the stem's GEMM output, fc1's output (GELU in place) and the pooled rows.
+int run_convnext(tsm_engine *e, Forward &f, const float *d_clips, int layout, int n, float *d_logits, hipStream_t s) {
+  const tsm_config &cfg = e->cfg;
+  const int prec = e->prec;
+  const float *in4 = e->d_in4;
+  if (layout >= TSM_LAYOUT_NTHWC4) {
+    in4 = d_clips;
+    skip_slots(e, 1);
+  } else {
+    TSM_LAUNCH(e, s, tsm::launch_pack_input(d_clips, e->d_in4, n, cfg.height, cfg.width, layout == TSM_LAYOUT_NTCHW ? 1 : 0, prec, s));
+  }
+  if (f.want("input")) return f.hit(in4, n, cfg.height, cfg.width, 4);
+  float *cur = e->buf[0], *out = e->buf[1], *t1 = f.t1, *t2 = f.t2;
+  int h = cnx_stem_size(cfg.height), w = cnx_stem_size(cfg.width);
+  TSM_LAUNCH(e, s, tsm::launch_stem_pack4(in4, t1, n, cfg.height, cfg.width, s));
+  int rc = f.conv(0, make_params(e->convs[0], t1, nullptr, t2, n, h, w, false, 0, 1, prec), 1, false);
+  if (rc) return rc;
+  TSM_LAUNCH(e, s, tsm::launch_layer_norm(t2, e->cnx_stem_norm.d_w, e->cnx_stem_norm.d_b, cur, (int64_t)n * h * w, kCnxWidths[0], s));
+  if (f.want("stem")) return f.hit(cur, n, h, w, kCnxWidths[0]);
+  for (int si = 0; si < kCnxStages; ++si) {
+    const CnxStage &st = e->cnx_stages[si];
+    const int c = kCnxWidths[si];
+    if (st.down >= 0) {
+      TSM_LAUNCH(e, s, tsm::launch_layer_norm_s2d(cur, st.norm.d_w, st.norm.d_b, t1, n, h, w, c / 2, s));
+      h = cnx_down_size(h);
+      w = cnx_down_size(w);
+      rc = f.conv(st.down, make_params(e->convs[st.down], t1, nullptr, out, n, h, w, false, 0, 1, prec), 1, false);
+      if (rc) return rc;
+      std::swap(cur, out);
+      if (f.want("stages." + std::to_string(si) + ".downsample")) return f.hit(cur, n, h, w, c);
+    }
+    for (int b = st.first; b < st.first + st.count; ++b) {
+      const CnxBlock &blk = e->cnx_blocks[b];
+      TSM_LAUNCH(e, s, tsm::launch_dwconv7_ln(cur, blk.d_dw, blk.d_dwb, blk.norm.d_w, blk.norm.d_b, t1, n, h, w, c, s));
+      if (f.want(blk.name + ".dwln")) return f.hit(t1, n, h, w, c);
+      rc = f.conv(blk.fc1, make_params(e->convs[blk.fc1], t1, nullptr, t2, n, h, w, false, 0, 1, prec), 1, false);
+      if (rc) return rc;
+      TSM_LAUNCH(e, s, tsm::launch_gelu(t2, (int64_t)n * h * w * c, s));   // (4 c channels: c quads per pixel)
+      if (f.want(blk.name + ".fc1")) return f.hit(t2, n, h, w, 4 * c);
+      rc = f.conv(blk.fc2, make_params(e->convs[blk.fc2], t2, cur, out, n, h, w, false, 0, 1, prec), 1, false);
+      if (rc) return rc;
+      std::swap(cur, out);
+      if (f.want(blk.name)) return f.hit(cur, n, h, w, c);
+    }
+  }
+  TSM_LAUNCH(e, s, tsm::launch_pool_features(cur, t2, nullptr, n, h * w, e->feat, prec, s));
+  if (f.want("head.pool")) return f.hit(t2, n, 1, 1, e->feat);
+  TSM_LAUNCH(e, s, tsm::launch_layer_norm(t2, e->cnx_head_norm.d_w, e->cnx_head_norm.d_b, t1, n, e->feat, s));
+  if (f.want("head.norm")) return f.hit(t1, n, 1, 1, e->feat);
+  if (f.stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + f.stage);
+  if (e->features) {   // tsm_forward_features: the normalised rows, or (normalize) each over its Euclidean norm
+    TSM_LAUNCH(e, s, tsm::launch_pool_features(t1, e->features == 1 ? d_logits : nullptr, e->features == 2 ? d_logits : nullptr, n, 1,
+                                               e->feat, prec, s));
+    return TSM_OK;
+  }
+  TSM_LAUNCH(e, s, tsm::launch_head(t1, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n, 1, 1, e->feat, cfg.num_class, prec, s));
+  return TSM_OK;
+}
+
 // Enqueue the forward on `s`.  If `stage` is non-null, stop right after that stage and report it.
 int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, float *d_logits,
                 hipStream_t s, const char *stage, Tap *tap) {
@@ -997,6 +1149,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     }
     f.tiles = &it->second;
   }
+  if (e->convnext) return run_convnext(e, f, d_clips, layout, n, d_logits, s);
 
   const int prec = e->prec;
   const float *in4 = e->d_in4;
@@ -1118,6 +1271,10 @@ void retag_tune_sig(tsm_engine *e) {
   if (e->depth != 50) e->tune_sig += " r" + std::to_string(e->depth);
   if (e->width != 64) e->tune_sig += " w" + std::to_string(e->width);
   if (e->place == 1) e->tune_sig += " block";
+  if (e->convnext) {
+    e->tune_sig += " cnx";
+    for (int s = 0; s < kCnxStages; ++s) e->tune_sig += (s ? "-" : "") + std::to_string(e->cnx_depths[s]);
+  }
   if (e->non_local) e->tune_sig += " nl";
   if (e->temporal_pool) e->tune_sig += " tp";
 }
@@ -1156,6 +1313,87 @@ int stage_input(tsm_engine *e, const void *clips, int memkind, int n_clips, void
 int check_before_weights(tsm_engine *e, const char *setter) {
   if (!e) return TSM_ERR_INVALID_ARG;
   if (e->weights_started || e->finalized) return fail(e, TSM_ERR_INVALID_ARG, std::string(setter) + " must come before the first tsm_set_tensor");
+  return TSM_OK;
+}
+
+// The ResNet setters on a ConvNeXt engine (tsm_set_convnext came first): refused, the topology has none of their parts.
+int refuse_on_convnext(tsm_engine *e, const char *setter) {
+  if (!e->convnext) return TSM_OK;
+  return fail(e, TSM_ERR_UNSUPPORTED, std::string(setter) + ": a ConvNeXt engine (tsm_set_convnext) has no such part");
+}
+
+// tsm_finalize of a ConvNeXt engine: every tensor checked, packed (tsm_host_util.h: cnx_pack_*, cnx_fold_gamma) and uploaded, then
+// the workspace -- the five rotating buffers, each the largest activation of the schedule (fc1's output in stage 0).
+int finalize_convnext(tsm_engine *e) {
+  const tsm_config &cfg = e->cfg;
+  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };
+  auto want = [e](const std::string &key, const std::vector<int64_t> &shape, const HostTensor **t) {
+    *t = find_tensor(e, key);
+    if (!*t) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + key);
+    if ((*t)->shape != shape) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + key);
+    return (int)TSM_OK;
+  };
+  auto upload_norm = [&](CnxNorm &n) {
+    const HostTensor *w, *b;
+    if (int rc = want(n.key + ".weight", {n.c}, &w)) return rc;
+    if (int rc = want(n.key + ".bias", {n.c}, &b)) return rc;
+    if (int rc = upload(e, alloc, &n.d_w, "ln_w", w->data)) return rc;
+    return upload(e, alloc, &n.d_b, "ln_b", b->data);
+  };
+  for (ConvLayer &c : e->convs) {
+    const std::string base = c.wkey.substr(0, c.wkey.size() - 7);   // without ".weight"
+    const HostTensor *w, *b, *g = nullptr;
+    const std::vector<int64_t> shape = c.cnx == 1   ? std::vector<int64_t>{c.cout, 3, 4, 4}
+                                       : c.cnx == 2 ? std::vector<int64_t>{c.cout, c.cin / 4, 2, 2}
+                                                    : std::vector<int64_t>{c.cout, c.cin};
+    if (int rc = want(c.wkey, shape, &w)) return rc;
+    if (int rc = want(base + ".bias", {c.cout}, &b)) return rc;
+    if (c.cnx == 4)
+      if (int rc = want(c.gkey, {c.cout}, &g)) return rc;
+    std::vector<float> wp, bias = b->data;
+    if (c.cnx == 1) cnx_pack_stem(w->data.data(), c.cout, &wp);
+    else if (c.cnx == 2) cnx_pack_down(w->data.data(), c.cout, c.cin / 4, &wp);
+    else if (c.cnx == 4) cnx_fold_gamma(w->data.data(), b->data.data(), g->data.data(), c.cout, c.cin, &wp, &bias);
+    else wp = w->data;
+    if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
+  }
+  if (int rc = upload_norm(e->cnx_stem_norm)) return rc;
+  if (int rc = upload_norm(e->cnx_head_norm)) return rc;
+  for (CnxStage &st : e->cnx_stages)
+    if (st.down >= 0)
+      if (int rc = upload_norm(st.norm)) return rc;
+  for (CnxBlock &blk : e->cnx_blocks) {
+    const HostTensor *w, *b;
+    if (int rc = want(blk.name + ".conv_dw.weight", {blk.c, 1, 7, 7}, &w)) return rc;
+    if (int rc = want(blk.name + ".conv_dw.bias", {blk.c}, &b)) return rc;
+    std::vector<float> wp;
+    cnx_pack_dw(w->data.data(), blk.c, &wp);
+    if (int rc = upload(e, alloc, &blk.d_dw, "dw_w", wp)) return rc;
+    if (int rc = upload(e, alloc, &blk.d_dwb, "dw_b", b->data)) return rc;
+    if (int rc = upload_norm(blk.norm)) return rc;
+  }
+  const HostTensor *fw, *fb;
+  if (int rc = want("head.fc.weight", {cfg.num_class, e->feat}, &fw)) return rc;
+  if (int rc = want("head.fc.bias", {cfg.num_class}, &fb)) return rc;
+  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
+  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
+
+  const size_t frames = (size_t)cfg.max_clips;   // (num_segments is 1)
+  const int64_t per_frame = cnx_frame_elems(cfg.height, cfg.width), total = cnx_workspace_elems((int64_t)frames, cfg.height, cfg.width);
+  if (total < 0) return fail(e, TSM_ERR_CAPACITY, "max_clips * (H / 4) * (W / 4) * 512 activations must stay below 2^29 (32-bit byte offsets)");
+  e->buf_elems = (size_t)total;
+  for (int i = 0; i < 5; ++i) {
+    static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
+    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], (size_t)per_frame))) return rc;
+  }
+  if ((rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width))) return rc;
+  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1)))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
+  if ((rc = dev_alloc(e, &e->d_logits, frames * cfg.num_class, "d_logits", (size_t)cfg.num_class))) return rc;
+  e->partial_elems = (size_t)16 << 20;   // split-K scratch, as every fp32 engine has
+  if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", (size_t)per_frame))) return rc;
+  e->tensors.clear();
+  e->finalized = true;
   return TSM_OK;
 }
 
@@ -1357,6 +1595,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
 
 int tsm_set_backbone(tsm_engine *e, int32_t depth) {
   if (int rc = check_before_weights(e, "tsm_set_backbone")) return rc;
+  if (int rc = refuse_on_convnext(e, "tsm_set_backbone")) return rc;
   if (!find_backbone(depth)) return fail(e, TSM_ERR_UNSUPPORTED, "depth must be 18, 34 or 50");
   if (find_backbone(depth)->basic && e->width != 64)
     return fail(e, TSM_ERR_UNSUPPORTED, "a BasicBlock backbone (depth 18 / 34) has no bottleneck width: the engine's is " +
@@ -1364,6 +1603,7 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
   if (find_backbone(depth)->basic && e->non_local)
     return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks need a Bottleneck backbone (depth 50)");
   e->depth = depth;
+  e->backbone_set = 1;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1371,12 +1611,14 @@ int tsm_set_backbone(tsm_engine *e, int32_t depth) {
 
 int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
   if (int rc = check_before_weights(e, "tsm_set_bottleneck_width")) return rc;
+  if (int rc = refuse_on_convnext(e, "tsm_set_bottleneck_width")) return rc;
   if (width_per_group != 64 && width_per_group != 128)
     return fail(e, TSM_ERR_UNSUPPORTED, "width_per_group must be 64 or 128 (wide_resnet50_2)");
   if (width_per_group != 64 && find_backbone(e->depth)->basic)
     return fail(e, TSM_ERR_UNSUPPORTED, "width_per_group 128 needs a Bottleneck backbone (depth 50): torchvision's BasicBlock "
                                         "supports 64 only");
   e->width = width_per_group;
+  e->backbone_set = 1;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1384,8 +1626,10 @@ int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
 
 int tsm_set_shift_place(tsm_engine *e, int32_t place) {
   if (int rc = check_before_weights(e, "tsm_set_shift_place")) return rc;
+  if (int rc = refuse_on_convnext(e, "tsm_set_shift_place")) return rc;
   if (place != 0 && place != 1) return fail(e, TSM_ERR_UNSUPPORTED, "place must be 0 (blockres) or 1 (block)");
   e->place = place;
+  e->backbone_set = 1;
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1393,6 +1637,7 @@ int tsm_set_shift_place(tsm_engine *e, int32_t place) {
 
 int tsm_set_non_local(tsm_engine *e, int32_t on) {
   if (int rc = check_before_weights(e, "tsm_set_non_local")) return rc;
+  if (int rc = refuse_on_convnext(e, "tsm_set_non_local")) return rc;
   if (on != 0 && on != 1) return fail(e, TSM_ERR_UNSUPPORTED, "non_local must be 0 or 1");
   if (on && e->prec != tsm::kPrecF32)
     return fail(e, TSM_ERR_UNSUPPORTED, "non-local blocks run in TSM_DTYPE_F32 only (the bf16 formats' fused forms do not know the block)");
@@ -1407,10 +1652,23 @@ int tsm_set_non_local(tsm_engine *e, int32_t on) {
 
 int tsm_set_temporal_pool(tsm_engine *e, int32_t on) {
   if (int rc = check_before_weights(e, "tsm_set_temporal_pool")) return rc;
+  if (int rc = refuse_on_convnext(e, "tsm_set_temporal_pool")) return rc;
   if (on != 0 && on != 1) return fail(e, TSM_ERR_UNSUPPORTED, "temporal_pool must be 0 or 1");
   if (on)
     if (const char *why = temporal_pool_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, e->non_local)) return fail(e, TSM_ERR_UNSUPPORTED, why);
   e->temporal_pool = on;
+  build_topology(e);
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]) {
+  if (int rc = check_before_weights(e, "tsm_set_convnext")) return rc;
+  if (!depths) return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_convnext: depths is NULL");
+  if (const char *why = cnx_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, e->backbone_set, e->non_local, e->temporal_pool, depths))
+    return fail(e, TSM_ERR_UNSUPPORTED, std::string("tsm_set_convnext: ") + why);
+  e->convnext = 1;
+  for (int s = 0; s < kCnxStages; ++s) e->cnx_depths[s] = depths[s];
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1462,6 +1720,7 @@ int tsm_finalize(tsm_engine *e) {
   if (!e) return TSM_ERR_INVALID_ARG;
   if (e->finalized) return TSM_OK;
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
+  if (e->convnext) return finalize_convnext(e);
   const tsm_config &cfg = e->cfg;
   auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };   // ("weights", no frame)
   std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
@@ -1761,6 +2020,7 @@ int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t c
   for (const Block &b : e->blocks)
     for (int ci : {b.down, b.conv1, b.conv2, b.conv3, b.nl_qkv, b.nl_w})
       if (ci >= 0) order.push_back(ci);
+  for (size_t ci = 1; e->convnext && ci < e->convs.size(); ++ci) order.push_back((int)ci);   // (a ConvNeXt engine's convs are in launch order)
   *n_out = (int32_t)order.size();
   if ((int)order.size() > cap) return fail(e, TSM_ERR_CAPACITY, "tiles_out too small");
   for (size_t i = 0; i < order.size(); ++i) tiles_out[i] = codes[order[i]];

@@ -1,7 +1,7 @@
 // Pure-host pieces of the engine: BatchNorm folding / weight packing, the bf16 storage-format converters, the
 // segment-length rule, a conv layer's packed geometry and the shapes of its launch's parameter block (conv_shape_params),
-// tsm_conv_op's argument rules (conv_op_check), the frame transforms' window and crop arithmetic, the NV12 conversion and the
-// TSM_TUNE_CACHE line parser.  (The launch rules themselves: tsm_conv_rules.h.)  No HIP types, so this header also compiles with plain
+// tsm_conv_op's argument rules (conv_op_check), the frame transforms' window and crop arithmetic, the NV12 conversion, the
+// ConvNeXt engine's sizes, K orders and weight packing (cnx_*) and the TSM_TUNE_CACHE line parser.  (The launch rules themselves: tsm_conv_rules.h.)  No HIP types, so this header also compiles with plain
 // g++: tests/host_sanitize.cpp builds it with -fsanitize=address,undefined, fuzzes the parser and drives conv_op_check over
 // its refusals, its accepted forms and the ends of int32 (CPU only; GPU ASAN is not available on this pool).
 #pragma once
@@ -630,6 +630,94 @@ inline bool clip_window_range(int64_t total_frames, int64_t first_clip, int n_cl
   r->first = lo / stride - first_frame;
   r->last = (r->tail ? total_frames - 1 : lo + span) / stride - first_frame;
   return r->first >= 0 && r->last < n_frames;
+}
+
+// ---- ConvNeXt-Base (tsm_set_convnext; timm 0.5.4 convnext_base): the host arithmetic of its schedule ----------------------------
+// Four stages of widths 128 / 256 / 512 / 1024; the stem is a 4x4 conv at stride 4, each later stage starts with a 2x2 conv at
+// stride 2, both without padding: floor mode, the last h % 4 (h % 2) rows and columns are not read.
+constexpr int kCnxStages = 4;
+constexpr int kCnxWidths[kCnxStages] = {128, 256, 512, 1024};
+constexpr int kCnxMaxDepth = 64;        // blocks per stage an engine accepts (convnext_base: 3, 3, 27, 3)
+constexpr float kCnxLnEps = 1e-6f;
+constexpr int kCnxStemK = 64;           // the stem as a 1x1 GEMM: K = (ky, kx, c4) = 4 x 4 x 4, channel 3 of every tap zero
+// dwconv7_ln_kernel<C>: one lane group per TS x TS output pixels, 4 x 4 but for the last stage's small maps, which take 2 x 2 (tsm_convnext.hip)
+TSM_HOST_DEVICE constexpr int cnx_dw_tile(int c) { return c >= 1024 ? 2 : 4; }
+inline int cnx_stem_size(int h) { return h > 0 ? h / 4 : 0; }
+inline int cnx_down_size(int h) { return h > 0 ? h / 2 : 0; }
+// Side of stage s's maps (s in 0 .. 3) for an input side h: ((h / 4) / 2) / 2 ...; 0 when nothing is left.
+inline int cnx_stage_size(int h, int s) {
+  int v = cnx_stem_size(h);
+  for (int i = 0; i < s; ++i) v = cnx_down_size(v);
+  return v;
+}
+// Position of input pixel (y, x)'s channel c in the K axis of the 2x2 space-to-depth row of output pixel (y / 2, x / 2): the
+// order (ky, kx, c) of every packed conv weight of the engine (fold_and_pack), ky = y & 1, kx = x & 1.
+TSM_HOST_DEVICE inline int64_t cnx_s2d_k(int y, int x, int c, int channels) { return (int64_t)((y & 1) * 2 + (x & 1)) * channels + c; }
+// The same for the stem's 4x4 taps over the packed input's 4 channels.
+TSM_HOST_DEVICE inline int cnx_stem_k(int ky, int kx, int c) { return (ky * 4 + kx) * 4 + c; }
+inline int cnx_tiles_along(int h, int ts) { return (int)(((int64_t)h + ts - 1) / ts); }   // tiles of side ts > 0 that cover a side of h > 0 pixels
+// ts x ts output tiles of dwconv7_ln_kernel over n frames of h x w pixels; -1 when the count leaves int32 (its grid) or a size is not positive.
+inline int64_t cnx_dw_tiles(int64_t n, int h, int w, int ts) {
+  if (n <= 0 || h <= 0 || w <= 0 || ts <= 0) return -1;
+  const int64_t ty = cnx_tiles_along(h, ts), tx = cnx_tiles_along(w, ts);
+  return mul_sat31(mul_sat31(n, ty), tx) >= kInt31 ? -1 : n * ty * tx;
+}
+// Floats of the largest activation of one frame: fc1's output in stage 0, 4 * 128 channels on the stem's map (every later
+// stage has a quarter of the pixels and twice the channels; the stem's packed patches are 64 wide).  0 when the frame is
+// smaller than one stem patch; saturates at 2^31.
+inline int64_t cnx_frame_elems(int h, int w) { return mul_sat31(mul_sat31(cnx_stem_size(h), cnx_stem_size(w)), 4 * kCnxWidths[0]); }
+// Floats of one workspace buffer for `frames` frames, or -1 when a conv of the schedule could not address it: the conv kernels
+// reach their operands through 32-bit byte offsets, so the largest tensor must stay below 2^31 bytes = 2^29 floats.
+inline int64_t cnx_workspace_elems(int64_t frames, int h, int w) {
+  const int64_t per = cnx_frame_elems(h, w);
+  if (frames <= 0 || per <= 0) return -1;
+  const int64_t total = mul_sat31(frames, per);
+  return total >= (kInt31 >> 2) ? -1 : total;
+}
+// Why tsm_set_convnext refuses an engine of this shape; nullptr when it can be built.
+inline const char *cnx_refusal(int prec, int is_shift, int num_segments, int backbone_set, int non_local, int temporal_pool,
+                               const int32_t *depths) {
+  if (!depths) return "depths is NULL";
+  if (num_segments != 1) return "a ConvNeXt engine is an image model: num_segments must be 1";
+  if (is_shift) return "a ConvNeXt engine has no temporal shift: is_shift must be 0";
+  if (prec != kPrecF32) return "a ConvNeXt engine runs in TSM_DTYPE_F32 only";
+  if (backbone_set) return "tsm_set_convnext excludes tsm_set_backbone / tsm_set_bottleneck_width / tsm_set_shift_place";
+  if (non_local) return "tsm_set_convnext excludes tsm_set_non_local";
+  if (temporal_pool) return "tsm_set_convnext excludes tsm_set_temporal_pool";
+  for (int s = 0; s < kCnxStages; ++s)
+    if (depths[s] < 1 || depths[s] > kCnxMaxDepth) return "every stage depth must be in 1 .. 64";
+  return nullptr;
+}
+// Weight packing.  The stem [128, 3, 4, 4] -> [128][64] in cnx_stem_k's order (channel 3 zero); a downsample conv
+// [cout, cin, 2, 2] -> [cout][4 cin] in cnx_s2d_k's order; a depthwise conv [c, 1, 7, 7] -> [49][c], tap-major (ky, kx), so
+// that the lanes of a pixel read one tap's weights as consecutive 16-byte quads.  All copies, bit for bit.
+inline void cnx_pack_stem(const float *w, int cout, std::vector<float> *wp) {
+  wp->assign((size_t)cout * kCnxStemK, 0.f);
+  for (int o = 0; o < cout; ++o)
+    for (int c = 0; c < 3; ++c)
+      for (int ky = 0; ky < 4; ++ky)
+        for (int kx = 0; kx < 4; ++kx) (*wp)[(size_t)o * kCnxStemK + cnx_stem_k(ky, kx, c)] = w[(((size_t)o * 3 + c) * 4 + ky) * 4 + kx];
+}
+inline void cnx_pack_down(const float *w, int cout, int cin, std::vector<float> *wp) {
+  wp->assign((size_t)cout * 4 * cin, 0.f);
+  for (int o = 0; o < cout; ++o)
+    for (int c = 0; c < cin; ++c)
+      for (int ky = 0; ky < 2; ++ky)
+        for (int kx = 0; kx < 2; ++kx) (*wp)[(size_t)o * 4 * cin + (size_t)cnx_s2d_k(ky, kx, c, cin)] = w[(((size_t)o * cin + c) * 2 + ky) * 2 + kx];
+}
+inline void cnx_pack_dw(const float *w, int c, std::vector<float> *wp) {
+  wp->assign((size_t)49 * c, 0.f);
+  for (int ch = 0; ch < c; ++ch)
+    for (int t = 0; t < 49; ++t) (*wp)[(size_t)t * c + ch] = w[(size_t)ch * 49 + t];
+}
+// out = x + gamma * (fc2(h) + b) = x + (gamma W) h + gamma b: the layer scale folds into fc2 [c][4 c] as a BatchNorm scale does.
+inline void cnx_fold_gamma(const float *w, const float *b, const float *gamma, int cout, int k, std::vector<float> *wp, std::vector<float> *bias) {
+  wp->resize((size_t)cout * k);
+  bias->resize(cout);
+  for (int o = 0; o < cout; ++o) {
+    for (int i = 0; i < k; ++i) (*wp)[(size_t)o * k + i] = w[(size_t)o * k + i] * gamma[o];
+    (*bias)[o] = b[o] * gamma[o];
+  }
 }
 
 // Tuned tile shapes are cached per power-of-two bucket of the clip count (ragged last batches of a video

@@ -184,6 +184,19 @@ hipError_t launch_maxpool2x2(const float *x, int64_t ld, int c0, int c, float *y
 hipError_t launch_nonlocal_attention(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *y,
                                      int64_t ldy, int n_clips, int nq, int nk, int d, hipStream_t s);
 
+// ConvNeXt-Base (tsm_convnext.hip), fp32 NHWC, c in {128, 256, 512, 1024}; anything else hipErrorInvalidValue, nothing launched.
+// dwconv7_ln: y = LayerNorm_c(depthwise 7x7 (padding 3) of x + b) on [n, h, w, c]; w [49][c] (tsm_host::cnx_pack_dw).
+hipError_t launch_dwconv7_ln(const float *x, const float *w, const float *b, const float *ln_w, const float *ln_b, float *y, int n,
+                             int h, int wi, int c, hipStream_t s);
+// LayerNorm over the c channels of every row of x [rows][c] (biased variance, eps 1e-6, affine)
+hipError_t launch_layer_norm(const float *x, const float *ln_w, const float *ln_b, float *y, int64_t rows, int c, hipStream_t s);
+// the same per pixel of x [n, h, w, c], written as 2x2 space-to-depth rows y [n, h / 2, w / 2, 4 c] (K order: tsm_host::cnx_s2d_k)
+hipError_t launch_layer_norm_s2d(const float *x, const float *ln_w, const float *ln_b, float *y, int n, int h, int w, int c, hipStream_t s);
+// the packed fp32 input [n, h, w, 4] -> the stem's 4x4 patches [n, h / 4, w / 4, 64] (K order: tsm_host::cnx_stem_k)
+hipError_t launch_stem_pack4(const float *x, float *y, int n, int h, int w, hipStream_t s);
+// exact GELU in place over n4 16-byte quads
+hipError_t launch_gelu(float *x, int64_t n4, hipStream_t s);
+
 // K9: per clip, (softmax,) first arg-max, class id if its score >= threshold else -1; top (nullable) = that score.
 hipError_t launch_scores_to_states(const float *logits, int n, int c, int softmax, float threshold, int *states, float *top,
                                    hipStream_t s);

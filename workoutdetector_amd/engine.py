@@ -1,4 +1,5 @@
-"""TsmEngine: Python host side of the MI355X TSM-ResNet clip-inference engine (R50; R18 / R34 / WRN-50-2 via ``base_model``).
+"""TsmEngine: Python host side of the MI355X TSM-ResNet clip-inference engine (R50; R18 / R34 / WRN-50-2 via ``base_model``;
+``base_model='convnext_base'``: the ConvNeXt-Base image model of ``create_image_model`` / ``create_feature_model``).
 
 Drop-in for the two duck types the reference's hot path is written against:
 
@@ -22,8 +23,9 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, DEPTHS, NL_BLOCKS, SHIFT_PLACES, WIDTHS, feature_width, is_mmaction_state_dict, make_state_dict,
-                      remap_checkpoint_keys, remap_mmaction_keys, remap_torchvision_keys)
+from .weights import (BACKBONES, CONVNEXT, CONVNEXT_DEPTHS, CONVNEXT_WIDTHS, DEPTHS, NL_BLOCKS, SHIFT_PLACES, WIDTHS, _convnext_depths,
+                      feature_width, is_convnext, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys, remap_mmaction_keys,
+                      remap_timm_keys, remap_torchvision_keys)
 
 CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
 
@@ -48,10 +50,18 @@ class TsmEngine:
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
                  base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg',
-                 non_local: bool = False, temporal_pool: bool = False):
-        if base_model not in DEPTHS:
+                 non_local: bool = False, temporal_pool: bool = False, convnext_depths: Optional[Sequence[int]] = None):
+        # base_model='convnext_base' (include/tsm_hip.h: tsm_set_convnext): an image model -- num_segments=1, is_shift=False,
+        # dtype='f32' -- of ``convnext_depths`` blocks per stage, (3, 3, 27, 3) unless given (tests build shallow engines).
+        convnext = is_convnext(base_model)
+        if convnext:      # every refusal before the library loads
+            convnext_depths = _check_convnext(convnext_depths, num_segments, is_shift, dtype, shift_place, non_local, temporal_pool)
+        elif convnext_depths is not None:
+            raise ValueError(f'convnext_depths= goes with base_model={CONVNEXT!r} only')
+        elif base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
-        _check_non_local(non_local, base_model, dtype)
+        if not convnext:
+            _check_non_local(non_local, base_model, dtype)
         _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
         if shift_place not in SHIFT_PLACES:
             raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
@@ -70,6 +80,7 @@ class TsmEngine:
         self.consensus_type = consensus_type
         self.non_local = bool(non_local)
         self.temporal_pool = bool(temporal_pool)
+        self.convnext_depths = convnext_depths      # None for a ResNet engine
         self.feature_dim = feature_width(base_model)      # row width of forward_features
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
@@ -77,7 +88,9 @@ class TsmEngine:
         cfg = _lib.TsmConfig(C.sizeof(_lib.TsmConfig), num_class, num_segments, height, width, shift_div,
                              1 if is_shift else 0, max_clips, device, _lib.DTYPES[dtype])
         _lib.check(self._lib.tsm_create(C.byref(cfg), C.byref(self._h)))
-        if DEPTHS[base_model] != 50:
+        if convnext:
+            _lib.check(self._lib.tsm_set_convnext(self._h, (C.c_int32 * 4)(*convnext_depths)), self._h)
+        elif DEPTHS[base_model] != 50:
             _lib.check(self._lib.tsm_set_backbone(self._h, DEPTHS[base_model]), self._h)
         if base_model in WIDTHS:
             _lib.check(self._lib.tsm_set_bottleneck_width(self._h, WIDTHS[base_model]), self._h)
@@ -291,6 +304,8 @@ class TsmEngine:
         h1, w1 = (self.height - 1) // 2 + 1, (self.width - 1) // 2 + 1          # stem conv output
         hp, wp = (h1 - 1) // 2 + 1, (w1 - 1) // 2 + 1                            # after the max-pool = layer1's size
         cap = n * max(h1 * w1 * 64, hp * wp * 256, self.height * self.width * 8)
+        if self.convnext_depths:                                                  # the largest tap: fc1's output in stage 0
+            cap = max(cap, n * (self.height // 4) * (self.width // 4) * 4 * CONVNEXT_WIDTHS[0])
         buf = np.empty(cap, dtype=np.float32)
         shape = (C.c_int64 * 4)()
         _lib.check(self._lib.tsm_forward_tap(self._h, clips.ctypes.data, _lib.MEM_HOST, _lib.LAYOUT_NTCHW,
@@ -303,6 +318,13 @@ class TsmEngine:
     def launch_names(self) -> List[str]:
         """Names of the kernel launches of one forward, in launch order (matches tsm_layer_times).  A non-local engine's
         wrapped blocks add four: the theta | phi | g conv, the pool, the attention and the W conv."""
+        if self.convnext_depths:      # (csrc/tsm_engine.hip, run_convnext)
+            names = ['pack_input', 'stem.pack', 'stem.conv', 'stem.norm']
+            for s, nb in enumerate(self.convnext_depths):
+                names += [f'stages.{s}.downsample.norm', f'stages.{s}.downsample'] if s else []
+                for b in range(nb):
+                    names += [f'stages.{s}.blocks.{b}' + part for part in ('.dwln', '.fc1', '.gelu', '.fc2')]
+            return names + ['head.pool', 'head.norm', 'head']
         names = ['pack_input', 'conv1', 'maxpool']
         blocks, kind = BACKBONES[self.base_model]
         for li, nb in enumerate(blocks, start=1):
@@ -337,9 +359,13 @@ class TsmEngine:
 
     def conv_tiles(self, n_clips: int) -> Dict[str, str]:
         """Tile shape the autotuner chose per conv launch for an ``n_clips`` forward."""
-        buf = (C.c_int32 * 64)()
+        buf = (C.c_int32 * 256)()
         n = C.c_int32()
-        _lib.check(self._lib.tsm_conv_tiles(self._h, n_clips, buf, 64, C.byref(n)), self._h)
+        _lib.check(self._lib.tsm_conv_tiles(self._h, n_clips, buf, 256, C.byref(n)), self._h)
+        if self.convnext_depths:
+            names = [k for k in self.launch_names() if k == 'stem.conv' or k.endswith(('.downsample', '.fc1', '.fc2'))]
+            assert n.value == len(names)
+            return {k: self.tile_name(buf[i]) for i, k in enumerate(names)}
         names = [k for k in self.launch_names() if k not in ('pack_input', 'maxpool', 'head', 'layer2.tpool') and not k.endswith(('.nl.pool', '.nl.attn'))]
         assert n.value == len(names)
         return {k: self.tile_name(buf[i]) for i, k in enumerate(names)}
@@ -348,9 +374,9 @@ class TsmEngine:
         _lib.check(self._lib.tsm_set_layer_timing(self._h, n_forwards, int(only_conv3x3)), self._h)
 
     def layer_times_ms(self, forward_index: int) -> Dict[str, float]:
-        buf = (C.c_float * 80)()
+        buf = (C.c_float * 512)()
         n = C.c_int32()
-        _lib.check(self._lib.tsm_layer_times(self._h, forward_index, C.addressof(buf), 80, C.byref(n)), self._h)
+        _lib.check(self._lib.tsm_layer_times(self._h, forward_index, C.addressof(buf), 512, C.byref(n)), self._h)
         names = self.launch_names()
         assert n.value == len(names), (n.value, len(names))
         return {k: float(buf[i]) for i, k in enumerate(names)}
@@ -373,6 +399,21 @@ class TsmEngine:
             self.close()
         except Exception:
             pass
+
+
+def _check_convnext(depths, num_segments: int, is_shift: bool, dtype: str, shift_place: str = 'blockres', non_local: bool = False,
+                    temporal_pool: bool = False):
+    """``base_model='convnext_base'`` is an image model: one frame per clip, no temporal shift, fp32 only.  Everything else is
+    refused up front, never ignored; returns the stage depths ((3, 3, 27, 3) unless given)."""
+    if dtype != 'f32':
+        if dtype in _lib.DTYPES:
+            raise NotImplementedError(f"{CONVNEXT} runs in dtype='f32' only, not {dtype!r}")
+        raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
+    if num_segments != 1 or is_shift:
+        raise NotImplementedError(f'{CONVNEXT} is an image model (num_segments=1, is_shift=False): there is no temporal shift in this family')
+    if non_local or temporal_pool or shift_place != 'blockres':
+        raise NotImplementedError(f'{CONVNEXT} has no non_local / temporal_pool / shift_place')
+    return _convnext_depths(depths)
 
 
 def _check_non_local(non_local: bool, base_model: str, dtype: str) -> None:
@@ -437,6 +478,9 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     ``layer2.net.<b>.*`` keys are mapped (``weights.remap_checkpoint_keys``).  ``dtype='bf16'``, ``non_local=True`` and an
     ``.onnx`` checkpoint raise NotImplementedError; ``is_shift=False`` and an odd ``num_segments`` raise ValueError.
     """
+    if is_convnext(base_model):
+        raise NotImplementedError(f'{base_model} is an image model: there is no temporal shift in this family; use create_image_model / '
+                                  'create_feature_model')
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     assert consensus_type in ['avg', 'identity']
@@ -484,8 +528,14 @@ def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpo
     through (``engine.image_resize`` / ``engine.image_crop``; ``inference_count.inference_images`` reads them).
     ``checkpoint``: a ``torch.save``d ``state_dict`` (or a dict with a ``state_dict`` entry) with plain torchvision keys --
     ``conv1.weight``, ``layer1.0.*``, ``fc.*`` -- or a Lightning one whose keys carry one leading component
-    (``weights.remap_torchvision_keys``).  Without one the engine gets the seeded synthetic weights, as ``create_model`` does."""
-    if base_model not in DEPTHS:
+    (``weights.remap_torchvision_keys``).  Without one the engine gets the seeded synthetic weights, as ``create_model`` does.
+    ``base_model='convnext_base'``: the classifier the reference's own image training produces (train_img.py:28-43:
+    ``timm.create_model('convnext_base', num_classes=...)`` under a Lightning module's ``classifier``; timm 0.5.4) -- a
+    ``TsmEngine(base_model='convnext_base', convnext_depths=(3, 3, 27, 3))``, include/tsm_hip.h: tsm_set_convnext.  Its
+    ``checkpoint`` has timm's keys, with or without that one leading component (``weights.remap_timm_keys``).  ``dtype`` other
+    than 'f32', an ``.onnx`` checkpoint and every other ConvNeXt variant raise NotImplementedError before the library loads."""
+    convnext = _convnext_image_model(base_model, checkpoint, dtype)
+    if not convnext and base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     if crop > resize:
         raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
@@ -498,11 +548,12 @@ def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpo
     if checkpoint is not None:
         import torch
         ckpt = torch.load(checkpoint, map_location='cpu')
-        sd = remap_torchvision_keys(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+        sd = (remap_timm_keys if convnext else remap_torchvision_keys)(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
     else:
         sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
     eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
-                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg')
+                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg',
+                    convnext_depths=CONVNEXT_DEPTHS if convnext else None)
     eng.image_resize, eng.image_crop = int(resize), int(crop)
     return eng
 
@@ -516,8 +567,11 @@ def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str]
     torchvision-keyed ``state_dict`` as ``create_image_model`` reads it; a ``num_classes=0`` model has no ``fc.*``, so a zero
     ``fc`` [1, feature_dim] stands in (the engine's finalize wants a classifier; its logits are never asked for).  Without a
     checkpoint: the seeded synthetic weights.  ``resize`` / ``crop``: ``Resize(resize)`` + ``CenterCrop(crop)`` through
-    ``tsm_preprocess`` (the reference resizes to 224 without a crop; an engine has one geometry -- DESIGN 4.17)."""
-    if base_model not in DEPTHS:
+    ``tsm_preprocess`` (the reference resizes to 224 without a crop; an engine has one geometry -- DESIGN 4.17).
+    ``base_model='convnext_base'`` (timm keys, ``weights.remap_timm_keys``): ``forward_features`` is [n, 1024], the head
+    LayerNorm's output -- what timm's ``num_classes=0`` model returns; the stand-in classifier is ``head.fc``."""
+    convnext = _convnext_image_model(base_model, checkpoint, dtype)
+    if not convnext and base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     if crop > resize:
         raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
@@ -531,18 +585,31 @@ def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str]
     if checkpoint is not None:
         import torch
         ckpt = torch.load(checkpoint, map_location='cpu')
-        sd = remap_torchvision_keys(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
-        if 'fc.weight' in sd:
-            num_class = int(sd['fc.weight'].shape[0])
+        sd = (remap_timm_keys if convnext else remap_torchvision_keys)(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+        fc = 'head.fc' if convnext else 'fc'
+        if fc + '.weight' in sd:
+            num_class = int(sd[fc + '.weight'].shape[0])
         else:
-            sd['fc.weight'] = np.zeros((1, feature_width(base_model)), dtype=np.float32)
-            sd['fc.bias'] = np.zeros((1,), dtype=np.float32)
+            sd[fc + '.weight'] = np.zeros((1, feature_width(base_model)), dtype=np.float32)
+            sd[fc + '.bias'] = np.zeros((1,), dtype=np.float32)
     else:
         sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
     eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
-                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg')
+                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg',
+                    convnext_depths=CONVNEXT_DEPTHS if convnext else None)
     eng.image_resize, eng.image_crop = int(resize), int(crop)
     return eng
+
+
+def _convnext_image_model(base_model: str, checkpoint, dtype: str) -> bool:
+    """Whether an image / feature model is the ConvNeXt one; its refusals (another variant, a bf16 format, an ``.onnx`` file)
+    raise NotImplementedError here, before a checkpoint is read or the library loads."""
+    if not is_convnext(base_model):
+        return False
+    _check_convnext(None, 1, False, dtype)
+    if checkpoint is not None and str(checkpoint).endswith('.onnx'):
+        raise NotImplementedError(f'{base_model} with an .onnx checkpoint: the importer reads the TSM-ResNet export only')
+    return True
 
 
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------

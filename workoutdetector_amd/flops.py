@@ -9,15 +9,37 @@ from __future__ import annotations
 
 from typing import Dict, List
 
-from .weights import NL_BLOCKS, STEM, block_specs, feature_width, nonlocal_specs
+from .weights import CONVNEXT_WIDTHS, NL_BLOCKS, STEM, _convnext_depths, block_specs, feature_width, is_convnext, nonlocal_specs
 
 
 def _out(size: int, k: int, stride: int) -> int:
     return (size + 2 * (k // 2) - k) // stride + 1
 
 
+def convnext_table(height: int = 224, width: int = 224, depths=None) -> List[Dict[str, int]]:
+    """``convnext_base``'s rows, the same columns as ``layer_table``: the stem (4x4 at stride 4 over 3 channels), per stage its
+    downsample (2x2 at stride 2, floor mode) and per block the depthwise 7x7 (``cin`` = 1: one input channel per output), fc1 and
+    fc2.  LayerNorm, GELU, the layer scale and the pooling count zero MACs.  15.4 GMAC per 224 x 224 frame with the 1000-class
+    head (``macs_per_frame``)."""
+    h, w = height // 4, width // 4
+    c0 = CONVNEXT_WIDTHS[0]
+    rows: List[Dict[str, int]] = [dict(name='stem', cin=3, cout=c0, k=4, s=4, m=h * w, macs=h * w * c0 * 3 * 16)]
+    for s, (nb, c) in enumerate(zip(_convnext_depths(depths), CONVNEXT_WIDTHS)):
+        if s > 0:
+            h, w = h // 2, w // 2
+            rows.append(dict(name=f'stages.{s}.downsample', cin=c // 2, cout=c, k=2, s=2, m=h * w, macs=h * w * c * (c // 2) * 4))
+        for b in range(nb):
+            p = f'stages.{s}.blocks.{b}'
+            rows.append(dict(name=p + '.conv_dw', cin=1, cout=c, k=7, s=1, m=h * w, macs=h * w * c * 49))
+            rows.append(dict(name=p + '.fc1', cin=c, cout=4 * c, k=1, s=1, m=h * w, macs=h * w * c * 4 * c))
+            rows.append(dict(name=p + '.fc2', cin=4 * c, cout=c, k=1, s=1, m=h * w, macs=h * w * c * 4 * c))
+    return rows
+
+
 def layer_table(height: int = 224, width: int = 224, base_model: str = 'resnet50') -> List[Dict[str, int]]:
     """One row per conv launch-able layer: name, cin, cout, k, s (stride), m (output pixels per frame), macs per frame."""
+    if is_convnext(base_model):
+        return convnext_table(height, width)
     _wkey, _bn, cout, cin, k = STEM
     ho, wo = _out(height, k, 2), _out(width, k, 2)
     rows: List[Dict[str, int]] = [dict(name='conv1', cin=cin, cout=cout, k=k, s=2, m=ho * wo, macs=ho * wo * cout * cin * k * k)]

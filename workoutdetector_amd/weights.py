@@ -1,4 +1,5 @@
-"""Weights for the TSM-ResNet engine (R50, R18, R34, WRN-50-2): seeded synthetic state dicts and checkpoint key remapping.
+"""Weights for the TSM-ResNet engine (R50, R18, R34, WRN-50-2) and the ConvNeXt-Base image model: seeded synthetic state dicts
+and checkpoint key remapping.
 
 No trained weights exist offline, so benches and parity tests use
 a deterministic, numerically non-trivial state dict keyed exactly like the reference's
@@ -40,6 +41,24 @@ NL_BLOCKS = ((2, 0), (2, 2), (3, 0), (3, 2), (3, 4))
 NL_GAINS = {(2, 0): 0.2, (2, 2): 0.16, (3, 0): 0.14, (3, 2): 0.11, (3, 4): 0.08}
 
 
+# The image model the reference trains (train_img.py: timm.create_model('convnext_base'), timm 0.5.4) -> tsm_set_convnext.
+# Widths are powers of two >= 128, so every GEMM of the network fits conv_igemm; the smaller variants' (96, 192, ...) do not.
+CONVNEXT = 'convnext_base'
+CONVNEXT_WIDTHS = (128, 256, 512, 1024)
+CONVNEXT_DEPTHS = (3, 3, 27, 3)
+
+
+def is_convnext(base_model: str) -> bool:
+    """True for 'convnext_base'; NotImplementedError for every other ConvNeXt variant, whose widths are not powers of two
+    (tiny / small: 96, 192, 384, 768; large: 192 ...; xlarge: 256 ... 2048, wider than the head kernels)."""
+    if base_model == CONVNEXT:
+        return True
+    if isinstance(base_model, str) and base_model.startswith('convnext'):
+        raise NotImplementedError(f'{base_model}: of the ConvNeXt family the engine implements {CONVNEXT} only (widths 128 .. 1024); the '
+                                  "other variants' widths are not powers of two in 128 .. 1024, which conv_igemm needs")
+    return False
+
+
 def _backbone(base_model: str):
     if base_model not in BACKBONES:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(BACKBONES))}')
@@ -53,7 +72,9 @@ def bottleneck_width(base_model: str = 'resnet50') -> int:
 
 
 def feature_width(base_model: str = 'resnet50') -> int:
-    """Channels of layer4's output = the classifier's input width: 2048 (Bottleneck), 512 (BasicBlock)."""
+    """Channels of layer4's output = the classifier's input width: 2048 (Bottleneck), 512 (BasicBlock); 1024 for convnext_base."""
+    if is_convnext(base_model):
+        return CONVNEXT_WIDTHS[-1]
     return R50_PLANES[-1] * (EXPANSION if _backbone(base_model)[1] == 'bottleneck' else 1)
 
 
@@ -136,8 +157,90 @@ def conv_specs(base_model: str = 'resnet50', shift_place: str = 'blockres',
     return specs
 
 
+def _convnext_depths(depths) -> Tuple[int, int, int, int]:
+    d = tuple(int(v) for v in (CONVNEXT_DEPTHS if depths is None else depths))
+    if len(d) != 4 or any(v < 1 or v > 64 for v in d):
+        raise ValueError(f'convnext depths must be four stage depths in 1 .. 64, got {depths!r}')
+    return d
+
+
+def convnext_specs(depths=None) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """(key, shape, kind) of every tensor of timm 0.5.4's ``convnext_base`` without its classifier, in ``state_dict()`` order;
+    ``depths``: blocks per stage, (3, 3, 27, 3) by default.  kind: ``conv`` (a conv / linear weight), ``bias``, ``ln_w`` / ``ln_b``
+    (a LayerNorm's pair), ``gamma`` (a block's layer scale).  The classifier is ``head.fc.{weight [num_class, 1024], bias}``."""
+    specs: List[Tuple[str, Tuple[int, ...], str]] = []
+
+    def pair(key, shape, kinds=('conv', 'bias')):
+        specs.append((key + '.weight', shape, kinds[0]))
+        specs.append((key + '.bias', (shape[0],), kinds[1]))
+
+    ln = ('ln_w', 'ln_b')
+    pair('stem.0', (CONVNEXT_WIDTHS[0], 3, 4, 4))
+    pair('stem.1', (CONVNEXT_WIDTHS[0],), ln)
+    for s, (nb, c) in enumerate(zip(_convnext_depths(depths), CONVNEXT_WIDTHS)):
+        p = f'stages.{s}'
+        if s > 0:
+            pair(p + '.downsample.0', (c // 2,), ln)
+            pair(p + '.downsample.1', (c, c // 2, 2, 2))
+        for b in range(nb):
+            q = f'{p}.blocks.{b}'
+            specs.append((q + '.gamma', (c,), 'gamma'))
+            pair(q + '.conv_dw', (c, 1, 7, 7))
+            pair(q + '.norm', (c,), ln)
+            pair(q + '.mlp.fc1', (4 * c, c))
+            pair(q + '.mlp.fc2', (c, 4 * c))
+    pair('head.norm', (CONVNEXT_WIDTHS[-1],), ln)
+    return specs
+
+
+def _make_convnext_state_dict(seed: int, num_class: int, depths) -> 'OrderedDict[str, np.ndarray]':
+    """The seeded ``convnext_base`` state dict, from a generator of its own (seeded from ``(seed, "cnx")``).  Conv / linear weights
+    are normal with std 1 / sqrt(fan_in), their biases std 0.1; LayerNorm weights uniform in 0.8 .. 1.2, biases std 0.1; ``gamma``
+    uniform in 0.1 .. 0.3 -- NOT timm's initial 1e-6, under which every block is the identity to fp32 and no test of a block could
+    fail.  A block then adds a branch of about a seventh of the stream's size: over the 36 blocks the root mean square of the
+    residual stream stays in 1.0 .. 1.3 (tests/test_convnext_cpu.py checks 0.5 .. 100 on the float64 model)."""
+    rng = np.random.default_rng([seed, int.from_bytes(b'cnx', 'big')])
+    sd: 'OrderedDict[str, np.ndarray]' = OrderedDict()
+    for key, shape, kind in convnext_specs(depths) + [('head.fc.weight', (num_class, CONVNEXT_WIDTHS[-1]), 'fc'), ('head.fc.bias', (num_class,), 'bias')]:
+        if kind == 'conv':
+            a = rng.standard_normal(shape) / np.sqrt(float(np.prod(shape[1:])))
+        elif kind == 'fc':
+            a = rng.standard_normal(shape) * 0.05
+        elif kind == 'ln_w':
+            a = rng.uniform(0.8, 1.2, shape)
+        elif kind == 'gamma':
+            a = rng.uniform(0.1, 0.3, shape)
+        else:
+            a = rng.standard_normal(shape) * 0.1
+        sd[key] = np.ascontiguousarray(a, dtype=np.float32)
+    return sd
+
+
+def remap_timm_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, object]':
+    """A timm ``convnext_base`` ``state_dict`` (``stem.0.weight``, ``stages.0.blocks.0.gamma``, ..., ``head.fc.*``) -> engine keys,
+    which are timm's own.  The reference's Lightning checkpoint holds the model as ``classifier`` (train_img.py:28-43), so every
+    key carries one leading component: it is stripped when every key has the same one and ``stem.0.weight`` is not already there.
+    Anything that is not a ConvNeXt key raises."""
+    keys = list(state_dict.keys())
+    if not keys:
+        raise ValueError('empty state dict')
+    strip = 0
+    if 'stem.0.weight' not in state_dict:
+        heads = {k.split('.', 1)[0] for k in keys}
+        if len(heads) != 1 or f'{next(iter(heads))}.stem.0.weight' not in state_dict:
+            raise ValueError('not a timm ConvNeXt state dict: no stem.0.weight, with or without one leading component')
+        strip = len(next(iter(heads))) + 1
+    out: 'OrderedDict[str, object]' = OrderedDict()
+    for k, v in state_dict.items():
+        name = k[strip:]
+        if name.split('.', 1)[0] not in ('stem', 'stages', 'head'):
+            raise ValueError(f'{k}: not a key of a timm ConvNeXt')
+        out[name] = v
+    return out
+
+
 def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resnet50',
-                    shift_place: str = 'blockres', non_local: bool = False) -> 'OrderedDict[str, np.ndarray]':
+                    shift_place: str = 'blockres', non_local: bool = False, depths=None) -> 'OrderedDict[str, np.ndarray]':
     """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048] -- [cls, 512] for R18/R34).
 
     He-normal convs; BN statistics are all non-trivial so the fold is exercised; the last BN of
@@ -150,7 +253,13 @@ def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resne
     every other key keeps its numbers.  theta / phi std ``NL_GAINS`` / sqrt(C) (soft but not uniform attention at the test
     sizes), g std 1 / sqrt(C), W.0 std 1 / sqrt(d), biases std 0.1; W.1 like every other BatchNorm with gamma damped by 0.35 -- NOT the zero
     of the original init, under which the block is the identity.
+    ``base_model='convnext_base'``: timm's keys from a generator of its own (``_make_convnext_state_dict``), ``depths`` blocks per
+    stage ((3, 3, 27, 3) by default); ``depths`` goes with no other backbone.
     """
+    if is_convnext(base_model):
+        return _make_convnext_state_dict(seed, num_class, depths)
+    if depths is not None:
+        raise ValueError(f'depths= goes with base_model={CONVNEXT!r} only')
     last_bn = '.bn2' if _backbone(base_model)[1] == 'basic' else '.bn3'
     rng = np.random.default_rng(seed)
     sd: 'OrderedDict[str, np.ndarray]' = OrderedDict()

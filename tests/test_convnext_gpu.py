@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import _convnext as cn
+from tests import _convnext_cases as cc
 from tests import _image_path as ip
 from tests._guard import guarded, guarded_out
 from tests._util import assert_close
@@ -74,18 +75,6 @@ def _bits(a):
 
 
 # ---- per kernel, through taps ---------------------------------------------------------------------------------------------
-def _block_inputs(depths):
-    """{block name: the tap that is its input}."""
-    out, prev = {}, 'stem'
-    for s, nb in enumerate(depths):
-        if s > 0:
-            prev = f'stages.{s}.downsample'
-        for b in range(nb):
-            out[f'stages.{s}.blocks.{b}'] = prev
-            prev = f'stages.{s}.blocks.{b}'
-    return out
-
-
 @pytest.mark.parametrize('size', SIZES, ids=lambda s: f'{s[0]}x{s[1]}')
 def test_every_operator_against_float64_from_the_tap_in_front_of_it(hip_lib, size, capsys):
     """dwconv7 + LayerNorm in all four widths, fc1 + GELU, fc2 + layer scale + residual, the three downsamples (LayerNorm + 2x2
@@ -106,36 +95,13 @@ def test_every_operator_against_float64_from_the_tap_in_front_of_it(hip_lib, siz
         def close(name, want, what):
             worst[what] = max(worst.get(what, 0.0), assert_close(tap(name), want, what=f'{name} ({what}) at {h}x{w}', **OP_BAR))
 
-        stem = tap('stem')
-        sizes = [(h // 4 >> s, w // 4 >> s) for s in range(4)]
-        assert stem.shape == (3, sizes[0][0], sizes[0][1], 128)
-        close('stem', cn.stem(sd, x[:, 0]), 'stem')
+        for name, what, want in cc.operator_cases(sd, SHALLOW, x, tap):
+            close(name, want, what)
         # the all-zero frame: the stem's bias through its LayerNorm in every pixel, the same bits everywhere
+        stem = tap('stem')
         bias_row = cn.layer_norm(sd['stem.0.bias'], sd['stem.1.weight'], sd['stem.1.bias'])
         assert (_bits(stem[2]) == _bits(stem[2])[0, 0]).all(), 'the zero frame\'s stem output is not constant over the pixels'
         assert_close(stem[2, 0, 0], bias_row, what='stem of the zero frame', **OP_BAR)
-        inputs = _block_inputs(SHALLOW)
-        for blk, src in inputs.items():
-            s = int(blk.split('.')[1])
-            c = cn.WIDTHS[s]
-            xin = tap(src)
-            assert xin.shape == (3,) + sizes[s] + (c,), (blk, xin.shape)
-            dwln = cn.layer_norm(cn.dwconv7(xin, sd[blk + '.conv_dw.weight'], sd[blk + '.conv_dw.bias']), sd[blk + '.norm.weight'],
-                                 sd[blk + '.norm.bias'])
-            close(blk + '.dwln', dwln, f'dwln{c}')
-            fc1 = cn.gelu(cn.linear(tap(blk + '.dwln'), sd[blk + '.mlp.fc1.weight'], sd[blk + '.mlp.fc1.bias']))
-            assert tap(blk + '.fc1').shape == (3,) + sizes[s] + (4 * c,)
-            close(blk + '.fc1', fc1, 'fc1+gelu')
-            out = cn.f64(xin) + cn.f64(sd[blk + '.gamma']) * cn.linear(tap(blk + '.fc1'), sd[blk + '.mlp.fc2.weight'], sd[blk + '.mlp.fc2.bias'])
-            close(blk, out, 'fc2+residual')
-        for s in (1, 2, 3):
-            last = f'stages.{s - 1}.blocks.{SHALLOW[s - 1] - 1}'
-            close(f'stages.{s}.downsample', cn.downsample(sd, s, tap(last)), 'downsample')
-            assert tap(f'stages.{s}.downsample').shape == (3,) + sizes[s] + (cn.WIDTHS[s],)
-        pool, _ = cn.head_norm(sd, tap('stages.3.blocks.0'))
-        close('head.pool', pool.reshape(3, 1, 1, 1024), 'pool')
-        _, norm = cn.head_norm(sd, tap('head.pool').reshape(3, 1, 1, 1024))
-        close('head.norm', norm.reshape(3, 1, 1, 1024), 'head.norm')
     finally:
         eng.close()
     with capsys.disabled():

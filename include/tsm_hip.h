@@ -304,6 +304,54 @@ int tsm_set_temporal_pool(tsm_engine *e, int32_t on);
  * those five are TSM_ERR_UNSUPPORTED in turn on an engine that is already a ConvNeXt one. */
 int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]);
 
+/* TDN-ResNet50 (Temporal Difference Network) -- create_model of workoutdetector/models/tdn.py: TSN(backbone_fn=tdn_net).  The
+ * engine builds the TDN topology in place of the TSM one.  Eval mode, fp32.  This comment is the network's definition.
+ *
+ * Input [n_clips, T, 5, 3, H, W] = [n_clips, T, 15, H, W] = [n_clips * T * 5, 3, H, W] (one memory layout): f0 .. f4 are the five
+ * frames of a segment, N = n_clips * T.
+ * Short-term path:  D = concat(f1 - f0, f2 - f1, f3 - f2, f4 - f3) (12 channels); P = avgpool2x2(D), stride 2;
+ *   x_c5 = ReLU(BN(conv7x7 s2 p3 (P))), 12 -> 64, no conv bias ("base_model.conv1_5.0.weight" [64, 12, 7, 7], BN "conv1_5.1.*");
+ *   xd0 = maxpool3x3 s2 p1 (x_c5); xd1 = resnext_layer1(xd0): depths[0] plain Bottlenecks 64 -> 256 with their own weights.
+ * Trunk:  s = maxpool(ReLU(BN(conv1(f2)))) -- the stem sees the centre frame only; x = alpha s + beta up(xd0); x = layer1_bak(x)
+ *   (plain Bottlenecks); x = alpha x + beta up(xd1); layer2_bak .. layer4_bak are BottleneckShift blocks; global average pool,
+ *   new_fc, consensus over T.  up is torch's 'nearest' to the target size: src = min(int(floorf(dst * ((float)in / out))), in - 1).
+ *   alpha, beta are arguments (tdn_net's rule: 0.5, 0.5 when T == 8, else 0.75, 0.25).
+ * Every conv of both ResNets (conv1, the block convs, the downsamples) has a bias and a BatchNorm behind it (eps 1e-5); a
+ * Bottleneck is torchvision's with the stride on conv2.
+ * BottleneckShift: conv1 + BN + ReLU, mse, shift, conv2 (3x3 at the block's stride) + BN + ReLU, conv3 + BN (+ downsample), add,
+ * ReLU.  With x = conv1's output [N, H, W, C] and r = C / 16:
+ *   b = BN_a(W1 x), 1x1 C -> r, no bias ("mse.conv1", "mse.bn1");  c = DW3x3(b), depthwise, pad 1, no bias, no BN ("mse.conv2" [r, 1, 3, 3]);
+ *   d+[t] = c[t + 1] - b[t] for t < T - 1 and 0 at t = T - 1;  d-[t] = c[t - 1] - b[t] for t > 0 and 0 at t = 0; frames of another
+ *   clip are never read.  For each direction d:
+ *     s2 = BN_2(K2 * avgpool2x2(d)), the pool in floor mode (7 -> 3), K2 a full 3x3 r -> r, pad 1, no bias
+ *          ("mse.conv3_smallscale2", "mse.bn3_smallscale2");  s4 = BN_4(K4 * d) at full size ("mse.conv3_smallscale4", "mse.bn3_smallscale4");
+ *     m = d / 3 + up(s2) / 3 + s4 / 3 -- the BatchNorm biases make m non-zero on the zero frame: it is not skipped;
+ *   e = BN_3(W3 m), 1x1 r -> C, no bias ("mse.conv3", "mse.bn3"; the same weights for both directions);
+ *   y = (sigmoid(e+) - 1/2) / 2 + (sigmoid(e-) - 1/2) / 2;  g = x + x y;
+ *   o[t, c] = w[c, 0] g[t - 1, c] + w[c, 1] g[t, c] + w[c, 2] g[t + 1, c], zeros beyond the clip's ends ("shift.conv.weight" [C, 1, 3]:
+ *   learned; the shift pattern is only its initial value).  o is conv2's input.
+ * State-dict keys, the TSN module's: "base_model.{conv1, bn1}.*", "base_model.conv1_5.*", "base_model.resnext_layer1.B.*",
+ * "base_model.layer1_bak.B.*", "base_model.layerL_bak.B.*" with ".mse.*" and ".shift.conv.weight", "new_fc.{weight, bias}".
+ * "base_model.conv1_temp.{weight, bias}" is in every checkpoint and unused by the forward: accepted and ignored, as every
+ * ".num_batches_tracked" is.
+ *
+ * depths: blocks per stage, (3, 4, 6, 3) for the model; resnext_layer1 has depths[0] blocks.
+ * Legal between tsm_create and the first tsm_set_tensor, later TSM_ERR_INVALID_ARG (as is depths == NULL or a non-finite alpha /
+ * beta).  TSM_ERR_UNSUPPORTED: a dtype other than TSM_DTYPE_F32, is_shift != 0 (TDN has no TSM shift), num_segments < 2, height or
+ * width not a multiple of 32 or below 64 (a layer4 mSE map could not be pooled), a depth outside 1 .. 64, and after
+ * tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_shift_place, tsm_set_non_local(e, 1), tsm_set_temporal_pool(e, 1) or
+ * tsm_set_convnext; those six are TSM_ERR_UNSUPPORTED in turn on a TDN engine.  tsm_set_consensus stays legal.
+ * tsm_forward / tsm_forward_features / tsm_forward_tap take TSM_LAYOUT_NTCHW only, 15 planes per segment, host or device memory
+ * (any other layout: TSM_ERR_UNSUPPORTED); everything else is tsm_forward's contract word for word: tsm_tune covers every conv
+ * of the engine (conv1_5 runs on conv_igemm as a 1x1 GEMM over patch rows of K = 1024, 588 of them real), tile codes never change
+ * a result bit, after tuning the call only enqueues and is capture-safe, and the tune-cache key carries " tdn<depths>".
+ * The front end runs in chunks of at most 8 clips through one patch buffer; a clip's result does not depend on the chunking.
+ * Launches between conv1 and conv2 of a BottleneckShift: mse_squeeze_kernel and mse_excite_shift_kernel are the only readers of
+ * conv1's output, and o is the only full-width tensor written: b, d, s2 and m have r channels, g never reaches memory.
+ * Taps (tsm_forward_tap): "diff.conv1_5" (x_c5), "diff.stem" (xd0), "resnext_layer1.B", "stem", "fuse1", "layer1.B", "fuse2",
+ * "layerL.B", "layerL.B.conv1", "layerL.B.mse.fwd" / ".mse.bwd" (m+ / m-, [N, H, W, r]), "layerL.B.shift" (o), "layerL.B.conv2". */
+int tsm_set_tdn(tsm_engine *e, const int32_t depths[4], float alpha, float beta);
+
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,
  * BN vectors [C], fc [num_class, 2048] -- [num_class, 512] for resnet18 / resnet34).  Names are the reference's TSM.state_dict() keys, e.g.
  * "base_model.layer1.0.conv1.net.weight" ("...conv1.weight" is accepted too).  The engine copies;
@@ -366,6 +414,11 @@ float tsm_last_forward_ms(tsm_engine *e);
  * synchronises on forward `forward_index` (0-based since the last tsm_set_layer_timing) and writes
  * one duration in ms per launch, in launch order: pack_input, conv1 (stem), maxpool, then per block
  * [downsample,] conv1, conv2, conv3 (BasicBlock: [downsample,] conv1, conv2), then head (pool + fc).
+ * A TDN engine (tsm_set_tdn): per front-end chunk the engine's capacity holds (ceil(max_clips / chunk), chunk = min(8, max_clips,
+ * what keeps a chunk's patch rows below 2^29 floats)) diff.front.<i>, diff.conv1_5.<i> -- a forward of fewer chunks leaves the
+ * rest not recorded --, then diff.maxpool, conv1 (the stem with its fused max-pool), fuse1; per block of resnext_layer1
+ * [downsample,] conv1, conv2, conv3; per block of layer1 the same; fuse2; per BottleneckShift of layers 2 - 4 [downsample,] conv1,
+ * mse_squeeze, mse_diff, mse_s2, mse_mix, mse_excite_shift, conv2, conv3; then head.
  * *n_out = number of launches. */
 int tsm_set_layer_timing(tsm_engine *e, int32_t n_forwards, int32_t only_conv3x3);
 int tsm_layer_times(tsm_engine *e, int32_t forward_index, float *ms_out, int32_t cap, int32_t *n_out);

@@ -7,11 +7,12 @@ without it (no CPU fallback).
 """
 from .counting import RepCounter, obo_mae, pred_to_count, scores_to_preds, to_softmax  # noqa: F401
 
-__all__ = ['RepCounter', 'obo_mae', 'pred_to_count', 'scores_to_preds', 'to_softmax', 'TsmEngine', 'create_model', 'create_image_model']
+__all__ = ['RepCounter', 'obo_mae', 'pred_to_count', 'scores_to_preds', 'to_softmax', 'TsmEngine', 'create_model', 'create_image_model',
+           'create_tdn_model']
 
 
 def __getattr__(name):
-    if name in ('TsmEngine', 'create_model', 'create_image_model'):
+    if name in ('TsmEngine', 'create_model', 'create_image_model', 'create_tdn_model'):
         from . import engine
         return getattr(engine, name)
     raise AttributeError(name)

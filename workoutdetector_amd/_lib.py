@@ -79,7 +79,7 @@ class TsmConvArgs(C.Structure):
                 + [(n, C.c_int32) for n in ('cin2', 'hi2', 'wi2', 'stride2', 'code', 'reverse')])
 
 
-EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_consensus', 'tsm_set_non_local', 'tsm_set_temporal_pool', 'tsm_set_convnext', 'tsm_set_tensor', 'tsm_finalize',
+EXPORTS = ('tsm_abi_version', 'tsm_build_id', 'tsm_trace_launches', 'tsm_launch_trace', 'tsm_create', 'tsm_destroy', 'tsm_last_error', 'tsm_set_backbone', 'tsm_set_bottleneck_width', 'tsm_set_shift_place', 'tsm_set_consensus', 'tsm_set_non_local', 'tsm_set_temporal_pool', 'tsm_set_convnext', 'tsm_set_tdn', 'tsm_set_tensor', 'tsm_finalize',
            'tsm_forward', 'tsm_tune', 'tsm_forward_tap', 'tsm_last_forward_ms', 'tsm_set_layer_timing', 'tsm_layer_times', 'tsm_conv_tiles', 'tsm_temporal_shift', 'tsm_conv_bn_act',
            'tsm_conv_op', 'tsm_maxpool3x3s2', 'tsm_head', 'tsm_head_segments', 'tsm_preprocess', 'tsm_gather_clips', 'tsm_preprocess_clips', 'tsm_scores_to_states', 'tsm_preprocess_image', 'tsm_frame_votes',
            'tsm_preprocess_indexed', 'tsm_preprocess_windows', 'tsm_top1_tally', 'tsm_forward_features', 'tsm_pool_features', 'tsm_cosine_distances', 'tsm_maxpool2x2', 'tsm_nonlocal_attention')
@@ -133,6 +133,8 @@ def load() -> C.CDLL:
     lib.tsm_set_temporal_pool.argtypes = [vp, i32]
     lib.tsm_set_convnext.restype = C.c_int
     lib.tsm_set_convnext.argtypes = [vp, C.POINTER(i32)]
+    lib.tsm_set_tdn.restype = C.c_int
+    lib.tsm_set_tdn.argtypes = [vp, C.POINTER(i32), C.c_float, C.c_float]
     lib.tsm_set_tensor.restype = C.c_int
     lib.tsm_set_tensor.argtypes = [vp, C.c_char_p, fp, C.POINTER(i64), i32]
     lib.tsm_finalize.restype = C.c_int

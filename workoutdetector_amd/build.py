@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get('TSM_LIB_PATH') or os.path.join(PKG_DIR, 'libtsm_hip.s
 # One translation unit per kernel family (csrc/tsm_device.h lists them): objects are rebuilt only when their own source or
 # a header changed, in parallel, then linked.
 SOURCES = ['tsm_igemm.hip', 'tsm_bf16_256.hip', 'tsm_ws.hip', 'tsm_bneck.hip', 'tsm_conv31.hip', 'tsm_front.hip', 'tsm_fused23.hip',
-           'tsm_stem.hip', 'tsm_ops.hip', 'tsm_similarity.hip', 'tsm_nonlocal.hip', 'tsm_convnext.hip', 'tsm_engine.hip']
+           'tsm_stem.hip', 'tsm_ops.hip', 'tsm_similarity.hip', 'tsm_nonlocal.hip', 'tsm_convnext.hip', 'tsm_tdn.hip', 'tsm_engine.hip']
 OBJ_DIR = os.path.join(CSRC, 'obj')
 # Per-file compiler options.  tsm_bneck.hip: MFMA results in architectural VGPRs (the "vgprcd" form).  Its kernels pin 208
 # weight registers in the accumulation half of the file, and with AGPRs in use the compiler otherwise puts EVERY MFMA

@@ -14,6 +14,7 @@
 //   tsm_similarity.hip cosine_dist_kernel: the cosine-distance matrix of unit rows on the exact-fp32 MFMA
 //   tsm_nonlocal.hip   maxpool2x2_kernel, nonlocal_attn_kernel: the non-local block's pool and its fused online-softmax attention (fp32)
 //   tsm_convnext.hip   dwconv7_ln_kernel, ln_kernel, stem_pack4_kernel, gelu_kernel: the non-GEMM part of a ConvNeXt-Base image model (fp32)
+//   tsm_tdn.hip        tdn_front_kernel, tdn_fuse_kernel, mse_*_kernel: the difference front end, the blends and the long-term (mSE + temporal conv) module of a TDN-ResNet50 (fp32)
 #pragma once
 #include "tsm_kernels.h"
 

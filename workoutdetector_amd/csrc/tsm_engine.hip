@@ -1,6 +1,7 @@
 // Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet clip forward on MI355X (ResNet-50 by default; ResNet-18 / 34
 // through tsm_set_backbone; the shift in front of conv1 by default, in front of the whole block through tsm_set_shift_place),
-// and for the ConvNeXt-Base image model through tsm_set_convnext (build_convnext_topology, run_convnext, finalize_convnext).
+// for the ConvNeXt-Base image model through tsm_set_convnext (build_convnext_topology, run_convnext, finalize_convnext), and for
+// TDN-ResNet50 through tsm_set_tdn (build_tdn_topology, run_tdn, finalize_tdn).
 //
 // Owns: packed weights (BatchNorm folded, K-major), an NHWC fp32 activation workspace sized for
 // max_clips, one HIP stream, two timing events.  The forward is a fixed schedule of kernel launches
@@ -76,6 +77,9 @@ struct ConvLayer : LayerGeom {   // cp, kp, kseg: tsm_host_util.h, layer_geometr
   // [cout, 3, 4, 4], 2 = a downsample [cout, cout / 2, 2, 2], 3 = fc1 [cout, cin], 4 = fc2 [cout, cin] with the block's gamma folded in
   int cnx = 0;
   std::string gkey;   // (4) the block's "gamma"
+  // a TDN engine's convs: 1 = a conv with a bias ("<name>.bias" beside wkey's "<name>.weight") in front of its BatchNorm, folded
+  // into the BatchNorm's mean; 2 = conv1_5 [64, 12, 7, 7] (no bias) as a 1x1 GEMM over the front end's patch rows
+  int tdn = 0;
   float *d_w = nullptr, *d_b = nullptr;
 };
 
@@ -102,6 +106,19 @@ struct Block {
   // whether the temporal pool runs behind this block (the last one of layer1)
   int T = 0;
   bool tpool_after = false;
+  // a TDN engine: the block's long-term module between conv1 and conv2 (index into tdn_mse; -1: a plain Bottleneck), and whether
+  // the block belongs to the difference path (resnext_layer1, on the maps of xd0) instead of the trunk
+  int mse = -1;
+  bool diff_path = false;
+};
+
+// A TDN engine's long-term module (mSE + the learned temporal conv) of one BottleneckShift: its packed weights on the device
+// (tsm_host_util.h: tdn_pack_mse).
+struct TdnMse {
+  int c = 0;          // conv1's width; the module works on r = c / 16 channels
+  std::string key;    // "base_model.layerL_bak.B": its tensors are "<key>.mse.*" and "<key>.shift.conv.weight"
+  float *d_wq = nullptr, *d_bq = nullptr, *d_dw = nullptr, *d_k2 = nullptr, *d_b2 = nullptr, *d_k4 = nullptr, *d_b4 = nullptr;
+  float *d_w3 = nullptr, *d_b3 = nullptr, *d_wt = nullptr;
 };
 
 // A ConvNeXt engine (tsm_set_convnext): one LayerNorm's affine pair, one block, one stage.  Every GEMM is a ConvLayer of
@@ -179,6 +196,15 @@ struct tsm_engine {
   std::vector<CnxBlock> cnx_blocks;
   CnxStage cnx_stages[4];
   CnxNorm cnx_stem_norm, cnx_head_norm;
+  int tdn = 0;                // tsm_set_tdn: a TDN-ResNet50 topology; input [n_clips, T, 15, H, W]
+  int tdn_depths[4] = {0, 0, 0, 0};
+  float tdn_alpha = 0.5f, tdn_beta = 0.5f;
+  std::vector<TdnMse> tdn_mse;
+  int tdn_chunk = 0;          // clips per front-end chunk (tdn_chunk_clips)
+  int hd = 0, wd = 0;         // the difference path's maps (xd0, resnext_layer1)
+  float *d_patches = nullptr; // conv1_5's patch rows of one chunk
+  // the long-term module's r-channel maps: b, d+, d-, m+, m- at the block's size; pooled d+, d-, s2+, s2- at half of it
+  float *d_mse[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int consensus = 0;          // tsm_set_consensus: 0 avg ([n_clips, num_class]), 1 identity ([n_clips, T, num_class])
   int feat = 2048;            // channels of the last stage = the classifier's input width
   int features = 0;           // for the duration of a tsm_forward_features call: 1 = the forward ends in the pooled rows, 2 = in the unit rows
@@ -301,8 +327,51 @@ void build_convnext_topology(tsm_engine *e) {
   e->feat = kCnxWidths[kCnxStages - 1];
 }
 
+// The TDN topology (include/tsm_hip.h, tsm_set_tdn; the TSN module's key spelling).  convs[0] is the trunk's stem, convs[1]
+// conv1_5 as a 1x1 GEMM over K = kTdnPatchK; then resnext_layer1's plain Bottlenecks (the difference path), then layer1_bak's
+// plain Bottlenecks and the BottleneckShift blocks of layer2_bak .. layer4_bak, each with a TdnMse.  Every conv but conv1_5
+// has a bias.
+void build_tdn_topology(tsm_engine *e) {
+  e->convs.clear();
+  e->blocks.clear();
+  e->tdn_mse.clear();
+  e->convs[add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false)].tdn = 1;
+  e->convs[add_conv(e, "base_model.conv1_5.0.weight", "base_model.conv1_5.1", kTdnPatchK, 64, 1, 1, true)].tdn = 2;
+  for (int li = -1; li < 4; ++li) {   // -1: resnext_layer1
+    const int stage = li < 0 ? 0 : li, planes = kPlanes[stage], cout = 4 * planes;
+    int cin = stage == 0 ? 64 : 4 * kPlanes[stage - 1];
+    for (int b = 0; b < e->tdn_depths[stage]; ++b) {
+      const int stride = (b == 0 && stage > 0) ? 2 : 1;
+      const std::string lname = li < 0 ? "resnext_layer1" : "layer" + std::to_string(li + 1);
+      const std::string p = "base_model." + lname + (li < 0 ? "." : "_bak.") + std::to_string(b);
+      Block blk;
+      blk.stride = stride;
+      blk.T = e->cfg.num_segments;
+      blk.name = blk.out_name = lname + "." + std::to_string(b);
+      blk.diff_path = li < 0;
+      blk.conv1 = add_conv(e, p + ".conv1.weight", p + ".bn1", cin, planes, 1, 1, true);
+      blk.conv2 = add_conv(e, p + ".conv2.weight", p + ".bn2", planes, planes, 3, stride, true);
+      blk.conv3 = add_conv(e, p + ".conv3.weight", p + ".bn3", planes, cout, 1, 1, false);
+      blk.down = b == 0 ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false) : -1;
+      for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down})
+        if (ci >= 0) e->convs[ci].tdn = 1;
+      if (li >= 1) {
+        TdnMse m;
+        m.c = planes;
+        m.key = p;
+        blk.mse = (int)e->tdn_mse.size();
+        e->tdn_mse.push_back(m);
+      }
+      e->blocks.push_back(blk);
+      cin = cout;
+    }
+  }
+  e->feat = 4 * kPlanes[3];
+}
+
 void build_topology(tsm_engine *e) {
   if (e->convnext) return build_convnext_topology(e);
+  if (e->tdn) return build_tdn_topology(e);
   e->convs.clear();
   e->blocks.clear();
   add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false);
@@ -407,8 +476,32 @@ bool known_convnext_name(const tsm_engine *e, const std::string &name) {
   return false;
 }
 
+// A TDN engine's tensors: the TSN module's keys as they are ("new_fc.*" is the classifier; "base_model.conv1_temp.*" is in every
+// checkpoint and unused by the forward: accepted, then ignored).
+const char *const kBnSuffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
+const char *const kTdnMseConvs[] = {".mse.conv1.weight", ".mse.conv2.weight", ".mse.conv3.weight", ".mse.conv3_smallscale2.weight",
+                                    ".mse.conv3_smallscale4.weight", ".shift.conv.weight"};
+const char *const kTdnMseBns[] = {".mse.bn1", ".mse.bn3", ".mse.bn3_smallscale2", ".mse.bn3_smallscale4"};
+bool known_tdn_name(const tsm_engine *e, const std::string &name) {
+  if (name == "new_fc.weight" || name == "new_fc.bias" || name == "base_model.conv1_temp.weight" || name == "base_model.conv1_temp.bias") return true;
+  for (const ConvLayer &c : e->convs) {
+    if (name == c.wkey || (c.tdn == 1 && name == c.wkey.substr(0, c.wkey.size() - 6) + "bias")) return true;
+    for (const char *s : kBnSuffix)
+      if (name == c.bnp + s) return true;
+  }
+  for (const TdnMse &m : e->tdn_mse) {
+    for (const char *s : kTdnMseConvs)
+      if (name == m.key + s) return true;
+    for (const char *bn : kTdnMseBns)
+      for (const char *s : kBnSuffix)
+        if (name == m.key + bn + s) return true;
+  }
+  return false;
+}
+
 bool known_name(const tsm_engine *e, const std::string &name) {
   if (e->convnext) return known_convnext_name(e, name);
+  if (e->tdn) return known_tdn_name(e, name);
   if (name == "fc.weight" || name == "fc.bias") return true;
   static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
   auto is = [&](const std::string &key) {
@@ -476,7 +569,9 @@ int upload_conv(tsm_engine *e, Alloc &alloc, int prec, int cout, std::vector<flo
 // poison word, so whatever a kernel relies on in them must be written by THIS forward, not inherited.  Weights are not touched.
 int poison_workspace(tsm_engine *e, hipStream_t s) {
   if (!e->poison) return TSM_OK;
-  const float *targets[] = {e->buf[0], e->buf[1], e->buf[2], e->buf[3], e->buf[4], e->d_in4, e->d_pooled, e->d_logits, e->d_partial, e->d_tap};
+  const float *targets[] = {e->buf[0], e->buf[1], e->buf[2], e->buf[3], e->buf[4], e->d_in4, e->d_pooled, e->d_logits, e->d_partial, e->d_tap,
+                            e->d_patches, e->d_mse[0], e->d_mse[1], e->d_mse[2], e->d_mse[3], e->d_mse[4], e->d_mse[5], e->d_mse[6], e->d_mse[7],
+                            e->d_mse[8]};
   for (const GuardBuf &g : e->guards)
     for (const float *t : targets)
       if (t && t == g.ptr())
@@ -773,6 +868,10 @@ std::vector<BlockPlan> plan_forward(const tsm_engine *e, const std::vector<int> 
   int hh = e->hp, ww = e->wp;
   for (size_t k = 0; k < e->blocks.size(); ++k) {
     const Block &blk = e->blocks[k];
+    if (e->tdn && (k == 0 || blk.diff_path != e->blocks[k - 1].diff_path)) {   // a TDN engine: the difference path's maps first, then the trunk's
+      hh = blk.diff_path ? e->hd : e->hp;
+      ww = blk.diff_path ? e->wd : e->wp;
+    }
     const BlockForms can = fused_forms(e, k, nn, hh, ww, stage);
     auto chosen = [&](int force, int conv, int bit) { return force == 1 || (codes && ((*codes)[conv] & bit)); };
     BlockPlan &p = plan[k];
@@ -796,6 +895,7 @@ struct Forward {
   Tap *tap;
   int prec;
   float *t1, *t2, *idb;                // branch temporaries, the BasicBlock's downsample output
+  float *obuf = nullptr;               // a TDN engine: the long-term module's output o, conv2's input in a BottleneckShift (run_tdn sets it)
   std::vector<int> *tiles = nullptr;   // tile codes of this bucket (null: heuristic shapes -- TSM_AUTOTUNE=0 or a tap)
   bool tuning = false;                 // the bucket's tuning pass: time the candidates, write the winners into *tiles
   bool tapped = false;
@@ -838,6 +938,7 @@ struct Forward {
   int run_basic(size_t k, int nn, float *x, float *y, int hh, int ww);
   int run_block(size_t k, const BlockPlan &plan, int nn, float *x, float *y, int hh, int ww);
   int run_nonlocal(size_t k, int nn, float *x, float *z, int hh, int ww);
+  int run_mse(size_t k, int nn, int hh, int ww);
   int tune_block(size_t k, int nn, float *x, float *y, int hh, int ww);
 };
 
@@ -937,6 +1038,7 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
   const int c1out = e->convs[blk.conv1].cout, c2out = e->convs[blk.conv2].cout, c3out = e->convs[blk.conv3].cout;
   const int ho = conv_out_size(hh, 3, blk.stride), wo = conv_out_size(ww, 3, blk.stride);
   BlockLaunches L = block_launches(e, k, nn, x, y, t1, t2, hh, ww);
+  if (blk.mse >= 0) L.p2.x = L.pf.x = obuf;   // a BottleneckShift: conv2 reads the long-term module's output, not conv1's
   if (blk.down >= 0) skip_slots(e, 1);
   if (plan.block) {
     L.pb.reverse = next_dir();
@@ -957,6 +1059,10 @@ int Forward::run_block(size_t k, const BlockPlan &plan, int nn, float *x, float 
       if (rc1) return rc1;
     }
     if (want(name + ".conv1")) return hit(t1, nn, hh, ww, c1out);
+    if (blk.mse >= 0) {
+      const int rcm = run_mse(k, nn, hh, ww);
+      if (rcm || tapped) return rcm;
+    }
     if (plan.conv23) {
       L.pf.reverse = next_dir();
       TSM_LAUNCH_K(e, s, true, tsm::launch_conv23_fused(L.pf, blk.cmid, blk.cout3, prec, s));
@@ -1001,6 +1107,26 @@ int Forward::run_nonlocal(size_t k, int nn, float *x, float *z, int hh, int ww) 
   return want(blk.name) ? hit(z, nn, hh, ww, cw.cout) : TSM_OK;
 }
 
+// The long-term module of BottleneckShift k of a TDN engine, between conv1 (its output in t1, nn frames of hh x ww pixels) and
+// conv2 (which reads obuf).  Five launches, five timing slots: mse_squeeze (the first of the two readers of t1), mse_diff, mse_s2,
+// mse_mix -- all on r = C / 16 channels -- and mse_excite_shift, the second reader of t1 and the only writer of a full-width
+// tensor, o.  Taps: ".mse.fwd" / ".mse.bwd" (m+ / m-), ".shift" (o).
+int Forward::run_mse(size_t k, int nn, int hh, int ww) {
+  const Block &blk = e->blocks[k];
+  const TdnMse &m = e->tdn_mse[blk.mse];
+  const int c = m.c, r = c / kTdnReduction, T = blk.T, hq = tdn_pool_size(hh), wq = tdn_pool_size(ww);
+  float *const *q = e->d_mse;   // b, d+, d-, m+, m-, pooled d+, pooled d-, s2+, s2-
+  TSM_LAUNCH(e, s, tsm::launch_mse_squeeze(t1, m.d_wq, m.d_bq, q[0], (int64_t)nn * hh * ww, c, s));
+  TSM_LAUNCH(e, s, tsm::launch_mse_diff(q[0], m.d_dw, q[1], q[2], q[5], q[6], nn, T, hh, ww, c, s));
+  TSM_LAUNCH(e, s, tsm::launch_mse_s2(q[5], q[6], m.d_k2, m.d_b2, q[7], q[8], nn, hq, wq, c, s));
+  TSM_LAUNCH(e, s, tsm::launch_mse_mix(q[1], q[2], q[7], q[8], m.d_k4, m.d_b4, q[3], q[4], nn, hh, ww, c, s));
+  if (want(blk.name + ".mse.fwd")) return hit(q[3], nn, hh, ww, r);
+  if (want(blk.name + ".mse.bwd")) return hit(q[4], nn, hh, ww, r);
+  TSM_LAUNCH(e, s, tsm::launch_mse_excite_shift(t1, q[3], q[4], m.d_w3, m.d_b3, m.d_wt, obuf, nn / T, T, hh * ww, c, s));
+  if (want(blk.name + ".shift")) return hit(obuf, nn, hh, ww, c);
+  return TSM_OK;
+}
+
 // One Bottleneck of the tuning pass: the candidate codes of conv1, conv2 and conv3 (conv()), and each fused form that can run
 // and that TSM_FUSE_* leaves to the tuner, timed against the tuned launches it replaces (same bits).  Every arm walks as in a
 // forward -- separate launches alternate r1, !r1, r1; a fused launch walks like the first launch it replaces -- so both arms
@@ -1011,10 +1137,12 @@ int Forward::tune_block(size_t k, int nn, float *x, float *y, int hh, int ww) {
   std::vector<int> &codes = *tiles;
   const BlockForms can = fused_forms(e, k, nn, hh, ww, nullptr);
   BlockLaunches L = block_launches(e, k, nn, x, y, t1, t2, hh, ww);
+  if (blk.mse >= 0) L.p2.x = L.pf.x = obuf;   // (as run_block)
   const int r1 = flip ^ 1;   // the walk direction conv() is about to give conv1
   bool wins = false;
   int rc = conv(blk.conv1, L.p1, 1, false);
   if (rc) return rc;
+  if (blk.mse >= 0 && (rc = run_mse(k, nn, hh, ww))) return rc;   // (one form, nothing to time: run so that its kernels are loaded)
   L.p1.reverse = dir(r1);
   if (prev31 >= 0 && e->fuse31 < 0) {   // the previous block's conv3 + this conv1 as one launch (both arms write the same bits)
     const int conv3 = e->blocks[prev31].conv3, code3 = codes[conv3], code1 = codes[blk.conv1];
@@ -1131,6 +1259,93 @@ int run_convnext(tsm_engine *e, Forward &f, const float *d_clips, int layout, in
   return TSM_OK;
 }
 
+// The head of a ResNet-shaped engine over the last block's output `cur` [n, hw, feat] -- one launch, one timing slot: the pooled
+// (or unit) rows of tsm_forward_features, the per-segment logits of an identity engine, or pool + fc + the mean over the segments.
+int run_head(tsm_engine *e, const float *cur, int n, int n_clips, int hw, float *d_logits, hipStream_t s, const char *stage) {
+  const int prec = e->prec;
+  if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
+  if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
+    TSM_LAUNCH(e, s, tsm::launch_pool_features(cur, e->features == 1 ? d_logits : nullptr, e->features == 2 ? d_logits : nullptr, n,
+                                               hw, e->feat, prec, s));
+    return TSM_OK;
+  }
+  if (e->consensus == 1) {   // per-segment logits: one launch, d_pooled is not written (the head's one timing slot either way)
+    TSM_LAUNCH(e, s, tsm::launch_head_segments(cur, e->d_fcw, e->d_fcb, d_logits, n, hw, e->feat, e->cfg.num_class, prec, s));
+    return TSM_OK;
+  }
+  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, out_segments(e), hw, e->feat,
+                                    e->cfg.num_class, prec, s));
+  return TSM_OK;
+}
+
+// The forward of a TDN engine (tsm_set_tdn) on n_clips clips of T segments, x [n_clips, T, 15, H, W].  Launches and timing slots,
+// in order (TsmEngine.launch_names spells them):
+//   per chunk of at most tdn_chunk clips: diff.front (tdn_front_kernel: the centre frames into d_in4, the patch rows of the chunk),
+//     diff.conv1_5 (the 1x1 GEMM over them into the chunk's rows of x_c5); a forward of fewer chunks than the engine's
+//     capacity holds leaves the other chunks' slots not recorded;
+//   diff.maxpool (xd0); conv1 (the fp32 stem with its fused max-pool, from d_in4), fuse1;
+//   per block of resnext_layer1: [downsample,] conv1, conv2, conv3 -- as every Bottleneck (run_block);
+//   per block of layer1: the same; fuse2;
+//   per BottleneckShift of layers 2 - 4: [downsample,] conv1, mse_squeeze, mse_diff, mse_s2, mse_mix, mse_excite_shift, conv2, conv3;
+//   head.
+// Buffers: xd0 in buf[0] and the stem's output in buf[4]; resnext_layer1 rotates buf[0] and buf[1], the trunk buf[4] and whichever
+// of buf[0] / buf[1] does not hold xd1; behind fuse2 xd1's buffer is dead and holds o, the long-term module's output.
+int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int n_clips, float *d_logits, hipStream_t s) {
+  const tsm_config &cfg = e->cfg;
+  const int T = cfg.num_segments, n = n_clips * T, H = cfg.height, W = cfg.width, prec = e->prec;
+  const int h5 = tdn_conv15_size(H), w5 = tdn_conv15_size(W);
+  const int64_t plane = (int64_t)H * W, rows = (int64_t)h5 * w5;
+  float *xc5 = f.t2;
+  const int max_chunks = (cfg.max_clips + e->tdn_chunk - 1) / e->tdn_chunk;
+  int chunks = 0;
+  for (int c0 = 0; c0 < n_clips; c0 += e->tdn_chunk, ++chunks) {
+    const int nf = std::min(e->tdn_chunk, n_clips - c0) * T;
+    const int64_t f0 = (int64_t)c0 * T;
+    TSM_LAUNCH(e, s, tsm::launch_tdn_front(d_clips + f0 * kTdnPlanes * plane, e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+    // (the tuning pass times conv1_5's candidates on its first chunk only; a later, smaller chunk re-validates the code: checked_code)
+    tsm::ConvParams p = make_params(e->convs[1], e->d_patches, nullptr, xc5 + f0 * rows * 64, nf, h5, w5, true, 0, 1, prec);
+    const bool was_tuning = f.tuning;
+    if (chunks > 0) f.tuning = false;
+    const int rc = f.conv(1, p, 1, false);
+    f.tuning = was_tuning;
+    if (rc) return rc;
+  }
+  skip_slots(e, 2 * (max_chunks - chunks));
+  if (f.want("diff.conv1_5")) return f.hit(xc5, n, h5, w5, 64);
+  float *xd0 = e->buf[0], *stem = e->buf[4];
+  TSM_LAUNCH(e, s, tsm::launch_maxpool3x3s2(xc5, xd0, n, h5, w5, 64, prec, s));
+  if (f.want("diff.stem")) return f.hit(xd0, n, e->hd, e->wd, 64);
+  TSM_LAUNCH(e, s, tsm::launch_stem_pool(e->d_in4, e->convs[0].d_w, e->convs[0].d_b, stem, n, H, W, e->convs[0].kp, 1, prec, s, 0));
+  if (f.want("stem")) return f.hit(stem, n, e->hp, e->wp, 64);
+  TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(stem, xd0, n, e->hp, e->wp, e->hd, e->wd, 64, e->tdn_alpha, e->tdn_beta, s));
+  if (f.want("fuse1")) return f.hit(stem, n, e->hp, e->wp, 64);
+
+  const std::vector<BlockPlan> plan = f.tuning ? std::vector<BlockPlan>() : plan_forward(e, f.tiles, n, f.stage);
+  float *cur = xd0, *out = e->buf[1], *xd1 = nullptr;
+  int h = e->hd, w = e->wd;
+  for (size_t k = 0; k < e->blocks.size(); ++k) {
+    const Block &blk = e->blocks[k];
+    if (!blk.diff_path && k > 0 && e->blocks[k - 1].diff_path) {   // the trunk starts: layer1 reads the blended stem
+      xd1 = cur;
+      f.obuf = xd1;   // (dead behind fuse2, which runs before the first BottleneckShift)
+      out = xd1 == e->buf[0] ? e->buf[1] : e->buf[0];
+      cur = stem;
+      h = e->hp;
+      w = e->wp;
+    }
+    if (blk.mse == 0) {   // the first BottleneckShift: layer1 is done
+      TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(cur, xd1, n, h, w, e->hd, e->wd, 256, e->tdn_alpha, e->tdn_beta, s));
+      if (f.want("fuse2")) return f.hit(cur, n, h, w, 256);
+    }
+    const int rc = f.tuning ? f.tune_block(k, n, cur, out, h, w) : f.run_block(k, plan[k], n, cur, out, h, w);
+    if (rc || f.tapped) return rc;
+    std::swap(cur, out);
+    h = conv_out_size(h, 3, blk.stride);
+    w = conv_out_size(w, 3, blk.stride);
+  }
+  return run_head(e, cur, n, n_clips, h * w, d_logits, s, f.stage);
+}
+
 // Enqueue the forward on `s`.  If `stage` is non-null, stop right after that stage and report it.
 int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, float *d_logits,
                 hipStream_t s, const char *stage, Tap *tap) {
@@ -1150,6 +1365,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     f.tiles = &it->second;
   }
   if (e->convnext) return run_convnext(e, f, d_clips, layout, n, d_logits, s);
+  if (e->tdn) return run_tdn(e, f, d_clips, n_clips, d_logits, s);
 
   const int prec = e->prec;
   const float *in4 = e->d_in4;
@@ -1216,20 +1432,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
       if (f.want("layer2.tpool")) return f.hit(cur, n, h, w, c);
     }
   }
-  const int T_out = out_segments(e);
-  if (stage) return fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + stage);
-  if (e->features) {   // tsm_forward_features: d_logits is the [n, feat] output; the pool launch takes the head's timing slot
-    TSM_LAUNCH(e, s, tsm::launch_pool_features(cur, e->features == 1 ? d_logits : nullptr, e->features == 2 ? d_logits : nullptr, n,
-                                               h * w, e->feat, prec, s));
-    return TSM_OK;
-  }
-  if (e->consensus == 1) {   // per-segment logits: one launch, d_pooled is not written (the head's one timing slot either way)
-    TSM_LAUNCH(e, s, tsm::launch_head_segments(cur, e->d_fcw, e->d_fcb, d_logits, n, h * w, e->feat, cfg.num_class, prec, s));
-    return TSM_OK;
-  }
-  TSM_LAUNCH(e, s, tsm::launch_head(cur, e->d_fcw, e->d_fcb, e->d_pooled, d_logits, n_clips, T_out, h * w, e->feat,
-                                    cfg.num_class, prec, s));
-  return TSM_OK;
+  return run_head(e, cur, n, n_clips, h * w, d_logits, s, stage);
 }
 
 // The tile codes of the bucket `n_clips` falls into: already in memory, read from the tune cache file, or timed now on
@@ -1275,6 +1478,10 @@ void retag_tune_sig(tsm_engine *e) {
     e->tune_sig += " cnx";
     for (int s = 0; s < kCnxStages; ++s) e->tune_sig += (s ? "-" : "") + std::to_string(e->cnx_depths[s]);
   }
+  if (e->tdn) {
+    e->tune_sig += " tdn";
+    for (int s = 0; s < 4; ++s) e->tune_sig += (s ? "-" : "") + std::to_string(e->tdn_depths[s]);
+  }
   if (e->non_local) e->tune_sig += " nl";
   if (e->temporal_pool) e->tune_sig += " tp";
 }
@@ -1285,6 +1492,8 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
   if (!clips) return fail(e, TSM_ERR_INVALID_ARG, "clips is NULL");
   if (memkind != TSM_MEM_HOST && memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "bad memkind");
   if (layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
+  if (e->tdn && layout != TSM_LAYOUT_NTCHW)
+    return fail(e, TSM_ERR_UNSUPPORTED, "a TDN engine takes TSM_LAYOUT_NTCHW only: [n_clips, T, 15, H, W], five frames per segment");
   if (layout >= TSM_LAYOUT_NTHWC4 && memkind != TSM_MEM_DEVICE)
     return fail(e, TSM_ERR_INVALID_ARG, "packed layouts (NTHWC4 / NTHWC8S / NTHWC8B) are device-memory layouts");
   if (layout >= TSM_LAYOUT_NTHWC4 && layout != packed_layout_of(e->prec))
@@ -1302,7 +1511,7 @@ int stage_input(tsm_engine *e, const void *clips, int memkind, int n_clips, void
   *s = pick_stream(e, memkind, stream);
   *d_clips = static_cast<const float *>(clips);
   if (memkind == TSM_MEM_HOST) {
-    const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * 3 * e->cfg.height * e->cfg.width;
+    const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * (e->tdn ? kTdnPlanes : 3) * e->cfg.height * e->cfg.width;
     TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, *s));
     *d_clips = e->d_in;
   }
@@ -1318,6 +1527,7 @@ int check_before_weights(tsm_engine *e, const char *setter) {
 
 // The ResNet setters on a ConvNeXt engine (tsm_set_convnext came first): refused, the topology has none of their parts.
 int refuse_on_convnext(tsm_engine *e, const char *setter) {
+  if (e->tdn) return fail(e, TSM_ERR_UNSUPPORTED, std::string(setter) + ": a TDN engine (tsm_set_tdn) has no such part");
   if (!e->convnext) return TSM_OK;
   return fail(e, TSM_ERR_UNSUPPORTED, std::string(setter) + ": a ConvNeXt engine (tsm_set_convnext) has no such part");
 }
@@ -1392,6 +1602,173 @@ int finalize_convnext(tsm_engine *e) {
   if ((rc = dev_alloc(e, &e->d_logits, frames * cfg.num_class, "d_logits", (size_t)cfg.num_class))) return rc;
   e->partial_elems = (size_t)16 << 20;   // split-K scratch, as every fp32 engine has
   if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", (size_t)per_frame))) return rc;
+  e->tensors.clear();
+  e->finalized = true;
+  return TSM_OK;
+}
+
+// The Bottleneck fusions' weights, from the folded fp32 matrices of the 1x1 layers (host_wp / host_bias by conv index), for
+// tsm_finalize and finalize_tdn alike.
+template <class Alloc>
+int upload_block_fusions(tsm_engine *e, Alloc &alloc, const std::vector<std::vector<float>> &host_wp, const std::vector<std::vector<float>> &host_bias) {
+  // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
+  for (Block &blk : e->blocks) {
+    if (blk.down < 0 || blk.conv3 < 0) continue;   // (Bottlenecks only)
+    const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
+    std::vector<float> wf, bf;
+    concat_k_pair(host_wp[blk.conv3], host_bias[blk.conv3], c3.kp, host_wp[blk.down], host_bias[blk.down], cd.kp, c3.cout,
+                  &wf, &bf);
+    if (int rc = upload_conv(e, alloc, e->prec, c3.cout, &wf, bf, &blk.d_wf, &blk.d_bf)) return rc;
+  }
+  // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide and whose conv3 has 4x as many outputs
+  // (conv23_fused_kernel: four phase-C chunks), or 128 wide with 2x as many (conv23_fused2_kernel, wide_resnet50_2's
+  // layer1.1-2: two chunks): conv3's weights once more, in the fragment order of the fused conv2 + conv3 kernel (fp32 and
+  // split-bf16 engines).  Any other mid / output pair keeps the two separate launches.
+  for (Block &blk : e->blocks) {
+    if (blk.conv3 < 0) continue;   // (Bottlenecks only)
+    const ConvLayer &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
+    if (blk.down >= 0 || blk.stride != 1 || (c2.cout != 64 && c2.cout != 128)) continue;
+    if (e->prec == tsm::kPrecBf16) {   // weight-stationary form: 64 mid channels only; it reads conv3's packed matrix itself
+      if (c2.cout == 64 && c2.cin == 64 && c3.cout == 256) { blk.cmid = 64; blk.cout3 = 256; }
+      continue;
+    }
+    const int nchunk = c3.cout == 4 * c2.cout ? 4 : (c3.cout == 2 * c2.cout && c2.cout == 128) ? 2 : 0;
+    if (nchunk == 0) continue;
+    std::vector<float> w3f;
+    if (e->prec == tsm::kPrecBf16x3) pack_w3_fragments_split(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
+    else pack_w3_fragments(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
+    if (int rc = upload(e, alloc, &blk.d_w3f, "d_w3f", w3f)) return rc;
+    blk.cmid = c2.cout;
+    blk.cout3 = c3.cout;
+  }
+  return TSM_OK;
+}
+
+// tsm_finalize of a TDN engine.  Every conv of both ResNets has a bias in front of its BatchNorm: folded into the BatchNorm's mean
+// (tdn_mean_less_bias), then the engine's own folds and fusions apply; conv1_5 goes into the patch rows' K order; each
+// BottleneckShift's long-term module is packed by tdn_pack_mse.  Workspace: the five rotating buffers, the 15-plane host
+// staging buffer, the patch rows of one front-end chunk and the nine r-channel maps of the widest long-term module.
+int finalize_tdn(tsm_engine *e) {
+  const tsm_config &cfg = e->cfg;
+  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };
+  auto want = [e](const std::string &key, const std::vector<int64_t> &shape, const HostTensor **t) {
+    *t = find_tensor(e, key);
+    if (!*t) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + key);
+    if ((*t)->shape != shape) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + key);
+    return (int)TSM_OK;
+  };
+  // the four vectors of BatchNorm `bnp` side by side: [gamma | beta | mean | var], c each
+  auto want_bn = [&](const std::string &bnp, int c, std::vector<float> *bn) {
+    bn->clear();
+    for (int i = 0; i < 4; ++i) {
+      const HostTensor *t;
+      if (int rc = want(bnp + kBnSuffix[i], {c}, &t)) return rc;
+      bn->insert(bn->end(), t->data.begin(), t->data.end());
+    }
+    return (int)TSM_OK;
+  };
+  std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
+  for (size_t ci = 0; ci < e->convs.size(); ++ci) {
+    ConvLayer &c = e->convs[ci];
+    const HostTensor *w;
+    std::vector<float> bn, wp, bias;
+    if (int rc = want(c.wkey, c.tdn == 2 ? std::vector<int64_t>{c.cout, kTdnDiffC, 7, 7} : std::vector<int64_t>{c.cout, c.cin, c.k, c.k}, &w)) return rc;
+    if (int rc = want_bn(c.bnp, c.cout, &bn)) return rc;
+    const float *g = bn.data(), *b = g + c.cout, *m = b + c.cout, *v = m + c.cout;
+    if (c.tdn == 2) {
+      tdn_pack_conv15(w->data.data(), g, b, m, v, c.cout, &wp, &bias);
+    } else {
+      const HostTensor *cb;
+      if (int rc = want(c.wkey.substr(0, c.wkey.size() - 6) + "bias", {c.cout}, &cb)) return rc;
+      const std::vector<float> mean = tdn_mean_less_bias(m, cb->data.data(), c.cout);
+      prepare_weights(c, w->data.data(), g, b, mean.data(), v, &wp, &bias);
+    }
+    if (c.k == 1 && c.tdn == 1) {
+      host_wp[ci] = wp;
+      host_bias[ci] = bias;
+    }
+    if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
+  }
+  if (int rc = upload_block_fusions(e, alloc, host_wp, host_bias)) return rc;
+  for (TdnMse &m : e->tdn_mse) {
+    const int C = m.c, r = C / kTdnReduction;
+    const HostTensor *c1, *c2, *c3, *k2, *k4, *wt;
+    std::vector<float> bn1, bn2, bn4, bn3;
+    if (int rc = want(m.key + ".mse.conv1.weight", {r, C, 1, 1}, &c1)) return rc;
+    if (int rc = want(m.key + ".mse.conv2.weight", {r, 1, 3, 3}, &c2)) return rc;
+    if (int rc = want(m.key + ".mse.conv3.weight", {C, r, 1, 1}, &c3)) return rc;
+    if (int rc = want(m.key + ".mse.conv3_smallscale2.weight", {r, r, 3, 3}, &k2)) return rc;
+    if (int rc = want(m.key + ".mse.conv3_smallscale4.weight", {r, r, 3, 3}, &k4)) return rc;
+    if (int rc = want(m.key + ".shift.conv.weight", {C, 1, 3}, &wt)) return rc;
+    if (int rc = want_bn(m.key + ".mse.bn1", r, &bn1)) return rc;
+    if (int rc = want_bn(m.key + ".mse.bn3_smallscale2", r, &bn2)) return rc;
+    if (int rc = want_bn(m.key + ".mse.bn3_smallscale4", r, &bn4)) return rc;
+    if (int rc = want_bn(m.key + ".mse.bn3", C, &bn3)) return rc;
+    TdnMseWeights pk;
+    tdn_pack_mse(C, c1->data.data(), bn1.data(), c2->data.data(), k2->data.data(), bn2.data(), k4->data.data(), bn4.data(),
+                 c3->data.data(), bn3.data(), wt->data.data(), &pk);
+    const std::pair<float **, const std::vector<float> *> parts[] = {
+        {&m.d_wq, &pk.wq}, {&m.d_bq, &pk.bq}, {&m.d_dw, &pk.dw}, {&m.d_k2, &pk.k2}, {&m.d_b2, &pk.b2},
+        {&m.d_k4, &pk.k4}, {&m.d_b4, &pk.b4}, {&m.d_w3, &pk.w3}, {&m.d_b3, &pk.b3}, {&m.d_wt, &pk.wt}};
+    for (const auto &part : parts)
+      if (int rc = upload(e, alloc, part.first, "mse_w", *part.second)) return rc;
+  }
+  const HostTensor *fw, *fb;
+  if (int rc = want("new_fc.weight", {cfg.num_class, e->feat}, &fw)) return rc;
+  if (int rc = want("new_fc.bias", {cfg.num_class}, &fb)) return rc;
+  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
+  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
+
+  const int H = cfg.height, W = cfg.width;
+  e->h1 = conv_out_size(H, 7, 2);
+  e->w1 = conv_out_size(W, 7, 2);
+  e->hp = conv_out_size(e->h1, 3, 2);
+  e->wp = conv_out_size(e->w1, 3, 2);
+  e->hd = tdn_diff_size(H);
+  e->wd = tdn_diff_size(W);
+  e->tdn_chunk = tdn_chunk_clips(cfg.max_clips, cfg.num_segments, H, W);
+  if (e->tdn_chunk <= 0) return fail(e, TSM_ERR_CAPACITY, "the patch rows of conv1_5 for one clip, T * (H / 4) * (W / 4) * 1024 floats, must stay below 2^29");
+  const size_t frames = (size_t)cfg.max_clips * cfg.num_segments;
+  // per frame: the largest activation (x_c5 and layer1's 256 channels on the stem's pooled map; the patch rows have their own
+  // buffer) and the largest r-channel map of a long-term module
+  size_t per_frame = (size_t)e->hp * e->wp * 256, mse_frame = 0;
+  {
+    int hh = 0, ww = 0;
+    for (size_t k = 0; k < e->blocks.size(); ++k) {
+      const Block &blk = e->blocks[k];
+      if (k == 0 || blk.diff_path != e->blocks[k - 1].diff_path) {
+        hh = blk.diff_path ? e->hd : e->hp;
+        ww = blk.diff_path ? e->wd : e->wp;
+      }
+      const size_t in_px = (size_t)hh * ww;
+      if (blk.mse >= 0) mse_frame = std::max(mse_frame, in_px * (size_t)(e->tdn_mse[blk.mse].c / kTdnReduction));
+      hh = conv_out_size(hh, 3, blk.stride);
+      ww = conv_out_size(ww, 3, blk.stride);
+      const size_t out_px = (size_t)hh * ww;
+      for (int ci : {blk.conv1, blk.conv2, blk.conv3})
+        per_frame = std::max(per_frame, (ci == blk.conv1 ? in_px : out_px) * (size_t)e->convs[ci].cout);
+    }
+  }
+  if ((double)frames * (double)per_frame >= (double)(kInt31 >> 2))
+    return fail(e, TSM_ERR_CAPACITY, "max_clips * num_segments * (H / 4) * (W / 4) * 256 activations must stay below 2^29 (32-bit byte offsets)");
+  e->buf_elems = frames * per_frame;
+  for (int i = 0; i < 5; ++i) {
+    static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
+    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame))) return rc;
+  }
+  const size_t in_frame = (size_t)kTdnPlanes * H * W;
+  if ((rc = dev_alloc(e, &e->d_in, frames * in_frame, "d_in", in_frame))) return rc;
+  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * H * W, "d_in4", (size_t)4 * H * W))) return rc;
+  const size_t patch_frame = (size_t)tdn_conv15_size(H) * tdn_conv15_size(W) * kTdnPatchK;
+  if ((rc = dev_alloc(e, &e->d_patches, (size_t)e->tdn_chunk * cfg.num_segments * patch_frame, "d_patches", patch_frame))) return rc;
+  static const char *const kMseNames[9] = {"mse.b", "mse.d+", "mse.d-", "mse.m+", "mse.m-", "mse.pool+", "mse.pool-", "mse.s2+", "mse.s2-"};
+  for (int i = 0; i < 9; ++i)   // (the pooled maps are a quarter of the size at most; one size for all keeps the bands' frame)
+    if ((rc = dev_alloc(e, &e->d_mse[i], frames * mse_frame, kMseNames[i], mse_frame))) return rc;
+  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
+  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
+                      (size_t)cfg.num_class))) return rc;
+  e->partial_elems = (size_t)16 << 20;   // split-K scratch, as every fp32 engine has
+  if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame))) return rc;
   e->tensors.clear();
   e->finalized = true;
   return TSM_OK;
@@ -1665,10 +2042,27 @@ int tsm_set_temporal_pool(tsm_engine *e, int32_t on) {
 int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]) {
   if (int rc = check_before_weights(e, "tsm_set_convnext")) return rc;
   if (!depths) return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_convnext: depths is NULL");
+  if (e->tdn) return fail(e, TSM_ERR_UNSUPPORTED, "tsm_set_convnext: a TDN engine (tsm_set_tdn) has no such part");
   if (const char *why = cnx_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, e->backbone_set, e->non_local, e->temporal_pool, depths))
     return fail(e, TSM_ERR_UNSUPPORTED, std::string("tsm_set_convnext: ") + why);
   e->convnext = 1;
   for (int s = 0; s < kCnxStages; ++s) e->cnx_depths[s] = depths[s];
+  build_topology(e);
+  retag_tune_sig(e);
+  return TSM_OK;
+}
+
+int tsm_set_tdn(tsm_engine *e, const int32_t depths[4], float alpha, float beta) {
+  if (int rc = check_before_weights(e, "tsm_set_tdn")) return rc;
+  if (!depths) return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_tdn: depths is NULL");
+  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(e, TSM_ERR_INVALID_ARG, "tsm_set_tdn: alpha and beta must be finite");
+  const int other = e->convnext || e->backbone_set || e->non_local || e->temporal_pool;
+  if (const char *why = tdn_refusal(e->prec, e->cfg.is_shift, e->cfg.num_segments, e->cfg.height, e->cfg.width, other, depths))
+    return fail(e, TSM_ERR_UNSUPPORTED, std::string("tsm_set_tdn: ") + why);
+  e->tdn = 1;
+  e->tdn_alpha = alpha;
+  e->tdn_beta = beta;
+  for (int s = 0; s < 4; ++s) e->tdn_depths[s] = depths[s];
   build_topology(e);
   retag_tune_sig(e);
   return TSM_OK;
@@ -1721,6 +2115,7 @@ int tsm_finalize(tsm_engine *e) {
   if (e->finalized) return TSM_OK;
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
   if (e->convnext) return finalize_convnext(e);
+  if (e->tdn) return finalize_tdn(e);
   const tsm_config &cfg = e->cfg;
   auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };   // ("weights", no frame)
   std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
@@ -1769,36 +2164,7 @@ int tsm_finalize(tsm_engine *e) {
     }
     if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
   }
-  // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
-  for (Block &blk : e->blocks) {
-    if (blk.down < 0 || blk.conv3 < 0) continue;   // (Bottlenecks only)
-    const ConvLayer &c3 = e->convs[blk.conv3], &cd = e->convs[blk.down];
-    std::vector<float> wf, bf;
-    concat_k_pair(host_wp[blk.conv3], host_bias[blk.conv3], c3.kp, host_wp[blk.down], host_bias[blk.down], cd.kp, c3.cout,
-                  &wf, &bf);
-    if (int rc = upload_conv(e, alloc, e->prec, c3.cout, &wf, bf, &blk.d_wf, &blk.d_bf)) return rc;
-  }
-  // Blocks without a downsample branch whose mid tensor is 64 / 128 channels wide and whose conv3 has 4x as many outputs
-  // (conv23_fused_kernel: four phase-C chunks), or 128 wide with 2x as many (conv23_fused2_kernel, wide_resnet50_2's
-  // layer1.1-2: two chunks): conv3's weights once more, in the fragment order of the fused conv2 + conv3 kernel (fp32 and
-  // split-bf16 engines).  Any other mid / output pair keeps the two separate launches.
-  for (Block &blk : e->blocks) {
-    if (blk.conv3 < 0) continue;   // (Bottlenecks only)
-    const ConvLayer &c2 = e->convs[blk.conv2], &c3 = e->convs[blk.conv3];
-    if (blk.down >= 0 || blk.stride != 1 || (c2.cout != 64 && c2.cout != 128)) continue;
-    if (e->prec == tsm::kPrecBf16) {   // weight-stationary form: 64 mid channels only; it reads conv3's packed matrix itself
-      if (c2.cout == 64 && c2.cin == 64 && c3.cout == 256) { blk.cmid = 64; blk.cout3 = 256; }
-      continue;
-    }
-    const int nchunk = c3.cout == 4 * c2.cout ? 4 : (c3.cout == 2 * c2.cout && c2.cout == 128) ? 2 : 0;
-    if (nchunk == 0) continue;
-    std::vector<float> w3f;
-    if (e->prec == tsm::kPrecBf16x3) pack_w3_fragments_split(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
-    else pack_w3_fragments(host_wp[blk.conv3].data(), c2.cout, &w3f, nchunk);
-    if (int rc = upload(e, alloc, &blk.d_w3f, "d_w3f", w3f)) return rc;
-    blk.cmid = c2.cout;
-    blk.cout3 = c3.cout;
-  }
+  if (int rc = upload_block_fusions(e, alloc, host_wp, host_bias)) return rc;
   host_wp.clear();
   host_bias.clear();
   const HostTensor *fw = find_tensor(e, "fc.weight"), *fb = find_tensor(e, "fc.bias");
@@ -1919,6 +2285,17 @@ int tsm_tune(tsm_engine *e, int32_t n_clips, void *stream) {
   // the engine's own packed-input buffer, zeroed, stands in for a batch: no caller memory, no host copy, no kernel of
   // anybody else's (a cold process pays first-use code-object loads for those)
   const size_t frames = (size_t)n_clips * e->cfg.num_segments;
+  if (e->tdn) {   // a TDN engine's input is the 15-plane tensor: its own staging buffer, zeroed, stands in (the front end fills d_in4)
+    TSM_HIP(e, hipMemsetAsync(e->d_in, 0, frames * kTdnPlanes * e->cfg.height * e->cfg.width * sizeof(float), s));
+    bool cached = false;
+    int rct = ensure_tuned(e, e->d_in, TSM_LAYOUT_NTCHW, n_clips, e->d_logits, s, &cached);
+    if (rct || !cached) return rct;
+    std::vector<hipEvent_t> *keep = e->cur_timing;   // (as below: the bucket's forward once, so that every kernel is loaded)
+    e->cur_timing = nullptr;
+    rct = run_forward(e, e->d_in, TSM_LAYOUT_NTCHW, n_clips, e->d_logits, s, nullptr, nullptr);
+    e->cur_timing = keep;
+    return rct;
+  }
   TSM_HIP(e, hipMemsetAsync(e->d_in4, 0, frames * 4 * e->cfg.height * (e->cfg.width + 1) * sizeof(float), s));
   const int layout = packed_layout_of(e->prec);
   bool from_file = false;
@@ -2017,6 +2394,7 @@ int tsm_conv_tiles(tsm_engine *e, int32_t n_clips, int32_t *tiles_out, int32_t c
   // launch order: stem, then per block [downsample,] conv1, conv2, conv3 (Bottleneck) / [downsample,] conv1, conv2 (BasicBlock)
   // [, the wrapper's theta | phi | g and W convs]
   std::vector<int> order{0};
+  if (e->tdn) order.push_back(1);   // (a TDN engine: the stem, conv1_5, then resnext_layer1's and the trunk's blocks)
   for (const Block &b : e->blocks)
     for (int ci : {b.down, b.conv1, b.conv2, b.conv3, b.nl_qkv, b.nl_w})
       if (ci >= 0) order.push_back(ci);

@@ -720,6 +720,134 @@ inline void cnx_fold_gamma(const float *w, const float *b, const float *gamma, i
   }
 }
 
+// ---- TDN-ResNet50 (tsm_set_tdn; include/tsm_hip.h holds the network's definition): the host arithmetic of its schedule --------
+constexpr int kTdnFrames = 5;            // frames per segment: 15 input planes
+constexpr int kTdnPlanes = 3 * kTdnFrames;
+constexpr int kTdnDiffC = 12;            // channels of the stacked frame differences
+constexpr int kTdnPatchReal = 7 * 7 * kTdnDiffC;   // 588: conv1_5's K, order (ky, kx, c)
+constexpr int kTdnPatchK = 1024;         // ... padded to what conv_igemm's 1x1 form takes: a power-of-two channel count
+constexpr int kTdnTile = 8;              // tdn_front_kernel: conv1_5 outputs per workgroup and side
+constexpr int kTdnChunkClips = 8;        // clips per front-end chunk through the one patch buffer
+constexpr int kTdnMaxDepth = 64;
+constexpr int kTdnReduction = 16;        // mSE squeeze: r = C / 16
+// torch's 'nearest' source index of output index dst for a side of `in` scaled to `out`: min(int(floorf(dst * ((float)in / out))), in - 1).
+TSM_HOST_DEVICE inline int tdn_nearest(int dst, int in, int out) {
+  const float scale = (float)in / (float)out;
+  const int src = (int)floorf((float)dst * scale);
+  return src < in - 1 ? src : in - 1;
+}
+// Sides along the two paths for an input side h (a multiple of 32, >= 64): the pooled differences h / 2, conv1_5 h / 4, xd0 and
+// resnext_layer1 h / 8; the trunk's stem conv h / 2, its max-pool and layer1 h / 4, then h / 8, h / 16, h / 32.
+inline int tdn_diff_pool_size(int h) { return h / 2; }
+inline int tdn_conv15_size(int h) { return conv_out_size(tdn_diff_pool_size(h), 7, 2); }
+inline int tdn_diff_size(int h) { return conv_out_size(tdn_conv15_size(h), 3, 2); }
+inline int tdn_stage_size(int h, int layer) {   // layer 1 .. 4: the side of that layer's block outputs
+  int v = conv_out_size(conv_out_size(h, 7, 2), 3, 2);
+  for (int l = 2; l <= layer; ++l) v = conv_out_size(v, 3, 2);
+  return v;
+}
+inline int tdn_pool_size(int h) { return h / 2; }   // the mSE module's AvgPool2d(2, 2), floor mode
+// Why tsm_set_tdn refuses an engine of this shape; nullptr when it can be built.
+inline const char *tdn_refusal(int prec, int is_shift, int num_segments, int height, int width, int other_topology, const int32_t *depths) {
+  if (!depths) return "depths is NULL";
+  if (prec != kPrecF32) return "a TDN engine runs in TSM_DTYPE_F32 only";
+  if (is_shift) return "a TDN engine has no TSM shift (its temporal conv is learned): is_shift must be 0";
+  if (num_segments < 2) return "a TDN engine needs num_segments >= 2 (the mSE module differences neighbouring segments)";
+  if (height < 64 || width < 64 || height % 32 != 0 || width % 32 != 0)
+    return "a TDN engine needs height and width that are multiples of 32 and at least 64 (a layer4 mSE map must be poolable)";
+  if (other_topology) return "tsm_set_tdn excludes every other tsm_set_* topology call";
+  for (int s = 0; s < 4; ++s)
+    if (depths[s] < 1 || depths[s] > kTdnMaxDepth) return "every stage depth must be in 1 .. 64";
+  return nullptr;
+}
+// Clips per front-end chunk: at most kTdnChunkClips, and few enough that the patch rows [chunk * T * rows][kTdnPatchK] stay below
+// 2^29 floats (the conv kernels' 32-bit byte offsets); 0 when one clip alone does not fit.
+inline int tdn_chunk_clips(int max_clips, int T, int h, int w) {
+  const int64_t rows = (int64_t)tdn_conv15_size(h) * tdn_conv15_size(w), per_clip = mul_sat31(mul_sat31(rows, T), kTdnPatchK);
+  if (per_clip <= 0 || per_clip >= (kInt31 >> 2)) return 0;
+  int64_t c = ((kInt31 >> 2) - 1) / per_clip;
+  if (c > kTdnChunkClips) c = kTdnChunkClips;
+  if (c > max_clips) c = max_clips;
+  return (int)c;
+}
+// K index of tap (ky, kx), difference channel c in a patch row.
+TSM_HOST_DEVICE inline int tdn_patch_k(int ky, int kx, int c) { return (ky * 7 + kx) * kTdnDiffC + c; }
+// Element of the pooled difference tensor P [hp, wp, 12] that patch-row element k of conv1_5 output (oy, ox) reads: its index, or
+// -1 for a padding tap or the K tail (written as zero).
+inline int64_t tdn_patch_source(int oy, int ox, int k, int hp, int wp) {
+  if (k < 0 || k >= kTdnPatchReal) return -1;
+  const int c = k % kTdnDiffC, kx = k / kTdnDiffC % 7, ky = k / kTdnDiffC / 7;
+  const int py = 2 * oy - 3 + ky, px = 2 * ox - 3 + kx;
+  if (py < 0 || py >= hp || px < 0 || px >= wp) return -1;
+  return ((int64_t)py * wp + px) * kTdnDiffC + c;
+}
+// conv1_5 [64, 12, 7, 7] + its BatchNorm -> [64][kTdnPatchK] in tdn_patch_k's order, the K tail zero.
+inline void tdn_pack_conv15(const float *w, const float *gamma, const float *beta, const float *mean, const float *var, int cout,
+                            std::vector<float> *wp, std::vector<float> *bias) {
+  wp->assign((size_t)cout * kTdnPatchK, 0.f);
+  bias->resize(cout);
+  for (int o = 0; o < cout; ++o) {
+    const float scale = gamma[o] / std::sqrt(var[o] + kBnEps);
+    (*bias)[o] = beta[o] - mean[o] * scale;
+    for (int c = 0; c < kTdnDiffC; ++c)
+      for (int ky = 0; ky < 7; ++ky)
+        for (int kx = 0; kx < 7; ++kx)
+          (*wp)[(size_t)o * kTdnPatchK + tdn_patch_k(ky, kx, c)] = w[(((size_t)o * kTdnDiffC + c) * 7 + ky) * 7 + kx] * scale;
+  }
+}
+// A conv bias in front of a BatchNorm: BN(conv(x) + b) = conv(x) * s + (beta + (b - mean) * s), i.e. the same BatchNorm with the
+// running mean moved by b.  Returns mean - b, which the bias-free folds (fold_and_pack, the stem's) then take as their mean.
+inline std::vector<float> tdn_mean_less_bias(const float *mean, const float *cbias, int cout) {
+  std::vector<float> m(cout);
+  for (int o = 0; o < cout; ++o) m[o] = mean[o] - cbias[o];
+  return m;
+}
+// The mSE module's weights as its kernels read them (tsm_tdn.hip), every BatchNorm folded into a scale on the weights and a bias.
+//   squeeze  mse.conv1 [r, C, 1, 1] + bn1          -> wq [C][r] (output channel fastest), bq [r]
+//   dw       mse.conv2 [r, 1, 3, 3]                -> [9][r], tap-major (ky, kx)
+//   k2 / k4  mse.conv3_smallscale{2,4} [r, r, 3, 3] + their bn -> [9][r in][r out], bias [r]
+//   excite   mse.conv3 [C, r, 1, 1] + bn3          -> [C][r], bias [C]
+//   temporal shift.conv.weight [C, 1, 3]           -> [3][C], tap-major
+struct TdnMseWeights {
+  std::vector<float> wq, bq, dw, k2, b2, k4, b4, w3, b3, wt;
+};
+inline void tdn_bn_fold(const float *bn, int c, std::vector<float> *scale, std::vector<float> *bias) {   // bn = [gamma | beta | mean | var], c each
+  scale->resize(c);
+  bias->resize(c);
+  for (int o = 0; o < c; ++o) {
+    (*scale)[o] = bn[o] / std::sqrt(bn[3 * (size_t)c + o] + kBnEps);
+    (*bias)[o] = bn[(size_t)c + o] - bn[2 * (size_t)c + o] * (*scale)[o];
+  }
+}
+inline void tdn_pack_mse(int C, const float *conv1, const float *bn1, const float *conv2, const float *k2, const float *bn2, const float *k4,
+                         const float *bn4, const float *conv3, const float *bn3, const float *shift_w, TdnMseWeights *out) {
+  const int r = C / kTdnReduction;
+  std::vector<float> s;
+  tdn_bn_fold(bn1, r, &s, &out->bq);
+  out->wq.assign((size_t)C * r, 0.f);
+  for (int j = 0; j < r; ++j)
+    for (int c = 0; c < C; ++c) out->wq[(size_t)c * r + j] = conv1[(size_t)j * C + c] * s[j];
+  out->dw.assign((size_t)9 * r, 0.f);
+  for (int j = 0; j < r; ++j)
+    for (int t = 0; t < 9; ++t) out->dw[(size_t)t * r + j] = conv2[(size_t)j * 9 + t];
+  for (int which = 0; which < 2; ++which) {
+    const float *k = which ? k4 : k2;
+    std::vector<float> &kp = which ? out->k4 : out->k2;
+    tdn_bn_fold(which ? bn4 : bn2, r, &s, which ? &out->b4 : &out->b2);
+    kp.assign((size_t)9 * r * r, 0.f);
+    for (int j = 0; j < r; ++j)
+      for (int i = 0; i < r; ++i)
+        for (int t = 0; t < 9; ++t) kp[((size_t)t * r + i) * r + j] = k[((size_t)j * r + i) * 9 + t] * s[j];
+  }
+  tdn_bn_fold(bn3, C, &s, &out->b3);
+  out->w3.assign((size_t)C * r, 0.f);
+  for (int c = 0; c < C; ++c)
+    for (int i = 0; i < r; ++i) out->w3[(size_t)c * r + i] = conv3[(size_t)c * r + i] * s[c];
+  out->wt.assign((size_t)3 * C, 0.f);
+  for (int c = 0; c < C; ++c)
+    for (int t = 0; t < 3; ++t) out->wt[(size_t)t * C + c] = shift_w[(size_t)c * 3 + t];
+}
+
 // Tuned tile shapes are cached per power-of-two bucket of the clip count (ragged last batches of a video
 // would otherwise each pay a tuning pass): the first clip count that lands in a bucket tunes it.
 inline int tile_bucket(int n_clips) {

@@ -197,6 +197,28 @@ hipError_t launch_stem_pack4(const float *x, float *y, int n, int h, int w, hipS
 // exact GELU in place over n4 16-byte quads
 hipError_t launch_gelu(float *x, int64_t n4, hipStream_t s);
 
+// TDN-ResNet50 (tsm_tdn.hip), fp32 NHWC.  The mSE launches take conv1's width c in {128, 256, 512} (r = c / 16 channels in
+// between); anything else hipErrorInvalidValue, nothing launched.  Weight layouts: tsm_host::tdn_pack_mse.
+// front: x [n, 15, h, w] (h, w multiples of 32, >= 64; n <= 65535) -> in4 [n, h, w, 4] (the centre frame, packed) and the patch
+// rows of conv1_5 [n * h / 4 * w / 4][tsm_host::kTdnPatchK]
+hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_frames, int h, int w, hipStream_t s);
+// x [n, h, w, c] <- alpha x + beta nearest-upsampled d [n, hd, wd, c], in place
+hipError_t launch_tdn_fuse(float *x, const float *d, int n, int h, int w, int hd, int wd, int c, float alpha, float beta, hipStream_t s);
+// b [m, r] = BN(W1 x), x [m, c]
+hipError_t launch_mse_squeeze(const float *x, const float *wq, const float *bq, float *b, int64_t m, int c, hipStream_t s);
+// d+ / d- [n, h, w, r] and their 2x2 average pools pf / pb [n, h / 2, w / 2, r] from b; n = clips * T
+hipError_t launch_mse_diff(const float *b, const float *dw, float *df, float *db, float *pf, float *pb, int n_frames, int T, int h, int w,
+                           int c, hipStream_t s);
+// s2 = BN(K2 * pooled d) on the pooled map, both directions
+hipError_t launch_mse_s2(const float *pf, const float *pb, const float *k2, const float *b2, float *sf, float *sb, int n_frames, int hp, int wp,
+                         int c, hipStream_t s);
+// m = d / 3 + up(s2) / 3 + BN(K4 * d) / 3, both directions
+hipError_t launch_mse_mix(const float *df, const float *db, const float *s2f, const float *s2b, const float *k4, const float *b4, float *mf,
+                          float *mb, int n_frames, int h, int w, int c, hipStream_t s);
+// o = temporal conv of g = x + x y, y from e = BN(W3 m); x, o [n_clips * T, hw, c]; n_clips <= 65535
+hipError_t launch_mse_excite_shift(const float *x, const float *mf, const float *mb, const float *w3, const float *b3, const float *wt, float *o,
+                                   int n_clips, int T, int hw, int c, hipStream_t s);
+
 // K9: per clip, (softmax,) first arg-max, class id if its score >= threshold else -1; top (nullable) = that score.
 hipError_t launch_scores_to_states(const float *logits, int n, int c, int softmax, float threshold, int *states, float *top,
                                    hipStream_t s);

@@ -23,9 +23,9 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .weights import (BACKBONES, CONVNEXT, CONVNEXT_DEPTHS, CONVNEXT_WIDTHS, DEPTHS, NL_BLOCKS, SHIFT_PLACES, WIDTHS, _convnext_depths,
-                      feature_width, is_convnext, is_mmaction_state_dict, make_state_dict, remap_checkpoint_keys, remap_mmaction_keys,
-                      remap_timm_keys, remap_torchvision_keys)
+from .weights import (BACKBONES, CONVNEXT, CONVNEXT_DEPTHS, CONVNEXT_WIDTHS, DEPTHS, NL_BLOCKS, SHIFT_PLACES, TDN, TDN_FRAMES, WIDTHS,
+                      _convnext_depths, _tdn_depths, feature_width, is_convnext, is_mmaction_state_dict, make_state_dict, make_tdn_state_dict,
+                      remap_checkpoint_keys, remap_mmaction_keys, remap_tdn_keys, remap_timm_keys, remap_torchvision_keys, tdn_alpha_beta)
 
 CONSENSUS_TYPES = {'avg': 0, 'identity': 1}      # tsm_set_consensus
 
@@ -50,17 +50,27 @@ class TsmEngine:
                  shift_div: int = 8, is_shift: bool = True, max_clips: int = 32, device: int = 0,
                  state_dict: Optional[Mapping[str, object]] = None, dtype: str = 'f32',
                  base_model: str = 'resnet50', shift_place: str = 'blockres', consensus_type: str = 'avg',
-                 non_local: bool = False, temporal_pool: bool = False, convnext_depths: Optional[Sequence[int]] = None):
+                 non_local: bool = False, temporal_pool: bool = False, convnext_depths: Optional[Sequence[int]] = None,
+                 tdn_depths: Optional[Sequence[int]] = None, tdn_alpha: Optional[float] = None, tdn_beta: Optional[float] = None):
         # base_model='convnext_base' (include/tsm_hip.h: tsm_set_convnext): an image model -- num_segments=1, is_shift=False,
         # dtype='f32' -- of ``convnext_depths`` blocks per stage, (3, 3, 27, 3) unless given (tests build shallow engines).
-        convnext = is_convnext(base_model)
-        if convnext:      # every refusal before the library loads
+        # base_model='tdn_resnet50' (include/tsm_hip.h: tsm_set_tdn): clips of 15 planes per segment, is_shift=False, dtype='f32',
+        # ``tdn_depths`` blocks per stage, (3, 4, 6, 3) unless given; ``tdn_alpha`` / ``tdn_beta`` default to tdn_net's rule.
+        tdn = base_model == TDN
+        convnext = not tdn and is_convnext(base_model)
+        if tdn:           # every refusal before the library loads
+            tdn_depths = _check_tdn(tdn_depths, num_segments, is_shift, dtype, height, width, shift_place, non_local, temporal_pool)
+            if tdn_alpha is None or tdn_beta is None:
+                tdn_alpha, tdn_beta = tdn_alpha_beta(num_segments)
+        elif tdn_depths is not None or tdn_alpha is not None or tdn_beta is not None:
+            raise ValueError(f'tdn_depths= / tdn_alpha= / tdn_beta= go with base_model={TDN!r} only')
+        if convnext:
             convnext_depths = _check_convnext(convnext_depths, num_segments, is_shift, dtype, shift_place, non_local, temporal_pool)
         elif convnext_depths is not None:
             raise ValueError(f'convnext_depths= goes with base_model={CONVNEXT!r} only')
-        elif base_model not in DEPTHS:
+        elif not tdn and base_model not in DEPTHS:
             raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
-        if not convnext:
+        if not convnext and not tdn:
             _check_non_local(non_local, base_model, dtype)
         _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
         if shift_place not in SHIFT_PLACES:
@@ -81,7 +91,9 @@ class TsmEngine:
         self.non_local = bool(non_local)
         self.temporal_pool = bool(temporal_pool)
         self.convnext_depths = convnext_depths      # None for a ResNet engine
-        self.feature_dim = feature_width(base_model)      # row width of forward_features
+        self.tdn_depths = tdn_depths                # None unless a TDN engine
+        self.planes = 3 * TDN_FRAMES if tdn else 3  # input planes per segment
+        self.feature_dim = 2048 if tdn else feature_width(base_model)      # row width of forward_features
         # layout tsm_preprocess must write for this engine to consume frames in place
         self.packed_layout = {'f32': _lib.LAYOUT_NTHWC4, 'bf16x3': _lib.LAYOUT_NTHWC8S,
                               'bf16': _lib.LAYOUT_NTHWC8B}[dtype]
@@ -90,6 +102,8 @@ class TsmEngine:
         _lib.check(self._lib.tsm_create(C.byref(cfg), C.byref(self._h)))
         if convnext:
             _lib.check(self._lib.tsm_set_convnext(self._h, (C.c_int32 * 4)(*convnext_depths)), self._h)
+        elif tdn:
+            _lib.check(self._lib.tsm_set_tdn(self._h, (C.c_int32 * 4)(*tdn_depths), float(tdn_alpha), float(tdn_beta)), self._h)
         elif DEPTHS[base_model] != 50:
             _lib.check(self._lib.tsm_set_backbone(self._h, DEPTHS[base_model]), self._h)
         if base_model in WIDTHS:
@@ -126,7 +140,7 @@ class TsmEngine:
 
     # ---- onnxruntime.InferenceSession duck type ---------------------------------------------------
     def get_inputs(self) -> List[NodeArg]:
-        return [NodeArg(self.INPUT_NAME, [None, self.num_segments, 3, self.height, self.width])]
+        return [NodeArg(self.INPUT_NAME, [None, self.num_segments, self.planes, self.height, self.width])]
 
     def get_outputs(self) -> List[NodeArg]:
         return [NodeArg(self.OUTPUT_NAME, [None] + list(self._out_shape(0)[1:]))]
@@ -149,9 +163,11 @@ class TsmEngine:
         if set(input_feed) != {self.INPUT_NAME}:
             raise ValueError(f'feed must have exactly the key {self.INPUT_NAME!r}, got {sorted(input_feed)}')
         x = input_feed[self.INPUT_NAME]
-        want = (self.num_segments, 3, self.height, self.width)
+        want = (self.num_segments, self.planes, self.height, self.width)
+        if self.tdn_depths and x.ndim == 6 and tuple(x.shape[1:]) == (want[0], TDN_FRAMES, 3) + want[2:]:
+            x = x.reshape((x.shape[0],) + want)
         if x.ndim != 5 or tuple(x.shape[1:]) != want:
-            raise ValueError(f'input must be [B,{want[0]},3,{want[2]},{want[3]}], got {tuple(x.shape)}')
+            raise ValueError(f'input must be [B,{want[0]},{want[1]},{want[2]},{want[3]}], got {tuple(x.shape)}')
         return [self.forward_host(_as_f32(x))]
 
     # ---- nn.Module duck type ----------------------------------------------------------------------
@@ -160,18 +176,23 @@ class TsmEngine:
         returns logits [B,num_class] ([B,T,num_class] with consensus_type='identity') of the same kind."""
         is_torch = hasattr(x, 'is_cuda')
         shape = tuple(x.shape)
-        if len(shape) == 4:
-            if shape[0] % self.num_segments or shape[1:] != (3, self.height, self.width):
-                raise ValueError(f'input must be [B*{self.num_segments},3,{self.height},{self.width}], got {shape}')
+        hw, p = (self.height, self.width), self.planes
+        if len(shape) == 4 and shape[1:] == (p,) + hw and shape[0] % self.num_segments == 0:
             b = shape[0] // self.num_segments
-        elif len(shape) == 5 and shape[1:] == (self.num_segments, 3, self.height, self.width):
+        elif len(shape) == 4 and self.tdn_depths and shape[1:] == (3,) + hw and shape[0] % (self.num_segments * TDN_FRAMES) == 0:
+            b = shape[0] // (self.num_segments * TDN_FRAMES)      # [B*T*5, 3, H, W]: the same memory (the reference's reshape)
+        elif len(shape) == 4:
+            raise ValueError(f'input must be [B*{self.num_segments},{p},{self.height},{self.width}], got {shape}')
+        elif len(shape) == 5 and shape[1:] == (self.num_segments, p) + hw:
+            b = shape[0]
+        elif len(shape) == 6 and self.tdn_depths and shape[1:] == (self.num_segments, TDN_FRAMES, 3) + hw:
             b = shape[0]
         else:
             raise ValueError(f'bad input shape {shape}')
         if is_torch and x.is_cuda:
-            return self.forward_device(x.reshape(b, self.num_segments, 3, self.height, self.width))
+            return self.forward_device(x.reshape(b, self.num_segments, p, self.height, self.width))
         arr = _as_f32(x.detach().numpy() if is_torch else x)
-        out = self.forward_host(arr.reshape(b, self.num_segments, 3, self.height, self.width))
+        out = self.forward_host(arr.reshape(b, self.num_segments, p, self.height, self.width))
         if is_torch:
             import torch
             return torch.from_numpy(out)
@@ -187,7 +208,7 @@ class TsmEngine:
     def _floats_per_clip(self, layout: int) -> int:
         """float32 slots one clip occupies in ``layout`` (the C ABI takes bare pointers: sizes are checked here)."""
         t, h, w = self.num_segments, self.height, self.width
-        per = {_lib.LAYOUT_NTCHW: 3 * h * w, _lib.LAYOUT_NTHWC: 3 * h * w, _lib.LAYOUT_NTHWC4: 4 * h * w,
+        per = {_lib.LAYOUT_NTCHW: self.planes * h * w, _lib.LAYOUT_NTHWC: 3 * h * w, _lib.LAYOUT_NTHWC4: 4 * h * w,
                _lib.LAYOUT_NTHWC8S: 8 * h * ((w + 1) // 2), _lib.LAYOUT_NTHWC8B: 4 * h * ((w + 1) // 2)}
         if layout not in per:
             raise ValueError(f'unknown layout {layout}')
@@ -318,6 +339,19 @@ class TsmEngine:
     def launch_names(self) -> List[str]:
         """Names of the kernel launches of one forward, in launch order (matches tsm_layer_times).  A non-local engine's
         wrapped blocks add four: the theta | phi | g conv, the pool, the attention and the W conv."""
+        if self.tdn_depths:           # (csrc/tsm_engine.hip, run_tdn: one front + conv1_5 pair per chunk the engine's capacity holds)
+            names = []
+            for i in range(-(-self.max_clips // self.tdn_chunk_clips)):
+                names += [f'diff.front.{i}', f'diff.conv1_5.{i}']
+            names += ['diff.maxpool', 'conv1', 'fuse1']
+            for li, nb in zip(range(5), (self.tdn_depths[0],) + tuple(self.tdn_depths)):      # 0: resnext_layer1
+                for b in range(nb):
+                    p = f'resnext_layer1.{b}' if li == 0 else f'layer{li}.{b}'
+                    names += ['fuse2'] if (li, b) == (2, 0) else []
+                    names += ([p + '.downsample'] if b == 0 else []) + [p + '.conv1']
+                    names += [p + part for part in ('.mse_squeeze', '.mse_diff', '.mse_s2', '.mse_mix', '.mse_excite_shift')] if li >= 2 else []
+                    names += [p + '.conv2', p + '.conv3']
+            return names + ['head']
         if self.convnext_depths:      # (csrc/tsm_engine.hip, run_convnext)
             names = ['pack_input', 'stem.pack', 'stem.conv', 'stem.norm']
             for s, nb in enumerate(self.convnext_depths):
@@ -339,6 +373,13 @@ class TsmEngine:
             if self.temporal_pool and li == 1:      # the pool's own launch, behind layer1's last block
                 names.append('layer2.tpool')
         return names + ['head']
+
+    @property
+    def tdn_chunk_clips(self) -> int:
+        """Clips per front-end chunk of a TDN engine (tsm_host_util.h: tdn_chunk_clips): at most 8, and few enough that the patch
+        rows of a chunk stay below 2^29 floats."""
+        per_clip = (self.height // 4) * (self.width // 4) * self.num_segments * 1024
+        return max(1, min(8, self.max_clips, ((1 << 29) - 1) // per_clip))
 
     TILE_NAMES = {0: 'heuristic', 1: '128x128', 2: '128x64', 3: '64x64', 4: '32x32', 5: '128x128w8', 6: '256x256', 7: 'ws',
                   8: '256x256p'}
@@ -362,6 +403,11 @@ class TsmEngine:
         buf = (C.c_int32 * 256)()
         n = C.c_int32()
         _lib.check(self._lib.tsm_conv_tiles(self._h, n_clips, buf, 256, C.byref(n)), self._h)
+        if self.tdn_depths:           # the stem, conv1_5 (one layer, whatever the chunks), then every block's convs
+            names = ['conv1', 'diff.conv1_5'] + [k for k in self.launch_names() if k.startswith(('resnext_layer1.', 'layer'))
+                                                 and k.endswith(('.downsample', '.conv1', '.conv2', '.conv3'))]
+            assert n.value == len(names)
+            return {k: self.tile_name(buf[i]) for i, k in enumerate(names)}
         if self.convnext_depths:
             names = [k for k in self.launch_names() if k == 'stem.conv' or k.endswith(('.downsample', '.fc1', '.fc2'))]
             assert n.value == len(names)
@@ -414,6 +460,64 @@ def _check_convnext(depths, num_segments: int, is_shift: bool, dtype: str, shift
     if non_local or temporal_pool or shift_place != 'blockres':
         raise NotImplementedError(f'{CONVNEXT} has no non_local / temporal_pool / shift_place')
     return _convnext_depths(depths)
+
+
+def _check_tdn(depths, num_segments: int, is_shift: bool, dtype: str, height: int, width: int, shift_place: str = 'blockres',
+               non_local: bool = False, temporal_pool: bool = False):
+    """``base_model='tdn_resnet50'``: fp32 only, no TSM shift, at least two segments, sides that are multiples of 32 and at least
+    64.  Everything else is refused up front, never ignored; returns the stage depths ((3, 4, 6, 3) unless given)."""
+    if dtype != 'f32':
+        if dtype in _lib.DTYPES:
+            raise NotImplementedError(f"{TDN} runs in dtype='f32' only, not {dtype!r}")
+        raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
+    if is_shift:
+        raise ValueError(f'{TDN} has no TSM shift (its temporal conv is learned): pass is_shift=False')
+    if non_local or temporal_pool or shift_place != 'blockres':
+        raise NotImplementedError(f'{TDN} has no non_local / temporal_pool / shift_place')
+    if num_segments < 2:
+        raise ValueError(f'{TDN} needs num_segments >= 2, got {num_segments}')
+    if height < 64 or width < 64 or height % 32 or width % 32:
+        raise ValueError(f'{TDN} needs height and width that are multiples of 32 and at least 64, got {height} x {width}')
+    return _tdn_depths(depths)
+
+
+def create_tdn_model(num_class: int, num_segments: int = 8, base_model: str = 'resnet50', num_frames: int = 5,
+                     checkpoint: Optional[str] = None, consensus_type: str = 'avg', dropout: float = 0.5, partial_bn: bool = False,
+                     fc_lr5: bool = False, device: Optional[object] = None, height: int = 224, width: int = 224, max_clips: int = 32,
+                     seed: int = 0, dtype: str = 'f32', depths: Optional[Sequence[int]] = None, **kwargs) -> 'TsmEngine':
+    """Counterpart of the reference's TDN factory (models/tdn.py:20-73: ``TSN(backbone_fn=tdn_net)``) returning a ready
+    ``TsmEngine(base_model='tdn_resnet50', tdn_depths=(3, 4, 6, 3))`` with tdn_net's blend weights (0.5 / 0.5 at eight segments,
+    else 0.75 / 0.25).  The engine takes [B, T, 5, 3, H, W], [B, T, 15, H, W] or [B*T*5, 3, H, W] -- one memory layout.
+    ``checkpoint``: a ``torch.save``d TDN checkpoint (``weights.remap_tdn_keys``: ``state_dict`` wrapper, ``module.`` prefix and
+    ``.net`` spellings as the reference's loader takes them; a ``new_fc`` of another class count raises).  Without one the engine
+    gets the seeded weights of ``weights.make_tdn_state_dict``.  ``dropout`` / ``partial_bn`` / ``fc_lr5`` are training options.
+    NotImplementedError, before the library loads: ``base_model='resnet101'`` (or anything but 'resnet50'), the bf16 formats, an
+    ``.onnx`` file, ``num_frames != 5``.  ``depths``: blocks per stage of a shallower engine (tests)."""
+    if base_model != 'resnet50':
+        raise NotImplementedError(f'TDN on {base_model}: the engine implements resnet50 (depths 3, 4, 6, 3) only')
+    if num_frames != TDN_FRAMES:
+        raise NotImplementedError(f'num_frames must be {TDN_FRAMES} (four differences around the centre frame), got {num_frames}')
+    if dtype != 'f32' and dtype in _lib.DTYPES:
+        raise NotImplementedError(f"{TDN} runs in dtype='f32' only, not {dtype!r}")
+    if checkpoint is not None and str(checkpoint).endswith('.onnx'):
+        raise NotImplementedError('a TDN .onnx file: the importer reads TSM graphs only')
+    assert consensus_type in ['avg', 'identity']
+    depths = _tdn_depths(depths)
+    dev = 0
+    if device is not None:
+        s = str(device)
+        if s == 'cpu':
+            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
+        dev = int(s.split(':')[1]) if ':' in s else 0
+    if checkpoint is not None:
+        import torch
+        sd = remap_tdn_keys(torch.load(checkpoint, map_location='cpu'), num_class, depths)
+    else:
+        sd = make_tdn_state_dict(seed=seed, num_class=num_class, depths=depths)
+    alpha, beta = tdn_alpha_beta(num_segments)
+    return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width, is_shift=False, max_clips=max_clips,
+                     device=dev, state_dict=sd, dtype=dtype, base_model=TDN, consensus_type=consensus_type, tdn_depths=depths,
+                     tdn_alpha=alpha, tdn_beta=beta)
 
 
 def _check_non_local(non_local: bool, base_model: str, dtype: str) -> None:

@@ -54,6 +54,52 @@ def layer_table(height: int = 224, width: int = 224, base_model: str = 'resnet50
     return rows
 
 
+def tdn_table(height: int = 224, width: int = 224, depths=None) -> List[Dict[str, int]]:
+    """TDN-ResNet50's rows per SEGMENT (five input frames), the same columns as ``layer_table``: the trunk's stem, conv1_5 (its 588
+    real K values, not the padded 1024 of its GEMM), resnext_layer1's and layer1's Bottlenecks and the BottleneckShift blocks of
+    layers 2-4, each with its long-term module: the squeeze (C -> r = C / 16), the depthwise 3x3 (``cin`` = 1), the two full 3x3
+    r -> r convs for both directions (``smallscale2`` on the pooled map), the excite (r -> C, both directions) and the 3-tap
+    temporal conv.  Differences, pools, blends, the sigmoid and BatchNorm count zero MACs."""
+    from .weights import EXPANSION, R50_PLANES, _tdn_depths
+    d = _tdn_depths(depths)
+    h1, w1 = _out(height, 7, 2), _out(width, 7, 2)
+    rows: List[Dict[str, int]] = [dict(name='conv1', cin=3, cout=64, k=7, s=2, m=h1 * w1, macs=h1 * w1 * 64 * 3 * 49)]
+    h5, w5 = _out(height // 2, 7, 2), _out(width // 2, 7, 2)
+    rows.append(dict(name='diff.conv1_5', cin=12, cout=64, k=7, s=2, m=h5 * w5, macs=h5 * w5 * 64 * 12 * 49))
+    for li in range(0, 5):      # 0: resnext_layer1, on the maps of xd0
+        stage = max(li, 1) - 1
+        planes, cout = R50_PLANES[stage], R50_PLANES[stage] * EXPANSION
+        cin = 64 if stage == 0 else R50_PLANES[stage - 1] * EXPANSION
+        if li == 0:
+            h, w = _out(h5, 3, 2), _out(w5, 3, 2)
+        elif li == 1:
+            h, w = _out(h1, 3, 2), _out(w1, 3, 2)
+        for b in range(d[stage]):
+            p = f'resnext_layer1.{b}' if li == 0 else f'layer{li}.{b}'
+            s = 2 if (b == 0 and stage > 0) else 1
+            ho, wo = _out(h, 3, s), _out(w, 3, s)
+            rows.append(dict(name=p + '.conv1', cin=cin, cout=planes, k=1, s=1, m=h * w, macs=h * w * planes * cin))
+            if li >= 2:
+                r, mp = planes // 16, (h // 2) * (w // 2)
+                rows.append(dict(name=p + '.mse.conv1', cin=planes, cout=r, k=1, s=1, m=h * w, macs=h * w * r * planes))
+                rows.append(dict(name=p + '.mse.conv2', cin=1, cout=r, k=3, s=1, m=h * w, macs=h * w * r * 9))
+                rows.append(dict(name=p + '.mse.conv3_smallscale2', cin=r, cout=r, k=3, s=1, m=2 * mp, macs=2 * mp * r * r * 9))
+                rows.append(dict(name=p + '.mse.conv3_smallscale4', cin=r, cout=r, k=3, s=1, m=2 * h * w, macs=2 * h * w * r * r * 9))
+                rows.append(dict(name=p + '.mse.conv3', cin=r, cout=planes, k=1, s=1, m=2 * h * w, macs=2 * h * w * planes * r))
+                rows.append(dict(name=p + '.shift.conv', cin=1, cout=planes, k=3, s=1, m=h * w, macs=h * w * planes * 3, one_d=True))      # (3 taps over time)
+            rows.append(dict(name=p + '.conv2', cin=planes, cout=planes, k=3, s=s, m=ho * wo, macs=ho * wo * planes * planes * 9))
+            rows.append(dict(name=p + '.conv3', cin=planes, cout=cout, k=1, s=1, m=ho * wo, macs=ho * wo * cout * planes))
+            if b == 0:
+                rows.append(dict(name=p + '.downsample', cin=cin, cout=cout, k=1, s=s, m=ho * wo, macs=ho * wo * cout * cin))
+            cin, h, w = cout, ho, wo
+    return rows
+
+
+def tdn_flops_per_clip(num_segments: int = 8, height: int = 224, width: int = 224, num_class: int = 12, depths=None) -> float:
+    """FLOPs of one TDN clip: ``tdn_table`` and the classifier, per segment, times ``num_segments``."""
+    return 2.0 * num_segments * (sum(r['macs'] for r in tdn_table(height, width, depths)) + 2048 * num_class)
+
+
 def macs_per_frame(height: int = 224, width: int = 224, num_class: int = 12, base_model: str = 'resnet50') -> int:
     return sum(r['macs'] for r in layer_table(height, width, base_model)) + feature_width(base_model) * num_class
 
@@ -81,8 +127,13 @@ def nonlocal_table(num_segments: int = 8, height: int = 224, width: int = 224, b
 def flops_per_clip(num_segments: int = 8, height: int = 224, width: int = 224, num_class: int = 12,
                    base_model: str = 'resnet50', non_local: bool = False, temporal_pool: bool = False) -> float:
     """``temporal_pool=True`` (``create_model(temporal_pool=True)``): the stem and layer1 run on all ``num_segments`` frames of a
-    clip, layers 2-4 and the classifier on the ``num_segments // 2`` frames the pool leaves; the pool itself counts zero FLOPs."""
-    nl = sum(r['conv_macs'] + r['attn_macs'] for r in nonlocal_table(num_segments, height, width, base_model)) if non_local else 0
+    clip, layers 2-4 and the classifier on the ``num_segments // 2`` frames the pool leaves; the pool itself counts zero FLOPs.
+    ``base_model='tdn_resnet50'``: ``tdn_flops_per_clip`` (full depth)."""
+    if base_model == 'tdn_resnet50':
+        if non_local or temporal_pool:
+            raise ValueError('tdn_resnet50 has no non_local / temporal_pool')
+        return tdn_flops_per_clip(num_segments, height, width, num_class)
+    nl =sum(r['conv_macs'] + r['attn_macs'] for r in nonlocal_table(num_segments, height, width, base_model)) if non_local else 0
     if not temporal_pool:
         return 2.0 * (macs_per_frame(height, width, num_class, base_model) * num_segments + nl)
     if non_local or num_segments <= 0 or num_segments % 2:

@@ -104,7 +104,11 @@ def make_clip(video_thwc_u8: torch.Tensor, start: int) -> torch.Tensor:
 def need_clip_rows(model, where: str) -> None:
     """The pipelines here take ONE row of scores per clip: refuse a model that returns one per segment up front (an engine
     built with consensus_type='identity', logits [B, T, num_class]) instead of failing later on a shape.  Sessions and
-    stubs without the attribute are 'avg'."""
+    stubs without the attribute are 'avg'.  They also build clips of ONE frame per segment: a TDN engine, which takes five, is
+    refused here too (NotImplementedError), never run on the wrong input."""
+    if getattr(model, 'tdn_depths', None):
+        raise NotImplementedError(f'{where} builds clips of one frame per segment; a TDN engine takes five ([B, T, 5, 3, H, W]): '
+                                  'call the engine on clips you assemble yourself')
     consensus = getattr(model, 'consensus_type', 'avg')
     if consensus != 'avg':
         raise ValueError(f"{where} needs one row of scores per clip: the model was built with consensus_type={consensus!r} "

@@ -239,6 +239,119 @@ def remap_timm_keys(state_dict: Mapping[str, object]) -> 'OrderedDict[str, objec
     return out
 
 
+# TDN-ResNet50 (models/tdn.py: TSN(backbone_fn=tdn_net)) -> tsm_set_tdn.  The keys are the TSN module's; include/tsm_hip.h holds the
+# network's definition.
+TDN = 'tdn_resnet50'
+TDN_DEPTHS = R50_BLOCKS
+TDN_FRAMES = 5
+
+
+def _tdn_depths(depths) -> Tuple[int, int, int, int]:
+    d = tuple(int(v) for v in (TDN_DEPTHS if depths is None else depths))
+    if len(d) != 4 or any(v < 1 or v > 64 for v in d):
+        raise ValueError(f'tdn depths must be four stage depths in 1 .. 64, got {depths!r}')
+    return d
+
+
+def tdn_alpha_beta(num_segments: int) -> Tuple[float, float]:
+    """tdn_net's blend weights: 0.5, 0.5 at eight segments, else 0.75, 0.25 (models/tdn.py:189-192)."""
+    return (0.5, 0.5) if num_segments == 8 else (0.75, 0.25)
+
+
+def tdn_specs(depths=None) -> List[Tuple[str, Tuple[int, ...], str]]:
+    """(key, shape, kind) of every tensor the engine reads from a TDN ``state_dict``, without the classifier
+    (``new_fc.{weight [num_class, 2048], bias}``).  kind: ``conv`` (a 2-d conv weight), ``bias`` (a conv bias), ``bn_w`` / ``bn_b`` /
+    ``bn_m`` / ``bn_v`` (a BatchNorm's weight, bias, running mean and variance), ``temporal`` (``shift.conv.weight`` [C, 1, 3])."""
+    specs: List[Tuple[str, Tuple[int, ...], str]] = []
+
+    def conv(key, cout, cin, k, bias=True, groups=1):
+        specs.append((key + '.weight', (cout, cin // groups, k, k), 'conv'))
+        if bias:
+            specs.append((key + '.bias', (cout,), 'bias'))
+
+    def bn(key, c):
+        specs.extend((key + s, (c,), kind) for s, kind in (('.weight', 'bn_w'), ('.bias', 'bn_b'), ('.running_mean', 'bn_m'), ('.running_var', 'bn_v')))
+
+    conv('base_model.conv1', 64, 3, 7)
+    bn('base_model.bn1', 64)
+    conv('base_model.conv1_5.0', 64, 12, 7, bias=False)
+    bn('base_model.conv1_5.1', 64)
+    d = _tdn_depths(depths)
+    for li in range(0, 5):      # 0: resnext_layer1
+        stage = max(li, 1) - 1
+        planes, cout = R50_PLANES[stage], R50_PLANES[stage] * EXPANSION
+        cin = 64 if stage == 0 else R50_PLANES[stage - 1] * EXPANSION
+        for b in range(d[stage]):
+            p = f'base_model.resnext_layer1.{b}' if li == 0 else f'base_model.layer{li}_bak.{b}'
+            conv(p + '.conv1', planes, cin, 1)
+            bn(p + '.bn1', planes)
+            if li >= 2:
+                r = planes // 16
+                conv(p + '.mse.conv1', r, planes, 1, bias=False)
+                bn(p + '.mse.bn1', r)
+                conv(p + '.mse.conv2', r, r, 3, bias=False, groups=r)
+                conv(p + '.mse.conv3', planes, r, 1, bias=False)
+                bn(p + '.mse.bn3', planes)
+                for sc in ('2', '4'):
+                    conv(p + '.mse.conv3_smallscale' + sc, r, r, 3, bias=False)
+                    bn(p + '.mse.bn3_smallscale' + sc, r)
+                specs.append((p + '.shift.conv.weight', (planes, 1, 3), 'temporal'))
+            conv(p + '.conv2', planes, planes, 3)
+            bn(p + '.bn2', planes)
+            conv(p + '.conv3', cout, planes, 1)
+            bn(p + '.bn3', cout)
+            if b == 0:
+                conv(p + '.downsample.0', cout, cin, 1)
+                bn(p + '.downsample.1', cout)
+            cin = cout
+    return specs
+
+
+def make_tdn_state_dict(seed: int = 0, num_class: int = 12, depths=None) -> 'OrderedDict[str, np.ndarray]':
+    """A seeded TDN state dict (numpy, torch layouts), drawn in sorted key order from ``np.random.default_rng(seed)``: conv weights
+    N(0, sqrt(2 / (k * k * cout))) (FBResNet's init), conv biases N(0, 0.1), BatchNorm weight and variance U(0.5, 1.5), bias and mean
+    N(0, 0.1), temporal weights N(0, 0.5), ``new_fc`` N(0, 0.05) / N(0, 0.1)."""
+    specs = tdn_specs(depths) + [('new_fc.weight', (num_class, R50_PLANES[-1] * EXPANSION), 'fc'), ('new_fc.bias', (num_class,), 'bias')]
+    rng = np.random.default_rng(seed)
+    sd: Dict[str, np.ndarray] = {}
+    for key, shape, kind in sorted(specs):
+        if kind == 'conv':
+            a = rng.standard_normal(shape) * np.sqrt(2.0 / (shape[2] * shape[3] * shape[0]))
+        elif kind in ('bn_w', 'bn_v'):
+            a = rng.uniform(0.5, 1.5, shape)
+        elif kind == 'temporal':
+            a = rng.standard_normal(shape) * 0.5
+        elif kind == 'fc':
+            a = rng.standard_normal(shape) * 0.05
+        else:
+            a = rng.standard_normal(shape) * 0.1
+        sd[key] = np.ascontiguousarray(a, dtype=np.float32)
+    return OrderedDict((k, sd[k]) for k, _s, _k in specs)
+
+
+def remap_tdn_keys(state_dict: Mapping[str, object], num_class: int, depths=None) -> 'OrderedDict[str, object]':
+    """A TDN checkpoint -> engine keys, which are the TSN module's own.  A ``state_dict`` wrapper is opened and a leading ``module.``
+    (DataParallel) stripped; a key that is unknown as it stands but known without its ``.net`` components is renamed, as the
+    reference's loader does (models/tdn.py:52-62).  ``base_model.conv1_temp.*`` and ``num_batches_tracked`` pass through (the engine
+    ignores them); keys of neither spelling are dropped, as ``load_state_dict`` of the reference's merged dict drops them.
+    A ``new_fc`` of another class count RAISES, naming both shapes: the reference would silently keep a random classifier."""
+    if 'state_dict' in state_dict and isinstance(state_dict['state_dict'], Mapping):
+        state_dict = state_dict['state_dict']
+    known = {k for k, _s, _k in tdn_specs(depths)} | {'new_fc.weight', 'new_fc.bias', 'base_model.conv1_temp.weight', 'base_model.conv1_temp.bias'}
+    out: 'OrderedDict[str, object]' = OrderedDict()
+    for k, v in state_dict.items():
+        name = k[len('module.'):] if k.startswith('module.') else k
+        if name not in known and name.replace('.net', '') in known:
+            name = name.replace('.net', '')
+        if name in known or name.endswith('num_batches_tracked'):
+            out[name] = v
+    want = (int(num_class), R50_PLANES[-1] * EXPANSION)
+    if 'new_fc.weight' in out and tuple(out['new_fc.weight'].shape) != want:
+        raise ValueError(f'new_fc.weight of the checkpoint is {list(out["new_fc.weight"].shape)}, the model needs {list(want)}: '
+                         'a classifier of another class count is not loaded')
+    return out
+
+
 def make_state_dict(seed: int = 0, num_class: int = 12, base_model: str = 'resnet50',
                     shift_place: str = 'blockres', non_local: bool = False, depths=None) -> 'OrderedDict[str, np.ndarray]':
     """Deterministic fp32 state dict (numpy arrays, torch layouts: conv OIHW, fc [cls, 2048] -- [cls, 512] for R18/R34).

@@ -4,9 +4,13 @@ tests/golden/ref_tdn.npz; the GPU tests then need neither the reference nor the 
 
     model = TDN(num_class, T, depths).double(); load(model, draw_weights(model, seed))
     logits, taps = model(x, taps=True)          # x [n_clips * T, 15, H, W]; taps are NHWC, under the engine's tap names
+
+build(..., recipe=f) applies a state-dict transform behind the draw (residual_gain, small_variance, gate_gain: the crafted networks
+of tests/_tdn_cases.py); its defaults are the fixture's network.
 """
 from __future__ import annotations
 
+import re
 from collections import OrderedDict
 
 import numpy as np
@@ -229,9 +233,63 @@ def make_input(seed: int, n_clips: int, T: int, H: int, W: int) -> np.ndarray:
     return np.random.default_rng([seed, n_clips, T, H, W]).standard_normal((n_clips * T, 15, H, W))
 
 
-def build(num_class: int, T: int, depths, seed: int, consensus: str = 'avg', dtype=torch.float64):
-    """The seeded model in ``dtype`` and its weights as float32 arrays (what an engine loads)."""
+def build(num_class: int, T: int, depths, seed: int, consensus: str = 'avg', dtype=torch.float64, recipe=None):
+    """The seeded model in ``dtype`` and its weights as float32 arrays (what an engine loads).  ``recipe``: a function of the
+    float32 weights that returns the float32 weights to use (residual_gain, small_variance, gate_gain below, or a composition)."""
     model = TDN(num_class, T, depths, consensus=consensus).to(dtype)
-    w = draw_weights(model, seed)
-    load(model, {k: np.asarray(v, dtype=np.float32) for k, v in w.items()})      # the model computes in `dtype` FROM the fp32 weights
-    return model, OrderedDict((k, np.asarray(v, dtype=np.float32)) for k, v in w.items())
+    w = OrderedDict((k, np.asarray(v, dtype=np.float32)) for k, v in draw_weights(model, seed).items())
+    if recipe is not None:
+        w = recipe(w)
+        assert all(v.dtype == np.float32 for v in w.values())
+    load(model, w)      # the model computes in `dtype` FROM the fp32 weights
+    return model, w
+
+
+# ---- recipes: state-dict transforms behind draw_weights, float32 in and float32 out ---------------------------------------------
+def _times(w, pattern: str, k: float):
+    out = OrderedDict(w)
+    hit = [key for key in w if re.search(pattern, key)]
+    assert hit, pattern
+    for key in hit:
+        out[key] = w[key] * np.float32(k)
+    return out
+
+
+def residual_gain(w, g: float):
+    """Every Block.bn3.weight (the residual branch's last BatchNorm, both paths; not the mSE's bn3) times g."""
+    return _times(w, r'\.\d+\.bn3\.weight$', g)
+
+
+def gate_gain(w, k: float):
+    """Every mse.bn3.weight and mse.bn3.bias times k: the gates' pre-activations e times k."""
+    return _times(w, r'\.mse\.bn3\.(weight|bias)$', k)
+
+
+def small_variance(w, seed: int):
+    """Every BatchNorm's running_var log-uniform in [1e-6, 1e-4] (np.random.default_rng(seed), sorted key order), as float32, and
+    its weight times sqrt(var + 1e-5) in float32: the folded scale keeps the size it had, and eps = 1e-5 is a tenth to ten times
+    the variance under the root."""
+    rng = np.random.default_rng(seed)
+    out = OrderedDict(w)
+    for key in sorted(w):
+        if not key.endswith('running_var'):
+            continue
+        var = np.exp(rng.uniform(np.log(1e-6), np.log(1e-4), w[key].shape)).astype(np.float32)
+        gamma = key[:-len('running_var')] + 'weight'
+        out[key] = var
+        out[gamma] = w[gamma] * np.sqrt(var + np.float32(1e-5))
+        assert out[gamma].dtype == np.float32
+    return out
+
+
+def set_eps(model: nn.Module, eps: float, only_mse: bool = False) -> nn.Module:
+    """The eps of every BatchNorm of ``model`` (only_mse: of the four inside every MSE) -- the CPU tests' mutation."""
+    roots = [m for m in model.modules() if isinstance(m, MSE)] if only_mse else [model]
+    n = 0
+    for root in roots:
+        for m in root.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eps = eps
+                n += 1
+    assert n > 0
+    return model

@@ -1,5 +1,5 @@
 // The pure-host arithmetic of the TDN engine (csrc/tsm_host_util.h: tdn_nearest, tdn_*_size, tdn_refusal, tdn_chunk_clips,
-// tdn_patch_k / tdn_patch_source, tdn_pack_conv15, tdn_mean_less_bias, tdn_pack_mse), built with -fsanitize=address,undefined and
+// tdn_patch_k / tdn_patch_source, tdn_pack_conv15, tdn_mean_less_bias, tdn_bn_fold, tdn_pack_mse), built with -fsanitize=address,undefined and
 // run on the CPU by tests/test_tdn_cpu.py: the sizes the engine hands the kernels and the weights it uploads.
 //   tdn_host
 #include <cinttypes>
@@ -167,8 +167,55 @@ static void weights() {
   }
 }
 
+// The folds' VALUES against a fold in double, at variances where eps decides (1e-10: the root is sqrt(eps); 1e-6: eps is ten times
+// the variance) and where it does not (1).  Bound: var + eps rounds once and eps itself is 1e-5 to float rounding (together at
+// most 2^-24 of the scale behind the root), the root, the division and the product with a weight round once each: 4 * 2^-24;
+// asserted at 8 * 2^-24 = 4.8e-7.  eps = 1.1e-5 moves the scale by 4.7 % at 1e-10 and 4.3 % at 1e-6, eps = 0 by 316 and 3.3 times.
+static void fold_values() {
+  using namespace tsm_host;
+  const double eps = 1e-5, ulps = 8.0 / 16777216.0;
+  std::mt19937 rng(11);
+  std::normal_distribution<float> nd(0.f, 1.f);
+  std::uniform_real_distribution<float> ud(0.5f, 1.5f);
+  for (float var0 : {1e-10f, 1e-6f, 1.0f}) {
+    const int c = 64;
+    std::vector<float> bn(4 * (size_t)c);
+    for (int o = 0; o < c; ++o) {
+      bn[o] = ud(rng) * (o % 2 ? -1.f : 1.f);
+      bn[c + o] = 0.1f * nd(rng);
+      bn[2 * c + o] = 0.1f * nd(rng);
+      bn[3 * c + o] = var0 * ud(rng);
+    }
+    std::vector<float> scale, bias;
+    tdn_bn_fold(bn.data(), c, &scale, &bias);
+    EXPECT(scale.size() == (size_t)c && bias.size() == (size_t)c, "sizes");
+    std::vector<float> w((size_t)c * kTdnDiffC * 49), wp, b15;
+    for (float &x : w) x = nd(rng);
+    tdn_pack_conv15(w.data(), bn.data(), bn.data() + c, bn.data() + 2 * c, bn.data() + 3 * c, c, &wp, &b15);
+    for (int o = 0; o < c; ++o) {
+      const double s = (double)bn[o] / std::sqrt((double)bn[3 * c + o] + eps), b = (double)bn[c + o] - (double)bn[2 * c + o] * s;
+      const double b_tol = ulps * (std::fabs((double)bn[c + o]) + 2.0 * std::fabs((double)bn[2 * c + o] * s));
+      EXPECT(std::isfinite(scale[o]) && std::fabs(scale[o] - s) <= ulps * std::fabs(s), "scale %d at variance %g: %.9g vs %.9g", o, var0, scale[o], s);
+      EXPECT(std::isfinite(bias[o]) && std::fabs(bias[o] - b) <= b_tol, "bias %d at variance %g: %.9g vs %.9g", o, var0, bias[o], b);
+      EXPECT(std::fabs(b15[o] - b) <= b_tol, "conv1_5 bias %d at variance %g: %.9g vs %.9g", o, var0, b15[o], b);
+      for (int k = 0; k < kTdnPatchReal; k += 5) {
+        const int ch = k % kTdnDiffC, kx = k / kTdnDiffC % 7, ky = k / (7 * kTdnDiffC);
+        const double want = (double)w[(((size_t)o * kTdnDiffC + ch) * 7 + ky) * 7 + kx] * s, got = wp[(size_t)o * kTdnPatchK + tdn_patch_k(ky, kx, ch)];
+        EXPECT(std::fabs(got - want) <= ulps * std::fabs(want), "conv1_5 weight (%d, %d) at variance %g: %.9g vs %.9g", o, k, var0, got, want);
+      }
+      // the near misses the bound must tell apart where eps decides
+      if (var0 < 1e-5f)
+        for (double other : {1.1e-5, 2e-5, 1e-3, 0.0}) {
+          const double s2 = (double)bn[o] / std::sqrt((double)bn[3 * c + o] + other);
+          EXPECT(std::fabs(s2 - s) > 1000 * ulps * std::fabs(s), "eps %g is told from 1e-5 at variance %g", other, var0);
+        }
+    }
+  }
+}
+
 int main() {
   sizes();
+  fold_values();
   refusals();
   patches();
   weights();

@@ -9,7 +9,6 @@ Bars, the project's own (tests/test_convnext_gpu.py): per operator, from the eng
 the scale; network taps rtol 1e-3 + 3e-5 of the scale; logits rtol 1e-3 + 1e-5 of the scale.  Everything that compares two runs
 of the engine is bit for bit."""
 import ctypes as C
-import functools
 import os
 import re
 
@@ -18,79 +17,20 @@ import pytest
 import torch
 
 from tests import _tdn
+from tests._tdn_cases import LOGITS_BAR, NUM_CLASS, OP_BAR, TAP_BAR      # the bars of the docstring
+from tests._tdn_cases import bits as _bits, engine as _cases_engine, tap_names as _tap_names, with_temporal as _with_temporal
+from tests._tdn_cases import clips as _clips, network as _model, reference as _reference      # cached, shared, read-only
 from tests._guard import guarded, guarded_out
 from tests._util import assert_close
 
 pytestmark = pytest.mark.gpu
 
-OP_BAR = dict(rtol=1e-4, atol_scale=1e-4)
-LOGITS_BAR = dict(rtol=1e-3, atol_scale=1e-5)
-TAP_BAR = dict(rtol=1e-3, atol_scale=3e-5)
-NUM_CLASS = 7
-KNOBS = ('TSM_AUTOTUNE', 'TSM_POISON', 'TSM_CONV_CODE', 'TSM_TUNE_CACHE')
 D64, D96, D224, FLAT = (1, 1, 1, 2), (1, 2, 1, 2), (1, 1, 1, 2), (1, 1, 1, 1)
 
 
-@functools.lru_cache(maxsize=None)
-def _model(depths, T, seed=5):
-    """(float64 model with per-segment logits, its weights as read-only float32 arrays)"""
-    model, w = _tdn.build(NUM_CLASS, T, depths, seed, consensus='identity')
-    for v in w.values():
-        v.setflags(write=False)
-    return model, w
-
-
-@functools.lru_cache(maxsize=None)
-def _clips(h, w, T, n, seed=31):
-    x = np.random.default_rng([seed, h, w, T]).standard_normal((n, T, 15, h, w)).astype(np.float32)
-    x.setflags(write=False)
-    return x
-
-
-@functools.lru_cache(maxsize=None)
-def _reference(h, w, depths, T, n):
-    """Per-segment logits [n, T, cls] and the taps of the float64 model -- computed once, shared, left unchanged."""
-    model, _w = _model(depths, T)
-    with torch.no_grad():
-        logits, taps = model(torch.from_numpy(np.array(_clips(h, w, T, n)).reshape(n * T, 15, h, w)).double(), taps=True)
-    return logits.numpy(), taps
-
-
-def _engine(h, w, T, depths, max_clips=3, sd=None, consensus='avg', autotune=False, poison=False, code=None):
-    """The TSM_* variables are read in tsm_create: set for the constructor only, then restored."""
-    from workoutdetector_amd.engine import TsmEngine
-    keep = {k: os.environ.get(k) for k in KNOBS}
-    for k in KNOBS:
-        os.environ.pop(k, None)
-    os.environ['TSM_AUTOTUNE'] = '1' if autotune else '0'
-    os.environ['TSM_TUNE_CACHE'] = '0'
-    if poison:
-        os.environ['TSM_POISON'] = '1'
-    if code is not None:
-        os.environ['TSM_CONV_CODE'] = str(code)
-    try:
-        return TsmEngine(num_class=NUM_CLASS, num_segments=T, height=h, width=w, is_shift=False, max_clips=max_clips,
-                         state_dict=sd if sd is not None else _model(depths, T)[1], base_model='tdn_resnet50', tdn_depths=depths,
-                         consensus_type=consensus)
-    finally:
-        for k, v in keep.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _tap_names(depths):
-    names = ['diff.conv1_5', 'diff.stem', 'stem', 'fuse1', 'fuse2']
-    names += [f'resnext_layer1.{b}' for b in range(depths[0])] + [f'layer1.{b}' for b in range(depths[0])]
-    for li in (2, 3, 4):
-        for b in range(depths[li - 1]):
-            p = f'layer{li}.{b}'
-            names += [p, p + '.conv1', p + '.mse.fwd', p + '.mse.bwd', p + '.shift', p + '.conv2']
-    return names
+def _engine(h, w, T, depths, max_clips=3, sd=None, **kw):
+    """tests/_tdn_cases.py: engine, of the seeded weights unless ``sd`` is given."""
+    return _cases_engine(h, w, T, depths, sd if sd is not None else _model(depths, T)[1], max_clips=max_clips, **kw)
 
 
 CASES = [(64, 64, D64, 2, 1, 'avg'), (64, 64, D64, 2, 3, 'identity'), (64, 64, D64, 3, 1, 'identity'), (64, 64, D64, 3, 3, 'avg'),
@@ -120,24 +60,6 @@ def test_taps_and_logits_against_float64(hip_lib, h, w, depths, T, n, consensus,
     assert_close(feats, taps['features'], what='forward_features', **LOGITS_BAR)
     with capsys.disabled():
         print(f'\n[tdn {h}x{w} T={T} n={n} {consensus}] max|err|/scale: logits {err:.2g}, worst tap {worst:.2g}')
-
-
-def _with_temporal(w, shift_block=None):
-    """The weights with every shift.conv.weight replaced by (0, 1, 0) -- but for block ``shift_block`` ('layerL_bak.B'), which gets
-    ShiftModule's initial pattern, fold = C / 8."""
-    sd = dict(w)
-    for k, v in w.items():
-        if k.endswith('.shift.conv.weight'):
-            t = np.zeros_like(v)
-            fold = v.shape[0] // 8
-            if shift_block is None or f'.{shift_block}.' not in k:
-                t[:, 0, 1] = 1
-            else:
-                t[:fold, 0, 2] = 1
-                t[fold:2 * fold, 0, 0] = 1
-                t[2 * fold:, 0, 1] = 1
-            sd[k] = t
-    return sd
 
 
 def test_the_gate_alone_and_the_temporal_conv_alone(hip_lib, capsys):

@@ -104,9 +104,24 @@ typedef enum tsm_layout {
                              elements (pixel 2j: c0 c1 c2 0, pixel 2j+1: c0 c1 c2 0), an odd width ends in a
                              zero pixel -- what tsm_preprocess writes for a TSM_DTYPE_BF16X3 engine (the 7x7
                              stride-2 stem then reads 4 aligned pairs per kernel row); device memory only */
-  TSM_LAYOUT_NTHWC8B = 4  /* bf16 [B,T,H,ceil(W/2),8]: the same pixel pairs, 16 bytes per pair -- for a
+  TSM_LAYOUT_NTHWC8B = 4, /* bf16 [B,T,H,ceil(W/2),8]: the same pixel pairs, 16 bytes per pair -- for a
                              TSM_DTYPE_BF16 engine */
+  TSM_LAYOUT_TDN_POOL = 16 /* a TDN engine only: `clips` points to a tsm_tdn_pool in HOST memory (below, beside tsm_set_tdn), which
+                              names a pool of transformed frames in device memory; memkind must be TSM_MEM_DEVICE.  Not an
+                              out_layout of the tsm_preprocess* entry points */
 } tsm_layout;
+
+/* The input of a TDN forward as a pool of frames (TSM_LAYOUT_TDN_POOL; the contract stands beside tsm_set_tdn). */
+typedef struct tsm_tdn_pool {
+  uint32_t struct_size;        /* sizeof(tsm_tdn_pool) */
+  int32_t mode;                /* 0 table, 1 window */
+  const float *frames;         /* device, [n_frames, 3, H, W], H x W the engine's, 8-byte aligned */
+  int64_t n_frames;
+  const int32_t *index;        /* mode 0: device, [n_clips, T, 5] */
+  int64_t first_source_frame, total_frames, first_clip; /* mode 1 */
+  int32_t clip_step, clip_stride;                       /* mode 1 */
+  int64_t pad_frame;           /* mode 1: pool frame standing for "no frame"; < 0 or >= n_frames: zero planes */
+} tsm_tdn_pool;
 
 /* The staged frames of a frame transform (tsm_preprocess, _clips, _indexed, _windows).
  *   TSM_PIXEL_U8 / TSM_PIXEL_F32   [h, w, 3] RGB, values 0..255.
@@ -341,15 +356,32 @@ int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]);
  * width not a multiple of 32 or below 64 (a layer4 mSE map could not be pooled), a depth outside 1 .. 64, and after
  * tsm_set_backbone, tsm_set_bottleneck_width, tsm_set_shift_place, tsm_set_non_local(e, 1), tsm_set_temporal_pool(e, 1) or
  * tsm_set_convnext; those six are TSM_ERR_UNSUPPORTED in turn on a TDN engine.  tsm_set_consensus stays legal.
- * tsm_forward / tsm_forward_features / tsm_forward_tap take TSM_LAYOUT_NTCHW only, 15 planes per segment, host or device memory
- * (any other layout: TSM_ERR_UNSUPPORTED); everything else is tsm_forward's contract word for word: tsm_tune covers every conv
+ * tsm_forward / tsm_forward_features / tsm_forward_tap take TSM_LAYOUT_NTCHW, 15 planes per segment, host or device memory, or
+ * TSM_LAYOUT_TDN_POOL (below); any other layout: TSM_ERR_UNSUPPORTED.  Everything else is tsm_forward's contract word for word: tsm_tune covers every conv
  * of the engine (conv1_5 runs on conv_igemm as a 1x1 GEMM over patch rows of K = 1024, 588 of them real), tile codes never change
  * a result bit, after tuning the call only enqueues and is capture-safe, and the tune-cache key carries " tdn<depths>".
  * The front end runs in chunks of at most 8 clips through one patch buffer; a clip's result does not depend on the chunking.
  * Launches between conv1 and conv2 of a BottleneckShift: mse_squeeze_kernel and mse_excite_shift_kernel are the only readers of
  * conv1's output, and o is the only full-width tensor written: b, d, s2 and m have r channels, g never reaches memory.
  * Taps (tsm_forward_tap): "diff.conv1_5" (x_c5), "diff.stem" (xd0), "resnext_layer1.B", "stem", "fuse1", "layer1.B", "fuse2",
- * "layerL.B", "layerL.B.conv1", "layerL.B.mse.fwd" / ".mse.bwd" (m+ / m-, [N, H, W, r]), "layerL.B.shift" (o), "layerL.B.conv2". */
+ * "layerL.B", "layerL.B.conv1", "layerL.B.mse.fwd" / ".mse.bwd" (m+ / m-, [N, H, W, r]), "layerL.B.shift" (o), "layerL.B.conv2".
+ *
+ * TSM_LAYOUT_TDN_POOL: the 15 planes of a segment are not handed over but FOUND.  `clips` is a tsm_tdn_pool in host memory; it is
+ * read during the call, its values travel as kernel parameters and nothing of it is dereferenced later.  `frames` is a pool of
+ * transformed frames [n_frames, 3, H, W] fp32 in device memory -- what tsm_preprocess writes as TSM_LAYOUT_NTCHW -- and plane pl
+ * of segment s is channel pl % 3 of pool frame frame_of(s, pl / 3).  tdn_front_pool_kernel takes tdn_front_kernel's place in the
+ * "diff.front" slot (same arithmetic, same bits as an NTCHW forward of the gathered planes); everything behind it is unchanged.
+ *   mode 0 (table): frame_of(s, j) = index[s * 5 + j], `index` int32 [n_clips, T, 5] in device memory, read on the device when the
+ *     kernel runs (at replay, for a captured call).  The kernel is total in the table: an entry outside [0, n_frames) reads
+ *     nothing and stands for a plane of 0.0f.
+ *   mode 1 (window): no table.  Segment k of clip c (counted from first_clip) has centre clip_step * c + clip_stride * k; frame j
+ *     is clamp(centre - 2 + j, 0, total_frames - 1) - first_source_frame.  A centre >= total_frames, or a result outside
+ *     [0, n_frames), takes pad_frame -- the pool's transformed zero frame, so the differences are exactly zero; a pad_frame
+ *     outside [0, n_frames) stands for planes of 0.0f.
+ * TSM_ERR_UNSUPPORTED: the layout on an engine without tsm_set_tdn.  TSM_ERR_INVALID_ARG: TSM_MEM_HOST; a struct_size other than
+ * sizeof(tsm_tdn_pool); frames NULL or not 8-byte aligned; n_frames <= 0; a mode other than 0 or 1; mode 0 with index NULL; mode 1
+ * with clip_step <= 0, clip_stride <= 0 or total_frames <= 0.  Nothing is launched on a refusal.  The first call of a bucket
+ * tunes exactly as an NTCHW call does (on the pool it was given); after tuning the call only enqueues and is capture-safe. */
 int tsm_set_tdn(tsm_engine *e, const int32_t depths[4], float alpha, float beta);
 
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,

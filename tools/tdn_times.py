@@ -2,6 +2,7 @@
 DESIGN 4.25.
 
     python tools/tdn_times.py <out.json> [clips]
+    python tools/tdn_times.py --pool <out.json> [clips]      the dense input route against the pool route (``pool_mode``)
 
 In one process, 3 warm-up rounds, then 10 rounds in which these alternate, each between two device events:
   * a plain TDN forward (``forward_device``): clips/s of the whole forward;
@@ -28,6 +29,9 @@ from workoutdetector_amd import flops                                           
 from workoutdetector_amd.engine import create_model, create_tdn_model           # noqa: E402
 from workoutdetector_amd.weights import TDN_DEPTHS, make_tdn_state_dict         # noqa: E402
 
+POOL = '--pool' in sys.argv
+if POOL:
+    sys.argv.remove('--pool')
 out_path = sys.argv[1]
 CLIPS = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 T, SIZE, WARM, ROUNDS, CLASSES = 8, 224, 3, 10, 12
@@ -46,6 +50,93 @@ def timed(fn):
 def stats(v):
     return {'ms_median': statistics.median(v), 'ms_min': min(v), 'ms_max': max(v)}
 
+
+def pool_mode():
+    """``--pool``: CLIPS consecutive clips of the counting geometry (a clip every 8 frames, every 2nd frame, five
+    frames per segment) from the middle of a 640 x 360 uint8 video staged on the device, two routes to the same logits:
+      (a) the dense route: ``preprocess_indexed`` over all CLIPS * 40 table rows into [CLIPS, 8, 15, 224, 224], the NTCHW forward;
+      (b) the pool route: ``preprocess_frames`` over the unique staged frames, ``forward_pool`` in window mode.
+    3 warm-up rounds, then 10 rounds in which (a) and (b) alternate; per round also the transform launch of each route alone and
+    a forward of each route with per-launch timing (diff.front per chunk: tdn_front_kernel against tdn_front_pool_kernel)."""
+    from workoutdetector_amd import _lib
+    from workoutdetector_amd.engine import preprocess_frames, preprocess_indexed
+    from workoutdetector_amd.tdn_pipeline import tdn_clip_indices, tdn_frame_range
+    vh, vw, total, lo = 360, 640, 1000, 4
+    a, b = tdn_frame_range(total, lo, lo + CLIPS)
+    nf = b - a
+    rng = np.random.default_rng(0)
+    staged = torch.from_numpy(rng.integers(0, 256, (nf + 1, vh, vw, 3), dtype=np.uint8)).cuda()
+    staged[-1].zero_()
+    table = torch.from_numpy(tdn_clip_indices(total, lo, lo + CLIPS, T, 8, 2, a, nf, nf + 1).reshape(CLIPS, T * 5)).cuda()
+    window = dict(first_source_frame=a, total_frames=total, first_clip=lo, clip_step=8, clip_stride=2, pad_frame=nf)
+    eng = create_tdn_model(CLASSES, num_segments=T, height=SIZE, width=SIZE, max_clips=CLIPS)
+    eng.warmup([CLIPS])
+    dense = torch.empty(CLIPS, T * 5, 3, SIZE, SIZE, device='cuda')
+    pool = torch.empty(nf + 1, 3, SIZE, SIZE, device='cuda')
+    out_a, out_b = torch.empty(CLIPS, CLASSES, device='cuda'), torch.empty(CLIPS, CLASSES, device='cuda')
+    kw = dict(resize=256, crop=SIZE, scale_255=False)
+
+    def transform_a():
+        preprocess_indexed(staged, table, layout=_lib.LAYOUT_NTCHW, out=dense, **kw)
+
+    def transform_b():
+        preprocess_frames(staged, packed=False, out=pool, **kw)
+
+    def forward_a():
+        eng.forward_device(dense.view(CLIPS, T, 15, SIZE, SIZE), out=out_a)
+
+    def forward_b():
+        eng.forward_pool(pool, window=window, n_clips=CLIPS, out=out_b)
+
+    def fronts(forward):
+        eng.set_layer_timing(1)
+        forward()
+        torch.cuda.synchronize()
+        return {k: v for k, v in eng.layer_times_ms(0).items() if k.startswith('diff.front') and v >= 0}
+    keys = ('route_a', 'route_b', 'transform_a', 'transform_b', 'forward_a', 'forward_b')
+    runs = {k: [] for k in keys}
+    front = {'tdn_front_kernel': {}, 'tdn_front_pool_kernel': {}}
+    for rnd in range(WARM + ROUNDS):
+        got = {'route_a': timed(lambda: (transform_a(), forward_a())), 'route_b': timed(lambda: (transform_b(), forward_b())),
+               'transform_a': timed(transform_a), 'transform_b': timed(transform_b),
+               'forward_a': timed(forward_a), 'forward_b': timed(forward_b)}
+        fa, fb = fronts(forward_a), fronts(forward_b)
+        if rnd >= WARM:
+            for k in keys:
+                runs[k].append(got[k])
+            for name, f in (('tdn_front_kernel', fa), ('tdn_front_pool_kernel', fb)):
+                for k, v in f.items():
+                    front[name].setdefault(k, []).append(v)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out_a.view(torch.int32), out_b.view(torch.int32)))
+    res = {k: stats(v) for k, v in runs.items()}
+    spread_a = res['route_a']['ms_max'] - res['route_a']['ms_min']
+    front_stats = {name: {k: stats(v) for k, v in f.items()} for name, f in front.items()}
+    front_sum = {name: sum(v['ms_median'] for v in f.values()) for name, f in front_stats.items()}
+    chunk_segments = eng.tdn_chunk_clips * T
+    result = {
+        'clips': CLIPS, 'segments': T, 'size': SIZE, 'video': [vh, vw], 'rounds': ROUNDS, 'device': torch.cuda.get_device_name(0),
+        'build': eng._lib.tsm_build_id().decode(), 'staged_frames': nf + 1, 'table_rows': CLIPS * T * 5,
+        'logits_bit_identical': same, **res,
+        'route_b_minus_a_ms': res['route_b']['ms_median'] - res['route_a']['ms_median'], 'route_a_spread_ms': spread_a,
+        'transform_b_over_a': res['transform_b']['ms_median'] / res['transform_a']['ms_median'],
+        'diff_front_per_chunk': front_stats, 'diff_front_sum_ms': front_sum,
+        'diff_front_bytes_per_chunk': chunk_segments * (15 * SIZE * SIZE + 4 * SIZE * SIZE + (SIZE // 4) ** 2 * 1024) * 4,
+        'input_device_bytes': {'route_a_dense': dense.numel() * 4, 'route_b_pool': pool.numel() * 4,
+                               'saved': (dense.numel() - pool.numel()) * 4},
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, 'w') as f:
+        json.dump(result, f, indent=1)
+    print(json.dumps({k: result[k] for k in ('logits_bit_identical', 'route_a', 'route_b', 'transform_a', 'transform_b', 'forward_a', 'forward_b',
+                                             'diff_front_sum_ms', 'input_device_bytes')}))
+    if not same:
+        sys.exit('the two routes disagree')
+
+
+if POOL:
+    pool_mode()
+    sys.exit(0)
 
 eng = create_tdn_model(CLASSES, num_segments=T, height=SIZE, width=SIZE, max_clips=CLIPS)
 plain = create_model(num_class=CLASSES, num_segments=T, is_shift=False, height=SIZE, width=SIZE, max_clips=CLIPS)

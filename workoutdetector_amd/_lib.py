@@ -12,6 +12,8 @@ ABI_VERSION = 7
 
 MEM_HOST, MEM_DEVICE = 0, 1
 LAYOUT_NTCHW, LAYOUT_NTHWC, LAYOUT_NTHWC4, LAYOUT_NTHWC8S, LAYOUT_NTHWC8B = 0, 1, 2, 3, 4
+LAYOUT_TDN_POOL = 16      # a TDN engine's input as a TsmTdnPool descriptor (host memory) naming device memory
+TDN_POOL_TABLE, TDN_POOL_WINDOW = 0, 1
 PIXEL_U8, PIXEL_F32 = 0, 1
 PIXEL_NV12_BT601, PIXEL_NV12_BT709, PIXEL_NV12_BT601_FULL, PIXEL_NV12_BT709_FULL = 16, 17, 18, 19
 _NV12_PIXELS = {'bt601': PIXEL_NV12_BT601, 'bt709': PIXEL_NV12_BT709, 'bt601-full': PIXEL_NV12_BT601_FULL,
@@ -62,6 +64,13 @@ STATUS_NAMES = {0: 'TSM_OK', -1: 'TSM_ERR_INVALID_ARG', -2: 'TSM_ERR_HIP', -3: '
 class TsmConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('struct_size', 'num_class', 'num_segments', 'height', 'width',
                                          'shift_div', 'is_shift', 'max_clips', 'device_id', 'dtype')]
+
+
+class TsmTdnPool(C.Structure):
+    """struct tsm_tdn_pool (include/tsm_hip.h): what ``clips`` points to with LAYOUT_TDN_POOL."""
+    _fields_ = [('struct_size', C.c_uint32), ('mode', C.c_int32), ('frames', C.c_void_p), ('n_frames', C.c_int64),
+                ('index', C.c_void_p), ('first_source_frame', C.c_int64), ('total_frames', C.c_int64), ('first_clip', C.c_int64),
+                ('clip_step', C.c_int32), ('clip_stride', C.c_int32), ('pad_frame', C.c_int64)]
 
 
 class TsmError(RuntimeError):

@@ -201,6 +201,7 @@ struct tsm_engine {
   float tdn_alpha = 0.5f, tdn_beta = 0.5f;
   std::vector<TdnMse> tdn_mse;
   int tdn_chunk = 0;          // clips per front-end chunk (tdn_chunk_clips)
+  tsm_tdn_pool tdn_pool{};    // TSM_LAYOUT_TDN_POOL: the caller's descriptor, copied behind its checks, for the running call only
   int hd = 0, wd = 0;         // the difference path's maps (xd0, resnext_layer1)
   float *d_patches = nullptr; // conv1_5's patch rows of one chunk
   // the long-term module's r-channel maps: b, d+, d-, m+, m- at the block's size; pooled d+, d-, s2+, s2- at half of it
@@ -1280,7 +1281,8 @@ int run_head(tsm_engine *e, const float *cur, int n, int n_clips, int hw, float 
 
 // The forward of a TDN engine (tsm_set_tdn) on n_clips clips of T segments, x [n_clips, T, 15, H, W].  Launches and timing slots,
 // in order (TsmEngine.launch_names spells them):
-//   per chunk of at most tdn_chunk clips: diff.front (tdn_front_kernel: the centre frames into d_in4, the patch rows of the chunk),
+//   per chunk of at most tdn_chunk clips: diff.front (tdn_front_kernel, or for TSM_LAYOUT_TDN_POOL tdn_front_pool_kernel over
+//     e->tdn_pool with the table / first clip advanced by the chunk: the centre frames into d_in4, the patch rows of the chunk),
 //     diff.conv1_5 (the 1x1 GEMM over them into the chunk's rows of x_c5); a forward of fewer chunks than the engine's
 //     capacity holds leaves the other chunks' slots not recorded;
 //   diff.maxpool (xd0); conv1 (the fp32 stem with its fused max-pool, from d_in4), fuse1;
@@ -1290,7 +1292,7 @@ int run_head(tsm_engine *e, const float *cur, int n, int n_clips, int hw, float 
 //   head.
 // Buffers: xd0 in buf[0] and the stem's output in buf[4]; resnext_layer1 rotates buf[0] and buf[1], the trunk buf[4] and whichever
 // of buf[0] / buf[1] does not hold xd1; behind fuse2 xd1's buffer is dead and holds o, the long-term module's output.
-int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int n_clips, float *d_logits, hipStream_t s) {
+int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int layout, int n_clips, float *d_logits, hipStream_t s) {
   const tsm_config &cfg = e->cfg;
   const int T = cfg.num_segments, n = n_clips * T, H = cfg.height, W = cfg.width, prec = e->prec;
   const int h5 = tdn_conv15_size(H), w5 = tdn_conv15_size(W);
@@ -1301,7 +1303,11 @@ int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int n_clips, float 
   for (int c0 = 0; c0 < n_clips; c0 += e->tdn_chunk, ++chunks) {
     const int nf = std::min(e->tdn_chunk, n_clips - c0) * T;
     const int64_t f0 = (int64_t)c0 * T;
-    TSM_LAUNCH(e, s, tsm::launch_tdn_front(d_clips + f0 * kTdnPlanes * plane, e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+    if (layout == TSM_LAYOUT_TDN_POOL) {
+      TSM_LAUNCH(e, s, tsm::launch_tdn_front_pool(tdn_pool_source(e->tdn_pool, T, c0), e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+    } else {
+      TSM_LAUNCH(e, s, tsm::launch_tdn_front(d_clips + f0 * kTdnPlanes * plane, e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+    }
     // (the tuning pass times conv1_5's candidates on its first chunk only; a later, smaller chunk re-validates the code: checked_code)
     tsm::ConvParams p = make_params(e->convs[1], e->d_patches, nullptr, xc5 + f0 * rows * 64, nf, h5, w5, true, 0, 1, prec);
     const bool was_tuning = f.tuning;
@@ -1365,7 +1371,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
     f.tiles = &it->second;
   }
   if (e->convnext) return run_convnext(e, f, d_clips, layout, n, d_logits, s);
-  if (e->tdn) return run_tdn(e, f, d_clips, n_clips, d_logits, s);
+  if (e->tdn) return run_tdn(e, f, d_clips, layout, n_clips, d_logits, s);
 
   const int prec = e->prec;
   const float *in4 = e->d_in4;
@@ -1491,12 +1497,18 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
   if (!e->finalized) return fail(e, TSM_ERR_NOT_FINALIZED, "tsm_finalize has not been called");
   if (!clips) return fail(e, TSM_ERR_INVALID_ARG, "clips is NULL");
   if (memkind != TSM_MEM_HOST && memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "bad memkind");
-  if (layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
-  if (e->tdn && layout != TSM_LAYOUT_NTCHW)
-    return fail(e, TSM_ERR_UNSUPPORTED, "a TDN engine takes TSM_LAYOUT_NTCHW only: [n_clips, T, 15, H, W], five frames per segment");
-  if (layout >= TSM_LAYOUT_NTHWC4 && memkind != TSM_MEM_DEVICE)
+  if ((layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) && layout != TSM_LAYOUT_TDN_POOL) return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
+  if (layout == TSM_LAYOUT_TDN_POOL) {   // `clips` is a tsm_tdn_pool in host memory: checked and copied here, nothing of it is read later
+    if (!e->tdn) return fail(e, TSM_ERR_UNSUPPORTED, "TSM_LAYOUT_TDN_POOL goes with a TDN engine (tsm_set_tdn) only");
+    if (memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "TSM_LAYOUT_TDN_POOL names frames in device memory: memkind must be TSM_MEM_DEVICE");
+    if (const char *why = tdn_pool_refusal(static_cast<const tsm_tdn_pool *>(clips))) return fail(e, TSM_ERR_INVALID_ARG, why);
+  } else if (e->tdn && layout != TSM_LAYOUT_NTCHW) {
+    return fail(e, TSM_ERR_UNSUPPORTED, "a TDN engine takes TSM_LAYOUT_NTCHW only: [n_clips, T, 15, H, W], five frames per segment (or TSM_LAYOUT_TDN_POOL)");
+  }
+  const bool packed = layout >= TSM_LAYOUT_NTHWC4 && layout <= TSM_LAYOUT_NTHWC8B;
+  if (packed && memkind != TSM_MEM_DEVICE)
     return fail(e, TSM_ERR_INVALID_ARG, "packed layouts (NTHWC4 / NTHWC8S / NTHWC8B) are device-memory layouts");
-  if (layout >= TSM_LAYOUT_NTHWC4 && layout != packed_layout_of(e->prec))
+  if (packed && layout != packed_layout_of(e->prec))
     return fail(e, TSM_ERR_INVALID_ARG, "packed layout does not match the engine dtype");
   if (n_clips <= 0) return fail(e, TSM_ERR_INVALID_ARG, "n_clips must be positive");
   if (n_clips > e->cfg.max_clips)
@@ -1506,10 +1518,14 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
 }
 
 // Behind check_forward_args: the engine's device, the call's stream, and clips in host memory staged into d_in.
-int stage_input(tsm_engine *e, const void *clips, int memkind, int n_clips, void *stream, hipStream_t *s, const float **d_clips) {
+int stage_input(tsm_engine *e, const void *clips, int memkind, int layout, int n_clips, void *stream, hipStream_t *s, const float **d_clips) {
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
   *s = pick_stream(e, memkind, stream);
   *d_clips = static_cast<const float *>(clips);
+  if (layout == TSM_LAYOUT_TDN_POOL) {   // (behind tdn_pool_refusal) the forward reads e->tdn_pool, never `clips`
+    e->tdn_pool = *static_cast<const tsm_tdn_pool *>(clips);
+    *d_clips = nullptr;
+  }
   if (memkind == TSM_MEM_HOST) {
     const size_t in_elems = (size_t)n_clips * e->cfg.num_segments * (e->tdn ? kTdnPlanes : 3) * e->cfg.height * e->cfg.width;
     TSM_HIP(e, hipMemcpyAsync(e->d_in, clips, in_elems * sizeof(float), hipMemcpyHostToDevice, *s));
@@ -2228,7 +2244,7 @@ static int forward_to(tsm_engine *e, const void *clips, int32_t memkind, int32_t
   if (!out) return fail(e, TSM_ERR_INVALID_ARG, features ? "features is NULL" : "logits is NULL");
   hipStream_t s;
   const float *d_clips;
-  if ((rc = stage_input(e, clips, memkind, n_clips, stream, &s, &d_clips))) return rc;
+  if ((rc = stage_input(e, clips, memkind, layout, n_clips, stream, &s, &d_clips))) return rc;
   float *d_stage = features ? e->d_pooled : e->d_logits, *d_out = memkind == TSM_MEM_HOST ? d_stage : out;
   struct Mode {   // run_forward's last launch, for this call only (every return path)
     tsm_engine *e;
@@ -2320,7 +2336,7 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
   if (!stage || !out || !out_shape) return fail(e, TSM_ERR_INVALID_ARG, "stage/out/out_shape is NULL");
   hipStream_t s;
   const float *d_clips;
-  if ((rc = stage_input(e, clips, memkind, n_clips, stream, &s, &d_clips))) return rc;
+  if ((rc = stage_input(e, clips, memkind, layout, n_clips, stream, &s, &d_clips))) return rc;
   rc = poison_workspace(e, s);
   if (rc) return rc;
   Tap tap;

@@ -781,6 +781,76 @@ inline int64_t tdn_patch_source(int oy, int ox, int k, int hp, int wp) {
   if (py < 0 || py >= hp || px < 0 || px >= wp) return -1;
   return ((int64_t)py * wp + px) * kTdnDiffC + c;
 }
+// ---- TSM_LAYOUT_TDN_POOL: where tdn_front_pool_kernel finds the five frames of a segment ----------------------------------------
+// Window mode, ONE rule for the kernel and the host: the pool frame of frame j (0 .. 4) of segment k of clip `clip`, or -1 for
+// planes of 0.0f.  centre = clip_step * clip + clip_stride * k; the source frame is clamp(centre - 2 + j, 0, total - 1); its pool
+// frame is that minus first_source_frame.  A centre >= total, a result outside [0, n_frames) or an argument outside the rule's
+// domain takes pad_frame (-1 when that is outside the pool too).  Total in its arguments: no product, sum or difference is formed
+// before it is known to fit (tests/tdn_pool_host.cpp runs it at the ends of int64 under UBSAN).
+TSM_HOST_DEVICE inline int64_t tdn_window_frame(int64_t first_source_frame, int64_t total_frames, int64_t clip, int k, int j,
+                                                int32_t clip_step, int32_t clip_stride, int64_t n_frames, int64_t pad_frame) {
+  const int64_t pad = pad_frame >= 0 && pad_frame < n_frames ? pad_frame : -1;
+  if (total_frames <= 0 || clip < 0 || k < 0 || j < 0 || j >= kTdnFrames || clip_step <= 0 || clip_stride <= 0) return pad;
+  const int64_t last = total_frames - 1;
+  int64_t base;
+  if (__builtin_mul_overflow((int64_t)clip_step, clip, &base) || base > last) return pad;
+  const int64_t off = (int64_t)clip_stride * k;   // (31 + 31 bits)
+  if (off > last - base) return pad;              // the centre is past the end
+  const int64_t centre = base + off;
+  const int d = j - 2;
+  const int64_t src = d > 0 ? (d > last - centre ? last : centre + d) : (centre < -d ? 0 : centre + d);
+  if (src < first_source_frame) return pad;
+  if (first_source_frame < 0 && src > INT64_MAX + first_source_frame) return pad;   // (src - first would not fit: far outside any pool)
+  const int64_t rel = src - first_source_frame;
+  return rel < n_frames ? rel : pad;
+}
+// A table entry: range-tested in 32 bits first, only then widened.  `limit` = tdn_table_limit(n_frames).
+TSM_HOST_DEVICE inline int64_t tdn_table_frame(int32_t entry, uint32_t limit) { return (uint32_t)entry < limit ? (int64_t)entry : -1; }
+inline uint32_t tdn_table_limit(int64_t n_frames) { return n_frames <= 0 ? 0u : n_frames > (int64_t)INT32_MAX ? 0x80000000u : (uint32_t)n_frames; }
+// What tdn_front_pool_kernel takes by value: a tsm_tdn_pool behind its checks, the table / first clip advanced to the launch's first
+// segment.  Nothing in it points to host memory.
+struct TdnPoolSource {
+  const float *frames;
+  const int32_t *index;   // mode 0, else nullptr
+  int64_t n_frames, first_source_frame, total_frames, first_clip, pad_frame;
+  int32_t clip_step, clip_stride, mode, T;
+  uint32_t limit;         // tdn_table_limit(n_frames)
+};
+// Why a forward refuses this descriptor (TSM_ERR_INVALID_ARG); nullptr when it can run.
+inline const char *tdn_pool_refusal(const tsm_tdn_pool *d) {
+  if (!d) return "clips is NULL";
+  if (d->struct_size != sizeof(tsm_tdn_pool)) return "tsm_tdn_pool: struct_size is not sizeof(tsm_tdn_pool)";
+  if (d->mode != 0 && d->mode != 1) return "tsm_tdn_pool: mode must be 0 (table) or 1 (window)";
+  if (!d->frames) return "tsm_tdn_pool: frames is NULL";
+  if (reinterpret_cast<uintptr_t>(d->frames) % 8 != 0) return "tsm_tdn_pool: frames must be 8-byte aligned";
+  if (d->n_frames <= 0) return "tsm_tdn_pool: n_frames must be positive";
+  if (d->mode == 0 && !d->index) return "tsm_tdn_pool: table mode needs index";
+  if (d->mode == 1 && (d->clip_step <= 0 || d->clip_stride <= 0)) return "tsm_tdn_pool: clip_step and clip_stride must be positive";
+  if (d->mode == 1 && d->total_frames <= 0) return "tsm_tdn_pool: total_frames must be positive";
+  return nullptr;
+}
+// The descriptor as the kernel's parameter, for the chunk that starts `clip0` clips into the call.
+inline TdnPoolSource tdn_pool_source(const tsm_tdn_pool &d, int T, int64_t clip0) {
+  TdnPoolSource p{};
+  p.frames = d.frames;
+  p.n_frames = d.n_frames;
+  p.mode = d.mode;
+  p.T = T;
+  p.limit = tdn_table_limit(d.n_frames);
+  p.pad_frame = -1;
+  if (d.mode == 0) {
+    p.index = d.index + clip0 * T * kTdnFrames;
+  } else {
+    p.first_source_frame = d.first_source_frame;
+    p.total_frames = d.total_frames;
+    p.first_clip = d.first_clip > INT64_MAX - clip0 ? INT64_MAX : d.first_clip + clip0;   // (saturated: past every video's end)
+    p.clip_step = d.clip_step;
+    p.clip_stride = d.clip_stride;
+    p.pad_frame = d.pad_frame;
+  }
+  return p;
+}
+
 // conv1_5 [64, 12, 7, 7] + its BatchNorm -> [64][kTdnPatchK] in tdn_patch_k's order, the K tail zero.
 inline void tdn_pack_conv15(const float *w, const float *gamma, const float *beta, const float *mean, const float *var, int cout,
                             std::vector<float> *wp, std::vector<float> *bias) {

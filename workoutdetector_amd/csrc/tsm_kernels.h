@@ -7,6 +7,10 @@
 // The parameter blocks, tile codes and every launch rule (conv_route, conv_tile_valid, the fused forms' *_valid): HIP-free.
 #include "tsm_conv_rules.h"
 
+namespace tsm_host {
+struct TdnPoolSource;   // tsm_host_util.h: tdn_front_pool_kernel's parameter
+}
+
 namespace tsm {
 
 // ks in {1, 3, 7}.  conv_route (tsm_conv_rules.h) decides; returns hipSuccess, hipErrorInvalidValue for a refused route, or the launch error.
@@ -202,6 +206,7 @@ hipError_t launch_gelu(float *x, int64_t n4, hipStream_t s);
 // front: x [n, 15, h, w] (h, w multiples of 32, >= 64; n <= 65535) -> in4 [n, h, w, 4] (the centre frame, packed) and the patch
 // rows of conv1_5 [n * h / 4 * w / 4][tsm_host::kTdnPatchK]
 hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_frames, int h, int w, hipStream_t s);
+hipError_t launch_tdn_front_pool(const tsm_host::TdnPoolSource &src, float *in4, float *patches, int n_segments, int h, int w, hipStream_t s);
 // x [n, h, w, c] <- alpha x + beta nearest-upsampled d [n, hd, wd, c], in place
 hipError_t launch_tdn_fuse(float *x, const float *d, int n, int h, int w, int hd, int wd, int c, float alpha, float beta, hipStream_t s);
 // b [m, r] = BN(W1 x), x [m, c]

@@ -1,6 +1,7 @@
 // The non-GEMM part of a TDN-ResNet50 (tsm_set_tdn; include/tsm_hip.h holds the network's definition), fp32, NHWC:
 //   tdn_front_kernel             the difference front end: the 15 input planes of a segment -> the centre frame as packed NHWC4 (what
 //                                the fp32 stem reads in place) and conv1_5's patch rows [frames * H/4 * W/4][1024], K = (ky, kx, c)
+//   tdn_front_pool_kernel        the same from a pool of transformed frames (TSM_LAYOUT_TDN_POOL): the planes found by a table or a window rule
 //   tdn_fuse_kernel              x <- alpha x + beta up(d) in place, torch's 'nearest' upsample
 //   mse_squeeze_kernel<R>        b = BN(W1 x): C = 16 R channels -> R, the only reader of conv1's output besides the excite kernel
 //   mse_diff_kernel<R>           c = depthwise 3x3 of b (never stored), d+[t] = c[t + 1] - b[t], d-[t] = c[t - 1] - b[t] (zero at the
@@ -53,6 +54,85 @@ __global__ void __launch_bounds__(kTdnThreads) tdn_front_kernel(const float *__r
       for (int pl = 0; pl < kTdnPlanes; ++pl)
 #pragma unroll
         for (int r = 0; r < 2; ++r) v[pl][r] = *reinterpret_cast<const f32x2 *>(xf + ((int64_t)pl * H + 2 * py + r) * W + 2 * px);
+#pragma unroll
+      for (int c = 0; c < kTdnDiffC; ++c) {
+        const f32x2 d0 = v[c + 3][0] - v[c][0], d1 = v[c + 3][1] - v[c][1];
+        p[c] = ((d0[0] + d0[1]) + (d1[0] + d1[1])) * 0.25f;
+      }
+      if (ty >= 3 && ty < 3 + 2 * kTdnTile && tx >= 3 && tx < 3 + 2 * kTdnTile) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const f32x4 px4 = {v[6][r][q], v[7][r][q], v[8][r][q], 0.f};
+            *reinterpret_cast<f32x4 *>(in4 + ((f * H + 2 * py + r) * W + 2 * px + q) * 4) = px4;
+          }
+      }
+    }
+#pragma unroll
+    for (int c4 = 0; c4 < kTdnDiffC / 4; ++c4) {
+      const f32x4 o = {p[4 * c4], p[4 * c4 + 1], p[4 * c4 + 2], p[4 * c4 + 3]};
+      *reinterpret_cast<f32x4 *>(tile + idx * kTdnDiffC + 4 * c4) = o;
+    }
+  }
+  __syncthreads();
+  // a thread keeps its K quad for all 64 rows: one row (4 KB) per pass of the workgroup
+  const int k = 4 * (int)threadIdx.x;
+  const bool real = k < kTdnPatchReal;
+  const int ky = k / (7 * kTdnDiffC), rem = k - ky * (7 * kTdnDiffC);
+  for (int row = 0; row < kTdnTile * kTdnTile; ++row) {
+    const int oyl = row / kTdnTile, oxl = row - oyl * kTdnTile;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (real) o = *reinterpret_cast<const f32x4 *>(tile + ((2 * oyl + ky) * kPT + 2 * oxl) * kTdnDiffC + rem);
+    *reinterpret_cast<f32x4 *>(patches + ((f * ho + oy0 + oyl) * wo + ox0 + oxl) * kTdnPatchK + k) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// tdn_front_pool_kernel (TSM_LAYOUT_TDN_POOL): tdn_front_kernel with its 15 planes found in a pool of transformed frames
+// [n_frames, 3, H, W]: plane pl of segment blockIdx.y is channel pl % 3 of pool frame frame_of(segment, pl / 3), from the table
+// (mode 0: src.index [segments][5], an entry outside the pool stands for planes of 0.0f) or from the window rule (mode 1:
+// tsm_host::tdn_window_frame).  The five frame numbers depend on blockIdx alone: they are fetched (scalar loads) or computed once
+// per workgroup and live in scalar registers; a missing frame is a null pointer and a uniform branch, never a load.  Everything
+// else -- the cells, the order of every sum, the stores -- is tdn_front_kernel's, spelled the same way: the same bits as that
+// kernel on the gathered planes.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kTdnThreads) tdn_front_pool_kernel(const tsm_host::TdnPoolSource src, float *__restrict__ in4,
+                                                                     float *__restrict__ patches, int H, int W) {
+  using namespace tsm_host;
+  __shared__ __attribute__((aligned(16))) float tile[kPT * kPT * kTdnDiffC];
+  const int hp = H / 2, wp = W / 2, ho = H / 4, wo = W / 4;
+  const int tiles_x = wo / kTdnTile;
+  const int oy0 = (int)(blockIdx.x / tiles_x) * kTdnTile, ox0 = (int)(blockIdx.x % tiles_x) * kTdnTile;
+  const int64_t f = blockIdx.y;
+  const float *fr[kTdnFrames];   // the segment's five frames, nullptr: planes of zeros
+  {
+    const int64_t dc = f / src.T;
+    const int64_t clip = src.first_clip > INT64_MAX - dc ? INT64_MAX : src.first_clip + dc;
+    const int k = (int)(f - dc * src.T);
+#pragma unroll
+    for (int j = 0; j < kTdnFrames; ++j) {
+      const int64_t n = src.mode == 0 ? tdn_table_frame(src.index[f * kTdnFrames + j], src.limit)
+                                      : tdn_window_frame(src.first_source_frame, src.total_frames, clip, k, j, src.clip_step,
+                                                         src.clip_stride, src.n_frames, src.pad_frame);
+      fr[j] = n >= 0 ? src.frames + n * 3 * (int64_t)H * W : nullptr;
+    }
+  }
+  for (int idx = threadIdx.x; idx < kPT * kPT; idx += kTdnThreads) {
+    const int ty = idx / kPT, tx = idx - ty * kPT;
+    const int py = 2 * oy0 - 3 + ty, px = 2 * ox0 - 3 + tx;
+    float p[kTdnDiffC];
+#pragma unroll
+    for (int c = 0; c < kTdnDiffC; ++c) p[c] = 0.f;
+    if (py >= 0 && py < hp && px >= 0 && px < wp) {
+      f32x2 v[kTdnPlanes][2];
+#pragma unroll
+      for (int pl = 0; pl < kTdnPlanes; ++pl)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const f32x2 zero = {0.f, 0.f};
+          v[pl][r] = fr[pl / 3] ? *reinterpret_cast<const f32x2 *>(fr[pl / 3] + ((int64_t)(pl % 3) * H + 2 * py + r) * W + 2 * px) : zero;
+        }
 #pragma unroll
       for (int c = 0; c < kTdnDiffC; ++c) {
         const f32x2 d0 = v[c + 3][0] - v[c][0], d1 = v[c + 3][1] - v[c][1];
@@ -357,6 +437,17 @@ hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_fr
   const int64_t tiles = (int64_t)(h / 4 / tsm_host::kTdnTile) * (w / 4 / tsm_host::kTdnTile);
   if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
   TSM_KLAUNCH(tdn_front_kernel, dim3((unsigned)tiles, (unsigned)n_frames), dim3(kTdnThreads), 0, s, x, in4, patches, h, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_tdn_front_pool(const tsm_host::TdnPoolSource &src, float *in4, float *patches, int n_segments, int h, int w, hipStream_t s) {
+  if (!src.frames || reinterpret_cast<uintptr_t>(src.frames) % 8 != 0 || src.n_frames <= 0 || (src.mode != 0 && src.mode != 1) ||
+      (src.mode == 0 && !src.index) || src.T <= 0 || src.limit != tsm_host::tdn_table_limit(src.n_frames))
+    return hipErrorInvalidValue;
+  if (!in4 || !patches || n_segments <= 0 || n_segments > 65535 || h < 64 || w < 64 || h % 32 != 0 || w % 32 != 0) return hipErrorInvalidValue;
+  const int64_t tiles = (int64_t)(h / 4 / tsm_host::kTdnTile) * (w / 4 / tsm_host::kTdnTile);
+  if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
+  TSM_KLAUNCH(tdn_front_pool_kernel, dim3((unsigned)tiles, (unsigned)n_segments), dim3(kTdnThreads), 0, s, src, in4, patches, h, w);
   return hipGetLastError();
 }
 

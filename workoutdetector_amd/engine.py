@@ -298,6 +298,101 @@ class TsmEngine:
                                                       o.ctypes.data, int(bool(normalize)), None), self._h)
         return res
 
+    # ---- a TDN engine's input as a pool of transformed frames (include/tsm_hip.h: TSM_LAYOUT_TDN_POOL) ------------------
+    def _pool_descriptors(self, frames, index, window, n_clips: int):
+        """The checks of ``forward_pool`` (the C ABI takes bare pointers) and one ``TsmTdnPool`` per ``max_clips`` chunk:
+        [(first clip of the chunk, clips in it, descriptor)]."""
+        import torch
+        self._need_finalized()
+        if not self.tdn_depths:
+            raise ValueError('forward_pool goes with a TDN engine (base_model=%r) only' % TDN)
+        if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous()):
+            raise ValueError('frames must be a contiguous float32 CUDA tensor [n_frames, 3, H, W]')
+        if frames.device.index != self.device:
+            raise ValueError(f'tensor on cuda:{frames.device.index}, engine on cuda:{self.device}')
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (3, self.height, self.width) or frames.shape[0] < 1:
+            raise ValueError(f'frames must be [n_frames, 3, {self.height}, {self.width}], got {tuple(frames.shape)}')
+        n_clips = int(n_clips)
+        if n_clips <= 0:
+            raise ValueError('n_clips must be positive')
+        if (index is None) == (window is None):
+            raise ValueError('give exactly one of index (table mode) and window= (window mode)')
+        T = self.num_segments
+        if index is not None:
+            if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
+                    and index.is_contiguous() and index.numel() == n_clips * T * TDN_FRAMES):
+                raise ValueError(f'index must be a contiguous int32 tensor of {n_clips} x {T} x {TDN_FRAMES} pool frame numbers on {frames.device}')
+        else:
+            keys = ('first_source_frame', 'total_frames', 'first_clip', 'clip_step', 'clip_stride', 'pad_frame')
+            if not isinstance(window, Mapping) or set(window) != set(keys):
+                raise ValueError(f'window= must be a mapping with exactly the keys {keys}')
+            window = {k: int(window[k]) for k in keys}
+        out = []
+        for s in range(0, n_clips, self.max_clips):
+            d = _lib.TsmTdnPool(struct_size=C.sizeof(_lib.TsmTdnPool), frames=frames.data_ptr(), n_frames=frames.shape[0])
+            if index is not None:
+                d.mode = _lib.TDN_POOL_TABLE
+                d.index = index.data_ptr() + 4 * s * T * TDN_FRAMES
+            else:
+                d.mode = _lib.TDN_POOL_WINDOW
+                for k, v in window.items():
+                    setattr(d, k, v)
+                d.first_clip = window['first_clip'] + s
+            out.append((s, min(self.max_clips, n_clips - s), d))
+        return out
+
+    def forward_pool(self, frames, index=None, *, window=None, n_clips: int, out=None):
+        """The forward of a TDN engine on clips whose frames are FOUND in a pool (``tsm_forward`` with TSM_LAYOUT_TDN_POOL): no
+        [B, T, 15, H, W] tensor exists.  frames: contiguous float32 CUDA tensor [n_frames, 3, H, W] of transformed frames, what
+        ``preprocess_frames(packed=False)`` writes.  Exactly one of
+
+        * ``index`` (table mode): int32 CUDA tensor [n_clips, T, 5] of pool frame numbers, read on the device when the kernel runs;
+          an entry outside ``[0, n_frames)`` stands for a frame of zeros;
+        * ``window=dict(first_source_frame, total_frames, first_clip, clip_step, clip_stride, pad_frame)`` (window mode): segment
+          k of clip c has centre ``clip_step * c + clip_stride * k``, frame j is ``clamp(centre - 2 + j, 0, total_frames - 1) -
+          first_source_frame``; a centre past the end or a frame outside the pool takes ``pad_frame``
+          (``tdn_pipeline.tdn_clip_indices`` is the same rule in NumPy).  Nothing is uploaded.
+
+        Enqueues on torch's current stream and returns what ``forward_device`` returns, bit for bit that of the gathered
+        planes; more than ``max_clips`` clips run in chunks."""
+        import torch
+        chunks = self._pool_descriptors(frames, index, window, n_clips)
+        out = _out(out, self._out_shape(int(n_clips)), torch.float32, frames)
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        for s, n, d in chunks:
+            _lib.check(self._lib.tsm_forward(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, n, out[s:s + n].data_ptr(),
+                                             stream), self._h)
+        return out
+
+    def forward_features_pool(self, frames, index=None, *, window=None, n_clips: int, normalize: bool = False, out=None):
+        """``forward_features`` on the clips ``forward_pool`` describes: float32 CUDA [n_clips * T, feature_dim]."""
+        import torch
+        chunks = self._pool_descriptors(frames, index, window, n_clips)
+        t = self.out_segments
+        out = _out(out, (int(n_clips) * t, self.feature_dim), torch.float32, frames)
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        for s, n, d in chunks:
+            _lib.check(self._lib.tsm_forward_features(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, n,
+                                                      out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
+        return out
+
+    def forward_tap_pool(self, frames, stage: str, index=None, *, window=None, n_clips: int) -> np.ndarray:
+        """``forward_tap`` on the clips ``forward_pool`` describes (at most ``max_clips``): the activation behind ``stage`` as an
+        NHWC float32 ndarray (parity tests)."""
+        import torch
+        chunks = self._pool_descriptors(frames, index, window, n_clips)
+        if len(chunks) != 1:
+            raise ValueError(f'forward_tap_pool takes at most max_clips = {self.max_clips} clips')
+        n = int(n_clips) * self.num_segments
+        cap = n * self.height * self.width * 16         # (forward_tap's bound: the stem conv's output, layer1's)
+        buf = torch.empty(cap, dtype=torch.float32, device=frames.device)
+        shape = (C.c_int64 * 4)()
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        _lib.check(self._lib.tsm_forward_tap(self._h, C.addressof(chunks[0][2]), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, int(n_clips),
+                                             stage.encode(), buf.data_ptr(), cap, shape, stream), self._h)
+        dims = tuple(int(v) for v in shape)
+        return buf[:int(np.prod(dims))].reshape(dims).cpu().numpy()
+
     def warmup(self, batch_sizes: Optional[Sequence[int]] = None) -> 'TsmEngine':
         """Tune every power-of-two bucket of the clip count that will occur (default: 1, 2, 4, ... max_clips) now
         (``tsm_tune``: a few hundred ms each of timed launches on the engine's own zeroed input buffer, or nothing when

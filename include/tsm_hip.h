@@ -106,9 +106,13 @@ typedef enum tsm_layout {
                              stride-2 stem then reads 4 aligned pairs per kernel row); device memory only */
   TSM_LAYOUT_NTHWC8B = 4, /* bf16 [B,T,H,ceil(W/2),8]: the same pixel pairs, 16 bytes per pair -- for a
                              TSM_DTYPE_BF16 engine */
-  TSM_LAYOUT_TDN_POOL = 16 /* a TDN engine only: `clips` points to a tsm_tdn_pool in HOST memory (below, beside tsm_set_tdn), which
-                              names a pool of transformed frames in device memory; memkind must be TSM_MEM_DEVICE.  Not an
-                              out_layout of the tsm_preprocess* entry points */
+  TSM_LAYOUT_TDN_POOL = 16, /* a TDN engine only: `clips` points to a tsm_tdn_pool in HOST memory (below, beside tsm_set_tdn), which
+                               names a pool of transformed frames in device memory; memkind must be TSM_MEM_DEVICE.  Not an
+                               out_layout of the tsm_preprocess* entry points */
+  TSM_LAYOUT_TDN_SEGMENTS = 17, /* a TDN engine only, the SEGMENT phase of the two-phase forward (beside tsm_set_tdn): `clips` points
+                                   to a tsm_tdn_segments in HOST memory; n_clips counts segments; memkind must be TSM_MEM_DEVICE */
+  TSM_LAYOUT_TDN_RING = 18 /* a TDN engine only, the TRUNK phase: `clips` points to a tsm_tdn_ring in HOST memory naming a ring of
+                              per-segment features and a table of slot numbers in device memory; memkind must be TSM_MEM_DEVICE */
 } tsm_layout;
 
 /* The input of a TDN forward as a pool of frames (TSM_LAYOUT_TDN_POOL; the contract stands beside tsm_set_tdn). */
@@ -122,6 +126,30 @@ typedef struct tsm_tdn_pool {
   int32_t clip_step, clip_stride;                       /* mode 1 */
   int64_t pad_frame;           /* mode 1: pool frame standing for "no frame"; < 0 or >= n_frames: zero planes */
 } tsm_tdn_pool;
+
+/* The segment phase of a TDN forward (TSM_LAYOUT_TDN_SEGMENTS): where the frames are -- tsm_tdn_pool's fields, one SEGMENT where
+ * that struct has a clip -- and where the two per-segment feature maps go. */
+typedef struct tsm_tdn_segments {
+  uint32_t struct_size;        /* sizeof(tsm_tdn_segments) */
+  int32_t mode;                /* 0 table, 1 window */
+  const float *frames;         /* device, [n_frames, 3, H, W], 8-byte aligned */
+  int64_t n_frames;
+  const int32_t *index;        /* mode 0: device, [n, 5] */
+  int64_t first_source_frame, total_frames, first_clip; /* mode 1: segment i has centre clip_stride * (first_clip + i) */
+  int32_t clip_step, clip_stride;                       /* mode 1 (clip_step is not read: a segment is its own clip) */
+  int64_t pad_frame;           /* mode 1, as tsm_tdn_pool's */
+  float *out_a;                /* device, [n, H / 4, W / 4, 256]: layer1's output before the blend; 16-byte aligned */
+  float *out_d;                /* device, [n, H / 8, W / 8, 256]: resnext_layer1's output; 16-byte aligned */
+} tsm_tdn_segments;
+
+/* The trunk phase of a TDN forward (TSM_LAYOUT_TDN_RING): segment k of clip c is slot table[c * T + k] of the ring. */
+typedef struct tsm_tdn_ring {
+  uint32_t struct_size;        /* sizeof(tsm_tdn_ring) */
+  int32_t n_slots;             /* > 0 */
+  const float *ring_a;         /* device, [n_slots, H / 4, W / 4, 256], 16-byte aligned */
+  const float *ring_d;         /* device, [n_slots, H / 8, W / 8, 256], 16-byte aligned */
+  const int32_t *table;        /* device, int32 [n_clips, T] of slot numbers; an entry outside [0, n_slots) stands for zeros */
+} tsm_tdn_ring;
 
 /* The staged frames of a frame transform (tsm_preprocess, _clips, _indexed, _windows).
  *   TSM_PIXEL_U8 / TSM_PIXEL_F32   [h, w, 3] RGB, values 0..255.
@@ -381,7 +409,33 @@ int tsm_set_convnext(tsm_engine *e, const int32_t depths[4]);
  * TSM_ERR_UNSUPPORTED: the layout on an engine without tsm_set_tdn.  TSM_ERR_INVALID_ARG: TSM_MEM_HOST; a struct_size other than
  * sizeof(tsm_tdn_pool); frames NULL or not 8-byte aligned; n_frames <= 0; a mode other than 0 or 1; mode 0 with index NULL; mode 1
  * with clip_step <= 0, clip_stride <= 0 or total_frames <= 0.  Nothing is launched on a refusal.  The first call of a bucket
- * tunes exactly as an NTCHW call does (on the pool it was given); after tuning the call only enqueues and is capture-safe. */
+ * tunes exactly as an NTCHW call does (on the pool it was given); after tuning the call only enqueues and is capture-safe.
+ *
+ * THE FORWARD IN TWO PHASES.  Everything in front of fuse2 is computed per segment and never looks at a neighbouring segment; only
+ * fuse2 onward mixes the segments of a clip.  The two layouts below cut the forward at that seam, so that a segment shared by
+ * overlapping clips (or kept between the steps of a live stream) is computed once.  Every kernel keeps one summation order per
+ * output whatever the batch: segment phase + trunk phase give the bits of the whole forward on the same frames.
+ *   TSM_LAYOUT_TDN_SEGMENTS (segment phase): `clips` is a tsm_tdn_segments in host memory, n_clips counts SEGMENTS, 1 .. max_clips *
+ *     T; `logits` is ignored and may be NULL.  Segment i reads pool frames index[5 i .. 5 i + 4] (mode 0) or has centre clip_stride *
+ *     (first_clip + i) (mode 1: tdn_front_pool_kernel with T = 1 and clip_step = clip_stride).  Launches: the chunked diff.front +
+ *     diff.conv1_5, diff.maxpool, conv1, fuse1 and the blocks of resnext_layer1 and layer1, whose last blocks write straight to
+ *     out_d [n, H / 8, W / 8, 256] and out_a [n, H / 4, W / 4, 256]: no fuse2, nothing behind it, no copy.  Taps: the names up to
+ *     "layer1.B"; "fuse2" and later are TSM_ERR_INVALID_ARG.  tsm_forward_features is TSM_ERR_UNSUPPORTED.
+ *   TSM_LAYOUT_TDN_RING (trunk phase): `clips` is a tsm_tdn_ring in host memory; `table` is int32 [n_clips, T] in device memory, read
+ *     on the device when the kernel runs (at replay, for a captured call).  One tdn_fuse_ring_kernel launch takes the fuse2 slot:
+ *     x[c, k] = alpha ring_a[slot] + beta up(ring_d[slot]), slot = table[c * T + k], into the trunk's own buffer -- tdn_fuse_kernel's
+ *     expression on the gathered operands, bit for bit, moving the bytes fuse2 moves; it is total in the table: a slot outside
+ *     [0, n_slots) reads nothing and stands for zeros.  Then layers 2 - 4 and the head (or the feature rows, or a tap) as in a whole
+ *     forward.  Taps: "fuse2" onward; earlier names are TSM_ERR_INVALID_ARG.
+ * Both: TSM_ERR_UNSUPPORTED on an engine without tsm_set_tdn; TSM_ERR_INVALID_ARG for TSM_MEM_HOST, a struct_size other than the
+ * struct's, a NULL pointer, frames not 8-byte aligned, out_a / out_d / ring_a / ring_d not 16-byte aligned, table not 4-byte
+ * aligned, n_slots <= 0, a segment count of 0 (TSM_ERR_CAPACITY above max_clips * T) and tsm_tdn_pool's refusals; nothing is
+ * launched on a refusal.  The descriptors are read during the call and never dereferenced later.  Timing slots keep those of a whole
+ * forward: the launches a phase does not make are "not recorded".  Tuning: the first call of a bucket tunes inside the call, the
+ * convs of its own phase only, after which the call only enqueues and is capture-safe.  The phases keep tile codes of their own,
+ * apart from whole forwards' (whose buckets are tuned once, all convs): a segment-phase bucket is keyed by the power-of-two bucket
+ * of its FRAME count (= segments) plus 2^28, a trunk-phase bucket by bucket(n_clips) * T frames plus 2^29; tsm_conv_tiles reports
+ * whole forwards' buckets only. */
 int tsm_set_tdn(tsm_engine *e, const int32_t depths[4], float alpha, float beta);
 
 /* Hand one state-dict tensor to the engine (host memory, float32, torch layout: conv OIHW,

@@ -13,6 +13,8 @@ ABI_VERSION = 7
 MEM_HOST, MEM_DEVICE = 0, 1
 LAYOUT_NTCHW, LAYOUT_NTHWC, LAYOUT_NTHWC4, LAYOUT_NTHWC8S, LAYOUT_NTHWC8B = 0, 1, 2, 3, 4
 LAYOUT_TDN_POOL = 16      # a TDN engine's input as a TsmTdnPool descriptor (host memory) naming device memory
+LAYOUT_TDN_SEGMENTS = 17  # the segment phase of a TDN forward: a TsmTdnSegments descriptor, n_clips counts segments
+LAYOUT_TDN_RING = 18      # the trunk phase: a TsmTdnRing descriptor naming a ring of per-segment features and a slot table
 TDN_POOL_TABLE, TDN_POOL_WINDOW = 0, 1
 PIXEL_U8, PIXEL_F32 = 0, 1
 PIXEL_NV12_BT601, PIXEL_NV12_BT709, PIXEL_NV12_BT601_FULL, PIXEL_NV12_BT709_FULL = 16, 17, 18, 19
@@ -71,6 +73,17 @@ class TsmTdnPool(C.Structure):
     _fields_ = [('struct_size', C.c_uint32), ('mode', C.c_int32), ('frames', C.c_void_p), ('n_frames', C.c_int64),
                 ('index', C.c_void_p), ('first_source_frame', C.c_int64), ('total_frames', C.c_int64), ('first_clip', C.c_int64),
                 ('clip_step', C.c_int32), ('clip_stride', C.c_int32), ('pad_frame', C.c_int64)]
+
+
+class TsmTdnSegments(C.Structure):
+    """struct tsm_tdn_segments (include/tsm_hip.h): what ``clips`` points to with LAYOUT_TDN_SEGMENTS."""
+    _fields_ = TsmTdnPool._fields_ + [('out_a', C.c_void_p), ('out_d', C.c_void_p)]
+
+
+class TsmTdnRing(C.Structure):
+    """struct tsm_tdn_ring (include/tsm_hip.h): what ``clips`` points to with LAYOUT_TDN_RING."""
+    _fields_ = [('struct_size', C.c_uint32), ('n_slots', C.c_int32), ('ring_a', C.c_void_p), ('ring_d', C.c_void_p),
+                ('table', C.c_void_p)]
 
 
 class TsmError(RuntimeError):

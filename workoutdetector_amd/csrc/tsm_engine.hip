@@ -202,6 +202,8 @@ struct tsm_engine {
   std::vector<TdnMse> tdn_mse;
   int tdn_chunk = 0;          // clips per front-end chunk (tdn_chunk_clips)
   tsm_tdn_pool tdn_pool{};    // TSM_LAYOUT_TDN_POOL: the caller's descriptor, copied behind its checks, for the running call only
+  tsm_tdn_segments tdn_seg{}; // TSM_LAYOUT_TDN_SEGMENTS: the same (its frame fields also go into tdn_pool: tdn_segments_pool)
+  tsm_tdn_ring tdn_ring{};    // TSM_LAYOUT_TDN_RING: the same
   int hd = 0, wd = 0;         // the difference path's maps (xd0, resnext_layer1)
   float *d_patches = nullptr; // conv1_5's patch rows of one chunk
   // the long-term module's r-channel maps: b, d+, d-, m+, m- at the block's size; pooled d+, d-, s2+, s2- at half of it
@@ -1292,45 +1294,66 @@ int run_head(tsm_engine *e, const float *cur, int n, int n_clips, int hw, float 
 //   head.
 // Buffers: xd0 in buf[0] and the stem's output in buf[4]; resnext_layer1 rotates buf[0] and buf[1], the trunk buf[4] and whichever
 // of buf[0] / buf[1] does not hold xd1; behind fuse2 xd1's buffer is dead and holds o, the long-term module's output.
+//
+// The two phases (include/tsm_hip.h, beside tsm_set_tdn) cut this schedule in front of fuse2 and keep its timing slots:
+//   TSM_LAYOUT_TDN_SEGMENTS: n_clips counts segments; the launches up to layer1's last block, the last blocks of resnext_layer1 and
+//     layer1 writing to e->tdn_seg.out_d / out_a; the slots of fuse2 and everything behind it are skipped;
+//   TSM_LAYOUT_TDN_RING: the slots in front of fuse2 are skipped; tdn_fuse_ring_kernel writes x from e->tdn_ring into buf[4] in
+//     fuse2's slot, then the BottleneckShift stages and the head as above (buf[4] and buf[1] rotate, buf[0] holds o).
 int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int layout, int n_clips, float *d_logits, hipStream_t s) {
   const tsm_config &cfg = e->cfg;
-  const int T = cfg.num_segments, n = n_clips * T, H = cfg.height, W = cfg.width, prec = e->prec;
+  const bool seg_phase = layout == TSM_LAYOUT_TDN_SEGMENTS, ring_phase = layout == TSM_LAYOUT_TDN_RING;
+  const int T = cfg.num_segments, n = seg_phase ? n_clips : n_clips * T, H = cfg.height, W = cfg.width, prec = e->prec;
   const int h5 = tdn_conv15_size(H), w5 = tdn_conv15_size(W);
   const int64_t plane = (int64_t)H * W, rows = (int64_t)h5 * w5;
   float *xc5 = f.t2;
   const int max_chunks = (cfg.max_clips + e->tdn_chunk - 1) / e->tdn_chunk;
-  int chunks = 0;
-  for (int c0 = 0; c0 < n_clips; c0 += e->tdn_chunk, ++chunks) {
-    const int nf = std::min(e->tdn_chunk, n_clips - c0) * T;
-    const int64_t f0 = (int64_t)c0 * T;
-    if (layout == TSM_LAYOUT_TDN_POOL) {
-      TSM_LAUNCH(e, s, tsm::launch_tdn_front_pool(tdn_pool_source(e->tdn_pool, T, c0), e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
-    } else {
-      TSM_LAUNCH(e, s, tsm::launch_tdn_front(d_clips + f0 * kTdnPlanes * plane, e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
-    }
-    // (the tuning pass times conv1_5's candidates on its first chunk only; a later, smaller chunk re-validates the code: checked_code)
-    tsm::ConvParams p = make_params(e->convs[1], e->d_patches, nullptr, xc5 + f0 * rows * 64, nf, h5, w5, true, 0, 1, prec);
-    const bool was_tuning = f.tuning;
-    if (chunks > 0) f.tuning = false;
-    const int rc = f.conv(1, p, 1, false);
-    f.tuning = was_tuning;
-    if (rc) return rc;
-  }
-  skip_slots(e, 2 * (max_chunks - chunks));
-  if (f.want("diff.conv1_5")) return f.hit(xc5, n, h5, w5, 64);
   float *xd0 = e->buf[0], *stem = e->buf[4];
-  TSM_LAUNCH(e, s, tsm::launch_maxpool3x3s2(xc5, xd0, n, h5, w5, 64, prec, s));
-  if (f.want("diff.stem")) return f.hit(xd0, n, e->hd, e->wd, 64);
-  TSM_LAUNCH(e, s, tsm::launch_stem_pool(e->d_in4, e->convs[0].d_w, e->convs[0].d_b, stem, n, H, W, e->convs[0].kp, 1, prec, s, 0));
-  if (f.want("stem")) return f.hit(stem, n, e->hp, e->wp, 64);
-  TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(stem, xd0, n, e->hp, e->wp, e->hd, e->wd, 64, e->tdn_alpha, e->tdn_beta, s));
-  if (f.want("fuse1")) return f.hit(stem, n, e->hp, e->wp, 64);
+  if (ring_phase) {   // the trunk phase: nothing in front of fuse2 runs
+    skip_slots(e, 2 * max_chunks + 3);
+  } else {
+    // (the segment phase: a segment is a clip of one segment -- e->tdn_pool is tdn_segments_pool's -- in chunks of as many frames)
+    const int chunk_frames = e->tdn_chunk * T, seg_T = seg_phase ? 1 : T;
+    int chunks = 0;
+    for (int f0 = 0; f0 < n; f0 += chunk_frames, ++chunks) {
+      const int nf = std::min(chunk_frames, n - f0);
+      if (layout == TSM_LAYOUT_TDN_POOL || seg_phase) {
+        TSM_LAUNCH(e, s, tsm::launch_tdn_front_pool(tdn_pool_source(e->tdn_pool, seg_T, f0 / seg_T), e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+      } else {
+        TSM_LAUNCH(e, s, tsm::launch_tdn_front(d_clips + f0 * kTdnPlanes * plane, e->d_in4 + f0 * 4 * plane, e->d_patches, nf, H, W, s));
+      }
+      // (the tuning pass times conv1_5's candidates on its first chunk only; a later, smaller chunk re-validates the code: checked_code)
+      tsm::ConvParams p = make_params(e->convs[1], e->d_patches, nullptr, xc5 + f0 * rows * 64, nf, h5, w5, true, 0, 1, prec);
+      const bool was_tuning = f.tuning;
+      if (chunks > 0) f.tuning = false;
+      const int rc = f.conv(1, p, 1, false);
+      f.tuning = was_tuning;
+      if (rc) return rc;
+    }
+    skip_slots(e, 2 * (max_chunks - chunks));
+    if (f.want("diff.conv1_5")) return f.hit(xc5, n, h5, w5, 64);
+    TSM_LAUNCH(e, s, tsm::launch_maxpool3x3s2(xc5, xd0, n, h5, w5, 64, prec, s));
+    if (f.want("diff.stem")) return f.hit(xd0, n, e->hd, e->wd, 64);
+    TSM_LAUNCH(e, s, tsm::launch_stem_pool(e->d_in4, e->convs[0].d_w, e->convs[0].d_b, stem, n, H, W, e->convs[0].kp, 1, prec, s, 0));
+    if (f.want("stem")) return f.hit(stem, n, e->hp, e->wp, 64);
+    TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(stem, xd0, n, e->hp, e->wp, e->hd, e->wd, 64, e->tdn_alpha, e->tdn_beta, s));
+    if (f.want("fuse1")) return f.hit(stem, n, e->hp, e->wp, 64);
+  }
 
   const std::vector<BlockPlan> plan = f.tuning ? std::vector<BlockPlan>() : plan_forward(e, f.tiles, n, f.stage);
   float *cur = xd0, *out = e->buf[1], *xd1 = nullptr;
   int h = e->hd, w = e->wd;
   for (size_t k = 0; k < e->blocks.size(); ++k) {
     const Block &blk = e->blocks[k];
+    const int conv_slots = (blk.down >= 0 ? 1 : 0) + 3;
+    if (ring_phase && blk.mse < 0) {   // resnext_layer1 and layer1 ran in the segment phase
+      skip_slots(e, conv_slots);
+      continue;
+    }
+    if (seg_phase && blk.mse >= 0) {   // behind the seam: fuse2 (in front of the first BottleneckShift), the block's convs and its long-term module
+      skip_slots(e, (blk.mse == 0 ? 1 : 0) + conv_slots + 5);
+      continue;
+    }
     if (!blk.diff_path && k > 0 && e->blocks[k - 1].diff_path) {   // the trunk starts: layer1 reads the blended stem
       xd1 = cur;
       f.obuf = xd1;   // (dead behind fuse2, which runs before the first BottleneckShift)
@@ -1340,16 +1363,42 @@ int run_tdn(tsm_engine *e, Forward &f, const float *d_clips, int layout, int n_c
       w = e->wp;
     }
     if (blk.mse == 0) {   // the first BottleneckShift: layer1 is done
-      TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(cur, xd1, n, h, w, e->hd, e->wd, 256, e->tdn_alpha, e->tdn_beta, s));
+      if (ring_phase) {   // x from the ring, into the trunk's own buffers: buf[4] and buf[1] rotate, buf[0] holds o
+        cur = stem;
+        out = e->buf[1];
+        f.obuf = e->buf[0];
+        h = e->hp;
+        w = e->wp;
+        TSM_LAUNCH(e, s, tsm::launch_tdn_fuse_ring(e->tdn_ring.ring_a, e->tdn_ring.ring_d, e->tdn_ring.table, e->tdn_ring.n_slots, cur, n, h, w,
+                                                   e->hd, e->wd, 256, e->tdn_alpha, e->tdn_beta, s));
+      } else {
+        TSM_LAUNCH(e, s, tsm::launch_tdn_fuse(cur, xd1, n, h, w, e->hd, e->wd, 256, e->tdn_alpha, e->tdn_beta, s));
+      }
       if (f.want("fuse2")) return f.hit(cur, n, h, w, 256);
     }
-    const int rc = f.tuning ? f.tune_block(k, n, cur, out, h, w) : f.run_block(k, plan[k], n, cur, out, h, w);
+    // the segment phase: the last block of resnext_layer1 and of layer1 write straight to the caller's out_d / out_a
+    float *dst = out;
+    if (seg_phase && (k + 1 == e->blocks.size() || e->blocks[k + 1].diff_path != blk.diff_path || e->blocks[k + 1].mse >= 0))
+      dst = blk.diff_path ? e->tdn_seg.out_d : e->tdn_seg.out_a;
+    const int rc = f.tuning ? f.tune_block(k, n, cur, dst, h, w) : f.run_block(k, plan[k], n, cur, dst, h, w);
     if (rc || f.tapped) return rc;
-    std::swap(cur, out);
+    if (dst == out) std::swap(cur, out);
     h = conv_out_size(h, 3, blk.stride);
     w = conv_out_size(w, 3, blk.stride);
   }
+  if (seg_phase) {
+    skip_slots(e, 1);   // the head
+    return f.stage ? fail(e, TSM_ERR_INVALID_ARG, std::string("unknown stage: ") + f.stage) : (int)TSM_OK;
+  }
   return run_head(e, cur, n, n_clips, h * w, d_logits, s, f.stage);
+}
+
+// The tile-cache key of a call: the bucket's frame count; the two phases of a TDN forward keep buckets of their own
+// (tsm_host_util.h: kTdnSegmentsKey / kTdnRingKey), so a phase that tunes only its own convs never stands in for a whole forward.
+int tune_key_of(const tsm_engine *e, int layout, int n_clips) {
+  if (layout == TSM_LAYOUT_TDN_SEGMENTS) return kTdnSegmentsKey + tile_bucket(n_clips);
+  if (layout == TSM_LAYOUT_TDN_RING) return kTdnRingKey + tile_bucket(n_clips) * e->cfg.num_segments;
+  return tile_bucket(n_clips) * e->cfg.num_segments;
 }
 
 // Enqueue the forward on `s`.  If `stage` is non-null, stop right after that stage and report it.
@@ -1363,9 +1412,10 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
   // the real launch (all shapes give bit-identical results: the k order per output does not depend on
   // the tile), then cached.  TSM_AUTOTUNE=0 keeps the static heuristic.
   if (e->autotune && !stage) {
-    auto it = e->tile_cache.find(tile_bucket(n_clips) * T);
+    const int key = tune_key_of(e, layout, n_clips);
+    auto it = e->tile_cache.find(key);
     if (it == e->tile_cache.end()) {
-      it = e->tile_cache.emplace(tile_bucket(n_clips) * T, std::vector<int>(e->convs.size(), 0)).first;
+      it = e->tile_cache.emplace(key, std::vector<int>(e->convs.size(), 0)).first;
       f.tuning = true;
     }
     f.tiles = &it->second;
@@ -1445,7 +1495,7 @@ int run_forward(tsm_engine *e, const float *d_clips, int layout, int n_clips, fl
 // the real launches over `d_clips` (synchronises; the codes then go to the cache file).
 int ensure_tuned(tsm_engine *e, const float *d_clips, int layout, int n_clips, float *d_out, hipStream_t s,
                  bool *from_file = nullptr) {
-  const int tune_key = tile_bucket(n_clips) * e->cfg.num_segments;
+  const int tune_key = tune_key_of(e, layout, n_clips);
   if (from_file) *from_file = false;
   if (!e->autotune || e->tile_cache.find(tune_key) != e->tile_cache.end()) return TSM_OK;
   std::vector<int> cached(e->convs.size(), 0);
@@ -1497,8 +1547,21 @@ int check_forward_args(tsm_engine *e, const void *clips, int memkind, int layout
   if (!e->finalized) return fail(e, TSM_ERR_NOT_FINALIZED, "tsm_finalize has not been called");
   if (!clips) return fail(e, TSM_ERR_INVALID_ARG, "clips is NULL");
   if (memkind != TSM_MEM_HOST && memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "bad memkind");
-  if ((layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) && layout != TSM_LAYOUT_TDN_POOL) return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
-  if (layout == TSM_LAYOUT_TDN_POOL) {   // `clips` is a tsm_tdn_pool in host memory: checked and copied here, nothing of it is read later
+  if ((layout < TSM_LAYOUT_NTCHW || layout > TSM_LAYOUT_NTHWC8B) && (layout < TSM_LAYOUT_TDN_POOL || layout > TSM_LAYOUT_TDN_RING))
+    return fail(e, TSM_ERR_INVALID_ARG, "bad layout");
+  if (layout == TSM_LAYOUT_TDN_SEGMENTS || layout == TSM_LAYOUT_TDN_RING) {   // `clips` is a descriptor in host memory, as below
+    const bool seg = layout == TSM_LAYOUT_TDN_SEGMENTS;
+    if (!e->tdn) return fail(e, TSM_ERR_UNSUPPORTED, "TSM_LAYOUT_TDN_SEGMENTS / TSM_LAYOUT_TDN_RING go with a TDN engine (tsm_set_tdn) only");
+    if (memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "the phases of a TDN forward name device memory: memkind must be TSM_MEM_DEVICE");
+    const char *why = seg ? tdn_segments_refusal(static_cast<const tsm_tdn_segments *>(clips)) : tdn_ring_refusal(static_cast<const tsm_tdn_ring *>(clips));
+    if (why) return fail(e, TSM_ERR_INVALID_ARG, why);
+    if (seg) {   // n_clips counts segments
+      const int64_t cap = (int64_t)e->cfg.max_clips * e->cfg.num_segments;
+      if (n_clips <= 0) return fail(e, TSM_ERR_INVALID_ARG, "the segment count must be positive");
+      if (n_clips > cap) return fail(e, TSM_ERR_CAPACITY, "segment count " + std::to_string(n_clips) + " exceeds max_clips * T = " + std::to_string(cap));
+      return TSM_OK;
+    }
+  } else if (layout == TSM_LAYOUT_TDN_POOL) {   // `clips` is a tsm_tdn_pool in host memory: checked and copied here, nothing of it is read later
     if (!e->tdn) return fail(e, TSM_ERR_UNSUPPORTED, "TSM_LAYOUT_TDN_POOL goes with a TDN engine (tsm_set_tdn) only");
     if (memkind != TSM_MEM_DEVICE) return fail(e, TSM_ERR_INVALID_ARG, "TSM_LAYOUT_TDN_POOL names frames in device memory: memkind must be TSM_MEM_DEVICE");
     if (const char *why = tdn_pool_refusal(static_cast<const tsm_tdn_pool *>(clips))) return fail(e, TSM_ERR_INVALID_ARG, why);
@@ -1524,6 +1587,13 @@ int stage_input(tsm_engine *e, const void *clips, int memkind, int layout, int n
   *d_clips = static_cast<const float *>(clips);
   if (layout == TSM_LAYOUT_TDN_POOL) {   // (behind tdn_pool_refusal) the forward reads e->tdn_pool, never `clips`
     e->tdn_pool = *static_cast<const tsm_tdn_pool *>(clips);
+    *d_clips = nullptr;
+  } else if (layout == TSM_LAYOUT_TDN_SEGMENTS) {   // (behind tdn_segments_refusal)
+    e->tdn_seg = *static_cast<const tsm_tdn_segments *>(clips);
+    e->tdn_pool = tdn_segments_pool(e->tdn_seg);
+    *d_clips = nullptr;
+  } else if (layout == TSM_LAYOUT_TDN_RING) {       // (behind tdn_ring_refusal)
+    e->tdn_ring = *static_cast<const tsm_tdn_ring *>(clips);
     *d_clips = nullptr;
   }
   if (memkind == TSM_MEM_HOST) {
@@ -2241,7 +2311,11 @@ static int forward_to(tsm_engine *e, const void *clips, int32_t memkind, int32_t
                       int features, void *stream) {
   int rc = check_forward_args(e, clips, memkind, layout, n_clips);
   if (rc) return rc;
-  if (!out) return fail(e, TSM_ERR_INVALID_ARG, features ? "features is NULL" : "logits is NULL");
+  if (layout == TSM_LAYOUT_TDN_SEGMENTS) {   // the segment phase has no head: its outputs are the descriptor's, `out` is ignored
+    if (features) return fail(e, TSM_ERR_UNSUPPORTED, "tsm_forward_features: TSM_LAYOUT_TDN_SEGMENTS has no feature rows (the trunk phase has)");
+  } else if (!out) {
+    return fail(e, TSM_ERR_INVALID_ARG, features ? "features is NULL" : "logits is NULL");
+  }
   hipStream_t s;
   const float *d_clips;
   if ((rc = stage_input(e, clips, memkind, layout, n_clips, stream, &s, &d_clips))) return rc;
@@ -2334,6 +2408,11 @@ int tsm_forward_tap(tsm_engine *e, const void *clips, int32_t memkind, int32_t l
   int rc = check_forward_args(e, clips, memkind, layout, n_clips);
   if (rc) return rc;
   if (!stage || !out || !out_shape) return fail(e, TSM_ERR_INVALID_ARG, "stage/out/out_shape is NULL");
+  if (layout == TSM_LAYOUT_TDN_SEGMENTS || layout == TSM_LAYOUT_TDN_RING) {   // a stage on the other side of the seam: refused before any launch
+    const bool front = tdn_stage_in_segment_phase(stage);
+    if (front != (layout == TSM_LAYOUT_TDN_SEGMENTS))
+      return fail(e, TSM_ERR_INVALID_ARG, std::string(front ? "the trunk phase starts at fuse2: no stage " : "the segment phase ends with layer1: no stage ") + stage);
+  }
   hipStream_t s;
   const float *d_clips;
   if ((rc = stage_input(e, clips, memkind, layout, n_clips, stream, &s, &d_clips))) return rc;

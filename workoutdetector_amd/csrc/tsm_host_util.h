@@ -850,6 +850,69 @@ inline TdnPoolSource tdn_pool_source(const tsm_tdn_pool &d, int T, int64_t clip0
   }
   return p;
 }
+// ---- The forward in two phases (TSM_LAYOUT_TDN_SEGMENTS / TSM_LAYOUT_TDN_RING) ------------------------------------------------
+// A segment descriptor's frame fields as the tsm_tdn_pool a front-end launch reads: a segment is a clip of ONE segment, so the
+// window rule runs with T = 1 and clip_step = clip_stride (centre = clip_stride * (first_clip + i)).
+inline tsm_tdn_pool tdn_segments_pool(const tsm_tdn_segments &d) {
+  tsm_tdn_pool p{};
+  p.struct_size = sizeof(tsm_tdn_pool);
+  p.mode = d.mode;
+  p.frames = d.frames;
+  p.n_frames = d.n_frames;
+  p.index = d.index;
+  p.first_source_frame = d.first_source_frame;
+  p.total_frames = d.total_frames;
+  p.first_clip = d.first_clip;
+  p.clip_step = d.clip_stride;
+  p.clip_stride = d.clip_stride;
+  p.pad_frame = d.pad_frame;
+  return p;
+}
+// Why a segment-phase call refuses this descriptor (TSM_ERR_INVALID_ARG); nullptr when it can run.
+inline const char *tdn_segments_refusal(const tsm_tdn_segments *d) {
+  if (!d) return "clips is NULL";
+  if (d->struct_size != sizeof(tsm_tdn_segments)) return "tsm_tdn_segments: struct_size is not sizeof(tsm_tdn_segments)";
+  if (d->mode != 0 && d->mode != 1) return "tsm_tdn_segments: mode must be 0 (table) or 1 (window)";
+  if (!d->frames) return "tsm_tdn_segments: frames is NULL";
+  if (reinterpret_cast<uintptr_t>(d->frames) % 8 != 0) return "tsm_tdn_segments: frames must be 8-byte aligned";
+  if (d->n_frames <= 0) return "tsm_tdn_segments: n_frames must be positive";
+  if (d->mode == 0 && !d->index) return "tsm_tdn_segments: table mode needs index";
+  if (d->mode == 0 && reinterpret_cast<uintptr_t>(d->index) % 4 != 0) return "tsm_tdn_segments: index must be 4-byte aligned";
+  if (d->mode == 1 && d->clip_stride <= 0) return "tsm_tdn_segments: clip_stride must be positive";
+  if (d->mode == 1 && d->total_frames <= 0) return "tsm_tdn_segments: total_frames must be positive";
+  if (!d->out_a || !d->out_d) return "tsm_tdn_segments: out_a / out_d is NULL";
+  if (reinterpret_cast<uintptr_t>(d->out_a) % 16 != 0 || reinterpret_cast<uintptr_t>(d->out_d) % 16 != 0)
+    return "tsm_tdn_segments: out_a and out_d must be 16-byte aligned";
+  return nullptr;
+}
+// Why a trunk-phase call refuses this descriptor (TSM_ERR_INVALID_ARG); nullptr when it can run.
+inline const char *tdn_ring_refusal(const tsm_tdn_ring *d) {
+  if (!d) return "clips is NULL";
+  if (d->struct_size != sizeof(tsm_tdn_ring)) return "tsm_tdn_ring: struct_size is not sizeof(tsm_tdn_ring)";
+  if (d->n_slots <= 0) return "tsm_tdn_ring: n_slots must be positive";
+  if (!d->ring_a || !d->ring_d) return "tsm_tdn_ring: ring_a / ring_d is NULL";
+  if (reinterpret_cast<uintptr_t>(d->ring_a) % 16 != 0 || reinterpret_cast<uintptr_t>(d->ring_d) % 16 != 0)
+    return "tsm_tdn_ring: ring_a and ring_d must be 16-byte aligned";
+  if (!d->table) return "tsm_tdn_ring: table is NULL";
+  if (reinterpret_cast<uintptr_t>(d->table) % 4 != 0) return "tsm_tdn_ring: table must be 4-byte aligned";
+  return nullptr;
+}
+// The slot rule, ONE for the kernel and the host: a table entry's ring slot, or -1 for "no segment: zeros".  Range-tested in 32
+// bits, only then widened (total in the entry: INT32_MIN and INT32_MAX are -1 unless inside the ring).
+TSM_HOST_DEVICE inline int64_t tdn_ring_slot(int32_t entry, int32_t n_slots) {
+  return n_slots > 0 && (uint32_t)entry < (uint32_t)n_slots ? (int64_t)entry : -1;
+}
+// Which side of the seam a tap name lies on: true for the stages the segment phase computes ("diff.*", "stem", "fuse1",
+// "resnext_layer1.*", "layer1.*"), false for "fuse2" and everything behind it (and any unknown name: the trunk phase reports it).
+inline bool tdn_stage_in_segment_phase(const char *stage) {
+  if (!stage) return false;
+  const std::string s(stage);
+  auto starts = [&](const char *p) { return s.compare(0, strlen(p), p) == 0; };
+  return s == "stem" || s == "fuse1" || starts("diff.") || starts("resnext_layer1.") || starts("layer1.");
+}
+// Tile-cache keys: a whole forward's bucket is its frame count bucket(n_clips) * T; the phases keep vectors of their own (each
+// tunes only its own convs), keyed by the frame count of the bucket plus a phase tag no whole forward's frame count reaches.
+constexpr int kTdnSegmentsKey = 1 << 28, kTdnRingKey = 1 << 29;
 
 // conv1_5 [64, 12, 7, 7] + its BatchNorm -> [64][kTdnPatchK] in tdn_patch_k's order, the K tail zero.
 inline void tdn_pack_conv15(const float *w, const float *gamma, const float *beta, const float *mean, const float *var, int cout,

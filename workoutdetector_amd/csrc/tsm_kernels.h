@@ -209,6 +209,10 @@ hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_fr
 hipError_t launch_tdn_front_pool(const tsm_host::TdnPoolSource &src, float *in4, float *patches, int n_segments, int h, int w, hipStream_t s);
 // x [n, h, w, c] <- alpha x + beta nearest-upsampled d [n, hd, wd, c], in place
 hipError_t launch_tdn_fuse(float *x, const float *d, int n, int h, int w, int hd, int wd, int c, float alpha, float beta, hipStream_t s);
+// x [n, h, w, c] = alpha ring_a[slot] + beta nearest-upsampled ring_d[slot], slot = tsm_host::tdn_ring_slot(table[segment], n_slots)
+// (device int32 [n]); a slot outside the ring stands for zeros
+hipError_t launch_tdn_fuse_ring(const float *ring_a, const float *ring_d, const int32_t *table, int n_slots, float *x, int n, int h, int w,
+                                int hd, int wd, int c, float alpha, float beta, hipStream_t s);
 // b [m, r] = BN(W1 x), x [m, c]
 hipError_t launch_mse_squeeze(const float *x, const float *wq, const float *bq, float *b, int64_t m, int c, hipStream_t s);
 // d+ / d- [n, h, w, r] and their 2x2 average pools pf / pb [n, h / 2, w / 2, r] from b; n = clips * T

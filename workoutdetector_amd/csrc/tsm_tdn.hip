@@ -188,6 +188,39 @@ __global__ void __launch_bounds__(256) tdn_fuse_kernel(float *__restrict__ x, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// tdn_fuse_ring_kernel (TSM_LAYOUT_TDN_RING): tdn_fuse_kernel with its two operands found in a ring of per-segment features.
+// x [n, h, w, c] = alpha a[slot] + beta d[slot, nearest(y), nearest(x), c], slot = tdn_ring_slot(table[segment], n_slots), a
+// [n_slots, h, w, c], d [n_slots, hd, wd, c]; x is the trunk's own contiguous buffer, so the gather costs no pass of its own: the
+// kernel moves the bytes fuse2 moves.  A workgroup walks 256-quad spans, `spans` of them per segment: the segment and its slot
+// depend on the span alone, so the table entry is one scalar load per (segment, workgroup) and the slot lives in a scalar
+// register; a slot outside the ring is a uniform branch, never a load, and stands for operands of 0.0f.  The same tdn_nearest,
+// the same expression alpha * a + beta * b on the same 16-byte operands: tdn_fuse_kernel's bits.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) tdn_fuse_ring_kernel(const float *__restrict__ ring_a, const float *__restrict__ ring_d,
+                                                            const int32_t *__restrict__ table, float *__restrict__ x, int64_t n_spans,
+                                                            int spans, int32_t n_slots, int h, int w, int hd, int wd, int c4, float alpha,
+                                                            float beta) {
+  const int64_t seg_quads = (int64_t)h * w * c4, d_quads = (int64_t)hd * wd * c4;
+  for (int64_t sp = blockIdx.x; sp < n_spans; sp += gridDim.x) {
+    const int64_t seg = sp / spans;
+    const int64_t slot = tsm_host::tdn_ring_slot(table[seg], n_slots);
+    const int64_t i = (sp - seg * spans) * 256 + threadIdx.x;
+    if (i >= seg_quads) continue;
+    const int q = (int)(i % c4);
+    int64_t pix = i / c4;
+    const int px = (int)(pix % w);
+    const int py = (int)(pix / w);
+    const int sy = tsm_host::tdn_nearest(py, hd, h), sx = tsm_host::tdn_nearest(px, wd, w);
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+    if (slot >= 0) {
+      a = *reinterpret_cast<const f32x4 *>(ring_a + (slot * seg_quads + i) * 4);
+      b = *reinterpret_cast<const f32x4 *>(ring_d + (slot * d_quads + ((int64_t)(sy * wd + sx) * c4 + q)) * 4);
+    }
+    *reinterpret_cast<f32x4 *>(x + (seg * seg_quads + i) * 4) = alpha * a + beta * b;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // mse_squeeze_kernel<R>: b [M, R] = x [M, 16 R] wq [16 R][R] + bq.  A workgroup stages 256 / R rows of x in LDS (16 KB, one
 // contiguous span, 16-byte loads) and a thread owns one output: its row's channels come as LDS broadcasts, the weights as
 // consecutive floats over the lanes of a row.  Four partial sums over c mod 4, then ((a0 + a1) + (a2 + a3)) + bias.
@@ -455,6 +488,19 @@ hipError_t launch_tdn_fuse(float *x, const float *d, int n, int h, int w, int hd
   if (!x || !d || n <= 0 || h <= 0 || w <= 0 || hd <= 0 || wd <= 0 || c <= 0 || c % 4 != 0) return hipErrorInvalidValue;
   const int64_t quads = (int64_t)n * h * w * (c / 4);
   TSM_KLAUNCH(tdn_fuse_kernel, dim3(grid_for(quads, 16384)), dim3(256), 0, s, x, d, quads, h, w, hd, wd, c / 4, alpha, beta);
+  return hipGetLastError();
+}
+
+// n segments of the trunk's buffer x from the ring; the launch cap is tdn_fuse_kernel's (16384 workgroups of 256 quads).
+hipError_t launch_tdn_fuse_ring(const float *ring_a, const float *ring_d, const int32_t *table, int n_slots, float *x, int n, int h, int w,
+                                int hd, int wd, int c, float alpha, float beta, hipStream_t s) {
+  if (!ring_a || !ring_d || !table || !x || n_slots <= 0 || n <= 0 || h <= 0 || w <= 0 || hd <= 0 || wd <= 0 || c <= 0 || c % 4 != 0)
+    return hipErrorInvalidValue;
+  const int64_t seg_quads = (int64_t)h * w * (c / 4), spans = (seg_quads + 255) / 256;
+  if (spans > 0x7fffffffL) return hipErrorInvalidValue;
+  const int64_t n_spans = spans * n;
+  TSM_KLAUNCH(tdn_fuse_ring_kernel, dim3(grid_for(n_spans * 256, 16384)), dim3(256), 0, s, ring_a, ring_d, table, x, n_spans, (int)spans,
+              n_slots, h, w, hd, wd, c / 4, alpha, beta);
   return hipGetLastError();
 }
 

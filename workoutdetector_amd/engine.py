@@ -393,6 +393,131 @@ class TsmEngine:
         dims = tuple(int(v) for v in shape)
         return buf[:int(np.prod(dims))].reshape(dims).cpu().numpy()
 
+    # ---- a TDN forward in two phases (include/tsm_hip.h: TSM_LAYOUT_TDN_SEGMENTS / TSM_LAYOUT_TDN_RING) ------------------
+    def ring_shapes(self, n_slots: int) -> tuple:
+        """Shapes of a ring of ``n_slots`` per-segment features: (a [n, H / 4, W / 4, 256], d [n, H / 8, W / 8, 256])."""
+        return ((int(n_slots), self.height // 4, self.width // 4, 256), (int(n_slots), self.height // 8, self.width // 8, 256))
+
+    def _check_ring(self, a, d, what: str = 'ring') -> int:
+        """The checks on a pair of per-segment feature tensors (the C ABI takes bare pointers); their slot count."""
+        import torch
+        self._need_finalized()
+        if not self.tdn_depths:
+            raise ValueError('the two-phase forward goes with a TDN engine (base_model=%r) only' % TDN)
+        for t in (a, d):
+            if not (hasattr(t, 'is_cuda') and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4):
+                raise ValueError(f'{what}: a and d must be contiguous float32 CUDA tensors [n, h, w, 256]')
+            if t.device.index != self.device:
+                raise ValueError(f'tensor on cuda:{t.device.index}, engine on cuda:{self.device}')
+        n = int(a.shape[0])
+        sa, sd = self.ring_shapes(n)
+        if n < 1 or tuple(a.shape) != sa or tuple(d.shape) != sd:
+            raise ValueError(f'{what}: need a {list(sa)} and d {list(sd)} with n >= 1, got {tuple(a.shape)} and {tuple(d.shape)}')
+        return n
+
+    def tdn_segments(self, frames, index=None, *, window=None, n_segments: int, out):
+        """The SEGMENT phase of a TDN forward (``tsm_forward`` with TSM_LAYOUT_TDN_SEGMENTS): everything in front of ``fuse2``,
+        once per segment.  ``frames`` is the pool of ``forward_pool``; exactly one of ``index`` (int32 CUDA ``[n_segments, 5]``
+        pool frame numbers) and ``window=dict(first_source_frame, total_frames, first_clip, clip_stride, pad_frame)`` (segment i
+        has centre ``clip_stride * (first_clip + i)``).  ``out=(a, d)``: float32 CUDA ``[n_segments, H / 4, W / 4, 256]`` and
+        ``[n_segments, H / 8, W / 8, 256]`` -- usually slices of a ring -- which the last blocks of layer1 and resnext_layer1
+        write directly.  More than ``max_clips * T`` segments run in chunks.  Enqueues on torch's current stream; returns ``out``."""
+        import torch
+        a, d = out
+        n = int(n_segments)
+        if self._check_ring(a, d, 'out') != n:
+            raise ValueError(f'out holds {a.shape[0]} segments, n_segments = {n}')
+        if not (hasattr(frames, 'is_cuda') and frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous()
+                and frames.dim() == 4 and tuple(frames.shape[1:]) == (3, self.height, self.width) and frames.shape[0] >= 1):
+            raise ValueError(f'frames must be a contiguous float32 CUDA tensor [n_frames, 3, {self.height}, {self.width}]')
+        if frames.device != a.device:
+            raise ValueError(f'frames on {frames.device}, out on {a.device}')
+        if (index is None) == (window is None):
+            raise ValueError('give exactly one of index (table mode) and window= (window mode)')
+        if index is not None:
+            if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
+                    and index.is_contiguous() and index.numel() == n * TDN_FRAMES):
+                raise ValueError(f'index must be a contiguous int32 tensor of {n} x {TDN_FRAMES} pool frame numbers on {frames.device}')
+        else:
+            keys = ('first_source_frame', 'total_frames', 'first_clip', 'clip_stride', 'pad_frame')
+            if not isinstance(window, Mapping) or set(window) != set(keys):
+                raise ValueError(f'window= must be a mapping with exactly the keys {keys}')
+            window = {k: int(window[k]) for k in keys}
+        stream = torch.cuda.current_stream(frames.device).cuda_stream
+        cap = self.max_clips * self.num_segments
+        for s in range(0, n, cap):
+            m = min(cap, n - s)
+            desc = _lib.TsmTdnSegments(struct_size=C.sizeof(_lib.TsmTdnSegments), frames=frames.data_ptr(), n_frames=frames.shape[0],
+                                       out_a=a[s:s + m].data_ptr(), out_d=d[s:s + m].data_ptr())
+            if index is not None:
+                desc.mode = _lib.TDN_POOL_TABLE
+                desc.index = index.data_ptr() + 4 * s * TDN_FRAMES
+            else:
+                desc.mode = _lib.TDN_POOL_WINDOW
+                for k, v in window.items():
+                    setattr(desc, k, v)
+                desc.clip_step = window['clip_stride']
+                desc.first_clip = window['first_clip'] + s
+            _lib.check(self._lib.tsm_forward(self._h, C.addressof(desc), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_SEGMENTS, m, None, stream), self._h)
+        return out
+
+    def _ring_descriptors(self, ring_a, ring_d, table, n_clips: int):
+        """The checks of ``forward_ring`` and one ``TsmTdnRing`` per ``max_clips`` chunk: [(first clip, clips, descriptor)]."""
+        import torch
+        n_slots = self._check_ring(ring_a, ring_d)
+        n_clips, T = int(n_clips), self.num_segments
+        if n_clips <= 0:
+            raise ValueError('n_clips must be positive')
+        if not (hasattr(table, 'is_cuda') and table.is_cuda and table.device == ring_a.device and table.dtype == torch.int32
+                and table.is_contiguous() and table.numel() == n_clips * T):
+            raise ValueError(f'table must be a contiguous int32 tensor of {n_clips} x {T} slot numbers on {ring_a.device}')
+        return [(s, min(self.max_clips, n_clips - s),
+                 _lib.TsmTdnRing(struct_size=C.sizeof(_lib.TsmTdnRing), n_slots=n_slots, ring_a=ring_a.data_ptr(), ring_d=ring_d.data_ptr(),
+                                 table=table.data_ptr() + 4 * s * T)) for s in range(0, n_clips, self.max_clips)]
+
+    def forward_ring(self, ring_a, ring_d, table, *, n_clips: int, out=None):
+        """The TRUNK phase of a TDN forward (``tsm_forward`` with TSM_LAYOUT_TDN_RING): ``fuse2`` onward on clips whose segments
+        are FOUND in a ring that ``tdn_segments`` filled.  ``table``: int32 CUDA ``[n_clips, T]`` of slot numbers, read on the
+        device when the kernel runs; an entry outside ``[0, n_slots)`` stands for a segment of zeros.  Returns what
+        ``forward_pool`` returns for the clips those segments make, bit for bit; more than ``max_clips`` clips run in chunks."""
+        import torch
+        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
+        out = _out(out, self._out_shape(int(n_clips)), torch.float32, ring_a)
+        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
+        for s, n, d in chunks:
+            _lib.check(self._lib.tsm_forward(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, n, out[s:s + n].data_ptr(),
+                                             stream), self._h)
+        return out
+
+    def forward_features_ring(self, ring_a, ring_d, table, *, n_clips: int, normalize: bool = False, out=None):
+        """``forward_features`` on the clips ``forward_ring`` describes: float32 CUDA [n_clips * T, feature_dim]."""
+        import torch
+        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
+        t = self.out_segments
+        out = _out(out, (int(n_clips) * t, self.feature_dim), torch.float32, ring_a)
+        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
+        for s, n, d in chunks:
+            _lib.check(self._lib.tsm_forward_features(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, n,
+                                                      out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
+        return out
+
+    def forward_tap_ring(self, ring_a, ring_d, table, *, n_clips: int, stage: str) -> np.ndarray:
+        """``forward_tap`` on the clips ``forward_ring`` describes (at most ``max_clips``; stages from ``fuse2`` on): the
+        activation behind ``stage`` as an NHWC float32 ndarray (parity tests)."""
+        import torch
+        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
+        if len(chunks) != 1:
+            raise ValueError(f'forward_tap_ring takes at most max_clips = {self.max_clips} clips')
+        n = int(n_clips) * self.num_segments
+        cap = n * self.height * self.width * 16         # (forward_tap's bound: layer1's width at its size)
+        buf = torch.empty(cap, dtype=torch.float32, device=ring_a.device)
+        shape = (C.c_int64 * 4)()
+        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
+        _lib.check(self._lib.tsm_forward_tap(self._h, C.addressof(chunks[0][2]), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, int(n_clips),
+                                             stage.encode(), buf.data_ptr(), cap, shape, stream), self._h)
+        dims = tuple(int(v) for v in shape)
+        return buf[:int(np.prod(dims))].reshape(dims).cpu().numpy()
+
     def warmup(self, batch_sizes: Optional[Sequence[int]] = None) -> 'TsmEngine':
         """Tune every power-of-two bucket of the clip count that will occur (default: 1, 2, 4, ... max_clips) now
         (``tsm_tune``: a few hundred ms each of timed launches on the engine's own zeroed input buffer, or nothing when

@@ -229,6 +229,8 @@ def test_new_kernels_use_no_scratch():
         lds = 21 * 21 * 12 * 4 if name == 'tdn_front_kernel' else 16384 if name.startswith('mse_squeeze') else 0
         assert r['.group_segment_fixed_size'] == lds, (name, r['.group_segment_fixed_size'])
     assert md['mse_excite_shift_kernel<512>']['.vgpr_count'] >= 128 and md['mse_excite_shift_kernel<512>']['waves_per_simd'] >= 2
+    # 74: tdn_front_kernel's count at commit 2cac9cf, read from a build with these flags; a rewrite must not cost registers (DESIGN_HISTORY.md H7)
+    assert md['tdn_front_kernel']['.vgpr_count'] <= 74, md['tdn_front_kernel']
 
 
 def test_conv1s_output_has_two_readers_and_o_one_writer():

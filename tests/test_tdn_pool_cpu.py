@@ -276,6 +276,9 @@ def test_the_pool_kernel_uses_no_scratch_and_the_plain_kernels_budget():
     assert pool['.group_segment_fixed_size'] == plain['.group_segment_fixed_size'] == 21 * 21 * 12 * 4
     # the frame numbers live in scalar registers: no more vector registers than the plain kernel, the same occupancy
     assert pool['.vgpr_count'] <= plain['.vgpr_count'] and pool['waves_per_simd'] >= plain['waves_per_simd'], (pool, plain)
+    # 74: the plain kernel's count at commit 2cac9cf, read from a build with these flags -- the two kernels are copies kept
+    # identical by hand, and a shared inlined body has cost the plain kernel 24 registers (DESIGN_HISTORY.md H7)
+    assert plain['.vgpr_count'] <= 74, plain
 
 
 # ---- host arithmetic -------------------------------------------------------------------------------------------------------

@@ -465,10 +465,16 @@ __global__ void __launch_bounds__(kTdnThreads) mse_excite_shift_kernel(const flo
 
 static bool mse_width_ok(int c) { return c == 128 || c == 256 || c == 512; }
 
-hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_frames, int h, int w, hipStream_t s) {
-  if (!x || !in4 || !patches || n_frames <= 0 || n_frames > 65535 || h < 64 || w < 64 || h % 32 != 0 || w % 32 != 0) return hipErrorInvalidValue;
+// What both front-end launches check: grid y = segments (at most 65535), grid x = 8 x 8 tiles of conv1_5 outputs; 0: refused.
+static int64_t tdn_front_tiles(const float *in4, const float *patches, int n_segments, int h, int w) {
+  if (!in4 || !patches || n_segments <= 0 || n_segments > 65535 || h < 64 || w < 64 || h % 32 != 0 || w % 32 != 0) return 0;
   const int64_t tiles = (int64_t)(h / 4 / tsm_host::kTdnTile) * (w / 4 / tsm_host::kTdnTile);
-  if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
+  return tiles > 0x7fffffffL ? 0 : tiles;
+}
+
+hipError_t launch_tdn_front(const float *x, float *in4, float *patches, int n_frames, int h, int w, hipStream_t s) {
+  const int64_t tiles = tdn_front_tiles(in4, patches, n_frames, h, w);
+  if (!x || !tiles) return hipErrorInvalidValue;
   TSM_KLAUNCH(tdn_front_kernel, dim3((unsigned)tiles, (unsigned)n_frames), dim3(kTdnThreads), 0, s, x, in4, patches, h, w);
   return hipGetLastError();
 }
@@ -477,9 +483,8 @@ hipError_t launch_tdn_front_pool(const tsm_host::TdnPoolSource &src, float *in4,
   if (!src.frames || reinterpret_cast<uintptr_t>(src.frames) % 8 != 0 || src.n_frames <= 0 || (src.mode != 0 && src.mode != 1) ||
       (src.mode == 0 && !src.index) || src.T <= 0 || src.limit != tsm_host::tdn_table_limit(src.n_frames))
     return hipErrorInvalidValue;
-  if (!in4 || !patches || n_segments <= 0 || n_segments > 65535 || h < 64 || w < 64 || h % 32 != 0 || w % 32 != 0) return hipErrorInvalidValue;
-  const int64_t tiles = (int64_t)(h / 4 / tsm_host::kTdnTile) * (w / 4 / tsm_host::kTdnTile);
-  if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
+  const int64_t tiles = tdn_front_tiles(in4, patches, n_segments, h, w);
+  if (!tiles) return hipErrorInvalidValue;
   TSM_KLAUNCH(tdn_front_pool_kernel, dim3((unsigned)tiles, (unsigned)n_segments), dim3(kTdnThreads), 0, s, src, in4, patches, h, w);
   return hipGetLastError();
 }

@@ -42,6 +42,23 @@ def _as_f32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
 
 
+def _addr(t) -> int:
+    """The address of an ndarray's or a tensor's first element."""
+    return t.ctypes.data if isinstance(t, np.ndarray) else t.data_ptr()
+
+
+@dataclass
+class _Input:
+    """What a forward reads, whatever it writes: ``chunks`` [(first clip, clips, address, keepalive)] is one C call each -- the
+    address of a clip slice or of a descriptor struct, which ``keepalive`` holds until the call has returned."""
+    layout: int
+    memkind: int
+    n_clips: int
+    like: object                # the ndarray or CUDA tensor outputs are allocated like
+    stream: Optional[int]       # None: host memory, the engine's own stream
+    chunks: list
+
+
 class TsmEngine:
     INPUT_NAME = 'input'
     OUTPUT_NAME = 'output'
@@ -219,19 +236,86 @@ class TsmEngine:
             raise ValueError(f'clips hold {n_elems} float32 values; layout {layout} needs {self._floats_per_clip(layout)} '
                              f'per clip x {b} clips (T={self.num_segments}, H={self.height}, W={self.width})')
 
+    # A builder (_clips_input, _pool_input, _ring_input) owns the checks on an input and describes it as an _Input; a runner
+    # (_run_logits, _run_features, _run_tap) owns the output and the C calls.  Every public forward is one of each.
+    def _clips_input(self, clips, layout: int, on_device: bool, need: str = '') -> '_Input':
+        """Dense clips in ``layout``: anything NumPy reads (host memory, the engine's own stream) or, ``on_device``, a float32 CUDA
+        tensor on this engine's device (torch's current stream) -- ``need`` is the refusal of any other tensor."""
+        self._need_finalized()
+        if on_device:
+            import torch
+            if not (clips.is_cuda and clips.dtype == torch.float32):
+                raise ValueError(need)
+            if clips.device.index != self.device:
+                raise ValueError(f'tensor on cuda:{clips.device.index}, engine on cuda:{self.device}')
+            clips = clips.contiguous()
+            b = clips.shape[0]
+            self._check_clips(clips.numel(), b, layout)
+            memkind, stream = _lib.MEM_DEVICE, torch.cuda.current_stream(clips.device).cuda_stream
+        else:
+            clips = _as_f32(clips)
+            b = clips.shape[0]
+            self._check_clips(clips.size, b, layout)
+            memkind, stream = _lib.MEM_HOST, None
+        chunks = [(s, min(self.max_clips, b - s), _addr(clips[s:s + self.max_clips]), clips) for s in range(0, b, self.max_clips)]
+        return _Input(layout, memkind, b, clips, stream, chunks)
+
+    def _descriptor_input(self, layout: int, n: int, like, make, per: Optional[int] = None) -> '_Input':
+        """``n`` clips that descriptor structs describe (a CUDA input): ``make(first, count)`` is the struct of one chunk of ``per``."""
+        import torch
+        per = per or self.max_clips
+        structs = [(s, min(per, n - s), make(s, min(per, n - s))) for s in range(0, n, per)]
+        return _Input(layout, _lib.MEM_DEVICE, n, like, torch.cuda.current_stream(like.device).cuda_stream,
+                      [(s, m, C.addressof(d), d) for s, m, d in structs])
+
+    def _rows(self, inp: '_Input', shape: tuple, out, own_message: bool = False):
+        """What a runner writes into: an ndarray for a host input, else ``out`` -- checked -- or a new tensor like the input."""
+        if inp.memkind == _lib.MEM_HOST:
+            return np.empty(shape, dtype=np.float32)
+        import torch
+        if own_message and out is not None:           # (forward_device's own, older wording)
+            if not (out.is_cuda and out.device == inp.like.device and out.dtype == torch.float32 and out.is_contiguous()
+                    and tuple(out.shape) == shape):
+                raise ValueError(f'out must be a contiguous float32 {list(shape)} tensor on {inp.like.device}')
+            return out
+        return _out(out, shape, torch.float32, inp.like)
+
+    def _run_logits(self, inp: '_Input', out=None, own_message: bool = False):
+        """``tsm_forward`` per chunk: clips [s, s + n) write rows [s, s + n) of ``_out_shape(n_clips)``."""
+        out = self._rows(inp, self._out_shape(inp.n_clips), out, own_message)
+        for s, n, address, _keepalive in inp.chunks:
+            _lib.check(self._lib.tsm_forward(self._h, address, inp.memkind, inp.layout, n, _addr(out[s:s + n]), inp.stream), self._h)
+        return out
+
+    def _run_features(self, inp: '_Input', normalize: bool, out=None):
+        """``tsm_forward_features`` per chunk: clips [s, s + n) write rows [s t, (s + n) t) of [n_clips * t, feature_dim]."""
+        t = self.out_segments
+        out = self._rows(inp, (inp.n_clips * t, self.feature_dim), out)
+        for s, n, address, _keepalive in inp.chunks:
+            _lib.check(self._lib.tsm_forward_features(self._h, address, inp.memkind, inp.layout, n, _addr(out[s * t:(s + n) * t]),
+                                                      int(bool(normalize)), inp.stream), self._h)
+        return out
+
+    def _run_tap(self, inp: '_Input', stage: str, cap: int, one_chunk: str = '') -> np.ndarray:
+        """``tsm_forward_tap`` on ALL the input's clips in one call -- ``one_chunk`` names a caller that refuses more than
+        ``max_clips`` itself -- into a buffer of ``cap`` floats beside the input; the NHWC activation as an ndarray."""
+        if one_chunk and len(inp.chunks) != 1:
+            raise ValueError(f'{one_chunk} takes at most max_clips = {self.max_clips} clips')
+        if inp.memkind == _lib.MEM_HOST:
+            buf = np.empty(cap, dtype=np.float32)
+        else:
+            import torch
+            buf = torch.empty(cap, dtype=torch.float32, device=inp.like.device)
+        shape = (C.c_int64 * 4)()
+        _lib.check(self._lib.tsm_forward_tap(self._h, inp.chunks[0][2], inp.memkind, inp.layout, inp.n_clips, stage.encode(), _addr(buf), cap,
+                                             shape, inp.stream), self._h)
+        dims = tuple(int(v) for v in shape)
+        res = buf[:int(np.prod(dims))].reshape(dims)
+        return res.copy() if inp.memkind == _lib.MEM_HOST else res.cpu().numpy()
+
     def forward_host(self, clips: np.ndarray, layout: int = _lib.LAYOUT_NTCHW) -> np.ndarray:
         """clips: float32 [B,T,3,H,W] (or [B,T,H,W,3] with LAYOUT_NTHWC) in host memory."""
-        self._need_finalized()
-        clips = _as_f32(clips)
-        b = clips.shape[0]
-        self._check_clips(clips.size, b, layout)
-        out = np.empty(self._out_shape(b), dtype=np.float32)
-        for s in range(0, b, self.max_clips):
-            chunk = np.ascontiguousarray(clips[s:s + self.max_clips])
-            o = out[s:s + chunk.shape[0]]
-            _lib.check(self._lib.tsm_forward(self._h, chunk.ctypes.data, _lib.MEM_HOST, layout, chunk.shape[0],
-                                             o.ctypes.data, None), self._h)
-        return out
+        return self._run_logits(self._clips_input(clips, layout, False))
 
     def forward_device(self, clips, out=None, layout: int = _lib.LAYOUT_NTCHW):
         """clips: contiguous float32 CUDA tensor [B,T,3,H,W] on this engine's device.  Enqueues on
@@ -239,26 +323,7 @@ class TsmEngine:
         no host sync).  An engine takes ONE in-flight call: a host forward (``run`` / ``forward_host`` / ``forward_tap``) runs on the
         engine's own non-blocking stream over the same workspace, so synchronise (``torch.cuda.synchronize()`` or the stream) after
         a device forward before the next host call on this engine."""
-        import torch
-        self._need_finalized()
-        if not (clips.is_cuda and clips.dtype == torch.float32):
-            raise ValueError('forward_device needs a float32 CUDA tensor')
-        if clips.device.index != self.device:
-            raise ValueError(f'tensor on cuda:{clips.device.index}, engine on cuda:{self.device}')
-        clips = clips.contiguous()
-        b = clips.shape[0]
-        self._check_clips(clips.numel(), b, layout)
-        if out is None:
-            out = torch.empty(self._out_shape(b), dtype=torch.float32, device=clips.device)
-        elif not (out.is_cuda and out.device == clips.device and out.dtype == torch.float32 and out.is_contiguous()
-                  and tuple(out.shape) == self._out_shape(b)):
-            raise ValueError(f'out must be a contiguous float32 {list(self._out_shape(b))} tensor on {clips.device}')
-        stream = torch.cuda.current_stream(clips.device).cuda_stream
-        for s in range(0, b, self.max_clips):
-            n = min(self.max_clips, b - s)
-            _lib.check(self._lib.tsm_forward(self._h, clips[s:s + n].data_ptr(), _lib.MEM_DEVICE, layout, n,
-                                             out[s:s + n].data_ptr(), stream), self._h)
-        return out
+        return self._run_logits(self._clips_input(clips, layout, True, 'forward_device needs a float32 CUDA tensor'), out, own_message=True)
 
     def forward_features(self, clips, normalize: bool = False, out=None, layout: int = _lib.LAYOUT_NTCHW):
         """Frame embeddings (``tsm_forward_features``; the reference's ``cnn_feature``, utils/common.py:79-106): the forward with
@@ -268,40 +333,56 @@ class TsmEngine:
         ``out`` (CUDA input only): a contiguous float32 [B*T, feature_dim] tensor to write into, e.g. a band of a video's
         feature buffer.  Any engine: consensus, backbone, placement and dtype change nothing about the call."""
         self._need_finalized()
-        t, d = self.out_segments, self.feature_dim
-        if hasattr(clips, 'is_cuda'):
-            import torch
-            if not (clips.is_cuda and clips.dtype == torch.float32):
-                raise ValueError('forward_features needs a float32 CUDA tensor or an ndarray')
-            if clips.device.index != self.device:
-                raise ValueError(f'tensor on cuda:{clips.device.index}, engine on cuda:{self.device}')
-            clips = clips.contiguous()
-            b = clips.shape[0]
-            self._check_clips(clips.numel(), b, layout)
-            out = _out(out, (b * t, d), torch.float32, clips)
-            stream = torch.cuda.current_stream(clips.device).cuda_stream
-            for s in range(0, b, self.max_clips):
-                n = min(self.max_clips, b - s)
-                _lib.check(self._lib.tsm_forward_features(self._h, clips[s:s + n].data_ptr(), _lib.MEM_DEVICE, layout, n,
-                                                          out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
-            return out
-        if out is not None:
+        on_device = hasattr(clips, 'is_cuda')
+        if out is not None and not on_device:
             raise ValueError('out= goes with a CUDA tensor')
-        clips = _as_f32(clips)
-        b = clips.shape[0]
-        self._check_clips(clips.size, b, layout)
-        res = np.empty((b * t, d), dtype=np.float32)
-        for s in range(0, b, self.max_clips):
-            chunk = np.ascontiguousarray(clips[s:s + self.max_clips])
-            o = res[s * t:(s + chunk.shape[0]) * t]
-            _lib.check(self._lib.tsm_forward_features(self._h, chunk.ctypes.data, _lib.MEM_HOST, layout, chunk.shape[0],
-                                                      o.ctypes.data, int(bool(normalize)), None), self._h)
-        return res
+        need = 'forward_features needs a float32 CUDA tensor or an ndarray'
+        return self._run_features(self._clips_input(clips, layout, on_device, need), normalize, out)
+
+    def forward_tap(self, clips: np.ndarray, stage: str) -> np.ndarray:
+        """Activation after ``stage`` as NHWC float32 ndarray (parity tests)."""
+        inp = self._clips_input(clips, _lib.LAYOUT_NTCHW, False)
+        n = inp.n_clips * self.num_segments
+        h1, w1 = (self.height - 1) // 2 + 1, (self.width - 1) // 2 + 1          # stem conv output
+        hp, wp = (h1 - 1) // 2 + 1, (w1 - 1) // 2 + 1                            # after the max-pool = layer1's size
+        cap = n * max(h1 * w1 * 64, hp * wp * 256, self.height * self.width * 8)
+        if self.convnext_depths:                                                  # the largest tap: fc1's output in stage 0
+            cap = max(cap, n * (self.height // 4) * (self.width // 4) * 4 * CONVNEXT_WIDTHS[0])
+        return self._run_tap(inp, stage, cap)
 
     # ---- a TDN engine's input as a pool of transformed frames (include/tsm_hip.h: TSM_LAYOUT_TDN_POOL) ------------------
-    def _pool_descriptors(self, frames, index, window, n_clips: int):
-        """The checks of ``forward_pool`` (the C ABI takes bare pointers) and one ``TsmTdnPool`` per ``max_clips`` chunk:
-        [(first clip of the chunk, clips in it, descriptor)]."""
+    @staticmethod
+    def _pool_source(frames, index, window, rows: tuple, keys: tuple):
+        """The checks on WHERE in a pool the frames are found, once for ``forward_pool`` (``rows`` = (n_clips, T)) and
+        ``tdn_segments`` ((n_segments,)): exactly one of an int32 table of ``rows x 5`` pool frame numbers and a window rule with
+        exactly ``keys``.  Returns ``point(d, first)``, which points a descriptor at the chunk that starts ``first`` rows[0] on."""
+        import torch
+        if (index is None) == (window is None):
+            raise ValueError('give exactly one of index (table mode) and window= (window mode)')
+        if index is not None:
+            if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
+                    and index.is_contiguous() and index.numel() == int(np.prod(rows)) * TDN_FRAMES):
+                raise ValueError(f'index must be a contiguous int32 tensor of {" x ".join(str(r) for r in rows + (TDN_FRAMES,))} pool frame '
+                                 f'numbers on {frames.device}')
+        elif not isinstance(window, Mapping) or set(window) != set(keys):
+            raise ValueError(f'window= must be a mapping with exactly the keys {keys}')
+        else:
+            window = {k: int(window[k]) for k in keys}
+
+        def point(d, first: int) -> None:
+            if index is not None:
+                d.mode = _lib.TDN_POOL_TABLE
+                d.index = index.data_ptr() + 4 * first * int(np.prod(rows[1:])) * TDN_FRAMES
+            else:
+                d.mode = _lib.TDN_POOL_WINDOW
+                for k, v in window.items():
+                    setattr(d, k, v)
+                d.clip_step = window.get('clip_step', window['clip_stride'])      # (a segment is a clip of one: tdn_segments)
+                d.first_clip = window['first_clip'] + first
+        return point
+
+    def _pool_input(self, frames, index, window, n_clips: int) -> '_Input':
+        """The checks of ``forward_pool`` (the C ABI takes bare pointers) and one ``TsmTdnPool`` per ``max_clips`` chunk."""
         import torch
         self._need_finalized()
         if not self.tdn_depths:
@@ -315,31 +396,14 @@ class TsmEngine:
         n_clips = int(n_clips)
         if n_clips <= 0:
             raise ValueError('n_clips must be positive')
-        if (index is None) == (window is None):
-            raise ValueError('give exactly one of index (table mode) and window= (window mode)')
-        T = self.num_segments
-        if index is not None:
-            if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
-                    and index.is_contiguous() and index.numel() == n_clips * T * TDN_FRAMES):
-                raise ValueError(f'index must be a contiguous int32 tensor of {n_clips} x {T} x {TDN_FRAMES} pool frame numbers on {frames.device}')
-        else:
-            keys = ('first_source_frame', 'total_frames', 'first_clip', 'clip_step', 'clip_stride', 'pad_frame')
-            if not isinstance(window, Mapping) or set(window) != set(keys):
-                raise ValueError(f'window= must be a mapping with exactly the keys {keys}')
-            window = {k: int(window[k]) for k in keys}
-        out = []
-        for s in range(0, n_clips, self.max_clips):
+        point = self._pool_source(frames, index, window, (n_clips, self.num_segments),
+                                  ('first_source_frame', 'total_frames', 'first_clip', 'clip_step', 'clip_stride', 'pad_frame'))
+
+        def make(s: int, _n: int):
             d = _lib.TsmTdnPool(struct_size=C.sizeof(_lib.TsmTdnPool), frames=frames.data_ptr(), n_frames=frames.shape[0])
-            if index is not None:
-                d.mode = _lib.TDN_POOL_TABLE
-                d.index = index.data_ptr() + 4 * s * T * TDN_FRAMES
-            else:
-                d.mode = _lib.TDN_POOL_WINDOW
-                for k, v in window.items():
-                    setattr(d, k, v)
-                d.first_clip = window['first_clip'] + s
-            out.append((s, min(self.max_clips, n_clips - s), d))
-        return out
+            point(d, s)
+            return d
+        return self._descriptor_input(_lib.LAYOUT_TDN_POOL, n_clips, frames, make)
 
     def forward_pool(self, frames, index=None, *, window=None, n_clips: int, out=None):
         """The forward of a TDN engine on clips whose frames are FOUND in a pool (``tsm_forward`` with TSM_LAYOUT_TDN_POOL): no
@@ -355,43 +419,17 @@ class TsmEngine:
 
         Enqueues on torch's current stream and returns what ``forward_device`` returns, bit for bit that of the gathered
         planes; more than ``max_clips`` clips run in chunks."""
-        import torch
-        chunks = self._pool_descriptors(frames, index, window, n_clips)
-        out = _out(out, self._out_shape(int(n_clips)), torch.float32, frames)
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
-        for s, n, d in chunks:
-            _lib.check(self._lib.tsm_forward(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, n, out[s:s + n].data_ptr(),
-                                             stream), self._h)
-        return out
+        return self._run_logits(self._pool_input(frames, index, window, n_clips), out)
 
     def forward_features_pool(self, frames, index=None, *, window=None, n_clips: int, normalize: bool = False, out=None):
         """``forward_features`` on the clips ``forward_pool`` describes: float32 CUDA [n_clips * T, feature_dim]."""
-        import torch
-        chunks = self._pool_descriptors(frames, index, window, n_clips)
-        t = self.out_segments
-        out = _out(out, (int(n_clips) * t, self.feature_dim), torch.float32, frames)
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
-        for s, n, d in chunks:
-            _lib.check(self._lib.tsm_forward_features(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, n,
-                                                      out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
-        return out
+        return self._run_features(self._pool_input(frames, index, window, n_clips), normalize, out)
 
     def forward_tap_pool(self, frames, stage: str, index=None, *, window=None, n_clips: int) -> np.ndarray:
         """``forward_tap`` on the clips ``forward_pool`` describes (at most ``max_clips``): the activation behind ``stage`` as an
         NHWC float32 ndarray (parity tests)."""
-        import torch
-        chunks = self._pool_descriptors(frames, index, window, n_clips)
-        if len(chunks) != 1:
-            raise ValueError(f'forward_tap_pool takes at most max_clips = {self.max_clips} clips')
-        n = int(n_clips) * self.num_segments
-        cap = n * self.height * self.width * 16         # (forward_tap's bound: the stem conv's output, layer1's)
-        buf = torch.empty(cap, dtype=torch.float32, device=frames.device)
-        shape = (C.c_int64 * 4)()
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
-        _lib.check(self._lib.tsm_forward_tap(self._h, C.addressof(chunks[0][2]), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_POOL, int(n_clips),
-                                             stage.encode(), buf.data_ptr(), cap, shape, stream), self._h)
-        dims = tuple(int(v) for v in shape)
-        return buf[:int(np.prod(dims))].reshape(dims).cpu().numpy()
+        inp = self._pool_input(frames, index, window, n_clips)      # (cap: forward_tap's bound, the stem conv's output, layer1's)
+        return self._run_tap(inp, stage, inp.n_clips * self.num_segments * self.height * self.width * 16, 'forward_tap_pool')
 
     # ---- a TDN forward in two phases (include/tsm_hip.h: TSM_LAYOUT_TDN_SEGMENTS / TSM_LAYOUT_TDN_RING) ------------------
     def ring_shapes(self, n_slots: int) -> tuple:
@@ -432,37 +470,20 @@ class TsmEngine:
             raise ValueError(f'frames must be a contiguous float32 CUDA tensor [n_frames, 3, {self.height}, {self.width}]')
         if frames.device != a.device:
             raise ValueError(f'frames on {frames.device}, out on {a.device}')
-        if (index is None) == (window is None):
-            raise ValueError('give exactly one of index (table mode) and window= (window mode)')
-        if index is not None:
-            if not (hasattr(index, 'is_cuda') and index.is_cuda and index.device == frames.device and index.dtype == torch.int32
-                    and index.is_contiguous() and index.numel() == n * TDN_FRAMES):
-                raise ValueError(f'index must be a contiguous int32 tensor of {n} x {TDN_FRAMES} pool frame numbers on {frames.device}')
-        else:
-            keys = ('first_source_frame', 'total_frames', 'first_clip', 'clip_stride', 'pad_frame')
-            if not isinstance(window, Mapping) or set(window) != set(keys):
-                raise ValueError(f'window= must be a mapping with exactly the keys {keys}')
-            window = {k: int(window[k]) for k in keys}
-        stream = torch.cuda.current_stream(frames.device).cuda_stream
-        cap = self.max_clips * self.num_segments
-        for s in range(0, n, cap):
-            m = min(cap, n - s)
+        point = self._pool_source(frames, index, window, (n,), ('first_source_frame', 'total_frames', 'first_clip', 'clip_stride', 'pad_frame'))
+
+        def make(s: int, m: int):
             desc = _lib.TsmTdnSegments(struct_size=C.sizeof(_lib.TsmTdnSegments), frames=frames.data_ptr(), n_frames=frames.shape[0],
                                        out_a=a[s:s + m].data_ptr(), out_d=d[s:s + m].data_ptr())
-            if index is not None:
-                desc.mode = _lib.TDN_POOL_TABLE
-                desc.index = index.data_ptr() + 4 * s * TDN_FRAMES
-            else:
-                desc.mode = _lib.TDN_POOL_WINDOW
-                for k, v in window.items():
-                    setattr(desc, k, v)
-                desc.clip_step = window['clip_stride']
-                desc.first_clip = window['first_clip'] + s
-            _lib.check(self._lib.tsm_forward(self._h, C.addressof(desc), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_SEGMENTS, m, None, stream), self._h)
+            point(desc, s)
+            return desc
+        inp = self._descriptor_input(_lib.LAYOUT_TDN_SEGMENTS, n, frames, make, self.max_clips * self.num_segments)
+        for _s, m, address, _keepalive in inp.chunks:      # (the descriptor names the outputs: no out pointer)
+            _lib.check(self._lib.tsm_forward(self._h, address, inp.memkind, inp.layout, m, None, inp.stream), self._h)
         return out
 
-    def _ring_descriptors(self, ring_a, ring_d, table, n_clips: int):
-        """The checks of ``forward_ring`` and one ``TsmTdnRing`` per ``max_clips`` chunk: [(first clip, clips, descriptor)]."""
+    def _ring_input(self, ring_a, ring_d, table, n_clips: int) -> '_Input':
+        """The checks of ``forward_ring`` and one ``TsmTdnRing`` per ``max_clips`` chunk."""
         import torch
         n_slots = self._check_ring(ring_a, ring_d)
         n_clips, T = int(n_clips), self.num_segments
@@ -471,52 +492,26 @@ class TsmEngine:
         if not (hasattr(table, 'is_cuda') and table.is_cuda and table.device == ring_a.device and table.dtype == torch.int32
                 and table.is_contiguous() and table.numel() == n_clips * T):
             raise ValueError(f'table must be a contiguous int32 tensor of {n_clips} x {T} slot numbers on {ring_a.device}')
-        return [(s, min(self.max_clips, n_clips - s),
-                 _lib.TsmTdnRing(struct_size=C.sizeof(_lib.TsmTdnRing), n_slots=n_slots, ring_a=ring_a.data_ptr(), ring_d=ring_d.data_ptr(),
-                                 table=table.data_ptr() + 4 * s * T)) for s in range(0, n_clips, self.max_clips)]
+        return self._descriptor_input(_lib.LAYOUT_TDN_RING, n_clips, ring_a, lambda s, _n: _lib.TsmTdnRing(
+            struct_size=C.sizeof(_lib.TsmTdnRing), n_slots=n_slots, ring_a=ring_a.data_ptr(), ring_d=ring_d.data_ptr(),
+            table=table.data_ptr() + 4 * s * T))
 
     def forward_ring(self, ring_a, ring_d, table, *, n_clips: int, out=None):
         """The TRUNK phase of a TDN forward (``tsm_forward`` with TSM_LAYOUT_TDN_RING): ``fuse2`` onward on clips whose segments
         are FOUND in a ring that ``tdn_segments`` filled.  ``table``: int32 CUDA ``[n_clips, T]`` of slot numbers, read on the
         device when the kernel runs; an entry outside ``[0, n_slots)`` stands for a segment of zeros.  Returns what
         ``forward_pool`` returns for the clips those segments make, bit for bit; more than ``max_clips`` clips run in chunks."""
-        import torch
-        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
-        out = _out(out, self._out_shape(int(n_clips)), torch.float32, ring_a)
-        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
-        for s, n, d in chunks:
-            _lib.check(self._lib.tsm_forward(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, n, out[s:s + n].data_ptr(),
-                                             stream), self._h)
-        return out
+        return self._run_logits(self._ring_input(ring_a, ring_d, table, n_clips), out)
 
     def forward_features_ring(self, ring_a, ring_d, table, *, n_clips: int, normalize: bool = False, out=None):
         """``forward_features`` on the clips ``forward_ring`` describes: float32 CUDA [n_clips * T, feature_dim]."""
-        import torch
-        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
-        t = self.out_segments
-        out = _out(out, (int(n_clips) * t, self.feature_dim), torch.float32, ring_a)
-        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
-        for s, n, d in chunks:
-            _lib.check(self._lib.tsm_forward_features(self._h, C.addressof(d), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, n,
-                                                      out[s * t:(s + n) * t].data_ptr(), int(bool(normalize)), stream), self._h)
-        return out
+        return self._run_features(self._ring_input(ring_a, ring_d, table, n_clips), normalize, out)
 
     def forward_tap_ring(self, ring_a, ring_d, table, *, n_clips: int, stage: str) -> np.ndarray:
         """``forward_tap`` on the clips ``forward_ring`` describes (at most ``max_clips``; stages from ``fuse2`` on): the
         activation behind ``stage`` as an NHWC float32 ndarray (parity tests)."""
-        import torch
-        chunks = self._ring_descriptors(ring_a, ring_d, table, n_clips)
-        if len(chunks) != 1:
-            raise ValueError(f'forward_tap_ring takes at most max_clips = {self.max_clips} clips')
-        n = int(n_clips) * self.num_segments
-        cap = n * self.height * self.width * 16         # (forward_tap's bound: layer1's width at its size)
-        buf = torch.empty(cap, dtype=torch.float32, device=ring_a.device)
-        shape = (C.c_int64 * 4)()
-        stream = torch.cuda.current_stream(ring_a.device).cuda_stream
-        _lib.check(self._lib.tsm_forward_tap(self._h, C.addressof(chunks[0][2]), _lib.MEM_DEVICE, _lib.LAYOUT_TDN_RING, int(n_clips),
-                                             stage.encode(), buf.data_ptr(), cap, shape, stream), self._h)
-        dims = tuple(int(v) for v in shape)
-        return buf[:int(np.prod(dims))].reshape(dims).cpu().numpy()
+        inp = self._ring_input(ring_a, ring_d, table, n_clips)      # (cap: forward_tap's bound, layer1's width at its size)
+        return self._run_tap(inp, stage, inp.n_clips * self.num_segments * self.height * self.width * 16, 'forward_tap_ring')
 
     def warmup(self, batch_sizes: Optional[Sequence[int]] = None) -> 'TsmEngine':
         """Tune every power-of-two bucket of the clip count that will occur (default: 1, 2, 4, ... max_clips) now
@@ -535,25 +530,6 @@ class TsmEngine:
             b = max(1, min(int(b), self.max_clips))
             _lib.check(self._lib.tsm_tune(self._h, b, stream), self._h)
         return self
-
-    def forward_tap(self, clips: np.ndarray, stage: str) -> np.ndarray:
-        """Activation after ``stage`` as NHWC float32 ndarray (parity tests)."""
-        self._need_finalized()
-        clips = _as_f32(clips)
-        self._check_clips(clips.size, clips.shape[0], _lib.LAYOUT_NTCHW)
-        n = clips.shape[0] * self.num_segments
-        h1, w1 = (self.height - 1) // 2 + 1, (self.width - 1) // 2 + 1          # stem conv output
-        hp, wp = (h1 - 1) // 2 + 1, (w1 - 1) // 2 + 1                            # after the max-pool = layer1's size
-        cap = n * max(h1 * w1 * 64, hp * wp * 256, self.height * self.width * 8)
-        if self.convnext_depths:                                                  # the largest tap: fc1's output in stage 0
-            cap = max(cap, n * (self.height // 4) * (self.width // 4) * 4 * CONVNEXT_WIDTHS[0])
-        buf = np.empty(cap, dtype=np.float32)
-        shape = (C.c_int64 * 4)()
-        _lib.check(self._lib.tsm_forward_tap(self._h, clips.ctypes.data, _lib.MEM_HOST, _lib.LAYOUT_NTCHW,
-                                             clips.shape[0], stage.encode(), buf.ctypes.data, cap, shape, None),
-                   self._h)
-        dims = tuple(int(v) for v in shape)
-        return buf[:int(np.prod(dims))].reshape(dims).copy()
 
     # ---- per-launch timing (bench.py roofline) -------------------------------------------------------
     def launch_names(self) -> List[str]:

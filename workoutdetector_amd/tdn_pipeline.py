@@ -114,6 +114,19 @@ def _call_host(model, x: torch.Tensor) -> np.ndarray:
     return staging.call_host_module(model, x)
 
 
+def _stage_pool(fill, n: int, frame_shape, zero_last: bool, tf: TestTransform, dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """How frames reach an engine here: ``fill(pinned)`` writes ``n`` uint8 frames of ``frame_shape`` (with ``zero_last`` a frame of
+    zeros rides behind them, as frame ``n``), ``staging.upload``, ONE ``preprocess_frames(packed=False)`` launch -> the pool."""
+    from .engine import preprocess_frames
+
+    def fill_all(pinned: torch.Tensor) -> None:
+        fill(pinned[:n])
+        if zero_last:
+            pinned[n].zero_()
+    staged, _ready = staging.upload((n + int(zero_last),) + tuple(frame_shape), fill_all, dev)
+    return preprocess_frames(staged, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255, packed=False, out=out)
+
+
 # ---- counting --------------------------------------------------------------------------------------------------------------------
 def tdn_frame_range(total: int, lo: int, hi: int, step: int = ic.CLIP_STEP, stride: int = ic.CLIP_STRIDE,
                     num_segments: int = ic.NUM_SEGMENTS) -> Tuple[int, int]:
@@ -288,13 +301,7 @@ def tdn_video_clip_logits(model, video_thwc_u8, transform: TestTransform, clip_r
         a, b = tdn_frame_range(total, p_lo, p_hi, step, stride, T)
         nf = b - a                                  # (the zero frame is pool frame nf)
         if engine:
-            from .engine import preprocess_frames
-
-            def fill(pinned: torch.Tensor, a=a, b=b) -> None:
-                pinned[:-1].copy_(video[a:b])
-                pinned[-1].zero_()
-            staged, _ready = staging.upload((nf + 1,) + hw + (3,), fill, dev)
-            pool = preprocess_frames(staged, resize=transform.size, crop=transform.crop, scale_255=transform.scale_255, packed=False)
+            pool = _stage_pool(lambda pinned, a=a, b=b: pinned.copy_(video[a:b]), nf, hw + (3,), True, transform, dev)
             if reuse_segments:
                 out += _ring_piece_logits(model, pool, a, nf, total, p_lo, p_hi, batch_clips, T, step, stride, dev)
                 continue
@@ -490,7 +497,6 @@ class TdnStreamBatcher:
         self._free.sort(reverse=True)
 
     def _logits_engine(self, jobs) -> Optional[torch.Tensor]:
-        from .engine import preprocess_frames
         tf, dev = self.transform, self._dev
         # 1. the new segments of every job: the final ones not yet computed and, with the length known, the rest the clips read
         new: List[Tuple[_TdnStream, Tuple[int, int]]] = []
@@ -521,15 +527,11 @@ class TdnStreamBatcher:
             for gi, (shape, g) in enumerate(groups.items()):
                 zero = 1 if want_pad and gi == 0 else 0        # (the zero frame rides with the first group, behind its frames)
 
-                def fill(pinned: torch.Tensor, g=g, zero=zero) -> None:
+                def fill(pinned: torch.Tensor, g=g) -> None:
                     for (sid_, f), i in g.items():
                         s_ = by_id[sid_]
                         pinned[i].copy_(torch.from_numpy(s_.frames[f - s_.base]))
-                    if zero:
-                        pinned[-1].zero_()
-                staged, _ready = staging.upload((len(g) + zero,) + shape, fill, dev)
-                preprocess_frames(staged, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255, packed=False,
-                                  out=pool[offset:offset + len(g) + zero])
+                _stage_pool(fill, len(g), shape, bool(zero), tf, dev, out=pool[offset:offset + len(g) + zero])
                 for key, i in g.items():
                     where[key] = offset + i
                 if zero:
@@ -598,7 +600,7 @@ def _tdn_groups(samples: Sequence[Mapping], T: int, rng) -> List[Tuple[str, List
 
 
 def _tdn_eval_engine(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
-    from .engine import preprocess_frames, top1_tally
+    from .engine import top1_tally
     dev = staging.engine_device(model)
     n, c = len(samples), int(model.num_class)
     counters = staging.upload_table(torch.zeros((2, c), dtype=torch.int32), dev)
@@ -617,8 +619,7 @@ def _tdn_eval_engine(model, samples, groups, reader, batch: int, transform: Test
                 if tuple(got.shape[1:]) != tuple(probe.shape[1:]):
                     raise ValueError(f'{frame_dir}: frames of {tuple(got.shape[1:3])} and {tuple(probe.shape[1:3])} pixels')
                 pinned.copy_(got)
-            staged, _ready = staging.upload((len(union),) + tuple(probe.shape[1:]), fill, dev)
-            pool = preprocess_frames(staged, resize=transform.size, crop=transform.crop, scale_255=transform.scale_255, packed=False)
+            pool = _stage_pool(fill, len(union), tuple(probe.shape[1:]), False, transform, dev)
             table, labels = staging.upload_table(table, dev), staging.upload_table(labels, dev)
             for lo in range(0, b - a, batch):
                 hi = min(lo + batch, b - a)

@@ -3,7 +3,11 @@ torch, and the engine against the float64 torch model with the wrapper's module 
 
 Bars.  Attention per op: ``assert_close(rtol=1e-4, atol_scale=1e-4)`` against the float64 reference, the per-op conv bar (torch's
 own fp32 composite sits at 3e-7 .. 1e-6 of the scale against float64).  Max-pool: bit-exact against torch.  Engine: the existing
-engine bars, logits ``rtol=1e-3, atol_scale=1e-5`` and taps ``atol_scale=3e-5``."""
+engine bars, logits ``rtol=1e-3, atol_scale=1e-5`` and taps ``atol_scale=3e-5``.
+
+Frames.  Square ones and the non-square ones of tests/_geometry_cases.py (48 x 80, 80 x 48, 64 x 112, 32 x 64): at H = W an exchange
+of rows and columns in the host plumbing changes no bit (tests/test_geometry_cases_cpu.py), so every engine-level check also runs
+where they differ, with tap shapes asserted from that table."""
 import ctypes as C
 import functools
 
@@ -12,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _geometry_cases as G
 from tests._guard import POISON, check, guarded, guarded_out
 from tests._nonlocal import TAPS, attention_ref, clip_input, run_with_taps, torch_tsm_nl
 from tests._util import assert_close
@@ -156,6 +161,24 @@ R50, WRN = 'resnet50', 'wide_resnet50_2'
 CASES = [(R50, 'blockres', 8, True, 64, 'avg'), (R50, 'blockres', 8, True, 80, 'avg'), (R50, 'blockres', 8, True, 48, 'avg'),
          (R50, 'blockres', 3, True, 64, 'avg'), (R50, 'blockres', 8, False, 64, 'avg'), (R50, 'block', 8, True, 64, 'avg'),
          (WRN, 'blockres', 8, True, 64, 'avg'), (R50, 'blockres', 8, True, 64, 'identity'), (R50, 'blockres', 8, True, 64, 'features')]
+# the non-square frames of tests/_geometry_cases.py (size = (h, w)): square frames hide an H/W exchange in the host plumbing
+CASES += [(c['base_model'], 'blockres', c['T'], True, (c['h'], c['w']), 'avg') for c in G.NON_LOCAL]
+CASES += [(R50, 'blockres', 8, True, (80, 48), 'identity'), (R50, 'blockres', 8, True, (80, 48), 'features')]
+TAP_MAPS = {'layer2.0': ('layer2', 512), 'layer2.0.block': ('layer2', 512), 'layer2.2.nl.y': ('layer2', 256), 'layer3.4': ('layer3', 1024)}
+
+
+def _hw(size):
+    return (size, size) if isinstance(size, int) else tuple(size)
+
+
+def _maps(size):
+    """The stage maps of a frame: the table's record for a frame of the table, the restated arithmetic for the square ones."""
+    h, w = _hw(size)
+    return G.maps_of('non_local', h, w) if (h, w) in G.frames_of('non_local') else G.tsm_maps(h, w)
+
+
+def _frame_id(v):
+    return '%dx%d' % v if isinstance(v, tuple) else None
 
 
 def _sd(base_model=R50, place='blockres', seed=0):
@@ -166,7 +189,8 @@ def _sd(base_model=R50, place='blockres', seed=0):
 @functools.lru_cache(maxsize=None)
 def _reference(base_model, place, T, is_shift, size):
     """The float64 torch model's outputs for the seeded weights and this configuration's two clips: computed once."""
-    x = clip_input(100 + size + T, 2, T, size, size)
+    h, w = _hw(size)
+    x = clip_input(100 + size + T if isinstance(size, int) else 100 + h + w + T, 2, T, h, w)
     net = torch_tsm_nl(base_model, place, 12, T, is_shift, sd=_sd(base_model, place))
     logits, seg, pooled, taps, _sharp = run_with_taps(net, x)
     return x, logits, seg, pooled, taps
@@ -174,24 +198,31 @@ def _reference(base_model, place, T, is_shift, size):
 
 def _engine(base_model=R50, place='blockres', T=8, is_shift=True, size=64, consensus='avg', max_clips=2, sd=None, non_local=True):
     from workoutdetector_amd.engine import TsmEngine
-    return TsmEngine(num_class=12, num_segments=T, height=size, width=size, is_shift=is_shift, max_clips=max_clips,
+    h, w = _hw(size)
+    return TsmEngine(num_class=12, num_segments=T, height=h, width=w, is_shift=is_shift, max_clips=max_clips,
                      state_dict=sd if sd is not None else _sd(base_model, place), base_model=base_model, shift_place=place,
                      consensus_type=consensus, non_local=non_local)
 
 
-@pytest.mark.parametrize('base_model,place,T,is_shift,size,mode', CASES)
+@pytest.mark.parametrize('base_model,place,T,is_shift,size,mode', CASES, ids=_frame_id)
 def test_engine_against_float64_torch(hip_lib, base_model, place, T, is_shift, size, mode):
+    """Tap shapes are held to the case table's maps (tests/_geometry_cases.py), not to what the engine or the reference says."""
     x, logits, seg, pooled, taps = _reference(base_model, place, T, is_shift, size)
     eng = _engine(base_model, place, T, is_shift, size, 'identity' if mode == 'identity' else 'avg')
-    what = f'{base_model} {place} T{T} shift {is_shift} {size}x{size} {mode}'
+    what = f'{base_model} {place} T{T} shift {is_shift} {"%dx%d" % _hw(size)} {mode}'
+    maps = _maps(size)
     if mode == 'features':
         got = eng.forward_features(x)
+        assert got.shape == (2 * T, 2048)
         assert_close(got, pooled, rtol=1e-3, atol_scale=1e-5, what=what + ' features')
     else:
         got = eng.run(None, {'input': x})[0]
+        assert got.shape == ((2, T, 12) if mode == 'identity' else (2, 12))
         assert_close(got, seg if mode == 'identity' else logits, rtol=1e-3, atol_scale=1e-5, what=what + ' logits')
     for stage in TAPS:
-        assert_close(eng.forward_tap(x, stage), taps[stage], rtol=1e-3, atol_scale=3e-5, what=f'{what} {stage}')
+        tap = eng.forward_tap(x, stage)
+        assert tap.shape == (2 * T, *maps[TAP_MAPS[stage][0]], TAP_MAPS[stage][1]), (stage, tap.shape)
+        assert_close(tap, taps[stage], rtol=1e-3, atol_scale=3e-5, what=f'{what} {stage}')
     eng.close()
 
 
@@ -202,6 +233,51 @@ def test_three_clips_through_two_slots_equal_the_single_runs(hip_lib):
     for c in range(3):
         assert np.array_equal(eng.run(None, {'input': x[c:c + 1]})[0][0], all3[c]), c
     eng.close()
+
+
+def test_three_clips_through_two_slots_on_a_non_square_frame(hip_lib):
+    x = clip_input(31, 3, 8, 48, 80)
+    eng = _engine(size=(48, 80))
+    all3 = eng.run(None, {'input': x})[0]
+    assert all3.shape == (3, 12)
+    for c in range(3):
+        assert np.array_equal(eng.run(None, {'input': x[c:c + 1]})[0][0], all3[c]), c
+    eng.close()
+    assert not np.array_equal(all3[0], all3[1]) and not np.array_equal(all3[1], all3[2])
+
+
+def test_tuned_and_untuned_on_both_orientations_share_one_cache_file(hip_lib, monkeypatch, tmp_path):
+    """48 x 80 and 80 x 48 tune into ONE TSM_TUNE_CACHE file: two lines whose signatures differ in the frame alone, each engine's
+    tuned logits bitwise its untuned ones (a line read back for the other orientation would carry tiles timed on other maps)."""
+    path = tmp_path / 'tune.txt'
+    monkeypatch.setenv('TSM_TUNE_CACHE', str(path))
+    tuned, xs = {}, {}
+    for hw in ((48, 80), (80, 48)):
+        xs[hw] = clip_input(32 + hw[0], 2, 8, *hw)
+        eng = _engine(size=hw)
+        eng.warmup([2])
+        tuned[hw] = eng.run(None, {'input': xs[hw]})[0]
+        tiles = eng.conv_tiles(2)
+        for li, b in ((2, 0), (2, 2), (3, 0), (3, 2), (3, 4)):
+            assert f'layer{li}.{b}.nl.qkv' in tiles and f'layer{li}.{b}.nl.W' in tiles, (hw, li, b)
+        assert len(tiles) == 53 + 10
+        eng.close()
+    lines = path.read_text().splitlines()
+    assert len(lines) == 2, lines
+    sigs = [ln.split('|')[0] for ln in lines]
+    assert ' 48x80 ' in sigs[0] and ' 80x48 ' in sigs[1] and sigs[0] != sigs[1], sigs
+    assert sigs[0].replace(' 48x80 ', ' 80x48 ') == sigs[1] and all(s.endswith(' nl') for s in sigs)
+    # a second engine per orientation reads its own line: nothing is appended, the bits stay
+    for hw in ((48, 80), (80, 48)):
+        eng = _engine(size=hw)
+        assert np.array_equal(eng.run(None, {'input': xs[hw]})[0], tuned[hw]), hw
+        eng.close()
+    assert path.read_text().splitlines() == lines
+    monkeypatch.setenv('TSM_AUTOTUNE', '0')
+    for hw in ((48, 80), (80, 48)):
+        eng = _engine(size=hw)
+        assert np.array_equal(eng.run(None, {'input': xs[hw]})[0], tuned[hw]), hw
+        eng.close()
 
 
 def test_tuned_and_untuned_forwards_are_bitwise_equal(hip_lib, monkeypatch, tmp_path):
@@ -236,6 +312,36 @@ def test_poisoned_engine_gives_the_same_bits(hip_lib, monkeypatch):
     assert np.array_equal(eng.run(None, {'input': x[:1]})[0], want[:1])
     assert np.array_equal(eng.forward_tap(x, 'layer3.2.nl.y'), want_y)
     eng.close()
+
+
+@pytest.mark.parametrize('hw', [(48, 80), (80, 48)], ids=_frame_id)
+def test_poisoned_engine_gives_the_same_bits_on_a_non_square_frame(hip_lib, monkeypatch, hw):
+    """The check that catches a buffer sized with the wrong side: under TSM_POISON=1 a launch that writes or reads H x W words
+    where W x H (or W / 2 x H / 2 keys) were allocated breaks a band or reads poison."""
+    x = clip_input(33 + hw[1], 2, 8, *hw)
+    eng = _engine(size=hw)
+    want = eng.run(None, {'input': x})[0]
+    want_y = eng.forward_tap(x, 'layer3.2.nl.y')
+    eng.close()
+    assert want_y.shape == (16, *G.maps_of('non_local', *hw)['layer3'], 512)
+    monkeypatch.setenv('TSM_POISON', '1')
+    eng = _engine(size=hw)
+    assert np.array_equal(eng.run(None, {'input': x})[0], want)
+    assert np.array_equal(eng.run(None, {'input': x[:1]})[0], want[:1])
+    assert np.array_equal(eng.forward_tap(x, 'layer3.2.nl.y'), want_y)
+    eng.close()
+
+
+def test_launch_counts_by_width_on_a_non_square_frame(hip_lib):
+    from workoutdetector_amd.engine import launch_trace
+    x = clip_input(34, 1, 8, 80, 48)
+    eng = _engine(size=(80, 48), max_clips=1)
+    eng.run(None, {'input': x})
+    with launch_trace() as tr:
+        eng.run(None, {'input': x})
+    eng.close()
+    assert tr.count('nonlocal_attn_kernel<256>') == 2 and tr.count('nonlocal_attn_kernel<512>') == 3, tr.kernels
+    assert tr.count('nonlocal_attn_kernel') == 5 and tr.count('maxpool2x2_kernel') == 5
 
 
 def test_launch_trace_and_timing_slots(hip_lib):

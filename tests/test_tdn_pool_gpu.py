@@ -3,7 +3,8 @@ csrc/tsm_tdn.hip: tdn_front_pool_kernel) and the pipelines on it (workoutdetecto
 
 The pool kernel spells the plain front end's arithmetic the same way, so everything that compares the pool forward with the NTCHW
 forward of the gathered planes is bit for bit.  Engines: depths (1, 1, 1, 2); 64 x 64 (2 x 2 front-end tiles: a halo across tiles
-and the map border) and 96 x 96 (3 x 3: an interior tile with a halo on every side).  Pools, tables and outputs are tests/_guard.py
+and the map border) and 96 x 96 (3 x 3: an interior tile with a halo on every side); and the non-square frames of
+tests/_geometry_cases.py, 64 x 96, 96 x 64 and 160 x 96 -- where H = W the two kernels cannot differ in a row pitch.  Pools, tables and outputs are tests/_guard.py
 tensors: a stray read reads poison, a stray store breaks a band."""
 import ctypes as C
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _geometry_cases as G
 from tests._guard import check, guarded, guarded_out
 from tests._tdn_cases import LOGITS_BAR, NUM_CLASS, bits as _bits, engine as _cases_engine, network as _model
 from tests._util import assert_close
@@ -22,12 +24,23 @@ TAPS = ('diff.conv1_5', 'diff.stem', 'stem')
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
-def _engine(h, T, max_clips=3, **kw):
-    return _cases_engine(h, h, T, D64, _model(D64, T)[1], max_clips=max_clips, **kw)
+def _hw(size):
+    return (size, size) if isinstance(size, int) else tuple(size)
 
 
-def _pool(n_frames, h, seed=7):
-    x = np.random.default_rng([seed, n_frames, h]).standard_normal((n_frames, 3, h, h)).astype(np.float32)
+def _frame_id(v):
+    return '%dx%d' % v if isinstance(v, tuple) else str(v)
+
+
+def _engine(size, T, max_clips=3, **kw):
+    """``size``: the side of a square frame, or (h, w)."""
+    h, w = _hw(size)
+    return _cases_engine(h, w, T, D64, _model(D64, T)[1], max_clips=max_clips, **kw)
+
+
+def _pool(n_frames, size, seed=7):
+    h, w = _hw(size)
+    x = np.random.default_rng([seed, n_frames, h] + ([] if isinstance(size, int) else [w])).standard_normal((n_frames, 3, h, w)).astype(np.float32)
     return guarded(torch.from_numpy(x).cuda(), name='pool')
 
 
@@ -51,7 +64,11 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
-def _assert_pool_equals_ntchw(eng, pool, table_np, taps=TAPS):
+TAP_MAPS = {'diff.conv1_5': 'conv1_5', 'diff.stem': 'ring_d', 'stem': 'ring_a'}          # (tests/_geometry_cases.py: tdn_maps)
+
+
+def _assert_pool_equals_ntchw(eng, pool, table_np, taps=TAPS, maps=None):
+    """``maps``: the case table's record of the frame -- the taps' shapes are then held to it."""
     n, T, _ = table_np.shape
     table = guarded(torch.from_numpy(table_np).cuda(), name='table')
     clips = _gathered(pool, table_np)
@@ -72,28 +89,70 @@ def _assert_pool_equals_ntchw(eng, pool, table_np, taps=TAPS):
             got = eng.forward_tap_pool(pool, name, table[lo:hi], n_clips=hi - lo)
             torch.cuda.synchronize()
             assert _same(got, eng.forward_tap(clips[lo:hi].cpu().numpy(), name)), name
+            if maps is not None:
+                assert got.shape == ((hi - lo) * T, *maps[TAP_MAPS[name]], 64), (name, got.shape)
     check(pool, table)
     return out
 
 
 # ---- 1. table mode against the NTCHW forward ------------------------------------------------------------------------------------
 @pytest.mark.parametrize('h, T, n, max_clips, consensus', [(64, 2, 1, 1, 'avg'), (64, 8, 3, 3, 'avg'), (64, 8, 3, 3, 'identity'),
-                                                          (96, 3, 3, 3, 'avg'), (64, 2, 10, 10, 'avg'), (64, 2, 5, 3, 'avg')],
-                         ids=lambda v: str(v))
+                                                          (96, 3, 3, 3, 'avg'), (64, 2, 10, 10, 'avg'), (64, 2, 5, 3, 'avg')] +
+                         [((c['h'], c['w']), c['T'], c['clips'], c['clips'], 'avg') for c in G.TDN_POOL], ids=_frame_id)
 def test_table_mode_is_the_ntchw_forward_of_the_gathered_planes(hip_lib, h, T, n, max_clips, consensus):
-    """(64, 2, 10, 10): front-end chunks of 8 + 2 inside one call; (64, 2, 5, 3): calls of 3 + 2 clips, split by forward_pool."""
+    """(64, 2, 10, 10): front-end chunks of 8 + 2 inside one call; (64, 2, 5, 3): calls of 3 + 2 clips, split by forward_pool.
+    h = (rows, columns): the non-square frames of tests/_geometry_cases.py, 2 x 3, 3 x 2 and 5 x 3 front-end tiles -- the pool
+    kernel's own copy of the plain front end's row pitch and tile walk, held to the plain kernel where H is not W."""
     eng = _engine(h, T, max_clips=max_clips, consensus=consensus)
     try:
         if max_clips == 10:
             assert eng.tdn_chunk_clips == 8
-        _assert_pool_equals_ntchw(eng, _pool(11, h), _table(n, T, 11))
+        maps = G.maps_of('tdn_pool', *h) if isinstance(h, tuple) else None
+        out = _assert_pool_equals_ntchw(eng, _pool(11, h), _table(n, T, 11), maps=maps)
+        assert tuple(out.shape) == ((n, T, NUM_CLASS) if consensus == 'identity' else (n, NUM_CLASS))
+        if maps is not None:                                    # which kernel that was
+            from workoutdetector_amd.engine import launch_trace
+            with launch_trace() as tr:
+                eng.forward_pool(_pool(11, h), torch.from_numpy(_table(n, T, 11)).cuda(), n_clips=n)
+            assert tr.count('tdn_front_pool_kernel') == 1 and tr.count('tdn_front_kernel') == 0, tr.kernels
+    finally:
+        eng.close()
+
+
+def test_non_square_pool_forward_against_float64(hip_lib, capsys):
+    """96 x 64: the bitwise chain above anchored to the float64 network at this orientation too (tests._tdn_cases.reference's
+    clips as the pool, the table naming each segment's five frames in place)."""
+    h, w, T, n = 96, 64, 3, 2
+    from tests._tdn_cases import clips_of, reference
+    want, _taps = reference(h, w, D64, T, n)
+    x = clips_of('plain', h, w, T, n)                                      # [n, T, 15, h, w]
+    pool = guarded(torch.from_numpy(np.array(x).reshape(n * T * 5, 3, h, w)).cuda(), name='pool')
+    table_np = np.arange(n * T * 5, dtype=np.int32).reshape(n, T, 5)
+    eng = _engine((h, w), T, max_clips=n, consensus='identity')
+    try:
+        table = guarded(torch.from_numpy(table_np).cuda(), name='table')
+        out = guarded_out(eng._out_shape(n), name='logits')
+        eng.forward_pool(pool, table, n_clips=n, out=out)
+        torch.cuda.synchronize()
+        check(out, pool, table)
+        err = assert_close(out.cpu().numpy(), want, what='pool forward 96x64', **LOGITS_BAR)
+        with capsys.disabled():
+            print(f'\n[tdn pool 96x64 T{T}] logits max|err|/scale {err:.2g}')
     finally:
         eng.close()
 
 
 # ---- 2. the kernel is total in the table ----------------------------------------------------------------------------------------
 def test_table_entries_outside_the_pool_are_planes_of_zeros(hip_lib):
-    h, T, n = 64, 3, 3
+    _entries_outside_the_pool(64)
+
+
+def test_table_entries_outside_the_pool_on_a_non_square_frame(hip_lib):
+    _entries_outside_the_pool((96, 64))
+
+
+def _entries_outside_the_pool(h):
+    T, n = 3, 3
     table = _table(n, T, 11)
     table[0, 0, 0], table[0, 1, 2], table[1, 0, 4], table[1, 2, 1], table[2, 1, 3] = -1, 11, I32_MIN, I32_MAX, 12
     table[2, 2] = (-1, 11, I32_MIN, I32_MAX, -2)            # a segment without any frame: an input of zeros
@@ -117,9 +176,19 @@ WINDOWS = {'clip 0: frames -2 and -1 clamp to 0': (45, 0, 3, 0, 34, 33),
 
 @pytest.mark.parametrize('case', list(WINDOWS), ids=lambda v: v.replace(' ', '_'))
 def test_window_mode_is_table_mode_of_the_numpy_rule(hip_lib, case):
+    _window_mode_is_table_mode(case, 64)
+
+
+@pytest.mark.parametrize('case', ['clip 0: frames -2 and -1 clamp to 0', 'a centre on the last frame, then past the end'],
+                         ids=lambda v: v.replace(' ', '_'))
+def test_window_mode_on_a_non_square_frame(hip_lib, case):
+    _window_mode_is_table_mode(case, (64, 96))
+
+
+def _window_mode_is_table_mode(case, h):
     from workoutdetector_amd.tdn_pipeline import tdn_clip_indices
     total, lo, hi, first, n_frames, pad = WINDOWS[case]
-    h, T, n = 64, 8, hi - lo
+    T, n = 8, hi - lo
     table_np = tdn_clip_indices(total, lo, hi, T, 8, 2, first_source_frame=first, pad=pad, n_frames=n_frames)
     if case.startswith('a centre on the last frame, then'):
         assert table_np[1, 2].tolist() == [12, 13, 14, 14, 14] and (table_np[1, 3:] == 15).all()
@@ -246,7 +315,15 @@ def test_window_mode_captured_on_a_side_stream(hip_lib):
 
 # ---- 6. poison ----------------------------------------------------------------------------------------------------------------------
 def test_the_whole_engine_under_poison(hip_lib):
-    h, T, n = 96, 3, 2
+    _whole_engine_under_poison(96)
+
+
+def test_the_whole_engine_under_poison_on_a_non_square_frame(hip_lib):
+    _whole_engine_under_poison((96, 64))
+
+
+def _whole_engine_under_poison(h):
+    T, n = 3, 2
     pool, table_np = _pool(11, h), _table(n, T, 11)
     table_np[1, 1, 4] = -1
     table = torch.from_numpy(table_np).cuda()
@@ -329,6 +406,38 @@ def test_the_error_contract_launches_nothing(hip_lib, sd0):
     finally:
         eng.close()
         other.close()
+
+
+def test_a_transposed_pool_is_refused_before_any_launch(hip_lib):
+    """[n, 3, W, H] frames to an H x W engine: as many words as the right pool, so the C ABI's bare pointer could not tell --
+    the wrapper's shape check is the only one there is."""
+    from workoutdetector_amd.engine import launch_trace
+    h, w, T = 96, 64, 2
+    pool = _pool(11, (h, w))
+    turned = guarded(pool.transpose(2, 3).contiguous(), name='transposed pool')
+    assert tuple(turned.shape) == (11, 3, w, h) and turned.numel() == pool.numel()
+    table = torch.from_numpy(_table(1, T, 11)).cuda()
+    window = dict(first_source_frame=0, total_frames=11, first_clip=0, clip_step=8, clip_stride=2, pad_frame=-1)
+    eng = _engine((h, w), T, max_clips=1)
+    try:
+        out = guarded_out(eng._out_shape(1), name='logits')
+        with launch_trace() as tr:
+            for kw in (dict(index=table), dict(window=window)):
+                with pytest.raises(ValueError, match=r'\[n_frames, 3, 96, 64\], got \(11, 3, 64, 96\)'):
+                    eng.forward_pool(turned, n_clips=1, out=out, **kw)
+                with pytest.raises(ValueError, match='3, 96, 64'):
+                    eng.forward_features_pool(turned, n_clips=1, **kw)
+                with pytest.raises(ValueError, match='3, 96, 64'):
+                    eng.forward_tap_pool(turned, 'stem', n_clips=1, **kw)
+        assert tr.kernels == [], tr.kernels
+        torch.cuda.synchronize()
+        assert bool((out.view(torch.int32) == 0x7FC07FC0).all()), 'the refused call wrote to its output'
+        check(turned)
+        eng.forward_pool(pool, table, n_clips=1, out=out)          # and the pool the right way round runs
+        torch.cuda.synchronize()
+        check(out, pool)
+    finally:
+        eng.close()
 
 
 # ---- 8. the counting pipeline -------------------------------------------------------------------------------------------------------

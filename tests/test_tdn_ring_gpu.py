@@ -3,7 +3,8 @@
 
 Every kernel keeps one summation order per output whatever the batch, and tdn_fuse_ring_kernel spells tdn_fuse_kernel's blend
 the same way: everything that compares segment phase + trunk phase with the whole forward on the same frames is bit for bit.
-Engines as in tests/test_tdn_pool_gpu.py: depths (1, 1, 1, 2) unless said otherwise.  Pools, tables, rings and outputs are
+Engines as in tests/test_tdn_pool_gpu.py: depths (1, 1, 1, 2) unless said otherwise; 64 x 96 and 96 x 64 from tests/_geometry_cases.py,
+where h, w, hd and wd are four different numbers.  Pools, tables, rings and outputs are
 tests/_guard.py tensors: a stray read reads poison, a stray store breaks a band."""
 import ctypes as C
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _geometry_cases as G
 from tests._guard import POISON, check, guarded, guarded_out
 from tests._tdn_cases import LOGITS_BAR, NUM_CLASS, bits as _bits, engine as _cases_engine, network as _model
 from tests._util import assert_close
@@ -22,12 +24,23 @@ TAPS = ('fuse2', 'layer2.0', 'layer4.0')
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
-def _engine(h, T, max_clips=3, depths=D64, **kw):
-    return _cases_engine(h, h, T, depths, _model(depths, T)[1], max_clips=max_clips, **kw)
+def _hw(size):
+    return (size, size) if isinstance(size, int) else tuple(size)
 
 
-def _pool(n_frames, h, seed=7):
-    x = np.random.default_rng([seed, n_frames, h]).standard_normal((n_frames, 3, h, h)).astype(np.float32)
+def _frame_id(v):
+    return '%dx%d' % v if isinstance(v, tuple) else str(v)
+
+
+def _engine(size, T, max_clips=3, depths=D64, **kw):
+    """``size``: the side of a square frame, or (h, w)."""
+    h, w = _hw(size)
+    return _cases_engine(h, w, T, depths, _model(depths, T)[1], max_clips=max_clips, **kw)
+
+
+def _pool(n_frames, size, seed=7):
+    h, w = _hw(size)
+    x = np.random.default_rng([seed, n_frames, h] + ([] if isinstance(size, int) else [w])).standard_normal((n_frames, 3, h, w)).astype(np.float32)
     return guarded(torch.from_numpy(x).cuda(), name='pool')
 
 
@@ -59,9 +72,13 @@ def _words(t):
     return t.contiguous().view(torch.int32)
 
 
-def _assert_split_equals_whole(eng, pool, seg_np, slots_np, first=0, n_slots=None, taps=TAPS, features=True):
+TAP_MAPS = {'fuse2': ('ring_a', 256), 'layer2.0': ('layer2', 512), 'layer4.0': ('layer4', 2048)}          # (tests/_geometry_cases.py)
+
+
+def _assert_split_equals_whole(eng, pool, seg_np, slots_np, first=0, n_slots=None, taps=TAPS, features=True, maps=None):
     """Segments ``seg_np`` [n, 5] into slots [first, first + n) of a guarded ring, clips by ``slots_np`` [n_clips, T] through
-    forward_ring: the forward_pool of the [n_clips, T, 5] table those slots expand to, bit for bit."""
+    forward_ring: the forward_pool of the [n_clips, T, 5] table those slots expand to, bit for bit.  ``maps``: the case table's
+    record of the frame -- the taps' shapes are then held to it."""
     n, (n_clips, T) = seg_np.shape[0], slots_np.shape
     ring_a, ring_d = _ring(eng, n_slots or first + n)
     seg = guarded(torch.from_numpy(seg_np).cuda(), name='segment table')
@@ -88,6 +105,8 @@ def _assert_split_equals_whole(eng, pool, seg_np, slots_np, first=0, n_slots=Non
         for name in taps:
             got_tap = eng.forward_tap_ring(ring_a, ring_d, slots[lo:hi], n_clips=hi - lo, stage=name)
             assert _same(got_tap, eng.forward_tap_pool(pool, name, table[lo:hi], n_clips=hi - lo)), name
+            if maps is not None:
+                assert got_tap.shape == ((hi - lo) * T, *maps[TAP_MAPS[name][0]], TAP_MAPS[name][1]), (name, got_tap.shape)
     torch.cuda.synchronize()
     check(pool, seg, slots)
     return ring_a, ring_d, out
@@ -95,21 +114,40 @@ def _assert_split_equals_whole(eng, pool, seg_np, slots_np, first=0, n_slots=Non
 
 # ---- 1. split equals whole --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('h, T, n_clips, max_clips, consensus', [(64, 8, 3, 3, 'avg'), (64, 8, 3, 3, 'identity'), (96, 8, 2, 2, 'avg'),
-                                                                (64, 2, 1, 1, 'avg')], ids=lambda v: str(v))
+                                                                (64, 2, 1, 1, 'avg')] +
+                         [((c['h'], c['w']), T, n, n, 'avg') for T, n in ((8, 2), (2, 1)) for c in G.TDN_RING], ids=_frame_id)
 def test_segment_phase_and_trunk_phase_are_the_whole_forward(hip_lib, h, T, n_clips, max_clips, consensus):
-    """(64, 2, 1, 1): alpha = 0.75, beta = 0.25 -- a blend whose products round, so the order of the fused multiply-add counts."""
+    """(64, 2, 1, 1): alpha = 0.75, beta = 0.25 -- a blend whose products round, so the order of the fused multiply-add counts.
+    h = (rows, columns): the non-square frames of tests/_geometry_cases.py, ring maps 16 x 24 / 8 x 12 and their transposes --
+    tdn_fuse_ring_kernel's own copy of the blend's h, w, hd, wd held to tdn_fuse_kernel where they differ."""
     eng = _engine(h, T, max_clips=max_clips, consensus=consensus)
     try:
         n = max(2, n_clips * T // 2 + 1)                       # fewer segments than clip positions: slots repeat
-        ring_a, ring_d, _out = _assert_split_equals_whole(eng, _pool(11, h), _segment_table(n, 11), _slot_table(n_clips, T, n))
+        maps = G.maps_of('tdn_ring', *h) if isinstance(h, tuple) else None
+        if maps is not None:
+            assert eng.ring_shapes(n) == ((n, *maps['ring_a'], 256), (n, *maps['ring_d'], 256))
+        ring_a, ring_d, _out = _assert_split_equals_whole(eng, _pool(11, h), _segment_table(n, 11), _slot_table(n_clips, T, n), maps=maps)
         check(ring_a, ring_d)                                  # every word of every slot was written, no band touched
+        if maps is not None:                                   # which kernel that was
+            from workoutdetector_amd.engine import launch_trace
+            with launch_trace() as tr:
+                eng.forward_ring(ring_a, ring_d, torch.from_numpy(_slot_table(n_clips, T, n)).cuda(), n_clips=n_clips)
+            assert tr.count('tdn_fuse_ring_kernel') == 1 and tr.count('tdn_fuse_kernel') == 0, tr.kernels
     finally:
         eng.close()
 
 
 # ---- 2. only what was asked is written --------------------------------------------------------------------------------------------
 def test_a_segment_call_writes_its_slots_and_nothing_else(hip_lib):
-    h, T, first, n, n_slots = 64, 8, 2, 3, 7
+    _writes_its_slots_and_nothing_else(64)
+
+
+def test_a_segment_call_writes_its_slots_on_a_non_square_frame(hip_lib):
+    _writes_its_slots_and_nothing_else((96, 64))
+
+
+def _writes_its_slots_and_nothing_else(h):
+    T, first, n, n_slots = 8, 2, 3, 7
     eng = _engine(h, T)
     try:
         ring_a, ring_d, _out = _assert_split_equals_whole(eng, _pool(11, h), _segment_table(n, 11), _slot_table(1, T, n, first=first),
@@ -128,10 +166,19 @@ def test_a_segment_call_writes_its_slots_and_nothing_else(hip_lib):
 def test_table_entries_outside_the_ring_are_zeros(hip_lib):
     """T = 8: alpha = beta = 0.5, both products exact, so torch's multiply-then-add equals the kernel's fused form bit for bit
     and fuse2's tap can be held to a torch expression on the ring itself."""
-    h, T, n_clips, n = 64, 8, 2, 6
-    eng = _engine(h, T)
+    _entries_outside_the_ring(64)
+
+
+def test_table_entries_outside_the_ring_on_a_non_square_frame(hip_lib):
+    """64 x 96: the torch expression indexes rows with h / 4 and columns with w / 4, each on its own."""
+    _entries_outside_the_ring((64, 96))
+
+
+def _entries_outside_the_ring(size):
+    (h, w), T, n_clips, n = _hw(size), 8, 2, 6
+    eng = _engine(size, T)
     try:
-        pool, seg_np = _pool(11, h), _segment_table(n, 11)
+        pool, seg_np = _pool(11, size), _segment_table(n, 11)
         ring_a, ring_d = _ring(eng, n + 1)                     # slot n: a segment of zeros
         eng.tdn_segments(pool, torch.from_numpy(seg_np).cuda(), n_segments=n, out=(ring_a[:n], ring_d[:n]))
         ring_a[n].zero_()
@@ -153,7 +200,9 @@ def test_table_entries_outside_the_ring_are_zeros(hip_lib):
         # fuse2 from the ring by torch: nearest upsample of an exact 2x is index // 2
         idx = torch.from_numpy(zeroed.reshape(-1).astype(np.int64)).cuda()
         a, d = ring_a[idx], ring_d[idx]
-        up = d[:, torch.arange(h // 4).cuda() // 2][:, :, torch.arange(h // 4).cuda() // 2]
+        rows, cols = torch.arange(h // 4).cuda() // 2, torch.arange(w // 4).cuda() // 2
+        up = d[:, rows][:, :, cols]
+        assert tuple(up.shape) == tuple(a.shape) == (n_clips * T, h // 4, w // 4, 256)
         assert _same(tap, (0.5 * a + 0.5 * up)), 'fuse2'
         assert not tap[1].any() and tap[0].any()                # clip 0, segment 1: zeros
     finally:
@@ -422,6 +471,47 @@ def test_the_error_contract_launches_nothing(hip_lib, sd0):
     finally:
         eng.close()
         other.close()
+
+
+def test_a_ring_with_its_spatial_dims_exchanged_is_refused_before_any_launch(hip_lib):
+    """a [n, W / 4, H / 4, 256] and d [n, W / 8, H / 8, 256] to an H x W engine: as many words as the right pair, so the C ABI's
+    bare pointers could not tell -- ``_check_ring`` is the only check there is, for both phases."""
+    from workoutdetector_amd.engine import launch_trace
+    h, w, T, n = 64, 96, 2, 3
+    eng = _engine((h, w), T, max_clips=2)
+    try:
+        pool = _pool(11, (h, w))
+        seg = torch.from_numpy(_segment_table(n, 11)).cuda()
+        slots = torch.from_numpy(_slot_table(1, T, n)).cuda()
+        maps = G.maps_of('tdn_ring', h, w)
+        sa, sd = (n, *maps['ring_a'], 256), (n, *maps['ring_d'], 256)
+        assert eng.ring_shapes(n) == (sa, sd)
+        turned = (guarded_out((n, sa[2], sa[1], 256), name='ring_a'), guarded_out((n, sd[2], sd[1], 256), name='ring_d'))
+        good = _ring(eng, n)
+        out = guarded_out((1, NUM_CLASS), name='logits')
+        with launch_trace() as tr:
+            for pair in (turned, (turned[0], good[1]), (good[0], turned[1])):
+                with pytest.raises(ValueError, match=r'need a \[3, 16, 24, 256\] and d \[3, 8, 12, 256\]'):
+                    eng._check_ring(*pair)
+                with pytest.raises(ValueError, match='need a'):
+                    eng.tdn_segments(pool, seg, n_segments=n, out=pair)
+                with pytest.raises(ValueError, match='need a'):
+                    eng.forward_ring(pair[0], pair[1], slots, n_clips=1, out=out)
+                with pytest.raises(ValueError, match='need a'):
+                    eng.forward_features_ring(pair[0], pair[1], slots, n_clips=1)
+                with pytest.raises(ValueError, match='need a'):
+                    eng.forward_tap_ring(pair[0], pair[1], slots, n_clips=1, stage='fuse2')
+        assert tr.kernels == [], tr.kernels
+        torch.cuda.synchronize()
+        for t in (out,) + turned + good:
+            assert bool((_words(t) == POISON).all())
+        assert eng._check_ring(*good) == n                      # and the pair the right way round runs
+        eng.tdn_segments(pool, seg, n_segments=n, out=good)
+        eng.forward_ring(good[0], good[1], slots, n_clips=1, out=out)
+        torch.cuda.synchronize()
+        check(out, pool, *good)
+    finally:
+        eng.close()
 
 
 # ---- 10. the pipelines -------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,9 @@
 and the engine against the float64 torch model with the wrapper's module tree (tests/_temporal_pool.py).
 
 Inputs are 64 x 64 (layer1 16 x 16, layer4 2 x 2; one case 80 x 80: 20 x 20 down to 3 x 3), seeded normal clips, two clips or more
-wherever the shift matters: with one clip a stage that still shifted over T instead of T / 2 would read the same frames.
+wherever the shift matters: with one clip a stage that still shifted over T instead of T / 2 would read the same frames.  The non-square frames come from
+tests/_geometry_cases.py (48 x 80, 80 x 48 and 90 x 70 with T = 6: layer1 23 x 18, three segments behind the pool); their tap shapes
+are asserted from that table.
 
 Bars.  The pool: ``torch.equal``.  Engine: the existing engine bars for f32 and bf16x3 alike (tests/test_bf16x3_gpu.py), logits
 ``rtol=1e-3, atol_scale=1e-5`` and taps ``rtol=1e-3, atol_scale=3e-5``."""
@@ -14,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _geometry_cases as G
 from tests._temporal_pool import clip_input, last_block, run_with_taps, taps_of, torch_tsm_tp, wrapper_keys
 from tests._util import assert_close
 
@@ -29,9 +32,18 @@ def _sd(base_model=R50, place='blockres'):
     return make_state_dict(0, 12, base_model, place)
 
 
+def _hw(size):
+    return (size, size) if isinstance(size, int) else tuple(size)
+
+
+def _frame_id(v):
+    return '%dx%d' % v if isinstance(v, tuple) else None
+
+
 def _engine(base_model=R50, place='blockres', T=8, size=64, consensus='avg', max_clips=2, dtype='f32', sd=None, temporal_pool=True):
     from workoutdetector_amd.engine import TsmEngine
-    return TsmEngine(num_class=12, num_segments=T, height=size, width=size, max_clips=max_clips,
+    h, w = _hw(size)
+    return TsmEngine(num_class=12, num_segments=T, height=h, width=w, max_clips=max_clips,
                      state_dict=sd if sd is not None else _sd(base_model, place), base_model=base_model, shift_place=place,
                      consensus_type=consensus, dtype=dtype, temporal_pool=temporal_pool)
 
@@ -64,6 +76,24 @@ def test_pool_equals_max_pool3d_bit_for_bit(hip_lib, T, B, dtype):
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'bf16x3'])
+@pytest.mark.parametrize('T', [8, 6, 2])
+@pytest.mark.parametrize('hw', G.frames_of('temporal_pool'), ids=_frame_id)
+def test_pool_equals_max_pool3d_bit_for_bit_on_non_square_frames(hip_lib, hw, T, dtype):
+    """The frames of tests/_geometry_cases.py (layer1 12 x 20, 20 x 12 and the odd 23 x 18), three clips; T = 6 leaves three
+    segments.  The tap shapes are the table's."""
+    B, (h1, w1) = 3, G.maps_of('temporal_pool', *hw)['layer1']
+    x = clip_input(10 * T + hw[0], B, T, *hw)
+    eng = _engine(T=T, size=hw, max_clips=B, dtype=dtype)
+    before = eng.forward_tap(x, f'layer1.{last_block(R50, 1)}')
+    after = eng.forward_tap(x, 'layer2.tpool')
+    eng.close()
+    assert before.shape == (B * T, h1, w1, 256) and after.shape == (B * T // 2, h1, w1, 256)
+    want = _pool_ref(before, T)
+    assert torch.equal(torch.from_numpy(after), want), f'{hw} T {T} {dtype}: {int((torch.from_numpy(after) != want).sum())} elements differ'
+    assert not np.array_equal(after, before[0::2])
+
+
+@pytest.mark.parametrize('dtype', ['f32', 'bf16x3'])
 def test_three_clips_through_two_slots_equal_the_single_runs(hip_lib, dtype):
     x = clip_input(31, 3, 8, 64, 64)
     eng = _engine(dtype=dtype)
@@ -77,28 +107,49 @@ def test_three_clips_through_two_slots_equal_the_single_runs(hip_lib, dtype):
     eng.close()
 
 
+def test_three_clips_through_two_slots_on_a_non_square_frame(hip_lib):
+    """90 x 70, T = 6: three segments a clip behind the pool, so clip c's pooled frames are rows 3 c .. 3 c + 2."""
+    x = clip_input(31, 3, 6, 90, 70)
+    eng = _engine(T=6, size=(90, 70))
+    all3 = eng.run(None, {'input': x})[0]
+    assert all3.shape == (3, 12)
+    pair = eng.forward_tap(x[:2], 'layer2.tpool')
+    assert pair.shape == (6, *G.maps_of('temporal_pool', 90, 70)['layer1'], 256)
+    for c in range(3):
+        assert np.array_equal(eng.run(None, {'input': x[c:c + 1]})[0][0], all3[c]), c
+    for c in range(2):
+        assert np.array_equal(eng.forward_tap(x[c:c + 1], 'layer2.tpool'), pair[3 * c:3 * c + 3]), c
+    eng.close()
+
+
 # ---- the engine against the float64 torch model --------------------------------------------------------------------------
 # (base_model, shift_place, T, size, mode, dtype)
 CASES = [(R50, 'blockres', 8, 64, 'avg', 'f32'), (R50, 'blockres', 4, 64, 'avg', 'f32'), (R50, 'blockres', 2, 64, 'avg', 'f32'),
          (R50, 'block', 8, 64, 'avg', 'f32'), (WRN, 'blockres', 8, 64, 'avg', 'f32'), (R18, 'blockres', 8, 64, 'avg', 'f32'),
          (R50, 'blockres', 8, 64, 'identity', 'f32'), (R50, 'blockres', 8, 64, 'features', 'f32'),
          (R50, 'blockres', 8, 64, 'avg', 'bf16x3'), (R50, 'blockres', 8, 80, 'avg', 'f32')]
+# the non-square frames of tests/_geometry_cases.py (size = (h, w)); 90 x 70 with T = 6: an odd segment count behind the pool
+CASES += [(R50, 'blockres', c['T'], (c['h'], c['w']), 'avg', c['dtype']) for c in G.TEMPORAL_POOL]
+CASES += [(R50, 'blockres', 6, (90, 70), 'identity', 'f32')]
+STAGE_MAPS = {'layer2.0': ('layer2', 512), 'layer3.1': ('layer3', 1024), 'layer4.2': ('layer4', 2048)}
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(base_model, place, T, size):
     """The float64 torch model's outputs for the seeded weights and this configuration's two clips: computed once."""
-    x = clip_input(100 + size + T, 2, T, size, size)
+    h, w = _hw(size)
+    x = clip_input(100 + size + T if isinstance(size, int) else 100 + h + w + T, 2, T, h, w)
     net = torch_tsm_tp(base_model, place, 12, T, sd=_sd(base_model, place))
     logits, seg, pooled, taps = run_with_taps(net, x, taps_of(base_model))
     return x, logits, seg, pooled, taps
 
 
-@pytest.mark.parametrize('base_model,place,T,size,mode,dtype', CASES)
+@pytest.mark.parametrize('base_model,place,T,size,mode,dtype', CASES, ids=_frame_id)
 def test_engine_against_float64_torch(hip_lib, base_model, place, T, size, mode, dtype):
     x, logits, seg, pooled, taps = _reference(base_model, place, T, size)
     eng = _engine(base_model, place, T, size, 'identity' if mode == 'identity' else 'avg', dtype=dtype)
-    what = f'{base_model} {place} T{T} {size}x{size} {mode} {dtype}'
+    what = f'{base_model} {place} T{T} {"%dx%d" % _hw(size)} {mode} {dtype}'
+    maps = G.maps_of('temporal_pool', *size) if isinstance(size, tuple) else None
     assert eng.out_segments == T // 2
     if mode == 'features':
         got = eng.forward_features(x)
@@ -112,6 +163,8 @@ def test_engine_against_float64_torch(hip_lib, base_model, place, T, size, mode,
     for stage in ('layer2.0', 'layer3.1', f'layer4.{last_block(base_model, 4)}'):
         tap = eng.forward_tap(x, stage)
         assert tap.shape[0] == 2 * (T // 2)
+        if maps is not None:                                    # a frame of the table: the whole shape, from the table
+            assert tap.shape == (2 * (T // 2), *maps[STAGE_MAPS[stage][0]], STAGE_MAPS[stage][1]), (stage, tap.shape)
         assert_close(tap, taps[stage], rtol=1e-3, atol_scale=3e-5, what=f'{what} {stage}')
     eng.close()
 
@@ -162,6 +215,23 @@ def test_poisoned_engine_gives_the_same_bits(hip_lib, monkeypatch, dtype):
     eng.close()
     monkeypatch.setenv('TSM_POISON', '1')
     eng = _engine(size=80, dtype=dtype)
+    assert np.array_equal(eng.run(None, {'input': x})[0], want)
+    assert np.array_equal(eng.run(None, {'input': x[:1]})[0], want[:1])
+    assert np.array_equal(eng.forward_tap(x, 'layer2.tpool'), want_pool)
+    eng.close()
+
+
+@pytest.mark.parametrize('hw, T', [((80, 48), 4), ((90, 70), 6)], ids=_frame_id)
+def test_poisoned_engine_gives_the_same_bits_on_a_non_square_frame(hip_lib, monkeypatch, hw, T):
+    """A per-frame buffer sized with the wrong side, or for T frames where T / 2 are left, breaks a band or reads poison."""
+    x = clip_input(33 + hw[0], 2, T, *hw)
+    eng = _engine(T=T, size=hw)
+    want = eng.run(None, {'input': x})[0]
+    want_pool = eng.forward_tap(x, 'layer2.tpool')
+    eng.close()
+    assert want_pool.shape == (T, *G.maps_of('temporal_pool', *hw)['layer1'], 256)
+    monkeypatch.setenv('TSM_POISON', '1')
+    eng = _engine(T=T, size=hw)
     assert np.array_equal(eng.run(None, {'input': x})[0], want)
     assert np.array_equal(eng.run(None, {'input': x[:1]})[0], want[:1])
     assert np.array_equal(eng.forward_tap(x, 'layer2.tpool'), want_pool)

@@ -708,7 +708,30 @@ int tsm_preprocess_indexed(const void *frames, int32_t pixel, int64_t n_frames, 
  * person_crop = 0, the crop fits the resized frame; the test is formed in 64 bits without overflow for ANY int32 words
  * (INT32_MIN and INT32_MAX included) before an address exists.  Every row of an invalid window is the normalised zero frame,
  * every channel (0 - mean) / std, and nothing is read for it; the box is total as in tsm_preprocess_clips.  One grid-stride
- * launch: n_windows is not limited by the launch geometry.  Enqueues on `stream`; no synchronisation. */
+ * launch: n_windows is not limited by the launch geometry.  Enqueues on `stream`; no synchronisation.
+ *
+ * person_crop = TSM_WINDOWS_IMAGE: the IMAGE model's transform over the windows -- tsm_preprocess_image's ToPILImage ->
+ * Resize(resize) -> CenterCrop(crop) -> ToTensor -> Normalize, Pillow's antialiased 8-bit resample in integers -- a step of
+ * ImageStreamBatcher, whose streams differ in resolution and whose every frame is a window of its own (n_segment = 1).
+ *   pixel:  TSM_PIXEL_U8, or a TSM_PIXEL_NV12_* code: a frame is 3 h w / 2 bytes with h and w even and is converted tap by tap
+ *           with the integer formula of the other NV12 paths.  TSM_PIXEL_F32 and the other YUV codes: TSM_ERR_UNSUPPORTED,
+ *           nothing launched (Pillow's path is 8-bit).
+ *   desc:   row c = {off_lo, off_hi, h, w, tab_lo, tab_hi, 0, 0}: off as above; tab = tab_hi * 2^32 + (unsigned) tab_lo, the
+ *           byte offset in `arena` of the coefficient block of the window's geometry, exactly tsm_preprocess_image's `tables`
+ *           for (h, w, resize, crop): [hb][hk] when the width changes, then [vb][vk] when the height does.  Windows of equal
+ *           geometry may share one block.  Words 6 and 7 are reserved and not read.
+ *   out:    as above; scale_255 must be 0 and crop <= resize, else TSM_ERR_INVALID_ARG.  A crop whose row of 3 * crop bytes
+ *           does not fit 64 KB of LDS: TSM_ERR_UNSUPPORTED.
+ *   A descriptor is valid only if the frame conditions above hold (for NV12: both sides even), the crop window lies in the
+ *   resized frame, the block -- crop * (2 + ksx) words if the width changes plus crop * (2 + ksy) if the height does, ksx =
+ *   2 * max(ceil(w / nw), 1) + 1 and ksy likewise, a count that follows from the geometry alone -- is empty or has tab >= 0,
+ *   tab % 16 == 0 and tab + 4 * words <= arena_bytes, and one output row's vertical support fits the kernel's 64 KB of LDS;
+ *   all formed in 64 bits for ANY int32 words before an address exists.  An invalid window reads nothing and is the
+ *   normalised zero frame.  The table CONTENTS cannot be validated: every bound is clamped before use, as in
+ *   tsm_preprocess_image, so the kernel reads only inside the window's frames and its block and writes exactly `out`.
+ *   Row (c, k) of a valid window equals, bit for bit, tsm_preprocess_image's row for that frame alone in the same out_layout
+ *   (NV12: for the frame converted to RGB).  One grid-stride launch over (window, frame, 8 output rows). */
+#define TSM_WINDOWS_IMAGE 16
 int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel, const int32_t *desc,
                            int32_t n_windows, int32_t n_segment, int32_t person_crop, float *out,
                            int32_t out_layout, int32_t resize, int32_t crop, int32_t scale_255, void *stream);

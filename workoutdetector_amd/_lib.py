@@ -16,6 +16,7 @@ LAYOUT_TDN_POOL = 16      # a TDN engine's input as a TsmTdnPool descriptor (hos
 LAYOUT_TDN_SEGMENTS = 17  # the segment phase of a TDN forward: a TsmTdnSegments descriptor, n_clips counts segments
 LAYOUT_TDN_RING = 18      # the trunk phase: a TsmTdnRing descriptor naming a ring of per-segment features and a slot table
 TDN_POOL_TABLE, TDN_POOL_WINDOW = 0, 1
+WINDOWS_IMAGE = 16        # tsm_preprocess_windows' person_crop argument: the image model's transform (TSM_WINDOWS_IMAGE)
 PIXEL_U8, PIXEL_F32 = 0, 1
 PIXEL_NV12_BT601, PIXEL_NV12_BT709, PIXEL_NV12_BT601_FULL, PIXEL_NV12_BT709_FULL = 16, 17, 18, 19
 _NV12_PIXELS = {'bt601': PIXEL_NV12_BT601, 'bt709': PIXEL_NV12_BT709, 'bt601-full': PIXEL_NV12_BT601_FULL,

@@ -2705,7 +2705,19 @@ int tsm_preprocess_windows(const void *arena, int64_t arena_bytes, int32_t pixel
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: non-positive size");
   tsm::WindowPreprocParams p{};
   if (int rc = set_pixel_format(&p, pixel, out_layout, scale_255)) return rc;
-  if (person_crop != 0 && person_crop != 1) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: person_crop must be 0 or 1");
+  if (person_crop == TSM_WINDOWS_IMAGE) {
+    if (scale_255) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: the image transform takes scale_255 = 0 (it divides by 255 itself)");
+    if (crop > resize) return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: crop larger than the resized frame");
+    if (pixel != TSM_PIXEL_U8 && !tsm_host::pixel_is_nv12(pixel))
+      return fail(nullptr, TSM_ERR_UNSUPPORTED, "preprocess_windows: the image transform takes TSM_PIXEL_U8 or TSM_PIXEL_NV12_* frames");
+    if (crop > tsm_host::kImageMaxCrop)
+      return fail(nullptr, TSM_ERR_UNSUPPORTED, "preprocess_windows: one row of crop " + std::to_string(crop) + " does not fit 64 KB of LDS");
+    p.arena = arena; p.dst = out; p.desc = desc; p.arena_bytes = arena_bytes; p.n_windows = n_windows; p.n_segment = n_segment;
+    p.person_crop = person_crop; p.resize = resize; p.crop = crop;
+    return op_status("preprocess_windows", tsm::launch_preprocess_image_windows(p, static_cast<hipStream_t>(stream)));
+  }
+  if (person_crop != 0 && person_crop != 1)
+    return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: person_crop must be 0, 1 or TSM_WINDOWS_IMAGE");
   if (!person_crop && crop > resize)
     return fail(nullptr, TSM_ERR_INVALID_ARG, "preprocess_windows: crop larger than the resized frame");
   p.arena = arena; p.dst = out; p.desc = desc; p.arena_bytes = arena_bytes; p.n_windows = n_windows; p.n_segment = n_segment;

@@ -607,6 +607,69 @@ TSM_HOST_DEVICE inline bool yuv_window_descriptor_ok(int layout, const int32_t d
   return true;
 }
 
+// ---- tsm_preprocess_windows in image mode (TSM_WINDOWS_IMAGE): the image model's transform (tsm_preprocess_image: Pillow's
+// antialiased 8-bit resample) over windows of different sizes.  Everything the kernel derives from a window's size is here, in
+// integers, for the kernel and for the host (tests/image_windows_host.cpp, under ASAN + UBSAN).
+// Taps per row of Pillow's coefficient table for one axis: 2 * ceil(max(in / out, 1)) + 1 (pil_ksize of the C ABI, whose
+// double quotient has the same ceiling: a non-integral in / out lies at least 1 / out from an integer).  in, out >= 1.
+TSM_HOST_DEVICE inline int image_ksize_int(int in, int out) {
+  const int64_t c = ((int64_t)in + out - 1) / out;
+  return 2 * (int)(c < 1 ? 1 : c) + 1;
+}
+// LDS rows a band of `band` output rows can need (image_rows_cap's rule, (band - 1) * scale + 2 * support + 2 with scale =
+// in / out and support = max(scale, 1), as an exact floor; never below the double's).  1 <= in <= 65535, out >= 1, band <= 8.
+TSM_HOST_DEVICE inline int image_rows_cap_int(int band, int in, int out) {
+  return in >= out ? (int)(((int64_t)(band + 1) * in) / out) + 2 : (int)(((int64_t)(band - 1) * in) / out) + 4;
+}
+// Bytes of one LDS row of `crop` pixels (three bytes each, padded to a dword).  crop <= kImageMaxCrop.
+constexpr int kImageMaxCrop = 21845;       // the largest crop whose row fits 64 KB
+TSM_HOST_DEVICE inline int image_row_stride(int crop) { return (crop * 3 + 3) & ~3; }
+// The band of output rows one pass works on: 8, 4, 2 or 1, the largest whose rows fit lds_bytes (`vert`: the height is
+// resampled, so a band needs the rows under its vertical support; else its own rows).  0: not even one output row fits.
+TSM_HOST_DEVICE inline int image_band(bool vert, int h, int nh, int crop, int lds_bytes, int *rows_cap) {
+  for (int band = 8; band >= 1; band /= 2) {
+    const int rows = vert ? image_rows_cap_int(band, h, nh) : band;
+    if ((int64_t)rows * image_row_stride(crop) <= lds_bytes) {
+      *rows_cap = rows;
+      return band;
+    }
+  }
+  return 0;
+}
+// One window of an image-mode launch: d = {off_lo, off_hi, h, w, tab_lo, tab_hi, -, -}; the frames as window_descriptor_ok
+// (one byte per channel) or nv12_window_descriptor_ok has them, the centre crop inside the resized frame, and the window's
+// coefficient block -- transform.image_tables' layout, [hb crop x 2][hk crop x ksx] when the width changes, then [vb crop x 2]
+// [vk crop x ksy] when the height does -- at byte `tab` of the arena: tab >= 0, tab % 16 == 0, tab + 4 * words <= arena_bytes
+// (not looked at when the block is empty), and one output row's vertical support within lds_bytes.  True only then, for ANY
+// eight int32 words, and no intermediate leaves int64.  n_segment, resize > 0, 0 < crop <= kImageMaxCrop, arena_bytes > 0.
+struct ImageWindow {
+  int64_t off, tab;            // byte offsets in the arena of the frames and of the table block
+  CropGeometry g;
+  int ksx, ksy;                // taps per table row; 0: that axis keeps its size and has no table
+  int64_t hwords, vwords;      // int32 words of the horizontal and the vertical part of the block
+  int band, rows_cap;          // image_band's choice
+};
+TSM_HOST_DEVICE inline bool image_window_ok(const int32_t d[kWindowDescWords], int n_segment, bool nv12, int64_t arena_bytes, int resize,
+                                            int crop, int lds_bytes, ImageWindow *win) {
+  if (nv12 ? !nv12_window_descriptor_ok(d, n_segment, arena_bytes, true, resize, crop, &win->off, &win->g)
+           : !window_descriptor_ok(d, n_segment, 1, arena_bytes, true, resize, crop, &win->off, &win->g))
+    return false;
+  const int h = d[2], w = d[3];
+  win->ksx = win->g.nw != w ? image_ksize_int(w, win->g.nw) : 0;
+  win->ksy = win->g.nh != h ? image_ksize_int(h, win->g.nh) : 0;
+  win->hwords = win->ksx ? (int64_t)crop * (2 + win->ksx) : 0;       // < 2^15 * 2^18
+  win->vwords = win->ksy ? (int64_t)crop * (2 + win->ksy) : 0;
+  const int64_t words = win->hwords + win->vwords;
+  win->tab = 0;
+  if (words > 0) {
+    const int64_t t = (int64_t)(((uint64_t)(uint32_t)d[5] << 32) | (uint32_t)d[4]);
+    if (t < 0 || (t & 15) != 0 || t > arena_bytes || 4 * words > arena_bytes - t) return false;
+    win->tab = t;
+  }
+  win->band = image_band(win->ksy != 0, h, win->g.nh, crop, lds_bytes, &win->rows_cap);
+  return win->band > 0;
+}
+
 // The buffer frames a range of clip windows touches.  Clip c, segment k is source frame step * c + stride * k; a position at or
 // past total_frames is the padded tail and reads no video frame; buffer frame j holds source frame stride * (first_frame + j).
 // For clips first_clip .. first_clip + n_clips - 1: `tail` = whether any position is padded, `first` = the buffer frame of the

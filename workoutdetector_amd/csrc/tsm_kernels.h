@@ -144,6 +144,11 @@ struct ImagePreprocParams {
   int band, rows_cap, stride;   // set by the launcher: output rows per workgroup, LDS rows, bytes per LDS row
 };
 hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s);
+// launch_preprocess_image's transform over windows of different sizes (see preprocess_image_windows_kernel): p.desc rows are
+// {off_lo, off_hi, h, w, tab_lo, tab_hi, -, -} (tsm_host::image_window_ok), frames uint8 RGB (src_is_u8) or NV12 (src_yuv 1),
+// person_crop and pre_scale are not read.  One launch with kImageMaxLds of dynamic LDS; hipErrorNotSupported for any other
+// frame format or a crop beyond tsm_host::kImageMaxCrop.
+hipError_t launch_preprocess_image_windows(const WindowPreprocParams &p, hipStream_t s);
 
 // The image model's vote (see frame_votes_kernel): pred [n] = first arg-max, state [n] = (sum of the last <= 7 preds) >= 4,
 // hist_in [n_hist <= 6] the preds before this batch (oldest first), hist_out [6] (nullable, must not alias hist_in) the last

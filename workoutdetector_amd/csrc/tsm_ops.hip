@@ -254,6 +254,12 @@ struct Taps {
       t[3][c] = m11 ? (float)a11[c] : 0.f;
     }
   }
+  // one pixel's three channels as integers (the image path: Pillow's 8-bit resample); 8-bit frames only
+  __device__ __forceinline__ void pixel(int64_t y, int64_t x, unsigned rgb[3]) const {
+    const T *a = frame + (y * w + x) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = (unsigned)a[c];
+  }
 };
 template <>
 struct Taps<Nv12> {
@@ -292,6 +298,14 @@ struct Taps<Nv12> {
     tap(y0, x1, uv01, m01, t[1]);
     tap(y1, x0, uv10, m10, t[2]);
     tap(y1, x1, uv11, m11, t[3]);
+  }
+  // one pixel as integers: one luma byte and one aligned 2-byte chroma load, then the conversion
+  __device__ __forceinline__ void pixel(int64_t y, int64_t x, unsigned rgb[3]) const {
+    const unsigned uv = pair(y, x);
+    int v[3];
+    tsm_host::nv12_pixel_rgb(k, frame[tsm_host::nv12_luma_offset(w, y, x)], (int)(uv & 255u), (int)(uv >> 8), v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb[c] = (unsigned)v[c];
   }
 };
 
@@ -1302,6 +1316,159 @@ hipError_t launch_preprocess_image(ImagePreprocParams p, hipStream_t s) {
   const int64_t blocks = (int64_t)p.n * ((p.crop + p.band - 1) / p.band);
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   TSM_KLAUNCH(preprocess_image_kernel, dim3((unsigned)blocks), dim3(256), (size_t)p.rows_cap * p.stride, s, p);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// preprocess_image_windows: preprocess_image over windows of DIFFERENT frame sizes (tsm_preprocess_windows with person_crop =
+// TSM_WINDOWS_IMAGE), one launch from raw frames to the engine's packed input in batch order -- a step of ImageStreamBatcher.
+// Window c's 8-dword descriptor {off_lo, off_hi, h, w, tab_lo, tab_hi, -, -} says where its n_segment contiguous frames and the
+// coefficient block of its geometry (transform.image_tables' layout) start in the arena.  The host sees neither the table nor
+// the sizes, so the launch has a FIXED dynamic LDS size (kImageMaxLds) and a grid-stride loop over the work items (window,
+// frame, group of 8 output rows); per item the workgroup
+//   * reads the descriptor and forms verdict and geometry (tsm_host::image_window_ok: int64, total in the eight words) BEFORE
+//     any address exists; an invalid window reads nothing and its rows are the normalised zero frame;
+//   * picks its own band -- 8, 4, 2 or 1 output rows, the largest whose rows under the vertical support fit the LDS -- and runs
+//     preprocess_image_kernel's two passes per band: horizontal, rounded to uint8, into LDS byte rows (the same row layout, so
+//     its bank behaviour), then vertical from LDS, (u8 / 255 - mean) / std, store_pixel_group.
+// Integer arithmetic up to the final normalisation: a row does not depend on the band, the item or the grid, and equals
+// preprocess_image_kernel's row for that frame bit for bit.  Src = Nv12: a source pixel is converted as it is read
+// (Taps<Nv12>::pixel), which is tsm_preprocess_image on the converted frame.  TOTAL in the table contents as well: every bound
+// is clamped -- in 64 bits where two table words meet -- into the frame / the rows in LDS before it is used.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int clampl(int64_t v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
+
+template <typename Src>
+__global__ void __launch_bounds__(256) preprocess_image_windows_kernel(const WindowPreprocParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char win_rows[];
+  const int crop = p.crop, stride = tsm_host::image_row_stride(crop);
+  const int nb8 = (crop + 7) / 8;
+  const int px = p.out_mode >= 2 ? 2 : 1;
+  const int wg = (crop + px - 1) / px;
+  const int64_t total = (int64_t)p.n_windows * p.n_segment * nb8;
+  for (int64_t item = blockIdx.x; item < total; item += gridDim.x) {
+    const int64_t f = item / nb8;                       // output frame: (window, segment)
+    const int g0 = (int)(item - f * nb8) * 8;
+    const int g1 = g0 + 8 < crop ? g0 + 8 : crop;
+    const int64_t c = f / p.n_segment;
+    const int k = (int)(f - c * p.n_segment);
+    typedef int desc_t __attribute__((ext_vector_type(4)));         // (16-byte aligned: the launcher checks the table's base)
+    const desc_t *dp = reinterpret_cast<const desc_t *>(p.desc) + c * 2;
+    const desc_t lo = dp[0], hi = dp[1];
+    const int32_t d[tsm_host::kWindowDescWords] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    tsm_host::ImageWindow win;
+    if (!tsm_host::image_window_ok(d, p.n_segment, p.src_yuv == 1, p.arena_bytes, p.resize, crop, kImageMaxLds, &win)) {
+      for (int i = threadIdx.x; i < (g1 - g0) * wg; i += 256) {
+        const int ry = i / wg, gx = i - ry * wg;
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        zero_frame_pixel(v);
+        if (px == 2 && gx * 2 + 1 < crop) zero_frame_pixel(v + 4);
+        store_pixel_group(p.dst, p.out_mode, crop, f, g0 + ry, gx, (f * crop + g0 + ry) * wg + gx, v);
+      }
+      continue;
+    }
+    const int h = d[2], w = d[3];
+    const Taps<Src> frame = Taps<Src>::of(static_cast<const char *>(p.arena) + win.off, k, h, w, p.nv12);
+    const int *tab = reinterpret_cast<const int *>(static_cast<const char *>(p.arena) + win.tab);
+    const int *hb = win.ksx ? tab : nullptr, *hk = tab + 2 * (int64_t)crop;
+    const int *vb = win.ksy ? tab + win.hwords : nullptr, *vk = tab + win.hwords + 2 * (int64_t)crop;
+    const int ksx = win.ksx, ksy = win.ksy;
+    for (int r0 = g0; r0 < g1; r0 += win.band) {
+      const int r1 = r0 + win.band < g1 ? r0 + win.band : g1;
+      // source rows [y0, y0 + nrows) under the band's vertical support
+      int y0, nrows;
+      if (vb) {
+        y0 = clampi(vb[2 * r0], 0, h - 1);
+        const int yend = clampl((int64_t)vb[2 * (r1 - 1)] + vb[2 * (r1 - 1) + 1], y0 + 1, h);
+        nrows = yend - y0 < win.rows_cap ? yend - y0 : win.rows_cap;
+      } else {
+        y0 = win.g.top + r0;
+        nrows = r1 - r0;
+      }
+      for (int i = threadIdx.x; i < nrows * crop; i += 256) {
+        const int r = i / crop, cx = i - r * crop;
+        unsigned char *o = win_rows + r * stride + cx * 3;
+        unsigned u[3];
+        if (hb) {
+          const int xmin = clampi(hb[2 * cx], 0, w - 1);
+          const int room = w - xmin < ksx ? w - xmin : ksx;
+          const int cnt = clampi(hb[2 * cx + 1], 0, room);
+          const int *kx = hk + (int64_t)cx * ksx;
+          unsigned s0 = 1u << 21, s1 = 1u << 21, s2 = 1u << 21;
+          for (int t = 0; t < cnt; ++t) {
+            const unsigned kv = (unsigned)kx[t];
+            frame.pixel(y0 + r, xmin + t, u);
+            s0 += u[0] * kv;
+            s1 += u[1] * kv;
+            s2 += u[2] * kv;
+          }
+          u[0] = clip8(s0);
+          u[1] = clip8(s1);
+          u[2] = clip8(s2);
+        } else {
+          frame.pixel(y0 + r, win.g.left + cx, u);
+        }
+        o[0] = (unsigned char)u[0];
+        o[1] = (unsigned char)u[1];
+        o[2] = (unsigned char)u[2];
+      }
+      __syncthreads();
+      for (int i = threadIdx.x; i < (r1 - r0) * wg; i += 256) {
+        const int ry = i / wg, gx = i - ry * wg;
+        const int cy = r0 + ry;
+        int ymin = ry, cnt = 1;
+        const int *ky = nullptr;
+        if (vb) {
+          ymin = clampl((int64_t)vb[2 * cy] - y0, 0, nrows - 1);
+          const int room = nrows - ymin < ksy ? nrows - ymin : ksy;
+          cnt = clampi(vb[2 * cy + 1], 0, room);
+          ky = vk + (int64_t)cy * ksy;
+        }
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int x = gx * px + q;
+          if (q >= px || x >= crop) continue;
+          const unsigned char *col = win_rows + ymin * stride + x * 3;
+          unsigned u[3];
+          if (ky) {
+            unsigned s0 = 1u << 21, s1 = 1u << 21, s2 = 1u << 21;
+            for (int t = 0; t < cnt; ++t) {
+              const unsigned kv = (unsigned)ky[t];
+              const unsigned char *e = col + t * stride;
+              s0 += e[0] * kv;
+              s1 += e[1] * kv;
+              s2 += e[2] * kv;
+            }
+            u[0] = clip8(s0);
+            u[1] = clip8(s1);
+            u[2] = clip8(s2);
+          } else {
+            u[0] = col[0];
+            u[1] = col[1];
+            u[2] = col[2];
+          }
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) v[4 * q + ch] = ((float)u[ch] / 255.0f - kMean[ch]) / kStd[ch];
+        }
+        store_pixel_group(p.dst, p.out_mode, crop, f, cy, gx, (f * crop + cy) * wg + gx, v);
+      }
+      __syncthreads();          // (the next band, or the next item, overwrites the rows this one still reads)
+    }
+  }
+}
+
+hipError_t launch_preprocess_image_windows(const WindowPreprocParams &p, hipStream_t s) {
+  if (!p.arena || !p.dst || !p.desc || (reinterpret_cast<uintptr_t>(p.arena) & 15) != 0 || (reinterpret_cast<uintptr_t>(p.desc) & 15) != 0 ||
+      p.arena_bytes <= 0 || p.n_windows <= 0 || p.n_segment <= 0 || p.resize <= 0 || p.crop <= 0 || p.out_mode < 0 || p.out_mode > 3 ||
+      p.crop > p.resize)
+    return hipErrorInvalidValue;
+  if (p.src_yuv > 1 || (!p.src_yuv && !p.src_is_u8) || p.crop > tsm_host::kImageMaxCrop) return hipErrorNotSupported;
+  const unsigned grid = grid_for((int64_t)p.n_windows * p.n_segment * ((p.crop + 7) / 8) * 256, 8192);
+  if (p.src_yuv)
+    TSM_KLAUNCH(preprocess_image_windows_kernel<Nv12>, dim3(grid), dim3(256), (size_t)kImageMaxLds, s, p);
+  else
+    TSM_KLAUNCH(preprocess_image_windows_kernel<unsigned char>, dim3(grid), dim3(256), (size_t)kImageMaxLds, s, p);
   return hipGetLastError();
 }
 

@@ -431,6 +431,14 @@ class TsmEngine:
         inp = self._pool_input(frames, index, window, n_clips)      # (cap: forward_tap's bound, the stem conv's output, layer1's)
         return self._run_tap(inp, stage, inp.n_clips * self.num_segments * self.height * self.width * 16, 'forward_tap_pool')
 
+    def preprocess_image_windows(self, arena, desc, n_windows: int, n_segment: Optional[int] = None, **kw):
+        """``engine.preprocess_image_windows`` into THIS engine's input: its ``packed_layout``, its ``num_segments`` and the
+        ``data_transform`` geometry ``create_image_model`` recorded (256 / the engine's height otherwise), unless given."""
+        kw.setdefault('resize', int(getattr(self, 'image_resize', 256)))
+        kw.setdefault('crop', int(getattr(self, 'image_crop', self.height)))
+        kw.setdefault('out_layout', self.packed_layout)
+        return preprocess_image_windows(arena, desc, n_windows, self.num_segments if n_segment is None else n_segment, **kw)
+
     # ---- a TDN forward in two phases (include/tsm_hip.h: TSM_LAYOUT_TDN_SEGMENTS / TSM_LAYOUT_TDN_RING) ------------------
     def ring_shapes(self, n_slots: int) -> tuple:
         """Shapes of a ring of ``n_slots`` per-segment features: (a [n, H / 4, W / 4, 256], d [n, H / 8, W / 8, 256])."""
@@ -1314,6 +1322,44 @@ def preprocess_windows(arena, desc, n_windows: int, n_segment: int = 8, person_c
     _lib.check(_lib.load().tsm_preprocess_windows(arena.data_ptr(), arena.numel() * arena.element_size(), pixel, desc.data_ptr(),
                                                   n_windows, n_segment, int(bool(person_crop)), out.data_ptr(), layout,
                                                   int(resize), int(crop), int(scale_255), _stream(arena)))
+    return out
+
+
+def preprocess_image_windows(arena, desc, n_windows: int, n_segment: int = 1, resize: int = 256, crop: int = 224,
+                             out_layout: Optional[int] = None, frame_format: str = 'rgb', colorimetry: Optional[str] = None,
+                             out=None):
+    """The image model's transform over windows of different frame sizes (``tsm_preprocess_windows`` with ``person_crop =
+    _lib.WINDOWS_IMAGE``), one launch from raw frames to the engine's input in batch order: what one step of
+    ``ImageStreamBatcher`` needs.
+
+    arena: contiguous, 16-byte aligned CUDA uint8 tensor holding every window's frames AND the coefficient block of every
+    geometry (``transform.image_tables``); desc: contiguous CUDA int32 [n_windows, 8], row c = (off_lo, off_hi, h, w, tab_lo,
+    tab_hi, 0, 0) (``transform.image_window_descriptors`` builds and validates it, ``transform.image_window_arena`` lays the
+    arena out).  Returns float32 [n_windows, n_segment, ...one frame] in ``out_layout`` (default LAYOUT_NTHWC4); every row
+    equals ``preprocess_image``'s row for that frame bit for bit.  ``frame_format='nv12'``: windows of NV12 frames [3h/2, w]
+    converted tap by tap by ``colorimetry`` -- ``preprocess_image`` of ``transform.nv12_to_rgb`` of the frame; any other format
+    is NotImplementedError.  The kernel is total in the table: an invalid window reads nothing and yields normalised zero
+    frames."""
+    import torch
+    from .transform import IMAGE_WINDOW_FORMATS, check_frame_format
+    if frame_format not in IMAGE_WINDOW_FORMATS:
+        raise NotImplementedError(f'the image transform takes frame_format in {IMAGE_WINDOW_FORMATS}, got {frame_format!r}')
+    colorimetry = check_frame_format(frame_format, colorimetry)
+    if not (hasattr(arena, 'is_cuda') and arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()
+            and arena.numel() > 0 and arena.data_ptr() % 16 == 0):
+        raise ValueError('arena must be a contiguous, 16-byte aligned, non-empty uint8 CUDA tensor')
+    n_windows, n_segment = int(n_windows), int(n_segment)
+    if n_windows <= 0 or n_segment <= 0:
+        raise ValueError(f'n_windows and n_segment must be positive, got {n_windows}, {n_segment}')
+    if not (hasattr(desc, 'is_cuda') and desc.is_cuda and desc.device == arena.device and desc.dtype == torch.int32
+            and tuple(desc.shape) == (n_windows, 8) and desc.is_contiguous() and desc.data_ptr() % 16 == 0):
+        raise ValueError(f'desc must be a contiguous, 16-byte aligned int32 tensor [{n_windows}, 8] on {arena.device}')
+    layout = _lib.LAYOUT_NTHWC4 if out_layout is None else out_layout
+    out = _out(out, (n_windows, n_segment) + _frame_shape(layout, crop, 'out_layout'), torch.float32, arena)
+    pixel = _lib.pixel_code(frame_format, colorimetry) if colorimetry is not None else _lib.PIXEL_U8
+    _lib.check(_lib.load().tsm_preprocess_windows(arena.data_ptr(), arena.numel(), pixel, desc.data_ptr(), n_windows, n_segment,
+                                                  _lib.WINDOWS_IMAGE, out.data_ptr(), layout, int(resize), int(crop), 0,
+                                                  _stream(arena)))
     return out
 
 

@@ -944,7 +944,11 @@ def _image_logits_device(model, frames_u8: torch.Tensor) -> torch.Tensor:
 def _image_scores_host(model, frames_u8: torch.Tensor, transform: ImageTransform) -> np.ndarray:
     """Non-engine models: the CPU ``ImageTransform``, then a torch module (``model(x[n,3,H,W])``) or an onnxruntime-style
     session (one ``run`` per frame on [1,3,H,W], as the reference feeds it)."""
-    x = transform(frames_u8)
+    return _image_scores_of(model, transform(frames_u8))
+
+
+def _image_scores_of(model, x: torch.Tensor) -> np.ndarray:
+    """``_image_scores_host`` behind the transform: x float32 [n, 3, crop, crop] -> scores [n, num_class]."""
     if hasattr(model, 'run') and hasattr(model, 'get_inputs'):
         name = model.get_inputs()[0].name
         return np.stack([np.asarray(model.run(None, {name: x[i:i + 1].numpy()})[0][0], dtype=np.float32)

@@ -12,6 +12,10 @@ The reference runs one blocking batch-1 ``session.run`` per client window.
 on streams: ``push(..., box=)`` carries the detector's first box of a frame, a window is cropped to the union of its frames'
 boxes (``transform.person_box``).  The detector and any tracker stay the caller's.
 
+``ImageStreamBatcher`` is the same for the per-frame image model (``count_by_image_model``, utils/inference_count.py:192-243):
+every frame of every stream, of any mix of sizes, through ONE ``tsm_preprocess_windows`` launch in image mode per batch; the
+vote over the last 7 frames and the counter per stream on the host.
+
 No transport here (the WebSocket/HTTP front is outside the hot path): a server
 calls ``push`` from its receive loop and ``step`` on a timer or whenever ``ready()`` is large enough.
 """
@@ -25,10 +29,11 @@ import numpy as np
 import torch
 
 from . import staging
-from .counting import RepCounter, scores_to_preds
+from .counting import VOTE_WINDOW, RepCounter, scores_to_preds, vote_states
 from .inference_count import NUM_SEGMENTS, need_clip_rows
-from .transform import (Box, PersonCropTransform, TestTransform, build_test_transform, check_frame_format, nv12_luma_hw,
-                        nv12_to_rgb, person_box, window_descriptors, yuv_frame_bytes_view, yuv_luma_hw, yuv_to_rgb)
+from .transform import (IMAGE_WINDOW_FORMATS, Box, ImageTransform, PersonCropTransform, TestTransform, build_test_transform,
+                        check_frame_format, image_tables, image_window_descriptors, nv12_luma_hw, nv12_to_rgb, person_box,
+                        window_descriptors, yuv_frame_bytes_view, yuv_luma_hw, yuv_to_rgb)
 
 
 @dataclass
@@ -291,4 +296,238 @@ class StreamBatcher:
                 out.setdefault(sid, []).append((widx, state, count))
                 if self.on_window is not None:
                     self.on_window(sid, widx, state, count)
+        return out
+
+
+# ---- the image model on streams --------------------------------------------------------------------------------------------
+@dataclass
+class ImageStreamState:
+    counter: RepCounter
+    history: List[int] = field(default_factory=list)      # arg-max of the stream's last <= 6 processed frames (the vote's deque)
+    states: List[int] = field(default_factory=list)       # one voted state per processed frame
+    frames_seen: int = 0
+    queued: int = 0                                       # frames pushed and not yet run
+
+
+class _ImageChunk:
+    """The frames of one future batch, in arrival order: on the engine path one byte arena (frames, and the coefficient
+    block of every geometry the chunk holds, each start 16-byte aligned) that is ONE upload away from the GPU; on the host
+    path the frames themselves."""
+
+    def __init__(self):
+        self.sids: List[Hashable] = []
+        self.shapes: List[Tuple[int, int]] = []
+        self.offsets: List[int] = []
+        self.tables: Dict[Tuple[int, int], int] = {}
+        self.buf: Optional[torch.Tensor] = None
+        self.used = 0
+        self.frames: List[np.ndarray] = []
+
+
+class ImageStreamBatcher:
+    """Online counting with the per-frame IMAGE model (the reference's default ``--model-type``; ``count_by_image_model``,
+    utils/inference_count.py:192-243) for many concurrent streams on one engine.  ``push(stream_id, frame)`` queues an HWC
+    uint8 frame -- every frame is a window of its own, so the size may change between the frames of a stream; ``step()`` runs
+    every queued frame of every stream, in arrival order, in batches of at most ``max_batch`` (default: the engine's
+    ``max_clips``) and returns ``{stream_id: [(frame_index, state, count), ...]}``; ``on_frame(stream_id, frame_index, state,
+    count)`` is called per frame.  ``result`` / ``close`` give ``(count, reps)``.
+
+    On a ``TsmEngine`` built by ``create_image_model`` a batch is: the frames and the coefficient tables of their geometries,
+    copied into a page-locked arena as the frames arrive; ONE upload (the descriptor table rides at the arena's end); ONE
+    ``tsm_preprocess_windows`` launch in image mode for any mix of sizes, into the engine's packed layout; the forward; one
+    ``tsm_scores_to_states`` launch (no softmax, threshold -inf: the first arg-max, ``tsm_frame_votes``' tie rule); 4 bytes
+    per frame back, once per step.  The vote -- ``counting.vote_states`` over a 6-deep history per stream -- and the
+    incremental ``RepCounter(7)`` stay on the host: a handful of integers per frame.  For any interleaving of ``push`` and
+    ``step`` a stream's states equal ``image_states(model, its frames)[0]`` and ``close`` equals ``count_by_image_model``.
+
+    ``frame_format='nv12'`` (``colorimetry``: ``transform.COLORIMETRIES``, default ``'bt601'``): ``push`` takes decoder
+    surfaces, uint8 [3H/2, W] with H and W even, staged as they are and converted inside the launch: states and counts equal
+    those of an RGB batcher fed ``nv12_to_rgb`` of the frames.  Any other model (a stub, a torch module, an
+    onnxruntime-style session) takes the host path: ``ImageTransform`` and the scoring of ``inference_images``, the same vote
+    and counters; NV12 frames are converted when they arrive.
+
+    Page-locked memory is bounded by ``max_pinned_bytes``: beyond it an arena is pageable (a slower upload, nothing else)."""
+
+    def __init__(self, model, max_batch: Optional[int] = None, frame_format: str = 'rgb', colorimetry: Optional[str] = None,
+                 on_frame: Optional[Callable[[Hashable, int, int, int], None]] = None, max_pinned_bytes: int = 1 << 30):
+        if frame_format not in IMAGE_WINDOW_FORMATS:
+            raise NotImplementedError(f'ImageStreamBatcher takes frame_format in {IMAGE_WINDOW_FORMATS} (Pillow\'s resample is 8-bit RGB), '
+                                      f'got {frame_format!r}')
+        self.colorimetry = check_frame_format(frame_format, colorimetry)
+        self.frame_format = frame_format
+        if getattr(model, 'tdn_depths', None):
+            raise NotImplementedError('ImageStreamBatcher runs the per-frame image model; a TDN engine takes five frames per segment: '
+                                      'use TdnStreamBatcher')
+        if getattr(model, 'num_segments', 1) != 1:
+            raise ValueError(f'ImageStreamBatcher needs an engine with num_segments=1 (engine.create_image_model), got '
+                             f'{model.num_segments}: use StreamBatcher for the video model')
+        need_clip_rows(model, 'ImageStreamBatcher')           # (consensus_type='identity')
+        self.model = model
+        self.resize, self.crop = int(getattr(model, 'image_resize', 256)), int(getattr(model, 'image_crop', 224))
+        self._dev = staging.engine_device(model) if staging.device_path(model) else None
+        if self._dev is not None and (model.height, model.width) != (self.crop, self.crop):
+            raise ValueError(f'the engine takes {model.height} x {model.width} frames, the transform crops to {self.crop}')
+        self.max_batch = int(max_batch if max_batch is not None else (getattr(model, 'max_clips', 32) if self._dev is not None else 32))
+        if self.max_batch <= 0:
+            raise ValueError(f'max_batch must be positive, got {max_batch}')
+        self.on_frame = on_frame
+        self.transform = ImageTransform(self.resize, self.crop)
+        self.streams: Dict[Hashable, ImageStreamState] = {}
+        self._chunks: Deque[_ImageChunk] = deque()
+        self.max_pinned_bytes, self.pinned_bytes = int(max_pinned_bytes), 0
+        self._free: List[torch.Tensor] = []                           # idle page-locked arenas
+        self._inflight: List[Tuple[object, torch.Tensor]] = []        # (event behind the upload, arena)
+        self._carry: Dict[Hashable, List[Tuple[int, int, int]]] = {}
+
+    # ---- ingest -------------------------------------------------------------------------------------------
+    def open(self, stream_id: Hashable) -> ImageStreamState:
+        if stream_id not in self.streams:
+            self.streams[stream_id] = ImageStreamState(RepCounter(VOTE_WINDOW))
+        return self.streams[stream_id]
+
+    def push(self, stream_id: Hashable, frame) -> None:
+        arr = np.asarray(frame)
+        if self.frame_format == 'nv12':
+            if arr.dtype != np.uint8 or arr.ndim != 2:
+                raise ValueError(f'an NV12 frame must be uint8 [3H/2,W], got {arr.dtype} {arr.shape}')
+            h, w = nv12_luma_hw(arr.shape)
+            if self._dev is None:
+                arr = nv12_to_rgb(arr, self.colorimetry)[0]
+        elif arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3 or 0 in arr.shape:
+            raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
+        else:
+            h, w = int(arr.shape[0]), int(arr.shape[1])
+        # the refusals of a window, before anything is queued: a side beyond 65535, a crop larger than the resized frame
+        image_window_descriptors([(h, w)], [0], [0], self.resize, self.crop, self.frame_format)
+        tables = image_tables(h, w, self.resize, self.crop) if self._dev is not None else None
+        st = self.open(stream_id)
+        if not self._chunks or len(self._chunks[-1].sids) >= self.max_batch:
+            self._chunks.append(_ImageChunk())
+        ch = self._chunks[-1]
+        if self._dev is not None:
+            if (h, w) not in ch.tables:
+                ch.tables[(h, w)] = self._append(ch, tables.view(np.uint8)) if tables.size else 0
+            ch.offsets.append(self._append(ch, arr.reshape(-1)))
+        else:
+            ch.frames.append(np.ascontiguousarray(arr))
+        ch.sids.append(stream_id)
+        ch.shapes.append((h, w))
+        st.frames_seen += 1
+        st.queued += 1
+
+    def _append(self, ch: _ImageChunk, data: np.ndarray) -> int:
+        """Copy ``data`` (uint8, flat) to the chunk's arena at the next 16-byte boundary; returns its byte offset."""
+        off, n = ch.used, int(data.size)
+        end = off + (n + 15) // 16 * 16
+        if ch.buf is None or end > ch.buf.numel():
+            old = ch.buf
+            ch.buf = self._take(max(end, 2 * (old.numel() if old is not None else 0)))
+            if old is not None:
+                ch.buf[:off].copy_(old[:off])
+                self._give_back(old)
+        ch.buf.numpy()[off:off + n] = data
+        ch.used = end
+        return off
+
+    def _take(self, nbytes: int) -> torch.Tensor:
+        """An arena of at least ``nbytes``: an idle page-locked one that is large enough, a newly pinned one while the budget
+        lasts (idle ones give their bytes back first), else pageable memory."""
+        self._recycle()
+        fit = [b for b in self._free if b.numel() >= nbytes]
+        if fit:
+            buf = min(fit, key=lambda b: b.numel())
+            self._free = [b for b in self._free if b is not buf]
+            return buf
+        nbytes = max(nbytes, 1 << 20)
+        if self.pinned_bytes + nbytes > self.max_pinned_bytes:
+            self.pinned_bytes -= sum(b.numel() for b in self._free)
+            self._free = []
+        if self.pinned_bytes + nbytes > self.max_pinned_bytes:
+            return torch.empty(nbytes, dtype=torch.uint8)
+        self.pinned_bytes += nbytes
+        return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+
+    def _give_back(self, buf: Optional[torch.Tensor]) -> None:
+        if buf is not None and buf.is_pinned():
+            self._free.append(buf)
+
+    def _recycle(self) -> None:
+        still = []
+        for ev, buf in self._inflight:
+            if ev.query():
+                self._give_back(buf)
+            else:
+                still.append((ev, buf))
+        self._inflight = still
+
+    def ready(self) -> int:
+        return sum(len(ch.sids) for ch in self._chunks)
+
+    def result(self, stream_id: Hashable) -> Tuple[int, List[int]]:
+        st = self.streams[stream_id]
+        return st.counter.count, list(st.counter.reps)
+
+    def close(self, stream_id: Hashable) -> Tuple[int, List[int]]:
+        """Run what is still queued (a frame counts once it was pushed: ``count_by_image_model`` drops none; the other streams'
+        rows of that step are returned by the next ``step()``), then drop the stream -> (count, reps)."""
+        if self.streams[stream_id].queued:
+            rest = self.step()
+            rest.pop(stream_id, None)
+            self._carry = rest                                # (the other streams' rows of that step: the next step() returns them)
+        st = self.streams.pop(stream_id)
+        if not self.streams:
+            self.pinned_bytes -= sum(b.numel() for b in self._free)
+            self._free = []
+        return st.counter.count, list(st.counter.reps)
+
+    # ---- compute ------------------------------------------------------------------------------------------
+    def _preds_device(self, ch: _ImageChunk) -> torch.Tensor:
+        """One batch on the engine: int32 CUDA [n], the first arg-max of every frame's logits (still being computed)."""
+        from .engine import preprocess_image_windows, scores_to_states
+        n = len(ch.sids)
+        desc = image_window_descriptors(ch.shapes, ch.offsets, [ch.tables[s] for s in ch.shapes], self.resize, self.crop, self.frame_format)
+        doff = self._append(ch, desc.reshape(-1).view(np.uint8))
+        arena = ch.buf[:ch.used].to(self._dev, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._inflight.append((done, ch.buf))
+        table = arena[doff:doff + n * 32].view(torch.int32).view(n, 8)
+        x = preprocess_image_windows(arena, table, n, 1, resize=self.resize, crop=self.crop, out_layout=self.model.packed_layout,
+                                     frame_format=self.frame_format, colorimetry=self.colorimetry)
+        logits = self.model.forward_device(x, layout=self.model.packed_layout)
+        return scores_to_states(logits, threshold=float('-inf'), softmax=False)
+
+    def _preds_host(self, ch: _ImageChunk) -> List[int]:
+        from .inference_count import _image_scores_of
+        x = torch.cat([self.transform(f) for f in ch.frames])
+        return _image_scores_of(self.model, x).argmax(axis=1).tolist()
+
+    def step(self) -> Dict[Hashable, List[Tuple[int, int, int]]]:
+        """Run every queued frame (arrival order: a stream's frames stay in order) and update the votes and the counters."""
+        out, self._carry = self._carry, {}
+        order: List[Hashable] = []
+        pending = []
+        while self._chunks:
+            ch = self._chunks.popleft()
+            # enqueue only: the next batch's upload and launches queue up behind this one's
+            pending.append(self._preds_device(ch) if self._dev is not None else self._preds_host(ch))
+            order += ch.sids
+        if not pending:
+            return out
+        if self._dev is not None:
+            preds = torch.cat(pending).cpu().tolist()       # the step's only sync: 4 bytes per frame
+            self._recycle()
+        else:
+            preds = [p for piece in pending for p in piece]
+        for sid, pred in zip(order, preds):
+            st = self.streams[sid]
+            # (-1 is tsm_scores_to_states' answer to a NaN first logit, where the first arg-max is class 0)
+            (state,), st.history = vote_states([max(int(pred), 0)], st.history)
+            idx = len(st.states)
+            st.states.append(state)
+            st.queued -= 1
+            count = st.counter.push(state)
+            out.setdefault(sid, []).append((idx, state, count))
+            if self.on_frame is not None:
+                self.on_frame(sid, idx, state, count)
         return out

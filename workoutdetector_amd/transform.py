@@ -20,7 +20,8 @@ out of scope; the boxes are the caller's (their own detector, a tracker, annotat
 The IMAGE model's transform is a third one (``data_transform``, utils/inference_count.py:27-34): ``ToPILImage -> Resize(256)
 -> CenterCrop(224) -> ToTensor -> Normalize`` -- Pillow's antialiased two-pass resample on uint8, NOT the tensor bilinear
 above.  ``pil_resample_tables`` / ``pil_resize_u8`` / ``ImageTransform`` reproduce it to the bit without Pillow;
-``image_tables`` packs the tables ``tsm_preprocess_image`` takes.
+``image_tables`` packs the tables ``tsm_preprocess_image`` takes; ``image_window_descriptors`` /
+``image_window_arena`` build the table and the arena of ``tsm_preprocess_windows`` in image mode (frames of different sizes).
 """
 from __future__ import annotations
 
@@ -493,6 +494,29 @@ def pil_ksize(in_size: int, out_size: int) -> int:
     return int(math.ceil(max(in_size / out_size, 1.0))) * 2 + 1
 
 
+def _pil_rows(in_size: int, out_size: int, first: int, count: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Rows ``first .. first + count - 1`` of Pillow's coefficient tables of one axis (below), all at once: every step is the
+    scalar loop's IEEE double operation on a column of rows -- the weights are added tap by tap, in order (Pillow adds them
+    so, in double; a tap behind a row's last adds 0.0) -- so the integers are those of the loop, whatever the rows asked for."""
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    center = (np.arange(first, first + count, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(0, (center - support + 0.5).astype(np.int64))                    # (int(): towards zero, as astype)
+    xmax = np.minimum(in_size, (center + support + 0.5).astype(np.int64)) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs(((x + xmin[:, None]) - center[:, None] + 0.5) * ss))
+    w[x >= xmax[:, None]] = 0.0
+    ww = np.zeros(count, dtype=np.float64)
+    for t in range(ksize):
+        ww += w[:, t]
+    w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+    kk = (w * float(1 << PRECISION_BITS) + np.where(w < 0.0, -0.5, 0.5)).astype(np.int64).astype(np.int32)
+    return np.stack([xmin, xmax], axis=1).astype(np.int32), kk
+
+
 @functools.lru_cache(maxsize=64)
 def pil_resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
     """Pillow's coefficient tables of one axis for the bilinear (triangle) filter on 8-bit channels (Resample.c:
@@ -501,25 +525,7 @@ def pil_resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.nda
     behind a row's taps.  The returned arrays are cached and read-only."""
     if in_size <= 0 or out_size <= 0:
         raise ValueError(f'sizes must be positive, got {in_size} -> {out_size}')
-    scale = in_size / out_size
-    filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
-    ksize = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), dtype=np.int32)
-    kk = np.zeros((out_size, ksize), dtype=np.int32)
-    ss = 1.0 / filterscale
-    for i in range(out_size):
-        center = (i + 0.5) * scale
-        xmin = max(0, int(center - support + 0.5))
-        xmax = min(in_size, int(center + support + 0.5)) - xmin
-        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) * ss)) for x in range(xmax)]
-        ww = 0.0
-        for v in w:                             # (Pillow adds the weights in order, in double; sum() may compensate)
-            ww += v
-        if ww != 0.0:
-            w = [v / ww for v in w]
-        bounds[i] = (xmin, xmax)
-        kk[i, :xmax] = [int(v * (1 << PRECISION_BITS) + (-0.5 if v < 0 else 0.5)) for v in w]
+    bounds, kk = _pil_rows(in_size, out_size, 0, out_size)
     bounds.setflags(write=False)
     kk.setflags(write=False)
     return bounds, kk
@@ -565,11 +571,58 @@ def image_tables(h: int, w: int, resize: int = 256, crop: int = INPUT_SIZE) -> n
     parts = []
     for size, new, first in ((w, nw, left), (h, nh, top)):
         if new != size:
-            bounds, kk = pil_resample_tables(size, new)
-            parts += [bounds[first:first + crop].reshape(-1), kk[first:first + crop].reshape(-1)]
+            bounds, kk = _pil_rows(size, new, first, crop)         # (the window's rows only: a long side can run to 65535 x resize)
+            parts += [bounds.reshape(-1), kk.reshape(-1)]
     block = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
     block.setflags(write=False)
     return block
+
+
+IMAGE_WINDOW_FORMATS = ('rgb', 'nv12')      # what tsm_preprocess_windows takes in image mode: Pillow's path is 8-bit
+
+
+def image_window_descriptors(shapes, offsets, table_offsets, resize: int = 256, crop: int = INPUT_SIZE,
+                             frame_format: str = 'rgb') -> np.ndarray:
+    """The descriptor table ``tsm_preprocess_windows`` takes in image mode (``_lib.WINDOWS_IMAGE``; include/tsm_hip.h), built
+    and VALIDATED on the host: int32 [n, 8], row c = ``(off_lo, off_hi, h, w, tab_lo, tab_hi, 0, 0)``.  ``shapes`` / ``offsets``
+    as ``window_descriptors`` takes them, with its refusals (a side outside 1 .. 65535, an odd NV12 side, an offset that is
+    negative or no multiple of 16, a crop larger than the resized frame); ``table_offsets``: per window the byte offset in the
+    arena of ``image_tables(h, w, resize, crop)``, under the same rule as an offset.  Windows of one geometry may name one
+    block; a geometry whose block is empty (neither axis changes) may name anything valid, 0 for instance."""
+    if frame_format not in IMAGE_WINDOW_FORMATS:
+        raise ValueError(f'frame_format must be one of {IMAGE_WINDOW_FORMATS} in image mode, got {frame_format!r}')
+    table_offsets = list(table_offsets)
+    desc = window_descriptors(shapes, offsets, None, resize=resize, crop=crop, frame_format=frame_format)
+    if len(table_offsets) != desc.shape[0]:
+        raise ValueError('shapes, offsets and table_offsets must have one entry per window')
+    for c, tab in enumerate(table_offsets):
+        if not isinstance(tab, (int, np.integer)) or tab < 0 or tab % 16 != 0 or tab >= 1 << 63:
+            raise ValueError(f'window {c}: table offset must be a non-negative multiple of 16 bytes, got {tab!r}')
+        tab = int(tab)
+        desc[c, 4:6] = ((tab & 0xFFFFFFFF) - ((tab & 0x80000000) << 1), tab >> 32)
+    return desc
+
+
+def image_window_arena(shapes, n_segment: int = 1, resize: int = 256, crop: int = INPUT_SIZE, frame_format: str = 'rgb'):
+    """The layout of one step's arena in image mode: the windows' frames in order (window c = ``n_segment`` contiguous frames
+    of ``shapes[c]``), then one table block per DISTINCT geometry (the cached ``image_tables``), each start 16-byte aligned.
+    Returns ``(desc, offsets, tables, nbytes)``: the descriptors (``image_window_descriptors``), the byte offset of every
+    window, ``[(byte offset, int32 block), ...]`` to copy in, and the arena's size, a multiple of 16."""
+    shapes = [tuple(int(d) for d in s[:2]) for s in shapes]
+    offsets, total = [], 0
+    for h, w in shapes:
+        offsets.append(total)
+        total += (n_segment * frame_bytes(h, w, frame_format) + 15) // 16 * 16
+    where, tables = {}, []
+    for h, w in shapes:
+        if (h, w) not in where:
+            block = image_tables(h, w, resize, crop)
+            where[(h, w)] = total
+            if block.size:
+                tables.append((total, block))
+                total += (block.nbytes + 15) // 16 * 16
+    desc = image_window_descriptors(shapes, offsets, [where[s] for s in shapes], resize, crop, frame_format)
+    return desc, offsets, tables, max(total, 16)
 
 
 class ImageTransform:

@@ -9,15 +9,16 @@ from workoutdetector_amd.weights import conv_specs, make_state_dict
 EPS = 1e-5
 
 
-def _named_export(sd):
-    """Export that keeps state-dict names (Lightning prefix 'model.'), BatchNormalization nodes unfused."""
+def _named_export(sd, epsilon=None):
+    """Export that keeps state-dict names (Lightning prefix 'model.'), BatchNormalization nodes unfused; ``epsilon``: the
+    float attribute every BatchNormalization node carries (None: absent, which is ONNX's default of 1e-5)."""
     inits = [('model.' + k.replace('fc.', 'new_fc.') if k.startswith('fc.') else 'model.' + k, v) for k, v in sd.items()]
     inits.append(('model.base_model.bn1.num_batches_tracked', np.array([7], dtype=np.int64)))
     nodes = []
     for i, (wkey, bnp, *_r) in enumerate(conv_specs()):
         nodes.append(('Conv', [f'x{i}', 'model.' + wkey], [f'c{i}'], f'Conv_{i}'))
         nodes.append(('BatchNormalization', [f'c{i}'] + ['model.' + bnp + s for s in ('.weight', '.bias', '.running_mean', '.running_var')],
-                      [f'b{i}'], f'BN_{i}'))
+                      [f'b{i}'], f'BN_{i}') + (() if epsilon is None else ({'epsilon': epsilon},)))
     nodes.append(('Gemm', ['feat', 'model.new_fc.weight', 'model.new_fc.bias'], ['out'], 'Gemm_0'))
     return nodes, inits
 
@@ -80,6 +81,38 @@ def test_named_initialisers_round_trip(tmp_path, sd, raw):
     assert set(got) == set(sd)
     for k in sd:
         assert np.array_equal(got[k], sd[k]), k
+
+
+@pytest.mark.parametrize('epsilon', [None, 1e-5])
+def test_batchnorm_epsilon_of_the_engine_loads(tmp_path, sd, epsilon):
+    """An absent ``epsilon`` (ONNX's default) and an explicit 1e-5 are the engine's constant: the export loads unchanged."""
+    nodes, inits = _named_export(sd, epsilon)
+    path = str(tmp_path / 'eps.onnx')
+    write_model(path, nodes, inits)
+    bn = [n for n in parse_onnx(path)[1] if n['op_type'] == 'BatchNormalization']
+    assert len(bn) == 53 and all(n['attrs'] == ({} if epsilon is None else {'epsilon': np.float32(1e-5)}) for n in bn)
+    got = load_onnx_state_dict(path, 12)
+    assert set(got) == set(sd) and all(np.array_equal(got[k], sd[k]) for k in sd)
+
+
+def test_another_batchnorm_epsilon_is_refused(tmp_path, sd, monkeypatch):
+    """epsilon = 1e-3 (another framework's default) cannot be folded by the engine: ValueError naming the node and the value,
+    raised before the backbone is recognised or a tensor is mapped; one such node among 53 is enough."""
+    from workoutdetector_amd import onnx_import
+    nodes, inits = _named_export(sd, 1e-3)
+    path = str(tmp_path / 'eps3.onnx')
+    write_model(path, nodes, inits)
+    built = []
+    monkeypatch.setattr(onnx_import, 'detect_backbone', lambda *a: built.append(a) or 'resnet50')
+    with pytest.raises(ValueError, match=r'BatchNormalization "BN_0" has epsilon = 0\.001'):
+        load_onnx_state_dict(path, 12)
+    assert not built
+    plain, _ = _named_export(sd)
+    plain[2 * 30 + 1] = plain[2 * 30 + 1] + ({'epsilon': 1.1e-5},)
+    write_model(path, plain, inits)
+    with pytest.raises(ValueError, match=r'"BN_30" has epsilon = 1\.1e-05'):
+        load_onnx_state_dict(path, 12)
+    assert not built
 
 
 def _assert_same_folded_weights(got, sd):

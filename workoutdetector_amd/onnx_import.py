@@ -8,7 +8,8 @@ fields needed) and maps the tensors onto the engine's ``TSM.state_dict()`` keys:
 
   * initialisers that still carry state-dict names (``...base_model.layer1.0.conv1.net.weight``,
     BatchNormalization inputs ``...bn1.weight/bias/running_mean/running_var``): any prefix in front of
-    ``base_model.`` / ``fc.`` / ``new_fc.`` is stripped;
+    ``base_model.`` / ``fc.`` / ``new_fc.`` is stripped; a BatchNormalization node whose ``epsilon`` attribute is not the
+    engine's 1e-5 (absent: ONNX's default, 1e-5) is refused -- a state dict cannot carry it and the engine folds with its own;
   * exports where the exporter folded BatchNorm into the convolutions (eval-mode Conv+BN fusion: anonymous
     ``onnx::Conv_###`` weight + bias initialisers): every Conv node is identified by CONNECTIVITY, not by its
     position in the file -- the number of Conv nodes upstream of it in the dataflow graph fixes its place in the
@@ -103,10 +104,23 @@ def _parse_tensor(buf: memoryview) -> Tuple[str, np.ndarray]:
     return name, arr.reshape(dims).copy()
 
 
+def _parse_float_attribute(buf: memoryview) -> Tuple[str, Optional[float]]:
+    """AttributeProto: name=1, f=2 (fixed32), type=20 (1 = FLOAT) -> (name, the float; None for every other type)."""
+    name, value, kind = '', None, None
+    for f, wt, v in _fields(buf):
+        if f == 1 and wt == 2:
+            name = bytes(v).decode()
+        elif f == 2 and wt == 5:
+            value = struct.unpack('<f', v)[0]
+        elif f == 20 and wt == 0:
+            kind = v
+    return name, (value if kind in (None, 1) else None)      # (type is optional before IR version 3)
+
+
 def _parse_node(buf: memoryview) -> dict:
-    """NodeProto: input=1, output=2, name=3, op_type=4 (attributes are not needed)."""
-    node = dict(input=[], output=[], name='', op_type='')
-    for f, _wt, v in _fields(buf):
+    """NodeProto: input=1, output=2, name=3, op_type=4, attribute=5 (the float ones only: BatchNormalization's epsilon)."""
+    node = dict(input=[], output=[], name='', op_type='', attrs={})
+    for f, wt, v in _fields(buf):
         if f == 1:
             node['input'].append(bytes(v).decode())
         elif f == 2:
@@ -115,7 +129,23 @@ def _parse_node(buf: memoryview) -> dict:
             node['name'] = bytes(v).decode()
         elif f == 4:
             node['op_type'] = bytes(v).decode()
+        elif f == 5 and wt == 2:
+            name, value = _parse_float_attribute(v)
+            if value is not None:
+                node['attrs'][name] = value
     return node
+
+
+def _check_batchnorm_eps(path: str, nodes: List[dict]) -> None:
+    """The engine folds every BatchNorm with eps = 1e-5 (csrc/tsm_host_util.h: kBnEps) and a state dict has no place for
+    another value: a BatchNormalization node whose ``epsilon`` (absent: ONNX's default, 1e-5) is not float32(1e-5) raises."""
+    for n in nodes:
+        if n['op_type'] != 'BatchNormalization':
+            continue
+        eps = n['attrs'].get('epsilon', BN_EPS)
+        if np.float32(eps) != np.float32(BN_EPS):
+            raise ValueError(f'{path}: BatchNormalization "{n["name"]}" has epsilon = {eps:g}; the engine folds every BatchNorm '
+                             f'with {BN_EPS:g} and cannot represent another value')
 
 
 def parse_onnx(path: str) -> Tuple[Dict[str, np.ndarray], List[dict]]:
@@ -230,6 +260,7 @@ def load_onnx_state_dict(path: str, num_class: int, base_model: Optional[str] = 
     recognised from the graph (``detect_backbone``); a ``base_model`` that disagrees with it raises.  The shift placement
     comes from the caller: it names the keys (``conv_specs``); the graph's convs are the same under both placements."""
     inits, nodes = parse_onnx(path)
+    _check_batchnorm_eps(path, nodes)
     found = detect_backbone(inits, nodes)
     if base_model is not None and base_model != found:
         raise ValueError(f'{path}: the graph is a {found}, not a {base_model}')

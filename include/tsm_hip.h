@@ -227,7 +227,14 @@ typedef struct tsm_config {
   int32_t num_segments; /* T, 8 (16 for the stress config)                           */
   int32_t height;       /* 224                                                       */
   int32_t width;        /* 224                                                       */
-  int32_t shift_div;    /* 8: fold = C / shift_div                                   */
+  int32_t shift_div;    /* 8: fold = C / shift_div.  TSM_DTYPE_F32: 1, 2, 4, 8 or 16; the
+                           bf16 formats: 1, 2, 4 or 8 (whole 8-channel groups); anything
+                           else TSM_ERR_UNSUPPORTED.  Channels [0, fold) of a shifted
+                           tensor read frame t + 1, [fold, 2 fold) frame t - 1, the rest
+                           frame t.  2: no channel reads its own frame.  1: fold = C, every
+                           channel reads t + 1 and the t - 1 group is empty (the
+                           reference's slicing); blockres placement only, see
+                           tsm_set_shift_place                                          */
   int32_t is_shift;     /* 1: temporal shift in front of every Bottleneck.conv1      */
   int32_t max_clips;    /* workspace capacity in clips per tsm_forward call          */
   int32_t device_id;    /* HIP device ordinal                                        */
@@ -284,7 +291,9 @@ int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group);
  * 0 = 'blockres' (default: the shift wraps conv1 of every block, the identity sees the unshifted input), 1 = 'block' (it
  * wraps every block of layer1-4 whole: conv1, the identity and the downsample all read the shifted input).  is_shift = 0
  * ignores it, as the reference does.  Same contract as tsm_set_backbone: legal between tsm_create and the first
- * tsm_set_tensor, later TSM_ERR_INVALID_ARG; any other value TSM_ERR_UNSUPPORTED.  State-dict keys of a block engine:
+ * tsm_set_tensor, later TSM_ERR_INVALID_ARG; any other value TSM_ERR_UNSUPPORTED.  place = 1 on an engine created with
+ * is_shift = 1 and shift_div = 1 is TSM_ERR_UNSUPPORTED with a message: the shifted identity and downsample launches need both
+ * channel groups inside the tensor (2 * fold <= channels), so such an engine could not run a forward.  State-dict keys of a block engine:
  * "base_model.layerL.B.net.<name>" (or the un-wrapped "base_model.layerL.B.<name>"); a blockres "conv1.net" key is unknown. */
 int tsm_set_shift_place(tsm_engine *e, int32_t place);
 

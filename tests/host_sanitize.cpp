@@ -801,6 +801,93 @@ static void check_conv_routes() {
   EXPECT(conv_route(p, 1, 256).family == kFamInvalid);
 }
 
+// The fold rules at the folds of shift_div 1, 2, 4 (and 8) for ResNet-50's channel counts: which families take the fold, which
+// fall back, and the two shift_div rules of the engine (shift_div_refusal, shift_place_refusal).
+static void check_shift_div_rules() {
+  using namespace tsm;
+  // tsm_create's accepted sets, with the texts naming them
+  for (int div : {1, 2, 4, 8, 16}) EXPECT(shift_div_refusal(div, kPrecF32) == nullptr);
+  for (int div : {1, 2, 4, 8}) EXPECT(shift_div_refusal(div, kPrecBf16x3) == nullptr && shift_div_refusal(div, kPrecBf16) == nullptr);
+  for (int div : {0, -8, 3, 7, 32, 64, INT_MAX, INT_MIN})
+    for (int prec : {(int)kPrecF32, (int)kPrecBf16x3, (int)kPrecBf16}) {
+      const char *why = shift_div_refusal(div, prec);
+      EXPECT(why && std::strstr(why, "1, 2, 4, 8 or 16") && std::strstr(why, "1, 2, 4 or 8"));
+    }
+  for (int prec : {(int)kPrecBf16x3, (int)kPrecBf16}) {
+    const char *why = shift_div_refusal(16, prec);
+    EXPECT(why && std::strstr(why, "1, 2, 4 or 8") && !std::strstr(why, "or 16"));
+  }
+  // block placement at shift_div 1: refused up front (its launches would be refused one by one: 2 * fold > channels)
+  for (int div : {2, 4, 8, 16}) EXPECT(shift_place_refusal(1, 1, div) == nullptr && shift_place_refusal(0, 1, div) == nullptr);
+  EXPECT(shift_place_refusal(0, 1, 1) == nullptr && shift_place_refusal(1, 0, 1) == nullptr);
+  EXPECT(shift_place_refusal(1, 1, 1) != nullptr && std::strstr(shift_place_refusal(1, 1, 1), "shift_div >= 2"));
+  EXPECT(shift_place_refusal(2, 1, 8) != nullptr && shift_place_refusal(-1, 0, 8) != nullptr);
+  {  // ... and the launch rule it anticipates
+    ConvParams p = layer_params(kPrecF32, 8, 56, 64, 256, 1, 1, 0, true);
+    p.T = 8; p.fold = 256;
+    EXPECT(conv_args_refused(p, 1));
+    p.fold = 128;
+    EXPECT(!conv_args_refused(p, 1));
+  }
+  // the whole-block and the front kernel: fold == cin / 8 (fold == 32) exactly
+  for (int div : {1, 2, 4, 8}) {
+    EXPECT(bneck_ws_valid(256, 8, 56, 56, 8, 256 / div) == (div == 8) && bneck_ws_valid(64, 8, 56, 56, 8, 64 / div) == (div == 8));
+    EXPECT(front_s2_valid(8, 56, 56, 8, 256 / div) == (div == 8));
+  }
+  EXPECT(!bneck_ws_valid(256, 8, 56, 56, 8, 256 / 8 + 8) && !bneck_ws_valid(64, 8, 56, 56, 8, 64 / 8 + 8) && !front_s2_valid(8, 56, 56, 8, 256 / 8 + 8));
+  EXPECT(bneck_ws_valid(256, 8, 56, 56, 0, 0) && front_s2_valid(8, 56, 56, 0, 0));            // (unshifted: no fold to meet)
+  // conv31: whole 64-channel chunks and 2 * fold <= C -- div 2, 4, 8 of 512 and 1024 channels, not div 1
+  const int c31[][3] = {{128, 512, 128}, {128, 512, 256}, {256, 1024, 256}};
+  for (const auto &s : c31)
+    for (int div : {1, 2, 4, 8}) {
+      Conv31Params q{};
+      q.n_clips = 2; q.T = 4; q.HW = 96; q.K3 = s[0]; q.C = s[1]; q.N1 = s[2]; q.fold = s[1] / div;
+      EXPECT(conv31_valid(q) == (div != 1));
+      q.fold = s[1] / 8 + 8;                                                                  // no whole chunk
+      EXPECT(!conv31_valid(q));
+    }
+  // the weight-stationary 1x1 kernels and the 256 tiles at ResNet-50's conv1 shapes
+  struct Shape { int hw, cin, cout; };
+  const Shape ws1[] = {{56, 64, 64}, {56, 256, 64}}, wsn[] = {{56, 256, 128}, {28, 512, 128}, {28, 512, 256}}, big[] = {{14, 1024, 256}, {14, 1024, 512}, {7, 2048, 512}};
+  for (int div : {1, 2, 4, 8}) {
+    for (const Shape &s : ws1) {
+      ConvParams p = layer_params(kPrecBf16, 8, s.hw, s.cin, s.cout, 1, 1, 8);
+      p.fold = s.cin / div; p.tile = kTileWs;
+      EXPECT(conv1x1_ws_valid(p) == (div != 1) && conv_tile_valid(p, kTileWs, 256) == (div != 1));
+      EXPECT(conv_route(p, 1, 256).family == (div != 1 ? kFamWs1x1 : kFamInvalid));
+      p.tile = kTileAuto;                                                                     // the fallback: conv_igemm takes any fold up to C
+      EXPECT(conv_route(p, 1, 256).family == kFamIgemm && conv_route(p, 1, 256).shift);
+      p.fold = s.cin / 8 + 4;                                                                 // no whole 8-channel group
+      EXPECT(!conv1x1_ws_valid(p));
+    }
+    for (const Shape &s : wsn) {
+      ConvParams p = layer_params(kPrecBf16, 8, s.hw, s.cin, s.cout, 1, 1, 8);
+      p.fold = s.cin / div; p.tile = kTileWs;
+      EXPECT(conv1x1_wsn_valid(p, 256) == (div != 1) && !conv1x1_ws_valid(p));
+      EXPECT(conv_route(p, 1, 256).family == (div != 1 ? kFamWsn : kFamInvalid));
+      p.tile = kTileAuto;
+      EXPECT(conv_route(p, 1, 256).family == kFamIgemm);
+    }
+    for (const Shape &s : big) {                                                              // lane masks: any fold
+      ConvParams p = layer_params(kPrecBf16, 8, s.hw, s.cin, s.cout, 1, 1, 8);
+      p.fold = s.cin / div;
+      EXPECT(conv_bf16_256_valid(p, 1) && conv_bf16_256p_valid(p, 1));
+      p.tile = kTile256x256;
+      EXPECT(conv_route(p, 1, 256).family == kFamBf16_256 && conv_route(p, 1, 256).shift);
+      p.tile = kTile256x256p;
+      EXPECT(conv_route(p, 1, 256).family == kFamBf16_256p);
+    }
+    // block placement's arms on the persistent tile: the shifted identity (fold of Cout) and second source (fold of C2)
+    ConvParams p = layer_params(kPrecBf16, 8, 28, 128, 512, 1, 1, 0, true);
+    p.T = 8; p.fold = 512 / div; p.tile = kTile256x256p;
+    EXPECT(conv_bf16_256p_valid(p, 1) == (div != 1) && conv_route(p, 1, 256).family == (div != 1 ? kFamBf16_256p : kFamInvalid));
+    p = layer_params(kPrecBf16, 8, 28, 128, 512, 1, 1);
+    add_second_source(&p, 256, 56, 2);
+    p.T = 8; p.fold = 256 / div; p.tile = kTile256x256p;
+    EXPECT(conv_bf16_256p_valid(p, 1) == (div != 1) && conv_route(p, 1, 256).family == (div != 1 ? kFamBf16_256p : kFamInvalid));
+  }
+}
+
 // The argument rules that moved out of launch_conv: every row edits an accepted launch into one refusal.  A row shows that the
 // edited launch is refused on every tile, not WHICH rule refused it: each edit leaves the other rules' fields as the accepted base
 // had them, so that the rule its comment names is the first that can object.
@@ -975,6 +1062,7 @@ int main(int argc, char **argv) {
   check_conv_geometry();
   check_conv_routes();
   check_conv_arg_refusals();
+  check_shift_div_rules();
   const int rounds = argc > 1 ? std::atoi(argv[1]) : 20000;
   fuzz_tune_lines(1234, rounds);
   fuzz_conv_op_check(4321, 10 * rounds);

@@ -140,6 +140,35 @@ def test_create_rejects_bad_config_before_touching_the_gpu(lib):
     assert lib.tsm_forward(None, None, 0, 0, 1, None, None) == -1
 
 
+def test_create_names_the_shift_div_sets(lib):
+    """shift_div per dtype: 0, -8, 3, 32 and 64 refused for every dtype and 16 for the two bf16 formats (TSM_ERR_UNSUPPORTED, the
+    text names the accepted sets); 1, 2, 4, 8 (and 16 in fp32) pass the argument rules -- the call then succeeds, or on a machine
+    without a GPU ends at the device query (TSM_ERR_HIP), which comes after every argument rule."""
+    from workoutdetector_amd import _lib
+    h = ctypes.c_void_p()
+
+    def create(div, dtype):
+        cfg = _lib.TsmConfig(40, 12, 8, 64, 64, div, 1, 1, 0, _lib.DTYPES[dtype])
+        rc = lib.tsm_create(ctypes.byref(cfg), ctypes.byref(h))
+        text = lib.tsm_last_error(None).decode()
+        if rc == 0:
+            lib.tsm_destroy(h)
+        return rc, text
+
+    for dtype in ('f32', 'bf16x3', 'bf16'):
+        for div in (0, -8, 3, 7, 32, 64):
+            rc, text = create(div, dtype)
+            assert rc == -7 and '1, 2, 4, 8 or 16' in text and '1, 2, 4 or 8' in text, (dtype, div, rc, text)
+        rc, text = create(16, dtype)
+        if dtype == 'f32':
+            assert rc in (0, -2), (dtype, rc, text)
+        else:
+            assert rc == -7 and 'bf16 formats' in text and '1, 2, 4 or 8' in text, (dtype, rc, text)
+        for div in (1, 2, 4, 8):
+            rc, text = create(div, dtype)
+            assert rc in (0, -2) and (rc == 0 or 'no HIP device' in text), (dtype, div, rc, text)
+
+
 def test_conv_op_refuses_a_null_or_foreign_argument_block_before_touching_the_gpu(lib):
     """The first rule of tsm_conv_op (csrc/tsm_host_util.h, conv_op_check) as the library applies it: no GPU needed.  Only NULL
     and a wrong struct_size are tried here -- the block never holds a made-up pointer, which a lost refusal would

@@ -14,7 +14,9 @@ geometries and the tail split to the values tests/_walk_cases.py restates, conv_
 family and template arm and one row per refusal of launch_conv's argument rules, and runs 200 000 random and extreme
 tsm_conv_args that conv_op_check accepts, turned into a launch the way tsm_conv_op does, through conv_route for 1, 8 and 256
 CUs: every accepted route covers M and Cout with its tiles, keeps a persistent grid within its tiles and ran a tile that
-conv_tile_valid offers.  CPU only."""
+conv_tile_valid offers; and holds the fold rules (bneck_ws, front_s2, conv31, conv1x1_ws / wsn, the 256 tiles) and the engine's two
+shift_div rules (shift_div_refusal, shift_place_refusal) to the folds of shift_div 1, 2, 4 and 8 at ResNet-50's channel counts.
+CPU only."""
 import os
 import shutil
 import subprocess

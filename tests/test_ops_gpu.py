@@ -33,7 +33,12 @@ def _nchw(x):
                                             # one clip only, and single-frame clips: both neighbours of a frame lie outside
                                             # the clip -- and, for the first and last frame, outside the tensor
                                             (1, 2, 64, 3, 5, 8), (1, 3, 128, 1, 1, 8), (1, 1, 64, 5, 7, 8), (4, 1, 256, 2, 3, 8),
-                                            (1, 1, 32, 1, 1, 8)])
+                                            (1, 1, 32, 1, 1, 8),
+                                            # shift_div 1 (every channel from t + 1, the second group empty), 2 (no channel
+                                            # from its own frame) and 4, at 64 and 256 channels, T = 1, 2 and 3
+                                            (2, 3, 64, 3, 5, 1), (2, 2, 256, 2, 3, 1), (3, 1, 64, 2, 2, 1),
+                                            (2, 3, 256, 3, 5, 2), (2, 2, 64, 2, 3, 2), (3, 1, 256, 2, 2, 2),
+                                            (2, 3, 64, 3, 5, 4), (2, 2, 256, 2, 3, 4), (3, 1, 64, 2, 2, 4)])
 def test_temporal_shift_bit_exact(hip_lib, nb, t, c, h, w, div):
     from workoutdetector_amd.engine import temporal_shift_nhwc
     g = torch.Generator().manual_seed(c + h)

@@ -1993,12 +1993,10 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
     if (rows >= (int64_t)1 << 31)
       return fail(nullptr, TSM_ERR_CAPACITY, "max_clips * num_segments * (H/2) * (W/2) must stay below 2^31");
   }
-  if (cfg->shift_div <= 0 || (64 % cfg->shift_div) != 0 || (64 / cfg->shift_div) % 4 != 0)
-    return fail(nullptr, TSM_ERR_UNSUPPORTED, "shift_div must divide 64 with fold % 4 == 0 (8 or 16... )");
+  if (const char *why = shift_div_refusal(cfg->shift_div, tsm::kPrecF32)) return fail(nullptr, TSM_ERR_UNSUPPORTED, why);
   if (prec_of_dtype(cfg->dtype) < 0)
     return fail(nullptr, TSM_ERR_UNSUPPORTED, "dtype must be TSM_DTYPE_F32, TSM_DTYPE_BF16X3 or TSM_DTYPE_BF16");
-  if (cfg->dtype != TSM_DTYPE_F32 && (64 / cfg->shift_div) % 8 != 0)
-    return fail(nullptr, TSM_ERR_UNSUPPORTED, "the bf16 formats need fold % 8 == 0 (shift_div <= 8)");
+  if (const char *why = shift_div_refusal(cfg->shift_div, prec_of_dtype(cfg->dtype))) return fail(nullptr, TSM_ERR_UNSUPPORTED, why);
   int ndev = 0;
   hipError_t st = hipGetDeviceCount(&ndev);
   if (st != hipSuccess || ndev <= 0)
@@ -2090,7 +2088,7 @@ int tsm_set_bottleneck_width(tsm_engine *e, int32_t width_per_group) {
 int tsm_set_shift_place(tsm_engine *e, int32_t place) {
   if (int rc = check_before_weights(e, "tsm_set_shift_place")) return rc;
   if (int rc = refuse_on_convnext(e, "tsm_set_shift_place")) return rc;
-  if (place != 0 && place != 1) return fail(e, TSM_ERR_UNSUPPORTED, "place must be 0 (blockres) or 1 (block)");
+  if (const char *why = shift_place_refusal(place, e->cfg.is_shift, e->cfg.shift_div)) return fail(e, TSM_ERR_UNSUPPORTED, why);
   e->place = place;
   e->backbone_set = 1;
   build_topology(e);

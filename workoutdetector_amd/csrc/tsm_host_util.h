@@ -209,6 +209,25 @@ inline void to_storage(std::vector<float> *v, int prec) {
 inline int prec_of_dtype(int dtype) {   // tsm_dtype -> precision, -1 for anything else
   return dtype == TSM_DTYPE_F32 ? kPrecF32 : dtype == TSM_DTYPE_BF16X3 ? kPrecBf16x3 : dtype == TSM_DTYPE_BF16 ? kPrecBf16 : -1;
 }
+// Why tsm_create refuses a shift_div for an engine of this precision; nullptr when it takes it.  fold = channels / shift_div must be
+// whole 16-byte groups of the narrowest shifted tensor (64 channels): 4 channels of fp32, 8 of the bf16 formats.  1 is taken:
+// fold = channels, every channel reads frame t + 1 and the t - 1 group is empty (the reference's slicing).
+inline const char *shift_div_refusal(int shift_div, int prec) {
+  if (shift_div <= 0 || 64 % shift_div != 0 || (64 / shift_div) % 4 != 0)
+    return "shift_div must be 1, 2, 4, 8 or 16 for TSM_DTYPE_F32 and 1, 2, 4 or 8 for the bf16 formats (fold = channels / shift_div in whole 4-channel groups)";
+  if (prec != kPrecF32 && (64 / shift_div) % 8 != 0)
+    return "the bf16 formats shift whole 8-channel groups (fold % 8 == 0): shift_div must be 1, 2, 4 or 8";
+  return nullptr;
+}
+// Why an engine of this shift flag and shift_div cannot take this placement; nullptr when it can.  Block placement shifts the
+// identity and the downsample operand, whose launches need both channel groups inside the tensor (conv_args_refused: 2 * fold
+// <= channels): at shift_div 1 every forward would be refused, so the placement is refused up front.
+inline const char *shift_place_refusal(int place, int is_shift, int shift_div) {
+  if (place != 0 && place != 1) return "place must be 0 (blockres) or 1 (block)";
+  if (place == 1 && is_shift && shift_div == 1)
+    return "block placement needs shift_div >= 2: its shifted identity and downsample launches take 2 * fold <= channels (shift_div 1 runs in blockres placement only)";
+  return nullptr;
+}
 inline int packed_layout_of(int prec) {   // the packed device-memory clip layout an engine of that precision consumes in place
   return prec == kPrecF32 ? TSM_LAYOUT_NTHWC4 : prec == kPrecBf16x3 ? TSM_LAYOUT_NTHWC8S : TSM_LAYOUT_NTHWC8B;
 }

@@ -79,7 +79,8 @@ enum ConvTile {
   kTile256x256 = 6,    // conv_bf16_256_kernel: bf16 only, 8 waves, one workgroup per CU, operands by LDS-DMA
   kTileWs = 7,       // conv3x3_ws[128]_kernel: bf16 3x3 s1 p1 with C = Cout = 64 / 128, weights resident in registers, input patch by LDS-DMA
   kTile256x256p = 8, // conv_bf16_256p_kernel: kTile256x256's pipeline run persistently over a workgroup's tiles (K >= 128, Cout <= 2048)
-  kNumTiles = 9
+  kTile64x128 = 9,   // conv_igemm<64, 128, 2, 2, 1, ..>: fp32 unsegmented 1x1 only, a 32x64 wave tile on two accumulators
+  kNumTiles = 10
 };
 
 // Bottleneck.conv2 (3x3, stride 1, pad 1) + bn2 + ReLU + conv3 (1x1) + bn3 + residual + ReLU as ONE launch (fp32 or split-bf16),
@@ -160,15 +161,15 @@ constexpr int kBK = 32;   // K-step of conv_igemm in channels-taps (bf16: 64)
 
 // ---- tiles ------------------------------------------------------------------------------------------------------------------
 inline void conv_tile_dims(int tile, int *bm, int *bn) {
-  *bm = (tile == kTile256x256 || tile == kTile256x256p || tile == kTileWs) ? 256 : tile == kTile32x32 ? 32 : (tile == kTile64x64 ? 64 : 128);
-  *bn = (tile == kTile256x256 || tile == kTile256x256p) ? 256 : tile == kTile32x32 ? 32 : ((tile == kTile128x128 || tile == kTile128x128w8) ? 128 : 64);
+  *bm = (tile == kTile256x256 || tile == kTile256x256p || tile == kTileWs) ? 256 : tile == kTile32x32 ? 32 : ((tile == kTile64x64 || tile == kTile64x128) ? 64 : 128);
+  *bn = (tile == kTile256x256 || tile == kTile256x256p) ? 256 : tile == kTile32x32 ? 32 : ((tile == kTile128x128 || tile == kTile128x128w8 || tile == kTile64x128) ? 128 : 64);
 }
 
-// "128x128" | "128x64" | "64x64" | "32x32" | "128x128w8" | "256x256" | "256x256p" | "ws" -> ConvTile (kTileAuto for anything else).
+// "128x128" | "128x64" | "64x64" | "32x32" | "128x128w8" | "256x256" | "256x256p" | "ws" | "64x128" -> ConvTile (kTileAuto for anything else).
 inline int conv_tile_from_name(const char *name) {
   if (!name) return kTileAuto;
   static const struct { const char *n; int t; } names[] = {{"128x128", kTile128x128}, {"128x64", kTile128x64},
-      {"64x64", kTile64x64}, {"32x32", kTile32x32}, {"128x128w8", kTile128x128w8}, {"256x256", kTile256x256}, {"ws", kTileWs}, {"256x256p", kTile256x256p}};
+      {"64x64", kTile64x64}, {"32x32", kTile32x32}, {"128x128w8", kTile128x128w8}, {"256x256", kTile256x256}, {"ws", kTileWs}, {"256x256p", kTile256x256p}, {"64x128", kTile64x128}};
   for (const auto &e : names)
     if (strcmp(name, e.n) == 0) return e.t;
   return kTileAuto;
@@ -446,6 +447,10 @@ inline bool conv_tile_valid(const ConvParams &p, int tile, int n_cu) {
     case kTile256x256p:   // (256p: at least two K-tiles, the bias of all channels in LDS)
       return p.prec == kPrecBf16 && p.Cout % 256 == 0 && p.C % 64 == 0 && !(p.res && p.x2) && (p.pad != 1 || (!p.res && p.T == 0)) &&
              (!p.x2 || (p.K1 % 64 == 0 && p.C2 % 64 == 0)) && (tile == kTile256x256 || (p.Cout <= 2048 && p.Kp >= 128));
+    // 64x128: fp32, a 1x1 (no padding), unsegmented, no block placement (a shifted identity / second source / strided 1x1)
+    case kTile64x128:
+      return p.prec == kPrecF32 && p.pad == 0 && p.kseg_len == 0 && p.Cout % 128 == 0 &&
+             !(p.T > 0 && (p.res || p.x2 || p.stride != 1));
     case kTileWs: {   // (pad singles out 3x3 / 1x1)
       int tr, tc;
       return conv3x3_ws_valid(p, &tr, &tc) || conv3x3_ws128s2_valid(p, &tr, &tc) || conv3x3_ws128_valid(p, &tr, &tc, nullptr) ||
@@ -587,6 +592,7 @@ inline ConvRoute conv_route(const ConvParams &p, int ks, int n_cu) {
     return r;
   }
   // conv_igemm
+  if (p.tile == kTile64x128 && ks != 1) return refused;   // (conv_tile_valid has no ks: a 3x3 or the stem without padding)
   if (p.kseg_len > 0 && r.bm != 32) r.bm = r.bn = 64;   // segmented accumulation exists on 64x64 / 32x32 tiles only
   if (r.bm == 32 && p.prec != kPrecF32) return refused;
   r.wgm = r.bm == 32 ? 1 : r.bm == 128 && r.bn == 128 && p.tile == kTile128x128w8 ? 4 : 2;

@@ -258,6 +258,7 @@ struct tsm_engine {
   int fuse31 = -1;       // TSM_FUSE_C3C1: the same for conv3 of block b + shift + conv1 of block b + 1 as one launch (bf16, layer2)
   int fuse_front = -1;   // TSM_FUSE_FRONT: the same for shift + conv1 + the stride-2 conv2 of layer2.0 as one launch (bf16)
   bool pos_major = true; // TSM_POS_MAJOR=0: the tuner does not offer the position-major 3x3 codes (kCodePosMajor); for the A/B
+  bool tile_64x128 = true; // TSM_TILE_64X128=0: the tuner does not offer the 64x128 tile (kTile64x128); for the A/B
   int walk = -1;         // TSM_WALK: 0 / 1 every tile-walking launch walks forward / in reverse; unset: alternate (Forward::next_dir)
   int n_cu = 256;
   int timing_left = 0;
@@ -983,7 +984,7 @@ int Forward::conv(int idx, tsm::ConvParams p, int ks, bool is3x3) {
     }
   } else {
     for (int t = 1; t < tsm::kNumTiles; ++t)
-      if (tsm::conv_tile_valid(p, t, e->n_cu)) cands.push_back(t);
+      if (tsm::conv_tile_valid(p, t, e->n_cu) && (t != tsm::kTile64x128 || e->tile_64x128)) cands.push_back(t);
   }
   float best_ms = 0.f;
   int best = 0;
@@ -2013,6 +2014,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   env_read("TSM_CONV_TILE", &e->force_tile, tsm::conv_tile_from_name);
   env_read("TSM_CONV_CODE", &e->force_code, atoi);
   env_read("TSM_POS_MAJOR", &e->pos_major, on);
+  env_read("TSM_TILE_64X128", &e->tile_64x128, on);
   env_read("TSM_FUSE_CONV23", &e->fuse23, on);
   env_read("TSM_FUSE_BLOCK", &e->fuse_block, on);
   env_read("TSM_FUSE_C3C1", &e->fuse31, on);

@@ -3,7 +3,7 @@
 //   conv_igemm       implicit-GEMM convolution (1x1 / 3x3 / 7x7, stride 1|2), NHWC activations, LDS-staged A
 //                    (im2col rows built on the fly, temporal shift fused into the 1x1 and 3x3 loaders) and B (packed
 //                    weights), epilogue = folded-BN bias + residual + ReLU.  Template axes: tile shape and wave
-//                    layout (128x128 on 4 or 8 waves, 128x64, 64x64, 32x32 on one wave), KS, SHIFT (fused
+//                    layout (128x128 on 4 or 8 waves, 128x64, 64x64, 64x128 for fp32 1x1 convs, 32x32 on one wave), KS, SHIFT (fused
 //                    temporal shift), RES (residual prefetched under the K loop), PREC (exact-fp32 MFMA /
 //                    split-bf16 x3 / bf16), DUAL (second A source concatenated along K = conv3 + downsample in
 //                    one GEMM), SEG (fp32 long-K layers: K summed in fixed segments, which makes whole-K and split-K
@@ -66,7 +66,8 @@ namespace tsm {
 template <int BM, int BN, int WGM, int WGN, int KS, bool SHIFT, bool RES, int PREC, bool DUAL = false, bool SEG = false>
 // (second launch-bounds argument = minimum waves per SIMD: the SEG 64x64 kernel needs 16 registers more than the
 // plain one and would drop from 5 to 4 workgroups per CU; asking for 5 costs 1-2 spills outside the K loop)
-__global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? ((PREC & kPrecBlockShift) ? 4 : 5) : 1)
+// (the 64x128 tile asks for 4: 128 registers, 4 workgroups of 27 KB per CU)
+__global__ void __launch_bounds__(64 * WGM * WGN, (SEG && BM == 64) ? ((PREC & kPrecBlockShift) ? 4 : 5) : (BM == 64 && BN == 128) ? 4 : 1)
 conv_igemm(const ConvParams p) {
   constexpr bool BSHIFT = (PREC & kPrecBlockShift) != 0;
   constexpr bool POSM = (PREC & kPrecPosMajor) != 0;
@@ -96,8 +97,14 @@ conv_igemm(const ConvParams p) {
   // buffer, and the 16 MFMAs of the step then run from registers while the next tile is written into LDS.
   // Half the LDS per workgroup -> more workgroups per CU, and no LDS wait inside the MFMA sequence.
   constexpr bool RK = PMODE == kPrecF32 && ((BM == 64 && BN == 64) || (BM == 32 && BN == 32));
-  constexpr int NBUF = RK ? 1 : 2;
-  constexpr int CLD = BN + 4;  // epilogue staging row stride (floats)
+  // RK2 (fp32 64x128 tiles, unsegmented 1x1 only): the same step with a 32x64 wave tile -- one A and two B fragment sets per
+  // k-group, 32 MFMAs on two independent accumulators, six loader items.  192 operand rows staged per 128 wave-MFMAs (64x64:
+  // 128 per 64) and 12 fragment vectors read per 32 MFMAs (8 per 16): a quarter fewer operand bytes per MFMA on both paths.
+  constexpr bool RK2 = PMODE == kPrecF32 && BM == 64 && BN == 128;
+  static_assert(!RK2 || (WGM == 2 && WGN == 2 && KS == 1 && !SEG && !BSHIFT && !POSM),
+                "64x128 tiles: unsegmented fp32 1x1 convs on 2x2 waves, no block placement (conv_tile_valid)");
+  constexpr int NBUF = (RK || RK2) ? 1 : 2;
+  constexpr int CLD = RK2 ? 68 : BN + 4;  // epilogue staging row stride (floats; 64x128 stages one 64-column half at a time)
   static_assert(TM >= 1 && TN >= 1, "wave tile must hold at least one 32x32 MFMA tile");
   constexpr int SMEM_FLOATS = NBUF * (BM + BN) * kLds > BM * CLD ? NBUF * (BM + BN) * kLds : BM * CLD;
 
@@ -453,7 +460,7 @@ conv_igemm(const ConvParams p) {
   constexpr int RPP = NT / TPR;        // rows per pass
   constexpr int EPASS = BM / RPP;
   const int ecol = (tid % TPR) * EW, erow = tid / TPR;
-  f32x4 rres[(RESID && !X3 && !BF) ? EPASS : 1];
+  f32x4 rres[(RESID && !X3 && !BF && !RK2) ? EPASS : 1];   // (64x128: fetched under the last K-step, into the loader's registers)
   u32x4 rres_h[(RESID && (X3 || BF)) ? EPASS : 1], rres_l[(RESID && X3) ? EPASS : 1];
   if (RESID && (X3 || BF) && !BSHIFT) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * EB;
@@ -465,7 +472,7 @@ conv_igemm(const ConvParams p) {
       if (X3) rres_l[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrcR, (int)(o + 16), 0, 0);
     }
   }
-  if (RESID && !X3 && !BF && !BSHIFT) {
+  if (RESID && !X3 && !BF && !BSHIFT && !RK2) {
     const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * 4;
     const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(p.res + (size_t)m0 * p.Cout, r_bytes);
 #pragma unroll
@@ -584,6 +591,99 @@ conv_igemm(const ConvParams p) {
       frag_load_bf(cur ^ 1, 1);
       __builtin_amdgcn_sched_barrier(0);
     }
+  } else if constexpr (RK2) {
+    // One step = fragments of all four k-groups (A: 4 vectors, B: 2 column tiles x 4), the barrier that frees the buffer, then
+    // 32 MFMAs from registers: k-group ascending, s ascending, acc[0][0] then acc[0][1] -- each accumulator sees the 64x64
+    // arm's sequence.  The 2 * NITEMS loader items (ds_writes of tile kt+1, then the loads of kt+2) go between the first 24.
+    f32x4 fa[4], fb[2][4];
+    auto frags = [&]() {
+      const float *As = smem + (wm * WTM + l31) * kLds + half * 4;
+      const float *Bs = smem + BM * kLds + (wn * WTN + l31) * kLds + half * 4;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        fa[kk] = *reinterpret_cast<const f32x4 *>(As + kk * 8);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) fb[j][kk] = *reinterpret_cast<const f32x4 *>(Bs + j * 32 * kLds + kk * 8);
+      }
+    };
+    auto mfma_step = [&](auto &&inject) {
+      int cnt = 0;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kk][s4], fb[j][kk][s4], acc[0][j], 0, 0, 0);
+            ++cnt;
+            const int done = cnt < 24 ? (cnt * 2 * NITEMS) / 24 : 2 * NITEMS;
+            const int before = cnt - 1 < 24 ? ((cnt - 1) * 2 * NITEMS) / 24 : 2 * NITEMS;
+#pragma unroll
+            for (int it = before; it < done; ++it) {
+              inject(it);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+    };
+    for (int kt = kt0; kt < nk - 1; ++kt) {
+      const KStep k2 = kstep(kt + 2, nk);
+      frags();
+      __syncthreads();  // every wave holds its fragments: the buffer may be overwritten
+      mfma_step([&](int it) {
+        if (it < NITEMS) lstore_item(0, it);
+        else gload_item(k2, kt + 2, it - NITEMS);
+      });
+      __syncthreads();  // tile kt+1 is complete in LDS
+    }
+    // The last K-step has nothing to stage, so the loader's registers are free: the residual of the first 64-column half (four
+    // vectors in the epilogue's mapping) is fetched here, under the step's MFMAs, and the second half's once the fragment
+    // registers are free, under the first half's staging and stores.  All eight before the loop, as the other tiles fetch
+    // theirs, do not fit the 128-register budget.
+    frags();
+    __syncthreads();  // the operand buffer is free: the epilogue stages into it
+    // Epilogue mapping: 16 threads per row of a 64-column half, 16 rows per pass, 4 passes.  Half h holds column tile h of both
+    // wave columns: staging column c is output column n0 + 64 * (c / 32) + 32 * h + c % 32, so all four waves stage and every
+    // thread's 16 bytes stay inside one 128-byte run.
+    const int hrow = tid >> 4, hcol = (tid & 15) * 4;
+    const int ocol = n0 + (hcol >> 5) * 64 + (hcol & 31);
+    f32x4 rr2[RES ? 2 : 1][RES ? 4 : 1];
+    auto res_half = [&](int h) {
+      if constexpr (RES) {
+        const size_t r_bytes = ((size_t)p.M - m0) * p.Cout * 4;
+        const __amdgpu_buffer_rsrc_t rsrcR = buffer_window(p.res + (size_t)m0 * p.Cout, r_bytes);   // (rows past M read as zeros)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rr2[h][k] = buf_load4(rsrcR, (unsigned)(((hrow + 16 * k) * p.Cout + ocol + 32 * h) * 4), 0);
+      }
+    };
+    res_half(0);
+    mfma_step([](int) {});
+    __builtin_amdgcn_sched_barrier(0);
+    res_half(1);
+    const size_t y_bytes = ((size_t)p.M - m0) * p.Cout * 4;   // rows past M are dropped by the range check
+    const __amdgpu_buffer_rsrc_t rsrcY = buffer_window(reinterpret_cast<char *>(p.y) + (size_t)m0 * p.Cout * 4, y_bytes);
+    const float floor_ = p.relu ? 0.f : -INFINITY;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (h) __syncthreads();  // half 0 has been read out
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        smem[(wm * WTM + (e & 3) + 8 * (e >> 2) + 4 * half) * CLD + wn * 32 + l31] = acc[0][h][e];
+      __syncthreads();
+      const f32x4 bias = *reinterpret_cast<const f32x4 *>(p.bias + ocol + 32 * h);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int rr = hrow + 16 * k;
+        f32x4 v = *reinterpret_cast<const f32x4 *>(smem + rr * CLD + hcol);
+        v += bias;
+        if constexpr (RES) v += rr2[h][k];
+        v[0] = fmaxf(v[0], floor_);
+        v[1] = fmaxf(v[1], floor_);
+        v[2] = fmaxf(v[2], floor_);
+        v[3] = fmaxf(v[3], floor_);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrcY, (int)((rr * p.Cout + ocol + 32 * h) * 4), 0, 0);
+      }
+    }
+    return;
   } else if constexpr (RK) {
     f32x4 ra_[4], rb_[4];  // all four k-groups of this wave's A / B fragments (TM = TN = 1)
     // fp32 stem: K = 49 taps x 4 channels = 196 of the 224 padded, so the last K-step holds real data in its first
@@ -878,6 +978,17 @@ static hipError_t launch_conv_t(const ConvParams &p, const ConvRoute &r, hipStre
   TSM_LAUNCH_IGEMM_AND_RETURN(TSM_ARM_PLAIN);
 }
 
+// The 64x128 tile (kTile64x128; conv_route: fp32, unsegmented 1x1, no block placement): its four arms, one launch line each.
+static hipError_t launch_conv_64x128(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
+  if (r.ks != 1 || r.family != kFamIgemm || r.block_shift || p.prec != kPrecF32) return hipErrorInvalidValue;
+  const dim3 grid(r.grid), block(256);
+  if (r.dual) TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 128, 2, 2, 1, false, false, kPrecF32, true>), grid, block, 0, s, p);
+  else if (r.res) TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 128, 2, 2, 1, false, true, kPrecF32>), grid, block, 0, s, p);
+  else if (r.shift) TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 128, 2, 2, 1, true, false, kPrecF32>), grid, block, 0, s, p);
+  else TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 128, 2, 2, 1, false, false, kPrecF32>), grid, block, 0, s, p);
+  return hipGetLastError();
+}
+
 template <int KS, bool SHIFT, bool RES>
 static hipError_t launch_conv_ks(const ConvParams &p, const ConvRoute &r, hipStream_t s) {
   if (r.bm == 32) return launch_conv_t<32, 32, 1, 1, KS, SHIFT, RES>(p, r, s);
@@ -900,6 +1011,7 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
   if (r.family == kFamBf16_256 || r.family == kFamBf16_256p) return launch_conv_bf16_256(p, r, s);
   if (r.family >= kFamWs3x3) return launch_conv_ws(p, r, s);
   if (p.ksplit == 2 && !p.ypart) return hipErrorInvalidValue;   // (the tail split's segment sums)
+  if (r.bm == 64 && r.bn == 128) return launch_conv_64x128(p, r, s);
   if (ks == 1) return r.res ? launch_conv_ks<1, false, true>(p, r, s) : r.shift ? launch_conv_ks<1, true, false>(p, r, s) : launch_conv_ks<1, false, false>(p, r, s);
   if (ks == 3) return r.res ? launch_conv_ks<3, false, true>(p, r, s) : r.shift ? launch_conv_ks<3, true, false>(p, r, s) : launch_conv_ks<3, false, false>(p, r, s);
   return launch_conv_ks<7, false, false>(p, r, s);

@@ -586,7 +586,7 @@ class TsmEngine:
         return max(1, min(8, self.max_clips, ((1 << 29) - 1) // per_clip))
 
     TILE_NAMES = {0: 'heuristic', 1: '128x128', 2: '128x64', 3: '64x64', 4: '32x32', 5: '128x128w8', 6: '256x256', 7: 'ws',
-                  8: '256x256p'}
+                  8: '256x256p', 9: '64x128'}
 
     @classmethod
     def tile_name(cls, code: int) -> str:

@@ -136,6 +136,35 @@ def test_eval_classification_on_a_stub_counts_the_intent(expected):
     json.dumps({k: v for k, v in res.items() if k != 'logits'})        # the result is JSON as it stands
 
 
+def test_a_torch_module_and_a_plain_callable_take_the_host_path_like_a_session(expected):
+    """The host path calls its model through staging.call_host: a torch module and a plain callable on [B, T, 3, H, W] give
+    what the session gives (they used to fail with AttributeError on get_inputs)."""
+    from workoutdetector_amd.classification import eval_classification
+    from workoutdetector_amd.transform import TestTransform
+
+    class Module(torch.nn.Module):
+        num_class = 12
+
+        def __init__(self):
+            super().__init__()
+            self.stub = StubModel(seed=3)
+
+        def forward(self, x):
+            assert isinstance(x, torch.Tensor) and not torch.is_grad_enabled()
+            return torch.from_numpy(self.stub.run(None, {'input': x.numpy()})[0])
+
+    labels = expected.argmax(axis=1).tolist()
+    kw = dict(batch_clips=2, return_logits=True, transform=TestTransform(RESIZE, CROP, scale_255=True))
+    want = eval_classification(StubModel(seed=3), _samples(labels), frame_reader=Reader(), **kw)
+    module, stub = Module(), StubModel(seed=3)
+    for model, calls in ((module, lambda: module.stub.calls), (lambda x: stub.run(None, {'input': x.numpy()})[0], lambda: stub.calls)):
+        reader = Reader()
+        got = eval_classification(model, _samples(labels), frame_reader=reader, **kw)
+        assert np.array_equal(got.pop('logits'), want['logits']) and got == {k: v for k, v in want.items() if k != 'logits'}
+        assert [d for d, _n in reader.calls] == ['a', 'b'] and calls() == 2 + 2
+    assert want['overall'] == 1.0 and want['logits'].dtype == np.float32
+
+
 def test_eval_classification_without_samples_and_bad_arguments():
     from workoutdetector_amd.classification import eval_classification
     res = eval_classification(StubModel(), [], frame_reader=Reader())

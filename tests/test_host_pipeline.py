@@ -205,6 +205,29 @@ def test_stream_batcher_matches_per_stream_counting():
         sb.push('d', np.zeros((4, 4, 3), np.float32))
 
 
+def test_stream_batcher_and_clip_logits_take_a_plain_callable():
+    """StreamBatcher and video_clip_logits call a model that is no engine through staging.call_host: a callable on
+    [B, 8, 3, 224, 224] gives what the session gives (it used to fail with AttributeError on get_inputs)."""
+    from workoutdetector_amd.streaming import StreamBatcher
+    vid = synthetic_video(4, 50, 30, 40, period=16)
+
+    def play(model):
+        sb = StreamBatcher(model, max_batch=2)
+        events = []
+        for t, f in enumerate(vid):
+            sb.push('s', f)
+            if t % 20 == 19:
+                events += sb.step().get('s', [])
+        return events + sb.step().get('s', []), sb.close('s')
+
+    stub = StubModel(gain=8.0)
+    got = play(lambda x: stub.run(None, {'input': x.numpy()})[0])
+    assert got == play(StubModel(gain=8.0)) and len(got[0]) == 6 and stub.calls == 4
+    tf = build_test_transform(False)
+    logits = ic.video_clip_logits(lambda x: stub.run(None, {'input': x.numpy()})[0], torch.from_numpy(vid), tf, batch_clips=3)
+    assert torch.equal(logits, ic.video_clip_logits(StubModel(gain=8.0), torch.from_numpy(vid), tf, batch_clips=3))
+
+
 def test_clip_batcher_hands_every_row_back_to_its_video():
     """_ClipBatcher (full batches across video boundaries, the dataset loop of shard='global'): random video lengths --
     empty ones, single clips, lengths below / equal to / far above the batch -- and random batch sizes; every video must

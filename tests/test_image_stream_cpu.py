@@ -270,3 +270,52 @@ def test_every_up_front_refusal_comes_before_the_library_loads(monkeypatch):
     model.image_resize, model.image_crop = 16, 17
     with pytest.raises(ValueError):
         ImageStreamBatcher(model).push('s', np.zeros((40, 56, 3), np.uint8))     # a crop larger than the resized frame
+
+
+def test_the_three_batchers_ask_the_same_of_a_pushed_frame_in_the_same_words():
+    """transform.pushed_frame behind StreamBatcher, ImageStreamBatcher and TdnStreamBatcher: one message per format, the luma
+    size, conversion on arrival only when asked; a side of 0 pixels is ImageStreamBatcher's own refusal."""
+    import re
+    from tests._stub import StubModel
+    from workoutdetector_amd.streaming import ImageStreamBatcher, StreamBatcher
+    from workoutdetector_amd.tdn_pipeline import TdnStreamBatcher
+    from workoutdetector_amd.transform import nv12_to_rgb, pushed_frame, rgb_to_nv12, rgb_to_yuv, yuv_to_rgb
+
+    class Tdn:
+        num_class, num_segments, height, width = 3, 8, 16, 16
+
+    rgb_words = re.escape('frame must be uint8 [H,W,3], got ')
+    for make in (lambda: StreamBatcher(StubModel()), lambda: ImageStreamBatcher(_Brightness()), lambda: TdnStreamBatcher(Tdn())):
+        for bad in (np.zeros((30, 40), np.uint8), np.zeros((30, 40, 3), np.float32), np.zeros((30, 40, 4), np.uint8)):
+            with pytest.raises(ValueError, match=rgb_words + re.escape(f'{bad.dtype} {bad.shape}')):
+                make().push('s', bad)
+    nv12_words = re.escape('an NV12 frame must be uint8 [3H/2,W], got ')
+    for make in (lambda: StreamBatcher(StubModel(), frame_format='nv12'), lambda: ImageStreamBatcher(_Brightness(), frame_format='nv12')):
+        for bad in (np.zeros((30, 40, 3), np.uint8), np.zeros((45, 40), np.int16)):
+            with pytest.raises(ValueError, match=nv12_words + re.escape(f'{bad.dtype} {bad.shape}')):
+                make().push('s', bad)
+        with pytest.raises(ValueError, match=re.escape('NV12 frames are [3h/2, w] with h and w even, got 45 x 41')):
+            make().push('s', np.zeros((45, 41), np.uint8))
+    with pytest.raises(ValueError, match=re.escape('a yuyv frame must be its uint8 container [rows, bytes], got uint8 (30, 40, 3)')):
+        StreamBatcher(StubModel(), frame_format='yuyv').push('s', np.zeros((30, 40, 3), np.uint8))
+    with pytest.raises(ValueError, match=re.escape('i420 frames are [3h/2, w] with h and w even, got 45 x 41')):
+        StreamBatcher(StubModel(), frame_format='i420').push('s', np.zeros((45, 41), np.uint8))
+    # a side of 0: ImageStreamBatcher alone refuses it
+    empty = np.zeros((0, 40, 3), np.uint8)
+    with pytest.raises(ValueError, match=rgb_words):
+        ImageStreamBatcher(_Brightness()).push('s', empty)
+    StreamBatcher(StubModel()).push('s', empty)
+    TdnStreamBatcher(Tdn()).push('s', empty)
+    # what is queued: the frame as it is, or -- converted on arrival -- its RGB pixels; the luma size either way
+    rgb = _blinking(1, 1, 30, 40)[0]
+    nv12, p010 = rgb_to_nv12(rgb)[0], rgb_to_yuv(rgb, 'p010')[0]
+    arr, hw = pushed_frame(rgb, 'rgb', None, False)
+    assert arr is rgb and hw == (30, 40)
+    arr, hw = pushed_frame(nv12, 'nv12', 'bt709', False)
+    assert arr is nv12 and hw == (30, 40)
+    arr, hw = pushed_frame(nv12, 'nv12', 'bt709', True)
+    assert np.array_equal(arr, nv12_to_rgb(nv12, 'bt709')[0]) and hw == (30, 40)
+    wide = p010.view('<u2')                                          # a 16-bit P010 frame is taken as its bytes
+    arr, hw = pushed_frame(wide, 'p010', 'bt601', False)
+    assert arr.dtype == np.uint8 and np.array_equal(arr, p010) and hw == (30, 40)
+    assert np.array_equal(pushed_frame(wide, 'p010', 'bt601', True)[0], yuv_to_rgb(p010, 'p010', 'bt601')[0])

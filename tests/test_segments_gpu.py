@@ -420,3 +420,57 @@ def test_an_identity_engine_is_refused_up_front(engine):
     with pytest.raises(ValueError, match='identity'):
         eval_classification(Identity(), _samples([0] * len(SEGMENTS)), frame_reader=lambda d, n: asked.append(d))
     assert asked == []
+
+
+def test_the_reader_is_asked_for_one_probe_frame_then_every_pieces_union_without_it(engine, labels, monkeypatch):
+    """What the engine path asks of the frame reader and of the GPU, to the call: per directory ONE read of its smallest sampled
+    frame, then per staged piece one read of the piece's union without that frame; no read and no launch for an empty list; the
+    same launches in the same order whether or not the logits are asked for; frames of another size than the probe's refused."""
+    from workoutdetector_amd import inference_count as ic
+    from workoutdetector_amd.classification import eval_classification
+    from workoutdetector_amd.engine import launch_trace
+    asked = []
+
+    def reader(frame_dir, numbers):
+        asked.append((frame_dir, list(numbers)))
+        return _reader(frame_dir, numbers)
+
+    rows = {d: [sg.sample(t, 8, s) for dd, s, t in SEGMENTS if dd == d] for d in DIRS}
+    union = {d: sorted(set().union(*rows[d])) for d in DIRS}
+    with launch_trace() as with_logits:
+        res = eval_classification(engine, _samples(labels), frame_reader=reader, return_logits=True)
+    assert asked == [('stu1', union['stu1'][:1]), ('stu1', union['stu1'][1:]), ('stu5', union['stu5'][:1]), ('stu5', union['stu5'][1:])]
+    with launch_trace() as without:
+        plain = eval_classification(engine, _samples(labels), frame_reader=_reader)
+    assert without.kernels == with_logits.kernels and plain == {k: v for k, v in res.items() if k != 'logits'}
+    starts = [i for i, k in enumerate(without.kernels) if 'preprocess_indexed_kernel' in k]
+    assert len(starts) == 3 and starts[0] == 0 and 'top1_tally_kernel' in without.kernels[-1]      # per batch: transform, forward, tally
+    assert all('top1_tally_kernel' in without.kernels[i - 1] for i in starts[1:])
+    # pieces: the budget of 12 frames of the larger directory (11 of the other); a piece's read leaves the probed frame out
+    budget = 12 * 48 * 36 * 3
+    monkeypatch.setattr(ic, 'MAX_STAGE_BYTES', budget)
+    del asked[:]
+    eval_classification(engine, _samples(labels), frame_reader=reader)
+    want = []
+    for d, (_seed, _frames, h, w) in DIRS.items():
+        pieces, cur = [], set()
+        for r in rows[d]:
+            if cur and len(cur | set(r)) * h * w * 3 > budget:
+                pieces.append(cur)
+                cur = set()
+            cur |= set(r)
+        want += [(d, union[d][:1])] + [(d, sorted(p - {union[d][0]})) for p in pieces + [cur]]
+    assert asked == want and len(want) > 4 + 1, asked
+    monkeypatch.undo()
+    del asked[:]
+    with launch_trace() as tr:
+        empty = eval_classification(engine, [], frame_reader=reader, return_logits=True)
+    assert asked == [] and tr.kernels == [] and empty['preds'] == [] and empty['overall'] is None and empty['logits'].shape == (0, 12)
+
+    def mixed(frame_dir, numbers):                                     # every frame but the probed one is a row short
+        got = _reader(frame_dir, numbers)
+        return got if len(numbers) == 1 else got[:, :-1]
+    with launch_trace() as tr:
+        with pytest.raises(ValueError, match=r'stu1: frames of \(47, 36\) and \(48, 36\) pixels'):
+            eval_classification(engine, _samples(labels), frame_reader=mixed)
+    assert tr.kernels == []

@@ -536,3 +536,63 @@ def test_classification_pipeline_engine_and_host_paths_agree(hip_lib):
         eng.close()
     assert_close(on_engine.pop('logits'), on_host.pop('logits'), what='engine path against host path', **LOGITS_BAR)
     assert on_engine == on_host and on_engine['total'] == [1, 1, 1, 0, 0, 0, 1] and len(on_engine['preds']) == 4
+
+
+def test_classification_pipeline_reader_calls_launch_order_and_refusals(hip_lib, monkeypatch):
+    """What the engine path asks of the frame reader and of the GPU, to the call: per directory ONE read of the first sample's first
+    frame, then per staged piece one read of the piece's whole union; no read and no launch for an empty list; the same launches in
+    the same order whether or not the logits are asked for; frames of another size than the probe's refused before any launch."""
+    from workoutdetector_amd import inference_count as ic, tdn_pipeline as tp
+    from workoutdetector_amd.engine import launch_trace
+    from workoutdetector_amd.transform import TestTransform
+    h, T = 64, 3
+    samples = [dict(frame_dir=d, start_index=s, total_frames=t, label=l) for d, s, t, l in
+               (('a', 1, 40, 0), ('b', 5, 9, 1), ('a', 11, 13, 2), ('a', 30, 60, 6), ('b', 2, 30, 3), ('a', 3, 5, 9), ('a', 20, 21, -1))]
+    rows = {d: [(tp.tdn_sample_frames(s['total_frames'], T) + s['start_index']).reshape(-1).tolist() for s in samples if s['frame_dir'] == d]
+            for d in 'ab'}
+    union = {d: sorted(set().union(*rows[d])) for d in 'ab'}
+    calls = []
+
+    def reader(frame_dir, numbers, rows_of=40):
+        calls.append((frame_dir, list(numbers)))
+        return np.stack([np.random.default_rng([ord(frame_dir), n]).integers(0, 256, (rows_of, 56, 3), dtype=np.uint8) for n in numbers])
+    tf = TestTransform(73, h, scale_255=True)
+    eng = _engine(h, T, max_clips=2)
+    try:
+        with launch_trace() as with_logits:
+            res = tp.tdn_eval_classification(eng, samples, reader, return_logits=True, transform=tf)
+        assert calls == [('a', rows['a'][0][:1]), ('a', union['a']), ('b', rows['b'][0][:1]), ('b', union['b'])]
+        assert res['total'] == [1, 1, 1, 1, 0, 0, 1] and len(res['preds']) == 7 and res['logits'].shape == (7, NUM_CLASS)
+        with launch_trace() as without:
+            plain = tp.tdn_eval_classification(eng, samples, reader, transform=tf)
+        assert without.kernels == with_logits.kernels and plain == {k: v for k, v in res.items() if k != 'logits'}
+        k = without.kernels                                             # per piece the transform, per batch the forward and the tally
+        assert without.count('preprocess') == 2 and 'preprocess' in k[0] and without.count('top1_tally') == 3 + 1
+        assert without.count('tdn_front_pool_kernel') == 4 and 'top1_tally' in k[-1]
+        assert [i for i, name in enumerate(k) if 'preprocess' in name][1] == [i for i, name in enumerate(k) if 'top1_tally' in name][2] + 1
+        # pieces of whole samples under a budget of 20 frames: each reads its whole union, the probe is read once per directory
+        monkeypatch.setattr(ic, 'MAX_STAGE_BYTES', 20 * 40 * 56 * 3)
+        del calls[:]
+        pieces = tp.tdn_eval_classification(eng, samples, reader, return_logits=True, transform=tf)
+        want = []
+        for d in 'ab':
+            parts, cur = [], set()
+            for r in rows[d]:
+                if cur and len(cur | set(r)) > 20:
+                    parts.append(cur)
+                    cur = set()
+                cur |= set(r)
+            want += [(d, rows[d][0][:1])] + [(d, sorted(p)) for p in parts + [cur]]
+        assert calls == want and len(want) > 4, calls
+        assert _same(pieces['logits'], res['logits']) and pieces['preds'] == res['preds'] and pieces['total'] == res['total']
+        monkeypatch.undo()
+        del calls[:]
+        with launch_trace() as tr:
+            empty = tp.tdn_eval_classification(eng, [], reader, return_logits=True, transform=tf)
+        assert calls == [] and tr.kernels == [] and empty['preds'] == [] and empty['overall'] is None
+        with launch_trace() as tr:
+            with pytest.raises(ValueError, match=r'a: frames of \(39, 56\) and \(40, 56\) pixels'):
+                tp.tdn_eval_classification(eng, samples, lambda d, n: reader(d, n, 40 if len(n) == 1 else 39), transform=tf)
+        assert tr.kernels == []
+    finally:
+        eng.close()

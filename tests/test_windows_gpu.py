@@ -396,3 +396,23 @@ def test_stream_batcher_person_crop_on_an_engine_equals_the_host_torch_route(eng
     finally:
         eng.close()
     assert ev_poison == ev and res_poison == res
+
+
+def test_a_step_ends_in_one_states_launch_and_its_sync_recycles_every_window_buffer(engine):
+    """Three windows in two batches: the step's last launch is its ONE scores_to_states_kernel, and the copy of those states --
+    the step's only sync, behind every upload -- is followed by the recycling of all three page-locked window buffers."""
+    from workoutdetector_amd.engine import launch_trace
+    from workoutdetector_amd.streaming import StreamBatcher
+    sb = StreamBatcher(engine, threshold=0.0, max_batch=2)
+    vid = _vid('a')
+    for t in range(24):
+        sb.push('a', vid[t])
+    assert sb.ready() == 3 and not sb._free and sb.pinned_bytes == 3 * 8 * 90 * 52 * 3
+    with launch_trace() as tr:
+        out = sb.step()
+    assert tr.count('preprocess_windows_kernel') == 2 and tr.count('scores_to_states_kernel') == 1, tr.kernels
+    assert 'scores_to_states_kernel' in tr.kernels[-1]
+    assert not sb._inflight and len(sb._free[(90, 52, 3)]) == 3
+    assert [w for w, _s, _c in out['a']] == [0, 1, 2]
+    sb.close('a')
+    assert sb.pinned_bytes == 0 and not sb._free

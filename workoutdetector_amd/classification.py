@@ -153,42 +153,40 @@ def _pieces(rows: Sequence[Sequence[int]], per_frame_bytes: int, budget: int) ->
     return out
 
 
-def _eval_engine(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
+def default_eval_transform(model) -> TestTransform:
+    """The test transform of an accuracy run or a TDN stream when none is given: ``TestTransform(256, model height or 224,
+    scale_255=True)``."""
+    return TestTransform(RESIZE, int(getattr(model, 'height', INPUT_SIZE)), scale_255=True)
+
+
+def _eval_engine(model, samples, groups, reader, batch: int, want_logits: bool, probe_frame, stage):
     """The device path: see the module docstring.  Returns (correct, total, preds, logits | None) in PROCESSING order."""
-    from .engine import preprocess_indexed, top1_tally
+    from .engine import top1_tally
     dev = staging.engine_device(model)
     n, c = len(samples), int(model.num_class)
     # (host zeros copied up, empty device buffers written by the library's own launches: no torch kernel anywhere)
     counters = staging.upload_table(torch.zeros((2, c), dtype=torch.int32), dev)
     preds = torch.empty((n,), dtype=torch.int32, device=dev)
-    logits = torch.empty((n, c), dtype=torch.float32, device=dev) if want_logits else None
+    logits = torch.empty((n, c), dtype=torch.float32, device=dev)
     done = 0
     for frame_dir, ids, rows in groups:
-        union_all = sorted(set().union(*rows))
-        probe = _read(reader, frame_dir, union_all[:1])                  # one frame: the directory's geometry
-        per_frame = int(probe[0].numel())
-        for a, b in _pieces(rows, per_frame, ic.MAX_STAGE_BYTES):
-            union = sorted(set().union(*rows[a:b]))
-            table = torch.from_numpy(_table(union, rows[a:b]))
-            labels = torch.tensor([int(samples[i]['label']) for i in ids[a:b]], dtype=torch.int32)
-            rest = [f for f in union if f != union_all[0]]
+        first = probe_frame(rows)
+        probe = _read(reader, frame_dir, [first])                        # one frame: the directory's geometry
 
-            def fill(pinned: torch.Tensor) -> None:
-                if len(rest) < len(union):                               # (the probed frame is the smallest: row 0)
-                    pinned[0].copy_(probe[0])
-                if rest:
-                    got = _read(reader, frame_dir, rest)
-                    if tuple(got.shape[1:]) != tuple(probe.shape[1:]):
-                        raise ValueError(f'{frame_dir}: frames of {tuple(got.shape[1:3])} and {tuple(probe.shape[1:3])} pixels')
-                    pinned[len(union) - len(rest):].copy_(got)
-            frames, _ready = staging.upload((len(union),) + tuple(probe.shape[1:]), fill, dev)
+        def read(numbers: Sequence[int]) -> torch.Tensor:
+            got = _read(reader, frame_dir, numbers)
+            if tuple(got.shape[1:]) != tuple(probe.shape[1:]):
+                raise ValueError(f'{frame_dir}: frames of {tuple(got.shape[1:3])} and {tuple(probe.shape[1:3])} pixels')
+            return got
+        for a, b in _pieces(rows, int(probe[0].numel()), ic.MAX_STAGE_BYTES):
+            union = sorted(set().union(*rows[a:b]))
+            table = torch.from_numpy(_table(union, rows[a:b]))           # validated on the host
+            labels = torch.tensor([int(samples[i]['label']) for i in ids[a:b]], dtype=torch.int32)
+            forward = stage(union, first, probe, read, dev)
             table, labels = staging.upload_table(table, dev), staging.upload_table(labels, dev)
             for lo in range(0, b - a, batch):
                 hi = min(lo + batch, b - a)
-                clips = preprocess_indexed(frames, table[lo:hi], resize=transform.size, crop=transform.crop,
-                                           scale_255=transform.scale_255, layout=model.packed_layout)
-                o = logits[done:done + hi - lo] if want_logits else None
-                out = model.forward_device(clips, out=o, layout=model.packed_layout)
+                out = forward(table[lo:hi], logits[done:done + hi - lo])
                 top1_tally(out, labels[lo:hi], counters[0], counters[1], out=preds[done:done + hi - lo])
                 done += hi - lo
     counters = counters.cpu()
@@ -196,22 +194,20 @@ def _eval_engine(model, samples, groups, reader, batch: int, transform: TestTran
             logits.cpu().numpy() if want_logits else None)
 
 
-def _eval_host(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
-    """Any other model (the onnxruntime duck type: sessions, CPU stubs): frames picked on the host, the torch
-    ``TestTransform``, ``run`` per batch, arg-max and tally in NumPy.  Same return as ``_eval_engine``."""
+def _eval_host(where: str, model, samples, groups, reader, batch: int, want_logits: bool, host_clips):
+    """Any other model (``staging.call_host``: sessions, torch modules, callables, CPU stubs): every directory's union read
+    once, ``host_clips`` of it, one call per batch, arg-max and tally in NumPy.  Same return as ``_eval_engine``."""
     c = int(getattr(model, 'num_class', 0))
-    name = model.get_inputs()[0].name
     rows_out: List[np.ndarray] = []
     for frame_dir, ids, rows in groups:
         union = sorted(set().union(*rows))
-        frames = _read(reader, frame_dir, union).permute(0, 3, 1, 2)
+        clips = host_clips(_read(reader, frame_dir, union))
         table = torch.from_numpy(_table(union, rows).astype(np.int64))
         for lo in range(0, len(ids), batch):
-            x = torch.stack([transform(frames[table[i]]) for i in range(lo, min(lo + batch, len(ids)))])
-            rows_out.append(np.asarray(model.run(None, {name: x.numpy()})[0], dtype=np.float32))
+            rows_out.append(staging.call_host(model, clips(table[lo:lo + batch])))
     logits = np.concatenate(rows_out) if rows_out else np.zeros((0, c), dtype=np.float32)
     if logits.ndim != 2:
-        raise ValueError(f'eval_classification needs one row of scores per clip, the model returned {logits.shape}')
+        raise ValueError(f'{where} needs one row of scores per clip, the model returned {logits.shape}')
     c = c or int(logits.shape[1])
     preds = logits.argmax(axis=1).astype(np.int64) if len(logits) else np.zeros((0,), dtype=np.int64)
     correct, total = [0] * c, [0] * c
@@ -222,6 +218,45 @@ def _eval_host(model, samples, groups, reader, batch: int, transform: TestTransf
             total[label] += 1
             correct[label] += int(p == label)
     return correct, total, preds.tolist(), logits if want_logits else None
+
+
+def evaluate(where: str, model, samples: Sequence[Mapping], groups, reader: FrameReader, batch_clips: Optional[int],
+             return_logits: bool, probe_frame, stage, host_clips) -> dict:
+    """The accuracy loop behind ``eval_classification`` and ``tdn_pipeline.tdn_eval_classification`` (``where``: the one that
+    was called, for messages): the batch size, the engine-or-host decision, the loop over directories, pieces and batches,
+    the tally and the result dict.  ``groups``: ``(frame_dir, sample indices, their frame numbers)`` per directory.  What a
+    family of models adds:
+
+      ``probe_frame(rows)``    the frame number ``first`` that is read first, alone: ``probe``, the directory's frame size
+                               (engine path);
+      ``stage(union, first, probe, read, dev)``
+                               stages the frames ``union`` of one piece on ``dev`` -- ``read(numbers)`` reads frames and
+                               refuses another size than the probe's -- and returns ``forward(table rows, out)``, which
+                               enqueues one batch into ``out``; None: the family has no device path for this model;
+      ``host_clips(frames)``   takes a directory's uint8 ``[n,H,W,3]`` union and returns ``clips(table rows)``, the batch a
+                               host model is called on."""
+    engine = staging.device_path(model) and stage is not None
+    limit = int(model.max_clips) if engine else None
+    batch = int(batch_clips or limit or 32)
+    if batch <= 0:
+        raise ValueError(f'batch_clips must be positive, got {batch_clips}')
+    if limit:
+        batch = min(batch, limit)
+    if engine and samples:
+        correct, total, preds, logits = _eval_engine(model, samples, groups, reader, batch, return_logits, probe_frame, stage)
+    else:
+        correct, total, preds, logits = _eval_host(where, model, samples, groups, reader, batch, return_logits, host_clips)
+    # processing order (by directory) -> sample order
+    order = [i for _d, ids, _r in groups for i in ids]
+    back = np.empty(len(order), dtype=np.int64)
+    back[order] = np.arange(len(order))
+    res = {'correct': [int(v) for v in correct], 'total': [int(v) for v in total],
+           'acc': [c / n if n else None for c, n in zip(correct, total)],
+           'overall': sum(correct) / sum(total) if sum(total) else None,
+           'preds': [int(preds[j]) for j in back]}
+    if return_logits:
+        res['logits'] = logits[back]
+    return res
 
 
 def eval_classification(model, samples: Sequence[Mapping], frame_reader: Optional[FrameReader] = None,
@@ -243,37 +278,37 @@ def eval_classification(model, samples: Sequence[Mapping], frame_reader: Optiona
     A ``TsmEngine`` stages that union (pinned, then device; a directory beyond ``inference_count.MAX_STAGE_BYTES`` in
     pieces of whole samples) and runs, per batch of at most ``batch_clips`` (default and limit: its ``max_clips``) samples,
     one ``preprocess_indexed_kernel`` launch, the forward and one ``top1_tally_kernel`` launch; counters and preds come back
-    once, at the end.  Any other model (``run()`` duck type) takes the host path with the same result.  ``transform``:
-    a ``TestTransform`` naming resize / crop / scaling (default ``TestTransform(256, model height or 224, scale_255=True)``).
-    A model with per-segment scores (``consensus_type='identity'``) is refused up front.
+    once, at the end.  Any other model -- an onnxruntime-style session (``run()`` duck type), a torch module or a plain
+    callable on ``[B, T, 3, H, W]`` (``staging.call_host``) -- takes the host path with the same result.  ``transform``:
+    a ``TestTransform`` naming resize / crop / scaling (default ``default_eval_transform``: ``TestTransform(256, model height
+    or 224, scale_255=True)``).  A model with per-segment scores (``consensus_type='identity'``) is refused up front.
     Out of scope: person crop, random sampling, multi-rank sharding, batches across directories (module docstring)."""
     ic.need_clip_rows(model, 'eval_classification')
-    reader = frame_reader or read_frames
     t = int(getattr(model, 'num_segments', ic.NUM_SEGMENTS))
-    if transform is None:
-        transform = TestTransform(RESIZE, int(getattr(model, 'height', INPUT_SIZE)), scale_255=True)
+    tf = transform or default_eval_transform(model)
+
+    def stage(union, first, probe, read, dev):
+        """The piece's union through ``staging.upload``, the probed frame copied from the probe, not read again; then per batch
+        ONE ``preprocess_indexed`` launch into the packed input and the forward."""
+        from .engine import preprocess_indexed
+        rest = [f for f in union if f != first]
+
+        def fill(pinned: torch.Tensor) -> None:
+            if len(rest) < len(union):                               # (the probed frame is the smallest: row 0)
+                pinned[0].copy_(probe[0])
+            if rest:
+                pinned[len(union) - len(rest):].copy_(read(rest))
+        frames, _ready = staging.upload((len(union),) + tuple(probe.shape[1:]), fill, dev)
+        return lambda table, out: model.forward_device(
+            preprocess_indexed(frames, table, resize=tf.size, crop=tf.crop, scale_255=tf.scale_255, layout=model.packed_layout),
+            out=out, layout=model.packed_layout)
+
+    def host_clips(frames: torch.Tensor):
+        chw = frames.permute(0, 3, 1, 2)
+        return lambda table: torch.stack([tf(chw[row]) for row in table])
     samples = list(samples)
-    groups = _by_directory(samples, t)
-    engine = staging.device_path(model)
-    limit = int(model.max_clips) if engine else None
-    batch = int(batch_clips or limit or 32)
-    if batch <= 0:
-        raise ValueError(f'batch_clips must be positive, got {batch_clips}')
-    if limit:
-        batch = min(batch, limit)
-    run = _eval_engine if engine and samples else _eval_host
-    correct, total, preds, logits = run(model, samples, groups, reader, batch, transform, return_logits)
-    # processing order (by directory) -> sample order
-    order = [i for _d, ids, _r in groups for i in ids]
-    back = np.empty(len(order), dtype=np.int64)
-    back[order] = np.arange(len(order))
-    res = {'correct': [int(v) for v in correct], 'total': [int(v) for v in total],
-           'acc': [c / n if n else None for c, n in zip(correct, total)],
-           'overall': sum(correct) / sum(total) if sum(total) else None,
-           'preds': [int(preds[j]) for j in back]}
-    if return_logits:
-        res['logits'] = logits[back]
-    return res
+    return evaluate('eval_classification', model, samples, _by_directory(samples, t), frame_reader or read_frames, batch_clips,
+                    return_logits, lambda rows: min(set().union(*rows)), stage, host_clips)
 
 
 def main(annos: Mapping[str, str], data_root: str, out_json: str, model=None, checkpoint: Optional[str] = None,

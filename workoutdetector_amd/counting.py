@@ -82,6 +82,15 @@ def scores_to_preds(scores: Iterable[Sequence[float]], threshold: float = 0.5, s
     return [int(b) if t >= threshold else -1 for b, t in zip(best, top)]
 
 
+def scores_to_state_list(scores, threshold: float = 0.5, softmax: bool = True) -> List[int]:
+    """``scores_to_preds`` wherever the scores are: a CUDA tensor [n, num_class] takes ONE ``engine.scores_to_states`` launch and
+    one int32 per row crosses PCIe in its single ``.cpu()`` (the caller's sync); an ndarray or a list stays on the host."""
+    if getattr(scores, 'is_cuda', False):
+        from .engine import scores_to_states
+        return scores_to_states(scores, threshold=threshold, softmax=softmax).cpu().tolist()
+    return scores_to_preds(scores, threshold=threshold, softmax=softmax)
+
+
 VOTE_WINDOW = 7         # count_by_image_model's deque(maxlen=7) ...
 VOTE_SUM = 4            # ... and its `sum(que) >= 4`
 

@@ -11,7 +11,8 @@ Counterpart of workoutdetector/utils/inference_count.py for the video-model path
   save_scores_to_json    :47-67
 
 What differs from the reference, on purpose:
-  * ``model`` is anything with the onnxruntime duck type (``get_inputs()[0].name`` / ``run``); a
+  * ``model`` is anything with the onnxruntime duck type (``get_inputs()[0].name`` / ``run``) -- the batched paths also take a
+    torch module or a plain callable (``staging.call_host``); ``inference_video`` keeps the reference's session call; a
     ``TsmEngine`` additionally gets the batched device path: the uint8 frames of a video go to the GPU
     once, the fused HIP transform (``tsm_preprocess``: resize 256 / crop 224 / normalise -> NHWC4) runs
     once per *frame* (each even frame belongs to two half-overlapping windows; the transform is
@@ -352,8 +353,7 @@ def _forward_clips(model, clips: torch.Tensor, hip_transform: bool) -> torch.Ten
         return model.forward_device(clips.contiguous(), layout=model.packed_layout)
     if staging.engine_device(model) is not None and hasattr(model, 'forward_device'):
         return model.forward_device(clips.contiguous())
-    name = model.get_inputs()[0].name
-    return torch.from_numpy(np.asarray(model.run(None, {name: clips.cpu().numpy()})[0]))
+    return torch.from_numpy(staging.call_host(model, clips))
 
 
 def video_clip_logits(model, video_thwc_u8: torch.Tensor, transform: Union[TestTransform, PersonCropTransform],
@@ -944,16 +944,7 @@ def _image_logits_device(model, frames_u8: torch.Tensor) -> torch.Tensor:
 def _image_scores_host(model, frames_u8: torch.Tensor, transform: ImageTransform) -> np.ndarray:
     """Non-engine models: the CPU ``ImageTransform``, then a torch module (``model(x[n,3,H,W])``) or an onnxruntime-style
     session (one ``run`` per frame on [1,3,H,W], as the reference feeds it)."""
-    return _image_scores_of(model, transform(frames_u8))
-
-
-def _image_scores_of(model, x: torch.Tensor) -> np.ndarray:
-    """``_image_scores_host`` behind the transform: x float32 [n, 3, crop, crop] -> scores [n, num_class]."""
-    if hasattr(model, 'run') and hasattr(model, 'get_inputs'):
-        name = model.get_inputs()[0].name
-        return np.stack([np.asarray(model.run(None, {name: x[i:i + 1].numpy()})[0][0], dtype=np.float32)
-                         for i in range(x.shape[0])])
-    return staging.call_host_module(model, x)
+    return staging.call_host(model, transform(frames_u8), one_per_run=True)
 
 
 def inference_images(model, frames_u8) -> np.ndarray:

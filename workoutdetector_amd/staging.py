@@ -1,6 +1,6 @@
 """Host staging, once for every pipeline: which models take the device path (``device_path``) and how host data reaches the
 engine's GPU -- uint8 frames through the process-wide ``pinned_pool`` (``upload``, ``wait_upload``), small tables through
-``upload_table``.  ``StreamBatcher``'s window buffers are NOT in the pool: they are filled when a frame arrives, long before the
+``upload_table`` -- and how a model that takes a host path is called (``call_host``).  ``StreamBatcher``'s window buffers are NOT in the pool: they are filled when a frame arrives, long before the
 copy, and have a byte budget of their own."""
 from __future__ import annotations
 
@@ -107,6 +107,18 @@ def upload_table(host: torch.Tensor, dev: torch.device) -> torch.Tensor:
     staged = torch.empty(host.shape, dtype=host.dtype, pin_memory=True)
     staged.copy_(host)
     return staged.to(dev, non_blocking=True)
+
+
+def call_host(model, x: torch.Tensor, one_per_run: bool = False) -> np.ndarray:
+    """A model without a device path on a batch ``x`` -> float32 ndarray: the one way the pipelines call it.  The onnxruntime
+    duck type (``run`` + ``get_inputs``) gets ``run(None, {first input name: x as numpy})[0]`` -- with ``one_per_run`` one ``run``
+    per row of ``x``, as the reference feeds the image model; anything else is ``call_host_module``'s."""
+    if not (hasattr(model, 'run') and hasattr(model, 'get_inputs')):
+        return call_host_module(model, x)
+    name, feed = model.get_inputs()[0].name, x.cpu().numpy()
+    if one_per_run:
+        return np.concatenate([np.asarray(model.run(None, {name: feed[i:i + 1]})[0], dtype=np.float32) for i in range(len(feed))])
+    return np.asarray(model.run(None, {name: feed})[0], dtype=np.float32)
 
 
 def call_host_module(model, x: torch.Tensor) -> np.ndarray:

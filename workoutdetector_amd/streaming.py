@@ -29,11 +29,11 @@ import numpy as np
 import torch
 
 from . import staging
-from .counting import VOTE_WINDOW, RepCounter, scores_to_preds, vote_states
+from .counting import VOTE_WINDOW, RepCounter, scores_to_state_list, vote_states
 from .inference_count import NUM_SEGMENTS, need_clip_rows
 from .transform import (IMAGE_WINDOW_FORMATS, Box, ImageTransform, PersonCropTransform, TestTransform, build_test_transform,
-                        check_frame_format, image_tables, image_window_descriptors, nv12_luma_hw, nv12_to_rgb, person_box,
-                        window_descriptors, yuv_frame_bytes_view, yuv_luma_hw, yuv_to_rgb)
+                        check_frame_format, image_tables, image_window_descriptors, person_box, pushed_frame, window_descriptors,
+                        yuv_luma_hw)
 
 
 @dataclass
@@ -55,7 +55,9 @@ class StreamBatcher:
 
     Windows are non-overlapping with stride 8 like the reference's streaming loop; ``softmax``/``threshold``
     follow utils/eval.py:153-164; frame sizes may differ between streams (a batch of mixed sizes is still ONE transform
-    launch, ``tsm_preprocess_windows``, in batch order at 224x224).
+    launch, ``tsm_preprocess_windows``, in batch order at 224x224).  A model that is no ``TsmEngine`` on a GPU takes the host
+    path -- the torch transform and ``staging.call_host``: an onnxruntime-style session, a torch module or a plain callable on
+    ``[B, 8, 3, H, W]``.
 
     ``person_crop=True``: ``push(stream_id, frame, box=(x1, y1, x2, y2))`` takes the detector's first box of that frame; a
     complete window is cropped to ``transform.person_box`` of the boxes pushed with its frames and resized to the crop size
@@ -112,22 +114,7 @@ class StreamBatcher:
             if len(box) != 4 or not all(np.isfinite(box)):
                 raise ValueError(f'box must be four finite numbers (x1, y1, x2, y2), got {box}')
         st = self.open(stream_id)
-        arr = np.asarray(frame)
-        if self.frame_format == 'nv12':
-            if arr.dtype != np.uint8 or arr.ndim != 2:
-                raise ValueError(f'an NV12 frame must be uint8 [3H/2,W], got {arr.dtype} {arr.shape}')
-            nv12_luma_hw(arr.shape)
-            if self._dev is None:
-                arr = nv12_to_rgb(arr, self.colorimetry)[0]
-        elif self.frame_format != 'rgb':
-            arr = yuv_frame_bytes_view(arr, self.frame_format)
-            if arr.dtype != np.uint8 or arr.ndim != 2:
-                raise ValueError(f'a {self.frame_format} frame must be its uint8 container [rows, bytes], got {arr.dtype} {arr.shape}')
-            yuv_luma_hw(arr.shape, self.frame_format)
-            if self._dev is None:
-                arr = yuv_to_rgb(arr, self.frame_format, self.colorimetry)[0]
-        elif arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
-            raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
+        arr, _hw = pushed_frame(frame, self.frame_format, self.colorimetry, to_rgb=self._dev is None)
         st.frames_seen += 1
         if self._dev is not None:
             if st.cur is None:
@@ -259,8 +246,7 @@ class StreamBatcher:
             xs = [self._crop_transform(torch.from_numpy(w).permute(0, 3, 1, 2).float(), box) for w, box in zip(windows, crops)]
         else:
             xs = [tf(torch.from_numpy(w).permute(0, 3, 1, 2).float()) for w in windows]
-        name = self.model.get_inputs()[0].name
-        return np.asarray(self.model.run(None, {name: torch.stack(xs).numpy()})[0])
+        return staging.call_host(self.model, torch.stack(xs))
 
     def step(self) -> Dict[Hashable, List[Tuple[int, int, int]]]:
         """Run all complete windows (oldest first, round-robin over streams) and update the counters."""
@@ -280,14 +266,12 @@ class StreamBatcher:
             pending.append(self._logits([w for _, w, _ in batch], [c for _, _, c in batch]))
             order += [sid for sid, _, _ in batch]
         if pending:
-            if isinstance(pending[0], torch.Tensor):
-                # HIP path: softmax / arg-max / threshold on the GPU too (tsm_scores_to_states): one int32 per window
-                # crosses PCIe, in the step's only host sync
-                from .engine import scores_to_states
-                states = scores_to_states(torch.cat(pending), threshold=self.threshold, softmax=self.softmax).cpu().tolist()
+            # HIP path: softmax / arg-max / threshold on the GPU too (tsm_scores_to_states): one int32 per window crosses PCIe,
+            # in the step's only host sync
+            hip = isinstance(pending[0], torch.Tensor)
+            states = scores_to_state_list(torch.cat(pending) if hip else np.concatenate(pending), self.threshold, self.softmax)
+            if hip:
                 self._recycle()     # that .cpu() was the step's sync: every upload queued before it has completed
-            else:
-                states = scores_to_preds(np.concatenate(pending).tolist(), threshold=self.threshold, softmax=self.softmax)
             for sid, state in zip(order, states):
                 st = self.streams[sid]
                 widx = len(st.states)
@@ -386,17 +370,9 @@ class ImageStreamBatcher:
         return self.streams[stream_id]
 
     def push(self, stream_id: Hashable, frame) -> None:
-        arr = np.asarray(frame)
-        if self.frame_format == 'nv12':
-            if arr.dtype != np.uint8 or arr.ndim != 2:
-                raise ValueError(f'an NV12 frame must be uint8 [3H/2,W], got {arr.dtype} {arr.shape}')
-            h, w = nv12_luma_hw(arr.shape)
-            if self._dev is None:
-                arr = nv12_to_rgb(arr, self.colorimetry)[0]
-        elif arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3 or 0 in arr.shape:
+        arr, (h, w) = pushed_frame(frame, self.frame_format, self.colorimetry, to_rgb=self._dev is None)
+        if 0 in (h, w):                                       # (an RGB frame: an NV12 one was refused above)
             raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
-        else:
-            h, w = int(arr.shape[0]), int(arr.shape[1])
         # the refusals of a window, before anything is queued: a side beyond 65535, a crop larger than the resized frame
         image_window_descriptors([(h, w)], [0], [0], self.resize, self.crop, self.frame_format)
         tables = image_tables(h, w, self.resize, self.crop) if self._dev is not None else None
@@ -498,9 +474,8 @@ class ImageStreamBatcher:
         return scores_to_states(logits, threshold=float('-inf'), softmax=False)
 
     def _preds_host(self, ch: _ImageChunk) -> List[int]:
-        from .inference_count import _image_scores_of
         x = torch.cat([self.transform(f) for f in ch.frames])
-        return _image_scores_of(self.model, x).argmax(axis=1).tolist()
+        return staging.call_host(self.model, x, one_per_run=True).argmax(axis=1).tolist()
 
     def step(self) -> Dict[Hashable, List[Tuple[int, int, int]]]:
         """Run every queued frame (arrival order: a stream's frames stay in order) and update the votes and the counters."""

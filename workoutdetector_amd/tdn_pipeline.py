@@ -27,9 +27,9 @@ import torch
 
 from . import inference_count as ic
 from . import staging
-from .classification import RESIZE, FrameReader, _pieces, _read, _table, read_frames
-from .counting import RepCounter, pred_to_count, scores_to_preds
-from .transform import INPUT_SIZE, PersonCropTransform, TestTransform
+from .classification import FrameReader, default_eval_transform, evaluate, read_frames
+from .counting import RepCounter, pred_to_count, scores_to_state_list
+from .transform import PersonCropTransform, TestTransform, pushed_frame
 
 TDN_FRAMES = 5
 
@@ -105,13 +105,6 @@ def _need_tdn_rows(model, transform, where: str, frame_format: str = 'rgb') -> N
             raise ValueError(f'{where} crops squares: the engine is {h} x {w}')
         if int(transform.crop) != int(h):
             raise ValueError(f'{where}: the transform crops {transform.crop} pixels, the engine takes {h}')
-
-
-def _call_host(model, x: torch.Tensor) -> np.ndarray:
-    """A model without a device path on clips ``[B, T, 5, 3, H, W]``: the onnxruntime duck type, a torch module or a callable."""
-    if hasattr(model, 'run') and hasattr(model, 'get_inputs'):
-        return np.asarray(model.run(None, {model.get_inputs()[0].name: x.cpu().numpy()})[0], dtype=np.float32)
-    return staging.call_host_module(model, x)
 
 
 def _stage_pool(fill, n: int, frame_shape, zero_last: bool, tf: TestTransform, dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -317,7 +310,7 @@ def tdn_video_clip_logits(model, video_thwc_u8, transform: TestTransform, clip_r
             for c in range(0, p_hi - p_lo, batch_clips):
                 sel = idx[c:c + batch_clips]
                 x = torch.index_select(pool, 0, sel.reshape(-1)).view(tuple(sel.shape) + tuple(pool.shape[1:]))
-                out.append(torch.from_numpy(_call_host(model, x)))
+                out.append(torch.from_numpy(staging.call_host(model, x)))
     return torch.cat(out, dim=0).to(torch.float32).cpu()
 
 
@@ -329,12 +322,8 @@ def tdn_count_video(model, video, transform: TestTransform, threshold: float = 0
     logits = tdn_video_clip_logits(model, video, transform, step=step, reuse_segments=reuse_segments)
     if logits.shape[0] == 0:
         return 0, []
-    if staging.device_path(model):
-        from .engine import scores_to_states
-        states = scores_to_states(logits.to(staging.engine_device(model)), threshold=threshold, softmax=softmax).cpu().tolist()
-    else:
-        states = scores_to_preds(logits.numpy(), threshold=threshold, softmax=softmax)
-    return pred_to_count(states, step)
+    rows = logits.to(staging.engine_device(model)) if staging.device_path(model) else logits.numpy()
+    return pred_to_count(scores_to_state_list(rows, threshold, softmax), step)
 
 
 # ---- streams ---------------------------------------------------------------------------------------------------------------------
@@ -382,8 +371,7 @@ class TdnStreamBatcher:
                  transform: Optional[TestTransform] = None,
                  on_window: Optional[Callable[[Hashable, int, int, int], None]] = None, keep_logits: bool = False,
                  frame_format: str = 'rgb'):
-        if transform is None:
-            transform = TestTransform(RESIZE, int(getattr(model, 'height', INPUT_SIZE)), scale_255=True)
+        transform = transform or default_eval_transform(model)
         _need_tdn_rows(model, transform, 'TdnStreamBatcher', frame_format)      # (before the library loads)
         if max_batch <= 0:
             raise ValueError(f'max_batch must be positive, got {max_batch}')
@@ -411,9 +399,7 @@ class TdnStreamBatcher:
         return self.streams[stream_id]
 
     def push(self, stream_id: Hashable, frame) -> None:
-        arr = np.asarray(frame)
-        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
-            raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
+        arr, _hw = pushed_frame(frame, 'rgb', None, to_rgb=False)      # (RGB only: the constructor refused anything else)
         st = self.open(stream_id)
         if st.shape is None:
             st.shape = tuple(arr.shape)
@@ -454,19 +440,16 @@ class TdnStreamBatcher:
         rows = self._logits_engine(jobs) if self._engine else self._logits_host(jobs)
         order = [(sid, st, c) for sid, st, lo, hi, _total in jobs for c in range(lo, hi)]
         if order:
-            if isinstance(rows, torch.Tensor):     # states on the GPU too: one int32 per clip crosses in the step's only sync
-                from .engine import scores_to_states
-                states = scores_to_states(rows, threshold=self.threshold, softmax=self.softmax).cpu().tolist()
-                host_rows = rows.cpu().numpy() if self.keep_logits else None
-            else:
-                states = scores_to_preds(rows, threshold=self.threshold, softmax=self.softmax)
-                host_rows = rows
+            # (an engine's rows: states on the GPU too, one int32 per clip crosses in the step's only sync; kept rows follow it)
+            states = scores_to_state_list(rows, self.threshold, self.softmax)
+            if self.keep_logits and isinstance(rows, torch.Tensor):
+                rows = rows.cpu().numpy()
             for i, ((sid, st, c), state) in enumerate(zip(order, states)):
                 count = st.counter.push(state)
                 st.emitted = c + 1
                 out.setdefault(sid, []).append((c, state, count))
                 if self.keep_logits:
-                    self.logits.setdefault(sid, []).append((c, np.array(host_rows[i], dtype=np.float32)))
+                    self.logits.setdefault(sid, []).append((c, np.array(rows[i], dtype=np.float32)))
                 if self.on_window is not None:
                     self.on_window(sid, c, state, count)
         for _sid, st, _lo, _hi, _total in jobs:
@@ -583,7 +566,7 @@ class TdnStreamBatcher:
         if not xs:
             return None
         x = torch.cat(xs, dim=0)
-        return np.concatenate([_call_host(self.model, x[c:c + self.max_batch]) for c in range(0, x.shape[0], self.max_batch)])
+        return np.concatenate([staging.call_host(self.model, x[c:c + self.max_batch]) for c in range(0, x.shape[0], self.max_batch)])
 
 
 # ---- accuracy --------------------------------------------------------------------------------------------------------------------
@@ -599,64 +582,6 @@ def _tdn_groups(samples: Sequence[Mapping], T: int, rng) -> List[Tuple[str, List
     return [(d, ids, rows) for d, (ids, rows) in groups.items()]
 
 
-def _tdn_eval_engine(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
-    from .engine import top1_tally
-    dev = staging.engine_device(model)
-    n, c = len(samples), int(model.num_class)
-    counters = staging.upload_table(torch.zeros((2, c), dtype=torch.int32), dev)
-    preds = torch.empty((n,), dtype=torch.int32, device=dev)
-    logits = torch.empty((n, c), dtype=torch.float32, device=dev)
-    done = 0
-    for frame_dir, ids, rows in groups:
-        probe = _read(reader, frame_dir, rows[0][:1])                        # one frame: the directory's geometry
-        for a, b in _pieces(rows, int(probe[0].numel()), ic.MAX_STAGE_BYTES):
-            union = sorted(set().union(*rows[a:b]))
-            table = torch.from_numpy(_table(union, rows[a:b]))           # [b - a, T * 5], validated on the host
-            labels = torch.tensor([int(samples[i]['label']) for i in ids[a:b]], dtype=torch.int32)
-
-            def fill(pinned: torch.Tensor, union=union) -> None:
-                got = _read(reader, frame_dir, union)
-                if tuple(got.shape[1:]) != tuple(probe.shape[1:]):
-                    raise ValueError(f'{frame_dir}: frames of {tuple(got.shape[1:3])} and {tuple(probe.shape[1:3])} pixels')
-                pinned.copy_(got)
-            pool = _stage_pool(fill, len(union), tuple(probe.shape[1:]), False, transform, dev)
-            table, labels = staging.upload_table(table, dev), staging.upload_table(labels, dev)
-            for lo in range(0, b - a, batch):
-                hi = min(lo + batch, b - a)
-                out = model.forward_pool(pool, table[lo:hi], n_clips=hi - lo, out=logits[done:done + hi - lo])
-                top1_tally(out, labels[lo:hi], counters[0], counters[1], out=preds[done:done + hi - lo])
-                done += hi - lo
-    counters = counters.cpu()
-    return counters[0].tolist(), counters[1].tolist(), preds.cpu().tolist(), logits.cpu().numpy() if want_logits else None
-
-
-def _tdn_eval_host(model, samples, groups, reader, batch: int, transform: TestTransform, want_logits: bool):
-    c = int(getattr(model, 'num_class', 0))
-    T = int(getattr(model, 'num_segments', ic.NUM_SEGMENTS))
-    rows_out: List[np.ndarray] = []
-    for frame_dir, ids, rows in groups:
-        union = sorted(set().union(*rows))
-        frames = transform(_read(reader, frame_dir, union).permute(0, 3, 1, 2).to(torch.float32))
-        table = torch.from_numpy(_table(union, rows).astype(np.int64))
-        for lo in range(0, len(ids), batch):
-            sel = table[lo:lo + batch]
-            x = torch.index_select(frames, 0, sel.reshape(-1)).view((sel.shape[0], T, TDN_FRAMES) + tuple(frames.shape[1:]))
-            rows_out.append(_call_host(model, x))
-    logits = np.concatenate(rows_out) if rows_out else np.zeros((0, c), dtype=np.float32)
-    if logits.ndim != 2:
-        raise ValueError(f'tdn_eval_classification needs one row of scores per clip, the model returned {logits.shape}')
-    c = c or int(logits.shape[1])
-    preds = logits.argmax(axis=1).astype(np.int64) if len(logits) else np.zeros((0,), dtype=np.int64)
-    correct, total = [0] * c, [0] * c
-    order = [i for _d, ids, _r in groups for i in ids]
-    for p, i in zip(preds.tolist(), order):
-        label = int(samples[i]['label'])
-        if 0 <= label < c:
-            total[label] += 1
-            correct[label] += int(p == label)
-    return correct, total, preds.tolist(), logits if want_logits else None
-
-
 def tdn_eval_classification(model, samples: Sequence[Mapping], frame_reader: Optional[FrameReader] = None,
                             rng: Optional[np.random.RandomState] = None, batch_clips: Optional[int] = None,
                             return_logits: bool = False, transform: Optional[TestTransform] = None) -> dict:
@@ -667,30 +592,20 @@ def tdn_eval_classification(model, samples: Sequence[Mapping], frame_reader: Opt
 
     A ``TsmEngine`` on a GPU stages the union of a directory's frames (beyond ``inference_count.MAX_STAGE_BYTES`` in pieces of
     whole samples), makes ONE ``preprocess_frames(packed=False)`` launch per piece and, per batch, one table-mode
-    ``forward_pool`` and one ``top1_tally`` into device counters.  Any other model takes the host path with the same result."""
-    if transform is None:
-        transform = TestTransform(RESIZE, int(getattr(model, 'height', INPUT_SIZE)), scale_255=True)
+    ``forward_pool`` and one ``top1_tally`` into device counters.  Any other model (``staging.call_host`` on ``[B, T, 5, 3, H, W]``:
+    a session, a torch module, a callable) takes the host path with the same result.  The loop, the tally and the result dict
+    are ``classification.evaluate``'s; what is TDN's own is below: the frame numbers, the pool and the clips of the host path."""
+    transform = transform or default_eval_transform(model)
     _need_tdn_rows(model, transform, 'tdn_eval_classification')
-    reader = frame_reader or read_frames
     T = int(getattr(model, 'num_segments', ic.NUM_SEGMENTS))
+
+    def stage(union, _first, probe, read, dev):
+        pool = _stage_pool(lambda pinned: pinned.copy_(read(union)), len(union), tuple(probe.shape[1:]), False, transform, dev)
+        return lambda table, out: model.forward_pool(pool, table, n_clips=int(table.shape[0]), out=out)
+
+    def host_clips(frames: torch.Tensor):
+        pool = transform(frames.permute(0, 3, 1, 2).to(torch.float32))
+        return lambda table: torch.index_select(pool, 0, table.reshape(-1)).view((table.shape[0], T, TDN_FRAMES) + tuple(pool.shape[1:]))
     samples = list(samples)
-    groups = _tdn_groups(samples, T, rng)
-    engine = staging.device_path(model) and hasattr(model, 'forward_pool')
-    limit = int(model.max_clips) if engine else None
-    batch = int(batch_clips or limit or 32)
-    if batch <= 0:
-        raise ValueError(f'batch_clips must be positive, got {batch_clips}')
-    if limit:
-        batch = min(batch, limit)
-    run = _tdn_eval_engine if engine and samples else _tdn_eval_host
-    correct, total, preds, logits = run(model, samples, groups, reader, batch, transform, return_logits)
-    order = [i for _d, ids, _r in groups for i in ids]
-    back = np.empty(len(order), dtype=np.int64)
-    back[order] = np.arange(len(order))
-    res = {'correct': [int(v) for v in correct], 'total': [int(v) for v in total],
-           'acc': [c / n if n else None for c, n in zip(correct, total)],
-           'overall': sum(correct) / sum(total) if sum(total) else None,
-           'preds': [int(preds[j]) for j in back]}
-    if return_logits:
-        res['logits'] = logits[back]
-    return res
+    return evaluate('tdn_eval_classification', model, samples, _tdn_groups(samples, T, rng), frame_reader or read_frames, batch_clips,
+                    return_logits, lambda rows: rows[0][0], stage if hasattr(model, 'forward_pool') else None, host_clips)

@@ -438,6 +438,30 @@ def nv12_black(h: int, w: int, colorimetry: str = 'bt601') -> np.ndarray:
     return out
 
 
+def pushed_frame(frame, frame_format: str, colorimetry: Optional[str], to_rgb: bool) -> Tuple[np.ndarray, Tuple[int, int]]:
+    """What a stream batcher's ``push`` asks of ONE frame of its ``frame_format``: ``'rgb'`` uint8 [H,W,3]; ``'nv12'`` uint8
+    [3H/2,W]; a YUV_FORMATS name that format's uint8 container (a 16-bit ``'p010'`` frame is taken as its bytes); ValueError
+    otherwise.  Returns the array to queue -- with ``to_rgb`` (the host path converts on arrival) ``nv12_to_rgb`` /
+    ``yuv_to_rgb`` of it -- and its luma ``(h, w)``."""
+    arr = np.asarray(frame)
+    if frame_format == 'rgb':
+        if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError(f'frame must be uint8 [H,W,3], got {arr.dtype} {arr.shape}')
+        return arr, (int(arr.shape[0]), int(arr.shape[1]))
+    if frame_format == 'nv12':
+        if arr.dtype != np.uint8 or arr.ndim != 2:
+            raise ValueError(f'an NV12 frame must be uint8 [3H/2,W], got {arr.dtype} {arr.shape}')
+        hw = nv12_luma_hw(arr.shape)
+    else:
+        arr = yuv_frame_bytes_view(arr, frame_format)
+        if arr.dtype != np.uint8 or arr.ndim != 2:
+            raise ValueError(f'a {frame_format} frame must be its uint8 container [rows, bytes], got {arr.dtype} {arr.shape}')
+        hw = yuv_luma_hw(arr.shape, frame_format)
+    if to_rgb:
+        arr = (nv12_to_rgb(arr, colorimetry) if frame_format == 'nv12' else yuv_to_rgb(arr, frame_format, colorimetry))[0]
+    return arr, hw
+
+
 def window_descriptors(shapes, offsets, boxes=None, resize: int = 256, crop: int = INPUT_SIZE,
                        frame_format: str = 'rgb') -> np.ndarray:
     """The descriptor table ``tsm_preprocess_windows`` takes (include/tsm_hip.h), built and VALIDATED on the host: int32

@@ -65,6 +65,12 @@ struct ConvParams {
   // where pos_major_valid does not hold the launch runs in natural order (n, oy, ox).  y and the tail's reduction keep the
   // natural layout [N, Ho, Wo, Cout]; the tail's segment sums (ypart) are in m' order.
   int pos_major;
+  // Live-balanced XCD runs of a position-major launch (pos_balanced_runs below).  pos_balance is the request; conv_route answers
+  // it and the launcher fills in the rest: pos_whole > 0 = the workgroups of the launch's whole-tile part (8 x the longest run),
+  // pos_run[x] .. pos_run[x + 1] = the whole tiles of XCD x.  All zero: equal-count runs.
+  int pos_balance;
+  int pos_whole;
+  int pos_run[9];
 };
 
 enum ConvPrec { kPrecF32 = 0, kPrecBf16x3 = 1, kPrecBf16 = 2 };
@@ -479,6 +485,8 @@ struct ConvRoute {
   long tiles = 0;         // output tiles (the segmented forms launch up to conv_num_segments workgroups for each)
   unsigned grid = 0;      // workgroups
   int tr = 0, tc = 0, swz = 0;   // weight-stationary 3x3 geometry
+  // pos_major with ConvParams::pos_balance: the whole-tile workgroups (8 x the longest run; 0 = equal-count runs) and the runs
+  int pos_whole = 0, pos_run[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // launch_conv's argument rules: true when the launch is refused whatever the tile.
@@ -550,6 +558,45 @@ inline bool pos_major_valid(const ConvParams &p, int ks) {
          (double)p.N * p.Hi * p.Wi * p.C * 4.0 < 2.0e9 && (double)p.M * p.Cout * 4.0 < 2.0e9;
 }
 
+// Live-balanced XCD runs.  conv_igemm gives XCD x (workgroups x, x + 8, ..) a contiguous run of tiles; with equal tile counts the
+// runs of a position-major launch differ in work, because a tile costs its position's live taps (4, 6 or 9 of 9) and the runs
+// holding the first and last rows of positions are light -- the launch then ends with its heaviest XCD.  This cuts the whole
+// tiles [0, nwg) (nwg % ntn == 0; tile order unchanged: n fastest, frame group, position) into 8 contiguous runs at multiples
+// of ntn (the n-tiles of one A panel stay together), boundary k at the tile group where the cumulative live taps come closest
+// to k / 8 of the total: every boundary is within half a tile group's cost of its target, so every run's live work lies within
+// one tile group (ntn tiles x 9 taps) of total / 8.  run[0] = 0 .. run[8] = nwg; returns 8 x the longest run: the workgroups of
+// the whole-tile part (the hardware deals workgroups evenly, so each XCD gets the longest run's count and a workgroup past its
+// own run's end returns at once).  Fewer tile groups than XCDs: some runs are empty.
+constexpr int kXcds = 8;
+inline int pos_balanced_runs(const ConvParams &p, int ntn, long nwg, int run[kXcds + 1]) {
+  const int groups = (int)(nwg / ntn), per_pos = p.N / 64;   // (pos_major_valid: N % 64 == 0, a tile group is one position's 64 frames)
+  int cached_pos = -1, cached_cost = 0;
+  auto cost = [&](int g) {
+    const int pos = g / per_pos;
+    if (pos != cached_pos) {
+      cached_pos = pos;
+      cached_cost = __builtin_popcount(pos_major_tap_mask(pos, p.Wo, p.Hi, p.Wi, p.stride, p.pad));
+    }
+    return cached_cost;
+  };
+  long total = 0;
+  for (int g = 0; g < groups; ++g) total += cost(g);
+  long cum = 0;   // the live taps of the groups [0, g)
+  int g = 0, longest = 0;
+  run[0] = 0;
+  for (int k = 1; k <= kXcds; ++k) {
+    int b = groups;
+    if (k < kXcds) {
+      while (g < groups && cum * kXcds < k * total) cum += cost(g++);
+      b = g;   // the first boundary at or past the target; the one before it when that is closer
+      if (g > 0 && k * total - (cum - cost(g - 1)) * kXcds < cum * kXcds - k * total) b = g - 1;
+    }
+    run[k] = b * ntn;
+    if (run[k] - run[k - 1] > longest) longest = run[k] - run[k - 1];
+  }
+  return kXcds * longest;
+}
+
 // ks in {1, 3, 7}; n_cu sizes the persistent grids (read by the 256p and weight-stationary families only).  A grid past 2^31 - 1
 // workgroups is refused (the products are formed in 64 bits; in 32 they were a signed overflow).
 inline ConvRoute conv_route(const ConvParams &p, int ks, int n_cu) {
@@ -606,6 +653,11 @@ inline ConvRoute conv_route(const ConvParams &p, int ks, int n_cu) {
     r.family = kFamIgemmSeg;
     r.pos_major = p.pos_major != 0 && r.bm == 64 && pos_major_valid(p, ks);   // (anything else: natural order, the same bits)
     grid = p.ksplit == 2 ? p.tail_from + (r.tiles - p.tail_from) * conv_num_segments(p) : r.tiles * (p.ksplit ? conv_num_segments(p) : 1);
+    if (r.pos_major && p.pos_balance) {   // live-balanced runs: the whole part grows to 8 x the longest run, the pieces follow it
+      const long whole = p.ksplit == 2 ? p.tail_from : r.tiles;
+      r.pos_whole = pos_balanced_runs(p, r.ntn, whole, r.pos_run);
+      grid += r.pos_whole - whole;
+    }
   } else {
     r.family = kFamIgemm;
   }

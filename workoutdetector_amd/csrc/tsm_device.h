@@ -179,6 +179,13 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
     hipLaunchKernelGGL(kern, __VA_ARGS__);                           \
   } while (0)
 
+// ... and with a bracket about its grid in the trace line (note_launch's `mark`; NULL: none)
+#define TSM_KLAUNCH_WALK_MARK(rev, mark, kern, ...)                          \
+  do {                                                                       \
+    ::tsm::note_launch(#kern, __PRETTY_FUNCTION__, (rev) ? 1 : 0, (mark));   \
+    hipLaunchKernelGGL(kern, __VA_ARGS__);                                   \
+  } while (0)
+
 inline unsigned grid_for(int64_t total, int cap) {
   const int64_t blocks = (total + 255) / 256;
   return (unsigned)(blocks < cap ? (blocks > 0 ? blocks : 1) : cap);

@@ -258,6 +258,7 @@ struct tsm_engine {
   int fuse31 = -1;       // TSM_FUSE_C3C1: the same for conv3 of block b + shift + conv1 of block b + 1 as one launch (bf16, layer2)
   int fuse_front = -1;   // TSM_FUSE_FRONT: the same for shift + conv1 + the stride-2 conv2 of layer2.0 as one launch (bf16)
   bool pos_major = true; // TSM_POS_MAJOR=0: the tuner does not offer the position-major 3x3 codes (kCodePosMajor); for the A/B
+  bool pos_balance = true; // TSM_POS_BALANCE=0: position-major launches keep equal-count XCD runs (ConvParams::pos_balance); for the A/B
   bool tile_64x128 = true; // TSM_TILE_64X128=0: the tuner does not offer the 64x128 tile (kTile64x128); for the A/B
   int walk = -1;         // TSM_WALK: 0 / 1 every tile-walking launch walks forward / in reverse; unset: alternate (Forward::next_dir)
   int n_cu = 256;
@@ -662,13 +663,16 @@ bool tail_split_from(const tsm::ConvParams &p, int n_cu, size_t partial_elems, i
 // writes raw segment sums, splitk_reduce adds them in segment order and applies bias / ReLU -- bit-identical to the unsplit
 // launch.  Every output element accumulates its K in the same order whatever the tiling, so codes are bit-neutral.
 // `partial` holds `partial_elems` floats of segment sums (the engine's split-K scratch; the per-op entry point's own).
-hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial, size_t partial_elems, int n_cu, hipStream_t s) {
+// `pos_balance`: position-major launches run live-balanced XCD runs (tsm_conv_rules.h::pos_balanced_runs; the same bits either way).
+hipError_t launch_conv_code(tsm::ConvParams p, int ks, int code, float *partial, size_t partial_elems, int n_cu, hipStream_t s,
+                            bool pos_balance = true) {
   p.tile = code & kCodeTileMask;
   // kCodePosMajor: position-major rows, honoured only where pos_major_valid holds for THIS launch (whole-K or with the tail
   // split; never with kCodeSplitK); anywhere else the bit is ignored and the natural order runs (same bits).
   const bool pos_major = (code & kCodePosMajor) && !(code & kCodeSplitK) && (code & kCodeTileMask) == tsm::kTile64x64 &&
                          tsm::pos_major_valid(p, ks);
   p.pos_major = pos_major ? 1 : 0;
+  p.pos_balance = pos_major && pos_balance ? 1 : 0;
   // A cached code may come from a smaller batch of the same bucket: the scratch-size condition is re-checked on
   // EVERY launch (falling back to the whole-K form, which gives the same bits).
   if ((code & kCodeSplitK) && p.kseg_len > 0 &&
@@ -947,7 +951,7 @@ struct Forward {
 };
 
 hipError_t Forward::launch_code(tsm::ConvParams p, int ks, int code) {
-  return launch_conv_code(p, ks, code, e->d_partial, e->partial_elems, e->n_cu, s);
+  return launch_conv_code(p, ks, code, e->d_partial, e->partial_elems, e->n_cu, s, e->pos_balance);
 }
 
 // One conv launch.  Steady forward: the layer's tuned code, trusted only after it has been checked against THIS layer --
@@ -2014,6 +2018,7 @@ int tsm_create(const tsm_config *cfg, tsm_engine **out) {
   env_read("TSM_CONV_TILE", &e->force_tile, tsm::conv_tile_from_name);
   env_read("TSM_CONV_CODE", &e->force_code, atoi);
   env_read("TSM_POS_MAJOR", &e->pos_major, on);
+  env_read("TSM_POS_BALANCE", &e->pos_balance, on);
   env_read("TSM_TILE_64X128", &e->tile_64x128, on);
   env_read("TSM_FUSE_CONV23", &e->fuse23, on);
   env_read("TSM_FUSE_BLOCK", &e->fuse_block, on);
@@ -2583,12 +2588,12 @@ int tsm_conv_op(const tsm_conv_args *a, void *stream) {
     if ((rc = scratch.alloc(&d_part, "d_part", part_elems, out_frame))) return rc;
   }
   // (a test / debug entry point that packs weights and allocates on every call: its tuning hook is read per call)
-  const char *sd_env = getenv("TSM_STEM_DIRECT");
+  const char *sd_env = getenv("TSM_STEM_DIRECT"), *pb_env = getenv("TSM_POS_BALANCE");
   hipError_t st;
   if (pl.stem && x3 && cout == 64 && !(sd_env && atoi(sd_env) == 0))
     st = tsm::launch_stem_direct(xin, c.d_w, c.d_b, yout, n, hi, wi, c.kp, a->relu != 0, prec, s);
   else
-    st = launch_conv_code(p, a->k, code, d_part, part_elems, n_cu, s);
+    st = launch_conv_code(p, a->k, code, d_part, part_elems, n_cu, s, !(pb_env && atoi(pb_env) == 0));
   if (st == hipSuccess && x3) st = tsm::launch_to_f32(d_ys, a->y, (int64_t)out_elems / 8, prec, s);
   const hipError_t st2 = hipStreamSynchronize(s);
   if (st != hipSuccess) return op_status("launch_conv", st);

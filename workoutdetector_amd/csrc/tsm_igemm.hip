@@ -120,18 +120,34 @@ conv_igemm(const ConvParams p) {
   // contiguous run of tiles, n fastest, so co-resident blocks re-use the same A panel from L2.
   const int bid = blockIdx.x;
   const bool tail_mode = SEG && p.ksplit == 2;            // whole tiles first, then (tile, segment) pieces of the last rows of tiles
-  const bool in_tail = tail_mode && bid >= p.tail_from;
-  const int nwg = tail_mode ? p.tail_from : (int)gridDim.x;   // (the remap covers the whole tiles; the pieces go round-robin over the XCDs)
+  // POSM with live-balanced runs (ConvParams::pos_whole > 0, pos_balanced_runs): XCD x owns the whole tiles pos_run[x] ..
+  // pos_run[x + 1], the whole part of the grid is pos_whole = 8 x the longest run, and the tail's pieces follow THAT.
+  bool balanced = false;
+  if constexpr (POSM) balanced = p.pos_whole > 0;
+  const int whole = balanced ? p.pos_whole : p.tail_from;   // tail mode: the workgroups in front of the pieces
+  const bool in_tail = tail_mode && bid >= whole;
+  const int nwg = tail_mode ? p.tail_from : balanced ? p.ntm * p.ntn : (int)gridDim.x;   // (the remap covers the whole tiles; the pieces go round-robin over the XCDs)
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
   int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  if (p.reverse) tile = nwg - 1 - tile;   // walk the tiles from the far end (ConvParams::reverse)
+  bool mirror = p.reverse != 0;   // walk the tiles from the far end (ConvParams::reverse)
+  if constexpr (POSM) {
+    if (balanced && !in_tail) {
+      // A reverse walk gives XCD x run 7 - x from its end: the mirror image of the forward walk as a whole, and each XCD still
+      // holds one balanced run (the mirror image of its own run need not be one: a tail split or stride 2 make the costs lopsided).
+      const int run = p.reverse ? 7 - xcd : xcd, first = p.pos_run[run], len = p.pos_run[run + 1] - first, idx = bid >> 3;
+      if (idx >= len) return;   // past this XCD's run: before any load or barrier, the whole workgroup alike
+      tile = p.reverse ? first + len - 1 - idx : first + idx;
+      mirror = false;
+    }
+  }
+  if (mirror) tile = nwg - 1 - tile;
   int seg = 0;  // SEG + ksplit = 1: the grid holds ntm * ntn tiles per K segment, segment-major
   if (SEG && p.ksplit == 1) {
     seg = tile / (p.ntm * p.ntn);
     tile -= seg * (p.ntm * p.ntn);
   }
   if (in_tail) {
-    const int u = bid - p.tail_from, n_tail = p.ntm * p.ntn - p.tail_from;
+    const int u = bid - whole, n_tail = p.ntm * p.ntn - p.tail_from;
     seg = u / n_tail;
     tile = p.tail_from + (u - seg * n_tail);
   }
@@ -952,7 +968,11 @@ static hipError_t launch_conv_seg(const ConvParams &p, const ConvRoute &r, hipSt
     }
     if constexpr (BM == 64 && WGM == 2 && KS == 3 && !SHIFT) {
       if (r.pos_major) {   // position-major rows (ConvParams::pos_major where pos_major_valid holds)
-        TSM_KLAUNCH_WALK(p.reverse, (conv_igemm<64, 64, 2, 2, 3, false, false, kPrecF32 | kPrecPosMajor, false, true>), grid, block, 0, s, p);
+        // the trace line says when the launch runs live-balanced XCD runs, and on what grid: the route's, as the kernel gets it
+        char mark[48];
+        snprintf(mark, sizeof mark, " [balanced %d/%ld]", p.pos_whole, p.ksplit == 2 ? (long)p.tail_from : r.tiles);
+        TSM_KLAUNCH_WALK_MARK(p.reverse, p.pos_whole > 0 ? mark : nullptr,
+                              (conv_igemm<64, 64, 2, 2, 3, false, false, kPrecF32 | kPrecPosMajor, false, true>), grid, block, 0, s, p);
         return hipGetLastError();
       }
     }
@@ -1008,6 +1028,8 @@ hipError_t launch_conv(const ConvParams &p_in, int ks, hipStream_t s) {
   if (di && di->status != hipSuccess) return di->status;
   ConvParams p = p_in;
   p.ntm = r.ntm; p.ntn = r.ntn;
+  p.pos_whole = r.pos_whole;   // (0 unless the route runs live-balanced position-major runs)
+  for (int k = 0; k <= kXcds; ++k) p.pos_run[k] = r.pos_run[k];
   if (r.family == kFamBf16_256 || r.family == kFamBf16_256p) return launch_conv_bf16_256(p, r, s);
   if (r.family >= kFamWs3x3) return launch_conv_ws(p, r, s);
   if (p.ksplit == 2 && !p.ypart) return hipErrorInvalidValue;   // (the tail split's segment sums)

@@ -239,7 +239,9 @@ hipError_t launch_scores_to_states(const float *logits, int n, int c, int softma
 
 // Launch trace of the calling thread (tsm_trace_launches / tsm_launch_trace in include/tsm_hip.h; tsm_ops.hip).
 // reverse: -1 for a kernel without a tile walk; 0 / 1 the direction of one that has one (1 appends " [reverse]")
-void note_launch(const char *kernel, const char *where, int reverse = -1);
+// mark: a bracket about the launch's grid, in front of the direction's (" [balanced 1792/1280]": live-balanced XCD runs,
+// workgroups of the whole part / whole tiles), so that a line still ends as it did
+void note_launch(const char *kernel, const char *where, int reverse = -1, const char *mark = nullptr);
 void trace_launches(bool on);
 const char *launch_trace();   // newline-separated, valid until the thread's next trace call
 

@@ -1585,7 +1585,7 @@ struct LaunchTrace {
 thread_local LaunchTrace g_trace;
 }  // namespace
 
-void note_launch(const char *kernel, const char *where, int reverse) {
+void note_launch(const char *kernel, const char *where, int reverse, const char *mark) {
   if (!g_trace.on) return;
   // "(conv_igemm<BM, BN, ...>)" as the launch site spells it; inside a template the enclosing function's
   // "[BM = 64, BN = 64, ...]" (clang's __PRETTY_FUNCTION__) resolves the names
@@ -1594,6 +1594,7 @@ void note_launch(const char *kernel, const char *where, int reverse) {
   const char *with = where ? strstr(where, " [") : nullptr;
   g_trace.text += k;
   if (with) g_trace.text += with;
+  if (mark) g_trace.text += mark;
   if (reverse > 0) g_trace.text += " [reverse]";
   g_trace.text += '\n';
 }

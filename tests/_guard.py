@@ -91,6 +91,16 @@ def guarded(t, fill=POISON, name='operand'):
     return view
 
 
+def guarded_repeat(small, reps, fill=POISON, name='operand'):
+    """guarded(small.repeat(reps, 1, ...)), the periods written into the guarded view itself: a multi-GiB periodic operand
+    (tests/_big_cases.py) exists once, not as a tensor and its guarded copy."""
+    small = small.contiguous()
+    view = _make((small.shape[0] * reps,) + tuple(small.shape[1:]), small.dtype, small.device, fill, name, False)
+    g = view._guard
+    g.base[g.lead: g.lead + g.nbytes].view(small.dtype).view(reps, -1).copy_(small.reshape(1, -1).expand(reps, -1))
+    return view
+
+
 def guarded_out(shape, dtype=torch.float32, device='cuda', fill=POISON, name='out'):
     """An output between two bands, the payload poisoned too: whatever the kernel does not write stays POISON."""
     return _make(shape, dtype, device, fill, name, True)

@@ -67,6 +67,23 @@ def torch_equal(a, b):
     return torch.equal(a, b)
 
 
+def assert_periodic(y, reps, what):
+    """y (a contiguous device tensor of 4-byte elements) is `reps` equal periods, compared as int32 words so that NaN poison
+    cannot equal itself; returns the words as [reps, period].  On failure: the first period that differs and where."""
+    import torch
+    words = y.view(torch.int32).view(reps, -1)
+    if torch.equal(words[1:], words[:-1]):
+        return words
+    for r in range(1, reps):           # (only on failure: name the first period that differs and where)
+        bad = words[r] != words[0]
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            raise AssertionError(f'{what}: period {r} of {reps} differs from period 0 in {int(bad.sum())} of {bad.numel()} words, '
+                                 f'first at word {i} of the period (byte offset {(r * bad.numel() + i) * 4:#x} of y): '
+                                 f'{int(words[r, i]) & 0xFFFFFFFF:#010x} vs {int(words[0, i]) & 0xFFFFFFFF:#010x}')
+    raise AssertionError(f'{what}: periods differ')
+
+
 def assert_ran(trace, prefix, what=''):
     assert trace.ran(prefix), f'{what}: no `{prefix}` launch; the trace holds {sorted(set(trace.kernels))}'
 

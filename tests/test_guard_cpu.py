@@ -4,7 +4,8 @@ is wanted: the bands are there so that a stray access lands in owned memory.)"""
 import pytest
 import torch
 
-from tests._guard import (ALIGN, MIN_BAND, POISON, GuardError, band_bytes, check, fill_word, guarded, guarded_out, where)
+from tests._guard import (ALIGN, MIN_BAND, POISON, GuardError, band_bytes, check, fill_word, guarded, guarded_out, guarded_repeat,
+                          where)
 
 SHAPE = (3, 5, 7, 8)     # frames, rows, cols, channels
 
@@ -48,6 +49,20 @@ def test_layout_of_a_guarded_tensor():
     words, at = _flat_with_bands(inf)
     assert bool(torch.isposinf(words[:at]).all()) and bool(torch.isposinf(words[at + inf.numel():]).all())
     check(inf)
+
+
+def test_a_periodic_operand_equals_the_guarded_repeat():
+    """guarded_repeat(small, R) is guarded(small.repeat(R, ...)): same payload, same bands, written in place."""
+    small = torch.arange(2 * 3 * 5 * 4, dtype=torch.float32).reshape(2, 3, 5, 4)
+    a, b = guarded_repeat(small, 7, name='x'), guarded(small.repeat(7, 1, 1, 1), name='x')
+    assert a.shape == b.shape == (14, 3, 5, 4) and torch.equal(a, b) and torch.equal(a._guard.base, b._guard.base)
+    check(a)
+    inf = guarded_repeat(small, 3, fill=float('inf'))
+    words, at = _flat_with_bands(inf)
+    assert bool(torch.isposinf(words[:at]).all()) and bool(torch.isposinf(words[at + inf.numel():]).all())
+    a._guard.base.view(torch.float32)[a._guard.lead // 4 - 1] = 1.0
+    with pytest.raises(GuardError):
+        check(a)
 
 
 def test_a_correct_kernel_passes():

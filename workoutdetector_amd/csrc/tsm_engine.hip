@@ -1,7 +1,9 @@
 // Host engine + C ABI (include/tsm_hip.h) for the TSM-ResNet clip forward on MI355X (ResNet-50 by default; ResNet-18 / 34
 // through tsm_set_backbone; the shift in front of conv1 by default, in front of the whole block through tsm_set_shift_place),
-// for the ConvNeXt-Base image model through tsm_set_convnext (build_convnext_topology, run_convnext, finalize_convnext), and for
-// TDN-ResNet50 through tsm_set_tdn (build_tdn_topology, run_tdn, finalize_tdn).
+// for the ConvNeXt-Base image model through tsm_set_convnext (build_convnext_topology, run_convnext), and for TDN-ResNet50
+// through tsm_set_tdn (build_tdn_topology, run_tdn).  Construction is one path for all of them: the topology builders spell
+// every tensor once into the engine's manifest (build_manifest), tsm_set_tensor accepts what the manifest names, and
+// tsm_finalize checks the manifest, packs every conv by its kind, and allocates the workspace (alloc_workspace).
 //
 // Owns: packed weights (BatchNorm folded, K-major), an NHWC fp32 activation workspace sized for
 // max_clips, one HIP stream, two timing events.  The forward is a fixed schedule of kernel launches
@@ -66,21 +68,37 @@ struct HostTensor {
   std::vector<int64_t> shape;
 };
 
+// Which tensors a conv layer reads and how tsm_finalize packs them (build_manifest, pack_conv); wkey = "<name>.weight", a conv
+// bias is "<name>.bias" beside it.
+enum class ConvKind {
+  kBn,         // [cout, cin, k, k] + the BatchNorm `bnp`
+  kNlQkv,      // a non-local block's theta | phi | g as one 1x1 conv: three [cout / 3, cin, 1, 1, 1] with a bias, no BatchNorm
+  kNlW,        // its W: "<nlp>.W.0" [cout, cin, 1, 1, 1] with a bias + the BatchNorm "<nlp>.W.1"
+  kCnxStem,    // a ConvNeXt engine's GEMMs, all with a bias and no BatchNorm: the stem [cout, 3, 4, 4],
+  kCnxDown,    // a downsample [cout, cout / 2, 2, 2],
+  kCnxFc1,     // fc1 [cout, cin]
+  kCnxFc2,     // and fc2 [cout, cin] with the block's gamma folded in
+  kTdnBias,    // a TDN engine's conv with a bias in front of its BatchNorm, folded into the BatchNorm's mean
+  kTdnConv15,  // conv1_5 [64, 12, 7, 7] (no bias) + BatchNorm, as a 1x1 GEMM over the front end's patch rows
+};
+
 struct ConvLayer : LayerGeom {   // cp, kp, kseg: tsm_host_util.h, layer_geometry
   std::string wkey, bnp;
   int cin = 0, cout = 0, k = 1, stride = 1;
-  // non-local block convs, both with a conv bias: 1 = theta | phi | g as one 1x1 conv (wkey = "<nlp>.theta.weight", no BatchNorm),
-  // 2 = W ("<nlp>.W.0.weight", BatchNorm "<nlp>.W.1"); nlp = "base_model.layerL.B.nl"
-  int nl = 0;
-  std::string nlp;
-  // a ConvNeXt engine's GEMMs, all with a conv bias and no BatchNorm (wkey = "<name>.weight", bias "<name>.bias"): 1 = the stem
-  // [cout, 3, 4, 4], 2 = a downsample [cout, cout / 2, 2, 2], 3 = fc1 [cout, cin], 4 = fc2 [cout, cin] with the block's gamma folded in
-  int cnx = 0;
-  std::string gkey;   // (4) the block's "gamma"
-  // a TDN engine's convs: 1 = a conv with a bias ("<name>.bias" beside wkey's "<name>.weight") in front of its BatchNorm, folded
-  // into the BatchNorm's mean; 2 = conv1_5 [64, 12, 7, 7] (no bias) as a 1x1 GEMM over the front end's patch rows
-  int tdn = 0;
+  ConvKind kind = ConvKind::kBn;
+  std::string nlp;    // (kNlQkv, kNlW) "base_model.layerL.B.nl"
+  std::string gkey;   // (kCnxFc2) the block's "gamma"
   float *d_w = nullptr, *d_b = nullptr;
+};
+
+// One tensor of the engine's manifest (build_manifest): what tsm_set_tensor accepts under this key and its other spellings,
+// and what tsm_finalize requires of it.
+struct TensorSpec {
+  std::string key;
+  std::vector<int64_t> shape;
+  std::string missing, mismatch;   // tsm_finalize's refusal when it is absent / has another shape
+  bool joins = false;              // checked together with the entry in front of it: all absences of the group first, then the shapes
+  bool ignored = false;            // accepted, never read (".num_batches_tracked", TDN's "conv1_temp")
 };
 
 struct Block {
@@ -131,6 +149,7 @@ struct CnxNorm {
 struct CnxBlock {
   int c = 0, fc1 = -1, fc2 = -1;   // width; indices into convs
   std::string name;                // "stages.S.blocks.B"
+  std::string dwkey;               // "<name>.conv_dw": "<dwkey>.weight" [c, 1, 7, 7] / "<dwkey>.bias"
   CnxNorm norm;
   float *d_dw = nullptr, *d_dwb = nullptr;   // conv_dw [49][c] (cnx_pack_dw) and its bias
 };
@@ -219,6 +238,7 @@ struct tsm_engine {
   int prec = tsm::kPrecF32;
   float *d_tap = nullptr;     // fp32 staging for tsm_forward_tap on split-format engines
   std::map<std::string, HostTensor> tensors;
+  std::vector<TensorSpec> manifest;   // every tensor of this topology (build_manifest), in the order tsm_finalize checks them
   std::vector<ConvLayer> convs;
   std::vector<Block> blocks;
   float *d_fcw = nullptr, *d_fcb = nullptr;
@@ -284,8 +304,10 @@ int fail(tsm_engine *e, int code, const std::string &msg) {
   } while (0)
 
 // Appends a conv layer in its packed geometry; returns its index.  `segmented` = false keeps a long-K fp32 layer whole-K.
-int add_conv(tsm_engine *e, const std::string &wkey, const std::string &bnp, int cin, int cout, int k, int stride, bool segmented) {
+int add_conv(tsm_engine *e, const std::string &wkey, const std::string &bnp, int cin, int cout, int k, int stride, bool segmented,
+             ConvKind kind = ConvKind::kBn) {
   ConvLayer c;
+  c.kind = kind;
   static_cast<LayerGeom &>(c) = layer_geometry(cin, k, stride, e->prec);
   if (!segmented) c.kseg = 0;
   c.wkey = wkey; c.bnp = bnp; c.cin = cin; c.cout = cout; c.k = k; c.stride = stride;
@@ -301,7 +323,7 @@ void build_convnext_topology(tsm_engine *e) {
   e->blocks.clear();
   e->cnx_blocks.clear();
   auto norm = [](const std::string &key, int c) { CnxNorm n; n.key = key; n.c = c; return n; };
-  e->convs[add_conv(e, "stem.0.weight", "", kCnxStemK, kCnxWidths[0], 1, 1, true)].cnx = 1;
+  add_conv(e, "stem.0.weight", "", kCnxStemK, kCnxWidths[0], 1, 1, true, ConvKind::kCnxStem);
   e->cnx_stem_norm = norm("stem.1", kCnxWidths[0]);
   for (int s = 0; s < kCnxStages; ++s) {
     const int c = kCnxWidths[s];
@@ -310,8 +332,7 @@ void build_convnext_topology(tsm_engine *e) {
     st = CnxStage();
     if (s > 0) {
       st.norm = norm(sp + ".downsample.0", c / 2);
-      st.down = add_conv(e, sp + ".downsample.1.weight", "", 4 * (c / 2), c, 1, 1, true);
-      e->convs[st.down].cnx = 2;
+      st.down = add_conv(e, sp + ".downsample.1.weight", "", 4 * (c / 2), c, 1, 1, true, ConvKind::kCnxDown);
     }
     st.first = (int)e->cnx_blocks.size();
     st.count = e->cnx_depths[s];
@@ -319,11 +340,10 @@ void build_convnext_topology(tsm_engine *e) {
       CnxBlock blk;
       blk.c = c;
       blk.name = sp + ".blocks." + std::to_string(b);
+      blk.dwkey = blk.name + ".conv_dw";
       blk.norm = norm(blk.name + ".norm", c);
-      blk.fc1 = add_conv(e, blk.name + ".mlp.fc1.weight", "", c, 4 * c, 1, 1, true);
-      blk.fc2 = add_conv(e, blk.name + ".mlp.fc2.weight", "", 4 * c, c, 1, 1, false);
-      e->convs[blk.fc1].cnx = 3;
-      e->convs[blk.fc2].cnx = 4;
+      blk.fc1 = add_conv(e, blk.name + ".mlp.fc1.weight", "", c, 4 * c, 1, 1, true, ConvKind::kCnxFc1);
+      blk.fc2 = add_conv(e, blk.name + ".mlp.fc2.weight", "", 4 * c, c, 1, 1, false, ConvKind::kCnxFc2);
       e->convs[blk.fc2].gkey = blk.name + ".gamma";
       e->cnx_blocks.push_back(blk);
     }
@@ -340,8 +360,9 @@ void build_tdn_topology(tsm_engine *e) {
   e->convs.clear();
   e->blocks.clear();
   e->tdn_mse.clear();
-  e->convs[add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false)].tdn = 1;
-  e->convs[add_conv(e, "base_model.conv1_5.0.weight", "base_model.conv1_5.1", kTdnPatchK, 64, 1, 1, true)].tdn = 2;
+  const ConvKind kb = ConvKind::kTdnBias;
+  add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false, kb);
+  add_conv(e, "base_model.conv1_5.0.weight", "base_model.conv1_5.1", kTdnPatchK, 64, 1, 1, true, ConvKind::kTdnConv15);
   for (int li = -1; li < 4; ++li) {   // -1: resnext_layer1
     const int stage = li < 0 ? 0 : li, planes = kPlanes[stage], cout = 4 * planes;
     int cin = stage == 0 ? 64 : 4 * kPlanes[stage - 1];
@@ -354,12 +375,10 @@ void build_tdn_topology(tsm_engine *e) {
       blk.T = e->cfg.num_segments;
       blk.name = blk.out_name = lname + "." + std::to_string(b);
       blk.diff_path = li < 0;
-      blk.conv1 = add_conv(e, p + ".conv1.weight", p + ".bn1", cin, planes, 1, 1, true);
-      blk.conv2 = add_conv(e, p + ".conv2.weight", p + ".bn2", planes, planes, 3, stride, true);
-      blk.conv3 = add_conv(e, p + ".conv3.weight", p + ".bn3", planes, cout, 1, 1, false);
-      blk.down = b == 0 ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false) : -1;
-      for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down})
-        if (ci >= 0) e->convs[ci].tdn = 1;
+      blk.conv1 = add_conv(e, p + ".conv1.weight", p + ".bn1", cin, planes, 1, 1, true, kb);
+      blk.conv2 = add_conv(e, p + ".conv2.weight", p + ".bn2", planes, planes, 3, stride, true, kb);
+      blk.conv3 = add_conv(e, p + ".conv3.weight", p + ".bn3", planes, cout, 1, 1, false, kb);
+      blk.down = b == 0 ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false, kb) : -1;
       if (li >= 1) {
         TdnMse m;
         m.c = planes;
@@ -374,9 +393,7 @@ void build_tdn_topology(tsm_engine *e) {
   e->feat = 4 * kPlanes[3];
 }
 
-void build_topology(tsm_engine *e) {
-  if (e->convnext) return build_convnext_topology(e);
-  if (e->tdn) return build_tdn_topology(e);
+void build_resnet_topology(tsm_engine *e) {
   e->convs.clear();
   e->blocks.clear();
   add_conv(e, "base_model.conv1.weight", "base_model.bn1", 3, 64, 7, 2, false);
@@ -415,10 +432,8 @@ void build_topology(tsm_engine *e) {
       blk.down = down ? add_conv(e, p + ".downsample.0.weight", p + ".downsample.1", cin, cout, 1, stride, false) : -1;
       blk.out_name = blk.name + (nl ? ".block" : "");
       if (nl) {   // theta | phi | g: cout -> 3 * cout / 2 (bias, no BN, no ReLU); W: cout / 2 -> cout (bias + BN, + x, no ReLU)
-        blk.nl_qkv = add_conv(e, lb + ".nl.theta.weight", "", cout, 3 * (cout / 2), 1, 1, false);
-        blk.nl_w = add_conv(e, lb + ".nl.W.0.weight", lb + ".nl.W.1", cout / 2, cout, 1, 1, false);
-        e->convs[blk.nl_qkv].nl = 1;
-        e->convs[blk.nl_w].nl = 2;
+        blk.nl_qkv = add_conv(e, lb + ".nl.theta.weight", "", cout, 3 * (cout / 2), 1, 1, false, ConvKind::kNlQkv);
+        blk.nl_w = add_conv(e, lb + ".nl.W.0.weight", lb + ".nl.W.1", cout / 2, cout, 1, 1, false, ConvKind::kNlW);
         e->convs[blk.nl_qkv].nlp = e->convs[blk.nl_w].nlp = lb + ".nl";
       }
       e->blocks.push_back(blk);
@@ -428,14 +443,14 @@ void build_topology(tsm_engine *e) {
   e->feat = kPlanes[3] * expansion;
 }
 
-// The un-wrapped spelling of an engine key, also accepted: TemporalShift wraps conv1 as ".conv1.net.weight" (blockres) or the
-// whole block as "layerL.B.net.<name>" (block placement); "" when the key has no wrapper.
 // The spelling of an engine key without the non-local wrapper's ".block" ("" when it has none).
 std::string without_block(const std::string &key) {
   const size_t at = key.find(".block.");
   return at == std::string::npos ? "" : key.substr(0, at) + key.substr(at + 6);
 }
 
+// The un-wrapped spelling of an engine key, also accepted: TemporalShift wraps conv1 as ".conv1.net.weight" (blockres) or the
+// whole block as "layerL.B.net.<name>" (block placement); "" when the key has no wrapper.
 std::string unwrapped(const tsm_engine *e, const std::string &key) {
   if (e->place == 1) {
     const size_t at = key.find(".net.");
@@ -454,78 +469,156 @@ std::string pool_wrapped(const tsm_engine *e, const std::string &key) {
   return e->temporal_pool && key.compare(0, stage.size(), stage) == 0 ? stage + "net." + key.substr(stage.size()) : "";
 }
 
+// f(spelling) for an engine key and every other spelling of it a checkpoint may use -- without the shift wrapper, without the
+// non-local wrapper, without both; the key and its unwrapped form under the temporal pool's wrapper -- in this order, until one
+// call returns true.
+template <class F>
+bool spellings(const tsm_engine *e, const std::string &key, F f) {
+  if (f(key)) return true;
+  const std::string uw = unwrapped(e, key), nb = without_block(key), both = nb.empty() ? nb : unwrapped(e, nb);
+  const std::string pooled = pool_wrapped(e, key), pooled_uw = pool_wrapped(e, uw);
+  for (const std::string *alt : {&uw, &nb, &both, &pooled, &pooled_uw})
+    if (!alt->empty() && f(*alt)) return true;
+  return false;
+}
+
 const HostTensor *find_tensor(const tsm_engine *e, const std::string &key) {
-  auto it = e->tensors.find(key);
-  if (it != e->tensors.end()) return &it->second;
-  // (every spelling: without the shift wrapper, without the non-local wrapper, without both; each under the temporal pool's wrapper)
-  const std::string nb = without_block(key), uw = unwrapped(e, key);
-  for (const std::string &alt : {uw, nb, nb.empty() ? nb : unwrapped(e, nb), pool_wrapped(e, key), pool_wrapped(e, uw)}) {
-    if (alt.empty()) continue;
-    it = e->tensors.find(alt);
-    if (it != e->tensors.end()) return &it->second;
-  }
-  return nullptr;
+  const HostTensor *hit = nullptr;
+  spellings(e, key, [&](const std::string &s) {
+    const auto it = e->tensors.find(s);
+    if (it != e->tensors.end()) hit = &it->second;
+    return hit != nullptr;
+  });
+  return hit;
 }
 
-// A ConvNeXt engine's tensors: timm's keys as they are ("head.fc.*" is the classifier).
-bool known_convnext_name(const tsm_engine *e, const std::string &name) {
-  if (name == "head.fc.weight" || name == "head.fc.bias") return true;
-  auto is_norm = [&](const CnxNorm &n) { return !n.key.empty() && (name == n.key + ".weight" || name == n.key + ".bias"); };
-  if (is_norm(e->cnx_stem_norm) || is_norm(e->cnx_head_norm)) return true;
-  for (const CnxStage &st : e->cnx_stages)
-    if (is_norm(st.norm)) return true;
-  for (const CnxBlock &b : e->cnx_blocks)
-    if (is_norm(b.norm) || name == b.name + ".conv_dw.weight" || name == b.name + ".conv_dw.bias") return true;
-  for (const ConvLayer &c : e->convs)
-    if (name == c.wkey || name == c.wkey.substr(0, c.wkey.size() - 6) + "bias" || (!c.gkey.empty() && name == c.gkey)) return true;
-  return false;
-}
+// The values of a manifest tensor, behind tsm_finalize's check_tensors: it is there, in its shape.
+const std::vector<float> &tensor(const tsm_engine *e, const std::string &key) { return find_tensor(e, key)->data; }
 
-// A TDN engine's tensors: the TSN module's keys as they are ("new_fc.*" is the classifier; "base_model.conv1_temp.*" is in every
-// checkpoint and unused by the forward: accepted, then ignored).
-const char *const kBnSuffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
-const char *const kTdnMseConvs[] = {".mse.conv1.weight", ".mse.conv2.weight", ".mse.conv3.weight", ".mse.conv3_smallscale2.weight",
-                                    ".mse.conv3_smallscale4.weight", ".shift.conv.weight"};
-const char *const kTdnMseBns[] = {".mse.bn1", ".mse.bn3", ".mse.bn3_smallscale2", ".mse.bn3_smallscale4"};
-bool known_tdn_name(const tsm_engine *e, const std::string &name) {
-  if (name == "new_fc.weight" || name == "new_fc.bias" || name == "base_model.conv1_temp.weight" || name == "base_model.conv1_temp.bias") return true;
-  for (const ConvLayer &c : e->convs) {
-    if (name == c.wkey || (c.tdn == 1 && name == c.wkey.substr(0, c.wkey.size() - 6) + "bias")) return true;
-    for (const char *s : kBnSuffix)
-      if (name == c.bnp + s) return true;
-  }
-  for (const TdnMse &m : e->tdn_mse) {
-    for (const char *s : kTdnMseConvs)
-      if (name == m.key + s) return true;
-    for (const char *bn : kTdnMseBns)
-      for (const char *s : kBnSuffix)
-        if (name == m.key + bn + s) return true;
-  }
-  return false;
-}
-
+// What tsm_set_tensor accepts: a manifest key in any of its spellings.
 bool known_name(const tsm_engine *e, const std::string &name) {
-  if (e->convnext) return known_convnext_name(e, name);
-  if (e->tdn) return known_tdn_name(e, name);
-  if (name == "fc.weight" || name == "fc.bias") return true;
-  static const char *bn_suffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
-  auto is = [&](const std::string &key) {
-    const std::string nb = without_block(key);
-    if (name == key || name == unwrapped(e, key) || (!nb.empty() && (name == nb || name == unwrapped(e, nb)))) return true;
-    return e->temporal_pool && (name == pool_wrapped(e, key) || name == pool_wrapped(e, unwrapped(e, key)));
+  for (const TensorSpec &t : e->manifest)
+    if (spellings(e, t.key, [&](const std::string &s) { return s == name; })) return true;
+  return false;
+}
+
+// Key suffixes that more than one place needs.  A BatchNorm `bnp`: its four vectors, then the counter checkpoints carry.
+const char *const kBnSuffix[] = {".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked"};
+// A non-local block `nlp`: the three convs that make the theta | phi | g conv, in its row order.
+const char *const kNlQkv[3] = {".theta", ".phi.0", ".g.0"};
+// A TDN long-term module `key`: its five convs and the temporal conv, then its BatchNorms (tdn_pack_mse's argument order).
+enum { kMseConv1, kMseConv2, kMseConv3, kMseSmall2, kMseSmall4, kMseTemporal, kMseConvs };
+const char *const kTdnMseConvs[kMseConvs] = {".mse.conv1.weight", ".mse.conv2.weight", ".mse.conv3.weight", ".mse.conv3_smallscale2.weight",
+                                             ".mse.conv3_smallscale4.weight", ".shift.conv.weight"};
+enum { kMseBn1, kMseBnSmall2, kMseBnSmall4, kMseBn3, kMseBns };
+const char *const kTdnMseBns[kMseBns] = {".mse.bn1", ".mse.bn3_smallscale2", ".mse.bn3_smallscale4", ".mse.bn3"};
+
+std::string bias_key(const std::string &wkey) { return wkey.substr(0, wkey.size() - 6) + "bias"; }   // "<name>.bias" of "<name>.weight"
+const char *head_prefix(const tsm_engine *e) { return e->convnext ? "head.fc" : e->tdn ? "new_fc" : "fc"; }   // the classifier
+
+// The engine's tensor manifest, from its topology: per conv by kind, then the family's other tensors, then the classifier --
+// the order in which tsm_finalize reports a defect.  The refusal texts are formed here because they differ by group: a ResNet's
+// BatchNorm and classifier are named as a whole, everything else by its own key.
+void build_manifest(tsm_engine *e) {
+  using Shape = std::vector<int64_t>;
+  std::vector<TensorSpec> &m = e->manifest;
+  m.clear();
+  auto want = [&](const std::string &key, Shape shape, bool joins = false) {
+    m.push_back({key, std::move(shape), "missing " + key, "shape mismatch for " + key, joins, false});
+  };
+  auto want_pair = [&](const std::string &wkey, Shape shape, bool joins = false) {   // "<name>.weight" and "<name>.bias" [shape[0]]
+    want(wkey, shape);
+    want(bias_key(wkey), {shape[0]}, joins);
+  };
+  auto ignore = [&](const std::string &key) { m.push_back({key, {}, "", "", false, true}); };
+  auto want_bn = [&](const std::string &bnp, int c, bool joins, bool as_a_whole) {
+    for (int i = 0; i < 4; ++i) {
+      want(bnp + kBnSuffix[i], {c}, joins);
+      if (as_a_whole) {
+        m.back().missing = "missing BatchNorm tensors of " + bnp;
+        m.back().mismatch = "BN shape mismatch for " + bnp;
+      }
+    }
+    ignore(bnp + kBnSuffix[4]);
   };
   for (const ConvLayer &c : e->convs) {
-    if (c.nl == 1) {
-      for (const char *s : {".theta.weight", ".theta.bias", ".phi.0.weight", ".phi.0.bias", ".g.0.weight", ".g.0.bias"})
-        if (name == c.nlp + s) return true;
-      continue;
+    switch (c.kind) {
+      case ConvKind::kBn:   // (the weight's absence, the BatchNorm's absence, then the shapes)
+        want(c.wkey, {c.cout, c.cin, c.k, c.k});
+        want_bn(c.bnp, c.cout, true, true);
+        break;
+      case ConvKind::kNlQkv:
+        for (const char *part : kNlQkv) want_pair(c.nlp + part + ".weight", {c.cout / 3, c.cin, 1, 1, 1}, true);
+        break;
+      case ConvKind::kNlW:
+        want_bn(c.bnp, c.cout, false, true);
+        want_pair(c.wkey, {c.cout, c.cin, 1, 1, 1}, true);
+        break;
+      case ConvKind::kCnxStem: want_pair(c.wkey, {c.cout, 3, 4, 4}); break;
+      case ConvKind::kCnxDown: want_pair(c.wkey, {c.cout, c.cin / 4, 2, 2}); break;
+      case ConvKind::kCnxFc1: want_pair(c.wkey, {c.cout, c.cin}); break;
+      case ConvKind::kCnxFc2:
+        want_pair(c.wkey, {c.cout, c.cin});
+        want(c.gkey, {c.cout});
+        break;
+      case ConvKind::kTdnBias:
+        want(c.wkey, {c.cout, c.cin, c.k, c.k});
+        want_bn(c.bnp, c.cout, false, false);
+        want(bias_key(c.wkey), {c.cout});
+        break;
+      case ConvKind::kTdnConv15:
+        want(c.wkey, {c.cout, kTdnDiffC, 7, 7});
+        want_bn(c.bnp, c.cout, false, false);
+        break;
     }
-    if (c.nl == 2 && name == c.nlp + ".W.0.bias") return true;
-    if (is(c.wkey)) return true;
-    for (const char *s : bn_suffix)
-      if (is(c.bnp + s)) return true;
   }
-  return false;
+  if (e->convnext) {
+    auto want_norm = [&](const CnxNorm &n) { want_pair(n.key + ".weight", {n.c}); };
+    want_norm(e->cnx_stem_norm);
+    want_norm(e->cnx_head_norm);
+    for (const CnxStage &st : e->cnx_stages)
+      if (st.down >= 0) want_norm(st.norm);
+    for (const CnxBlock &blk : e->cnx_blocks) {
+      want_pair(blk.dwkey + ".weight", {blk.c, 1, 7, 7});
+      want_norm(blk.norm);
+    }
+  }
+  for (const TdnMse &mse : e->tdn_mse) {
+    const int C = mse.c, r = C / kTdnReduction;
+    const Shape conv_shapes[kMseConvs] = {{r, C, 1, 1}, {r, 1, 3, 3}, {C, r, 1, 1}, {r, r, 3, 3}, {r, r, 3, 3}, {C, 1, 3}};
+    for (int i = 0; i < kMseConvs; ++i) want(mse.key + kTdnMseConvs[i], conv_shapes[i]);
+    for (int i = 0; i < kMseBns; ++i) want_bn(mse.key + kTdnMseBns[i], i == kMseBn3 ? C : r, false, false);
+  }
+  if (e->tdn)   // (in every TDN checkpoint, unused by the forward)
+    for (const char *s : {".weight", ".bias"}) ignore(std::string("base_model.conv1_temp") + s);
+  const std::string fc = head_prefix(e);
+  want_pair(fc + ".weight", {e->cfg.num_class, e->feat}, !e->convnext && !e->tdn);
+  if (!e->convnext && !e->tdn)   // (a ResNet's classifier is refused as a pair)
+    for (size_t i = m.size() - 2; i < m.size(); ++i) {
+      m[i].missing = "missing fc.weight / fc.bias";
+      m[i].mismatch = "fc shape mismatch (want [num_class, " + std::to_string(e->feat) + "])";
+    }
+}
+
+void build_topology(tsm_engine *e) {
+  if (e->convnext) build_convnext_topology(e);
+  else if (e->tdn) build_tdn_topology(e);
+  else build_resnet_topology(e);
+  build_manifest(e);
+}
+
+// tsm_finalize's check of the host tensors against the manifest, in its order; within a group every absence before any shape.
+int check_tensors(tsm_engine *e) {
+  const std::vector<TensorSpec> &m = e->manifest;
+  for (size_t first = 0, end; first < m.size(); first = end) {
+    for (end = first + 1; end < m.size() && m[end].joins;) ++end;
+    if (m[first].ignored) continue;
+    for (size_t i = first; i < end; ++i)
+      if (!find_tensor(e, m[i].key)) return fail(e, TSM_ERR_MISSING_TENSOR, m[i].missing);
+    for (size_t i = first; i < end; ++i)
+      if (find_tensor(e, m[i].key)->shape != m[i].shape) return fail(e, TSM_ERR_SHAPE, m[i].mismatch);
+  }
+  return TSM_OK;
 }
 
 int dev_alloc(tsm_engine *e, float **p, size_t elems, const char *name = "weights", size_t frame_elems = 0) {
@@ -1623,83 +1716,101 @@ int refuse_on_convnext(tsm_engine *e, const char *setter) {
   return fail(e, TSM_ERR_UNSUPPORTED, std::string(setter) + ": a ConvNeXt engine (tsm_set_convnext) has no such part");
 }
 
-// tsm_finalize of a ConvNeXt engine: every tensor checked, packed (tsm_host_util.h: cnx_pack_*, cnx_fold_gamma) and uploaded, then
-// the workspace -- the five rotating buffers, each the largest activation of the schedule (fc1's output in stage 0).
-int finalize_convnext(tsm_engine *e) {
-  const tsm_config &cfg = e->cfg;
-  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };
-  auto want = [e](const std::string &key, const std::vector<int64_t> &shape, const HostTensor **t) {
-    *t = find_tensor(e, key);
-    if (!*t) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + key);
-    if ((*t)->shape != shape) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + key);
-    return (int)TSM_OK;
-  };
-  auto upload_norm = [&](CnxNorm &n) {
-    const HostTensor *w, *b;
-    if (int rc = want(n.key + ".weight", {n.c}, &w)) return rc;
-    if (int rc = want(n.key + ".bias", {n.c}, &b)) return rc;
-    if (int rc = upload(e, alloc, &n.d_w, "ln_w", w->data)) return rc;
-    return upload(e, alloc, &n.d_b, "ln_b", b->data);
-  };
-  for (ConvLayer &c : e->convs) {
-    const std::string base = c.wkey.substr(0, c.wkey.size() - 7);   // without ".weight"
-    const HostTensor *w, *b, *g = nullptr;
-    const std::vector<int64_t> shape = c.cnx == 1   ? std::vector<int64_t>{c.cout, 3, 4, 4}
-                                       : c.cnx == 2 ? std::vector<int64_t>{c.cout, c.cin / 4, 2, 2}
-                                                    : std::vector<int64_t>{c.cout, c.cin};
-    if (int rc = want(c.wkey, shape, &w)) return rc;
-    if (int rc = want(base + ".bias", {c.cout}, &b)) return rc;
-    if (c.cnx == 4)
-      if (int rc = want(c.gkey, {c.cout}, &g)) return rc;
-    std::vector<float> wp, bias = b->data;
-    if (c.cnx == 1) cnx_pack_stem(w->data.data(), c.cout, &wp);
-    else if (c.cnx == 2) cnx_pack_down(w->data.data(), c.cout, c.cin / 4, &wp);
-    else if (c.cnx == 4) cnx_fold_gamma(w->data.data(), b->data.data(), g->data.data(), c.cout, c.cin, &wp, &bias);
-    else wp = w->data;
-    if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
+// tsm_finalize's weight allocations: dev_alloc under the name "weights", no frame.
+struct WeightAlloc {
+  tsm_engine *e;
+  int operator()(float **p, const char *, size_t elems, size_t) const { return dev_alloc(e, p, elems); }
+};
+
+// The four vectors of BatchNorm `bnp` side by side: [gamma | beta | mean | var], c each.
+std::vector<float> batchnorm(const tsm_engine *e, const std::string &bnp) {
+  std::vector<float> bn;
+  for (int i = 0; i < 4; ++i) {
+    const std::vector<float> &v = tensor(e, bnp + kBnSuffix[i]);
+    bn.insert(bn.end(), v.begin(), v.end());
   }
+  return bn;
+}
+
+// Conv c's host tensors -> the folded fp32 matrix [cout][kp] in c's geometry and the bias, as its kind packs them
+// (tsm_host_util.h: fold_and_pack*, cnx_pack_*, cnx_fold_gamma, tdn_*).
+void pack_conv(const tsm_engine *e, const ConvLayer &c, std::vector<float> *wp, std::vector<float> *bias) {
+  const float *w = tensor(e, c.wkey).data();
+  const std::vector<float> bn = c.bnp.empty() ? std::vector<float>() : batchnorm(e, c.bnp);
+  const float *g = nullptr, *b = nullptr, *m = nullptr, *v = nullptr;
+  if (!bn.empty()) { g = bn.data(); b = g + c.cout; m = b + c.cout; v = m + c.cout; }
+  auto conv_bias = [&]() -> const std::vector<float> & { return tensor(e, bias_key(c.wkey)); };
+  switch (c.kind) {
+    case ConvKind::kBn: prepare_weights(c, w, g, b, m, v, wp, bias); break;
+    case ConvKind::kNlQkv:
+    case ConvKind::kNlW: {   // [cout, cin, 1, 1, 1] weights with a bias; theta | phi | g concatenated along cout
+      const int parts = c.kind == ConvKind::kNlQkv ? 3 : 1, pc = c.cout / parts;
+      wp->assign((size_t)c.cout * c.kp, 0.f);
+      bias->assign(c.cout, 0.f);
+      for (int part = 0; part < parts; ++part) {
+        const std::string wkey = parts == 3 ? c.nlp + kNlQkv[part] + ".weight" : c.wkey;
+        fold_and_pack_bias(tensor(e, wkey).data(), tensor(e, bias_key(wkey)).data(), g, b, m, v, pc, c.cin, c.kp, part * pc, wp, bias);
+      }
+      break;
+    }
+    case ConvKind::kCnxStem: cnx_pack_stem(w, c.cout, wp); *bias = conv_bias(); break;
+    case ConvKind::kCnxDown: cnx_pack_down(w, c.cout, c.cin / 4, wp); *bias = conv_bias(); break;
+    case ConvKind::kCnxFc1: *wp = tensor(e, c.wkey); *bias = conv_bias(); break;
+    case ConvKind::kCnxFc2: cnx_fold_gamma(w, conv_bias().data(), tensor(e, c.gkey).data(), c.cout, c.cin, wp, bias); break;
+    case ConvKind::kTdnBias: {
+      const std::vector<float> mean = tdn_mean_less_bias(m, conv_bias().data(), c.cout);
+      prepare_weights(c, w, g, b, mean.data(), v, wp, bias);
+      break;
+    }
+    case ConvKind::kTdnConv15: tdn_pack_conv15(w, g, b, m, v, c.cout, wp, bias); break;
+  }
+}
+
+// One affine pair "<key>.weight" / "<key>.bias" as it is: a LayerNorm's, the classifier's.
+int upload_pair(tsm_engine *e, WeightAlloc &alloc, const std::string &key, float **d_w, float **d_b, const char *wname, const char *bname) {
+  const int rc = upload(e, alloc, d_w, wname, tensor(e, key + ".weight"));
+  return rc ? rc : upload(e, alloc, d_b, bname, tensor(e, key + ".bias"));
+}
+
+// A ConvNeXt engine's tensors outside its GEMMs: the LayerNorm pairs and every block's depthwise conv (cnx_pack_dw).
+int upload_convnext_norms_and_dw(tsm_engine *e, WeightAlloc &alloc) {
+  auto upload_norm = [&](CnxNorm &n) { return upload_pair(e, alloc, n.key, &n.d_w, &n.d_b, "ln_w", "ln_b"); };
   if (int rc = upload_norm(e->cnx_stem_norm)) return rc;
   if (int rc = upload_norm(e->cnx_head_norm)) return rc;
   for (CnxStage &st : e->cnx_stages)
     if (st.down >= 0)
       if (int rc = upload_norm(st.norm)) return rc;
   for (CnxBlock &blk : e->cnx_blocks) {
-    const HostTensor *w, *b;
-    if (int rc = want(blk.name + ".conv_dw.weight", {blk.c, 1, 7, 7}, &w)) return rc;
-    if (int rc = want(blk.name + ".conv_dw.bias", {blk.c}, &b)) return rc;
     std::vector<float> wp;
-    cnx_pack_dw(w->data.data(), blk.c, &wp);
+    cnx_pack_dw(tensor(e, blk.dwkey + ".weight").data(), blk.c, &wp);
     if (int rc = upload(e, alloc, &blk.d_dw, "dw_w", wp)) return rc;
-    if (int rc = upload(e, alloc, &blk.d_dwb, "dw_b", b->data)) return rc;
+    if (int rc = upload(e, alloc, &blk.d_dwb, "dw_b", tensor(e, blk.dwkey + ".bias"))) return rc;
     if (int rc = upload_norm(blk.norm)) return rc;
   }
-  const HostTensor *fw, *fb;
-  if (int rc = want("head.fc.weight", {cfg.num_class, e->feat}, &fw)) return rc;
-  if (int rc = want("head.fc.bias", {cfg.num_class}, &fb)) return rc;
-  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
-  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
+  return TSM_OK;
+}
 
-  const size_t frames = (size_t)cfg.max_clips;   // (num_segments is 1)
-  const int64_t per_frame = cnx_frame_elems(cfg.height, cfg.width), total = cnx_workspace_elems((int64_t)frames, cfg.height, cfg.width);
-  if (total < 0) return fail(e, TSM_ERR_CAPACITY, "max_clips * (H / 4) * (W / 4) * 512 activations must stay below 2^29 (32-bit byte offsets)");
-  e->buf_elems = (size_t)total;
-  for (int i = 0; i < 5; ++i) {
-    static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
-    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], (size_t)per_frame))) return rc;
+// A TDN engine's long-term modules, one per BottleneckShift (tdn_pack_mse).
+int upload_tdn_mse(tsm_engine *e, WeightAlloc &alloc) {
+  for (TdnMse &m : e->tdn_mse) {
+    const float *conv[kMseConvs];
+    std::vector<float> bn[kMseBns];
+    for (int i = 0; i < kMseConvs; ++i) conv[i] = tensor(e, m.key + kTdnMseConvs[i]).data();
+    for (int i = 0; i < kMseBns; ++i) bn[i] = batchnorm(e, m.key + kTdnMseBns[i]);
+    TdnMseWeights pk;
+    tdn_pack_mse(m.c, conv[kMseConv1], bn[kMseBn1].data(), conv[kMseConv2], conv[kMseSmall2], bn[kMseBnSmall2].data(), conv[kMseSmall4],
+                 bn[kMseBnSmall4].data(), conv[kMseConv3], bn[kMseBn3].data(), conv[kMseTemporal], &pk);
+    const std::pair<float **, const std::vector<float> *> parts[] = {
+        {&m.d_wq, &pk.wq}, {&m.d_bq, &pk.bq}, {&m.d_dw, &pk.dw}, {&m.d_k2, &pk.k2}, {&m.d_b2, &pk.b2},
+        {&m.d_k4, &pk.k4}, {&m.d_b4, &pk.b4}, {&m.d_w3, &pk.w3}, {&m.d_b3, &pk.b3}, {&m.d_wt, &pk.wt}};
+    for (const auto &part : parts)
+      if (int rc = upload(e, alloc, part.first, "mse_w", *part.second)) return rc;
   }
-  if ((rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width))) return rc;
-  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1)))) return rc;
-  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
-  if ((rc = dev_alloc(e, &e->d_logits, frames * cfg.num_class, "d_logits", (size_t)cfg.num_class))) return rc;
-  e->partial_elems = (size_t)16 << 20;   // split-K scratch, as every fp32 engine has
-  if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", (size_t)per_frame))) return rc;
-  e->tensors.clear();
-  e->finalized = true;
   return TSM_OK;
 }
 
 // The Bottleneck fusions' weights, from the folded fp32 matrices of the 1x1 layers (host_wp / host_bias by conv index), for
-// tsm_finalize and finalize_tdn alike.
+// the ResNet and TDN engines alike.
 template <class Alloc>
 int upload_block_fusions(tsm_engine *e, Alloc &alloc, const std::vector<std::vector<float>> &host_wp, const std::vector<std::vector<float>> &host_bias) {
   // First block of every stage: out = relu(conv3(h2) + downsample(x)) as one GEMM, K concatenated.
@@ -1735,132 +1846,74 @@ int upload_block_fusions(tsm_engine *e, Alloc &alloc, const std::vector<std::vec
   return TSM_OK;
 }
 
-// tsm_finalize of a TDN engine.  Every conv of both ResNets has a bias in front of its BatchNorm: folded into the BatchNorm's mean
-// (tdn_mean_less_bias), then the engine's own folds and fusions apply; conv1_5 goes into the patch rows' K order; each
-// BottleneckShift's long-term module is packed by tdn_pack_mse.  Workspace: the five rotating buffers, the 15-plane host
-// staging buffer, the patch rows of one front-end chunk and the nine r-channel maps of the widest long-term module.
-int finalize_tdn(tsm_engine *e) {
-  const tsm_config &cfg = e->cfg;
-  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };
-  auto want = [e](const std::string &key, const std::vector<int64_t> &shape, const HostTensor **t) {
-    *t = find_tensor(e, key);
-    if (!*t) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + key);
-    if ((*t)->shape != shape) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + key);
-    return (int)TSM_OK;
-  };
-  // the four vectors of BatchNorm `bnp` side by side: [gamma | beta | mean | var], c each
-  auto want_bn = [&](const std::string &bnp, int c, std::vector<float> *bn) {
-    bn->clear();
-    for (int i = 0; i < 4; ++i) {
-      const HostTensor *t;
-      if (int rc = want(bnp + kBnSuffix[i], {c}, &t)) return rc;
-      bn->insert(bn->end(), t->data.begin(), t->data.end());
+// Floats of the largest activation of one frame of a ResNet or TDN engine: `start` (the stem conv's output; a TDN engine's x_c5
+// and layer1 on the stem's pooled map) or a conv output of some block (R50: layer1's 256 channels).  *mse_frame: the largest
+// r-channel map of a TDN long-term module.  The walk starts again on the difference path's maps where a TDN engine changes path.
+size_t activation_frame_elems(const tsm_engine *e, size_t start, size_t *mse_frame) {
+  size_t per_frame = start;
+  *mse_frame = 0;
+  int hh = 0, ww = 0;
+  for (size_t k = 0; k < e->blocks.size(); ++k) {
+    const Block &blk = e->blocks[k];
+    if (k == 0 || blk.diff_path != e->blocks[k - 1].diff_path) {
+      hh = blk.diff_path ? e->hd : e->hp;
+      ww = blk.diff_path ? e->wd : e->wp;
     }
-    return (int)TSM_OK;
-  };
-  std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
-  for (size_t ci = 0; ci < e->convs.size(); ++ci) {
-    ConvLayer &c = e->convs[ci];
-    const HostTensor *w;
-    std::vector<float> bn, wp, bias;
-    if (int rc = want(c.wkey, c.tdn == 2 ? std::vector<int64_t>{c.cout, kTdnDiffC, 7, 7} : std::vector<int64_t>{c.cout, c.cin, c.k, c.k}, &w)) return rc;
-    if (int rc = want_bn(c.bnp, c.cout, &bn)) return rc;
-    const float *g = bn.data(), *b = g + c.cout, *m = b + c.cout, *v = m + c.cout;
-    if (c.tdn == 2) {
-      tdn_pack_conv15(w->data.data(), g, b, m, v, c.cout, &wp, &bias);
-    } else {
-      const HostTensor *cb;
-      if (int rc = want(c.wkey.substr(0, c.wkey.size() - 6) + "bias", {c.cout}, &cb)) return rc;
-      const std::vector<float> mean = tdn_mean_less_bias(m, cb->data.data(), c.cout);
-      prepare_weights(c, w->data.data(), g, b, mean.data(), v, &wp, &bias);
+    const size_t in_px = (size_t)hh * ww;
+    if (blk.mse >= 0) *mse_frame = std::max(*mse_frame, in_px * (size_t)(e->tdn_mse[blk.mse].c / kTdnReduction));
+    hh = conv_out_size(hh, 3, blk.stride);
+    ww = conv_out_size(ww, 3, blk.stride);
+    const size_t out_px = (size_t)hh * ww;
+    for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down}) {
+      if (ci < 0) continue;
+      // (a Bottleneck's conv1 runs at the block input's size, every other conv at the block output's)
+      const bool at_input = blk.conv3 >= 0 && ci == blk.conv1;
+      per_frame = std::max(per_frame, (at_input ? in_px : out_px) * (size_t)e->convs[ci].cout);
     }
-    if (c.k == 1 && c.tdn == 1) {
-      host_wp[ci] = wp;
-      host_bias[ci] = bias;
-    }
-    if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
+    // (a non-local engine only: theta | phi | g of a wrapped block, 3 d channels at the block's output size)
+    if (blk.nl_qkv >= 0) per_frame = std::max(per_frame, out_px * (size_t)e->convs[blk.nl_qkv].cout);
   }
-  if (int rc = upload_block_fusions(e, alloc, host_wp, host_bias)) return rc;
-  for (TdnMse &m : e->tdn_mse) {
-    const int C = m.c, r = C / kTdnReduction;
-    const HostTensor *c1, *c2, *c3, *k2, *k4, *wt;
-    std::vector<float> bn1, bn2, bn4, bn3;
-    if (int rc = want(m.key + ".mse.conv1.weight", {r, C, 1, 1}, &c1)) return rc;
-    if (int rc = want(m.key + ".mse.conv2.weight", {r, 1, 3, 3}, &c2)) return rc;
-    if (int rc = want(m.key + ".mse.conv3.weight", {C, r, 1, 1}, &c3)) return rc;
-    if (int rc = want(m.key + ".mse.conv3_smallscale2.weight", {r, r, 3, 3}, &k2)) return rc;
-    if (int rc = want(m.key + ".mse.conv3_smallscale4.weight", {r, r, 3, 3}, &k4)) return rc;
-    if (int rc = want(m.key + ".shift.conv.weight", {C, 1, 3}, &wt)) return rc;
-    if (int rc = want_bn(m.key + ".mse.bn1", r, &bn1)) return rc;
-    if (int rc = want_bn(m.key + ".mse.bn3_smallscale2", r, &bn2)) return rc;
-    if (int rc = want_bn(m.key + ".mse.bn3_smallscale4", r, &bn4)) return rc;
-    if (int rc = want_bn(m.key + ".mse.bn3", C, &bn3)) return rc;
-    TdnMseWeights pk;
-    tdn_pack_mse(C, c1->data.data(), bn1.data(), c2->data.data(), k2->data.data(), bn2.data(), k4->data.data(), bn4.data(),
-                 c3->data.data(), bn3.data(), wt->data.data(), &pk);
-    const std::pair<float **, const std::vector<float> *> parts[] = {
-        {&m.d_wq, &pk.wq}, {&m.d_bq, &pk.bq}, {&m.d_dw, &pk.dw}, {&m.d_k2, &pk.k2}, {&m.d_b2, &pk.b2},
-        {&m.d_k4, &pk.k4}, {&m.d_b4, &pk.b4}, {&m.d_w3, &pk.w3}, {&m.d_b3, &pk.b3}, {&m.d_wt, &pk.wt}};
-    for (const auto &part : parts)
-      if (int rc = upload(e, alloc, part.first, "mse_w", *part.second)) return rc;
-  }
-  const HostTensor *fw, *fb;
-  if (int rc = want("new_fc.weight", {cfg.num_class, e->feat}, &fw)) return rc;
-  if (int rc = want("new_fc.bias", {cfg.num_class}, &fb)) return rc;
-  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
-  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
+  return per_frame;
+}
 
-  const int H = cfg.height, W = cfg.width;
-  e->h1 = conv_out_size(H, 7, 2);
-  e->w1 = conv_out_size(W, 7, 2);
-  e->hp = conv_out_size(e->h1, 3, 2);
-  e->wp = conv_out_size(e->w1, 3, 2);
-  e->hd = tdn_diff_size(H);
-  e->wd = tdn_diff_size(W);
-  e->tdn_chunk = tdn_chunk_clips(cfg.max_clips, cfg.num_segments, H, W);
-  if (e->tdn_chunk <= 0) return fail(e, TSM_ERR_CAPACITY, "the patch rows of conv1_5 for one clip, T * (H / 4) * (W / 4) * 1024 floats, must stay below 2^29");
-  const size_t frames = (size_t)cfg.max_clips * cfg.num_segments;
-  // per frame: the largest activation (x_c5 and layer1's 256 channels on the stem's pooled map; the patch rows have their own
-  // buffer) and the largest r-channel map of a long-term module
-  size_t per_frame = (size_t)e->hp * e->wp * 256, mse_frame = 0;
-  {
-    int hh = 0, ww = 0;
-    for (size_t k = 0; k < e->blocks.size(); ++k) {
-      const Block &blk = e->blocks[k];
-      if (k == 0 || blk.diff_path != e->blocks[k - 1].diff_path) {
-        hh = blk.diff_path ? e->hd : e->hp;
-        ww = blk.diff_path ? e->wd : e->wp;
-      }
-      const size_t in_px = (size_t)hh * ww;
-      if (blk.mse >= 0) mse_frame = std::max(mse_frame, in_px * (size_t)(e->tdn_mse[blk.mse].c / kTdnReduction));
-      hh = conv_out_size(hh, 3, blk.stride);
-      ww = conv_out_size(ww, 3, blk.stride);
-      const size_t out_px = (size_t)hh * ww;
-      for (int ci : {blk.conv1, blk.conv2, blk.conv3})
-        per_frame = std::max(per_frame, (ci == blk.conv1 ? in_px : out_px) * (size_t)e->convs[ci].cout);
-    }
-  }
-  if ((double)frames * (double)per_frame >= (double)(kInt31 >> 2))
-    return fail(e, TSM_ERR_CAPACITY, "max_clips * num_segments * (H / 4) * (W / 4) * 256 activations must stay below 2^29 (32-bit byte offsets)");
-  e->buf_elems = frames * per_frame;
+// What alloc_workspace sizes the buffers from, in floats.
+struct Workspace {
+  size_t frames = 0;        // max_clips * num_segments
+  size_t per_frame = 0;     // the largest activation of one frame
+  size_t in_frame = 0;      // one input frame as a host caller hands it over (d_in) ...
+  size_t in4_frame = 0;     // ... and packed (d_in4)
+  // a TDN engine: conv1_5's patch rows of one frame and the frames of one front-end chunk; the long-term modules' largest map
+  size_t patch_frame = 0, patch_frames = 0, mse_frame = 0;
+};
+
+// The workspace of every family: five rotating buffers (block in / out, two branch temporaries, identity), each the largest
+// activation of the schedule; the input staging and packing buffers; a TDN engine's patch rows and its nine r-channel maps; the
+// head's buffers; the split-K scratch of an fp32 engine.  Then the host copies go and the engine is finalized.
+int alloc_workspace(tsm_engine *e, const Workspace &ws) {
+  const tsm_config &cfg = e->cfg;
+  int rc;
+  e->buf_elems = ws.frames * ws.per_frame;
   for (int i = 0; i < 5; ++i) {
     static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
-    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame))) return rc;
+    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], ws.per_frame))) return rc;
   }
-  const size_t in_frame = (size_t)kTdnPlanes * H * W;
-  if ((rc = dev_alloc(e, &e->d_in, frames * in_frame, "d_in", in_frame))) return rc;
-  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * H * W, "d_in4", (size_t)4 * H * W))) return rc;
-  const size_t patch_frame = (size_t)tdn_conv15_size(H) * tdn_conv15_size(W) * kTdnPatchK;
-  if ((rc = dev_alloc(e, &e->d_patches, (size_t)e->tdn_chunk * cfg.num_segments * patch_frame, "d_patches", patch_frame))) return rc;
-  static const char *const kMseNames[9] = {"mse.b", "mse.d+", "mse.d-", "mse.m+", "mse.m-", "mse.pool+", "mse.pool-", "mse.s2+", "mse.s2-"};
-  for (int i = 0; i < 9; ++i)   // (the pooled maps are a quarter of the size at most; one size for all keeps the bands' frame)
-    if ((rc = dev_alloc(e, &e->d_mse[i], frames * mse_frame, kMseNames[i], mse_frame))) return rc;
-  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
-  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? cfg.num_segments : 1) * cfg.num_class, "d_logits",
+  if ((rc = dev_alloc(e, &e->d_in, ws.frames * ws.in_frame, "d_in", ws.in_frame))) return rc;
+  if ((rc = dev_alloc(e, &e->d_in4, ws.frames * ws.in4_frame, "d_in4", ws.in4_frame))) return rc;
+  if (ws.patch_frame) {
+    if ((rc = dev_alloc(e, &e->d_patches, ws.patch_frames * ws.patch_frame, "d_patches", ws.patch_frame))) return rc;
+    static const char *const kMseNames[9] = {"mse.b", "mse.d+", "mse.d-", "mse.m+", "mse.m-", "mse.pool+", "mse.pool-", "mse.s2+", "mse.s2-"};
+    for (int i = 0; i < 9; ++i)   // (the pooled maps are a quarter of the size at most; one size for all keeps the bands' frame)
+      if ((rc = dev_alloc(e, &e->d_mse[i], ws.frames * ws.mse_frame, kMseNames[i], ws.mse_frame))) return rc;
+  }
+  if ((rc = dev_alloc(e, &e->d_pooled, ws.frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
+  // avg: one row per clip; identity: one per (clip, segment)
+  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? out_segments(e) : 1) * cfg.num_class, "d_logits",
                       (size_t)cfg.num_class))) return rc;
-  e->partial_elems = (size_t)16 << 20;   // split-K scratch, as every fp32 engine has
-  if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame))) return rc;
-  e->tensors.clear();
+  if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
+    e->partial_elems = (size_t)16 << 20;
+    if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", ws.per_frame))) return rc;
+  }
+  e->tensors.clear();  // host copies are no longer needed
   e->finalized = true;
   return TSM_OK;
 }
@@ -2205,109 +2258,60 @@ int tsm_finalize(tsm_engine *e) {
   if (!e) return TSM_ERR_INVALID_ARG;
   if (e->finalized) return TSM_OK;
   TSM_HIP(e, hipSetDevice(e->cfg.device_id));
-  if (e->convnext) return finalize_convnext(e);
-  if (e->tdn) return finalize_tdn(e);
+  if (int rc = check_tensors(e)) return rc;
   const tsm_config &cfg = e->cfg;
-  auto alloc = [e](float **p, const char *, size_t elems, size_t) { return dev_alloc(e, p, elems); };   // ("weights", no frame)
+  WeightAlloc alloc{e};
+  // Every conv packed by its kind; the folded fp32 copies of a Bottleneck's 1x1 layers are kept for the fusions behind them.
   std::vector<std::vector<float>> host_wp(e->convs.size()), host_bias(e->convs.size());
   for (size_t ci = 0; ci < e->convs.size(); ++ci) {
     ConvLayer &c = e->convs[ci];
-    if (c.nl) {   // the non-local block's convs: [cout, cin, 1, 1, 1] weights with a bias; theta | phi | g concatenated along cout
-      const int parts = c.nl == 1 ? 3 : 1, pc = c.cout / parts;
-      static const char *const kQkv[3] = {".theta", ".phi.0", ".g.0"};
-      std::vector<float> wp((size_t)c.cout * c.kp, 0.f), bias(c.cout);
-      const HostTensor *bn[4] = {nullptr, nullptr, nullptr, nullptr};
-      if (c.nl == 2) {
-        static const char *const kBn[4] = {".weight", ".bias", ".running_mean", ".running_var"};
-        for (int i = 0; i < 4; ++i) {
-          bn[i] = find_tensor(e, c.bnp + kBn[i]);
-          if (!bn[i]) return fail(e, TSM_ERR_MISSING_TENSOR, "missing BatchNorm tensors of " + c.bnp);
-          if (bn[i]->shape != std::vector<int64_t>{c.cout}) return fail(e, TSM_ERR_SHAPE, "BN shape mismatch for " + c.bnp);
-        }
-      }
-      for (int part = 0; part < parts; ++part) {
-        const std::string base = c.nlp + (c.nl == 1 ? kQkv[part] : ".W.0");
-        const HostTensor *w = find_tensor(e, base + ".weight"), *b = find_tensor(e, base + ".bias");
-        if (!w || !b) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + base + (w ? ".bias" : ".weight"));
-        if (w->shape != std::vector<int64_t>{pc, c.cin, 1, 1, 1}) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + base + ".weight");
-        if (b->shape != std::vector<int64_t>{pc}) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + base + ".bias");
-        fold_and_pack_bias(w->data.data(), b->data.data(), bn[0] ? bn[0]->data.data() : nullptr, bn[0] ? bn[1]->data.data() : nullptr,
-                           bn[0] ? bn[2]->data.data() : nullptr, bn[0] ? bn[3]->data.data() : nullptr, pc, c.cin, c.kp, part * pc,
-                           &wp, &bias);
-      }
-      if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
-      continue;
-    }
-    const HostTensor *w = find_tensor(e, c.wkey);
-    const HostTensor *g = find_tensor(e, c.bnp + ".weight"), *b = find_tensor(e, c.bnp + ".bias");
-    const HostTensor *m = find_tensor(e, c.bnp + ".running_mean"), *v = find_tensor(e, c.bnp + ".running_var");
-    if (!w) return fail(e, TSM_ERR_MISSING_TENSOR, "missing " + c.wkey);
-    if (!g || !b || !m || !v) return fail(e, TSM_ERR_MISSING_TENSOR, "missing BatchNorm tensors of " + c.bnp);
-    const std::vector<int64_t> want = {c.cout, c.cin, c.k, c.k};
-    if (w->shape != want) return fail(e, TSM_ERR_SHAPE, "shape mismatch for " + c.wkey);
-    for (const HostTensor *t : {g, b, m, v})
-      if (t->shape.size() != 1 || t->shape[0] != c.cout) return fail(e, TSM_ERR_SHAPE, "BN shape mismatch for " + c.bnp);
     std::vector<float> wp, bias;
-    prepare_weights(c, w->data.data(), g->data.data(), b->data.data(), m->data.data(), v->data.data(), &wp, &bias);
-    if (c.k == 1) {  // fp32 packed copies of the 1x1 layers, for the conv3 + downsample fusion below
+    pack_conv(e, c, &wp, &bias);
+    if (c.k == 1 && (c.kind == ConvKind::kBn || c.kind == ConvKind::kTdnBias)) {
       host_wp[ci] = wp;
       host_bias[ci] = bias;
     }
     if (int rc = upload_conv(e, alloc, e->prec, c.cout, &wp, bias, &c.d_w, &c.d_b)) return rc;
   }
-  if (int rc = upload_block_fusions(e, alloc, host_wp, host_bias)) return rc;
+  if (int rc = upload_block_fusions(e, alloc, host_wp, host_bias)) return rc;   // (a ConvNeXt engine has no blocks)
   host_wp.clear();
   host_bias.clear();
-  const HostTensor *fw = find_tensor(e, "fc.weight"), *fb = find_tensor(e, "fc.bias");
-  if (!fw || !fb) return fail(e, TSM_ERR_MISSING_TENSOR, "missing fc.weight / fc.bias");
-  if (fw->shape != std::vector<int64_t>{cfg.num_class, e->feat} || fb->shape != std::vector<int64_t>{cfg.num_class})
-    return fail(e, TSM_ERR_SHAPE, "fc shape mismatch (want [num_class, " + std::to_string(e->feat) + "])");
-  int rc = upload(e, alloc, &e->d_fcw, "d_fcw", fw->data);
-  if (rc || (rc = upload(e, alloc, &e->d_fcb, "d_fcb", fb->data))) return rc;
+  if (e->convnext)
+    if (int rc = upload_convnext_norms_and_dw(e, alloc)) return rc;
+  if (int rc = upload_tdn_mse(e, alloc)) return rc;
+  if (int rc = upload_pair(e, alloc, head_prefix(e), &e->d_fcw, &e->d_fcb, "d_fcw", "d_fcb")) return rc;
 
-  // Workspace: five rotating buffers (block in/out, two branch temporaries, identity), each the largest activation of the
-  // topology per frame: the stem conv output or a conv output of some block (R50: layer1's 256 channels).
-  e->h1 = conv_out_size(cfg.height, 7, 2);
-  e->w1 = conv_out_size(cfg.width, 7, 2);
+  // The workspace, sized per frame; both capacity refusals come before its first allocation.
+  const int H = cfg.height, W = cfg.width;
+  Workspace ws;
+  ws.frames = (size_t)cfg.max_clips * cfg.num_segments;
+  ws.in_frame = (size_t)(e->tdn ? kTdnPlanes : 3) * H * W;
+  ws.in4_frame = (size_t)4 * H * (e->tdn ? W : W + 1);   // 16 bytes per pixel in every format (pairs: odd widths padded)
+  if (e->convnext) {   // (num_segments is 1) the largest activation of the schedule is fc1's output in stage 0
+    if (cnx_workspace_elems((int64_t)ws.frames, H, W) < 0)
+      return fail(e, TSM_ERR_CAPACITY, "max_clips * (H / 4) * (W / 4) * 512 activations must stay below 2^29 (32-bit byte offsets)");
+    ws.per_frame = (size_t)cnx_frame_elems(H, W);
+    return alloc_workspace(e, ws);
+  }
+  e->h1 = conv_out_size(H, 7, 2);
+  e->w1 = conv_out_size(W, 7, 2);
   e->hp = conv_out_size(e->h1, 3, 2);   // (the max-pool)
   e->wp = conv_out_size(e->w1, 3, 2);
-  const size_t frames = (size_t)cfg.max_clips * cfg.num_segments;
-  size_t per_frame = (size_t)e->h1 * e->w1 * 64;
-  {
-    int hh = e->hp, ww = e->wp;
-    for (const Block &blk : e->blocks) {
-      const size_t in_px = (size_t)hh * ww;
-      hh = conv_out_size(hh, 3, blk.stride);
-      ww = conv_out_size(ww, 3, blk.stride);
-      const size_t out_px = (size_t)hh * ww;
-      for (int ci : {blk.conv1, blk.conv2, blk.conv3, blk.down}) {
-        if (ci < 0) continue;
-        // (a Bottleneck's conv1 runs at the block input's size, every other conv at the block output's)
-        const bool at_input = blk.conv3 >= 0 && ci == blk.conv1;
-        per_frame = std::max(per_frame, (at_input ? in_px : out_px) * (size_t)e->convs[ci].cout);
-      }
-      // (a non-local engine only: theta | phi | g of a wrapped block, 3 d channels at the block's output size)
-      if (blk.nl_qkv >= 0) per_frame = std::max(per_frame, out_px * (size_t)e->convs[blk.nl_qkv].cout);
-    }
+  if (!e->tdn) {
+    ws.per_frame = activation_frame_elems(e, (size_t)e->h1 * e->w1 * 64, &ws.mse_frame);
+    return alloc_workspace(e, ws);
   }
-  e->buf_elems = frames * per_frame;
-  for (int i = 0; i < 5; ++i) {
-    static const char *const kBufNames[5] = {"buf[0]", "buf[1]", "buf[2]", "buf[3]", "buf[4]"};
-    if ((rc = dev_alloc(e, &e->buf[i], e->buf_elems, kBufNames[i], per_frame))) return rc;
-  }
-  if ((rc = dev_alloc(e, &e->d_in, frames * 3 * cfg.height * cfg.width, "d_in", (size_t)3 * cfg.height * cfg.width))) return rc;
-  if ((rc = dev_alloc(e, &e->d_in4, frames * 4 * cfg.height * (cfg.width + 1), "d_in4", (size_t)4 * cfg.height * (cfg.width + 1)))) return rc;  // 16 bytes per pixel in every format (pairs: odd widths padded)
-  if ((rc = dev_alloc(e, &e->d_pooled, frames * (size_t)e->feat, "d_pooled", (size_t)e->feat))) return rc;
-  // avg: one row per clip; identity: one per (clip, segment)
-  if ((rc = dev_alloc(e, &e->d_logits, (size_t)cfg.max_clips * (e->consensus == 1 ? out_segments(e) : 1) * cfg.num_class, "d_logits",
-                 (size_t)cfg.num_class))) return rc;
-  if (e->prec == tsm::kPrecF32) {  // split-K scratch: 64 MB covers the small-batch cases where split-K can win
-    e->partial_elems = (size_t)16 << 20;
-    if ((rc = dev_alloc(e, &e->d_partial, e->partial_elems, "d_partial", per_frame))) return rc;
-  }
-  e->tensors.clear();  // host copies are no longer needed
-  e->finalized = true;
-  return TSM_OK;
+  e->hd = tdn_diff_size(H);
+  e->wd = tdn_diff_size(W);
+  e->tdn_chunk = tdn_chunk_clips(cfg.max_clips, cfg.num_segments, H, W);
+  if (e->tdn_chunk <= 0) return fail(e, TSM_ERR_CAPACITY, "the patch rows of conv1_5 for one clip, T * (H / 4) * (W / 4) * 1024 floats, must stay below 2^29");
+  // (x_c5 and layer1's 256 channels on the stem's pooled map; the patch rows have their own buffer)
+  ws.per_frame = activation_frame_elems(e, (size_t)e->hp * e->wp * 256, &ws.mse_frame);
+  if ((double)ws.frames * (double)ws.per_frame >= (double)(kInt31 >> 2))
+    return fail(e, TSM_ERR_CAPACITY, "max_clips * num_segments * (H / 4) * (W / 4) * 256 activations must stay below 2^29 (32-bit byte offsets)");
+  ws.patch_frame = (size_t)tdn_conv15_size(H) * tdn_conv15_size(W) * kTdnPatchK;
+  ws.patch_frames = (size_t)e->tdn_chunk * cfg.num_segments;
+  return alloc_workspace(e, ws);
 }
 
 // tsm_forward (features = 0: `out` = the logits) and tsm_forward_features (1 / 2: `out` = the pooled / unit rows): one contract,

@@ -73,34 +73,18 @@ class TsmEngine:
         # dtype='f32' -- of ``convnext_depths`` blocks per stage, (3, 3, 27, 3) unless given (tests build shallow engines).
         # base_model='tdn_resnet50' (include/tsm_hip.h: tsm_set_tdn): clips of 15 planes per segment, is_shift=False, dtype='f32',
         # ``tdn_depths`` blocks per stage, (3, 4, 6, 3) unless given; ``tdn_alpha`` / ``tdn_beta`` default to tdn_net's rule.
-        tdn = base_model == TDN
-        convnext = not tdn and is_convnext(base_model)
-        if tdn:           # every refusal before the library loads
-            tdn_depths = _check_tdn(tdn_depths, num_segments, is_shift, dtype, height, width, shift_place, non_local, temporal_pool)
-            if tdn_alpha is None or tdn_beta is None:
-                tdn_alpha, tdn_beta = tdn_alpha_beta(num_segments)
-        elif tdn_depths is not None or tdn_alpha is not None or tdn_beta is not None:
-            raise ValueError(f'tdn_depths= / tdn_alpha= / tdn_beta= go with base_model={TDN!r} only')
-        if convnext:
-            convnext_depths = _check_convnext(convnext_depths, num_segments, is_shift, dtype, shift_place, non_local, temporal_pool)
-        elif convnext_depths is not None:
-            raise ValueError(f'convnext_depths= goes with base_model={CONVNEXT!r} only')
-        elif not tdn and base_model not in DEPTHS:
-            raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
-        if not convnext and not tdn:
-            _check_non_local(non_local, base_model, dtype)
-        _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
-        if shift_place not in SHIFT_PLACES:
-            raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
-        if consensus_type not in CONSENSUS_TYPES:
-            raise ValueError(f"consensus_type must be one of {list(CONSENSUS_TYPES)}, got {consensus_type!r}")
+        convnext_depths, tdn_depths = _check_engine_args(      # every refusal before the library loads
+            base_model, num_segments=num_segments, is_shift=is_shift, dtype=dtype, height=height, width=width, shift_place=shift_place,
+            consensus_type=consensus_type, non_local=non_local, temporal_pool=temporal_pool, convnext_depths=convnext_depths,
+            tdn_depths=tdn_depths, tdn_alpha=tdn_alpha, tdn_beta=tdn_beta)
+        tdn, convnext = tdn_depths is not None, convnext_depths is not None
+        if tdn and (tdn_alpha is None or tdn_beta is None):
+            tdn_alpha, tdn_beta = tdn_alpha_beta(num_segments)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.num_class, self.num_segments = int(num_class), int(num_segments)
         self.height, self.width = int(height), int(width)
         self.max_clips, self.device = int(max_clips), int(device)
-        if dtype not in _lib.DTYPES:
-            raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
         self.dtype = dtype
         self.base_model = base_model
         self.shift_place = shift_place
@@ -651,38 +635,96 @@ class TsmEngine:
             pass
 
 
-def _check_convnext(depths, num_segments: int, is_shift: bool, dtype: str, shift_place: str = 'blockres', non_local: bool = False,
-                    temporal_pool: bool = False):
-    """``base_model='convnext_base'`` is an image model: one frame per clip, no temporal shift, fp32 only.  Everything else is
-    refused up front, never ignored; returns the stage depths ((3, 3, 27, 3) unless given)."""
+def _f32_only(family: str, dtype: str) -> None:
+    """A family that runs in fp32 only: NotImplementedError for the bf16 formats, ValueError for an unknown dtype."""
     if dtype != 'f32':
         if dtype in _lib.DTYPES:
-            raise NotImplementedError(f"{CONVNEXT} runs in dtype='f32' only, not {dtype!r}")
+            raise NotImplementedError(f"{family} runs in dtype='f32' only, not {dtype!r}")
         raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
-    if num_segments != 1 or is_shift:
-        raise NotImplementedError(f'{CONVNEXT} is an image model (num_segments=1, is_shift=False): there is no temporal shift in this family')
-    if non_local or temporal_pool or shift_place != 'blockres':
-        raise NotImplementedError(f'{CONVNEXT} has no non_local / temporal_pool / shift_place')
-    return _convnext_depths(depths)
 
 
-def _check_tdn(depths, num_segments: int, is_shift: bool, dtype: str, height: int, width: int, shift_place: str = 'blockres',
-               non_local: bool = False, temporal_pool: bool = False):
-    """``base_model='tdn_resnet50'``: fp32 only, no TSM shift, at least two segments, sides that are multiples of 32 and at least
-    64.  Everything else is refused up front, never ignored; returns the stage depths ((3, 4, 6, 3) unless given)."""
-    if dtype != 'f32':
-        if dtype in _lib.DTYPES:
-            raise NotImplementedError(f"{TDN} runs in dtype='f32' only, not {dtype!r}")
+def _check_engine_args(base_model: str = 'resnet50', *, num_segments: int = 8, is_shift: bool = True, dtype: str = 'f32', height: int = 224,
+                       width: int = 224, shift_place: str = 'blockres', consensus_type: str = 'avg', non_local: bool = False,
+                       temporal_pool: bool = False, convnext_depths=None, tdn_depths=None, tdn_alpha=None, tdn_beta=None):
+    """The argument checks of an engine, for ``TsmEngine`` and for the factories in front of their checkpoint: everything the
+    engine cannot do is refused up front, never ignored, before the library loads.  Returns ``(convnext_depths, tdn_depths)``, each
+    None unless the engine is of that family (then (3, 3, 27, 3) / (3, 4, 6, 3) unless given).
+
+    * ``base_model='tdn_resnet50'``: fp32 only, no TSM shift, at least two segments, sides that are multiples of 32 and at least 64.
+    * ``base_model='convnext_base'`` is an image model: one frame per clip, no temporal shift, fp32 only.
+    * ``non_local=True``: Bottleneck backbones in fp32 (the bf16 formats' cross-block fused forms and storage formats do not know
+      the block).
+    * ``temporal_pool=True``: not ``dtype='bf16'`` (its cross-block and whole-block kernels tile over all T frames of a clip), not
+      ``is_shift=False`` (make_temporal_pool is a branch of make_temporal_shift), not an odd ``num_segments``, and not together
+      with ``non_local=True`` (whose wrapper assumes one segment count)."""
+    tdn = base_model == TDN
+    convnext = not tdn and is_convnext(base_model)
+    if tdn:
+        _f32_only(TDN, dtype)
+        if is_shift:
+            raise ValueError(f'{TDN} has no TSM shift (its temporal conv is learned): pass is_shift=False')
+        if non_local or temporal_pool or shift_place != 'blockres':
+            raise NotImplementedError(f'{TDN} has no non_local / temporal_pool / shift_place')
+        if num_segments < 2:
+            raise ValueError(f'{TDN} needs num_segments >= 2, got {num_segments}')
+        if height < 64 or width < 64 or height % 32 or width % 32:
+            raise ValueError(f'{TDN} needs height and width that are multiples of 32 and at least 64, got {height} x {width}')
+        tdn_depths = _tdn_depths(tdn_depths)
+    elif tdn_depths is not None or tdn_alpha is not None or tdn_beta is not None:
+        raise ValueError(f'tdn_depths= / tdn_alpha= / tdn_beta= go with base_model={TDN!r} only')
+    if convnext:
+        _f32_only(CONVNEXT, dtype)
+        if num_segments != 1 or is_shift:
+            raise NotImplementedError(f'{CONVNEXT} is an image model (num_segments=1, is_shift=False): there is no temporal shift in this family')
+        if non_local or temporal_pool or shift_place != 'blockres':
+            raise NotImplementedError(f'{CONVNEXT} has no non_local / temporal_pool / shift_place')
+        convnext_depths = _convnext_depths(convnext_depths)
+    elif convnext_depths is not None:
+        raise ValueError(f'convnext_depths= goes with base_model={CONVNEXT!r} only')
+    elif not tdn and base_model not in DEPTHS:
+        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+    if non_local and not convnext and not tdn:
+        if BACKBONES[base_model][1] != 'bottleneck':
+            raise NotImplementedError(f'non_local=True needs a Bottleneck backbone (resnet50, wide_resnet50_2), not {base_model}')
+        if dtype != 'f32':
+            raise NotImplementedError(f"non_local=True runs in dtype='f32' only, not {dtype!r}")
+    if temporal_pool:
+        if dtype == 'bf16':
+            raise NotImplementedError("temporal_pool=True runs in dtype='f32' and 'bf16x3' only, not 'bf16'")
+        if non_local:
+            raise NotImplementedError('temporal_pool=True and non_local=True exclude each other')
+        if not is_shift:
+            raise ValueError('temporal_pool=True needs is_shift=True')
+        if num_segments <= 0 or num_segments % 2:
+            raise ValueError(f'temporal_pool=True needs an even num_segments, got {num_segments}')
+    if shift_place not in SHIFT_PLACES:
+        raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
+    if consensus_type not in CONSENSUS_TYPES:
+        raise ValueError(f"consensus_type must be one of {list(CONSENSUS_TYPES)}, got {consensus_type!r}")
+    if dtype not in _lib.DTYPES:
         raise ValueError(f'dtype must be one of {sorted(_lib.DTYPES)}, got {dtype!r}')
-    if is_shift:
-        raise ValueError(f'{TDN} has no TSM shift (its temporal conv is learned): pass is_shift=False')
-    if non_local or temporal_pool or shift_place != 'blockres':
-        raise NotImplementedError(f'{TDN} has no non_local / temporal_pool / shift_place')
-    if num_segments < 2:
-        raise ValueError(f'{TDN} needs num_segments >= 2, got {num_segments}')
-    if height < 64 or width < 64 or height % 32 or width % 32:
-        raise ValueError(f'{TDN} needs height and width that are multiples of 32 and at least 64, got {height} x {width}')
-    return _tdn_depths(depths)
+    return convnext_depths, tdn_depths
+
+
+def _device_index(device) -> int:
+    """The factories' ``device`` argument (None, 'cuda', 'cuda:1', a ``torch.device``) as a device number; 'cpu' raises."""
+    if device is None:
+        return 0
+    s = str(device)
+    if s == 'cpu':
+        raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
+    return int(s.split(':')[1]) if ':' in s else 0
+
+
+def _is_onnx(checkpoint) -> bool:
+    return checkpoint is not None and str(checkpoint).endswith('.onnx')
+
+
+def _load_state_dict(checkpoint):
+    """A ``torch.save``d checkpoint on the CPU: its ``state_dict`` entry where it has one, else the mapping itself."""
+    import torch
+    ckpt = torch.load(checkpoint, map_location='cpu')
+    return ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
 
 
 def create_tdn_model(num_class: int, num_segments: int = 8, base_model: str = 'resnet50', num_frames: int = 5,
@@ -701,54 +743,20 @@ def create_tdn_model(num_class: int, num_segments: int = 8, base_model: str = 'r
         raise NotImplementedError(f'TDN on {base_model}: the engine implements resnet50 (depths 3, 4, 6, 3) only')
     if num_frames != TDN_FRAMES:
         raise NotImplementedError(f'num_frames must be {TDN_FRAMES} (four differences around the centre frame), got {num_frames}')
-    if dtype != 'f32' and dtype in _lib.DTYPES:
-        raise NotImplementedError(f"{TDN} runs in dtype='f32' only, not {dtype!r}")
-    if checkpoint is not None and str(checkpoint).endswith('.onnx'):
-        raise NotImplementedError('a TDN .onnx file: the importer reads TSM graphs only')
     assert consensus_type in ['avg', 'identity']
-    depths = _tdn_depths(depths)
-    dev = 0
-    if device is not None:
-        s = str(device)
-        if s == 'cpu':
-            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
-        dev = int(s.split(':')[1]) if ':' in s else 0
+    _convnext, depths = _check_engine_args(TDN, num_segments=num_segments, is_shift=False, dtype=dtype, height=height, width=width,
+                                           consensus_type=consensus_type, tdn_depths=depths)
+    if _is_onnx(checkpoint):
+        raise NotImplementedError('a TDN .onnx file: the importer reads TSM graphs only')
+    dev = _device_index(device)
     if checkpoint is not None:
-        import torch
-        sd = remap_tdn_keys(torch.load(checkpoint, map_location='cpu'), num_class, depths)
+        sd = remap_tdn_keys(_load_state_dict(checkpoint), num_class, depths)
     else:
         sd = make_tdn_state_dict(seed=seed, num_class=num_class, depths=depths)
     alpha, beta = tdn_alpha_beta(num_segments)
     return TsmEngine(num_class=num_class, num_segments=num_segments, height=height, width=width, is_shift=False, max_clips=max_clips,
                      device=dev, state_dict=sd, dtype=dtype, base_model=TDN, consensus_type=consensus_type, tdn_depths=depths,
                      tdn_alpha=alpha, tdn_beta=beta)
-
-
-def _check_non_local(non_local: bool, base_model: str, dtype: str) -> None:
-    """``non_local=True`` is refused up front, never ignored, where the engine has no non-local block: BasicBlock backbones
-    and the bf16 formats (whose cross-block fused forms and storage formats do not know the block)."""
-    if not non_local:
-        return
-    if BACKBONES[base_model][1] != 'bottleneck':
-        raise NotImplementedError(f'non_local=True needs a Bottleneck backbone (resnet50, wide_resnet50_2), not {base_model}')
-    if dtype != 'f32':
-        raise NotImplementedError(f"non_local=True runs in dtype='f32' only, not {dtype!r}")
-
-
-def _check_temporal_pool(temporal_pool: bool, num_segments: int, is_shift: bool, dtype: str, non_local: bool) -> None:
-    """``temporal_pool=True`` is refused up front, never ignored, where the engine cannot pool: ``dtype='bf16'`` (its cross-block
-    and whole-block kernels tile over all T frames of a clip), ``is_shift=False`` (make_temporal_pool is a branch of
-    make_temporal_shift), an odd ``num_segments``, and together with ``non_local=True`` (whose wrapper assumes one segment count)."""
-    if not temporal_pool:
-        return
-    if dtype == 'bf16':
-        raise NotImplementedError("temporal_pool=True runs in dtype='f32' and 'bf16x3' only, not 'bf16'")
-    if non_local:
-        raise NotImplementedError('temporal_pool=True and non_local=True exclude each other')
-    if not is_shift:
-        raise ValueError('temporal_pool=True needs is_shift=True')
-    if num_segments <= 0 or num_segments % 2:
-        raise ValueError(f'temporal_pool=True needs an even num_segments, got {num_segments}')
 
 
 def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'resnet50',
@@ -792,27 +800,18 @@ def create_model(num_class: int = 2, num_segments: int = 8, base_model: str = 'r
     if base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
     assert consensus_type in ['avg', 'identity']
-    if shift_place not in SHIFT_PLACES:
-        raise ValueError(f"shift_place must be one of {list(SHIFT_PLACES)}, got {shift_place!r}")
-    _check_non_local(non_local, base_model, dtype)
-    _check_temporal_pool(temporal_pool, num_segments, is_shift, dtype, non_local)
-    if non_local and checkpoint is not None and str(checkpoint).endswith('.onnx'):
+    _check_engine_args(base_model, num_segments=num_segments, is_shift=is_shift, dtype=dtype, height=height, width=width,
+                       shift_place=shift_place, consensus_type=consensus_type, non_local=non_local, temporal_pool=temporal_pool)
+    if non_local and _is_onnx(checkpoint):
         raise NotImplementedError('non_local=True with an .onnx checkpoint: the importer does not read non-local blocks')
-    if temporal_pool and checkpoint is not None and str(checkpoint).endswith('.onnx'):
+    if temporal_pool and _is_onnx(checkpoint):
         raise NotImplementedError('temporal_pool=True with an .onnx checkpoint: the importer does not read the pooled graph')
-    dev = 0
-    if device is not None:
-        s = str(device)
-        if s == 'cpu':
-            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
-        dev = int(s.split(':')[1]) if ':' in s else 0
-    if checkpoint is not None and str(checkpoint).endswith('.onnx'):
+    dev = _device_index(device)
+    if _is_onnx(checkpoint):
         from .onnx_import import load_onnx_state_dict        # the reference's deployed artefact
         sd = load_onnx_state_dict(checkpoint, num_class, base_model, shift_place=shift_place)
     elif checkpoint is not None:
-        import torch
-        ckpt = torch.load(checkpoint, map_location='cpu')
-        raw = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
+        raw = _load_state_dict(checkpoint)
         # mmaction2 checkpoints (the reference's --mmlab branch) vs the reference's own TSM / Lightning ones
         if non_local and is_mmaction_state_dict(raw):
             raise NotImplementedError('non_local=True with an mmaction2 checkpoint: its non-local key spelling is not mapped')
@@ -842,28 +841,7 @@ def create_image_model(num_class: int = 2, base_model: str = 'resnet18', checkpo
     ``TsmEngine(base_model='convnext_base', convnext_depths=(3, 3, 27, 3))``, include/tsm_hip.h: tsm_set_convnext.  Its
     ``checkpoint`` has timm's keys, with or without that one leading component (``weights.remap_timm_keys``).  ``dtype`` other
     than 'f32', an ``.onnx`` checkpoint and every other ConvNeXt variant raise NotImplementedError before the library loads."""
-    convnext = _convnext_image_model(base_model, checkpoint, dtype)
-    if not convnext and base_model not in DEPTHS:
-        raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
-    if crop > resize:
-        raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
-    dev = 0
-    if device is not None:
-        s = str(device)
-        if s == 'cpu':
-            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
-        dev = int(s.split(':')[1]) if ':' in s else 0
-    if checkpoint is not None:
-        import torch
-        ckpt = torch.load(checkpoint, map_location='cpu')
-        sd = (remap_timm_keys if convnext else remap_torchvision_keys)(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
-    else:
-        sd = make_state_dict(seed=seed, num_class=num_class, base_model=base_model)
-    eng = TsmEngine(num_class=num_class, num_segments=1, height=crop, width=crop, is_shift=False, max_clips=max_frames,
-                    device=dev, state_dict=sd, dtype=dtype, base_model=base_model, consensus_type='avg',
-                    convnext_depths=CONVNEXT_DEPTHS if convnext else None)
-    eng.image_resize, eng.image_crop = int(resize), int(crop)
-    return eng
+    return _create_frame_model(num_class, base_model, checkpoint, max_frames, dtype, resize, crop, seed, device)
 
 
 def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str] = None, max_frames: int = 32, dtype: str = 'f32',
@@ -878,26 +856,30 @@ def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str]
     ``tsm_preprocess`` (the reference resizes to 224 without a crop; an engine has one geometry -- DESIGN 4.17).
     ``base_model='convnext_base'`` (timm keys, ``weights.remap_timm_keys``): ``forward_features`` is [n, 1024], the head
     LayerNorm's output -- what timm's ``num_classes=0`` model returns; the stand-in classifier is ``head.fc``."""
-    convnext = _convnext_image_model(base_model, checkpoint, dtype)
+    return _create_frame_model(None, base_model, checkpoint, max_frames, dtype, resize, crop, seed, device)
+
+
+def _create_frame_model(num_class: Optional[int], base_model: str, checkpoint, max_frames: int, dtype: str, resize: int, crop: int,
+                        seed: int, device) -> TsmEngine:
+    """The body of ``create_image_model`` and ``create_feature_model`` (``num_class=None``: one class, or the checkpoint's own,
+    and a zero classifier where the checkpoint has none).  Every refusal -- another ConvNeXt variant, a bf16 format or an ``.onnx``
+    file with ``convnext_base`` -- comes before a checkpoint is read or the library loads."""
+    convnext = is_convnext(base_model)
     if not convnext and base_model not in DEPTHS:
         raise NotImplementedError(f'{base_model}: the engine implements {", ".join(sorted(DEPTHS))}')
+    _check_engine_args(base_model, num_segments=1, is_shift=False, dtype=dtype, height=crop, width=crop)
+    if convnext and _is_onnx(checkpoint):
+        raise NotImplementedError(f'{base_model} with an .onnx checkpoint: the importer reads the TSM-ResNet export only')
     if crop > resize:
         raise ValueError(f'crop {crop} is larger than resize {resize}: the shorter side of a resized frame is {resize}')
-    dev = 0
-    if device is not None:
-        s = str(device)
-        if s == 'cpu':
-            raise RuntimeError('TsmEngine has no CPU path; pass a CUDA/HIP device')
-        dev = int(s.split(':')[1]) if ':' in s else 0
-    num_class = 1
+    dev = _device_index(device)
+    features, num_class = num_class is None, 1 if num_class is None else num_class
     if checkpoint is not None:
-        import torch
-        ckpt = torch.load(checkpoint, map_location='cpu')
-        sd = (remap_timm_keys if convnext else remap_torchvision_keys)(ckpt['state_dict'] if 'state_dict' in ckpt else ckpt)
+        sd = (remap_timm_keys if convnext else remap_torchvision_keys)(_load_state_dict(checkpoint))
         fc = 'head.fc' if convnext else 'fc'
-        if fc + '.weight' in sd:
+        if features and fc + '.weight' in sd:
             num_class = int(sd[fc + '.weight'].shape[0])
-        else:
+        elif features:
             sd[fc + '.weight'] = np.zeros((1, feature_width(base_model)), dtype=np.float32)
             sd[fc + '.bias'] = np.zeros((1,), dtype=np.float32)
     else:
@@ -907,17 +889,6 @@ def create_feature_model(base_model: str = 'resnet18', checkpoint: Optional[str]
                     convnext_depths=CONVNEXT_DEPTHS if convnext else None)
     eng.image_resize, eng.image_crop = int(resize), int(crop)
     return eng
-
-
-def _convnext_image_model(base_model: str, checkpoint, dtype: str) -> bool:
-    """Whether an image / feature model is the ConvNeXt one; its refusals (another variant, a bf16 format, an ``.onnx`` file)
-    raise NotImplementedError here, before a checkpoint is read or the library loads."""
-    if not is_convnext(base_model):
-        return False
-    _check_convnext(None, 1, False, dtype)
-    if checkpoint is not None and str(checkpoint).endswith('.onnx'):
-        raise NotImplementedError(f'{base_model} with an .onnx checkpoint: the importer reads the TSM-ResNet export only')
-    return True
 
 
 # ---- launch trace (tests): which kernels did the calls inside the block launch? ----------------------------
